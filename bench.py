@@ -79,7 +79,16 @@ def parse():
     ap.add_argument('--dense_adam', action='store_true', help='config 5 A/B: the dense Adam pass over all 770 M parameters every step instead '
                     'of the row-lazy form (optim.LazyRows: same arithmetic, bit-identical tables, rows updated when they are used)')
     ap.add_argument('--traffic_json', default=None, help='optional JSON with PMC-derived HBM bytes per launch')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the LAST timed step computed -- the loss, and every parameter and its '
+                         'gradient as the step left them -- to DIR/<name>.npy (float32 / float64, at most 64 MB in all: larger '
+                         'tensors as a fixed seeded sample of their elements; row-lazy tables brought up to date first), so that two '
+                         'builds can be compared output for output. '
+                         'The inputs and the step are the same in every run: the files of two runs are bit-identical '
+                         '(B4C_DETERMINISTIC=0, the float-atomic reductions, gives up that guarantee)')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if a.config == 'c4':
         a.vocab, a.d_model, a.layers, a.heads, a.action_dim = 100000, 256, 6, 4, 64
     a.sampled = 0
@@ -356,6 +365,50 @@ class Training:
         return loss
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6      # (64 MB: below 64 MiB too)
+
+
+def dump_outputs(out_dir, model, loss, opt=None, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the loss of the last timed step (loss.npy, float64) and every parameter and gradient as that step left
+    them (param.<name>.npy, grad.<name>.npy, float32, flattened).  When they do not fit the budget, every tensor keeps at
+    most `cap` elements, `cap` the largest that fits: a larger tensor is written as the elements at `cap` positions drawn
+    without replacement (sorted) by a generator seeded from its name, so the same arguments select the same elements in
+    every run and every build.  Tables whose Adam update is row-lazy (config 5) are brought up to date first (`opt`), as
+    before any read of a whole table.  Returns {file name: number of elements written}."""
+    import zlib
+    if opt is not None:
+        opt.sync_rows()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [('loss', loss.detach().reshape(()), np.float64)]
+    for n, p in model.named_parameters():
+        arrays.append(('param.' + n, p.detach().reshape(-1), np.float32))
+        if p.grad is not None:
+            arrays.append(('grad.' + n, p.grad.detach().reshape(-1), np.float32))
+    sizes = [t.numel() * np.dtype(dt).itemsize for _, t, dt in arrays]
+    room = budget - 128 * len(arrays)          # (npy headers)
+    cap = None
+    if sum(sizes) > room:
+        # largest element count per tensor that fits: sum(min(numel, cap)) * 4 <= room
+        lo, hi = 0, max(t.numel() for _, t, _ in arrays)
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if sum(min(t.numel(), mid) * np.dtype(dt).itemsize for _, t, dt in arrays) <= room:
+                lo = mid
+            else:
+                hi = mid - 1
+        cap = lo
+    written = {}
+    for name, t, dt in arrays:
+        if cap is not None and t.numel() > cap:
+            pos = np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), cap, replace=False)
+            pos.sort()
+            t = t.index_select(0, torch.from_numpy(pos).to(t.device))
+        a = t.to(torch.float64 if dt == np.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name] = int(a.size)
+    return written
+
+
 def visible_gpus():
     """Number of GPUs this process may use, WITHOUT bringing up the HIP / HSA runtime (the launcher must stay a process that has
     never touched the GPU): the KFD topology nodes that have SIMDs (CPUs are nodes too, with simd_count 0), narrowed by the
@@ -458,6 +511,9 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dist.all_reduce(rr, op=dist.ReduceOp.SUM)
     dt, items = float(tt[0]), float(rr[0])
+    if a.dump_outputs and rank == 0:
+        # before the scoring leg and the every-position steps below (the latter train on and move the parameters)
+        dump_outputs(a.dump_outputs, model, loss, tr.opt)
 
     if rank == 0:
         fams = ops.stop_recording(fams) if fams is not None else None

@@ -372,7 +372,20 @@ __global__ void __launch_bounds__(256) embed_bwd_runs_kernel(EmbedArgs a, EmbedO
         if (col >= fd) continue;
         const float *t = part + (b * 2 + 1) * (int64_t)fd + col;
         float s0 = t[0], s1 = t[1];
-        for (int64_t w = b + 1; w <= e; ++w) {               // (independent loads: the order of the adds is what is fixed)
+        // (independent loads: the order of the adds is what is fixed) -- 16 shares in flight, then added in range order
+        int64_t w = b + 1;
+        for (; w + 16 <= e + 1; w += 16) {
+            float x0[16], x1[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const float *h = part + ((w + u) * 2) * (int64_t)fd + col;
+                x0[u] = h[0];
+                x1[u] = h[1];
+            }
+#pragma unroll
+            for (int u = 0; u < 16; ++u) { s0 += x0[u]; s1 += x1[u]; }
+        }
+        for (; w <= e; ++w) {
             const float *h = part + (w * 2) * (int64_t)fd + col;
             s0 += h[0];
             s1 += h[1];

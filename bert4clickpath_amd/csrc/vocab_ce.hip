@@ -994,7 +994,30 @@ struct VceDwArgs {
     int64_t R;
     int V, tsplit;
     int vt0, nvt;        // the vocabulary tiles [vt0, vt0 + nvt) this launch sweeps
+    float *part;         // NULL, or [tsplit - 1][KD + 1][V]: split 0 adds into dW / db, every later split stores its sums here
+                         // (vce_dw_part_reduce_kernel adds them in split order once the sweep is done)
 };
+
+// one (row, vocabulary id) result of a dW sweep unit: row < KD a dW entry, row == KD the db entry
+template <int KD>
+__device__ __forceinline__ void vce_dw_put(const VceDwArgs &a, int ts, int row, int v, float *p, float val, bool direct) {
+    if (a.part && ts > 0) a.part[((int64_t)(ts - 1) * (KD + 1) + row) * a.V + v] = val;
+    else if (direct || a.part) *p += val;            // (split 0 of the partials form: the only writer of p until the reduce)
+    else atomicAdd(p, val);
+}
+
+// the partial sums of token splits 1 .. nparts, added in split order: the split sweep's result without float atomics
+template <int KD>
+__global__ void __launch_bounds__(256) vce_dw_part_reduce_kernel(const float *__restrict__ part, int nparts, int V, float *dW, int ldw,
+                                                                  float *db) {
+    const int64_t n = (int64_t)(KD + 1) * V, e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    float s = part[e];
+    for (int t = 1; t < nparts; ++t) s += part[(int64_t)t * n + e];
+    const int row = (int)(e / V), v = (int)(e - (int64_t)row * V);
+    if (row < KD) dW[(int64_t)row * ldw + v] += s;
+    else if (db) db[v] += s;
+}
 
 template <int KD, int TH>
 __global__ void __launch_bounds__(256 * TH, 2) vce_dw_kernel(VceDwArgs a) {
@@ -1143,29 +1166,19 @@ __global__ void __launch_bounds__(256 * TH, 2) vce_dw_kernel(VceDwArgs a) {
                 for (int t = 0; t < 16; ++t) {
                     const int d = dt * 32 + vce_rowmap(t, hf);
                     const float val = dW[dt][t] + sD[d * 32 + r];
-                    float *p = a.dW + (int64_t)d * a.ldw + v;
-                    if (direct) *p += val;
-                    else atomicAdd(p, val);
+                    vce_dw_put<KD>(a, ts, d, v, a.dW + (int64_t)d * a.ldw + v, val, direct);
                 }
-            if (hf == 0 && a.db) {
-                const float val = dbv + sD[KD * 32 + r];
-                if (direct) a.db[v] += val;
-                else atomicAdd(a.db + v, val);
-            }
+            if (hf == 0 && a.db) vce_dw_put<KD>(a, ts, KD, v, a.db + v, dbv + sD[KD * 32 + r], direct);
         }
     } else if (v < a.V) {
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
-                float *p = a.dW + (int64_t)(dt * 32 + vce_rowmap(t, hf)) * a.ldw + v;
-                if (direct) *p += dW[dt][t];
-                else atomicAdd(p, dW[dt][t]);
+                const int d = dt * 32 + vce_rowmap(t, hf);
+                vce_dw_put<KD>(a, ts, d, v, a.dW + (int64_t)d * a.ldw + v, dW[dt][t], direct);
             }
-        if (hf == 0 && a.db) {
-            if (direct) a.db[v] += dbv;
-            else atomicAdd(a.db + v, dbv);
-        }
+        if (hf == 0 && a.db) vce_dw_put<KD>(a, ts, KD, v, a.db + v, dbv, direct);
     }
     if (TH == 1) __syncthreads();        // the next unit's tiles land in the images this one read
     unit += gridDim.x;
@@ -1234,30 +1247,129 @@ __global__ void __launch_bounds__(256) vce_label_add_kernel(float *__restrict__ 
     }
 }
 
-// K5, deterministic form: the rows are sorted by label (stable: b4c_sort_ids), ONE wave sums each run of equal labels in row
-// order and is the only writer of that label's row of the scratch -- no float atomics, the same bits every time.
+// K5, deterministic form: the rows are sorted by label (stable: b4c_sort_ids) and summed in that order in chunks of
+// VCE_LCHUNK sorted rows, one wave per chunk.  A run of equal labels inside one chunk goes straight to its row of the scratch;
+// a run that crosses chunk boundaries leaves one partial per chunk (slot 0: the run began in an earlier chunk, slot 1: it
+// began here), and vce_label_join_kernel adds them in chunk order.  No float atomics: the same bits every time, and a
+// frequent label's long run is shared among many waves.
+#define VCE_LCHUNK 32
 __global__ void __launch_bounds__(256) vce_label_keys_kernel(const int32_t *__restrict__ labels, int64_t R, int V, int64_t *__restrict__ keys) {
     const int64_t i = blockIdx.x * 256ll + threadIdx.x;
     if (i < R) { const int y = labels[i]; keys[i] = (y >= 0 && y < V) ? y : V; }          // V: ignored rows sort to the end
 }
 template <int KD>
-__global__ void __launch_bounds__(256) vce_label_sorted_kernel(VceDwArgs a, const int64_t *__restrict__ keys, const int32_t *__restrict__ order,
-                                                               float *__restrict__ tmp) {
+__global__ void __launch_bounds__(256) vce_label_chunk_kernel(VceDwArgs a, const int64_t *__restrict__ keys, const int32_t *__restrict__ order,
+                                                              float *__restrict__ tmp, float *__restrict__ slot) {
+    constexpr int C = VCE_LCHUNK, NE = KD / 64;
     const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= a.R) return;
-    const int64_t y = keys[order[i]];
-    if (y >= a.V || (i > 0 && keys[order[i - 1]] == y)) return;           // not the first row of a run of a valid label
-    float acc[KD / 64], sb = 0.f;
+    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t p0 = c * C;
+    if (p0 >= a.R) return;
+    const int n = (int)(a.R - p0 < C ? a.R - p0 : C);
+    const int64_t p1 = p0 + n;
+    const bool from_before = p0 > 0 && keys[order[p0 - 1]] == keys[order[p0]];
+    const bool to_after = p1 < a.R && keys[order[p1]] == keys[order[p1 - 1]];
+    // lane u < n holds sorted row p0 + u: its row index, label and scale -- one round trip for the whole chunk
+    int64_t ol = 0, kl = a.V;
+    float ydl = 0.f;
+    if (lane < n) {
+        ol = order[p0 + lane];
+        kl = keys[ol];
+        if (kl < a.V) ydl = a.rowscal[ol * 8 + 4];
+    }
+    // every row's h values in flight at once (rows past the chunk or of ignored labels: 0)
+    float hv[C][NE];
 #pragma unroll
-    for (int e = 0; e < KD / 64; ++e) acc[e] = 0.f;
-    for (int64_t j = i; j < a.R; ++j) {
-        const int64_t row = order[j];
-        if (keys[row] != y) break;
-        const float yd = a.rowscal[row * 8 + 4];
+    for (int u = 0; u < C; ++u) {
+        const int64_t o = __shfl(ol, u), k = __shfl(kl, u);
 #pragma unroll
-        for (int e = 0; e < KD / 64; ++e) acc[e] += -yd * (float)a.h[row * a.ld_h + lane + 64 * e];
-        sb += -yd;
+        for (int e = 0; e < NE; ++e) hv[u][e] = (u < n && k < a.V) ? (float)a.h[o * a.ld_h + lane + 64 * e] : 0.f;
+    }
+    float acc[NE], sb = 0.f;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) acc[e] = 0.f;
+    int64_t y = __shfl(kl, 0), s0 = p0;
+    auto emit = [&](int64_t pe) {          // the segment [s0, pe) of label y
+        if (y >= a.V) return;
+        float *dst;
+        if (s0 == p0 && from_before) dst = slot + (c * 2 + 0) * (KD + 1);
+        else if (pe == p1 && to_after) dst = slot + (c * 2 + 1) * (KD + 1);
+        else {
+#pragma unroll
+            for (int e = 0; e < NE; ++e) tmp[y * KD + lane + 64 * e] = acc[e];
+            if (lane == 0 && a.db) a.db[y] += sb;
+            return;
+        }
+#pragma unroll
+        for (int e = 0; e < NE; ++e) dst[lane + 64 * e] = acc[e];
+        if (lane == 0) dst[KD] = sb;
+    };
+#pragma unroll
+    for (int u = 0; u < C; ++u) {
+        const int64_t k = __shfl(kl, u);
+        const float yd = __shfl(ydl, u);
+        if (u < n) {          // (wave-uniform)
+            if (k != y) {
+                emit(p0 + u);
+                y = k; s0 = p0 + u; sb = 0.f;
+#pragma unroll
+                for (int e = 0; e < NE; ++e) acc[e] = 0.f;
+            }
+            if (y < a.V) {
+#pragma unroll
+                for (int e = 0; e < NE; ++e) acc[e] += -yd * hv[u][e];
+                sb += -yd;
+            }
+        }
+    }
+    emit(p1);
+}
+// the runs that cross chunk boundaries: the wave of the chunk where such a run begins adds its chunk partials in chunk order
+template <int KD>
+__global__ void __launch_bounds__(256) vce_label_join_kernel(VceDwArgs a, const int64_t *__restrict__ keys, const int32_t *__restrict__ order,
+                                                             float *__restrict__ tmp, const float *__restrict__ slot) {
+    const int lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t p0 = c * VCE_LCHUNK;
+    if (p0 >= a.R) return;
+    const int64_t p1 = p0 + VCE_LCHUNK < a.R ? p0 + VCE_LCHUNK : a.R;
+    const int64_t y = keys[order[p1 - 1]];
+    if (y >= a.V || p1 >= a.R || keys[order[p1]] != y) return;                        // this chunk's last run ends here
+    if (p0 > 0 && keys[order[p0]] == y && keys[order[p0 - 1]] == y) return;           // ... or began in an earlier chunk
+    float acc[KD / 64];
+    const float *src = slot + (c * 2 + 1) * (KD + 1);
+#pragma unroll
+    for (int e = 0; e < KD / 64; ++e) acc[e] = src[lane + 64 * e];
+    float sb = src[KD];
+    // the last chunk the run reaches into ("chunk w starts with y" is monotone in w: sorted): a binary search
+    const int64_t nch = (a.R + VCE_LCHUNK - 1) / VCE_LCHUNK;
+    int64_t lo = c + 1, hi = nch - 1;                       // chunk c + 1 starts with y
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (keys[order[mid * VCE_LCHUNK]] == y) lo = mid; else hi = mid - 1;
+    }
+    int64_t c2 = c + 1;
+    for (; c2 + 8 <= lo + 1; c2 += 8) {                     // independent loads, added in chunk order
+        float x[8][KD / 64 + 1];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float *q = slot + ((c2 + u) * 2 + 0) * (KD + 1);
+#pragma unroll
+            for (int e = 0; e < KD / 64; ++e) x[u][e] = q[lane + 64 * e];
+            x[u][KD / 64] = q[KD];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+#pragma unroll
+            for (int e = 0; e < KD / 64; ++e) acc[e] += x[u][e];
+            sb += x[u][KD / 64];
+        }
+    }
+    for (; c2 <= lo; ++c2) {
+        src = slot + (c2 * 2 + 0) * (KD + 1);
+#pragma unroll
+        for (int e = 0; e < KD / 64; ++e) acc[e] += src[lane + 64 * e];
+        sb += src[KD];
     }
 #pragma unroll
     for (int e = 0; e < KD / 64; ++e) tmp[y * KD + lane + 64 * e] = acc[e];
@@ -1321,8 +1433,21 @@ extern "C" int64_t b4c_vocab_ce_workspace_bytes(int64_t R, int V, int K) {
     // 8 = the largest vocabulary split; + the lse-first form's own statistics (8 parts x R x 4, and 2 per row merged)
     const int64_t fwd = (int64_t)8 * R * (4 + 2 * (int64_t)K + 4) * 4 + (int64_t)R * (8 * 4 + 2) * 4 + 64;
     // vocabulary-major scratch of the label term; deterministic form: + sort keys, order and the sort's own workspace
-    const int64_t dw = (int64_t)V * K * 4 + 64 + R * 12 + b4c_sort_ids_workspace_bytes(R, V + 1);
+    const int64_t dw = (int64_t)V * K * 4 + 64 + R * 12 + b4c_sort_ids_workspace_bytes(R, V + 1) + 64 + ((R + 31) / 32) * 2 * (K + 1) * 4;
     return fwd > dw ? fwd : dw;
+}
+
+// b4c_vocab_ce_dw's workspace: the above, and in the deterministic form room for the [split - 1][K + 1][V] partial sums of
+// the token split the sweep will pick (at most 256 MB of them, or what the above already holds: a smaller workspace only
+// costs the sweep splits, vce_dw_sweep_launch)
+extern "C" int64_t b4c_vocab_ce_dw_workspace_bytes(int64_t R, int V, int K, int deterministic) {
+    const int64_t base = b4c_vocab_ce_workspace_bytes(R, V, K);
+    if (!deterministic || base == 0) return base;
+    const int64_t cap = base > ((int64_t)1 << 28) ? base : ((int64_t)1 << 28);
+    int ts = vce_pick_split((V + 127) / 128, ceil_div64(R, 128), 0.025);
+    while (ts > 1 && (int64_t)(ts - 1) * (K + 1) * V * 4 > cap) --ts;
+    const int64_t parts = (int64_t)(ts - 1) * (K + 1) * V * 4;
+    return base > parts ? base : parts;
 }
 
 // The "lse first" form (round 4): lse sweep -> per-row {lse2, max x} -> ONE exact sweep at one wave per SIMD -> combine.
@@ -1478,7 +1603,8 @@ extern "C" int b4c_vocab_lse(const void *h, int ld_h, const void *wt, int ld_w, 
 }
 
 template <int KD>
-static void vce_dw_sweep_launch(VceDwArgs a, int vt0, int nvt, int background_wgs, bool deterministic, hipStream_t st) {
+static void vce_dw_sweep_launch(VceDwArgs a, int vt0, int nvt, int background_wgs, bool deterministic, hipStream_t st,
+                                float *part = nullptr, int64_t part_bytes = 0) {
     const int64_t ntt = ceil_div64(a.R, 128);
     const size_t lds = vce_dw_lds<KD>();
     static thread_local bool done = false;
@@ -1500,8 +1626,16 @@ static void vce_dw_sweep_launch(VceDwArgs a, int vt0, int nvt, int background_wg
         const int64_t units = (int64_t)nvt * ts, rounds = ceil_div64(units, background_wgs);
         vce_dw_kernel<KD, 1><<<(unsigned)ceil_div64(units, rounds), 256, lds, st>>>(a);
     } else {
-        a.tsplit = deterministic ? 1 : vce_pick_split(nvt, ntt, 0.025);
+        int ts = vce_pick_split(nvt, ntt, 0.025);
+        if (deterministic) {
+            // fixed order: the splits' partial sums through the caller's scratch when it holds them, else one split
+            while (ts > 1 && (!part || (int64_t)(ts - 1) * (KD + 1) * a.V * 4 > part_bytes)) --ts;
+            a.part = ts > 1 ? part : nullptr;
+        }
+        a.tsplit = ts;
         vce_dw_kernel<KD, 2><<<(unsigned)(nvt * a.tsplit), 512, lds, st>>>(a);
+        if (a.part)
+            vce_dw_part_reduce_kernel<KD><<<(unsigned)ceil_div64((int64_t)(KD + 1) * a.V, 256), 256, 0, st>>>(a.part, ts - 1, a.V, a.dW, a.ldw, a.db);
     }
 }
 template <int KD>
@@ -1512,10 +1646,13 @@ static int vce_dw_label_launch(VceDwArgs a, const int32_t *labels, float *tmp, i
         int64_t *keys = (int64_t *)p;          p += (size_t)a.R * 8;
         int32_t *order = (int32_t *)p;         p += (size_t)a.R * 4;
         const int64_t sort_bytes = b4c_sort_ids_workspace_bytes(a.R, a.V + 1);
-        B4C_REQUIRE(p + sort_bytes <= (char *)tmp + tmp_bytes, "vocab_ce_dw_labels: workspace too small for the deterministic form");
+        const int64_t nch = ceil_div64(a.R, VCE_LCHUNK);
+        float *slot = (float *)(((uintptr_t)(p + sort_bytes) + 63) & ~(uintptr_t)63);
+        B4C_REQUIRE((char *)(slot + nch * 2 * (KD + 1)) <= (char *)tmp + tmp_bytes, "vocab_ce_dw_labels: workspace too small for the deterministic form");
         vce_label_keys_kernel<<<(unsigned)ceil_div64(a.R, 256), 256, 0, st>>>(labels, a.R, a.V, keys);
         if (int rc = b4c_sort_ids(keys, a.R, a.V + 1, order, p, sort_bytes, st)) return rc;
-        vce_label_sorted_kernel<KD><<<(unsigned)ceil_div64(a.R, 4), 256, 0, st>>>(a, keys, order, tmp);
+        vce_label_chunk_kernel<KD><<<(unsigned)ceil_div64(nch, 4), 256, 0, st>>>(a, keys, order, tmp, slot);
+        vce_label_join_kernel<KD><<<(unsigned)ceil_div64(nch, 4), 256, 0, st>>>(a, keys, order, tmp, slot);
     } else {
         vce_label_kernel<KD><<<(unsigned)ceil_div64(a.R, VCE_LABEL_ROWS), 256, 0, st>>>(a, labels, tmp);
     }
@@ -1551,8 +1688,9 @@ extern "C" int b4c_vocab_ce_dw(const void *h, int ld_h, const void *wt, int ld_w
     const int nvt = (V + 127) / 128;
     const bool det = deterministic != 0;
     int rc;
-    if (K == 128) { vce_dw_sweep_launch<128>(a, 0, nvt, 0, det, (hipStream_t)stream); rc = vce_dw_label_launch<128>(a, labels, (float *)workspace, workspace_bytes, det, (hipStream_t)stream); }
-    else { vce_dw_sweep_launch<64>(a, 0, nvt, 0, det, (hipStream_t)stream); rc = vce_dw_label_launch<64>(a, labels, (float *)workspace, workspace_bytes, det, (hipStream_t)stream); }
+    // (the sweep's split partials and the label term's scratch share the workspace: the label term clears it after the sweep)
+    if (K == 128) { vce_dw_sweep_launch<128>(a, 0, nvt, 0, det, (hipStream_t)stream, (float *)workspace, workspace_bytes); rc = vce_dw_label_launch<128>(a, labels, (float *)workspace, workspace_bytes, det, (hipStream_t)stream); }
+    else { vce_dw_sweep_launch<64>(a, 0, nvt, 0, det, (hipStream_t)stream, (float *)workspace, workspace_bytes); rc = vce_dw_label_launch<64>(a, labels, (float *)workspace, workspace_bytes, det, (hipStream_t)stream); }
     if (rc) return rc;
     return b4c_check_launch("vocab_ce_dw");
 }

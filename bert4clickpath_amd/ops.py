@@ -287,16 +287,18 @@ def _sort_order(ids, n_rows):
 
 sorted_embed_bwd = True     # sort the tokens of every feature by id (one radix sort per call) and sum runs in registers
 
-# ops.deterministic (B4C_DETERMINISTIC=1): ONE switch for a bit-reproducible training step -- every reduction that otherwise
-# finishes through float atomics (whose arrival order, and with it the last bit of the sum, changes from run to run) takes a
-# fixed-order form instead:
-#   the vocabulary projection's dW / db      one workgroup per vocabulary tile walks every token; label term through a stable sort
+# ops.deterministic (on by default; B4C_DETERMINISTIC=0 switches it off): ONE switch for a bit-reproducible training step --
+# every reduction that otherwise finishes through float atomics (whose arrival order, and with it the last bit of the sum,
+# changes from run to run, and training carries such differences on into every later step) takes a fixed-order form instead:
+#   the vocabulary projection's dW / db      the token splits of the sweep store partial sums in the workspace, added in split
+#                                            order (background pieces: one workgroup per vocabulary tile walks every token);
+#                                            label term through a stable sort
 #   the embedding tables' gradient rows      runs of one id that cross the kernel's 64-entry ranges are summed in range order
 #                                            (b4c_embed_concat_pe_bwd_sorted_ws); the unsorted atomic kernel is never taken
 #   LayerNorm dgamma / dbeta                 per-workgroup sums in a fixed order, added block by block (b4c_add_dropout_layernorm_bwd_ws)
 # (the dense weight gradients already are: ops.tn_deterministic).  Not covered: the sampled-softmax head's row scatter (config 5).
 # Two identical runs of bench.py's step then give torch.equal arenas (tests/test_gpu_deterministic.py); cost: DESIGN.md.
-deterministic = os.environ.get('B4C_DETERMINISTIC', '0') == '1'
+deterministic = os.environ.get('B4C_DETERMINISTIC', '1') == '1'
 
 
 def embed_concat_pe_bwd(ids_list, tables, dout, scale, rate, seed, into=None, order=None):
@@ -958,10 +960,12 @@ def vocab_ce_dw(h, wt, bias, labels_i32, rowscal, V, dW, db):
     R, K = h.shape
     if R == 0:
         return
-    ws = _vce_workspace(h, R, V, K)
+    det = int(deterministic_vocab_dw or deterministic)
+    # (the deterministic form's split partial sums: a larger workspace than the forward's)
+    ws = _workspace('vocab_ce', h.device, L.lib().b4c_vocab_ce_dw_workspace_bytes(R, V, K, det))
     with _record('vocab_ce_dw', R * K * 2 + V * K * 2 + V * K * 4, 4 * R * V * K):
         L.check(L.lib().b4c_vocab_ce_dw(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), _p(labels_i32), _p(rowscal),
-                                        _p(dW), dW.stride(0), _p(db), ws.data_ptr(), ws.numel(), R, V, K, int(deterministic_vocab_dw or deterministic), _st()),
+                                        _p(dW), dW.stride(0), _p(db), ws.data_ptr(), ws.numel(), R, V, K, det, _st()),
                 'vocab_ce_dw')
 
 
@@ -1674,10 +1678,8 @@ def _background_dw_for(actx):
         return overlap_vocab_dw
     return not getattr(actx, 'fused_blocks', False)
 background_workgroups = int(os.environ.get('B4C_VCE_DW_BG', '0'))      # 0: one per CU of the device
-# deterministic_vocab_dw: the projection's dW / db are summed in a fixed order (no float atomics: one workgroup per
-# vocabulary tile walks every token, the label term goes through a stable sort of the rows by label) -- two identical steps
-# give a bit-identical projection gradient (LayerNorm dgamma / dbeta and a few embedding rows still meet through float atomics).
-# Default off: the split sweep fills the CUs better (B4C_DETERMINISTIC_DW=1 switches it on).
+# deterministic_vocab_dw: the projection's dW / db alone in their fixed-order form (see `deterministic`, which includes it and
+# is on by default) -- for A/B runs with B4C_DETERMINISTIC=0 (B4C_DETERMINISTIC_DW=1 switches it on).
 deterministic_vocab_dw = os.environ.get('B4C_DETERMINISTIC_DW', '0') == '1'
 
 

@@ -316,10 +316,14 @@ int b4c_vocab_ce_fwd(const void *h, int ld_h, const void *wt, int ld_w, const fl
 int b4c_vocab_ce_dw(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *labels,
                     const float *rowscal, float *dW, int ldw, float *db, void *workspace, int64_t workspace_bytes,
                     int64_t R, int V, int K, int deterministic, void *stream);
-/* (ABI version 8) `deterministic` != 0 (b4c_vocab_ce_dw and its pieces): dW / db are summed in a fixed order -- one workgroup
- * per vocabulary tile walks every token (plain adds instead of float atomics over token splits), and the label term goes
- * through a stable sort of the rows by label with one wave summing each run: the same bits on every run of the same inputs.
- * Costs the sweep its token split (fewer workgroups than CUs' worth of rounds); workspace as b4c_vocab_ce_workspace_bytes. */
+/* (ABI version 8) `deterministic` != 0 (b4c_vocab_ce_dw and its pieces): dW / db are summed in a fixed order, without float
+ * atomics -- the same bits on every run of the same inputs.  b4c_vocab_ce_dw keeps the sweep's token split: split 0 adds into
+ * dW / db, the later splits store partial sums in the workspace and one pass adds them in split order (a workspace of
+ * b4c_vocab_ce_dw_workspace_bytes(R, V, K, 1) holds them; a smaller one, at least b4c_vocab_ce_workspace_bytes, costs the
+ * sweep splits); b4c_vocab_ce_dw_sweep (no workspace) has one workgroup per vocabulary tile walk every token.  The label
+ * term goes through a stable sort of the rows by label, summed in chunks of 32 sorted rows whose shares of a run are then
+ * added in chunk order. */
+int64_t b4c_vocab_ce_dw_workspace_bytes(int64_t R, int V, int K, int deterministic);
 /* (ABI version 5) b4c_vocab_ce_dw in pieces, so that the sweep can run BESIDE the HBM-bound encoder backward:
  * b4c_vocab_ce_dw_sweep adds the dlogit part of dW / db for the 128-id vocabulary tiles [tile_begin, tile_end) only
  * (tiles own disjoint columns of dW: any partition of [0, ceil(V / 128)) over any number of calls gives the full sweep);

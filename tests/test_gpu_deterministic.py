@@ -1,7 +1,7 @@
-"""ops.deterministic: ONE switch for a bit-reproducible training step.  By default three reductions of the step finish through
-float atomics (the vocabulary projection's dW / db, the embedding rows of runs that cross the kernel's 64-entry ranges, the
-LayerNorm dgamma / dbeta), so two runs of the same step differ in last bits; with the switch every one of them takes a
-fixed-order form.  Two fresh runs of the same three optimizer steps -- bf16, padding-free layout, dropout, arena optimizer,
+"""ops.deterministic (on by default): ONE switch for a bit-reproducible training step.  Switched off, three reductions of
+the step finish through float atomics (the vocabulary projection's dW / db, the embedding rows of runs that cross the kernel's
+64-entry ranges, the LayerNorm dgamma / dbeta), so two runs of the same step differ in last bits; with the switch every one
+of them takes a fixed-order form.  Two fresh runs of the same three optimizer steps -- bf16, padding-free layout, dropout, arena optimizer,
 the projection's dW as a background sweep: bench.py's step -- must leave bit-identical arenas (parameters, both Adam moments)."""
 import numpy as np
 import pytest
