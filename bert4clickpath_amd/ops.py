@@ -680,6 +680,15 @@ def _ready(*params):
             c.grad_ready_cb(p)
 
 
+def _tied_table_steps_whole(table):
+    """called where a tied projection (TiedPackedLinear) adds its dW into rows off .. off + V of its table, read in this step
+    or not: under a row-lazy optimizer (optim.LazyRows) the whole table then takes the next step, as the dense update would
+    (the gather sites' row notes cover the rows the embedding read, not these)"""
+    lz = getattr(table, '_b4c_lazy', None)
+    if lz is not None:
+        lz.all_rows = True
+
+
 def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None):
     """Attention of a few query rows per sequence against all of its keys (b4c_attn_mq_fwd).
     q [R, H*dh]; kv [T, 2*H*dh] (k | v); cu [B+1] token offsets; moff [B+1] query-row offsets -> (o [R, H*dh], lse [R, H])."""
@@ -1850,6 +1859,7 @@ class VocabCEFn(torch.autograd.Function):
             vocab_ce_dw(h, wt, b, labels_i32, rowscal, ctx.V, dWt, db)
             dtab = kernel.grad if inplace else torch.zeros(kernel.shape, dtype=torch.float32, device=h.device)
             transpose_add_(dtab[off:off + ctx.V], dWt)
+            _tied_table_steps_whole(kernel)
             if inplace:
                 _ready(bias)        # the table is announced by the embedding backward, which runs last
                 return dh, None, None, None, None, None, None, None, None
@@ -2203,6 +2213,7 @@ class TiedLogitsFn(torch.autograd.Function):
         dWt, db = gemm_tn(h, g, pack.K, pack.N)                 # [K, V] fp32, [V]
         dh = gemm_nt(g, wc, h.shape[1])
         off = pack.tied_offset
+        _tied_table_steps_whole(table)
         if _inplace_ok(table, bias):
             transpose_add_(table.grad[off:off + pack.N], dWt)
             bias.grad += db

@@ -165,15 +165,23 @@ class Adam:
     def lr_hist(self, t):
         """device fp32 table of the lr_t of steps 1 .. t (what the dense kernel was / is handed at each of them): the replay of
         a missed step needs that step's own value.  Entries of past steps never change; a change of `self.lr` (ReduceLROnPlateau)
-        shows from the step it first applies to."""
+        shows from the step it first applies to.  The table keeps its capacity: a step writes its own entry only (no host sync);
+        it is reallocated, twice as large, when it is full, and rewritten in place when past entries change (reset_rows)."""
         while len(self._lr_host) <= t:
             self._lr_host.append(self._lr_t(len(self._lr_host)))
-        if self._lr_dev is None or self._lr_valid <= t:
-            n = max(1024, 2 * (t + 1))
-            host = torch.zeros(n, dtype=torch.float32)
-            host[:len(self._lr_host)] = torch.tensor(self._lr_host, dtype=torch.float64).to(torch.float32)
-            self._lr_dev = host.to(self.arena.flat.device)
-            self._lr_valid = len(self._lr_host)
+        n = len(self._lr_host)
+        if self._lr_dev is None or self._lr_dev.numel() < n:
+            cap = max(1024, 2 * n)
+            self._lr_dev = ops.zeros(cap, dtype=torch.float32, device=self.arena.flat.device)
+            self._lr_valid = 0
+        if self._lr_valid < n:
+            lo = self._lr_valid
+            if n - lo == 1:       # one entry per step: a fill (the value rounded to fp32 as below), stream-ordered behind the readers
+                self._lr_dev[lo:n].fill_(self._lr_host[lo])
+            else:
+                host = torch.tensor(self._lr_host[lo:n], dtype=torch.float64).to(torch.float32)
+                self._lr_dev[lo:n].copy_(host)
+            self._lr_valid = n
         return self._lr_dev
 
     def zero_grad(self):
@@ -183,8 +191,10 @@ class Adam:
                 ops.zero_(self.arena.grad[lo:hi])
         else:
             self.arena.zero_grad()
-        for lz in self.lazy:
-            lz.touched, lz.all_rows = [], False
+        # the lazy tables' row notes (touched / all_rows) stay: the forward pass may have run already
+        # (`loss = model(x); opt.zero_grad(); loss.backward(); opt.step()`), and its notes name the rows that will receive a
+        # gradient.  step() consumes them; a note left by a step that never ran is harmless (a row stepped with a zero
+        # gradient takes exactly the dense update)
         self._grads_clean = False
 
     def sync_rows(self):
