@@ -576,7 +576,7 @@ grouped_dw = True
 def queue_dw(c, a, g, K, N, dWs, dbs, params):
     """dW_i += a^T g (column segments), db_i += colsum(g) -- now or with the next flush_pending_dw(c).  `c`: the ArenaContext
     of the step in flight (the queue lives there: a step that fails leaves nothing behind for the next one)."""
-    ok = c is not None and grouped_dw and a.dtype == torch.bfloat16 and a.stride(0) % 8 == 0 and g.stride(0) % 8 == 0 and \
+    ok = _arena_routes(c) and grouped_dw and a.dtype == torch.bfloat16 and a.stride(0) % 8 == 0 and g.stride(0) % 8 == 0 and \
         a.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and a.shape[0] >= 4096
     if not ok:
         gemm_tn(a, g, K, N, into=(dWs, dbs))
@@ -613,8 +613,9 @@ def flush_pending_dw(c):
 
 
 # ---- per-arena host state ------------------------------------------------------------------------------------------
-# optim.FlatArena re-homes parameters and their gradients into two flat buffers; the weight-gradient kernels then add
-# straight into param.grad (autograd receives None for those inputs).  Everything the host keeps about such a training
+# optim.FlatArena re-homes parameters and their gradients into two flat buffers.  Every autograd block adds its weight
+# gradients into sinks (grad_sinks): in an arena param.grad itself (autograd receives None for those inputs), without one
+# fresh zeros that autograd receives (sink_returns).  Everything the host keeps about such a training
 # step -- who is told when a gradient is complete, and the side-stream work of the backward pass in flight -- lives in
 # the arena's ArenaContext, reachable from every parameter of the arena as `p._b4c_ctx`.  Nothing here is process
 # state: two models, with or without an arena, train side by side in one process (tests/test_gpu_context.py).
@@ -669,8 +670,26 @@ def arena_context(*params):
     return ctx
 
 
-def _inplace_ok(*params):
-    return arena_context(*params) is not None
+def grad_sinks(*params):
+    """-> (actx, sinks): where the backward kernels add each parameter's fp32 gradient.  In an arena (actx = arena_context(...))
+    sinks[i] is params[i].grad, the arena's view; otherwise a fresh zero tensor of the parameter's shape, handed to autograd by
+    sink_returns."""
+    actx = arena_context(*params)
+    if actx is not None:
+        return actx, [p.grad for p in params]
+    return None, [torch.zeros(p.shape, dtype=torch.float32, device=p.device) for p in params]
+
+
+def sink_returns(ctx, lead, actx, sinks):
+    """autograd's return values of a block: `lead` for the inputs in front of its parameters, then per parameter its sink (None in
+    an arena: the kernels have already added into .grad), then None for every input after them"""
+    out = tuple(lead) + ((None,) * len(sinks) if actx is not None else tuple(sinks))
+    return out + (None,) * (len(ctx.needs_input_grad) - len(out))
+
+
+def _arena_routes(actx):
+    # the fused backward kernels, the grouped dW queue and the background sweep run in arena mode only, as they always have
+    return actx is not None
 
 
 def _ready(*params):
@@ -1100,16 +1119,12 @@ class VocabSoftmaxFn(torch.autograd.Function):
         g = _rows_ok(g, probs.dtype)
         dlogits = softmax_rows_bwd(probs, g, ctx.V)
         _, wc, _ = pack.get(h.dtype, h.shape[1], True)
-        actx = arena_context(kernel, bias)
-        if actx is not None:
-            queue_dw(actx, h, dlogits, pack.K, pack.N, [kernel.grad], [bias.grad], (kernel, bias))
-            dW = db = None
-        else:
-            dW, db = gemm_tn(h, dlogits, pack.K, pack.N)
+        actx, sinks = grad_sinks(kernel, bias)
+        queue_dw(actx, h, dlogits, pack.K, pack.N, sinks[:1], sinks[1:], (kernel, bias))
         with _timed('vocab_proj_dx'):
             dh = gemm_nt(dlogits, wc, h.shape[1])
         flush_pending_dw(actx)
-        return dh, None, None, dW, db
+        return sink_returns(ctx, (dh, None, None), actx, sinks)
 
 
 topk_threshold = True     # threshold-selection kernel (one HBM read per row); False: per-thread sorted lists only
@@ -1238,15 +1253,6 @@ class PackedLinear:
             repack_stale(dtype, dev)
         return ent['wt'], ent['wc'], ent['bias']
 
-    def split_grads(self, dW, db):
-        """dW [K, N] / db [N] of the fused layer -> per-kernel gradients."""
-        gk, gb, off = [], [], 0
-        for n in self.Ns:
-            gk.append(dW[:, off:off + n].contiguous() if len(self.Ns) > 1 else dW)
-            gb.append(db[off:off + n].contiguous() if len(self.Ns) > 1 else db)
-            off += n
-        return gk, gb
-
 
 _desc_cache = {}
 
@@ -1352,12 +1358,10 @@ class EmbedFn(torch.autograd.Function):
         if dout is None:
             return (None,) * (6 + 2 * ctx.n)
         dout = dout.reshape(ids[0].shape[0], ids[0].shape[1], -1)
-        if _inplace_ok(*tables):
-            embed_concat_pe_bwd(ids, tables, dout.contiguous(), ctx.scale, ctx.rate, ctx.seed, into=[t.grad for t in tables])
-            _ready(*tables)
-            return (None,) * (6 + 2 * ctx.n)
-        dtabs = embed_concat_pe_bwd(ids, tables, dout.contiguous(), ctx.scale, ctx.rate, ctx.seed)
-        return (None,) * 6 + (None,) * ctx.n + tuple(dtabs)
+        actx, sinks = grad_sinks(*tables)
+        embed_concat_pe_bwd(ids, tables, dout.contiguous(), ctx.scale, ctx.rate, ctx.seed, into=sinks)
+        _ready(*tables)
+        return sink_returns(ctx, (None,) * (6 + ctx.n), actx, sinks)
 
 
 class AttnBlockFn(torch.autograd.Function):
@@ -1395,43 +1399,34 @@ class AttnBlockFn(torch.autograd.Function):
         B, S, H, dh, rate, seed = ctx.dims
         wq, bq, wk, bk, wv, bv, wo, bo, gam, bet = ctx.params
         d = H * dh
-        actx = arena_context(*ctx.params)
-        inplace = actx is not None
+        actx, sinks = grad_sinks(*ctx.params)
+        gwq, gbq, gwk, gbk, gwv, gbv, gwo, gbo, ggam, gbet = sinks
+        routes = _arena_routes(actx)
         _, wc_o, _ = pk_o.get(x.dtype, d, True)
         _, wc_qkv, _ = pk_qkv.get(x.dtype, d, True)
-        if inplace and fused_attn_out_bwd and attn_out_bwd_supported(o, z):
-            dz, d_o = attn_out_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, o, wc_o, wo.grad, bo.grad, gam.grad, bet.grad)
+        if routes and fused_attn_out_bwd and attn_out_bwd_supported(o, z):
+            dz, d_o = attn_out_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, o, wc_o, gwo, gbo, ggam, gbet)
             _ready(wo, bo)
         else:
-            dz, dy, dgamma, dbeta = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed,
-                                                              into=(gam.grad, bet.grad) if inplace else None)
-            if inplace and fused_dxdw >= 3 and dxdw_supported(o, dy, 1):
-                d_o = gemm_dxdw(o, dy, wc_o, [wo.grad], [bo.grad])
+            dz, dy, _, _ = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, into=(ggam, gbet))
+            if routes and fused_dxdw >= 3 and dxdw_supported(o, dy, 1):
+                d_o = gemm_dxdw(o, dy, wc_o, [gwo], [gbo])
                 _ready(wo, bo)
             else:
-                if inplace:
-                    queue_dw(actx, o, dy, d, d, [wo.grad], [bo.grad], (wo, bo))
-                else:
-                    dWo, dbo = gemm_tn(o, dy, d, d)
+                queue_dw(actx, o, dy, d, d, [gwo], [gbo], (wo, bo))
                 d_o = gemm_nt(dy, wc_o, d)
         with _timed('attn_bwd'):
             dqkv = attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, ctx.cu, actx)
-        if inplace and fused_dxdw and dxdw_supported(x, dqkv, 3):
+        if routes and fused_dxdw and dxdw_supported(x, dqkv, 3):
             # dX and dW | db of the fused Q | K | V projection in one pass over dqkv (csrc/gemm_dxdw.hip)
-            dx = gemm_dxdw(x, dqkv, wc_qkv, [wq.grad, wk.grad, wv.grad], [bq.grad, bk.grad, bv.grad], residual=dz)
+            dx = gemm_dxdw(x, dqkv, wc_qkv, [gwq, gwk, gwv], [gbq, gbk, gbv], residual=dz)
             _ready(wq, bq, wk, bk, wv, bv)
         else:
-            if inplace:
-                queue_dw(actx, x, dqkv, d, 3 * d, [wq.grad, wk.grad, wv.grad], [bq.grad, bk.grad, bv.grad], (wq, bq, wk, bk, wv, bv))
-            else:
-                dWqkv, dbqkv = gemm_tn(x, dqkv, d, 3 * d)
+            queue_dw(actx, x, dqkv, d, 3 * d, [gwq, gwk, gwv], [gbq, gbk, gbv], (wq, bq, wk, bk, wv, bv))
             dx = gemm_nt(dqkv, wc_qkv, d, residual=dz)
-        if inplace:
-            _ready(gam, bet)
-            flush_pending_dw(actx)      # this layer's four weight gradients (two queued by FFNBlockFn.backward) in one launch
-            return (dx,) + (None,) * 20
-        (gq, gk, gv), (gbq, gbk, gbv) = pk_qkv.split_grads(dWqkv, dbqkv)
-        return (dx, None, gq, gbq, gk, gbk, gv, gbv, dWo, dbo, dgamma, dbeta) + (None,) * 9
+        _ready(gam, bet)
+        flush_pending_dw(actx)      # this layer's four weight gradients (two queued by FFNBlockFn.backward) in one launch
+        return sink_returns(ctx, (dx, None), actx, sinks)
 
 
 def rows_add_(dst, idx, src):
@@ -1487,46 +1482,33 @@ class MQAttnBlockFn(torch.autograd.Function):
         B, max_len, H, dh, rate, seed = ctx.dims
         wq, bq, wk, bk, wv, bv, wo, bo, gam, bet = ctx.params
         d = H * dh
-        actx = arena_context(*ctx.params)
-        inplace = actx is not None
+        actx, sinks = grad_sinks(*ctx.params)
+        gwq, gbq, gwk, gbk, gwv, gbv, gwo, gbo, ggam, gbet = sinks
+        routes = _arena_routes(actx)
         _, wc_o, _ = pk_o.get(x.dtype, d, True)
         _, wc_qkv, _ = pk_qkv.get(x.dtype, d, True)
-        if inplace and fused_attn_out_bwd and attn_out_bwd_supported(o_m, z):
-            dz, d_o = attn_out_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, o_m, wc_o, wo.grad, bo.grad, gam.grad, bet.grad)
+        if routes and fused_attn_out_bwd and attn_out_bwd_supported(o_m, z):
+            dz, d_o = attn_out_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, o_m, wc_o, gwo, gbo, ggam, gbet)
             _ready(wo, bo)
         else:
-            dz, dy, dgamma, dbeta = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed,
-                                                              into=(gam.grad, bet.grad) if inplace else None)
-            if inplace:
-                queue_dw(actx, o_m, dy, d, d, [wo.grad], [bo.grad], (wo, bo))
-            else:
-                dWo, dbo = gemm_tn(o_m, dy, d, d)
+            dz, dy, _, _ = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, into=(ggam, gbet))
+            queue_dw(actx, o_m, dy, d, d, [gwo], [gbo], (wo, bo))
             d_o = gemm_nt(dy, wc_o, d)
         dq, dkv = attn_mq_bwd(q_m, kv, cu, moff, o_m, d_o, lse, B, max_len, H, dh, key_pad)
-        if inplace:
-            queue_dw(actx, x_m, dq, d, d, [wq.grad], [bq.grad], (wq, bq))
-            flush_pending_dw(actx)                  # (the query-row problems have R rows, the key / value problem T)
-        else:
-            dWq, dbq = gemm_tn(x_m, dq, d, d)
+        queue_dw(actx, x_m, dq, d, d, [gwq], [gbq], (wq, bq))
+        flush_pending_dw(actx)                  # (the query-row problems have R rows, the key / value problem T)
         dx_m = gemm_nt(dq, wc_qkv[:, :d], d, residual=dz, out_dtype=torch.float32)      # query rows: through Wq + the residual branch (kept in fp32 until it joins dx)
         # every token: through Wk | Wv
-        if inplace and fused_dxdw >= 2 and dxdw_supported(x, dkv, 2):
-            dx = gemm_dxdw(x, dkv, wc_qkv[:, d:3 * d], [wk.grad, wv.grad], [bk.grad, bv.grad])
+        if routes and fused_dxdw >= 2 and dxdw_supported(x, dkv, 2):
+            dx = gemm_dxdw(x, dkv, wc_qkv[:, d:3 * d], [gwk, gwv], [gbk, gbv])
             _ready(wk, bk, wv, bv)
         else:
-            if inplace:
-                queue_dw(actx, x, dkv, d, 2 * d, [wk.grad, wv.grad], [bk.grad, bv.grad], (wk, bk, wv, bv))
-            else:
-                dWkv, dbkv = gemm_tn(x, dkv, d, 2 * d)
+            queue_dw(actx, x, dkv, d, 2 * d, [gwk, gwv], [gbk, gbv], (wk, bk, wv, bv))
             dx = gemm_nt(dkv, wc_qkv[:, d:3 * d], d)
         rows_add_(dx, midx, dx_m)
-        if inplace:
-            _ready(gam, bet)
-            flush_pending_dw(actx)
-            return (dx,) + (None,) * 22
-        dWk, dWv = dWkv[:, :d].contiguous(), dWkv[:, d:].contiguous()
-        dbk, dbv = dbkv[:d].contiguous(), dbkv[d:].contiguous()
-        return (dx, None, None, None, None, dWq, dbq, dWk, dbk, dWv, dbv, dWo, dbo, dgamma, dbeta) + (None,) * 8
+        _ready(gam, bet)
+        flush_pending_dw(actx)
+        return sink_returns(ctx, (dx, None, None, None, None), actx, sinks)
 
 
 class FFNBlockFn(torch.autograd.Function):
@@ -1569,31 +1551,21 @@ class FFNBlockFn(torch.autograd.Function):
         rate, seed = ctx.dims
         w1, b1, w2, b2, gam, bet = ctx.params
         d, Fp = x.shape[1], h.shape[1]
-        actx = arena_context(*ctx.params)
-        inplace = actx is not None
+        actx, sinks = grad_sinks(*ctx.params)
+        gw1, gb1, gw2, gb2, ggam, gbet = sinks
         _, wc1, _ = pk1.get(x.dtype, d, True)
         _, wc2, _ = pk2.get(x.dtype, Fp, True)
-        if inplace and fused_ffn_bwd and ffn_bwd_supported(x, h, z):
-            dx = ffn_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, h, x, wc2, wc1, pk1.N, w1.grad, b1.grad,
-                         w2.grad, b2.grad, gam.grad, bet.grad)
+        if _arena_routes(actx) and fused_ffn_bwd and ffn_bwd_supported(x, h, z):
+            dx = ffn_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, h, x, wc2, wc1, pk1.N, gw1, gb1, gw2, gb2, ggam, gbet)
             _ready(w1, b1, w2, b2, gam, bet)
-            return (dx,) + (None,) * 11
-        dz, dy, dgamma, dbeta = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed,
-                                                          into=(gam.grad, bet.grad) if inplace else None)
-        if inplace:
-            queue_dw(actx, h, dy, pk2.K, d, [w2.grad], [b2.grad], (w2, b2))
-        else:
-            dW2, db2 = gemm_tn(h, dy, pk2.K, d)
+            return sink_returns(ctx, (dx,), actx, sinks)
+        dz, dy, _, _ = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, into=(ggam, gbet))
+        queue_dw(actx, h, dy, pk2.K, d, [gw2], [gb2], (w2, b2))
         dh = gemm_nt(dy, wc2, Fp, gate=h)
-        if inplace:
-            queue_dw(actx, x, dh, d, pk1.N, [w1.grad], [b1.grad], (w1, b1))
-        else:
-            dW1, db1 = gemm_tn(x, dh, d, pk1.N)
+        queue_dw(actx, x, dh, d, pk1.N, [gw1], [gb1], (w1, b1))
         dx = gemm_nt(dh, wc1, d, residual=dz)
-        if inplace:
-            _ready(gam, bet)
-            return (dx,) + (None,) * 11
-        return (dx, dW1, db1, dW2, db2, dgamma, dbeta) + (None,) * 5
+        _ready(gam, bet)
+        return sink_returns(ctx, (dx,), actx, sinks)
 
 
 class MLPFn(torch.autograd.Function):
@@ -1634,27 +1606,18 @@ class MLPFn(torch.autograd.Function):
             else:
                 g = g * (acts[-1] > 0).to(g.dtype)
         g = _rows_ok(g, acts[0].dtype)      # a pitched [R, Vp] view (empty_rows) is taken as it is
-        grads = [None] * (2 * len(packs))
-        dx = None
-        actx = arena_context(*ctx.params)
-        inplace = actx is not None
+        actx, sinks = grad_sinks(*ctx.params)
         for i in range(len(packs) - 1, -1, -1):
             a = acts[i]
             pk = packs[i]
             _, wc, _ = pk.get(a.dtype, a.shape[1], True)
             last = i == len(packs) - 1
-            kern, bias = ctx.params[2 * i], ctx.params[2 * i + 1]
-            if inplace:          # queued: the layers' weight gradients go out as one grouped launch below
-                queue_dw(actx, a, g, pk.K, pk.N, [kern.grad], [bias.grad], (kern, bias))
-                dW = db = None
-            else:
-                dW, db = gemm_tn(a, g, pk.K, pk.N)
-            grads[2 * i], grads[2 * i + 1] = dW, db
+            # (in an arena the layers' weight gradients are queued and go out as one grouped launch below)
+            queue_dw(actx, a, g, pk.K, pk.N, [sinks[2 * i]], [sinks[2 * i + 1]], ctx.params[2 * i:2 * i + 2])
             with _timed('vocab_proj_dx' if last else 'head_mlp_dx'):
                 g = gemm_nt(g, wc, a.shape[1], gate=a if i > 0 else None)
-            dx = g
         flush_pending_dw(actx)
-        return (dx, None, None, None) + tuple(grads)
+        return sink_returns(ctx, (g, None, None, None), actx, sinks)
 
 
 # Vocabulary-head weight gradient BESIDE the encoder backward.  The dW sweep is MFMA / VALU bound and leaves HBM idle;
@@ -1851,32 +1814,20 @@ class VocabCEFn(torch.autograd.Function):
                                                     _p(rowscal_g), dh.shape[0], dh.shape[1], _st()), 'vocab_ce_apply_grad')
             dh, rowscal = dh_g, rowscal_g
         wt, _, b = ctx.pack.get(h.dtype, h.shape[1], False)
+        actx, (dW, db) = grad_sinks(kernel, bias)
         off = getattr(ctx.pack, 'tied_offset', None)
         if off is not None:     # tied head: `kernel` is the (rows, K) embedding table; dW [K, V] is added transposed
             dWt = torch.zeros(h.shape[1], ctx.V, dtype=torch.float32, device=h.device)
-            inplace = _inplace_ok(kernel, bias)
-            db = bias.grad if inplace else torch.zeros(bias.shape, dtype=torch.float32, device=h.device)
             vocab_ce_dw(h, wt, b, labels_i32, rowscal, ctx.V, dWt, db)
-            dtab = kernel.grad if inplace else torch.zeros(kernel.shape, dtype=torch.float32, device=h.device)
-            transpose_add_(dtab[off:off + ctx.V], dWt)
+            transpose_add_(dW[off:off + ctx.V], dWt)
             _tied_table_steps_whole(kernel)
-            if inplace:
-                _ready(bias)        # the table is announced by the embedding backward, which runs last
-                return dh, None, None, None, None, None, None, None, None
-            return dh, None, None, None, None, None, dtab, db, None
-        actx = arena_context(kernel, bias)
-        if actx is not None:
-            if h.is_cuda and _background_dw_for(actx):
-                _queue_background_dw(actx, h, wt, b, labels_i32, rowscal, ctx.V, kernel, bias)
-            else:
-                vocab_ce_dw(h, wt, b, labels_i32, rowscal, ctx.V, kernel.grad, bias.grad)
-                _ready(kernel, bias)
-            dW = db = None
+            _ready(bias)        # the table is announced by the embedding backward, which runs last
+        elif _arena_routes(actx) and h.is_cuda and _background_dw_for(actx):
+            _queue_background_dw(actx, h, wt, b, labels_i32, rowscal, ctx.V, kernel, bias)
         else:
-            dW = torch.zeros(kernel.shape, dtype=torch.float32, device=h.device)
-            db = torch.zeros(bias.shape, dtype=torch.float32, device=h.device)
             vocab_ce_dw(h, wt, b, labels_i32, rowscal, ctx.V, dW, db)
-        return dh, None, None, None, None, None, dW, db, None
+            _ready(kernel, bias)
+        return sink_returns(ctx, (dh, None, None, None, None, None), actx, (dW, db))
 
 
 class GatherRowsFn(torch.autograd.Function):
@@ -2125,6 +2076,7 @@ class MHAFn(torch.autograd.Function):
         w = attn_weights(qkv, key_pad, lse, B, S, H, dh) if want_w else None
         ctx.save_for_backward(xq, xk, xv, key_pad, qkv, o, lse)
         ctx.pk, ctx.dims, ctx.same = (pk_qkv, pk_o), (B, S, H, dh), same
+        ctx.params = (wq, bq, wk, bk, wv, bv, wo, bo)
         if w is None:
             w = torch.empty(0, device=xq.device)
         ctx.mark_non_differentiable(w)
@@ -2138,23 +2090,23 @@ class MHAFn(torch.autograd.Function):
         d = H * dh
         _, wc_o, _ = pk_o.get(xq.dtype, d, True)
         _, wc_qkv, _ = pk_qkv.get(xq.dtype, d, True)
+        actx, sinks = grad_sinks(*ctx.params)
+        gw, gb = sinks[0:8:2], sinks[1:8:2]         # Q, K, V, output projection
         dy = dout.contiguous()
-        dWo, dbo = gemm_tn(o, dy, d, d)
+        gemm_tn(o, dy, d, d, into=(gw[3:], gb[3:]))
         d_o = gemm_nt(dy, wc_o, d)
         dqkv = attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh)
         if ctx.same:
-            dW, db = gemm_tn(xq, dqkv, d, 3 * d)
-            (gq, gk, gv), (gbq, gbk, gbv) = pk_qkv.split_grads(dW, db)
-            dx = gemm_nt(dqkv, wc_qkv, d)
-            return (dx, None, None, None, gq, gbq, gk, gbk, gv, gbv, dWo, dbo) + (None,) * 7
-        gw, gb, gx = [], [], []
-        for i, x in enumerate((xq, xk, xv)):
-            g = dqkv[:, i * d:(i + 1) * d]
-            dW, db = gemm_tn(x, g, d, d)
-            gw.append(dW)
-            gb.append(db)
-            gx.append(gemm_nt(g, wc_qkv[:, i * d:(i + 1) * d], d))
-        return (gx[0], gx[1], gx[2], None, gw[0], gb[0], gw[1], gb[1], gw[2], gb[2], dWo, dbo) + (None,) * 7
+            gemm_tn(xq, dqkv, d, 3 * d, into=(gw[:3], gb[:3]))
+            gx = (gemm_nt(dqkv, wc_qkv, d), None, None)
+        else:
+            gx = []
+            for i, x in enumerate((xq, xk, xv)):
+                g = dqkv[:, i * d:(i + 1) * d]
+                gemm_tn(x, g, d, d, into=(gw[i:i + 1], gb[i:i + 1]))
+                gx.append(gemm_nt(g, wc_qkv[:, i * d:(i + 1) * d], d))
+        _ready(*ctx.params)
+        return sink_returns(ctx, tuple(gx) + (None,), actx, sinks)
 
 
 class TiedPackedLinear(PackedLinear):
@@ -2187,9 +2139,6 @@ class TiedPackedLinear(PackedLinear):
         return [L.PackDesc(rows.data_ptr(), None, ent['wc'].data_ptr() if ent['wc'] is not None else None,
                            ent['wt'].data_ptr(), None, self.N, self.K, self.Np, Kp, 0, 0)]
 
-    def split_grads(self, dW, db):
-        return [dW], [db]
-
 
 class TiedLogitsFn(torch.autograd.Function):
     """logits [R, Vp] = h . E[off : off + V]^T + bias for the tied-weight head (materialised route)."""
@@ -2214,14 +2163,11 @@ class TiedLogitsFn(torch.autograd.Function):
         dh = gemm_nt(g, wc, h.shape[1])
         off = pack.tied_offset
         _tied_table_steps_whole(table)
-        if _inplace_ok(table, bias):
-            transpose_add_(table.grad[off:off + pack.N], dWt)
-            bias.grad += db
-            _ready(bias)
-            return dh, None, None, None, None
-        dtab = torch.zeros(table.shape, dtype=torch.float32, device=h.device)
+        actx, (dtab, dbias) = grad_sinks(table, bias)
         transpose_add_(dtab[off:off + pack.N], dWt)
-        return dh, dtab, db, None, None
+        dbias += db
+        _ready(bias)
+        return sink_returns(ctx, (dh,), actx, (dtab, dbias))
 
 
 # --------------------------------------------------------------------------------------
@@ -2303,14 +2249,10 @@ class SampledCEFn(torch.autograd.Function):
         dWs = torch.zeros(dZ.shape[1], Kd, dtype=torch.float32, device=h.device)
         transpose_add_(dWs, dWT)
         dWy = row_scale_f32(h, dtrue)
-        inplace = _inplace_ok(table, bias)
-        tg = table.grad if inplace else torch.zeros(table.shape, dtype=torch.float32, device=h.device)
-        bg = bias.grad if inplace else torch.zeros(bias.shape, dtype=torch.float32, device=h.device)
+        actx, (tg, bg) = grad_sinks(table, bias)
         rows_scatter_add_f32_(tg, samples, dWs)
         rows_scatter_add_f32_(tg, idx_y, dWy)
         scatter_add_1d_(bg, samples, dbs.contiguous())
         scatter_add_1d_(bg, idx_y, dtrue.contiguous())
-        if inplace:
-            _ready(table, bias)
-            return dh, None, None, None, None, None, None
-        return dh, tg, bg, None, None, None, None
+        _ready(table, bias)
+        return sink_returns(ctx, (dh,), actx, (tg, bg))

@@ -287,3 +287,65 @@ def test_a_failed_backward_leaves_no_queued_weight_gradient(monkeypatch, route):
             assert float((got[n] - g).abs().max()) <= 1e-5 * float(g.abs().max()) + 1e-9, n
     finally:
         ops.background_workgroups, ops.fused_ffn_bwd, ops.fused_dxdw, ops.overlap_vocab_dw = prev
+
+
+def _head_model(kind, seed=7):
+    from bert4clickpath_amd.clickstream_transformer import (ClickstreamTransformer, ClozeMaskedItemPrediction,
+                                                            SampledSoftmaxHead, SoftMaxHead)
+    torch.manual_seed(seed)
+    hd = {'bf16': lambda: SoftMaxHead([64, 128], V), 'fp32': lambda: SoftMaxHead([64, 128], V),
+          'tied': lambda: ClozeMaskedItemPrediction([64], V), 'sampled': lambda: SampledSoftmaxHead([64, 128], V, num_sampled=512)}[kind]()
+    m = ClickstreamTransformer({'items': ['asin']}, {'items': ['i%d' % i for i in range(V)]}, {'items': 128}, hd,
+                               value_to_head='[MASK]', num_encoder_layers=2, num_attention_heads=2, dropout_rate=0.1,
+                               compute_dtype=torch.float32 if kind == 'fp32' else torch.bfloat16)
+    if kind == 'tied':
+        hd.tie(m.transformer.embedding_layers['items'].weight)
+    return m.to('cuda')
+
+
+# The sampled head's row scatter (b4c_rows_scatter_add_f32, b4c_scatter_add_1d) adds with float atomics: a row hit three or
+# more times sums in whatever order the adds land, run to run, in either convention (ops.deterministic does not cover it).
+_ATOMIC_SCATTER = pytest.mark.xfail(reason='the sampled head scatters its table gradient with float atomics', strict=False)
+
+
+@pytest.mark.parametrize('kind', ['bf16', 'fp32', 'tied', pytest.param('sampled', marks=_ATOMIC_SCATTER)])
+def test_arena_and_plain_gradients_differ_only_in_where_they_land(kind):
+    """One backward through an arena (the kernels add into p.grad) and one through plain autograd (the same kernels add into
+    fresh zeros that autograd receives) give torch.equal gradients for every parameter, with the arena-only routes (fused
+    backward kernels, grouped dW queue, background sweep) switched off.  >= 4,096 token rows: the full-sequence layers run
+    their large-M code."""
+    from bert4clickpath_amd import input_pipeline, ops, optim
+    from bert4clickpath_amd.clickstream_transformer.transformer import set_dropout_seed
+    names = ('fused_dxdw', 'fused_ffn_bwd', 'fused_attn_out_bwd', 'grouped_dw', 'overlap_vocab_dw')
+    prev = {n: getattr(ops, n) for n in names}
+    ops.fused_dxdw, ops.fused_ffn_bwd, ops.fused_attn_out_bwd, ops.grouped_dw, ops.overlap_vocab_dw = 0, False, False, False, False
+    try:
+        b = input_pipeline.synthetic_cloze_batch(256, S, V, seed=71, min_len=20)
+        items, labels = torch.from_numpy(b['ids'])[:, 2:S - 1].contiguous().cuda(), torch.from_numpy(b['labels_padded']).cuda()
+        n_real = int((b['ids'] != 0).sum())
+        assert n_real >= 4096
+
+        def grads(arena):
+            m = _head_model(kind)
+            if arena:
+                opt = optim.Adam(m.parameters())
+                opt.zero_grad()
+            set_dropout_seed(1234)
+            loss = m.cloze_loss({'asin': items}, labels, training=True, max_masked_per_row=10, n_real_tokens=n_real)
+            loss.backward()
+            if arena:
+                ops.join_side_work(opt.arena.ctx)
+                assert all(getattr(p, '_b4c_ctx', None) is opt.arena.ctx for p in m.parameters())
+            else:
+                assert all(getattr(p, '_b4c_ctx', None) is None for p in m.parameters())
+            torch.cuda.synchronize()
+            return {n: p.grad.detach().clone() for n, p in m.named_parameters() if p.grad is not None}
+
+        a, p = grads(True), grads(False)
+        assert sorted(a) == sorted(p) and len(a) > 0
+        for n in a:
+            assert torch.equal(a[n], p[n]), (kind, n, float((a[n] - p[n]).abs().max()))
+        assert any(float(g.abs().max()) > 0 for g in a.values())
+    finally:
+        for n, v in prev.items():
+            setattr(ops, n, v)
