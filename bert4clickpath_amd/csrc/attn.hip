@@ -274,22 +274,13 @@ static int check_attn(const char *who, int ld_qkv, int ld_o, int B, int S, int H
         default: KERNEL<T, 128> __VA_ARGS__; break;              \
     }
 
-static int g_attn_force_row = -1;
-static bool force_row() {
-    if (g_attn_force_row < 0) {
-        const char *e = getenv("B4C_ATTN_ROW");
-        g_attn_force_row = (e && e[0] == '1') ? 1 : 0;
-    }
-    return g_attn_force_row == 1;
-}
-
 extern "C" int b4c_attn_fwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
                             int S, int H, int dh, int dtype, void *stream) {
     B4C_REQUIRE(qkv && key_pad && o, "attn_fwd: null pointer");
     int rc = check_attn("attn_fwd", ld_qkv, ld_o, B, S, H, dh);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == B4C_BF16 && !force_row()) {
+    if (dtype == B4C_BF16) {
         rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, nullptr, st);
         if (rc != B4C_EUNSUPPORTED) return rc;
         note_row_fallback("attn_fwd", S, dh);
@@ -323,7 +314,7 @@ extern "C" int b4c_attn_bwd_ws(const void *qkv, int ld_qkv, const uint8_t *key_p
     if (rc) return rc;
     B4C_REQUIRE(ld_do >= H * dh && ld_do % 8 == 0 && ld_dqkv >= 3 * H * dh && ld_dqkv % 8 == 0, "attn_bwd: bad pitch");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == B4C_BF16 && !force_row()) {
+    if (dtype == B4C_BF16) {
         rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
                                workspace_bytes, nullptr, st);
         if (rc != B4C_EUNSUPPORTED) return rc;

@@ -5,7 +5,7 @@
 // read.  There the queries are the ~10 masked rows of a sequence, the keys / values all of its tokens:
 //     o_m = softmax(q_m K^T / sqrt(dk) + pad * -1e9) V        (transformer.py:64-97), m = the sequence's masked rows.
 // With so few queries per (sequence, head) the arithmetic is tiny (2 * 10 * S * dh MACs) and the cost is reading K and V
-// once: plain fp32 VALU math (exact parity arithmetic, both dtypes), no MFMA.
+// once.  fp32 runs on plain VALU math (exact parity arithmetic, no MFMA); bf16 on the matrix-core kernels further down.
 //
 // Layouts: q / o / dq [R][ld] with head h in columns h*DH ..; kv / dkv [T][ld] with k in columns h*DH.. and v in
 // H*DH + h*DH..; sequence b owns token rows cu[b] .. cu[b+1] and query rows moff[b] .. moff[b+1]; lse [R][H].
@@ -749,8 +749,7 @@ extern "C" int b4c_attn_mq_fwd(const void *q, int ld_q, const void *kv, int ld_k
     const int SP = (max_len + 63) / 64 * 64;
     const float sq = sqrtf((float)dh);
     hipStream_t st = (hipStream_t)stream;
-    static const bool valu_only = getenv("B4C_MQ_VALU") && atoi(getenv("B4C_MQ_VALU")) != 0;
-    if (dtype == B4C_BF16 && !valu_only) {      // matrix-core form, one wave per (sequence, head)
+    if (dtype == B4C_BF16) {      // matrix-core form, one wave per (sequence, head)
         const int n_items = B * H;
         const size_t shm_m = (size_t)MQ_WAVES * 2 * 32 * (dh * 2 + 16);
         const int grid = (n_items + MQ_WAVES - 1) / MQ_WAVES;
@@ -762,7 +761,7 @@ extern "C" int b4c_attn_mq_fwd(const void *q, int ld_q, const void *kv, int ld_k
 #undef MQ_MFMA
         return b4c_check_launch("attn_mq_fwd (mfma)");
     }
-    const size_t shm = mq_fwd_lds(SP, dh, dtype == B4C_BF16 ? 2 : 4);
+    const size_t shm = mq_fwd_lds(SP, dh, sizeof(float));
     B4C_REQUIRE(shm <= 160 * 1024, "attn_mq_fwd: max_len %d needs %zu bytes of LDS", max_len, shm);
 #define MQ_FWD(TT, DHH)                                                                                                              \
     do {                                                                                                                             \
@@ -770,8 +769,7 @@ extern "C" int b4c_attn_mq_fwd(const void *q, int ld_q, const void *kv, int ld_k
         attn_mq_fwd_kernel<TT, DHH><<<B * H, MQ_THREADS, shm, st>>>((const TT *)q, ld_q, (const TT *)kv, ld_kv, key_pad, cu_seqlens, q_offsets, \
                                                              (TT *)o, ld_o, lse, H, SP, sq);                                        \
     } while (0)
-    if (dtype == B4C_BF16) { if (dh == 64) MQ_FWD(bf16_t, 64); else MQ_FWD(bf16_t, 32); }
-    else { if (dh == 64) MQ_FWD(float, 64); else MQ_FWD(float, 32); }
+    if (dh == 64) MQ_FWD(float, 64); else MQ_FWD(float, 32);
 #undef MQ_FWD
     return b4c_check_launch("attn_mq_fwd");
 }
@@ -786,8 +784,7 @@ extern "C" int b4c_attn_mq_bwd(const void *q, int ld_q, const void *kv, int ld_k
                     ld_dq % 8 == 0 && ld_dkv % 8 == 0, "attn_mq_bwd: pitches");
     const float sq = sqrtf((float)dh);
     hipStream_t st = (hipStream_t)stream;
-    static const bool valu_only = getenv("B4C_MQ_VALU") && atoi(getenv("B4C_MQ_VALU")) != 0;
-    if (dtype == B4C_BF16 && !valu_only) {      // matrix-core form, one wave per (sequence, head)
+    if (dtype == B4C_BF16) {      // matrix-core form, one wave per (sequence, head)
         const int n_items = B * H, kstr = dh * 2 + 16;
         const size_t shm_m = (size_t)MQ_WAVES * (3 * 32 * kstr + 32 * (32 * 2 + 16) + 2 * 32 * 4);
         const int grid = (n_items + MQ_WAVES - 1) / MQ_WAVES;
@@ -802,7 +799,7 @@ extern "C" int b4c_attn_mq_bwd(const void *q, int ld_q, const void *kv, int ld_k
 #undef MQ_MFMA_B
         return b4c_check_launch("attn_mq_bwd (mfma)");
     }
-    const size_t shm = mq_bwd_lds(dh, dtype == B4C_BF16 ? 2 : 4);
+    const size_t shm = mq_bwd_lds(dh, sizeof(float));
 #define MQ_BWD(TT, DHH)                                                                                                              \
     do {                                                                                                                             \
         mq_allow_lds(attn_mq_bwd_kernel<TT, DHH>, shm);                                                                              \
@@ -810,8 +807,7 @@ extern "C" int b4c_attn_mq_bwd(const void *q, int ld_q, const void *kv, int ld_k
                                                              (const TT *)o, ld_o, (const TT *)d_o, ld_do, lse, (TT *)dq, ld_dq,      \
                                                              (TT *)dkv, ld_dkv, H, sq);                                              \
     } while (0)
-    if (dtype == B4C_BF16) { if (dh == 64) MQ_BWD(bf16_t, 64); else MQ_BWD(bf16_t, 32); }
-    else { if (dh == 64) MQ_BWD(float, 64); else MQ_BWD(float, 32); }
+    if (dh == 64) MQ_BWD(float, 64); else MQ_BWD(float, 32);
 #undef MQ_BWD
     return b4c_check_launch("attn_mq_bwd");
 }

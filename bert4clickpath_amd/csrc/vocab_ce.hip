@@ -20,7 +20,6 @@
 // HBM traffic: h, W (L2 / MALL resident, 12.8 MB), per-row partial sums.  Work: 4 GEMM units + 2 R V exps.
 // W / h tiles arrive by LDS-DMA (buffer_load ... lds) into an XOR-swizzled image that both the direct
 // (ds_read_b128) and the transposed (ds_read_b64_tr_b16) fragment reads hit without bank conflicts.
-// B4C_VCE_TIMING=1 prints per-kernel HIP-event times of the previous call (no synchronisation).
 //
 // MFMA 32x32x16 bf16 maps (lane l: r = l & 31, hf = l >> 5): A[row r][k = 8 hf + j], B[k = 8 hf + j][col r],
 // D reg t: row (t&3) + 8 (t>>2) + 4 hf, col r.  An accumulator tile used as B operand of the next MFMA sums
@@ -169,22 +168,11 @@ struct VceArgs {
     int64_t R;
     int V, parts, variant;
     int ntt;              // 128-token tiles
-    // "lse first" form of the forward (vce_exact_kernel): the row's lse and largest logit are known before the one sweep that
-    // accumulates U and Ud, both against that final lse
-    const float *rowstat; // [R][2]: lse2, max x  (NULL: the online form, statistics per part in st1)
-    int parts_st;         // vocabulary parts of the sweep that filled st1 (the lse sweep's own split)
 };
 
 // merge the per-part statistics of one row: lse2 = log2 sum_j 2^(x_j log2e), clipped flag, and (optionally) the
 // factor f_p = 2^(m2_p - M2) / l that turns part p's un-normalised sums into probabilities
 __device__ __forceinline__ void vce_row_stats(const VceArgs &a, int64_t row, float &lse2, bool &clipped, float &pmax) {
-    if (a.rowstat) {          // the lse-first form: one merged record per row; whether the row is clipped is read off the sweep's counts
-        const f32x2 s = *reinterpret_cast<const f32x2 *>(a.rowstat + row * 2);
-        lse2 = s[0];
-        pmax = __builtin_amdgcn_exp2f(s[1] * VCE_LOG2E - lse2);
-        clipped = a.variant == B4C_CE_TF;
-        return;
-    }
     float M = -INFINITY, l = 0.f, mn = INFINITY, mx = -INFINITY;
     for (int p = 0; p < a.parts; ++p) {
         const f32x4 s = *reinterpret_cast<const f32x4 *>(a.st1 + ((int64_t)p * a.R + row) * 4);
@@ -228,10 +216,6 @@ extern "C" int b4c_debug_vce_stamps(void *dst, size_t nbytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_vce_stamps), nbytes < sizeof(g_vce_stamps) ? nbytes : sizeof(g_vce_stamps));
 }
 #define VCE_STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_[k] += t_ - t0_; t0_ = t_; } while (0)
-__device__ unsigned long long g_vce_xstamps[2048 * 4 * 8];       // vce_exact_kernel: per wave, per pipeline step
-extern "C" int b4c_debug_vce_xstamps(void *dst, size_t nbytes) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_vce_xstamps), nbytes < sizeof(g_vce_xstamps) ? nbytes : sizeof(g_vce_xstamps));
-}
 #else
 #define VCE_STAMP(k) do { } while (0)
 #endif
@@ -538,343 +522,6 @@ __global__ void __launch_bounds__(512, 2) vce_token_kernel(VceArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
-// K2x (round 4): the "lse first" form of the forward.  The row's lse is known (lse sweep: vce_token_kernel<KD, 0> +
-// vce_rowstat_kernel), so ONE sweep forms the final probabilities p = 2^(x log2e - lse2) and accumulates BOTH products from the
-// same P and the same W fragments:  U = P W  and  Ud = P (1 - u) W  (the entries below TF's clip range), with Pc, the counts
-// and the dominant entry kept apart exactly as vce_token_kernel<KD, 2> keeps them.  No running maximum, no lazily raised
-// reference, no rescaling: the max / raise chain of the online sweep (21 % of a tile there) does not exist.
-//
-// One workgroup = 128 tokens x one part of the vocabulary, 256 threads = ONE WAVE PER SIMD with up to 512 registers per lane:
-// both accumulator sets (2 x 64 registers at K = 128), two logits tiles, double-buffered fragment sets.  A wave has no partner
-// to overlap with, so the overlap is made inside the wave: the loop over the four 32-row tiles of a W tile is software-
-// pipelined -- step k issues the logits MFMAs of tile k + 1 and the 16 P W MFMAs of tile k - 1 between the VALU
-// instructions of tile k's probabilities (two thirds of an entry's ~6 instructions per MFMA, at most one exponential per gap:
-// the issue costs of MI355X_MICROARCH.md fit the MFMA's 32 cycles), and the LDS fragment reads of step k + 1.
-// sched_barrier(0) after every MFMA's group pins the interleave.  Three GEMM units per W tile (3,072 cycles of matrix pipe
-// per SIMD) cover the tile's arrival by LDS-DMA (~2,900 cycles per CU) at 128 tokens per workgroup.
-// ------------------------------------------------------------------------------------------
-template <int KD> static size_t vce_exact_lds() {
-    const size_t tiles = 3 * (size_t)VTile<KD>::BYTES + 3 * 128 * 4;          // a ring of three W tiles + their bias
-    const size_t outs = (size_t)4 * 32 * (KD + 4) * 4 + 4 * 64 * 16;
-    return tiles > outs ? tiles : outs;
-}
-
-template <int KD>
-__global__ void __launch_bounds__(256, 1) vce_exact_kernel(VceArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NKS = KD / 16, NDT = KD / 32, STR = VTile<KD>::STR;
-    constexpr int TILE_B = VTile<KD>::BYTES;
-    constexpr int NPF = 2 * NDT;                        // transposed fragments of one 32-row tile
-    constexpr int NDMA = VTile<KD>::NIT * 2;              // DMA instructions per thread and W tile (256 threads)
-    constexpr int BIAS0 = 3 * TILE_B;                   // bias ring [3][128] floats behind the tile ring
-    const int unit = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hf = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, g = lane >> 4;
-    const int64_t tok0 = (int64_t)(unit % a.ntt) * 128;
-    const int64_t tok = tok0 + wave * 32 + r;
-    const int part = unit / a.ntt;
-    const int nvt = (a.V + 127) >> 7;
-    const int vt0 = (int)((int64_t)nvt * part / a.parts), vt1 = (int)((int64_t)nvt * (part + 1) / a.parts);
-
-    float lse2 = INFINITY;                              // rows past R: p = 2^(-inf) = 0
-    float pmax = 0.f;
-    if (tok < a.R) {
-        const f32x2 rs = *reinterpret_cast<const f32x2 *>(a.rowstat + tok * 2);
-        lse2 = rs[0];
-        pmax = __builtin_amdgcn_exp2f(rs[1] * VCE_LOG2E - lse2);
-    }
-    // (block-uniform) some row here has a dominant entry, the one probability that may exceed 1 - 1e-7: counted apart, see
-    // vce_token_kernel<KD, 2>
-    const bool anyhi = __syncthreads_or(pmax > 0.4f);
-
-    bf16x8 hfr[NKS];
-    vce_load_hfrag<KD>(a.h, a.ld_h, tok, a.R, hf, hfr);
-
-    // ---- W tiles: a ring of three LDS slots.  Tile t is read while the chain of tile t + 1's first rows already runs and
-    // tile t + 2 is on its way (LDS-DMA).  Slot bases are run-time values: every per-lane LDS address is a VGPR (fragment
-    // offset + slot base) + an immediate (the 32-row tile inside the W tile) ----
-    int aLc[NKS], aLn[NKS];          // direct fragments: this W tile / the next one
-    int aP[NDT][2];                  // transposed fragments: this W tile
-    int aBc, aBn;                    // bias quads
-    // (absolute LDS byte addresses: formed from `smem + offset` the compiler re-adds the array's base in front of every read)
-    const int lds0i = (int)(size_t)(__attribute__((address_space(3))) char *)smem;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) { aLc[ks] = lds0i + VTile<KD>::frag_off(r, ks, hf); aLn[ks] = aLc[ks] + TILE_B; }
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-        aP[dt][0] = lds0i + VTile<KD>::tr_off(hf, li, g, dt, 0);
-        aP[dt][1] = lds0i + VTile<KD>::tr_off(hf, li, g, dt, 1);
-    }
-    aBc = lds0i + BIAS0 + 16 * hf;
-    aBn = aBc + 512;
-    int slot_c = 0;                  // ring slot of the W tile whose probabilities are being formed
-
-    // the DMA of W tile vt into ring slot `slot`, one piece (1 KiB per wave instruction) at a time, and the tile's bias
-    const unsigned lds0 = (unsigned)lds0i;
-    float breg = 0.f;
-    auto dma_piece = [&](int vt, int slot, int i) __attribute__((always_inline)) {
-        VTile<KD>::template dma_piece_asm<256>(a.wt, a.ld_w, (int64_t)vt * 128, vt < vt1 ? a.V : 0, lds0 + (unsigned)(slot * TILE_B), wave, lane, i);
-    };
-    auto bias_fetch = [&](int vt) __attribute__((always_inline)) {
-        if (tid < 128) {
-            const int v = vt * 128 + tid;
-            breg = (vt < vt1 && v < a.V) ? (a.bias ? a.bias[v] : 0.f) : -INFINITY;   // rows past V: logit = -inf, p = 0
-        }
-    };
-    auto bias_store = [&](int slot) __attribute__((always_inline)) {
-        if (tid < 128) *reinterpret_cast<float *>(smem + BIAS0 + slot * 512 + tid * 4) = breg;
-    };
-    // tiles vt0 (slot 0) and vt0 + 1 (slot 1) before anything else
-#pragma unroll
-    for (int i = 0; i < NDMA; ++i) dma_piece(vt0, 0, i);
-    bias_fetch(vt0);
-    bias_store(0);
-#pragma unroll
-    for (int i = 0; i < NDMA; ++i) dma_piece(vt0 + 1, 1, i);
-    bias_fetch(vt0 + 1);
-    bias_store(1);
-    VCE_DMA_WAIT();
-    __syncthreads();
-
-#ifdef VCE_SCAN_STAMPS
-    unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0_ = __builtin_amdgcn_s_memtime();
-#define XSTAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_[k] += t_ - t0_; t0_ = t_; } while (0)
-#else
-#define XSTAMP(k) do { } while (0)
-#endif
-    float Pc = 0.f;                 // sum of the probabilities below the clip range
-    unsigned nlow = 0, nhi = 0;     // entries below the range (rows past V among them: p = 0) / dominant entries (p > 1/2)
-    f32x16 U[NDT], Ud[NDT];
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) { U[dt][t] = 0.f; Ud[dt][t] = 0.f; }
-
-    // The pipeline: global step s (one 32-row tile of the vocabulary) does
-    //   VALU : probabilities of tile s (logits in acc[s & 3]) -> pk / pl[s & 1], Pc, counts
-    //   MFMA : logits chain of tile s + 1 into acc[(s + 1) & 3];  U / Ud += W^T P of tile s - 1 (pk / pl[(s - 1) & 1])
-    //   LDS  : every fragment register is re-loaded right behind the MFMA that consumed it with what the NEXT step's MFMA of
-    //          that slot needs: the direct fragments (and the bias, into acc[(s + 2) & 3]) of tile s + 2, the transposed
-    //          fragments of tile s.  One set of fragment registers, a full step of latency cover; four logits accumulators.
-    // A W tile is four steps (RT = 0 .. 3): the re-loads of RT = 2, 3 reach into the NEXT W tile (aLn / aBn).
-    // The accumulators of the logits chain must be ordinary VGPRs: the VALU reads every entry, and with more than 256
-    // registers in use the compiler keeps MFMA results in the accumulation half of the file (one v_accvgpr_read per entry).
-    // The chain's MFMA is therefore inline assembly with VGPR operands; its results are first read a whole step later
-    // (>= 16 MFMAs), so no hazard wait is due -- except after the fill step, which waits explicitly.  The two accumulations
-    // (Pc, counts) are inline assembly as well: left to the compiler they sink to the end of the W tile (64 masks and values
-    // kept alive: spills), out of the MFMA gaps they are meant to fill.
-    f32x16 acc[4];
-    bf16x8 Lf[NKS], Pf[NPF], pk[2][2], pl[2][2];
-#pragma unroll
-    for (int i = 0; i < NPF; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) Pf[i][j] = (bf16_t)0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { pk[i][k][j] = (bf16_t)0.f; pl[i][k][j] = (bf16_t)0.f; }
-    const float l2e = VCE_LOG2E;
-    typedef const __attribute__((address_space(3))) bf16x8 *lds_bf8_t;
-    typedef const __attribute__((address_space(3))) f32x4 *lds_f4_t;
-    typedef vs16x4 __attribute__((address_space(3))) *lds_tr_t;
-    auto ldsL = [&](int addr, int imm) __attribute__((always_inline)) { return *(lds_bf8_t)(size_t)(unsigned)(addr + imm); };
-    auto ldsT = [&](int a0, int a1, int imm) __attribute__((always_inline)) {
-        const vs16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t)(size_t)(unsigned)(a0 + imm));
-        const vs16x4 y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t)(size_t)(unsigned)(a1 + imm));
-        const vs16x8 w = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-        return __builtin_bit_cast(bf16x8, w);
-    };
-    auto ldsB = [&](int addr, int rt, f32x16 &acc_) __attribute__((always_inline)) {
-#pragma unroll
-        for (int tq = 0; tq < 4; ++tq) {
-            const f32x4 q = *(lds_f4_t)(size_t)(unsigned)(addr + (rt * 32 + 8 * tq) * 4);
-            acc_[4 * tq] = q[0]; acc_[4 * tq + 1] = q[1]; acc_[4 * tq + 2] = q[2]; acc_[4 * tq + 3] = q[3];
-        }
-    };
-    // DOE: probabilities of this step's tile; DOC: chain of the next; DOP: P W of the previous; LDP: re-load the transposed
-    // fragments; DMA: the W tile after the next one is requested piece by piece in this step's gaps (vt_dma -> slot_dma)
-    auto step = [&](auto RTT, auto DOE, auto DOC, auto DOP, auto LDP, auto DMA, auto HI, int vt_dma, int slot_dma) __attribute__((always_inline)) {
-        constexpr int RT = decltype(RTT)::value;
-        constexpr bool do_e = decltype(DOE)::value, do_c = decltype(DOC)::value, do_p = decltype(DOP)::value;
-        constexpr bool ld_p = decltype(LDP)::value, dma = decltype(DMA)::value, hi = decltype(HI)::value;
-        constexpr int cur = RT & 1, prv = (RT + 1) & 1;
-        constexpr int ac = RT & 3, an = (RT + 1) & 3, an2 = (RT + 2) & 3;
-        constexpr int rt2 = (RT + 2) & 3;                      // the 32-row tile the direct re-loads fetch ...
-        constexpr bool nextw = RT >= 2;                          // ... of the next W tile
-        constexpr int n_c = do_c ? NKS : 0, n_p = do_p ? 4 * NDT : 0, n_mfma = n_c + n_p;
-        constexpr int n_gap = n_mfma > 0 ? n_mfma : 1;
-        float pv0 = 0.f, pv1 = 0.f, pl0 = 0.f, pl1 = 0.f;
-        auto entry = [&](int t, float &pv, float &plo) __attribute__((always_inline)) {
-            pv = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[ac][t], l2e, -lse2));
-            const bool low = pv < VCE_EPS;
-            plo = low ? pv : 0.f;
-            asm volatile("v_add_f32_e32 %0, %1, %0" : "+v"(Pc) : "v"(plo));
-            asm volatile("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(nlow) : "s"(__builtin_amdgcn_ballot_w64(low)) : "vcc");
-            // (tried: compare, select and carry-in through VCC in one assembly block -- v_cmp_e32 / s_nop 1 / v_cndmask_e32 /
-            // v_addc_co_e32 -- 1.5 % faster and WRONG on the lanes with bit 2 clear; not understood, not kept)
-            unsigned &nhi_ = nhi;          // (named outside the discarded branch: the capture must not depend on `hi`)
-            if constexpr (hi) asm volatile("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(nhi_) : "s"(__builtin_amdgcn_ballot_w64(pv > 0.5f)) : "vcc");
-        };
-        // the 24 chunks of a tile's VALU work: entry 2 j | entry 2 j + 1 | their two packs
-        auto chunk = [&](int c) __attribute__((always_inline)) {
-            const int j = c / 3, ph = c % 3, t0 = 2 * j, t1 = 2 * j + 1;
-            if (ph == 0) entry(t0, pv0, pl0);
-            else if (ph == 1) entry(t1, pv1, pl1);
-            else {
-                // entries t0, t1: elements (t & 7) of the k-step (t >> 3) of the B operand
-                pk[cur][t0 >> 3][t0 & 7] = (bf16_t)pv0; pk[cur][t0 >> 3][t1 & 7] = (bf16_t)pv1;
-                pl[cur][t0 >> 3][t0 & 7] = (bf16_t)pl0; pl[cur][t0 >> 3][t1 & 7] = (bf16_t)pl1;
-            }
-        };
-        if (do_c) ldsB(nextw ? aBn : aBc, rt2, acc[an2]);
-#pragma unroll
-        for (int i = 0; i < n_gap; ++i) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (i < n_c) {
-                asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc[an]) : "v"(Lf[i]), "v"(hfr[i]));
-                Lf[i] = ldsL(nextw ? aLn[i] : aLc[i], rt2 * 32 * STR);
-            } else if (i < n_mfma) {
-                const int q = i - n_c, f = q / 2;                 // fragment f = s2 * NDT + dt serves U then Ud
-                const int s2 = f / NDT, dt = f % NDT;
-                if ((q & 1) == 0) U[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Pf[f], pk[prv][s2], U[dt], 0, 0, 0);
-                else {
-                    Ud[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Pf[f], pl[prv][s2], Ud[dt], 0, 0, 0);
-                    if (ld_p) {
-                        const int o = (RT * 32 + 16 * s2) * STR;
-                        Pf[f] = ldsT(aP[dt][0], aP[dt][1], o);
-                    }
-                }
-            }
-            if (dma) {
-#pragma unroll
-                for (int d = (i * NDMA) / n_gap; d < ((i + 1) * NDMA) / n_gap; ++d) dma_piece(vt_dma, slot_dma, d);
-            }
-            if (do_e) {
-#pragma unroll
-                for (int c = (i * 24) / n_gap; c < ((i + 1) * 24) / n_gap; ++c) chunk(c);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    constexpr std::integral_constant<bool, true> Y{};
-    constexpr std::integral_constant<bool, false> N{};
-    constexpr std::integral_constant<int, 0> R0{};
-    constexpr std::integral_constant<int, 1> R1{};
-    constexpr std::integral_constant<int, 2> R2{};
-    constexpr std::integral_constant<int, 3> R3{};
-
-    auto sweep = [&](auto HI) __attribute__((always_inline)) {
-        // fill: fragments and bias of the first 32-row tile, its chain (as "step 3 of the W tile before": the re-loads reach
-        // into the NEXT W tile, which is the first one), then a wait: nothing orders the inline-assembly MFMAs' results
-        // against the VALU reads that follow at once
-        {
-            // the first W tile plays "next": aLn / aBn point at slot 0 for the fill step
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) aLn[ks] -= TILE_B;
-            aBn -= 512;
-            ldsB(aBn, 0, acc[0]);
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) Lf[ks] = ldsL(aLn[ks], 0);
-            step(R3, N, Y, N, N, N, HI, 0, 0);      // chain(0) into acc[0]; re-loads: L(1), bias(1) -> acc[1]
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) aLn[ks] += TILE_B;
-            aBn += 512;
-            asm volatile("s_nop 15\n\ts_nop 7");
-        }
-        for (int vt = vt0; vt < vt1; ++vt) {
-            XSTAMP(7);
-            step(R0, Y, Y, Y, Y, N, HI, 0, 0);
-            XSTAMP(0);
-            step(R1, Y, Y, Y, Y, N, HI, 0, 0);
-            XSTAMP(1);
-            // W tile vt + 1 has landed (requested a tile ago) and every wave is past its last read of tile vt - 1: that slot
-            // takes tile vt + 2, requested in the gaps of the next step
-            bias_store((slot_c + 1) % 3);      // the bias requested together with tile vt + 1, one W tile ago
-            VCE_DMA_WAIT();
-            B4C_LDS_BARRIER();
-            XSTAMP(6);
-            const int slot_n2 = (slot_c + 2) % 3;
-            bias_fetch(vt + 2);
-            step(R2, Y, Y, Y, Y, Y, HI, vt + 2, slot_n2);
-            XSTAMP(2);
-            step(R3, Y, Y, Y, Y, N, HI, 0, 0);
-            XSTAMP(3);
-            // the ring turns: next -> current
-            const int d_c = ((slot_c + 1) % 3 - slot_c) * TILE_B, d_n = ((slot_c + 2) % 3 - (slot_c + 1) % 3) * TILE_B;
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) { aLc[ks] += d_c; aLn[ks] += d_n; }
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) { aP[dt][0] += d_c; aP[dt][1] += d_c; }
-            aBc += d_c / TILE_B * 512;
-            aBn += d_n / TILE_B * 512;
-            slot_c = (slot_c + 1) % 3;
-        }
-        // drain: P W of the last 32-row tile
-        step(R0, N, N, Y, N, N, HI, 0, 0);
-        XSTAMP(4);
-    };
-    if (anyhi) sweep(Y); else sweep(N);
-    // the last W tile's request (a tile past this part: zeros) may still be on its way into the ring, and the compiler knows
-    // nothing of the inline-assembly DMA: it must have landed before the ring's memory is reused below
-    VCE_DMA_WAIT();
-#ifdef VCE_SCAN_STAMPS
-    if (lane == 0 && blockIdx.x < 2048)
-        for (int k = 0; k < 8; ++k) g_vce_xstamps[(blockIdx.x * 4 + wave) * 8 + k] = st_[k];
-#endif
-    __syncthreads();   // all tiles consumed: LDS is reused below
-
-    // U^T / Ud^T tiles -> LDS [token][d] per wave -> row-major partial sums of this vocabulary part; per-lane scalars summed
-    // over the two lanes of a token
-    constexpr int USTR = KD + 4;
-    float *sU = reinterpret_cast<float *>(smem) + wave * 32 * USTR;
-    auto flush = [&](f32x16 (&X)[NDT], float *dst) __attribute__((always_inline)) {
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-            for (int tq = 0; tq < 4; ++tq) {
-                const f32x4 v = {X[dt][4 * tq], X[dt][4 * tq + 1], X[dt][4 * tq + 2], X[dt][4 * tq + 3]};
-                *reinterpret_cast<f32x4 *>(sU + r * USTR + dt * 32 + 8 * tq + 4 * hf) = v;
-            }
-        __syncthreads();
-        for (int c = tid; c < 128 * (KD / 4); c += 256) {
-            const int t = c / (KD / 4), q = c % (KD / 4);
-            if (tok0 + t < a.R)
-                *reinterpret_cast<f32x4 *>(dst + (tok0 + t) * KD + q * 4) =
-                    *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(smem) + t * USTR + q * 4);
-        }
-        __syncthreads();
-    };
-    flush(U, a.u + (int64_t)part * a.R * KD);
-    flush(Ud, a.ud + (int64_t)part * a.R * KD);
-    f32x4 *sS = reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(smem) + 4 * 32 * USTR);   // [wave][lane]
-    // (n_low counts the rows past V of the last W tile too -- their p is 0: the combine kernel takes them out again)
-    sS[wave * 64 + lane] = (f32x4){(float)nlow, Pc, (float)nhi, 0.f};
-    __syncthreads();
-    if (tid < 128 && tok0 + tid < a.R) {
-        const int tgi = tid >> 5, ri = tid & 31;
-        *reinterpret_cast<f32x4 *>(a.sp + ((int64_t)part * a.R + tok0 + tid) * 4) = sS[tgi * 64 + ri] + sS[tgi * 64 + ri + 32];
-    }
-}
-
-// {lse2, max x} per row from the per-part statistics of the lse sweep (vce_token_kernel<KD, 0>: m2, l, -, max x)
-__global__ void __launch_bounds__(256) vce_rowstat_kernel(VceArgs a, float *__restrict__ out) {
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= a.R) return;
-    float M = -INFINITY, l = 0.f, mx = -INFINITY;
-    for (int p = 0; p < a.parts_st; ++p) {
-        const f32x4 s = *reinterpret_cast<const f32x4 *>(a.st1 + ((int64_t)p * a.R + row) * 4);
-        const float M2 = fmaxf(M, s[0]);
-        l = l * __builtin_amdgcn_exp2f(M - M2) + s[1] * __builtin_amdgcn_exp2f(s[0] - M2);
-        M = M2;
-        mx = fmaxf(mx, s[3]);
-    }
-    *reinterpret_cast<f32x2 *>(out + row * 2) = (f32x2){M + __log2f(l), mx};
-}
-
-// ------------------------------------------------------------------------------------------
 // K3: one wave per row.  loss, dh, row scalars for the dW sweep.
 //   dL/dx_j = p_j (u_j / S - G) - [j = y] u_y p_y / clip(p_y),  G = Pu / S - u_y p_y / clip(p_y)
 //   (u = 1, S = 1, G = 0 on rows that never leave the clip range; plain variant: p_j - [j = y])
@@ -912,9 +559,8 @@ __global__ void __launch_bounds__(256) vce_combine_kernel(VceArgs a) {
         U[e] = 0.f;
         Ud[e] = 0.f;
         for (int p = 0; p < a.parts; ++p) {
-            // part p's sums are relative to its own reference m2_p: 2^(m2_p - lse2) makes them probabilities (the lse-first
-            // sweep accumulated probabilities to begin with)
-            const float f = a.rowstat ? 1.f : __builtin_amdgcn_exp2f(a.st1[((int64_t)p * a.R + row) * 4] - lse2);
+            // part p's sums are relative to its own reference m2_p: 2^(m2_p - lse2) makes them probabilities
+            const float f = __builtin_amdgcn_exp2f(a.st1[((int64_t)p * a.R + row) * 4] - lse2);
             U[e] += f * a.u[((int64_t)p * a.R + row) * KD + d];
             if (clipped) Ud[e] += a.ud[((int64_t)p * a.R + row) * KD + d];     // the second sweep ran against lse2 itself
         }
@@ -934,16 +580,11 @@ __global__ void __launch_bounds__(256) vce_combine_kernel(VceArgs a) {
             const f32x4 q = *reinterpret_cast<const f32x4 *>(a.sp + ((int64_t)p * a.R + row) * 4);
             nu += q[0]; Pc += q[1]; ntop += q[2];
         }
-        // (the lse-first sweep counts the entries BELOW the range, the padding rows of the last W tile among them)
-        if (a.rowstat) nu = (float)a.V - (nu - (float)(((a.V + 127) >> 7) * 128 - a.V)) - ntop;
         // Does the dominant entry (p > 1/2, if the row has one) exceed 1 - 1e-7?  Exactly when all the OTHER entries together
         // stay below 1e-7: none of them inside the clip range (each of those alone is >= 1e-7) and the mass Pc of the ones
         // below it -- a sum of tiny numbers, exact to fp32 rounding -- under 1e-7.  (1 - p itself is not representable
         // there, and 2^(x log2e - lse2) is off by 1e-6 at logits of +-50: a decision read off p flipped between the kernels.)
         all_out = ntop > 0.5f && nu < 0.5f && Pc < VCE_EPS;
-        // (lse-first form: every row went through the clipped sweep; one with every probability inside the range -- all V
-        // entries counted -- is an unclipped row and takes the unclipped formulas, to the bit)
-        if (a.rowstat && nu + ntop >= (float)a.V) { clipped = false; all_out = false; }
         if (!clipped) {
             loss = lse - xy;
         } else if (all_out) {
@@ -1430,7 +1071,9 @@ template <int KD> static size_t vce_dw_lds() {
 
 extern "C" int64_t b4c_vocab_ce_workspace_bytes(int64_t R, int V, int K) {
     if (R <= 0 || V <= 0 || !vce_shape_ok(K)) return 0;
-    // 8 = the largest vocabulary split; + the lse-first form's own statistics (8 parts x R x 4, and 2 per row merged)
+    // 8 = the largest vocabulary split; + R x (8 x 4 + 2) floats that no kernel uses any more (they held the statistics of
+    // a removed forward form).  Kept: this size is the cap in b4c_vocab_ce_dw_workspace_bytes, which picks the token split
+    // of the deterministic dW sweep, and the split fixes the order of its sums (at C2 this term is the larger one)
     const int64_t fwd = (int64_t)8 * R * (4 + 2 * (int64_t)K + 4) * 4 + (int64_t)R * (8 * 4 + 2) * 4 + 64;
     // vocabulary-major scratch of the label term; deterministic form: + sort keys, order and the sort's own workspace
     const int64_t dw = (int64_t)V * K * 4 + 64 + R * 12 + b4c_sort_ids_workspace_bytes(R, V + 1) + 64 + ((R + 31) / 32) * 2 * (K + 1) * 4;
@@ -1450,66 +1093,8 @@ extern "C" int64_t b4c_vocab_ce_dw_workspace_bytes(int64_t R, int V, int K, int 
     return base > parts ? base : parts;
 }
 
-// The "lse first" form (round 4): lse sweep -> per-row {lse2, max x} -> ONE exact sweep at one wave per SIMD -> combine.
-// B4C_VCE_FORM=online|exact selects (A/B on one library); TF's clip semantics only (the plain variant needs one sweep as it is).
-static bool vce_exact_form() {
-    static const char *e = getenv("B4C_VCE_FORM");
-    return e ? (e[0] == 'e') : false;
-}
-
-template <int KD>
-static int vce_fwd_exact_launch(VceArgs a, hipStream_t st) {
-    // workspace: [exact sweep: sp | u | ud (its own `parts`)] [lse sweep: st1 (parts_st)] [rowstat]
-    const int nh = vce_token_nh(a.R);
-    const int64_t ntt_l = ceil_div64(a.R, 128 * nh), ntt = ceil_div64(a.R, 128);
-    const int nvt = (a.V + 127) / 128;
-    float *ws = a.st1;
-    VceArgs l = a;                                     // the lse sweep (MODE 0 of the token kernel)
-    l.parts = vce_pick_split(ntt_l, nvt, 0.005);
-    l.ntt = (int)ntt_l;
-    a.parts = vce_pick_split(ntt, nvt, 0.01);
-    a.ntt = (int)ntt;
-    a.sp = ws;
-    a.u = a.sp + (int64_t)a.parts * a.R * 4;
-    a.ud = a.u + (int64_t)a.parts * a.R * KD;
-    l.st1 = a.ud + (int64_t)a.parts * a.R * KD;
-    float *rowstat = l.st1 + (int64_t)l.parts * a.R * 4;
-    a.st1 = l.st1;
-    a.parts_st = l.parts_st = l.parts;
-    a.rowstat = rowstat;
-    const size_t lds_l = vce_token_lds<KD>(), lds_x = vce_exact_lds<KD>();
-    static thread_local bool done = false;
-    if (!done) {
-        vce_allow_lds(vce_token_kernel<KD, 0, 1>, lds_l); vce_allow_lds(vce_token_kernel<KD, 0, 2>, lds_l);
-        vce_allow_lds(vce_exact_kernel<KD>, lds_x);
-        done = true;
-    }
-    static const bool dbg = getenv("B4C_VCE_TIMING") != nullptr;
-    static hipEvent_t ev[4];
-    static bool have = false;
-    if (dbg) {
-        if (have && hipEventQuery(ev[3]) == hipSuccess) {
-            float t1 = 0, t2 = 0, t3 = 0;
-            (void)hipEventElapsedTime(&t1, ev[0], ev[1]); (void)hipEventElapsedTime(&t2, ev[1], ev[2]); (void)hipEventElapsedTime(&t3, ev[2], ev[3]);
-            fprintf(stderr, "[vce_fwd exact] previous call: lse sweep %.3f ms, exact sweep %.3f ms, combine %.3f ms (parts %d / %d)\n", t1, t2, t3, l.parts, a.parts);
-        }
-        if (!have) { for (auto &e : ev) (void)hipEventCreate(&e); have = true; }
-        (void)hipEventRecord(ev[0], st);
-    }
-    if (nh == 2) vce_token_kernel<KD, 0, 2><<<(unsigned)(ntt_l * l.parts), 512, lds_l, st>>>(l);
-    else vce_token_kernel<KD, 0, 1><<<(unsigned)(ntt_l * l.parts), 512, lds_l, st>>>(l);
-    vce_rowstat_kernel<<<(unsigned)ceil_div64(a.R, 256), 256, 0, st>>>(l, rowstat);
-    if (dbg) (void)hipEventRecord(ev[1], st);
-    vce_exact_kernel<KD><<<(unsigned)(ntt * a.parts), 256, lds_x, st>>>(a);
-    if (dbg) (void)hipEventRecord(ev[2], st);
-    vce_combine_kernel<KD><<<(unsigned)ceil_div64(a.R, 4), 256, 0, st>>>(a);
-    if (dbg) (void)hipEventRecord(ev[3], st);
-    return b4c_check_launch("vocab_ce_fwd (lse first)");
-}
-
 template <int KD>
 static int vce_fwd_launch(VceArgs a, hipStream_t st) {
-    if (a.variant == B4C_CE_TF && vce_exact_form()) return vce_fwd_exact_launch<KD>(a, st);
     const int nh = vce_token_nh(a.R);
     const int64_t ntt = ceil_div64(a.R, 128 * nh);
     const int nvt = (a.V + 127) / 128;
@@ -1529,27 +1114,11 @@ static int vce_fwd_launch(VceArgs a, hipStream_t st) {
     }
     a.ntt = (int)ntt;
     const unsigned grid = (unsigned)(ntt * a.parts);
-    // B4C_VCE_TIMING=1: HIP events around the kernels, read back (without synchronising) at the next call
-    static const bool dbg = getenv("B4C_VCE_TIMING") != nullptr;
-    static hipEvent_t ev[4];
-    static bool have = false;
-    if (dbg) {
-        if (have && hipEventQuery(ev[3]) == hipSuccess) {
-            float t1 = 0, t2 = 0, t3 = 0;
-            (void)hipEventElapsedTime(&t1, ev[0], ev[1]); (void)hipEventElapsedTime(&t2, ev[1], ev[2]); (void)hipEventElapsedTime(&t3, ev[2], ev[3]);
-            fprintf(stderr, "[vce_fwd] previous call: sweep %.3f ms, clipped sweep %.3f ms, combine %.3f ms (parts %d)\n", t1, t2, t3, a.parts);
-        }
-        if (!have) { for (auto &e : ev) (void)hipEventCreate(&e); have = true; }
-        (void)hipEventRecord(ev[0], st);
-    }
     if (nh == 2) vce_token_kernel<KD, 1, 2><<<grid, 512, lds, st>>>(a); else vce_token_kernel<KD, 1, 1><<<grid, 512, lds, st>>>(a);
-    if (dbg) (void)hipEventRecord(ev[1], st);
     if (a.variant == B4C_CE_TF) {
         if (nh == 2) vce_token_kernel<KD, 2, 2><<<grid, 512, lds, st>>>(a); else vce_token_kernel<KD, 2, 1><<<grid, 512, lds, st>>>(a);
     }
-    if (dbg) (void)hipEventRecord(ev[2], st);
     vce_combine_kernel<KD><<<(unsigned)ceil_div64(a.R, 4), 256, 0, st>>>(a);
-    if (dbg) (void)hipEventRecord(ev[3], st);
     return b4c_check_launch("vocab_ce_fwd");
 }
 

@@ -34,7 +34,7 @@ GROUPS = [
     (('vocab_rank',), ('vce_scan_kernel<128, 0,', 'vce_scan_kernel<64, 0,', 'vce_label_logit'), 'vce_label_logit'),
     (('vocab_topk',), ('vce_scan_kernel', 'vce_tau_kernel', 'vce_select_kernel'), 'vce_select_kernel'),
     (('vocab_lse',), ('vce_token_kernel<128, 0,', 'vce_token_kernel<64, 0,', 'vce_lse_kernel'), 'vce_lse_kernel'),
-    (('vocab_ce_fwd',), ('vce_token_kernel', 'vce_combine_kernel', 'vce_exact_kernel', 'vce_rowstat_kernel'), 'vce_combine_kernel'),
+    (('vocab_ce_fwd',), ('vce_token_kernel', 'vce_combine_kernel'), 'vce_combine_kernel'),
     # (the background form goes out in pieces: every piece is a note; the label kernels ride on the last piece)
     (('vocab_ce_dw_bg', 'vocab_ce_dw'), ('vce_dw_kernel', 'vce_label'), 'vce_dw_kernel'),
 ]

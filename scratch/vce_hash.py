@@ -1,5 +1,5 @@
 """Hashes of the logits-free head's forward outputs (item loss, dh, row scalars) on seeded C2-sized operands, for
-bit-identity checks between two builds of the library (B4C_LIB_PATH) -- and the sweeps' times (B4C_VCE_TIMING=1)."""
+bit-identity checks between two builds of the library (B4C_LIB_PATH)."""
 import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

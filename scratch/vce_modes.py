@@ -1,5 +1,5 @@
-"""Per-kernel times of the logits-free vocabulary head at C2 (R = 40,960, V = 50,000, K = 128): forward sweeps (B4C_VCE_TIMING
-prints them), lse sweep, dW sweep.  A/B of two builds: run once per library with B4C_LIB_PATH set, interleaved, in ONE gpurun call.
+"""Per-kernel times of the logits-free vocabulary head at C2 (R = 40,960, V = 50,000, K = 128): forward, dW sweep,
+lse sweep + softmax projection.  A/B of two builds: run once per library with B4C_LIB_PATH set, interleaved, on one box.
 usage: [VCE_W_SCALE=0.74] [B4C_LIB_PATH=...] python scratch/vce_modes.py [iterations]"""
 import os
 import sys
@@ -7,7 +7,6 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault('B4C_VCE_TIMING', '1')
 from bert4clickpath_amd import ops, _lib as L  # noqa: E402
 
 R, V, K = 40960, 50000, 128
