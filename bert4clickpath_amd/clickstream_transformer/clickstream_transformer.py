@@ -339,6 +339,7 @@ class ClickstreamTransformer(nn.Module):
         with the compact int32 labels.  Neither: R is read back from the device (one host sync).
         pack: the encoder runs on the padding-free layout; the dense [MASK] indices are mapped to its rows."""
         self._mask_flag = None
+        self._row_offsets = None
 
         def positions(ids_first, raw_first):
             if cap is not None:
@@ -349,8 +350,10 @@ class ClickstreamTransformer(nn.Module):
                 counts, offsets, flat, mx = self._match_positions(ids_first, raw_first, cap, pk_flag)
                 self._mask_flag = mx if pk_flag is None else None
                 lab = ops.compact_labels(labels_padded, counts, offsets, cap, flat)     # also sets flat[R:] = -1
+                self._row_offsets = offsets
                 return flat, offsets, lab
             _, offsets, flat, _ = self._match_positions(ids_first, raw_first)
+            self._row_offsets = offsets          # [B + 1]: rows offsets[b] .. offsets[b + 1] are sequence b's (predict_topk)
             R = int(offsets[-1].item())
             return flat[:R], offsets, None
 
@@ -413,10 +416,14 @@ class ClickstreamTransformer(nn.Module):
         return loss
 
     @torch.no_grad()
-    def predict_topk(self, inputs, k, labels=None, flat_idx=None, packed=None, n_real_tokens=None):
+    def predict_topk(self, inputs, k, labels=None, flat_idx=None, packed=None, n_real_tokens=None, exclude=None):
         """Top-k item ids (label space) at every masked position, ranked over all V items: the fp32 path ranks the fp32
         probabilities as the reference's metrics do (utils.py:176, 245), the bf16 path the fp32 logits (head.SoftMaxHead.topk);
-        returns (topk_idx (R,k) int32, hit (R,), ndcg (R,)) -- the latter two when labels are given."""
+        returns (topk_idx (R,k) int32, hit (R,), ndcg (R,)) -- the latter two when labels are given.
+        exclude: items (label space) left out of the ranking -- an integer tensor padded with negative ids, or a host list of
+        lists: (R, E) one list per masked row in row-major order, or (B, E) one per sequence, for each of its [MASK] rows (a
+        first dimension equal to R is read per row).  An excluded item is never returned and never ranks before the label;
+        the label itself is never excluded; fewer than k items left: ids -1."""
         rows, _ = self._masked_rows(inputs, False, flat_idx, pack=self._use_packed(inputs, packed, n_real_tokens),
                                     n_real_tokens=n_real_tokens)
         lab = None
@@ -425,13 +432,16 @@ class ClickstreamTransformer(nn.Module):
             if lab.dim() == 2:
                 lab = lab[lab != -1.0]
             lab = lab.to(torch.int32).contiguous()
+        ex = None
+        if exclude is not None:
+            ex = self._row_exclusions(exclude, rows.shape[0], rows.device, lab)
         if hasattr(self.head, 'topk'):           # logits-free where the head's kernels cover it (head.SoftMaxHead.topk)
-            idx, hit, ndcg = self.head.topk(rows, k, lab)
+            idx, hit, ndcg = self.head.topk(rows, k, lab, exclude=ex)
         else:
             scores = self.head.logits(rows, out_fp32=True)
             if rows.dtype == torch.float32:
                 scores = ops.softmax_rows(scores, self.head.output_vocab_size)
-            idx, hit, ndcg = ops.topk_rows(scores, self.head.output_vocab_size, k, lab)
+            idx, hit, ndcg = ops.topk_rows(scores, self.head.output_vocab_size, k, lab, exclude=ex)
         if self._packed is not None and n_real_tokens is not None:
             # a caller-given token count that the device's own contradicts: ids -1, hit / ndcg NaN (no read-back)
             flag = self._packed.ids_packed
@@ -440,6 +450,22 @@ class ClickstreamTransformer(nn.Module):
                 ops.poison_rows(hit.view(-1, 1), flag)
                 ops.poison_rows(ndcg.view(-1, 1), flag)
         return idx, hit, ndcg
+
+    def _row_exclusions(self, exclude, R, device, lab):
+        """predict_topk's `exclude` -> the canonical (R, E) lists of ops.exclusions, one per masked row"""
+        if not isinstance(exclude, torch.Tensor):
+            exclude = ops.exclusions(exclude, 1 << 30)         # host lists -> one int32 tensor, -1 padded (ids kept as given)
+        if exclude.dim() != 2:
+            raise B4CError('predict_topk: exclude must be (R, E) or (B, E), got shape %s' % (tuple(exclude.shape),))
+        exclude = exclude.to(device)
+        if exclude.shape[0] != R:
+            offsets = self._row_offsets
+            if offsets is None or exclude.shape[0] != offsets.shape[0] - 1:
+                raise B4CError('predict_topk: exclude has %d lists for %d masked rows%s' % (
+                    exclude.shape[0], R, '' if offsets is None else ' of %d sequences' % (offsets.shape[0] - 1)))
+            seq = torch.searchsorted(offsets[1:].long(), torch.arange(R, device=device), right=True)
+            exclude = exclude[seq]
+        return ops.exclusions(exclude, self.head.output_vocab_size, lab)
 
     def get_serving_signature(self):
         names = []

@@ -100,7 +100,7 @@ class SoftMaxHead(nn.Module):
             h = self.trunk(x2d).contiguous()
         return ClozeScores(self, h, shp[:-1], inputs) if self._rank_supported(h) else None
 
-    def topk(self, x2d, k, labels_i32=None, trunk_done=False):
+    def topk(self, x2d, k, labels_i32=None, trunk_done=False, exclude=None):
         """-> (ids [R, k] int32, hit [R], ndcg [R]) of the V scores of every row, ranked as tf.math.top_k ranks (ties -> lower
         index first).
         fp32 (the parity path): what is ranked is what the reference ranks -- the fp32 softmax OUTPUT (utils.py:176, 245 call
@@ -109,18 +109,21 @@ class SoftMaxHead(nn.Module):
         bf16 (the throughput path): the fp32 LOGITS are ranked (softmax is monotone; no probability is ever formed) -- 64- or
         128-wide projection input: the scores never reach memory (b4c_vocab_topk); rows with mass ties at the selection
         threshold, and every other configuration, on materialised fp32 logits.  Logits that differ although their
-        probabilities would tie are ordered strictly: a documented deviation (tests/test_gpu_rank.py)."""
+        probabilities would tie are ordered strictly: a documented deviation (tests/test_gpu_rank.py).
+        exclude (ops.exclusions, one list per row): the listed items are left out of each row's ranking on every route."""
         V = self.output_vocab_size
         with torch.no_grad():
             h = x2d if trunk_done else self.trunk(x2d)
             if self._rank_supported(h):
                 K, _, _ = self._proj()
                 wt, _, b = self._packs[-1].get(h.dtype, K, False)
-                idx, hit, ndcg, overflow = ops.vocab_topk(h.contiguous(), wt, b, V, k, labels_i32)
+                idx, hit, ndcg, overflow = ops.vocab_topk(h.contiguous(), wt, b, V, k, labels_i32, exclude=exclude)
                 if int(overflow.item()):          # (one 4-byte read-back per call; the ids are read by the host anyway)
+                    # (a row whose lists leave no item at all also starts with -1: ranked again, it gets -1 again)
                     bad = (idx[:, 0] < 0).nonzero().reshape(-1)
                     i2, h2, n2 = ops.topk_rows(self._project(h[bad].contiguous(), out_fp32=True), V, k,
-                                               labels_i32[bad].contiguous() if labels_i32 is not None else None)
+                                               labels_i32[bad].contiguous() if labels_i32 is not None else None,
+                                               exclude=exclude[bad].contiguous() if exclude is not None else None)
                     idx[bad] = i2
                     if hit is not None:
                         hit[bad], ndcg[bad] = h2, n2
@@ -128,7 +131,7 @@ class SoftMaxHead(nn.Module):
             scores = self._project(h, out_fp32=True)
             if h.dtype == torch.float32:
                 scores = ops.softmax_rows(scores, V)
-            return ops.topk_rows(scores, V, k, labels_i32)
+            return ops.topk_rows(scores, V, k, labels_i32, exclude=exclude)
 
     def forward(self, inputs, **kwargs):
         """inputs (B, M, d) -> probabilities (B, M, V), materialised as the reference does."""
@@ -169,16 +172,19 @@ class ClozeScores:
         wt, _, b = self.head._packs[-1].get(self.h2d.dtype, K, False)
         return wt, b
 
-    def rank_of(self, labels_i32):
-        """items ranked before the label, per row (ties -> lower index first); negative where the label is a pad"""
-        key = (labels_i32.data_ptr(), labels_i32._version, tuple(labels_i32.shape))
+    def rank_of(self, labels_i32, exclude=None):
+        """items ranked before the label, per row (ties -> lower index first); negative where the label is a pad.
+        exclude (ops.exclusions, one list per row): listed items do not count."""
+        key = (labels_i32.data_ptr(), labels_i32._version, tuple(labels_i32.shape),
+               None if exclude is None else (exclude.data_ptr(), exclude._version, tuple(exclude.shape)))
         if self._rank is None or self._rank[0] != key:
             wt, b = self._operands()
-            self._rank = (key, ops.vocab_rank(self.h2d, wt, b, labels_i32, self.head.output_vocab_size), labels_i32)
+            self._rank = (key, ops.vocab_rank(self.h2d, wt, b, labels_i32, self.head.output_vocab_size, exclude=exclude),
+                          labels_i32, exclude)
         return self._rank[1]
 
-    def topk(self, k, labels_i32=None):
-        return self.head.topk(self.h2d, k, labels_i32, trunk_done=True)
+    def topk(self, k, labels_i32=None, exclude=None):
+        return self.head.topk(self.h2d, k, labels_i32, trunk_done=True, exclude=exclude)
 
     def probabilities(self):
         """the (B, M, V) tensor this object stands for: what the head returns when called as the reference calls it"""

@@ -632,83 +632,54 @@ extern "C" int b4c_softmax_ce_fwd_bwd(void *logits, int ld, const int32_t *label
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
 
+// Exclusions (EX = true, b4c_topk_rows_excl): the row's canonical list (ascending ids, then -1) is staged in LDS; a chunk of 8
+// elements [8 c, 8 c + 8) finds its first list entry by binary search and takes the bits of the entries below its end.  An
+// excluded element is treated as absent: it reaches no per-thread maximum, no candidate list and no sorted list.
+template <bool EX, int NT>
+__device__ __forceinline__ int topk_excl_stage(const int32_t *__restrict__ excl, int ld_e, int E, int64_t row, int *sx, int *s_nx, int tid) {
+    if (!EX) return 0;
+    if (tid == 0) *s_nx = 0;
+    __syncthreads();
+    const int32_t *xl = excl + row * ld_e;
+    for (int i = tid; i < E; i += NT) {
+        const int v = xl[i];
+        sx[i] = v;
+        if (v >= 0 && (i + 1 == E || xl[i + 1] < 0)) *s_nx = i + 1;
+    }
+    __syncthreads();
+    return *s_nx;
+}
+// bit e set: element 8 c + e of the row is excluded
+__device__ __forceinline__ unsigned topk_excl_bits(const int *sx, int nx, int c) {
+    const int j0 = c * 8;
+    int p = 0, n = nx;
+    while (n > 0) {
+        const int half = n >> 1;
+        if (sx[p + half] < j0) { p += half + 1; n -= half + 1; } else n = half;
+    }
+    unsigned m = 0;
+    for (; p < nx && sx[p] < j0 + 8; ++p) m |= 1u << (sx[p] - j0);
+    return m;
+}
+
 template <typename T, int KM>
 __global__ void __launch_bounds__(256) topk_rows_lists_kernel(const T *__restrict__ x, int ld, int64_t R, int V, int k,
                                                         int32_t *__restrict__ topk_idx, const int32_t *__restrict__ labels,
                                                         float *__restrict__ hit, float *__restrict__ ndcg,
                                                         const int32_t *__restrict__ redo) {
-    __shared__ float lv[256][KM + 1];
-    __shared__ int li[256][KM + 1];
-    __shared__ float wv[4];
-    __shared__ int wi[4], wo[4];
-    __shared__ int s_owner;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nch = (V + 7) >> 3;
-    for (int64_t row = blockIdx.x; row < R; row += gridDim.x) {
-        if (redo && !redo[row]) continue;       // block-uniform: the threshold kernel has done this row
-        const T *xr = x + row * ld;
-        float tv[KM];
-        int ti[KM];
-#pragma unroll
-        for (int q = 0; q < KM; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
-        for (int c = tid; c < nch; c += 256) {
-            float v[8];
-            Vec8<T>::load(xr + c * 8, v);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int j = c * 8 + e;
-                if (j < V && better(v[e], j, tv[KM - 1], ti[KM - 1])) {
-                    tv[KM - 1] = v[e];
-                    ti[KM - 1] = j;
-#pragma unroll
-                    for (int q = KM - 1; q > 0; --q) {
-                        if (better(tv[q], ti[q], tv[q - 1], ti[q - 1])) {
-                            const float fv = tv[q]; tv[q] = tv[q - 1]; tv[q - 1] = fv;
-                            const int fi = ti[q]; ti[q] = ti[q - 1]; ti[q - 1] = fi;
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < KM; ++q) { lv[tid][q] = tv[q]; li[tid][q] = ti[q]; }
-        lv[tid][KM] = -INFINITY; li[tid][KM] = 0x7fffffff;
-        int hp = 0;
-        const int lab = labels ? labels[row] : -1;
-        float h_acc = 0.f, n_acc = 0.f;
-        for (int kk = 0; kk < k; ++kk) {
-            float bv = lv[tid][hp];
-            int bi = li[tid][hp], bo = tid;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o);
-                const int oi = __shfl_xor(bi, o), oo = __shfl_xor(bo, o);
-                if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; bo = oo; }
-            }
-            __syncthreads();
-            if (lane == 0) { wv[wave] = bv; wi[wave] = bi; wo[wave] = bo; }
-            __syncthreads();
-            if (tid == 0) {
-                float fv = wv[0]; int fi = wi[0], fo = wo[0];
-                for (int w = 1; w < 4; ++w)
-                    if (better(wv[w], wi[w], fv, fi)) { fv = wv[w]; fi = wi[w]; fo = wo[w]; }
-                s_owner = fo;
-                topk_idx[row * k + kk] = fi == 0x7fffffff ? -1 : fi;
-                if (labels && fi == lab) {
-                    h_acc += 1.f;
-                    n_acc += 1.0f / (logf((float)(kk + 2)) / logf(2.0f));
-                }
-            }
-            __syncthreads();
-            if (tid == s_owner && hp < KM) ++hp;
-        }
-        if (tid == 0) {
-            if (hit) hit[row] = h_acc;
-            if (ndcg) ndcg[row] = n_acc;
-        }
-        __syncthreads();
-    }
+    constexpr bool EX = false;
+    constexpr const int32_t *excl = nullptr;
+    constexpr int ld_e = 0, E = 0;
+#include "topk_lists_body.inc"
+}
+template <typename T, int KM>
+__global__ void __launch_bounds__(256) topk_rows_lists_excl_kernel(const T *__restrict__ x, int ld, int64_t R, int V, int k,
+                                                             int32_t *__restrict__ topk_idx, const int32_t *__restrict__ labels,
+                                                             float *__restrict__ hit, float *__restrict__ ndcg,
+                                                             const int32_t *__restrict__ redo, const int32_t *__restrict__ excl,
+                                                             int ld_e, int E) {
+    constexpr bool EX = true;
+#include "topk_lists_body.inc"
 }
 
 // Fast path: threshold selection.  Pass 1 finds every thread's best element; k rounds of block arg-max over those 256
@@ -799,78 +770,19 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_rows_kernel(const T *__rest
                                                                  int32_t *__restrict__ topk_idx, const int32_t *__restrict__ labels,
                                                                  float *__restrict__ hit, float *__restrict__ ndcg,
                                                                  int32_t *__restrict__ redo) {
-    __shared__ float cv[TOPK_CAP];
-    __shared__ int ci[TOPK_CAP];
-    __shared__ float mv[TOPK_THREADS];
-    __shared__ int s_cnt;
-    __shared__ float s_tv;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nch = (V + 7) >> 3;
-    for (int64_t row = blockIdx.x; row < R; row += gridDim.x) {
-        const T *xr = x + row * ld;
-        // pass 1: per-thread maximum (values only; fmaxf drops NaNs).  Four loads in flight per thread.
-        float m = -INFINITY;
-        for (int c0 = tid; c0 < nch; c0 += 4 * TOPK_THREADS) {
-            float v[4][8];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int c = c0 + u * TOPK_THREADS;
-                Vec8<T>::load(xr + (c < nch ? c : c0) * 8, v[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int c = c0 + u * TOPK_THREADS;
-                if (c + 1 < nch) {           // whole chunk inside the row (the last chunk may hold pad columns)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) m = fmaxf(m, v[u][e]);
-                } else if (c < nch) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        if (c * 8 + e < V) m = fmaxf(m, v[u][e]);
-                }
-            }
-        }
-        mv[tid] = m;
-        if (tid == 0) s_cnt = 0;
-        __syncthreads();
-        if (wave == 0) {
-            // 64 maxima of disjoint element sets (lane l: threads l, l + 64, ...); the k-th largest of them is a lower
-            // bound of the row's k-th largest value: at least k elements are >= it
-            float g = mv[lane];
-#pragma unroll
-            for (int w = 1; w < TOPK_THREADS / 64; ++w) g = fmaxf(g, mv[lane + 64 * w]);
-            const int rank = wave_rank(g, lane, 64);
-            if (rank == k - 1) s_tv = g;      // ranks are a permutation of 0..63 (ties broken by lane)
-        }
-        __syncthreads();
-        const float tv = s_tv;
-        // Candidates = the elements >= tv.  A thread whose own maximum is below tv holds none, so only the few threads
-        // with m >= tv (about k of the 512) read their chunks again: the row is NOT read a second time.
-        if (m >= tv)
-        for (int c0 = tid; c0 < nch; c0 += 4 * TOPK_THREADS) {
-            float v[4][8];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int c = c0 + u * TOPK_THREADS;
-                Vec8<T>::load(xr + (c < nch ? c : c0) * 8, v[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int c = c0 + u * TOPK_THREADS;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int j = c * 8 + e;
-                    if (c < nch && j < V && v[u][e] >= tv) {
-                        const int pos = atomicAdd(&s_cnt, 1);
-                        if (pos < TOPK_CAP) { cv[pos] = v[u][e]; ci[pos] = j; }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        topk_select(cv, ci, s_cnt, k, row, tid, lane, wave, topk_idx, labels, hit, ndcg, redo);
-        __syncthreads();
-    }
+    constexpr bool EX = false;
+    constexpr const int32_t *excl = nullptr;
+    constexpr int ld_e = 0, E = 0;
+#include "topk_rows_body.inc"
+}
+template <typename T>
+__global__ void __launch_bounds__(TOPK_THREADS) topk_rows_excl_kernel(const T *__restrict__ x, int ld, int64_t R, int V, int k,
+                                                                      int32_t *__restrict__ topk_idx, const int32_t *__restrict__ labels,
+                                                                      float *__restrict__ hit, float *__restrict__ ndcg,
+                                                                      int32_t *__restrict__ redo, const int32_t *__restrict__ excl,
+                                                                      int ld_e, int E) {
+    constexpr bool EX = true;
+#include "topk_rows_body.inc"
 }
 
 // bf16, V <= 65536: the row stays in registers as raw bf16 pairs (NCH x 16 B per thread, all loads in flight at once), so the
@@ -1001,4 +913,37 @@ extern "C" int b4c_topk_rows_ws(const void *scores, int ld, int64_t R, int V, in
     else if (dtype == B4C_BF16) { TOPK_DISPATCH(bf16_t) }
     else B4C_REQUIRE(false, "topk_rows: dtype %d", dtype);
     return b4c_check_launch("topk_rows");
+}
+
+// the materialised ranking with per-row exclusion lists (b4c_exclusions_prep form): the threshold kernel (fp32 and bf16 alike:
+// the register-resident bf16 form has no exclusion variant), then the list kernel for the rows it flags.  `scores` is read only.
+extern "C" int b4c_topk_rows_excl(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx, const int32_t *labels,
+                                  float *hit, float *ndcg, int32_t *redo, int dtype, const int32_t *excl, int ld_e, int E,
+                                  void *stream) {
+    B4C_REQUIRE(E >= 0 && E <= B4C_MAX_EXCL, "topk_rows_excl: E = %d (0 .. %d)", E, B4C_MAX_EXCL);
+    B4C_REQUIRE(E == 0 || (excl && ld_e >= E), "topk_rows_excl: exclusion list (ld_e = %d, E = %d)", ld_e, E);
+    if (E == 0) return b4c_topk_rows_ws(scores, ld, R, V, k, topk_idx, labels, hit, ndcg, redo, dtype, stream);
+    B4C_REQUIRE(scores && topk_idx && R >= 0 && V > 0, "topk_rows_excl: bad argument");
+    B4C_REQUIRE(k >= 1 && k <= B4C_MAX_TOPK && k <= V, "topk_rows_excl: k=%d must be in [1, min(%d, V)]", k, B4C_MAX_TOPK);
+    B4C_REQUIRE(ld % 8 == 0 && ld >= V, "topk_rows_excl: pitch");
+    B4C_REQUIRE(dtype == B4C_F32 || dtype == B4C_BF16, "topk_rows_excl: dtype %d", dtype);
+    if (R == 0) return B4C_OK;
+    const int grid = (int)(R < 4096 ? R : 4096);
+    hipStream_t st = (hipStream_t)stream;
+    if (redo) {
+        const int g2 = (int)(R < 2048 ? R : 2048);
+        if (dtype == B4C_F32)
+            topk_rows_excl_kernel<float><<<g2, TOPK_THREADS, 0, st>>>((const float *)scores, ld, R, V, k, topk_idx, labels, hit, ndcg,
+                                                                      redo, excl, ld_e, E);
+        else
+            topk_rows_excl_kernel<bf16_t><<<g2, TOPK_THREADS, 0, st>>>((const bf16_t *)scores, ld, R, V, k, topk_idx, labels, hit, ndcg,
+                                                                       redo, excl, ld_e, E);
+    }
+#undef TOPK_LAUNCH
+#define TOPK_LAUNCH(T, KM) topk_rows_lists_excl_kernel<T, KM><<<grid, 256, 0, st>>>((const T *)scores, ld, R, V, k, topk_idx, labels, \
+                                                                                 hit, ndcg, redo, excl, ld_e, E)
+    if (dtype == B4C_F32) { TOPK_DISPATCH(float) }
+    else { TOPK_DISPATCH(bf16_t) }
+#undef TOPK_LAUNCH
+    return b4c_check_launch("topk_rows_excl");
 }

@@ -1367,219 +1367,41 @@ __global__ void __launch_bounds__(64) vce_label_logit_kernel(VceScanArgs a, floa
 // NH = 2: 256 tokens per workgroup, 8 token groups, every wave takes both halves in turn -- each W tile (32 KB by LDS-DMA
 // from L2 / Infinity Cache: the sweeps stream the whole of W once per token tile, 4.1 GB per sweep at C2, and that stream, not
 // the matrix pipe, paces them) serves twice the tokens.
+// The exclusion-aware sweeps (b4c_vocab_rank_excl / b4c_vocab_topk_excl): the same arguments plus every row's canonical list
+// (b4c_exclusions_prep: ids of [0, V) ascending, -1 after the last).  A separate type, so that the kernels without exclusions
+// keep their argument block and their code.
+struct VceScanExArgs : VceScanArgs {
+    const int32_t *excl;
+    int ld_e, E;
+};
+
+// Exclusions inside the sweep (EX = true).  Each lane owns one token and, of every half-tile it scores, the 32 vocabulary rows
+// base + 4 hf + 32 rt + (t & 3) + 8 (t >> 2) of its accumulator slots.  It walks its token's sorted list with a cursor: xn =
+// the next excluded id not yet passed, xq = the one after it (loaded one step ahead, so the walk never waits on its own load).
+// Once per half-tile, one compare and one __any: only when some lane's next id falls below the half-tile's end does the wave
+// take the branch that turns the lane's excluded entries into NaN -- before `entry` adds the bias and folds them.  NaN, not
+// -inf: no comparison of the sweeps holds for it (x > ref, x == ref, x >= tau with tau = -inf when fewer than k items
+// remain), and fmaxf drops it, so an excluded entry neither counts before the label, nor reaches a class maximum, nor is
+// collected.
+// the exclusion fields of either argument block (read in the EX = true parts of the body only)
+struct VceExView {
+    const int32_t *excl;
+    int ld_e, E;
+};
+__device__ __forceinline__ VceExView vce_ex(const VceScanArgs &) { return {nullptr, 0, 0}; }
+__device__ __forceinline__ VceExView vce_ex(const VceScanExArgs &a) { return {a.excl, a.ld_e, a.E}; }
+
+// The body is vce_scan_body.inc, included by both kernels: each is a kernel of its own, compiled as written (the form without
+// exclusions is the code it was before they existed).
 template <int KD, int OP, int NH>
 __global__ void __launch_bounds__(512, 2) vce_scan_kernel(VceScanArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NKS = KD / 16, STR = VTile<KD>::STR;
-    constexpr int TILE_B = VTile<KD>::BYTES;
-    float *sBias = reinterpret_cast<float *>(smem + 2 * TILE_B);     // [3][128]: a ring -- the scores of a tile's second half are
-                                                                     // formed one tile later, while the next bias arrives
-    const int unit = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hf = lane >> 5;
-    const int tg = NH == 2 ? wave : (wave & 3), vh = NH == 2 ? 0 : (wave >> 2);
-    const int64_t tok0 = (int64_t)(unit % a.ntt) * (128 * NH);
-    const int64_t tok = tok0 + tg * 32 + r;
-    const int part = unit / a.ntt;
-    const int nvt = (a.V + 127) >> 7;
-    const int vt0 = (int)((int64_t)nvt * part / a.parts), vt1 = (int)((int64_t)nvt * (part + 1) / a.parts);
-    const bool live = tok < a.R;
-
-    bf16x8 hfr[NKS];
-    vce_load_hfrag<KD>(a.h, a.ld_h, tok, a.R, hf, hfr);
-    int foff[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) foff[ks] = VTile<KD>::frag_off(r, ks, hf) + vh * 64 * STR;
-
-    // per-lane state
-    float ref = INFINITY;          // RANK: x_y;  COLLECT: tau  (+inf: nothing counts / nothing is collected)
-    int y = -1;
-    if (OP == SCAN_RANK && live) { ref = a.xy[tok]; y = a.labels[tok]; }
-    if (OP == SCAN_COLLECT && live) ref = a.tau[tok];
-    unsigned n_before = 0;         // RANK
-    float cm[16];                  // CLASSMAX
-#pragma unroll
-    for (int t = 0; t < 16; ++t) cm[t] = -INFINITY;
-
-    float breg = 0.f;
-    auto fetch = [&](int vt, int buf) {
-        VTile<KD>::template dma<512>(a.wt, a.ld_w, (int64_t)vt * 128, vt < vt1 ? a.V : 0, smem + buf * TILE_B, tid);
-        if (tid < 128) {
-            const int v = vt * 128 + tid;
-            breg = (vt < vt1 && v < a.V) ? (a.bias ? a.bias[v] : 0.f) : -INFINITY;   // rows past V: score = -inf
-        }
-    };
-    fetch(vt0, 0);
-    if (tid < 128) sBias[tid] = breg;
-    VCE_DMA_WAIT();
-    __syncthreads();
-
-    // One half-tile (64 vocabulary rows x the wave's 32 tokens) = 16 MFMAs into acc, then ~4 VALU instructions per entry
-    // on the result.  A VALU wave-instruction holds the SIMD's issue port for 4 cycles, an MFMA for 8 of its 32: run one
-    // after the other the two phases add up (measured: matrix pipe 36 % busy, VALU issue 43 %, sum 79 % of the kernel's
-    // cycles); interleaved -- the MFMA chain of one half-tile issued between the VALU instructions of the previous one --
-    // they overlap.  So the loop is software-pipelined by half a tile: `scores` of half-tile i runs inside the instruction
-    // stream of `chain` of half-tile i + 1 (sched_group_barrier pins the interleave), on two accumulator sets.
-    // one entry of a half-tile's scores: x = accumulator + bias (the bias last, as the materialising GEMM adds it; rows past
-    // V: -inf); RANK: count it if it beats x_y, note an equal one; CLASSMAX: the running maximum of its accumulator slot;
-    // COLLECT: note one that reaches tau
-    bool hot = false;
-    auto entry = [&](f32x16 (&acc)[2], int rt, int t, float bj) __attribute__((always_inline)) {
-        const float x = acc[rt][t] + bj;
-        acc[rt][t] = x;
-        if (OP == SCAN_RANK) {
-            n_before += x > ref ? 1u : 0u;
-            hot |= x == ref;
-        } else if (OP == SCAN_CLASSMAX) {
-            cm[t] = fmaxf(cm[t], x);
-        } else {
-            hot |= x >= ref;
-        }
-    };
-    // The 16 MFMAs of a half-tile's chain into accN, and -- WITH = true -- between them the scores of the half-tile before
-    // it (accP: 32 entries per lane, two per MFMA).  sched_barrier(0) after every MFMA's group pins the interleave (left to
-    // itself, or to sched_group_barrier, the compiler issues the sixteen MFMAs first and the VALU after them).
-    auto chain = [&](auto WITH, f32x16 (&accN)[2], const char *w, f32x16 (&accP)[2], const float *bs, int vhe) __attribute__((always_inline)) {
-        constexpr bool with = decltype(WITH)::value;
-        bf16x8 wfq[NKS];
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int t = 0; t < 16; ++t) accN[rt][t] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) wfq[ks] = *reinterpret_cast<const bf16x8 *>(w + foff[ks]);
-        hot = false;
-        // the eight bias quads of the previous half-tile are requested up front, with the first fragments: a quad requested
-        // where it is used parks the wave for a full LDS round trip (~130 cycles) sixteen times per tile
-        f32x4 bq[8];
-        if (with) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(bs + vhe * 64 + (q >> 2) * 32 + 8 * (q & 3) + 4 * hf);
-        }
-#pragma unroll
-        for (int i = 0; i < 2 * NKS; ++i) {
-            const int rt = i / NKS, ks = i % NKS;
-            __builtin_amdgcn_sched_barrier(0);
-            accN[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfq[ks], hfr[ks], accN[rt], 0, 0, 0);
-            if (rt == 0) wfq[ks] = *reinterpret_cast<const bf16x8 *>(w + 32 * STR + foff[ks]);
-            if (with) {
-                // entries 2 i, 2 i + 1 of the previous half-tile (NKS = 8: all 32; NKS = 4: the rest follows the chain)
-#pragma unroll
-                for (int e = 2 * i; e < 2 * i + 2; ++e) entry(accP, e >> 4, e & 15, bq[e >> 2][e & 3]);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (with && NKS < 8) {
-#pragma unroll
-            for (int e = 4 * NKS; e < 32; ++e) entry(accP, e >> 4, e & 15, bq[e >> 2][e & 3]);
-        }
-    };
-    // the scores of a half-tile on their own (NH = 1; the last half-tile of NH = 2)
-    auto scores = [&](f32x16 (&acc)[2], const float *bs, int vhe) __attribute__((always_inline)) {
-        hot = false;
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int tq = 0; tq < 4; ++tq) {
-                const f32x4 b4 = *reinterpret_cast<const f32x4 *>(bs + vhe * 64 + rt * 32 + 8 * tq + 4 * hf);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) entry(acc, rt, 4 * tq + k, b4[k]);
-            }
-    };
-    auto rare = [&](f32x16 (&acc)[2], int vt, int vhe) __attribute__((always_inline)) {       // the half-tile that holds the label / a candidate
-        const int row0 = vt * 128 + vhe * 64 + 4 * hf;
-        int slot = 0;
-        if (OP == SCAN_COLLECT) {          // the lane's candidates of this half-tile take consecutive slots: one atomic
-            int n = 0;
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                for (int t = 0; t < 16; ++t)
-                    n += (acc[rt][t] >= ref && row0 + rt * 32 + (t & 3) + 8 * (t >> 2) < a.V) ? 1 : 0;
-            if (n) slot = atomicAdd(a.cnt + tok, n);
-        }
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const int j = row0 + rt * 32 + (t & 3) + 8 * (t >> 2);
-                const float x = acc[rt][t];
-                if (OP == SCAN_RANK) {
-                    n_before += (x == ref && j < y) ? 1u : 0u;        // ties: the lower index ranks first
-                } else if (x >= ref && j < a.V) {
-                    if (slot < VCE_CAND) {
-                        a.cand_v[tok * VCE_CAND + slot] = x;
-                        a.cand_i[tok * VCE_CAND + slot] = j;
-                    }
-                    ++slot;
-                }
-            }
-    };
-    f32x16 accA[2], accB[2];
-    int vt_prev = vt0;
-    bool have_prev = false;
-    int bcur = 0, bprev = 2;           // bias ring slots of this tile and of the previous one; the next one's goes to the third
-#ifdef VCE_SCAN_STAMPS
-    unsigned long long st_[6] = {0, 0, 0, 0, 0, 0}, t0_ = __builtin_amdgcn_s_memtime();
-#endif
-    constexpr std::integral_constant<bool, true> YES{};
-    constexpr std::integral_constant<bool, false> NO{};
-    auto tile = [&](auto BUF, int vt) __attribute__((always_inline)) {
-        constexpr int buf = decltype(BUF)::value;
-        VCE_STAMP(5);
-        fetch(vt + 1, buf ^ 1);
-        VCE_STAMP(0);
-        const char *w = smem + buf * TILE_B;
-        const int bnext = 3 - bcur - bprev;
-        if (NH == 2) {
-            // accA <- half 0 of this tile, beside the scores of the previous tile's half 1 (accB)
-            if (have_prev) {
-                chain(YES, accA, w, accB, sBias + bprev * 128, 1);
-                if (OP != SCAN_CLASSMAX && __any(hot)) rare(accB, vt_prev, 1);
-            } else {
-                chain(NO, accA, w, accB, sBias, 0);
-            }
-            VCE_STAMP(1);
-            // accB <- half 1, beside the scores of half 0
-            chain(YES, accB, w + 64 * STR, accA, sBias + bcur * 128, 0);
-            if (OP != SCAN_CLASSMAX && __any(hot)) rare(accA, vt, 0);
-            VCE_STAMP(2);
-            have_prev = true;
-            vt_prev = vt;
-        } else {
-            chain(NO, accA, w, accB, sBias, 0);
-            scores(accA, sBias + bcur * 128, vh);
-            if (OP != SCAN_CLASSMAX && __any(hot)) rare(accA, vt, vh);
-        }
-        if (tid < 128) sBias[bnext * 128 + tid] = breg;
-        bprev = bcur;
-        bcur = bnext;
-        VCE_DMA_WAIT();
-        VCE_STAMP(3);
-        B4C_LDS_BARRIER();
-        VCE_STAMP(4);
-    };
-    for (int vt = vt0; vt < vt1; vt += 2) {
-        tile(std::integral_constant<int, 0>{}, vt);
-        if (vt + 1 < vt1) tile(std::integral_constant<int, 1>{}, vt + 1);
-    }
-    if (NH == 2 && have_prev) {          // the last half-tile's scores
-        scores(accB, sBias + bprev * 128, 1);
-        if (OP != SCAN_CLASSMAX && __any(hot)) rare(accB, vt_prev, 1);
-    }
-#ifdef VCE_SCAN_STAMPS
-    if (lane == 0 && blockIdx.x < 2048)
-        for (int k = 0; k < 6; ++k) g_vce_stamps[(blockIdx.x * 8 + wave) * 6 + k] = st_[k];
-#endif
-    if (!live) return;
-    if (OP == SCAN_RANK) {
-        if (n_before) atomicAdd(a.rank + tok, (int)n_before);          // integer adds: any order gives the same count
-    } else if (OP == SCAN_CLASSMAX) {
-        // sub-list index: (part, half of the tile, lane half) for NH = 1; (part, lane half) for NH = 2 (a.nsub_per_part of them)
-        const int sub = NH == 2 ? part * 2 + hf : part * 4 + vh * 2 + hf;
-        float *o = a.cm + ((int64_t)sub * a.R + tok) * 16;
-#pragma unroll
-        for (int tq = 0; tq < 4; ++tq) *reinterpret_cast<f32x4 *>(o + 4 * tq) = (f32x4){cm[4 * tq], cm[4 * tq + 1], cm[4 * tq + 2], cm[4 * tq + 3]};
-    }
+    constexpr bool EX = false;
+#include "vce_scan_body.inc"
+}
+template <int KD, int OP, int NH>
+__global__ void __launch_bounds__(512, 2) vce_scan_excl_kernel(VceScanExArgs a) {
+    constexpr bool EX = true;
+#include "vce_scan_body.inc"
 }
 
 // tau[row] = k-th largest of the row's nsub * 16 class maxima (one wave per row; k rounds of "take the maximum out")
@@ -1711,6 +1533,21 @@ static void vce_scan_launch(VceScanArgs a, int nh, hipStream_t st) {
     else vce_scan_kernel<KD, OP, 1><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(a);
 }
 
+template <int KD, int OP>
+static void vce_scan_excl_launch(VceScanExArgs a, int nh, hipStream_t st) {
+    const size_t lds = 2 * (size_t)VTile<KD>::BYTES + 3 * 128 * 4;
+    static thread_local bool done = false;
+    if (!done) { vce_allow_lds(vce_scan_excl_kernel<KD, OP, 1>, lds); vce_allow_lds(vce_scan_excl_kernel<KD, OP, 2>, lds); done = true; }
+    if (nh == 2) vce_scan_excl_kernel<KD, OP, 2><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(a);
+    else vce_scan_excl_kernel<KD, OP, 1><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(a);
+}
+
+static int vce_excl_check(const int32_t *excl, int ld_e, int E, const char *who) {
+    B4C_REQUIRE(E >= 0 && E <= B4C_MAX_EXCL, "%s: E = %d (0 .. %d)", who, E, B4C_MAX_EXCL);
+    B4C_REQUIRE(E == 0 || (excl && ld_e >= E), "%s: exclusion list (ld_e = %d, E = %d)", who, ld_e, E);
+    return B4C_OK;
+}
+
 extern "C" int b4c_vocab_rank(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *labels, int32_t *rank,
                               void *workspace, int64_t workspace_bytes, int64_t R, int V, int K, void *stream) {
     if (int rc = vce_scan_check(h, ld_h, wt, ld_w, workspace, workspace_bytes, R, V, K, "vocab_rank")) return rc;
@@ -1767,4 +1604,116 @@ extern "C" int b4c_vocab_topk(const void *h, int ld_h, const void *wt, int ld_w,
     if (K == 128) vce_scan_launch<128, SCAN_COLLECT>(a, nh, st); else vce_scan_launch<64, SCAN_COLLECT>(a, nh, st);
     vce_select_kernel<<<(unsigned)ceil_div64(R, 4), 256, 0, st>>>(a.cand_v, a.cand_i, a.cnt, R, V, k, idx, labels, hit, ndcg, overflow);
     return b4c_check_launch("vocab_topk");
+}
+
+// ---- exclusions: the canonical per-row list the *_excl entry points take --------------------------------------------------
+// one workgroup per row: ids outside [0, V) and the row's label become +inf keys, a bitonic sort in LDS orders them, the first
+// of every run of equal keys is kept (a scan gives its slot), -1 fills the rest of the row.
+__global__ void __launch_bounds__(B4C_MAX_EXCL) vce_excl_prep_kernel(const int32_t *__restrict__ in, int ld_in, int E, int V,
+                                                                     const int32_t *__restrict__ labels, int32_t *__restrict__ out) {
+    __shared__ int key[B4C_MAX_EXCL];
+    __shared__ int pos[B4C_MAX_EXCL];
+    const int tid = threadIdx.x, n = blockDim.x;           // n: a power of two >= E
+    const int64_t row = blockIdx.x;
+    const int y = labels ? labels[row] : -1;
+    int v = tid < E ? in[row * ld_in + tid] : -1;
+    key[tid] = (v >= 0 && v < V && v != y) ? v : 0x7fffffff;
+    __syncthreads();
+    for (int size = 2; size <= n; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const int other = tid ^ stride;
+            if (other > tid) {
+                const int a = key[tid], b = key[other];
+                const bool up = (tid & size) == 0;
+                if ((a > b) == up) { key[tid] = b; key[other] = a; }
+            }
+            __syncthreads();
+        }
+    v = key[tid];
+    const int first = (v != 0x7fffffff && (tid == 0 || key[tid - 1] != v)) ? 1 : 0;
+    pos[tid] = first;
+    __syncthreads();
+    for (int d = 1; d < n; d <<= 1) {          // inclusive scan of the "first of its run" flags
+        const int t = tid >= d ? pos[tid - d] : 0;
+        __syncthreads();
+        pos[tid] += t;
+        __syncthreads();
+    }
+    const int total = pos[n - 1];
+    __syncthreads();
+    if (first) key[pos[tid] - 1] = v;           // slots below `total` only: every thread has read its own key already
+    __syncthreads();
+    if (tid < E) out[row * (int64_t)E + tid] = tid < total ? key[tid] : -1;
+}
+
+extern "C" int b4c_exclusions_prep(const int32_t *ex_in, int ld_in, int64_t R, int E, int V, const int32_t *labels, int32_t *ex_out,
+                                   void *stream) {
+    B4C_REQUIRE(R >= 0 && V > 0 && E >= 0 && E <= B4C_MAX_EXCL, "exclusions_prep: R = %lld, E = %d (0 .. %d), V = %d", (long long)R, E,
+                B4C_MAX_EXCL, V);
+    if (R == 0 || E == 0) return B4C_OK;
+    B4C_REQUIRE(ex_in && ex_out && ld_in >= E, "exclusions_prep: null pointer or ld_in < E");
+    int n = 64;
+    while (n < E) n <<= 1;
+    vce_excl_prep_kernel<<<(unsigned)R, n, 0, (hipStream_t)stream>>>(ex_in, ld_in, E, V, labels, ex_out);
+    return b4c_check_launch("exclusions_prep");
+}
+
+extern "C" int b4c_vocab_rank_excl(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *labels,
+                                   int32_t *rank, void *workspace, int64_t workspace_bytes, int64_t R, int V, int K,
+                                   const int32_t *excl, int ld_e, int E, void *stream) {
+    if (int rc = vce_excl_check(excl, ld_e, E, "vocab_rank_excl")) return rc;
+    if (E == 0) return b4c_vocab_rank(h, ld_h, wt, ld_w, bias, labels, rank, workspace, workspace_bytes, R, V, K, stream);
+    if (int rc = vce_scan_check(h, ld_h, wt, ld_w, workspace, workspace_bytes, R, V, K, "vocab_rank_excl")) return rc;
+    B4C_REQUIRE(labels && rank, "vocab_rank_excl: null pointer");
+    if (R == 0) return B4C_OK;
+    hipStream_t st = (hipStream_t)stream;
+    VceScanExArgs a = {};
+    a.h = (const bf16_t *)h; a.wt = (const bf16_t *)wt; a.bias = bias; a.labels = labels; a.rank = rank;
+    a.ld_h = ld_h; a.ld_w = ld_w; a.R = R; a.V = V;
+    a.excl = excl; a.ld_e = ld_e; a.E = E;
+    const int nh = vce_scan_nh(R);
+    vce_scan_geometry(a, nh);
+    float *xy = (float *)workspace;
+    a.xy = xy;
+    if (K == 128) {
+        vce_label_logit_kernel<128><<<(unsigned)ceil_div64(R, 32), 64, 0, st>>>(a, xy, rank);
+        vce_scan_excl_launch<128, SCAN_RANK>(a, nh, st);
+    } else {
+        vce_label_logit_kernel<64><<<(unsigned)ceil_div64(R, 32), 64, 0, st>>>(a, xy, rank);
+        vce_scan_excl_launch<64, SCAN_RANK>(a, nh, st);
+    }
+    return b4c_check_launch("vocab_rank_excl");
+}
+
+extern "C" int b4c_vocab_topk_excl(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, int k, int32_t *idx,
+                                   const int32_t *labels, float *hit, float *ndcg, int32_t *overflow, void *workspace,
+                                   int64_t workspace_bytes, int64_t R, int V, int K, const int32_t *excl, int ld_e, int E,
+                                   void *stream) {
+    if (int rc = vce_excl_check(excl, ld_e, E, "vocab_topk_excl")) return rc;
+    if (E == 0)
+        return b4c_vocab_topk(h, ld_h, wt, ld_w, bias, k, idx, labels, hit, ndcg, overflow, workspace, workspace_bytes, R, V, K, stream);
+    if (int rc = vce_scan_check(h, ld_h, wt, ld_w, workspace, workspace_bytes, R, V, K, "vocab_topk_excl")) return rc;
+    B4C_REQUIRE(idx && overflow && k >= 1 && k <= B4C_MAX_TOPK, "vocab_topk_excl: k = %d (1 .. %d)", k, B4C_MAX_TOPK);
+    B4C_REQUIRE(!labels || (hit && ndcg), "vocab_topk_excl: labels need hit and ndcg");
+    hipStream_t st = (hipStream_t)stream;
+    (void)hipMemsetAsync(overflow, 0, 4, st);
+    if (R == 0) return B4C_OK;
+    VceScanExArgs a = {};
+    a.h = (const bf16_t *)h; a.wt = (const bf16_t *)wt; a.bias = bias;
+    a.ld_h = ld_h; a.ld_w = ld_w; a.R = R; a.V = V;
+    a.excl = excl; a.ld_e = ld_e; a.E = E;
+    const int nh = vce_scan_nh(R);
+    vce_scan_geometry(a, nh);
+    char *ws = (char *)workspace;
+    a.cm = (float *)ws;                         ws += (size_t)R * 32 * 16 * 4;
+    float *tau = (float *)ws;                   ws += (size_t)R * 4;
+    a.cnt = (int32_t *)ws;                      ws += (size_t)R * 4;
+    a.cand_v = (float *)ws;                     ws += (size_t)R * VCE_CAND * 4;
+    a.cand_i = (int32_t *)ws;
+    a.tau = tau;
+    if (K == 128) vce_scan_excl_launch<128, SCAN_CLASSMAX>(a, nh, st); else vce_scan_excl_launch<64, SCAN_CLASSMAX>(a, nh, st);
+    vce_tau_kernel<<<(unsigned)ceil_div64(R, 4), 256, 0, st>>>(a.cm, a.parts * (nh == 2 ? 2 : 4), R, k, tau, a.cnt);
+    if (K == 128) vce_scan_excl_launch<128, SCAN_COLLECT>(a, nh, st); else vce_scan_excl_launch<64, SCAN_COLLECT>(a, nh, st);
+    vce_select_kernel<<<(unsigned)ceil_div64(R, 4), 256, 0, st>>>(a.cand_v, a.cand_i, a.cnt, R, V, k, idx, labels, hit, ndcg, overflow);
+    return b4c_check_launch("vocab_topk_excl");
 }

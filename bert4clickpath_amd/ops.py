@@ -1051,15 +1051,68 @@ def _rank_workspace(h, R, V, K):
     return _workspace('vocab_rank', h.device, L.lib().b4c_vocab_rank_workspace_bytes(R, V, K))
 
 
-def vocab_rank(h, wt, bias, labels_i32, V):
+def exclusions(ex, V, labels=None):
+    """-> int32 [R, E] device tensor: the canonical per-row exclusion lists every `exclude=` of the ranking entry points takes
+    (b4c_exclusions_prep: the ids of [0, V) other than the row's label, ascending, no duplicates, then -1).
+    ex: an integer tensor [R, E] (negative entries: padding; out-of-range ids and duplicates are ignored) or a host list of R
+    lists of ids.  labels (int [R], optional): a row's label is never excluded.  E <= MAX_EXCL."""
+    if isinstance(ex, torch.Tensor):
+        if ex.dim() != 2:
+            raise B4CError('exclusions: an [R, E] tensor of item ids is needed, got shape %s' % (tuple(ex.shape),))
+        if ex.dtype.is_floating_point or ex.dtype.is_complex or ex.dtype == torch.bool:
+            raise B4CError('exclusions: item ids must be an integer tensor, got %s' % ex.dtype)
+        t = ex
+    else:
+        rows = [list(r) for r in ex]
+        E = max([len(r) for r in rows] + [0])
+        t = torch.full((len(rows), E), -1, dtype=torch.int64)
+        for i, r in enumerate(rows):
+            if r:
+                t[i, :len(r)] = torch.as_tensor(r, dtype=torch.int64)
+    R, E = t.shape
+    if E > L.MAX_EXCL:
+        raise B4CError('exclusions: %d ids per row; at most %d (B4C_MAX_EXCL)' % (E, L.MAX_EXCL))
+    if t.dtype != torch.int32:          # ids outside the int32 range cannot be items: mark them out of range before narrowing
+        t = torch.where((t >= 0) & (t < V), t, torch.full_like(t, -1)).to(torch.int32)
+    dev = t.device if t.is_cuda else (labels.device if isinstance(labels, torch.Tensor) and labels.is_cuda else torch.device('cuda'))
+    t = t.to(dev).contiguous()
+    lab = None
+    if labels is not None:
+        lab = torch.as_tensor(labels, device=dev).reshape(-1).to(torch.int32).contiguous()
+        if lab.shape[0] != R:
+            raise B4CError('exclusions: %d labels for %d rows' % (lab.shape[0], R))
+    out = torch.empty(R, E, dtype=torch.int32, device=dev)
+    if R and E:
+        L.check(L.lib().b4c_exclusions_prep(_p(t), t.stride(0), R, E, V, _p(lab), _p(out), _st()), 'exclusions_prep')
+    return out
+
+
+def _excl_args(exclude, R, who):
+    """(pointer, ld, E) of a canonical exclusion tensor (ops.exclusions) for R rows"""
+    if not isinstance(exclude, torch.Tensor) or exclude.dim() != 2 or exclude.dtype != torch.int32 or not exclude.is_cuda:
+        raise B4CError('%s: exclude must be the int32 [R, E] device tensor of ops.exclusions' % who)
+    if exclude.shape[0] != R or (exclude.shape[1] and exclude.stride(1) != 1):
+        raise B4CError('%s: exclude has %d rows (contiguous ids) for %d rows' % (who, exclude.shape[0], R))
+    return _p(exclude), max(exclude.stride(0), exclude.shape[1]), exclude.shape[1]
+
+
+def vocab_rank(h, wt, bias, labels_i32, V, exclude=None):
     """rank [R] int32 of the label among the V scores h wt^T + bias (items ranked before it; ties -> lower index first;
-    negative: no valid label).  The scores never exist in memory."""
+    negative: no valid label).  The scores never exist in memory.  exclude (ops.exclusions): items of a row's list do not
+    count (b4c_vocab_rank_excl)."""
     _cuda(h)
     R, K = h.shape
     rank = torch.empty(R, dtype=torch.int32, device=h.device)
+    if exclude is not None:
+        ex, ld_e, E = _excl_args(exclude, R, 'vocab_rank')
     if R == 0:
         return rank
     ws = _rank_workspace(h, R, V, K)
+    if exclude is not None:
+        with _record('vocab_rank', R * K * 2 + V * K * 2, 2 * R * V * K):
+            L.check(L.lib().b4c_vocab_rank_excl(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), _p(labels_i32), _p(rank),
+                                                ws.data_ptr(), ws.numel(), R, V, K, ex, ld_e, E, _st()), 'vocab_rank_excl')
+        return rank
     with _record('vocab_rank', R * K * 2 + V * K * 2, 2 * R * V * K):
         L.check(L.lib().b4c_vocab_rank(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), _p(labels_i32), _p(rank), ws.data_ptr(),
                                        ws.numel(), R, V, K, _st()), 'vocab_rank')
@@ -1076,12 +1129,15 @@ def rank_metrics(rank, k):
     return hit, ndcg
 
 
-def vocab_topk(h, wt, bias, V, k, labels_i32=None):
+def vocab_topk(h, wt, bias, V, k, labels_i32=None, exclude=None):
     """-> (idx [R, k] int32, hit, ndcg (when labels are given), overflow int32 [1]): the k best item ids of every row of
     h wt^T + bias in order, scores never in memory.  overflow[0] rows (ids -1) have too many ties at the selection
-    threshold: rank those on materialised scores."""
+    threshold: rank those on materialised scores.  exclude (ops.exclusions): a row's listed items are left out
+    (b4c_vocab_topk_excl; ids -1 past the items that remain)."""
     _cuda(h)
     R, K = h.shape
+    if exclude is not None:
+        ex, ld_e, E = _excl_args(exclude, R, 'vocab_topk')
     idx = torch.empty(R, k, dtype=torch.int32, device=h.device)
     hit = torch.empty(R, dtype=torch.float32, device=h.device) if labels_i32 is not None else None
     ndcg = torch.empty(R, dtype=torch.float32, device=h.device) if labels_i32 is not None else None
@@ -1089,6 +1145,12 @@ def vocab_topk(h, wt, bias, V, k, labels_i32=None):
     if R == 0:
         return idx, hit, ndcg, overflow.zero_()
     ws = _rank_workspace(h, R, V, K)
+    if exclude is not None:
+        with _record('vocab_topk', 2 * (R * K * 2 + V * K * 2), 4 * R * V * K):
+            L.check(L.lib().b4c_vocab_topk_excl(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), k, _p(idx), _p(labels_i32),
+                                                _p(hit), _p(ndcg), _p(overflow), ws.data_ptr(), ws.numel(), R, V, K, ex, ld_e, E,
+                                                _st()), 'vocab_topk_excl')
+        return idx, hit, ndcg, overflow
     with _record('vocab_topk', 2 * (R * K * 2 + V * K * 2), 4 * R * V * K):
         L.check(L.lib().b4c_vocab_topk(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), k, _p(idx), _p(labels_i32), _p(hit),
                                        _p(ndcg), _p(overflow), ws.data_ptr(), ws.numel(), R, V, K, _st()), 'vocab_topk')
@@ -1130,15 +1192,24 @@ class VocabSoftmaxFn(torch.autograd.Function):
 topk_threshold = True     # threshold-selection kernel (one HBM read per row); False: per-thread sorted lists only
 
 
-def topk_rows(scores, V, k, labels_i32=None):
+def topk_rows(scores, V, k, labels_i32=None, exclude=None):
+    """-> (idx [R, k] int32, hit, ndcg) of materialised scores [R, >= V] (fp32 / bf16).  exclude (ops.exclusions): a row's
+    listed items are left out (b4c_topk_rows_excl); `scores` is only read."""
     _cuda(scores)
     R, ld = scores.shape[0], scores.stride(0)
+    if exclude is not None:
+        ex, ld_e, E = _excl_args(exclude, R, 'topk_rows')
     idx = torch.empty(R, k, dtype=torch.int32, device=scores.device)
     hit = torch.empty(R, dtype=torch.float32, device=scores.device) if labels_i32 is not None else None
     ndcg = torch.empty(R, dtype=torch.float32, device=scores.device) if labels_i32 is not None else None
     if R == 0:
         return idx, hit, ndcg
     redo = torch.empty(R, dtype=torch.int32, device=scores.device) if topk_threshold else None
+    if exclude is not None:
+        with _record('topk_rows', R * ld * scores.element_size()):
+            L.check(L.lib().b4c_topk_rows_excl(_p(scores), ld, R, V, k, _p(idx), _p(labels_i32), _p(hit), _p(ndcg), _p(redo),
+                                               dt_code(scores.dtype), ex, ld_e, E, _st()), 'topk_rows_excl')
+        return idx, hit, ndcg
     with _record('topk_rows', R * ld * scores.element_size()):
         L.check(L.lib().b4c_topk_rows_ws(_p(scores), ld, R, V, k, _p(idx), _p(labels_i32), _p(hit), _p(ndcg), _p(redo),
                                          dt_code(scores.dtype), _st()), 'topk_rows')

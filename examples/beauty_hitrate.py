@@ -36,6 +36,8 @@ def main():
     ap.add_argument('--seed', type=int, default=4321)
     ap.add_argument('--eval_limit', type=int, default=None)
     ap.add_argument('--data', default=os.path.join(ROOT, 'data', 'beauty_sequences.npz'))
+    ap.add_argument('--exclude_seen', action='store_true',
+                    help='also report the filtered protocol: the held-out item ranked against the items absent from the history')
     a = ap.parse_args()
     from bert4clickpath_amd import input_pipeline, optim
     from bert4clickpath_amd.clickstream_transformer import transformer as T
@@ -57,16 +59,23 @@ def main():
             losses.append((step, float(loss.detach())))
     torch.cuda.synchronize()
     train_s = time.perf_counter() - t0
-    hits = ndcg = n = 0.0
+    from bert4clickpath_amd import cloze
+    hits = ndcg = n = fhits = fndcg = 0.0
     for b in data.eval_batches(1024, a.eval_limit):
         ids = torch.from_numpy(b['ids'])
         items = ids[:, 2:-1].contiguous().cuda()
-        _, h, nd = model.predict_topk({'asin': items}, 10, torch.from_numpy(b['labels']).cuda(),
-                                      flat_idx=torch.from_numpy(b['flat_idx']).cuda())
+        labels, flat = torch.from_numpy(b['labels']).cuda(), torch.from_numpy(b['flat_idx']).cuda()
+        _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat)
         hits += float(h.sum()); ndcg += float(nd.sum()); n += h.numel()
-    print(json.dumps({'what': 'Amazon Beauty, HIP path', 'dtype': a.dtype, 'steps': a.steps, 'batch': a.batch,
-                      'dropout': a.dropout, 'hitrate@10': 100.0 * hits / n, 'ndcg@10': 100.0 * ndcg / n, 'n_eval': int(n),
-                      'train_seconds': train_s, 'loss_curve': losses}))
+        if a.exclude_seen:          # one [MASK] (the last item) per sequence: the rows are the sequences, in order
+            _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, exclude=cloze.seen_items(items))
+            fhits += float(h.sum()); fndcg += float(nd.sum())
+    out = {'what': 'Amazon Beauty, HIP path', 'dtype': a.dtype, 'steps': a.steps, 'batch': a.batch,
+           'dropout': a.dropout, 'hitrate@10': 100.0 * hits / n, 'ndcg@10': 100.0 * ndcg / n, 'n_eval': int(n),
+           'train_seconds': train_s, 'loss_curve': losses}
+    if a.exclude_seen:
+        out.update({'filtered_hitrate@10': 100.0 * fhits / n, 'filtered_ndcg@10': 100.0 * fndcg / n})
+    print(json.dumps(out))
 
 
 if __name__ == '__main__':

@@ -38,6 +38,7 @@ extern "C" {
 
 #define B4C_MAX_FEATURES 4
 #define B4C_MAX_TOPK 16
+#define B4C_MAX_EXCL 1024   /* longest exclusion list per ranked row (b4c_exclusions_prep and the *_excl entry points) */
 
 #define B4C_ACT_NONE 0
 #define B4C_ACT_RELU 1
@@ -392,6 +393,30 @@ int b4c_topk_rows(const void *scores, int ld, int64_t R, int V, int k, int32_t *
  * rows with more than 1024 candidates (massive ties) are flagged there and redone by the list kernel.  Same results. */
 int b4c_topk_rows_ws(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx,
                      const int32_t *labels, float *hit, float *ndcg, int32_t *redo, int dtype, void *stream);
+
+/* ---- exclusions: rank / top-k over the items NOT in a per-row list (filtered evaluation, "not seen yet" serving) ----------
+ * A list belongs to one ranked row and holds item ids of the label space.  An excluded item is absent from that row's ranking:
+ * it is never among the ids and never counts before the label; every other item keeps its order (score descending, ties ->
+ * lower index) and its score (nothing is renormalised).  Fewer than k items left: the tail ids are -1.  The label itself is
+ * never excluded.
+ * b4c_exclusions_prep: ex_in [R][ld_in] int32, any ids (out of range, negative, duplicate: ignored) -> ex_out [R][E] in the
+ *   canonical form every *_excl entry point takes (and does not check again): the ids of [0, V) other than labels[r] (labels
+ *   may be NULL), ascending, no duplicates, then -1.  E <= B4C_MAX_EXCL (one workgroup per row, sorted in LDS).
+ * b4c_vocab_rank_excl / b4c_vocab_topk_excl: b4c_vocab_rank / b4c_vocab_topk of the excluded scores; the lists act inside the
+ *   sweeps (an excluded entry reaches neither a class maximum nor the candidates nor the count), so the threshold is that of
+ *   the items that remain.  Rows with mass ties are still handed back with ids -1 and counted in overflow[0].
+ * b4c_topk_rows_excl: b4c_topk_rows_ws on materialised scores (fp32 probabilities / logits, bf16) with the lists; `scores` is
+ *   only read.  redo may be NULL (per-thread-list kernel for every row).
+ * E == 0: the entry points without exclusions, unchanged. */
+int b4c_exclusions_prep(const int32_t *ex_in, int ld_in, int64_t R, int E, int V, const int32_t *labels, int32_t *ex_out, void *stream);
+int b4c_vocab_rank_excl(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *labels, int32_t *rank,
+                        void *workspace, int64_t workspace_bytes, int64_t R, int V, int K, const int32_t *excl, int ld_e, int E,
+                        void *stream);
+int b4c_vocab_topk_excl(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, int k, int32_t *idx,
+                        const int32_t *labels, float *hit, float *ndcg, int32_t *overflow, void *workspace, int64_t workspace_bytes,
+                        int64_t R, int V, int K, const int32_t *excl, int ld_e, int E, void *stream);
+int b4c_topk_rows_excl(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx, const int32_t *labels, float *hit,
+                       float *ndcg, int32_t *redo, int dtype, const int32_t *excl, int ld_e, int E, void *stream);
 
 /* ---- R16: Adam (Keras semantics, eps outside the sqrt) ------------------------------------
  * replaces tf.keras.optimizers.Adam(1e-3, .9, .999, 1e-9) (main.py:87), dense update over a flat
