@@ -146,9 +146,10 @@ __global__ void __launch_bounds__(512, 1) ao_bwd_kernel(AoBwdArgs a) {
     auto tile = [&](int slot, int64_t t) {
         const bool body = t < t1;
         if (body) {
+            // (tests/test_vmcnt_accounting.py checks both counts in the assembly: attn_out_bwd.second, attn_out_bwd.steady)
             if (t == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (t == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+            else if (t == 1) asm volatile("s_waitcnt vmcnt(2) ; vmcheck attn_out_bwd.second" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(3) ; vmcheck attn_out_bwd.steady" ::: "memory");
             // ---- LayerNorm + dropout backward of this thread's 8 columns of row orow (rowops.hip add_ln_bwd_kernel) ----
             const int64_t tk = (gfirst + t * gstep) * DD_TOK + orow;
             const bool live = tk < a.M;

@@ -241,9 +241,10 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
         dd_u32x4 &dz_cur = odd_tile ? dz1 : dz0;
         dd_u32x4 &dz_prev = odd_tile ? dz0 : dz1;
         if (body) {
+            // (tests/test_vmcnt_accounting.py checks both counts in the assembly: ffn_bwd.second, ffn_bwd.steady)
             if (t == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (t == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+            else if (t == 1) asm volatile("s_waitcnt vmcnt(2) ; vmcheck ffn_bwd.second" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(3) ; vmcheck ffn_bwd.steady" ::: "memory");
             // ---- LayerNorm + dropout backward of this thread's 8 columns of row orow (rowops.hip add_ln_bwd_kernel) ----
             const int64_t tk = (gfirst + t * gstep) * DD_TOK + orow;
             const bool live = tk < a.M;

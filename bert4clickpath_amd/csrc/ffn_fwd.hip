@@ -136,7 +136,8 @@ __global__ void __launch_bounds__(512, 4) ffn_fwd_kernel(FfnFwdArgs a) {
     for (int64_t t = 0; t <= t1; ++t) {
         const bool body = t < t1;
         const int slot = (int)(t & 3);
-        if (body) { if (t < 3) asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
+        // (tests/test_vmcnt_accounting.py checks both counts in the assembly: ffn_fwd.first, ffn_fwd.steady)
+        if (body) { if (t < 3) asm volatile("s_waitcnt vmcnt(1) ; vmcheck ffn_fwd.first" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6) ; vmcheck ffn_fwd.steady" ::: "memory"); }
         __syncthreads();                                // x(t) landed for every wave; the staged y of tile t - 1 complete, its h image read
         if (body) {
             // ---- h = relu(x W1^T + b1): this wave's 16 hidden columns x 32 tokens ----

@@ -119,7 +119,10 @@ __global__ void __launch_bounds__(512, 1) gemm_dxdw_kernel(DxDwArgs a) {
     fetch(t0 + 1, 1);
     fetch(t0 + 2, 2);
     // (1 + NG) DMA instructions per thread and tile; the first tile must have landed: all but the two younger ones' are waited for
-    if (NG == 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else if (NG == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    // (tests/test_vmcnt_accounting.py checks every hand-counted wait of this file in the assembly: dxdw.prologue, .steady, .first)
+    if (NG == 3) asm volatile("s_waitcnt vmcnt(8) ; vmcheck dxdw.prologue" ::: "memory");
+    else if (NG == 2) asm volatile("s_waitcnt vmcnt(6) ; vmcheck dxdw.prologue" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(4) ; vmcheck dxdw.prologue" ::: "memory");
     __syncthreads();
     // ---- pipeline of one tile: [DMA of tile t + 3] [everything older landed?] [dX rows of tile t - 1: staged tile + residual ->
     // global] [residual chunk of this tile requested] [dW, dX of tile t -> staged] [barrier].  ONE barrier per tile: the staged dX tile
@@ -129,9 +132,9 @@ __global__ void __launch_bounds__(512, 1) gemm_dxdw_kernel(DxDwArgs a) {
     // issued AFTER the one waited for.
     const int orow = tid >> 4, opart = tid & 15;
     constexpr int ND = 1 + NG;                          // DMA requests per thread and tile
-#define DD_WAIT_VM(n) do { switch (n) { case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break; case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break; \
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break; case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break; \
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break; case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break; \
+#define DD_WAIT_VM(n) do { switch (n) { case 4: asm volatile("s_waitcnt vmcnt(4) ; vmcheck dxdw.first" ::: "memory"); break; case 5: asm volatile("s_waitcnt vmcnt(5) ; vmcheck dxdw.first" ::: "memory"); break; \
+        case 6: asm volatile("s_waitcnt vmcnt(6) ; vmcheck dxdw.first" ::: "memory"); break; case 7: asm volatile("s_waitcnt vmcnt(7) ; vmcheck dxdw.first" ::: "memory"); break; \
+        case 8: asm volatile("s_waitcnt vmcnt(8) ; vmcheck dxdw.first" ::: "memory"); break; case 9: asm volatile("s_waitcnt vmcnt(9) ; vmcheck dxdw.first" ::: "memory"); break; \
         default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break; } } while (0)
     // The residual chunk of a tile lands in LDS too (LDS-DMA, 16 B per thread at thread * 16; the thread reads back its own piece, so
     // the issuing wave's counted wait is all the ordering it needs).  It landed in REGISTERS first (an inline-assembly global load
@@ -188,9 +191,9 @@ __global__ void __launch_bounds__(512, 1) gemm_dxdw_kernel(DxDwArgs a) {
 #endif
         fetch(t + 3, (slot + 3) % DD_RING);             // that stage held tile t - 1: every wave is past it (the barrier below)
         if (t > t0) {
-            if (ND == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if (ND == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            if (ND == 4) asm volatile("s_waitcnt vmcnt(4) ; vmcheck dxdw.steady" ::: "memory");
+            else if (ND == 3) asm volatile("s_waitcnt vmcnt(3) ; vmcheck dxdw.steady" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(2) ; vmcheck dxdw.steady" ::: "memory");
             store_rows(t - 1, sOut + ((slot + 1) & 1) * (DD_TOK * DD_OSTR));      // the dX rows of tile t - 1 leave now
         }
         res_load(t);

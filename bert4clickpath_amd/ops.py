@@ -466,10 +466,12 @@ def _gemm_tn_impl(a, g, K, N, want_bias, into):
 fused_dxdw = int(os.environ.get('B4C_FUSED_DXDW', '3'))
 
 
-def dxdw_supported(x, g, n_seg):
-    """bf16, 128-wide layer input, gradient of 128 x n_seg columns (n_seg 1 to 3), rows the kernels' 16-B accesses can take"""
+def dxdw_supported(x, g, n_seg, residual=None):
+    """bf16, 128-wide layer input, gradient of 128 x n_seg columns (n_seg 1 to 3), rows the kernels' 16-B accesses can take; a
+    residual's chunks are addressed with 32-bit byte offsets (b4c_gemm_dxdw refuses M * pitch * 2 >= 2^32)"""
     return x.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and x.shape[1] == 128 and n_seg in (1, 2, 3) and \
-        g.shape[1] == 128 * n_seg and x.stride(0) % 8 == 0 and g.stride(0) % 8 == 0 and x.shape[0] >= 4096
+        g.shape[1] == 128 * n_seg and x.stride(0) % 8 == 0 and g.stride(0) % 8 == 0 and x.shape[0] >= 4096 and \
+        (residual is None or x.shape[0] * residual.stride(0) * 2 < (1 << 32))
 
 
 def gemm_dxdw(x, g, wc, dWs, dbs, residual=None):
@@ -500,8 +502,9 @@ def ffn_bwd_shape_ok(x, h, z):
 
 
 def ffn_bwd_supported(x, h, z):
-    """... and enough rows for a persistent kernel (below 4,096 the five kernels are launched)"""
-    return ffn_bwd_shape_ok(x, h, z) and x.shape[0] >= 4096
+    """... and enough rows for a persistent kernel (below 4,096 the five kernels are launched), fewer than 2^24 (b4c_ffn_bwd addresses
+    its row chunks with 32-bit byte offsets)"""
+    return ffn_bwd_shape_ok(x, h, z) and 4096 <= x.shape[0] < (1 << 24)
 
 
 def ffn_bwd(dout, z, stats, gamma, rate, seed, h, x, wc2, wc1, F, dW1, db1, dW2, db2, dgamma, dbeta):
@@ -550,7 +553,7 @@ fused_attn_out_bwd = os.environ.get('B4C_FUSED_ATTN_OUT_BWD', '1') != '0'
 
 def attn_out_bwd_supported(o, z):
     return o.dtype == torch.bfloat16 and z.dtype == torch.bfloat16 and o.shape[1] == 128 and z.shape[1] == 128 and \
-        o.stride(0) % 8 == 0 and z.is_contiguous() and o.shape[0] >= 4096
+        o.stride(0) % 8 == 0 and z.is_contiguous() and 4096 <= o.shape[0] < (1 << 24)     # (32-bit byte offsets of the row chunks)
 
 
 def attn_out_bwd(dout, z, stats, gamma, rate, seed, o, wc, dW, db, dgamma, dbeta):
@@ -1488,7 +1491,7 @@ class AttnBlockFn(torch.autograd.Function):
                 d_o = gemm_nt(dy, wc_o, d)
         with _timed('attn_bwd'):
             dqkv = attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, ctx.cu, actx)
-        if routes and fused_dxdw and dxdw_supported(x, dqkv, 3):
+        if routes and fused_dxdw and dxdw_supported(x, dqkv, 3, residual=dz):
             # dX and dW | db of the fused Q | K | V projection in one pass over dqkv (csrc/gemm_dxdw.hip)
             dx = gemm_dxdw(x, dqkv, wc_qkv, [gwq, gwk, gwv], [gbq, gbk, gbv], residual=dz)
             _ready(wq, bq, wk, bk, wv, bv)
