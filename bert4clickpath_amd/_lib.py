@@ -14,6 +14,7 @@ ACT_NONE, ACT_RELU = 0, 1
 CE_TF, CE_PLAIN = 0, 1
 MAX_FEATURES, MAX_TOPK = 4, 16
 MAX_EXCL = 1024       # B4C_MAX_EXCL: longest exclusion list per ranked row
+MAX_CAND = 1024       # B4C_MAX_CAND: longest candidate list per row
 
 
 class B4CError(RuntimeError):
@@ -136,6 +137,9 @@ def lib():
             'b4c_vocab_rank_excl': (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, i32, vp]),
             'b4c_vocab_topk_excl': (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, i32, vp]),
             'b4c_topk_rows_excl': (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp]),
+            'b4c_sample_candidates': (i32, [vp, i64, i32, i32, u64, i64, vp, i32, i32, vp, vp, i32, vp, vp]),
+            'b4c_candidate_score': (i32, [vp, i32, vp, i32, vp, vp, i32, i64, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp]),
+            'b4c_candidate_rank_rows': (i32, [vp, i32, i32, vp, i32, i64, i32, i32, vp, vp, i32, vp, vp]),
             'b4c_adam_step': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
             'b4c_adam_rows': (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, i32, f32, f32, f32, f32, i32, vp]),
             'b4c_dropout': (i32, [vp, vp, i64, f32, u64, i32, vp]),

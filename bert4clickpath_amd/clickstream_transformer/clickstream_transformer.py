@@ -416,14 +416,20 @@ class ClickstreamTransformer(nn.Module):
         return loss
 
     @torch.no_grad()
-    def predict_topk(self, inputs, k, labels=None, flat_idx=None, packed=None, n_real_tokens=None, exclude=None):
+    def predict_topk(self, inputs, k, labels=None, flat_idx=None, packed=None, n_real_tokens=None, exclude=None, candidates=None):
         """Top-k item ids (label space) at every masked position, ranked over all V items: the fp32 path ranks the fp32
         probabilities as the reference's metrics do (utils.py:176, 245), the bf16 path the fp32 logits (head.SoftMaxHead.topk);
         returns (topk_idx (R,k) int32, hit (R,), ndcg (R,)) -- the latter two when labels are given.
         exclude: items (label space) left out of the ranking -- an integer tensor padded with negative ids, or a host list of
         lists: (R, E) one list per masked row in row-major order, or (B, E) one per sequence, for each of its [MASK] rows (a
         first dimension equal to R is read per row).  An excluded item is never returned and never ranks before the label;
-        the label itself is never excluded; fewer than k items left: ids -1."""
+        the label itself is never excluded; fewer than k items left: ids -1.
+        candidates: the ranking is limited to a list of items per row (label space; < 0 or >= V: absent) -- an integer tensor
+        (R, C) one list per masked row, or (B, C) one per sequence, C <= 1024 (cloze.sample_candidates for the sampled-negative
+        protocol); the fp32 logits of the listed items are ranked, the label counts only where it is listed, and hit / ndcg
+        come from the label's rank among the listed items.  Not together with exclude."""
+        if candidates is not None and exclude is not None:
+            raise B4CError('predict_topk: candidates and exclude together; leave excluded items out of the lists')
         rows, _ = self._masked_rows(inputs, False, flat_idx, pack=self._use_packed(inputs, packed, n_real_tokens),
                                     n_real_tokens=n_real_tokens)
         lab = None
@@ -435,7 +441,14 @@ class ClickstreamTransformer(nn.Module):
         ex = None
         if exclude is not None:
             ex = self._row_exclusions(exclude, rows.shape[0], rows.device, lab)
-        if hasattr(self.head, 'topk'):           # logits-free where the head's kernels cover it (head.SoftMaxHead.topk)
+        if candidates is not None:
+            cand = self._row_candidates(candidates, rows.shape[0], rows.device, 'predict_topk')
+            if hasattr(self.head, 'score_candidates'):
+                _, rank, idx = self.head.score_candidates(rows, cand, lab, k, want_scores=False)
+            else:
+                rank, idx = ops.candidate_rank_rows(self.head.logits(rows, out_fp32=True), self.head.output_vocab_size, cand, lab, k)
+            hit, ndcg = ops.rank_metrics(rank, k) if rank is not None else (None, None)
+        elif hasattr(self.head, 'topk'):           # logits-free where the head's kernels cover it (head.SoftMaxHead.topk)
             idx, hit, ndcg = self.head.topk(rows, k, lab, exclude=ex)
         else:
             scores = self.head.logits(rows, out_fp32=True)
@@ -450,6 +463,40 @@ class ClickstreamTransformer(nn.Module):
                 ops.poison_rows(hit.view(-1, 1), flag)
                 ops.poison_rows(ndcg.view(-1, 1), flag)
         return idx, hit, ndcg
+
+    @torch.no_grad()
+    def score_candidates(self, inputs, candidates, labels=None, flat_idx=None, packed=None, n_real_tokens=None):
+        """fp32 logits (R, C) of each [MASK] row's own candidate list (label-space ids; an id < 0 or >= V is absent and scores
+        NaN): the head's projection at the listed items only (head.SoftMaxHead.score_candidates, b4c_candidate_score).
+        candidates: an integer tensor (R, C) one list per masked row in row-major order, or (B, C) one per sequence, C <= 1024.
+        labels are not needed for the scores; they are accepted as predict_topk accepts them (and ignored)."""
+        rows, _ = self._masked_rows(inputs, False, flat_idx, pack=self._use_packed(inputs, packed, n_real_tokens),
+                                    n_real_tokens=n_real_tokens)
+        cand = self._row_candidates(candidates, rows.shape[0], rows.device, 'score_candidates')
+        if hasattr(self.head, 'score_candidates'):
+            scores, _, _ = self.head.score_candidates(rows, cand)
+        else:
+            raise B4CError('score_candidates: the head %s has no vocabulary projection to score items with' % type(self.head).__name__)
+        if self._packed is not None and n_real_tokens is not None:
+            ops.poison_rows(scores, self._packed.ids_packed)      # contradicted token count: NaN rows (no read-back)
+        return scores
+
+    def _row_candidates(self, candidates, R, device, who):
+        """(R, C) or (B, C) integer candidate lists -> int32 (R, C) on the device, one list per masked row"""
+        c = torch.as_tensor(candidates)
+        if c.dim() != 2 or c.dtype.is_floating_point or c.dtype == torch.bool:
+            raise B4CError('%s: candidates must be an integer (R, C) or (B, C) tensor, got %s %s' % (who, c.dtype, tuple(c.shape)))
+        if c.dtype != torch.int32:          # ids outside the int32 range cannot be items: absent
+            c = torch.where((c >= 0) & (c < self.head.output_vocab_size), c, torch.full_like(c, -1)).to(torch.int32)
+        c = c.to(device)
+        if c.shape[0] != R:
+            offsets = self._row_offsets
+            if offsets is None or c.shape[0] != offsets.shape[0] - 1:
+                raise B4CError('%s: candidates have %d lists for %d masked rows%s' % (
+                    who, c.shape[0], R, '' if offsets is None else ' of %d sequences' % (offsets.shape[0] - 1)))
+            seq = torch.searchsorted(offsets[1:].long(), torch.arange(R, device=device), right=True)
+            c = c[seq]
+        return c.contiguous()
 
     def _row_exclusions(self, exclude, R, device, lab):
         """predict_topk's `exclude` -> the canonical (R, E) lists of ops.exclusions, one per masked row"""

@@ -133,6 +133,24 @@ class SoftMaxHead(nn.Module):
                 scores = ops.softmax_rows(scores, V)
             return ops.topk_rows(scores, V, k, labels_i32, exclude=exclude)
 
+    def score_candidates(self, x2d, cand, labels=None, k=0, trunk_done=False, want_scores=True):
+        """-> (scores fp32 [R, C] or None, rank int32 [R] or None, idx int32 [R, k] or None): the fp32 logits of each row's own
+        candidate list cand (int32 [R, C], label-space ids; < 0 or >= V: absent, NaN score) and, from the same pass, the rank
+        of labels (int32 [R]) among the listed items and the k best listed items (ops.candidate_scores; b4c_candidate_score).
+        fp32 and bf16, any projection input width that is a multiple of 8 (up to 1024); the operands are the head's packed
+        projection (untied, tied to the item table, or the sampled head's full table)."""
+        if not self._built():
+            self.build(x2d.shape[-1])
+            self.to(x2d.device)
+        with torch.no_grad():
+            h = x2d if trunk_done else self.trunk(x2d)
+            K, _, _ = self._proj()
+            if K % 8 or h.shape[1] != K:
+                raise ops.B4CError('score_candidates: the projection input is %d wide; the candidate kernels need a multiple '
+                                   'of 8' % K)
+            wt, _, b = self._packs[-1].get(h.dtype, K, False)
+            return ops.candidate_scores(h, wt, b, cand, self.output_vocab_size, labels, k, want_scores)
+
     def forward(self, inputs, **kwargs):
         """inputs (B, M, d) -> probabilities (B, M, V), materialised as the reference does."""
         shp = inputs.shape
@@ -172,19 +190,34 @@ class ClozeScores:
         wt, _, b = self.head._packs[-1].get(self.h2d.dtype, K, False)
         return wt, b
 
-    def rank_of(self, labels_i32, exclude=None):
+    def rank_of(self, labels_i32, exclude=None, candidates=None):
         """items ranked before the label, per row (ties -> lower index first); negative where the label is a pad.
-        exclude (ops.exclusions, one list per row): listed items do not count."""
-        key = (labels_i32.data_ptr(), labels_i32._version, tuple(labels_i32.shape),
-               None if exclude is None else (exclude.data_ptr(), exclude._version, tuple(exclude.shape)))
+        exclude (ops.exclusions, one list per row): listed items do not count.
+        candidates (int32 [R, C] device, label-space ids): the rank among the row's listed items only (b4c_candidate_score)."""
+        def tkey(t):
+            return None if t is None else (t.data_ptr(), t._version, tuple(t.shape))
+        key = (labels_i32.data_ptr(), labels_i32._version, tuple(labels_i32.shape), tkey(exclude), tkey(candidates))
         if self._rank is None or self._rank[0] != key:
-            wt, b = self._operands()
-            self._rank = (key, ops.vocab_rank(self.h2d, wt, b, labels_i32, self.head.output_vocab_size, exclude=exclude),
-                          labels_i32, exclude)
+            if candidates is not None:
+                if exclude is not None:
+                    raise ops.B4CError('rank_of: candidates and exclude together; leave excluded items out of the lists')
+                _, rank, _ = self.head.score_candidates(self.h2d, candidates, labels_i32, trunk_done=True, want_scores=False)
+            else:
+                wt, b = self._operands()
+                rank = ops.vocab_rank(self.h2d, wt, b, labels_i32, self.head.output_vocab_size, exclude=exclude)
+            self._rank = (key, rank, labels_i32, exclude, candidates)
         return self._rank[1]
 
-    def topk(self, k, labels_i32=None, exclude=None):
-        return self.head.topk(self.h2d, k, labels_i32, trunk_done=True, exclude=exclude)
+    def topk(self, k, labels_i32=None, exclude=None, candidates=None):
+        """-> (ids [R, k], hit, ndcg): over all V items, or over each row's candidate list (candidates: int32 [R, C]; ids -1
+        past the listed items; hit / ndcg from the label's rank among the listed items, b4c_rank_metrics)"""
+        if candidates is None:
+            return self.head.topk(self.h2d, k, labels_i32, trunk_done=True, exclude=exclude)
+        if exclude is not None:
+            raise ops.B4CError('topk: candidates and exclude together; leave excluded items out of the lists')
+        _, rank, idx = self.head.score_candidates(self.h2d, candidates, labels_i32, k, trunk_done=True, want_scores=False)
+        hit, ndcg = ops.rank_metrics(rank, k) if rank is not None else (None, None)
+        return idx, hit, ndcg
 
     def probabilities(self):
         """the (B, M, V) tensor this object stands for: what the head returns when called as the reference calls it"""

@@ -65,6 +65,78 @@ def _row_exclusions(exclude, n_rows, y_true, V, lab, device):
     return ops.exclusions(ex, V, lab)
 
 
+def item_counts(ids, V, label_offset=NUM_RESERVED_TOKENS):
+    """int64 [V] counts of each label-space item (input id - label_offset) among input ids -- the training split's, for the
+    popularity sampler of sample_candidates.  Reserved tokens, padding and ids past the vocabulary are not counted."""
+    t = torch.as_tensor(ids)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError('item_counts: integer item ids are needed, got %s' % t.dtype)
+    V = int(V)
+    if V <= 0:
+        raise ValueError('item_counts: V = %d' % V)
+    t = t.reshape(-1).to(torch.int64) - int(label_offset)
+    t = t[(t >= 0) & (t < V)]
+    return torch.bincount(t.cpu(), minlength=V).to(torch.int64)
+
+
+def _labels_i32(y_true, device):
+    yt = torch.as_tensor(y_true, device=device).reshape(-1)
+    valid = yt != LABEL_PAD
+    return torch.where(valid, yt, torch.full_like(yt, -1)).to(torch.int32).contiguous(), valid
+
+
+def sample_candidates(y_true, num_negatives=100, exclude=None, item_counts=None, seed=0, row_base=0, num_items=None):
+    """(R, 1 + N) int32 device candidate lists for the flattened rows of y_true (R = y_true.numel(), (B, M) padded with -1):
+    column 0 the label, then num_negatives distinct items of [0, V) that are neither the label nor excluded -- the BERT4Rec
+    paper's protocol (100 negatives ranked with the held-out item).  item_counts (int [V], e.g. item_counts() of the training
+    split): drawn by popularity, items of count 0 never; None: uniform over num_items = V items.  exclude: (B, E) per sequence
+    or (R, E) per row (cloze.seen_items), as update_state's.  Rows of a pad label are -1 throughout.  ops.sample_candidates
+    (b4c_sample_candidates) with seed and row_base: the lists are a pure function of (seed, row_base + row, ...), so a
+    data-parallel rank passes the global index of its first row as row_base."""
+    cdf = None
+    if item_counts is not None:
+        cnt = torch.as_tensor(item_counts)
+        if cnt.dim() != 1 or cnt.dtype.is_floating_point or cnt.dtype == torch.bool:
+            raise ValueError('sample_candidates: item_counts must be an integer [V] tensor')
+        cnt = cnt.to(torch.int64)
+        if num_items is not None and int(num_items) != cnt.shape[0]:
+            raise ValueError('sample_candidates: %d item counts for num_items = %d' % (cnt.shape[0], num_items))
+        if bool((cnt < 0).any()) or int(cnt.sum()) <= 0:
+            raise ValueError('sample_candidates: item counts must be >= 0 with a positive total')
+        V = cnt.shape[0]
+        cdf = torch.cumsum(cnt, 0)
+    elif num_items is None:
+        raise ValueError('sample_candidates: give item_counts (popularity) or num_items (uniform)')
+    else:
+        V = int(num_items)
+    dev = torch.device('cuda')
+    lab, _ = _labels_i32(y_true, dev)
+    ex = None if exclude is None else _row_exclusions(exclude, lab.shape[0], y_true, V, lab, dev)
+    cand, _ = ops.sample_candidates(lab, V, num_negatives, seed, row_base, exclude=ex,
+                                    item_cdf=None if cdf is None else cdf.to(dev))
+    return cand
+
+
+def _cand_key(c):
+    return None if c is None else (c.data_ptr(), c._version, tuple(c.shape), c.dtype)
+
+
+def _row_candidates(candidates, n_rows, y_true, device):
+    """update_state's `candidates` -> int32 (rows, C) device lists: (B*M, C) per row, or (B, C) per sequence of a (B, M) y_true"""
+    c = torch.as_tensor(candidates)
+    if c.dim() != 2 or c.dtype.is_floating_point or c.dtype == torch.bool:
+        raise ValueError('candidates must be an integer (rows, C) or (B, C) tensor, got %s %s' % (c.dtype, tuple(c.shape)))
+    if c.dtype != torch.int32:
+        c = torch.where((c >= 0) & (c < (1 << 31)), c, torch.full_like(c, -1)).to(torch.int32)
+    c = c.to(device)
+    if c.shape[0] != n_rows:
+        yt = torch.as_tensor(y_true)
+        if yt.dim() != 2 or c.shape[0] != yt.shape[0]:
+            raise ValueError('candidates have %d lists for %d rows' % (c.shape[0], n_rows))
+        c = c.repeat_interleave(yt.shape[1], dim=0)
+    return c.contiguous()
+
+
 _last_rank = {'key': None, 'val': None}     # Recall@k and NDCG@k of one (y_true, y_pred) pair share one top-k pass
 
 
@@ -74,7 +146,12 @@ class _ClozeRankMetric:
         self.n_examples = None
         self.total = None
 
-    def _rows(self, y_true, y_pred, exclude=None):
+    def _rows(self, y_true, y_pred, exclude=None, candidates=None):
+        if candidates is not None and exclude is not None:
+            raise ValueError('candidates and exclude together: leave the excluded items out of the lists '
+                             '(cloze.sample_candidates(..., exclude=))')
+        if candidates is not None:
+            return self._cand_rows(y_true, y_pred, candidates)
         if hasattr(y_pred, 'rank_of'):
             # head.ClozeScores (model(x, scores='lazy')): rank of the true item through the logits-free sweep; one sweep
             # serves every k and both metrics (the scores object caches the rank of a label tensor)
@@ -114,6 +191,43 @@ class _ClozeRankMetric:
         _last_rank.update(key=key, val=(hit, ndcg, valid), ref=weakref.ref(y_pred))     # same object, same version -> same scores
         return hit, ndcg, valid
 
+    def _cand_rows(self, y_true, y_pred, candidates):
+        """hit / ndcg of the label's rank among each row's candidate list: through the head's candidate scores (lazy y_pred,
+        b4c_candidate_score) or gathered from the materialised probabilities (b4c_candidate_rank_rows); one rank serves
+        Recall@k and NDCG@k of the same triple"""
+        dev = y_pred.device
+        yt = torch.as_tensor(y_true, device=dev).reshape(-1)
+        lazy = hasattr(y_pred, 'rank_of')
+        if lazy:
+            yp, V = None, y_pred.shape[-1]
+            pkey = ('lazy', id(y_pred))
+        else:
+            ops._cuda(y_pred)
+            V = y_pred.shape[-1]
+            yp = y_pred.reshape(-1, V)
+            if yp.stride(1) != 1:
+                yp = yp.contiguous()
+            pkey = (yp.data_ptr(), yp._version, tuple(yp.shape), yp.stride(0), yp.dtype)
+        ckey = _cand_key(candidates) if isinstance(candidates, torch.Tensor) else ('host', id(candidates))
+        key = ('cand',) + pkey + (yt.data_ptr(), yt._version, tuple(yt.shape), ckey, torch.cuda.current_stream().cuda_stream)
+        if _last_rank['key'] == key and _last_rank['ref']() is y_pred:
+            rank, valid = _last_rank['val'][:2]
+        else:
+            lab, valid = _labels_i32(yt, dev)
+            cand = _row_candidates(candidates, yt.shape[0], y_true, dev)
+            if lazy:
+                rank = y_pred.rank_of(lab, candidates=cand)
+            else:          # y_pred is only read
+                rank, _ = ops.candidate_rank_rows(yp, V, cand, lab)
+            # the key names the lists and labels by address (or id()): the entry holds them, so that no later list or label
+            # tensor can take the same address while the entry stands and be answered with this rank
+            _last_rank.update(key=key, val=(rank, valid, candidates, y_true, yt), ref=weakref.ref(y_pred))
+        hit, ndcg = ops.rank_metrics(rank, self.k)
+        if lazy and y_pred.flag is not None:
+            ops.poison_rows(hit.view(-1, 1), y_pred.flag)
+            ops.poison_rows(ndcg.view(-1, 1), y_pred.flag)
+        return hit, ndcg, valid
+
     def _add(self, value, n):
         if self.total is None:
             self.total, self.n_examples = value.clone(), n.clone()
@@ -142,10 +256,12 @@ class ClozeMaskedRecall(_ClozeRankMetric):
     def __init__(self, k, name=None):
         super().__init__(k, name or 'Recall_at_%d' % k)
 
-    def update_state(self, y_true, y_pred, sample_weight=None, exclude=None):
+    def update_state(self, y_true, y_pred, sample_weight=None, exclude=None, candidates=None):
         """exclude: items left out of each row's ranking (cloze.seen_items for the filtered protocol): (B, E) per sequence
-        or (B*M, E) per row, integer ids padded with negatives, or host lists; the label is never excluded"""
-        hit, _, valid = self._rows(y_true, y_pred, exclude)
+        or (B*M, E) per row, integer ids padded with negatives, or host lists; the label is never excluded.
+        candidates: rank among a list of items per row instead of all V (cloze.sample_candidates: the sampled-negative
+        protocol): (B*M, C) per row or (B, C) per sequence, label-space ids, < 0 absent; not together with exclude"""
+        hit, _, valid = self._rows(y_true, y_pred, exclude, candidates)
         self._add((hit * valid).sum(), valid.sum().to(torch.float32))
 
 
@@ -155,8 +271,10 @@ class ClozeMaskedNDCG(_ClozeRankMetric):
     def __init__(self, k, name=None):
         super().__init__(k, name or 'NDCG_at_%d' % k)
 
-    def update_state(self, y_true, y_pred, sample_weight=None, exclude=None):
+    def update_state(self, y_true, y_pred, sample_weight=None, exclude=None, candidates=None):
         """exclude: items left out of each row's ranking (cloze.seen_items for the filtered protocol): (B, E) per sequence
-        or (B*M, E) per row, integer ids padded with negatives, or host lists; the label is never excluded"""
-        _, ndcg, valid = self._rows(y_true, y_pred, exclude)
+        or (B*M, E) per row, integer ids padded with negatives, or host lists; the label is never excluded.
+        candidates: rank among a list of items per row instead of all V (cloze.sample_candidates: the sampled-negative
+        protocol): (B*M, C) per row or (B, C) per sequence, label-space ids, < 0 absent; not together with exclude"""
+        _, ndcg, valid = self._rows(y_true, y_pred, exclude, candidates)
         self._add((ndcg * valid).sum(), valid.sum().to(torch.float32))

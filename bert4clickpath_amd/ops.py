@@ -1096,6 +1096,9 @@ def _excl_args(exclude, R, who):
         raise B4CError('%s: exclude must be the int32 [R, E] device tensor of ops.exclusions' % who)
     if exclude.shape[0] != R or (exclude.shape[1] and exclude.stride(1) != 1):
         raise B4CError('%s: exclude has %d rows (contiguous ids) for %d rows' % (who, exclude.shape[0], R))
+    if R > 1 and exclude.shape[1] and exclude.stride(0) < exclude.shape[1]:      # (rows that overlap: not ops.exclusions' own)
+        raise B4CError('%s: exclude rows overlap in memory (stride %d < %d ids); pass ops.exclusions(...)'
+                       % (who, exclude.stride(0), exclude.shape[1]))
     return _p(exclude), max(exclude.stride(0), exclude.shape[1]), exclude.shape[1]
 
 
@@ -1219,6 +1222,124 @@ def topk_rows(scores, V, k, labels_i32=None, exclude=None):
     return idx, hit, ndcg
 
 
+
+# ---- candidate lists (include/b4c.h "candidate lists"): sampled negatives, scores / rank / top-k of a per-row list of items ----
+def _cand_args(cand, R, who):
+    """(tensor, ld, C) of an int32 [R, C] device candidate tensor.  Rows that overlap in memory (a list shared by every row
+    through expand(R, -1): stride(0) == 0) are copied out first: the kernels address row r at r * ld with ld >= C."""
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 2 or cand.dtype != torch.int32:
+        raise B4CError('%s: candidates must be an int32 [R, C] tensor of item ids' % who)
+    if cand.shape[0] != R:
+        raise B4CError('%s: candidates have %d rows for %d rows' % (who, cand.shape[0], R))
+    C = cand.shape[1]
+    if not 1 <= C <= L.MAX_CAND:
+        raise B4CError('%s: %d candidates per row; 1 .. %d (B4C_MAX_CAND)' % (who, C, L.MAX_CAND))
+    if R and cand.stride(1) != 1:
+        raise B4CError('%s: candidate ids must be contiguous within a row' % who)
+    if R > 1 and cand.stride(0) < C:
+        cand = cand.contiguous()
+    return cand, max(cand.stride(0), C), C
+
+
+def _cand_labels(labels, R, who):
+    if labels is None:
+        return None
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.numel() != R:
+        raise B4CError('%s: labels must be an int32 tensor of %d ids' % (who, R))
+    return labels.reshape(-1).contiguous()
+
+
+def _cand_k(k, who):
+    if not 0 <= int(k) <= L.MAX_TOPK:
+        raise B4CError('%s: k = %d (0 .. %d)' % (who, k, L.MAX_TOPK))
+    return int(k)
+
+
+def sample_candidates(labels, V, num_negatives, seed, row_base=0, exclude=None, item_cdf=None):
+    """-> (cand int32 [R, 1 + N], short int32 [1]) (b4c_sample_candidates): cand[r][0] = labels[r], then N distinct negatives
+    of [0, V) in acceptance order -- never the label, never an item of the row's exclusion list.  Attempt j of row r draws
+    x = b4c_rand64(seed, ((row_base + r) << 20) | j): uniform (item_cdf None) mulhi64(x, V), or popularity (item_cdf: int64 [V]
+    inclusive prefix sum of per-item counts, total = item_cdf[-1] > 0) min{i : item_cdf[i] > mulhi64(x, total)}.  After 64 N
+    attempts a row still short keeps -1 in its tail and is counted in short[0]; rows without a valid label are -1 throughout.
+    exclude: ops.exclusions lists, one per row.  A pure function of (seed, row_base + r, labels, exclusions, item_cdf).
+    The total of item_cdf is not read back (no stream synchronisation here): a cdf whose total is <= 0 draws nothing, and every
+    row with a valid label comes back short.  cloze.sample_candidates checks the counts on the host, where it builds the cdf."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.dtype != torch.int32:
+        raise B4CError('sample_candidates: labels must be an int32 [R] tensor')
+    R, V, N = labels.shape[0], int(V), int(num_negatives)
+    if V <= 0 or not 0 <= N < L.MAX_CAND:
+        raise B4CError('sample_candidates: V = %d, num_negatives = %d (0 .. %d)' % (V, N, L.MAX_CAND - 1))
+    if not 0 <= int(row_base) < (1 << 44) or not 0 <= int(seed) < (1 << 64):
+        raise B4CError('sample_candidates: row_base %d (0 .. 2^44) / seed %d (0 .. 2^64)' % (row_base, seed))
+    ex, ld_e, E = _excl_args(exclude, R, 'sample_candidates') if exclude is not None else (None, 0, 0)
+    if item_cdf is not None:
+        if not isinstance(item_cdf, torch.Tensor) or item_cdf.dtype != torch.int64 or item_cdf.dim() != 1 or item_cdf.shape[0] != V:
+            raise B4CError('sample_candidates: item_cdf must be an int64 [V] = [%d] prefix sum of item counts' % V)
+        item_cdf = item_cdf.contiguous()      # (its total is not read back here: a cdf without mass draws nothing, rows short)
+    _cuda(labels, item_cdf)
+    labels = labels.contiguous()
+    cand = torch.empty(R, N + 1, dtype=torch.int32, device=labels.device)
+    short = torch.empty(1, dtype=torch.int32, device=labels.device)
+    with _record('sample_candidates', R * (N + 1) * 4 + R * E * 4):
+        L.check(L.lib().b4c_sample_candidates(_p(labels), R, V, N, int(seed), int(row_base), ex, ld_e, E, _p(item_cdf), _p(cand),
+                                              N + 1, _p(short), _st()), 'sample_candidates')
+    return cand, short
+
+
+def candidate_scores(h, wt, bias, cand, V, labels=None, k=0, want_scores=True):
+    """-> (scores fp32 [R, C] or None, rank int32 [R] or None, idx int32 [R, k] or None) of a per-row candidate list
+    (b4c_candidate_score): s(r, c) = h[r] . wt[c] + bias[c] (fp32 accumulation); NaN where cand[r][p] is absent (< 0 or >= V).
+    rank (labels int32 [R] given): distinct listed items other than the label that score above it, or equal and with a lower id
+    (negative: no valid label).  idx (k > 0): the k best distinct listed items, ties -> lower id, -1 past the last.
+    h [R, K] and wt [>= V, >= K] bf16 or fp32 (one dtype), K % 8 == 0, K <= 1024; bias fp32 [>= V]."""
+    if not isinstance(h, torch.Tensor) or h.dim() != 2:
+        raise B4CError('candidate_scores: h must be an [R, K] tensor')
+    R, K = h.shape
+    dt = dt_code(h.dtype)
+    if K % 8 or not 8 <= K <= 1024 or h.stride(1) != 1:
+        raise B4CError('candidate_scores: K = %d (a multiple of 8, 8 .. 1024, contiguous rows)' % K)
+    if (not isinstance(wt, torch.Tensor) or wt.dim() != 2 or wt.dtype != h.dtype or wt.shape[0] < V or wt.shape[1] < K
+            or wt.stride(1) != 1 or wt.stride(0) % 8):
+        raise B4CError('candidate_scores: wt must be [>= V, >= K] in h\'s dtype with a pitch that is a multiple of 8')
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.numel() < V:
+        raise B4CError('candidate_scores: bias must be fp32 [>= V]')
+    cand, ld_c, C = _cand_args(cand, R, 'candidate_scores')
+    k = _cand_k(k, 'candidate_scores')
+    lab = _cand_labels(labels, R, 'candidate_scores')
+    _cuda(h, wt, bias, cand, lab)
+    dev = h.device
+    scores = torch.empty(R, C, dtype=torch.float32, device=dev) if want_scores else None
+    rank = torch.empty(R, dtype=torch.int32, device=dev) if lab is not None else None
+    idx = torch.empty(R, k, dtype=torch.int32, device=dev) if k else None
+    if R == 0:
+        return scores, rank, idx
+    es, Kp = h.element_size(), wt.shape[1]
+    with _record('candidate_score', R * K * es + R * C * Kp * es + R * C * 4, 2 * R * C * K):
+        L.check(L.lib().b4c_candidate_score(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias.contiguous()), _p(cand), ld_c, R, C, V, K,
+                                            dt, _p(lab), _p(scores), C, _p(rank), k, _p(idx), _st()), 'candidate_score')
+    return scores, rank, idx
+
+
+def candidate_rank_rows(scores, V, cand, labels=None, k=0):
+    """-> (rank, idx) of candidate_scores' definition on MATERIALISED scores [R, >= V] (fp32 probabilities or logits, bf16
+    logits) (b4c_candidate_rank_rows): the listed columns are gathered, `scores` is only read."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.shape[1] < V or scores.stride(1) != 1:
+        raise B4CError('candidate_rank_rows: scores must be an [R, >= V] tensor with contiguous rows')
+    dt = dt_code(scores.dtype)
+    R = scores.shape[0]
+    cand, ld_c, C = _cand_args(cand, R, 'candidate_rank_rows')
+    k = _cand_k(k, 'candidate_rank_rows')
+    lab = _cand_labels(labels, R, 'candidate_rank_rows')
+    _cuda(scores, cand, lab)
+    rank = torch.empty(R, dtype=torch.int32, device=scores.device) if lab is not None else None
+    idx = torch.empty(R, k, dtype=torch.int32, device=scores.device) if k else None
+    if R == 0:
+        return rank, idx
+    with _record('candidate_rank_rows', R * C * (scores.element_size() + 4)):
+        L.check(L.lib().b4c_candidate_rank_rows(_p(scores), scores.stride(0), dt, _p(cand), ld_c, R, C, V, _p(lab), _p(rank), k, _p(idx),
+                                                _st()), 'candidate_rank_rows')
+    return rank, idx
+
 def adam_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul=1.0):
     with _record('adam', p.numel() * 28):
         L.check(L.lib().b4c_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr_t, beta1, beta2, eps, grad_mul, _st()),
@@ -1260,6 +1381,22 @@ def rand64_host(seed, ctr):
         x1 = (x1 + a1 + np.uint64(j)) & M
     return x0 | (x1 << np.uint64(32))
 
+
+
+def mulhi64_host(x, v):
+    """Host restatement of the sampler's mulhi64 (csrc/candidates.hip): the high 64 bits of the 128-bit product of uint64 x
+    (array) and 0 <= v < 2^64, exact (32-bit halves)."""
+    import numpy as np
+    M = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    x = np.asarray(x, dtype=np.uint64)
+    v = int(v)
+    vl, vh = np.uint64(v & 0xFFFFFFFF), np.uint64(v >> 32)
+    xl, xh = x & M, x >> s32
+    t = xl * vl
+    m1 = xh * vl + (t >> s32)
+    m2 = xl * vh + (m1 & M)
+    return xh * vh + (m1 >> s32) + (m2 >> s32)
 
 def keep_mask(seed, n, rate):
     """Host regeneration of a dropout keep-mask (tests): element e kept iff b4c_keep(seed, e, rate) --

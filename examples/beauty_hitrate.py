@@ -3,6 +3,8 @@
 (examples/BERT4Rec/source/main.py: d_model 64, 2 layers, 2 heads, dff 100, head [1024,512,256,128] -> V,
 Adam 1e-3/.9/.999/1e-9, dropout 0.1, 512 sequences per step), trained for a bounded number of steps, then
 HitRate@10 / NDCG@10 with the reference's evaluation protocol (mask the last item, rank over ALL V items).
+--negatives N adds the BERT4Rec paper's protocol beside it: the held-out item ranked against N sampled items the user has not
+seen (uniform, or by popularity counted on the training split), HR@10 / NDCG@10 over those 1 + N candidates.
 
     python examples/beauty_hitrate.py --steps 3000 --dtype f32
 Prints one JSON line.  The CPU counterpart on the oracle is oracle/train_beauty_cpu.py (same seeds, batches,
@@ -15,6 +17,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
@@ -38,6 +41,11 @@ def main():
     ap.add_argument('--data', default=os.path.join(ROOT, 'data', 'beauty_sequences.npz'))
     ap.add_argument('--exclude_seen', action='store_true',
                     help='also report the filtered protocol: the held-out item ranked against the items absent from the history')
+    ap.add_argument('--negatives', type=int, default=0,
+                    help='also report the sampled-negative protocol of the BERT4Rec paper: the held-out item against N '
+                         'sampled unseen items (100 in the paper)')
+    ap.add_argument('--sampler', default='popularity', choices=['uniform', 'popularity'],
+                    help='how the negatives are drawn; popularity counts come from the training split only')
     a = ap.parse_args()
     from bert4clickpath_amd import input_pipeline, optim
     from bert4clickpath_amd.clickstream_transformer import transformer as T
@@ -60,7 +68,12 @@ def main():
     torch.cuda.synchronize()
     train_s = time.perf_counter() - t0
     from bert4clickpath_amd import cloze
-    hits = ndcg = n = fhits = fndcg = 0.0
+    from bert4clickpath_amd.clickstream_transformer.constants import NUM_RESERVED_TOKENS
+    hits = ndcg = n = fhits = fndcg = shits = sndcg = 0.0
+    counts = None
+    if a.negatives and a.sampler == 'popularity':       # the training split: every sequence without its held-out last item
+        train = np.concatenate([data.seq(i)[:-1] for i in range(data.n_seq)]) + NUM_RESERVED_TOKENS
+        counts = cloze.item_counts(train, data.V)
     for b in data.eval_batches(1024, a.eval_limit):
         ids = torch.from_numpy(b['ids'])
         items = ids[:, 2:-1].contiguous().cuda()
@@ -70,11 +83,21 @@ def main():
         if a.exclude_seen:          # one [MASK] (the last item) per sequence: the rows are the sequences, in order
             _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, exclude=cloze.seen_items(items))
             fhits += float(h.sum()); fndcg += float(nd.sum())
+        if a.negatives:             # row_base: the draws of a row do not depend on the batch size
+            cand = cloze.sample_candidates(labels, a.negatives, exclude=cloze.seen_items(items), item_counts=counts,
+                                           seed=a.seed, row_base=int(n) - labels.numel(),
+                                           num_items=data.V)
+            _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, candidates=cand)
+            shits += float(h.sum()); sndcg += float(nd.sum())
     out = {'what': 'Amazon Beauty, HIP path', 'dtype': a.dtype, 'steps': a.steps, 'batch': a.batch,
            'dropout': a.dropout, 'hitrate@10': 100.0 * hits / n, 'ndcg@10': 100.0 * ndcg / n, 'n_eval': int(n),
            'train_seconds': train_s, 'loss_curve': losses}
     if a.exclude_seen:
         out.update({'filtered_hitrate@10': 100.0 * fhits / n, 'filtered_ndcg@10': 100.0 * fndcg / n})
+    if a.negatives:
+        out.update({'sampled_protocol': 'BERT4Rec paper: 1 held-out + %d %s-sampled unseen items (not the reference\'s '
+                                        'full ranking)' % (a.negatives, a.sampler),
+                    'sampled_hitrate@10': 100.0 * shits / n, 'sampled_ndcg@10': 100.0 * sndcg / n})
     print(json.dumps(out))
 
 

@@ -39,6 +39,7 @@ extern "C" {
 #define B4C_MAX_FEATURES 4
 #define B4C_MAX_TOPK 16
 #define B4C_MAX_EXCL 1024   /* longest exclusion list per ranked row (b4c_exclusions_prep and the *_excl entry points) */
+#define B4C_MAX_CAND 1024   /* longest candidate list per row (b4c_sample_candidates, b4c_candidate_score, b4c_candidate_rank_rows) */
 
 #define B4C_ACT_NONE 0
 #define B4C_ACT_RELU 1
@@ -417,6 +418,40 @@ int b4c_vocab_topk_excl(const void *h, int ld_h, const void *wt, int ld_w, const
                         int64_t R, int V, int K, const int32_t *excl, int ld_e, int E, void *stream);
 int b4c_topk_rows_excl(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx, const int32_t *labels, float *hit,
                        float *ndcg, int32_t *redo, int dtype, const int32_t *excl, int ld_e, int E, void *stream);
+
+/* ---- candidate lists: score and rank a per-row list of items (sampled-negative evaluation, re-ranking) ---------------------
+ * Item ids are in the label space [0, V) (input id - NUM_RESERVED_TOKENS), the space of the exclusion lists.
+ * cand [R][C] int32 (pitch ld_c), 1 <= C <= B4C_MAX_CAND: an entry < 0 or >= V is ABSENT -- it never ranks and its `scores`
+ *   entry is NaN.  A duplicated id counts once for rank and top-k; every position still gets its own score.
+ * Score: s(r, c) = sum_k h[r][k] * wt[c][k] (fp32 accumulation) + bias[c]; h / wt bf16 or fp32 (dtype), K % 8 == 0, K <= 1024.
+ *   The label's score and a listed item's score come from the same arithmetic: a listed copy of the label compares equal to
+ *   the label, and no summation order creates or breaks a tie between them.
+ * Rank: rank[r] = #{distinct present c of cand[r], c != y_r : s_c > s_y or (s_c == s_y and c < y_r)}; the label y_r is scored
+ *   whether it is listed or not; negative for a row without a valid label (y < 0 or y >= V).  The tie rule of b4c_vocab_rank:
+ *   with the list 0 .. V-1 the rank is the full-vocabulary rank wherever both compute the same fp32 scores.  HitRate@k /
+ *   NDCG@k: b4c_rank_metrics.
+ * Top-k: idx [R][k] (k <= B4C_MAX_TOPK) = the k best distinct present items of the list, score descending, ties -> lower id;
+ *   fewer than k: the tail is -1.  The label appears only if it is listed.
+ * b4c_sample_candidates: cand [R][1 + N] (pitch ld_c), cand[r][0] = y_r, then N <= B4C_MAX_CAND - 1 negatives in acceptance
+ *   order.  Attempt j of row r draws x = b4c_rand64(seed, ((row_base + r) << 20) | j) (csrc/common.h) and the item
+ *   mulhi64(x, V) (cdf == NULL: uniform) or min{i : cdf[i] > mulhi64(x, total)} (popularity: cdf [V] the inclusive int64 prefix
+ *   sum of per-item counts, total = cdf[V-1] > 0 -- not checked: a total <= 0 draws nothing; items of count 0 are never drawn),
+ *   mulhi64 = the high 64 bits of the 128-bit product.  An attempt is accepted iff its item is != y_r, not in the row's exclusion list (b4c_exclusions_prep
+ *   form, E may be 0) and not accepted before; the first N accepted attempts in j order are kept.  Attempts stop at
+ *   j = 64 N: a row still short has -1 in its tail and is counted in short_count[0] (zeroed here).  Rows without a valid label
+ *   get -1 throughout and draw nothing.  A pure function of (seed, row_base + r, labels, exclusions, cdf): row_base keeps the
+ *   draws independent of how the rows are split into batches or ranks.
+ * b4c_candidate_score: scores [R][ld_s] fp32 (may be NULL), rank [R] (may be NULL; needs labels), idx [R][k] (k = 0 / NULL:
+ *   no top-k).  One wave per row; the scores live in LDS and reach memory only when `scores` is given.
+ * b4c_candidate_rank_rows: rank / top-k of the same definition on MATERIALISED scores [R][ld] (fp32 probabilities or logits,
+ *   bf16 logits; dtype): the listed columns are gathered; `scores` is only read. */
+int b4c_sample_candidates(const int32_t *labels, int64_t R, int V, int N, uint64_t seed, int64_t row_base, const int32_t *excl,
+                          int ld_e, int E, const int64_t *cdf, int32_t *cand, int ld_c, int32_t *short_count, void *stream);
+int b4c_candidate_score(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *cand, int ld_c,
+                        int64_t R, int C, int V, int K, int dtype, const int32_t *labels, float *scores, int ld_s, int32_t *rank,
+                        int k, int32_t *idx, void *stream);
+int b4c_candidate_rank_rows(const void *scores, int ld, int dtype, const int32_t *cand, int ld_c, int64_t R, int C, int V,
+                            const int32_t *labels, int32_t *rank, int k, int32_t *idx, void *stream);
 
 /* ---- R16: Adam (Keras semantics, eps outside the sqrt) ------------------------------------
  * replaces tf.keras.optimizers.Adam(1e-3, .9, .999, 1e-9) (main.py:87), dense update over a flat
