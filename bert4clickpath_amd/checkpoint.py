@@ -98,7 +98,9 @@ def load_checkpoint(path, model, optimizer=None, strict=True):
                     raise ValueError('%s: moment shape %s, parameter shape %s' % (n, tuple(o['m'][n].shape), tuple(p.shape)))
                 optimizer.m[off:off + p.numel()].view(p.shape).copy_(o['m'][n])
                 optimizer.v[off:off + p.numel()].view(p.shape).copy_(o['v'][n])
-        optimizer.iterations, optimizer.lr = int(o['iterations']), float(o['lr'])
+        optimizer.iterations = int(o['iterations'])
+        if not getattr(optimizer, 'scheduled', False):     # a learning-rate schedule is the caller's to construct again: it is a
+            optimizer.lr = float(o['lr'])                   # function of `iterations`, and the stored float is for the record only
         optimizer.beta_1, optimizer.beta_2, optimizer.epsilon = o['beta_1'], o['beta_2'], o['epsilon']
     if optimizer is not None and hasattr(optimizer, 'reset_rows'):
         optimizer.reset_rows()     # (the loaded tables are current through `iterations`, whatever the optimizer held before)
@@ -139,6 +141,8 @@ class ReduceLROnPlateau:
     def __init__(self, optimizer, factor=0.317, patience=10, min_delta=1e-4, cooldown=0, min_lr=0.0):
         if factor >= 1.0:
             raise ValueError('ReduceLROnPlateau does not support a factor >= 1.0.')
+        if getattr(optimizer, 'scheduled', False):
+            raise TypeError('ReduceLROnPlateau needs an optimizer with a float learning rate; this one follows a schedule')
         self.opt, self.factor, self.patience, self.min_delta = optimizer, factor, patience, min_delta
         self.cooldown, self.min_lr = cooldown, min_lr
         self.best, self.wait, self.cooldown_counter = float('inf'), 0, 0

@@ -24,7 +24,7 @@ int b4c_check_launch(const char *what) {
     return B4C_OK;
 }
 extern "C" const char *b4c_last_error(void) { return g_err; }
-extern "C" int b4c_abi_version(void) { return 12; }
+extern "C" int b4c_abi_version(void) { return 12; }    // (still 12 with the grad-norm / *_clipped entry points: additive, no signature changed)
 extern "C" int b4c_keep(uint64_t seed, uint64_t e, float rate) { return b4c_keep_elem(seed, e, rate) ? 1 : 0; }
 
 // ------------------------------------------------------------------------------------------
@@ -1055,7 +1055,10 @@ __device__ __forceinline__ void adam_elem(float &pp, float gk, float &mm, float 
 
 __global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                    float *__restrict__ v, int64_t n, float lr_t, float b1, float b2,
-                                                   float eps, float gmul) {
+                                                   float eps, float gmul, const float *__restrict__ coef) {
+    // coef: the device's clip coefficient (gradnorm.hip), exactly 1.0f when nothing is clipped; NULL: no clipping.  The same
+    // expression in adam_rows_kernel: one fp32 product, then g * that
+    if (coef) gmul = gmul * *coef;
     const int64_t n4 = n >> 2;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         f32x4 pp = reinterpret_cast<f32x4 *>(p)[i], gg = reinterpret_cast<const f32x4 *>(g)[i];
@@ -1098,7 +1101,8 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(float *__restrict__ p, f
                                                         float *__restrict__ v, int32_t *__restrict__ stamp,
                                                         const int64_t *__restrict__ ids, int64_t n, int64_t row_lo, int64_t rows,
                                                         int width, const float *__restrict__ lr_hist, int t, float b1, float b2,
-                                                        float eps, float gmul) {
+                                                        float eps, float gmul, const float *__restrict__ coef) {
+    if (MODE == 1 && coef) gmul = gmul * *coef;                // (as adam_kernel; replayed steps have g = 0 and need no past coefficient)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t i = blockIdx.x * 4ll + wave;
@@ -1152,9 +1156,9 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(float *__restrict__ p, f
     if (!ids && lane == 0) stamp[r] = t;
 }
 
-extern "C" int b4c_adam_rows(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n, int64_t row_lo,
-                             int64_t rows, int width, const float *lr_hist, int t, float beta1, float beta2, float eps,
-                             float grad_mul, int mode, void *stream) {
+static int adam_rows_launch(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n, int64_t row_lo,
+                            int64_t rows, int width, const float *lr_hist, int t, float beta1, float beta2, float eps,
+                            float grad_mul, const float *coef, int mode, void *stream) {
     B4C_REQUIRE(p && m && v && stamp && lr_hist && rows > 0 && width > 0 && t >= 0, "adam_rows: bad argument");
     B4C_REQUIRE(mode == 0 || (mode == 1 && g), "adam_rows: mode %d (0 = catch up, 1 = step; the step needs the gradient table)", mode);
     B4C_REQUIRE(width % 4 == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
@@ -1164,15 +1168,39 @@ extern "C" int b4c_adam_rows(float *p, float *g, float *m, float *v, int32_t *st
     if (n <= 0) return 0;
     const int64_t blocks = (n + 3) / 4;
     B4C_REQUIRE(blocks < (1ll << 31), "adam_rows: %lld rows in one call", (long long)n);
-    if (mode == 0) adam_rows_kernel<0><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul);
-    else adam_rows_kernel<1><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul);
+    if (mode == 0) adam_rows_kernel<0><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, coef);
+    else adam_rows_kernel<1><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, coef);
     return b4c_check_launch("adam_rows");
+}
+
+extern "C" int b4c_adam_rows(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n, int64_t row_lo,
+                             int64_t rows, int width, const float *lr_hist, int t, float beta1, float beta2, float eps,
+                             float grad_mul, int mode, void *stream) {
+    return adam_rows_launch(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, nullptr, mode, stream);
+}
+
+extern "C" int b4c_adam_rows_clipped(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n,
+                                     int64_t row_lo, int64_t rows, int width, const float *lr_hist, int t, float beta1, float beta2,
+                                     float eps, float grad_mul, const float *coef, int mode, void *stream) {
+    B4C_REQUIRE(coef && ((uintptr_t)coef & 3) == 0, "adam_rows_clipped: null / misaligned coefficient (b4c_adam_rows is the form without one)");
+    return adam_rows_launch(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, coef, mode, stream);
+}
+
+static int adam_step_launch(float *p, const float *g, float *m, float *v, int64_t n, float lr_t, float beta1, float beta2, float eps,
+                            float grad_mul, const float *coef, void *stream) {
+    B4C_REQUIRE(p && g && m && v && n > 0, "adam_step: bad argument");
+    B4C_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step: pointers must be 16-byte aligned");
+    adam_kernel<<<grid_for(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr_t, beta1, beta2, eps, grad_mul, coef);
+    return b4c_check_launch("adam_step");
 }
 
 extern "C" int b4c_adam_step(float *p, const float *g, float *m, float *v, int64_t n, float lr_t, float beta1,
                              float beta2, float eps, float grad_mul, void *stream) {
-    B4C_REQUIRE(p && g && m && v && n > 0, "adam_step: bad argument");
-    B4C_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step: pointers must be 16-byte aligned");
-    adam_kernel<<<grid_for(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr_t, beta1, beta2, eps, grad_mul);
-    return b4c_check_launch("adam_step");
+    return adam_step_launch(p, g, m, v, n, lr_t, beta1, beta2, eps, grad_mul, nullptr, stream);
+}
+
+extern "C" int b4c_adam_step_clipped(float *p, const float *g, float *m, float *v, int64_t n, float lr_t, float beta1, float beta2,
+                                     float eps, float grad_mul, const float *coef, void *stream) {
+    B4C_REQUIRE(coef && ((uintptr_t)coef & 3) == 0, "adam_step_clipped: null / misaligned coefficient (b4c_adam_step is the form without one)");
+    return adam_step_launch(p, g, m, v, n, lr_t, beta1, beta2, eps, grad_mul, coef, stream);
 }

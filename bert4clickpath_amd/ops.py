@@ -1357,6 +1357,57 @@ def adam_rows_(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1
                                       beta1, beta2, eps, grad_mul, mode, _st()), 'adam_rows')
 
 
+def adam_step_clipped_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul, coef):
+    """adam_step_ with the gradient scaled by grad_mul * coef[0] (coef: device fp32 scalar of grad_clip_coef_)"""
+    with _record('adam', p.numel() * 28):
+        L.check(L.lib().b4c_adam_step_clipped(_p(p), _p(g), _p(m), _p(v), p.numel(), lr_t, beta1, beta2, eps, grad_mul, _p(coef),
+                                              _st()), 'adam_step_clipped')
+
+
+def adam_rows_clipped_(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, coef, mode):
+    """adam_rows_ with the step's gradient scaled by grad_mul * coef[0] (booked as adam_rows_)"""
+    if n <= 0:
+        return
+    nrows = min(n, rec_hints.get('adam_distinct_rows', n)) if ids is not None else n
+    with _record('adam' if mode == 1 else 'adam_catch_up', nrows * width * (32 if mode == 1 else 24) + (n * 8 if ids is not None else 0)):
+        L.check(L.lib().b4c_adam_rows_clipped(_p(p), _p(g), _p(m), _p(v), _p(stamp), _p(ids), n, row_lo, rows, width, _p(lr_hist),
+                                              t, beta1, beta2, eps, grad_mul, _p(coef), mode, _st()), 'adam_rows_clipped')
+
+
+def grad_chunks(n):
+    """number of chunk partials of an arena of n elements (b4c_grad_sumsq)"""
+    return (n + L.GRAD_CHUNK - 1) // L.GRAD_CHUNK
+
+
+def grad_sumsq_(grad, lo, hi, partial):
+    """partial[c] (float64) := sum of squares of every chunk of the fp32 arena `grad` that overlaps [lo, hi) (csrc/gradnorm.hip)"""
+    if hi <= lo:
+        return
+    c = grad_chunks(hi) - lo // L.GRAD_CHUNK
+    with _record('grad_norm', c * (L.GRAD_CHUNK * 4 + 8)):
+        L.check(L.lib().b4c_grad_sumsq(_p(grad), grad.numel(), lo, hi, _p(partial), _st()), 'grad_sumsq')
+
+
+def grad_sumsq_rows_(grad, table_lo, rows, width, ids, partial):
+    """the same for the chunks that the rows `ids` (int64, contiguous; repeats and out-of-range values as adam_rows_ takes
+    them) of the (rows, width) table at grad[table_lo:] overlap.  Booked bytes: every named row's chunks (an upper bound)."""
+    n = ids.numel()
+    if n <= 0:
+        return
+    per = (width + L.GRAD_CHUNK - 1) // L.GRAD_CHUNK + 1          # (a row of `width` elements overlaps at most this many chunks)
+    with _record('grad_norm', n * (8 + per * (L.GRAD_CHUNK * 4 + 8))):
+        L.check(L.lib().b4c_grad_sumsq_rows(_p(grad), grad.numel(), table_lo, rows, width, _p(ids), n, _p(partial), _st()),
+                'grad_sumsq_rows')
+
+
+def grad_clip_coef_(partial, group_sums, clip, grad_mul, total, norm_coef):
+    """total (float64 [1], may be None) := fixed tree over `partial`; norm_coef (fp32 [2]) := (sqrt(total) |grad_mul|, clip
+    coefficient: exactly 1 when the norm is <= clip, NaN when it is not finite).  All on the device."""
+    with _record('grad_norm', partial.numel() * 8 + group_sums.numel() * 16 + 16):
+        L.check(L.lib().b4c_grad_clip_coef(_p(partial), partial.numel(), _p(group_sums), group_sums.numel(), clip, grad_mul,
+                                           _p(total), _p(norm_coef), _st()), 'grad_clip_coef')
+
+
 def rand64_host(seed, ctr):
     """Host restatement of b4c_rand64 (csrc/common.h): Threefry-2x32, 12 rounds, key = seed, counter = ctr (uint64 array)."""
     import numpy as np

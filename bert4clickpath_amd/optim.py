@@ -1,5 +1,8 @@
 """Adam with Keras semantics (reference examples/BERT4Rec/source/main.py:87:
-Adam(1e-3, beta_1=.9, beta_2=.999, epsilon=1e-9), constant lr) over one flat fp32 arena.
+Adam(1e-3, beta_1=.9, beta_2=.999, epsilon=1e-9), constant lr) over one flat fp32 arena.  Beyond the reference's
+hard-coded recipe: `learning_rate` may be a schedule (a callable step -> lr, Keras' LearningRateSchedule convention;
+clickstream_transformer.training_utils has the reference's two) and `global_clipnorm` clips the gradient by its global L2
+norm, computed and applied on the device (csrc/gradnorm.hip).
 
 All parameters are re-homed into a single contiguous buffer (64-element aligned slices), gradients
 into a second one: the optimizer step is ONE HIP kernel launch over the arena and the data-parallel
@@ -75,11 +78,17 @@ class LazyRows:
         a = o.arena
         return a.flat[self.lo:self.lo + n], a.grad[self.lo:self.lo + n], o.m[self.lo:self.lo + n], o.v[self.lo:self.lo + n]
 
-    def _launch(self, ids, n, row_lo, t, mode, grad_mul=1.0):
+    def _launch(self, ids, n, row_lo, t, mode, grad_mul=1.0, coef=None):
         o = self.opt
         p, g, m, v = self._slices()
-        ops.adam_rows_(p, g, m, v, self.stamp, ids, n, row_lo, self.rows, self.width, o.lr_hist(t), t, o.beta_1, o.beta_2, o.epsilon,
-                       grad_mul, mode)
+        if coef is None:
+            ops.adam_rows_(p, g, m, v, self.stamp, ids, n, row_lo, self.rows, self.width, o.lr_hist(t), t, o.beta_1, o.beta_2,
+                           o.epsilon, grad_mul, mode)
+        else:
+            # the clip coefficient scales the gradient of step t alone: the zero-gradient steps a row replays (here and in
+            # catch_up / sync) are g = 0 whatever was clipped at the time, so no past coefficient is ever needed
+            ops.adam_rows_clipped_(p, g, m, v, self.stamp, ids, n, row_lo, self.rows, self.width, o.lr_hist(t), t, o.beta_1,
+                                   o.beta_2, o.epsilon, grad_mul, coef, mode)
 
     @staticmethod
     def _ids(ids):
@@ -111,12 +120,22 @@ class LazyRows:
         if self.opt.iterations > 0:
             self._launch(None, self.rows, 0, self.opt.iterations, 0)
 
-    def step(self, t, grad_mul):
+    def grad_sumsq(self, partial):
+        """this step's gradient rows into the chunk partials of the global norm (before step() consumes `touched`): the rows
+        named since the last step are the only ones that can hold a gradient; the other chunks stay at the caller's 0.0"""
+        g = self.opt.arena.grad
         if self.all_rows:
-            self._launch(None, self.rows, 0, t, 1, grad_mul)
+            ops.grad_sumsq_(g, self.lo, self.lo + self.rows * self.width, partial)
         else:
             for ids in self.touched:
-                self._launch(ids, ids.numel(), 0, t, 1, grad_mul)
+                ops.grad_sumsq_rows_(g, self.lo, self.rows, self.width, ids, partial)
+
+    def step(self, t, grad_mul, coef=None):
+        if self.all_rows:
+            self._launch(None, self.rows, 0, t, 1, grad_mul, coef)
+        else:
+            for ids in self.touched:
+                self._launch(ids, ids.numel(), 0, t, 1, grad_mul, coef)
             # bounded staleness: a rotating slice of the table is caught up every step, so no row ever replays more than
             # `max_staleness` steps at once (a rare item's first re-occurrence after 50,000 steps would otherwise be 50,000
             # dependent iterations in one wave)
@@ -130,13 +149,30 @@ class LazyRows:
 
 class Adam:
     def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-9, arena=None, order=None, lazy_rows=(),
-                 max_staleness=256):
-        """lazy_rows: 2-D (rows, width) parameters whose gradient is row-sparse (embedding tables, a vocabulary-major sampled
+                 max_staleness=256, global_clipnorm=None):
+        """learning_rate: a float, or a callable `step -> lr` called with the number of steps already taken (0 at the first
+        step), as Keras calls a LearningRateSchedule.  `opt.lr` reads the current value; assigning to it (ReduceLROnPlateau)
+        raises TypeError on a scheduled optimizer, as Keras does.  state_dict() / checkpoint.save_checkpoint store
+        `iterations` and the current float: the schedule object is the caller's to construct again before loading.
+
+        global_clipnorm (Keras' name; None: off, today's launches exactly): the gradient -- `grad_mul * g`, i.e. the mean
+        gradient under a reducer with reduce='mean' -- is scaled by min(1, global_clipnorm / ||grad_mul * g||) over the whole
+        arena.  A plain attribute: it may be switched between steps.  The norm never leaves the device; `last_grad_norm` is the
+        0-d device tensor the last clipped step wrote (reading it is the caller's sync, and the next step overwrites it).
+        Results are bit-identical between the row-lazy and the dense optimizer and between data-parallel replicas
+        (csrc/gradnorm.hip: the reduction is defined by arena position) as long as the norm is finite; a non-finite norm makes
+        the coefficient NaN and with it every parameter that takes the step.
+
+        lazy_rows: 2-D (rows, width) parameters whose gradient is row-sparse (embedding tables, a vocabulary-major sampled
         projection): their share of the update runs over the rows in use only, with results bit-identical to the dense
         update (LazyRows).  Code that reads such a table as a whole calls `sync_rows()` first; `state_dict()` and
         checkpoint.save_checkpoint do."""
+        self._learning_rate = learning_rate if callable(learning_rate) else float(learning_rate)
+        self.global_clipnorm = global_clipnorm
+        self.last_grad_norm = None
+        self._clip_bufs = None
         self.arena = arena or FlatArena(list(params), order)
-        self.lr, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
+        self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
         self.m = torch.zeros_like(self.arena.flat)
         self.v = torch.zeros_like(self.arena.flat)
         self.iterations = 0
@@ -159,8 +195,40 @@ class Adam:
             cuts.append((pos, self.arena.numel))
         self.dense_ranges = cuts
 
+    @property
+    def global_clipnorm(self):
+        return self._global_clipnorm
+
+    @global_clipnorm.setter
+    def global_clipnorm(self, value):
+        if value is not None:
+            value = float(value)
+            if not value > 0.0:
+                raise ValueError('global_clipnorm must be a positive number or None, got %r' % (value,))
+        self._global_clipnorm = value
+
+    @property
+    def scheduled(self):
+        return callable(self._learning_rate)
+
+    @property
+    def lr(self):
+        """the learning rate of the next step (a schedule is evaluated at `iterations`, the number of steps taken)"""
+        return float(self._learning_rate(self.iterations)) if self.scheduled else self._learning_rate
+
+    @lr.setter
+    def lr(self, value):
+        if self.scheduled:
+            raise TypeError('this optimizer was created with a learning-rate schedule (%r): its learning rate cannot be set; '
+                            'only a float learning_rate is settable' % (self._learning_rate,))
+        self._learning_rate = float(value)
+
+    learning_rate = lr
+
     def _lr_t(self, t):
-        return self.lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+        """bias-corrected step size of step t (t = 1 is the first): a schedule sees t - 1, the steps taken before it"""
+        lr = float(self._learning_rate(t - 1)) if self.scheduled else self._learning_rate
+        return lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
 
     def lr_hist(self, t):
         """device fp32 table of the lr_t of steps 1 .. t (what the dense kernel was / is handed at each of them): the replay of
@@ -211,8 +279,9 @@ class Adam:
         self.iterations += 1
         t = self.iterations
         lr_t = self._lr_t(t)
+        coef = self._clip_coef(grad_mul) if self._global_clipnorm is not None else None
         if not self.lazy:
-            ops.adam_step_(a.flat, a.grad, self.m, self.v, lr_t, self.beta_1, self.beta_2, self.epsilon, grad_mul)
+            self._adam_range(0, a.numel, lr_t, grad_mul, coef)
         else:
             if len(self._lr_host) == t:
                 self._lr_host.append(lr_t)
@@ -220,26 +289,60 @@ class Adam:
                 self._lr_host[t:] = [lr_t]
                 self._lr_valid = min(self._lr_valid, t)
             for lo, hi in self.dense_ranges:
-                ops.adam_step_(a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], lr_t, self.beta_1, self.beta_2,
-                               self.epsilon, grad_mul)
+                self._adam_range(lo, hi, lr_t, grad_mul, coef)
             for lz in self.lazy:
-                lz.step(t, grad_mul)
+                lz.step(t, grad_mul, coef)
             self._grads_clean = True
         ops.bump_weights_epoch()
+
+    def _adam_range(self, lo, hi, lr_t, grad_mul, coef):
+        a = self.arena
+        if coef is None:
+            ops.adam_step_(a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], lr_t, self.beta_1, self.beta_2, self.epsilon,
+                           grad_mul)
+        else:
+            ops.adam_step_clipped_(a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], lr_t, self.beta_1, self.beta_2,
+                                   self.epsilon, grad_mul, coef)
+
+    def _clip_coef(self, grad_mul):
+        """the device's clip coefficient of this step (fp32 [1]); also sets last_grad_norm.  Launches only: no host sync.
+        Chunk partials over the dense share (or the whole arena), the rows in use of each lazy table, then the fixed tree."""
+        a = self.arena
+        if self._clip_bufs is None:
+            n_chunks = ops.grad_chunks(a.numel)
+            dev = a.flat.device
+            self._clip_bufs = (ops.zeros(n_chunks, dtype=torch.float64, device=dev),
+                               ops.zeros((n_chunks + ops.L.GRAD_GROUP - 1) // ops.L.GRAD_GROUP, dtype=torch.float64, device=dev),
+                               ops.zeros(2, dtype=torch.float32, device=dev))
+            self.last_grad_norm = self._clip_bufs[2][0]
+        partial, groups, norm_coef = self._clip_bufs
+        if not self.lazy:
+            ops.grad_sumsq_(a.grad, 0, a.numel, partial)
+        else:
+            ops.zero_(partial)        # (config 5: 4 MB) chunks of the lazy tables that nobody names this step: their gradient is zero
+            for lo, hi in self.dense_ranges:
+                ops.grad_sumsq_(a.grad, lo, hi, partial)
+            for lz in self.lazy:
+                lz.grad_sumsq(partial)
+        ops.grad_clip_coef_(partial, groups, self._global_clipnorm, grad_mul, None, norm_coef)
+        return norm_coef[1:]
 
     def state_dict(self):
         self.sync_rows()
         return {'iterations': self.iterations, 'm': self.m, 'v': self.v, 'lr': self.lr}
 
     def load_state_dict(self, sd):
-        self.iterations, self.lr = int(sd['iterations']), float(sd['lr'])
+        self.iterations = int(sd['iterations'])
+        if not self.scheduled:        # (a schedule is a function of `iterations`: the stored float is for the record only)
+            self.lr = float(sd['lr'])
         self.m.copy_(sd['m'])
         self.v.copy_(sd['v'])
         self.reset_rows()
 
     def reset_rows(self):
         """after the moments / parameters were loaded from outside: every row counts as current through `iterations`; the lr_t
-        history of the steps before is rebuilt from the present lr (nothing will replay them)"""
+        history of the steps before is rebuilt from the present lr, or by calling the schedule for each past step (nothing will
+        replay them)"""
         self._lr_host = [0.0] + [self._lr_t(s) for s in range(1, self.iterations + 1)]
         self._lr_valid = 0
         for lz in self.lazy:

@@ -624,6 +624,33 @@ int b4c_attn_mq_bwd(const void *q, int ld_q, const void *kv, int ld_kv, const ui
                     const int32_t *q_offsets, const void *o, int ld_o, const void *d_o, int ld_do, const float *lse,
                     void *dq, int ld_dq, void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream);
 
+/* ---- global-norm gradient clipping (Adam(global_clipnorm=...); the reference never clips: no oracle, the BERT4Rec paper's
+ * recipe) -- additive to ABI 12: no existing signature changed, b4c_abi_version() stays 12 ------------------------------
+ * The squared L2 norm of the fp32 gradient arena g[0, n) with a POSITION-DEFINED reduction (csrc/gradnorm.hip): the arena is
+ * cut into chunks of B4C_GRAD_CHUNK consecutive elements counted from g; partial[c] (float64, ceil(n / B4C_GRAD_CHUNK)
+ * entries) is the sum of the squares of the WHOLE chunk c in a fixed order, whoever computes it.
+ *   b4c_grad_sumsq       writes partial[c] of every chunk that overlaps [lo, hi) (each over its whole extent).
+ *   b4c_grad_sumsq_rows  one wave per id (int64, repeats allowed, clamped to [0, rows) as b4c_adam_rows clamps them) rewrites
+ *                        the partial of every chunk that row of the (rows x width) table at g + table_lo overlaps; the caller
+ *                        zero-fills the partials of chunks nobody names (their gradient is all zeros).
+ *   b4c_grad_clip_coef   total = fixed tree over partial[0, n_chunks) (group_sums: scratch of n_groups =
+ *                        ceil(n_chunks / B4C_GRAD_GROUP) doubles); *total (may be NULL) = it; norm_coef[0] = sqrt(total) |grad_mul|
+ *                        in fp32, norm_coef[1] = norm > clip ? clip / norm : exactly 1.0f; NaN when the norm is not finite.
+ * b4c_adam_step_clipped / b4c_adam_rows_clipped: b4c_adam_step / b4c_adam_rows with the gradient scaled by
+ * grad_mul * *coef (coef: device fp32, e.g. norm_coef + 1) -- no host read-back anywhere. */
+#define B4C_GRAD_CHUNK 1024
+#define B4C_GRAD_GROUP 4096
+int b4c_grad_sumsq(const float *g, int64_t n, int64_t lo, int64_t hi, double *partial, void *stream);
+int b4c_grad_sumsq_rows(const float *g, int64_t n, int64_t table_lo, int64_t rows, int width, const int64_t *ids, int64_t n_ids,
+                        double *partial, void *stream);
+int b4c_grad_clip_coef(const double *partial, int64_t n_chunks, double *group_sums, int64_t n_groups, float clip, float grad_mul,
+                       double *total, float *norm_coef, void *stream);
+int b4c_adam_step_clipped(float *p, const float *g, float *m, float *v, int64_t n, float lr_t, float beta1, float beta2, float eps,
+                          float grad_mul, const float *coef, void *stream);
+int b4c_adam_rows_clipped(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n, int64_t row_lo,
+                          int64_t rows, int width, const float *lr_hist, int t, float beta1, float beta2, float eps, float grad_mul,
+                          const float *coef, int mode, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
