@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('B4C_LIB_PATH') or os.path.join(_HERE, 'libb4c_hip.so')     # override: A/B of two builds (scratch)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')
 
-ABI_VERSION = 12      # include/b4c.h; b4c_abi_version() of the library must agree (the grad-norm entry points are additive: still 12)
+ABI_VERSION = 12      # include/b4c.h; b4c_abi_version() of the library must agree (the grad-norm and AdamW entry points are additive: still 12)
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 CE_TF, CE_PLAIN = 0, 1
@@ -148,6 +148,8 @@ def lib():
             'b4c_grad_clip_coef': (i32, [vp, i64, vp, i64, f32, f32, vp, vp, vp]),
             'b4c_adam_step_clipped': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, vp]),
             'b4c_adam_rows_clipped': (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, i32, f32, f32, f32, f32, vp, i32, vp]),
+            'b4c_adamw_step': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, vp]),
+            'b4c_adamw_rows': (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, vp, i32, f32, f32, f32, f32, vp, i32, vp]),
             'b4c_dropout': (i32, [vp, vp, i64, f32, u64, i32, vp]),
             'b4c_softmax_rows_bwd': (i32, [vp, i32, vp, i32, vp, i32, i64, i32, i32, vp]),
             'b4c_sparse_ce_from_probs_bwd': (i32, [vp, i32, vp, vp, vp, i32, i64, i32, i32, i32, vp]),

@@ -48,7 +48,9 @@ def save_checkpoint(path, model, optimizer=None, epoch=0, metrics=None):
             v[names[id(p)]] = optimizer.v[o:o + p.numel()].detach().to('cpu', copy=True).view(p.shape)
         blob['optimizer'] = {'iterations': int(optimizer.iterations), 'lr': float(optimizer.lr),
                              'beta_1': float(optimizer.beta_1), 'beta_2': float(optimizer.beta_2),
-                             'epsilon': float(optimizer.epsilon), 'm': m, 'v': v}
+                             'epsilon': float(optimizer.epsilon), 'm': m, 'v': v,
+                             # for the record only: load_checkpoint does not restore it (optim.Adam's docstring)
+                             'weight_decay': getattr(optimizer, 'weight_decay', None)}
     tmp = path + '.tmp'
     torch.save(blob, tmp)
     os.replace(tmp, path)          # a crash never leaves a half-written "latest" checkpoint

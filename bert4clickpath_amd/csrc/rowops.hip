@@ -1053,9 +1053,23 @@ __device__ __forceinline__ void adam_elem(float &pp, float gk, float &mm, float 
     pp = pp - num / den;
 }
 
-__global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                                                   float *__restrict__ v, int64_t n, float lr_t, float b1, float b2,
-                                                   float eps, float gmul, const float *__restrict__ coef) {
+// decoupled weight decay of one element, one step (Keras AdamW: p <- p - (lr wd) p, applied BEFORE adam_elem and not through
+// the gradient).  d = fp32(lr(t - 1) * weight_decay), rounded once on the host.  The form chosen: ONE fp32 product d * p, then
+// ONE subtraction -- not p * (1 - d), not fma(-d, p, p) -- in the dense and in the row kernel alike (contraction off, as above).
+__device__ __forceinline__ void decay_elem(float &pp, float d) {
+#pragma clang fp contract(off)
+    const float dp = d * pp;
+    pp = pp - dp;
+}
+
+// DECAY: the AdamW form (b4c_adamw_step).  blocks[i] != 0: the 64 elements [64 i, 64 i + 64) of this range decay (every arena
+// slice is padded to 64 elements, so a block belongs to one parameter; a 16-byte group lies inside one block).  One byte per
+// 256 B of parameters rather than a sorted boundary list: no search per group, and the table is built once on the host.
+// Without DECAY this is the kernel as it was: d and blocks are dead arguments of an inlined function.
+template <bool DECAY>
+__device__ __forceinline__ void adam_body(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                          float *__restrict__ v, int64_t n, float lr_t, float b1, float b2, float eps, float gmul,
+                                          const float *__restrict__ coef, float d, const uint8_t *__restrict__ blocks) {
     // coef: the device's clip coefficient (gradnorm.hip), exactly 1.0f when nothing is clipped; NULL: no clipping.  The same
     // expression in adam_rows_kernel: one fp32 product, then g * that
     if (coef) gmul = gmul * *coef;
@@ -1063,9 +1077,11 @@ __global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const 
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         f32x4 pp = reinterpret_cast<f32x4 *>(p)[i], gg = reinterpret_cast<const f32x4 *>(g)[i];
         f32x4 mm = reinterpret_cast<f32x4 *>(m)[i], vv = reinterpret_cast<f32x4 *>(v)[i];
+        const bool dec = DECAY && blocks[i >> 4] != 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float pk = pp[k], mk = mm[k], vk = vv[k];
+            if (DECAY && dec) decay_elem(pk, d);
             adam_elem(pk, gg[k] * gmul, mk, vk, lr_t, b1, b2, eps);
             pp[k] = pk; mm[k] = mk; vv[k] = vk;
         }
@@ -1076,9 +1092,23 @@ __global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const 
     // tail
     for (int64_t i = (n4 << 2) + blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         float pk = p[i], mk = m[i], vk = v[i];
+        if (DECAY && blocks[i >> 6] != 0) decay_elem(pk, d);
         adam_elem(pk, g[i] * gmul, mk, vk, lr_t, b1, b2, eps);
         p[i] = pk; m[i] = mk; v[i] = vk;
     }
+}
+
+__global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                   float *__restrict__ v, int64_t n, float lr_t, float b1, float b2,
+                                                   float eps, float gmul, const float *__restrict__ coef) {
+    adam_body<false>(p, g, m, v, n, lr_t, b1, b2, eps, gmul, coef, 0.f, nullptr);
+}
+
+__global__ void __launch_bounds__(256) adamw_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                    float *__restrict__ v, int64_t n, float lr_t, float b1, float b2,
+                                                    float eps, float gmul, const float *__restrict__ coef, float d,
+                                                    const uint8_t *__restrict__ blocks) {
+    adam_body<true>(p, g, m, v, n, lr_t, b1, b2, eps, gmul, coef, d, blocks);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1095,13 +1125,18 @@ __global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const 
 // ids != NULL: one wave per entry of ids; a row that occurs several times is claimed once (atomicMax on its stamp).
 // ids == NULL: rows [row_lo, row_lo + n): each exactly once -- the rotating catch-up that bounds every row's staleness,
 //              the full catch-up in front of a checkpoint, and the dense fallback of a data-parallel step.
+// DECAY (b4c_adamw_rows; the table decays as a whole): every missed step s also applies decay_elem with that step's own
+// d_hist[s], so a row moves even with zero moments and both shortcuts of the plain form are gone: a row is replayed from its
+// stamp even when the stamp is 0, and whatever its moments.  For a group with m = v = 0 the Adam part of a zero-gradient step
+// is the identity (lr 0 / (0 + eps) = 0, p - 0 = p, given eps > 0), so its replay runs the decay line alone -- step by step,
+// never a closed form: p prod(1 - d_s) rounds differently from what the dense kernel did -- and its moments are not stored.
 // ------------------------------------------------------------------------------------------
-template <int MODE>
-__global__ void __launch_bounds__(256) adam_rows_kernel(float *__restrict__ p, float *__restrict__ g, float *__restrict__ m,
-                                                        float *__restrict__ v, int32_t *__restrict__ stamp,
-                                                        const int64_t *__restrict__ ids, int64_t n, int64_t row_lo, int64_t rows,
-                                                        int width, const float *__restrict__ lr_hist, int t, float b1, float b2,
-                                                        float eps, float gmul, const float *__restrict__ coef) {
+template <int MODE, bool DECAY>
+__device__ __forceinline__ void adam_rows_body(float *__restrict__ p, float *__restrict__ g, float *__restrict__ m,
+                                               float *__restrict__ v, int32_t *__restrict__ stamp,
+                                               const int64_t *__restrict__ ids, int64_t n, int64_t row_lo, int64_t rows,
+                                               int width, const float *__restrict__ lr_hist, const float *__restrict__ d_hist,
+                                               int t, float b1, float b2, float eps, float gmul, const float *__restrict__ coef) {
     if (MODE == 1 && coef) gmul = gmul * *coef;                // (as adam_kernel; replayed steps have g = 0 and need no past coefficient)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1122,7 +1157,7 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(float *__restrict__ p, f
     } else {
         r = row_lo + i;
         old = stamp[r];
-        if (old >= t || (MODE == 0 && old == 0)) return;       // (stamp 0: never touched, all moments zero -- nothing to replay)
+        if (old >= t || (!DECAY && MODE == 0 && old == 0)) return;   // (stamp 0: never touched, all moments zero -- nothing to replay)
     }
     const int t_replay = MODE == 0 ? t : t - 1;                // zero-gradient steps old + 1 .. t_replay
     for (int c = lane * 4; c < width; c += 256) {
@@ -1134,7 +1169,37 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(float *__restrict__ p, f
         // a row that never received a gradient has m = v = 0 and every zero-gradient step leaves it as it is
         const bool live = (mm[0] != 0.f) | (mm[1] != 0.f) | (mm[2] != 0.f) | (mm[3] != 0.f) | (vv[0] != 0.f) | (vv[1] != 0.f) |
                           (vv[2] != 0.f) | (vv[3] != 0.f);
-        if (old > 0 && live) {
+        if (DECAY) {
+            if (live) {
+                for (int s = old + 1; s <= t_replay; ++s) {
+                    const float d_s = d_hist[s], lr_s = lr_hist[s];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        decay_elem(pp[k], d_s);
+                        adam_elem(pp[k], 0.f, mm[k], vv[k], lr_s, b1, b2, eps);
+                    }
+                }
+            } else {
+                // two dependent operations per step: the loop waits for d_hist[s], not for arithmetic, so the factors are
+                // fetched eight steps at a time (one wait per eight steps; the same operations in the same order)
+                int s = old + 1;
+                for (; s + 7 <= t_replay; s += 8) {
+                    float d8[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) d8[j] = d_hist[s + j];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) decay_elem(pp[k], d8[j]);
+                    }
+                }
+                for (; s <= t_replay; ++s) {
+                    const float d_s = d_hist[s];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) decay_elem(pp[k], d_s);
+                }
+            }
+        } else if (old > 0 && live) {
             for (int s = old + 1; s <= t_replay; ++s) {
                 const float lr_s = lr_hist[s];
 #pragma unroll
@@ -1143,6 +1208,11 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(float *__restrict__ p, f
         }
         if (MODE == 1) {
             const float lr_t = lr_hist[t];
+            if (DECAY) {
+                const float d_t = d_hist[t];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) decay_elem(pp[k], d_t);
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k) adam_elem(pp[k], gg[k] * gmul, mm[k], vv[k], lr_t, b1, b2, eps);
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
@@ -1150,15 +1220,36 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(float *__restrict__ p, f
         }
         const f32x4 po = {pp[0], pp[1], pp[2], pp[3]}, mo = {mm[0], mm[1], mm[2], mm[3]}, vo = {vv[0], vv[1], vv[2], vv[3]};
         *reinterpret_cast<f32x4 *>(p + o) = po;
-        *reinterpret_cast<f32x4 *>(m + o) = mo;
-        *reinterpret_cast<f32x4 *>(v + o) = vo;
+        if (!DECAY || MODE == 1 || live) {                       // (a catch-up of zero moments leaves them zero)
+            *reinterpret_cast<f32x4 *>(m + o) = mo;
+            *reinterpret_cast<f32x4 *>(v + o) = vo;
+        }
     }
     if (!ids && lane == 0) stamp[r] = t;
 }
 
+template <int MODE>
+__global__ void __launch_bounds__(256) adam_rows_kernel(float *__restrict__ p, float *__restrict__ g, float *__restrict__ m,
+                                                        float *__restrict__ v, int32_t *__restrict__ stamp,
+                                                        const int64_t *__restrict__ ids, int64_t n, int64_t row_lo, int64_t rows,
+                                                        int width, const float *__restrict__ lr_hist, int t, float b1, float b2,
+                                                        float eps, float gmul, const float *__restrict__ coef) {
+    adam_rows_body<MODE, false>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, nullptr, t, b1, b2, eps, gmul, coef);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) adamw_rows_kernel(float *__restrict__ p, float *__restrict__ g, float *__restrict__ m,
+                                                         float *__restrict__ v, int32_t *__restrict__ stamp,
+                                                         const int64_t *__restrict__ ids, int64_t n, int64_t row_lo, int64_t rows,
+                                                         int width, const float *__restrict__ lr_hist,
+                                                         const float *__restrict__ d_hist, int t, float b1, float b2, float eps,
+                                                         float gmul, const float *__restrict__ coef) {
+    adam_rows_body<MODE, true>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, d_hist, t, b1, b2, eps, gmul, coef);
+}
+
 static int adam_rows_launch(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n, int64_t row_lo,
-                            int64_t rows, int width, const float *lr_hist, int t, float beta1, float beta2, float eps,
-                            float grad_mul, const float *coef, int mode, void *stream) {
+                            int64_t rows, int width, const float *lr_hist, const float *d_hist, int t, float beta1, float beta2,
+                            float eps, float grad_mul, const float *coef, int mode, void *stream) {
     B4C_REQUIRE(p && m && v && stamp && lr_hist && rows > 0 && width > 0 && t >= 0, "adam_rows: bad argument");
     B4C_REQUIRE(mode == 0 || (mode == 1 && g), "adam_rows: mode %d (0 = catch up, 1 = step; the step needs the gradient table)", mode);
     B4C_REQUIRE(width % 4 == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
@@ -1168,6 +1259,11 @@ static int adam_rows_launch(float *p, float *g, float *m, float *v, int32_t *sta
     if (n <= 0) return 0;
     const int64_t blocks = (n + 3) / 4;
     B4C_REQUIRE(blocks < (1ll << 31), "adam_rows: %lld rows in one call", (long long)n);
+    if (d_hist) {               // the AdamW form: NULL is the plain form, launched as it always was
+        if (mode == 0) adamw_rows_kernel<0><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, d_hist, t, beta1, beta2, eps, grad_mul, coef);
+        else adamw_rows_kernel<1><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, d_hist, t, beta1, beta2, eps, grad_mul, coef);
+        return b4c_check_launch("adamw_rows");
+    }
     if (mode == 0) adam_rows_kernel<0><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, coef);
     else adam_rows_kernel<1><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, coef);
     return b4c_check_launch("adam_rows");
@@ -1176,14 +1272,24 @@ static int adam_rows_launch(float *p, float *g, float *m, float *v, int32_t *sta
 extern "C" int b4c_adam_rows(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n, int64_t row_lo,
                              int64_t rows, int width, const float *lr_hist, int t, float beta1, float beta2, float eps,
                              float grad_mul, int mode, void *stream) {
-    return adam_rows_launch(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, nullptr, mode, stream);
+    return adam_rows_launch(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, nullptr, t, beta1, beta2, eps, grad_mul, nullptr, mode, stream);
 }
 
 extern "C" int b4c_adam_rows_clipped(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n,
                                      int64_t row_lo, int64_t rows, int width, const float *lr_hist, int t, float beta1, float beta2,
                                      float eps, float grad_mul, const float *coef, int mode, void *stream) {
     B4C_REQUIRE(coef && ((uintptr_t)coef & 3) == 0, "adam_rows_clipped: null / misaligned coefficient (b4c_adam_rows is the form without one)");
-    return adam_rows_launch(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, coef, mode, stream);
+    return adam_rows_launch(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, nullptr, t, beta1, beta2, eps, grad_mul, coef, mode, stream);
+}
+
+// AdamW for a row-sparse table that decays as a whole.  d_hist[s] = fp32(lr(s - 1) * weight_decay) of step s, beside lr_hist;
+// coef may be NULL (no clipping): one entry point for both.
+extern "C" int b4c_adamw_rows(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n, int64_t row_lo,
+                              int64_t rows, int width, const float *lr_hist, const float *decay_hist, int t, float beta1,
+                              float beta2, float eps, float grad_mul, const float *coef, int mode, void *stream) {
+    B4C_REQUIRE(decay_hist && ((uintptr_t)decay_hist & 3) == 0, "adamw_rows: null / misaligned decay history (b4c_adam_rows is the form without one)");
+    B4C_REQUIRE(((uintptr_t)coef & 3) == 0, "adamw_rows: misaligned coefficient");
+    return adam_rows_launch(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, decay_hist, t, beta1, beta2, eps, grad_mul, coef, mode, stream);
 }
 
 static int adam_step_launch(float *p, const float *g, float *m, float *v, int64_t n, float lr_t, float beta1, float beta2, float eps,
@@ -1203,4 +1309,19 @@ extern "C" int b4c_adam_step_clipped(float *p, const float *g, float *m, float *
                                      float eps, float grad_mul, const float *coef, void *stream) {
     B4C_REQUIRE(coef && ((uintptr_t)coef & 3) == 0, "adam_step_clipped: null / misaligned coefficient (b4c_adam_step is the form without one)");
     return adam_step_launch(p, g, m, v, n, lr_t, beta1, beta2, eps, grad_mul, coef, stream);
+}
+
+// AdamW over a dense range of the arena: elements of the 64-element blocks with decay_blocks[i] != 0 (ceil(n / 64) bytes, block
+// 0 = p[0, 64)) take p <- p - decay * p first, decay = fp32(lr(t - 1) * weight_decay); the others exactly b4c_adam_step.
+// coef may be NULL (no clipping).  One launch, whatever the number of parameters in the range.
+extern "C" int b4c_adamw_step(float *p, const float *g, float *m, float *v, int64_t n, float lr_t, float beta1, float beta2,
+                              float eps, float grad_mul, const float *coef, float decay, const uint8_t *decay_blocks,
+                              void *stream) {
+    B4C_REQUIRE(p && g && m && v && n > 0, "adamw_step: bad argument");
+    B4C_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adamw_step: pointers must be 16-byte aligned");
+    B4C_REQUIRE(((uintptr_t)coef & 3) == 0, "adamw_step: misaligned coefficient");
+    B4C_REQUIRE(decay_blocks, "adamw_step: null block table (b4c_adam_step is the form without decay)");
+    B4C_REQUIRE(decay >= 0.f && decay < INFINITY, "adamw_step: decay factor %g must be finite and >= 0", (double)decay);
+    adamw_kernel<<<grid_for(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, lr_t, beta1, beta2, eps, grad_mul, coef, decay, decay_blocks);
+    return b4c_check_launch("adamw_step");
 }

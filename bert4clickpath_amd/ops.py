@@ -1374,6 +1374,25 @@ def adam_rows_clipped_(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, 
                                               t, beta1, beta2, eps, grad_mul, _p(coef), mode, _st()), 'adam_rows_clipped')
 
 
+def adamw_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul, coef, decay, blocks):
+    """adam_step_ / adam_step_clipped_ (coef None / a device fp32 scalar) with decoupled weight decay: the elements of the
+    64-element blocks flagged in `blocks` (uint8, one per block of p) take p <- p - decay * p first (b4c_adamw_step)"""
+    with _record('adam', p.numel() * 28 + blocks.numel()):
+        L.check(L.lib().b4c_adamw_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr_t, beta1, beta2, eps, grad_mul, _p(coef), decay,
+                                       _p(blocks), _st()), 'adamw_step')
+
+
+def adamw_rows_(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, decay_hist, t, beta1, beta2, eps, grad_mul, coef, mode):
+    """adam_rows_ / adam_rows_clipped_ (coef None / a device fp32 scalar) for a table that decays: decay_hist[s] beside
+    lr_hist[s] (b4c_adamw_rows; booked as adam_rows_)"""
+    if n <= 0:
+        return
+    nrows = min(n, rec_hints.get('adam_distinct_rows', n)) if ids is not None else n
+    with _record('adam' if mode == 1 else 'adam_catch_up', nrows * width * (32 if mode == 1 else 24) + (n * 8 if ids is not None else 0)):
+        L.check(L.lib().b4c_adamw_rows(_p(p), _p(g), _p(m), _p(v), _p(stamp), _p(ids), n, row_lo, rows, width, _p(lr_hist),
+                                       _p(decay_hist), t, beta1, beta2, eps, grad_mul, _p(coef), mode, _st()), 'adamw_rows')
+
+
 def grad_chunks(n):
     """number of chunk partials of an arena of n elements (b4c_grad_sumsq)"""
     return (n + L.GRAD_CHUNK - 1) // L.GRAD_CHUNK

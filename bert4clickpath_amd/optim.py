@@ -2,12 +2,13 @@
 Adam(1e-3, beta_1=.9, beta_2=.999, epsilon=1e-9), constant lr) over one flat fp32 arena.  Beyond the reference's
 hard-coded recipe: `learning_rate` may be a schedule (a callable step -> lr, Keras' LearningRateSchedule convention;
 clickstream_transformer.training_utils has the reference's two) and `global_clipnorm` clips the gradient by its global L2
-norm, computed and applied on the device (csrc/gradnorm.hip).
+norm, computed and applied on the device (csrc/gradnorm.hip); `weight_decay` is Keras AdamW's decoupled decay.
 
 All parameters are re-homed into a single contiguous buffer (64-element aligned slices), gradients
 into a second one: the optimizer step is ONE HIP kernel launch over the arena and the data-parallel
 all-reduce works on contiguous buckets of the gradient arena (parallel.py)."""
 import math
+import struct
 
 import torch
 
@@ -55,6 +56,57 @@ class FlatArena:
         ops.zero_(self.grad)
 
 
+def _f32(x):
+    """the double x rounded to fp32 (to nearest), as a Python float: what a kernel argument and a device table both hold"""
+    return struct.unpack('f', struct.pack('f', x))[0]
+
+
+def no_decay_params(module):
+    """the BERT convention for Adam(exclude_from_weight_decay=...): every parameter with dim() < 2 -- LayerNorm gamma / beta and
+    every bias, the vocabulary head's among them.  Embedding tables and weight matrices decay."""
+    return [p for p in module.parameters() if p.dim() < 2]
+
+
+class StepHistory:
+    """One fp32 value per optimizer step (index = step, entry 0 unused) as the row kernels replay it: a host list in double and
+    a device table.  Entries of past steps never change; the table keeps its capacity: a step writes its own entry only (no
+    host sync); it is reallocated, twice as large, when it is full, and rewritten when entries change (record / rebuild)."""
+
+    def __init__(self, value_of):
+        self.value_of = value_of      # step -> the value under the optimizer's PRESENT settings (look-ahead, rebuild)
+        self.host, self.dev, self.valid = [0.0], None, 0
+
+    def record(self, t, value):
+        """step t is being taken with `value` (what the dense kernel is handed now)"""
+        if len(self.host) == t:
+            self.host.append(value)
+        else:                               # (pre-computed with settings that have changed since)
+            self.host[t:] = [value]
+            self.valid = min(self.valid, t)
+
+    def rebuild(self, t):
+        self.host = [0.0] + [self.value_of(s) for s in range(1, t + 1)]
+        self.valid = 0
+
+    def table(self, t, device):
+        """the device table, valid for steps 1 .. t"""
+        while len(self.host) <= t:
+            self.host.append(self.value_of(len(self.host)))
+        n = len(self.host)
+        if self.dev is None or self.dev.numel() < n:
+            cap = max(1024, 2 * n)
+            self.dev = ops.zeros(cap, dtype=torch.float32, device=device)
+            self.valid = 0
+        if self.valid < n:
+            lo = self.valid
+            if n - lo == 1:       # one entry per step: a fill (the value rounded to fp32 as below), stream-ordered behind the readers
+                self.dev[lo:n].fill_(self.host[lo])
+            else:
+                self.dev[lo:n].copy_(torch.tensor(self.host[lo:n], dtype=torch.float64).to(torch.float32))
+            self.valid = n
+        return self.dev
+
+
 class LazyRows:
     """Row-lazy Adam state of ONE row-sparse table of the arena (config 5's 2M-row tables; include/b4c.h b4c_adam_rows).
     `stamp[row]` = the last optimizer step the row is current through (0: never touched, all moments zero).  Whoever is
@@ -72,6 +124,7 @@ class LazyRows:
         self.touched = []          # id tensors (int64, contiguous) read / named since the last step
         self.all_rows = False      # the whole table takes the next step (dense fallback of a data-parallel exchange)
         self.cursor = 0            # next row of the rotating catch-up
+        self.decay = True          # the table takes weight decay, as a whole (Adam(exclude_from_weight_decay=...) clears it)
 
     def _slices(self):
         o, n = self.opt, self.rows * self.width
@@ -81,7 +134,12 @@ class LazyRows:
     def _launch(self, ids, n, row_lo, t, mode, grad_mul=1.0, coef=None):
         o = self.opt
         p, g, m, v = self._slices()
-        if coef is None:
+        if self.decay and o._decay_seen:
+            # AdamW: every replayed step decays with its own factor.  Also when weight_decay is None by now: the rows still
+            # owe the decayed steps they missed (a step taken without decay has the factor 0.0: p - 0 p = p)
+            ops.adamw_rows_(p, g, m, v, self.stamp, ids, n, row_lo, self.rows, self.width, o.lr_hist(t), o.decay_hist(t), t,
+                            o.beta_1, o.beta_2, o.epsilon, grad_mul, coef, mode)
+        elif coef is None:
             ops.adam_rows_(p, g, m, v, self.stamp, ids, n, row_lo, self.rows, self.width, o.lr_hist(t), t, o.beta_1, o.beta_2,
                            o.epsilon, grad_mul, mode)
         else:
@@ -149,7 +207,7 @@ class LazyRows:
 
 class Adam:
     def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-9, arena=None, order=None, lazy_rows=(),
-                 max_staleness=256, global_clipnorm=None):
+                 max_staleness=256, global_clipnorm=None, weight_decay=None, exclude_from_weight_decay=()):
         """learning_rate: a float, or a callable `step -> lr` called with the number of steps already taken (0 at the first
         step), as Keras calls a LearningRateSchedule.  `opt.lr` reads the current value; assigning to it (ReduceLROnPlateau)
         raises TypeError on a scheduled optimizer, as Keras does.  state_dict() / checkpoint.save_checkpoint store
@@ -163,26 +221,48 @@ class Adam:
         (csrc/gradnorm.hip: the reduction is defined by arena position) as long as the norm is finite; a non-finite norm makes
         the coefficient NaN and with it every parameter that takes the step.
 
+        weight_decay (Keras AdamW; None: off, today's launches exactly -- no extra buffer, no other entry point): a float >= 0.
+        A decayed parameter takes  p <- p - (lr * weight_decay) * p  first, with the plain learning rate of the step (the
+        schedule's value or the float, not the bias-corrected lr_t), and then the Adam update unchanged.  The decay does not go
+        through the gradient: grad_mul and the clip leave it alone and it does not enter the global norm.  A plain attribute:
+        it may be changed between steps, and each step is recorded with the factor it was taken with.  Parameters in
+        `exclude_from_weight_decay` (optim.no_decay_params(model) is the BERT convention) take exactly the update they take
+        without decay; a row-lazy table decays, or not, as a whole.  A never-touched row of a decayed table moves every step,
+        so the rotating catch-up and sync_rows() visit every row (max_staleness bounds the replay as before) and lazy == dense
+        still holds bit for bit.  Switching the decay on in mid-run first brings every row of the decayed tables up to date
+        and stamps it (launches, no host sync), so no row ever replays more than max_staleness steps.  state_dict() / checkpoint.save_checkpoint store `weight_decay` FOR THE RECORD ONLY: loading
+        does not restore it (the exclusion set cannot be stored, and half a recipe would mislead) -- the constructor's
+        arguments govern, as with a schedule.
+
         lazy_rows: 2-D (rows, width) parameters whose gradient is row-sparse (embedding tables, a vocabulary-major sampled
         projection): their share of the update runs over the rows in use only, with results bit-identical to the dense
         update (LazyRows).  Code that reads such a table as a whole calls `sync_rows()` first; `state_dict()` and
         checkpoint.save_checkpoint do."""
         self._learning_rate = learning_rate if callable(learning_rate) else float(learning_rate)
         self.global_clipnorm = global_clipnorm
+        self.lazy, self.iterations = [], 0
+        self._decay_seen = False                 # some step since reset_rows() may have decayed (set with weight_decay)
+        self.weight_decay = weight_decay
         self.last_grad_norm = None
         self._clip_bufs = None
         self.arena = arena or FlatArena(list(params), order)
         self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
         self.m = torch.zeros_like(self.arena.flat)
         self.v = torch.zeros_like(self.arena.flat)
-        self.iterations = 0
         self.max_staleness = int(max_staleness)
-        self.lazy = []
-        self._lr_host, self._lr_dev, self._lr_valid = [0.0], None, 0     # lr_t of every step so far (index = step)
+        self._lr = StepHistory(self._lr_t)       # lr_t of every step so far
+        self._wd = StepHistory(self._decay_t)    # the decay factor of every step so far, beside it
+        self._decay_blocks_dev = None
+        exclude = list(exclude_from_weight_decay)
+        for q in exclude:
+            if not any(q is p for p in self.arena.params):
+                raise ValueError('exclude_from_weight_decay names a parameter that is not in the optimizer\'s arena')
+        self._no_decay = {id(q) for q in exclude}
         self._grads_clean = False      # the lazy tables' gradient rows are all zero (left so by the last completed step)
         for p in lazy_rows:
             lo, _ = self.arena.slice_of(p)
             lz = LazyRows(self, p, lo)
+            lz.decay = id(p) not in self._no_decay
             p._b4c_lazy = lz
             self.lazy.append(lz)
         # the dense share of the arena: what is left between the lazy tables
@@ -208,6 +288,56 @@ class Adam:
         self._global_clipnorm = value
 
     @property
+    def weight_decay(self):
+        return self._weight_decay
+
+    @weight_decay.setter
+    def weight_decay(self, value):
+        if value is not None:
+            value = float(value)
+            if not (value >= 0.0 and math.isfinite(value)):
+                raise ValueError('weight_decay must be a finite number >= 0 or None, got %r' % (value,))
+            if not self._decay_seen:
+                self._start_decay()
+        self._weight_decay = value
+
+    def _start_decay(self):
+        """the decay is switched on: from here the decayed tables take the AdamW row kernel.  In mid-run the plain kernel has
+        left every never-touched row at stamp 0, and the AdamW kernel would replay the whole run so far for each of them on
+        its first visit, which is what max_staleness exists to prevent.  So every row is brought up to date with the plain
+        kernel (no step so far decayed) and stamped current -- launches only, and the notes of a forward pass already made
+        (LazyRows.touched) stay."""
+        if self.iterations > 0 and self.arena.flat.is_cuda:
+            for lz in self.lazy:
+                if lz.decay:
+                    lz.sync()
+                    lz.stamp.fill_(self.iterations)
+        self._decay_seen = True
+
+    # (the histories' parts under the names they had as plain attributes)
+    _lr_host = property(lambda self: self._lr.host)
+    _lr_dev = property(lambda self: self._lr.dev)
+    _wd_host = property(lambda self: self._wd.host)
+    _wd_dev = property(lambda self: self._wd.dev)
+
+    def decay_blocks_host(self):
+        """uint8 [arena.numel / 64]: 1 for every 64-element block of a parameter that decays.  Every arena slice starts at a
+        multiple of FlatArena.ALIGN = 64 and is padded to one, so no block belongs to two parameters; a parameter's padding
+        shares its last block (zeros stay zeros under the decay as under Adam)."""
+        A = FlatArena.ALIGN
+        a = self.arena
+        blocks = torch.zeros(a.numel // A, dtype=torch.uint8)
+        for p, o in zip(a.params, a.offsets):
+            if id(p) not in self._no_decay:
+                blocks[o // A:(o + p.numel() + A - 1) // A] = 1
+        return blocks
+
+    def _decay_blocks(self):
+        if self._decay_blocks_dev is None:       # built once (the one host-to-device copy of the decay, at its first step)
+            self._decay_blocks_dev = self.decay_blocks_host().to(self.arena.flat.device)
+        return self._decay_blocks_dev
+
+    @property
     def scheduled(self):
         return callable(self._learning_rate)
 
@@ -230,27 +360,25 @@ class Adam:
         lr = float(self._learning_rate(t - 1)) if self.scheduled else self._learning_rate
         return lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
 
+    def _decay_t(self, t):
+        """decay factor of step t: fp32(lr(t - 1) * weight_decay), the product in double, rounded once -- the dense kernel's
+        scalar and the row kernel's table entry are this same fp32 value.  0.0 while weight_decay is None."""
+        if self._weight_decay is None:
+            return 0.0
+        lr = float(self._learning_rate(t - 1)) if self.scheduled else self._learning_rate
+        return _f32(lr * self._weight_decay)
+
     def lr_hist(self, t):
         """device fp32 table of the lr_t of steps 1 .. t (what the dense kernel was / is handed at each of them): the replay of
         a missed step needs that step's own value.  Entries of past steps never change; a change of `self.lr` (ReduceLROnPlateau)
         shows from the step it first applies to.  The table keeps its capacity: a step writes its own entry only (no host sync);
         it is reallocated, twice as large, when it is full, and rewritten in place when past entries change (reset_rows)."""
-        while len(self._lr_host) <= t:
-            self._lr_host.append(self._lr_t(len(self._lr_host)))
-        n = len(self._lr_host)
-        if self._lr_dev is None or self._lr_dev.numel() < n:
-            cap = max(1024, 2 * n)
-            self._lr_dev = ops.zeros(cap, dtype=torch.float32, device=self.arena.flat.device)
-            self._lr_valid = 0
-        if self._lr_valid < n:
-            lo = self._lr_valid
-            if n - lo == 1:       # one entry per step: a fill (the value rounded to fp32 as below), stream-ordered behind the readers
-                self._lr_dev[lo:n].fill_(self._lr_host[lo])
-            else:
-                host = torch.tensor(self._lr_host[lo:n], dtype=torch.float64).to(torch.float32)
-                self._lr_dev[lo:n].copy_(host)
-            self._lr_valid = n
-        return self._lr_dev
+        return self._lr.table(t, self.arena.flat.device)
+
+    def decay_hist(self, t):
+        """device fp32 table of the decay factors of steps 1 .. t beside lr_hist: same capacity rule, one entry per step, no
+        host sync; a change of weight_decay or of lr shows from the step it first applies to"""
+        return self._wd.table(t, self.arena.flat.device)
 
     def zero_grad(self):
         if self.lazy and self._grads_clean:
@@ -276,28 +404,37 @@ class Adam:
             raise ops.B4CError('Adam.step runs on the HIP device only')
         ops.flush_pending_dw(a.ctx)
         ops.join_side_work(a.ctx)
-        self.iterations += 1
-        t = self.iterations
-        lr_t = self._lr_t(t)
+        t, lr_t, decay = self._begin_step()
         coef = self._clip_coef(grad_mul) if self._global_clipnorm is not None else None
         if not self.lazy:
-            self._adam_range(0, a.numel, lr_t, grad_mul, coef)
+            self._adam_range(0, a.numel, lr_t, grad_mul, coef, decay)
         else:
-            if len(self._lr_host) == t:
-                self._lr_host.append(lr_t)
-            else:                               # (pre-computed with an lr that has changed since)
-                self._lr_host[t:] = [lr_t]
-                self._lr_valid = min(self._lr_valid, t)
             for lo, hi in self.dense_ranges:
-                self._adam_range(lo, hi, lr_t, grad_mul, coef)
+                self._adam_range(lo, hi, lr_t, grad_mul, coef, decay)
             for lz in self.lazy:
                 lz.step(t, grad_mul, coef)
             self._grads_clean = True
         ops.bump_weights_epoch()
 
-    def _adam_range(self, lo, hi, lr_t, grad_mul, coef):
+    def _begin_step(self):
+        """the host side of a step: -> (t, lr_t, decay factor or None), all three as the dense kernel is handed them; with
+        row-lazy tables step t also enters the histories their kernels replay from"""
+        self.iterations += 1
+        t = self.iterations
+        lr_t = self._lr_t(t)
+        decay = self._decay_t(t) if self._weight_decay is not None else None
+        if self.lazy:
+            self._lr.record(t, lr_t)
+            self._wd.record(t, decay or 0.0)
+        return t, lr_t, decay
+
+    def _adam_range(self, lo, hi, lr_t, grad_mul, coef, decay=None):
         a = self.arena
-        if coef is None:
+        if decay is not None:
+            A = FlatArena.ALIGN      # (dense ranges start at slice boundaries: multiples of 64)
+            ops.adamw_step_(a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], lr_t, self.beta_1, self.beta_2, self.epsilon,
+                            grad_mul, coef, decay, self._decay_blocks()[lo // A:(hi + A - 1) // A])
+        elif coef is None:
             ops.adam_step_(a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], lr_t, self.beta_1, self.beta_2, self.epsilon,
                            grad_mul)
         else:
@@ -329,7 +466,8 @@ class Adam:
 
     def state_dict(self):
         self.sync_rows()
-        return {'iterations': self.iterations, 'm': self.m, 'v': self.v, 'lr': self.lr}
+        # (weight_decay: for the record only -- load_state_dict leaves the constructor's value alone)
+        return {'iterations': self.iterations, 'm': self.m, 'v': self.v, 'lr': self.lr, 'weight_decay': self._weight_decay}
 
     def load_state_dict(self, sd):
         self.iterations = int(sd['iterations'])
@@ -341,10 +479,11 @@ class Adam:
 
     def reset_rows(self):
         """after the moments / parameters were loaded from outside: every row counts as current through `iterations`; the lr_t
-        history of the steps before is rebuilt from the present lr, or by calling the schedule for each past step (nothing will
-        replay them)"""
-        self._lr_host = [0.0] + [self._lr_t(s) for s in range(1, self.iterations + 1)]
-        self._lr_valid = 0
+        and decay histories of the steps before are rebuilt from the present lr and weight_decay, or by calling the schedule
+        for each past step (nothing will replay them)"""
+        self._lr.rebuild(self.iterations)
+        self._wd.rebuild(self.iterations)
+        self._decay_seen = self._weight_decay is not None
         for lz in self.lazy:
             lz.stamp.fill_(self.iterations)
             lz.touched, lz.all_rows, lz.cursor = [], False, 0

@@ -51,6 +51,10 @@ def main():
     ap.add_argument('--warmup', type=int, default=0,
                     help='linear warm-up of the learning rate over this many steps, then linear decay to 0 at --steps (the '
                          'paper\'s shape, training_utils.WarmupLinearDecay); default 0: the constant 1e-3 of the reference')
+    ap.add_argument('--weight_decay', type=float, default=None,
+                    help='decoupled weight decay (AdamW; the paper uses 0.01) on every weight matrix and embedding table, not on '
+                         'biases and LayerNorm vectors (optim.no_decay_params); default: none.  The paper\'s recipe in full: '
+                         '--clipnorm 5 --warmup 100 --weight_decay 0.01')
     a = ap.parse_args()
     from bert4clickpath_amd import input_pipeline, optim
     from bert4clickpath_amd.clickstream_transformer.training_utils import WarmupLinearDecay
@@ -59,7 +63,8 @@ def main():
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
     model = build_model(data.V, a.dropout, dtype).cuda()
     lr = WarmupLinearDecay(1e-3, a.warmup, max(a.steps, a.warmup + 1)) if a.warmup > 0 else 1e-3
-    opt = optim.Adam(model.parameters(), learning_rate=lr, global_clipnorm=a.clipnorm)
+    opt = optim.Adam(model.parameters(), learning_rate=lr, global_clipnorm=a.clipnorm, weight_decay=a.weight_decay,
+                     exclude_from_weight_decay=optim.no_decay_params(model) if a.weight_decay is not None else ())
     T.set_dropout_seed(a.seed)
     t0, losses = time.perf_counter(), []
     for step, b in enumerate(data.train_batches(a.batch, a.seed, a.steps)):

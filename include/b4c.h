@@ -651,6 +651,23 @@ int b4c_adam_rows_clipped(float *p, float *g, float *m, float *v, int32_t *stamp
                           int64_t rows, int width, const float *lr_hist, int t, float beta1, float beta2, float eps, float grad_mul,
                           const float *coef, int mode, void *stream);
 
+/* ---- decoupled weight decay (Adam(weight_decay=...), Keras AdamW; the reference never decays: no oracle, the BERT4Rec paper's
+ * recipe) -- additive to ABI 12 ------------------------------------------------------------------------------------------------
+ * A decayed element takes  p <- p - decay * p  (one fp32 product, one subtraction) and then the Adam update of b4c_adam_step,
+ * unchanged.  decay = fp32(lr(t - 1) * weight_decay): the plain learning rate of the step, not lr_t, rounded once by the host.
+ * The decay does not go through the gradient (grad_mul and coef do not touch it).  coef may be NULL in both entry points: the
+ * clipped and the unclipped step share them.
+ *   b4c_adamw_step  over a dense range: decay_blocks[i] != 0 (uint8, ceil(n / 64) entries) marks the 64-element block
+ *                   p[64 i, 64 i + 64) as decayed; elements of the other blocks take exactly the update of b4c_adam_step.
+ *   b4c_adamw_rows  b4c_adam_rows for a table that decays as a whole: decay_hist[s] is the decay factor of step s beside
+ *                   lr_hist[s].  A row is replayed from its stamp even when that is 0 and when its moments are zero, one
+ *                   step at a time, so the table still equals the dense kernel's bit for bit. */
+int b4c_adamw_step(float *p, const float *g, float *m, float *v, int64_t n, float lr_t, float beta1, float beta2, float eps,
+                   float grad_mul, const float *coef, float decay, const uint8_t *decay_blocks, void *stream);
+int b4c_adamw_rows(float *p, float *g, float *m, float *v, int32_t *stamp, const int64_t *ids, int64_t n, int64_t row_lo,
+                   int64_t rows, int width, const float *lr_hist, const float *decay_hist, int t, float beta1, float beta2,
+                   float eps, float grad_mul, const float *coef, int mode, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
