@@ -8,15 +8,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('B4C_LIB_PATH') or os.path.join(_HERE, 'libb4c_hip.so')     # override: A/B of two builds (scratch)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')
 
-ABI_VERSION = 12      # include/b4c.h; b4c_abi_version() of the library must agree (the grad-norm and AdamW entry points are additive: still 12)
-F32, BF16 = 0, 1
-ACT_NONE, ACT_RELU = 0, 1
-CE_TF, CE_PLAIN = 0, 1
-MAX_FEATURES, MAX_TOPK = 4, 16
-MAX_EXCL = 1024       # B4C_MAX_EXCL: longest exclusion list per ranked row
-MAX_CAND = 1024       # B4C_MAX_CAND: longest candidate list per row
-GRAD_CHUNK, GRAD_GROUP = 1024, 4096     # B4C_GRAD_CHUNK / B4C_GRAD_GROUP: the gradient norm's chunk and group sizes
-
 
 class B4CError(RuntimeError):
     pass
@@ -36,13 +27,79 @@ class TNDesc(ctypes.Structure):
                 ('seg_width', ctypes.c_int32), ('ldw', ctypes.c_int32)]
 
 
+# The header is the one place a signature or a constant is written: the binding below is derived from its text.
+_CTYPES = {'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
+           'uint64_t': ctypes.c_uint64}
+
+
+def _header_text(header_path):
+    """include/b4c.h without its comments"""
+    try:
+        with open(header_path) as f:
+            return re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+    except OSError as e:
+        raise B4CError('cannot read the C header %s (%s): the binding is derived from it' % (header_path, e)) from None
+
+
+def _ctype(text, decl, is_return=False):
+    """ctypes type of one parameter (`const float *bias`, `int64_t M`) or return type.  Every pointer argument is c_void_p,
+    the HOST arrays (h_ids, h_dims, ...) too: c_void_p takes the ctypes arrays the callers build ((c_void_p * n)(...),
+    (c_int * n)(...)) as well as None and integers, where a typed POINTER would also check the element type."""
+    words = re.findall(r'\w+|\*', text)
+    if '*' in words:
+        if not is_return:
+            return ctypes.c_void_p
+        if words == ['const', 'char', '*']:
+            return ctypes.c_char_p
+    else:
+        words = [w for w in words if w != 'const']
+        if len(words) == (1 if is_return else 2) and words[0] in _CTYPES:      # (a parameter: its type and its name)
+            return _CTYPES[words[0]]
+    raise B4CError('include/b4c.h: unknown type %r in the declaration %r' % (' '.join(text.split()), decl))
+
+
+def parse_header(src):
+    """{name: (restype, [argtypes])} of every function the header text `src` (comments removed) declares.  Anything between two
+    `;` that is not a function declaration of known types raises: a skipped or guessed argument would shift all that follow."""
+    src = re.sub(r'^[ \t]*#.*$', '', src, flags=re.M)                                   # preprocessor lines
+    src = re.sub(r'typedef\s+struct\s*\{[^}]*\}\s*\w+\s*;', '', src)                   # b4c_pack_desc, b4c_tn_desc: PackDesc, TNDesc
+    src = re.sub(r'extern\s+"C"\s*\{|^\s*\}\s*$', '', src, flags=re.M)
+    table = {}
+    for decl in src.split(';'):
+        decl = ' '.join(decl.split())
+        if not decl:
+            continue
+        m = re.fullmatch(r'(.*?)\b(\w+) ?\(([^()]*)\)', decl)
+        if not m or not m.group(1).strip() or m.group(2) in table:
+            raise B4CError('include/b4c.h: cannot parse the declaration %r' % decl)
+        ret, name, args = m.groups()
+        args = [] if args.strip() == 'void' else [_ctype(a, decl) for a in args.split(',')]
+        table[name] = (_ctype(ret, decl, True), args)
+    return table
+
+
+def header_constants(src):
+    """{name: value} of the header's integer #defines (B4C_F32, B4C_MAX_TOPK, B4C_EINVAL, ...)"""
+    return {k: int(v) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(B4C_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$', src, flags=re.M)}
+
+
+def signatures(header_path=HEADER_PATH):
+    return parse_header(_header_text(header_path))
+
+
 def declared_symbols(header_path=HEADER_PATH):
     """Names of every function include/b4c.h declares (used by the symbol-export test)."""
-    with open(header_path) as f:
-        src = f.read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    return sorted(set(re.findall(r'\b(b4c_[a-z0-9_]+)\s*\(', src)))
+    return sorted(signatures(header_path))
 
+
+_C = header_constants(_header_text(HEADER_PATH))
+ABI_VERSION = _C['B4C_ABI_VERSION']       # b4c_abi_version() of the library must agree
+F32, BF16 = _C['B4C_F32'], _C['B4C_BF16']
+ACT_NONE, ACT_RELU = _C['B4C_ACT_NONE'], _C['B4C_ACT_RELU']
+CE_TF, CE_PLAIN = _C['B4C_CE_TF'], _C['B4C_CE_PLAIN']
+MAX_FEATURES, MAX_TOPK = _C['B4C_MAX_FEATURES'], _C['B4C_MAX_TOPK']
+MAX_EXCL, MAX_CAND = _C['B4C_MAX_EXCL'], _C['B4C_MAX_CAND']
+GRAD_CHUNK, GRAD_GROUP = _C['B4C_GRAD_CHUNK'], _C['B4C_GRAD_GROUP']
 
 _lib = None
 
@@ -64,119 +121,11 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        c = ctypes
-        vp, i32, i64, f32, u64 = c.c_void_p, c.c_int, c.c_int64, c.c_float, c.c_uint64
-        pp = c.POINTER(c.c_void_p)
-        sig = {
-            'b4c_abi_version': (i32, []),
-            'b4c_last_error': (c.c_char_p, []),
-            'b4c_keep': (i32, [u64, u64, f32]),
-            'b4c_embed_concat_pe_fwd': (i32, [i32, pp, pp, c.POINTER(i32), c.POINTER(i64), vp, f32, vp, i32, vp, i32, i32, i32, f32, u64, i32, vp]),
-            'b4c_embed_concat_pe_bwd': (i32, [i32, pp, pp, c.POINTER(i32), c.POINTER(i64), f32, vp, i32, i32, i32, i32, f32, u64, i32, vp]),
-            'b4c_embed_concat_pe_bwd_sorted': (i32, [i32, pp, pp, pp, c.POINTER(i32), c.POINTER(i64), f32, vp, i32, i32, i32, i32, f32, u64, i32, vp]),
-            'b4c_pack_weight': (i32, [vp, i32, i32, vp, i32, i32, i32, vp]),
-            'b4c_gemm_nt': (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp]),
-            'b4c_gemm_nt_add_ln': (i32, [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, u64, i32, vp]),
-            'b4c_gemm_dxdw_workspace_bytes': (i64, [i64, i32]),
-            'b4c_gemm_dxdw': (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, pp, pp, i32, i64, vp, i64, vp]),
-            'b4c_ffn_bwd_workspace_bytes': (i64, [i64]),
-            'b4c_ffn_bwd': (i32, [vp, vp, vp, vp, f32, u64, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, i64, vp, i64, vp]),
-            'b4c_ffn_fwd': (i32, [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i64, f32, f32, u64, vp]),
-            'b4c_attn_out_bwd_workspace_bytes': (i64, [i64]),
-            'b4c_attn_out_bwd': (i32, [vp, vp, vp, vp, f32, u64, vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, i64, vp]),
-            'b4c_gemm_tn_group_workspace_bytes': (i64, [vp, i32, i32]),
-            'b4c_gemm_tn_group': (i32, [vp, i32, i32, i32, vp, i64, vp]),
-            'b4c_gemm_tn_workspace_bytes': (i64, [i32, i32, i32, i32]),
-            'b4c_gemm_tn': (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i64, vp]),
-            'b4c_gemm_tn_seg': (i32, [vp, i32, vp, i32, i32, pp, pp, i32, i32, i32, i32, vp, i64, vp]),
-            'b4c_pack_weights_batched': (i32, [vp, i32, i32, i32, vp]),
-            'b4c_attn_fwd': (i32, [vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
-            'b4c_attn_bwd': (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
-            'b4c_attn_bwd_workspace_bytes': (i64, [i32, i32, i32, i32, i32]),
-            'b4c_attn_bwd_ws': (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp]),
-            'b4c_add_dropout_layernorm_fwd': (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, u64, i32, vp]),
-            'b4c_add_dropout_layernorm_bwd': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, u64, i32, vp]),
-            'b4c_add_dropout_layernorm_bwd_workspace_bytes': (i64, [i64, i32]),
-            'b4c_add_dropout_layernorm_bwd_ws': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, u64, vp, i64, i32, vp]),
-            'b4c_embed_concat_pe_bwd_sorted_workspace_bytes': (i64, [i32, c.POINTER(i32), i32, i32]),
-            'b4c_embed_concat_pe_bwd_sorted_ws': (i32, [i32, pp, pp, pp, c.POINTER(i32), c.POINTER(i64), f32, vp, i32, i32, i32, i32, f32, u64, vp, i64, i32, vp]),
-            'b4c_vocab_rank_workspace_bytes': (i64, [i64, i32, i32]),
-            'b4c_vocab_rank': (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i64, i64, i32, i32, vp]),
-            'b4c_rank_metrics': (i32, [vp, i64, i32, vp, vp, vp]),
-            'b4c_vocab_topk': (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]),
-            'b4c_poison_rows': (i32, [vp, i32, i64, i32, vp, i32, vp]),
-            'b4c_mask_positions': (i32, [vp, i32, i32, i64, vp, vp, vp, i32, vp, vp, vp]),
-            'b4c_padded_index': (i32, [vp, vp, vp, i32, i32, vp, vp]),
-            'b4c_gather_rows': (i32, [vp, i32, vp, vp, i32, i64, i32, i32, vp]),
-            'b4c_scatter_rows': (i32, [vp, i32, vp, vp, i32, i64, i64, i32, i32, vp]),
-            'b4c_softmax_rows': (i32, [vp, i32, vp, i32, i64, i32, i32, vp]),
-            'b4c_sparse_ce_from_probs': (i32, [vp, i32, vp, vp, vp, i64, i32, i32, i32, vp]),
-            'b4c_softmax_ce_fwd_bwd': (i32, [vp, i32, vp, vp, vp, i64, i32, i32, i32, vp]),
-            'b4c_vocab_ce_workspace_bytes': (i64, [i64, i32, i32]),
-            'b4c_vocab_ce_dw_workspace_bytes': (i64, [i64, i32, i32, i32]),
-            'b4c_vocab_ce_fwd': (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, vp]),
-            'b4c_vocab_ce_dw': (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, vp]),
-            'b4c_vocab_ce_dw_sweep': (i32, [vp, i32, vp, i32, vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
-            'b4c_vocab_ce_dw_labels': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, vp]),
-            'b4c_sort_ids_workspace_bytes': (i64, [i64, i32]),
-            'b4c_sort_ids': (i32, [vp, i64, i32, vp, vp, i64, vp]),
-            'b4c_gather_i64': (i32, [vp, vp, vp, i64, vp]),
-            'b4c_zero': (i32, [vp, i64, vp]),
-            'b4c_chain_ids': (i32, [vp, vp, vp, i32, i32, i64, i64, vp, i32, vp]),
-            'b4c_rows_add': (i32, [vp, i32, vp, vp, i32, i64, i32, i32, i32, vp]),
-            'b4c_attn_mq_fwd': (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
-            'b4c_attn_mq_bwd': (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
-            'b4c_label_scale': (i32, [vp, i64, i32, vp, vp]),
-            'b4c_sum_scaled': (i32, [vp, i64, vp, vp, vp, vp]),
-            'b4c_vocab_ce_apply_grad': (i32, [vp, i32, vp, vp, vp, i32, vp, i64, i32, vp]),
-            'b4c_relu_gate': (i32, [vp, vp, vp, i64, i32, vp]),
-            'b4c_vocab_lse': (i32, [vp, i32, vp, i32, vp, vp, vp, i64, i64, i32, i32, vp]),
-            'b4c_gemm_nt_softmax': (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
-            'b4c_topk_rows': (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, i32, vp]),
-            'b4c_topk_rows_ws': (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
-            'b4c_exclusions_prep': (i32, [vp, i32, i64, i32, i32, vp, vp, vp]),
-            'b4c_vocab_rank_excl': (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, i32, vp]),
-            'b4c_vocab_topk_excl': (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, i32, i32, vp]),
-            'b4c_topk_rows_excl': (i32, [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp]),
-            'b4c_sample_candidates': (i32, [vp, i64, i32, i32, u64, i64, vp, i32, i32, vp, vp, i32, vp, vp]),
-            'b4c_candidate_score': (i32, [vp, i32, vp, i32, vp, vp, i32, i64, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp]),
-            'b4c_candidate_rank_rows': (i32, [vp, i32, i32, vp, i32, i64, i32, i32, vp, vp, i32, vp, vp]),
-            'b4c_adam_step': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
-            'b4c_adam_rows': (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, i32, f32, f32, f32, f32, i32, vp]),
-            'b4c_grad_sumsq': (i32, [vp, i64, i64, i64, vp, vp]),
-            'b4c_grad_sumsq_rows': (i32, [vp, i64, i64, i64, i32, vp, i64, vp, vp]),
-            'b4c_grad_clip_coef': (i32, [vp, i64, vp, i64, f32, f32, vp, vp, vp]),
-            'b4c_adam_step_clipped': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, vp]),
-            'b4c_adam_rows_clipped': (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, i32, f32, f32, f32, f32, vp, i32, vp]),
-            'b4c_adamw_step': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, vp]),
-            'b4c_adamw_rows': (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, vp, i32, f32, f32, f32, f32, vp, i32, vp]),
-            'b4c_dropout': (i32, [vp, vp, i64, f32, u64, i32, vp]),
-            'b4c_softmax_rows_bwd': (i32, [vp, i32, vp, i32, vp, i32, i64, i32, i32, vp]),
-            'b4c_sparse_ce_from_probs_bwd': (i32, [vp, i32, vp, vp, vp, i32, i64, i32, i32, i32, vp]),
-            'b4c_sigmoid_fwd': (i32, [vp, vp, i64, i32, vp]),
-            'b4c_sigmoid_bwd': (i32, [vp, vp, vp, i64, i32, vp]),
-            'b4c_masked_bce': (i32, [vp, vp, f32, vp, vp, vp, i64, i32, vp]),
-            'b4c_binary_counts': (i32, [vp, vp, vp, i64, i32, vp]),
-            'b4c_compact_labels': (i32, [vp, i32, i32, vp, vp, vp, vp, i32, vp]),
-            'b4c_attn_weights': (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-            'b4c_transpose_add': (i32, [vp, i32, vp, i32, i32, i32, vp]),
-            'b4c_log_uniform_sample': (i32, [u64, i32, i64, vp, vp, vp]),
-            'b4c_row_dot': (i32, [vp, i32, vp, i32, vp, i64, i32, i32, vp]),
-            'b4c_sampled_ce_fwd_bwd': (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, vp]),
-            'b4c_scatter_add_1d': (i32, [vp, vp, vp, i64, vp]),
-            'b4c_row_scale_f32': (i32, [vp, i32, vp, vp, i32, i64, i32, i32, vp]),
-            'b4c_nonpad_positions': (i32, [vp, i32, i32, i64, vp, vp, vp, i32, vp, vp, vp]),
-            'b4c_remap_index': (i32, [vp, vp, vp, i64, vp]),
-            'b4c_embed_concat_pe_fwd_packed': (i32, [i32, pp, pp, c.POINTER(i32), c.POINTER(i64), vp, f32, vp, i32, vp, i32, i32, i32, f32, u64, vp, i64, i32, vp]),
-            'b4c_attn_fwd_varlen': (i32, [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
-            'b4c_attn_bwd_varlen': (i32, [vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, i32, vp]),
-            'b4c_rows_gather_f32': (i32, [vp, i32, vp, vp, i32, i64, i32, vp]),
-            'b4c_rows_scatter_add_f32': (i32, [vp, i32, vp, vp, i32, i64, i32, vp]),
-        }
-        # The argument lists below belong to ONE ABI version: a library that exports the same names with older lists would
+        sig = signatures()
+        # The argument lists of the header belong to ONE ABI version: a library that exports the same names with older lists would
         # take a device pointer for a stream and fault on the GPU.  Compare before anything is bound.
         try:
-            L.b4c_abi_version.restype = i32
+            L.b4c_abi_version.restype = ctypes.c_int
             have = int(L.b4c_abi_version())
         except AttributeError:
             raise B4CError('%s does not export b4c_abi_version: not a libb4c_hip.so of this tree; rebuild it '

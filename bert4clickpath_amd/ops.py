@@ -1340,57 +1340,36 @@ def candidate_rank_rows(scores, V, cand, labels=None, k=0):
                                                 _st()), 'candidate_rank_rows')
     return rank, idx
 
-def adam_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul=1.0):
-    with _record('adam', p.numel() * 28):
-        L.check(L.lib().b4c_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr_t, beta1, beta2, eps, grad_mul, _st()),
-                'adam_step')
+def adam_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul=1.0, coef=None, decay=None, blocks=None):
+    """Dense Adam over a flat fp32 range (b4c_adam_step).  coef (device fp32 scalar of grad_clip_coef_): the gradient is scaled by
+    grad_mul * coef[0] (b4c_adam_step_clipped).  decay: decoupled weight decay -- the elements of the 64-element blocks flagged in
+    `blocks` (uint8, one per block of p) take p <- p - decay * p first (b4c_adamw_step; coef may still be None)."""
+    lib, args = L.lib(), (_p(p), _p(g), _p(m), _p(v), p.numel(), lr_t, beta1, beta2, eps, grad_mul)
+    with _record('adam', p.numel() * 28 + (blocks.numel() if decay is not None else 0)):
+        if decay is not None:
+            L.check(lib.b4c_adamw_step(*args, _p(coef), decay, _p(blocks), _st()), 'adamw_step')
+        elif coef is not None:
+            L.check(lib.b4c_adam_step_clipped(*args, _p(coef), _st()), 'adam_step_clipped')
+        else:
+            L.check(lib.b4c_adam_step(*args, _st()), 'adam_step')
 
 
-def adam_rows_(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, mode):
+def adam_rows_(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, mode, coef=None, decay_hist=None):
     """b4c_adam_rows over one row-sparse table of the arena (optim.LazyRows): mode 0 = bring rows to step t, 1 = take step t.
+    coef (device fp32 scalar): the step's gradient is scaled by grad_mul * coef[0] (b4c_adam_rows_clipped).  decay_hist: the table
+    decays, decay_hist[s] beside lr_hist[s] (b4c_adamw_rows; coef may still be None).
     Booked bytes: the rows NAMED (an upper bound of the distinct rows; rec_hints['adam_distinct_rows'] when the host knows it)."""
     if n <= 0:
         return
     nrows = min(n, rec_hints.get('adam_distinct_rows', n)) if ids is not None else n
+    lib, args = L.lib(), (_p(p), _p(g), _p(m), _p(v), _p(stamp), _p(ids), n, row_lo, rows, width, _p(lr_hist))
     with _record('adam' if mode == 1 else 'adam_catch_up', nrows * width * (32 if mode == 1 else 24) + (n * 8 if ids is not None else 0)):
-        L.check(L.lib().b4c_adam_rows(_p(p), _p(g), _p(m), _p(v), _p(stamp), _p(ids), n, row_lo, rows, width, _p(lr_hist), t,
-                                      beta1, beta2, eps, grad_mul, mode, _st()), 'adam_rows')
-
-
-def adam_step_clipped_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul, coef):
-    """adam_step_ with the gradient scaled by grad_mul * coef[0] (coef: device fp32 scalar of grad_clip_coef_)"""
-    with _record('adam', p.numel() * 28):
-        L.check(L.lib().b4c_adam_step_clipped(_p(p), _p(g), _p(m), _p(v), p.numel(), lr_t, beta1, beta2, eps, grad_mul, _p(coef),
-                                              _st()), 'adam_step_clipped')
-
-
-def adam_rows_clipped_(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, t, beta1, beta2, eps, grad_mul, coef, mode):
-    """adam_rows_ with the step's gradient scaled by grad_mul * coef[0] (booked as adam_rows_)"""
-    if n <= 0:
-        return
-    nrows = min(n, rec_hints.get('adam_distinct_rows', n)) if ids is not None else n
-    with _record('adam' if mode == 1 else 'adam_catch_up', nrows * width * (32 if mode == 1 else 24) + (n * 8 if ids is not None else 0)):
-        L.check(L.lib().b4c_adam_rows_clipped(_p(p), _p(g), _p(m), _p(v), _p(stamp), _p(ids), n, row_lo, rows, width, _p(lr_hist),
-                                              t, beta1, beta2, eps, grad_mul, _p(coef), mode, _st()), 'adam_rows_clipped')
-
-
-def adamw_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul, coef, decay, blocks):
-    """adam_step_ / adam_step_clipped_ (coef None / a device fp32 scalar) with decoupled weight decay: the elements of the
-    64-element blocks flagged in `blocks` (uint8, one per block of p) take p <- p - decay * p first (b4c_adamw_step)"""
-    with _record('adam', p.numel() * 28 + blocks.numel()):
-        L.check(L.lib().b4c_adamw_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr_t, beta1, beta2, eps, grad_mul, _p(coef), decay,
-                                       _p(blocks), _st()), 'adamw_step')
-
-
-def adamw_rows_(p, g, m, v, stamp, ids, n, row_lo, rows, width, lr_hist, decay_hist, t, beta1, beta2, eps, grad_mul, coef, mode):
-    """adam_rows_ / adam_rows_clipped_ (coef None / a device fp32 scalar) for a table that decays: decay_hist[s] beside
-    lr_hist[s] (b4c_adamw_rows; booked as adam_rows_)"""
-    if n <= 0:
-        return
-    nrows = min(n, rec_hints.get('adam_distinct_rows', n)) if ids is not None else n
-    with _record('adam' if mode == 1 else 'adam_catch_up', nrows * width * (32 if mode == 1 else 24) + (n * 8 if ids is not None else 0)):
-        L.check(L.lib().b4c_adamw_rows(_p(p), _p(g), _p(m), _p(v), _p(stamp), _p(ids), n, row_lo, rows, width, _p(lr_hist),
-                                       _p(decay_hist), t, beta1, beta2, eps, grad_mul, _p(coef), mode, _st()), 'adamw_rows')
+        if decay_hist is not None:
+            L.check(lib.b4c_adamw_rows(*args, _p(decay_hist), t, beta1, beta2, eps, grad_mul, _p(coef), mode, _st()), 'adamw_rows')
+        elif coef is not None:
+            L.check(lib.b4c_adam_rows_clipped(*args, t, beta1, beta2, eps, grad_mul, _p(coef), mode, _st()), 'adam_rows_clipped')
+        else:
+            L.check(lib.b4c_adam_rows(*args, t, beta1, beta2, eps, grad_mul, mode, _st()), 'adam_rows')
 
 
 def grad_chunks(n):

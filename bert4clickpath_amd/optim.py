@@ -134,19 +134,12 @@ class LazyRows:
     def _launch(self, ids, n, row_lo, t, mode, grad_mul=1.0, coef=None):
         o = self.opt
         p, g, m, v = self._slices()
-        if self.decay and o._decay_seen:
-            # AdamW: every replayed step decays with its own factor.  Also when weight_decay is None by now: the rows still
-            # owe the decayed steps they missed (a step taken without decay has the factor 0.0: p - 0 p = p)
-            ops.adamw_rows_(p, g, m, v, self.stamp, ids, n, row_lo, self.rows, self.width, o.lr_hist(t), o.decay_hist(t), t,
-                            o.beta_1, o.beta_2, o.epsilon, grad_mul, coef, mode)
-        elif coef is None:
-            ops.adam_rows_(p, g, m, v, self.stamp, ids, n, row_lo, self.rows, self.width, o.lr_hist(t), t, o.beta_1, o.beta_2,
-                           o.epsilon, grad_mul, mode)
-        else:
-            # the clip coefficient scales the gradient of step t alone: the zero-gradient steps a row replays (here and in
-            # catch_up / sync) are g = 0 whatever was clipped at the time, so no past coefficient is ever needed
-            ops.adam_rows_clipped_(p, g, m, v, self.stamp, ids, n, row_lo, self.rows, self.width, o.lr_hist(t), t, o.beta_1,
-                                   o.beta_2, o.epsilon, grad_mul, coef, mode)
+        # coef, the clip coefficient, scales the gradient of step t alone: the zero-gradient steps a row replays (here and in
+        # catch_up / sync) are g = 0 whatever was clipped at the time, so no past coefficient is ever needed.
+        # decay_hist (AdamW): every replayed step decays with its own factor.  Also when weight_decay is None by now: the rows
+        # still owe the decayed steps they missed (a step taken without decay has the factor 0.0: p - 0 p = p)
+        ops.adam_rows_(p, g, m, v, self.stamp, ids, n, row_lo, self.rows, self.width, o.lr_hist(t), t, o.beta_1, o.beta_2, o.epsilon,
+                       grad_mul, mode, coef, o.decay_hist(t) if self.decay and o._decay_seen else None)
 
     @staticmethod
     def _ids(ids):
@@ -430,16 +423,10 @@ class Adam:
 
     def _adam_range(self, lo, hi, lr_t, grad_mul, coef, decay=None):
         a = self.arena
-        if decay is not None:
-            A = FlatArena.ALIGN      # (dense ranges start at slice boundaries: multiples of 64)
-            ops.adamw_step_(a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], lr_t, self.beta_1, self.beta_2, self.epsilon,
-                            grad_mul, coef, decay, self._decay_blocks()[lo // A:(hi + A - 1) // A])
-        elif coef is None:
-            ops.adam_step_(a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], lr_t, self.beta_1, self.beta_2, self.epsilon,
-                           grad_mul)
-        else:
-            ops.adam_step_clipped_(a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], lr_t, self.beta_1, self.beta_2,
-                                   self.epsilon, grad_mul, coef)
+        A = FlatArena.ALIGN      # (dense ranges start at slice boundaries: multiples of 64)
+        blocks = self._decay_blocks()[lo // A:(hi + A - 1) // A] if decay is not None else None
+        ops.adam_step_(a.flat[lo:hi], a.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], lr_t, self.beta_1, self.beta_2, self.epsilon,
+                       grad_mul, coef, decay, blocks)
 
     def _clip_coef(self, grad_mul):
         """the device's clip coefficient of this step (fp32 [1]); also sets last_grad_norm.  Launches only: no host sync.

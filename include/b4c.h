@@ -47,6 +47,8 @@ extern "C" {
 #define B4C_CE_TF 0    /* clip[1e-7,1-1e-7] -> log -> log-softmax (tf.keras.backend, TF 2.3.1) */
 #define B4C_CE_PLAIN 1 /* -log p_y                                                            */
 
+#define B4C_ABI_VERSION 12   /* what b4c_abi_version() returns; additive entry points (new names, no signature changed) keep it */
+
 int b4c_abi_version(void);
 const char *b4c_last_error(void);
 

@@ -10,6 +10,8 @@
 
 The float64 AdamW restated here (the reference never decays, so oracle/numpy_ref has none):
     P <- P - (lr * wd) * P;   P, M, V <- numpy_ref.adam_step(P, g, M, V, t, lr)        with lr the plain rate of step t."""
+import contextlib
+import inspect
 import math
 import os
 
@@ -24,6 +26,33 @@ from test_gpu_lazy_training import B1, B2, EPS, _grad_schedule, _lr_t, _magnitud
 pytestmark = pytest.mark.gpu
 
 WD = 0.01
+
+
+@contextlib.contextmanager
+def _adamw_calls():
+    """-> a dict that counts, while the block runs, the calls of ops.adam_step_ / ops.adam_rows_ that carry a decay ('step',
+    'rows') and the calls that reach the C entry points b4c_adamw_step / b4c_adamw_rows: a decayed call that the wrapper
+    routed to b4c_adam_step / b4c_adam_rows (or their clipped forms) would leave the C count behind"""
+    from bert4clickpath_amd import _lib, ops
+    lib = _lib.lib()
+    n = {'step': 0, 'rows': 0, 'b4c_adamw_step': 0, 'b4c_adamw_rows': 0}
+    prev = [(ops, 'adam_step_', 'step', 'decay'), (ops, 'adam_rows_', 'rows', 'decay_hist'),
+            (lib, 'b4c_adamw_step', 'b4c_adamw_step', None), (lib, 'b4c_adamw_rows', 'b4c_adamw_rows', None)]
+    prev = [(obj, name, key, arg, getattr(obj, name)) for obj, name, key, arg in prev]
+
+    def counted(fn, key, arg):
+        def f(*a, **k):
+            if arg is None or inspect.signature(fn).bind(*a, **k).arguments.get(arg) is not None:
+                n[key] += 1
+            return fn(*a, **k)
+        return f
+    for obj, name, key, arg, fn in prev:
+        setattr(obj, name, counted(fn, key, arg))
+    try:
+        yield n
+    finally:
+        for obj, name, key, arg, fn in prev:
+            setattr(obj, name, fn)
 
 
 # ---- 1. lazy == dense ------------------------------------------------------------------------------------------------------
@@ -129,24 +158,14 @@ def test_decay_switched_on_in_mid_run(rows, width, staleness):
 # ---- 2., 3. exclusions, zero decay, None ----------------------------------------------------------------------------------------
 def _mixed_run(steps=12, clip=None, count=None, **kw):
     """two dense vectors, two lazy tables and a ragged tail in one arena, fixed gradients -> {name: final values}, m, v"""
-    from bert4clickpath_amd import ops, optim
+    from bert4clickpath_amd import optim
     g = torch.Generator().manual_seed(11)
     shapes = dict(a=(1000,), b=(130,), t1=(400, 16), t2=(300, 8), c=(77,), tail=(37,))
     P = {k: torch.nn.Parameter((torch.randn(*s, generator=g) * 0.5).cuda()) for k, s in shapes.items()}
     excl = [P[k] for k in kw.pop('exclude', ())]
     opt = optim.Adam(list(P.values()), lazy_rows=[P['t1'], P['t2']], max_staleness=5, global_clipnorm=clip,
                      exclude_from_weight_decay=excl, **kw)
-    calls = {'adamw_step_': 0, 'adamw_rows_': 0}
-    prev = {k: getattr(ops, k) for k in calls}
-
-    def counted(name):
-        def f(*a, **k):
-            calls[name] += 1
-            return prev[name](*a, **k)
-        return f
-    for k in calls:
-        setattr(ops, k, counted(k))
-    try:
+    with _adamw_calls() as calls:
         rng = np.random.default_rng(5)
         for step in range(1, steps + 1):
             opt.zero_grad()
@@ -162,9 +181,6 @@ def _mixed_run(steps=12, clip=None, count=None, **kw):
             opt.step(0.5 if step % 3 == 0 else 1.0)
         sd = opt.state_dict()
         torch.cuda.synchronize()
-    finally:
-        for k in calls:
-            setattr(ops, k, prev[k])
     if count is not None:
         count.update(calls)
     return {k: p.detach().clone() for k, p in P.items()}, sd['m'].clone(), sd['v'].clone(), opt
@@ -177,7 +193,8 @@ def test_excluded_parameters_take_exactly_the_update_without_decay(clip):
     base, m0, v0, o0 = _mixed_run(clip=clip)
     n = {}
     dec, m1, v1, o1 = _mixed_run(clip=clip, weight_decay=WD, exclude=('b', 't2', 'c'), count=n)
-    assert len(o1.dense_ranges) >= 1 and n['adamw_step_'] == 12 * len(o1.dense_ranges) and n['adamw_rows_'] > 0
+    assert len(o1.dense_ranges) >= 1 and n['b4c_adamw_step'] == n['step'] == 12 * len(o1.dense_ranges)
+    assert n['rows'] >= n['b4c_adamw_rows'] > 0           # (a call that names no row launches nothing)
     for k in ('b', 't2', 'c'):
         assert torch.equal(base[k], dec[k]), k
     for k in ('a', 't1', 'tail'):
@@ -197,9 +214,9 @@ def test_zero_weight_decay_changes_no_bit_and_none_launches_nothing_new(clip):
     n_none, n_zero = {}, {}
     base, m0, v0, o0 = _mixed_run(clip=clip, count=n_none)
     zero, m1, v1, o1 = _mixed_run(clip=clip, weight_decay=0.0, count=n_zero)
-    assert n_none == {'adamw_step_': 0, 'adamw_rows_': 0}, n_none
+    assert n_none == {'step': 0, 'rows': 0, 'b4c_adamw_step': 0, 'b4c_adamw_rows': 0}, n_none
     assert o0._wd_dev is None and o0._decay_blocks_dev is None           # no extra buffer either
-    assert n_zero['adamw_step_'] > 0 and n_zero['adamw_rows_'] > 0, n_zero
+    assert n_zero['b4c_adamw_step'] == n_zero['step'] > 0 and n_zero['rows'] >= n_zero['b4c_adamw_rows'] > 0, n_zero
     for k in base:
         assert torch.equal(base[k], zero[k]), k
     assert torch.equal(m0, m1) and torch.equal(v0, v1)
@@ -391,36 +408,35 @@ def _worker(rank, world, port, out_dir, fill):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank if multi else 0), B4C_DIST_BACKEND='nccl' if multi else 'gloo',
                       HSA_ENABLE_IPC_MODE_LEGACY='0')
-    from bert4clickpath_amd import ops, optim, parallel
+    from bert4clickpath_amd import optim, parallel
     parallel.init_distributed()
     torch.cuda.set_device(rank if multi else 0)
     model = _pmodel()
     table = model.transformer.embedding_layers['items'].weight
     opt = optim.Adam(model.parameters(), lazy_rows=[table], max_staleness=4, global_clipnorm=0.05, weight_decay=WD,
                      exclude_from_weight_decay=optim.no_decay_params(model))
-    calls, prev = [], ops.adamw_rows_
-    ops.adamw_rows_ = lambda *a, **k: (calls.append(1), prev(*a, **k))[1]
-    head_end = max(opt.arena.slice_of(p)[1] for n, p in model.named_parameters() if n.startswith('head.'))
-    red = parallel.GradReducer(opt.arena, bucket_bounds=[head_end], reduce='mean', sparse_params=[table], sparse_max_fill=fill)
-    items, labels, flat = _batch(rank)
-    table0 = table.detach().clone()
-    kinds = []
-    for step in range(3):
-        opt.zero_grad()
-        red.begin_backward()
-        loss = model.cloze_loss({'asin': items}, labels, training=True, flat_idx=flat)
-        loss.backward()
-        ids = torch.cat([torch.full((items.shape[0], 2), 3, device=items.device), items,
-                         torch.full((items.shape[0], 1), 4, device=items.device)], dim=1)
-        ids[:, 1] = 4
-        red.set_touched_rows(table, ids)
-        red.finish()
-        kinds.append(red.last_exchange[id(table)])
-        opt.step(red.grad_mul)
-        assert float(table.grad.abs().max()) == 0.0
-    opt.sync_rows()
-    torch.cuda.synchronize()
-    assert calls, 'the decayed table never reached b4c_adamw_rows'
+    with _adamw_calls() as calls:
+        head_end = max(opt.arena.slice_of(p)[1] for n, p in model.named_parameters() if n.startswith('head.'))
+        red = parallel.GradReducer(opt.arena, bucket_bounds=[head_end], reduce='mean', sparse_params=[table], sparse_max_fill=fill)
+        items, labels, flat = _batch(rank)
+        table0 = table.detach().clone()
+        kinds = []
+        for step in range(3):
+            opt.zero_grad()
+            red.begin_backward()
+            loss = model.cloze_loss({'asin': items}, labels, training=True, flat_idx=flat)
+            loss.backward()
+            ids = torch.cat([torch.full((items.shape[0], 2), 3, device=items.device), items,
+                             torch.full((items.shape[0], 1), 4, device=items.device)], dim=1)
+            ids[:, 1] = 4
+            red.set_touched_rows(table, ids)
+            red.finish()
+            kinds.append(red.last_exchange[id(table)])
+            opt.step(red.grad_mul)
+            assert float(table.grad.abs().max()) == 0.0
+        opt.sync_rows()
+        torch.cuda.synchronize()
+    assert calls['rows'] >= calls['b4c_adamw_rows'] > 0, 'the decayed table never reached b4c_adamw_rows: %r' % calls
     moved = (table.detach() != table0).any(dim=1) | (table0 == 0).all(dim=1)        # (an all-zero row has nothing to decay)
     assert bool(moved.all()), 'rows of the decayed table that did not move: %d' % int((~moved).sum())
     np.save(os.path.join(out_dir, 'rank%d.npy' % rank), opt.arena.flat.cpu().numpy())

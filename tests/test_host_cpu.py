@@ -21,6 +21,56 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().b4c_abi_version() == _lib.ABI_VERSION == 12
 
 
+def test_binding_is_derived_from_the_header(tmp_path):
+    """_lib binds every entry point with the argument list include/b4c.h declares, and takes its constants from the header's
+    #defines; what the parser does not understand is an error that names the declaration, never a guess."""
+    import re
+    from ctypes import c_char_p, c_float as f32, c_int as i32, c_int64 as i64, c_uint64 as u64, c_void_p as vp
+    from bert4clickpath_amd import _lib
+    sig = _lib.signatures()
+    assert sorted(sig) == _lib.declared_symbols() and len(sig) == len(_lib.declared_symbols()) >= 104
+    assert sig['b4c_abi_version'] == (i32, [])
+    assert sig['b4c_last_error'] == (c_char_p, [])
+    ws = [n for n in sig if n.endswith('_workspace_bytes')]
+    assert len(ws) >= 12 and all(sig[n][0] is i64 for n in ws)
+    assert all(res is i32 for n, (res, args) in sig.items() if n not in ws and n != 'b4c_last_error')
+    assert sig['b4c_gemm_nt'] == (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp])
+    assert sig['b4c_embed_concat_pe_fwd'] == (i32, [i32, vp, vp, vp, vp, vp, f32, vp, i32, vp, i32, i32, i32, f32, u64, i32, vp])
+    assert sig['b4c_adamw_rows'] == (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, vp, i32, f32, f32, f32, f32, vp, i32, vp])
+    L = _lib.lib()                      # ... and these are the lists the loaded library carries
+    for n, (res, args) in sig.items():
+        assert getattr(L, n).restype is res and list(getattr(L, n).argtypes) == args, n
+
+    ok = 'int b4c_a(void);\nconst char *b4c_b(void);\nint64_t b4c_c(const int64_t *const *h, int32_t n, uint64_t s, float x, void *stream);\n'
+    assert _lib.parse_header(ok) == {'b4c_a': (i32, []), 'b4c_b': (c_char_p, []), 'b4c_c': (i64, [vp, i32, u64, f32, vp])}
+    for bad, named in (('int b4c_x(long n, void *stream);', 'long n'),                # a scalar type the binding has no mapping for
+                       ('int b4c_x(unsigned int n);', 'unsigned int n'),
+                       ('int b4c_x(double clip);', 'double clip'),
+                       ('double b4c_x(void);', 'double'),
+                       ('float *b4c_x(void);', 'float *'),
+                       ('int b4c_x(int);', 'b4c_x'),                                    # no parameter name: not this header's form
+                       ('int b4c_x();', 'b4c_x'),
+                       ('int b4c_x(int n, void *stream)', 'b4c_x'),                     # the `;` is missing: runs into the next one
+                       ('int b4c_x(int n;', 'b4c_x'),
+                       ('b4c_x(int n);', 'b4c_x'),                                      # no return type
+                       ('int b4c_x(int n, void (*cb)(int));', 'b4c_x'),
+                       ('int b4c_a(void);\nint b4c_a(int n);', 'b4c_a'),                # declared twice
+                       ('struct b4c_s { int a; };', 'struct b4c_s')):
+        with pytest.raises(_lib.B4CError, match=re.escape(named)):
+            _lib.parse_header(ok + bad + '\nint b4c_z(void);\n')
+    with pytest.raises(_lib.B4CError, match='no_such_b4c.h'):
+        _lib.signatures(str(tmp_path / 'no_such_b4c.h'))
+
+    with open(_lib.HEADER_PATH) as f:
+        defines = dict(re.findall(r'^#define (B4C_\w+) \(?(-?\d+)\)?', f.read(), flags=re.M))
+    for name in ('F32', 'BF16', 'ACT_NONE', 'ACT_RELU', 'CE_TF', 'CE_PLAIN', 'MAX_FEATURES', 'MAX_TOPK', 'MAX_EXCL', 'MAX_CAND',
+                 'GRAD_CHUNK', 'GRAD_GROUP', 'ABI_VERSION'):
+        assert getattr(_lib, name) == int(defines['B4C_' + name]), name
+    assert (_lib.F32, _lib.BF16, _lib.ACT_NONE, _lib.ACT_RELU, _lib.CE_TF, _lib.CE_PLAIN) == (0, 1, 0, 1, 0, 1)
+    assert (_lib.MAX_FEATURES, _lib.MAX_TOPK, _lib.MAX_EXCL, _lib.MAX_CAND, _lib.GRAD_CHUNK, _lib.GRAD_GROUP) == (4, 16, 1024, 1024, 1024, 4096)
+    assert L.b4c_abi_version() == _lib.ABI_VERSION == int(defines['B4C_ABI_VERSION']) == 12
+
+
 def test_keep_mask_hash_host_vs_library():
     from bert4clickpath_amd import _lib, ops
     L = _lib.lib()
