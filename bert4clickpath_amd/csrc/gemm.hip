@@ -781,6 +781,8 @@ extern "C" int b4c_gemm_nt_softmax(const void *A, int lda, const void *Bt, int l
                 "gemm_nt_softmax: K=%d (<= 128) lda=%d ldb=%d must be multiples of 8 with ld >= K", K, lda, ldb);
     B4C_REQUIRE(ldc >= N && vec_ok_wide(C, ldc, N, bias), "gemm_nt_softmax: N=%d ldc=%d must be multiples of 8, C / bias 16-byte aligned", N, ldc);
     B4C_REQUIRE((((uintptr_t)A | (uintptr_t)Bt) & 15) == 0, "gemm_nt_softmax: operands must be 16-byte aligned");
+    B4C_REQUIRE((int64_t)(lda > ldb ? lda : ldb) * TILE * 2 < (1ll << 30),
+                "gemm_nt_softmax: lda=%d / ldb=%d: a 128-row tile of an operand must span less than 2^30 bytes (tile_rsrc's descriptor)", lda, ldb);
     const int mt = (int)ceil_div64(M, TILE), ntn = (int)ceil_div64(N, TILE);
     int chunks = (int)ceil_div64(512 * 5, mt);       // two workgroups per CU resident, ~5 rounds over the launch
     if (chunks > ntn) chunks = ntn;
@@ -804,6 +806,8 @@ extern "C" int b4c_gemm_nt(const void *A, int lda, const void *Bt, int ldb, void
                 "gemm_nt: K=%d lda=%d ldb=%d must be multiples of %d with ld >= K", K, lda, ldb, ve);
     B4C_REQUIRE(ldc >= N, "gemm_nt: ldc %d < N %d", ldc, N);
     B4C_REQUIRE((((uintptr_t)A | (uintptr_t)Bt) & 15) == 0, "gemm_nt: operands must be 16-byte aligned");
+    B4C_REQUIRE((int64_t)(lda > ldb ? lda : ldb) * TILE * (dtype == B4C_BF16 ? 2 : 4) < (1ll << 30),
+                "gemm_nt: lda=%d / ldb=%d: a 128-row tile of an operand must span less than 2^30 bytes (tile_rsrc's descriptor)", lda, ldb);
     B4C_REQUIRE(out_dtype == dtype || out_dtype == B4C_F32, "gemm_nt: out_dtype %d", out_dtype);
     B4C_REQUIRE(act == B4C_ACT_NONE || act == B4C_ACT_RELU, "gemm_nt: act %d", act);
     hipStream_t st_w = (hipStream_t)stream;

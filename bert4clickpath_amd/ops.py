@@ -899,7 +899,7 @@ def scatter_rows(src, idx, n_dst):
 
 
 def softmax_rows(logits, V):
-    """probabilities with the shape and the row pitch of `logits` ([R, W >= V], pad columns are not written)"""
+    """probabilities with the shape and the row pitch of `logits` ([R, W >= V]; the pad columns V .. pitch are written as 0, as include/b4c.h states)"""
     R, ld = logits.shape[0], logits.stride(0)
     probs = torch.empty(R, ld, dtype=logits.dtype, device=logits.device)
     if ld != logits.shape[1]:

@@ -17,6 +17,12 @@
  *    LayerNorm params, statistics, losses and gradients of weights are always fp32;
  *  - ld* are row pitches in ELEMENTS.  Vector paths need pitches and inner sizes that are
  *    multiples of 8 elements; the host pads (zeros) where the model's sizes are not.
+ *  - rows * ld may exceed 2^31 elements (and 2^32 bytes) in the row-wise entry points (softmax, the losses on
+ *    probabilities and logits, top-k, candidate ranking, row gather / scatter, the embedding stage, the row
+ *    forms of Adam) and in C / gate / residual of b4c_gemm_nt, unless one states a limit of its own.  The
+ *    operands that the GEMM, attention and vocab_ce kernels stage tile by tile (A, Bt, X, G, h, wt, q | k | v)
+ *    are addressed with 32-bit byte offsets inside a tile: keep 128 * ld * element size below 2^30 bytes
+ *    (b4c_gemm_nt and b4c_gemm_nt_softmax check it).
  */
 #ifndef B4C_H
 #define B4C_H
@@ -124,7 +130,9 @@ int b4c_pack_weights_batched(const b4c_pack_desc *d_desc, int n_desc, int max_ti
  *   v = v * (gate[m][n] > 0)     if gate != NULL   (ReLU backward: gate = saved activation, pitch ldg)
  *   v = v + residual[m][n]       if residual != NULL (T, pitch ldr)
  * out_dtype chooses C's element type (T of `dtype`, or B4C_F32 for fp32 logits from bf16 inputs).
- * K % 8 == 0, lda/ldb % 8 == 0 (bf16) or % 4 (fp32). */
+ * K % 8 == 0, lda/ldb % 8 == 0 (bf16) or % 4 (fp32).  LIMIT: A and Bt are staged tile by tile through a buffer
+ * descriptor of less than 2^30 bytes, so 128 * lda and 128 * ldb elements must span less than 2^30 bytes
+ * (B4C_EINVAL otherwise; b4c_gemm_nt_softmax alike).  M * ldc -- C, gate and residual -- may exceed 2^31 elements. */
 int b4c_gemm_nt(const void *A, int lda, const void *Bt, int ldb, void *C, int ldc, int M, int N, int K,
                 const float *bias, int act, const void *gate, int ldg, const void *residual, int ldr,
                 int dtype, int out_dtype, void *stream);
