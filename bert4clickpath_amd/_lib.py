@@ -96,6 +96,7 @@ _C = header_constants(_header_text(HEADER_PATH))
 ABI_VERSION = _C['B4C_ABI_VERSION']       # b4c_abi_version() of the library must agree
 F32, BF16 = _C['B4C_F32'], _C['B4C_BF16']
 ACT_NONE, ACT_RELU = _C['B4C_ACT_NONE'], _C['B4C_ACT_RELU']
+ACT_GELU, ACT_GELU_TANH = _C['B4C_ACT_GELU'], _C['B4C_ACT_GELU_TANH']
 CE_TF, CE_PLAIN = _C['B4C_CE_TF'], _C['B4C_CE_PLAIN']
 MAX_FEATURES, MAX_TOPK = _C['B4C_MAX_FEATURES'], _C['B4C_MAX_TOPK']
 MAX_EXCL, MAX_CAND = _C['B4C_MAX_EXCL'], _C['B4C_MAX_CAND']

@@ -97,8 +97,12 @@ class TransformerInputPrep:
 class ClickstreamTransformer(nn.Module):
     def __init__(self, sequential_input_config, feature_vocabs, embedding_dims, head_unit, segment_to_head=None,
                  value_to_head=None, num_encoder_layers=1, num_attention_heads=1, dropout_rate=0.1,
-                 compute_dtype=torch.float32, feature_combine='concat', encoder_ff_dim=100, **kwargs):
+                 compute_dtype=torch.float32, feature_combine='concat', encoder_ff_dim=100, ffn_activation='relu',
+                 position_encoding='sinusoidal', max_positions=None, **kwargs):
         super().__init__()
+        # ffn_activation / position_encoding / max_positions: the BERT4Rec paper's GELU feed-forward and learned positions
+        # (extensions, validated by transformer.Transformer); the defaults are the reference's ReLU and fixed sinusoid
+        self.ffn_activation, self.position_encoding = ffn_activation, position_encoding
         # encoder_ff_dim: the reference hard-codes the FFN width 100 in this constructor (:225) and takes it as an argument of the
         # inner API (transformer.Transformer); 4 * d_model is the BERT4Rec paper's width.  Default = the reference's.
         self.encoder_ff_dim = int(encoder_ff_dim)
@@ -121,7 +125,9 @@ class ClickstreamTransformer(nn.Module):
             embedding_sizes={f: self.embedding_sizes[f] for f in self.embedding_dims.keys()},
             embedding_dims=self.embedding_dims, num_layers=num_encoder_layers,
             num_attention_heads=num_attention_heads, encoder_ff_dim=self.encoder_ff_dim,   # 100: hard-coded in the reference (:225)
-            dropout_rate=dropout_rate, compute_dtype=compute_dtype, feature_combine=feature_combine)
+            dropout_rate=dropout_rate, compute_dtype=compute_dtype, feature_combine=feature_combine,
+            ffn_activation=ffn_activation, position_encoding=position_encoding, max_positions=max_positions)
+        self.max_positions = self.transformer.max_positions
         if hasattr(self.head, 'tie') and getattr(self.head, '_table', None) is None:
             # tied-weight head: project back onto the FIRST embedded feature's table (the items)
             first = list(self.embedding_dims.keys())[0]
@@ -143,7 +149,10 @@ class ClickstreamTransformer(nn.Module):
                 'value_to_head': self.value_to_head, 'num_encoder_layers': self.num_encoder_layers,
                 'num_attention_heads': self.num_attention_heads, 'dropout_rate': self.dropout_rate,
                 **({'feature_combine': 'sum'} if self.feature_combine == 'sum' else {}),
-                **({'encoder_ff_dim': self.encoder_ff_dim} if self.encoder_ff_dim != 100 else {})}
+                **({'encoder_ff_dim': self.encoder_ff_dim} if self.encoder_ff_dim != 100 else {}),
+                **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
+                **({'position_encoding': 'learned', 'max_positions': self.max_positions}
+                   if self.position_encoding == 'learned' else {})}
 
     @staticmethod
     def _create_lookup_tables(vocabularies, tokens_to_prepend=None):
@@ -173,7 +182,7 @@ class ClickstreamTransformer(nn.Module):
         """rows_of(ids_first, raw_first) -> (flat_idx, offsets, extra) or None: called once the ids are known; when it returns
         indices, the last encoder layer is evaluated at those positions only and `enc` is the (R, d) rows."""
         raw_features, seg_starts, seg_ends = self.transformer_input_prep(features=inputs)
-        dev = self.transformer.pos_encoding.device
+        dev = self.transformer.position_table.device
         if dev.type != 'cuda':
             raise B4CError('model is on %s: move it to the HIP device with .to("cuda") (no CPU path)' % dev)
         features = dict(raw_features)
@@ -385,7 +394,7 @@ class ClickstreamTransformer(nn.Module):
         packed: run the encoder on the padding-free layout (bf16 throughput path; same loss and gradients, the pad
         positions' work is not done)."""
         pack = self._use_packed(inputs, packed, n_real_tokens)
-        lab = torch.as_tensor(labels, device=self.transformer.pos_encoding.device)
+        lab = torch.as_tensor(labels, device=self.transformer.position_table.device)
         if max_masked_per_row is not None and flat_idx is None:
             if lab.dim() != 2:
                 raise ValueError('the sync-free form needs the padded (B, M) labels')

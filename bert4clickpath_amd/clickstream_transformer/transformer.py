@@ -182,8 +182,11 @@ class _FeedForward(nn.ModuleList):
     """Two Dense layers addressed as ffn[0] / ffn[1] (state-dict keys ``ffn.0.*`` / ``ffn.1.*``) like the
     reference's keras.Sequential (transformer.py:163-167)."""
 
-    def __init__(self, d_model, dff):
+    def __init__(self, d_model, dff, ffn_activation='relu'):
         super().__init__([Dense(d_model, dff), Dense(dff, d_model)])
+        # 'relu' (the reference) | 'gelu' (x Phi(x), erf) | 'gelu_tanh' (the BERT4Rec code's form): no reference counterpart
+        self.act = ops.ffn_act_code(ffn_activation)
+        self.ffn_activation = ffn_activation
         self._pk1 = ops.PackedLinear([self[0].kernel], [self[0].bias])
         self._pk2 = ops.PackedLinear([self[1].kernel], [self[1].bias])
 
@@ -193,29 +196,31 @@ class _FeedForward(nn.ModuleList):
         wt1, _, b1 = self._pk1.get(x2.dtype, shp[-1], False)
         wt2, _, b2 = self._pk2.get(x2.dtype, self._pk1.Np, False)
         with torch.no_grad():
-            h = ops.gemm_nt(x2, wt1, self._pk1.Np, b1, act=ops.L.ACT_RELU)
+            h = ops.gemm_nt(x2, wt1, self._pk1.Np, b1, act=self.act)
             y = ops.gemm_nt(h, wt2, shp[-1], b2)
         return y.view(shp)
 
 
-def point_wise_feed_forward_network(d_model, dff):
-    return _FeedForward(d_model, dff)
+def point_wise_feed_forward_network(d_model, dff, ffn_activation='relu'):
+    return _FeedForward(d_model, dff, ffn_activation)
 
 
 class EncoderLayer(nn.Module):
     """Post-LN block: out1 = LN1(x + drop(mha(x))); out2 = LN2(out1 + drop(ffn(out1))) (reference :202-213).
     Runs as two fused autograd blocks of HIP kernels."""
 
-    def __init__(self, d_model, num_heads, dff, rate=0.1, **kwargs):
+    def __init__(self, d_model, num_heads, dff, rate=0.1, ffn_activation='relu', **kwargs):
         super().__init__()
         self.d_model, self.num_heads, self.dff, self.rate = d_model, num_heads, dff, rate
+        self.ffn_activation = ffn_activation
         self.mha = MultiHeadAttention(d_model, num_heads)
-        self.ffn = point_wise_feed_forward_network(d_model, dff)
+        self.ffn = point_wise_feed_forward_network(d_model, dff, ffn_activation)
         self.layernorm1 = LayerNormalization(d_model, 1e-6)
         self.layernorm2 = LayerNormalization(d_model, 1e-6)
 
     def get_config(self):
-        return {'d_model': self.d_model, 'num_heads': self.num_heads, 'dff': self.dff, 'rate': self.rate}
+        return {'d_model': self.d_model, 'num_heads': self.num_heads, 'dff': self.dff, 'rate': self.rate,
+                **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {})}
 
     def forward(self, x, training=None, mask=None, packed=None, rows=None):
         """x (B, S, d); or, with `packed` (ops.Packed), the (1, T, d) rows of the real tokens only and mask = the (T,) key
@@ -250,12 +255,12 @@ class EncoderLayer(nn.Module):
                                            m.wv.bias, m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
                                            m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape)
             return ops.FFNBlockFn.apply(out1, f[0].kernel, f[0].bias, f[1].kernel, f[1].bias, self.layernorm2.gamma,
-                                        self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape)
+                                        self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape, f.act)
         out1 = ops.AttnBlockFn.apply(x2, key_pad, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel, m.wv.bias,
                                      m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
                                      m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape, cu)
         out2 = ops.FFNBlockFn.apply(out1, f[0].kernel, f[0].bias, f[1].kernel, f[1].bias, self.layernorm2.gamma,
-                                    self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape)
+                                    self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape, f.act)
         return out2.view(out_shape)
 
 
@@ -264,15 +269,19 @@ class Encoder(nn.Module):
     reference's Encoder.call (:263) is fused into the embedding kernel when ``Transformer`` calls the Encoder;
     an Encoder called on its own applies it with the stand-alone dropout kernel (same keep-mask generator)."""
 
-    def __init__(self, num_layers, d_model, num_heads, dff, dropout_rate, **kwargs):
+    def __init__(self, num_layers, d_model, num_heads, dff, dropout_rate, ffn_activation='relu', **kwargs):
         super().__init__()
         self.num_layers, self.d_model, self.num_heads, self.dff, self.dropout_rate = \
             num_layers, d_model, num_heads, dff, dropout_rate
-        self.enc_layers = nn.ModuleList([EncoderLayer(d_model, num_heads, dff, dropout_rate) for _ in range(num_layers)])
+        ops.ffn_act_code(ffn_activation)        # (ValueError also for an encoder of no layers)
+        self.ffn_activation = ffn_activation
+        self.enc_layers = nn.ModuleList([EncoderLayer(d_model, num_heads, dff, dropout_rate, ffn_activation)
+                                         for _ in range(num_layers)])
 
     def get_config(self):
         return {'num_layers': self.num_layers, 'd_model': self.d_model, 'num_heads': self.num_heads, 'dff': self.dff,
-                'dropout_rate': self.dropout_rate}
+                'dropout_rate': self.dropout_rate,
+                **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {})}
 
     def forward(self, inputs, training=None, mask=None, _input_dropout_done=False, packed=None, rows=None):
         """rows (see EncoderLayer.forward): the LAST layer is evaluated for those query rows only; returns (R, d)."""
@@ -300,6 +309,14 @@ class _Embedding(nn.Module):
         self.weight = nn.Parameter(torch.empty(rows, dim).uniform_(-0.05, 0.05))
 
 
+class _PositionEmbedding(nn.Module):
+    """Learned positional table: weight (max_positions, d_model) ~ N(0, 0.02^2) cut at two sigma."""
+
+    def __init__(self, rows, dim):
+        super().__init__()
+        self.weight = nn.Parameter(torch.nn.init.trunc_normal_(torch.empty(rows, dim), mean=0.0, std=0.02, a=-0.04, b=0.04))
+
+
 class _FeatureModules(nn.Module):
     """name -> module container whose keys may be ANY feature name ('items', 'keys', ...), which
     nn.ModuleDict refuses; state-dict keys stay ``embedding_layers.<feature>.weight``."""
@@ -319,11 +336,22 @@ class _FeatureModules(nn.Module):
 class Transformer(nn.Module):
     """Encoder-only Transformer over one or more categorical sequence features (reference :271-402):
     per-feature embedding -> concat on the last axis (or, feature_combine='sum', added) -> * sqrt(d_model) -> + sinusoidal
-    PE -> Encoder."""
+    PE -> Encoder.
+    Extensions of the BERT4Rec paper, no reference counterpart: ffn_activation ('relu' | 'gelu' | 'gelu_tanh') for the
+    feed-forward blocks, and position_encoding='learned' with max_positions: the positional table is a parameter
+    ``position_embedding.weight`` [max_positions, d_model] (truncated normal, sigma 0.02) instead of the fixed sinusoid."""
 
     def __init__(self, num_layers, num_attention_heads, embedding_sizes, embedding_dims, encoder_ff_dim, dropout_rate,
-                 item_embedding_weights=None, compute_dtype=torch.float32, feature_combine='concat', **kwargs):
+                 item_embedding_weights=None, compute_dtype=torch.float32, feature_combine='concat', ffn_activation='relu',
+                 position_encoding='sinusoidal', max_positions=None, **kwargs):
         super().__init__()
+        ops.ffn_act_code(ffn_activation)
+        if position_encoding not in ('sinusoidal', 'learned'):
+            raise ValueError("position_encoding must be 'sinusoidal' or 'learned', got %r" % (position_encoding,))
+        if position_encoding == 'learned' and (max_positions is None or int(max_positions) < 1):
+            raise ValueError("position_encoding='learned' needs max_positions (a positive table length), got %r" % (max_positions,))
+        self.ffn_activation, self.position_encoding = ffn_activation, position_encoding
+        self.max_positions = int(max_positions) if position_encoding == 'learned' else None
         assert set(embedding_sizes.keys()) == set(embedding_dims.keys()), \
             "embedding_sizes and embedding_dims must have the same set of keys."
         self.num_layers, self.num_attention_heads = num_layers, num_attention_heads
@@ -347,11 +375,16 @@ class Transformer(nn.Module):
             if dim % 8 != 0:
                 raise B4CError('MI355X build: embedding dim of feature %r is %d; must be a multiple of 8' % (f, dim))
         self.compute_dtype = compute_dtype
-        self.encoder = Encoder(num_layers, self.d_model, num_attention_heads, encoder_ff_dim, dropout_rate)
+        self.encoder = Encoder(num_layers, self.d_model, num_attention_heads, encoder_ff_dim, dropout_rate, ffn_activation)
         self.embedding_layers = _FeatureModules({f: _Embedding(int(embedding_sizes[f]), int(embedding_dims[f]))
                                                  for f in embedding_dims.keys()})
-        self.register_buffer('pos_encoding', positional_encoding(self.maximum_position_encoding, self.d_model)[0].clone(),
-                             persistent=False)
+        if position_encoding == 'learned':
+            # the paper's code: truncated normal, sigma 0.02, cut at 2 sigma; a dense parameter like any other (decayed by AdamW)
+            self.maximum_position_encoding = self.max_positions
+            self.position_embedding = _PositionEmbedding(self.max_positions, self.d_model)
+        else:
+            self.register_buffer('pos_encoding', positional_encoding(self.maximum_position_encoding, self.d_model)[0].clone(),
+                                 persistent=False)
         self.scale = float(np.sqrt(np.float32(self.d_model)))   # sqrt taken in float32 (reference :390)
 
     def get_config(self):
@@ -359,7 +392,15 @@ class Transformer(nn.Module):
                 'embedding_sizes': self.embedding_sizes, 'embedding_dims': self.embedding_dims,
                 'encoder_ff_dim': self.encoder_ff_dim, 'dropout_rate': self.dropout_rate,
                 'item_embedding_weights': self.item_embedding_weights,
-                **({'feature_combine': 'sum'} if self.feature_combine == 'sum' else {})}
+                **({'feature_combine': 'sum'} if self.feature_combine == 'sum' else {}),
+                **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
+                **({'position_encoding': 'learned', 'max_positions': self.max_positions}
+                   if self.position_encoding == 'learned' else {})}
+
+    @property
+    def position_table(self):
+        """the fp32 positional table the embedding stage adds: the sinusoidal buffer or the learned parameter"""
+        return self.position_embedding.weight if self.position_encoding == 'learned' else self.pos_encoding
 
     def packed_supported(self, S):
         """The padding-free layout runs on the bf16 MFMA attention kernels only (head depth 32 / 64, S <= 512)."""
@@ -378,13 +419,17 @@ class Transformer(nn.Module):
         tables = [self.embedding_layers[f].weight for f in feats]
         B, S = ids[0].shape
         if S > self.maximum_position_encoding:
-            raise B4CError('sequence length %d exceeds the positional table (10000)' % S)
+            raise B4CError('sequence length %d exceeds the positional table (%d)' % (S, self.maximum_position_encoding))
         rate = self.dropout_rate if training else 0.0
         seed = dropout_seeds.next() if training else 0
         if packed is not None and not self.packed_supported(S):
             raise B4CError('packed layout needs bf16, head depth 32 / 64 and S <= 512')
-        x, key_pad = ops.EmbedFn.apply(self.pos_encoding, self.scale, rate, seed, self.compute_dtype,
-                                       (len(ids), packed, 'sum') if self.feature_combine == 'sum' else
-                                       (len(ids) if packed is None else (len(ids), packed)), *ids, *tables)
+        n_arg = (len(ids), packed, 'sum') if self.feature_combine == 'sum' else (len(ids) if packed is None else (len(ids), packed))
+        if self.position_encoding == 'learned':
+            # the table is a differentiable input (its gradient: b4c_pos_table_bwd); the sinusoidal call is the reference's
+            x, key_pad = ops.EmbedFn.apply(self.position_embedding.weight, self.scale, rate, seed, self.compute_dtype, n_arg,
+                                           *ids, *tables)
+        else:
+            x, key_pad = ops.EmbedFn.apply(self.pos_encoding, self.scale, rate, seed, self.compute_dtype, n_arg, *ids, *tables)
         out = self.encoder(x, training, key_pad, _input_dropout_done=True, packed=packed, rows=rows)
         return (out, key_pad) if return_key_pad else out

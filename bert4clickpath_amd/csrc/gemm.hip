@@ -146,6 +146,23 @@ __device__ __forceinline__ void epilogue8(float (&v)[8], int64_t row, int col, O
     Vec8<OutT>::store(C + row * ldc + col, v);
 }
 
+// GELU (B4C_ACT_GELU: x Phi(x) with erf; B4C_ACT_GELU_TANH: the tanh form) and its derivative, in fp32.  The derivative is
+// applied to the SAVED pre-activation u (the `pre` output of b4c_gemm_nt_act): GELU is not monotone, so unlike ReLU its
+// backward cannot be read off the activation.
+__device__ __forceinline__ float act_gelu(float x, int act) {
+    if (act == B4C_ACT_GELU) return 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
+    const float t = tanhf(0.79788456080286536f * (x + 0.044715f * x * x * x));
+    return 0.5f * x * (1.f + t);
+}
+__device__ __forceinline__ float act_gelu_grad(float u, int act) {
+    if (act == B4C_ACT_GELU)      // Phi(u) + u phi(u)
+        return 0.5f * (1.f + erff(u * 0.70710678118654752f)) + u * 0.39894228040143268f * __expf(-0.5f * u * u);
+    u = fminf(fmaxf(u, -10.f), 10.f);      // tanh is +-1 in fp32 well before |u| = 10: the step's limit, and u * u stays finite
+    const float u2 = u * u;
+    const float t = tanhf(0.79788456080286536f * (u + 0.044715f * u * u2));
+    return 0.5f * (1.f + t) + 0.5f * u * (1.f - t * t) * 0.79788456080286536f * (1.f + 3.f * 0.044715f * u2);
+}
+
 // One LDS stage (36.9 KB -> 4 workgroups per CU) with register prefetch of the next K tile.  The kernel is
 // latency-bound at K = 128 (two K tiles), so dependent round trips to memory are issued early:
 //   * the bias chunk of each lane is loaded at entry,
@@ -155,11 +172,15 @@ __device__ __forceinline__ void epilogue8(float (&v)[8], int64_t row, int col, O
 // as 16-byte row chunks.
 #define OUT_STRIDE 136   // bytes per staged output row (128 + 8: 8-byte writes spread over the banks)
 
-template <typename T, typename OutT, bool EPI>
+// ACTX (b4c_gemm_nt_act with a GELU activation, a GELU gate or a `pre` output): the epilogue also knows B4C_ACT_GELU /
+// B4C_ACT_GELU_TANH, writes the pre-activation acc + bias to `pre`, and applies `gate` as act'(gate) when gate_act is a GELU.
+// The ACTX = false instantiations are the kernels of b4c_gemm_nt as they were: the transcendental code is not in them.
+template <typename T, typename OutT, bool EPI, bool ACTX>
 __global__ void __launch_bounds__(256, 3) gemm_nt_kernel(const T *__restrict__ A, int lda, const T *__restrict__ Bt, int ldb,
                                                       OutT *__restrict__ C, int ldc, int M, int N, int K,
                                                       const float *__restrict__ bias, int act, const T *__restrict__ gate,
-                                                      int ldg, const T *__restrict__ residual, int ldr, int vec_ok, int xcd_map) {
+                                                      int ldg, const T *__restrict__ residual, int ldr, int vec_ok, int xcd_map,
+                                                      T *__restrict__ pre, int ldp, int gate_act) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, r = lane & 31, h = lane >> 5;
@@ -262,14 +283,23 @@ __global__ void __launch_bounds__(256, 3) gemm_nt_kernel(const T *__restrict__ A
                 float v[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[k] = (float)cv[k] + bv[k];
+                if (ACTX && pre) Vec8<T>::store(pre + grow * ldp + gcol, v);
                 if (act == B4C_ACT_RELU) {
 #pragma unroll
                     for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
+                } else if (ACTX && act != B4C_ACT_NONE) {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) v[k] = act_gelu(v[k], act);
                 }
                 if (EPI && gate) {
                     const bf16x8 gv = __builtin_bit_cast(bf16x8, pe[EPI ? q : 0]);
+                    if (ACTX && gate_act != B4C_ACT_RELU) {
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = ((float)gv[k] > 0.f) ? v[k] : 0.f;
+                        for (int k = 0; k < 8; ++k) v[k] *= act_gelu_grad((float)gv[k], gate_act);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) v[k] = ((float)gv[k] > 0.f) ? v[k] : 0.f;
+                    }
                     if (residual) {   // both operands at once: not on the model's path, loaded late
                         float rr[8];
                         Vec8<T>::load(residual + grow * ldr + gcol, rr);
@@ -296,8 +326,14 @@ __global__ void __launch_bounds__(256, 3) gemm_nt_kernel(const T *__restrict__ A
                 const int col = n0 + wn * 64 + j * 32 + (t & 3) + 8 * (t >> 2) + 4 * h;
                 if (row < M && col < N) {
                     float v = acc[j][i][t] + (bias ? bias[col] : 0.f);
+                    if (ACTX && pre) pre[(int64_t)row * ldp + col] = (T)v;
                     if (act == B4C_ACT_RELU) v = fmaxf(v, 0.f);
-                    if (gate) v = ((float)gate[(int64_t)row * ldg + col] > 0.f) ? v : 0.f;
+                    else if (ACTX && act != B4C_ACT_NONE) v = act_gelu(v, act);
+                    if (gate) {
+                        const float g = (float)gate[(int64_t)row * ldg + col];
+                        if (ACTX && gate_act != B4C_ACT_RELU) v *= act_gelu_grad(g, gate_act);
+                        else v = (g > 0.f) ? v : 0.f;
+                    }
                     if (residual) v += (float)residual[(int64_t)row * ldr + col];
                     C[(int64_t)row * ldc + col] = (OutT)v;
                 }
@@ -799,6 +835,13 @@ extern "C" int b4c_gemm_nt_softmax(const void *A, int lda, const void *Bt, int l
 extern "C" int b4c_gemm_nt(const void *A, int lda, const void *Bt, int ldb, void *C, int ldc, int M, int N, int K,
                            const float *bias, int act, const void *gate, int ldg, const void *residual, int ldr,
                            int dtype, int out_dtype, void *stream) {
+    return b4c_gemm_nt_act(A, lda, Bt, ldb, C, ldc, M, N, K, bias, act, gate, ldg, B4C_ACT_RELU, residual, ldr, nullptr, 0,
+                           dtype, out_dtype, stream);
+}
+
+extern "C" int b4c_gemm_nt_act(const void *A, int lda, const void *Bt, int ldb, void *C, int ldc, int M, int N, int K,
+                               const float *bias, int act, const void *gate, int ldg, int gate_act, const void *residual, int ldr,
+                               void *pre, int ldp, int dtype, int out_dtype, void *stream) {
     B4C_REQUIRE(A && Bt && C && M > 0 && N > 0 && K > 0, "gemm_nt: null pointer / empty (M=%d N=%d K=%d)", M, N, K);
     B4C_REQUIRE(dtype == B4C_F32 || dtype == B4C_BF16, "gemm_nt: dtype %d", dtype);
     const int ve = dtype == B4C_BF16 ? 8 : 4;
@@ -809,9 +852,12 @@ extern "C" int b4c_gemm_nt(const void *A, int lda, const void *Bt, int ldb, void
     B4C_REQUIRE((int64_t)(lda > ldb ? lda : ldb) * TILE * (dtype == B4C_BF16 ? 2 : 4) < (1ll << 30),
                 "gemm_nt: lda=%d / ldb=%d: a 128-row tile of an operand must span less than 2^30 bytes (tile_rsrc's descriptor)", lda, ldb);
     B4C_REQUIRE(out_dtype == dtype || out_dtype == B4C_F32, "gemm_nt: out_dtype %d", out_dtype);
-    B4C_REQUIRE(act == B4C_ACT_NONE || act == B4C_ACT_RELU, "gemm_nt: act %d", act);
+    B4C_REQUIRE(act == B4C_ACT_NONE || act == B4C_ACT_RELU || act == B4C_ACT_GELU || act == B4C_ACT_GELU_TANH, "gemm_nt: act %d", act);
+    B4C_REQUIRE(!gate || gate_act == B4C_ACT_RELU || gate_act == B4C_ACT_GELU || gate_act == B4C_ACT_GELU_TANH,
+                "gemm_nt: gate_act %d", gate_act);
+    B4C_REQUIRE(!pre || ldp >= N, "gemm_nt: ldp %d < N %d", ldp, N);
     hipStream_t st_w = (hipStream_t)stream;
-    if (dtype == B4C_BF16 && out_dtype == B4C_BF16 && K <= 128 && N >= 2048 && act == B4C_ACT_NONE && !gate && !residual &&
+    if (dtype == B4C_BF16 && out_dtype == B4C_BF16 && K <= 128 && N >= 2048 && act == B4C_ACT_NONE && !gate && !residual && !pre &&
         vec_ok_wide(C, ldc, N, bias)) {
         const int mt = (int)ceil_div64(M, TILE), ntn = (int)ceil_div64(N, TILE);
         int chunks = (int)ceil_div64(512 * 5, mt);       // two workgroups per CU resident, ~5 rounds over the launch
@@ -835,19 +881,26 @@ extern "C" int b4c_gemm_nt(const void *A, int lda, const void *Bt, int ldb, void
     const int vec_ok = (N % 8 == 0) && (ldc % 8 == 0) && (((uintptr_t)C & 15) == 0) &&
                        (!gate || (ldg % 8 == 0 && ((uintptr_t)gate & 15) == 0)) &&
                        (!residual || (ldr % 8 == 0 && ((uintptr_t)residual & 15) == 0)) &&
-                       (!bias || ((uintptr_t)bias & 15) == 0);
-#define NT_ARGS(TT, OT) (const TT *)A, lda, (const TT *)Bt, ldb, (OT *)C, ldc, M, N, K, bias, act, (const TT *)gate, ldg, (const TT *)residual, ldr, vec_ok, xcd_map
+                       (!bias || ((uintptr_t)bias & 15) == 0) &&
+                       (!pre || (ldp % 8 == 0 && ((uintptr_t)pre & 15) == 0));
+#define NT_ARGS(TT, OT) (const TT *)A, lda, (const TT *)Bt, ldb, (OT *)C, ldc, M, N, K, bias, act, (const TT *)gate, ldg, (const TT *)residual, ldr, vec_ok, xcd_map, (TT *)pre, ldp, gate_act
+#define NT_LAUNCH(TT, OT)                                                                                       \
+    do {                                                                                                        \
+        if (actx) {                                                                                             \
+            if (epi) gemm_nt_kernel<TT, OT, true, true><<<grid, 256, shm, st>>>(NT_ARGS(TT, OT));               \
+            else gemm_nt_kernel<TT, OT, false, true><<<grid, 256, shm, st>>>(NT_ARGS(TT, OT));                  \
+        } else {                                                                                                \
+            if (epi) gemm_nt_kernel<TT, OT, true, false><<<grid, 256, shm, st>>>(NT_ARGS(TT, OT));              \
+            else gemm_nt_kernel<TT, OT, false, false><<<grid, 256, shm, st>>>(NT_ARGS(TT, OT));                 \
+        }                                                                                                       \
+    } while (0)
     const bool epi = gate || residual;
-    if (dtype == B4C_F32) {
-        if (epi) gemm_nt_kernel<float, float, true><<<grid, 256, shm, st>>>(NT_ARGS(float, float));
-        else gemm_nt_kernel<float, float, false><<<grid, 256, shm, st>>>(NT_ARGS(float, float));
-    } else if (out_dtype == B4C_F32) {
-        if (epi) gemm_nt_kernel<bf16_t, float, true><<<grid, 256, shm, st>>>(NT_ARGS(bf16_t, float));
-        else gemm_nt_kernel<bf16_t, float, false><<<grid, 256, shm, st>>>(NT_ARGS(bf16_t, float));
-    } else {
-        if (epi) gemm_nt_kernel<bf16_t, bf16_t, true><<<grid, 256, shm, st>>>(NT_ARGS(bf16_t, bf16_t));
-        else gemm_nt_kernel<bf16_t, bf16_t, false><<<grid, 256, shm, st>>>(NT_ARGS(bf16_t, bf16_t));
-    }
+    // the GELU forms and the `pre` output live in instantiations of their own: b4c_gemm_nt's ReLU / plain launches run the code they ran
+    const bool actx = pre || act == B4C_ACT_GELU || act == B4C_ACT_GELU_TANH || (gate && gate_act != B4C_ACT_RELU);
+    if (dtype == B4C_F32) NT_LAUNCH(float, float);
+    else if (out_dtype == B4C_F32) NT_LAUNCH(bf16_t, float);
+    else NT_LAUNCH(bf16_t, bf16_t);
+#undef NT_LAUNCH
 #undef NT_ARGS
     return b4c_check_launch("gemm_nt");
 }

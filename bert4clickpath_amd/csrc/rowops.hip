@@ -227,6 +227,119 @@ extern "C" int b4c_embed_concat_pe_bwd(int n_feat, const int64_t *const *h_ids, 
     return b4c_check_launch("embed_bwd");
 }
 
+// Gradient of a LEARNED positional table: dpe[s] += sum_b keep / (1 - rate) * dout[cu[b] + s].  A pure streaming reduction over
+// the sequences (dout read once, 16-B chunks).  A workgroup owns POS_TILE(d) consecutive positions x one contiguous block of
+// sequences: for one sequence its threads read one contiguous piece of dout (4 KB at d = 128, bf16), every thread keeps its 8
+// columns of one position in registers, and the block's sum goes to part[block][s][d].  The grid splits the sequences as well
+// as the positions (S = 200 alone would be 13 workgroups).  row_of (the packed layout of a batch whose pads are not at the end of
+// a sequence): the row of position s of sequence b is row_of[b * S + s], none where that is negative, instead of cu[b] + s.  Rows
+// outside [0, n_rows) are skipped, whatever the index arrays say.  pos_table_reduce_kernel adds the blocks in block order: no float
+// atomics, the same bits on every launch.
+template <typename T>
+__global__ void __launch_bounds__(256) pos_table_partial_kernel(const T *__restrict__ dout, int ld, int64_t n_rows,
+                                                                const int32_t *__restrict__ cu, const int32_t *__restrict__ row_of,
+                                                                int B, int S, int d, float rate, uint64_t seed, int seq_per_wg,
+                                                                float *__restrict__ part) {
+    const int cpr = d >> 3, ptile = 256 / cpr;
+    const int ps = threadIdx.x / cpr, c = (threadIdx.x - ps * cpr) << 3;
+    const int s = blockIdx.x * ptile + ps;
+    if (ps >= ptile || s >= S) return;
+    const int b0 = blockIdx.y * seq_per_wg, b1 = min(b0 + seq_per_wg, B);
+    const uint32_t thr = b4c_keep_threshold(rate);
+    float acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+    // four sequences per trip: their loads are issued together (one load in flight per wave would leave HBM idle), and are
+    // added in sequence order
+    for (int b = b0; b < b1; b += 4) {
+        float g[4][8];
+        uint32_t km[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int bb = min(b + u, b1 - 1);
+            int64_t t;
+            if (row_of) {
+                t = row_of[(int64_t)bb * S + s];
+            } else {
+                const int64_t first = cu[bb];
+                t = (cu[bb + 1] - first > s) ? first + s : -1;
+            }
+            km[u] = 0u;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) g[u][k] = 0.f;
+            if (b + u < b1 && t >= 0 && t < n_rows) {
+                Vec8<T>::load(dout + t * ld + c, g[u]);
+                km[u] = rate > 0.f ? b4c_keep8(seed, (uint64_t)(t * d + c), thr) : 0xFFu;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[k] += ((km[u] >> k) & 1u) ? g[u][k] : 0.f;
+    }
+    if (rate > 0.f) {
+        const float inv_keep = 1.0f / (1.0f - rate);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] *= inv_keep;
+    }
+    Vec8<float>::store(part + ((int64_t)blockIdx.y * S + s) * d + c, acc);
+}
+
+__global__ void __launch_bounds__(256) pos_table_reduce_kernel(const float *__restrict__ part, int nblocks, int64_t n4,
+                                                               float *__restrict__ dpe) {
+    const int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x;      // one float4 of the [S][d] table
+    if (i >= n4) return;
+    f32x4 sum = reinterpret_cast<const f32x4 *>(part)[i];
+    for (int j = 1; j < nblocks; ++j) sum += reinterpret_cast<const f32x4 *>(part)[(int64_t)j * n4 + i];
+    reinterpret_cast<f32x4 *>(dpe)[i] += sum;
+}
+
+// sequences per workgroup: about 1024 workgroups in all (4 per CU), at least 8 sequences each
+static int pos_table_seq_per_wg(int B, int S, int d_model) {
+    const int ptile = 256 / (d_model / 8);
+    const int64_t n_pt = ceil_div64(S, ptile);
+    int64_t nb = 1024 / n_pt;
+    if (nb > ceil_div64(B, 8)) nb = ceil_div64(B, 8);
+    if (nb < 1) nb = 1;
+    return (int)ceil_div64(B, nb);
+}
+
+extern "C" int64_t b4c_pos_table_bwd_workspace_bytes(int B, int S, int d_model) {
+    if (B <= 0 || S <= 0 || d_model <= 0 || d_model % 8 != 0 || d_model > 2048) return 0;
+    const int64_t nb = ceil_div64(B, pos_table_seq_per_wg(B, S, d_model));
+    return nb * S * d_model * (int64_t)sizeof(float);
+}
+
+extern "C" int b4c_pos_table_bwd(const void *dout, int ld_dout, int64_t n_rows, const int32_t *cu, const int32_t *row_of, int B, int S,
+                                 int d_model, float dropout_rate, uint64_t seed, float *dpe, void *workspace, int64_t workspace_bytes,
+                                 int dtype, void *stream) {
+    B4C_REQUIRE(dout && (cu || row_of) && dpe && B > 0 && S > 0 && n_rows > 0, "pos_table_bwd: null pointer / empty (B=%d S=%d)", B, S);
+    B4C_REQUIRE(d_model > 0 && d_model % 8 == 0 && d_model <= 2048, "pos_table_bwd: d_model %d must be a multiple of 8, <= 2048", d_model);
+    B4C_REQUIRE(ld_dout >= d_model && ld_dout % 8 == 0 && ((uintptr_t)dout & 15) == 0 && ((uintptr_t)dpe & 15) == 0,
+                "pos_table_bwd: dout / dpe must be 16-byte aligned, ld_dout %d a multiple of 8 >= d_model", ld_dout);
+    B4C_REQUIRE(dropout_rate >= 0.f && dropout_rate < 1.f, "pos_table_bwd: dropout_rate %f", dropout_rate);
+    B4C_REQUIRE(dtype == B4C_F32 || dtype == B4C_BF16, "pos_table_bwd: dtype %d", dtype);
+    const int64_t need = b4c_pos_table_bwd_workspace_bytes(B, S, d_model);
+    B4C_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0,
+                "pos_table_bwd: workspace of %lld bytes needed (16-byte aligned), got %lld", (long long)need, (long long)workspace_bytes);
+    const int spw = pos_table_seq_per_wg(B, S, d_model);
+    const int nb = (int)ceil_div64(B, spw);
+    const int ptile = 256 / (d_model / 8);
+    B4C_REQUIRE(nb <= 65535, "pos_table_bwd: %d sequence blocks", nb);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid((unsigned)ceil_div64(S, ptile), (unsigned)nb);
+    float *part = (float *)workspace;
+    if (dtype == B4C_F32)
+        pos_table_partial_kernel<float><<<grid, 256, 0, st>>>((const float *)dout, ld_dout, n_rows, cu, row_of, B, S, d_model, dropout_rate, seed, spw, part);
+    else
+        pos_table_partial_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t *)dout, ld_dout, n_rows, cu, row_of, B, S, d_model, dropout_rate, seed, spw, part);
+    int rc = b4c_check_launch("pos_table_bwd");
+    if (rc) return rc;
+    const int64_t n4 = (int64_t)S * d_model / 4;
+    pos_table_reduce_kernel<<<(unsigned)ceil_div64(n4, 256), 256, 0, st>>>(part, nb, n4, dpe);
+    return b4c_check_launch("pos_table_bwd_reduce");
+}
+
 // Sorted form of the same scatter-add: `order` lists the token indices of one feature sorted by id, so a wave
 // that walks 64 consecutive entries meets every id as one run, sums the run in registers and writes each
 // gradient row once.  Only a run that may continue in a neighbouring wave's range (same id just before / after

@@ -261,6 +261,38 @@ def _workspace(kind, device, need, floor=0):
     return ws
 
 
+_dense_cu = {}
+
+
+def dense_cu(B, S, device):
+    """int32 [B + 1] = b * S: the first row of every sequence of the dense (B, S) layout (built once per shape and device)"""
+    key = (B, S, device)
+    if key not in _dense_cu:
+        _dense_cu[key] = torch.arange(B + 1, dtype=torch.int32, device=device) * S
+    return _dense_cu[key]
+
+
+def pos_table_bwd(dout, cu, B, S, rate, seed, into, row_of=None):
+    """into [>= S, d] (fp32) += the embedding stage's gradient w.r.t. a learned positional table (b4c_pos_table_bwd):
+    dout [T, d] the stage's output gradient, cu [B+1] int32 first row of every sequence (b * S in the dense layout), or
+    row_of [B*S] int32 (Packed.packed_of: the row of every dense position, -1 = none) for the packed layout;
+    rate / seed: the forward's dropout.  Fixed summation order: the same bits on every launch."""
+    d = dout.shape[-1]
+    dout = dout.reshape(-1, d)
+    if into.dtype != torch.float32 or not into.is_contiguous() or into.shape[0] < S or into.shape[1] != d:
+        raise B4CError('pos_table_bwd: the gradient table must be contiguous float32 [>= %d, %d]' % (S, d))
+    if row_of is not None:
+        if row_of.dtype != torch.int32 or row_of.numel() != B * S or not row_of.is_contiguous():
+            raise B4CError('pos_table_bwd: row_of must be a contiguous int32 [B * S] tensor')
+    elif cu is None or cu.dtype != torch.int32 or cu.numel() != B + 1 or not cu.is_contiguous():
+        raise B4CError('pos_table_bwd: cu must be a contiguous int32 [B + 1] tensor')
+    ws = _workspace('pos_table_bwd', dout.device, L.lib().b4c_pos_table_bwd_workspace_bytes(B, S, d))
+    with _record('pos_table_bwd', dout.shape[0] * d * dout.element_size() + S * d * 4):
+        L.check(L.lib().b4c_pos_table_bwd(_p(dout), dout.stride(0), dout.shape[0], _p(cu), _p(row_of), B, S, d, rate, seed, _p(into),
+                                          ws.data_ptr(), ws.numel(), dt_code(dout.dtype), _st()), 'pos_table_bwd')
+    return into
+
+
 def _sort_order(ids, n_rows):
     """Token indices sorted by id (int32).  Radix-sort cost grows with the key width, and ids are row indices of a
     table: 16-bit keys for tables of up to 65,536 rows (biased into int16), else 32-bit (63 / 178 / 224 us for 16 / 32 / 64
@@ -378,8 +410,22 @@ def _rows_ok(g, dtype):
     return g
 
 
-def gemm_nt(a, bt, n, bias=None, act=L.ACT_NONE, gate=None, residual=None, out_dtype=None, out=None):
-    """a: [M, Kp], bt: [>=n, Kp] -> [M, n] (written into `out`, a row-pitched [M, n] view, when given)"""
+FFN_ACTIVATIONS = {'relu': L.ACT_RELU, 'gelu': L.ACT_GELU, 'gelu_tanh': L.ACT_GELU_TANH}
+
+
+def ffn_act_code(name):
+    """B4C_ACT_* of a feed-forward activation name ('relu' | 'gelu' | 'gelu_tanh'); anything else is a ValueError"""
+    try:
+        return FFN_ACTIVATIONS[name]
+    except (KeyError, TypeError):
+        raise ValueError("ffn_activation must be 'relu', 'gelu' or 'gelu_tanh', got %r" % (name,)) from None
+
+
+def gemm_nt(a, bt, n, bias=None, act=L.ACT_NONE, gate=None, residual=None, out_dtype=None, out=None, gate_act=L.ACT_RELU,
+            pre=None):
+    """a: [M, Kp], bt: [>=n, Kp] -> [M, n] (written into `out`, a row-pitched [M, n] view, when given).
+    gate_act: how `gate` is applied (ACT_RELU: the gate's sign; a GELU: act'(gate), gate = the saved pre-activation).
+    pre: an [M, n] tensor of a's dtype that also receives the pre-activation acc + bias (b4c_gemm_nt_act)."""
     M, K = a.shape
     out_dtype = out_dtype or a.dtype
     if out is None:
@@ -390,7 +436,9 @@ def gemm_nt(a, bt, n, bias=None, act=L.ACT_NONE, gate=None, residual=None, out_d
         return out
     es = a.element_size()
     nbytes = M * K * es + n * K * es + M * n * out.element_size() + (M * n * es if gate is not None else 0) + \
-        (M * n * es if residual is not None else 0)
+        (M * n * es if residual is not None else 0) + (M * n * es if pre is not None else 0)
+    if pre is not None and (pre.dtype != a.dtype or tuple(pre.shape) != (M, n) or pre.stride(1) != 1):
+        raise B4CError('gemm_nt: pre must be a [%d, %d] %s view with unit column stride' % (M, n, a.dtype))
     # the materialised vocabulary projection (wide kernel: bf16, K <= 128, N >= 2048, plain epilogue) is its own family
     fam = 'vocab_proj' if (n >= 2048 and K <= 128 and a.dtype == torch.bfloat16 and out_dtype == torch.bfloat16 and
                            act == L.ACT_NONE and gate is None and residual is None) else 'gemm_nt'
@@ -398,6 +446,14 @@ def gemm_nt(a, bt, n, bias=None, act=L.ACT_NONE, gate=None, residual=None, out_d
     # each, matrix work -- and of the rows-only last layer, a few us each) are two families: one number would describe neither
     if fam == 'gemm_nt' and 2 * M < rec_hints.get('token_rows', 0):
         fam = 'gemm_nt_rows'
+    if pre is not None or gate_act != L.ACT_RELU or act in (L.ACT_GELU, L.ACT_GELU_TANH):
+        with _record(fam, nbytes, 2 * M * n * K):
+            L.check(L.lib().b4c_gemm_nt_act(_p(a), a.stride(0), _p(bt), bt.stride(0), _p(out), out.stride(0), M, n, K, _p(bias), act,
+                                            _p(gate), gate.stride(0) if gate is not None else 0, gate_act,
+                                            _p(residual), residual.stride(0) if residual is not None else 0,
+                                            _p(pre), pre.stride(0) if pre is not None else 0,
+                                            dt_code(a.dtype), dt_code(out_dtype), _st()), 'gemm_nt_act')
+        return out
     with _record(fam, nbytes, 2 * M * n * K):
         L.check(L.lib().b4c_gemm_nt(_p(a), a.stride(0), _p(bt), bt.stride(0), _p(out), out.stride(0), M, n, K, _p(bias), act,
                                     _p(gate), gate.stride(0) if gate is not None else 0,
@@ -1575,7 +1631,8 @@ def _as2d(x):
 # --------------------------------------------------------------------------------------
 class EmbedFn(torch.autograd.Function):
     """R6: gather + concat + *sqrt(d) + PE (+ input dropout).  apply(pe, scale, rate, seed, dtype, n, *ids, *tables);
-    n may be (n, Packed): the packed layout, output (1, T, d); or (n, Packed | None, 'sum'): the features' rows are added."""
+    n may be (n, Packed): the packed layout, output (1, T, d); or (n, Packed | None, 'sum'): the features' rows are added.
+    pe is differentiable when it is a parameter (learned positions): its gradient is b4c_pos_table_bwd's."""
 
     @staticmethod
     def forward(ctx, pe, scale, rate, seed, dtype, n, *args):
@@ -1603,9 +1660,15 @@ class EmbedFn(torch.autograd.Function):
             lz = getattr(t, '_b4c_lazy', None)
             if lz is not None:
                 lz.catch_up(i, note=ctx.needs_input_grad[6 + n + j])
-        out, key_pad = embed_concat_pe_fwd(dense_ids, [t.detach() for t in tables], pe, scale, rate, seed, dtype, packed, combine)
+        out, key_pad = embed_concat_pe_fwd(dense_ids, [t.detach() for t in tables], pe.detach(), scale, rate, seed, dtype, packed,
+                                           combine)
         ctx.save_for_backward(*ids, *tables)
         ctx.n, ctx.scale, ctx.rate, ctx.seed = n, scale, rate, seed
+        if ctx.needs_input_grad[0]:        # a learned positional table: what its gradient kernel needs
+            ctx.pe = pe
+            if packed is not None and packed.packed_of is None:
+                raise B4CError('learned positions in the packed layout need Packed.packed_of (the row of every dense position)')
+            ctx.seqs = (dense_ids[0].shape[0], dense_ids[0].shape[1], packed.packed_of if packed is not None else None)
         ctx.mark_non_differentiable(key_pad)
         ctx.set_materialize_grads(False)       # (or autograd fills a zero "gradient" of key_pad's size every step)
         return out, key_pad
@@ -1617,11 +1680,21 @@ class EmbedFn(torch.autograd.Function):
         flush_pending_dw(getattr(tables[0], '_b4c_ctx', None))
         if dout is None:
             return (None,) * (6 + 2 * ctx.n)
-        dout = dout.reshape(ids[0].shape[0], ids[0].shape[1], -1)
+        dout = dout.reshape(ids[0].shape[0], ids[0].shape[1], -1).contiguous()
+        dpe = None
+        if ctx.needs_input_grad[0]:
+            B, S, row_of = ctx.seqs
+            # dense layout: sequence b owns rows b*S .. (b+1)*S, pad rows included (the forward adds P there too); packed: the row
+            # of a dense position is packed_of's (a Cloze batch pads BEFORE its closing [SEP]: positions are not 0 .. len-1)
+            cu = dense_cu(B, S, dout.device) if row_of is None else None
+            pactx, (psink,) = grad_sinks(ctx.pe)
+            pos_table_bwd(dout, cu, B, S, ctx.rate, ctx.seed, psink, row_of=row_of)
+            _ready(ctx.pe)
+            dpe = None if pactx is not None else psink
         actx, sinks = grad_sinks(*tables)
-        embed_concat_pe_bwd(ids, tables, dout.contiguous(), ctx.scale, ctx.rate, ctx.seed, into=sinks)
+        embed_concat_pe_bwd(ids, tables, dout, ctx.scale, ctx.rate, ctx.seed, into=sinks)
         _ready(*tables)
-        return sink_returns(ctx, (None,) * (6 + ctx.n), actx, sinks)
+        return sink_returns(ctx, (dpe,) + (None,) * (5 + ctx.n), actx, sinks)
 
 
 class AttnBlockFn(torch.autograd.Function):
@@ -1772,18 +1845,23 @@ class MQAttnBlockFn(torch.autograd.Function):
 
 
 class FFNBlockFn(torch.autograd.Function):
-    """R9 + second half of R10: LN2(x + drop(relu(x W1 + b1) W2 + b2))."""
+    """R9 + second half of R10: LN2(x + drop(act(x W1 + b1) W2 + b2)), act = relu (the reference) or a GELU (`act`: B4C_ACT_*,
+    no reference counterpart).  A GELU block saves the pre-activation u beside h = gelu(u) -- one GEMM launch writes both --
+    and its backward gates with gelu'(u); the fused kernels (b4c_ffn_fwd / b4c_ffn_bwd) are ReLU kernels and are not taken."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, pk1, pk2, rate, seed, training):
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, pk1, pk2, rate, seed, training, act=L.ACT_RELU):
         T_tok, d = x.shape
         wt1, _, bb1 = pk1.get(x.dtype, d, training)
         Fp = pk1.Np
         wt2, _, bb2 = pk2.get(x.dtype, Fp, training)
-        if fused_ffn_fwd and ffn_fwd_supported(x, Fp):
+        relu = act == L.ACT_RELU
+        # a GELU block in training: the pre-activation leaves the first GEMM beside h (inference saves nothing extra)
+        u = torch.empty(T_tok, Fp, dtype=x.dtype, device=x.device) if (training and not relu) else None
+        if relu and fused_ffn_fwd and ffn_fwd_supported(x, Fp):
             h, z, out, stats = ffn_fwd(x, wt1, bb1, wt2, bb2, gamma.detach(), beta.detach(), pk1.N, Fp, rate if training else 0.0, seed,
                                        save=training)
-        elif gemm_ln_supported((h := gemm_nt(x, wt1, Fp, bb1, act=L.ACT_RELU)), d):
+        elif gemm_ln_supported((h := gemm_nt(x, wt1, Fp, bb1, act=act, pre=u)), d):
             z, out, stats = gemm_nt_add_ln(h, wt2, bb2, x, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
                                            save=training)
         else:
@@ -1791,14 +1869,15 @@ class FFNBlockFn(torch.autograd.Function):
             z, out, stats = add_dropout_layernorm_fwd(x, y, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
                                                       save=training)
         if training:
-            ctx.save_for_backward(x, h, z, stats, gamma)
+            ctx.save_for_backward(x, h, z, stats, gamma, *(() if relu else (u,)))
             ctx.pk = (pk1, pk2)
             ctx.dims = (rate, seed)
+            ctx.act = act
             ctx.params = (w1, b1, w2, b2, gamma, beta)
             # A model of the fused kernels' shape runs the head's dW sweep in the foreground (_background_dw_for) -- decided by the
             # SHAPE, whatever the batch's row count, so that it agrees with background_dw_expected(), by which callers order their
             # gradient arenas (a background sweep's gradient completes last and belongs to the reducer's last bucket)
-            if fused_ffn_bwd and ffn_bwd_shape_ok(x, h, z):
+            if relu and fused_ffn_bwd and ffn_bwd_shape_ok(x, h, z):
                 actx = arena_context(w1, b1, w2, b2, gamma, beta)
                 if actx is not None:
                     actx.fused_blocks = True
@@ -1806,22 +1885,24 @@ class FFNBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        x, h, z, stats, gamma = ctx.saved_tensors
+        x, h, z, stats, gamma = ctx.saved_tensors[:5]
         pk1, pk2 = ctx.pk
         rate, seed = ctx.dims
+        relu = ctx.act == L.ACT_RELU
         w1, b1, w2, b2, gam, bet = ctx.params
         d, Fp = x.shape[1], h.shape[1]
         actx, sinks = grad_sinks(*ctx.params)
         gw1, gb1, gw2, gb2, ggam, gbet = sinks
         _, wc1, _ = pk1.get(x.dtype, d, True)
         _, wc2, _ = pk2.get(x.dtype, Fp, True)
-        if _arena_routes(actx) and fused_ffn_bwd and ffn_bwd_supported(x, h, z):
+        if relu and _arena_routes(actx) and fused_ffn_bwd and ffn_bwd_supported(x, h, z):
             dx = ffn_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, h, x, wc2, wc1, pk1.N, gw1, gb1, gw2, gb2, ggam, gbet)
             _ready(w1, b1, w2, b2, gam, bet)
             return sink_returns(ctx, (dx,), actx, sinks)
         dz, dy, _, _ = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, into=(ggam, gbet))
         queue_dw(actx, h, dy, pk2.K, d, [gw2], [gb2], (w2, b2))
-        dh = gemm_nt(dy, wc2, Fp, gate=h)
+        # ReLU: the saved activation's sign; GELU: gelu'(u) of the saved pre-activation (gelu is not invertible)
+        dh = gemm_nt(dy, wc2, Fp, gate=h) if relu else gemm_nt(dy, wc2, Fp, gate=ctx.saved_tensors[5], gate_act=ctx.act)
         queue_dw(actx, x, dh, d, pk1.N, [gw1], [gb1], (w1, b1))
         dx = gemm_nt(dh, wc1, d, residual=dz)
         _ready(gam, bet)
@@ -1898,11 +1979,12 @@ class MLPFn(torch.autograd.Function):
 overlap_vocab_dw = {'1': True, '0': False}.get(os.environ.get('B4C_OVERLAP_DW', ''), None)
 
 
-def background_dw_expected(d_model, dff, dtype):
-    """Will a model of this shape run the vocabulary head's dW sweep as a background job (see overlap_vocab_dw)?"""
+def background_dw_expected(d_model, dff, dtype, ffn_activation='relu'):
+    """Will a model of this shape run the vocabulary head's dW sweep as a background job (see overlap_vocab_dw)?
+    (The fused feed-forward backward is a ReLU kernel: a GELU model never takes it and keeps the background sweep.)"""
     if overlap_vocab_dw is not None:
         return overlap_vocab_dw
-    return not (fused_ffn_bwd and d_model == 128 and dff <= 128 and dtype == torch.bfloat16)
+    return not (fused_ffn_bwd and d_model == 128 and dff <= 128 and dtype == torch.bfloat16 and ffn_activation == 'relu')
 
 
 def _background_dw_for(actx):

@@ -49,6 +49,8 @@ extern "C" {
 
 #define B4C_ACT_NONE 0
 #define B4C_ACT_RELU 1
+#define B4C_ACT_GELU 2       /* x Phi(x), Phi through erf (Keras / torch default)                    */
+#define B4C_ACT_GELU_TANH 3  /* 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) (the BERT4Rec code)  */
 
 #define B4C_CE_TF 0    /* clip[1e-7,1-1e-7] -> log -> log-softmax (tf.keras.backend, TF 2.3.1) */
 #define B4C_CE_PLAIN 1 /* -log p_y                                                            */
@@ -81,6 +83,21 @@ int b4c_embed_concat_pe_bwd(int n_feat, const int64_t *const *h_ids, float *cons
                             const int *h_dims, const int64_t *h_rows, float scale, const void *dout,
                             int ld_dout, int B, int S, int d_model, float dropout_rate, uint64_t seed,
                             int dtype, void *stream);
+/* LEARNED POSITIONS (no reference counterpart; the reference's table is the fixed sinusoid): gradient of the embedding stage
+ * w.r.t. the positional table `pe` of b4c_embed_concat_pe_fwd / _fwd_packed,
+ *   dpe[s][j] += sum over sequences b with cu[b+1] - cu[b] > s of  keep(e) / (1 - rate) * dout[cu[b] + s][j],   s < S,
+ * e = (cu[b] + s) * d_model + j: the element index, and so the dropout mask, of the forward pass (and of b4c_embed_concat_pe_bwd).
+ * cu int32 [B+1]: row of every sequence's first token in dout -- b * S in the dense layout (pad rows then count: the forward adds
+ * pe there too); sequences longer than S contribute their first S rows.  row_of (int32 [B*S], or NULL): when given, the row of
+ * position s of sequence b is row_of[b*S + s] (negative: none) and cu is not read -- packed_of of b4c_nonpad_positions, for the
+ * packed layout, whose forward takes row t's position from token_src[t] % S: pads need not be at a sequence's end (the Cloze
+ * batches keep the closing [SEP] at S - 1).  Rows outside [0, n_rows), n_rows = rows of dout, are skipped.  dpe fp32 [>= S][d_model], ADDED to; rows >= S are not touched.  dout T [.][ld_dout],
+ * rows * ld_dout may exceed 2^31.  d_model % 8 == 0, <= 2048.  No float atomics: workgroups sum contiguous blocks of sequences
+ * in sequence order into the workspace, and the blocks are added in block order -- the same bits on every launch. */
+int64_t b4c_pos_table_bwd_workspace_bytes(int B, int S, int d_model);
+int b4c_pos_table_bwd(const void *dout, int ld_dout, int64_t n_rows, const int32_t *cu, const int32_t *row_of, int B, int S,
+                      int d_model, float dropout_rate, uint64_t seed, float *dpe, void *workspace, int64_t workspace_bytes,
+                      int dtype, void *stream);
 /* same, given for every feature the token indices sorted by id (order[f][p], int32, any order among equal ids):
  * runs of one id are summed in registers and written once -- two float atomics per distinct id and wave boundary
  * instead of one per token and column.  The sort is the caller's (one radix sort of B*S keys per feature). */
@@ -126,7 +143,7 @@ int b4c_pack_weights_batched(const b4c_pack_desc *d_desc, int n_desc, int max_ti
 
 /* C[M][N] = epilogue( A[M][K] . Bt[N][K]^T )     (both operands K-contiguous)
  *   v = acc + bias[n]            (bias fp32 or NULL)
- *   v = relu(v)                  if act == B4C_ACT_RELU
+ *   v = relu(v)                  if act == B4C_ACT_RELU;   v = gelu(v) if act == B4C_ACT_GELU / B4C_ACT_GELU_TANH (fp32)
  *   v = v * (gate[m][n] > 0)     if gate != NULL   (ReLU backward: gate = saved activation, pitch ldg)
  *   v = v + residual[m][n]       if residual != NULL (T, pitch ldr)
  * out_dtype chooses C's element type (T of `dtype`, or B4C_F32 for fp32 logits from bf16 inputs).
@@ -136,6 +153,16 @@ int b4c_pack_weights_batched(const b4c_pack_desc *d_desc, int n_desc, int max_ti
 int b4c_gemm_nt(const void *A, int lda, const void *Bt, int ldb, void *C, int ldc, int M, int N, int K,
                 const float *bias, int act, const void *gate, int ldg, const void *residual, int ldr,
                 int dtype, int out_dtype, void *stream);
+/* b4c_gemm_nt with two more operands (no reference counterpart: the GELU feed-forward block of the BERT4Rec paper):
+ *   pre [M][ldp] (T, or NULL): the pre-activation u = acc + bias is written as well -- what the backward of a GELU needs, which
+ *     cannot be recovered from gelu(u).  Bit-identical to C of b4c_gemm_nt(..., act = B4C_ACT_NONE) with out_dtype == dtype on
+ *     the same operands (N < 2048 or K > 128: the wide-N route of the plain launch rounds on its own); C is the same with or
+ *     without it.  M * ldp may exceed 2^31 elements.
+ *   gate_act: how `gate` is applied.  B4C_ACT_RELU: v * (gate > 0), as b4c_gemm_nt.  B4C_ACT_GELU / B4C_ACT_GELU_TANH:
+ *     v * act'(gate), gate = the saved pre-activation u; the derivative is evaluated in fp32 (erf: Phi(u) + u phi(u)). */
+int b4c_gemm_nt_act(const void *A, int lda, const void *Bt, int ldb, void *C, int ldc, int M, int N, int K,
+                    const float *bias, int act, const void *gate, int ldg, int gate_act, const void *residual, int ldr,
+                    void *pre, int ldp, int dtype, int out_dtype, void *stream);
 
 /* R9/R10 fused with the GEMM that feeds them (bf16, N <= 256; N > 128 runs 64-row x 256-column workgroups):
  *   y = A . Bt^T + bias;  z = x + dropout(y);  out = LayerNorm(z) * gamma + beta;  stats = (mean, rstd)

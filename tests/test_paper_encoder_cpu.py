@@ -1,0 +1,110 @@
+"""Host side of the paper-faithful encoder extensions (no GPU): the GELU activation codes and the new entry points in the C
+header and its binding, constructor validation and get_config() rules of `ffn_activation` / `position_encoding` /
+`max_positions`, state-dict names, the weight-decay exclusion list, and the background-sweep rule of a GELU model."""
+import pytest
+import torch
+
+DEFAULT_KEYS = [
+    'head.intermediate_layers.0.kernel', 'head.intermediate_layers.0.bias', 'head.output_layer.kernel', 'head.output_layer.bias',
+    'transformer.encoder.enc_layers.0.mha.wq.kernel', 'transformer.encoder.enc_layers.0.mha.wq.bias',
+    'transformer.encoder.enc_layers.0.mha.wk.kernel', 'transformer.encoder.enc_layers.0.mha.wk.bias',
+    'transformer.encoder.enc_layers.0.mha.wv.kernel', 'transformer.encoder.enc_layers.0.mha.wv.bias',
+    'transformer.encoder.enc_layers.0.mha.dense.kernel', 'transformer.encoder.enc_layers.0.mha.dense.bias',
+    'transformer.encoder.enc_layers.0.ffn.0.kernel', 'transformer.encoder.enc_layers.0.ffn.0.bias',
+    'transformer.encoder.enc_layers.0.ffn.1.kernel', 'transformer.encoder.enc_layers.0.ffn.1.bias',
+    'transformer.encoder.enc_layers.0.layernorm1.gamma', 'transformer.encoder.enc_layers.0.layernorm1.beta',
+    'transformer.encoder.enc_layers.0.layernorm2.gamma', 'transformer.encoder.enc_layers.0.layernorm2.beta',
+    'transformer.embedding_layers.items.weight']
+
+
+def _model(**kw):
+    from bert4clickpath_amd.clickstream_transformer import ClickstreamTransformer, SoftMaxHead
+    V = 20
+    return ClickstreamTransformer({'items': ['asin']}, {'items': ['i%d' % i for i in range(V)]}, {'items': 16}, SoftMaxHead([8], V),
+                                  value_to_head='[MASK]', num_encoder_layers=1, num_attention_heads=2, dropout_rate=0.0, **kw)
+
+
+def test_header_constants_abi_and_entry_points():
+    from bert4clickpath_amd import _lib as L
+    consts = L.header_constants(L._header_text(L.HEADER_PATH))
+    assert consts['B4C_ACT_GELU'] == 2 and consts['B4C_ACT_GELU_TANH'] == 3
+    assert (L.ACT_NONE, L.ACT_RELU, L.ACT_GELU, L.ACT_GELU_TANH) == (0, 1, 2, 3)
+    assert L.ABI_VERSION == 12
+    names = L.declared_symbols()
+    for n in ('b4c_gemm_nt_act', 'b4c_pos_table_bwd', 'b4c_pos_table_bwd_workspace_bytes'):
+        assert n in names
+    sig = L.signatures()
+    assert len(sig['b4c_gemm_nt_act'][1]) == len(sig['b4c_gemm_nt'][1]) + 3      # gate_act, pre, ldp
+    assert sig['b4c_gemm_nt'][1] == L.parse_header(L._header_text(L.HEADER_PATH))['b4c_gemm_nt'][1]
+
+
+def test_constructor_validation():
+    from bert4clickpath_amd.clickstream_transformer import transformer as T
+    with pytest.raises(ValueError):
+        _model(ffn_activation='swish')
+    with pytest.raises(ValueError):
+        _model(position_encoding='learned')
+    with pytest.raises(ValueError):
+        _model(position_encoding='rotary', max_positions=8)
+    for cls, args in ((T.Encoder, (1, 16, 2, 8, 0.0)), (T.EncoderLayer, (16, 2, 8, 0.0)), (T.point_wise_feed_forward_network, (16, 8))):
+        with pytest.raises(ValueError):
+            cls(*args, ffn_activation='GELU')
+        for name in ('relu', 'gelu', 'gelu_tanh'):
+            cls(*args, ffn_activation=name)
+    with pytest.raises(ValueError):
+        T.Transformer(1, 2, {'items': 30}, {'items': 16}, 8, 0.0, ffn_activation=None)
+
+
+def test_get_config_key_rules_and_round_trip():
+    from bert4clickpath_amd.clickstream_transformer import ClickstreamTransformer
+    base = _model()
+    for cfg in (base.get_config(), base.transformer.get_config(), base.transformer.encoder.get_config(),
+                base.transformer.encoder.enc_layers[0].get_config()):
+        assert not {'ffn_activation', 'position_encoding', 'max_positions'} & set(cfg)
+    m = _model(ffn_activation='gelu_tanh', position_encoding='learned', max_positions=40)
+    cfg = m.get_config()
+    assert cfg['ffn_activation'] == 'gelu_tanh' and cfg['position_encoding'] == 'learned' and cfg['max_positions'] == 40
+    tcfg = m.transformer.get_config()
+    assert tcfg['ffn_activation'] == 'gelu_tanh' and tcfg['position_encoding'] == 'learned' and tcfg['max_positions'] == 40
+    assert m.transformer.encoder.get_config()['ffn_activation'] == 'gelu_tanh'
+    assert m.transformer.encoder.enc_layers[0].get_config()['ffn_activation'] == 'gelu_tanh'
+    again = ClickstreamTransformer(**cfg)
+    assert again.get_config() == cfg and again.transformer.get_config() == tcfg
+    g = _model(ffn_activation='gelu')
+    assert g.get_config()['ffn_activation'] == 'gelu' and 'position_encoding' not in g.get_config()
+    assert set(_model(ffn_activation='relu', position_encoding='sinusoidal').get_config()) == set(base.get_config())
+
+
+def test_state_dict_names():
+    assert list(_model().state_dict().keys()) == DEFAULT_KEYS
+    assert list(_model(ffn_activation='gelu').state_dict().keys()) == DEFAULT_KEYS
+    m = _model(position_encoding='learned', max_positions=40)
+    keys = list(m.state_dict().keys())
+    assert sorted(keys) == sorted(DEFAULT_KEYS + ['transformer.position_embedding.weight'])
+    w = m.transformer.position_embedding.weight
+    assert w.shape == (40, 16) and w.dtype == torch.float32 and w.requires_grad
+    assert float(w.detach().abs().max()) <= 0.04 and 0.01 < float(w.detach().std()) < 0.03       # N(0, 0.02^2) cut at two sigma
+    assert any(p is w for p in m.parameters())
+
+
+def test_weight_decay_list_does_not_hold_the_position_table():
+    from bert4clickpath_amd import optim
+    m = _model(position_encoding='learned', max_positions=40)
+    w = m.transformer.position_embedding.weight
+    assert not any(p is w for p in optim.no_decay_params(m))
+
+
+def test_background_sweep_rule_sees_the_activation():
+    from bert4clickpath_amd import ops
+    prev = ops.overlap_vocab_dw
+    ops.overlap_vocab_dw = None
+    try:
+        fused = ops.background_dw_expected(128, 100, torch.bfloat16)
+        assert fused == (not ops.fused_ffn_bwd)
+        assert ops.background_dw_expected(128, 100, torch.bfloat16, ffn_activation='relu') == fused
+        non_fused = ops.background_dw_expected(128, 136, torch.bfloat16)
+        assert non_fused is True
+        for name in ('gelu', 'gelu_tanh'):
+            assert ops.background_dw_expected(128, 100, torch.bfloat16, ffn_activation=name) == non_fused
+    finally:
+        ops.overlap_vocab_dw = prev
