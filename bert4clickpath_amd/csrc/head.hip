@@ -872,78 +872,73 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_rows_bf16_reg_kernel(const 
     }
 }
 
-extern "C" int b4c_topk_rows(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx,
-                             const int32_t *labels, float *hit, float *ndcg, int dtype, void *stream) {
-    return b4c_topk_rows_ws(scores, ld, R, V, k, topk_idx, labels, hit, ndcg, nullptr, dtype, stream);
-}
-
+// The materialised ranking, without (E == 0) and with per-row exclusion lists (b4c_exclusions_prep form).  `scores` is read only.
 // `redo` (int32 [R], scratch) enables the threshold kernel; rows it could not finish (more than TOPK_CAP candidates:
 // massive ties) are redone by the per-thread-list kernel.  redo == NULL: list kernel for every row.
-extern "C" int b4c_topk_rows_ws(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx,
-                                const int32_t *labels, float *hit, float *ndcg, int32_t *redo, int dtype, void *stream) {
-    B4C_REQUIRE(scores && topk_idx && R >= 0 && V > 0, "topk_rows: bad argument");
-    B4C_REQUIRE(k >= 1 && k <= B4C_MAX_TOPK && k <= V, "topk_rows: k=%d must be in [1, min(%d, V)]", k, B4C_MAX_TOPK);
-    B4C_REQUIRE(ld % 8 == 0 && ld >= V, "topk_rows: pitch");
+// `who` names the entry point in messages.
+static int topk_rows_run(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx, const int32_t *labels, float *hit,
+                         float *ndcg, int32_t *redo, int dtype, const int32_t *excl, int ld_e, int E, void *stream, const char *who) {
+    B4C_REQUIRE(E >= 0 && E <= B4C_MAX_EXCL, "%s: E = %d (0 .. %d)", who, E, B4C_MAX_EXCL);
+    B4C_REQUIRE(E == 0 || (excl && ld_e >= E), "%s: exclusion list (ld_e = %d, E = %d)", who, ld_e, E);
+    B4C_REQUIRE(scores && topk_idx && R >= 0 && V > 0, "%s: bad argument", who);
+    B4C_REQUIRE(k >= 1 && k <= B4C_MAX_TOPK && k <= V, "%s: k=%d must be in [1, min(%d, V)]", who, k, B4C_MAX_TOPK);
+    B4C_REQUIRE(ld % 8 == 0 && ld >= V, "%s: pitch", who);
+    // without a list, a call with no rows has never looked at dtype
+    B4C_REQUIRE(dtype == B4C_F32 || dtype == B4C_BF16 || (E == 0 && R == 0), "%s: dtype %d", who, dtype);
     if (R == 0) return B4C_OK;
-    const int grid = (int)(R < 4096 ? R : 4096);
+    const int grid = (int)(R < 4096 ? R : 4096), g2 = (int)(R < 2048 ? R : 2048);
     hipStream_t st = (hipStream_t)stream;
-    if (redo) {
-        const int g2 = (int)(R < 2048 ? R : 2048);
-        if (dtype == B4C_F32) topk_rows_kernel<float><<<g2, TOPK_THREADS, 0, st>>>((const float *)scores, ld, R, V, k, topk_idx, labels, hit, ndcg, redo);
-        else if (dtype == B4C_BF16) {
-            const int per_thread = ((V + 7) / 8 + TOPK_THREADS - 1) / TOPK_THREADS;      // 16-B chunks per thread
-            const bool al = (((uintptr_t)scores) & 15) == 0;
-#define TOPK_REG(N) topk_rows_bf16_reg_kernel<N><<<g2, TOPK_THREADS, 0, st>>>((const bf16_t *)scores, ld, R, V, k, topk_idx, labels, hit, ndcg, redo)
-            if (al && per_thread <= 4) TOPK_REG(4);
-            else if (al && per_thread <= 8) TOPK_REG(8);
-            else if (al && per_thread <= 13) TOPK_REG(13);
-            else if (al && per_thread <= 16) TOPK_REG(16);
-            else topk_rows_kernel<bf16_t><<<g2, TOPK_THREADS, 0, st>>>((const bf16_t *)scores, ld, R, V, k, topk_idx, labels, hit, ndcg, redo);
-#undef TOPK_REG
-        }
-        else B4C_REQUIRE(false, "topk_rows: dtype %d", dtype);
-    }
-#define TOPK_LAUNCH(T, KM) topk_rows_lists_kernel<T, KM><<<grid, 256, 0, st>>>((const T *)scores, ld, R, V, k, topk_idx, labels, hit, ndcg, redo)
+    const bool f32 = dtype == B4C_F32;
+#define TOPK_ARGS(T) (const T *)scores, ld, R, V, k, topk_idx, labels, hit, ndcg, redo
+#define TOPK_REG(N) topk_rows_bf16_reg_kernel<N><<<g2, TOPK_THREADS, 0, st>>>(TOPK_ARGS(bf16_t))
+#define TOPK_ROWS(T)                                                                               \
+    do {                                                                                           \
+        if (E) topk_rows_excl_kernel<T><<<g2, TOPK_THREADS, 0, st>>>(TOPK_ARGS(T), excl, ld_e, E); \
+        else topk_rows_kernel<T><<<g2, TOPK_THREADS, 0, st>>>(TOPK_ARGS(T));                       \
+    } while (0)
+#define TOPK_LAUNCH(T, KM)                                                                            \
+    do {                                                                                              \
+        if (E) topk_rows_lists_excl_kernel<T, KM><<<grid, 256, 0, st>>>(TOPK_ARGS(T), excl, ld_e, E); \
+        else topk_rows_lists_kernel<T, KM><<<grid, 256, 0, st>>>(TOPK_ARGS(T));                       \
+    } while (0)
 #define TOPK_DISPATCH(T)                  \
     if (k <= 1) TOPK_LAUNCH(T, 1);        \
     else if (k <= 4) TOPK_LAUNCH(T, 4);   \
     else if (k <= 8) TOPK_LAUNCH(T, 8);   \
     else TOPK_LAUNCH(T, 16);
-    if (dtype == B4C_F32) { TOPK_DISPATCH(float) }
-    else if (dtype == B4C_BF16) { TOPK_DISPATCH(bf16_t) }
-    else B4C_REQUIRE(false, "topk_rows: dtype %d", dtype);
-    return b4c_check_launch("topk_rows");
+    if (redo) {
+        // bf16 without a list: the register-resident form, if the row fits (it has no exclusion variant)
+        const int per_thread = ((V + 7) / 8 + TOPK_THREADS - 1) / TOPK_THREADS;      // 16-B chunks per thread
+        const bool reg = E == 0 && (((uintptr_t)scores) & 15) == 0 && per_thread <= 16;
+        if (f32) TOPK_ROWS(float);
+        else if (!reg) TOPK_ROWS(bf16_t);
+        else if (per_thread <= 4) TOPK_REG(4);
+        else if (per_thread <= 8) TOPK_REG(8);
+        else if (per_thread <= 13) TOPK_REG(13);
+        else TOPK_REG(16);
+    }
+    if (f32) { TOPK_DISPATCH(float) }
+    else { TOPK_DISPATCH(bf16_t) }
+#undef TOPK_DISPATCH
+#undef TOPK_LAUNCH
+#undef TOPK_ROWS
+#undef TOPK_REG
+#undef TOPK_ARGS
+    return b4c_check_launch(who);
 }
 
-// the materialised ranking with per-row exclusion lists (b4c_exclusions_prep form): the threshold kernel (fp32 and bf16 alike:
-// the register-resident bf16 form has no exclusion variant), then the list kernel for the rows it flags.  `scores` is read only.
+extern "C" int b4c_topk_rows(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx,
+                             const int32_t *labels, float *hit, float *ndcg, int dtype, void *stream) {
+    return topk_rows_run(scores, ld, R, V, k, topk_idx, labels, hit, ndcg, nullptr, dtype, nullptr, 0, 0, stream, "topk_rows");
+}
+
+extern "C" int b4c_topk_rows_ws(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx,
+                                const int32_t *labels, float *hit, float *ndcg, int32_t *redo, int dtype, void *stream) {
+    return topk_rows_run(scores, ld, R, V, k, topk_idx, labels, hit, ndcg, redo, dtype, nullptr, 0, 0, stream, "topk_rows");
+}
+
 extern "C" int b4c_topk_rows_excl(const void *scores, int ld, int64_t R, int V, int k, int32_t *topk_idx, const int32_t *labels,
                                   float *hit, float *ndcg, int32_t *redo, int dtype, const int32_t *excl, int ld_e, int E,
                                   void *stream) {
-    B4C_REQUIRE(E >= 0 && E <= B4C_MAX_EXCL, "topk_rows_excl: E = %d (0 .. %d)", E, B4C_MAX_EXCL);
-    B4C_REQUIRE(E == 0 || (excl && ld_e >= E), "topk_rows_excl: exclusion list (ld_e = %d, E = %d)", ld_e, E);
-    if (E == 0) return b4c_topk_rows_ws(scores, ld, R, V, k, topk_idx, labels, hit, ndcg, redo, dtype, stream);
-    B4C_REQUIRE(scores && topk_idx && R >= 0 && V > 0, "topk_rows_excl: bad argument");
-    B4C_REQUIRE(k >= 1 && k <= B4C_MAX_TOPK && k <= V, "topk_rows_excl: k=%d must be in [1, min(%d, V)]", k, B4C_MAX_TOPK);
-    B4C_REQUIRE(ld % 8 == 0 && ld >= V, "topk_rows_excl: pitch");
-    B4C_REQUIRE(dtype == B4C_F32 || dtype == B4C_BF16, "topk_rows_excl: dtype %d", dtype);
-    if (R == 0) return B4C_OK;
-    const int grid = (int)(R < 4096 ? R : 4096);
-    hipStream_t st = (hipStream_t)stream;
-    if (redo) {
-        const int g2 = (int)(R < 2048 ? R : 2048);
-        if (dtype == B4C_F32)
-            topk_rows_excl_kernel<float><<<g2, TOPK_THREADS, 0, st>>>((const float *)scores, ld, R, V, k, topk_idx, labels, hit, ndcg,
-                                                                      redo, excl, ld_e, E);
-        else
-            topk_rows_excl_kernel<bf16_t><<<g2, TOPK_THREADS, 0, st>>>((const bf16_t *)scores, ld, R, V, k, topk_idx, labels, hit, ndcg,
-                                                                       redo, excl, ld_e, E);
-    }
-#undef TOPK_LAUNCH
-#define TOPK_LAUNCH(T, KM) topk_rows_lists_excl_kernel<T, KM><<<grid, 256, 0, st>>>((const T *)scores, ld, R, V, k, topk_idx, labels, \
-                                                                                 hit, ndcg, redo, excl, ld_e, E)
-    if (dtype == B4C_F32) { TOPK_DISPATCH(float) }
-    else { TOPK_DISPATCH(bf16_t) }
-#undef TOPK_LAUNCH
-    return b4c_check_launch("topk_rows_excl");
+    return topk_rows_run(scores, ld, R, V, k, topk_idx, labels, hit, ndcg, redo, dtype, excl, ld_e, E, stream, "topk_rows_excl");
 }

@@ -1363,18 +1363,18 @@ __global__ void __launch_bounds__(64) vce_label_logit_kernel(VceScanArgs a, floa
     }
 }
 
-// NH = 1: 128 tokens per workgroup, 8 waves = 4 token groups x the 2 halves of each 128-row W tile;
-// NH = 2: 256 tokens per workgroup, 8 token groups, every wave takes both halves in turn -- each W tile (32 KB by LDS-DMA
-// from L2 / Infinity Cache: the sweeps stream the whole of W once per token tile, 4.1 GB per sweep at C2, and that stream, not
-// the matrix pipe, paces them) serves twice the tokens.
-// The exclusion-aware sweeps (b4c_vocab_rank_excl / b4c_vocab_topk_excl): the same arguments plus every row's canonical list
-// (b4c_exclusions_prep: ids of [0, V) ascending, -1 after the last).  A separate type, so that the kernels without exclusions
-// keep their argument block and their code.
+// The exclusion-aware sweeps (b4c_vocab_rank_excl / b4c_vocab_topk_excl, EX = true) take the same arguments plus every row's
+// canonical list (b4c_exclusions_prep: ids of [0, V) ascending, -1 after the last).  A derived type, chosen by EX, so that the
+// kernels without exclusions keep their argument block and their code.
 struct VceScanExArgs : VceScanArgs {
     const int32_t *excl;
     int ld_e, E;
 };
 
+// NH = 1: 128 tokens per workgroup, 8 waves = 4 token groups x the 2 halves of each 128-row W tile;
+// NH = 2: 256 tokens per workgroup, 8 token groups, every wave takes both halves in turn -- each W tile (32 KB by LDS-DMA
+// from L2 / Infinity Cache: the sweeps stream the whole of W once per token tile, 4.1 GB per sweep at C2, and that stream, not
+// the matrix pipe, paces them) serves twice the tokens.
 // Exclusions inside the sweep (EX = true).  Each lane owns one token and, of every half-tile it scores, the 32 vocabulary rows
 // base + 4 hf + 32 rt + (t & 3) + 8 (t >> 2) of its accumulator slots.  It walks its token's sorted list with a cursor: xn =
 // the next excluded id not yet passed, xq = the one after it (loaded one step ahead, so the walk never waits on its own load).
@@ -1383,25 +1383,263 @@ struct VceScanExArgs : VceScanArgs {
 // -inf: no comparison of the sweeps holds for it (x > ref, x == ref, x >= tau with tau = -inf when fewer than k items
 // remain), and fmaxf drops it, so an excluded entry neither counts before the label, nor reaches a class maximum, nor is
 // collected.
-// the exclusion fields of either argument block (read in the EX = true parts of the body only)
-struct VceExView {
-    const int32_t *excl;
-    int ld_e, E;
-};
-__device__ __forceinline__ VceExView vce_ex(const VceScanArgs &) { return {nullptr, 0, 0}; }
-__device__ __forceinline__ VceExView vce_ex(const VceScanExArgs &a) { return {a.excl, a.ld_e, a.E}; }
+template <int KD, int OP, int NH, bool EX>
+__global__ void __launch_bounds__(512, 2) vce_scan_kernel(std::conditional_t<EX, VceScanExArgs, VceScanArgs> a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NKS = KD / 16, STR = VTile<KD>::STR;
+    constexpr int TILE_B = VTile<KD>::BYTES;
+    float *sBias = reinterpret_cast<float *>(smem + 2 * TILE_B);     // [3][128]: a ring -- the scores of a tile's second half are
+                                                                     // formed one tile later, while the next bias arrives
+    const int unit = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hf = lane >> 5;
+    const int tg = NH == 2 ? wave : (wave & 3), vh = NH == 2 ? 0 : (wave >> 2);
+    const int64_t tok0 = (int64_t)(unit % a.ntt) * (128 * NH);
+    const int64_t tok = tok0 + tg * 32 + r;
+    const int part = unit / a.ntt;
+    const int nvt = (a.V + 127) >> 7;
+    const int vt0 = (int)((int64_t)nvt * part / a.parts), vt1 = (int)((int64_t)nvt * (part + 1) / a.parts);
+    const bool live = tok < a.R;
 
-// The body is vce_scan_body.inc, included by both kernels: each is a kernel of its own, compiled as written (the form without
-// exclusions is the code it was before they existed).
-template <int KD, int OP, int NH>
-__global__ void __launch_bounds__(512, 2) vce_scan_kernel(VceScanArgs a) {
-    constexpr bool EX = false;
-#include "vce_scan_body.inc"
-}
-template <int KD, int OP, int NH>
-__global__ void __launch_bounds__(512, 2) vce_scan_excl_kernel(VceScanExArgs a) {
-    constexpr bool EX = true;
-#include "vce_scan_body.inc"
+    bf16x8 hfr[NKS];
+    vce_load_hfrag<KD>(a.h, a.ld_h, tok, a.R, hf, hfr);
+    int foff[NKS];
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) foff[ks] = VTile<KD>::frag_off(r, ks, hf) + vh * 64 * STR;
+
+    // per-lane state
+    float ref = INFINITY;          // RANK: x_y;  COLLECT: tau  (+inf: nothing counts / nothing is collected)
+    int y = -1;
+    if (OP == SCAN_RANK && live) { ref = a.xy[tok]; y = a.labels[tok]; }
+    if (OP == SCAN_COLLECT && live) ref = a.tau[tok];
+    unsigned n_before = 0;         // RANK
+    float cm[16];                  // CLASSMAX
+#pragma unroll
+    for (int t = 0; t < 16; ++t) cm[t] = -INFINITY;
+
+    int xn = 0x7fffffff, xq = 0x7fffffff, xp = 0;     // EX: cursor (next excluded id, the one after it, index of the latter)
+    const int32_t *xl = nullptr;
+    if constexpr (EX) {
+        if (live) {
+            // first list entry at or past this part's first row (entries after the last id are -1)
+            xl = a.excl + tok * a.ld_e;
+            const int lo = vt0 * 128;
+            int p = 0, n = a.E;
+            while (n > 0) {
+                const int half = n >> 1, v = xl[p + half];
+                if (v >= 0 && v < lo) { p += half + 1; n -= half + 1; } else n = half;
+            }
+            const int v0 = p < a.E ? xl[p] : -1, v1 = p + 1 < a.E ? xl[p + 1] : -1;
+            xn = v0 < 0 ? 0x7fffffff : v0;
+            xq = v1 < 0 ? 0x7fffffff : v1;
+            xp = p + 1;
+        }
+    }
+    // EX: NaN into the lane's excluded entries of the half-tile (vt, vhe) whose MFMA chain has just completed in acc
+    auto excl = [&](f32x16 (&acc)[2], int vt, int vhe) __attribute__((always_inline)) {
+        if constexpr (EX) {
+            const int base = vt * 128 + vhe * 64, hi = base + 64;
+            if (__any(xn < hi)) {
+                unsigned m = 0;
+                while (xn < hi) {
+                    const int o = xn - base;          // negative: an id of the half-tile this wave does not score (NH = 1)
+                    if (o >= 0 && ((o >> 2) & 1) == hf) m |= 1u << ((o >> 5) * 16 + (o & 3) + 4 * ((o >> 3) & 3));
+                    xn = xq;
+                    ++xp;
+                    const int v = xp < a.E ? xl[xp] : -1;
+                    xq = v < 0 ? 0x7fffffff : v;
+                }
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int t = 0; t < 16; ++t)
+                        if ((m >> (rt * 16 + t)) & 1u) acc[rt][t] = __builtin_nanf("");
+            }
+        }
+    };
+
+    float breg = 0.f;
+    auto fetch = [&](int vt, int buf) {
+        VTile<KD>::template dma<512>(a.wt, a.ld_w, (int64_t)vt * 128, vt < vt1 ? a.V : 0, smem + buf * TILE_B, tid);
+        if (tid < 128) {
+            const int v = vt * 128 + tid;
+            breg = (vt < vt1 && v < a.V) ? (a.bias ? a.bias[v] : 0.f) : -INFINITY;   // rows past V: score = -inf
+        }
+    };
+    fetch(vt0, 0);
+    if (tid < 128) sBias[tid] = breg;
+    VCE_DMA_WAIT();
+    __syncthreads();
+
+    // One half-tile (64 vocabulary rows x the wave's 32 tokens) = 16 MFMAs into acc, then ~4 VALU instructions per entry
+    // on the result.  A VALU wave-instruction holds the SIMD's issue port for 4 cycles, an MFMA for 8 of its 32: run one
+    // after the other the two phases add up (measured: matrix pipe 36 % busy, VALU issue 43 %, sum 79 % of the kernel's
+    // cycles); interleaved -- the MFMA chain of one half-tile issued between the VALU instructions of the previous one --
+    // they overlap.  So the loop is software-pipelined by half a tile: `scores` of half-tile i runs inside the instruction
+    // stream of `chain` of half-tile i + 1 (sched_group_barrier pins the interleave), on two accumulator sets.
+    // one entry of a half-tile's scores: x = accumulator + bias (the bias last, as the materialising GEMM adds it; rows past
+    // V: -inf); RANK: count it if it beats x_y, note an equal one; CLASSMAX: the running maximum of its accumulator slot;
+    // COLLECT: note one that reaches tau
+    bool hot = false;
+    auto entry = [&](f32x16 (&acc)[2], int rt, int t, float bj) __attribute__((always_inline)) {
+        const float x = acc[rt][t] + bj;
+        acc[rt][t] = x;
+        if (OP == SCAN_RANK) {
+            n_before += x > ref ? 1u : 0u;
+            hot |= x == ref;
+        } else if (OP == SCAN_CLASSMAX) {
+            cm[t] = fmaxf(cm[t], x);
+        } else {
+            hot |= x >= ref;
+        }
+    };
+    // The 16 MFMAs of a half-tile's chain into accN, and -- WITH = true -- between them the scores of the half-tile before
+    // it (accP: 32 entries per lane, two per MFMA).  sched_barrier(0) after every MFMA's group pins the interleave (left to
+    // itself, or to sched_group_barrier, the compiler issues the sixteen MFMAs first and the VALU after them).
+    auto chain = [&](auto WITH, f32x16 (&accN)[2], const char *w, f32x16 (&accP)[2], const float *bs, int vhe) __attribute__((always_inline)) {
+        constexpr bool with = decltype(WITH)::value;
+        bf16x8 wfq[NKS];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int t = 0; t < 16; ++t) accN[rt][t] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) wfq[ks] = *reinterpret_cast<const bf16x8 *>(w + foff[ks]);
+        hot = false;
+        // the eight bias quads of the previous half-tile are requested up front, with the first fragments: a quad requested
+        // where it is used parks the wave for a full LDS round trip (~130 cycles) sixteen times per tile
+        f32x4 bq[8];
+        if (with) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(bs + vhe * 64 + (q >> 2) * 32 + 8 * (q & 3) + 4 * hf);
+        }
+#pragma unroll
+        for (int i = 0; i < 2 * NKS; ++i) {
+            const int rt = i / NKS, ks = i % NKS;
+            __builtin_amdgcn_sched_barrier(0);
+            accN[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfq[ks], hfr[ks], accN[rt], 0, 0, 0);
+            if (rt == 0) wfq[ks] = *reinterpret_cast<const bf16x8 *>(w + 32 * STR + foff[ks]);
+            if (with) {
+                // entries 2 i, 2 i + 1 of the previous half-tile (NKS = 8: all 32; NKS = 4: the rest follows the chain)
+#pragma unroll
+                for (int e = 2 * i; e < 2 * i + 2; ++e) entry(accP, e >> 4, e & 15, bq[e >> 2][e & 3]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (with && NKS < 8) {
+#pragma unroll
+            for (int e = 4 * NKS; e < 32; ++e) entry(accP, e >> 4, e & 15, bq[e >> 2][e & 3]);
+        }
+    };
+    // the scores of a half-tile on their own (NH = 1; the last half-tile of NH = 2)
+    auto scores = [&](f32x16 (&acc)[2], const float *bs, int vhe) __attribute__((always_inline)) {
+        hot = false;
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int tq = 0; tq < 4; ++tq) {
+                const f32x4 b4 = *reinterpret_cast<const f32x4 *>(bs + vhe * 64 + rt * 32 + 8 * tq + 4 * hf);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) entry(acc, rt, 4 * tq + k, b4[k]);
+            }
+    };
+    auto rare = [&](f32x16 (&acc)[2], int vt, int vhe) __attribute__((always_inline)) {       // the half-tile that holds the label / a candidate
+        const int row0 = vt * 128 + vhe * 64 + 4 * hf;
+        int slot = 0;
+        if (OP == SCAN_COLLECT) {          // the lane's candidates of this half-tile take consecutive slots: one atomic
+            int n = 0;
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int t = 0; t < 16; ++t)
+                    n += (acc[rt][t] >= ref && row0 + rt * 32 + (t & 3) + 8 * (t >> 2) < a.V) ? 1 : 0;
+            if (n) slot = atomicAdd(a.cnt + tok, n);
+        }
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const int j = row0 + rt * 32 + (t & 3) + 8 * (t >> 2);
+                const float x = acc[rt][t];
+                if (OP == SCAN_RANK) {
+                    n_before += (x == ref && j < y) ? 1u : 0u;        // ties: the lower index ranks first
+                } else if (x >= ref && j < a.V) {
+                    if (slot < VCE_CAND) {
+                        a.cand_v[tok * VCE_CAND + slot] = x;
+                        a.cand_i[tok * VCE_CAND + slot] = j;
+                    }
+                    ++slot;
+                }
+            }
+    };
+    f32x16 accA[2], accB[2];
+    int vt_prev = vt0;
+    bool have_prev = false;
+    int bcur = 0, bprev = 2;           // bias ring slots of this tile and of the previous one; the next one's goes to the third
+#ifdef VCE_SCAN_STAMPS
+    unsigned long long st_[6] = {0, 0, 0, 0, 0, 0}, t0_ = __builtin_amdgcn_s_memtime();
+#endif
+    constexpr std::integral_constant<bool, true> YES{};
+    constexpr std::integral_constant<bool, false> NO{};
+    auto tile = [&](auto BUF, int vt) __attribute__((always_inline)) {
+        constexpr int buf = decltype(BUF)::value;
+        VCE_STAMP(5);
+        fetch(vt + 1, buf ^ 1);
+        VCE_STAMP(0);
+        const char *w = smem + buf * TILE_B;
+        const int bnext = 3 - bcur - bprev;
+        if (NH == 2) {
+            // accA <- half 0 of this tile, beside the scores of the previous tile's half 1 (accB)
+            if (have_prev) {
+                chain(YES, accA, w, accB, sBias + bprev * 128, 1);
+                if (OP != SCAN_CLASSMAX && __any(hot)) rare(accB, vt_prev, 1);
+            } else {
+                chain(NO, accA, w, accB, sBias, 0);
+            }
+            excl(accA, vt, 0);
+            VCE_STAMP(1);
+            // accB <- half 1, beside the scores of half 0
+            chain(YES, accB, w + 64 * STR, accA, sBias + bcur * 128, 0);
+            if (OP != SCAN_CLASSMAX && __any(hot)) rare(accA, vt, 0);
+            excl(accB, vt, 1);
+            VCE_STAMP(2);
+            have_prev = true;
+            vt_prev = vt;
+        } else {
+            chain(NO, accA, w, accB, sBias, 0);
+            excl(accA, vt, vh);
+            scores(accA, sBias + bcur * 128, vh);
+            if (OP != SCAN_CLASSMAX && __any(hot)) rare(accA, vt, vh);
+        }
+        if (tid < 128) sBias[bnext * 128 + tid] = breg;
+        bprev = bcur;
+        bcur = bnext;
+        VCE_DMA_WAIT();
+        VCE_STAMP(3);
+        B4C_LDS_BARRIER();
+        VCE_STAMP(4);
+    };
+    for (int vt = vt0; vt < vt1; vt += 2) {
+        tile(std::integral_constant<int, 0>{}, vt);
+        if (vt + 1 < vt1) tile(std::integral_constant<int, 1>{}, vt + 1);
+    }
+    if (NH == 2 && have_prev) {          // the last half-tile's scores
+        scores(accB, sBias + bprev * 128, 1);
+        if (OP != SCAN_CLASSMAX && __any(hot)) rare(accB, vt_prev, 1);
+    }
+#ifdef VCE_SCAN_STAMPS
+    if (lane == 0 && blockIdx.x < 2048)
+        for (int k = 0; k < 6; ++k) g_vce_stamps[(blockIdx.x * 8 + wave) * 6 + k] = st_[k];
+#endif
+    if (!live) return;
+    if (OP == SCAN_RANK) {
+        if (n_before) atomicAdd(a.rank + tok, (int)n_before);          // integer adds: any order gives the same count
+    } else if (OP == SCAN_CLASSMAX) {
+        // sub-list index: (part, half of the tile, lane half) for NH = 1; (part, lane half) for NH = 2 (a.nsub_per_part of them)
+        const int sub = NH == 2 ? part * 2 + hf : part * 4 + vh * 2 + hf;
+        float *o = a.cm + ((int64_t)sub * a.R + tok) * 16;
+#pragma unroll
+        for (int tq = 0; tq < 4; ++tq) *reinterpret_cast<f32x4 *>(o + 4 * tq) = (f32x4){cm[4 * tq], cm[4 * tq + 1], cm[4 * tq + 2], cm[4 * tq + 3]};
+    }
 }
 
 // tau[row] = k-th largest of the row's nsub * 16 class maxima (one wave per row; k rounds of "take the maximum out")
@@ -1524,22 +1762,20 @@ static void vce_scan_geometry(VceScanArgs &a, int nh) {
     a.ntt = (int)ceil_div64(a.R, 128 * nh);
     a.parts = vce_pick_split(a.ntt, (a.V + 127) / 128, 0.005);
 }
-template <int KD, int OP>
-static void vce_scan_launch(VceScanArgs a, int nh, hipStream_t st) {
+template <int KD, int OP, bool EX>
+static void vce_scan_launch(const VceScanExArgs &a, int nh, hipStream_t st) {
     const size_t lds = 2 * (size_t)VTile<KD>::BYTES + 3 * 128 * 4;
     static thread_local bool done = false;
-    if (!done) { vce_allow_lds(vce_scan_kernel<KD, OP, 1>, lds); vce_allow_lds(vce_scan_kernel<KD, OP, 2>, lds); done = true; }
-    if (nh == 2) vce_scan_kernel<KD, OP, 2><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(a);
-    else vce_scan_kernel<KD, OP, 1><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(a);
+    if (!done) { vce_allow_lds(vce_scan_kernel<KD, OP, 1, EX>, lds); vce_allow_lds(vce_scan_kernel<KD, OP, 2, EX>, lds); done = true; }
+    const std::conditional_t<EX, VceScanExArgs, VceScanArgs> ka = a;          // EX = false: the block without the list fields
+    if (nh == 2) vce_scan_kernel<KD, OP, 2, EX><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(ka);
+    else vce_scan_kernel<KD, OP, 1, EX><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(ka);
 }
-
-template <int KD, int OP>
-static void vce_scan_excl_launch(VceScanExArgs a, int nh, hipStream_t st) {
-    const size_t lds = 2 * (size_t)VTile<KD>::BYTES + 3 * 128 * 4;
-    static thread_local bool done = false;
-    if (!done) { vce_allow_lds(vce_scan_excl_kernel<KD, OP, 1>, lds); vce_allow_lds(vce_scan_excl_kernel<KD, OP, 2>, lds); done = true; }
-    if (nh == 2) vce_scan_excl_kernel<KD, OP, 2><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(a);
-    else vce_scan_excl_kernel<KD, OP, 1><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(a);
+// one sweep: the kernels without exclusions when no list is given (E == 0)
+template <int OP>
+static void vce_scan(const VceScanExArgs &a, int K, int nh, hipStream_t st) {
+    if (K == 128) { if (a.E) vce_scan_launch<128, OP, true>(a, nh, st); else vce_scan_launch<128, OP, false>(a, nh, st); }
+    else { if (a.E) vce_scan_launch<64, OP, true>(a, nh, st); else vce_scan_launch<64, OP, false>(a, nh, st); }
 }
 
 static int vce_excl_check(const int32_t *excl, int ld_e, int E, const char *who) {
@@ -1548,27 +1784,47 @@ static int vce_excl_check(const int32_t *excl, int ld_e, int E, const char *who)
     return B4C_OK;
 }
 
-extern "C" int b4c_vocab_rank(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *labels, int32_t *rank,
-                              void *workspace, int64_t workspace_bytes, int64_t R, int V, int K, void *stream) {
-    if (int rc = vce_scan_check(h, ld_h, wt, ld_w, workspace, workspace_bytes, R, V, K, "vocab_rank")) return rc;
-    B4C_REQUIRE(labels && rank, "vocab_rank: null pointer");
+// the argument block both entry-point pairs start from: operands, shape, geometry, exclusion list (E == 0: none)
+static VceScanExArgs vce_scan_args(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, int64_t R, int V, int nh,
+                                   const int32_t *excl, int ld_e, int E) {
+    VceScanExArgs a = {};
+    a.h = (const bf16_t *)h; a.wt = (const bf16_t *)wt; a.bias = bias;
+    a.ld_h = ld_h; a.ld_w = ld_w; a.R = R; a.V = V;
+    a.excl = excl; a.ld_e = ld_e; a.E = E;
+    vce_scan_geometry(a, nh);
+    return a;
+}
+
+// b4c_vocab_rank (excl = NULL, E = 0) and b4c_vocab_rank_excl; `who` names the entry point in messages
+static int vce_rank_run(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *labels, int32_t *rank,
+                        void *workspace, int64_t workspace_bytes, int64_t R, int V, int K, const int32_t *excl, int ld_e, int E,
+                        void *stream, const char *who) {
+    if (int rc = vce_excl_check(excl, ld_e, E, who)) return rc;
+    if (int rc = vce_scan_check(h, ld_h, wt, ld_w, workspace, workspace_bytes, R, V, K, who)) return rc;
+    B4C_REQUIRE(labels && rank, "%s: null pointer", who);
     if (R == 0) return B4C_OK;
     hipStream_t st = (hipStream_t)stream;
-    VceScanArgs a = {};
-    a.h = (const bf16_t *)h; a.wt = (const bf16_t *)wt; a.bias = bias; a.labels = labels; a.rank = rank;
-    a.ld_h = ld_h; a.ld_w = ld_w; a.R = R; a.V = V;
     const int nh = vce_scan_nh(R);
-    vce_scan_geometry(a, nh);
+    VceScanExArgs a = vce_scan_args(h, ld_h, wt, ld_w, bias, R, V, nh, excl, ld_e, E);
+    a.labels = labels; a.rank = rank;
     float *xy = (float *)workspace;
     a.xy = xy;
-    if (K == 128) {
-        vce_label_logit_kernel<128><<<(unsigned)ceil_div64(R, 32), 64, 0, st>>>(a, xy, rank);
-        vce_scan_launch<128, SCAN_RANK>(a, nh, st);
-    } else {
-        vce_label_logit_kernel<64><<<(unsigned)ceil_div64(R, 32), 64, 0, st>>>(a, xy, rank);
-        vce_scan_launch<64, SCAN_RANK>(a, nh, st);
-    }
-    return b4c_check_launch("vocab_rank");
+    if (K == 128) vce_label_logit_kernel<128><<<(unsigned)ceil_div64(R, 32), 64, 0, st>>>(a, xy, rank);
+    else vce_label_logit_kernel<64><<<(unsigned)ceil_div64(R, 32), 64, 0, st>>>(a, xy, rank);
+    vce_scan<SCAN_RANK>(a, K, nh, st);
+    return b4c_check_launch(who);
+}
+
+extern "C" int b4c_vocab_rank(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *labels, int32_t *rank,
+                              void *workspace, int64_t workspace_bytes, int64_t R, int V, int K, void *stream) {
+    return vce_rank_run(h, ld_h, wt, ld_w, bias, labels, rank, workspace, workspace_bytes, R, V, K, nullptr, 0, 0, stream, "vocab_rank");
+}
+
+extern "C" int b4c_vocab_rank_excl(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *labels,
+                                   int32_t *rank, void *workspace, int64_t workspace_bytes, int64_t R, int V, int K,
+                                   const int32_t *excl, int ld_e, int E, void *stream) {
+    return vce_rank_run(h, ld_h, wt, ld_w, bias, labels, rank, workspace, workspace_bytes, R, V, K, excl, ld_e, E, stream,
+                        "vocab_rank_excl");
 }
 
 extern "C" int b4c_rank_metrics(const int32_t *rank, int64_t R, int k, float *hit, float *ndcg, void *stream) {
@@ -1578,20 +1834,19 @@ extern "C" int b4c_rank_metrics(const int32_t *rank, int64_t R, int k, float *hi
     return b4c_check_launch("rank_metrics");
 }
 
-extern "C" int b4c_vocab_topk(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, int k, int32_t *idx,
-                              const int32_t *labels, float *hit, float *ndcg, int32_t *overflow, void *workspace,
-                              int64_t workspace_bytes, int64_t R, int V, int K, void *stream) {
-    if (int rc = vce_scan_check(h, ld_h, wt, ld_w, workspace, workspace_bytes, R, V, K, "vocab_topk")) return rc;
-    B4C_REQUIRE(idx && overflow && k >= 1 && k <= B4C_MAX_TOPK, "vocab_topk: k = %d (1 .. %d)", k, B4C_MAX_TOPK);
-    B4C_REQUIRE(!labels || (hit && ndcg), "vocab_topk: labels need hit and ndcg");
+// b4c_vocab_topk (excl = NULL, E = 0) and b4c_vocab_topk_excl
+static int vce_topk_run(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, int k, int32_t *idx, const int32_t *labels,
+                        float *hit, float *ndcg, int32_t *overflow, void *workspace, int64_t workspace_bytes, int64_t R, int V, int K,
+                        const int32_t *excl, int ld_e, int E, void *stream, const char *who) {
+    if (int rc = vce_excl_check(excl, ld_e, E, who)) return rc;
+    if (int rc = vce_scan_check(h, ld_h, wt, ld_w, workspace, workspace_bytes, R, V, K, who)) return rc;
+    B4C_REQUIRE(idx && overflow && k >= 1 && k <= B4C_MAX_TOPK, "%s: k = %d (1 .. %d)", who, k, B4C_MAX_TOPK);
+    B4C_REQUIRE(!labels || (hit && ndcg), "%s: labels need hit and ndcg", who);
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(overflow, 0, 4, st);
     if (R == 0) return B4C_OK;
-    VceScanArgs a = {};
-    a.h = (const bf16_t *)h; a.wt = (const bf16_t *)wt; a.bias = bias;
-    a.ld_h = ld_h; a.ld_w = ld_w; a.R = R; a.V = V;
     const int nh = vce_scan_nh(R);
-    vce_scan_geometry(a, nh);
+    VceScanExArgs a = vce_scan_args(h, ld_h, wt, ld_w, bias, R, V, nh, excl, ld_e, E);
     char *ws = (char *)workspace;
     a.cm = (float *)ws;                         ws += (size_t)R * 32 * 16 * 4;
     float *tau = (float *)ws;                   ws += (size_t)R * 4;
@@ -1599,11 +1854,26 @@ extern "C" int b4c_vocab_topk(const void *h, int ld_h, const void *wt, int ld_w,
     a.cand_v = (float *)ws;                     ws += (size_t)R * VCE_CAND * 4;
     a.cand_i = (int32_t *)ws;
     a.tau = tau;
-    if (K == 128) vce_scan_launch<128, SCAN_CLASSMAX>(a, nh, st); else vce_scan_launch<64, SCAN_CLASSMAX>(a, nh, st);
+    vce_scan<SCAN_CLASSMAX>(a, K, nh, st);
     vce_tau_kernel<<<(unsigned)ceil_div64(R, 4), 256, 0, st>>>(a.cm, a.parts * (nh == 2 ? 2 : 4), R, k, tau, a.cnt);
-    if (K == 128) vce_scan_launch<128, SCAN_COLLECT>(a, nh, st); else vce_scan_launch<64, SCAN_COLLECT>(a, nh, st);
+    vce_scan<SCAN_COLLECT>(a, K, nh, st);
     vce_select_kernel<<<(unsigned)ceil_div64(R, 4), 256, 0, st>>>(a.cand_v, a.cand_i, a.cnt, R, V, k, idx, labels, hit, ndcg, overflow);
-    return b4c_check_launch("vocab_topk");
+    return b4c_check_launch(who);
+}
+
+extern "C" int b4c_vocab_topk(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, int k, int32_t *idx,
+                              const int32_t *labels, float *hit, float *ndcg, int32_t *overflow, void *workspace,
+                              int64_t workspace_bytes, int64_t R, int V, int K, void *stream) {
+    return vce_topk_run(h, ld_h, wt, ld_w, bias, k, idx, labels, hit, ndcg, overflow, workspace, workspace_bytes, R, V, K, nullptr, 0, 0,
+                        stream, "vocab_topk");
+}
+
+extern "C" int b4c_vocab_topk_excl(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, int k, int32_t *idx,
+                                   const int32_t *labels, float *hit, float *ndcg, int32_t *overflow, void *workspace,
+                                   int64_t workspace_bytes, int64_t R, int V, int K, const int32_t *excl, int ld_e, int E,
+                                   void *stream) {
+    return vce_topk_run(h, ld_h, wt, ld_w, bias, k, idx, labels, hit, ndcg, overflow, workspace, workspace_bytes, R, V, K, excl, ld_e, E,
+                        stream, "vocab_topk_excl");
 }
 
 // ---- exclusions: the canonical per-row list the *_excl entry points take --------------------------------------------------
@@ -1656,64 +1926,4 @@ extern "C" int b4c_exclusions_prep(const int32_t *ex_in, int ld_in, int64_t R, i
     while (n < E) n <<= 1;
     vce_excl_prep_kernel<<<(unsigned)R, n, 0, (hipStream_t)stream>>>(ex_in, ld_in, E, V, labels, ex_out);
     return b4c_check_launch("exclusions_prep");
-}
-
-extern "C" int b4c_vocab_rank_excl(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, const int32_t *labels,
-                                   int32_t *rank, void *workspace, int64_t workspace_bytes, int64_t R, int V, int K,
-                                   const int32_t *excl, int ld_e, int E, void *stream) {
-    if (int rc = vce_excl_check(excl, ld_e, E, "vocab_rank_excl")) return rc;
-    if (E == 0) return b4c_vocab_rank(h, ld_h, wt, ld_w, bias, labels, rank, workspace, workspace_bytes, R, V, K, stream);
-    if (int rc = vce_scan_check(h, ld_h, wt, ld_w, workspace, workspace_bytes, R, V, K, "vocab_rank_excl")) return rc;
-    B4C_REQUIRE(labels && rank, "vocab_rank_excl: null pointer");
-    if (R == 0) return B4C_OK;
-    hipStream_t st = (hipStream_t)stream;
-    VceScanExArgs a = {};
-    a.h = (const bf16_t *)h; a.wt = (const bf16_t *)wt; a.bias = bias; a.labels = labels; a.rank = rank;
-    a.ld_h = ld_h; a.ld_w = ld_w; a.R = R; a.V = V;
-    a.excl = excl; a.ld_e = ld_e; a.E = E;
-    const int nh = vce_scan_nh(R);
-    vce_scan_geometry(a, nh);
-    float *xy = (float *)workspace;
-    a.xy = xy;
-    if (K == 128) {
-        vce_label_logit_kernel<128><<<(unsigned)ceil_div64(R, 32), 64, 0, st>>>(a, xy, rank);
-        vce_scan_excl_launch<128, SCAN_RANK>(a, nh, st);
-    } else {
-        vce_label_logit_kernel<64><<<(unsigned)ceil_div64(R, 32), 64, 0, st>>>(a, xy, rank);
-        vce_scan_excl_launch<64, SCAN_RANK>(a, nh, st);
-    }
-    return b4c_check_launch("vocab_rank_excl");
-}
-
-extern "C" int b4c_vocab_topk_excl(const void *h, int ld_h, const void *wt, int ld_w, const float *bias, int k, int32_t *idx,
-                                   const int32_t *labels, float *hit, float *ndcg, int32_t *overflow, void *workspace,
-                                   int64_t workspace_bytes, int64_t R, int V, int K, const int32_t *excl, int ld_e, int E,
-                                   void *stream) {
-    if (int rc = vce_excl_check(excl, ld_e, E, "vocab_topk_excl")) return rc;
-    if (E == 0)
-        return b4c_vocab_topk(h, ld_h, wt, ld_w, bias, k, idx, labels, hit, ndcg, overflow, workspace, workspace_bytes, R, V, K, stream);
-    if (int rc = vce_scan_check(h, ld_h, wt, ld_w, workspace, workspace_bytes, R, V, K, "vocab_topk_excl")) return rc;
-    B4C_REQUIRE(idx && overflow && k >= 1 && k <= B4C_MAX_TOPK, "vocab_topk_excl: k = %d (1 .. %d)", k, B4C_MAX_TOPK);
-    B4C_REQUIRE(!labels || (hit && ndcg), "vocab_topk_excl: labels need hit and ndcg");
-    hipStream_t st = (hipStream_t)stream;
-    (void)hipMemsetAsync(overflow, 0, 4, st);
-    if (R == 0) return B4C_OK;
-    VceScanExArgs a = {};
-    a.h = (const bf16_t *)h; a.wt = (const bf16_t *)wt; a.bias = bias;
-    a.ld_h = ld_h; a.ld_w = ld_w; a.R = R; a.V = V;
-    a.excl = excl; a.ld_e = ld_e; a.E = E;
-    const int nh = vce_scan_nh(R);
-    vce_scan_geometry(a, nh);
-    char *ws = (char *)workspace;
-    a.cm = (float *)ws;                         ws += (size_t)R * 32 * 16 * 4;
-    float *tau = (float *)ws;                   ws += (size_t)R * 4;
-    a.cnt = (int32_t *)ws;                      ws += (size_t)R * 4;
-    a.cand_v = (float *)ws;                     ws += (size_t)R * VCE_CAND * 4;
-    a.cand_i = (int32_t *)ws;
-    a.tau = tau;
-    if (K == 128) vce_scan_excl_launch<128, SCAN_CLASSMAX>(a, nh, st); else vce_scan_excl_launch<64, SCAN_CLASSMAX>(a, nh, st);
-    vce_tau_kernel<<<(unsigned)ceil_div64(R, 4), 256, 0, st>>>(a.cm, a.parts * (nh == 2 ? 2 : 4), R, k, tau, a.cnt);
-    if (K == 128) vce_scan_excl_launch<128, SCAN_COLLECT>(a, nh, st); else vce_scan_excl_launch<64, SCAN_COLLECT>(a, nh, st);
-    vce_select_kernel<<<(unsigned)ceil_div64(R, 4), 256, 0, st>>>(a.cand_v, a.cand_i, a.cnt, R, V, k, idx, labels, hit, ndcg, overflow);
-    return b4c_check_launch("vocab_topk_excl");
 }

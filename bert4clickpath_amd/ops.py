@@ -1158,6 +1158,14 @@ def _excl_args(exclude, R, who):
     return _p(exclude), max(exclude.stride(0), exclude.shape[1]), exclude.shape[1]
 
 
+def _excl_entry(who, exclude, R):
+    """(name, trailing arguments) of the entry point `who` serves a call through: `who` itself and none without a list, the
+    _excl one and the list's (pointer, ld, E) with one; the name is also the label of the call's status check"""
+    if exclude is None:
+        return who, ()
+    return who + '_excl', _excl_args(exclude, R, who)
+
+
 def vocab_rank(h, wt, bias, labels_i32, V, exclude=None):
     """rank [R] int32 of the label among the V scores h wt^T + bias (items ranked before it; ties -> lower index first;
     negative: no valid label).  The scores never exist in memory.  exclude (ops.exclusions): items of a row's list do not
@@ -1165,19 +1173,13 @@ def vocab_rank(h, wt, bias, labels_i32, V, exclude=None):
     _cuda(h)
     R, K = h.shape
     rank = torch.empty(R, dtype=torch.int32, device=h.device)
-    if exclude is not None:
-        ex, ld_e, E = _excl_args(exclude, R, 'vocab_rank')
+    name, ex = _excl_entry('vocab_rank', exclude, R)
     if R == 0:
         return rank
     ws = _rank_workspace(h, R, V, K)
-    if exclude is not None:
-        with _record('vocab_rank', R * K * 2 + V * K * 2, 2 * R * V * K):
-            L.check(L.lib().b4c_vocab_rank_excl(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), _p(labels_i32), _p(rank),
-                                                ws.data_ptr(), ws.numel(), R, V, K, ex, ld_e, E, _st()), 'vocab_rank_excl')
-        return rank
     with _record('vocab_rank', R * K * 2 + V * K * 2, 2 * R * V * K):
-        L.check(L.lib().b4c_vocab_rank(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), _p(labels_i32), _p(rank), ws.data_ptr(),
-                                       ws.numel(), R, V, K, _st()), 'vocab_rank')
+        L.check(getattr(L.lib(), 'b4c_' + name)(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), _p(labels_i32), _p(rank),
+                                                ws.data_ptr(), ws.numel(), R, V, K, *ex, _st()), name)
     return rank
 
 
@@ -1198,8 +1200,7 @@ def vocab_topk(h, wt, bias, V, k, labels_i32=None, exclude=None):
     (b4c_vocab_topk_excl; ids -1 past the items that remain)."""
     _cuda(h)
     R, K = h.shape
-    if exclude is not None:
-        ex, ld_e, E = _excl_args(exclude, R, 'vocab_topk')
+    name, ex = _excl_entry('vocab_topk', exclude, R)
     idx = torch.empty(R, k, dtype=torch.int32, device=h.device)
     hit = torch.empty(R, dtype=torch.float32, device=h.device) if labels_i32 is not None else None
     ndcg = torch.empty(R, dtype=torch.float32, device=h.device) if labels_i32 is not None else None
@@ -1207,15 +1208,10 @@ def vocab_topk(h, wt, bias, V, k, labels_i32=None, exclude=None):
     if R == 0:
         return idx, hit, ndcg, overflow.zero_()
     ws = _rank_workspace(h, R, V, K)
-    if exclude is not None:
-        with _record('vocab_topk', 2 * (R * K * 2 + V * K * 2), 4 * R * V * K):
-            L.check(L.lib().b4c_vocab_topk_excl(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), k, _p(idx), _p(labels_i32),
-                                                _p(hit), _p(ndcg), _p(overflow), ws.data_ptr(), ws.numel(), R, V, K, ex, ld_e, E,
-                                                _st()), 'vocab_topk_excl')
-        return idx, hit, ndcg, overflow
     with _record('vocab_topk', 2 * (R * K * 2 + V * K * 2), 4 * R * V * K):
-        L.check(L.lib().b4c_vocab_topk(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), k, _p(idx), _p(labels_i32), _p(hit),
-                                       _p(ndcg), _p(overflow), ws.data_ptr(), ws.numel(), R, V, K, _st()), 'vocab_topk')
+        L.check(getattr(L.lib(), 'b4c_' + name)(_p(h), h.stride(0), _p(wt), wt.stride(0), _p(bias), k, _p(idx), _p(labels_i32),
+                                                _p(hit), _p(ndcg), _p(overflow), ws.data_ptr(), ws.numel(), R, V, K, *ex, _st()),
+                name)
     return idx, hit, ndcg, overflow
 
 
@@ -1259,24 +1255,18 @@ def topk_rows(scores, V, k, labels_i32=None, exclude=None):
     listed items are left out (b4c_topk_rows_excl); `scores` is only read."""
     _cuda(scores)
     R, ld = scores.shape[0], scores.stride(0)
-    if exclude is not None:
-        ex, ld_e, E = _excl_args(exclude, R, 'topk_rows')
+    name, ex = _excl_entry('topk_rows', exclude, R)
     idx = torch.empty(R, k, dtype=torch.int32, device=scores.device)
     hit = torch.empty(R, dtype=torch.float32, device=scores.device) if labels_i32 is not None else None
     ndcg = torch.empty(R, dtype=torch.float32, device=scores.device) if labels_i32 is not None else None
     if R == 0:
         return idx, hit, ndcg
     redo = torch.empty(R, dtype=torch.int32, device=scores.device) if topk_threshold else None
-    if exclude is not None:
-        with _record('topk_rows', R * ld * scores.element_size()):
-            L.check(L.lib().b4c_topk_rows_excl(_p(scores), ld, R, V, k, _p(idx), _p(labels_i32), _p(hit), _p(ndcg), _p(redo),
-                                               dt_code(scores.dtype), ex, ld_e, E, _st()), 'topk_rows_excl')
-        return idx, hit, ndcg
+    fn = L.lib().b4c_topk_rows_excl if ex else L.lib().b4c_topk_rows_ws
     with _record('topk_rows', R * ld * scores.element_size()):
-        L.check(L.lib().b4c_topk_rows_ws(_p(scores), ld, R, V, k, _p(idx), _p(labels_i32), _p(hit), _p(ndcg), _p(redo),
-                                         dt_code(scores.dtype), _st()), 'topk_rows')
+        L.check(fn(_p(scores), ld, R, V, k, _p(idx), _p(labels_i32), _p(hit), _p(ndcg), _p(redo), dt_code(scores.dtype), *ex, _st()),
+                name)
     return idx, hit, ndcg
-
 
 
 # ---- candidate lists (include/b4c.h "candidate lists"): sampled negatives, scores / rank / top-k of a per-row list of items ----
