@@ -98,11 +98,14 @@ class ClickstreamTransformer(nn.Module):
     def __init__(self, sequential_input_config, feature_vocabs, embedding_dims, head_unit, segment_to_head=None,
                  value_to_head=None, num_encoder_layers=1, num_attention_heads=1, dropout_rate=0.1,
                  compute_dtype=torch.float32, feature_combine='concat', encoder_ff_dim=100, ffn_activation='relu',
-                 position_encoding='sinusoidal', max_positions=None, **kwargs):
+                 position_encoding='sinusoidal', max_positions=None, attention_dropout_rate=0.0, **kwargs):
         super().__init__()
         # ffn_activation / position_encoding / max_positions: the BERT4Rec paper's GELU feed-forward and learned positions
         # (extensions, validated by transformer.Transformer); the defaults are the reference's ReLU and fixed sinusoid
         self.ffn_activation, self.position_encoding = ffn_activation, position_encoding
+        # attention_dropout_rate: dropout on the attention probabilities in training (BERT's attention_probs_dropout_prob, 0.2 in
+        # the published BERT4Rec configurations); the reference's attention has none, the default 0 is the reference's
+        self.attention_dropout_rate = float(attention_dropout_rate)
         # encoder_ff_dim: the reference hard-codes the FFN width 100 in this constructor (:225) and takes it as an argument of the
         # inner API (transformer.Transformer); 4 * d_model is the BERT4Rec paper's width.  Default = the reference's.
         self.encoder_ff_dim = int(encoder_ff_dim)
@@ -126,7 +129,8 @@ class ClickstreamTransformer(nn.Module):
             embedding_dims=self.embedding_dims, num_layers=num_encoder_layers,
             num_attention_heads=num_attention_heads, encoder_ff_dim=self.encoder_ff_dim,   # 100: hard-coded in the reference (:225)
             dropout_rate=dropout_rate, compute_dtype=compute_dtype, feature_combine=feature_combine,
-            ffn_activation=ffn_activation, position_encoding=position_encoding, max_positions=max_positions)
+            ffn_activation=ffn_activation, position_encoding=position_encoding, max_positions=max_positions,
+            attention_dropout_rate=attention_dropout_rate)
         self.max_positions = self.transformer.max_positions
         if hasattr(self.head, 'tie') and getattr(self.head, '_table', None) is None:
             # tied-weight head: project back onto the FIRST embedded feature's table (the items)
@@ -152,7 +156,8 @@ class ClickstreamTransformer(nn.Module):
                 **({'encoder_ff_dim': self.encoder_ff_dim} if self.encoder_ff_dim != 100 else {}),
                 **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
                 **({'position_encoding': 'learned', 'max_positions': self.max_positions}
-                   if self.position_encoding == 'learned' else {})}
+                   if self.position_encoding == 'learned' else {}),
+                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {})}
 
     @staticmethod
     def _create_lookup_tables(vocabularies, tokens_to_prepend=None):
@@ -288,7 +293,7 @@ class ClickstreamTransformer(nn.Module):
         feats = {k: v for k, v in inputs.items() if k != 'instance_id'}
         pack = self._use_packed(feats, packed, n_real_tokens)
         if self.segment_to_head is None and self.value_to_head is not None and ops.mq_last_layer and \
-                self.transformer.encoder.rows_supported(None):
+                self.transformer.encoder.rows_supported(None, training):
             # the head reads the rows at the value_to_head positions only: the last encoder layer is evaluated for those
             # rows alone (padded to M per sequence; a padding slot is a query row made of zeros whose output nobody reads)
             def positions(ids_first, raw_first):
@@ -368,7 +373,8 @@ class ClickstreamTransformer(nn.Module):
 
         # The positions depend on the ids alone.  With them in hand BEFORE the encoder runs, its last layer is evaluated
         # for those rows only (ops.MQAttnBlockFn): nothing else of that layer's output is ever read on this path.
-        mq = flat_idx is None and ops.mq_last_layer and self.transformer.encoder.rows_supported(None)
+        # (not in training with attention dropout: the masked-query kernels have none, the full layer runs and its rows are gathered)
+        mq = flat_idx is None and ops.mq_last_layer and self.transformer.encoder.rows_supported(None, bool(training))
         if mq:
             rows, _, _, _, _ = self._encode(inputs, training, pack, n_real_tokens, rows_of=positions)
             return rows, self._rows_extra

@@ -47,6 +47,13 @@ def set_dropout_seed(seed):
     dropout_seeds.reseed(seed)
 
 
+def _attention_rate(rate):
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError('attention_dropout_rate must lie in [0, 1), got %r' % (rate,))
+    return rate
+
+
 def create_segment_markers(seq, sep=SEP):
     """Cumulative count of SEP tokens along axis 1 (reference transformer.py:6-34; unused on the hot path)."""
     return torch.cumsum((seq == sep).to(torch.int32), dim=1)
@@ -207,12 +214,16 @@ def point_wise_feed_forward_network(d_model, dff, ffn_activation='relu'):
 
 class EncoderLayer(nn.Module):
     """Post-LN block: out1 = LN1(x + drop(mha(x))); out2 = LN2(out1 + drop(ffn(out1))) (reference :202-213).
-    Runs as two fused autograd blocks of HIP kernels."""
+    Runs as two fused autograd blocks of HIP kernels.
+    attention_dropout_rate (BERT's attention_probs_dropout_prob; no reference counterpart): dropout on the attention
+    probabilities inside the attention kernels, in training only.  Its seed is a THIRD draw from dropout_seeds, taken after the
+    two of the residual branches and only when the rate is > 0: at rate 0 the seed stream is what it always was."""
 
-    def __init__(self, d_model, num_heads, dff, rate=0.1, ffn_activation='relu', **kwargs):
+    def __init__(self, d_model, num_heads, dff, rate=0.1, ffn_activation='relu', attention_dropout_rate=0.0, **kwargs):
         super().__init__()
         self.d_model, self.num_heads, self.dff, self.rate = d_model, num_heads, dff, rate
         self.ffn_activation = ffn_activation
+        self.attention_dropout_rate = _attention_rate(attention_dropout_rate)
         self.mha = MultiHeadAttention(d_model, num_heads)
         self.ffn = point_wise_feed_forward_network(d_model, dff, ffn_activation)
         self.layernorm1 = LayerNormalization(d_model, 1e-6)
@@ -220,7 +231,8 @@ class EncoderLayer(nn.Module):
 
     def get_config(self):
         return {'d_model': self.d_model, 'num_heads': self.num_heads, 'dff': self.dff, 'rate': self.rate,
-                **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {})}
+                **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
+                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {})}
 
     def forward(self, x, training=None, mask=None, packed=None, rows=None):
         """x (B, S, d); or, with `packed` (ops.Packed), the (1, T, d) rows of the real tokens only and mask = the (T,) key
@@ -243,8 +255,13 @@ class EncoderLayer(nn.Module):
         m, f = self.mha, self.ffn
         s1 = dropout_seeds.next() if training else 0
         s2 = dropout_seeds.next() if training else 0
+        a_rate = self.attention_dropout_rate if training else 0.0
+        s3 = dropout_seeds.next() if a_rate > 0 else 0
         need_tape = training or torch.is_grad_enabled()
         if rows is not None:
+            if a_rate > 0:
+                raise B4CError('the masked-query last layer (rows=) has no attention dropout: evaluate the full layer while '
+                               'training with attention_dropout_rate > 0 (Encoder.rows_supported(dtype, training))')
             midx, moff = rows
             if cu is None:          # dense layout: sequence b owns token rows b*S .. (b+1)*S, pad keys are masked by their bytes
                 cu = torch.arange(B + 1, dtype=torch.int32, device=x.device) * S
@@ -258,7 +275,8 @@ class EncoderLayer(nn.Module):
                                         self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape, f.act)
         out1 = ops.AttnBlockFn.apply(x2, key_pad, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel, m.wv.bias,
                                      m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
-                                     m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape, cu)
+                                     m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape, cu,
+                                     a_rate, s3)
         out2 = ops.FFNBlockFn.apply(out1, f[0].kernel, f[0].bias, f[1].kernel, f[1].bias, self.layernorm2.gamma,
                                     self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape, f.act)
         return out2.view(out_shape)
@@ -269,19 +287,22 @@ class Encoder(nn.Module):
     reference's Encoder.call (:263) is fused into the embedding kernel when ``Transformer`` calls the Encoder;
     an Encoder called on its own applies it with the stand-alone dropout kernel (same keep-mask generator)."""
 
-    def __init__(self, num_layers, d_model, num_heads, dff, dropout_rate, ffn_activation='relu', **kwargs):
+    def __init__(self, num_layers, d_model, num_heads, dff, dropout_rate, ffn_activation='relu', attention_dropout_rate=0.0,
+                 **kwargs):
         super().__init__()
         self.num_layers, self.d_model, self.num_heads, self.dff, self.dropout_rate = \
             num_layers, d_model, num_heads, dff, dropout_rate
         ops.ffn_act_code(ffn_activation)        # (ValueError also for an encoder of no layers)
         self.ffn_activation = ffn_activation
-        self.enc_layers = nn.ModuleList([EncoderLayer(d_model, num_heads, dff, dropout_rate, ffn_activation)
-                                         for _ in range(num_layers)])
+        self.attention_dropout_rate = _attention_rate(attention_dropout_rate)
+        self.enc_layers = nn.ModuleList([EncoderLayer(d_model, num_heads, dff, dropout_rate, ffn_activation,
+                                                      self.attention_dropout_rate) for _ in range(num_layers)])
 
     def get_config(self):
         return {'num_layers': self.num_layers, 'd_model': self.d_model, 'num_heads': self.num_heads, 'dff': self.dff,
                 'dropout_rate': self.dropout_rate,
-                **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {})}
+                **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
+                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {})}
 
     def forward(self, inputs, training=None, mask=None, _input_dropout_done=False, packed=None, rows=None):
         """rows (see EncoderLayer.forward): the LAST layer is evaluated for those query rows only; returns (R, d)."""
@@ -294,9 +315,10 @@ class Encoder(nn.Module):
             x = layer(x, training, mask, packed, rows if i == last else None)
         return x
 
-    def rows_supported(self, x_dtype):
-        """The masked-query form of the last layer: head depth 32 / 64 (b4c_attn_mq_*), at least one layer."""
-        if not self.enc_layers:
+    def rows_supported(self, x_dtype, training=False):
+        """The masked-query form of the last layer: head depth 32 / 64 (b4c_attn_mq_*), at least one layer.  Those kernels have no
+        attention dropout: a training pass with attention_dropout_rate > 0 takes the full last layer and gathers its rows."""
+        if not self.enc_layers or (training and self.attention_dropout_rate > 0):
             return False
         return (self.d_model // self.num_heads) in (32, 64) and self.d_model % 8 == 0
 
@@ -338,14 +360,16 @@ class Transformer(nn.Module):
     per-feature embedding -> concat on the last axis (or, feature_combine='sum', added) -> * sqrt(d_model) -> + sinusoidal
     PE -> Encoder.
     Extensions of the BERT4Rec paper, no reference counterpart: ffn_activation ('relu' | 'gelu' | 'gelu_tanh') for the
-    feed-forward blocks, and position_encoding='learned' with max_positions: the positional table is a parameter
-    ``position_embedding.weight`` [max_positions, d_model] (truncated normal, sigma 0.02) instead of the fixed sinusoid."""
+    feed-forward blocks, position_encoding='learned' with max_positions: the positional table is a parameter
+    ``position_embedding.weight`` [max_positions, d_model] (truncated normal, sigma 0.02) instead of the fixed sinusoid, and
+    attention_dropout_rate: dropout on the attention probabilities (BERT's attention_probs_dropout_prob), in training only."""
 
     def __init__(self, num_layers, num_attention_heads, embedding_sizes, embedding_dims, encoder_ff_dim, dropout_rate,
                  item_embedding_weights=None, compute_dtype=torch.float32, feature_combine='concat', ffn_activation='relu',
-                 position_encoding='sinusoidal', max_positions=None, **kwargs):
+                 position_encoding='sinusoidal', max_positions=None, attention_dropout_rate=0.0, **kwargs):
         super().__init__()
         ops.ffn_act_code(ffn_activation)
+        self.attention_dropout_rate = _attention_rate(attention_dropout_rate)
         if position_encoding not in ('sinusoidal', 'learned'):
             raise ValueError("position_encoding must be 'sinusoidal' or 'learned', got %r" % (position_encoding,))
         if position_encoding == 'learned' and (max_positions is None or int(max_positions) < 1):
@@ -375,7 +399,8 @@ class Transformer(nn.Module):
             if dim % 8 != 0:
                 raise B4CError('MI355X build: embedding dim of feature %r is %d; must be a multiple of 8' % (f, dim))
         self.compute_dtype = compute_dtype
-        self.encoder = Encoder(num_layers, self.d_model, num_attention_heads, encoder_ff_dim, dropout_rate, ffn_activation)
+        self.encoder = Encoder(num_layers, self.d_model, num_attention_heads, encoder_ff_dim, dropout_rate, ffn_activation,
+                               self.attention_dropout_rate)
         self.embedding_layers = _FeatureModules({f: _Embedding(int(embedding_sizes[f]), int(embedding_dims[f]))
                                                  for f in embedding_dims.keys()})
         if position_encoding == 'learned':
@@ -395,7 +420,8 @@ class Transformer(nn.Module):
                 **({'feature_combine': 'sum'} if self.feature_combine == 'sum' else {}),
                 **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
                 **({'position_encoding': 'learned', 'max_positions': self.max_positions}
-                   if self.position_encoding == 'learned' else {})}
+                   if self.position_encoding == 'learned' else {}),
+                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {})}
 
     @property
     def position_table(self):

@@ -63,10 +63,12 @@ template <int DH> __device__ __forceinline__ float dot_lds(const float (&a)[DH],
     return s;
 }
 
-template <typename T, int DH>
+// DROP (all three kernels): attention-probability dropout by the keep rule of common.h (b4c_attn_keep); q and k are the positions,
+// the pitch is S.  The DROP = false instantiations are the kernels without it.
+template <typename T, int DH, bool DROP>
 __global__ void __launch_bounds__(256) attn_fwd_row_kernel(const T *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                            T *__restrict__ o, int ld_o, float *__restrict__ lse, int S, int H,
-                                                           float sqrt_dk) {
+                                                           float sqrt_dk, float rate, uint64_t seed) {
     __shared__ __attribute__((aligned(16))) float sK[ATT_TILE][DH];
     __shared__ __attribute__((aligned(16))) float sV[ATT_TILE][DH];
     __shared__ uint8_t sPad[ATT_TILE];
@@ -80,6 +82,9 @@ __global__ void __launch_bounds__(256) attn_fwd_row_kernel(const T *__restrict__
     for (int d = 0; d < DH; ++d) { q[d] = 0.f; acc[d] = 0.f; }
     if (active) load_row<T, DH>(qkv + (tok0 + qi) * ld + h * DH, q);
     float m = -INFINITY, l = 0.f;
+    const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
+    const uint64_t drow = (uint64_t)blockIdx.y * S + (uint32_t)qi;
+    uint32_t kb = 0;
     for (int k0 = 0; k0 < S; k0 += ATT_TILE) {
         __syncthreads();
         stage_tile<T, DH>(qkv, ld, tok0, k0, S, dm + h * DH, sK, tid);
@@ -100,6 +105,10 @@ __global__ void __launch_bounds__(256) attn_fwd_row_kernel(const T *__restrict__
             }
             const float p = expf(s - m);
             l += p;
+            if (DROP) {      // l keeps the undropped sum; 1 / (1 - rate) joins the final 1 / l.  One hash per four keys.
+                if ((j & 3) == 0) kb = b4c_attn_keep4(seed, b4c_attn_ctr(drow, k0 + j, S), thr);
+                if (!((kb >> (j & 3)) & 1u)) continue;
+            }
 #pragma unroll
             for (int d = 0; d < DH; d += 4) {
                 const f32x4 vv = *reinterpret_cast<const f32x4 *>(&sV[j][d]);
@@ -111,7 +120,7 @@ __global__ void __launch_bounds__(256) attn_fwd_row_kernel(const T *__restrict__
         }
     }
     if (active) {
-        const float inv = 1.0f / l;
+        const float inv = DROP ? (1.0f / (1.0f - rate)) / l : 1.0f / l;
 #pragma unroll
         for (int d = 0; d < DH; ++d) acc[d] *= inv;
         store_row<T, DH>(o + (tok0 + qi) * ld_o + h * DH, acc);
@@ -120,11 +129,12 @@ __global__ void __launch_bounds__(256) attn_fwd_row_kernel(const T *__restrict__
 }
 
 // dQ: thread per query; also writes delta[q] = sum_d dO[q][d] * O[q][d]
-template <typename T, int DH>
+template <typename T, int DH, bool DROP>
 __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                           const T *__restrict__ o, int ld_o, const T *__restrict__ d_o, int ld_do,
                                                           const float *__restrict__ lse, float *__restrict__ delta,
-                                                          T *__restrict__ dqkv, int ld_dq, int S, int H, float sqrt_dk) {
+                                                          T *__restrict__ dqkv, int ld_dq, int S, int H, float sqrt_dk, float rate,
+                                                          uint64_t seed) {
     __shared__ __attribute__((aligned(16))) float sK[ATT_TILE][DH];
     __shared__ __attribute__((aligned(16))) float sV[ATT_TILE][DH];
     __shared__ uint8_t sPad[ATT_TILE];
@@ -147,6 +157,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T *__restrict__ 
         L = lse[((int64_t)b * H + h) * S + qi];
         delta[((int64_t)b * H + h) * S + qi] = dlt;
     }
+    const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
+    const float inv_keep = DROP ? 1.0f / (1.0f - rate) : 1.0f;
+    const uint64_t drow = (uint64_t)blockIdx.y * S + (uint32_t)qi;
+    uint32_t kb = 0;
     for (int k0 = 0; k0 < S; k0 += ATT_TILE) {
         __syncthreads();
         stage_tile<T, DH>(qkv, ld, tok0, k0, S, dm + h * DH, sK, tid);
@@ -156,10 +170,12 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T *__restrict__ 
         if (!active) continue;
         const int nk = min(ATT_TILE, S - k0);
         for (int j = 0; j < nk; ++j) {
+            if (DROP && (j & 3) == 0) kb = b4c_attn_keep4(seed, b4c_attn_ctr(drow, k0 + j, S), thr);
             if (sPad[j]) continue;  // p == 0 exactly (exp(-1e9 - lse))
             const float s = dot_lds<DH>(q, &sK[j][0]) / sqrt_dk;
             const float p = expf(s - L);
-            const float dp = dot_lds<DH>(g, &sV[j][0]);
+            float dp = dot_lds<DH>(g, &sV[j][0]);
+            if (DROP) dp = ((kb >> (j & 3)) & 1u) ? dp * inv_keep : 0.f;     // dP = keep / (1 - rate) * dP~
             const float ds = p * (dp - dlt);
 #pragma unroll
             for (int d = 0; d < DH; d += 4) {
@@ -179,11 +195,11 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T *__restrict__ 
 }
 
 // dK, dV: thread per key; queries (q, dO, lse, delta) stream through LDS
-template <typename T, int DH>
+template <typename T, int DH, bool DROP>
 __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                            const T *__restrict__ d_o, int ld_do, const float *__restrict__ lse,
                                                            const float *__restrict__ delta, T *__restrict__ dqkv, int ld_dq, int S,
-                                                           int H, float sqrt_dk) {
+                                                           int H, float sqrt_dk, float rate, uint64_t seed) {
     __shared__ __attribute__((aligned(16))) float sQ[ATT_TILE][DH];
     __shared__ __attribute__((aligned(16))) float sG[ATT_TILE][DH];
     __shared__ float sL[ATT_TILE], sD[ATT_TILE];
@@ -215,16 +231,25 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T *__restrict__
         for (int i = 0; i < nq; ++i) {
             const float s = dot_lds<DH>(k, &sQ[i][0]) / sqrt_dk;
             const float p = expf(s - sL[i]);
-            const float dp = dot_lds<DH>(v, &sG[i][0]);
+            float dp = dot_lds<DH>(v, &sG[i][0]);
+            float pd = p;           // what dV sums: the dropped, rescaled P~
+            if (DROP) {
+                // one hash per (query, key): the thread owns ONE key of the four a hash covers (the exact-parity path, not the
+                // throughput path)
+                const float kf = b4c_keep_elem(seed, ((uint64_t)blockIdx.y * S + (uint32_t)(q0 + i)) * b4c_attn_s4(S) + (uint32_t)kj, rate)
+                                     ? 1.0f / (1.0f - rate) : 0.f;
+                pd = p * kf;
+                dp *= kf;
+            }
             const float ds = p * (dp - sD[i]);
 #pragma unroll
             for (int d = 0; d < DH; d += 4) {
                 const f32x4 gv = *reinterpret_cast<const f32x4 *>(&sG[i][d]);
                 const f32x4 qv = *reinterpret_cast<const f32x4 *>(&sQ[i][d]);
-                dv[d] += p * gv[0];
-                dv[d + 1] += p * gv[1];
-                dv[d + 2] += p * gv[2];
-                dv[d + 3] += p * gv[3];
+                dv[d] += pd * gv[0];
+                dv[d + 1] += pd * gv[1];
+                dv[d + 2] += pd * gv[2];
+                dv[d + 3] += pd * gv[3];
                 dk[d] += ds * qv[0];
                 dk[d + 1] += ds * qv[1];
                 dk[d + 2] += ds * qv[2];
@@ -242,10 +267,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T *__restrict__
 
 // bf16 MFMA forward/backward (attn_mfma.hip); return B4C_EUNSUPPORTED when the shape is not covered.
 int b4c_attn_fwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B, int S,
-                      int H, int dh, const int32_t *cu, hipStream_t st);
+                      int H, int dh, const int32_t *cu, float rate, uint64_t seed, hipStream_t st);
 int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o, const void *d_o,
                       int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B, int S, int H, int dh,
-                      void *workspace, int64_t workspace_bytes, const int32_t *cu, hipStream_t st);
+                      void *workspace, int64_t workspace_bytes, const int32_t *cu, float rate, uint64_t seed, hipStream_t st);
 int64_t b4c_attn_bwd_mfma_workspace_bytes(int B, int S, int H, int dh);
 
 // bf16 shapes the MFMA kernels do not cover (S > 512 or head depth 16 / 128) run on the fp32-math row kernels, which are
@@ -265,39 +290,88 @@ static int check_attn(const char *who, int ld_qkv, int ld_o, int B, int S, int H
     B4C_REQUIRE((int64_t)B * H <= 65535, "%s: B*H = %lld exceeds the grid.y limit 65535", who, (long long)B * H);
     return B4C_OK;
 }
+// the attention-probability dropout rate of the *_drop entry points: [0, 1) (a NaN fails the comparison too)
+static int check_attn_rate(const char *who, float rate) {
+    B4C_REQUIRE(rate >= 0.f && rate < 1.f, "%s: dropout rate %g outside [0, 1)", who, (double)rate);
+    return B4C_OK;
+}
 
-#define ATT_DISPATCH_DH(dh, KERNEL, T, ...)                      \
-    switch (dh) {                                                \
-        case 16: KERNEL<T, 16> __VA_ARGS__; break;               \
-        case 32: KERNEL<T, 32> __VA_ARGS__; break;               \
-        case 64: KERNEL<T, 64> __VA_ARGS__; break;               \
-        default: KERNEL<T, 128> __VA_ARGS__; break;              \
+// rate == 0 selects the DROP = false instantiations: the kernels of the entry points without dropout
+#define ATT_DISPATCH_DH(dh, KERNEL, T, DR, ...)                      \
+    switch (dh) {                                                    \
+        case 16: KERNEL<T, 16, DR> __VA_ARGS__; break;               \
+        case 32: KERNEL<T, 32, DR> __VA_ARGS__; break;               \
+        case 64: KERNEL<T, 64, DR> __VA_ARGS__; break;               \
+        default: KERNEL<T, 128, DR> __VA_ARGS__; break;              \
     }
+#define ATT_DISPATCH(dh, KERNEL, T, ...)                                                     \
+    if (rate == 0.f) { ATT_DISPATCH_DH(dh, KERNEL, T, false, __VA_ARGS__) }                  \
+    else { ATT_DISPATCH_DH(dh, KERNEL, T, true, __VA_ARGS__) }
 
-extern "C" int b4c_attn_fwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
-                            int S, int H, int dh, int dtype, void *stream) {
-    B4C_REQUIRE(qkv && key_pad && o, "attn_fwd: null pointer");
-    int rc = check_attn("attn_fwd", ld_qkv, ld_o, B, S, H, dh);
+static int attn_fwd_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
+                        int S, int H, int dh, float rate, uint64_t seed, int dtype, void *stream) {
+    B4C_REQUIRE(qkv && key_pad && o, "%s: null pointer", who);
+    int rc = check_attn(who, ld_qkv, ld_o, B, S, H, dh);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == B4C_BF16) {
-        rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, nullptr, st);
+        rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, nullptr, rate, seed, st);
         if (rc != B4C_EUNSUPPORTED) return rc;
-        note_row_fallback("attn_fwd", S, dh);
+        note_row_fallback(who, S, dh);
     }
     const float sq = sqrtf((float)dh);
     dim3 grid((S + 255) / 256, B * H);
     if (dtype == B4C_F32) {
-        ATT_DISPATCH_DH(dh, attn_fwd_row_kernel, float, <<<grid, 256, 0, st>>>((const float *)qkv, ld_qkv, key_pad, (float *)o, ld_o, lse, S, H, sq))
+        ATT_DISPATCH(dh, attn_fwd_row_kernel, float, <<<grid, 256, 0, st>>>((const float *)qkv, ld_qkv, key_pad, (float *)o, ld_o, lse, S, H, sq, rate, seed))
     } else if (dtype == B4C_BF16) {
-        ATT_DISPATCH_DH(dh, attn_fwd_row_kernel, bf16_t, <<<grid, 256, 0, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, sq))
+        ATT_DISPATCH(dh, attn_fwd_row_kernel, bf16_t, <<<grid, 256, 0, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, sq, rate, seed))
     } else
-        B4C_REQUIRE(false, "attn_fwd: dtype %d", dtype);
-    return b4c_check_launch("attn_fwd");
+        B4C_REQUIRE(false, "%s: dtype %d", who, dtype);
+    return b4c_check_launch(who);
+}
+
+extern "C" int b4c_attn_fwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
+                            int S, int H, int dh, int dtype, void *stream) {
+    return attn_fwd_any("attn_fwd", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, 0.f, 0, dtype, stream);
+}
+
+extern "C" int b4c_attn_fwd_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
+                                 int S, int H, int dh, int dtype, void *stream, float dropout_rate, uint64_t seed) {
+    int rc = check_attn_rate("attn_fwd_drop", dropout_rate);
+    if (rc) return rc;
+    return attn_fwd_any("attn_fwd_drop", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, dropout_rate, seed, dtype, stream);
 }
 
 extern "C" int64_t b4c_attn_bwd_workspace_bytes(int B, int S, int H, int dh, int dtype) {
     return dtype == B4C_BF16 ? b4c_attn_bwd_mfma_workspace_bytes(B, S, H, dh) : 0;
+}
+
+static int attn_bwd_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
+                        const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B,
+                        int S, int H, int dh, void *workspace, int64_t workspace_bytes, float rate, uint64_t seed, int dtype,
+                        void *stream) {
+    B4C_REQUIRE(qkv && key_pad && o && d_o && lse && delta && dqkv, "%s: null pointer", who);
+    int rc = check_attn(who, ld_qkv, ld_o, B, S, H, dh);
+    if (rc) return rc;
+    B4C_REQUIRE(ld_do >= H * dh && ld_do % 8 == 0 && ld_dqkv >= 3 * H * dh && ld_dqkv % 8 == 0, "%s: bad pitch", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == B4C_BF16) {
+        rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
+                               workspace_bytes, nullptr, rate, seed, st);
+        if (rc != B4C_EUNSUPPORTED) return rc;
+        note_row_fallback(who, S, dh);
+    }
+    const float sq = sqrtf((float)dh);
+    dim3 grid((S + 255) / 256, B * H);
+    if (dtype == B4C_F32) {
+        ATT_DISPATCH(dh, attn_bwd_dq_kernel, float, <<<grid, 256, 0, st>>>((const float *)qkv, ld_qkv, key_pad, (const float *)o, ld_o, (const float *)d_o, ld_do, lse, delta, (float *)dqkv, ld_dqkv, S, H, sq, rate, seed))
+        ATT_DISPATCH(dh, attn_bwd_dkv_kernel, float, <<<grid, 256, 0, st>>>((const float *)qkv, ld_qkv, key_pad, (const float *)d_o, ld_do, lse, delta, (float *)dqkv, ld_dqkv, S, H, sq, rate, seed))
+    } else if (dtype == B4C_BF16) {
+        ATT_DISPATCH(dh, attn_bwd_dq_kernel, bf16_t, <<<grid, 256, 0, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, delta, (bf16_t *)dqkv, ld_dqkv, S, H, sq, rate, seed))
+        ATT_DISPATCH(dh, attn_bwd_dkv_kernel, bf16_t, <<<grid, 256, 0, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)d_o, ld_do, lse, delta, (bf16_t *)dqkv, ld_dqkv, S, H, sq, rate, seed))
+    } else
+        B4C_REQUIRE(false, "%s: dtype %d", who, dtype);
+    return b4c_check_launch(who);
 }
 
 extern "C" int b4c_attn_bwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
@@ -309,28 +383,18 @@ extern "C" int b4c_attn_bwd(const void *qkv, int ld_qkv, const uint8_t *key_pad,
 extern "C" int b4c_attn_bwd_ws(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
                                const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B,
                                int S, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype, void *stream) {
-    B4C_REQUIRE(qkv && key_pad && o && d_o && lse && delta && dqkv, "attn_bwd: null pointer");
-    int rc = check_attn("attn_bwd", ld_qkv, ld_o, B, S, H, dh);
+    return attn_bwd_any("attn_bwd", qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
+                        workspace_bytes, 0.f, 0, dtype, stream);
+}
+
+extern "C" int b4c_attn_bwd_drop_ws(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
+                                    const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B,
+                                    int S, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype, void *stream,
+                                    float dropout_rate, uint64_t seed) {
+    int rc = check_attn_rate("attn_bwd_drop", dropout_rate);
     if (rc) return rc;
-    B4C_REQUIRE(ld_do >= H * dh && ld_do % 8 == 0 && ld_dqkv >= 3 * H * dh && ld_dqkv % 8 == 0, "attn_bwd: bad pitch");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == B4C_BF16) {
-        rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
-                               workspace_bytes, nullptr, st);
-        if (rc != B4C_EUNSUPPORTED) return rc;
-        note_row_fallback("attn_bwd", S, dh);
-    }
-    const float sq = sqrtf((float)dh);
-    dim3 grid((S + 255) / 256, B * H);
-    if (dtype == B4C_F32) {
-        ATT_DISPATCH_DH(dh, attn_bwd_dq_kernel, float, <<<grid, 256, 0, st>>>((const float *)qkv, ld_qkv, key_pad, (const float *)o, ld_o, (const float *)d_o, ld_do, lse, delta, (float *)dqkv, ld_dqkv, S, H, sq))
-        ATT_DISPATCH_DH(dh, attn_bwd_dkv_kernel, float, <<<grid, 256, 0, st>>>((const float *)qkv, ld_qkv, key_pad, (const float *)d_o, ld_do, lse, delta, (float *)dqkv, ld_dqkv, S, H, sq))
-    } else if (dtype == B4C_BF16) {
-        ATT_DISPATCH_DH(dh, attn_bwd_dq_kernel, bf16_t, <<<grid, 256, 0, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, delta, (bf16_t *)dqkv, ld_dqkv, S, H, sq))
-        ATT_DISPATCH_DH(dh, attn_bwd_dkv_kernel, bf16_t, <<<grid, 256, 0, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)d_o, ld_do, lse, delta, (bf16_t *)dqkv, ld_dqkv, S, H, sq))
-    } else
-        B4C_REQUIRE(false, "attn_bwd: dtype %d", dtype);
-    return b4c_check_launch("attn_bwd");
+    return attn_bwd_any("attn_bwd_drop", qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
+                        workspace_bytes, dropout_rate, seed, dtype, stream);
 }
 
 
@@ -338,14 +402,44 @@ extern "C" int b4c_attn_bwd_ws(const void *qkv, int ld_qkv, const uint8_t *key_p
 // the longest sequence (LDS sizing, lse / delta pitch: [B][H][max_len]).  bf16, head depth 32 / 64, max_len <= 512 only: the
 // packed layout exists for the throughput path, the fp32 parity path stays dense.  key_pad [total tokens]: all zeros unless
 // the caller keeps masked keys inside the packed rows.
+static int attn_fwd_varlen_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o,
+                               int ld_o, float *lse, int B, int max_len, int H, int dh, float rate, uint64_t seed, int dtype,
+                               void *stream) {
+    B4C_REQUIRE(qkv && key_pad && cu_seqlens && o, "%s: null pointer", who);
+    int rc = check_attn(who, ld_qkv, ld_o, B, max_len, H, dh);
+    if (rc) return rc;
+    B4C_REQUIRE(dtype == B4C_BF16, "%s: bf16 only", who);
+    rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, max_len, H, dh, cu_seqlens, rate, seed, (hipStream_t)stream);
+    B4C_REQUIRE(rc != B4C_EUNSUPPORTED, "%s: max_len %d / head depth %d outside the MFMA kernels (<= 512, 32 or 64)", who, max_len, dh);
+    return rc;
+}
+
 extern "C" int b4c_attn_fwd_varlen(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
                                    float *lse, int B, int max_len, int H, int dh, int dtype, void *stream) {
-    B4C_REQUIRE(qkv && key_pad && cu_seqlens && o, "attn_fwd_varlen: null pointer");
-    int rc = check_attn("attn_fwd_varlen", ld_qkv, ld_o, B, max_len, H, dh);
+    return attn_fwd_varlen_any("attn_fwd_varlen", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, max_len, H, dh, 0.f, 0, dtype, stream);
+}
+
+extern "C" int b4c_attn_fwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o,
+                                        int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype, void *stream,
+                                        float dropout_rate, uint64_t seed) {
+    int rc = check_attn_rate("attn_fwd_varlen_drop", dropout_rate);
     if (rc) return rc;
-    B4C_REQUIRE(dtype == B4C_BF16, "attn_fwd_varlen: bf16 only");
-    rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, max_len, H, dh, cu_seqlens, (hipStream_t)stream);
-    B4C_REQUIRE(rc != B4C_EUNSUPPORTED, "attn_fwd_varlen: max_len %d / head depth %d outside the MFMA kernels (<= 512, 32 or 64)", max_len, dh);
+    return attn_fwd_varlen_any("attn_fwd_varlen_drop", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, max_len, H, dh, dropout_rate,
+                               seed, dtype, stream);
+}
+
+static int attn_bwd_varlen_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                               const void *o, int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv,
+                               int ld_dqkv, int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes, float rate,
+                               uint64_t seed, int dtype, void *stream) {
+    B4C_REQUIRE(qkv && key_pad && cu_seqlens && o && d_o && lse && delta && dqkv, "%s: null pointer", who);
+    int rc = check_attn(who, ld_qkv, ld_o, B, max_len, H, dh);
+    if (rc) return rc;
+    B4C_REQUIRE(dtype == B4C_BF16, "%s: bf16 only", who);
+    B4C_REQUIRE(ld_do >= H * dh && ld_do % 8 == 0 && ld_dqkv >= 3 * H * dh && ld_dqkv % 8 == 0, "%s: bad pitch", who);
+    rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, max_len, H, dh, workspace,
+                           workspace_bytes, cu_seqlens, rate, seed, (hipStream_t)stream);
+    B4C_REQUIRE(rc != B4C_EUNSUPPORTED, "%s: shape outside the MFMA kernels, or workspace missing for max_len > 256", who);
     return rc;
 }
 
@@ -353,13 +447,21 @@ extern "C" int b4c_attn_bwd_varlen(const void *qkv, int ld_qkv, const uint8_t *k
                                    int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv,
                                    int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype,
                                    void *stream) {
-    B4C_REQUIRE(qkv && key_pad && cu_seqlens && o && d_o && lse && delta && dqkv, "attn_bwd_varlen: null pointer");
-    int rc = check_attn("attn_bwd_varlen", ld_qkv, ld_o, B, max_len, H, dh);
+    return attn_bwd_varlen_any("attn_bwd_varlen", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B,
+                               max_len, H, dh, workspace, workspace_bytes, 0.f, 0, dtype, stream);
+}
+
+extern "C" int b4c_attn_bwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, const void *o,
+                                        int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv,
+                                        int ld_dqkv, int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes,
+                                        int dtype, void *stream, float dropout_rate, uint64_t seed) {
+    int rc = check_attn_rate("attn_bwd_varlen_drop", dropout_rate);
     if (rc) return rc;
-    B4C_REQUIRE(dtype == B4C_BF16, "attn_bwd_varlen: bf16 only");
-    B4C_REQUIRE(ld_do >= H * dh && ld_do % 8 == 0 && ld_dqkv >= 3 * H * dh && ld_dqkv % 8 == 0, "attn_bwd_varlen: bad pitch");
-    rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, max_len, H, dh, workspace,
-                           workspace_bytes, cu_seqlens, (hipStream_t)stream);
-    B4C_REQUIRE(rc != B4C_EUNSUPPORTED, "attn_bwd_varlen: shape outside the MFMA kernels, or workspace missing for max_len > 256");
-    return rc;
+    return attn_bwd_varlen_any("attn_bwd_varlen_drop", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv,
+                               B, max_len, H, dh, workspace, workspace_bytes, dropout_rate, seed, dtype, stream);
+}
+
+// the keep rule of the *_drop entry points on the host (common.h: b4c_attn_keep_elem)
+extern "C" int b4c_attn_keep(uint64_t seed, int b, int h, int q, int k, int H, int S_arg, float rate) {
+    return b4c_attn_keep_elem(seed, b, h, q, k, H, S_arg, rate) ? 1 : 0;
 }

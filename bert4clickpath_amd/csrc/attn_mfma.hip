@@ -98,14 +98,40 @@ __device__ __forceinline__ bf16x8 frag_tr(const char *p, int second_off) {
 }
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
+// ---- attention-probability dropout (template parameter DROP; the DROP = false bodies are the kernels without it) ----
+// Keep bits of one 32 x 32 score tile of the BACKWARD kernels, which hold the KEY on the lane (r) and the QUERY on the accumulator
+// rows (rowmap): bit t = register t.  The keep rule (common.h) hashes four consecutive keys of one query at once, and the four
+// lanes of a quad hold exactly such four keys: each lane hashes the queries of the registers (r & 3) + 4 tq, tq = 0..3, and the
+// quad exchanges the bits (DPP quad broadcast) -- four hashes per lane per tile, as in the forward, where the four keys are
+// four registers of one lane.  The hash counter b4c_attn_ctr(row, k0, S_arg) is split into the workgroup-uniform
+// base = (b*H + h) * S_arg * (S4 / 4) and a 32-bit lane part q * (S4 / 4) + k0 / 4 (q < 512, S4 / 4 <= 128).  q0 / k_tile = first
+// query / key of the tile.  EXEC must be full.
+template <int C> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, C * 0x55, 0xf, 0xf, true);
+}
+__device__ __forceinline__ uint64_t attn_ctr_base(int bh, int S_arg) { return (uint64_t)bh * S_arg * (b4c_attn_s4(S_arg) >> 2); }
+__device__ __forceinline__ uint32_t attn_keep_tile_bwd(uint64_t seed, uint64_t base, int S_arg, int q0, int k_tile, uint32_t thr, int r, int hf) {
+    const int c = r & 3;
+    const uint32_t s4q = b4c_attn_s4(S_arg) >> 2, kq = (uint32_t)(k_tile + (r & ~3)) >> 2;
+    uint32_t mk = 0;
+#pragma unroll
+    for (int tq = 0; tq < 4; ++tq)
+        mk |= b4c_attn_keep4(seed, base + ((uint32_t)(q0 + c + 8 * tq + 4 * hf) * s4q + kq), thr) << (4 * tq);
+    uint32_t km = ((quad_bcast<0>(mk) >> c) & 0x1111u);
+    km |= ((quad_bcast<1>(mk) >> c) & 0x1111u) << 1;
+    km |= ((quad_bcast<2>(mk) >> c) & 0x1111u) << 2;
+    km |= ((quad_bcast<3>(mk) >> c) & 0x1111u) << 3;
+    return km;
+}
+
 // ------------------------------------------------------------------------------------------
 // forward: 512 threads, wave w owns query tiles w, w + 8, ... (QPW of them: S <= 256 QPW; QPW = 2 covers S <= 512, where
 // the K / V images of one (sequence, head) take 147 KB of LDS and one workgroup runs per CU)
 // ------------------------------------------------------------------------------------------
-template <int DH, int QPW>
+template <int DH, int QPW, bool DROP>
 __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(const bf16_t *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                             bf16_t *__restrict__ o, int ld_o, float *__restrict__ lse, int S_arg, int H,
-                                                            float scale, const int32_t *__restrict__ cu) {
+                                                            float scale, const int32_t *__restrict__ cu, float rate, uint64_t seed) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KSTR = DH * 2 + 16;
     constexpr int NKS = DH / 16, NDT = DH / 32, CH = DH / 8;
@@ -122,6 +148,7 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hf = lane >> 5;
     const float scale2 = scale * 1.4426950408889634f;
     const int li = lane & 15, g = lane >> 4;
+    const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
     if (S <= 0) return;
     const bf16_t *kbase = qkv + tok0 * ld + dm + hh * DH;
     const bf16_t *vbase = kbase + dm;
@@ -235,6 +262,17 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
                 acc[t] = __builtin_amdgcn_exp2f(acc[t] - mref);
                 l[qi] += acc[t];
             }
+            if (DROP) {
+                // l keeps the undropped sum; the dropped probabilities only lose their place in P V (1 / (1 - rate) joins the
+                // final 1 / l).  Registers 4 tq .. 4 tq + 3 are the keys kt*32 + 8 tq + 4 hf + {0..3} of this lane's query: one hash.
+                const uint32_t s4q = b4c_attn_s4(S_arg) >> 2, dq = (uint32_t)((wave + 8 * qi) * 32 + r) * s4q;
+#pragma unroll
+                for (int tq = 0; tq < 4; ++tq) {
+                    const uint32_t kb = b4c_attn_keep4(seed, attn_ctr_base(blockIdx.x, S_arg) + (dq + (uint32_t)(kt * 8 + 2 * tq + hf)), thr);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[4 * tq + j] = ((kb >> j) & 1u) ? acc[4 * tq + j] : 0.f;
+                }
+            }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 float pv[8];
@@ -260,7 +298,7 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
     for (int qi = 0; qi < QPW; ++qi) {
         const int qt = wave + 8 * qi;
         if (qt < nkt) {
-            const float inv = 1.0f / l[qi];
+            const float inv = DROP ? (1.0f / (1.0f - rate)) / l[qi] : 1.0f / l[qi];
             char *st = smem + qt * (32 * KSTR);
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt)
@@ -288,12 +326,12 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
 // stream through a double-buffered LDS image with register prefetch; delta = rowsum(dO * O) is
 // computed while staging; dQ tile = 8 (16 x 16) MFMA tiles, one per wave.
 // ------------------------------------------------------------------------------------------
-template <int DH>
+template <int DH, bool DROP>
 __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                    const bf16_t *__restrict__ o, int ld_o, const bf16_t *__restrict__ d_o,
                                                    int ld_do, const float *__restrict__ lse, bf16_t *__restrict__ dqkv,
                                                    int ld_dq, int S_arg, int H, float scale, int key0, float *__restrict__ dq_acc,
-                                                   int acc_mode, const int32_t *__restrict__ cu) {
+                                                   int acc_mode, const int32_t *__restrict__ cu, float rate, uint64_t seed) {
     // One block of up to 256 keys of one (sequence, head): the workgroup owns the dK / dV rows of those keys and the part of
     // dQ that sums over them.  acc_mode 0: dQ is complete, written as bf16; 1: first block of several, the partial dQ goes
     // to dq_acc (fp32 [B*S][H*DH]); 2: middle block, dq_acc += partial; 3: last block, dQ = bf16(dq_acc + partial).  Every
@@ -384,6 +422,8 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
     const bool key_live = kt < nkt && key < S && !key_pad[tok0 + key];
     const float madd = (kt >= nkt || key >= S) ? -INFINITY : (key_live ? 0.f : -1e9f);
     const bool tile_live = __any(key_live);           // ballot over the wave's 64 lanes (both halves hold the same keys)
+    const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
+    const float inv_keep = DROP ? 1.0f / (1.0f - rate) : 1.0f;
     f32x16 dk[NDT], dv[NDT];
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
@@ -413,12 +453,20 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
                     pa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fg, fv, pa, 0, 0, 0);
                 }
                 float pv[16], dsv[16];
+                // dropout: dV takes the dropped, rescaled P~; dS = P o (keep / (1 - rate) * dP~ - delta) with the undropped P
+                const uint32_t km = DROP ? attn_keep_tile_bwd(seed, attn_ctr_base(blockIdx.x, S_arg), S_arg, q0, key0 + kt * 32, thr, r, hf) : 0u;
 #pragma unroll
                 for (int t = 0; t < 16; ++t) {
                     const int q = rowmap(t, hf);
                     const float p = __expf(sa[t] * scale + madd - sLse[q]);
-                    pv[t] = p;
-                    dsv[t] = p * (pa[t] - sDelta[q]);
+                    if (DROP) {
+                        const bool kp = (km >> t) & 1u;
+                        pv[t] = kp ? p * inv_keep : 0.f;
+                        dsv[t] = p * ((kp ? pa[t] * inv_keep : 0.f) - sDelta[q]);
+                    } else {
+                        pv[t] = p;
+                        dsv[t] = p * (pa[t] - sDelta[q]);
+                    }
                     *reinterpret_cast<bf16_t *>(sDS + q * TSTR + (kt * 32 + r) * 2) = (bf16_t)dsv[t];
                 }
 #pragma unroll
@@ -491,15 +539,15 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
 // Sequences of up to 256 keys: one block (acc_mode 0).  Longer ones (S <= 512): the workgroup walks the blocks of 256 keys
 // one after the other in ONE launch (round 2 launched the kernel once per block): Q, dO, O and the fp32 partial dQ of the
 // second pass come out of L2 right behind the first instead of from HBM behind a whole launch.
-template <int DH>
+template <int DH, bool DROP>
 __global__ void __launch_bounds__(512) attn_bwd_mfma_kernel(const bf16_t *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                             const bf16_t *__restrict__ o, int ld_o, const bf16_t *__restrict__ d_o,
                                                             int ld_do, const float *__restrict__ lse, bf16_t *__restrict__ dqkv,
                                                             int ld_dq, int S_arg, int H, float scale, int nblk, float *__restrict__ dq_acc,
-                                                            const int32_t *__restrict__ cu) {
+                                                            const int32_t *__restrict__ cu, float rate, uint64_t seed) {
     for (int kb = 0; kb < nblk; ++kb) {
         const int mode = nblk == 1 ? 0 : (kb == 0 ? 1 : (kb == nblk - 1 ? 3 : 2));
-        attn_bwd_key_block<DH>(qkv, ld, key_pad, o, ld_o, d_o, ld_do, lse, dqkv, ld_dq, S_arg, H, scale, kb * 256, dq_acc, mode, cu);
+        attn_bwd_key_block<DH, DROP>(qkv, ld, key_pad, o, ld_o, d_o, ld_do, lse, dqkv, ld_dq, S_arg, H, scale, kb * 256, dq_acc, mode, cu, rate, seed);
     }
 }
 
@@ -509,12 +557,12 @@ __global__ void __launch_bounds__(512) attn_bwd_mfma_kernel(const bf16_t *__rest
 // streaming kernel above spends ~60 % of its wave-cycles parked on those, SQ_WAIT_ANY) -- then the 32-query
 // tiles run back to back out of LDS.
 // ------------------------------------------------------------------------------------------
-template <int DH>
+template <int DH, bool DROP>
 __global__ void __launch_bounds__(512) attn_bwd_resident_kernel(const bf16_t *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                                 const bf16_t *__restrict__ o, int ld_o, const bf16_t *__restrict__ d_o,
                                                                 int ld_do, const float *__restrict__ lse, bf16_t *__restrict__ dqkv,
                                                                 int ld_dq, int S_arg, int H, float scale, int n_items, int *__restrict__ work_counter,
-                                                                const int32_t *__restrict__ cu) {
+                                                                const int32_t *__restrict__ cu, float rate, uint64_t seed) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KSTR = DH * 2 + 16;
     constexpr int NKS = DH / 16, NDT = DH / 32, CH = DH / 8;
@@ -534,6 +582,8 @@ __global__ void __launch_bounds__(512) attn_bwd_resident_kernel(const bf16_t *__
     char *sDQ = reinterpret_cast<char *>(sNext + 4);      // [32][KSTR] bf16: the dQ tile on its way out as row chunks
     constexpr int RPW = 64 / CH, SPT = 32 / RPW;          // rows one wave stages per pass, such slices per query tile
     const int dm = H * DH;
+    const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
+    const float inv_keep = DROP ? 1.0f / (1.0f - rate) : 1.0f;
     // One workgroup per CU walks the (sequence, head) items: no dispatch gap between items, and the stores of one item
     // drain under the loads of the next.  After its first item a workgroup takes items from a global counter (ragged
     // sequences and skipped query tiles make item times differ by several x; a static split leaves CUs idle at the end).
@@ -668,12 +718,20 @@ __global__ void __launch_bounds__(512) attn_bwd_resident_kernel(const bf16_t *__
                 pa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fg, fvr[ks], pa, 0, 0, 0);
             }
             float pv[16], dsv[16];
+            // dropout: dV takes the dropped, rescaled P~; dS = P o (keep / (1 - rate) * dP~ - delta) with the undropped P
+            const uint32_t km = DROP ? attn_keep_tile_bwd(seed, attn_ctr_base(item, S_arg), S_arg, q0, kt * 32, thr, r, hf) : 0u;
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 const int q = rowmap(t, hf);
                 const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[t], scale2, madd - sLse[q]));
-                pv[t] = p;
-                dsv[t] = p * (pa[t] - sDelta[q]);
+                if (DROP) {
+                    const bool kp = (km >> t) & 1u;
+                    pv[t] = kp ? p * inv_keep : 0.f;
+                    dsv[t] = p * ((kp ? pa[t] * inv_keep : 0.f) - sDelta[q]);
+                } else {
+                    pv[t] = p;
+                    dsv[t] = p * (pa[t] - sDelta[q]);
+                }
                 *reinterpret_cast<bf16_t *>(sDS + q * TSTR + (kt * 32 + r) * 2) = (bf16_t)dsv[t];
             }
 #pragma unroll
@@ -767,20 +825,26 @@ static int att_num_cus() {
 #define ATT_MAX_S 512      // two query tiles per wave in the forward; key blocks of 256 in the backward
 static bool mfma_shape_ok(int S, int dh) { return (dh == 32 || dh == 64) && S <= ATT_MAX_S; }
 
+// rate == 0 launches the DROP = false instantiations: the kernels of the entry points without dropout.
 int b4c_attn_fwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B, int S,
-                      int H, int dh, const int32_t *cu, hipStream_t st) {
+                      int H, int dh, const int32_t *cu, float rate, uint64_t seed, hipStream_t st) {
     if (!mfma_shape_ok(S, dh)) return B4C_EUNSUPPORTED;
     const int S_pad = (S + 31) / 32 * 32;
     const int qpw = S_pad > 32 * ATT_MAX_KT ? 2 : 1;
     const size_t shm = 2 * (size_t)S_pad * (dh * 2 + 16) + (size_t)S_pad * 4 + ATT_MAX_KT * qpw * 4;
     const float scale = 1.0f / sqrtf((float)dh);
-#define ATT_FWD_LAUNCH(DHH, QQ)                                                                                          \
+#define ATT_FWD_LAUNCH(DHH, QQ, DR)                                                                                      \
     do {                                                                                                                 \
-        allow_lds_attn(attn_fwd_mfma_kernel<DHH, QQ>, shm);                                                              \
-        attn_fwd_mfma_kernel<DHH, QQ><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, scale, cu); \
+        allow_lds_attn(attn_fwd_mfma_kernel<DHH, QQ, DR>, shm);                                                          \
+        attn_fwd_mfma_kernel<DHH, QQ, DR><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, scale, cu, rate, seed); \
     } while (0)
-    if (dh == 64) { if (qpw == 1) ATT_FWD_LAUNCH(64, 1); else ATT_FWD_LAUNCH(64, 2); }
-    else { if (qpw == 1) ATT_FWD_LAUNCH(32, 1); else ATT_FWD_LAUNCH(32, 2); }
+#define ATT_FWD_LAUNCH_DH(DHH)                                                                                           \
+    do {                                                                                                                 \
+        if (rate == 0.f) { if (qpw == 1) ATT_FWD_LAUNCH(DHH, 1, false); else ATT_FWD_LAUNCH(DHH, 2, false); }            \
+        else { if (qpw == 1) ATT_FWD_LAUNCH(DHH, 1, true); else ATT_FWD_LAUNCH(DHH, 2, true); }                          \
+    } while (0)
+    if (dh == 64) ATT_FWD_LAUNCH_DH(64); else ATT_FWD_LAUNCH_DH(32);
+#undef ATT_FWD_LAUNCH_DH
 #undef ATT_FWD_LAUNCH
     return b4c_check_launch("attn_fwd_mfma");
 }
@@ -792,9 +856,24 @@ int64_t b4c_attn_bwd_mfma_workspace_bytes(int B, int S, int H, int dh) {
 
 int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o, const void *d_o,
                       int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B, int S, int H, int dh,
-                      void *workspace, int64_t workspace_bytes, const int32_t *cu, hipStream_t st) {
+                      void *workspace, int64_t workspace_bytes, const int32_t *cu, float rate, uint64_t seed, hipStream_t st) {
     if (!mfma_shape_ok(S, dh)) return B4C_EUNSUPPORTED;
-    const float scale_s = 1.0f / sqrtf((float)dh);
+    const float scale = 1.0f / sqrtf((float)dh);
+#define ATT_BWD_BLOCKS(DHH, DR, SHM, NBLK, ACC)                                                                          \
+    do {                                                                                                                 \
+        allow_lds_attn(attn_bwd_mfma_kernel<DHH, DR>, SHM);                                                              \
+        attn_bwd_mfma_kernel<DHH, DR><<<B * H, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, NBLK, ACC, cu, rate, seed); \
+    } while (0)
+#define ATT_BWD_RESIDENT(DHH, DR, SHM, GRID)                                                                             \
+    do {                                                                                                                 \
+        allow_lds_attn(attn_bwd_resident_kernel<DHH, DR>, SHM);                                                          \
+        attn_bwd_resident_kernel<DHH, DR><<<GRID, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, B * H, (int *)delta, cu, rate, seed); \
+    } while (0)
+#define ATT_BWD_SELECT(LAUNCH, ...)                                                                                      \
+    do {                                                                                                                 \
+        if (dh == 64) { if (rate == 0.f) LAUNCH(64, false, __VA_ARGS__); else LAUNCH(64, true, __VA_ARGS__); }           \
+        else { if (rate == 0.f) LAUNCH(32, false, __VA_ARGS__); else LAUNCH(32, true, __VA_ARGS__); }                    \
+    } while (0)
     if (S > 32 * ATT_MAX_KT) {
         // the blocks of 256 keys one after the other inside one launch; their partial dQ sums meet in an fp32 accumulator
         // (caller's workspace)
@@ -802,39 +881,23 @@ int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const
         const size_t kstr2 = dh * 2 + 16, tstr2 = 256 * 2 + 16;
         const size_t shm2 = 2 * 256 * kstr2 + 2 * (2 * 32 * kstr2 + 256) + 32 * tstr2;
         const int nblk = (S + 255) / 256;
-        if (dh == 64) {
-            allow_lds_attn(attn_bwd_mfma_kernel<64>, shm2);
-            attn_bwd_mfma_kernel<64><<<B * H, 512, shm2, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale_s, nblk, (float *)workspace, cu);
-        } else {
-            allow_lds_attn(attn_bwd_mfma_kernel<32>, shm2);
-            attn_bwd_mfma_kernel<32><<<B * H, 512, shm2, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale_s, nblk, (float *)workspace, cu);
-        }
+        ATT_BWD_SELECT(ATT_BWD_BLOCKS, shm2, nblk, (float *)workspace);
         return b4c_check_launch("attn_bwd_mfma (key blocks)");
     }
     const int S_pad = (S + 31) / 32 * 32;
     const size_t kstr = dh * 2 + 16, tstr = S_pad * 2 + 16;
     const size_t shm = 2 * S_pad * kstr + 2 * (2 * 32 * kstr + 256) + 32 * tstr;
     const size_t shm_res = 4 * S_pad * kstr + 32 * tstr + 2 * (size_t)S_pad * 4 + ATT_MAX_KT * 4 * 4 + 16 + 32 * kstr;
-    const float scale = 1.0f / sqrtf((float)dh);
     if (shm_res <= 160 * 1024) {
         const int grid_res = B * H < att_num_cus() ? B * H : att_num_cus();   // > 80 KB of LDS: one workgroup per CU
         // delta itself is computed while staging dO / O; its first word is the work counter of the persistent grid
         if (hipMemsetAsync(delta, 0, sizeof(int), st) != hipSuccess) return B4C_ELAUNCH;
-        if (dh == 64) {
-            allow_lds_attn(attn_bwd_resident_kernel<64>, shm_res);
-            attn_bwd_resident_kernel<64><<<grid_res, 512, shm_res, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, B * H, (int *)delta, cu);
-        } else {
-            allow_lds_attn(attn_bwd_resident_kernel<32>, shm_res);
-            attn_bwd_resident_kernel<32><<<grid_res, 512, shm_res, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, B * H, (int *)delta, cu);
-        }
+        ATT_BWD_SELECT(ATT_BWD_RESIDENT, shm_res, grid_res);
         return b4c_check_launch("attn_bwd_resident");
     }
-    if (dh == 64) {
-        allow_lds_attn(attn_bwd_mfma_kernel<64>, shm);
-        attn_bwd_mfma_kernel<64><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, 1, nullptr, cu);
-    } else {
-        allow_lds_attn(attn_bwd_mfma_kernel<32>, shm);
-        attn_bwd_mfma_kernel<32><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, 1, nullptr, cu);
-    }
+    ATT_BWD_SELECT(ATT_BWD_BLOCKS, shm, 1, (float *)nullptr);
+#undef ATT_BWD_SELECT
+#undef ATT_BWD_RESIDENT
+#undef ATT_BWD_BLOCKS
     return b4c_check_launch("attn_bwd_mfma");
 }

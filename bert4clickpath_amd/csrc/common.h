@@ -134,6 +134,28 @@ __host__ __device__ __forceinline__ uint32_t b4c_keep8(uint64_t seed, uint64_t e
     return m;
 }
 
+// ---- attention-probability dropout: the one keep rule (include/b4c.h, b4c_attn_keep) ----
+// The probability of (sequence b, head h, query q, key k) is element e = ((b*H + h) * S_arg + q) * S4 + k of the keep-mask
+// stream, S4 = S_arg rounded up to a multiple of 4; q, k = row indices inside the sequence, S_arg = the pitch of the launch (S, or
+// the packed layout's max_len).  S4 % 4 == 0: the four keys k0 .. k0+3 (k0 % 4 == 0) of one query share ONE hash, whose
+// counter is b4c_attn_ctr(row, k0), row = (b*H + h) * S_arg + q.
+__host__ __device__ __forceinline__ uint32_t b4c_attn_s4(int S_arg) { return ((uint32_t)S_arg + 3u) & ~3u; }
+__host__ __device__ __forceinline__ uint64_t b4c_attn_ctr(uint64_t row, int k0, int S_arg) {
+    return row * (b4c_attn_s4(S_arg) >> 2) + (uint32_t)(k0 >> 2);
+}
+__host__ __device__ __forceinline__ bool b4c_attn_keep_elem(uint64_t seed, int b, int h, int q, int k, int H, int S_arg, float rate) {
+    const uint64_t row = ((uint64_t)b * H + h) * S_arg + q;
+    return b4c_keep_elem(seed, row * b4c_attn_s4(S_arg) + (uint32_t)k, rate);
+}
+// keep bits of the keys k0 .. k0+3 of one query (bit j = key k0 + j), ctr = b4c_attn_ctr(row, k0, S_arg).  One hash.
+__host__ __device__ __forceinline__ uint32_t b4c_attn_keep4(uint64_t seed, uint64_t ctr, uint32_t thr) {
+    const uint64_t h = b4c_rand64(seed, ctr);
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) m |= (((uint32_t)(h >> (16 * j)) & 0xFFFFu) >= thr ? 1u : 0u) << j;
+    return m;
+}
+
 // ---- wave / block reductions ----
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -801,8 +801,18 @@ def attn_mq_bwd(q, kv, cu, moff, o, d_o, lse, B, max_len, H, dh, key_pad=None):
     return dq, dkv
 
 
-def attn_fwd(qkv, key_pad, B, S, H, dh, cu=None):
-    """cu (int32 [B+1]): packed layout -- sequence b owns rows cu[b] .. cu[b+1] of qkv, S = upper bound of the longest one."""
+def _attn_rate(rate):
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError('attention dropout rate must lie in [0, 1), got %r' % (rate,))
+    return rate
+
+
+def attn_fwd(qkv, key_pad, B, S, H, dh, cu=None, rate=0.0, seed=0):
+    """cu (int32 [B+1]): packed layout -- sequence b owns rows cu[b] .. cu[b+1] of qkv, S = upper bound of the longest one.
+    rate > 0: dropout on the attention probabilities, mask b4c_attn_keep(seed, b, h, q, k, H, S, rate) (include/b4c.h); lse is that
+    of the undropped softmax.  rate == 0 is the call without dropout."""
+    rate = _attn_rate(rate)
     d = H * dh
     T_tok = qkv.shape[0]
     o = torch.empty(T_tok, d, dtype=qkv.dtype, device=qkv.device)
@@ -811,7 +821,13 @@ def attn_fwd(qkv, key_pad, B, S, H, dh, cu=None):
     # padded layout computes)
     pairs = rec_hints.get('sum_len_sq', T_tok * S) if cu is not None else T_tok * S
     with _record('attn_fwd', T_tok * 4 * d * qkv.element_size(), 4 * pairs * d):
-        if cu is None:
+        if rate > 0 and cu is None:
+            L.check(L.lib().b4c_attn_fwd_drop(_p(qkv), qkv.stride(0), _p(key_pad), _p(o), d, _p(lse), B, S, H, dh,
+                                              dt_code(qkv.dtype), _st(), rate, seed), 'attn_fwd_drop')
+        elif rate > 0:
+            L.check(L.lib().b4c_attn_fwd_varlen_drop(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), d, _p(lse), B, S, H, dh,
+                                                     dt_code(qkv.dtype), _st(), rate, seed), 'attn_fwd_varlen_drop')
+        elif cu is None:
             L.check(L.lib().b4c_attn_fwd(_p(qkv), qkv.stride(0), _p(key_pad), _p(o), d, _p(lse), B, S, H, dh,
                                          dt_code(qkv.dtype), _st()), 'attn_fwd')
         else:
@@ -820,8 +836,10 @@ def attn_fwd(qkv, key_pad, B, S, H, dh, cu=None):
     return o, lse
 
 
-def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None):
-    """actx: the ArenaContext of the training step in flight (its background work gets a launch opportunity behind this kernel)"""
+def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None, rate=0.0, seed=0):
+    """actx: the ArenaContext of the training step in flight (its background work gets a launch opportunity behind this kernel)
+    rate, seed: those of the forward (attn_fwd); o is the forward's output, dropped probabilities included."""
+    rate = _attn_rate(rate)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
     need = L.lib().b4c_attn_bwd_workspace_bytes(B, S, H, dh, dt_code(qkv.dtype))     # > 0 only for bf16 256 < S <= 512
@@ -829,7 +847,15 @@ def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None):
     T_tok = qkv.shape[0]
     pairs = rec_hints.get('sum_len_sq', T_tok * S) if cu is not None else T_tok * S
     with _record('attn_bwd', T_tok * 8 * H * dh * qkv.element_size(), 10 * pairs * H * dh):
-        if cu is None:
+        if rate > 0 and cu is None:
+            L.check(L.lib().b4c_attn_bwd_drop_ws(_p(qkv), qkv.stride(0), _p(key_pad), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
+                                                 _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
+                                                 dt_code(qkv.dtype), _st(), rate, seed), 'attn_bwd_drop')
+        elif rate > 0:
+            L.check(L.lib().b4c_attn_bwd_varlen_drop(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), o.stride(0), _p(d_o),
+                                                     d_o.stride(0), _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh,
+                                                     _p(ws), need, dt_code(qkv.dtype), _st(), rate, seed), 'attn_bwd_varlen_drop')
+        elif cu is None:
             L.check(L.lib().b4c_attn_bwd_ws(_p(qkv), qkv.stride(0), _p(key_pad), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
                                             _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
                                             dt_code(qkv.dtype), _st()), 'attn_bwd')
@@ -1688,10 +1714,12 @@ class EmbedFn(torch.autograd.Function):
 
 
 class AttnBlockFn(torch.autograd.Function):
-    """R8 + first half of R10: LN1(x + drop(MHA(x))).  x: [T, d] in the compute dtype."""
+    """R8 + first half of R10: LN1(x + drop(MHA(x))).  x: [T, d] in the compute dtype.
+    attn_rate, attn_seed: dropout on the attention probabilities (attn_fwd; no reference counterpart), applied as given."""
 
     @staticmethod
-    def forward(ctx, x, key_pad, wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta, pk_qkv, pk_o, B, S, H, rate, seed, training, cu=None):
+    def forward(ctx, x, key_pad, wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta, pk_qkv, pk_o, B, S, H, rate, seed, training, cu=None,
+                attn_rate=0.0, attn_seed=0):
         T_tok, d = x.shape
         dh = d // H
         wt_qkv, _, b_qkv = pk_qkv.get(x.dtype, d, training)
@@ -1699,7 +1727,8 @@ class AttnBlockFn(torch.autograd.Function):
         with _timed('qkv_fwd'):
             qkv = gemm_nt(x, wt_qkv, 3 * d, b_qkv)
         with _timed('attn_fwd'):
-            o, lse = attn_fwd(qkv, key_pad, B, S, H, dh, cu)
+            # (without attention dropout: the call as it has always been)
+            o, lse = attn_fwd(qkv, key_pad, B, S, H, dh, cu, **({'rate': attn_rate, 'seed': attn_seed} if attn_rate > 0 else {}))
         if gemm_ln_supported(o, d):
             z, out, stats = gemm_nt_add_ln(o, wt_o, b_o, x, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
                                            save=training)
@@ -1712,6 +1741,7 @@ class AttnBlockFn(torch.autograd.Function):
             ctx.pk = (pk_qkv, pk_o)
             ctx.dims = (B, S, H, dh, rate, seed)
             ctx.cu = cu
+            ctx.attn_drop = {'rate': attn_rate, 'seed': attn_seed} if attn_rate > 0 else {}
             ctx.params = (wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta)
         return out
 
@@ -1739,7 +1769,7 @@ class AttnBlockFn(torch.autograd.Function):
                 queue_dw(actx, o, dy, d, d, [gwo], [gbo], (wo, bo))
                 d_o = gemm_nt(dy, wc_o, d)
         with _timed('attn_bwd'):
-            dqkv = attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, ctx.cu, actx)
+            dqkv = attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, ctx.cu, actx, **ctx.attn_drop)
         if routes and fused_dxdw and dxdw_supported(x, dqkv, 3, residual=dz):
             # dX and dW | db of the fused Q | K | V projection in one pass over dqkv (csrc/gemm_dxdw.hip)
             dx = gemm_dxdw(x, dqkv, wc_qkv, [gwq, gwk, gwv], [gbq, gbk, gbv], residual=dz)
@@ -1750,6 +1780,16 @@ class AttnBlockFn(torch.autograd.Function):
         _ready(gam, bet)
         flush_pending_dw(actx)      # this layer's four weight gradients (two queued by FFNBlockFn.backward) in one launch
         return sink_returns(ctx, (dx, None), actx, sinks)
+
+
+def attn_keep_mask(seed, B, H, S_arg, rate):
+    """Host regeneration of an attention-dropout keep-mask (tests): bool [B, H, S_arg, S_arg], element (b, h, q, k) kept iff
+    b4c_attn_keep(seed, b, h, q, k, H, S_arg, rate): element ((b*H + h) * S_arg + q) * S4 + k of keep_mask's stream, S4 = S_arg
+    rounded up to a multiple of 4.  S_arg: the pitch of the launch (S, or the packed layout's max_len); q, k count inside the
+    sequence."""
+    S4 = (S_arg + 3) // 4 * 4
+    m = torch.from_numpy(keep_mask(seed, B * H * S_arg * S4, rate))
+    return m.view(B, H, S_arg, S4)[..., :S_arg].contiguous()
 
 
 def rows_add_(dst, idx, src):

@@ -705,6 +705,37 @@ int b4c_adamw_rows(float *p, float *g, float *m, float *v, int32_t *stamp, const
                    int64_t rows, int width, const float *lr_hist, const float *decay_hist, int t, float beta1, float beta2,
                    float eps, float grad_mul, const float *coef, int mode, void *stream);
 
+/* ---- attention-probability dropout (BERT's attention_probs_dropout_prob, nn.MultiheadAttention(dropout=); the reference's
+ * attention has none: no oracle, the BERT4Rec paper's recipe) -- additive to ABI 12 --------------------------------------------
+ * With P the masked softmax of b4c_attn_fwd, for sequence b, head h, query q, key k:
+ *   P~[q][k] = keep(b, h, q, k) ? P[q][k] / (1 - rate) : 0;   o = P~ v;   lse is that of P (the row sum takes the undropped p).
+ * Backward, with dP~ = dO V^T and delta = rowsum(dO o O) (O already holds the dropped probabilities):
+ *   dV = P~^T dO;   dS = P o (keep / (1 - rate) * dP~ - delta);   dQ = dS K / sqrt(dh);   dK = dS^T Q / sqrt(dh).
+ * THE KEEP RULE (one rule for every kernel; csrc/common.h): the probability of (b, h, q, k) is element
+ *   e = ((b*H + h) * S_arg + q) * S4 + k,   S4 = S_arg rounded up to a multiple of 4,
+ * of the keep-mask stream of b4c_keep: kept iff b4c_keep(seed, e, rate).  q and k are the row indices INSIDE the sequence as the
+ * kernel sees them (dense layout: the position; packed layout: row - cu_seqlens[b]); S_arg is the pitch of the launch (S, or the
+ * packed layout's max_len).  Four consecutive keys k0 .. k0+3 (k0 % 4 == 0) of one query share one hash.
+ * b4c_attn_keep is that rule on the host (1 = kept), so tests and other hosts regenerate the masks without a GPU.
+ * The four entry points are b4c_attn_fwd, b4c_attn_bwd_ws, b4c_attn_fwd_varlen and b4c_attn_bwd_varlen with (dropout_rate, seed)
+ * appended; the workspace is b4c_attn_bwd_workspace_bytes'.  dropout_rate == 0 launches the very kernels of those entry points;
+ * a rate outside [0, 1) is B4C_EINVAL.  b4c_attn_weights keeps returning the undropped softmax; the masked-query kernels
+ * (b4c_attn_mq_*) have no dropout. */
+int b4c_attn_keep(uint64_t seed, int b, int h, int q, int k, int H, int S_arg, float rate);
+int b4c_attn_fwd_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
+                      int S, int H, int dh, int dtype, void *stream, float dropout_rate, uint64_t seed);
+int b4c_attn_bwd_drop_ws(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
+                         const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B,
+                         int S, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype, void *stream,
+                         float dropout_rate, uint64_t seed);
+int b4c_attn_fwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
+                             float *lse, int B, int max_len, int H, int dh, int dtype, void *stream, float dropout_rate,
+                             uint64_t seed);
+int b4c_attn_bwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, const void *o,
+                             int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv,
+                             int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype,
+                             void *stream, float dropout_rate, uint64_t seed);
+
 #ifdef __cplusplus
 }
 #endif
