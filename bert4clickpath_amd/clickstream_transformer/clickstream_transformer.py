@@ -293,7 +293,7 @@ class ClickstreamTransformer(nn.Module):
         feats = {k: v for k, v in inputs.items() if k != 'instance_id'}
         pack = self._use_packed(feats, packed, n_real_tokens)
         if self.segment_to_head is None and self.value_to_head is not None and ops.mq_last_layer and \
-                self.transformer.encoder.rows_supported(None, training):
+                self.transformer.encoder.rows_route(None, training):
             # the head reads the rows at the value_to_head positions only: the last encoder layer is evaluated for those
             # rows alone (padded to M per sequence; a padding slot is a query row made of zeros whose output nobody reads)
             def positions(ids_first, raw_first):
@@ -373,8 +373,8 @@ class ClickstreamTransformer(nn.Module):
 
         # The positions depend on the ids alone.  With them in hand BEFORE the encoder runs, its last layer is evaluated
         # for those rows only (ops.MQAttnBlockFn): nothing else of that layer's output is ever read on this path.
-        # (not in training with attention dropout: the masked-query kernels have none, the full layer runs and its rows are gathered)
-        mq = flat_idx is None and ops.mq_last_layer and self.transformer.encoder.rows_supported(None, bool(training))
+        # (in training with attention dropout only with ops.mq_attn_dropout: without it the full layer runs and its rows are gathered)
+        mq = flat_idx is None and ops.mq_last_layer and self.transformer.encoder.rows_route(None, bool(training))
         if mq:
             rows, _, _, _, _ = self._encode(inputs, training, pack, n_real_tokens, rows_of=positions)
             return rows, self._rows_extra

@@ -238,7 +238,9 @@ class EncoderLayer(nn.Module):
         """x (B, S, d); or, with `packed` (ops.Packed), the (1, T, d) rows of the real tokens only and mask = the (T,) key
         bytes the embedding stage produced for them.
         rows = (midx [R] int32 token rows, moff [B+1] int32 per-sequence offsets into them): the layer is evaluated for
-        those query rows only (keys / values from every token) and returns (R, d) -- the last layer of the Cloze path."""
+        those query rows only (keys / values from every token) and returns (R, d) -- the last layer of the Cloze path.
+        In training with attention_dropout_rate > 0 that takes ops.mq_attn_dropout (off by default: B4CError); the masked-query
+        kernels then draw, with the layer's third seed, the masks the full layer draws for those rows."""
         B, S, d = x.shape
         training = bool(training)
         cu = None
@@ -259,7 +261,7 @@ class EncoderLayer(nn.Module):
         s3 = dropout_seeds.next() if a_rate > 0 else 0
         need_tape = training or torch.is_grad_enabled()
         if rows is not None:
-            if a_rate > 0:
+            if a_rate > 0 and not ops.mq_attn_dropout:
                 raise B4CError('the masked-query last layer (rows=) has no attention dropout: evaluate the full layer while '
                                'training with attention_dropout_rate > 0 (Encoder.rows_supported(dtype, training))')
             midx, moff = rows
@@ -270,7 +272,8 @@ class EncoderLayer(nn.Module):
                 kp = None           # packed layout: every token is real
             out1 = ops.MQAttnBlockFn.apply(x2, midx, moff, cu, kp, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel,
                                            m.wv.bias, m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
-                                           m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape)
+                                           m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape,
+                                           a_rate, s3)
             return ops.FFNBlockFn.apply(out1, f[0].kernel, f[0].bias, f[1].kernel, f[1].bias, self.layernorm2.gamma,
                                         self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape, f.act)
         out1 = ops.AttnBlockFn.apply(x2, key_pad, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel, m.wv.bias,
@@ -321,6 +324,13 @@ class Encoder(nn.Module):
         if not self.enc_layers or (training and self.attention_dropout_rate > 0):
             return False
         return (self.d_model // self.num_heads) in (32, 64) and self.d_model % 8 == 0
+
+    def rows_route(self, x_dtype, training=False):
+        """Does the last layer take its masked-query form in this pass?  rows_supported(...); with ops.mq_attn_dropout on, the same
+        shape conditions without the dropout exclusion (b4c_attn_mq_*_drop draws the full layer's masks for the query rows)."""
+        if ops.mq_attn_dropout:
+            return self.rows_supported(x_dtype, False)
+        return self.rows_supported(x_dtype, training)
 
 
 class _Embedding(nn.Module):

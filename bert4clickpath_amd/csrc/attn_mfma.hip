@@ -105,11 +105,7 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 // quad exchanges the bits (DPP quad broadcast) -- four hashes per lane per tile, as in the forward, where the four keys are
 // four registers of one lane.  The hash counter b4c_attn_ctr(row, k0, S_arg) is split into the workgroup-uniform
 // base = (b*H + h) * S_arg * (S4 / 4) and a 32-bit lane part q * (S4 / 4) + k0 / 4 (q < 512, S4 / 4 <= 128).  q0 / k_tile = first
-// query / key of the tile.  EXEC must be full.
-template <int C> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, C * 0x55, 0xf, 0xf, true);
-}
-__device__ __forceinline__ uint64_t attn_ctr_base(int bh, int S_arg) { return (uint64_t)bh * S_arg * (b4c_attn_s4(S_arg) >> 2); }
+// query / key of the tile.  EXEC must be full.  (quad_bcast, attn_ctr_base: common.h.)
 __device__ __forceinline__ uint32_t attn_keep_tile_bwd(uint64_t seed, uint64_t base, int S_arg, int q0, int k_tile, uint32_t thr, int r, int hf) {
     const int c = r & 3;
     const uint32_t s4q = b4c_attn_s4(S_arg) >> 2, kq = (uint32_t)(k_tile + (r & ~3)) >> 2;

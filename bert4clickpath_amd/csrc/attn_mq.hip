@@ -16,6 +16,12 @@
 //            live in the thread's registers, q_m (and dO_m) are broadcast reads from LDS;
 //   phase 2  lane per feature, queries dealt to the waves: o_m = sum_key p V[key] / dq_m = sum_key dS K[key], V / K rows
 //            read from LDS (conflict-free: a wave reads one 128-B row).
+//
+// DROP (all four kernels): attention-probability dropout by the keep rule of common.h (b4c_attn_keep).  The rule counts the QUERY
+// inside its sequence, and these kernels see compact query rows: q_rows [R] (the token row of each query row) gives the position
+// q = q_rows[r] - cu[b], the pitch S_arg is the launch's max_len -- the masks are those of the full layer's kernels for the same
+// rows.  q_rows is read for the rows below the sequence's query count only (an unused slot holds -1) and no address depends on
+// it.  The DROP = false instantiations are the kernels without it.
 #include <math.h>
 
 #include "common.h"
@@ -58,11 +64,12 @@ template <int N> __device__ __forceinline__ float mq_dot(const float (&a)[N], co
 }
 
 // LDS (dynamic): sQ [MQ][DH] f32 | sP [MQ][SP] f32 | sV [MQ_KB][DH] T          (SP = padded longest sequence)
-template <typename T, int DH>
+template <typename T, int DH, bool DROP>
 __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__restrict__ q, int ld_q, const T *__restrict__ kv, int ld_kv,
                                                                  const uint8_t *__restrict__ key_pad, const int32_t *__restrict__ cu,
                                                                  const int32_t *__restrict__ moff, T *__restrict__ o, int ld_o,
-                                                                 float *__restrict__ lse, int H, int SP, float sqrt_dk) {
+                                                                 float *__restrict__ lse, int H, int SP, float sqrt_dk,
+                                                                 const int32_t *__restrict__ q_rows, int S_arg, float rate, uint64_t seed) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int HD = DH / 2;                                // features per thread of a key pair
     float *sQ = reinterpret_cast<float *>(smem);
@@ -76,6 +83,8 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
     const int r0 = moff[b], M = moff[b + 1] - moff[b];
     if (M <= 0) return;
     constexpr int VCH = MQ_KB * (DH / 8) / MQ_THREADS;           // 16-B chunks of a V block per thread
+    const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
+    const float inv_keep = DROP ? 1.0f / (1.0f - rate) : 1.0f;
     for (int mc = 0; mc < M; mc += MQ) {
         const int mq = min(MQ, M - mc);
         // every global load of the first key block goes out before the first wait: the K half row of this thread's key, the
@@ -146,6 +155,18 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
             for (int j = lane; j < S; j += 64) row[j] = expf(row[j] - L);
             for (int j = S + lane; j < SP; j += 64) row[j] = 0.f;     // (the loop below runs over whole groups of four keys)
             if (lane == 0) lse[(int64_t)(r0 + mc + m) * H + h] = L;
+            if (DROP) {
+                // the row holds the undropped p (lse is theirs); the dropped ones lose their place in P V and 1 / (1 - rate) joins
+                // the output.  A lane takes four consecutive keys: one hash.  (The wave's own LDS writes are in order.)
+                const uint64_t drow = (uint64_t)blockIdx.x * S_arg + (uint32_t)(q_rows[r0 + mc + m] - (int)tok0);
+                for (int j = 4 * lane; j < S; j += 256) {
+                    const uint32_t kb = b4c_attn_keep4(seed, b4c_attn_ctr(drow, j, S_arg), thr);
+                    f32x4 p4 = *reinterpret_cast<const f32x4 *>(row + j);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) p4[u] = ((kb >> u) & 1u) ? p4[u] : 0.f;
+                    *reinterpret_cast<f32x4 *>(row + j) = p4;
+                }
+            }
         }
         // phase 2: o_m = sum_key p[m][key] V[key]: lane = feature, the wave's queries share every V read
         constexpr int QW = (MQ + 3) / 4;
@@ -185,20 +206,21 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
 #pragma unroll
             for (int i = 0; i < QW; ++i) {
                 const int m = wave + 4 * i;
-                if (m < mq) o[(int64_t)(r0 + mc + m) * ld_o + h * DH + lane] = (T)acc[i];
+                if (m < mq) o[(int64_t)(r0 + mc + m) * ld_o + h * DH + lane] = (T)(DROP ? acc[i] * inv_keep : acc[i]);
             }
         }
     }
 }
 
-// LDS (dynamic): sQ [MQ][DH] | sG [MQ][DH] | sLse [MQ] | sDelta [MQ] | sDS [MQ][MQ_KB] (f32) | sK [MQ_KB][DH] T
-template <typename T, int DH>
+// LDS (dynamic): sQ [MQ][DH] | sG [MQ][DH] | sLse [MQ] | sDelta [MQ] | sDS [MQ][MQ_KB] (f32) | sK [MQ_KB][DH] T | DROP: sPos [MQ] i32
+template <typename T, int DH, bool DROP>
 __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__restrict__ q, int ld_q, const T *__restrict__ kv, int ld_kv,
                                                                  const uint8_t *__restrict__ key_pad, const int32_t *__restrict__ cu,
                                                                  const int32_t *__restrict__ moff, const T *__restrict__ o, int ld_o,
                                                                  const T *__restrict__ d_o, int ld_do, const float *__restrict__ lse,
                                                                  T *__restrict__ dq, int ld_dq, T *__restrict__ dkv, int ld_dkv, int H,
-                                                                 float sqrt_dk) {
+                                                                 float sqrt_dk, const int32_t *__restrict__ q_rows, int S_arg, float rate,
+                                                                 uint64_t seed) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int HD = DH / 2;
     float *sQ = reinterpret_cast<float *>(smem);
@@ -207,12 +229,15 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
     float *sDelta = sLse + MQ;
     float *sDS = sDelta + MQ;
     T *sK = reinterpret_cast<T *>(sDS + MQ * MQ_KB);
+    int32_t *sPos = reinterpret_cast<int32_t *>(sK + MQ_KB * DH);      // (DROP only) the chunk's query positions
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, kl = wave * 32 + (lane & 31);
     const int b = blockIdx.x / H, h = blockIdx.x % H, dm = H * DH;
     const int64_t tok0 = cu[b];
     const int S = cu[b + 1] - cu[b];
     const int r0 = moff[b], M = moff[b + 1] - moff[b];
+    const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
+    const float inv_keep = DROP ? 1.0f / (1.0f - rate) : 1.0f;
     if (M <= 0) {     // no query reads this sequence's keys in this layer: their gradient is zero
         for (int c = tid; c < S * (DH / 8); c += MQ_THREADS) {
             const int row = c / (DH / 8), part = c % (DH / 8);
@@ -261,6 +286,7 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
                 if (part == 0) {
                     sDelta[m] = pd;
                     sLse[m] = m < mq ? lse[(int64_t)(r0 + mc + m) * H + h] : INFINITY;     // p = exp(s - inf) = 0 for the zero rows
+                    if (DROP) sPos[m] = m < mq ? q_rows[r0 + mc + m] - (int)tok0 : 0;
                 }
             }
             __syncthreads();
@@ -273,7 +299,15 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
                 float p = 0.f, ds = 0.f;
                 if (live && !pad) {                           // a padded key has p == 0 exactly (exp(-1e9 - lse))
                     p = expf(sc / sqrt_dk - sLse[m]);
-                    ds = p * (dp - sDelta[m]);
+                    if (DROP) {
+                        // dS = P o (keep / (1 - rate) * dP~ - delta) with the undropped P; dV takes the dropped, rescaled P~
+                        const uint64_t drow = (uint64_t)blockIdx.x * S_arg + (uint32_t)sPos[m];
+                        const bool kp = (b4c_attn_keep4(seed, b4c_attn_ctr(drow, j, S_arg), thr) >> (j & 3)) & 1u;
+                        ds = p * ((kp ? dp * inv_keep : 0.f) - sDelta[m]);
+                        p = kp ? p * inv_keep : 0.f;
+                    } else {
+                        ds = p * (dp - sDelta[m]);
+                    }
                 }
 #pragma unroll
                 for (int d = 0; d < HD; d += 4) {
@@ -357,12 +391,13 @@ __device__ __forceinline__ bf16x8 mq_frag_tr(const char *p, int second_off) {
 }
 
 #define MQ_WAVES 4
-template <int DH, bool HAS_PAD>
+template <int DH, bool HAS_PAD, bool DROP>
 __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(const bf16_t *__restrict__ q, int ld_q, const bf16_t *__restrict__ kv,
                                                                          int ld_kv, const uint8_t *__restrict__ key_pad,
                                                                          const int32_t *__restrict__ cu, const int32_t *__restrict__ moff,
                                                                          bf16_t *__restrict__ o, int ld_o, float *__restrict__ lse, int H,
-                                                                         int n_items, float scale) {
+                                                                         int n_items, float scale, const int32_t *__restrict__ q_rows,
+                                                                         int S_arg, float rate, uint64_t seed) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KSTR = DH * 2 + 16;
     constexpr int NKS = DH / 16, NDT = DH / 32, CH = DH / 8, VC = 32 * CH / 64;
@@ -379,9 +414,13 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
     const float scale2 = scale * 1.4426950408889634f;
     const bf16_t *kbase = kv + tok0 * ld_kv + hh * DH;
     const bf16_t *vbase = kbase + dm;
+    const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
     for (int q0 = 0; q0 < M; q0 += 32) {
         const int qrow = q0 + r;
         const bool qvalid = qrow < M;
+        // (DROP) the lane part of the hash counter: this lane's query position times S4 / 4
+        uint32_t dq = 0;
+        if (DROP) { if (qvalid) dq = (uint32_t)(q_rows[r0 + qrow] - (int)tok0) * (b4c_attn_s4(S_arg) >> 2); }
         bf16x8 qf[NKS];
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
@@ -467,6 +506,16 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
                 acc[t] = __builtin_amdgcn_exp2f(acc[t] - mref);
                 l += acc[t];
             }
+            if (DROP) {
+                // l keeps the undropped sum; the dropped probabilities only lose their place in P V (1 / (1 - rate) joins the
+                // final 1 / l).  Registers 4 tq .. 4 tq + 3 are the keys kt*32 + 8 tq + 4 hf + {0..3} of this lane's query: one hash.
+#pragma unroll
+                for (int tq = 0; tq < 4; ++tq) {
+                    const uint32_t kb = b4c_attn_keep4(seed, attn_ctr_base(item, S_arg) + (dq + (uint32_t)(kt * 8 + 2 * tq + hf)), thr);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[4 * tq + j] = ((kb >> j) & 1u) ? acc[4 * tq + j] : 0.f;
+                }
+            }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this tile's V rows are in LDS (written by the wave's lanes)
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -486,7 +535,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
         }
         l += __shfl_xor(l, 32);
         if (qvalid) {
-            const float inv = 1.0f / l;
+            const float inv = DROP ? (1.0f / (1.0f - rate)) / l : 1.0f / l;
             bf16_t *orow = o + (int64_t)(r0 + qrow) * ld_o + hh * DH;
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt)
@@ -509,7 +558,8 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
 //   accumulator registers; dS crosses LDS once for dQ^T += K^T dS^T (query on the lane: dQ stays in registers over the key
 //   tiles).  dK / dV of a tile leave as 8-byte pieces of their rows.  More than 32 query rows: further passes that add to
 //   the dK / dV rows already written.
-// LDS per wave: sQ | sG [32][KSTR] (the query tile and its dO), sK [32][KSTR] (current key tile), sDS [32][TSTR], lse2 / delta.
+// LDS per wave: sQ | sG [32][KSTR] (the query tile and its dO), sK [32][KSTR] (current key tile), sDS [32][TSTR], lse2 / delta;
+// DROP: the tile's 32 query positions behind them.
 // ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bf16x8 mq_frag_2x8B(const char *p0, const char *p1) {
     typedef __attribute__((ext_vector_type(2))) unsigned u32x2v;
@@ -519,18 +569,36 @@ __device__ __forceinline__ bf16x8 mq_frag_2x8B(const char *p0, const char *p1) {
     return __builtin_bit_cast(bf16x8, w);
 }
 
-template <int DH, bool HAS_PAD>
+// Keep bits of one 32 x 32 score tile of the backward (key on the lane, query on the accumulator rows; bit t = register t): the quad
+// exchange of attn_mfma.hip's attn_keep_tile_bwd, with the query of tile row i at the position pos[i] (LDS) instead of q0 + i.
+// base = attn_ctr_base(item, S_arg), k_tile = first key of the tile.  EXEC must be full.
+__device__ __forceinline__ uint32_t mq_keep_tile_bwd(uint64_t seed, uint64_t base, int S_arg, const int32_t *pos, int k_tile, uint32_t thr, int r, int hf) {
+    const int c = r & 3;
+    const uint32_t s4q = b4c_attn_s4(S_arg) >> 2, kq = (uint32_t)(k_tile + (r & ~3)) >> 2;
+    uint32_t mk = 0;
+#pragma unroll
+    for (int tq = 0; tq < 4; ++tq)
+        mk |= b4c_attn_keep4(seed, base + ((uint32_t)pos[c + 8 * tq + 4 * hf] * s4q + kq), thr) << (4 * tq);
+    uint32_t km = ((quad_bcast<0>(mk) >> c) & 0x1111u);
+    km |= ((quad_bcast<1>(mk) >> c) & 0x1111u) << 1;
+    km |= ((quad_bcast<2>(mk) >> c) & 0x1111u) << 2;
+    km |= ((quad_bcast<3>(mk) >> c) & 0x1111u) << 3;
+    return km;
+}
+
+template <int DH, bool HAS_PAD, bool DROP>
 __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(const bf16_t *__restrict__ q, int ld_q, const bf16_t *__restrict__ kv,
                                                                          int ld_kv, const uint8_t *__restrict__ key_pad,
                                                                          const int32_t *__restrict__ cu, const int32_t *__restrict__ moff,
                                                                          const bf16_t *__restrict__ o, int ld_o, const bf16_t *__restrict__ d_o,
                                                                          int ld_do, const float *__restrict__ lse, bf16_t *__restrict__ dq,
                                                                          int ld_dq, bf16_t *__restrict__ dkv, int ld_dkv, int H, int n_items,
-                                                                         float scale) {
+                                                                         float scale, const int32_t *__restrict__ q_rows, int S_arg,
+                                                                         float rate, uint64_t seed) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KSTR = DH * 2 + 16, TSTR = 32 * 2 + 16;
     constexpr int NKS = DH / 16, NDT = DH / 32, CH = DH / 8, VC = 32 * CH / 64;
-    constexpr int WBYTES = 3 * 32 * KSTR + 32 * TSTR + 2 * 32 * 4;
+    constexpr int WBYTES = 3 * 32 * KSTR + 32 * TSTR + (DROP ? 3 : 2) * 32 * 4;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31, hf = lane >> 5, li = lane & 15, g = lane >> 4;
     char *sQ = smem + wave * WBYTES;
     char *sG = sQ + 32 * KSTR;
@@ -538,12 +606,15 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
     char *sDS = sK + 32 * KSTR;
     float *sLse = reinterpret_cast<float *>(sDS + 32 * TSTR);
     float *sDelta = sLse + 32;
+    int32_t *sPos = reinterpret_cast<int32_t *>(sDelta + 32);   // (DROP only)
     const int item = blockIdx.x * MQ_WAVES + wave;
     if (item >= n_items) return;                              // (no workgroup barrier anywhere below)
     const int b = item / H, hh = item % H, dm = H * DH;
     const int64_t tok0 = cu[b];
     const int S = cu[b + 1] - cu[b];
     const int r0 = moff[b], M = moff[b + 1] - moff[b];
+    const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
+    const float inv_keep = DROP ? 1.0f / (1.0f - rate) : 1.0f;
     if (S <= 0) return;
     bf16_t *dkbase = dkv + tok0 * ld_dkv + hh * DH;
     if (M <= 0) {                                             // no query reads this sequence's keys in this layer
@@ -587,6 +658,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
                 if (part == 0) sDelta[row] = pd;
             }
             if (lane < 32) sLse[lane] = (q0 + lane < M) ? lse[(int64_t)(r0 + q0 + lane) * H + hh] * 1.4426950408889634f : INFINITY;
+            if (DROP) { if (lane < 32) sPos[lane] = (q0 + lane < M) ? q_rows[r0 + q0 + lane] - (int)tok0 : 0; }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
@@ -642,11 +714,19 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
                 pa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ga[ks], vcur[ks], pa, 0, 0, 0);
             }
             float pv[16], dsv[16];
+            // dropout: dV takes the dropped, rescaled P~; dS = P o (keep / (1 - rate) * dP~ - delta) with the undropped P
+            const uint32_t km = DROP ? mq_keep_tile_bwd(seed, attn_ctr_base(item, S_arg), S_arg, sPos, kt * 32, thr, r, hf) : 0u;
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[t], scale2, madd - lq[t]));
-                pv[t] = p;
-                dsv[t] = p * (pa[t] - dl[t]);
+                if (DROP) {
+                    const bool kp = (km >> t) & 1u;
+                    pv[t] = kp ? p * inv_keep : 0.f;
+                    dsv[t] = p * ((kp ? pa[t] * inv_keep : 0.f) - dl[t]);
+                } else {
+                    pv[t] = p;
+                    dsv[t] = p * (pa[t] - dl[t]);
+                }
                 *reinterpret_cast<bf16_t *>(sDS + mq_rowmap(t, hf) * TSTR + r * 2) = (bf16_t)dsv[t];
             }
             // dV^T = dO^T P, dK^T = Q^T dS (key on the lane), from the accumulator registers
@@ -723,7 +803,9 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
 }
 
 static size_t mq_fwd_lds(int SP, int dh, int esz) { return (size_t)MQ * dh * 4 + (size_t)MQ * SP * 4 + (size_t)MQ_KB * dh * esz; }
-static size_t mq_bwd_lds(int dh, int esz) { return (size_t)2 * MQ * dh * 4 + 2 * MQ * 4 + (size_t)MQ * MQ_KB * 4 + (size_t)MQ_KB * dh * esz; }
+static size_t mq_bwd_lds(int dh, int esz, bool drop) {
+    return (size_t)2 * MQ * dh * 4 + 2 * MQ * 4 + (size_t)MQ * MQ_KB * 4 + (size_t)MQ_KB * dh * esz + (drop ? MQ * 4 : 0);
+}
 
 template <typename Kern> static void mq_allow_lds(Kern k, size_t bytes) {
     (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
@@ -740,12 +822,26 @@ static int mq_check(const char *who, const void *q, const void *kv, const int32_
     return B4C_OK;
 }
 
-extern "C" int b4c_attn_mq_fwd(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
-                               const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype,
-                               void *stream) {
-    const int rc = mq_check("attn_mq_fwd", q, kv, cu_seqlens, q_offsets, ld_q, ld_kv, B, max_len, H, dh, dtype);
+// the *_drop entry points: a rate in [0, 1) (a NaN fails the comparison too), and the query rows' token rows when it is > 0
+static int mq_check_drop(const char *who, const int32_t *q_rows, float rate) {
+    B4C_REQUIRE(rate >= 0.f && rate < 1.f, "%s: dropout rate %g outside [0, 1)", who, (double)rate);
+    B4C_REQUIRE(rate == 0.f || q_rows, "%s: dropout rate %g needs q_rows", who, (double)rate);
+    return B4C_OK;
+}
+
+// rate == 0 launches the DROP = false instantiations: the kernels of the entry points without dropout
+#define MQ_BY_RATE(LAUNCH, ...)                            \
+    do {                                                   \
+        if (rate == 0.f) LAUNCH(__VA_ARGS__, false);       \
+        else LAUNCH(__VA_ARGS__, true);                    \
+    } while (0)
+
+static int mq_fwd_any(const char *who, const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                      const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype, void *stream,
+                      const int32_t *q_rows, float rate, uint64_t seed) {
+    const int rc = mq_check(who, q, kv, cu_seqlens, q_offsets, ld_q, ld_kv, B, max_len, H, dh, dtype);
     if (rc != B4C_OK) return rc;
-    B4C_REQUIRE(o && lse && ld_o >= H * dh && ld_o % 8 == 0, "attn_mq_fwd: output");
+    B4C_REQUIRE(o && lse && ld_o >= H * dh && ld_o % 8 == 0, "%s: output", who);
     const int SP = (max_len + 63) / 64 * 64;
     const float sq = sqrtf((float)dh);
     hipStream_t st = (hipStream_t)stream;
@@ -753,61 +849,96 @@ extern "C" int b4c_attn_mq_fwd(const void *q, int ld_q, const void *kv, int ld_k
         const int n_items = B * H;
         const size_t shm_m = (size_t)MQ_WAVES * 2 * 32 * (dh * 2 + 16);
         const int grid = (n_items + MQ_WAVES - 1) / MQ_WAVES;
-#define MQ_MFMA(DHH, PP)                                                                                                             \
-    attn_mq_fwd_mfma_kernel<DHH, PP><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens, \
-                                                                       q_offsets, (bf16_t *)o, ld_o, lse, H, n_items, 1.0f / sq)
-        if (dh == 64) { if (key_pad) MQ_MFMA(64, true); else MQ_MFMA(64, false); }
-        else { if (key_pad) MQ_MFMA(32, true); else MQ_MFMA(32, false); }
+#define MQ_MFMA(DHH, PP, DR)                                                                                                         \
+    attn_mq_fwd_mfma_kernel<DHH, PP, DR><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens, \
+                                                                       q_offsets, (bf16_t *)o, ld_o, lse, H, n_items, 1.0f / sq, q_rows, max_len, rate, seed)
+        if (dh == 64) { if (key_pad) MQ_BY_RATE(MQ_MFMA, 64, true); else MQ_BY_RATE(MQ_MFMA, 64, false); }
+        else { if (key_pad) MQ_BY_RATE(MQ_MFMA, 32, true); else MQ_BY_RATE(MQ_MFMA, 32, false); }
 #undef MQ_MFMA
-        return b4c_check_launch("attn_mq_fwd (mfma)");
+        return b4c_check_launch(who);
     }
     const size_t shm = mq_fwd_lds(SP, dh, sizeof(float));
-    B4C_REQUIRE(shm <= 160 * 1024, "attn_mq_fwd: max_len %d needs %zu bytes of LDS", max_len, shm);
-#define MQ_FWD(TT, DHH)                                                                                                              \
+    B4C_REQUIRE(shm <= 160 * 1024, "%s: max_len %d needs %zu bytes of LDS", who, max_len, shm);
+#define MQ_FWD(TT, DHH, DR)                                                                                                          \
     do {                                                                                                                             \
-        mq_allow_lds(attn_mq_fwd_kernel<TT, DHH>, shm);                                                                              \
-        attn_mq_fwd_kernel<TT, DHH><<<B * H, MQ_THREADS, shm, st>>>((const TT *)q, ld_q, (const TT *)kv, ld_kv, key_pad, cu_seqlens, q_offsets, \
-                                                             (TT *)o, ld_o, lse, H, SP, sq);                                        \
+        mq_allow_lds(attn_mq_fwd_kernel<TT, DHH, DR>, shm);                                                                          \
+        attn_mq_fwd_kernel<TT, DHH, DR><<<B * H, MQ_THREADS, shm, st>>>((const TT *)q, ld_q, (const TT *)kv, ld_kv, key_pad, cu_seqlens, q_offsets, \
+                                                                 (TT *)o, ld_o, lse, H, SP, sq, q_rows, max_len, rate, seed);        \
     } while (0)
-    if (dh == 64) MQ_FWD(float, 64); else MQ_FWD(float, 32);
+    if (dh == 64) MQ_BY_RATE(MQ_FWD, float, 64); else MQ_BY_RATE(MQ_FWD, float, 32);
 #undef MQ_FWD
-    return b4c_check_launch("attn_mq_fwd");
+    return b4c_check_launch(who);
+}
+
+extern "C" int b4c_attn_mq_fwd(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                               const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype,
+                               void *stream) {
+    return mq_fwd_any("attn_mq_fwd", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, lse, B, max_len, H, dh, dtype, stream,
+                      nullptr, 0.f, 0);
+}
+
+extern "C" int b4c_attn_mq_fwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                                    const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype,
+                                    void *stream, const int32_t *q_rows, float dropout_rate, uint64_t seed) {
+    const int rc = mq_check_drop("attn_mq_fwd_drop", q_rows, dropout_rate);
+    if (rc != B4C_OK) return rc;
+    return mq_fwd_any("attn_mq_fwd_drop", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, lse, B, max_len, H, dh, dtype, stream,
+                      q_rows, dropout_rate, seed);
+}
+
+static int mq_bwd_any(const char *who, const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                      const int32_t *q_offsets, const void *o, int ld_o, const void *d_o, int ld_do, const float *lse, void *dq, int ld_dq,
+                      void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream, const int32_t *q_rows, float rate,
+                      uint64_t seed) {
+    const int rc = mq_check(who, q, kv, cu_seqlens, q_offsets, ld_q, ld_kv, B, max_len, H, dh, dtype);
+    if (rc != B4C_OK) return rc;
+    B4C_REQUIRE(o && d_o && lse && dq && dkv, "%s: null pointer", who);
+    B4C_REQUIRE(ld_o >= H * dh && ld_do >= H * dh && ld_dq >= H * dh && ld_dkv >= 2 * H * dh && ld_o % 8 == 0 && ld_do % 8 == 0 &&
+                    ld_dq % 8 == 0 && ld_dkv % 8 == 0, "%s: pitches", who);
+    const float sq = sqrtf((float)dh);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == B4C_BF16) {      // matrix-core form, one wave per (sequence, head)
+        const int n_items = B * H, kstr = dh * 2 + 16;
+        const int grid = (n_items + MQ_WAVES - 1) / MQ_WAVES;
+#define MQ_MFMA_B(DHH, PP, DR)                                                                                                       \
+    do {                                                                                                                             \
+        const size_t shm_m = (size_t)MQ_WAVES * (3 * 32 * kstr + 32 * (32 * 2 + 16) + (DR ? 3 : 2) * 32 * 4);                        \
+        mq_allow_lds(attn_mq_bwd_mfma_kernel<DHH, PP, DR>, shm_m);                                                                   \
+        attn_mq_bwd_mfma_kernel<DHH, PP, DR><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens, \
+            q_offsets, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dq, ld_dq, (bf16_t *)dkv, ld_dkv, H, n_items, 1.0f / sq, \
+            q_rows, max_len, rate, seed);                                                                                            \
+    } while (0)
+        if (dh == 64) { if (key_pad) MQ_BY_RATE(MQ_MFMA_B, 64, true); else MQ_BY_RATE(MQ_MFMA_B, 64, false); }
+        else { if (key_pad) MQ_BY_RATE(MQ_MFMA_B, 32, true); else MQ_BY_RATE(MQ_MFMA_B, 32, false); }
+#undef MQ_MFMA_B
+        return b4c_check_launch(who);
+    }
+#define MQ_BWD(TT, DHH, DR)                                                                                                          \
+    do {                                                                                                                             \
+        const size_t shm = mq_bwd_lds(dh, sizeof(float), DR);                                                                        \
+        mq_allow_lds(attn_mq_bwd_kernel<TT, DHH, DR>, shm);                                                                          \
+        attn_mq_bwd_kernel<TT, DHH, DR><<<B * H, MQ_THREADS, shm, st>>>((const TT *)q, ld_q, (const TT *)kv, ld_kv, key_pad, cu_seqlens, q_offsets, \
+                                                                 (const TT *)o, ld_o, (const TT *)d_o, ld_do, lse, (TT *)dq, ld_dq,  \
+                                                                 (TT *)dkv, ld_dkv, H, sq, q_rows, max_len, rate, seed);             \
+    } while (0)
+    if (dh == 64) MQ_BY_RATE(MQ_BWD, float, 64); else MQ_BY_RATE(MQ_BWD, float, 32);
+#undef MQ_BWD
+    return b4c_check_launch(who);
 }
 
 extern "C" int b4c_attn_mq_bwd(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
                                const int32_t *q_offsets, const void *o, int ld_o, const void *d_o, int ld_do, const float *lse,
                                void *dq, int ld_dq, void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream) {
-    const int rc = mq_check("attn_mq_bwd", q, kv, cu_seqlens, q_offsets, ld_q, ld_kv, B, max_len, H, dh, dtype);
+    return mq_bwd_any("attn_mq_bwd", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, d_o, ld_do, lse, dq, ld_dq, dkv, ld_dkv, B,
+                      max_len, H, dh, dtype, stream, nullptr, 0.f, 0);
+}
+
+extern "C" int b4c_attn_mq_bwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                                    const int32_t *q_offsets, const void *o, int ld_o, const void *d_o, int ld_do, const float *lse,
+                                    void *dq, int ld_dq, void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream,
+                                    const int32_t *q_rows, float dropout_rate, uint64_t seed) {
+    const int rc = mq_check_drop("attn_mq_bwd_drop", q_rows, dropout_rate);
     if (rc != B4C_OK) return rc;
-    B4C_REQUIRE(o && d_o && lse && dq && dkv, "attn_mq_bwd: null pointer");
-    B4C_REQUIRE(ld_o >= H * dh && ld_do >= H * dh && ld_dq >= H * dh && ld_dkv >= 2 * H * dh && ld_o % 8 == 0 && ld_do % 8 == 0 &&
-                    ld_dq % 8 == 0 && ld_dkv % 8 == 0, "attn_mq_bwd: pitches");
-    const float sq = sqrtf((float)dh);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == B4C_BF16) {      // matrix-core form, one wave per (sequence, head)
-        const int n_items = B * H, kstr = dh * 2 + 16;
-        const size_t shm_m = (size_t)MQ_WAVES * (3 * 32 * kstr + 32 * (32 * 2 + 16) + 2 * 32 * 4);
-        const int grid = (n_items + MQ_WAVES - 1) / MQ_WAVES;
-#define MQ_MFMA_B(DHH, PP)                                                                                                           \
-    do {                                                                                                                             \
-        mq_allow_lds(attn_mq_bwd_mfma_kernel<DHH, PP>, shm_m);                                                                       \
-        attn_mq_bwd_mfma_kernel<DHH, PP><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens, \
-            q_offsets, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dq, ld_dq, (bf16_t *)dkv, ld_dkv, H, n_items, 1.0f / sq); \
-    } while (0)
-        if (dh == 64) { if (key_pad) MQ_MFMA_B(64, true); else MQ_MFMA_B(64, false); }
-        else { if (key_pad) MQ_MFMA_B(32, true); else MQ_MFMA_B(32, false); }
-#undef MQ_MFMA_B
-        return b4c_check_launch("attn_mq_bwd (mfma)");
-    }
-    const size_t shm = mq_bwd_lds(dh, sizeof(float));
-#define MQ_BWD(TT, DHH)                                                                                                              \
-    do {                                                                                                                             \
-        mq_allow_lds(attn_mq_bwd_kernel<TT, DHH>, shm);                                                                              \
-        attn_mq_bwd_kernel<TT, DHH><<<B * H, MQ_THREADS, shm, st>>>((const TT *)q, ld_q, (const TT *)kv, ld_kv, key_pad, cu_seqlens, q_offsets, \
-                                                             (const TT *)o, ld_o, (const TT *)d_o, ld_do, lse, (TT *)dq, ld_dq,      \
-                                                             (TT *)dkv, ld_dkv, H, sq);                                              \
-    } while (0)
-    if (dh == 64) MQ_BWD(float, 64); else MQ_BWD(float, 32);
-#undef MQ_BWD
-    return b4c_check_launch("attn_mq_bwd");
+    return mq_bwd_any("attn_mq_bwd_drop", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, d_o, ld_do, lse, dq, ld_dq, dkv, ld_dkv,
+                      B, max_len, H, dh, dtype, stream, q_rows, dropout_rate, seed);
 }

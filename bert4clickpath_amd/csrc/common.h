@@ -155,6 +155,12 @@ __host__ __device__ __forceinline__ uint32_t b4c_attn_keep4(uint64_t seed, uint6
     for (int j = 0; j < 4; ++j) m |= (((uint32_t)(h >> (16 * j)) & 0xFFFFu) >= thr ? 1u : 0u) << j;
     return m;
 }
+// (device) the workgroup-uniform part of b4c_attn_ctr for item bh = b*H + h, and the value of lane C of every quad (DPP quad
+// broadcast; EXEC must be full): what the matrix-core attention kernels build their keep bits from
+__device__ __forceinline__ uint64_t attn_ctr_base(int bh, int S_arg) { return (uint64_t)bh * S_arg * (b4c_attn_s4(S_arg) >> 2); }
+template <int C> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, C * 0x55, 0xf, 0xf, true);
+}
 
 // ---- wave / block reductions ----
 __device__ __forceinline__ float wave_sum(float v) {

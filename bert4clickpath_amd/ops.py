@@ -767,9 +767,19 @@ def _tied_table_steps_whole(table):
         lz.all_rows = True
 
 
-def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None):
+def _attn_mq_drop(q_rows, rate):
+    rate = _attn_rate(rate)
+    if rate > 0 and q_rows is None:
+        raise ValueError('attention dropout in the masked-query kernels needs q_rows (the token row of each query row)')
+    return rate
+
+
+def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None, q_rows=None, rate=0.0, seed=0):
     """Attention of a few query rows per sequence against all of its keys (b4c_attn_mq_fwd).
-    q [R, H*dh]; kv [T, 2*H*dh] (k | v); cu [B+1] token offsets; moff [B+1] query-row offsets -> (o [R, H*dh], lse [R, H])."""
+    q [R, H*dh]; kv [T, 2*H*dh] (k | v); cu [B+1] token offsets; moff [B+1] query-row offsets -> (o [R, H*dh], lse [R, H]).
+    rate > 0 (b4c_attn_mq_fwd_drop): dropout on the attention probabilities with the masks attn_fwd(..., rate, seed) draws for the
+    token rows q_rows [R] (int32; an unused row holds -1): b4c_attn_keep(seed, b, h, q_rows[r] - cu[b], k, H, max_len, rate)."""
+    rate = _attn_mq_drop(q_rows, rate)
     R = q.shape[0]
     # rows outside every [moff[b], moff[b+1]) range (the unused tail of the sync-free form) are not written: zeros, not garbage
     o = zeros(R, H * dh, dtype=q.dtype, device=q.device)
@@ -779,13 +789,20 @@ def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None):
     es = q.element_size()
     # algorithmic work: every query row against the keys of its own sequence (host hint; R x max_len is an upper bound)
     with _record('attn_mq_fwd', kv.shape[0] * 2 * H * dh * es + 2 * R * H * dh * es, 4 * rec_hints.get('sum_q_len', R * max_len) * H * dh):
-        L.check(L.lib().b4c_attn_mq_fwd(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
-                                        _p(lse), B, max_len, H, dh, dt_code(q.dtype), _st()), 'attn_mq_fwd')
+        if rate > 0:
+            L.check(L.lib().b4c_attn_mq_fwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o),
+                                                 o.stride(0), _p(lse), B, max_len, H, dh, dt_code(q.dtype), _st(), _p(q_rows), rate,
+                                                 seed), 'attn_mq_fwd_drop')
+        else:
+            L.check(L.lib().b4c_attn_mq_fwd(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
+                                            _p(lse), B, max_len, H, dh, dt_code(q.dtype), _st()), 'attn_mq_fwd')
     return o, lse
 
 
-def attn_mq_bwd(q, kv, cu, moff, o, d_o, lse, B, max_len, H, dh, key_pad=None):
-    """-> (dq [R, H*dh], dkv [T, 2*H*dh]); every token row of dkv is written (zeros where no query reads the sequence)."""
+def attn_mq_bwd(q, kv, cu, moff, o, d_o, lse, B, max_len, H, dh, key_pad=None, q_rows=None, rate=0.0, seed=0):
+    """-> (dq [R, H*dh], dkv [T, 2*H*dh]); every token row of dkv is written (zeros where no query reads the sequence).
+    q_rows, rate, seed: those of the forward (attn_mq_fwd); o is the forward's output, dropped probabilities included."""
+    rate = _attn_mq_drop(q_rows, rate)
     R = q.shape[0]
     dq = zeros(q.shape[0], q.shape[1], dtype=q.dtype, device=q.device)
     if R == 0:                 # no query row anywhere: no key or value receives a gradient from this layer
@@ -795,9 +812,15 @@ def attn_mq_bwd(q, kv, cu, moff, o, d_o, lse, B, max_len, H, dh, key_pad=None):
         return dq, dkv
     es = q.element_size()
     with _record('attn_mq_bwd', kv.shape[0] * 4 * H * dh * es + 4 * R * H * dh * es, 10 * rec_hints.get('sum_q_len', R * max_len) * H * dh):
-        L.check(L.lib().b4c_attn_mq_bwd(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
-                                        _p(d_o), d_o.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dkv), dkv.stride(0), B, max_len,
-                                        H, dh, dt_code(q.dtype), _st()), 'attn_mq_bwd')
+        if rate > 0:
+            L.check(L.lib().b4c_attn_mq_bwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o),
+                                                 o.stride(0), _p(d_o), d_o.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dkv),
+                                                 dkv.stride(0), B, max_len, H, dh, dt_code(q.dtype), _st(), _p(q_rows), rate, seed),
+                    'attn_mq_bwd_drop')
+        else:
+            L.check(L.lib().b4c_attn_mq_bwd(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
+                                            _p(d_o), d_o.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dkv), dkv.stride(0), B, max_len,
+                                            H, dh, dt_code(q.dtype), _st()), 'attn_mq_bwd')
     return dq, dkv
 
 
@@ -1803,6 +1826,10 @@ def rows_add_(dst, idx, src):
 
 # Cloze path: the last encoder layer runs for the [MASK] rows only (MQAttnBlockFn); B4C_MQ_LAST_LAYER=0 computes the full layer
 mq_last_layer = os.environ.get('B4C_MQ_LAST_LAYER', '1') != '0'
+# ... also in training with attention_dropout_rate > 0: the masked-query kernels draw the full layer's masks for their rows
+# (b4c_attn_mq_*_drop).  Off (B4C_MQ_ATTN_DROPOUT=1 switches it on): such a pass takes the full last layer and gathers its rows,
+# Encoder.rows_supported's answer; Encoder.rows_route is the route with this switch applied.
+mq_attn_dropout = os.environ.get('B4C_MQ_ATTN_DROPOUT', '0') == '1'
 
 
 class MQAttnBlockFn(torch.autograd.Function):
@@ -1810,11 +1837,12 @@ class MQAttnBlockFn(torch.autograd.Function):
     Every other row of that layer's output is never read on the Cloze path (clickstream_transformer.py:281-295 keeps the
     [MASK] rows); keys and values still come from every token.
       x [T, d] (all tokens), midx [R] int32 (token row of each query row, -1 = unused row), moff [B+1] (query rows of
-      sequence b), cu [B+1] (its token rows), key_pad [T] or None  ->  out1_m [R, d]."""
+      sequence b), cu [B+1] (its token rows), key_pad [T] or None  ->  out1_m [R, d].
+    attn_rate > 0: dropout on the attention probabilities, the masks AttnBlockFn draws with attn_seed for the rows midx."""
 
     @staticmethod
     def forward(ctx, x, midx, moff, cu, key_pad, wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta, pk_qkv, pk_o, B, max_len, H, rate, seed,
-                training):
+                training, attn_rate=0.0, attn_seed=0):
         T_tok, d = x.shape
         dh = d // H
         R = midx.shape[0]
@@ -1823,7 +1851,7 @@ class MQAttnBlockFn(torch.autograd.Function):
         kv = gemm_nt(x, wt_qkv[d:3 * d], 2 * d, b_qkv[d:3 * d])            # K | V of every token
         x_m = gather_rows(x, midx, R)
         q_m = gemm_nt(x_m, wt_qkv[:d], d, b_qkv[:d])
-        o_m, lse = attn_mq_fwd(q_m, kv, cu, moff, B, max_len, H, dh, key_pad)
+        o_m, lse = attn_mq_fwd(q_m, kv, cu, moff, B, max_len, H, dh, key_pad, midx, attn_rate, attn_seed)
         if gemm_ln_supported(o_m, d):
             z, out, stats = gemm_nt_add_ln(o_m, wt_o, b_o, x_m, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
                                            save=training)
@@ -1834,7 +1862,7 @@ class MQAttnBlockFn(torch.autograd.Function):
         if training:
             ctx.save_for_backward(x, x_m, midx, moff, cu, key_pad, q_m, kv, o_m, lse, z, stats, gamma)
             ctx.pk = (pk_qkv, pk_o)
-            ctx.dims = (B, max_len, H, dh, rate, seed)
+            ctx.dims = (B, max_len, H, dh, rate, seed, attn_rate, attn_seed)
             ctx.params = (wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta)
         return out
 
@@ -1842,7 +1870,7 @@ class MQAttnBlockFn(torch.autograd.Function):
     def backward(ctx, dout):
         x, x_m, midx, moff, cu, key_pad, q_m, kv, o_m, lse, z, stats, gamma = ctx.saved_tensors
         pk_qkv, pk_o = ctx.pk
-        B, max_len, H, dh, rate, seed = ctx.dims
+        B, max_len, H, dh, rate, seed, attn_rate, attn_seed = ctx.dims
         wq, bq, wk, bk, wv, bv, wo, bo, gam, bet = ctx.params
         d = H * dh
         actx, sinks = grad_sinks(*ctx.params)
@@ -1857,7 +1885,7 @@ class MQAttnBlockFn(torch.autograd.Function):
             dz, dy, _, _ = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, into=(ggam, gbet))
             queue_dw(actx, o_m, dy, d, d, [gwo], [gbo], (wo, bo))
             d_o = gemm_nt(dy, wc_o, d)
-        dq, dkv = attn_mq_bwd(q_m, kv, cu, moff, o_m, d_o, lse, B, max_len, H, dh, key_pad)
+        dq, dkv = attn_mq_bwd(q_m, kv, cu, moff, o_m, d_o, lse, B, max_len, H, dh, key_pad, midx, attn_rate, attn_seed)
         queue_dw(actx, x_m, dq, d, d, [gwq], [gbq], (wq, bq))
         flush_pending_dw(actx)                  # (the query-row problems have R rows, the key / value problem T)
         dx_m = gemm_nt(dq, wc_qkv[:, :d], d, residual=dz, out_dtype=torch.float32)      # query rows: through Wq + the residual branch (kept in fp32 until it joins dx)

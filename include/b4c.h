@@ -719,8 +719,13 @@ int b4c_adamw_rows(float *p, float *g, float *m, float *v, int32_t *stamp, const
  * b4c_attn_keep is that rule on the host (1 = kept), so tests and other hosts regenerate the masks without a GPU.
  * The four entry points are b4c_attn_fwd, b4c_attn_bwd_ws, b4c_attn_fwd_varlen and b4c_attn_bwd_varlen with (dropout_rate, seed)
  * appended; the workspace is b4c_attn_bwd_workspace_bytes'.  dropout_rate == 0 launches the very kernels of those entry points;
- * a rate outside [0, 1) is B4C_EINVAL.  b4c_attn_weights keeps returning the undropped softmax; the masked-query kernels
- * (b4c_attn_mq_*) have no dropout. */
+ * a rate outside [0, 1) is B4C_EINVAL.  b4c_attn_weights keeps returning the undropped softmax.
+ * The masked-query kernels: b4c_attn_mq_fwd_drop / b4c_attn_mq_bwd_drop are b4c_attn_mq_fwd / _bwd with (q_rows, dropout_rate,
+ * seed) appended.  q_rows (int32 [R]) is the token row of each query row: the keep rule's q of query row r of sequence b is
+ * q_rows[r] - cu_seqlens[b] and S_arg is max_len, so with the same seed the masks are those the full layer's entry points draw
+ * for these rows, in the dense (cu_seqlens[b] = b*S) and the packed layout.  q_rows is read for the rows q_offsets names only (an
+ * unused row may hold -1) and no address depends on it.  dropout_rate == 0 launches the very kernels of b4c_attn_mq_fwd / _bwd and
+ * q_rows may be NULL; a rate outside [0, 1), or a rate > 0 with a NULL q_rows, is B4C_EINVAL. */
 int b4c_attn_keep(uint64_t seed, int b, int h, int q, int k, int H, int S_arg, float rate);
 int b4c_attn_fwd_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
                       int S, int H, int dh, int dtype, void *stream, float dropout_rate, uint64_t seed);
@@ -735,6 +740,13 @@ int b4c_attn_bwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad
                              int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv,
                              int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype,
                              void *stream, float dropout_rate, uint64_t seed);
+int b4c_attn_mq_fwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                         const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype,
+                         void *stream, const int32_t *q_rows, float dropout_rate, uint64_t seed);
+int b4c_attn_mq_bwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                         const int32_t *q_offsets, const void *o, int ld_o, const void *d_o, int ld_do, const float *lse,
+                         void *dq, int ld_dq, void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream,
+                         const int32_t *q_rows, float dropout_rate, uint64_t seed);
 
 #ifdef __cplusplus
 }

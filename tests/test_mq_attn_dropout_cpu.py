@@ -1,0 +1,132 @@
+"""Attention dropout in the masked-query last layer, the parts that need no GPU: the switch ops.mq_attn_dropout and the route it
+opens (Encoder.rows_route beside the unchanged Encoder.rows_supported), the seeds EncoderLayer.forward(rows=) draws and hands to
+the masked-query block, and the two entry points in the header."""
+import pytest
+import torch
+
+
+def _encoder(attn_rate):
+    from bert4clickpath_amd.clickstream_transformer import transformer as T
+    return T.Encoder(num_layers=2, d_model=64, num_heads=2, dff=32, dropout_rate=0.1, attention_dropout_rate=attn_rate)
+
+
+def test_the_switch_is_off_by_default():
+    import os
+    from bert4clickpath_amd import ops
+    if 'B4C_MQ_ATTN_DROPOUT' not in os.environ:
+        assert ops.mq_attn_dropout is False
+
+
+def test_rows_route_follows_the_switch_and_rows_supported_does_not(monkeypatch):
+    from bert4clickpath_amd import ops
+    enc, enc0, deep = _encoder(0.2), _encoder(0.0), None
+    from bert4clickpath_amd.clickstream_transformer import transformer as T
+    deep = T.Encoder(num_layers=1, d_model=64, num_heads=4, dff=32, dropout_rate=0.1, attention_dropout_rate=0.2)    # head depth 16
+    want_supported = {}
+    for on in (False, True):
+        monkeypatch.setattr(ops, 'mq_attn_dropout', on)
+        for name, e in (('rate', enc), ('rate0', enc0), ('dh16', deep)):
+            for training in (False, True):
+                got = e.rows_supported(None, training)
+                assert want_supported.setdefault((name, training), got) == got          # the same answer either way
+                if not on:
+                    assert e.rows_route(None, training) == got
+        assert enc.rows_route(None) == enc.rows_supported(None)
+    assert want_supported[('rate', True)] is False and want_supported[('rate', False)] is True
+    assert want_supported[('rate0', True)] is True and want_supported[('dh16', False)] is False
+    monkeypatch.setattr(ops, 'mq_attn_dropout', True)
+    assert enc.rows_route(None, True) is True and enc.rows_route(None, False) is True and enc0.rows_route(None, True) is True
+    assert deep.rows_route(None, True) is False and deep.rows_route(None, False) is False     # the shape conditions stay
+
+
+class _Stub:
+    def __init__(self):
+        self.draws = 0
+
+    def next(self):
+        self.draws += 1
+        return 1000 + self.draws
+
+
+def _layer_with_rows(monkeypatch, attn_rate, switch):
+    """EncoderLayer.forward(rows=) in training with the blocks stubbed as in test_attn_dropout_cpu.test_encoder_layer_seed_draws"""
+    from bert4clickpath_amd import ops
+    from bert4clickpath_amd.clickstream_transformer import transformer as T
+    stub = _Stub()
+    monkeypatch.setattr(T, 'dropout_seeds', stub)
+    monkeypatch.setattr(ops, 'mq_attn_dropout', switch)
+    seen = {}
+
+    class MQ:
+        @staticmethod
+        def apply(x2, midx, *a):
+            seen['mq'] = (midx,) + a
+            return x2[:midx.shape[0]]
+
+    class FFN:
+        @staticmethod
+        def apply(x2, *a):
+            seen['ffn'] = a
+            return x2
+    monkeypatch.setattr(ops, 'MQAttnBlockFn', MQ)
+    monkeypatch.setattr(ops, 'FFNBlockFn', FFN)
+    layer = T.EncoderLayer(32, 2, 64, 0.1, attention_dropout_rate=attn_rate)
+    midx = torch.tensor([1, 3, 7], dtype=torch.int32)
+    moff = torch.tensor([0, 2, 3], dtype=torch.int32)
+    return layer, stub, seen, (midx, moff)
+
+
+def test_rows_with_the_switch_on_draws_three_seeds_and_hands_the_third_down(monkeypatch):
+    layer, stub, seen, rows = _layer_with_rows(monkeypatch, 0.2, True)
+    out = layer(torch.zeros(2, 5, 32), training=True, mask=torch.zeros(2, 5, dtype=torch.uint8), rows=rows)
+    assert out.shape == (3, 32) and stub.draws == 3
+    a = seen['mq']
+    assert a[0] is rows[0] and a[1] is rows[1]                    # midx goes down as it came: the block's q_rows
+    assert (a[-2], a[-1]) == (0.2, 1003)                          # the third draw, taken after the two of the residual branches
+    assert a[-4] == 1001 and seen['ffn'][-3] == 1002              # s1, s2: as ever
+
+
+def test_rows_with_the_switch_off_raises_as_today(monkeypatch):
+    from bert4clickpath_amd._lib import B4CError
+    layer, stub, seen, rows = _layer_with_rows(monkeypatch, 0.2, False)
+    with pytest.raises(B4CError, match='no attention dropout'):
+        layer(torch.zeros(2, 5, 32), training=True, mask=torch.zeros(2, 5, dtype=torch.uint8), rows=rows)
+    assert 'mq' not in seen and stub.draws == 3                   # the draws come before the route, as today
+
+
+@pytest.mark.parametrize('switch', [False, True])
+@pytest.mark.parametrize('attn_rate,training,draws', [(0.0, True, 2), (0.2, False, 0)])
+def test_rows_at_rate_zero_is_unchanged(monkeypatch, switch, attn_rate, training, draws):
+    layer, stub, seen, rows = _layer_with_rows(monkeypatch, attn_rate, switch)
+    layer(torch.zeros(2, 5, 32), training=training, mask=torch.zeros(2, 5, dtype=torch.uint8), rows=rows)
+    assert stub.draws == draws
+    assert (seen['mq'][-2], seen['mq'][-1]) == (0.0, 0)
+
+
+def test_header_declares_the_entry_points_and_the_abi_stays_12():
+    from bert4clickpath_amd import _lib
+    assert _lib.ABI_VERSION == 12
+    sig = _lib.signatures()
+    c = _lib.ctypes
+    for new, old in (('b4c_attn_mq_fwd_drop', 'b4c_attn_mq_fwd'), ('b4c_attn_mq_bwd_drop', 'b4c_attn_mq_bwd')):
+        assert new in _lib.declared_symbols()
+        assert sig[new][0] == sig[old][0]
+        assert sig[new][1][:-3] == sig[old][1]                    # (q_rows, dropout_rate, seed) appended
+        assert sig[new][1][-2:] == [c.c_float, c.c_uint64]
+        assert sig[new][1][-3] == sig[old][1][6]                  # q_rows: an int32 pointer like q_offsets
+
+
+def test_library_exports_the_entry_points():
+    from bert4clickpath_amd import _lib
+    lib = _lib.lib()
+    assert lib.b4c_abi_version() == 12
+    assert hasattr(lib, 'b4c_attn_mq_fwd_drop') and hasattr(lib, 'b4c_attn_mq_bwd_drop')
+
+
+def test_ops_wrappers_refuse_a_rate_without_q_rows():
+    from bert4clickpath_amd import ops
+    q = torch.zeros(1, 64)
+    with pytest.raises(ValueError, match='q_rows'):
+        ops.attn_mq_fwd(q, q, None, None, 1, 1, 1, 64, None, None, 0.2, 1)
+    with pytest.raises(ValueError):
+        ops.attn_mq_fwd(q, q, None, None, 1, 1, 1, 64, None, q, 1.0, 1)
