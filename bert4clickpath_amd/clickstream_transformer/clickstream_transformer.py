@@ -98,7 +98,8 @@ class ClickstreamTransformer(nn.Module):
     def __init__(self, sequential_input_config, feature_vocabs, embedding_dims, head_unit, segment_to_head=None,
                  value_to_head=None, num_encoder_layers=1, num_attention_heads=1, dropout_rate=0.1,
                  compute_dtype=torch.float32, feature_combine='concat', encoder_ff_dim=100, ffn_activation='relu',
-                 position_encoding='sinusoidal', max_positions=None, attention_dropout_rate=0.0, **kwargs):
+                 position_encoding='sinusoidal', max_positions=None, attention_dropout_rate=0.0, embedding_layernorm=False,
+                 embedding_scale=None, **kwargs):
         super().__init__()
         # ffn_activation / position_encoding / max_positions: the BERT4Rec paper's GELU feed-forward and learned positions
         # (extensions, validated by transformer.Transformer); the defaults are the reference's ReLU and fixed sinusoid
@@ -130,8 +131,11 @@ class ClickstreamTransformer(nn.Module):
             num_attention_heads=num_attention_heads, encoder_ff_dim=self.encoder_ff_dim,   # 100: hard-coded in the reference (:225)
             dropout_rate=dropout_rate, compute_dtype=compute_dtype, feature_combine=feature_combine,
             ffn_activation=ffn_activation, position_encoding=position_encoding, max_positions=max_positions,
-            attention_dropout_rate=attention_dropout_rate)
+            attention_dropout_rate=attention_dropout_rate, embedding_layernorm=embedding_layernorm,
+            embedding_scale=embedding_scale)
         self.max_positions = self.transformer.max_positions
+        # embedding_layernorm / embedding_scale: the paper's input stage drop(LayerNorm(E + P)) (transformer.Transformer)
+        self.embedding_layernorm, self.embedding_scale = self.transformer.embedding_layernorm, self.transformer.embedding_scale
         if hasattr(self.head, 'tie') and getattr(self.head, '_table', None) is None:
             # tied-weight head: project back onto the FIRST embedded feature's table (the items)
             first = list(self.embedding_dims.keys())[0]
@@ -157,7 +161,9 @@ class ClickstreamTransformer(nn.Module):
                 **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
                 **({'position_encoding': 'learned', 'max_positions': self.max_positions}
                    if self.position_encoding == 'learned' else {}),
-                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {})}
+                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {}),
+                **({'embedding_layernorm': True} if self.embedding_layernorm else {}),
+                **({'embedding_scale': self.embedding_scale} if self.embedding_scale is not None else {})}
 
     @staticmethod
     def _create_lookup_tables(vocabularies, tokens_to_prepend=None):

@@ -8,7 +8,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from .transformer import Dense
+from .transformer import Dense, LayerNormalization
 
 
 class SoftMaxHead(nn.Module):
@@ -297,10 +297,17 @@ class ClozeMaskedItemPrediction(SoftMaxHead):
     with E the item-embedding table of the model (input id = label id + 10, constants.py:14-24, so offset = 10).
     Same head_unit contract and the same fused entry points as SoftMaxHead (cloze_ce / logits / forward); the
     projection's gradient is added, transposed, into rows offset .. offset+V of the table's gradient.
+    transform ('relu' | 'gelu' | 'gelu_tanh'; None: the trunk above): the paper's transform in front of the projection -- after
+    relu(Dense) x n ALWAYS one more Dense back to the item-embedding width, the activation and a LayerNorm (parameters
+    ``transform_norm.gamma`` / ``.beta``): dense_layer_dims=[] with 'gelu_tanh' is the paper's head, LayerNorm(gelu(Dense(d -> d))).
     No reference oracle: checked against the build's own fp64 restatement (oracle/numpy_ref.py)."""
 
-    def __init__(self, dense_layer_dims, output_vocab_size, item_embedding=None, id_offset=10, input_dim=None, **kwargs):
+    def __init__(self, dense_layer_dims, output_vocab_size, item_embedding=None, id_offset=10, input_dim=None, transform=None,
+                 **kwargs):
         super().__init__(dense_layer_dims, output_vocab_size, None)
+        if transform is not None and not (isinstance(transform, str) and transform in ops.FFN_ACTIVATIONS):
+            raise ValueError("transform must be None, 'relu', 'gelu' or 'gelu_tanh', got %r" % (transform,))
+        self.transform = transform
         self.id_offset = int(id_offset)
         self._table = None
         if item_embedding is not None:
@@ -325,11 +332,13 @@ class ClozeMaskedItemPrediction(SoftMaxHead):
         d_item = int(self._table.shape[1])
         prev = int(input_dim)
         dims = list(self.dense_layer_dims)
-        if (dims[-1] if dims else prev) != d_item:
+        if self.transform is not None or (dims[-1] if dims else prev) != d_item:
             dims.append(d_item)
         for h in dims:
             self.intermediate_layers.append(Dense(prev, h))
             prev = h
+        if self.transform is not None:
+            self.transform_norm = LayerNormalization(d_item, 1e-6)
         self.output_bias = nn.Parameter(torch.zeros(self.output_vocab_size))
         self._packs = [ops.PackedLinear([l.kernel], [l.bias]) for l in self.intermediate_layers] + \
                       [ops.TiedPackedLinear(self._table, self.id_offset, self.output_vocab_size, self.output_bias)]
@@ -341,7 +350,24 @@ class ClozeMaskedItemPrediction(SoftMaxHead):
         out = []
         for l in self.intermediate_layers:
             out += [l.kernel, l.bias]
+        if self.transform is not None:
+            out += [self.transform_norm.gamma, self.transform_norm.beta]
         return out + [self._table, self.output_bias]
+
+    def trunk(self, x2d):
+        """the projection's input: relu(Dense) x n, and with a transform LayerNorm(act(Dense(.))) of the last Dense"""
+        if self.transform is None:
+            return super().trunk(x2d)
+        if not self._built():
+            self.build(x2d.shape[-1])
+            self.to(x2d.device)
+        need_tape = torch.is_grad_enabled()
+        layers = list(self.intermediate_layers)
+        if len(layers) > 1:
+            x2d = ops.MLPFn.apply(x2d, self._packs[:-2], need_tape, 'relu_last', *[p for l in layers[:-1] for p in (l.kernel, l.bias)])
+        last, norm = layers[-1], self.transform_norm
+        return ops.DenseActLNFn.apply(x2d, last.kernel, last.bias, norm.gamma, norm.beta, self._packs[-2],
+                                      ops.ffn_act_code(self.transform), need_tape)
 
     def _proj(self):
         return int(self._table.shape[1]), self._table, self.output_bias

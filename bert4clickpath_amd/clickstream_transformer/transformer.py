@@ -11,6 +11,7 @@ Build constraints of the HIP path: every feature's embedding dim % 8 == 0, head 
 {16, 32, 64, 128}, sequence tensors are int64 on the HIP device.
 """
 import math
+import numbers
 
 import numpy as np
 import torch
@@ -372,12 +373,21 @@ class Transformer(nn.Module):
     Extensions of the BERT4Rec paper, no reference counterpart: ffn_activation ('relu' | 'gelu' | 'gelu_tanh') for the
     feed-forward blocks, position_encoding='learned' with max_positions: the positional table is a parameter
     ``position_embedding.weight`` [max_positions, d_model] (truncated normal, sigma 0.02) instead of the fixed sinusoid, and
-    attention_dropout_rate: dropout on the attention probabilities (BERT's attention_probs_dropout_prob), in training only."""
+    attention_dropout_rate: dropout on the attention probabilities (BERT's attention_probs_dropout_prob), in training only;
+    embedding_layernorm=True: the input stage is drop(LayerNorm(scale * rows + PE)) with the parameters
+    ``embedding_norm.gamma`` / ``.beta`` (eps 1e-6, as every LayerNormalization here); embedding_scale: a positive number in
+    place of sqrt(d_model) (None; the paper does not scale: 1.0)."""
 
     def __init__(self, num_layers, num_attention_heads, embedding_sizes, embedding_dims, encoder_ff_dim, dropout_rate,
                  item_embedding_weights=None, compute_dtype=torch.float32, feature_combine='concat', ffn_activation='relu',
-                 position_encoding='sinusoidal', max_positions=None, attention_dropout_rate=0.0, **kwargs):
+                 position_encoding='sinusoidal', max_positions=None, attention_dropout_rate=0.0, embedding_layernorm=False,
+                 embedding_scale=None, **kwargs):
         super().__init__()
+        if embedding_scale is not None and not (isinstance(embedding_scale, numbers.Real) and not isinstance(embedding_scale, bool)
+                                                and 0 < float(embedding_scale) < float('inf')):
+            raise ValueError('embedding_scale must be None (sqrt(d_model)) or a positive number, got %r' % (embedding_scale,))
+        self.embedding_layernorm = bool(embedding_layernorm)
+        self.embedding_scale = None if embedding_scale is None else float(embedding_scale)
         ops.ffn_act_code(ffn_activation)
         self.attention_dropout_rate = _attention_rate(attention_dropout_rate)
         if position_encoding not in ('sinusoidal', 'learned'):
@@ -421,6 +431,12 @@ class Transformer(nn.Module):
             self.register_buffer('pos_encoding', positional_encoding(self.maximum_position_encoding, self.d_model)[0].clone(),
                                  persistent=False)
         self.scale = float(np.sqrt(np.float32(self.d_model)))   # sqrt taken in float32 (reference :390)
+        if self.embedding_scale is not None:
+            self.scale = self.embedding_scale
+        if self.embedding_layernorm:
+            if self.d_model > 1024:
+                raise B4CError('embedding_layernorm: d_model %d > 1024 (the LayerNorm row kernels)' % self.d_model)
+            self.embedding_norm = LayerNormalization(self.d_model, 1e-6)
 
     def get_config(self):
         return {'num_layers': self.num_layers, 'num_attention_heads': self.num_attention_heads,
@@ -431,7 +447,9 @@ class Transformer(nn.Module):
                 **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
                 **({'position_encoding': 'learned', 'max_positions': self.max_positions}
                    if self.position_encoding == 'learned' else {}),
-                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {})}
+                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {}),
+                **({'embedding_layernorm': True} if self.embedding_layernorm else {}),
+                **({'embedding_scale': self.embedding_scale} if self.embedding_scale is not None else {})}
 
     @property
     def position_table(self):
@@ -461,7 +479,11 @@ class Transformer(nn.Module):
         if packed is not None and not self.packed_supported(S):
             raise B4CError('packed layout needs bf16, head depth 32 / 64 and S <= 512')
         n_arg = (len(ids), packed, 'sum') if self.feature_combine == 'sum' else (len(ids) if packed is None else (len(ids), packed))
-        if self.position_encoding == 'learned':
+        if self.embedding_layernorm:
+            # the paper's input stage; the positional table is differentiable when it is the learned parameter
+            x, key_pad = ops.EmbedLNFn.apply(self.position_table, self.embedding_norm.gamma, self.embedding_norm.beta, self.scale,
+                                             rate, seed, self.compute_dtype, n_arg, *ids, *tables)
+        elif self.position_encoding == 'learned':
             # the table is a differentiable input (its gradient: b4c_pos_table_bwd); the sinusoidal call is the reference's
             x, key_pad = ops.EmbedFn.apply(self.position_embedding.weight, self.scale, rate, seed, self.compute_dtype, n_arg,
                                            *ids, *tables)

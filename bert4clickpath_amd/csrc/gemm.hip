@@ -146,23 +146,6 @@ __device__ __forceinline__ void epilogue8(float (&v)[8], int64_t row, int col, O
     Vec8<OutT>::store(C + row * ldc + col, v);
 }
 
-// GELU (B4C_ACT_GELU: x Phi(x) with erf; B4C_ACT_GELU_TANH: the tanh form) and its derivative, in fp32.  The derivative is
-// applied to the SAVED pre-activation u (the `pre` output of b4c_gemm_nt_act): GELU is not monotone, so unlike ReLU its
-// backward cannot be read off the activation.
-__device__ __forceinline__ float act_gelu(float x, int act) {
-    if (act == B4C_ACT_GELU) return 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
-    const float t = tanhf(0.79788456080286536f * (x + 0.044715f * x * x * x));
-    return 0.5f * x * (1.f + t);
-}
-__device__ __forceinline__ float act_gelu_grad(float u, int act) {
-    if (act == B4C_ACT_GELU)      // Phi(u) + u phi(u)
-        return 0.5f * (1.f + erff(u * 0.70710678118654752f)) + u * 0.39894228040143268f * __expf(-0.5f * u * u);
-    u = fminf(fmaxf(u, -10.f), 10.f);      // tanh is +-1 in fp32 well before |u| = 10: the step's limit, and u * u stays finite
-    const float u2 = u * u;
-    const float t = tanhf(0.79788456080286536f * (u + 0.044715f * u * u2));
-    return 0.5f * (1.f + t) + 0.5f * u * (1.f - t * t) * 0.79788456080286536f * (1.f + 3.f * 0.044715f * u2);
-}
-
 // One LDS stage (36.9 KB -> 4 workgroups per CU) with register prefetch of the next K tile.  The kernel is
 // latency-bound at K = 128 (two K tiles), so dependent round trips to memory are issued early:
 //   * the bias chunk of each lane is loaded at entry,

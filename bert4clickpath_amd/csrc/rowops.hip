@@ -40,6 +40,32 @@ struct EmbedArgs {
     int sum;                          // 1: every feature is d_model wide and the rows are ADDED (config 4 of the north star)
 };
 
+// v = the 8 columns c .. c+7 of dense position ts before the scale: the features' table rows, added (a.sum) or concatenated,
+// ids clamped into their tables.  The one gather of the embedding stage (embed_fwd_kernel, the LayerNorm form and its backward).
+__device__ __forceinline__ void embed_gather8(const EmbedArgs &a, int64_t ts, int c, int d, float (&v)[8]) {
+    if (a.sum) {        // rows of all features added in feature order (fp32), then scaled
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = 0.f;
+        for (int f = 0; f < a.n; ++f) {
+            int64_t id = a.ids[f][ts];
+            id = id < 0 ? 0 : (id >= a.rows[f] ? a.rows[f] - 1 : id);
+            float w[8];
+            Vec8<float>::load(a.table[f] + id * d + c, w);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] += w[k];
+        }
+    } else {
+        int f = 0;
+#pragma unroll
+        for (int k = 1; k < B4C_MAX_FEATURES; ++k)
+            if (k < a.n && c >= a.col0[k]) f = k;
+        int64_t id = a.ids[f][ts];
+        id = id < 0 ? 0 : (id >= a.rows[f] ? a.rows[f] - 1 : id);
+        // every feature dim is a multiple of 8 (the host checks): a chunk never straddles two features
+        Vec8<float>::load(a.table[f] + id * a.fd[f] + (c - a.col0[f]), v);
+    }
+}
+
 // one thread = 8 consecutive output columns of one token (a 16-B bf16 / 32-B fp32 store)
 template <typename T>
 __global__ void __launch_bounds__(256) embed_fwd_kernel(EmbedArgs a, const float *__restrict__ pe, float scale,
@@ -57,27 +83,7 @@ __global__ void __launch_bounds__(256) embed_fwd_kernel(EmbedArgs a, const float
         const int s = (int)(ts % S);
         if (c == 0 && key_pad) key_pad[t] = (a.ids[0][ts] == 0) ? 1 : 0;
         float v[8], p[8];
-        if (a.sum) {        // rows of all features added in feature order (fp32), then scaled
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = 0.f;
-            for (int f = 0; f < a.n; ++f) {
-                int64_t id = a.ids[f][ts];
-                id = id < 0 ? 0 : (id >= a.rows[f] ? a.rows[f] - 1 : id);
-                float w[8];
-                Vec8<float>::load(a.table[f] + id * d + c, w);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] += w[k];
-            }
-        } else {
-            int f = 0;
-#pragma unroll
-            for (int k = 1; k < B4C_MAX_FEATURES; ++k)
-                if (k < a.n && c >= a.col0[k]) f = k;
-            int64_t id = a.ids[f][ts];
-            id = id < 0 ? 0 : (id >= a.rows[f] ? a.rows[f] - 1 : id);
-            // every feature dim is a multiple of 8 (the host checks): a chunk never straddles two features
-            Vec8<float>::load(a.table[f] + id * a.fd[f] + (c - a.col0[f]), v);
-        }
+        embed_gather8(a, ts, c, d, v);
         Vec8<float>::load(pe + (int64_t)s * d + c, p);
         const uint32_t km = rate > 0.f ? b4c_keep8(seed, (uint64_t)(t * d + c), b4c_keep_threshold(rate)) : 0xFFu;
 #pragma unroll
@@ -570,15 +576,89 @@ extern "C" int b4c_embed_concat_pe_bwd_sorted_ws(int n_feat, const int64_t *cons
 // ------------------------------------------------------------------------------------------
 #define LN_MAX_PASS 2  // d <= 64 lanes * 8 elems * 2 passes = 1024 (keeps the per-lane row slice in registers)
 
-template <typename T, int G>
-__global__ void __launch_bounds__(256) add_ln_fwd_kernel(const T *__restrict__ x, const T *__restrict__ y,
-                                                         const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                         T *__restrict__ z, T *__restrict__ out, float *__restrict__ stats,
-                                                         int64_t rows, int d, float eps, float rate, uint64_t seed) {
+// Where a LayerNorm row comes from: load(row, c, v) = its columns c .. c+7 in fp32 (c < d).
+template <typename T> struct AddDropSrc {       // x + drop(y), saved to z when z != NULL
+    const T *x, *y;
+    T *z;
+    int d;
+    float rate, inv_keep;
+    uint64_t seed;
+    __device__ __forceinline__ void load(int64_t row, int c, float (&v)[8]) const {
+        float a[8], b[8];
+        Vec8<T>::load(x + row * d + c, a);
+        Vec8<T>::load(y + row * d + c, b);
+        const uint32_t km = rate > 0.f ? b4c_keep8(seed, (uint64_t)(row * d + c), b4c_keep_threshold(rate)) : 0xFFu;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float yy = b[k];
+            if (rate > 0.f) yy = ((km >> k) & 1u) ? yy * inv_keep : 0.f;
+            v[k] = a[k] + yy;
+        }
+        if (z) Vec8<T>::store(z + row * d + c, v);
+    }
+};
+template <typename T> struct RowSrc {           // the row itself: plain LayerNorm
+    const T *x;
+    int d;
+    __device__ __forceinline__ void load(int64_t row, int c, float (&v)[8]) const { Vec8<T>::load(x + row * d + c, v); }
+};
+struct EmbedSrc {       // scale * (the features' table rows) + pe[s]: the fp32 rows go from the tables into registers, nothing is rounded
+    EmbedArgs a;
+    const float *pe;
+    const int32_t *token_src;
+    uint8_t *key_pad;       // written by the lane of column 0 (NULL: not written)
+    float scale;
+    int S, d;
+    __device__ __forceinline__ void load(int64_t row, int c, float (&v)[8]) const {
+        const int64_t ts = token_src ? (int64_t)token_src[row] : row;
+        if (c == 0 && key_pad) key_pad[row] = (a.ids[0][ts] == 0) ? 1 : 0;
+        float p[8];
+        embed_gather8(a, ts, c, d, v);
+        Vec8<float>::load(pe + (ts % S) * d + c, p);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = v[k] * scale + p[k];
+    }
+};
+// What happens to 8 results of a row before they are stored: apply(row, c, o).
+// kNone: nothing is applied -- the backward body then keeps dz in the registers dy is made from.
+struct NoEpi {
+    static constexpr bool kNone = true;
+    __device__ __forceinline__ void apply(int64_t, int, float (&)[8]) const {}
+};
+struct DropEpi {        // inverted dropout, element row * d + c + k of the keep-mask stream
+    static constexpr bool kNone = false;
+    float rate, inv_keep;
+    uint64_t seed;
+    int d;
+    __device__ __forceinline__ void apply(int64_t row, int c, float (&o)[8]) const {
+        if (rate > 0.f) {
+            const uint32_t km = b4c_keep8(seed, (uint64_t)(row * d + c), b4c_keep_threshold(rate));
+#pragma unroll
+            for (int k = 0; k < 8; ++k) o[k] = ((km >> k) & 1u) ? o[k] * inv_keep : 0.f;
+        }
+    }
+};
+template <typename T> struct GateEpi {          // o *= act'(gate[row][c + k]): ReLU = the gate's sign, a GELU = its derivative (NULL: none)
+    static constexpr bool kNone = false;
+    const T *gate;
+    int ld, act;
+    __device__ __forceinline__ void apply(int64_t row, int c, float (&o)[8]) const {
+        if (!gate) return;
+        float u[8];
+        Vec8<T>::load(gate + row * ld + c, u);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = act == B4C_ACT_RELU ? (u[k] > 0.f ? o[k] : 0.f) : o[k] * act_gelu_grad(u[k], act);
+    }
+};
+
+// The LayerNorm row body: rows from `src`, out[row] = epi(gamma * (v - mean) * rstd + beta), stats[row] = {mean, rstd}.
+template <typename T, int G, typename Src, typename Epi>
+__device__ __forceinline__ void ln_fwd_rows(const Src &src, const Epi &epi, const float *__restrict__ gamma,
+                                            const float *__restrict__ beta, T *__restrict__ out, int ld_out,
+                                            float *__restrict__ stats, int64_t rows, int d, float eps) {
     const int lane_in_row = threadIdx.x & (G - 1);
     const int rows_per_block = 256 / G;
     const int npass = (d + G * 8 - 1) / (G * 8);
-    const float inv_keep = rate > 0.f ? 1.0f / (1.0f - rate) : 1.0f;
     const float inv_d = 1.0f / (float)d;
     for (int64_t row = blockIdx.x * (int64_t)rows_per_block + threadIdx.x / G; row < rows;
          row += (int64_t)gridDim.x * rows_per_block) {
@@ -589,18 +669,9 @@ __global__ void __launch_bounds__(256) add_ln_fwd_kernel(const T *__restrict__ x
             if (p < npass) {
                 const int c = (p * G + lane_in_row) * 8;
                 if (c < d) {
-                    float a[8], b[8];
-                    Vec8<T>::load(x + row * d + c, a);
-                    Vec8<T>::load(y + row * d + c, b);
-                    const uint32_t km = rate > 0.f ? b4c_keep8(seed, (uint64_t)(row * d + c), b4c_keep_threshold(rate)) : 0xFFu;
+                    src.load(row, c, v[p]);
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        float yy = b[k];
-                        if (rate > 0.f) yy = ((km >> k) & 1u) ? yy * inv_keep : 0.f;
-                        v[p][k] = a[k] + yy;
-                        sum += v[p][k];
-                    }
-                    if (z) Vec8<T>::store(z + row * d + c, v[p]);
+                    for (int k = 0; k < 8; ++k) sum += v[p][k];
                 } else {
 #pragma unroll
                     for (int k = 0; k < 8; ++k) v[p][k] = 0.f;
@@ -634,7 +705,8 @@ __global__ void __launch_bounds__(256) add_ln_fwd_kernel(const T *__restrict__ x
                     Vec8<float>::load(beta + c, b);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) o[k] = (v[p][k] - mean) * rstd * g[k] + b[k];
-                    Vec8<T>::store(out + row * d + c, o);
+                    epi.apply(row, c, o);
+                    Vec8<T>::store(out + row * ld_out + c, o);
                 }
             }
         }
@@ -645,16 +717,63 @@ __global__ void __launch_bounds__(256) add_ln_fwd_kernel(const T *__restrict__ x
     }
 }
 
-// backward: dz = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dout * gamma.
+template <typename T, int G>
+__global__ void __launch_bounds__(256) add_ln_fwd_kernel(const T *__restrict__ x, const T *__restrict__ y,
+                                                         const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                         T *__restrict__ z, T *__restrict__ out, float *__restrict__ stats,
+                                                         int64_t rows, int d, float eps, float rate, uint64_t seed) {
+    const AddDropSrc<T> src = {x, y, z, d, rate, rate > 0.f ? 1.0f / (1.0f - rate) : 1.0f, seed};
+    ln_fwd_rows<T, G>(src, NoEpi(), gamma, beta, out, d, stats, rows, d, eps);
+}
+
+// plain LayerNorm of x (no residual, no dropout)
+template <typename T, int G>
+__global__ void __launch_bounds__(256) ln_fwd_kernel(const T *__restrict__ x, const float *__restrict__ gamma,
+                                                     const float *__restrict__ beta, T *__restrict__ out,
+                                                     float *__restrict__ stats, int64_t rows, int d, float eps) {
+    const RowSrc<T> src = {x, d};
+    ln_fwd_rows<T, G>(src, NoEpi(), gamma, beta, out, d, stats, rows, d, eps);
+}
+
+// the embedding stage with LayerNorm: drop(LayerNorm(scale * table rows + pe)), one pass, the pre-norm row in registers only
+template <typename T, int G>
+__global__ void __launch_bounds__(256) embed_ln_fwd_kernel(EmbedSrc src, DropEpi drop, const float *__restrict__ gamma,
+                                                           const float *__restrict__ beta, T *__restrict__ out, int ld_out,
+                                                           float *__restrict__ stats, int64_t rows, float eps) {
+    ln_fwd_rows<T, G>(src, drop, gamma, beta, out, ld_out, stats, rows, src.d, eps);
+}
+
+// Where the backward's rows come from: load(row, c, go, zz) = the upstream gradient and the LayerNorm input, columns c .. c+7.
+template <typename T> struct RowGradSrc {
+    const T *dout, *z;
+    int d;
+    __device__ __forceinline__ void load(int64_t row, int c, float (&go)[8], float (&zz)[8]) const {
+        Vec8<T>::load(dout + row * d + c, go);
+        Vec8<T>::load(z + row * d + c, zz);
+    }
+};
+template <typename T> struct EmbedGradSrc {     // go = the forward's dropout on dout; the pre-norm row is gathered again
+    EmbedSrc pre;
+    DropEpi drop;
+    const T *dout;
+    int ld;
+    __device__ __forceinline__ void load(int64_t row, int c, float (&go)[8], float (&zz)[8]) const {
+        Vec8<T>::load(dout + row * ld + c, go);
+        drop.apply(row, c, go);
+        pre.load(row, c, zz);
+    }
+};
+
+// The backward row body: dz = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dout * gamma.
 // dgamma/dbeta: per-thread partials over the block's rows -> LDS -> one atomic per column per block.
 // DET (deterministic form, `partial` != NULL): the threads' partials meet in a fixed order -- through LDS [row group][2][d], summed
 // group by group, the block's sums stored to partial[block][2][d]; ln_bwd_reduce_kernel then adds the blocks in block order.
-template <typename T, int G, int NP, bool DET>
-__global__ void __launch_bounds__(256, 4) add_ln_bwd_kernel(const T *__restrict__ dout, const T *__restrict__ z,
-                                                         const float *__restrict__ stats, const float *__restrict__ gamma,
-                                                         T *__restrict__ dz, T *__restrict__ dy, float *__restrict__ dgamma,
-                                                         float *__restrict__ dbeta, int64_t rows, int d, float rate,
-                                                         uint64_t seed, float *__restrict__ partial) {
+// dz pitch ld_dz; `epi` is applied to dz; dy = the forward's dropout on dz, written by the forms without an epilogue only.
+template <typename T, int G, int NP, bool DET, typename Src, typename Epi>
+__device__ __forceinline__ void ln_bwd_rows(const Src &src, const Epi &epi, const float *__restrict__ stats,
+                                            const float *__restrict__ gamma, T *__restrict__ dz, int ld_dz, T *__restrict__ dy,
+                                            float *__restrict__ dgamma, float *__restrict__ dbeta, int64_t rows, int d, float rate,
+                                            uint64_t seed, float *__restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) float red[];  // [2][d]  (DET: [256 / G][2][d])
     const int lane_in_row = threadIdx.x & (G - 1);
     const int rows_per_block = 256 / G;
@@ -683,8 +802,7 @@ __global__ void __launch_bounds__(256, 4) add_ln_bwd_kernel(const T *__restrict_
                 const int c = (p * G + lane_in_row) * 8;
                 if (c < d) {
                     float go[8], zz[8], gm[8];
-                    Vec8<T>::load(dout + row * d + c, go);
-                    Vec8<T>::load(z + row * d + c, zz);
+                    src.load(row, c, go, zz);
                     Vec8<float>::load(gamma + c, gm);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
@@ -708,8 +826,9 @@ __global__ void __launch_bounds__(256, 4) add_ln_bwd_kernel(const T *__restrict_
                     float o[8];
 #pragma unroll
                     for (int k = 0; k < 8; ++k) o[k] = rstd * (gv[p][k] - s1 - xh[p][k] * s2);
-                    Vec8<T>::template store_sel<B4C_NT(B4C_NT_LNBWD_DZ)>(dz + row * d + c, o);
-                    if (rate > 0.f && dy) {
+                    if (!Epi::kNone) epi.apply(row, c, o);          // (a form with an epilogue has no dy: its callers pass rate 0)
+                    Vec8<T>::template store_sel<B4C_NT(B4C_NT_LNBWD_DZ)>(dz + row * ld_dz + c, o);
+                    if (Epi::kNone && rate > 0.f && dy) {
                         const uint32_t km = b4c_keep8(seed, (uint64_t)(row * d + c), b4c_keep_threshold(rate));
 #pragma unroll
                         for (int k = 0; k < 8; ++k) o[k] = ((km >> k) & 1u) ? o[k] * inv_keep : 0.f;
@@ -755,6 +874,35 @@ __global__ void __launch_bounds__(256, 4) add_ln_bwd_kernel(const T *__restrict_
         atomicAdd(dgamma + i, red[i]);
         atomicAdd(dbeta + i, red[d + i]);
     }
+}
+
+template <typename T, int G, int NP, bool DET>
+__global__ void __launch_bounds__(256, 4) add_ln_bwd_kernel(const T *__restrict__ dout, const T *__restrict__ z,
+                                                         const float *__restrict__ stats, const float *__restrict__ gamma,
+                                                         T *__restrict__ dz, T *__restrict__ dy, float *__restrict__ dgamma,
+                                                         float *__restrict__ dbeta, int64_t rows, int d, float rate,
+                                                         uint64_t seed, float *__restrict__ partial) {
+    const RowGradSrc<T> src = {dout, z, d};
+    ln_bwd_rows<T, G, NP, DET>(src, NoEpi(), stats, gamma, dz, d, dy, dgamma, dbeta, rows, d, rate, seed, partial);
+}
+
+// plain LayerNorm backward, deterministic form only; dx *= act'(gate) when a gate is given (the activation in front of the norm)
+template <typename T, int G, int NP>
+__global__ void __launch_bounds__(256, 4) ln_bwd_kernel(const T *__restrict__ dout, const T *__restrict__ x,
+                                                        const float *__restrict__ stats, const float *__restrict__ gamma,
+                                                        T *__restrict__ dx, GateEpi<T> gate, int64_t rows, int d,
+                                                        float *__restrict__ partial) {
+    const RowGradSrc<T> src = {dout, x, d};
+    ln_bwd_rows<T, G, NP, true>(src, gate, stats, gamma, dx, d, (T *)nullptr, (float *)nullptr, (float *)nullptr, rows, d, 0.f, 0, partial);
+}
+
+// backward of embed_ln_fwd_kernel up to the pre-norm row: dpre, and the partial dgamma / dbeta sums (deterministic form only)
+template <typename T, int G, int NP>
+__global__ void __launch_bounds__(256, 4) embed_ln_bwd_kernel(EmbedGradSrc<T> src, const float *__restrict__ stats,
+                                                              const float *__restrict__ gamma, T *__restrict__ dpre, int ld_dpre,
+                                                              int64_t rows, float *__restrict__ partial) {
+    ln_bwd_rows<T, G, NP, true>(src, NoEpi(), stats, gamma, dpre, ld_dpre, (T *)nullptr, (float *)nullptr, (float *)nullptr, rows,
+                                src.pre.d, 0.f, 0, partial);
 }
 
 // dgamma[i] += sum over blocks of partial[block][0][i]; dbeta likewise.  One wave per column, in a FIXED order: lane l adds the
@@ -851,6 +999,152 @@ extern "C" int b4c_add_dropout_layernorm_bwd_ws(const void *dout, const void *z,
         B4C_REQUIRE(false, "add_ln_bwd: dtype %d", dtype);
     if (det) ln_bwd_reduce_kernel<<<(2 * d + 3) / 4, 256, 0, st>>>(partial, grid, d, dgamma, dbeta);
     return b4c_check_launch("add_ln_bwd");
+}
+
+// plain LayerNorm over rows (no residual, no dropout): the same row bodies
+extern "C" int b4c_layernorm_fwd(const void *x, const float *gamma, const float *beta, void *out, float *stats, int64_t rows, int d,
+                                 float eps, int dtype, void *stream) {
+    B4C_REQUIRE(x && gamma && beta && out && rows > 0, "layernorm_fwd: null pointer / empty");
+    B4C_REQUIRE(d > 0 && d % 8 == 0 && d <= 64 * 8 * LN_MAX_PASS, "layernorm_fwd: d=%d must be a multiple of 8, <= 1024", d);
+    const int g = ln_group(d);
+    const int grid = grid_for(rows * g, 256);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == B4C_F32) {
+        LN_DISPATCH_G(ln_fwd_kernel, float, g, <<<grid, 256, 0, st>>>((const float *)x, gamma, beta, (float *)out, stats, rows, d, eps))
+    } else if (dtype == B4C_BF16) {
+        LN_DISPATCH_G(ln_fwd_kernel, bf16_t, g, <<<grid, 256, 0, st>>>((const bf16_t *)x, gamma, beta, (bf16_t *)out, stats, rows, d, eps))
+    } else
+        B4C_REQUIRE(false, "layernorm_fwd: dtype %d", dtype);
+    return b4c_check_launch("layernorm_fwd");
+}
+
+// grid, LDS bytes and passes of the deterministic backward kernels (ln_bwd_kernel, embed_ln_bwd_kernel): those of add_ln_bwd_kernel<.., true>
+struct LnBwdShape {
+    int g, grid, npass;
+    size_t shm;
+};
+static LnBwdShape ln_bwd_shape(int64_t rows, int d) {
+    LnBwdShape s;
+    s.g = ln_group(d);
+    s.grid = grid_for(rows * s.g, 256);
+    if (s.grid > 1024) s.grid = 1024;      // b4c_add_dropout_layernorm_bwd_workspace_bytes holds 1024 blocks' partial sums
+    s.npass = (d + s.g * 8 - 1) / (s.g * 8);
+    s.shm = (size_t)(256 / s.g) * 2 * (size_t)d * sizeof(float);
+    return s;
+}
+// KERNEL<TT, G, NP><<<grid, 256, shm, st>>>(args) for the row group and pass count of `sh`
+#define LN_DET_BWD_DISPATCH(KERNEL, TT, sh, ...)                                                                     \
+    switch ((sh).g) {                                                                                                \
+        case 1: KERNEL<TT, 1, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                               \
+        case 2: KERNEL<TT, 2, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                               \
+        case 4: KERNEL<TT, 4, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                               \
+        case 8: KERNEL<TT, 8, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                               \
+        case 16: KERNEL<TT, 16, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                             \
+        case 32: KERNEL<TT, 32, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                             \
+        default: if ((sh).npass == 1) KERNEL<TT, 64, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__;               \
+                 else KERNEL<TT, 64, 2><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                        \
+    }
+
+extern "C" int64_t b4c_layernorm_bwd_workspace_bytes(int64_t rows, int d) { return b4c_add_dropout_layernorm_bwd_workspace_bytes(rows, d); }
+
+extern "C" int b4c_layernorm_bwd(const void *dout, const void *x, const float *stats, const float *gamma, void *dx, float *dgamma,
+                                 float *dbeta, int64_t rows, int d, const void *gate, int ld_gate, int gate_act, void *workspace,
+                                 int64_t workspace_bytes, int dtype, void *stream) {
+    B4C_REQUIRE(dout && x && stats && gamma && dx && dgamma && dbeta && rows > 0, "layernorm_bwd: null pointer / empty");
+    B4C_REQUIRE(d > 0 && d % 8 == 0 && d <= 64 * 8 * LN_MAX_PASS, "layernorm_bwd: d=%d must be a multiple of 8, <= 1024", d);
+    B4C_REQUIRE(workspace && workspace_bytes >= b4c_layernorm_bwd_workspace_bytes(rows, d), "layernorm_bwd: workspace too small");
+    B4C_REQUIRE(!gate || (ld_gate >= d && ld_gate % 8 == 0 && (gate_act == B4C_ACT_RELU || gate_act == B4C_ACT_GELU || gate_act == B4C_ACT_GELU_TANH)),
+                "layernorm_bwd: gate pitch %d / gate_act %d", ld_gate, gate_act);
+    const LnBwdShape sh = ln_bwd_shape(rows, d);
+    float *partial = (float *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == B4C_F32) {
+        const GateEpi<float> ge = {(const float *)gate, ld_gate, gate_act};
+        LN_DET_BWD_DISPATCH(ln_bwd_kernel, float, sh, ((const float *)dout, (const float *)x, stats, gamma, (float *)dx, ge, rows, d, partial))
+    } else if (dtype == B4C_BF16) {
+        const GateEpi<bf16_t> ge = {(const bf16_t *)gate, ld_gate, gate_act};
+        LN_DET_BWD_DISPATCH(ln_bwd_kernel, bf16_t, sh, ((const bf16_t *)dout, (const bf16_t *)x, stats, gamma, (bf16_t *)dx, ge, rows, d, partial))
+    } else
+        B4C_REQUIRE(false, "layernorm_bwd: dtype %d", dtype);
+    ln_bwd_reduce_kernel<<<(2 * d + 3) / 4, 256, 0, st>>>(partial, sh.grid, d, dgamma, dbeta);
+    return b4c_check_launch("layernorm_bwd");
+}
+
+// the embedding stage with LayerNorm (embed_ln_fwd_kernel) and its backward up to the pre-norm row
+static int fill_embed_src(EmbedSrc &src, int64_t &T_tok, const char *who, int n_feat, const int64_t *const *h_ids,
+                          const float *const *h_tables, const int *h_dims, const int64_t *h_rows, const float *pe, float scale, int B,
+                          int S, int d_model, float dropout_rate, const int32_t *token_src, int64_t n_tokens) {
+    int rc = fill_embed_args(src.a, n_feat, h_ids, (float *const *)h_tables, h_dims, h_rows, d_model);
+    if (rc) return rc;
+    B4C_REQUIRE(pe && B > 0 && S > 0, "%s: bad shape", who);
+    B4C_REQUIRE(d_model <= 64 * 8 * LN_MAX_PASS, "%s: d_model=%d must be <= 1024", who, d_model);
+    B4C_REQUIRE(dropout_rate >= 0.f && dropout_rate < 1.f, "%s: dropout_rate %f", who, dropout_rate);
+    B4C_REQUIRE(n_tokens >= 0 && n_tokens <= (int64_t)B * S, "%s: n_tokens %lld out of range", who, (long long)n_tokens);
+    T_tok = token_src ? n_tokens : (int64_t)B * S;
+    src.pe = pe;
+    src.token_src = token_src;
+    src.key_pad = nullptr;
+    src.scale = scale;
+    src.S = S;
+    src.d = d_model;
+    return B4C_OK;
+}
+
+extern "C" int b4c_embed_ln_fwd(int n_feat, const int64_t *const *h_ids, const float *const *h_tables, const int *h_dims,
+                                const int64_t *h_rows, const float *pe, float scale, const float *gamma, const float *beta, float eps,
+                                void *out, int ld_out, float *stats, uint8_t *key_pad, int B, int S, int d_model, float dropout_rate,
+                                uint64_t seed, const int32_t *token_src, int64_t n_tokens, int dtype, void *stream) {
+    EmbedSrc src;
+    int64_t T_tok;
+    int rc = fill_embed_src(src, T_tok, "embed_ln_fwd", n_feat, h_ids, h_tables, h_dims, h_rows, pe, scale, B, S, d_model, dropout_rate,
+                            token_src, n_tokens);
+    if (rc) return rc;
+    B4C_REQUIRE(gamma && beta && out && ld_out >= d_model && ld_out % 8 == 0, "embed_ln_fwd: null pointer / bad pitch");
+    if (T_tok == 0) return B4C_OK;
+    src.key_pad = key_pad;
+    const DropEpi drop = {dropout_rate, dropout_rate > 0.f ? 1.0f / (1.0f - dropout_rate) : 1.0f, seed, d_model};
+    const int g = ln_group(d_model);
+    const int grid = grid_for(T_tok * g, 256);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == B4C_F32) {
+        LN_DISPATCH_G(embed_ln_fwd_kernel, float, g, <<<grid, 256, 0, st>>>(src, drop, gamma, beta, (float *)out, ld_out, stats, T_tok, eps))
+    } else if (dtype == B4C_BF16) {
+        LN_DISPATCH_G(embed_ln_fwd_kernel, bf16_t, g, <<<grid, 256, 0, st>>>(src, drop, gamma, beta, (bf16_t *)out, ld_out, stats, T_tok, eps))
+    } else
+        B4C_REQUIRE(false, "embed_ln_fwd: dtype %d", dtype);
+    return b4c_check_launch("embed_ln_fwd");
+}
+
+extern "C" int64_t b4c_embed_ln_bwd_workspace_bytes(int64_t rows, int d_model) { return b4c_add_dropout_layernorm_bwd_workspace_bytes(rows, d_model); }
+
+extern "C" int b4c_embed_ln_bwd(int n_feat, const int64_t *const *h_ids, const float *const *h_tables, const int *h_dims,
+                                const int64_t *h_rows, const float *pe, float scale, const float *gamma, const float *stats,
+                                const void *dout, int ld_dout, void *dpre, int ld_dpre, float *dgamma, float *dbeta, int B, int S,
+                                int d_model, float dropout_rate, uint64_t seed, const int32_t *token_src, int64_t n_tokens,
+                                void *workspace, int64_t workspace_bytes, int dtype, void *stream) {
+    EmbedSrc src;
+    int64_t T_tok;
+    int rc = fill_embed_src(src, T_tok, "embed_ln_bwd", n_feat, h_ids, h_tables, h_dims, h_rows, pe, scale, B, S, d_model, dropout_rate,
+                            token_src, n_tokens);
+    if (rc) return rc;
+    B4C_REQUIRE(gamma && stats && dout && dpre && dgamma && dbeta, "embed_ln_bwd: null pointer");
+    B4C_REQUIRE(ld_dout >= d_model && ld_dout % 8 == 0 && ld_dpre >= d_model && ld_dpre % 8 == 0, "embed_ln_bwd: bad pitch");
+    if (T_tok == 0) return B4C_OK;
+    B4C_REQUIRE(workspace && workspace_bytes >= b4c_embed_ln_bwd_workspace_bytes(T_tok, d_model), "embed_ln_bwd: workspace too small");
+    const DropEpi drop = {dropout_rate, dropout_rate > 0.f ? 1.0f / (1.0f - dropout_rate) : 1.0f, seed, d_model};
+    const LnBwdShape sh = ln_bwd_shape(T_tok, d_model);
+    float *partial = (float *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == B4C_F32) {
+        const EmbedGradSrc<float> gs = {src, drop, (const float *)dout, ld_dout};
+        LN_DET_BWD_DISPATCH(embed_ln_bwd_kernel, float, sh, (gs, stats, gamma, (float *)dpre, ld_dpre, T_tok, partial))
+    } else if (dtype == B4C_BF16) {
+        const EmbedGradSrc<bf16_t> gs = {src, drop, (const bf16_t *)dout, ld_dout};
+        LN_DET_BWD_DISPATCH(embed_ln_bwd_kernel, bf16_t, sh, (gs, stats, gamma, (bf16_t *)dpre, ld_dpre, T_tok, partial))
+    } else
+        B4C_REQUIRE(false, "embed_ln_bwd: dtype %d", dtype);
+    ln_bwd_reduce_kernel<<<(2 * d_model + 3) / 4, 256, 0, st>>>(partial, sh.grid, d_model, dgamma, dbeta);
+    return b4c_check_launch("embed_ln_bwd");
 }
 
 // ------------------------------------------------------------------------------------------

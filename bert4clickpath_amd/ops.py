@@ -202,9 +202,8 @@ def remap_index(idx, mapping):
     return out
 
 
-def embed_concat_pe_fwd(ids_list, tables, pe, scale, rate, seed, dtype, packed=None, combine='concat'):
-    """combine='sum' (two or more features of one width): the gathered rows are added instead of concatenated -- the
-    library takes that form when every table is d_model wide."""
+def _embed_shape(ids_list, tables, pe, combine):
+    """-> (B, S, d_model) of an embedding-stage call, after the checks the kernels rely on"""
     _cuda(pe, *ids_list, *tables)
     B, S = ids_list[0].shape
     if combine == 'sum':
@@ -223,6 +222,13 @@ def embed_concat_pe_fwd(ids_list, tables, pe, scale, rate, seed, dtype, packed=N
             raise B4CError('embedding tables must be contiguous float32')
     if pe.shape[0] < S or pe.shape[1] != d:
         raise B4CError('positional table (%d,%d) too small for S=%d d=%d' % (pe.shape[0], pe.shape[1], S, d))
+    return B, S, d
+
+
+def embed_concat_pe_fwd(ids_list, tables, pe, scale, rate, seed, dtype, packed=None, combine='concat'):
+    """combine='sum' (two or more features of one width): the gathered rows are added instead of concatenated -- the
+    library takes that form when every table is d_model wide."""
+    B, S, d = _embed_shape(ids_list, tables, pe, combine)
     n, ids_arr, tab_arr, dims, rows = _feature_arrays(ids_list, tables)
     if packed is not None:      # rows of the real tokens only
         T_tok = packed.T
@@ -354,6 +360,88 @@ def embed_concat_pe_bwd(ids_list, tables, dout, scale, rate, seed, into=None, or
         L.check(L.lib().b4c_embed_concat_pe_bwd(n, ids_arr, tab_arr, dims, rows, scale, _p(dout), d, B, S, d, rate, seed,
                                                 dt_code(dout.dtype), _st()), 'embed_concat_pe_bwd')
     return dtabs
+
+
+def _embed_ln_shape(ids_list, tables, pe, combine):
+    """_embed_shape for the LayerNorm form, whose kernels also read pe in the backward: contiguous float32"""
+    if pe.dtype != torch.float32 or not pe.is_contiguous():
+        raise B4CError('embed_ln: the positional table must be contiguous float32')
+    return _embed_shape(ids_list, tables, pe, combine)
+
+
+def _ln_vectors(d, *vs):
+    for v in vs:
+        if v.dtype != torch.float32 or not v.is_contiguous() or tuple(v.shape) != (d,):
+            raise B4CError('LayerNorm gamma / beta / their gradient sinks must be contiguous float32 [%d]' % d)
+
+
+def _rows_view(t, T_tok, d, dtype, what):
+    """a caller-given [T, d] output (any leading shape, unit column stride, 16-B rows) as the kernels take it"""
+    t2 = t.reshape(-1, t.shape[-1]) if t.is_contiguous() else t
+    if t2.dtype != dtype or tuple(t2.shape) != (T_tok, d) or t2.stride(1) != 1 or (t2.stride(0) * t2.element_size()) % 16 or \
+            t2.data_ptr() % 16:
+        raise B4CError('%s must be a [%d, %d] %s tensor with unit column stride and 16-B aligned rows' % (what, T_tok, d, dtype))
+    return t2
+
+
+def embed_ln_fwd(ids_list, tables, pe, scale, gamma, beta, rate, seed, dtype, packed=None, combine='concat', eps=LN_EPS,
+                 out=None, stats=None):
+    """The embedding stage with LayerNorm (b4c_embed_ln_fwd): drop(LayerNorm(scale * rows + pe)) -> (out, key_pad, stats);
+    out (B, S, d), or (1, T, d) with `packed`; stats fp32 [T, 2] = (mean, rstd) of every row.  out / stats: tensors to write
+    into (a [T, d] view with unit column stride; a contiguous [T, 2])."""
+    B, S, d = _embed_ln_shape(ids_list, tables, pe, combine)
+    _cuda(gamma, beta)
+    _ln_vectors(d, gamma, beta)
+    n, ids_arr, tab_arr, dims, rows = _feature_arrays(ids_list, tables)
+    T_tok = packed.T if packed is not None else B * S
+    dev = pe.device
+    if out is None:
+        out = torch.empty((1, T_tok, d) if packed is not None else (B, S, d), dtype=dtype, device=dev)
+    o2 = _rows_view(out, T_tok, d, dtype, 'embed_ln_fwd: out')
+    if stats is None:
+        stats = torch.empty(T_tok, 2, dtype=torch.float32, device=dev)
+    elif stats.dtype != torch.float32 or not stats.is_contiguous() or tuple(stats.shape) != (T_tok, 2):
+        raise B4CError('embed_ln_fwd: stats must be a contiguous float32 [%d, 2] tensor' % T_tok)
+    key_pad = torch.empty((T_tok,) if packed is not None else (B, S), dtype=torch.uint8, device=dev)
+    with _record('embed_ln_fwd', T_tok * d * (4 + o2.element_size()) + 8 * T_tok):
+        L.check(L.lib().b4c_embed_ln_fwd(n, ids_arr, tab_arr, dims, rows, _p(pe), scale, _p(gamma), _p(beta), eps, _p(o2),
+                                         o2.stride(0), _p(stats), _p(key_pad), B, S, d, rate, seed,
+                                         _p(packed.tok_src) if packed is not None else None, T_tok, dt_code(dtype), _st()),
+                'embed_ln_fwd')
+    return out, key_pad, stats
+
+
+def embed_ln_bwd(ids_list, tables, pe, scale, gamma, stats, dout, rate, seed, packed=None, combine='concat', into=None,
+                 dpre=None, workspace=None):
+    """Backward of embed_ln_fwd up to the pre-norm row (b4c_embed_ln_bwd) -> (dpre, dgamma, dbeta).  ids_list: the DENSE (B, S)
+    ids of the forward call (with `packed`, rows are taken through packed.tok_src as there); dout [T, d] in the compute dtype.
+    into = (dgamma, dbeta): fp32 [d] sinks that are added to.  The tables' and a learned pe's gradients follow from dpre through
+    embed_concat_pe_bwd / pos_table_bwd at rate 0.  Fixed summation order: the same bits on every launch."""
+    B, S, d = _embed_ln_shape(ids_list, tables, pe, combine)
+    T_tok = packed.T if packed is not None else B * S
+    g2 = _rows_view(dout, T_tok, d, dout.dtype, 'embed_ln_bwd: dout')
+    dt_code(g2.dtype)
+    _cuda(gamma, stats, g2)
+    if into is not None:
+        dgamma, dbeta = into
+    else:
+        dgamma, dbeta = zeros(d, device=g2.device), zeros(d, device=g2.device)
+    _ln_vectors(d, gamma, dgamma, dbeta)
+    if stats.dtype != torch.float32 or not stats.is_contiguous() or tuple(stats.shape) != (T_tok, 2):
+        raise B4CError('embed_ln_bwd: stats must be the contiguous float32 [%d, 2] tensor of the forward call' % T_tok)
+    if dpre is None:
+        dpre = torch.empty(T_tok, d, dtype=g2.dtype, device=g2.device)
+    p2 = _rows_view(dpre, T_tok, d, g2.dtype, 'embed_ln_bwd: dpre')
+    if T_tok == 0:
+        return dpre, dgamma, dbeta
+    n, ids_arr, tab_arr, dims, rows = _feature_arrays(ids_list, tables)
+    ws = workspace if workspace is not None else _workspace('ln_bwd', g2.device, L.lib().b4c_embed_ln_bwd_workspace_bytes(T_tok, d))
+    with _record('embed_ln_bwd', T_tok * d * (4 + 2 * g2.element_size()) + 8 * T_tok):
+        L.check(L.lib().b4c_embed_ln_bwd(n, ids_arr, tab_arr, dims, rows, _p(pe), scale, _p(gamma), _p(stats), _p(g2), g2.stride(0),
+                                         _p(p2), p2.stride(0), _p(dgamma), _p(dbeta), B, S, d, rate, seed,
+                                         _p(packed.tok_src) if packed is not None else None, T_tok, ws.data_ptr(),
+                                         ws.numel() * ws.element_size(), dt_code(g2.dtype), _st()), 'embed_ln_bwd')
+    return dpre, dgamma, dbeta
 
 
 def row_pitch(n):
@@ -948,6 +1036,56 @@ def add_dropout_layernorm_bwd(dout, z, stats, gamma, rate, seed, into=None):
                                                          dt_code(z.dtype), _st()),
                 'add_dropout_layernorm_bwd')
     return dz, (dy if dy is not None else dz), dgamma, dbeta
+
+
+def layernorm_fwd(x, gamma, beta, eps=LN_EPS, out=None, stats=None):
+    """Plain LayerNorm over the rows of x [rows, d] (b4c_layernorm_fwd) -> (out, stats fp32 [rows, 2] = mean, rstd)"""
+    rows, d = x.shape
+    _cuda(x, gamma, beta)
+    _ln_vectors(d, gamma, beta)
+    if not x.is_contiguous():
+        raise B4CError('layernorm_fwd: x must be contiguous')
+    out = torch.empty_like(x) if out is None else out
+    stats = torch.empty(rows, 2, dtype=torch.float32, device=x.device) if stats is None else stats
+    if out.dtype != x.dtype or out.shape != x.shape or not out.is_contiguous() or stats.dtype != torch.float32 or \
+            tuple(stats.shape) != (rows, 2) or not stats.is_contiguous():
+        raise B4CError('layernorm_fwd: out must be contiguous like x, stats a contiguous float32 [%d, 2]' % rows)
+    if rows == 0:
+        return out, stats
+    with _record('layernorm_fwd', rows * d * x.element_size() * 2 + 8 * rows):
+        L.check(L.lib().b4c_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(out), _p(stats), rows, d, eps, dt_code(x.dtype), _st()),
+                'layernorm_fwd')
+    return out, stats
+
+
+def layernorm_bwd(dout, x, stats, gamma, into=None, gate=None, gate_act=L.ACT_RELU, dx=None, workspace=None):
+    """Backward of layernorm_fwd (b4c_layernorm_bwd) -> (dx, dgamma, dbeta); into = (dgamma, dbeta): fp32 [d] sinks, added to.
+    gate [rows, d]: dx is multiplied by act'(gate) as it is stored (gate_act: ACT_RELU = the gate's sign, a GELU = its derivative
+    at the saved pre-activation) -- the activation in front of the norm.  Fixed summation order: the same bits every launch."""
+    rows, d = x.shape
+    _cuda(dout, x, stats, gamma)
+    if into is not None:
+        dgamma, dbeta = into
+    else:
+        dgamma, dbeta = zeros(d, device=x.device), zeros(d, device=x.device)
+    _ln_vectors(d, gamma, dgamma, dbeta)
+    dx = torch.empty_like(x) if dx is None else dx
+    if dout.dtype != x.dtype or dout.shape != x.shape or not dout.is_contiguous() or not x.is_contiguous() or \
+            dx.dtype != x.dtype or dx.shape != x.shape or not dx.is_contiguous():
+        raise B4CError('layernorm_bwd: dout, x and dx must be contiguous tensors of one shape and dtype')
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (rows, 2) or not stats.is_contiguous():
+        raise B4CError('layernorm_bwd: stats must be the contiguous float32 [%d, 2] tensor of the forward call' % rows)
+    if gate is not None and (gate.dtype != x.dtype or tuple(gate.shape) != (rows, d) or gate.stride(1) != 1 or
+                             (gate.stride(0) * gate.element_size()) % 16 or gate.data_ptr() % 16):
+        raise B4CError('layernorm_bwd: gate must be a [%d, %d] %s view with unit column stride' % (rows, d, x.dtype))
+    if rows == 0:
+        return dx, dgamma, dbeta
+    ws = workspace if workspace is not None else _workspace('ln_bwd', x.device, L.lib().b4c_layernorm_bwd_workspace_bytes(rows, d))
+    with _record('layernorm_bwd', rows * d * x.element_size() * (3 if gate is None else 4) + 8 * rows):
+        L.check(L.lib().b4c_layernorm_bwd(_p(dout), _p(x), _p(stats), _p(gamma), _p(dx), _p(dgamma), _p(dbeta), rows, d, _p(gate),
+                                          gate.stride(0) if gate is not None else 0, gate_act, ws.data_ptr(),
+                                          ws.numel() * ws.element_size(), dt_code(x.dtype), _st()), 'layernorm_bwd')
+    return dx, dgamma, dbeta
 
 
 def mask_positions(ids, value, cap=None, poison=None):
@@ -1734,6 +1872,118 @@ class EmbedFn(torch.autograd.Function):
         embed_concat_pe_bwd(ids, tables, dout, ctx.scale, ctx.rate, ctx.seed, into=sinks)
         _ready(*tables)
         return sink_returns(ctx, (dpe,) + (None,) * (5 + ctx.n), actx, sinks)
+
+
+class EmbedLNFn(torch.autograd.Function):
+    """The paper's input stage (no reference counterpart): drop(LayerNorm(scale * rows + PE)), one kernel each way
+    (b4c_embed_ln_fwd / _bwd).  apply(pe, gamma, beta, scale, rate, seed, dtype, n, *ids, *tables); n as EmbedFn's.  The tables'
+    and a learned pe's gradients are EmbedFn's kernels on the pre-norm gradient, at rate 0."""
+
+    @staticmethod
+    def forward(ctx, pe, gamma, beta, scale, rate, seed, dtype, n, *args):
+        packed, combine = None, 'concat'
+        if isinstance(n, tuple):
+            if len(n) == 3:
+                n, packed, combine = n
+            else:
+                n, packed = n
+        ids, tables = list(args[:n]), list(args[n:])
+        dense_ids = ids
+        if packed is not None:
+            # the tables' backward works on the packed ids (one gather per feature): B = 1, S = T rows
+            pk_ids = []
+            for i in ids:
+                flat = i.reshape(-1)
+                if flat.dtype != torch.int64 or not flat.is_contiguous():
+                    flat = flat.to(torch.int64).contiguous()
+                o = torch.empty(1, packed.T, dtype=torch.int64, device=flat.device)
+                L.check(L.lib().b4c_gather_i64(_p(flat), _p(packed.tok_src), _p(o), packed.T, _st()), 'gather_i64')
+                pk_ids.append(o)
+            ids = pk_ids
+        # a table under a row-lazy optimizer (optim.LazyRows): the rows about to be read are brought up to date first (the
+        # backward's second gather reads the same, caught-up rows)
+        for j, (t, i) in enumerate(zip(tables, ids)):
+            lz = getattr(t, '_b4c_lazy', None)
+            if lz is not None:
+                lz.catch_up(i, note=ctx.needs_input_grad[8 + n + j])
+        out, key_pad, stats = embed_ln_fwd(dense_ids, [t.detach() for t in tables], pe.detach(), scale, gamma.detach(), beta.detach(),
+                                           rate, seed, dtype, packed, combine)
+        ctx.save_for_backward(*ids, *tables, *(dense_ids if packed is not None else ()), stats)
+        ctx.n, ctx.scale, ctx.rate, ctx.seed, ctx.packed, ctx.combine = n, scale, rate, seed, packed, combine
+        ctx.pe, ctx.norm = pe, (gamma, beta)
+        if ctx.needs_input_grad[0]:        # a learned positional table: what its gradient kernel needs
+            if packed is not None and packed.packed_of is None:
+                raise B4CError('learned positions in the packed layout need Packed.packed_of (the row of every dense position)')
+            ctx.seqs = (dense_ids[0].shape[0], dense_ids[0].shape[1], packed.packed_of if packed is not None else None)
+        ctx.mark_non_differentiable(key_pad)
+        ctx.set_materialize_grads(False)       # (or autograd fills a zero "gradient" of key_pad's size every step)
+        return out, key_pad
+
+    @staticmethod
+    def backward(ctx, dout, _):
+        saved, n = ctx.saved_tensors, ctx.n
+        ids, tables, stats = list(saved[:n]), list(saved[n:2 * n]), saved[-1]
+        dense_ids = list(saved[2 * n:3 * n]) if ctx.packed is not None else ids
+        flush_pending_dw(getattr(tables[0], '_b4c_ctx', None))
+        if dout is None:
+            return (None,) * (8 + 2 * n)
+        gamma, beta = ctx.norm
+        gctx, gsinks = grad_sinks(gamma, beta)
+        dpre, _, _ = embed_ln_bwd(dense_ids, [t.detach() for t in tables], ctx.pe.detach(), ctx.scale, gamma.detach(), stats,
+                                  dout.reshape(-1, dout.shape[-1]).contiguous(), ctx.rate, ctx.seed, ctx.packed, ctx.combine,
+                                  into=gsinks)
+        _ready(gamma, beta)
+        dgam, dbet = (None, None) if gctx is not None else gsinks
+        dpre = dpre.reshape(ids[0].shape[0], ids[0].shape[1], -1)
+        dpe = None
+        if ctx.needs_input_grad[0]:
+            B, S, row_of = ctx.seqs
+            cu = dense_cu(B, S, dpre.device) if row_of is None else None
+            pactx, (psink,) = grad_sinks(ctx.pe)
+            pos_table_bwd(dpre, cu, B, S, 0.0, 0, psink, row_of=row_of)
+            _ready(ctx.pe)
+            dpe = None if pactx is not None else psink
+        actx, sinks = grad_sinks(*tables)
+        embed_concat_pe_bwd(ids, tables, dpre, ctx.scale, 0.0, 0, into=sinks)
+        _ready(*tables)
+        return sink_returns(ctx, (dpe, dgam, dbet) + (None,) * (5 + n), actx, sinks)
+
+
+class DenseActLNFn(torch.autograd.Function):
+    """The paper's masked-item transform (no reference counterpart): LayerNorm(act(x W + b)), act = relu or a GELU (`act`:
+    B4C_ACT_*).  apply(x, w, b, gamma, beta, pack, act, training).  A GELU saves the pre-activation beside the activation, as
+    FFNBlockFn does; the LayerNorm backward applies act' as it stores its dx."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, pk, act, training):
+        wt, _, bias = pk.get(x.dtype, x.shape[1], training)
+        relu = act == L.ACT_RELU
+        u = torch.empty(x.shape[0], pk.Np, dtype=x.dtype, device=x.device) if (training and not relu) else None
+        with _timed('head_mlp_fwd'):
+            a = gemm_nt(x, wt, pk.Np, bias, act=act, pre=u)
+            out, stats = layernorm_fwd(a, gamma.detach(), beta.detach())
+        if training:
+            ctx.save_for_backward(x, a, stats, *(() if relu else (u,)))
+            ctx.pk, ctx.act, ctx.params = pk, act, (w, b, gamma, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, a, stats = ctx.saved_tensors[:3]
+        w, b, gamma, beta = ctx.params
+        pk = ctx.pk
+        actx, sinks = grad_sinks(*ctx.params)
+        gw, gb, ggam, gbet = sinks
+        gate = a if ctx.act == L.ACT_RELU else ctx.saved_tensors[3]
+        du, _, _ = layernorm_bwd(_rows_ok(dout, a.dtype).contiguous(), a, stats, gamma.detach(), into=(ggam, gbet), gate=gate,
+                                 gate_act=ctx.act)
+        _ready(gamma, beta)
+        _, wc, _ = pk.get(x.dtype, x.shape[1], True)
+        queue_dw(actx, x, du, pk.K, pk.N, [gw], [gb], (w, b))
+        with _timed('head_mlp_dx'):
+            dx = gemm_nt(du, wc, x.shape[1])
+        flush_pending_dw(actx)
+        return sink_returns(ctx, (dx,), actx, sinks)
 
 
 class AttnBlockFn(torch.autograd.Function):

@@ -5,6 +5,9 @@ Adam 1e-3/.9/.999/1e-9, dropout 0.1, 512 sequences per step), trained for a boun
 HitRate@10 / NDCG@10 with the reference's evaluation protocol (mask the last item, rank over ALL V items).
 --negatives N adds the BERT4Rec paper's protocol beside it: the held-out item ranked against N sampled items the user has not
 seen (uniform, or by popularity counted on the training split), HR@10 / NDCG@10 over those 1 + N candidates.
+--paper_model builds the paper's MODEL instead of the reference's (no reference oracle): learned positions, GELU feed-forward of width
+4 d, drop(LayerNorm(E + P)) at the input, attention dropout, the tied head LayerNorm(gelu(Dense(d -> d))) . E^T + b; with the paper's
+recipe (--clipnorm 5 --warmup 100 --weight_decay 0.01) and --negatives 100 its sampled-negative numbers stand beside the published ones.
 
     python examples/beauty_hitrate.py --steps 3000 --dtype f32
 Prints one JSON line.  The CPU counterpart on the oracle is oracle/train_beauty_cpu.py (same seeds, batches,
@@ -21,10 +24,18 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def build_model(V, dropout, dtype, seed=1234):
-    from bert4clickpath_amd.clickstream_transformer import ClickstreamTransformer, SoftMaxHead
+def build_model(V, dropout, dtype, seed=1234, paper_positions=None):
+    """paper_positions (the longest encoder input): the BERT4Rec paper's model, one constructor call"""
+    from bert4clickpath_amd.clickstream_transformer import ClickstreamTransformer, ClozeMaskedItemPrediction, SoftMaxHead
     torch.manual_seed(seed)            # CPU generator: identical initial weights on any machine
     vocab = ['item%d' % i for i in range(V)]
+    if paper_positions is not None:
+        return ClickstreamTransformer({'items': ['asin']}, {'items': vocab}, {'items': 64},
+                                      ClozeMaskedItemPrediction([], V, transform='gelu_tanh'), value_to_head='[MASK]',
+                                      num_encoder_layers=2, num_attention_heads=2, encoder_ff_dim=256, dropout_rate=dropout,
+                                      attention_dropout_rate=dropout, compute_dtype=dtype, ffn_activation='gelu_tanh',
+                                      position_encoding='learned', max_positions=paper_positions, embedding_layernorm=True,
+                                      embedding_scale=1.0)
     head = SoftMaxHead([1024, 512, 256, 128], V)
     return ClickstreamTransformer({'items': ['asin']}, {'items': vocab}, {'items': 64}, head, value_to_head='[MASK]',
                                   num_encoder_layers=2, num_attention_heads=2, dropout_rate=dropout, compute_dtype=dtype)
@@ -55,13 +66,17 @@ def main():
                     help='decoupled weight decay (AdamW; the paper uses 0.01) on every weight matrix and embedding table, not on '
                          'biases and LayerNorm vectors (optim.no_decay_params); default: none.  The paper\'s recipe in full: '
                          '--clipnorm 5 --warmup 100 --weight_decay 0.01')
+    ap.add_argument('--paper_model', action='store_true',
+                    help='the BERT4Rec paper\'s model (learned positions, GELU, normalised input stage, attention dropout, tied head '
+                         'with its transform) instead of the reference\'s; a measurement, no reference oracle')
     a = ap.parse_args()
     from bert4clickpath_amd import input_pipeline, optim
     from bert4clickpath_amd.clickstream_transformer.training_utils import WarmupLinearDecay
     from bert4clickpath_amd.clickstream_transformer import transformer as T
     data = input_pipeline.BeautyCloze(a.data)
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
-    model = build_model(data.V, a.dropout, dtype).cuda()
+    longest = int(np.diff(data.offsets).max()) + 3       # [CLS] [SEP] items [SEP]
+    model = build_model(data.V, a.dropout, dtype, paper_positions=longest if a.paper_model else None).cuda()
     lr = WarmupLinearDecay(1e-3, a.warmup, max(a.steps, a.warmup + 1)) if a.warmup > 0 else 1e-3
     opt = optim.Adam(model.parameters(), learning_rate=lr, global_clipnorm=a.clipnorm, weight_decay=a.weight_decay,
                      exclude_from_weight_decay=optim.no_decay_params(model) if a.weight_decay is not None else ())
@@ -101,7 +116,7 @@ def main():
                                            num_items=data.V)
             _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, candidates=cand)
             shits += float(h.sum()); sndcg += float(nd.sum())
-    out = {'what': 'Amazon Beauty, HIP path', 'dtype': a.dtype, 'steps': a.steps, 'batch': a.batch,
+    out = {'what': 'Amazon Beauty, HIP path' + (', the BERT4Rec paper\'s model' if a.paper_model else ''), 'dtype': a.dtype, 'steps': a.steps, 'batch': a.batch,
            'dropout': a.dropout, 'hitrate@10': 100.0 * hits / n, 'ndcg@10': 100.0 * ndcg / n, 'n_eval': int(n),
            'train_seconds': train_s, 'loss_curve': losses}
     if a.exclude_seen:

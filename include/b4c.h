@@ -300,6 +300,22 @@ int b4c_add_dropout_layernorm_bwd_ws(const void *dout, const void *z, const floa
                                      float dropout_rate, uint64_t seed, void *workspace, int64_t workspace_bytes, int dtype,
                                      void *stream);
 
+/* PLAIN LAYERNORM over rows (no reference counterpart: the transform of the paper's masked-item head, head.py `transform`):
+ *   out = (x - mean) * rstd * gamma + beta;  stats[row] = {mean, rstd}   (biased variance, eps inside the root)
+ * no residual, no dropout; x, out `dtype` [rows][d], d % 8 == 0, d <= 1024; the row body of b4c_add_dropout_layernorm_fwd.
+ * b4c_layernorm_bwd: dx = rstd * (a - mean_j(a) - xhat * mean_j(a * xhat)), a = dout * gamma, xhat from the saved stats;
+ *   dgamma += sum_rows dout * xhat, dbeta += sum_rows dout (fp32 [d], ADDED to) through per-workgroup sums in the workspace
+ *   (b4c_layernorm_bwd_workspace_bytes, required) added in a fixed order: no float atomics, the same bits on every launch.
+ *   gate (or NULL): dx is multiplied by act'(gate[row][j]) (pitch ld_gate) before it is stored -- the activation in FRONT of
+ *   the norm: gate_act B4C_ACT_RELU = (gate > 0), gate = the activation or its pre-activation; a GELU = its derivative at the
+ *   saved pre-activation (the `pre` output of b4c_gemm_nt_act), evaluated in fp32 as b4c_gemm_nt_act's gate is. */
+int b4c_layernorm_fwd(const void *x, const float *gamma, const float *beta, void *out, float *stats, int64_t rows, int d,
+                      float eps, int dtype, void *stream);
+int64_t b4c_layernorm_bwd_workspace_bytes(int64_t rows, int d);
+int b4c_layernorm_bwd(const void *dout, const void *x, const float *stats, const float *gamma, void *dx, float *dgamma,
+                      float *dbeta, int64_t rows, int d, const void *gate, int ld_gate, int gate_act, void *workspace,
+                      int64_t workspace_bytes, int dtype, void *stream);
+
 /* ---- R11: [MASK]-position index generation and row gather -----------------------------
  * replaces _gather_output_by_raw_value (clickstream_transformer.py:260-297):
  * tf.where(raw == value) row-major, ragged per batch row, gather_nd, to_tensor(0).
@@ -616,6 +632,31 @@ int b4c_embed_concat_pe_fwd_packed(int n_feat, const int64_t *const *h_ids, cons
                                    void *out, int ld_out, uint8_t *key_pad, int B, int S, int d_model,
                                    float dropout_rate, uint64_t seed, const int32_t *token_src, int64_t n_tokens,
                                    int dtype, void *stream);
+/* EMBEDDING STAGE WITH LAYERNORM (no reference counterpart: the input stage of the BERT4Rec paper), one pass.  The arguments
+ * of b4c_embed_concat_pe_fwd_packed (token_src == NULL: the dense layout, T = B*S rows) plus gamma, beta (fp32 [d_model]), eps
+ * and stats (fp32 [T][2] = {mean, rstd}, may be NULL).  Per output row t, in fp32:
+ *   pre  = scale * (concat_f | sum_f) table_f[ids_f[ts]] + pe[ts % S],  ts = token_src ? token_src[t] : t
+ *   mean = sum(pre) / d,  var = sum((pre - mean)^2) / d  (biased),  rstd = 1 / sqrt(var + eps)
+ *   out  = keep(e) / (1 - rate) * (gamma * (pre - mean) * rstd + beta),  e = t*d_model + col  (the numbering of the plain stage)
+ * key_pad as b4c_embed_concat_pe_fwd.  pre never reaches memory and is not rounded to `dtype` before the statistics; pad rows of
+ * the dense layout are normalised like any other.  d_model % 8 == 0, d_model <= 1024 (the rows of b4c_add_dropout_layernorm_fwd).
+ * b4c_embed_ln_bwd: dout [T][ld_dout] -> dpre [T][ld_dpre] (`dtype`), dgamma / dbeta (fp32 [d_model], ADDED to); pre is gathered
+ * again from the same ids, tables, pe and scale, xhat = (pre - mean) * rstd from the saved stats:
+ *   g = keep(e) / (1 - rate) * dout;  dbeta += sum_t g;  dgamma += sum_t g * xhat
+ *   a = g * gamma;  dpre = rstd * (a - mean_j(a) - xhat * mean_j(a * xhat))
+ * dgamma / dbeta as b4c_layernorm_bwd: fixed-order sums through the workspace (b4c_embed_ln_bwd_workspace_bytes(T, d_model),
+ * required), no float atomics.  The tables' and a learned pe's gradients are those of the plain stage with dout = dpre and
+ * dropout_rate = 0: b4c_embed_concat_pe_bwd(_sorted_ws) and b4c_pos_table_bwd. */
+int b4c_embed_ln_fwd(int n_feat, const int64_t *const *h_ids, const float *const *h_tables, const int *h_dims,
+                     const int64_t *h_rows, const float *pe, float scale, const float *gamma, const float *beta, float eps,
+                     void *out, int ld_out, float *stats, uint8_t *key_pad, int B, int S, int d_model, float dropout_rate,
+                     uint64_t seed, const int32_t *token_src, int64_t n_tokens, int dtype, void *stream);
+int64_t b4c_embed_ln_bwd_workspace_bytes(int64_t rows, int d_model);
+int b4c_embed_ln_bwd(int n_feat, const int64_t *const *h_ids, const float *const *h_tables, const int *h_dims,
+                     const int64_t *h_rows, const float *pe, float scale, const float *gamma, const float *stats,
+                     const void *dout, int ld_dout, void *dpre, int ld_dpre, float *dgamma, float *dbeta, int B, int S,
+                     int d_model, float dropout_rate, uint64_t seed, const int32_t *token_src, int64_t n_tokens,
+                     void *workspace, int64_t workspace_bytes, int dtype, void *stream);
 int b4c_attn_fwd_varlen(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
                         float *lse, int B, int max_len, int H, int dh, int dtype, void *stream);
 int b4c_attn_bwd_varlen(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, const void *o,
