@@ -11,6 +11,7 @@ import torch
 
 from oracle import numpy_ref as nr
 from oracle.torch_ref import dropout, layer_norm
+from paper_encoder_ref import act
 
 
 def elem_index(b, h, q, k, H, S_arg):
@@ -48,10 +49,10 @@ def attention_qkv(qkv, H, dh, key_pad, keep, rate):
     return o.permute(0, 2, 1, 3).reshape(B, S, d), lse
 
 
-def encoder_forward(x, key_pad, P, num_layers, num_heads, rate, attn_rate, keep_res, keep_attn):
+def encoder_forward(x, key_pad, P, num_layers, num_heads, rate, attn_rate, keep_res, keep_attn, activation='relu'):
     """The post-LN encoder stack on x [B, S, d] float64 (the input dropout already applied): oracle/torch_ref.transformer_forward's
     layer lines with the attention dropout added.  P: 'enc_layers.<i>.mha.wq.kernel' ...; keep_res['l<i>.1' | 'l<i>.2'] [B, S, d],
-    keep_attn[i] [B, H, S, S]."""
+    keep_attn[i] [B, H, S, S]; activation: that of the feed-forward ('relu' | 'gelu' | 'gelu_tanh', paper_encoder_ref.act)."""
     B, S, d = x.shape
     depth = d // num_heads
     neg = key_pad.to(x.dtype)[:, None, None, :] * -1e9
@@ -67,6 +68,61 @@ def encoder_forward(x, key_pad, P, num_layers, num_heads, rate, attn_rate, keep_
         o = o.permute(0, 2, 1, 3).reshape(B, S, d)
         attn = dropout(lin(o, 'mha.dense'), rate, keep_res['l%d.1' % i])
         out1 = layer_norm(x + attn, P[pre + 'layernorm1.gamma'], P[pre + 'layernorm1.beta'], nr.LN_EPS)
-        f = dropout(lin(torch.relu(lin(out1, 'ffn.0')), 'ffn.1'), rate, keep_res['l%d.2' % i])
+        f = dropout(lin(act(activation, lin(out1, 'ffn.0')), 'ffn.1'), rate, keep_res['l%d.2' % i])
         x = layer_norm(out1 + f, P[pre + 'layernorm2.gamma'], P[pre + 'layernorm2.beta'], nr.LN_EPS)
     return x
+
+
+def attention_grads(qkv, do, key_pad, B, S, H, dh, keep, rate):
+    """dense layout: qkv [B*S, 3*H*dh], do [B*S, H*dh] (any dtype; taken to float64 as they are), key_pad [B, S], keep [B, H, S, S] or
+    None -> (o [B*S, H*dh], lse [B, H, S], d qkv) in float64, the gradient by autograd through attention_qkv"""
+    q64 = qkv.double().cpu().requires_grad_(True)
+    o, lse = attention_qkv(q64.view(B, S, -1), H, dh, key_pad, keep, rate)
+    o = o.reshape(B * S, H * dh)
+    o.backward(do.double().cpu())
+    return o.detach(), lse.detach(), q64.grad
+
+
+# ---- exact mask recovery (tests/test_gpu_attn_dropout_routes.py; shown on this file alone by tests/test_attn_dropout_cpu.py) -----
+# q = k = 0 makes P uniform over the real keys of a sequence, so every kept, unpadded probability is the same nonzero number and
+# every dropped or padded one is exactly 0.  A one-hot V (dO) then copies a window of dh keys (queries) of P~ into o (dV).
+def recovery_passes(S, dh):
+    return -(-S // dh)
+
+
+def recovery_operands(lens, H, dh, p, dtype):
+    """pass p over sequences of the lengths `lens`, stored one after the other -> (qkv [T, 3*H*dh], do [T, H*dh]):
+    q = k = 0; V row k of a sequence = one-hot at column k - p*dh for p*dh <= k < (p+1)*dh, zero elsewhere; dO row q likewise."""
+    d, off = H * dh, np.concatenate([[0], np.cumsum(lens)])
+    qkv = torch.zeros(int(off[-1]), 3 * d, dtype=dtype)
+    do = torch.zeros(int(off[-1]), d, dtype=dtype)
+    for b, L in enumerate(lens):
+        i = torch.arange(p * dh, max(p * dh, min((p + 1) * dh, L)))          # (empty: the sequence ends before this window)
+        for h in range(H):
+            qkv[off[b] + i, 2 * d + h * dh + i - p * dh] = 1.0
+            do[off[b] + i, h * dh + i - p * dh] = 1.0
+    return qkv, do
+
+
+def recovery_collect(fwd, bwd, o, dv, lens, H, dh, p):
+    """books pass p: fwd[b][h][q][p*dh + c] = (o[q][h][c] != 0), bwd[b][h][p*dh + c][k] = (dV[k][h][c] != 0); fwd, bwd: lists of
+    bool [H, L, L] per sequence ([h][query][key]); o, dv: [T, H*dh] on the host.  Columns past the sequence must be zero."""
+    off = np.concatenate([[0], np.cumsum(lens)])
+    for b, L in enumerate(lens):
+        n = max(0, min(dh, L - p * dh))
+        ob = (o[off[b]:off[b] + L].reshape(L, H, dh) != 0).permute(1, 0, 2)          # [h][q][c]
+        vb = (dv[off[b]:off[b] + L].reshape(L, H, dh) != 0).permute(1, 2, 0)         # [h][c][k]
+        assert not ob[:, :, n:].any() and not vb[:, n:, :].any(), ('a column past the window is nonzero', b, p)
+        fwd[b][:, :, p * dh:p * dh + n] = ob[:, :, :n]
+        bwd[b][:, p * dh:p * dh + n, :] = vb[:, :n, :]
+
+
+def recovery_pads(B, S):
+    """key bytes [B, S] of the recovery cases: sequence 0 pads its last 4 keys, sequence 1 the keys 5 .. S-2 (whole key tiles in the
+    middle), as tests/test_gpu_kernels.py::test_attention_fwd_bwd; key 0 always stays real (a sequence without any real key has
+    no masked softmax to recover: the kernels and the reference fall back to uniform weights over the pads)."""
+    pad = torch.zeros(B, S, dtype=torch.uint8)
+    pad[0, max(S - 4, 1):] = 1
+    if B > 1:
+        pad[1, 5:max(S - 1, 5)] = 1
+    return pad

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_dropout_ref as ref
 from attn_dropout_ref import elem_index
 
 H, B = 2, 2
@@ -39,6 +40,33 @@ def test_kept_fraction_and_rate_zero(lib):
     assert m.size == 6400
     assert 0.70 <= float(m.mean()) <= 0.80          # 0.75 +- 9 sigma of the binomial (sigma = 0.0054)
     assert _mask(lib, 99, 40, 0.0).all()
+
+
+@pytest.mark.parametrize('S,dh', [(10, 4), (22, 8), (37, 16)])      # S > dh: 3 passes each; 22, 37: S4 != S; 10: a pass of two keys
+def test_recovery_construction_on_the_restatement(S, dh):
+    """The harness of tests/test_gpu_attn_dropout_routes.py, shown on the float64 restatement alone: with q = k = 0 and the one-hot
+    V / dO of pass p, the nonzero pattern of o and of dV over ceil(S / dh) passes IS the regenerated mask AND NOT pad."""
+    from bert4clickpath_amd import ops
+    Bn, rate, seed = 2, 0.25, 0xC0FFEE + S
+    lens = [S] * Bn
+    pad = ref.recovery_pads(Bn, S)
+    assert pad[0, S - 4:].all() and pad[1, 5:S - 1].all() and int(pad.sum()) == 4 + S - 6
+    keep = ops.attn_keep_mask(seed, Bn, H, S, rate)
+    fwd = [torch.zeros(H, S, S, dtype=torch.bool) for _ in lens]
+    bwd = [torch.zeros(H, S, S, dtype=torch.bool) for _ in lens]
+    assert ref.recovery_passes(S, dh) == 3
+    for p in range(ref.recovery_passes(S, dh)):
+        qkv, do = ref.recovery_operands(lens, H, dh, p, torch.float64)
+        o, lse, g = ref.attention_grads(qkv, do, pad, Bn, S, H, dh, keep, rate)
+        d = H * dh
+        assert not g[:, :2 * d].any()                                   # dQ, dK: exactly zero
+        real = (pad == 0).sum(1).double()
+        assert float((lse - real.log()[:, None, None]).abs().max()) < 1e-12
+        ref.recovery_collect(fwd, bwd, o, g[:, 2 * d:], lens, H, dh, p)
+    for b in range(Bn):
+        want = keep[b] & (pad[b] == 0)[None, None, :]
+        assert torch.equal(fwd[b], want) and torch.equal(bwd[b], want), b
+        assert want.any() and not want.all() and not want[:, :, pad[b] != 0].any()
 
 
 def test_abi_version_stays_12(lib):
