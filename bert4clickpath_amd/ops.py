@@ -1573,6 +1573,62 @@ def candidate_rank_rows(scores, V, cand, labels=None, k=0):
                                                 _st()), 'candidate_rank_rows')
     return rank, idx
 
+
+# ---- Cloze batches (include/b4c.h "Cloze batches"): model inputs and padded labels from a CSR data set on the device ----
+CLOZE_TRAIN, CLOZE_EVAL = 0, 1
+CLOZE_MAX_WIDTH, CLOZE_MAX_LABELS = 1021, 64
+
+
+def cloze_batch(items, offsets, seq_idx, W, mode, seed, masked_percentage=0.4, max_masked=10, M=None):
+    """-> (items_out int64 [B, W], labels_padded fp32 [B, M], n_masked int32 [B]) (b4c_cloze_batch): row b is sequence
+    g = seq_idx[b] of the CSR data set (items int32 [N] label-space indices, offsets int64 [n_seq + 1]) as the model's
+    {'asin': items} input -- index + 10, [MASK] = 1 at the masked positions, 0 past the row's length -- with the masked items'
+    indices in position order, padded with -1.  mode CLOZE_TRAIN: the last item dropped, n = n_masked(L) positions drawn by the
+    keys b4c_rand64(seed, (g << 10) | p) (cloze_choose_host regenerates them); CLOZE_EVAL: the last position masked.
+    M: label columns, default max_masked (TRAIN) / 1 (EVAL).  Stream-ordered, nothing is read back: seq_idx is NOT checked
+    against n_seq here, and a sequence longer than W is cut at W -- cloze_batches.DeviceCloze checks both on its host copies."""
+    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
+        raise B4CError('cloze_batch: items must be an int32 [N] tensor of item indices')
+    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
+        raise B4CError('cloze_batch: offsets must be an int64 [n_seq + 1] tensor')
+    if not isinstance(seq_idx, torch.Tensor) or seq_idx.dim() != 1 or seq_idx.dtype != torch.int32:
+        raise B4CError('cloze_batch: seq_idx must be an int32 [B] tensor of sequence indices')
+    B, W, mode, max_masked = seq_idx.shape[0], int(W), int(mode), int(max_masked)
+    if mode not in (CLOZE_TRAIN, CLOZE_EVAL):
+        raise B4CError('cloze_batch: mode %d (CLOZE_TRAIN = 0, CLOZE_EVAL = 1)' % mode)
+    if not 1 <= W <= CLOZE_MAX_WIDTH:
+        raise B4CError('cloze_batch: W = %d (1 .. %d)' % (W, CLOZE_MAX_WIDTH))
+    M = (max_masked if mode == CLOZE_TRAIN else 1) if M is None else int(M)
+    if not mode <= M <= CLOZE_MAX_LABELS or (mode == CLOZE_TRAIN and not 0 <= max_masked <= M):
+        raise B4CError('cloze_batch: max_masked = %d, M = %d (0 <= max_masked <= M <= %d; EVAL: M >= 1)' % (max_masked, M, CLOZE_MAX_LABELS))
+    if mode == CLOZE_TRAIN and not 0.0 <= float(masked_percentage) <= 1.0:
+        raise B4CError('cloze_batch: masked_percentage %g outside [0, 1]' % masked_percentage)
+    if not 0 <= int(seed) < (1 << 64) or offsets.shape[0] - 1 > (1 << 31) - 1:
+        raise B4CError('cloze_batch: seed %d (0 .. 2^64) / %d sequences (int32 seq_idx)' % (seed, offsets.shape[0] - 1))
+    _cuda(items, offsets, seq_idx)
+    items, offsets, seq_idx = items.contiguous(), offsets.contiguous(), seq_idx.contiguous()
+    dev = items.device
+    out = torch.empty(B, W, dtype=torch.int64, device=dev)
+    lab = torch.empty(B, M, dtype=torch.float32, device=dev)
+    nm = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return out, lab, nm
+    with _record('cloze_batch', B * (W * 12 + M * 4 + 24)):
+        L.check(L.lib().b4c_cloze_batch(_p(items), _p(offsets), _p(seq_idx), B, W, mode, float(masked_percentage), max_masked,
+                                        int(seed), _p(out), W, _p(lab), M, M, _p(nm), _st()), 'cloze_batch')
+    return out, lab, nm
+
+
+def cloze_choose_host(seed, g, L, n):
+    """-> int32 numpy [n]: the positions of [0, L) that cloze_batch masks in TRAIN mode for sequence g, ascending
+    (b4c_cloze_choose: the kernel's rule evaluated on the host, no device work)."""
+    import numpy as np
+    from . import _lib              # (the argument L, the header's name, hides this module's alias)
+    pos = np.empty(max(int(n), 0), dtype=np.int32)
+    _lib.check(_lib.lib().b4c_cloze_choose(int(seed) & 0xFFFFFFFFFFFFFFFF, int(g), int(L), int(n), pos.ctypes.data), 'cloze_choose')
+    return pos
+
+
 def adam_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul=1.0, coef=None, decay=None, blocks=None):
     """Dense Adam over a flat fp32 range (b4c_adam_step).  coef (device fp32 scalar of grad_clip_coef_): the gradient is scaled by
     grad_mul * coef[0] (b4c_adam_step_clipped).  decay: decoupled weight decay -- the elements of the 64-element blocks flagged in

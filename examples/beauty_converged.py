@@ -26,13 +26,17 @@ from examples.beauty_hitrate import build_model  # noqa: E402
 
 
 def evaluate(model, data, batch=1024):
-    """-> (val_loss, HitRate@10 %, NDCG@10 %) on every user: mask the last item, rank over all V items."""
+    """-> (val_loss, HitRate@10 %, NDCG@10 %) on every user: mask the last item, rank over all V items.
+    data: input_pipeline.BeautyCloze (host batches) or cloze_batches.DeviceCloze (batches built on the device)."""
     tot = hits = ndcg = n = 0.0
     with torch.no_grad():
         for b in data.eval_batches(batch):
-            items = torch.from_numpy(b['ids'])[:, 2:-1].contiguous().cuda()
-            lab = torch.from_numpy(b['labels']).cuda()
-            flat = torch.from_numpy(b['flat_idx']).cuda()
+            if 'items' in b:           # DeviceCloze: one [MASK] per row, the (B, 1) labels are the compact labels
+                items, lab, flat = b['items'], b['labels_padded'].reshape(-1).to(torch.int32), None
+            else:
+                items = torch.from_numpy(b['ids'])[:, 2:-1].contiguous().cuda()
+                lab = torch.from_numpy(b['labels']).cuda()
+                flat = torch.from_numpy(b['flat_idx']).cuda()
             loss = model.cloze_loss({'asin': items}, lab, training=False, flat_idx=flat)
             _, h, nd = model.predict_topk({'asin': items}, 10, lab, flat_idx=flat)
             tot += float(loss) * h.numel()
@@ -51,10 +55,17 @@ def main():
     ap.add_argument('--dropout', type=float, default=0.1)
     ap.add_argument('--log', default=None, help='progress file (one line per epoch)')
     ap.add_argument('--data', default=os.path.join(ROOT, 'data', 'beauty_sequences.npz'))
+    ap.add_argument('--device_batches', action='store_true',
+                    help='build the training and validation batches on the device (cloze_batches.DeviceCloze); the masks are that '
+                         'kernel\'s own stream')
     a = ap.parse_args()
     from bert4clickpath_amd import checkpoint as ck, input_pipeline, optim
     from bert4clickpath_amd.clickstream_transformer import transformer as T
-    data = input_pipeline.BeautyCloze(a.data)
+    if a.device_batches:
+        from bert4clickpath_amd.cloze_batches import DeviceCloze
+        data = DeviceCloze.from_npz(a.data)
+    else:
+        data = input_pipeline.BeautyCloze(a.data)
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
     model = build_model(data.V, a.dropout, dtype, seed=1234 + a.seed).cuda()
     opt = optim.Adam(model.parameters())
@@ -70,9 +81,13 @@ def main():
         tl = 0.0
         for _ in range(a.steps_per_epoch):
             b = next(batches)
-            items = torch.from_numpy(b['ids'])[:, 2:-1].contiguous().cuda()
             opt.zero_grad()
-            loss = model.cloze_loss({'asin': items}, torch.from_numpy(b['labels_padded']).cuda(), training=True, max_masked_per_row=10)
+            if a.device_batches:
+                loss = model.cloze_loss({'asin': b['items']}, b['labels_padded'], training=True,
+                                        max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
+            else:
+                items = torch.from_numpy(b['ids'])[:, 2:-1].contiguous().cuda()
+                loss = model.cloze_loss({'asin': items}, torch.from_numpy(b['labels_padded']).cuda(), training=True, max_masked_per_row=10)
             loss.backward()
             opt.step()
             tl = loss

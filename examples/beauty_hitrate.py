@@ -69,6 +69,9 @@ def main():
     ap.add_argument('--paper_model', action='store_true',
                     help='the BERT4Rec paper\'s model (learned positions, GELU, normalised input stage, attention dropout, tied head '
                          'with its transform) instead of the reference\'s; a measurement, no reference oracle')
+    ap.add_argument('--device_batches', action='store_true',
+                    help='build the training and evaluation batches on the device (cloze_batches.DeviceCloze): no per-row host '
+                         'work and no upload per step; the masks are that kernel\'s own stream, so losses differ from the default')
     a = ap.parse_args()
     from bert4clickpath_amd import input_pipeline, optim
     from bert4clickpath_amd.clickstream_transformer.training_utils import WarmupLinearDecay
@@ -82,12 +85,20 @@ def main():
                      exclude_from_weight_decay=optim.no_decay_params(model) if a.weight_decay is not None else ())
     T.set_dropout_seed(a.seed)
     t0, losses = time.perf_counter(), []
-    for step, b in enumerate(data.train_batches(a.batch, a.seed, a.steps)):
-        ids = torch.from_numpy(b['ids'])
-        items = ids[:, 2:-1].contiguous().cuda()
+    dev_data = None
+    if a.device_batches:
+        from bert4clickpath_amd.cloze_batches import DeviceCloze
+        dev_data = DeviceCloze.from_npz(a.data)
+    for step, b in enumerate((dev_data or data).train_batches(a.batch, a.seed, a.steps)):
         opt.zero_grad()
-        loss = model.cloze_loss({'asin': items}, torch.from_numpy(b['labels']).cuda(), training=True,
-                                flat_idx=torch.from_numpy(b['flat_idx']).cuda())
+        if dev_data is not None:      # items and padded labels are on the device already; nothing is read back
+            loss = model.cloze_loss({'asin': b['items']}, b['labels_padded'], training=True,
+                                    max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
+        else:
+            ids = torch.from_numpy(b['ids'])
+            items = ids[:, 2:-1].contiguous().cuda()
+            loss = model.cloze_loss({'asin': items}, torch.from_numpy(b['labels']).cuda(), training=True,
+                                    flat_idx=torch.from_numpy(b['flat_idx']).cuda())
         loss.backward()
         opt.step()
         if step % 100 == 0 or step == a.steps - 1:
@@ -101,10 +112,13 @@ def main():
     if a.negatives and a.sampler == 'popularity':       # the training split: every sequence without its held-out last item
         train = np.concatenate([data.seq(i)[:-1] for i in range(data.n_seq)]) + NUM_RESERVED_TOKENS
         counts = cloze.item_counts(train, data.V)
-    for b in data.eval_batches(1024, a.eval_limit):
-        ids = torch.from_numpy(b['ids'])
-        items = ids[:, 2:-1].contiguous().cuda()
-        labels, flat = torch.from_numpy(b['labels']).cuda(), torch.from_numpy(b['flat_idx']).cuda()
+    for b in (dev_data or data).eval_batches(1024, a.eval_limit):
+        if dev_data is not None:      # one [MASK] per row: the (B, 1) labels are the compact labels
+            items, labels, flat = b['items'], b['labels_padded'].reshape(-1).to(torch.int32), None
+        else:
+            ids = torch.from_numpy(b['ids'])
+            items = ids[:, 2:-1].contiguous().cuda()
+            labels, flat = torch.from_numpy(b['labels']).cuda(), torch.from_numpy(b['flat_idx']).cuda()
         _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat)
         hits += float(h.sum()); ndcg += float(nd.sum()); n += h.numel()
         if a.exclude_seen:          # one [MASK] (the last item) per sequence: the rows are the sequences, in order
@@ -118,7 +132,7 @@ def main():
             shits += float(h.sum()); sndcg += float(nd.sum())
     out = {'what': 'Amazon Beauty, HIP path' + (', the BERT4Rec paper\'s model' if a.paper_model else ''), 'dtype': a.dtype, 'steps': a.steps, 'batch': a.batch,
            'dropout': a.dropout, 'hitrate@10': 100.0 * hits / n, 'ndcg@10': 100.0 * ndcg / n, 'n_eval': int(n),
-           'train_seconds': train_s, 'loss_curve': losses}
+           'train_seconds': train_s, 'loss_curve': losses, 'device_batches': bool(a.device_batches)}
     if a.exclude_seen:
         out.update({'filtered_hitrate@10': 100.0 * fhits / n, 'filtered_ndcg@10': 100.0 * fndcg / n})
     if a.negatives:

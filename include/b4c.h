@@ -506,6 +506,34 @@ int b4c_candidate_score(const void *h, int ld_h, const void *wt, int ld_w, const
 int b4c_candidate_rank_rows(const void *scores, int ld, int dtype, const int32_t *cand, int ld_c, int64_t R, int C, int V,
                             const int32_t *labels, int32_t *rank, int k, int32_t *idx, void *stream);
 
+/* ---- Cloze batches: model inputs and padded labels built on the device from a CSR data set --------------------------------
+ * replaces the host batch construction of input_pipeline.py:21-133 (drop / mask / pad) for integer item indices.
+ * The data set: items int32 [N] (label-space item indices, input id = index + NUM_RESERVED_TOKENS = index + 10), offsets
+ *   int64 [n_seq + 1]; sequence g is items[offsets[g] : offsets[g+1]], of length n_g.  seq_idx int32 [B] names the sequence
+ *   of every batch row (not range-checked against n_seq: the caller's; a negative entry is an empty row).
+ * The masking rule of a row that names sequence g:
+ *   TRAIN (mode 0): L = max(n_g - 1, 0) (the last item is held out);
+ *     n = min(max((int)((float)L * masked_percentage), 0), max_masked)  (float32 product, then truncation);
+ *     position p in [0, L) has the key k_p = b4c_rand64(seed, ((uint64_t)g << 10) | p) (csrc/common.h); the masked set is the
+ *     n positions smallest in (k_p, p) lexicographic order: p is masked iff #{q < L : (k_q, q) < (k_p, p)} < n.  A uniform draw
+ *     without replacement, and a total function of its inputs (equal keys: the lower position first).
+ *   EVAL (mode 1): L = n_g, the masked set is {L - 1} (empty for L = 0); no draw, max_masked / masked_percentage are not read.
+ * Outputs: items_out int64 [B][W] (pitch ld_items >= W; columns past W are not written): column p < L is MASK_ID (1) where
+ *   masked, else items[offsets[g] + p] + 10; columns L .. W-1 are INPUT_PAD (0) -- the {'asin': items} input of the model,
+ *   which chains [CLS] [SEP] .. [SEP] itself (S = W + 3).  labels_out fp32 [B][M] (pitch ld_lab >= M): the masked positions'
+ *   item indices in ascending position order, then LABEL_PAD (-1.0).  n_masked_out int32 [B] (may be NULL): the row's n.
+ * A row is a pure function of (seed, g, the sequence, mode, masked_percentage, max_masked): not of the batch, the rank or the
+ *   row's place in the batch.
+ * Limits: 1 <= W <= 1021 (p < 1024 in the counter), g < 2^54, 0 <= max_masked <= M <= 64 (EVAL: 1 <= M <= 64),
+ *   0 <= masked_percentage <= 1.  A sequence longer than W is the caller's error: L is clamped to W, nothing is written
+ *   outside the row.  B = 0 is a no-op.
+ * b4c_cloze_choose is the TRAIN rule on the HOST (no device work): pos[0 .. n) = the n masked positions of [0, L) for
+ *   sequence g, ascending; 0 <= n <= L <= 1021. */
+int b4c_cloze_batch(const int32_t *items, const int64_t *offsets, const int32_t *seq_idx, int B, int W, int mode,
+                    float masked_percentage, int max_masked, uint64_t seed, int64_t *items_out, int ld_items,
+                    float *labels_out, int ld_lab, int M, int32_t *n_masked_out, void *stream);
+int b4c_cloze_choose(uint64_t seed, int64_t g, int L, int n, int32_t *pos);
+
 /* ---- R16: Adam (Keras semantics, eps outside the sqrt) ------------------------------------
  * replaces tf.keras.optimizers.Adam(1e-3, .9, .999, 1e-9) (main.py:87), dense update over a flat
  * fp32 arena: m,v EMA; p -= lr_t * m / (sqrt(v) + eps), lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (host).
