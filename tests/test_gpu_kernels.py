@@ -10,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import numpy_ref as nr  # noqa: E402
+import local_bounds as lb  # noqa: E402
 
 
 @pytest.fixture(scope='module')
@@ -215,6 +216,22 @@ def test_add_dropout_layernorm(ops, dtype, d, rate):
 
 
 # ---------------------------------------------------------------------------------------------
+def _attn_local(qd, pad, dod, o, lse, dqkv, grad, B, S, H, dh):
+    """Beside the whole-tensor assertions: o, lse, dq, dk, dv each ELEMENT against its own derived bound (tests/local_bounds.py), on
+    the routes tabulated there (bf16 MFMA at head depths 32 / 64, the fp32 row kernels)."""
+    if qd.dtype == torch.bfloat16 and dh not in (32, 64):
+        return
+    d = H * dh
+    res = lb.attn_dense(qd.float().cpu(), pad, dod.float().cpu(), B, S, H, dh, 'row_f32' if qd.dtype == torch.float32 else 'mfma')
+    if grad is not None:          # the restated backward of local_bounds.py is the autograd reference
+        assert float((torch.cat([res[n][0] for n in ('dq', 'dk', 'dv')], 1) - grad).abs().max()) < 1e-9
+    got = {'dq': dqkv[:, :d], 'dk': dqkv[:, d:2 * d], 'dv': dqkv[:, 2 * d:]}
+    if o is not None:
+        got.update(o=o, lse=lse)
+    for n, t in got.items():
+        lb.check(n, t, *res[n])
+
+
 def _attn_ref(qkv, pad, B, S, H, dh):
     d = H * dh
     q, k, v = [qkv[:, i * d:(i + 1) * d].reshape(B, S, H, dh).permute(0, 2, 1, 3) for i in range(3)]
@@ -252,6 +269,7 @@ def test_attention_fwd_bwd(ops, dtype, B, S, H, dh):
     # padded keys receive exactly zero dK / dV
     kv_grad = dqkv[:, d:].reshape(B, S, 2 * d)
     assert float(kv_grad[0, S - 4:].abs().max()) == 0.0
+    _attn_local(qd, pad, dod, o, lse, dqkv, q64.grad, B, S, H, dh)
     if dtype == torch.bfloat16 and S > 256 and dh in (32, 64):
         assert ops.L.lib().b4c_attn_bwd_workspace_bytes(B, S, H, dh, ops.L.BF16) == B * S * H * dh * 4     # the MFMA route ran
         again = ops.attn_bwd(qd, pad.cuda(), o, dod, lse, B, S, H, dh)
@@ -280,6 +298,7 @@ def test_attention_bwd_more_items_than_workgroups(ops):
     dqkv = ops.attn_bwd(qd, pad.cuda(), o, dod, lse, B, S, H, dh)
     assert rel_err(dqkv, q64.grad) < 2.5e-2
     assert float(dqkv.reshape(B, S, 3 * d)[::7].abs().max()) == 0.0
+    _attn_local(qd, pad, dod, o, lse, dqkv, q64.grad, B, S, H, dh)
     again = ops.attn_bwd(qd, pad.cuda(), o, dod, lse, B, S, H, dh)     # item order differs from run to run, the result does not
     assert torch.equal(again, dqkv)
 
@@ -308,6 +327,7 @@ def test_attention_bwd_zero_do_tiles(ops, B, S, H, dh):
     o_ref.backward(dod.double().cpu())
     dqkv = ops.attn_bwd(qd, pad.cuda(), o, dod, lse, B, S, H, dh)
     assert rel_err(dqkv, q64.grad) < 2.5e-2
+    _attn_local(qd, pad, dod, o, lse, dqkv, q64.grad, B, S, H, dh)
     dq = dqkv[:, :d].reshape(B, S, d)
     assert float(dq[1, 32:].abs().max()) == 0.0 and float(dq[0, 64:S - 1].abs().max()) == 0.0
     if B > 2:

@@ -85,6 +85,12 @@ def test_attn_mq_kernels_match_fp64(dtype, H, dh, smax, mmax, pad):
     for b in range(B):
         if moff[b + 1] == moff[b]:
             assert float(dkv[int(cu[b]):int(cu[b + 1])].abs().max()) == 0.0
+    # beside the whole-tensor bounds: every element of o, lse, dq and of dk and dv SEPARATELY against its own derived bound
+    import local_bounds as lb
+    d = H * dh
+    res = lb.attn_mq(q, kv, cu, moff, go, H, dh, 'row_f32' if dtype == torch.float32 else 'mq_mfma', key_pad)
+    for n, t in {'o': o, 'lse': lse, 'dq': dq, 'dk': dkv[:, :d], 'dv': dkv[:, d:]}.items():
+        lb.check(n, t, *res[n])
 
 
 # ------------------------------------------------------------------------------------------------------------------

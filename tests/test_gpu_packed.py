@@ -10,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import torch_ref as tr  # noqa: E402
+import local_bounds as lb  # noqa: E402
 
 
 @pytest.fixture(scope='module')
@@ -82,6 +83,11 @@ def test_varlen_attention_matches_fp64(gpu, lens, H, dh):
     o_ref.backward(do.double())
     dqkv = ops.attn_bwd(qd, key_pad, o, dod, lse, B, S_max, H, dh, cu)
     assert rel_err(dqkv, q64.grad) < 2.5e-2
+    # beside the whole-tensor norms: every element of o, lse, dq, dk, dv against its own derived bound (tests/local_bounds.py)
+    res = lb.attn_packed(qkv.float(), cu.cpu(), do.float(), H, dh, 'mfma')
+    got = {'o': o, 'lse': lb.packed_lse(lse.cpu(), cu.cpu()), 'dq': dqkv[:, :d], 'dk': dqkv[:, d:2 * d], 'dv': dqkv[:, 2 * d:]}
+    for n, t in got.items():
+        lb.check(n, t, *res[n])
     again = ops.attn_bwd(qd, key_pad, o, dod, lse, B, S_max, H, dh, cu)
     assert torch.equal(again, dqkv)
     # a uniform-length packed batch is the dense batch: same kernels, same bits

@@ -302,6 +302,12 @@ def test_varlen_attention_random_ragged_batches(ops, seed, B, smax, H, dh, with_
     o_ref.backward(do.double())
     dqkv = ops.attn_bwd(qkv.cuda(), key_pad, o, do.cuda(), lse, B, S_max, H, dh, cu)
     assert err(dqkv, q64.grad) < 2.5e-2
+    # beside the whole-tensor norms: every element against its own derived bound (tests/local_bounds.py)
+    import local_bounds as lb
+    res = lb.attn_packed(qkv.float(), cu_h, do.float(), H, dh, 'mfma')
+    got = {'o': o, 'lse': lb.packed_lse(lse.cpu(), cu_h), 'dq': dqkv[:, :d], 'dk': dqkv[:, d:2 * d], 'dv': dqkv[:, 2 * d:]}
+    for n, t in got.items():
+        lb.check(n, t, *res[n])
     assert torch.equal(ops.attn_bwd(qkv.cuda(), key_pad, o, do.cuda(), lse, B, S_max, H, dh, cu), dqkv)     # run-to-run identical
 
 
@@ -354,6 +360,13 @@ def test_logits_free_softmax_ce_any_shape_and_clip_regime(ops, seed, R, V, K, sc
     assert np.linalg.norm(dh.float().cpu().numpy() - dh_o) < 1e-2 * max(np.linalg.norm(dh_o), 1e-3 * g * np.sqrt(R) * wn) + bf16_abs * np.sqrt(R) * wn
     assert np.linalg.norm(dW.cpu().numpy() - dW_o.T) < 1e-2 * max(np.linalg.norm(dW_o), 1e-3 * g * np.linalg.norm(h)) + bf16_abs * np.linalg.norm(h)
     assert np.linalg.norm(db.cpu().numpy() - db_o) < 1e-2 * max(np.linalg.norm(db_o), 1e-3 * g * np.sqrt(R)) + bf16_abs * np.sqrt(R)
+    # beside the norms: dh, dW, db each ELEMENT against its own derived bound (tests/local_bounds.py; an entry whose clip decision
+    # fp32 cannot settle adds its contribution to the bounds it feeds -- a drawn case may have more of those than a committed one)
+    import local_bounds as lb
+    ref = lb.vocab_ref(h, W, b, y, variant)
+    lb.check('dh', dh, *ref['dh'])
+    lb.check('dW', dW, *ref['dW'])
+    lb.check('db', db, *ref['db'])
     ign = y < 0
     if ign.any():
         assert np.all(item[ign] == 0) and np.all(dh.float().cpu().numpy()[ign] == 0)
@@ -426,6 +439,11 @@ def test_masked_query_attention_random_ragged_batches(ops, seed, B, smax, mmax, 
     for b in range(B):
         if nq[b] == 0:
             assert float(dkv[int(cu[b]):int(cu[b + 1])].abs().max()) == 0.0
+    # beside the whole-tensor bounds: every element of o, lse, dq, dk, dv against its own derived bound (tests/local_bounds.py)
+    import local_bounds as lb
+    res = lb.attn_mq(q, kv, cu, moff, go, H, dh, 'row_f32' if dt == torch.float32 else 'mq_mfma', key_pad)
+    for n, t in {'o': o, 'lse': lse, 'dq': dq, 'dk': dkv[:, :d], 'dv': dkv[:, d:]}.items():
+        lb.check(n, t, *res[n])
 
 
 @settings(**SET)
@@ -672,6 +690,14 @@ def test_padded_layout_attention_any_shape(ops, seed, B, S, H, dh, dtype, pad_mo
     for b in range(B):
         if bool(live[b]) and int(pad[b].sum()):
             assert float(kv_grad[b][pad[b].bool()].abs().max()) == 0.0
+    # beside the whole-tensor norms: every element against its own derived bound, on the routes tabulated in tests/local_bounds.py
+    # (bf16 at head depths 32 / 64: the MFMA kernels; fp32: the row kernels)
+    if dt == torch.float32 or dh in (32, 64):
+        import local_bounds as lb
+        res = lb.attn_dense(qd.float().cpu(), pad, do.float().cpu(), B, S, H, dh, 'row_f32' if dt == torch.float32 else 'mfma')
+        got = {'o': o, 'lse': lse, 'dq': dqkv[:, :d], 'dk': dqkv[:, d:2 * d], 'dv': dqkv[:, 2 * d:]}
+        for n, t in got.items():
+            lb.check(n, t, *res[n])
 
 
 @settings(**SET)

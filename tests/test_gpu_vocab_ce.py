@@ -56,7 +56,8 @@ CASES = [
     (300, 1000, 128, 0.3, 0, 'tf'),          # nothing clipped
     (300, 1000, 128, 1.6, 5, 'tf'),          # many probabilities < 1e-7, some rows > 1 - 1e-7
     (77, 50, 64, 0.5, 3, 'tf'),              # one partial vocabulary tile, partial token tile
-    (130, 129, 64, 2.0, 0, 'tf'),            # vocabulary tail of one row
+    (130, 129, 64, 2.0, 0, 'tf'),            # clip regime with a one-column tail tile (at this scale the tail column and the last
+                                             # rows carry next to no gradient: the tail edges are pinned in test_gpu_vocab_ce_local.py)
     (257, 700, 128, 1.2, 7, 'plain'),
     (1, 300, 128, 1.0, 0, 'tf'),
 ]
