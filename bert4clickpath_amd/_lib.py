@@ -29,7 +29,7 @@ class TNDesc(ctypes.Structure):
 
 # The header is the one place a signature or a constant is written: the binding below is derived from its text.
 _CTYPES = {'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
-           'uint64_t': ctypes.c_uint64}
+           'uint64_t': ctypes.c_uint64, 'uint32_t': ctypes.c_uint32}
 
 
 def _header_text(header_path):

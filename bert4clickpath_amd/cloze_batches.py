@@ -1,11 +1,20 @@
-"""Cloze training and evaluation batches built on the device (ops.cloze_batch, include/b4c.h "Cloze batches").
+"""Cloze training and evaluation batches built on the device (ops.cloze_batch_windows, include/b4c.h "Cloze batches").
 
 input_pipeline.BeautyCloze walks every batch row by row on the host and the training loop then uploads ids and labels;
 DeviceCloze keeps the data set's CSR form on the device and leaves `items` and `labels_padded` there, in the layout
 model.cloze_loss(items, labels_padded, max_masked_per_row=M, n_real_tokens=n) takes without a read-back.  The host keeps the
 offsets: row widths and the token count n_real_tokens come from them with numpy, nothing is read back from the device.
-The masking rule is a pure function of (seed, sequence index, sequence): a row does not depend on the batch it is in, on the
-rank or on the batch size.  The random stream is this build's own (the reference's shuffle is unseeded)."""
+The masking rule is a pure function of (seed, sequence index, window start, the window's items): a row does not depend on the
+batch it is in, on the rank or on the batch size.  The random stream is this build's own (the reference's shuffle is unseeded,
+SURVEY.md D9).
+
+A row is a WINDOW of a sequence.  By default every sequence is one window (all but its last item for training, all of it for
+evaluation).  The BERT4Rec paper's data protocol is four constructor arguments: max_len / stride cut the training view of a long
+sequence into sliding windows and keep the most recent max_len positions for evaluation, holdout=2 holds out the penultimate
+item for validation and the last for test, last_item_rate adds training rows whose only masked position is the last one.  The
+window table is built once with numpy and uploaded once; a batch names its windows by index."""
+import collections
+
 import numpy as np
 import torch
 
@@ -15,12 +24,36 @@ from .input_pipeline import EVAL, MASKED_PERCENTAGE, MAX_MASKED_ITEMS, TRAIN
 _MODES = {TRAIN: ops.CLOZE_TRAIN, EVAL: ops.CLOZE_EVAL, ops.CLOZE_TRAIN: ops.CLOZE_TRAIN, ops.CLOZE_EVAL: ops.CLOZE_EVAL}
 
 
+_SPLITS = ('test', 'valid')
+Windows = collections.namedtuple('Windows', 'seq start len')       # host int32 arrays [n_windows]
+
+
+def window_table(lengths, max_len=None, stride=None, holdout=1):
+    """-> Windows: the training windows of sequences of `lengths` items, sequence by sequence.  The training view of a sequence
+    of n items is [0, T), T = max(n - holdout, 0).  max_len None: one window (0, T) each.  Otherwise T <= max_len: one window
+    (0, T), none for T = 0; T > max_len: windows of max_len items at the starts T - max_len - j stride, j = 0, 1, .. while
+    positive, then at 0 -- 1 + ceil((T - max_len) / stride) of them, the first ending at T.  No Python loop over sequences."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    T = np.maximum(lengths - holdout, 0)
+    if max_len is None:
+        return Windows(np.arange(len(T), dtype=np.int32), np.zeros(len(T), np.int32), T.astype(np.int32))
+    count = np.where(T > 0, 1 + -(-np.maximum(T - max_len, 0) // stride), 0)
+    seq = np.repeat(np.arange(len(T), dtype=np.int64), count)
+    j = np.arange(len(seq), dtype=np.int64) - (np.cumsum(count) - count)[seq]
+    start = np.maximum(T[seq] - max_len - j * stride, 0)
+    return Windows(seq.astype(np.int32), start.astype(np.int32), np.minimum(T[seq], max_len).astype(np.int32))
+
+
 class DeviceCloze:
     """items: item indices of every sequence back to back (label space: input id = 10 + index), offsets [n_seq + 1]: their
     CSR bounds -- numpy arrays or CPU tensors, as data/beauty_sequences.npz holds them.  V: vocabulary size (labels are float32,
-    the reference's format, and must be exact: V <= 2^24).  device=None keeps the host side only (no batches can be built)."""
+    the reference's format, and must be exact: V <= 2^24).  device=None keeps the host side only (no batches can be built).
+    max_len (None: whole sequences), stride (None: max_len; 1 .. max_len): the training windows (window_table) and the
+    evaluation rows' length; holdout 1 (the last item is the test target) or 2 (the penultimate is the validation target too);
+    last_item_rate in [0, 1]: the share of training rows that mask only their last position."""
 
-    def __init__(self, items, offsets, V=None, max_masked=MAX_MASKED_ITEMS, masked_percentage=MASKED_PERCENTAGE, device='cuda'):
+    def __init__(self, items, offsets, V=None, max_masked=MAX_MASKED_ITEMS, masked_percentage=MASKED_PERCENTAGE, device='cuda',
+                 max_len=None, stride=None, holdout=1, last_item_rate=0.0):
         items = np.ascontiguousarray(np.asarray(items), dtype=np.int32)
         offsets = np.ascontiguousarray(np.asarray(offsets), dtype=np.int64)
         if items.ndim != 1 or offsets.ndim != 1 or len(offsets) < 1:
@@ -35,27 +68,69 @@ class DeviceCloze:
             raise ValueError('DeviceCloze: item indices outside [0, V = %d)' % self.V)
         if not 0 <= int(max_masked) <= ops.CLOZE_MAX_LABELS:
             raise ValueError('DeviceCloze: max_masked = %d (0 .. %d)' % (max_masked, ops.CLOZE_MAX_LABELS))
+        if max_len is not None and not 1 <= int(max_len) <= ops.CLOZE_MAX_WIDTH:
+            raise ValueError('DeviceCloze: max_len = %d (1 .. %d, or None)' % (max_len, ops.CLOZE_MAX_WIDTH))
+        if stride is not None and (max_len is None or not 1 <= int(stride) <= int(max_len)):
+            raise ValueError('DeviceCloze: stride = %d (1 .. max_len = %s)' % (stride, max_len))
+        if holdout not in (1, 2):
+            raise ValueError('DeviceCloze: holdout = %r (1: test item, 2: validation and test items)' % (holdout,))
+        if not 0.0 <= float(last_item_rate) <= 1.0:
+            raise ValueError('DeviceCloze: last_item_rate = %g outside [0, 1]' % last_item_rate)
+        if float(last_item_rate) > 0.0 and int(max_masked) < 1:
+            raise ValueError('DeviceCloze: last_item_rate = %g needs max_masked >= 1' % last_item_rate)
         self.max_masked, self.masked_percentage = int(max_masked), float(masked_percentage)
-        self.offsets, self.lengths = offsets, lengths
+        self.max_len = None if max_len is None else int(max_len)
+        self.stride = self.max_len if stride is None else int(stride)
+        self.holdout, self.last_item_rate = int(holdout), float(last_item_rate)
+        self.last_thr = ops.cloze_last_thr(self.last_item_rate)
+        self.items, self.offsets, self.lengths = items, offsets, lengths
         self.n_seq = len(lengths)
-        self.items_dev = self.offsets_dev = None
+        self.windows = window_table(lengths, self.max_len, self.stride, self.holdout)
+        self.n_windows = len(self.windows.seq)
+        self._win_count = np.bincount(self.windows.seq, minlength=self.n_seq)
+        self._win_first = np.cumsum(self._win_count) - self._win_count
+        self._eval = {}                                              # split -> (Windows, device tensors)
+        self.items_dev = self.offsets_dev = self.windows_dev = None
         if device is not None:
             self.items_dev = torch.from_numpy(items).to(device)
             self.offsets_dev = torch.from_numpy(offsets).to(device)
+            self.windows_dev = tuple(torch.from_numpy(a).to(device) for a in self.windows)
 
     @classmethod
     def from_npz(cls, path, **kw):
         z = np.load(path, allow_pickle=False)
         return cls(z['items'], z['offsets'], V=int(z['vocab'].shape[0]), **kw)
 
-    def row_lengths(self, seq_idx, mode):
-        """host: L of every named sequence (TRAIN: without the held-out last item)"""
-        n = self.lengths[np.asarray(seq_idx, dtype=np.int64)]
-        return np.maximum(n - 1, 0) if _MODES[mode] == ops.CLOZE_TRAIN else n
+    # ---- the evaluation rows: one per sequence and split ------------------------------------------------------------------
+    def _drop(self, split):
+        """items from the sequence's end to the split's target, the target included"""
+        if split not in _SPLITS or (split == 'valid' and self.holdout != 2):
+            raise ValueError('DeviceCloze: split %r (holdout = %d: %s)' % (split, self.holdout, "'valid' or 'test'" if self.holdout == 2
+                                                                           else "'test' only; 'valid' needs holdout=2"))
+        return 2 if split == 'valid' else 1
 
-    def n_real_tokens(self, seq_idx, mode):
+    def _eval_table(self, split):
+        """(Windows, device tensors) of the split: sequence g's row is the last min(t + 1, max_len) positions ending at its
+        target t = n_g - drop, empty when the sequence is too short to have one"""
+        if split not in self._eval:
+            end = np.maximum(self.lengths - self._drop(split) + 1, 0)
+            start = np.zeros_like(end) if self.max_len is None else np.maximum(end - self.max_len, 0)
+            table = Windows(np.arange(self.n_seq, dtype=np.int32), start.astype(np.int32), (end - start).astype(np.int32))
+            dev = None if self.items_dev is None else tuple(torch.from_numpy(a).to(self.items_dev.device) for a in table)
+            self._eval[split] = (table, dev)
+        return self._eval[split]
+
+    def row_lengths(self, seq_idx, mode, split='test'):
+        """host: L of the row of every named sequence (TRAIN: of each of its windows; EVAL: of the split's row)"""
+        seq = np.asarray(seq_idx, dtype=np.int64)
+        if _MODES[mode] == ops.CLOZE_EVAL:
+            return self._eval_table(split)[0].len[seq].astype(np.int64)
+        T = np.maximum(self.lengths[seq] - self.holdout, 0)
+        return T if self.max_len is None else np.minimum(T, self.max_len)
+
+    def n_real_tokens(self, seq_idx, mode, split='test'):
         """host int: non-pad positions of the chained batch = sum of the row lengths + [CLS] [SEP] .. [SEP] per row"""
-        L = self.row_lengths(seq_idx, mode)
+        L = self.row_lengths(seq_idx, mode, split)
         return int(L.sum()) + 3 * len(L)
 
     def _width(self, L, width):
@@ -66,15 +141,19 @@ class DeviceCloze:
             raise ValueError('DeviceCloze: width = %d is shorter than a row of %d items' % (width, longest))
         return int(width)
 
-    def _batch(self, seq_host, seq_dev, mode, seed, width):
-        L = self.row_lengths(seq_host, mode)
+    def _batch(self, table, row_host, row_dev, seq_dev, mode, seed, width):
+        """rows row_host (window indices of `table` = (Windows, device tensors); negative: an empty row) -> the batch dict"""
+        host, dev = table
+        row_host = np.asarray(row_host, dtype=np.int64)
+        L = np.where(row_host >= 0, host.len[np.maximum(row_host, 0)], 0).astype(np.int64)
         W = self._width(L, width)
         if W > ops.CLOZE_MAX_WIDTH:
             raise ValueError('DeviceCloze: a row of %d items; at most %d' % (W, ops.CLOZE_MAX_WIDTH))
         self._need_device()
-        items, lab, nm = ops.cloze_batch(self.items_dev, self.offsets_dev, seq_dev, W, _MODES[mode], seed, self.masked_percentage,
-                                         self.max_masked)
-        return {'items': items, 'labels_padded': lab, 'n_masked': nm, 'seq_idx': seq_dev, 'n_real_tokens': int(L.sum()) + 3 * len(L)}
+        items, lab, nm = ops.cloze_batch_windows(self.items_dev, self.offsets_dev, dev[0], dev[1], dev[2], row_dev, W, _MODES[mode], seed,
+                                                 self.masked_percentage, self.max_masked, last_thr=self.last_thr)
+        return {'items': items, 'labels_padded': lab, 'n_masked': nm, 'seq_idx': seq_dev, 'win_idx': row_dev,
+                'n_real_tokens': int(L.sum()) + 3 * len(L)}
 
     def _need_device(self):
         if self.items_dev is None:
@@ -86,52 +165,95 @@ class DeviceCloze:
             raise ValueError('DeviceCloze: sequence indices outside [0, %d)' % self.n_seq)
         return seq
 
-    def batch(self, seq_idx, mode, seed=0, width=None):
+    def _upload(self, a):
+        return None if self.items_dev is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.items_dev.device)
+
+    def batch(self, seq_idx, mode, seed=0, width=None, split='test'):
         """One batch of the sequences seq_idx (host integers, any order, repeats allowed) -> dict(items (B, W) int64,
-        labels_padded (B, M) float32 -- M = max_masked for TRAIN, 1 for EVAL --, n_masked (B,) int32, seq_idx int32: device
-        tensors; n_real_tokens: host int).  width None: the batch's longest row (as BeautyCloze pads); an int fixes W."""
+        labels_padded (B, M) float32 -- M = max_masked for TRAIN, 1 for EVAL --, n_masked (B,) int32, seq_idx, win_idx int32:
+        device tensors; n_real_tokens: host int).  width None: the batch's longest row (as BeautyCloze pads); an int fixes W.
+        TRAIN: the one window of every sequence (a sequence cut into several windows: window_batch); EVAL: the row of `split`."""
         seq = self._check_seq(seq_idx)
-        dev = None if self.items_dev is None else torch.from_numpy(seq.astype(np.int32)).to(self.items_dev.device)
-        return self._batch(seq, dev, mode, seed, width)
+        if _MODES[mode] == ops.CLOZE_EVAL:
+            return self._batch(self._eval_table(split), seq, self._upload(seq), self._upload(seq), mode, seed, width)
+        count = self._win_count[seq]
+        if (count > 1).any():
+            g = int(seq[np.argmax(count > 1)])
+            raise ValueError('DeviceCloze: sequence %d has %d training windows (max_len = %d); name them with window_batch'
+                             % (g, self._win_count[g], self.max_len))
+        rows = np.where(count == 1, self._win_first[seq], -1)
+        return self._batch((self.windows, self.windows_dev), rows, self._upload(rows), self._upload(seq), mode, seed, width)
+
+    def window_batch(self, win_idx, seed=0, width=None):
+        """One TRAIN batch of the windows win_idx (host indices into self.windows, any order, repeats allowed)"""
+        win = np.asarray(win_idx, dtype=np.int64).reshape(-1)
+        if len(win) and (win.min() < 0 or win.max() >= self.n_windows):
+            raise ValueError('DeviceCloze: window indices outside [0, %d)' % self.n_windows)
+        return self._batch((self.windows, self.windows_dev), win, self._upload(win), self._upload(self.windows.seq[win]), TRAIN, seed, width)
 
     def epoch_order(self, seed, epoch):
-        return np.random.default_rng([int(seed), int(epoch)]).permutation(self.n_seq)
+        return np.random.default_rng([int(seed), int(epoch)]).permutation(self.n_windows)
 
     def rank_slices(self, batch_size, seed, epoch, rank=0, world=1):
-        """host: (order, [(lo, hi), ...]) -- epoch `epoch`'s permutation and rank `rank`'s slice of every full global batch of
-        batch_size * world consecutive entries (the remainder is dropped, as BeautyCloze does)"""
+        """host: (order, [(lo, hi), ...]) -- epoch `epoch`'s permutation of the windows and rank `rank`'s slice of every full
+        global batch of batch_size * world consecutive entries (the remainder is dropped, as BeautyCloze does)"""
         if not (batch_size > 0 and 0 <= rank < world):
             raise ValueError('DeviceCloze: batch_size = %d, rank %d of %d' % (batch_size, rank, world))
         order = self.epoch_order(seed, epoch)
         G = batch_size * world
-        return order, [(s + rank * batch_size, s + (rank + 1) * batch_size) for s in range(0, self.n_seq - G + 1, G)]
+        return order, [(s + rank * batch_size, s + (rank + 1) * batch_size) for s in range(0, self.n_windows - G + 1, G)]
 
     def train_batches(self, batch_size, seed, steps, rank=0, world=1, width=None):
-        """`steps` TRAIN batches of batch_size sequences for rank `rank` of `world`: one seeded permutation per epoch (uploaded
+        """`steps` TRAIN batches of batch_size windows for rank `rank` of `world`: one seeded permutation per epoch (uploaded
         once), the mask seed of epoch e is rand64_host(seed, e)."""
         self._need_device()
         order, slices = self.rank_slices(batch_size, seed, 0, rank, world)
         if steps > 0 and not slices:
-            raise ValueError('DeviceCloze: %d sequences do not fill one batch of %d x %d' % (self.n_seq, batch_size, world))
+            raise ValueError('DeviceCloze: %d %s do not fill one batch of %d x %d'
+                             % (self.n_windows, 'sequences' if self.max_len is None else 'windows', batch_size, world))
+        table = (self.windows, self.windows_dev)
         done = epoch = 0
         while done < steps:
             if epoch:
                 order, slices = self.rank_slices(batch_size, seed, epoch, rank, world)
-            order_dev = torch.from_numpy(order.astype(np.int32)).to(self.items_dev.device)
+            order_dev = self._upload(order)
+            seq_dev = order_dev if self.max_len is None else self.windows_dev[0][order_dev.long()]      # (a window's sequence)
             mask_seed = int(ops.rand64_host(seed, epoch))
             for lo, hi in slices:
-                yield self._batch(order[lo:hi], order_dev[lo:hi], TRAIN, mask_seed, width)
+                yield self._batch(table, order[lo:hi], order_dev[lo:hi], seq_dev[lo:hi], TRAIN, mask_seed, width)
                 done += 1
                 if done >= steps:
                     return
             epoch += 1
 
-    def eval_batches(self, batch_size, limit=None, width=None):
-        """EVAL batches of the sequences 0 .. limit in order, the last one partial.  An empty sequence gives a row without a
+    def eval_batches(self, batch_size, limit=None, width=None, split='test'):
+        """EVAL batches of the sequences 0 .. limit in order, the last one partial; split 'test' (the last item) or, with
+        holdout=2, 'valid' (the penultimate).  An empty sequence, or one too short to have the target, gives a row without a
         [MASK] whose label column is -1: compact labels taken from labels_padded then need the rows with n_masked == 1."""
+        table = self._eval_table(split)
         self._need_device()
         n = self.n_seq if limit is None else min(int(limit), self.n_seq)
         seq = np.arange(n, dtype=np.int64)
         seq_dev = torch.arange(n, dtype=torch.int32, device=self.items_dev.device)
         for s in range(0, n, batch_size):
-            yield self._batch(seq[s:s + batch_size], seq_dev[s:s + batch_size], EVAL, 0, width)
+            yield self._batch(table, seq[s:s + batch_size], seq_dev[s:s + batch_size], seq_dev[s:s + batch_size], EVAL, 0, width)
+
+    # ---- filtered evaluation ---------------------------------------------------------------------------------------------------
+    def history(self, seq_idx_dev, split='test', width=None):
+        """(B, E) int32 device tensor: every item of the sequences seq_idx_dev (a batch's 'seq_idx') in front of the split's
+        target, whether the row's window holds it or not -- the `exclude=` of predict_topk, of the ranking metrics and of
+        cloze.sample_candidates.  width None: E = the longest history of the data set, at most ops.L.MAX_EXCL; more items than E:
+        the most recent E."""
+        drop = self._drop(split)
+        self._need_device()
+        if width is None:
+            width = min(max(int(self.lengths.max()) - drop if self.n_seq else 0, 1), ops.L.MAX_EXCL)
+        return ops.cloze_history(self.items_dev, self.offsets_dev, seq_idx_dev, width, drop)
+
+    def item_counts(self, split='train'):
+        """host int64 [V]: how often every item occurs in the training views (all but the `holdout` last items of every
+        sequence) -- the popularity the negative sampler draws by, free of held-out items"""
+        if split != 'train':
+            raise ValueError("DeviceCloze: item_counts(split=%r): 'train' only" % (split,))
+        pos = np.arange(len(self.items), dtype=np.int64) - np.repeat(self.offsets[:-1], self.lengths)
+        return np.bincount(self.items[pos < np.repeat(self.lengths - self.holdout, self.lengths)], minlength=self.V).astype(np.int64)

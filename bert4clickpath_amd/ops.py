@@ -1579,6 +1579,23 @@ CLOZE_TRAIN, CLOZE_EVAL = 0, 1
 CLOZE_MAX_WIDTH, CLOZE_MAX_LABELS = 1021, 64
 
 
+def _cloze_rule_args(who, offsets, W, mode, seed, masked_percentage, max_masked, M):
+    """the checks cloze_batch and cloze_batch_windows share -> (W, mode, max_masked, M)"""
+    W, mode, max_masked = int(W), int(mode), int(max_masked)
+    if mode not in (CLOZE_TRAIN, CLOZE_EVAL):
+        raise B4CError('%s: mode %d (CLOZE_TRAIN = 0, CLOZE_EVAL = 1)' % (who, mode))
+    if not 1 <= W <= CLOZE_MAX_WIDTH:
+        raise B4CError('%s: W = %d (1 .. %d)' % (who, W, CLOZE_MAX_WIDTH))
+    M = (max_masked if mode == CLOZE_TRAIN else 1) if M is None else int(M)
+    if not mode <= M <= CLOZE_MAX_LABELS or (mode == CLOZE_TRAIN and not 0 <= max_masked <= M):
+        raise B4CError('%s: max_masked = %d, M = %d (0 <= max_masked <= M <= %d; EVAL: M >= 1)' % (who, max_masked, M, CLOZE_MAX_LABELS))
+    if mode == CLOZE_TRAIN and not 0.0 <= float(masked_percentage) <= 1.0:
+        raise B4CError('%s: masked_percentage %g outside [0, 1]' % (who, masked_percentage))
+    if not 0 <= int(seed) < (1 << 64) or offsets.shape[0] - 1 > (1 << 31) - 1:
+        raise B4CError('%s: seed %d (0 .. 2^64) / %d sequences (int32 seq_idx)' % (who, seed, offsets.shape[0] - 1))
+    return W, mode, max_masked, M
+
+
 def cloze_batch(items, offsets, seq_idx, W, mode, seed, masked_percentage=0.4, max_masked=10, M=None):
     """-> (items_out int64 [B, W], labels_padded fp32 [B, M], n_masked int32 [B]) (b4c_cloze_batch): row b is sequence
     g = seq_idx[b] of the CSR data set (items int32 [N] label-space indices, offsets int64 [n_seq + 1]) as the model's
@@ -1593,18 +1610,8 @@ def cloze_batch(items, offsets, seq_idx, W, mode, seed, masked_percentage=0.4, m
         raise B4CError('cloze_batch: offsets must be an int64 [n_seq + 1] tensor')
     if not isinstance(seq_idx, torch.Tensor) or seq_idx.dim() != 1 or seq_idx.dtype != torch.int32:
         raise B4CError('cloze_batch: seq_idx must be an int32 [B] tensor of sequence indices')
-    B, W, mode, max_masked = seq_idx.shape[0], int(W), int(mode), int(max_masked)
-    if mode not in (CLOZE_TRAIN, CLOZE_EVAL):
-        raise B4CError('cloze_batch: mode %d (CLOZE_TRAIN = 0, CLOZE_EVAL = 1)' % mode)
-    if not 1 <= W <= CLOZE_MAX_WIDTH:
-        raise B4CError('cloze_batch: W = %d (1 .. %d)' % (W, CLOZE_MAX_WIDTH))
-    M = (max_masked if mode == CLOZE_TRAIN else 1) if M is None else int(M)
-    if not mode <= M <= CLOZE_MAX_LABELS or (mode == CLOZE_TRAIN and not 0 <= max_masked <= M):
-        raise B4CError('cloze_batch: max_masked = %d, M = %d (0 <= max_masked <= M <= %d; EVAL: M >= 1)' % (max_masked, M, CLOZE_MAX_LABELS))
-    if mode == CLOZE_TRAIN and not 0.0 <= float(masked_percentage) <= 1.0:
-        raise B4CError('cloze_batch: masked_percentage %g outside [0, 1]' % masked_percentage)
-    if not 0 <= int(seed) < (1 << 64) or offsets.shape[0] - 1 > (1 << 31) - 1:
-        raise B4CError('cloze_batch: seed %d (0 .. 2^64) / %d sequences (int32 seq_idx)' % (seed, offsets.shape[0] - 1))
+    B = seq_idx.shape[0]
+    W, mode, max_masked, M = _cloze_rule_args('cloze_batch', offsets, W, mode, seed, masked_percentage, max_masked, M)
     _cuda(items, offsets, seq_idx)
     items, offsets, seq_idx = items.contiguous(), offsets.contiguous(), seq_idx.contiguous()
     dev = items.device
@@ -1627,6 +1634,96 @@ def cloze_choose_host(seed, g, L, n):
     pos = np.empty(max(int(n), 0), dtype=np.int32)
     _lib.check(_lib.lib().b4c_cloze_choose(int(seed) & 0xFFFFFFFFFFFFFFFF, int(g), int(L), int(n), pos.ctypes.data), 'cloze_choose')
     return pos
+
+
+CLOZE_LAST_ONE = 1 << 24        # last_thr of a last-item rate of 1 (b4c_cloze_batch_windows)
+
+
+def cloze_last_thr(rate):
+    """the integer threshold of a last-item rate in [0, 1]: round(rate * 2^24)"""
+    if not 0.0 <= float(rate) <= 1.0:
+        raise B4CError('cloze_last_thr: rate %g outside [0, 1]' % rate)
+    return int(round(float(rate) * CLOZE_LAST_ONE))
+
+
+def cloze_batch_windows(items, offsets, win_seq, win_start, win_len, row_win, W, mode, seed, masked_percentage=0.4, max_masked=10, M=None,
+                        last_thr=0):
+    """-> (items_out int64 [B, W], labels_padded fp32 [B, M], n_masked int32 [B]) (b4c_cloze_batch_windows): row b is window
+    w = row_win[b] of the device table (win_seq, win_start, win_len: int32 [n_win]) -- the win_len[w] items of sequence win_seq[w]
+    from win_start[w] on -- in cloze_batch's layout.  row_win None: row b is window b; a negative entry: an empty row.
+    mode CLOZE_TRAIN: the positions drawn with the window's own seed, or only the last one in a row the last-only draw picks
+    (last_thr = cloze_last_thr(rate), 0 .. 2^24; cloze_choose_window_host regenerates both); CLOZE_EVAL: the last position.
+    A whole-sequence window (g, 0, n_g - 1) with last_thr = 0 is cloze_batch's TRAIN row.  Stream-ordered, nothing is read back:
+    row_win is NOT checked against n_win nor a window against its sequence, and win_len is cut at W."""
+    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
+        raise B4CError('cloze_batch_windows: items must be an int32 [N] tensor of item indices')
+    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
+        raise B4CError('cloze_batch_windows: offsets must be an int64 [n_seq + 1] tensor')
+    for name, t in (('win_seq', win_seq), ('win_start', win_start), ('win_len', win_len)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.shape[0] != win_seq.shape[0]:
+            raise B4CError('cloze_batch_windows: %s must be an int32 [n_win] tensor (win_seq, win_start, win_len: one length)' % name)
+    if row_win is not None and (not isinstance(row_win, torch.Tensor) or row_win.dim() != 1 or row_win.dtype != torch.int32):
+        raise B4CError('cloze_batch_windows: row_win must be an int32 [B] tensor of window indices, or None')
+    B = win_seq.shape[0] if row_win is None else row_win.shape[0]
+    W, mode, max_masked, M = _cloze_rule_args('cloze_batch_windows', offsets, W, mode, seed, masked_percentage, max_masked, M)
+    last_thr = int(last_thr)
+    if mode == CLOZE_TRAIN and (not 0 <= last_thr <= CLOZE_LAST_ONE or (last_thr > 0 and M < 1)):
+        raise B4CError('cloze_batch_windows: last_thr = %d (0 .. 2^24 = %d; > 0 needs M >= 1), M = %d' % (last_thr, CLOZE_LAST_ONE, M))
+    if mode == CLOZE_EVAL:
+        last_thr = 0
+    _cuda(items, offsets, win_seq, win_start, win_len, row_win)
+    items, offsets, win_seq, win_start, win_len = (t.contiguous() for t in (items, offsets, win_seq, win_start, win_len))
+    row_win = None if row_win is None else row_win.contiguous()
+    dev = items.device
+    out = torch.empty(B, W, dtype=torch.int64, device=dev)
+    lab = torch.empty(B, M, dtype=torch.float32, device=dev)
+    nm = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return out, lab, nm
+    with _record('cloze_batch', B * (W * 12 + M * 4 + 40)):
+        L.check(L.lib().b4c_cloze_batch_windows(_p(items), _p(offsets), _p(win_seq), _p(win_start), _p(win_len), _p(row_win), B, W, mode,
+                                                float(masked_percentage), max_masked, int(seed), last_thr, _p(out), W, _p(lab), M, M,
+                                                _p(nm), _st()), 'cloze_batch_windows')
+    return out, lab, nm
+
+
+def cloze_choose_window_host(seed, g, a, L, masked_percentage=0.4, max_masked=10, last_thr=0):
+    """-> int32 numpy [n]: the positions of [0, L) that cloze_batch_windows masks in TRAIN mode for the window of L items at
+    start a of sequence g, ascending (b4c_cloze_choose_window: the kernel's rule evaluated on the host, no device work)."""
+    import ctypes
+    import numpy as np
+    from . import _lib              # (the argument L, the header's name, hides this module's alias)
+    if not 0 <= int(max_masked) <= CLOZE_MAX_LABELS or not 0 <= int(last_thr) <= CLOZE_LAST_ONE:
+        raise B4CError('cloze_choose_window: max_masked = %d (0 .. %d), last_thr = %d (0 .. 2^24)' % (max_masked, CLOZE_MAX_LABELS, last_thr))
+    pos = np.empty(max(int(max_masked), 1), dtype=np.int32)
+    n = ctypes.c_int32(0)
+    _lib.check(_lib.lib().b4c_cloze_choose_window(int(seed) & 0xFFFFFFFFFFFFFFFF, int(g), int(a), int(L), float(masked_percentage),
+                                                  int(max_masked), int(last_thr), pos.ctypes.data, ctypes.addressof(n)), 'cloze_choose_window')
+    return pos[:n.value].copy()
+
+
+def cloze_history(items, offsets, seq_idx, E, drop=1):
+    """-> int32 [B, E] device tensor (b4c_cloze_history): row b holds the items of sequence seq_idx[b] in front of its target --
+    item n_g - drop --, the most recent E when there are more, then -1.  A negative seq_idx: all -1.  The `exclude=` of
+    predict_topk, of the ranking metrics and of cloze.sample_candidates takes it (through ops.exclusions).  Stream-ordered,
+    nothing is read back: seq_idx is NOT checked against n_seq."""
+    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
+        raise B4CError('cloze_history: items must be an int32 [N] tensor of item indices')
+    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
+        raise B4CError('cloze_history: offsets must be an int64 [n_seq + 1] tensor')
+    if not isinstance(seq_idx, torch.Tensor) or seq_idx.dim() != 1 or seq_idx.dtype != torch.int32:
+        raise B4CError('cloze_history: seq_idx must be an int32 [B] tensor of sequence indices')
+    E, drop = int(E), int(drop)
+    if not 1 <= E <= L.MAX_EXCL or drop < 1:
+        raise B4CError('cloze_history: E = %d (1 .. %d = B4C_MAX_EXCL), drop = %d (>= 1)' % (E, L.MAX_EXCL, drop))
+    _cuda(items, offsets, seq_idx)
+    items, offsets, seq_idx = items.contiguous(), offsets.contiguous(), seq_idx.contiguous()
+    B = seq_idx.shape[0]
+    out = torch.empty(B, E, dtype=torch.int32, device=items.device)
+    if B:
+        with _record('cloze_history', B * (E * 8 + 20)):
+            L.check(L.lib().b4c_cloze_history(_p(items), _p(offsets), _p(seq_idx), B, drop, E, _p(out), E, _st()), 'cloze_history')
+    return out
 
 
 def adam_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul=1.0, coef=None, decay=None, blocks=None):

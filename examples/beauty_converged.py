@@ -8,6 +8,9 @@ val_loss; ReduceLROnPlateau(val_loss, patience 10, factor 0.317) (main.py:134), 
 
 Reports HitRate@10 / NDCG@10 (rank over all V items) of the final weights and of the best-val_loss checkpoint, plus the
 per-epoch curve, as one JSON line.  --max_seconds bounds the wall time (the run then reports stopped_by = "time").
+With --device_batches, --max_len / --stride / --holdout / --last_item_rate select the BERT4Rec paper's data protocol
+(cloze_batches.DeviceCloze); with --holdout 2 the callbacks monitor the validation split (the penultimate item) and the test split
+(the last item) is read once at the end, full-ranking and filtered by the user's whole history.
 
     python examples/beauty_converged.py --seed 1 --dtype f32 --max_seconds 1000
 """
@@ -25,20 +28,25 @@ import torch  # noqa: E402
 from examples.beauty_hitrate import build_model  # noqa: E402
 
 
-def evaluate(model, data, batch=1024):
-    """-> (val_loss, HitRate@10 %, NDCG@10 %) on every user: mask the last item, rank over all V items.
+def evaluate(model, data, batch=1024, split='test', filtered=False):
+    """-> (val_loss, HitRate@10 %, NDCG@10 %) on every user: mask the split's target, rank over all V items; filtered: the
+    ranking leaves out the user's history (DeviceCloze.history: a row's window does not hold the older items).
     data: input_pipeline.BeautyCloze (host batches) or cloze_batches.DeviceCloze (batches built on the device)."""
     tot = hits = ndcg = n = 0.0
     with torch.no_grad():
-        for b in data.eval_batches(batch):
-            if 'items' in b:           # DeviceCloze: one [MASK] per row, the (B, 1) labels are the compact labels
-                items, lab, flat = b['items'], b['labels_padded'].reshape(-1).to(torch.int32), None
+        for b in (data.eval_batches(batch, split=split) if hasattr(data, 'history') else data.eval_batches(batch)):
+            seen = None
+            if 'items' in b:           # DeviceCloze: at most one [MASK] per row; a sequence too short for the target has none
+                real = b['n_masked'] == 1
+                items, lab, flat = b['items'][real], b['labels_padded'][real].reshape(-1).to(torch.int32), None
+                if filtered:
+                    seen = data.history(b['seq_idx'], split=split)[real]
             else:
                 items = torch.from_numpy(b['ids'])[:, 2:-1].contiguous().cuda()
                 lab = torch.from_numpy(b['labels']).cuda()
                 flat = torch.from_numpy(b['flat_idx']).cuda()
             loss = model.cloze_loss({'asin': items}, lab, training=False, flat_idx=flat)
-            _, h, nd = model.predict_topk({'asin': items}, 10, lab, flat_idx=flat)
+            _, h, nd = model.predict_topk({'asin': items}, 10, lab, flat_idx=flat, exclude=seen)
             tot += float(loss) * h.numel()
             hits += float(h.sum()); ndcg += float(nd.sum()); n += h.numel()
     return tot / n, 100.0 * hits / n, 100.0 * ndcg / n
@@ -58,12 +66,24 @@ def main():
     ap.add_argument('--device_batches', action='store_true',
                     help='build the training and validation batches on the device (cloze_batches.DeviceCloze); the masks are that '
                          'kernel\'s own stream')
+    ap.add_argument('--max_len', type=int, default=None,
+                    help='with --device_batches: rows of at most this many items -- long training sequences are cut into sliding '
+                         'windows, evaluation keeps the most recent ones (the BERT4Rec paper\'s protocol); default: whole sequences')
+    ap.add_argument('--stride', type=int, default=None, help='with --max_len: the step between two training windows; default: max_len')
+    ap.add_argument('--holdout', type=int, default=1, choices=[1, 2],
+                    help='with --device_batches: 2 holds out the penultimate item for validation -- the callbacks monitor it -- and '
+                         'the last for test, reported once at the end; default 1: the callbacks monitor the last item')
+    ap.add_argument('--last_item_rate', type=float, default=0.0,
+                    help='with --device_batches: the share of training rows whose only masked position is the last one')
     a = ap.parse_args()
+    protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
+    if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
+        ap.error('--max_len, --stride, --holdout and --last_item_rate need --device_batches')
     from bert4clickpath_amd import checkpoint as ck, input_pipeline, optim
     from bert4clickpath_amd.clickstream_transformer import transformer as T
     if a.device_batches:
         from bert4clickpath_amd.cloze_batches import DeviceCloze
-        data = DeviceCloze.from_npz(a.data)
+        data = DeviceCloze.from_npz(a.data, **protocol)
     else:
         data = input_pipeline.BeautyCloze(a.data)
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
@@ -75,6 +95,7 @@ def main():
     plateau = ck.ReduceLROnPlateau(opt, factor=0.317, patience=10)
     stopper = ck.EarlyStopping(patience=30)
     batches = data.train_batches(a.batch, a.seed, a.steps_per_epoch * a.max_epochs)
+    monitored = 'valid' if a.holdout == 2 else 'test'      # the split the callbacks see
     t0 = time.perf_counter()
     curve, stopped_by, best = [], 'max_epochs', None
     for epoch in range(a.max_epochs):
@@ -91,7 +112,7 @@ def main():
             loss.backward()
             opt.step()
             tl = loss
-        val_loss, hr, nd = evaluate(model, data)
+        val_loss, hr, nd = evaluate(model, data, split=monitored)
         row = {'epoch': epoch + 1, 'train_loss_last': float(tl), 'val_loss': val_loss, 'hitrate@10': hr, 'ndcg@10': nd,
                'lr': opt.lr, 'seconds': time.perf_counter() - t0}
         curve.append(row)
@@ -110,10 +131,18 @@ def main():
             break
     final = curve[-1]
     by_hr = max(curve, key=lambda r: r['hitrate@10'])
+    report = {}
+    if a.device_batches:
+        report['data_protocol'] = dict(protocol, monitored_split=monitored)
+    if a.holdout == 2:                 # the held-out last item, read once: the weights are the last epoch's
+        loss, hr, nd = evaluate(model, data, split='test')
+        report['test'] = {'loss': loss, 'hitrate@10': hr, 'ndcg@10': nd}
+        _, fhr, fnd = evaluate(model, data, split='test', filtered=True)
+        report['test'].update({'filtered_hitrate@10': fhr, 'filtered_ndcg@10': fnd})
     print(json.dumps({'what': 'Amazon Beauty, HIP path, reference loop controls (ReduceLROnPlateau 0.317/10, EarlyStopping 30, '
                               'best-val_loss checkpoint)', 'dtype': a.dtype, 'seed': a.seed, 'batch': a.batch,
                       'steps_per_epoch': a.steps_per_epoch, 'epochs_run': len(curve), 'stopped_by': stopped_by,
-                      'final': final, 'best_val_loss_epoch': best, 'best_hitrate_epoch': by_hr, 'curve': curve}))
+                      'final': final, 'best_val_loss_epoch': best, 'best_hitrate_epoch': by_hr, 'curve': curve, **report}))
 
 
 if __name__ == '__main__':

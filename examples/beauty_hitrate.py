@@ -8,6 +8,9 @@ seen (uniform, or by popularity counted on the training split), HR@10 / NDCG@10 
 --paper_model builds the paper's MODEL instead of the reference's (no reference oracle): learned positions, GELU feed-forward of width
 4 d, drop(LayerNorm(E + P)) at the input, attention dropout, the tied head LayerNorm(gelu(Dense(d -> d))) . E^T + b; with the paper's
 recipe (--clipnorm 5 --warmup 100 --weight_decay 0.01) and --negatives 100 its sampled-negative numbers stand beside the published ones.
+--device_batches with --max_len / --stride / --holdout / --last_item_rate is the paper's DATA protocol: sliding training windows, the
+penultimate item held out for validation and the last for test (both reported), last-item training rows; the filtered and the
+sampled-negative figures then exclude a user's whole history (DeviceCloze.history), not only the row's window.
 
     python examples/beauty_hitrate.py --steps 3000 --dtype f32
 Prints one JSON line.  The CPU counterpart on the oracle is oracle/train_beauty_cpu.py (same seeds, batches,
@@ -72,13 +75,25 @@ def main():
     ap.add_argument('--device_batches', action='store_true',
                     help='build the training and evaluation batches on the device (cloze_batches.DeviceCloze): no per-row host '
                          'work and no upload per step; the masks are that kernel\'s own stream, so losses differ from the default')
+    ap.add_argument('--max_len', type=int, default=None,
+                    help='with --device_batches: rows of at most this many items -- long training sequences are cut into sliding '
+                         'windows, evaluation keeps the most recent ones (the paper\'s protocol); default: whole sequences')
+    ap.add_argument('--stride', type=int, default=None, help='with --max_len: the step between two training windows; default: max_len')
+    ap.add_argument('--holdout', type=int, default=1, choices=[1, 2],
+                    help='with --device_batches: 2 holds out the penultimate item for validation and the last for test (the '
+                         'paper\'s leave-one-out split; both are reported); default 1: the last item is the test target')
+    ap.add_argument('--last_item_rate', type=float, default=0.0,
+                    help='with --device_batches: the share of training rows whose only masked position is the last one')
     a = ap.parse_args()
+    protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
+    if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
+        ap.error('--max_len, --stride, --holdout and --last_item_rate need --device_batches')
     from bert4clickpath_amd import input_pipeline, optim
     from bert4clickpath_amd.clickstream_transformer.training_utils import WarmupLinearDecay
     from bert4clickpath_amd.clickstream_transformer import transformer as T
     data = input_pipeline.BeautyCloze(a.data)
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
-    longest = int(np.diff(data.offsets).max()) + 3       # [CLS] [SEP] items [SEP]
+    longest = (int(np.diff(data.offsets).max()) if a.max_len is None else a.max_len) + 3       # [CLS] [SEP] items [SEP]
     model = build_model(data.V, a.dropout, dtype, paper_positions=longest if a.paper_model else None).cuda()
     lr = WarmupLinearDecay(1e-3, a.warmup, max(a.steps, a.warmup + 1)) if a.warmup > 0 else 1e-3
     opt = optim.Adam(model.parameters(), learning_rate=lr, global_clipnorm=a.clipnorm, weight_decay=a.weight_decay,
@@ -88,7 +103,7 @@ def main():
     dev_data = None
     if a.device_batches:
         from bert4clickpath_amd.cloze_batches import DeviceCloze
-        dev_data = DeviceCloze.from_npz(a.data)
+        dev_data = DeviceCloze.from_npz(a.data, **protocol)
     for step, b in enumerate((dev_data or data).train_batches(a.batch, a.seed, a.steps)):
         opt.zero_grad()
         if dev_data is not None:      # items and padded labels are on the device already; nothing is read back
@@ -107,38 +122,58 @@ def main():
     train_s = time.perf_counter() - t0
     from bert4clickpath_amd import cloze
     from bert4clickpath_amd.clickstream_transformer.constants import NUM_RESERVED_TOKENS
-    hits = ndcg = n = fhits = fndcg = shits = sndcg = 0.0
     counts = None
-    if a.negatives and a.sampler == 'popularity':       # the training split: every sequence without its held-out last item
-        train = np.concatenate([data.seq(i)[:-1] for i in range(data.n_seq)]) + NUM_RESERVED_TOKENS
-        counts = cloze.item_counts(train, data.V)
-    for b in (dev_data or data).eval_batches(1024, a.eval_limit):
-        if dev_data is not None:      # one [MASK] per row: the (B, 1) labels are the compact labels
-            items, labels, flat = b['items'], b['labels_padded'].reshape(-1).to(torch.int32), None
+    if a.negatives and a.sampler == 'popularity':       # the training split: every sequence without its held-out items
+        if dev_data is not None:
+            counts = dev_data.item_counts('train')
         else:
-            ids = torch.from_numpy(b['ids'])
-            items = ids[:, 2:-1].contiguous().cuda()
-            labels, flat = torch.from_numpy(b['labels']).cuda(), torch.from_numpy(b['flat_idx']).cuda()
-        _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat)
-        hits += float(h.sum()); ndcg += float(nd.sum()); n += h.numel()
-        if a.exclude_seen:          # one [MASK] (the last item) per sequence: the rows are the sequences, in order
-            _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, exclude=cloze.seen_items(items))
-            fhits += float(h.sum()); fndcg += float(nd.sum())
-        if a.negatives:             # row_base: the draws of a row do not depend on the batch size
-            cand = cloze.sample_candidates(labels, a.negatives, exclude=cloze.seen_items(items), item_counts=counts,
-                                           seed=a.seed, row_base=int(n) - labels.numel(),
-                                           num_items=data.V)
-            _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, candidates=cand)
-            shits += float(h.sum()); sndcg += float(nd.sum())
+            train = np.concatenate([data.seq(i)[:-1] for i in range(data.n_seq)]) + NUM_RESERVED_TOKENS
+            counts = cloze.item_counts(train, data.V)
+
+    def evaluate(split):
+        """the metrics of one split ('test': the last item; 'valid', with --holdout 2: the penultimate one)"""
+        hits = ndcg = n = fhits = fndcg = shits = sndcg = 0.0
+        for b in (dev_data.eval_batches(1024, a.eval_limit, split=split) if dev_data is not None else data.eval_batches(1024, a.eval_limit)):
+            seen = None
+            if dev_data is not None:      # at most one [MASK] per row; a sequence too short for the target has none
+                real = b['n_masked'] == 1
+                items, labels, flat = b['items'][real], b['labels_padded'][real].reshape(-1).to(torch.int32), None
+                if a.max_len is not None and (a.exclude_seen or a.negatives):      # a window does not hold the older items
+                    seen = dev_data.history(b['seq_idx'], split=split)[real]
+            else:
+                ids = torch.from_numpy(b['ids'])
+                items = ids[:, 2:-1].contiguous().cuda()
+                labels, flat = torch.from_numpy(b['labels']).cuda(), torch.from_numpy(b['flat_idx']).cuda()
+            if seen is None and (a.exclude_seen or a.negatives):
+                seen = cloze.seen_items(items)
+            _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat)
+            hits += float(h.sum()); ndcg += float(nd.sum()); n += h.numel()
+            if a.exclude_seen:          # one [MASK] (the target) per sequence: the rows are the sequences, in order
+                _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, exclude=seen)
+                fhits += float(h.sum()); fndcg += float(nd.sum())
+            if a.negatives:             # row_base: the draws of a row do not depend on the batch size
+                cand = cloze.sample_candidates(labels, a.negatives, exclude=seen, item_counts=counts, seed=a.seed,
+                                               row_base=int(n) - labels.numel(), num_items=data.V)
+                _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, candidates=cand)
+                shits += float(h.sum()); sndcg += float(nd.sum())
+        res = {'hitrate@10': 100.0 * hits / n, 'ndcg@10': 100.0 * ndcg / n, 'n_eval': int(n)}
+        if a.exclude_seen:
+            res.update({'filtered_hitrate@10': 100.0 * fhits / n, 'filtered_ndcg@10': 100.0 * fndcg / n})
+        if a.negatives:
+            res.update({'sampled_hitrate@10': 100.0 * shits / n, 'sampled_ndcg@10': 100.0 * sndcg / n})
+        return res
+
     out = {'what': 'Amazon Beauty, HIP path' + (', the BERT4Rec paper\'s model' if a.paper_model else ''), 'dtype': a.dtype, 'steps': a.steps, 'batch': a.batch,
-           'dropout': a.dropout, 'hitrate@10': 100.0 * hits / n, 'ndcg@10': 100.0 * ndcg / n, 'n_eval': int(n),
-           'train_seconds': train_s, 'loss_curve': losses, 'device_batches': bool(a.device_batches)}
-    if a.exclude_seen:
-        out.update({'filtered_hitrate@10': 100.0 * fhits / n, 'filtered_ndcg@10': 100.0 * fndcg / n})
+           'dropout': a.dropout}
+    out.update(evaluate('test'))
+    out.update({'train_seconds': train_s, 'loss_curve': losses, 'device_batches': bool(a.device_batches)})
     if a.negatives:
-        out.update({'sampled_protocol': 'BERT4Rec paper: 1 held-out + %d %s-sampled unseen items (not the reference\'s '
-                                        'full ranking)' % (a.negatives, a.sampler),
-                    'sampled_hitrate@10': 100.0 * shits / n, 'sampled_ndcg@10': 100.0 * sndcg / n})
+        out['sampled_protocol'] = ('BERT4Rec paper: 1 held-out + %d %s-sampled unseen items (not the reference\'s full ranking)'
+                                   % (a.negatives, a.sampler))
+    if a.device_batches:
+        out['data_protocol'] = protocol
+    if a.holdout == 2:                # the split a model is selected on; the test numbers above are read once, at the end
+        out['valid'] = evaluate('valid')
     print(json.dumps(out))
 
 

@@ -534,6 +534,43 @@ int b4c_cloze_batch(const int32_t *items, const int64_t *offsets, const int32_t 
                     float *labels_out, int ld_lab, int M, int32_t *n_masked_out, void *stream);
 int b4c_cloze_choose(uint64_t seed, int64_t g, int L, int n, int32_t *pos);
 
+/* ---- Cloze batches over windows: the paper's data protocol (sliding training windows, last-item rows, history lists) -------
+ * b4c_cloze_batch_windows: one row per WINDOW.  A window is (g, a, L): sequence g, start a inside it and L <= W items
+ *   items[offsets[g] + a .. + L).  The window table is on the device: win_seq, win_start, win_len int32 [n_win].  row_win int32 [B]
+ *   names the window of every batch row (NULL: row b is window b; a negative entry is an empty row, like a negative seq_idx
+ *   above).  Neither row_win against n_win nor a window against its sequence is range-checked: the caller's.  The other
+ *   arguments are those of b4c_cloze_batch, and last_thr in [0, 2^24].
+ * The masking rule of a row that names window (g, a, L):
+ *   window seed: seed_a = seed when a == 0, else b4c_rand64(seed ^ 0x9E3779B97F4A7C15, a).
+ *   TRAIN (mode 0), ordinary row: n = min(max((int)((float)L * masked_percentage), 0), max_masked) as above, keys
+ *     k_p = b4c_rand64(seed_a, ((uint64_t)g << 10) | p) for p in [0, L) (p counts from the window's start); the masked set is
+ *     the n positions smallest in (k_p, p) order, as above.  A window (g, 0, n_g - 1) with last_thr = 0 is b4c_cloze_batch's
+ *     TRAIN row of sequence g, bit for bit.
+ *   TRAIN, last-only row: a row is last-only iff (b4c_rand64(seed_a ^ 0xD1B54A32D192ED03, g) >> 40) < last_thr and L > 0.  Then the
+ *     masked set is {L - 1} and n = 1, whatever max_masked and masked_percentage are (so last_thr > 0 needs M >= 1).  The
+ *     threshold is an integer (rate * 2^24, rounded by the caller) so that host and device cannot disagree on a float product.
+ *   EVAL (mode 1): the masked set is {L - 1} (empty for L = 0); nothing is drawn, last_thr is not read.
+ * Outputs, pad columns, label order, the -1.0 label pad and n_masked_out are exactly those of b4c_cloze_batch.
+ * A row is a pure function of (seed, g, a, the window's items, mode, masked_percentage, max_masked, last_thr).
+ * Limits: W and M as in b4c_cloze_batch, a >= 0 (a < 2^31: int32); win_len is clamped to [0, W]; nothing is written outside
+ *   the row (columns past W are untouched).  B = 0 is a no-op.
+ * b4c_cloze_choose_window is the TRAIN rule of one window on the HOST (no device work): pos[0 .. n_out[0]) = the masked
+ *   positions of [0, L), ascending; pos has room for max(max_masked, 1) entries; 0 <= L <= 1021.  With a = 0 and last_thr = 0
+ *   it is b4c_cloze_choose(seed, g, L, n(L), pos).
+ * b4c_cloze_history: the items of a sequence that precede its target, as an exclusion list of filtered evaluation.
+ *   out int32 [B][E] (pitch ld >= E, 1 <= E <= B4C_MAX_EXCL; columns past E are not written).  Row b names sequence
+ *   g = seq_idx[b]; its history is h = items[offsets[g] .. offsets[g+1] - drop) with drop >= 1 (the target is item n_g - drop), of
+ *   H = max(n_g - drop, 0) items.  out[b][e] = h[max(H - E, 0) + e] for e < min(H, E) (more than E items: the most recent E
+ *   are kept), -1 after them.  A negative seq_idx gives an all -1 row.  The form b4c_exclusions_prep takes as ex_in. */
+int b4c_cloze_batch_windows(const int32_t *items, const int64_t *offsets, const int32_t *win_seq, const int32_t *win_start,
+                            const int32_t *win_len, const int32_t *row_win, int B, int W, int mode, float masked_percentage,
+                            int max_masked, uint64_t seed, uint32_t last_thr, int64_t *items_out, int ld_items, float *labels_out,
+                            int ld_lab, int M, int32_t *n_masked_out, void *stream);
+int b4c_cloze_choose_window(uint64_t seed, int64_t g, int64_t a, int L, float masked_percentage, int max_masked, uint32_t last_thr,
+                            int32_t *pos, int32_t *n_out);
+int b4c_cloze_history(const int32_t *items, const int64_t *offsets, const int32_t *seq_idx, int B, int drop, int E, int32_t *out,
+                      int ld, void *stream);
+
 /* ---- R16: Adam (Keras semantics, eps outside the sqrt) ------------------------------------
  * replaces tf.keras.optimizers.Adam(1e-3, .9, .999, 1e-9) (main.py:87), dense update over a flat
  * fp32 arena: m,v EMA; p -= lr_t * m / (sqrt(v) + eps), lr_t = lr*sqrt(1-b2^t)/(1-b1^t) (host).
