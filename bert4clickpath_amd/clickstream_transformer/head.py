@@ -54,7 +54,7 @@ class SoftMaxHead(nn.Module):
             self.build(x2d.shape[-1])
             self.to(x2d.device)
         need_tape = torch.is_grad_enabled()
-        return ops.MLPFn.apply(x2d, self._packs, need_tape, out_fp32, *self._params())
+        return ops.MLPFn.apply(x2d, self._packs, need_tape, bool(out_fp32), False, *self._params())
 
     def trunk(self, x2d):
         """relu(Dense) x n of head.py:35 alone: the input of the vocabulary projection."""
@@ -63,7 +63,7 @@ class SoftMaxHead(nn.Module):
             self.to(x2d.device)
         if not self.intermediate_layers:
             return x2d
-        return ops.MLPFn.apply(x2d, self._packs[:-1], torch.is_grad_enabled(), 'relu_last', *self._params()[:-2])
+        return ops.MLPFn.apply(x2d, self._packs[:-1], torch.is_grad_enabled(), False, True, *self._params()[:-2])
 
     accepts_poison = True      # cloze_ce(..., poison=): an int32 device flag whose negative value turns the loss into NaN
 
@@ -81,7 +81,7 @@ class SoftMaxHead(nn.Module):
     def _project(self, h, out_fp32=False):
         """Vocabulary projection alone: trunk output [R, K] -> logits [R, round_up(V, 8)]."""
         K, kernel, bias = self._proj()
-        return ops.MLPFn.apply(h, self._packs[-1:], torch.is_grad_enabled(), out_fp32, kernel, bias)
+        return ops.MLPFn.apply(h, self._packs[-1:], torch.is_grad_enabled(), bool(out_fp32), False, kernel, bias)
 
     def _rank_supported(self, h):
         """the logits-free ranking kernels: bf16 trunk output of width 64 / 128"""
@@ -260,7 +260,7 @@ class _DenseStackHead(nn.Module):
         if self.output_layer is None:
             self.build(shp[-1])
             self.to(x2d.device)
-        lg = ops.MLPFn.apply(x2d, self._packs, torch.is_grad_enabled(), False, *self._params())   # [R, rup8(units)]
+        lg = ops.MLPFn.apply(x2d, self._packs, torch.is_grad_enabled(), False, False, *self._params())   # [R, rup8(units)]
         p = ops.SigmoidFn.apply(lg)
         return p[:, :self.out_units].reshape(*shp[:-1], self.out_units)
 
@@ -364,7 +364,7 @@ class ClozeMaskedItemPrediction(SoftMaxHead):
         need_tape = torch.is_grad_enabled()
         layers = list(self.intermediate_layers)
         if len(layers) > 1:
-            x2d = ops.MLPFn.apply(x2d, self._packs[:-2], need_tape, 'relu_last', *[p for l in layers[:-1] for p in (l.kernel, l.bias)])
+            x2d = ops.MLPFn.apply(x2d, self._packs[:-2], need_tape, False, True, *[p for l in layers[:-1] for p in (l.kernel, l.bias)])
         last, norm = layers[-1], self.transform_norm
         return ops.DenseActLNFn.apply(x2d, last.kernel, last.bias, norm.gamma, norm.beta, self._packs[-2],
                                       ops.ffn_act_code(self.transform), need_tape)

@@ -275,15 +275,14 @@ class EncoderLayer(nn.Module):
                                            m.wv.bias, m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
                                            m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape,
                                            a_rate, s3)
-            return ops.FFNBlockFn.apply(out1, f[0].kernel, f[0].bias, f[1].kernel, f[1].bias, self.layernorm2.gamma,
-                                        self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape, f.act)
-        out1 = ops.AttnBlockFn.apply(x2, key_pad, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel, m.wv.bias,
-                                     m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
-                                     m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape, cu,
-                                     a_rate, s3)
+        else:
+            out1 = ops.AttnBlockFn.apply(x2, key_pad, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel, m.wv.bias,
+                                         m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
+                                         m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape, cu,
+                                         a_rate, s3)
         out2 = ops.FFNBlockFn.apply(out1, f[0].kernel, f[0].bias, f[1].kernel, f[1].bias, self.layernorm2.gamma,
                                     self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape, f.act)
-        return out2.view(out_shape)
+        return out2 if rows is not None else out2.view(out_shape)      # rows: (R, d) as the blocks leave it
 
 
 class Encoder(nn.Module):
@@ -478,16 +477,12 @@ class Transformer(nn.Module):
         seed = dropout_seeds.next() if training else 0
         if packed is not None and not self.packed_supported(S):
             raise B4CError('packed layout needs bf16, head depth 32 / 64 and S <= 512')
-        n_arg = (len(ids), packed, 'sum') if self.feature_combine == 'sum' else (len(ids) if packed is None else (len(ids), packed))
+        # the positional table is a differentiable input when it is the learned parameter (its gradient: b4c_pos_table_bwd); the
+        # sinusoidal EmbedFn call is the reference's, EmbedLNFn the paper's input stage
+        args = (self.scale, rate, seed, self.compute_dtype, packed, self.feature_combine, len(ids), *ids, *tables)
         if self.embedding_layernorm:
-            # the paper's input stage; the positional table is differentiable when it is the learned parameter
-            x, key_pad = ops.EmbedLNFn.apply(self.position_table, self.embedding_norm.gamma, self.embedding_norm.beta, self.scale,
-                                             rate, seed, self.compute_dtype, n_arg, *ids, *tables)
-        elif self.position_encoding == 'learned':
-            # the table is a differentiable input (its gradient: b4c_pos_table_bwd); the sinusoidal call is the reference's
-            x, key_pad = ops.EmbedFn.apply(self.position_embedding.weight, self.scale, rate, seed, self.compute_dtype, n_arg,
-                                           *ids, *tables)
+            x, key_pad = ops.EmbedLNFn.apply(self.position_table, self.embedding_norm.gamma, self.embedding_norm.beta, *args)
         else:
-            x, key_pad = ops.EmbedFn.apply(self.pos_encoding, self.scale, rate, seed, self.compute_dtype, n_arg, *ids, *tables)
+            x, key_pad = ops.EmbedFn.apply(self.position_table, *args)
         out = self.encoder(x, training, key_pad, _input_dropout_done=True, packed=packed, rows=rows)
         return (out, key_pad) if return_key_pad else out

@@ -855,6 +855,13 @@ def _tied_table_steps_whole(table):
         lz.all_rows = True
 
 
+def _attn_call(stem, args, varlen=False, drop=False, dense_suffix=''):
+    """One launch of the attention family `stem`: b4c_<stem>[_varlen][_drop], chosen by the layout (cu given: _varlen) and by
+    whether dropout is on (rate 0 is the entry point without dropout); `args` is that entry point's list."""
+    name = stem + ('_varlen' if varlen else '') + ('_drop' if drop else '')
+    L.check(getattr(L.lib(), 'b4c_' + name + ('' if varlen else dense_suffix))(*args), name)
+
+
 def _attn_mq_drop(q_rows, rate):
     rate = _attn_rate(rate)
     if rate > 0 and q_rows is None:
@@ -877,13 +884,9 @@ def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None, q_rows=None, r
     es = q.element_size()
     # algorithmic work: every query row against the keys of its own sequence (host hint; R x max_len is an upper bound)
     with _record('attn_mq_fwd', kv.shape[0] * 2 * H * dh * es + 2 * R * H * dh * es, 4 * rec_hints.get('sum_q_len', R * max_len) * H * dh):
-        if rate > 0:
-            L.check(L.lib().b4c_attn_mq_fwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o),
-                                                 o.stride(0), _p(lse), B, max_len, H, dh, dt_code(q.dtype), _st(), _p(q_rows), rate,
-                                                 seed), 'attn_mq_fwd_drop')
-        else:
-            L.check(L.lib().b4c_attn_mq_fwd(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
-                                            _p(lse), B, max_len, H, dh, dt_code(q.dtype), _st()), 'attn_mq_fwd')
+        args = [_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0), _p(lse), B, max_len, H, dh,
+                dt_code(q.dtype), _st()]
+        _attn_call('attn_mq_fwd', args + ([_p(q_rows), rate, seed] if rate > 0 else []), drop=rate > 0)
     return o, lse
 
 
@@ -900,15 +903,9 @@ def attn_mq_bwd(q, kv, cu, moff, o, d_o, lse, B, max_len, H, dh, key_pad=None, q
         return dq, dkv
     es = q.element_size()
     with _record('attn_mq_bwd', kv.shape[0] * 4 * H * dh * es + 4 * R * H * dh * es, 10 * rec_hints.get('sum_q_len', R * max_len) * H * dh):
-        if rate > 0:
-            L.check(L.lib().b4c_attn_mq_bwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o),
-                                                 o.stride(0), _p(d_o), d_o.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dkv),
-                                                 dkv.stride(0), B, max_len, H, dh, dt_code(q.dtype), _st(), _p(q_rows), rate, seed),
-                    'attn_mq_bwd_drop')
-        else:
-            L.check(L.lib().b4c_attn_mq_bwd(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
-                                            _p(d_o), d_o.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dkv), dkv.stride(0), B, max_len,
-                                            H, dh, dt_code(q.dtype), _st()), 'attn_mq_bwd')
+        args = [_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
+                _p(lse), _p(dq), dq.stride(0), _p(dkv), dkv.stride(0), B, max_len, H, dh, dt_code(q.dtype), _st()]
+        _attn_call('attn_mq_bwd', args + ([_p(q_rows), rate, seed] if rate > 0 else []), drop=rate > 0)
     return dq, dkv
 
 
@@ -932,18 +929,9 @@ def attn_fwd(qkv, key_pad, B, S, H, dh, cu=None, rate=0.0, seed=0):
     # padded layout computes)
     pairs = rec_hints.get('sum_len_sq', T_tok * S) if cu is not None else T_tok * S
     with _record('attn_fwd', T_tok * 4 * d * qkv.element_size(), 4 * pairs * d):
-        if rate > 0 and cu is None:
-            L.check(L.lib().b4c_attn_fwd_drop(_p(qkv), qkv.stride(0), _p(key_pad), _p(o), d, _p(lse), B, S, H, dh,
-                                              dt_code(qkv.dtype), _st(), rate, seed), 'attn_fwd_drop')
-        elif rate > 0:
-            L.check(L.lib().b4c_attn_fwd_varlen_drop(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), d, _p(lse), B, S, H, dh,
-                                                     dt_code(qkv.dtype), _st(), rate, seed), 'attn_fwd_varlen_drop')
-        elif cu is None:
-            L.check(L.lib().b4c_attn_fwd(_p(qkv), qkv.stride(0), _p(key_pad), _p(o), d, _p(lse), B, S, H, dh,
-                                         dt_code(qkv.dtype), _st()), 'attn_fwd')
-        else:
-            L.check(L.lib().b4c_attn_fwd_varlen(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), d, _p(lse), B, S, H, dh,
-                                                dt_code(qkv.dtype), _st()), 'attn_fwd_varlen')
+        args = [_p(qkv), qkv.stride(0), _p(key_pad)] + ([] if cu is None else [_p(cu)]) + \
+            [_p(o), d, _p(lse), B, S, H, dh, dt_code(qkv.dtype), _st()]
+        _attn_call('attn_fwd', args + ([rate, seed] if rate > 0 else []), varlen=cu is not None, drop=rate > 0)
     return o, lse
 
 
@@ -958,22 +946,12 @@ def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None, rate=0.
     T_tok = qkv.shape[0]
     pairs = rec_hints.get('sum_len_sq', T_tok * S) if cu is not None else T_tok * S
     with _record('attn_bwd', T_tok * 8 * H * dh * qkv.element_size(), 10 * pairs * H * dh):
-        if rate > 0 and cu is None:
-            L.check(L.lib().b4c_attn_bwd_drop_ws(_p(qkv), qkv.stride(0), _p(key_pad), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
-                                                 _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
-                                                 dt_code(qkv.dtype), _st(), rate, seed), 'attn_bwd_drop')
-        elif rate > 0:
-            L.check(L.lib().b4c_attn_bwd_varlen_drop(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), o.stride(0), _p(d_o),
-                                                     d_o.stride(0), _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh,
-                                                     _p(ws), need, dt_code(qkv.dtype), _st(), rate, seed), 'attn_bwd_varlen_drop')
-        elif cu is None:
-            L.check(L.lib().b4c_attn_bwd_ws(_p(qkv), qkv.stride(0), _p(key_pad), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
-                                            _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
-                                            dt_code(qkv.dtype), _st()), 'attn_bwd')
-        else:
-            L.check(L.lib().b4c_attn_bwd_varlen(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), o.stride(0), _p(d_o),
-                                                d_o.stride(0), _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws),
-                                                need, dt_code(qkv.dtype), _st()), 'attn_bwd_varlen')
+        args = [_p(qkv), qkv.stride(0), _p(key_pad)] + ([] if cu is None else [_p(cu)]) + \
+            [_p(o), o.stride(0), _p(d_o), d_o.stride(0), _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
+             dt_code(qkv.dtype), _st()]
+        # (the dense entry points that take the workspace are b4c_attn_bwd_ws / b4c_attn_bwd_drop_ws)
+        _attn_call('attn_bwd', args + ([rate, seed] if rate > 0 else []), varlen=cu is not None, drop=rate > 0,
+                   dense_suffix='_ws')
     _background_kick(actx)      # the next piece of the vocabulary head's dW sweep starts when this kernel has left the CUs
     return dqkv
 
@@ -1959,46 +1937,70 @@ def _as2d(x):
 # --------------------------------------------------------------------------------------
 # autograd blocks
 # --------------------------------------------------------------------------------------
+def _embed_stage_fwd(ctx, pe, n, packed, args):
+    """What the two input stages do in front of their forward kernel.  args = (*ids, *tables), the LAST 2 n inputs of apply
+    -> (dense_ids, ids, tables): ids are the ones the tables' backward works on (packed layout: the packed ids, B = 1, S = T rows)."""
+    ids, tables = list(args[:n]), list(args[n:])
+    dense_ids = ids
+    if packed is not None:
+        # one gather per feature
+        pk_ids = []
+        for i in ids:
+            flat = i.reshape(-1)
+            if flat.dtype != torch.int64 or not flat.is_contiguous():
+                flat = flat.to(torch.int64).contiguous()
+            o = torch.empty(1, packed.T, dtype=torch.int64, device=flat.device)
+            L.check(L.lib().b4c_gather_i64(_p(flat), _p(packed.tok_src), _p(o), packed.T, _st()), 'gather_i64')
+            pk_ids.append(o)
+        ids = pk_ids
+    # a table under a row-lazy optimizer (optim.LazyRows): the rows about to be read are brought up to date first (a backward
+    # that gathers again reads the same, caught-up rows)
+    first_table = len(ctx.needs_input_grad) - n
+    for j, (t, i) in enumerate(zip(tables, ids)):
+        lz = getattr(t, '_b4c_lazy', None)
+        if lz is not None:
+            lz.catch_up(i, note=ctx.needs_input_grad[first_table + j])
+    ctx.pe = pe
+    if ctx.needs_input_grad[0]:        # a learned positional table: what its gradient kernel needs
+        if packed is not None and packed.packed_of is None:
+            raise B4CError('learned positions in the packed layout need Packed.packed_of (the row of every dense position)')
+        ctx.seqs = (dense_ids[0].shape[0], dense_ids[0].shape[1], packed.packed_of if packed is not None else None)
+    return dense_ids, ids, tables
+
+
+def _embed_stage_bwd(ctx, ids, tables, g, rate, seed, lead=()):
+    """The gradients both input stages end with: g [B, S, d] (packed layout [1, T, d]) is the gradient behind scale * rows + PE,
+    (rate, seed) the dropout still to be applied to it.  Adds the learned positional table's and the tables' gradients into their
+    sinks and announces them -> autograd's return values; `lead`: the gradients of the inputs right behind pe."""
+    dpe = None
+    if ctx.needs_input_grad[0]:
+        B, S, row_of = ctx.seqs
+        # dense layout: sequence b owns rows b*S .. (b+1)*S, pad rows included (the forward adds P there too); packed: the row
+        # of a dense position is packed_of's (a Cloze batch pads BEFORE its closing [SEP]: positions are not 0 .. len-1)
+        cu = dense_cu(B, S, g.device) if row_of is None else None
+        pactx, (psink,) = grad_sinks(ctx.pe)
+        pos_table_bwd(g, cu, B, S, rate, seed, psink, row_of=row_of)
+        _ready(ctx.pe)
+        dpe = None if pactx is not None else psink
+    actx, sinks = grad_sinks(*tables)
+    embed_concat_pe_bwd(ids, tables, g, ctx.scale, rate, seed, into=sinks)
+    _ready(*tables)
+    lead = (dpe,) + tuple(lead)
+    return sink_returns(ctx, lead + (None,) * (len(ctx.needs_input_grad) - len(tables) - len(lead)), actx, sinks)
+
+
 class EmbedFn(torch.autograd.Function):
-    """R6: gather + concat + *sqrt(d) + PE (+ input dropout).  apply(pe, scale, rate, seed, dtype, n, *ids, *tables);
-    n may be (n, Packed): the packed layout, output (1, T, d); or (n, Packed | None, 'sum'): the features' rows are added.
+    """R6: gather + concat + *sqrt(d) + PE (+ input dropout).  apply(pe, scale, rate, seed, dtype, packed, combine, n, *ids, *tables);
+    packed (Packed or None): the packed layout, output (1, T, d); combine 'concat' or 'sum' (the features' rows are added).
     pe is differentiable when it is a parameter (learned positions): its gradient is b4c_pos_table_bwd's."""
 
     @staticmethod
-    def forward(ctx, pe, scale, rate, seed, dtype, n, *args):
-        packed, combine = None, 'concat'
-        if isinstance(n, tuple):
-            if len(n) == 3:
-                n, packed, combine = n
-            else:
-                n, packed = n
-        ids, tables = list(args[:n]), list(args[n:])
-        dense_ids = ids
-        if packed is not None:
-            # backward works on the packed ids (one gather per feature): B = 1, S = T rows
-            pk_ids = []
-            for i in ids:
-                flat = i.reshape(-1)
-                if flat.dtype != torch.int64 or not flat.is_contiguous():
-                    flat = flat.to(torch.int64).contiguous()
-                o = torch.empty(1, packed.T, dtype=torch.int64, device=flat.device)
-                L.check(L.lib().b4c_gather_i64(_p(flat), _p(packed.tok_src), _p(o), packed.T, _st()), 'gather_i64')
-                pk_ids.append(o)
-            ids = pk_ids
-        # a table under a row-lazy optimizer (optim.LazyRows): the rows about to be read are brought up to date first
-        for j, (t, i) in enumerate(zip(tables, ids)):
-            lz = getattr(t, '_b4c_lazy', None)
-            if lz is not None:
-                lz.catch_up(i, note=ctx.needs_input_grad[6 + n + j])
+    def forward(ctx, pe, scale, rate, seed, dtype, packed, combine, n, *args):
+        dense_ids, ids, tables = _embed_stage_fwd(ctx, pe, n, packed, args)
         out, key_pad = embed_concat_pe_fwd(dense_ids, [t.detach() for t in tables], pe.detach(), scale, rate, seed, dtype, packed,
                                            combine)
         ctx.save_for_backward(*ids, *tables)
         ctx.n, ctx.scale, ctx.rate, ctx.seed = n, scale, rate, seed
-        if ctx.needs_input_grad[0]:        # a learned positional table: what its gradient kernel needs
-            ctx.pe = pe
-            if packed is not None and packed.packed_of is None:
-                raise B4CError('learned positions in the packed layout need Packed.packed_of (the row of every dense position)')
-            ctx.seqs = (dense_ids[0].shape[0], dense_ids[0].shape[1], packed.packed_of if packed is not None else None)
         ctx.mark_non_differentiable(key_pad)
         ctx.set_materialize_grads(False)       # (or autograd fills a zero "gradient" of key_pad's size every step)
         return out, key_pad
@@ -2009,65 +2011,24 @@ class EmbedFn(torch.autograd.Function):
         ids, tables = list(saved[:ctx.n]), list(saved[ctx.n:])
         flush_pending_dw(getattr(tables[0], '_b4c_ctx', None))
         if dout is None:
-            return (None,) * (6 + 2 * ctx.n)
+            return (None,) * len(ctx.needs_input_grad)
         dout = dout.reshape(ids[0].shape[0], ids[0].shape[1], -1).contiguous()
-        dpe = None
-        if ctx.needs_input_grad[0]:
-            B, S, row_of = ctx.seqs
-            # dense layout: sequence b owns rows b*S .. (b+1)*S, pad rows included (the forward adds P there too); packed: the row
-            # of a dense position is packed_of's (a Cloze batch pads BEFORE its closing [SEP]: positions are not 0 .. len-1)
-            cu = dense_cu(B, S, dout.device) if row_of is None else None
-            pactx, (psink,) = grad_sinks(ctx.pe)
-            pos_table_bwd(dout, cu, B, S, ctx.rate, ctx.seed, psink, row_of=row_of)
-            _ready(ctx.pe)
-            dpe = None if pactx is not None else psink
-        actx, sinks = grad_sinks(*tables)
-        embed_concat_pe_bwd(ids, tables, dout, ctx.scale, ctx.rate, ctx.seed, into=sinks)
-        _ready(*tables)
-        return sink_returns(ctx, (dpe,) + (None,) * (5 + ctx.n), actx, sinks)
+        return _embed_stage_bwd(ctx, ids, tables, dout, ctx.rate, ctx.seed)
 
 
 class EmbedLNFn(torch.autograd.Function):
     """The paper's input stage (no reference counterpart): drop(LayerNorm(scale * rows + PE)), one kernel each way
-    (b4c_embed_ln_fwd / _bwd).  apply(pe, gamma, beta, scale, rate, seed, dtype, n, *ids, *tables); n as EmbedFn's.  The tables'
-    and a learned pe's gradients are EmbedFn's kernels on the pre-norm gradient, at rate 0."""
+    (b4c_embed_ln_fwd / _bwd).  apply(pe, gamma, beta, scale, rate, seed, dtype, packed, combine, n, *ids, *tables), as EmbedFn's.
+    The tables' and a learned pe's gradients are EmbedFn's kernels on the pre-norm gradient, at rate 0."""
 
     @staticmethod
-    def forward(ctx, pe, gamma, beta, scale, rate, seed, dtype, n, *args):
-        packed, combine = None, 'concat'
-        if isinstance(n, tuple):
-            if len(n) == 3:
-                n, packed, combine = n
-            else:
-                n, packed = n
-        ids, tables = list(args[:n]), list(args[n:])
-        dense_ids = ids
-        if packed is not None:
-            # the tables' backward works on the packed ids (one gather per feature): B = 1, S = T rows
-            pk_ids = []
-            for i in ids:
-                flat = i.reshape(-1)
-                if flat.dtype != torch.int64 or not flat.is_contiguous():
-                    flat = flat.to(torch.int64).contiguous()
-                o = torch.empty(1, packed.T, dtype=torch.int64, device=flat.device)
-                L.check(L.lib().b4c_gather_i64(_p(flat), _p(packed.tok_src), _p(o), packed.T, _st()), 'gather_i64')
-                pk_ids.append(o)
-            ids = pk_ids
-        # a table under a row-lazy optimizer (optim.LazyRows): the rows about to be read are brought up to date first (the
-        # backward's second gather reads the same, caught-up rows)
-        for j, (t, i) in enumerate(zip(tables, ids)):
-            lz = getattr(t, '_b4c_lazy', None)
-            if lz is not None:
-                lz.catch_up(i, note=ctx.needs_input_grad[8 + n + j])
+    def forward(ctx, pe, gamma, beta, scale, rate, seed, dtype, packed, combine, n, *args):
+        dense_ids, ids, tables = _embed_stage_fwd(ctx, pe, n, packed, args)
         out, key_pad, stats = embed_ln_fwd(dense_ids, [t.detach() for t in tables], pe.detach(), scale, gamma.detach(), beta.detach(),
                                            rate, seed, dtype, packed, combine)
         ctx.save_for_backward(*ids, *tables, *(dense_ids if packed is not None else ()), stats)
         ctx.n, ctx.scale, ctx.rate, ctx.seed, ctx.packed, ctx.combine = n, scale, rate, seed, packed, combine
-        ctx.pe, ctx.norm = pe, (gamma, beta)
-        if ctx.needs_input_grad[0]:        # a learned positional table: what its gradient kernel needs
-            if packed is not None and packed.packed_of is None:
-                raise B4CError('learned positions in the packed layout need Packed.packed_of (the row of every dense position)')
-            ctx.seqs = (dense_ids[0].shape[0], dense_ids[0].shape[1], packed.packed_of if packed is not None else None)
+        ctx.norm = (gamma, beta)
         ctx.mark_non_differentiable(key_pad)
         ctx.set_materialize_grads(False)       # (or autograd fills a zero "gradient" of key_pad's size every step)
         return out, key_pad
@@ -2079,27 +2040,15 @@ class EmbedLNFn(torch.autograd.Function):
         dense_ids = list(saved[2 * n:3 * n]) if ctx.packed is not None else ids
         flush_pending_dw(getattr(tables[0], '_b4c_ctx', None))
         if dout is None:
-            return (None,) * (8 + 2 * n)
+            return (None,) * len(ctx.needs_input_grad)
         gamma, beta = ctx.norm
         gctx, gsinks = grad_sinks(gamma, beta)
         dpre, _, _ = embed_ln_bwd(dense_ids, [t.detach() for t in tables], ctx.pe.detach(), ctx.scale, gamma.detach(), stats,
                                   dout.reshape(-1, dout.shape[-1]).contiguous(), ctx.rate, ctx.seed, ctx.packed, ctx.combine,
                                   into=gsinks)
         _ready(gamma, beta)
-        dgam, dbet = (None, None) if gctx is not None else gsinks
         dpre = dpre.reshape(ids[0].shape[0], ids[0].shape[1], -1)
-        dpe = None
-        if ctx.needs_input_grad[0]:
-            B, S, row_of = ctx.seqs
-            cu = dense_cu(B, S, dpre.device) if row_of is None else None
-            pactx, (psink,) = grad_sinks(ctx.pe)
-            pos_table_bwd(dpre, cu, B, S, 0.0, 0, psink, row_of=row_of)
-            _ready(ctx.pe)
-            dpe = None if pactx is not None else psink
-        actx, sinks = grad_sinks(*tables)
-        embed_concat_pe_bwd(ids, tables, dpre, ctx.scale, 0.0, 0, into=sinks)
-        _ready(*tables)
-        return sink_returns(ctx, (dpe, dgam, dbet) + (None,) * (5 + n), actx, sinks)
+        return _embed_stage_bwd(ctx, ids, tables, dpre, 0.0, 0, lead=(None, None) if gctx is not None else gsinks)
 
 
 class DenseActLNFn(torch.autograd.Function):
@@ -2139,6 +2088,39 @@ class DenseActLNFn(torch.autograd.Function):
         return sink_returns(ctx, (dx,), actx, sinks)
 
 
+def _residual_ln_fwd(a, wt, bias, x, gamma, beta, rate, seed, training):
+    """The tail of an encoder half: LayerNorm(x + drop(a @ wt^T + bias)) -> (z, out, stats); z and stats only in training.  bf16 up
+    to d_model 256: the GEMM does it in its epilogue (gemm_ln_supported)."""
+    d = x.shape[1]
+    rate = rate if training else 0.0
+    if gemm_ln_supported(a, d):
+        return gemm_nt_add_ln(a, wt, bias, x, gamma.detach(), beta.detach(), rate, seed, save=training)
+    y = gemm_nt(a, wt, d, bias)
+    return add_dropout_layernorm_fwd(x, y, gamma.detach(), beta.detach(), rate, seed, save=training)
+
+
+def _attn_tail_bwd(dout, z, stats, gamma, rate, seed, o, wc_o, params, actx, sinks, dxdw):
+    """Backward of _residual_ln_fwd behind an attention kernel -> (dz, d_o): the gradient of the residual branch and of the
+    attention output o.  params / sinks: the block's ten (wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta) and their sinks; the
+    gradients of wo, bo, gamma, beta are added here.  dxdw: the output projection may take gemm_dxdw (the full block alone)."""
+    wo, bo = params[6:8]
+    gwo, gbo, ggam, gbet = sinks[6:]
+    d = z.shape[1]
+    routes = _arena_routes(actx)
+    if routes and fused_attn_out_bwd and attn_out_bwd_supported(o, z):
+        dz, d_o = attn_out_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, o, wc_o, gwo, gbo, ggam, gbet)
+        _ready(wo, bo)
+        return dz, d_o
+    dz, dy, _, _ = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, into=(ggam, gbet))
+    if dxdw and routes and fused_dxdw >= 3 and dxdw_supported(o, dy, 1):
+        d_o = gemm_dxdw(o, dy, wc_o, [gwo], [gbo])
+        _ready(wo, bo)
+    else:
+        queue_dw(actx, o, dy, d, d, [gwo], [gbo], (wo, bo))
+        d_o = gemm_nt(dy, wc_o, d)
+    return dz, d_o
+
+
 class AttnBlockFn(torch.autograd.Function):
     """R8 + first half of R10: LN1(x + drop(MHA(x))).  x: [T, d] in the compute dtype.
     attn_rate, attn_seed: dropout on the attention probabilities (attn_fwd; no reference counterpart), applied as given."""
@@ -2152,22 +2134,17 @@ class AttnBlockFn(torch.autograd.Function):
         wt_o, _, b_o = pk_o.get(x.dtype, d, training)
         with _timed('qkv_fwd'):
             qkv = gemm_nt(x, wt_qkv, 3 * d, b_qkv)
+        # (without attention dropout: attn_fwd / attn_bwd are called as they have always been, without the keywords)
+        attn_drop = {'rate': attn_rate, 'seed': attn_seed} if attn_rate > 0 else {}
         with _timed('attn_fwd'):
-            # (without attention dropout: the call as it has always been)
-            o, lse = attn_fwd(qkv, key_pad, B, S, H, dh, cu, **({'rate': attn_rate, 'seed': attn_seed} if attn_rate > 0 else {}))
-        if gemm_ln_supported(o, d):
-            z, out, stats = gemm_nt_add_ln(o, wt_o, b_o, x, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
-                                           save=training)
-        else:
-            y = gemm_nt(o, wt_o, d, b_o)
-            z, out, stats = add_dropout_layernorm_fwd(x, y, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
-                                                      save=training)
+            o, lse = attn_fwd(qkv, key_pad, B, S, H, dh, cu, **attn_drop)
+        z, out, stats = _residual_ln_fwd(o, wt_o, b_o, x, gamma, beta, rate, seed, training)
         if training:
             ctx.save_for_backward(x, key_pad, qkv, o, lse, z, stats, gamma)
             ctx.pk = (pk_qkv, pk_o)
             ctx.dims = (B, S, H, dh, rate, seed)
             ctx.cu = cu
-            ctx.attn_drop = {'rate': attn_rate, 'seed': attn_seed} if attn_rate > 0 else {}
+            ctx.attn_drop = attn_drop
             ctx.params = (wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta)
         return out
 
@@ -2176,34 +2153,23 @@ class AttnBlockFn(torch.autograd.Function):
         x, key_pad, qkv, o, lse, z, stats, gamma = ctx.saved_tensors
         pk_qkv, pk_o = ctx.pk
         B, S, H, dh, rate, seed = ctx.dims
-        wq, bq, wk, bk, wv, bv, wo, bo, gam, bet = ctx.params
+        wq, bq, wk, bk, wv, bv = ctx.params[:6]
         d = H * dh
         actx, sinks = grad_sinks(*ctx.params)
-        gwq, gbq, gwk, gbk, gwv, gbv, gwo, gbo, ggam, gbet = sinks
-        routes = _arena_routes(actx)
+        gwq, gbq, gwk, gbk, gwv, gbv = sinks[:6]
         _, wc_o, _ = pk_o.get(x.dtype, d, True)
         _, wc_qkv, _ = pk_qkv.get(x.dtype, d, True)
-        if routes and fused_attn_out_bwd and attn_out_bwd_supported(o, z):
-            dz, d_o = attn_out_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, o, wc_o, gwo, gbo, ggam, gbet)
-            _ready(wo, bo)
-        else:
-            dz, dy, _, _ = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, into=(ggam, gbet))
-            if routes and fused_dxdw >= 3 and dxdw_supported(o, dy, 1):
-                d_o = gemm_dxdw(o, dy, wc_o, [gwo], [gbo])
-                _ready(wo, bo)
-            else:
-                queue_dw(actx, o, dy, d, d, [gwo], [gbo], (wo, bo))
-                d_o = gemm_nt(dy, wc_o, d)
+        dz, d_o = _attn_tail_bwd(dout, z, stats, gamma, rate, seed, o, wc_o, ctx.params, actx, sinks, dxdw=True)
         with _timed('attn_bwd'):
             dqkv = attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, ctx.cu, actx, **ctx.attn_drop)
-        if routes and fused_dxdw and dxdw_supported(x, dqkv, 3, residual=dz):
+        if _arena_routes(actx) and fused_dxdw and dxdw_supported(x, dqkv, 3, residual=dz):
             # dX and dW | db of the fused Q | K | V projection in one pass over dqkv (csrc/gemm_dxdw.hip)
             dx = gemm_dxdw(x, dqkv, wc_qkv, [gwq, gwk, gwv], [gbq, gbk, gbv], residual=dz)
             _ready(wq, bq, wk, bk, wv, bv)
         else:
             queue_dw(actx, x, dqkv, d, 3 * d, [gwq, gwk, gwv], [gbq, gbk, gbv], (wq, bq, wk, bk, wv, bv))
             dx = gemm_nt(dqkv, wc_qkv, d, residual=dz)
-        _ready(gam, bet)
+        _ready(*ctx.params[8:])
         flush_pending_dw(actx)      # this layer's four weight gradients (two queued by FFNBlockFn.backward) in one launch
         return sink_returns(ctx, (dx, None), actx, sinks)
 
@@ -2255,13 +2221,7 @@ class MQAttnBlockFn(torch.autograd.Function):
         x_m = gather_rows(x, midx, R)
         q_m = gemm_nt(x_m, wt_qkv[:d], d, b_qkv[:d])
         o_m, lse = attn_mq_fwd(q_m, kv, cu, moff, B, max_len, H, dh, key_pad, midx, attn_rate, attn_seed)
-        if gemm_ln_supported(o_m, d):
-            z, out, stats = gemm_nt_add_ln(o_m, wt_o, b_o, x_m, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
-                                           save=training)
-        else:
-            y = gemm_nt(o_m, wt_o, d, b_o)
-            z, out, stats = add_dropout_layernorm_fwd(x_m, y, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
-                                                      save=training)
+        z, out, stats = _residual_ln_fwd(o_m, wt_o, b_o, x_m, gamma, beta, rate, seed, training)
         if training:
             ctx.save_for_backward(x, x_m, midx, moff, cu, key_pad, q_m, kv, o_m, lse, z, stats, gamma)
             ctx.pk = (pk_qkv, pk_o)
@@ -2274,33 +2234,26 @@ class MQAttnBlockFn(torch.autograd.Function):
         x, x_m, midx, moff, cu, key_pad, q_m, kv, o_m, lse, z, stats, gamma = ctx.saved_tensors
         pk_qkv, pk_o = ctx.pk
         B, max_len, H, dh, rate, seed, attn_rate, attn_seed = ctx.dims
-        wq, bq, wk, bk, wv, bv, wo, bo, gam, bet = ctx.params
+        wq, bq, wk, bk, wv, bv = ctx.params[:6]
         d = H * dh
         actx, sinks = grad_sinks(*ctx.params)
-        gwq, gbq, gwk, gbk, gwv, gbv, gwo, gbo, ggam, gbet = sinks
-        routes = _arena_routes(actx)
+        gwq, gbq, gwk, gbk, gwv, gbv = sinks[:6]
         _, wc_o, _ = pk_o.get(x.dtype, d, True)
         _, wc_qkv, _ = pk_qkv.get(x.dtype, d, True)
-        if routes and fused_attn_out_bwd and attn_out_bwd_supported(o_m, z):
-            dz, d_o = attn_out_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, o_m, wc_o, gwo, gbo, ggam, gbet)
-            _ready(wo, bo)
-        else:
-            dz, dy, _, _ = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, into=(ggam, gbet))
-            queue_dw(actx, o_m, dy, d, d, [gwo], [gbo], (wo, bo))
-            d_o = gemm_nt(dy, wc_o, d)
+        dz, d_o = _attn_tail_bwd(dout, z, stats, gamma, rate, seed, o_m, wc_o, ctx.params, actx, sinks, dxdw=False)
         dq, dkv = attn_mq_bwd(q_m, kv, cu, moff, o_m, d_o, lse, B, max_len, H, dh, key_pad, midx, attn_rate, attn_seed)
         queue_dw(actx, x_m, dq, d, d, [gwq], [gbq], (wq, bq))
         flush_pending_dw(actx)                  # (the query-row problems have R rows, the key / value problem T)
         dx_m = gemm_nt(dq, wc_qkv[:, :d], d, residual=dz, out_dtype=torch.float32)      # query rows: through Wq + the residual branch (kept in fp32 until it joins dx)
         # every token: through Wk | Wv
-        if routes and fused_dxdw >= 2 and dxdw_supported(x, dkv, 2):
+        if _arena_routes(actx) and fused_dxdw >= 2 and dxdw_supported(x, dkv, 2):
             dx = gemm_dxdw(x, dkv, wc_qkv[:, d:3 * d], [gwk, gwv], [gbk, gbv])
             _ready(wk, bk, wv, bv)
         else:
             queue_dw(actx, x, dkv, d, 2 * d, [gwk, gwv], [gbk, gbv], (wk, bk, wv, bv))
             dx = gemm_nt(dkv, wc_qkv[:, d:3 * d], d)
         rows_add_(dx, midx, dx_m)
-        _ready(gam, bet)
+        _ready(*ctx.params[8:])
         flush_pending_dw(actx)
         return sink_returns(ctx, (dx, None, None, None, None), actx, sinks)
 
@@ -2322,13 +2275,9 @@ class FFNBlockFn(torch.autograd.Function):
         if relu and fused_ffn_fwd and ffn_fwd_supported(x, Fp):
             h, z, out, stats = ffn_fwd(x, wt1, bb1, wt2, bb2, gamma.detach(), beta.detach(), pk1.N, Fp, rate if training else 0.0, seed,
                                        save=training)
-        elif gemm_ln_supported((h := gemm_nt(x, wt1, Fp, bb1, act=act, pre=u)), d):
-            z, out, stats = gemm_nt_add_ln(h, wt2, bb2, x, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
-                                           save=training)
         else:
-            y = gemm_nt(h, wt2, d, bb2)
-            z, out, stats = add_dropout_layernorm_fwd(x, y, gamma.detach(), beta.detach(), rate if training else 0.0, seed,
-                                                      save=training)
+            h = gemm_nt(x, wt1, Fp, bb1, act=act, pre=u)
+            z, out, stats = _residual_ln_fwd(h, wt2, bb2, x, gamma, beta, rate, seed, training)
         if training:
             ctx.save_for_backward(x, h, z, stats, gamma, *(() if relu else (u,)))
             ctx.pk = (pk1, pk2)
@@ -2372,19 +2321,18 @@ class FFNBlockFn(torch.autograd.Function):
 
 class MLPFn(torch.autograd.Function):
     """Chain of dense layers (relu on all but the last): the SoftMaxHead's trunk + vocabulary
-    projection (R12, logits).  apply(x, packs, training, out_fp32, *[k0, b0, k1, b1, ...])"""
+    projection (R12, logits).  apply(x, packs, training, out_fp32, relu_last, *[k0, b0, k1, b1, ...]); out_fp32: the last layer's
+    output in fp32; relu_last: every layer (also the last) is followed by relu -- the head's trunk alone."""
 
     @staticmethod
-    def forward(ctx, x, packs, training, out_fp32, *params):
-        # out_fp32 == 'relu_last': every layer (also the last) is followed by relu -- the head's trunk alone
-        relu_last = out_fp32 == 'relu_last'
+    def forward(ctx, x, packs, training, out_fp32, relu_last, *params):
         acts = [x]
         n = len(packs)
         for i, pk in enumerate(packs):
             a = acts[-1]
             wt, _, bias = pk.get(x.dtype, a.shape[1], training)
             last = i == n - 1
-            odt = torch.float32 if (last and out_fp32 is True) else a.dtype
+            odt = torch.float32 if (last and out_fp32) else a.dtype
             with _timed('vocab_proj_fwd' if last else 'head_mlp_fwd'):
                 acts.append(gemm_nt(a, wt, pk.Np, bias, act=L.ACT_RELU if (relu_last or not last) else L.ACT_NONE,
                                     out_dtype=odt, out=empty_rows(a.shape[0], pk.Np, odt, a.device)))
@@ -2419,7 +2367,7 @@ class MLPFn(torch.autograd.Function):
             with _timed('vocab_proj_dx' if last else 'head_mlp_dx'):
                 g = gemm_nt(g, wc, a.shape[1], gate=a if i > 0 else None)
         flush_pending_dw(actx)
-        return sink_returns(ctx, (g, None, None, None), actx, sinks)
+        return sink_returns(ctx, (g, None, None, None, None), actx, sinks)
 
 
 # Vocabulary-head weight gradient BESIDE the encoder backward.  The dW sweep is MFMA / VALU bound and leaves HBM idle;
