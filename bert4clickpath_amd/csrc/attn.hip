@@ -13,26 +13,6 @@
 
 #define ATT_TILE 64
 
-template <typename T, int DH>
-__device__ __forceinline__ void load_row(const T *__restrict__ p, float (&v)[DH]) {
-#pragma unroll
-    for (int c = 0; c < DH; c += 8) {
-        float t[8];
-        Vec8<T>::load(p + c, t);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[c + k] = t[k];
-    }
-}
-template <typename T, int DH>
-__device__ __forceinline__ void store_row(T *__restrict__ p, const float (&v)[DH]) {
-#pragma unroll
-    for (int c = 0; c < DH; c += 8) {
-        float t[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[k] = v[c + k];
-        Vec8<T>::store(p + c, t);
-    }
-}
 // stage rows [r0, r0+64) x DH columns starting at column col0 of a [B*S][ld] matrix into fp32 LDS
 template <typename T, int DH>
 __device__ __forceinline__ void stage_tile(const T *__restrict__ base, int ld, int64_t tok0, int r0, int S, int col0,
@@ -49,18 +29,6 @@ __device__ __forceinline__ void stage_tile(const T *__restrict__ base, int ld, i
 #pragma unroll
         for (int k = 0; k < 8; ++k) s[row][part * 8 + k] = t[k];
     }
-}
-template <int DH> __device__ __forceinline__ float dot_lds(const float (&a)[DH], const float *__restrict__ row) {
-    float s = 0.f;
-#pragma unroll
-    for (int d = 0; d < DH; d += 4) {
-        const f32x4 kv = *reinterpret_cast<const f32x4 *>(row + d);
-        s += a[d] * kv[0];
-        s += a[d + 1] * kv[1];
-        s += a[d + 2] * kv[2];
-        s += a[d + 3] * kv[3];
-    }
-    return s;
 }
 
 // DROP (all three kernels): attention-probability dropout by the keep rule of common.h (b4c_attn_keep); q and k are the positions,

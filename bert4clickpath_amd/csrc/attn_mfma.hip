@@ -9,16 +9,12 @@
 //           dK^T = Q^T dS from registers; only dS crosses LDS once, for dQ = dS K.
 //           Waves own key tiles (dK^T / dV^T never leave registers), queries stream in 32-row tiles.
 //
-// v_mfma_f32_32x32x16_bf16 operand maps (lane l: r = l & 31, hf = l >> 5):
-//   A[row r][k = 8 hf + j], B[k = 8 hf + j][col r], j = 0..7;  D reg t: row (t&3) + 8 (t>>2) + 4 hf, col r.
-//   An accumulator tile X used as the B operand of the next MFMA (summing over X's rows): k-step s takes
-//   regs 8s..8s+7, whose rows are 16 s + 8 (j>>2) + 4 hf + (j&3) -- the A operand must use the same k order.
+// The v_mfma_f32_32x32x16_bf16 operand maps and the fragment helpers (rowmap, pack8, frag_tr, frag_from_2x8B) are mfma.h's.
+// DROP (template parameter; the DROP = false bodies are the kernels without it): attention-probability dropout by the keep rule
+// of common.h; the backward kernels build a tile's keep bits with keep_tile_bwd (mfma.h).
 #include <math.h>
 
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+#include "mfma.h"
 
 #define ATT_MAX_KT 8   // key tiles of 32 -> S <= 256
 
@@ -32,34 +28,10 @@ extern "C" void b4c_attn_phases_set(void *p) { (void)hipMemcpyToSymbol(HIP_SYMBO
 #define ATT_STAMP(i) do { } while (0)
 #endif
 
-template <typename K> static void allow_lds_attn(K kernel, size_t bytes) {
-    static thread_local const void *done[8];
-    static thread_local size_t done_bytes[8];
-    static thread_local int ndone = 0;
-    for (int i = 0; i < ndone; ++i)
-        if (done[i] == (const void *)kernel && done_bytes[i] >= bytes) return;
-    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (ndone < 8) { done[ndone] = (const void *)kernel; done_bytes[ndone++] = bytes; }
-}
-
 template <bool NT> __device__ __forceinline__ void att_store16(bf16_t *p, const u32x4 &v) {
     if (NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
     else *reinterpret_cast<u32x4 *>(p) = v;
 }
-__device__ __forceinline__ bf16x8 pack8(const float *p) {
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (bf16_t)p[j];
-    return v;
-}
-__device__ __forceinline__ bf16x8 frag_from_2x8B(const char *p0, const char *p1) {
-    const u32x2 lo = *reinterpret_cast<const u32x2 *>(p0);
-    const u32x2 hi = *reinterpret_cast<const u32x2 *>(p1);
-    u32x4 w = {lo[0], lo[1], hi[0], hi[1]};
-    return __builtin_bit_cast(bf16x8, w);
-}
-__device__ __forceinline__ int rowmap(int t, int hf) { return (t & 3) + 8 * (t >> 2) + 4 * hf; }
-
 // Stage the transpose of a [rows][DH] bf16 block (global, row pitch ld) into LDS as [DH][rows] with row
 // stride `str` bytes (multiple of 8).  Each participating lane owns one dword (2 columns) of 8 consecutive
 // rows: 8 coalesced dword loads, 4 ds_write_b64.  `slot` = which 8-row group this lane-group handles.
@@ -81,43 +53,6 @@ __device__ __forceinline__ void stage_transposed8(const bf16_t *__restrict__ src
     *reinterpret_cast<u32x2 *>(b + 8) = lo1;
     *reinterpret_cast<u32x2 *>(b + str) = hi0;
     *reinterpret_cast<u32x2 *>(b + str + 8) = hi1;
-}
-
-// 4 rows x 16 columns of bf16 read transposed (ds_read_b64_tr_b16): lane i of each 16-lane group gets
-// column (col0 + i) of rows row0..row0+3; the lane supplies the address of row (i>>2), columns 4(i&3)...
-// Checked on MI355X with integer data (scratch/trtest.hip).  EXEC must be full.
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ s16x4 tr_read(const char *p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)(p));
-}
-__device__ __forceinline__ bf16x8 frag_tr(const char *p, int second_off) {
-    const s16x4 a = tr_read(p), b = tr_read(p + second_off);
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 w = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, w);
-}
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-
-// ---- attention-probability dropout (template parameter DROP; the DROP = false bodies are the kernels without it) ----
-// Keep bits of one 32 x 32 score tile of the BACKWARD kernels, which hold the KEY on the lane (r) and the QUERY on the accumulator
-// rows (rowmap): bit t = register t.  The keep rule (common.h) hashes four consecutive keys of one query at once, and the four
-// lanes of a quad hold exactly such four keys: each lane hashes the queries of the registers (r & 3) + 4 tq, tq = 0..3, and the
-// quad exchanges the bits (DPP quad broadcast) -- four hashes per lane per tile, as in the forward, where the four keys are
-// four registers of one lane.  The hash counter b4c_attn_ctr(row, k0, S_arg) is split into the workgroup-uniform
-// base = (b*H + h) * S_arg * (S4 / 4) and a 32-bit lane part q * (S4 / 4) + k0 / 4 (q < 512, S4 / 4 <= 128).  q0 / k_tile = first
-// query / key of the tile.  EXEC must be full.  (quad_bcast, attn_ctr_base: common.h.)
-__device__ __forceinline__ uint32_t attn_keep_tile_bwd(uint64_t seed, uint64_t base, int S_arg, int q0, int k_tile, uint32_t thr, int r, int hf) {
-    const int c = r & 3;
-    const uint32_t s4q = b4c_attn_s4(S_arg) >> 2, kq = (uint32_t)(k_tile + (r & ~3)) >> 2;
-    uint32_t mk = 0;
-#pragma unroll
-    for (int tq = 0; tq < 4; ++tq)
-        mk |= b4c_attn_keep4(seed, base + ((uint32_t)(q0 + c + 8 * tq + 4 * hf) * s4q + kq), thr) << (4 * tq);
-    uint32_t km = ((quad_bcast<0>(mk) >> c) & 0x1111u);
-    km |= ((quad_bcast<1>(mk) >> c) & 0x1111u) << 1;
-    km |= ((quad_bcast<2>(mk) >> c) & 0x1111u) << 2;
-    km |= ((quad_bcast<3>(mk) >> c) & 0x1111u) << 3;
-    return km;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -450,7 +385,7 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
                 }
                 float pv[16], dsv[16];
                 // dropout: dV takes the dropped, rescaled P~; dS = P o (keep / (1 - rate) * dP~ - delta) with the undropped P
-                const uint32_t km = DROP ? attn_keep_tile_bwd(seed, attn_ctr_base(blockIdx.x, S_arg), S_arg, q0, key0 + kt * 32, thr, r, hf) : 0u;
+                const uint32_t km = DROP ? keep_tile_bwd(seed, attn_ctr_base(blockIdx.x, S_arg), S_arg, [q0](int i) { return q0 + i; }, key0 + kt * 32, thr, r, hf) : 0u;
 #pragma unroll
                 for (int t = 0; t < 16; ++t) {
                     const int q = rowmap(t, hf);
@@ -715,7 +650,7 @@ __global__ void __launch_bounds__(512) attn_bwd_resident_kernel(const bf16_t *__
             }
             float pv[16], dsv[16];
             // dropout: dV takes the dropped, rescaled P~; dS = P o (keep / (1 - rate) * dP~ - delta) with the undropped P
-            const uint32_t km = DROP ? attn_keep_tile_bwd(seed, attn_ctr_base(item, S_arg), S_arg, q0, kt * 32, thr, r, hf) : 0u;
+            const uint32_t km = DROP ? keep_tile_bwd(seed, attn_ctr_base(item, S_arg), S_arg, [q0](int i) { return q0 + i; }, kt * 32, thr, r, hf) : 0u;
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 const int q = rowmap(t, hf);
@@ -831,7 +766,7 @@ int b4c_attn_fwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, void 
     const float scale = 1.0f / sqrtf((float)dh);
 #define ATT_FWD_LAUNCH(DHH, QQ, DR)                                                                                      \
     do {                                                                                                                 \
-        allow_lds_attn(attn_fwd_mfma_kernel<DHH, QQ, DR>, shm);                                                          \
+        b4c_allow_lds(attn_fwd_mfma_kernel<DHH, QQ, DR>, shm);                                                         \
         attn_fwd_mfma_kernel<DHH, QQ, DR><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, scale, cu, rate, seed); \
     } while (0)
 #define ATT_FWD_LAUNCH_DH(DHH)                                                                                           \
@@ -857,12 +792,12 @@ int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const
     const float scale = 1.0f / sqrtf((float)dh);
 #define ATT_BWD_BLOCKS(DHH, DR, SHM, NBLK, ACC)                                                                          \
     do {                                                                                                                 \
-        allow_lds_attn(attn_bwd_mfma_kernel<DHH, DR>, SHM);                                                              \
+        b4c_allow_lds(attn_bwd_mfma_kernel<DHH, DR>, SHM);                                                             \
         attn_bwd_mfma_kernel<DHH, DR><<<B * H, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, NBLK, ACC, cu, rate, seed); \
     } while (0)
 #define ATT_BWD_RESIDENT(DHH, DR, SHM, GRID)                                                                             \
     do {                                                                                                                 \
-        allow_lds_attn(attn_bwd_resident_kernel<DHH, DR>, SHM);                                                          \
+        b4c_allow_lds(attn_bwd_resident_kernel<DHH, DR>, SHM);                                                         \
         attn_bwd_resident_kernel<DHH, DR><<<GRID, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, B * H, (int *)delta, cu, rate, seed); \
     } while (0)
 #define ATT_BWD_SELECT(LAUNCH, ...)                                                                                      \

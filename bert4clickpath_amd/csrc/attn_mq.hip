@@ -24,44 +24,11 @@
 // it.  The DROP = false instantiations are the kernels without it.
 #include <math.h>
 
-#include "common.h"
+#include "mfma.h"
 
 #define MQ 16            // query rows per chunk
 #define MQ_THREADS 256
 #define MQ_KB 128        // keys per block: TWO threads per key (lanes l and l + 32 of a wave own the two halves of its row)
-
-template <typename T, int N>
-__device__ __forceinline__ void mq_load(const T *__restrict__ p, float (&v)[N]) {
-#pragma unroll
-    for (int c = 0; c < N; c += 8) {
-        float t[8];
-        Vec8<T>::load(p + c, t);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[c + k] = t[k];
-    }
-}
-template <typename T, int N>
-__device__ __forceinline__ void mq_store(T *__restrict__ p, const float (&v)[N]) {
-#pragma unroll
-    for (int c = 0; c < N; c += 8) {
-        float t[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[k] = v[c + k];
-        Vec8<T>::store(p + c, t);
-    }
-}
-template <int N> __device__ __forceinline__ float mq_dot(const float (&a)[N], const float *__restrict__ row) {
-    float s = 0.f;
-#pragma unroll
-    for (int d = 0; d < N; d += 4) {
-        const f32x4 q4 = *reinterpret_cast<const f32x4 *>(row + d);      // the 32 lanes of a half read one address: broadcast
-        s += a[d] * q4[0];
-        s += a[d + 1] * q4[1];
-        s += a[d + 2] * q4[2];
-        s += a[d + 3] * q4[3];
-    }
-    return s;
-}
 
 // LDS (dynamic): sQ [MQ][DH] f32 | sP [MQ][SP] f32 | sV [MQ_KB][DH] T          (SP = padded longest sequence)
 template <typename T, int DH, bool DROP>
@@ -92,7 +59,7 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
         float kr0[HD];
 #pragma unroll
         for (int d = 0; d < HD; ++d) kr0[d] = 0.f;
-        if (kl < S) mq_load<T, HD>(kv + (tok0 + kl) * ld_kv + h * DH + half * HD, kr0);
+        if (kl < S) load_row<T, HD>(kv + (tok0 + kl) * ld_kv + h * DH + half * HD, kr0);
         float vraw[VCH][8];
 #pragma unroll
         for (int i = 0; i < VCH; ++i) {
@@ -124,13 +91,13 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
             if (k0 > 0) {
 #pragma unroll
                 for (int d = 0; d < HD; ++d) kr[d] = 0.f;
-                if (j < S) mq_load<T, HD>(kv + (tok0 + j) * ld_kv + h * DH + half * HD, kr);
+                if (j < S) load_row<T, HD>(kv + (tok0 + j) * ld_kv + h * DH + half * HD, kr);
             }
             const bool pad = j < S && key_pad && key_pad[tok0 + j];
             for (int m0 = 0; m0 < mq; m0 += 4) {              // four independent dot -> shuffle chains in flight
                 float s4[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) s4[u] = mq_dot<HD>(kr, sQ + (m0 + u) * DH + half * HD);
+                for (int u = 0; u < 4; ++u) s4[u] = dot_lds<HD>(kr, sQ + (m0 + u) * DH + half * HD);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) s4[u] += __shfl_xor(s4[u], 32);
 #pragma unroll
@@ -255,12 +222,12 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
 #pragma unroll
         for (int d = 0; d < HD; ++d) { kr[d] = 0.f; vr[d] = 0.f; dk[d] = 0.f; dv[d] = 0.f; }
         if (live) {
-            mq_load<T, HD>(kv + (tok0 + j) * ld_kv + h * DH + half * HD, kr);
-            mq_load<T, HD>(kv + (tok0 + j) * ld_kv + dm + h * DH + half * HD, vr);
+            load_row<T, HD>(kv + (tok0 + j) * ld_kv + h * DH + half * HD, kr);
+            load_row<T, HD>(kv + (tok0 + j) * ld_kv + dm + h * DH + half * HD, vr);
         }
         const bool pad = live && key_pad && key_pad[tok0 + j];
         __syncthreads();                                      // the previous key block's dq phase is done with sK
-        mq_store<T, HD>(sK + kl * DH + half * HD, kr);          // (zeros for the slots past the sequence)
+        store_row<T, HD>(sK + kl * DH + half * HD, kr);          // (zeros for the slots past the sequence)
         for (int ci = 0; ci < nchunk; ++ci) {
             const int mc = ci * MQ, mq = min(MQ, M - mc);
             __syncthreads();                                  // the previous chunk's dq phase is done with sQ / sG / sDS
@@ -292,8 +259,8 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
             __syncthreads();
             // phase 1: this thread's half key against the chunk's queries
             for (int m = 0; m < mq; ++m) {
-                float sc = mq_dot<HD>(kr, sQ + m * DH + half * HD);
-                float dp = mq_dot<HD>(vr, sG + m * DH + half * HD);
+                float sc = dot_lds<HD>(kr, sQ + m * DH + half * HD);
+                float dp = dot_lds<HD>(vr, sG + m * DH + half * HD);
                 sc += __shfl_xor(sc, 32);
                 dp += __shfl_xor(dp, 32);
                 float p = 0.f, ds = 0.f;
@@ -358,8 +325,8 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
         if (live) {
 #pragma unroll
             for (int d = 0; d < HD; ++d) dk[d] /= sqrt_dk;
-            mq_store<T, HD>(dkv + (tok0 + j) * ld_dkv + h * DH + half * HD, dk);
-            mq_store<T, HD>(dkv + (tok0 + j) * ld_dkv + dm + h * DH + half * HD, dv);
+            store_row<T, HD>(dkv + (tok0 + j) * ld_dkv + h * DH + half * HD, dk);
+            store_row<T, HD>(dkv + (tok0 + j) * ld_dkv + dm + h * DH + half * HD, dv);
         }
     }
 }
@@ -367,29 +334,11 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
 // ------------------------------------------------------------------------------------------------------------------
 // bf16 forward on the matrix cores, ONE WAVE per (sequence, head): the item's work (a 32-row query tile against S keys)
 // is too small for a workgroup's barriers, and what it needs is many items in flight per CU (16 waves = 16 items).
-//   S^T = K Q^T per 32-key tile, key on the accumulator rows, query on the lane (the maps of attn_mfma.hip): K and Q
+//   S^T = K Q^T per 32-key tile, key on the accumulator rows, query on the lane (attn_mfma.hip's forward; operand maps: mfma.h): K and Q
 //   fragments come straight from global memory (16 B per lane and k-step), the softmax statistics are lane-local (one
 //   xor-32 exchange), P^T feeds O^T = V^T P^T from the accumulator registers; only V passes through LDS (a wave-private
 //   double buffer, for the transposed fragment reads).  The next tile's K and V loads are in flight during a tile.
 // ------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) unsigned mq_u32x4;
-typedef __attribute__((ext_vector_type(4))) short mq_s16x4;
-typedef __attribute__((ext_vector_type(4))) __bf16 mq_bf16x4;
-__device__ __forceinline__ int mq_rowmap(int t, int hf) { return (t & 3) + 8 * (t >> 2) + 4 * hf; }
-__device__ __forceinline__ bf16x8 mq_pack8(const float *p) {
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (bf16_t)p[j];
-    return v;
-}
-__device__ __forceinline__ bf16x8 mq_frag_tr(const char *p, int second_off) {
-    const mq_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mq_s16x4 __attribute__((address_space(3))) *)(p));
-    const mq_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mq_s16x4 __attribute__((address_space(3))) *)(p + second_off));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    const s16x8 w = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, w);
-}
-
 #define MQ_WAVES 4
 template <int DH, bool HAS_PAD, bool DROP>
 __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(const bf16_t *__restrict__ q, int ld_q, const bf16_t *__restrict__ kv,
@@ -424,8 +373,8 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
         bf16x8 qf[NKS];
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
-            mq_u32x4 v = {0u, 0u, 0u, 0u};
-            if (qvalid) v = *reinterpret_cast<const mq_u32x4 *>(q + (int64_t)(r0 + qrow) * ld_q + hh * DH + ks * 16 + hf * 8);
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (qvalid) v = *reinterpret_cast<const u32x4 *>(q + (int64_t)(r0 + qrow) * ld_q + hh * DH + ks * 16 + hf * 8);
             qf[ks] = __builtin_bit_cast(bf16x8, v);
         }
         // K / V rows through buffer loads: one descriptor for the sequence's rows (reads past its end return zeros), 32-bit
@@ -434,12 +383,12 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
         const int koff = (r * ld_kv + hf * 8) * 2;                        // this lane's K row, its half of a k-step
         const int voff0 = ((lane / CH) * ld_kv + dm + (lane % CH) * 8) * 2;     // V chunk i: rows (lane + 64 i) / CH
         const int tile_bytes = 32 * ld_kv * 2;
-        mq_u32x4 kf[NKS], rv[VC];
-        auto fetch_k = [&](int kt, mq_u32x4 (&fk)[NKS]) {
+        u32x4 kf[NKS], rv[VC];
+        auto fetch_k = [&](int kt, u32x4 (&fk)[NKS]) {
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) fk[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, koff + kt * tile_bytes + ks * 32, 0, 0);
         };
-        auto fetch_v = [&](int kt, mq_u32x4 (&fv)[VC]) {
+        auto fetch_v = [&](int kt, u32x4 (&fv)[VC]) {
 #pragma unroll
             for (int i = 0; i < VC; ++i) fv[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff0 + kt * tile_bytes + i * (64 / CH) * ld_kv * 2, 0, 0);
         };
@@ -456,7 +405,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
 #pragma unroll
             for (int i = 0; i < VC; ++i) {
                 const int c = lane + 64 * i, row = c / CH, part = c % CH;
-                *reinterpret_cast<mq_u32x4 *>(vt + row * KSTR + part * 16) = rv[i];
+                *reinterpret_cast<u32x4 *>(vt + row * KSTR + part * 16) = rv[i];
             }
             f32x16 acc;
 #pragma unroll
@@ -473,7 +422,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
             if (HAS_PAD || edge) {
 #pragma unroll
                 for (int t = 0; t < 16; ++t) {
-                    const int key = kt * 32 + mq_rowmap(t, hf);
+                    const int key = kt * 32 + rowmap(t, hf);
                     float madd = 0.f;
                     if (key >= S) madd = -INFINITY;
                     else if (HAS_PAD && key_pad[tok0 + key]) madd = -1e9f * 1.4426950408889634f;
@@ -523,12 +472,12 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
                 float pv[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pv[j] = acc[8 * s2 + j];
-                const bf16x8 pf = mq_pack8(pv);
+                const bf16x8 pf = pack8(pv);
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) {
                     // V^T[dh = dt*32 + r][keys 16 s2 + 4 hf + {0..3, 8..11} of the tile] from the row-major V tile
                     const char *vb = vt + (16 * s2 + 4 * hf + (li >> 2)) * KSTR + (dt * 32 + 16 * (g & 1) + 4 * (li & 3)) * 2;
-                    const bf16x8 vf = mq_frag_tr(vb, 8 * KSTR);
+                    const bf16x8 vf = frag_tr(vb, 8 * KSTR);
                     oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[dt], 0, 0, 0);
                 }
             }
@@ -541,10 +490,10 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
             for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
                 for (int tq = 0; tq < 4; ++tq) {
-                    mq_bf16x4 w;
+                    bf16x4 w;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(oacc[dt][4 * tq + j] * inv);
-                    *reinterpret_cast<mq_bf16x4 *>(orow + dt * 32 + 8 * tq + 4 * hf) = w;
+                    *reinterpret_cast<bf16x4 *>(orow + dt * 32 + 8 * tq + 4 * hf) = w;
                 }
             if (hf == 0) lse[(int64_t)(r0 + qrow) * H + hh] = (m + __log2f(l)) * 0.6931471805599453f;
         }
@@ -552,40 +501,15 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// bf16 backward on the matrix cores, one wave per (sequence, head), key tiles of 32 (the maps of attn_mfma.hip's backward):
+// bf16 backward on the matrix cores, one wave per (sequence, head), key tiles of 32 (attn_mfma.hip's backward):
 //   S = Q K^T and dP = dO V^T with the KEY on the lane (Q / dO rows and the K tile from LDS, V rows straight from global),
 //   P = 2^(S scale log2e + mask - lse_q), dS = P (dP - delta_q); P and dS feed dV^T = dO^T P and dK^T = Q^T dS from the
 //   accumulator registers; dS crosses LDS once for dQ^T += K^T dS^T (query on the lane: dQ stays in registers over the key
 //   tiles).  dK / dV of a tile leave as 8-byte pieces of their rows.  More than 32 query rows: further passes that add to
 //   the dK / dV rows already written.
 // LDS per wave: sQ | sG [32][KSTR] (the query tile and its dO), sK [32][KSTR] (current key tile), sDS [32][TSTR], lse2 / delta;
-// DROP: the tile's 32 query positions behind them.
+// DROP: the tile's 32 query positions behind them (sPos): keep_tile_bwd (mfma.h) takes the query of tile row i at sPos[i].
 // ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bf16x8 mq_frag_2x8B(const char *p0, const char *p1) {
-    typedef __attribute__((ext_vector_type(2))) unsigned u32x2v;
-    const u32x2v lo = *reinterpret_cast<const u32x2v *>(p0);
-    const u32x2v hi = *reinterpret_cast<const u32x2v *>(p1);
-    const mq_u32x4 w = {lo[0], lo[1], hi[0], hi[1]};
-    return __builtin_bit_cast(bf16x8, w);
-}
-
-// Keep bits of one 32 x 32 score tile of the backward (key on the lane, query on the accumulator rows; bit t = register t): the quad
-// exchange of attn_mfma.hip's attn_keep_tile_bwd, with the query of tile row i at the position pos[i] (LDS) instead of q0 + i.
-// base = attn_ctr_base(item, S_arg), k_tile = first key of the tile.  EXEC must be full.
-__device__ __forceinline__ uint32_t mq_keep_tile_bwd(uint64_t seed, uint64_t base, int S_arg, const int32_t *pos, int k_tile, uint32_t thr, int r, int hf) {
-    const int c = r & 3;
-    const uint32_t s4q = b4c_attn_s4(S_arg) >> 2, kq = (uint32_t)(k_tile + (r & ~3)) >> 2;
-    uint32_t mk = 0;
-#pragma unroll
-    for (int tq = 0; tq < 4; ++tq)
-        mk |= b4c_attn_keep4(seed, base + ((uint32_t)pos[c + 8 * tq + 4 * hf] * s4q + kq), thr) << (4 * tq);
-    uint32_t km = ((quad_bcast<0>(mk) >> c) & 0x1111u);
-    km |= ((quad_bcast<1>(mk) >> c) & 0x1111u) << 1;
-    km |= ((quad_bcast<2>(mk) >> c) & 0x1111u) << 2;
-    km |= ((quad_bcast<3>(mk) >> c) & 0x1111u) << 3;
-    return km;
-}
-
 template <int DH, bool HAS_PAD, bool DROP>
 __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(const bf16_t *__restrict__ q, int ld_q, const bf16_t *__restrict__ kv,
                                                                          int ld_kv, const uint8_t *__restrict__ key_pad,
@@ -620,9 +544,9 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
     if (M <= 0) {                                             // no query reads this sequence's keys in this layer
         for (int c = lane; c < S * CH; c += 64) {
             const int row = c / CH, part = c % CH;
-            const mq_u32x4 z = {0u, 0u, 0u, 0u};
-            *reinterpret_cast<mq_u32x4 *>(dkbase + (int64_t)row * ld_dkv + part * 8) = z;
-            *reinterpret_cast<mq_u32x4 *>(dkbase + (int64_t)row * ld_dkv + dm + part * 8) = z;
+            const u32x4 z = {0u, 0u, 0u, 0u};
+            *reinterpret_cast<u32x4 *>(dkbase + (int64_t)row * ld_dkv + part * 8) = z;
+            *reinterpret_cast<u32x4 *>(dkbase + (int64_t)row * ld_dkv + dm + part * 8) = z;
         }
         return;
     }
@@ -642,14 +566,14 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
 #pragma unroll
             for (int i = 0; i < VC; ++i) {
                 const int c = lane + 64 * i, row = c / CH, part = c % CH;
-                mq_u32x4 vq = {0u, 0u, 0u, 0u}, vg = {0u, 0u, 0u, 0u}, vo = {0u, 0u, 0u, 0u};
+                u32x4 vq = {0u, 0u, 0u, 0u}, vg = {0u, 0u, 0u, 0u}, vo = {0u, 0u, 0u, 0u};
                 if (q0 + row < M) {
-                    vq = *reinterpret_cast<const mq_u32x4 *>(q + (int64_t)(r0 + q0 + row) * ld_q + hh * DH + part * 8);
-                    vg = *reinterpret_cast<const mq_u32x4 *>(d_o + (int64_t)(r0 + q0 + row) * ld_do + hh * DH + part * 8);
-                    vo = *reinterpret_cast<const mq_u32x4 *>(o + (int64_t)(r0 + q0 + row) * ld_o + hh * DH + part * 8);
+                    vq = *reinterpret_cast<const u32x4 *>(q + (int64_t)(r0 + q0 + row) * ld_q + hh * DH + part * 8);
+                    vg = *reinterpret_cast<const u32x4 *>(d_o + (int64_t)(r0 + q0 + row) * ld_do + hh * DH + part * 8);
+                    vo = *reinterpret_cast<const u32x4 *>(o + (int64_t)(r0 + q0 + row) * ld_o + hh * DH + part * 8);
                 }
-                *reinterpret_cast<mq_u32x4 *>(sQ + row * KSTR + part * 16) = vq;
-                *reinterpret_cast<mq_u32x4 *>(sG + row * KSTR + part * 16) = vg;
+                *reinterpret_cast<u32x4 *>(sQ + row * KSTR + part * 16) = vq;
+                *reinterpret_cast<u32x4 *>(sG + row * KSTR + part * 16) = vg;
                 const bf16x8 g8 = __builtin_bit_cast(bf16x8, vg), o8 = __builtin_bit_cast(bf16x8, vo);
                 pd = 0.f;
 #pragma unroll
@@ -681,7 +605,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
         for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int t = 0; t < 16; ++t) dqa[dt][t] = 0.f;
-        mq_u32x4 rk[VC], vb[NKS];
+        u32x4 rk[VC], vb[NKS];
         auto fetch = [&](int kt) {
 #pragma unroll
             for (int i = 0; i < VC; ++i) rk[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, koff0 + kt * tile_bytes + i * (64 / CH) * ld_kv * 2, 0, 0);
@@ -694,7 +618,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
 #pragma unroll
             for (int i = 0; i < VC; ++i) {
                 const int c = lane + 64 * i, row = c / CH, part = c % CH;
-                *reinterpret_cast<mq_u32x4 *>(sK + row * KSTR + part * 16) = rk[i];
+                *reinterpret_cast<u32x4 *>(sK + row * KSTR + part * 16) = rk[i];
             }
             bf16x8 vcur[NKS];
 #pragma unroll
@@ -715,7 +639,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
             }
             float pv[16], dsv[16];
             // dropout: dV takes the dropped, rescaled P~; dS = P o (keep / (1 - rate) * dP~ - delta) with the undropped P
-            const uint32_t km = DROP ? mq_keep_tile_bwd(seed, attn_ctr_base(item, S_arg), S_arg, sPos, kt * 32, thr, r, hf) : 0u;
+            const uint32_t km = DROP ? keep_tile_bwd(seed, attn_ctr_base(item, S_arg), S_arg, [sPos](int i) { return sPos[i]; }, kt * 32, thr, r, hf) : 0u;
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[t], scale2, madd - lq[t]));
@@ -727,7 +651,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
                     pv[t] = p;
                     dsv[t] = p * (pa[t] - dl[t]);
                 }
-                *reinterpret_cast<bf16_t *>(sDS + mq_rowmap(t, hf) * TSTR + r * 2) = (bf16_t)dsv[t];
+                *reinterpret_cast<bf16_t *>(sDS + rowmap(t, hf) * TSTR + r * 2) = (bf16_t)dsv[t];
             }
             // dV^T = dO^T P, dK^T = Q^T dS (key on the lane), from the accumulator registers
             f32x16 dv[NDT], dk[NDT];
@@ -737,14 +661,14 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
                 for (int t = 0; t < 16; ++t) { dv[dt][t] = 0.f; dk[dt][t] = 0.f; }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 pf = mq_pack8(pv + 8 * s2);
-                const bf16x8 df = mq_pack8(dsv + 8 * s2);
+                const bf16x8 pf = pack8(pv + 8 * s2);
+                const bf16x8 df = pack8(dsv + 8 * s2);
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) {
                     const int off = (16 * s2 + 4 * hf + (li >> 2)) * KSTR + (dt * 32 + 16 * (g & 1) + 4 * (li & 3)) * 2;
-                    const bf16x8 fgt = mq_frag_tr(sG + off, 8 * KSTR);
+                    const bf16x8 fgt = frag_tr(sG + off, 8 * KSTR);
                     dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fgt, pf, dv[dt], 0, 0, 0);
-                    const bf16x8 fqt = mq_frag_tr(sQ + off, 8 * KSTR);
+                    const bf16x8 fqt = frag_tr(sQ + off, 8 * KSTR);
                     dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fqt, df, dk[dt], 0, 0, 0);
                 }
             }
@@ -753,11 +677,11 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
             // dQ^T += K^T dS^T (query on the lane)
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 fs = mq_frag_2x8B(sDS + r * TSTR + (16 * s2 + 4 * hf) * 2, sDS + r * TSTR + (16 * s2 + 8 + 4 * hf) * 2);
+                const bf16x8 fs = frag_from_2x8B(sDS + r * TSTR + (16 * s2 + 4 * hf) * 2, sDS + r * TSTR + (16 * s2 + 8 + 4 * hf) * 2);
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) {
                     const int off = (16 * s2 + 4 * hf + (li >> 2)) * KSTR + (dt * 32 + 16 * (g & 1) + 4 * (li & 3)) * 2;
-                    const bf16x8 fkt = mq_frag_tr(sK + off, 8 * KSTR);
+                    const bf16x8 fkt = frag_tr(sK + off, 8 * KSTR);
                     dqa[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fkt, fs, dqa[dt], 0, 0, 0);
                 }
             }
@@ -768,11 +692,11 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
                 for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
                     for (int tq = 0; tq < 4; ++tq) {
-                        mq_bf16x4 wk, wv;
+                        bf16x4 wk, wv;
                         bf16_t *pk = krow + dt * 32 + 8 * tq + 4 * hf;
                         float ak[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
                         if (q0 > 0) {
-                            const mq_bf16x4 ek = *reinterpret_cast<const mq_bf16x4 *>(pk), ev = *reinterpret_cast<const mq_bf16x4 *>(pk + dm);
+                            const bf16x4 ek = *reinterpret_cast<const bf16x4 *>(pk), ev = *reinterpret_cast<const bf16x4 *>(pk + dm);
 #pragma unroll
                             for (int j = 0; j < 4; ++j) { ak[j] = (float)ek[j]; av[j] = (float)ev[j]; }
                         }
@@ -781,8 +705,8 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
                             wk[j] = (bf16_t)(dk[dt][4 * tq + j] * scale + ak[j]);
                             wv[j] = (bf16_t)(dv[dt][4 * tq + j] + av[j]);
                         }
-                        *reinterpret_cast<mq_bf16x4 *>(pk) = wk;
-                        *reinterpret_cast<mq_bf16x4 *>(pk + dm) = wv;
+                        *reinterpret_cast<bf16x4 *>(pk) = wk;
+                        *reinterpret_cast<bf16x4 *>(pk + dm) = wv;
                     }
             }
             __builtin_amdgcn_wave_barrier();                  // (sK / sDS are rewritten by the next tile: LDS is in order per wave)
@@ -793,10 +717,10 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
             for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
                 for (int tq = 0; tq < 4; ++tq) {
-                    mq_bf16x4 w;
+                    bf16x4 w;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(dqa[dt][4 * tq + j] * scale);
-                    *reinterpret_cast<mq_bf16x4 *>(qo + dt * 32 + 8 * tq + 4 * hf) = w;
+                    *reinterpret_cast<bf16x4 *>(qo + dt * 32 + 8 * tq + 4 * hf) = w;
                 }
         }
     }
@@ -805,10 +729,6 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
 static size_t mq_fwd_lds(int SP, int dh, int esz) { return (size_t)MQ * dh * 4 + (size_t)MQ * SP * 4 + (size_t)MQ_KB * dh * esz; }
 static size_t mq_bwd_lds(int dh, int esz, bool drop) {
     return (size_t)2 * MQ * dh * 4 + 2 * MQ * 4 + (size_t)MQ * MQ_KB * 4 + (size_t)MQ_KB * dh * esz + (drop ? MQ * 4 : 0);
-}
-
-template <typename Kern> static void mq_allow_lds(Kern k, size_t bytes) {
-    (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 static int mq_check(const char *who, const void *q, const void *kv, const int32_t *cu, const int32_t *moff, int ld_q, int ld_kv, int B,
@@ -861,7 +781,7 @@ static int mq_fwd_any(const char *who, const void *q, int ld_q, const void *kv, 
     B4C_REQUIRE(shm <= 160 * 1024, "%s: max_len %d needs %zu bytes of LDS", who, max_len, shm);
 #define MQ_FWD(TT, DHH, DR)                                                                                                          \
     do {                                                                                                                             \
-        mq_allow_lds(attn_mq_fwd_kernel<TT, DHH, DR>, shm);                                                                          \
+        b4c_allow_lds(attn_mq_fwd_kernel<TT, DHH, DR>, shm);                                                                         \
         attn_mq_fwd_kernel<TT, DHH, DR><<<B * H, MQ_THREADS, shm, st>>>((const TT *)q, ld_q, (const TT *)kv, ld_kv, key_pad, cu_seqlens, q_offsets, \
                                                                  (TT *)o, ld_o, lse, H, SP, sq, q_rows, max_len, rate, seed);        \
     } while (0)
@@ -903,7 +823,7 @@ static int mq_bwd_any(const char *who, const void *q, int ld_q, const void *kv, 
 #define MQ_MFMA_B(DHH, PP, DR)                                                                                                       \
     do {                                                                                                                             \
         const size_t shm_m = (size_t)MQ_WAVES * (3 * 32 * kstr + 32 * (32 * 2 + 16) + (DR ? 3 : 2) * 32 * 4);                        \
-        mq_allow_lds(attn_mq_bwd_mfma_kernel<DHH, PP, DR>, shm_m);                                                                   \
+        b4c_allow_lds(attn_mq_bwd_mfma_kernel<DHH, PP, DR>, shm_m);                                                                  \
         attn_mq_bwd_mfma_kernel<DHH, PP, DR><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens, \
             q_offsets, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dq, ld_dq, (bf16_t *)dkv, ld_dkv, H, n_items, 1.0f / sq, \
             q_rows, max_len, rate, seed);                                                                                            \
@@ -916,7 +836,7 @@ static int mq_bwd_any(const char *who, const void *q, int ld_q, const void *kv, 
 #define MQ_BWD(TT, DHH, DR)                                                                                                          \
     do {                                                                                                                             \
         const size_t shm = mq_bwd_lds(dh, sizeof(float), DR);                                                                        \
-        mq_allow_lds(attn_mq_bwd_kernel<TT, DHH, DR>, shm);                                                                          \
+        b4c_allow_lds(attn_mq_bwd_kernel<TT, DHH, DR>, shm);                                                                         \
         attn_mq_bwd_kernel<TT, DHH, DR><<<B * H, MQ_THREADS, shm, st>>>((const TT *)q, ld_q, (const TT *)kv, ld_kv, key_pad, cu_seqlens, q_offsets, \
                                                                  (const TT *)o, ld_o, (const TT *)d_o, ld_do, lse, (TT *)dq, ld_dq,  \
                                                                  (TT *)dkv, ld_dkv, H, sq, q_rows, max_len, rate, seed);             \

@@ -73,15 +73,15 @@ __global__ void __launch_bounds__(512, 1) ao_bwd_kernel(AoBwdArgs a) {
 
     int toffA[2][2], toffB[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) { toffA[i][0] = dd_tr_off(hf, li, g, 2 * wm + i, 0); toffA[i][1] = dd_tr_off(hf, li, g, 2 * wm + i, 1); }
-    toffB[0] = dd_tr_off(hf, li, g, wn, 0);
-    toffB[1] = dd_tr_off(hf, li, g, wn, 1);
+    for (int i = 0; i < 2; ++i) { toffA[i][0] = VTile<128>::tr_off(hf, li, g, 2 * wm + i, 0); toffA[i][1] = VTile<128>::tr_off(hf, li, g, 2 * wm + i, 1); }
+    toffB[0] = VTile<128>::tr_off(hf, li, g, wn, 0);
+    toffB[1] = VTile<128>::tr_off(hf, li, g, wn, 1);
     int xoff[2][4];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) xoff[mi][q] = dd_chunk_off(16 * mi + li, 4 * q + g);
-    const int rowoff = dd_chunk_off(orow, opart);       // the row phase's 16-B chunk inside an image
+        for (int q = 0; q < 4; ++q) xoff[mi][q] = VTile<128>::chunk_off(16 * mi + li, 4 * q + g);
+    const int rowoff = VTile<128>::chunk_off(orow, opart);       // the row phase's 16-B chunk inside an image
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
     auto fetch = [&](int64_t t, int slot) {
@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(512, 1) ao_bwd_kernel(AoBwdArgs a) {
         const int64_t M = t < t1 ? a.M : 0;             // past the last tile: zero rows (still LDS writes, still counted)
         dd_dma(a.O, a.ldo_in, 0, tok0, M, lds0 + (unsigned)(slot * STAGE), wave, lane);
     };
-    dd_u32x4 ds_do, ds_z, ds_st;                        // descriptors of dOut, z (M x 256 B) and stats (M x 8 B): whole tensors
+    u32x4 ds_do, ds_z, ds_st;                        // descriptors of dOut, z (M x 256 B) and stats (M x 8 B): whole tensors
     {
         const uint64_t bd = (uint64_t)a.dOut, bz = (uint64_t)a.Z, bs = (uint64_t)a.stats;
         ds_do[0] = __builtin_amdgcn_readfirstlane((unsigned)bd); ds_do[1] = __builtin_amdgcn_readfirstlane((unsigned)(bd >> 32) & 0xFFFFu);
@@ -197,8 +197,8 @@ __global__ void __launch_bounds__(512, 1) ao_bwd_kernel(AoBwdArgs a) {
             const char *bx = so + kk * 16 * 256, *bg = sDY + kk * 16 * 256;
             bf16x8 fa[2];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = dd_frag_tr(bx + toffA[i][0], bx + toffA[i][1]);
-            const bf16x8 fb = dd_frag_tr(bg + toffB[0], bg + toffB[1]);
+            for (int i = 0; i < 2; ++i) fa[i] = frag_tr2(bx + toffA[i][0], bx + toffA[i][1]);
+            const bf16x8 fb = frag_tr2(bg + toffB[0], bg + toffB[1]);
             if (wm == 0) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) bsum += (float)fb[e];
@@ -311,8 +311,7 @@ extern "C" int b4c_attn_out_bwd(const void *dout, const void *z, const float *st
     AoBwdOut out = {dW, db, dgamma, dbeta, ld_dw};
     const int grid = ao_bwd_grid(M);
     const size_t lds = DD_RING * (size_t)DD_SUB + DD_SUB + DD_TOK * AO_OSTR + 3 * 8192;
-    static thread_local bool done = false;
-    if (!done) { (void)hipFuncSetAttribute((const void *)ao_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
+    b4c_allow_lds(ao_bwd_kernel, lds);
     hipStream_t st = (hipStream_t)stream;
     ao_bwd_kernel<<<grid, 512, lds, st>>>(a);
     ao_bwd_reduce_kernel<<<(AO_ROWS * 128 + 31) / 32, 256, 0, st>>>(a.part, grid, out);

@@ -10,6 +10,11 @@ typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 #define B4C_WAVE 64
 
@@ -31,6 +36,21 @@ int b4c_check_launch(const char *what);
     } while (0)
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Opt `kernel` in to `bytes` of dynamic LDS (more than the 64 KiB a launch may ask for unasked).  Per host thread the runtime is
+// called when the kernel is new or asks for more than it was last given.  One table per kernel signature and file; the most that
+// share one are vocab_ce.hip's 12 token sweeps over VceArgs.  A kernel that finds the table full is not remembered: it asks every time.
+template <typename K> static void b4c_allow_lds(K kernel, size_t bytes) {
+    constexpr int CAP = 32;
+    static thread_local const void *done[CAP];
+    static thread_local size_t done_bytes[CAP];
+    static thread_local int ndone = 0;
+    int i = 0;
+    while (i < ndone && done[i] != (const void *)kernel) ++i;
+    if (i < ndone && done_bytes[i] >= bytes) return;
+    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (i < CAP) { done[i] = (const void *)kernel; done_bytes[i] = bytes; if (i == ndone) ++ndone; }
+}
 
 // ---- element IO: 8 consecutive elements <-> 8 floats (16 B for bf16, 32 B for fp32) ----
 // Which streaming outputs use nontemporal stores (bit per site): measured per site on the C2 step.
@@ -91,6 +111,41 @@ template <> struct Vec8<bf16_t> {
         if (NT) store_nt(p, v); else store(p, v);
     }
 };
+
+// one row (or part of one) of N elements <-> N floats, and its dot product with an fp32 row in LDS (the lanes that share `row`
+// read one address: broadcast)
+template <typename T, int N>
+__device__ __forceinline__ void load_row(const T *__restrict__ p, float (&v)[N]) {
+#pragma unroll
+    for (int c = 0; c < N; c += 8) {
+        float t[8];
+        Vec8<T>::load(p + c, t);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[c + k] = t[k];
+    }
+}
+template <typename T, int N>
+__device__ __forceinline__ void store_row(T *__restrict__ p, const float (&v)[N]) {
+#pragma unroll
+    for (int c = 0; c < N; c += 8) {
+        float t[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t[k] = v[c + k];
+        Vec8<T>::store(p + c, t);
+    }
+}
+template <int N> __device__ __forceinline__ float dot_lds(const float (&a)[N], const float *__restrict__ row) {
+    float s = 0.f;
+#pragma unroll
+    for (int d = 0; d < N; d += 4) {
+        const f32x4 kv = *reinterpret_cast<const f32x4 *>(row + d);
+        s += a[d] * kv[0];
+        s += a[d + 1] * kv[1];
+        s += a[d + 2] * kv[2];
+        s += a[d + 3] * kv[3];
+    }
+    return s;
+}
 
 // ---- counter-based dropout mask ----
 // Threefry-2x32 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11), 12 rounds,

@@ -80,7 +80,7 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
     // resident operands of the two dX-type products: this wave's 16 output columns, B[k = 32 ks + 8 g + j][col = 16 wave + li]
     bf16x8 w2f[4], w1f[4];
     {
-        const bf16x8 zero = __builtin_bit_cast(bf16x8, (dd_u32x4){0u, 0u, 0u, 0u});
+        const bf16x8 zero = __builtin_bit_cast(bf16x8, (u32x4){0u, 0u, 0u, 0u});
         const int col = 16 * wave + li;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -102,19 +102,19 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
 
     int toffA[2][2], toffB[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) { toffA[i][0] = dd_tr_off(hf, li, g, 2 * wm + i, 0); toffA[i][1] = dd_tr_off(hf, li, g, 2 * wm + i, 1); }
-    toffB[0] = dd_tr_off(hf, li, g, wn, 0);
-    toffB[1] = dd_tr_off(hf, li, g, wn, 1);
+    for (int i = 0; i < 2; ++i) { toffA[i][0] = VTile<128>::tr_off(hf, li, g, 2 * wm + i, 0); toffA[i][1] = VTile<128>::tr_off(hf, li, g, 2 * wm + i, 1); }
+    toffB[0] = VTile<128>::tr_off(hf, li, g, wn, 0);
+    toffB[1] = VTile<128>::tr_off(hf, li, g, wn, 1);
     int xoff[2][4];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) xoff[mi][q] = dd_chunk_off(16 * mi + li, 4 * q + g);
+        for (int q = 0; q < 4; ++q) xoff[mi][q] = VTile<128>::chunk_off(16 * mi + li, 4 * q + g);
     // the lane's 4 consecutive columns 16 wave + 4 g .. + 3 of token 16 mi + li inside an image (8-B piece of a 16-B chunk)
     int poff[2];
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi) poff[mi] = dd_chunk_off(16 * mi + li, (16 * wave + 4 * g) >> 3) + ((4 * g) & 7) * 2;
-    const int rowoff = dd_chunk_off(orow, opart);       // the row phases' 16-B chunk inside an image
+    for (int mi = 0; mi < 2; ++mi) poff[mi] = VTile<128>::chunk_off(16 * mi + li, (16 * wave + 4 * g) >> 3) + ((4 * g) & 7) * 2;
+    const int rowoff = VTile<128>::chunk_off(orow, opart);       // the row phases' 16-B chunk inside an image
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
     auto fetch = [&](int64_t t, int slot) {
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
     // (stale mean / rstd whenever the load had not landed: single rows of lanes 48-63, or whole tiles of every workgroup at once
     // when a page-table miss delayed them all; ~1 launch in 2 at 456 k rows, none below 100 k), and naming the registers on the
     // wait made it copy all of them in front of it.  Nothing can copy LDS.
-    dd_u32x4 ds_do, ds_z, ds_st;                        // descriptors of dOut, z (M x 256 B) and stats (M x 8 B): whole tensors
+    u32x4 ds_do, ds_z, ds_st;                        // descriptors of dOut, z (M x 256 B) and stats (M x 8 B): whole tensors
     {
         const uint64_t bd = (uint64_t)a.dOut, bz = (uint64_t)a.Z, bs = (uint64_t)a.stats;
         ds_do[0] = __builtin_amdgcn_readfirstlane((unsigned)bd); ds_do[1] = __builtin_amdgcn_readfirstlane((unsigned)(bd >> 32) & 0xFFFFu);
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
 
     const float inv_keep = a.rate > 0.f ? 1.0f / (1.0f - a.rate) : 1.0f;
     const uint32_t thr = b4c_keep_threshold(a.rate);
-    dd_u32x4 dz0 = {0u, 0u, 0u, 0u}, dz1 = {0u, 0u, 0u, 0u};        // dz of the even / odd tiles, bf16, until their dx rows leave
+    u32x4 dz0 = {0u, 0u, 0u, 0u}, dz1 = {0u, 0u, 0u, 0u};        // dz of the even / odd tiles, bf16, until their dx rows leave
 
     // ---- phase 3 of a tile: dW1 += x^T dh, dx = dh W1^T -> staged (x from ring stage `slot`, dh from its image) ----
     auto phase3 = [&](int slot) {
@@ -190,8 +190,8 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
             const char *bx = sx + kk * 16 * 256, *bg = sDH + kk * 16 * 256;
             bf16x8 fa[2];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = dd_frag_tr(bx + toffA[i][0], bx + toffA[i][1]);
-            const bf16x8 fb = dd_frag_tr(bg + toffB[0], bg + toffB[1]);
+            for (int i = 0; i < 2; ++i) fa[i] = frag_tr2(bx + toffA[i][0], bx + toffA[i][1]);
+            const bf16x8 fb = frag_tr2(bg + toffB[0], bg + toffB[1]);
             if (wm == 0) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) bsum1 += (float)fb[e];
@@ -215,7 +215,7 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
         for (int mi = 0; mi < 2; ++mi) *reinterpret_cast<f32x4 *>(sOut + (16 * mi + li) * FB_OSTR + (16 * wave + 4 * g) * 4) = ax[mi];
     };
     // ---- rows of tile tp: staged dx + dz -> global ----
-    auto store_rows = [&](int64_t tp, dd_u32x4 dzp) {
+    auto store_rows = [&](int64_t tp, u32x4 dzp) {
         const int64_t tk = (gfirst + tp * gstep) * DD_TOK + orow;
         if (tk < a.M) {
             const f32x4 lo = *reinterpret_cast<const f32x4 *>(sOut + orow * FB_OSTR + opart * 32);
@@ -238,8 +238,8 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
         constexpr bool odd_tile = decltype(ODD)::value;  // (dz of a tile waits in one of two register quadruples: the parity is compile time)
         const int slot = (int)(t & 3);
         const bool body = t < t1;
-        dd_u32x4 &dz_cur = odd_tile ? dz1 : dz0;
-        dd_u32x4 &dz_prev = odd_tile ? dz0 : dz1;
+        u32x4 &dz_cur = odd_tile ? dz1 : dz0;
+        u32x4 &dz_prev = odd_tile ? dz0 : dz1;
         if (body) {
             // (tests/test_vmcnt_accounting.py checks both counts in the assembly: ffn_bwd.second, ffn_bwd.steady)
             if (t == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -279,7 +279,7 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
             } else {
                 dyv = dzv;
             }
-            dz_cur = __builtin_bit_cast(dd_u32x4, dzv);
+            dz_cur = __builtin_bit_cast(u32x4, dzv);
             *reinterpret_cast<bf16x8 *>(sDY + rowoff) = dyv;
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -291,22 +291,22 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
             // is the h | x image of tile t what global memory holds?  (every request of tile t was waited for above, by every wave)
             const int64_t tk = (gfirst + t * gstep) * DD_TOK + orow;
             if (tk < a.M && opart * 8 < a.Fp) {
-                const dd_u32x4 l = *reinterpret_cast<const dd_u32x4 *>(smem + slot * STAGE + rowoff);
-                const dd_u32x4 gq = *reinterpret_cast<const dd_u32x4 *>(a.H + tk * a.ldh + opart * 8);
+                const u32x4 l = *reinterpret_cast<const u32x4 *>(smem + slot * STAGE + rowoff);
+                const u32x4 gq = *reinterpret_cast<const u32x4 *>(a.H + tk * a.ldh + opart * 8);
                 const bool ne = l[0] != gq[0] || l[1] != gq[1] || l[2] != gq[2] || l[3] != gq[3];
                 if (ne) {
                     atomicAdd(&g_fb_dbg[(slot * 32 + orow) * 4 + 0], 1u);
                     if (t >= 4) {
                         const int64_t tk4 = (gfirst + (t - 4) * gstep) * DD_TOK + orow;
-                        const dd_u32x4 g4 = *reinterpret_cast<const dd_u32x4 *>(a.H + tk4 * a.ldh + opart * 8);
+                        const u32x4 g4 = *reinterpret_cast<const u32x4 *>(a.H + tk4 * a.ldh + opart * 8);
                         if (l[0] == g4[0] && l[1] == g4[1] && l[2] == g4[2] && l[3] == g4[3]) atomicAdd(&g_fb_dbg[(slot * 32 + orow) * 4 + 1], 1u);
                     }
                 }
                 if (opart == 0) atomicAdd(&g_fb_dbg[(slot * 32 + orow) * 4 + 3], 1u);
             }
             if (tk < a.M) {
-                const dd_u32x4 l = *reinterpret_cast<const dd_u32x4 *>(smem + slot * STAGE + DD_SUB + rowoff);
-                const dd_u32x4 gq = *reinterpret_cast<const dd_u32x4 *>(a.X + tk * a.ldx + opart * 8);
+                const u32x4 l = *reinterpret_cast<const u32x4 *>(smem + slot * STAGE + DD_SUB + rowoff);
+                const u32x4 gq = *reinterpret_cast<const u32x4 *>(a.X + tk * a.ldx + opart * 8);
                 if (l[0] != gq[0] || l[1] != gq[1] || l[2] != gq[2] || l[3] != gq[3]) atomicAdd(&g_fb_dbg[(slot * 32 + orow) * 4 + 2], 1u);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -322,8 +322,8 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
             const char *bx = sh + kk * 16 * 256, *bg = sDY + kk * 16 * 256;
             bf16x8 fa[2];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = dd_frag_tr(bx + toffA[i][0], bx + toffA[i][1]);
-            const bf16x8 fb = dd_frag_tr(bg + toffB[0], bg + toffB[1]);
+            for (int i = 0; i < 2; ++i) fa[i] = frag_tr2(bx + toffA[i][0], bx + toffA[i][1]);
+            const bf16x8 fb = frag_tr2(bg + toffB[0], bg + toffB[1]);
             if (wm == 0) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) bsum2 += (float)fb[e];
@@ -337,9 +337,9 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) fg[mi][q] = *reinterpret_cast<const bf16x8 *>(sDY + xoff[mi][q]);
-        dd_bf16x4 hv[2];
+        bf16x4 hv[2];
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi) hv[mi] = *reinterpret_cast<const dd_bf16x4 *>(sh + poff[mi]);
+        for (int mi = 0; mi < 2; ++mi) hv[mi] = *reinterpret_cast<const bf16x4 *>(sh + poff[mi]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -347,10 +347,10 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
             for (int mi = 0; mi < 2; ++mi) ax[mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f[q], fg[mi][q], ax[mi], 0, 0, 0);
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
-            dd_bf16x4 w;
+            bf16x4 w;
 #pragma unroll
             for (int j = 0; j < 4; ++j) w[j] = (float)hv[mi][j] > 0.f ? (bf16_t)ax[mi][j] : (bf16_t)0.f;
-            *reinterpret_cast<dd_bf16x4 *>(sDH + poff[mi]) = w;
+            *reinterpret_cast<bf16x4 *>(sDH + poff[mi]) = w;
         }
         __syncthreads();
     };
@@ -467,8 +467,7 @@ extern "C" int b4c_ffn_bwd(const void *dout, const void *z, const float *stats, 
     FfnBwdOut out = {dW2, dW1, db2, db1, dgamma, dbeta, ld_dw2, ld_dw1, F};
     const int grid = ffn_bwd_grid(M);
     const size_t lds = DD_RING * (size_t)2 * DD_SUB + 2 * DD_SUB + DD_TOK * FB_OSTR + 3 * 8192;
-    static thread_local bool done = false;
-    if (!done) { (void)hipFuncSetAttribute((const void *)ffn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
+    b4c_allow_lds(ffn_bwd_kernel, lds);
     hipStream_t st = (hipStream_t)stream;
     ffn_bwd_kernel<<<grid, 512, lds, st>>>(a);
     ffn_bwd_reduce_kernel<<<FB_ROWS * 128 / 32, 256, 0, st>>>(a.part, grid, out);

@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(512, 4) ffn_fwd_kernel(FfnFwdArgs a) {
     bf16x8 w1f[4], w2f[4];
     float bias1[4];
     {
-        const bf16x8 zero = __builtin_bit_cast(bf16x8, (dd_u32x4){0u, 0u, 0u, 0u});
+        const bf16x8 zero = __builtin_bit_cast(bf16x8, (u32x4){0u, 0u, 0u, 0u});
         const int col = 16 * wave + li;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -76,11 +76,11 @@ __global__ void __launch_bounds__(512, 4) ffn_fwd_kernel(FfnFwdArgs a) {
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) xoff[mi][q] = dd_chunk_off(16 * mi + li, 4 * q + g);
+        for (int q = 0; q < 4; ++q) xoff[mi][q] = VTile<128>::chunk_off(16 * mi + li, 4 * q + g);
         // the lane's 4 consecutive columns 16 wave + 4 g .. + 3 of token 16 mi + li inside an image (8-B piece of a 16-B chunk)
-        poff[mi] = dd_chunk_off(16 * mi + li, (16 * wave + 4 * g) >> 3) + ((4 * g) & 7) * 2;
+        poff[mi] = VTile<128>::chunk_off(16 * mi + li, (16 * wave + 4 * g) >> 3) + ((4 * g) & 7) * 2;
     }
-    const int rowoff = dd_chunk_off(orow, opart);
+    const int rowoff = VTile<128>::chunk_off(orow, opart);
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
     auto fetch = [&](int64_t t) {
@@ -155,10 +155,10 @@ __global__ void __launch_bounds__(512, 4) ffn_fwd_kernel(FfnFwdArgs a) {
                 for (int mi = 0; mi < 2; ++mi) ax[mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f[q], fg[mi][q], ax[mi], 0, 0, 0);
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) {
-                dd_bf16x4 w;
+                bf16x4 w;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) w[j] = (bf16_t)fmaxf(ax[mi][j] + bias1[j], 0.f);
-                *reinterpret_cast<dd_bf16x4 *>(sH + poff[mi]) = w;
+                *reinterpret_cast<bf16x4 *>(sH + poff[mi]) = w;
             }
         }
         if (t > 0) row_phase(t - 1);
@@ -183,8 +183,8 @@ __global__ void __launch_bounds__(512, 4) ffn_fwd_kernel(FfnFwdArgs a) {
             // h rows of tile t -> global (16-B chunks of the image)
             const int64_t tk = (gfirst + t * gstep) * DD_TOK + orow;
             if (tk < a.M && opart * 8 < a.Fp) {
-                const dd_u32x4 hv = *reinterpret_cast<const dd_u32x4 *>(sH + rowoff);
-                *reinterpret_cast<dd_u32x4 *>(a.H + tk * a.ldh + opart * 8) = hv;
+                const u32x4 hv = *reinterpret_cast<const u32x4 *>(sH + rowoff);
+                *reinterpret_cast<u32x4 *>(a.H + tk * a.ldh + opart * 8) = hv;
             }
         }
     }
@@ -210,8 +210,7 @@ extern "C" int b4c_ffn_fwd(const void *X, int ldx, const void *W1t, int ldw1, co
     const int64_t ntiles = (M + DD_TOK - 1) / DD_TOK;
     const int grid = (int)(ntiles < 512 ? ntiles : 512);        // two workgroups per CU (57 KB of LDS, <= 128 registers each)
     const size_t lds = DD_RING * (size_t)DD_SUB + DD_SUB + DD_TOK * FF_OSTR + 3 * 128 * 4;
-    static thread_local bool done = false;
-    if (!done) { (void)hipFuncSetAttribute((const void *)ffn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
+    b4c_allow_lds(ffn_fwd_kernel, lds);
     ffn_fwd_kernel<<<grid, 512, lds, (hipStream_t)stream>>>(a);
     return b4c_check_launch("ffn_fwd");
 }

@@ -13,20 +13,7 @@
 // reduction axis (tokens) is contiguous for the fragment reads.
 #include <stdlib.h>
 
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-// > 64 KiB of dynamic LDS needs an explicit opt-in per kernel (once per process).
-template <typename K> static void allow_lds(K kernel, size_t bytes) {
-    static thread_local const void *done[16];
-    static thread_local int ndone = 0;
-    for (int i = 0; i < ndone; ++i)
-        if (done[i] == (const void *)kernel) return;
-    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (ndone < 16) done[ndone++] = (const void *)kernel;
-}
+#include "mfma.h"
 
 // Branch-free guarded loads: a raw buffer descriptor over the tile's rows makes out-of-range rows read as 0,
 // and an out-of-range K chunk is steered out of range by its offset.  (A per-chunk `if` inside the unrolled
@@ -809,7 +796,7 @@ extern "C" int b4c_gemm_nt_softmax(const void *A, int lda, const void *Bt, int l
     const int tpc = (int)ceil_div64(ntn, chunks);
     chunks = (int)ceil_div64(ntn, tpc);
     const size_t shm = WIDE_TILE_BYTES + WOUT_BYTES + 128 * sizeof(float);
-    allow_lds(gemm_nt_wide2_kernel<true>, shm);
+    b4c_allow_lds(gemm_nt_wide2_kernel<true>, shm);
     gemm_nt_wide2_kernel<true><<<mt * chunks, 256, shm, (hipStream_t)stream>>>((const bf16_t *)A, lda, (const bf16_t *)Bt, ldb, (bf16_t *)C, ldc,
                                                                            M, N, K, bias, mt, tpc, lse2);
     return b4c_check_launch("gemm_nt_softmax");
@@ -849,7 +836,7 @@ extern "C" int b4c_gemm_nt_act(const void *A, int lda, const void *Bt, int ldb, 
         const int tpc = (int)ceil_div64(ntn, chunks);
         chunks = (int)ceil_div64(ntn, tpc);
         const size_t shm = WIDE_TILE_BYTES + WOUT_BYTES + 128 * sizeof(float);
-        allow_lds(gemm_nt_wide2_kernel<false>, shm);
+        b4c_allow_lds(gemm_nt_wide2_kernel<false>, shm);
         gemm_nt_wide2_kernel<false><<<mt * chunks, 256, shm, st_w>>>((const bf16_t *)A, lda, (const bf16_t *)Bt, ldb, (bf16_t *)C, ldc, M, N, K, bias, mt, tpc, nullptr);
         return b4c_check_launch("gemm_nt_wide2");
     }
@@ -1182,14 +1169,7 @@ __global__ void __launch_bounds__(256) gemm_tn_kernel(const T *__restrict__ A, i
 #define TN_STR 320                      // bytes per token row in LDS (256 + 64)
 #define TN_TILE_BYTES (64 * TN_STR)     // one operand, one stage
 
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-__device__ __forceinline__ bf16x8 tn_frag(const char *p) {   // tokens +0..3 and +4..7 of the lane's feature
-    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3))) *)(p));
-    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3))) *)(p + 4 * TN_STR));
-    typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-    const s16x8_t w = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, w);
-}
+__device__ __forceinline__ bf16x8 tn_frag(const char *p) { return frag_tr(p, 4 * TN_STR); }   // tokens +0..3 and +4..7 of the lane's feature
 __device__ __forceinline__ void tn_load16(const bf16_t *__restrict__ P, int ld, int f0, int64_t tok0, int64_t tok_end, int tid, u32x4 (&reg)[4]) {
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc(P + tok0 * ld, tok_end - tok0, 64, (int64_t)ld * 2);
 #pragma unroll

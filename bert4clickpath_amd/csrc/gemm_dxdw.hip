@@ -21,8 +21,6 @@
 
 #include <type_traits>
 
-#include "common.h"
-
 #include "dxdw_common.h"
 
 #ifdef DD_STAMPS
@@ -90,12 +88,12 @@ __global__ void __launch_bounds__(512, 1) gemm_dxdw_kernel(DxDwArgs a) {
     // would live in scratch memory)
     int toffA[2][2], toffB[NT][2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) { toffA[i][0] = dd_tr_off(hf, li, g, 2 * wm + i, 0); toffA[i][1] = dd_tr_off(hf, li, g, 2 * wm + i, 1); }
+    for (int i = 0; i < 2; ++i) { toffA[i][0] = VTile<128>::tr_off(hf, li, g, 2 * wm + i, 0); toffA[i][1] = VTile<128>::tr_off(hf, li, g, 2 * wm + i, 1); }
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int nt = NT * wn + j;                     // 32-column tile of the gradient: sub-tile nt >> 2, dt = nt & 3
-        toffB[j][0] = (nt >> 2) * DD_SUB + dd_tr_off(hf, li, g, nt & 3, 0);
-        toffB[j][1] = (nt >> 2) * DD_SUB + dd_tr_off(hf, li, g, nt & 3, 1);
+        toffB[j][0] = (nt >> 2) * DD_SUB + VTile<128>::tr_off(hf, li, g, nt & 3, 0);
+        toffB[j][1] = (nt >> 2) * DD_SUB + VTile<128>::tr_off(hf, li, g, nt & 3, 1);
     }
     // dX A operand (16x16x32): row 16 mi + li, chunk 4 (ks & 3) + g of sub-tile ks >> 2
     constexpr int NMI = DD_TOK / 16;
@@ -103,7 +101,7 @@ __global__ void __launch_bounds__(512, 1) gemm_dxdw_kernel(DxDwArgs a) {
 #pragma unroll
     for (int mi = 0; mi < NMI; ++mi)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) xoff[mi][q] = dd_chunk_off(16 * mi + li, 4 * q + g);
+        for (int q = 0; q < 4; ++q) xoff[mi][q] = VTile<128>::chunk_off(16 * mi + li, 4 * q + g);
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
     auto fetch = [&](int64_t t, int slot) {
@@ -143,7 +141,7 @@ __global__ void __launch_bounds__(512, 1) gemm_dxdw_kernel(DxDwArgs a) {
     // csrc/ffn_bwd.hip hipcc 7.2 hoisted a copy above the counted s_waitcnt, and naming the registers on the wait made it copy all
     // of them in front of it.  Nothing can copy LDS.
     char *sRes = sOut + 2 * DD_TOK * DD_OSTR;           // [512 threads][16 B]
-    dd_u32x4 ds_res = {0u, 0u, 0u, 0x00020000u};
+    u32x4 ds_res = {0u, 0u, 0u, 0x00020000u};
     if (a.Res) {
         const uint64_t br = (uint64_t)a.Res;
         ds_res[0] = __builtin_amdgcn_readfirstlane((unsigned)br); ds_res[1] = __builtin_amdgcn_readfirstlane((unsigned)(br >> 32) & 0xFFFFu);
@@ -166,7 +164,7 @@ __global__ void __launch_bounds__(512, 1) gemm_dxdw_kernel(DxDwArgs a) {
         if (a.debug == 3) return;
 #endif
         if (tk < a.M) {
-            const dd_u32x4 w4 = *reinterpret_cast<const dd_u32x4 *>(so + orow * DD_OSTR + opart * 16);
+            const u32x4 w4 = *reinterpret_cast<const u32x4 *>(so + orow * DD_OSTR + opart * 16);
             const bf16x8 cv = __builtin_bit_cast(bf16x8, w4);
             const bf16x8 rv = a.Res ? *reinterpret_cast<const bf16x8 *>(sRes + tid * 16) : cv;
             float v[8];
@@ -207,11 +205,11 @@ __global__ void __launch_bounds__(512, 1) gemm_dxdw_kernel(DxDwArgs a) {
             const char *bx = sx + kk * 16 * 256;
             bf16x8 fa[2], fb[NT];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = dd_frag_tr(bx + toffA[i][0], bx + toffA[i][1]);
+            for (int i = 0; i < 2; ++i) fa[i] = frag_tr2(bx + toffA[i][0], bx + toffA[i][1]);
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const char *bg = sg + kk * 16 * 256;
-                fb[j] = dd_frag_tr(bg + toffB[j][0], bg + toffB[j][1]);
+                fb[j] = frag_tr2(bg + toffB[j][0], bg + toffB[j][1]);
                 if (wm == 0) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) bsum[j] += (float)fb[j][e];
@@ -251,10 +249,10 @@ __global__ void __launch_bounds__(512, 1) gemm_dxdw_kernel(DxDwArgs a) {
         char *so = sOut + (slot & 1) * (DD_TOK * DD_OSTR);
 #pragma unroll
         for (int mi = 0; mi < NMI; ++mi) {
-            dd_bf16x4 w;
+            bf16x4 w;
 #pragma unroll
             for (int j = 0; j < 4; ++j) w[j] = (bf16_t)ax[mi][j];
-            *reinterpret_cast<dd_bf16x4 *>(so + (16 * mi + li) * DD_OSTR + (16 * wave + 4 * g) * 2) = w;
+            *reinterpret_cast<bf16x4 *>(so + (16 * mi + li) * DD_OSTR + (16 * wave + 4 * g) * 2) = w;
         }
         // tile t + 1 must have landed before the next tile reads it: the wait at the top of this tile saw to that, except in the
         // workgroup's first tile -- issued after tile t0 + 1's DMA: the DMA of tiles t0 + 2 and t0 + 3 and this tile's residual chunk
@@ -356,8 +354,7 @@ static int dxdw_launch(DxDwArgs a, DxDwOut out, hipStream_t st) {
     const int grid = dxdw_grid(a.M, &per);
     a.tiles_per_wg = per;
     const size_t lds = DD_RING * (size_t)(1 + NG) * DD_SUB + 2 * DD_TOK * DD_OSTR + 8192;
-    static thread_local bool done = false;
-    if (!done) { (void)hipFuncSetAttribute((const void *)gemm_dxdw_kernel<NG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done = true; }
+    b4c_allow_lds(gemm_dxdw_kernel<NG>, lds);
     gemm_dxdw_kernel<NG><<<grid, 512, lds, st>>>(a);
     dxdw_reduce_kernel<NG><<<(128 * NG + NG) * 128 / 32, 256, 0, st>>>(a.part, grid, out);
     return b4c_check_launch("gemm_dxdw");

@@ -77,7 +77,6 @@ __global__ void __launch_bounds__(256) softmax_rows_kernel(const T *__restrict__
 template <int NCH>
 __global__ void __launch_bounds__(512, 4) softmax_rows_bf16_kernel(const bf16_t *__restrict__ x, int ld_in, bf16_t *__restrict__ y,
                                                                    int ld_out, int64_t R, int V) {
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     __shared__ float buf[8];
     const int tid = threadIdx.x;
     const int nch_in = (V + 7) >> 3, nch_out = ld_out >> 3;
@@ -349,7 +348,6 @@ template <int NCH>
 __global__ void __launch_bounds__(512, 4) softmax_ce_bf16_kernel(bf16_t *__restrict__ x, int ld, const int32_t *__restrict__ labels,
                                                               float *__restrict__ item_loss, const float *__restrict__ grad_scale,
                                                               int64_t R, int V, int variant) {
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     __shared__ float buf[8];
     __shared__ float buf2[8];
     __shared__ float s_ey;
@@ -794,7 +792,6 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_rows_bf16_reg_kernel(const 
                                                                           int32_t *__restrict__ topk_idx, const int32_t *__restrict__ labels,
                                                                           float *__restrict__ hit, float *__restrict__ ndcg,
                                                                           int32_t *__restrict__ redo) {
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     __shared__ float cv[TOPK_CAP];
     __shared__ int ci[TOPK_CAP];
     __shared__ float mv[TOPK_THREADS];

@@ -221,8 +221,8 @@ extern "C" int b4c_embed_concat_pe_bwd(int n_feat, const int64_t *const *h_ids, 
     const size_t shm = (size_t)EMB_HOT * d_model * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
     if (shm > 64 * 1024) {
-        (void)hipFuncSetAttribute((const void *)embed_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        (void)hipFuncSetAttribute((const void *)embed_bwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        b4c_allow_lds(embed_bwd_kernel<float>, shm);
+        b4c_allow_lds(embed_bwd_kernel<bf16_t>, shm);
     }
     if (dtype == B4C_F32)
         embed_bwd_kernel<float><<<grid, 256, shm, st>>>(a, scale, (const float *)dout, ld_dout, T_tok, d_model, dropout_rate, seed, tok_per_wg);

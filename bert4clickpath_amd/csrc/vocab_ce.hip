@@ -21,132 +21,28 @@
 // W / h tiles arrive by LDS-DMA (buffer_load ... lds) into an XOR-swizzled image that both the direct
 // (ds_read_b128) and the transposed (ds_read_b64_tr_b16) fragment reads hit without bank conflicts.
 //
-// MFMA 32x32x16 bf16 maps (lane l: r = l & 31, hf = l >> 5): A[row r][k = 8 hf + j], B[k = 8 hf + j][col r],
-// D reg t: row (t&3) + 8 (t>>2) + 4 hf, col r.  An accumulator tile used as B operand of the next MFMA sums
-// over its rows in the order 16 s + 8 (j>>2) + 4 hf + (j&3); the A operand reads the same order through
-// ds_read_b64_tr_b16.
+// The MFMA 32x32x16 bf16 operand maps, the fragment reads and the tile image (VTile) are mfma.h's.
 #include <math.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
-#include "common.h"
+#include "mfma.h"
 
-typedef __attribute__((ext_vector_type(4))) unsigned vu32x4;
-typedef __attribute__((ext_vector_type(4))) short vs16x4;
-typedef __attribute__((ext_vector_type(8))) short vs16x8;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 #define VCE_EPS 1e-7f
 #define VCE_LOG2E 1.4426950408889634f
 #define VCE_LN2 0.6931471805599453f
 
-__device__ __forceinline__ int vce_rowmap(int t, int hf) { return (t & 3) + 8 * (t >> 2) + 4 * hf; }
-__device__ __forceinline__ bf16x8 vce_pack8(const float *p) {
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (bf16_t)p[j];
-    return v;
-}
-__device__ __forceinline__ bf16x8 vce_frag_tr(const char *p, int second_off) {
-    const vs16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((vs16x4 __attribute__((address_space(3))) *)(p));
-    const vs16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((vs16x4 __attribute__((address_space(3))) *)(p + second_off));
-    const vs16x8 w = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, w);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t vce_rsrc(const void *base, int64_t rows, int64_t row_bytes) {
-    int64_t bytes = (rows < 0 ? 0 : rows) * row_bytes;
-    if (bytes > 0x3FFFFFF0ll) bytes = 0x3FFFFFF0ll;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (unsigned)bytes, 0x00020000);
-}
-
-// A [128 rows][KD] bf16 tile in LDS, filled by LDS-DMA (buffer_load ... lds: no staging registers, no ds_write).
-// Rows are unpadded (KD * 2 bytes); the 16-B chunk c of row j sits at chunk c ^ f(j):
-//   KD = 128 (a row = one 256-B bank row):   f(j) = ((j & 3) << 2) | ((j >> 2) & 3)
-//   KD =  64 (two rows per bank row):        f(j) = (((j >> 1) & 1) << 2) | ((j >> 2) & 3)
-// so that a transposed read (32-lane group: 4 consecutive rows x the same 64 B) and a direct fragment read
-// (ds_read_b128 16-lane groups: rows {0-3,12-15,20-27} / {4-11,16-19,28-31}, same chunk) both land on distinct
-// 16-B slots of the 64 banks (MI355X_MICROARCH.md, LDS).  An LDS-DMA wave instruction writes 64 x 16 B
-// contiguously (lane l -> base + 16 l), so the swizzle is applied to the SOURCE address of each lane.
-template <int KD> struct VTile {
-    static constexpr int CH = KD / 8;            // 16-B chunks per row
-    static constexpr int NIT = 128 * CH / 512;   // DMA instructions per thread: 4 (KD = 128) or 2 (KD = 64)
-    static constexpr int STR = KD * 2;
-    static constexpr int BYTES = 128 * STR;
-    static __device__ __forceinline__ int swz(int row) {
-        return KD == 128 ? (((row & 3) << 2) | ((row >> 2) & 3)) : ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
-    }
-    static __device__ __forceinline__ int chunk_off(int row, int chunk) { return row * STR + ((chunk ^ swz(row)) << 4); }
-    // rows [row0, row0 + 128) of P (row pitch ld elements) -> LDS tile at `dst`; rows >= nrows arrive as zeros.
-    // Completion is on the VM counter: s_waitcnt vmcnt(0) + a barrier before any wave reads the tile.
-    template <int NT = 512>
-    static __device__ __forceinline__ void dma(const bf16_t *__restrict__ P, int ld, int64_t row0, int64_t nrows, char *dst, int tid) {
-        const int64_t left = nrows - row0;
-        const __amdgpu_buffer_rsrc_t rs = vce_rsrc(P + row0 * ld, left < 128 ? left : 128, (int64_t)ld * 2);
-#pragma unroll
-        for (int i = 0; i < NIT * 512 / NT; ++i) {
-            const int c = tid + i * NT, row = c / CH, slot = c % CH;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)(dst + ((c & ~63) << 4)), 16,
-                                                     (row * ld + ((slot ^ swz(row)) << 3)) * 2, 0, 0, 0);
-        }
-    }
-    // one DMA instruction of the same transfer (piece i of NIT * 512 / NT; a 256-thread workgroup spreads them over its loop)
-    template <int NT>
-    static __device__ __forceinline__ void dma_piece(const bf16_t *__restrict__ P, int ld, int64_t row0, int64_t nrows, char *dst, int tid, int i) {
-        const int64_t left = nrows - row0;
-        const __amdgpu_buffer_rsrc_t rs = vce_rsrc(P + row0 * ld, left < 128 ? left : 128, (int64_t)ld * 2);
-        const int c = tid + i * NT, row = c / CH, slot = c % CH;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)(dst + ((c & ~63) << 4)), 16,
-                                                 (row * ld + ((slot ^ swz(row)) << 3)) * 2, 0, 0, 0);
-    }
-    // The same piece as inline assembly, for a loop whose LDS slots are run-time values: through the builtin the compiler
-    // cannot tell the DMA's destination from the slots the loop's ds_reads address and parks every wave on vmcnt(0) after
-    // each piece (400 cycles per piece measured).  Here it sees no LDS write at all: the caller orders the tile's arrival
-    // against its first read itself (s_waitcnt vmcnt(0) + barrier), as every sweep of this file does anyway.
-    // lds_base: LDS byte address of the slot (wave-uniform); wave: the wave's index (wave-uniform).
-    template <int NT>
-    static __device__ __forceinline__ void dma_piece_asm(const bf16_t *__restrict__ P, int ld, int64_t row0, int64_t nrows, unsigned lds_base,
-                                                         int wave, int lane, int i) {
-        const int64_t left = nrows - row0;
-        int64_t bytes = (left < 0 ? 0 : (left < 128 ? left : 128)) * (int64_t)ld * 2;
-        if (bytes > 0x3FFFFFF0ll) bytes = 0x3FFFFFF0ll;
-        const uint64_t base = (uint64_t)(P + row0 * ld);
-        vu32x4 rs;
-        rs[0] = __builtin_amdgcn_readfirstlane((unsigned)base);
-        rs[1] = __builtin_amdgcn_readfirstlane((unsigned)(base >> 32) & 0xFFFFu);
-        rs[2] = __builtin_amdgcn_readfirstlane((unsigned)bytes);
-        rs[3] = 0x00020000u;
-        const int c = wave * 64 + lane + i * NT, row = c / CH, slot = c % CH;
-        const unsigned dst = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)((wave * 64 + i * NT) << 4));
-        const unsigned voff = (unsigned)((row * ld + ((slot ^ swz(row)) << 3)) * 2);
-        // (s_nop 0: one wait state between a SALU write of M0 and an LDS-DMA that reads it -- csrc/dxdw_common.h dd_dma)
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" : : "s"(dst), "v"(voff), "s"(rs) : "m0");
-    }
-    // per-lane offsets, relative to a row base that is a multiple of 16 rows:
-    //   direct fragment (row r, k-step ks, half hf): 16 B
-    static __device__ __forceinline__ int frag_off(int r, int ks, int hf) { return chunk_off(r, 2 * ks + hf); }
-    //   transposed fragment piece: rows 4 hf + (li >> 2) (+ 8 for the second piece), columns dt*32 + 16 (g&1) + 4 (li&3)
-    static __device__ __forceinline__ int tr_off(int hf, int li, int g, int dt, int second) {
-        const int row = 4 * hf + (li >> 2) + 8 * second;
-        const int e = dt * 32 + 16 * (g & 1) + 4 * (li & 3);
-        return chunk_off(row, e >> 3) + (e & 7) * 2;
-    }
-};
 #define VCE_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-__device__ __forceinline__ bf16x8 vce_frag_tr2(const char *p0, const char *p1) {
-    const vs16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((vs16x4 __attribute__((address_space(3))) *)(p0));
-    const vs16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((vs16x4 __attribute__((address_space(3))) *)(p1));
-    const vs16x8 w = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, w);
-}
-
 // The lane's token row of h as MFMA B fragments (KD / 16 k-steps)
 template <int KD>
 __device__ __forceinline__ void vce_load_hfrag(const bf16_t *__restrict__ h, int ld_h, int64_t tok, int64_t R, int hf, bf16x8 (&f)[KD / 16]) {
 #pragma unroll
     for (int ks = 0; ks < KD / 16; ++ks) {
-        vu32x4 v = {0u, 0u, 0u, 0u};
-        if (tok < R) v = *reinterpret_cast<const vu32x4 *>(h + tok * ld_h + ks * 16 + hf * 8);
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (tok < R) v = *reinterpret_cast<const u32x4 *>(h + tok * ld_h + ks * 16 + hf * 8);
         f[ks] = __builtin_bit_cast(bf16x8, v);
     }
 }
@@ -369,7 +265,7 @@ __global__ void __launch_bounds__(512, 2) vce_token_kernel(VceArgs a) {
                 for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
                     for (int t = 0; t < 16; ++t)
-                        if (vt * 128 + vhe * 64 + rt * 32 + vce_rowmap(t, hf) < a.V) mn = fminf(mn, acc[rt][t]);
+                        if (vt * 128 + vhe * 64 + rt * 32 + rowmap(t, hf) < a.V) mn = fminf(mn, acc[rt][t]);
             }
             // the two lanes of a token share the reference (their P mix in U): lanes l and l + 32 exchange through
             // v_permlane32_swap (one VALU instruction; __shfl_xor is a ds_bpermute: an LDS round trip on the critical path
@@ -439,12 +335,12 @@ __global__ void __launch_bounds__(512, 2) vce_token_kernel(VceArgs a) {
             if (MODE != 0)
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 pf = vce_pack8(p + 8 * s2);
+                const bf16x8 pf = pack8(p + 8 * s2);
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) {
                     // W^T[d = dt*32 + r][vocab rows 16 s2 + 4 hf + {0..3, 8..11} of this 32-row tile]
                     const char *wb = w + (rt * 32 + 16 * s2) * STR;
-                    const bf16x8 wtf = vce_frag_tr2(wb + toff[dt][0], wb + toff[dt][1]);
+                    const bf16x8 wtf = frag_tr2(wb + toff[dt][0], wb + toff[dt][1]);
                     U[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wtf, pf, U[dt], 0, 0, 0);
                 }
             }
@@ -690,8 +586,8 @@ __global__ void __launch_bounds__(256 * TH, 2) vce_dw_kernel(VceDwArgs a) {
     bf16x8 wfr[NKS];
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
-        vu32x4 q = {0u, 0u, 0u, 0u};
-        if (v < a.V) q = *reinterpret_cast<const vu32x4 *>(a.wt + (int64_t)v * a.ld_w + ks * 16 + hf * 8);
+        u32x4 q = {0u, 0u, 0u, 0u};
+        if (v < a.V) q = *reinterpret_cast<const u32x4 *>(a.wt + (int64_t)v * a.ld_w + ks * 16 + hf * 8);
         wfr[ks] = __builtin_bit_cast(bf16x8, q);
     }
     const float bv = (v < a.V) ? (a.bias ? a.bias[v] : 0.f) : -INFINITY;
@@ -768,12 +664,12 @@ __global__ void __launch_bounds__(256 * TH, 2) vce_dw_kernel(VceDwArgs a) {
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const bf16x8 gf = vce_pack8(gv + 8 * s2);
+                const bf16x8 gf = pack8(gv + 8 * s2);
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) {
                     // h^T[d = dt*32 + r][tokens 16 s2 + 4 hf + {0..3, 8..11} of this 32-token tile]
                     const char *hb = hh + (rt * 32 + 16 * s2) * STR;
-                    const bf16x8 htf = vce_frag_tr2(hb + toff[dt][0], hb + toff[dt][1]);
+                    const bf16x8 htf = frag_tr2(hb + toff[dt][0], hb + toff[dt][1]);
                     dW[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(htf, gf, dW[dt], 0, 0, 0);
                 }
             }
@@ -796,7 +692,7 @@ __global__ void __launch_bounds__(256 * TH, 2) vce_dw_kernel(VceDwArgs a) {
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
-                for (int t = 0; t < 16; ++t) sD[(dt * 32 + vce_rowmap(t, hf)) * 32 + r] = dW[dt][t];
+                for (int t = 0; t < 16; ++t) sD[(dt * 32 + rowmap(t, hf)) * 32 + r] = dW[dt][t];
             if (hf == 0) sD[KD * 32 + r] = dbv;
         }
         __syncthreads();
@@ -805,7 +701,7 @@ __global__ void __launch_bounds__(256 * TH, 2) vce_dw_kernel(VceDwArgs a) {
             for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
                 for (int t = 0; t < 16; ++t) {
-                    const int d = dt * 32 + vce_rowmap(t, hf);
+                    const int d = dt * 32 + rowmap(t, hf);
                     const float val = dW[dt][t] + sD[d * 32 + r];
                     vce_dw_put<KD>(a, ts, d, v, a.dW + (int64_t)d * a.ldw + v, val, direct);
                 }
@@ -816,7 +712,7 @@ __global__ void __launch_bounds__(256 * TH, 2) vce_dw_kernel(VceDwArgs a) {
         for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
-                const int d = dt * 32 + vce_rowmap(t, hf);
+                const int d = dt * 32 + rowmap(t, hf);
                 vce_dw_put<KD>(a, ts, d, v, a.dW + (int64_t)d * a.ldw + v, dW[dt][t], direct);
             }
         if (hf == 0 && a.db) vce_dw_put<KD>(a, ts, KD, v, a.db + v, dbv, direct);
@@ -1048,9 +944,6 @@ static int vce_pick_split(int64_t units, int64_t max_split, double penalty) {
 }
 static bool vce_shape_ok(int K) { return K == 64 || K == 128; }
 
-template <typename Kern> static void vce_allow_lds(Kern k, size_t bytes) {
-    (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 template <int KD> static size_t vce_token_lds() {
     const size_t tiles = 2 * (size_t)VTile<KD>::BYTES + 2 * 128 * 4;
     const size_t outs = (size_t)8 * 32 * (KD + 4) * 4 + 8 * 64 * 16;
@@ -1106,12 +999,8 @@ static int vce_fwd_launch(VceArgs a, hipStream_t st) {
     a.ud = a.u + (int64_t)a.parts * a.R * KD;
     a.sp = a.ud + (int64_t)a.parts * a.R * KD;
     const size_t lds = vce_token_lds<KD>();
-    static thread_local bool done = false;
-    if (!done) {
-        vce_allow_lds(vce_token_kernel<KD, 1, 1>, lds); vce_allow_lds(vce_token_kernel<KD, 2, 1>, lds);
-        vce_allow_lds(vce_token_kernel<KD, 1, 2>, lds); vce_allow_lds(vce_token_kernel<KD, 2, 2>, lds);
-        done = true;
-    }
+    b4c_allow_lds(vce_token_kernel<KD, 1, 1>, lds); b4c_allow_lds(vce_token_kernel<KD, 2, 1>, lds);
+    b4c_allow_lds(vce_token_kernel<KD, 1, 2>, lds); b4c_allow_lds(vce_token_kernel<KD, 2, 2>, lds);
     a.ntt = (int)ntt;
     const unsigned grid = (unsigned)(ntt * a.parts);
     if (nh == 2) vce_token_kernel<KD, 1, 2><<<grid, 512, lds, st>>>(a); else vce_token_kernel<KD, 1, 1><<<grid, 512, lds, st>>>(a);
@@ -1147,8 +1036,7 @@ static int vce_lse_launch(VceArgs a, float *lse2, hipStream_t st) {
     const int nvt = (a.V + 127) / 128;
     a.parts = vce_pick_split(ntt, nvt, 0.005);
     const size_t lds = vce_token_lds<KD>();
-    static thread_local bool done = false;
-    if (!done) { vce_allow_lds(vce_token_kernel<KD, 0, 1>, lds); vce_allow_lds(vce_token_kernel<KD, 0, 2>, lds); done = true; }
+    b4c_allow_lds(vce_token_kernel<KD, 0, 1>, lds); b4c_allow_lds(vce_token_kernel<KD, 0, 2>, lds);
     a.ntt = (int)ntt;
     if (nh == 2) vce_token_kernel<KD, 0, 2><<<(unsigned)(ntt * a.parts), 512, lds, st>>>(a);
     else vce_token_kernel<KD, 0, 1><<<(unsigned)(ntt * a.parts), 512, lds, st>>>(a);
@@ -1176,8 +1064,7 @@ static void vce_dw_sweep_launch(VceDwArgs a, int vt0, int nvt, int background_wg
                                 float *part = nullptr, int64_t part_bytes = 0) {
     const int64_t ntt = ceil_div64(a.R, 128);
     const size_t lds = vce_dw_lds<KD>();
-    static thread_local bool done = false;
-    if (!done) { vce_allow_lds(vce_dw_kernel<KD, 2>, lds); vce_allow_lds(vce_dw_kernel<KD, 1>, lds); done = true; }
+    b4c_allow_lds(vce_dw_kernel<KD, 2>, lds); b4c_allow_lds(vce_dw_kernel<KD, 1>, lds);
     a.vt0 = vt0; a.nvt = nvt;
     if (background_wgs > 0) {
         // beside other kernels: at most background_wgs workgroups of 4 waves (one per SIMD), whole rounds of units
@@ -1347,8 +1234,8 @@ __global__ void __launch_bounds__(64) vce_label_logit_kernel(VceScanArgs a, floa
     for (int t = 0; t < 16; ++t) acc[t] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
-        vu32x4 q = {0u, 0u, 0u, 0u};
-        if (valid) q = *reinterpret_cast<const vu32x4 *>(a.wt + (int64_t)y * a.ld_w + ks * 16 + hf * 8);
+        u32x4 q = {0u, 0u, 0u, 0u};
+        if (valid) q = *reinterpret_cast<const u32x4 *>(a.wt + (int64_t)y * a.ld_w + ks * 16 + hf * 8);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, q), hfr[ks], acc, 0, 0, 0);
     }
     // D[row i][col j] = W[y_i] . h_j: the diagonal element of token r sits in the lane with hf = (r >> 2) & 1, register
@@ -1765,8 +1652,7 @@ static void vce_scan_geometry(VceScanArgs &a, int nh) {
 template <int KD, int OP, bool EX>
 static void vce_scan_launch(const VceScanExArgs &a, int nh, hipStream_t st) {
     const size_t lds = 2 * (size_t)VTile<KD>::BYTES + 3 * 128 * 4;
-    static thread_local bool done = false;
-    if (!done) { vce_allow_lds(vce_scan_kernel<KD, OP, 1, EX>, lds); vce_allow_lds(vce_scan_kernel<KD, OP, 2, EX>, lds); done = true; }
+    b4c_allow_lds(vce_scan_kernel<KD, OP, 1, EX>, lds); b4c_allow_lds(vce_scan_kernel<KD, OP, 2, EX>, lds);
     const std::conditional_t<EX, VceScanExArgs, VceScanArgs> ka = a;          // EX = false: the block without the list fields
     if (nh == 2) vce_scan_kernel<KD, OP, 2, EX><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(ka);
     else vce_scan_kernel<KD, OP, 1, EX><<<(unsigned)(a.ntt * a.parts), 512, lds, st>>>(ka);

@@ -30,30 +30,30 @@ Roundings per output and route (file:line of the instruction that rounds; "out" 
 
   route        kernels                                   output  n   where
   -----------  ----------------------------------------  ------  --  -----------------------------------------------------------
-  mfma         attn_fwd_mfma_kernel                      o       1   P -> bf16 in front of P V: attn_mfma.hip:277 pack8(pv); out :305
+  mfma         attn_fwd_mfma_kernel                      o       1   P -> bf16 in front of P V: attn_mfma.hip:212 pack8(pv); out :240
                (dense + packed, bf16, dh 32 / 64)        lse     0   logits are fp32 sums of exact bf16 products, the scale is
-                                                                     applied in fp32 (attn_mfma.hip:239); stored fp32 (:315)
-               attn_bwd_resident_kernel (S <= 256)       dv      1   P -> bf16: attn_mfma.hip:735 (key blocks: :470); out :782 (:527)
-               attn_bwd_mfma_kernel (key blocks, S>256)  dq, dk  1   dS -> bf16: attn_mfma.hip:731 / :736 (key blocks: :466 / :471);
-                                                                     out: dq :759 (key blocks :509, once, after the fp32 sum of the
-                                                                     block partials), dk :781 (:526)
+                                                                     applied in fp32 (attn_mfma.hip:174); stored fp32 (:250)
+               attn_bwd_resident_kernel (S <= 256)       dv      1   P -> bf16: attn_mfma.hip:670 (key blocks: :405); out :717 (:462)
+               attn_bwd_mfma_kernel (key blocks, S>256)  dq, dk  1   dS -> bf16: attn_mfma.hip:666 / :671 (key blocks: :401 / :406);
+                                                                     out: dq :694 (key blocks :444, once, after the fp32 sum of the
+                                                                     block partials), dk :716 (:461)
                                                          delta   -   delta = sum dO o reads the FORWARD's stored bf16 o
-                                                                     (attn_mfma.hip:385-387 / :640): it carries o's whole bound
+                                                                     (attn_mfma.hip:320-322 / :575): it carries o's whole bound
                                                                      (n = 1 and out), |delta delta_q| <= sum_j |dO_qj| bound_o[q, j]
-  mq_mfma      attn_mq_fwd_mfma_kernel                   o       1   attn_mq.hip:526 mq_pack8(pv); out :546
+  mq_mfma      attn_mq_fwd_mfma_kernel                   o       1   attn_mq.hip:475 pack8(pv); out :495
                attn_mq_bwd_mfma_kernel                   lse     0   as above
-               (bf16, dh 32 / 64)                        dv      1   P -> bf16 attn_mq.hip:740; out :782, once per pass of 32 queries
-                                                         dq, dk  1   dS -> bf16 attn_mq.hip:730 / :741; out: dq :798, dk :781 once
+               (bf16, dh 32 / 64)                        dv      1   P -> bf16 attn_mq.hip:664; out :706, once per pass of 32 queries
+                                                         dq, dk  1   dS -> bf16 attn_mq.hip:654 / :665; out: dq :722, dk :705 once
                                                                      per pass of 32 queries (a pass reads the stored bf16 row back
                                                                      and adds: ceil(queries / 32) - 1 further roundings of a partial
                                                                      sum, each bounded by u A)
   row_f32      attn.hip / attn_mq.hip fp32 kernels       all     0   plain fp32 VALU arithmetic, fp32 outputs (u_out = 2^-24)
 
-  vce          vce_token_kernel<K,1> / <K,2> + combine   dh      1   P' -> bf16 in front of U = P' W: vocab_ce.hip:442 vce_pack8(p);
-                                                                     out :611
-               vce_dw_kernel (atomic, deterministic,     dW      1   dlogit -> bf16 in front of h^T dlogit: vocab_ce.hip:771; the label
+  vce          vce_token_kernel<K,1> / <K,2> + combine   dh      1   P' -> bf16 in front of U = P' W: vocab_ce.hip:338 pack8(p);
+                                                                     out :507
+               vce_dw_kernel (atomic, deterministic,     dW      1   dlogit -> bf16 in front of h^T dlogit: vocab_ce.hip:667; the label
                foreground and background sweeps) + the               term -yd h_row is added in fp32; fp32 output
-               label kernels                             db      0   column sums of the UNROUNDED fp32 dlogit (vocab_ce.hip:755 / :766)
+               label kernels                             db      0   column sums of the UNROUNDED fp32 dlogit (vocab_ce.hip:651 / :662)
                vce_lse_kernel / rowscal[:, 0]            lse     0   fp32 sums of exact bf16 products
 
 The attention companions (c = 1 / sqrt(dh), w = n u + E + length 2^-24):
@@ -68,7 +68,7 @@ p_y went through the rounding, the 1 did not):
     dh     A = D |W|,   dW: A = |h|^T D,   db: A = sum_r D
 TF clip variant: a row that leaves [1e-7, 1 - 1e-7] gets U and Ud (the part outside the range) from two sweeps with two
 roundings of the same p, so D gains 2 gs p / S on the entries outside the range; and the row's coefficients gs (1 / S - G) and
--gs G, G = Pu / S - yd, are fp32 differences of O(1) numbers (vocab_ce.hip:602, :617): D gains 8 * 2^-24 gs p on every entry of
+-gs G, G = Pu / S - yd, are fp32 differences of O(1) numbers (vocab_ce.hip:498, :513): D gains 8 * 2^-24 gs p on every entry of
 such a row (on a confidently wrong row the exact coefficient gs Pc / S is smaller than that error: the MI355X run showed the
 dominant entries' dW off by their own size, 3e-10 against gradients of 1e-3, until this term was counted).  The kernels decide the clipping on fp32
 probabilities: an entry with |log(p_ref / 1e-7)| <= E[r, v] (E as above with depth K and the logits' sum_j |h_j||w_j| + |b|),
@@ -340,7 +340,7 @@ def vocab_ref(h, W, b, y, variant):
             unit = gs * p / S[:, None]                                     # an entry's contribution when it counts as inside
             D = D + (outside & clipped[:, None]).double() * 2.0 * unit
             # the row's two coefficients (inside the range: gs (1 / S - G), outside: -gs G, G = Pu / S - yd) are fp32 DIFFERENCES of
-            # O(1) numbers (vocab_ce.hip:602 G = Pu * invS - yd, :617 ra - rb): an absolute error of up to COEF_ULPS 2^-24 gs each, whatever
+            # O(1) numbers (vocab_ce.hip:498 G = Pu * invS - yd, :513 ra - rb): an absolute error of up to COEF_ULPS 2^-24 gs each, whatever
             # is left of them after the cancellation (a confidently wrong row: gs Pc / S with Pc the mass beside its dominant entry)
             coef = clipped[:, None].double() * (COEF_ULPS * U_F32 * gs) * p            # absolute: not scaled by n u
             und = (torch.log(p.clamp_min(1e-300) / EPS_TF).abs() <= E) & valid[:, None]

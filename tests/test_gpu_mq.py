@@ -93,6 +93,22 @@ def test_attn_mq_kernels_match_fp64(dtype, H, dh, smax, mmax, pad):
         lb.check(n, t, *res[n])
 
 
+def test_attn_mq_fwd_lds_need_grows_within_one_process():
+    """One kernel, two launches whose dynamic LDS need grows across the 64 KiB that a launch gets without an opt-in: the fp32
+    forward with dh = 64 needs 16 * 64 * 4 + 16 * SP * 4 + 128 * 64 * 4 bytes (mq_fwd_lds; SP = max_len rounded up to 64), that is
+    40,960 at max_len = 64 and 69,632 at max_len = 512.  The opt-in (b4c_allow_lds) must be renewed for the second launch: a helper
+    that remembers the kernel and not the size lets the runtime reject it, and the entry point returns an error.
+    The fp32 backward cannot cross the line: its need (mq_bwd_lds) does not depend on max_len and is 49,280 bytes at dh = 64."""
+    from bert4clickpath_amd import ops
+    B, H, dh, dev = 2, 1, 64, 'cuda'
+    for max_len in (64, 512):
+        cu, moff, q, kv, go = _ragged(B, max_len, 3, H, dh, 7 + max_len, torch.float32, with_empty=False)
+        ro, rl, _, _ = _ref(cu, moff, q, kv, go, H, dh)
+        o, lse = ops.attn_mq_fwd(q.to(dev), kv.to(dev), cu.to(dev), moff.to(dev), B, max_len, H, dh, None)   # raises unless B4C_OK
+        assert float((o.double().cpu() - ro).abs().max()) < 2e-5 * max(1.0, float(ro.abs().max())), max_len
+        assert float((lse.double().cpu() - rl).abs().max()) < 1e-4, max_len
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # the model: last encoder layer evaluated at the [MASK] rows only (ops.mq_last_layer) against the full layer and the oracle
 # ------------------------------------------------------------------------------------------------------------------
