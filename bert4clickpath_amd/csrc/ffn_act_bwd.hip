@@ -1,29 +1,17 @@
-// Backward of the position-wise feed-forward block of one encoder layer -- LayerNorm, dropout, both Dense layers -- in ONE pass
-// over its tensors (round 4; VERDICT r3 item 1: the encoder backward's byte diet).
-//
-// The reference's block (transformer.py:154-170: Dense(dff, relu), Dense(d_model), dropout, residual add, LayerNormalization)
-// comes back, in the backward pass, as five kernels here until now:
-//     add_ln_bwd      dOut, z, stats -> dz (residual branch), dy (through the dropout mask); dgamma, dbeta      4 [T][128] passes
-//     gemm_nt (gate)  dh = (dy W2^T) o [h > 0]                                                                    ~2.6
-//     gemm_nt (+res)  dx = dh W1^T + dz                                                                            ~2.8
-//     gemm_tn x 2     dW2 = h^T dy, dW1 = x^T dh (+ the bias sums)                                                 ~3.6
-// 13 passes of [T][128] bf16 over HBM.  dz, dy and dh exist only between these kernels: here they live in registers and LDS, and
-// the block's backward reads dOut, z, h, x and writes dx -- 4.8 passes (1,240 B per token against 3,340).
-//
-// A persistent 512-thread workgroup per CU walks 32-token tiles (tile i of a workgroup = global tile blockIdx.x + i gridDim.x):
-//   LDS-DMA     h tile [32][Fp] and x tile [32][128] into a four-stage ring of XOR-swizzled images (three tiles ahead)
-//   rows        dOut / z chunks and the rows' statistics arrive by LDS-DMA too, a tile ahead, 16 B per thread at thread * 16 (every
-//               request lands in LDS: a register that a load is still filling gets copied by the compiler -- see ln_load below);
-//               16 threads per token row hold 8 columns each: LayerNorm backward with 16-lane sums -> dz (kept, bf16, for the
-//               residual add two phases later) and dy -> LDS image; dgamma / dbeta partial sums stay in registers over all tiles
-//   phase 2     dW2 += h^T dy (MFMA 32x32x16, fragments by transposed LDS reads), dh = (dy W2^T) o [h > 0] (MFMA 16x16x32, the
-//               wave's 16 hidden columns of W2 resident in registers) -> LDS image
-//   phase 1'    (with the NEXT tile's LayerNorm phase) dW1 += x^T dh, dx = dh W1^T -> staged fp32 tile
-//   store       (with the next tile's phase 2) staged dx + dz -> bf16 -> global, 16-B row chunks
-//   end         the workgroup's partial sums -> scratch; ffn_bwd_reduce_kernel adds them in a fixed order into the Keras-layout
-//               gradient tensors (bit-repeatable: no float atomics anywhere, also not for dgamma / dbeta).
-// Two barriers per tile.  d_model = 128, dff <= 128 (the reference hard-codes 100, transformer.py:113), bf16: every other shape
-// keeps the five kernels.
+// Backward of the feed-forward block with a GELU activation in ONE pass over its tensors: the kernel of ffn_bwd.hip (read its
+// description of the skeleton first) with the pre-activation u as a third image of every ring stage, h | x | u.  GELU is not
+// monotone, so the gate cannot be read off h: dW2 += h^T dy still reads the h image, and the hidden gradient becomes
+//     dh = (dy W2^T) * act'(u),  act = B4C_ACT_GELU (erf) or B4C_ACT_GELU_TANH,
+// with the rounding points of b4c_gemm_nt_act(..., gate = u, gate_act = act), which this replaces -- its bf16 epilogue stages
+// dy W2^T as bf16, multiplies in fp32 and rounds the product: dh = bf16(bf16(dy W2^T) * act'(u)), so that a model computes the
+// same step on either route -- and guarded by column:
+// an image of a tensor narrower than 128 columns holds past its width whatever follows the row in memory (dxdw_common.h), and
+// 0 * act'(garbage) is not 0 when the garbage is not finite (the ReLU kernel selects, and is safe without the guard).
+// One more LDS-DMA request per fetch: the counted waits are vmcnt(4) in the steady state and vmcnt(3) for the second tile, derived
+// where they stand.  156,160 B of LDS, one workgroup per CU.  The partial sums' layout, their reduction and the workspace are
+// b4c_ffn_bwd's.
+// The kernel is a copy of ffn_bwd_kernel with these changes, not a shared template: wrapped into an inlined function template the
+// ReLU kernel came out of the compiler with other registers and another schedule, and its assembly is pinned.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -31,40 +19,33 @@
 #include "dxdw_common.h"
 
 #define FB_OSTR 528                  // bytes per staged dx row: 128 fp32 + 16
+#define FB_ROWS 260                  // rows of a workgroup's partial sums (ffn_bwd.hip)
 
-struct FfnBwdArgs {
+struct FfnActBwdArgs {
     const bf16_t *dOut;   // [M][128]  gradient of the block's output
     const bf16_t *Z;      // [M][128]  x + dropout(y): the LayerNorm's input, saved by the forward pass
     const float *stats;   // [M][2]    mean, 1 / std of z's rows
     const float *gamma;   // [128]
-    const bf16_t *H;      // [M][ldh]  relu(x W1 + b1), Fp columns
+    const bf16_t *H;      // [M][ldh]  act(u), Fp columns
+    const bf16_t *U;      // [M][ldu]  u = x W1 + b1, Fp columns
     const bf16_t *X;      // [M][ldx]  the block's input
     const bf16_t *W2c;    // [Fp][ldw2]  row = hidden column, 128 entries: the operand of dh = dy W2^T
     const bf16_t *W1c;    // [128][ldw1] row = input feature, Fp entries: the operand of dx = dh W1^T
     bf16_t *dX;           // [M][ldo]
-    float *part;          // [workgroups][260][128]: dW2^T (row = output column, 128 hidden), dW1^T (row = hidden column, 128 inputs), db2, db1, dgamma, dbeta
-    int ldh, ldx, ldw2, ldw1, ldo, Fp;
+    float *part;          // [workgroups][260][128]: dW2^T, dW1^T, db2, db1, dgamma, dbeta (ffn_bwd.hip's layout)
+    int ldh, ldu, ldx, ldw2, ldw1, ldo, Fp;
     float rate;
     uint64_t seed;
     int64_t M;
-#ifdef DD_EXPERIMENT
-    int debug;            // scratch builds only: the counted wait of the steady state (3) replaced by this many
-#endif
 };
 
-#define FB_ROWS 260
+// ffn_bwd.hip: the workgroups' partial sums += into the gradient tensors in a fixed order
+void ffn_bwd_reduce(const float *part, int nwg, float *dW2, int ld2, float *dW1, int ld1, float *db2, float *db1, float *dgamma,
+                    float *dbeta, int F, hipStream_t st);
 
-#ifdef DD_EXPERIMENT
-__device__ unsigned g_fb_dbg[4 * 32 * 4];      // [slot][row][0: h chunk != global, 1: == the tile four back, 2: x chunk != global, 3: checks]
-extern "C" int b4c_debug_fb(void *dst, size_t nbytes, int clear) {
-    if (clear) { static unsigned z[4 * 32 * 4]; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_fb_dbg), z, sizeof(z)); }
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_fb_dbg), nbytes < sizeof(g_fb_dbg) ? nbytes : sizeof(g_fb_dbg));
-}
-#endif
-
-__global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
+template <int ACT> __global__ void __launch_bounds__(512, 1) ffn_act_bwd_kernel(FfnActBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int STAGE = 2 * DD_SUB;                   // h | x
+    constexpr int STAGE = 3 * DD_SUB;                   // h | x | u
     char *sDY = smem + DD_RING * STAGE;                 // [32][128] bf16 image of dy
     char *sDH = sDY + DD_SUB;                           // [32][128] bf16 image of dh
     char *sOut = sDH + DD_SUB;                          // [32][FB_OSTR] fp32 dx = dh W1^T (before the residual)
@@ -121,21 +102,9 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
         const unsigned st = lds0 + (unsigned)(slot * STAGE);
         const int64_t tok0 = (gfirst + t * gstep) * DD_TOK;
         const int64_t M = t < t1 ? a.M : 0;             // past the last tile: zero rows (still LDS writes, still counted)
-#ifdef DD_EXPERIMENT
-        if (a.debug == 20) {            // x first
-            dd_dma(a.X, a.ldx, 0, tok0, M, st + DD_SUB, wave, lane);
-            dd_dma(a.H, a.ldh, 0, tok0, M, st, wave, lane, a.Fp * 2);
-            return;
-        }
-        if (a.debug == 21) {            // 64 more wait states between the two
-            dd_dma(a.H, a.ldh, 0, tok0, M, st, wave, lane, a.Fp * 2);
-            asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7");
-            dd_dma(a.X, a.ldx, 0, tok0, M, st + DD_SUB, wave, lane);
-            return;
-        }
-#endif
         dd_dma(a.H, a.ldh, 0, tok0, M, st, wave, lane, a.Fp * 2);
         dd_dma(a.X, a.ldx, 0, tok0, M, st + DD_SUB, wave, lane);
+        dd_dma(a.U, a.ldu, 0, tok0, M, st + 2 * DD_SUB, wave, lane, a.Fp * 2);
     };
     // dOut / z chunks and the row's statistics land in LDS too (LDS-DMA, 16 B per thread at thread * 16: every thread reads back its
     // own piece, so the issuing wave's counted wait is all the ordering it needs).  They landed in REGISTERS first (inline-assembly
@@ -230,10 +199,13 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
 
     // One iteration = two barrier intervals.  Iteration t (0 .. t1; the last one only finishes tile t1 - 1):
     //   interval 1: LayerNorm backward of tile t -> dy image, dz kept; requests tile t + 1's rows; phase 3 of tile t - 1
-    //   interval 2: requests tile t + 3's h | x; dx rows of tile t - 1 leave; phase 2 of tile t (dW2, dh image)
-    // Vector-memory operations per thread in issue order: ... [3 row loads of t + 1] [2 DMA of t + 3] [1 store of t - 1] ...
-    // The only counted wait: tile t's row loads at the top of iteration t -- issued since: 2 DMA + 1 store (none / no store in
-    // the first iterations).  Everything older has landed with them: the h | x tiles t and t + 1.
+    //   interval 2: requests tile t + 3's h | x | u; dx rows of tile t - 1 leave; phase 2 of tile t (dW2, dh image)
+    // Vector-memory operations per thread in issue order: ... [3 row loads of t + 1] [3 DMA of t + 3] [1 store of t - 1] ...
+    // The only counted wait: tile t's row loads at the top of iteration t.  They went out in interval 1 of iteration t - 1; issued
+    // since: the 3 DMA of h | x | u (t + 2) and the dX store of tile t - 2 = 4 operations, `vmcnt(4)`; the youngest row request is
+    // the 4th LDS-DMA request back.  At t == 1 no store has gone out yet (iteration 0 has no tile before it): the 3 DMA of tile 3,
+    // `vmcnt(3)`.  Everything older has landed with the row loads: the h | x | u tiles t and t + 1.  (ffn_bwd.hip, one request
+    // fewer per fetch, counts 3 and 2.)
     auto tile = [&](auto ODD, int64_t t) {
         constexpr bool odd_tile = decltype(ODD)::value;  // (dz of a tile waits in one of two register quadruples: the parity is compile time)
         const int slot = (int)(t & 3);
@@ -241,10 +213,10 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
         u32x4 &dz_cur = odd_tile ? dz1 : dz0;
         u32x4 &dz_prev = odd_tile ? dz0 : dz1;
         if (body) {
-            // (tests/test_vmcnt_accounting.py checks both counts in the assembly: ffn_bwd.second, ffn_bwd.steady)
+            // (tests/test_vmcnt_ffn_act.py checks both counts in the assembly: ffn_act_bwd.second, ffn_act_bwd.steady)
             if (t == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (t == 1) asm volatile("s_waitcnt vmcnt(2) ; vmcheck ffn_bwd.second" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(3) ; vmcheck ffn_bwd.steady" ::: "memory");
+            else if (t == 1) asm volatile("s_waitcnt vmcnt(3) ; vmcheck ffn_act_bwd.second" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(4) ; vmcheck ffn_act_bwd.steady" ::: "memory");
             // ---- LayerNorm + dropout backward of this thread's 8 columns of row orow (rowops.hip add_ln_bwd_kernel) ----
             const int64_t tk = (gfirst + t * gstep) * DD_TOK + orow;
             const bool live = tk < a.M;
@@ -286,36 +258,10 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
         }
         if (t > 0) phase3((slot + 3) & 3);
         __syncthreads();
-#ifdef DD_EXPERIMENT
-        if (body && a.debug >= 10) {
-            // is the h | x image of tile t what global memory holds?  (every request of tile t was waited for above, by every wave)
-            const int64_t tk = (gfirst + t * gstep) * DD_TOK + orow;
-            if (tk < a.M && opart * 8 < a.Fp) {
-                const u32x4 l = *reinterpret_cast<const u32x4 *>(smem + slot * STAGE + rowoff);
-                const u32x4 gq = *reinterpret_cast<const u32x4 *>(a.H + tk * a.ldh + opart * 8);
-                const bool ne = l[0] != gq[0] || l[1] != gq[1] || l[2] != gq[2] || l[3] != gq[3];
-                if (ne) {
-                    atomicAdd(&g_fb_dbg[(slot * 32 + orow) * 4 + 0], 1u);
-                    if (t >= 4) {
-                        const int64_t tk4 = (gfirst + (t - 4) * gstep) * DD_TOK + orow;
-                        const u32x4 g4 = *reinterpret_cast<const u32x4 *>(a.H + tk4 * a.ldh + opart * 8);
-                        if (l[0] == g4[0] && l[1] == g4[1] && l[2] == g4[2] && l[3] == g4[3]) atomicAdd(&g_fb_dbg[(slot * 32 + orow) * 4 + 1], 1u);
-                    }
-                }
-                if (opart == 0) atomicAdd(&g_fb_dbg[(slot * 32 + orow) * 4 + 3], 1u);
-            }
-            if (tk < a.M) {
-                const u32x4 l = *reinterpret_cast<const u32x4 *>(smem + slot * STAGE + DD_SUB + rowoff);
-                const u32x4 gq = *reinterpret_cast<const u32x4 *>(a.X + tk * a.ldx + opart * 8);
-                if (l[0] != gq[0] || l[1] != gq[1] || l[2] != gq[2] || l[3] != gq[3]) atomicAdd(&g_fb_dbg[(slot * 32 + orow) * 4 + 2], 1u);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-#endif
         if (body) fetch(t + 3, (slot + 3) & 3);         // that stage held tile t - 1: phase 3 above was its last reader
         if (t > 0) store_rows(t - 1, dz_prev);
         if (!body) return;
-        // ---- phase 2: dW2 += h^T dy, dh = (dy W2^T) o [h > 0] ----
+        // ---- phase 2: dW2 += h^T dy, dh = (dy W2^T) o act'(u) ----
         const char *sh = smem + slot * STAGE;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
@@ -337,9 +283,9 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi) fg[mi][q] = *reinterpret_cast<const bf16x8 *>(sDY + xoff[mi][q]);
-        bf16x4 hv[2];
+        bf16x4 uv[2];
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi) hv[mi] = *reinterpret_cast<const bf16x4 *>(sh + poff[mi]);
+        for (int mi = 0; mi < 2; ++mi) uv[mi] = *reinterpret_cast<const bf16x4 *>(sh + 2 * DD_SUB + poff[mi]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -349,7 +295,8 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
         for (int mi = 0; mi < 2; ++mi) {
             bf16x4 w;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) w[j] = (float)hv[mi][j] > 0.f ? (bf16_t)ax[mi][j] : (bf16_t)0.f;
+            for (int j = 0; j < 4; ++j)      // (by column, not by the zero W2 fragment: see the top of the file)
+                w[j] = 16 * wave + 4 * g + j < a.Fp ? (bf16_t)((float)(bf16_t)ax[mi][j] * act_gelu_grad((float)uv[mi][j], ACT)) : (bf16_t)0.f;
             *reinterpret_cast<bf16x4 *>(sDH + poff[mi]) = w;
         }
         __syncthreads();
@@ -395,88 +342,42 @@ __global__ void __launch_bounds__(512, 1) ffn_bwd_kernel(FfnBwdArgs a) {
     }
 }
 
-struct FfnBwdOut {
-    float *dW2, *dW1, *db2, *db1, *dgamma, *dbeta;
-    int ld2, ld1, F;      // dW2 [F][ld2] (Keras kernel of the second Dense), dW1 [128][ld1], F valid hidden columns
-};
-// The workgroups' partial sums in a fixed order, as dxdw_reduce_kernel (gemm_dxdw.hip): a block owns 32 consecutive entries, its
-// eight 32-lane groups each add every eighth workgroup's partial.
-__global__ void __launch_bounds__(256) ffn_bwd_reduce_kernel(const float *__restrict__ part, int nwg, FfnBwdOut out) {
-    __shared__ float sh[8][32];
-    const int c = threadIdx.x & 31, q = threadIdx.x >> 5;
-    const int idx = blockIdx.x * 32 + c;                 // over FB_ROWS x 128
-    float s = 0.f;
-#pragma unroll 8
-    for (int w = q; w < nwg; w += 8) s += part[(int64_t)w * FB_ROWS * 128 + idx];
-    sh[q][c] = s;
-    __syncthreads();
-    if (q != 0) return;
-    s = sh[0][c];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) s += sh[k][c];
-    const int row = idx >> 7, k = idx & 127;
-    if (row < 128) {                                     // dW2^T: row = output column, k = hidden column
-        if (k < out.F) out.dW2[(int64_t)k * out.ld2 + row] += s;
-    } else if (row < 256) {                              // dW1^T: row - 128 = hidden column, k = input feature
-        if (row - 128 < out.F) out.dW1[(int64_t)k * out.ld1 + (row - 128)] += s;
-    } else if (row == 256) {
-        if (out.db2) out.db2[k] += s;
-    } else if (row == 257) {
-        if (out.db1 && k < out.F) out.db1[k] += s;
-    } else if (row == 258) {
-        out.dgamma[k] += s;
-    } else {
-        out.dbeta[k] += s;
-    }
+template <int ACT> static void ffn_act_bwd_launch(const FfnActBwdArgs &a, int grid, hipStream_t st) {
+    constexpr size_t lds = DD_RING * (size_t)3 * DD_SUB + 2 * DD_SUB + DD_TOK * FB_OSTR + 3 * 8192;
+    b4c_allow_lds(ffn_act_bwd_kernel<ACT>, lds);
+    ffn_act_bwd_kernel<ACT><<<grid, 512, lds, st>>>(a);
 }
 
-// (host) the reduction alone: b4c_ffn_act_bwd (ffn_act_bwd.hip) leaves its partial sums in the same layout
-void ffn_bwd_reduce(const float *part, int nwg, float *dW2, int ld2, float *dW1, int ld1, float *db2, float *db1, float *dgamma,
-                    float *dbeta, int F, hipStream_t st) {
-    const FfnBwdOut out = {dW2, dW1, db2, db1, dgamma, dbeta, ld2, ld1, F};
-    ffn_bwd_reduce_kernel<<<FB_ROWS * 128 / 32, 256, 0, st>>>(part, nwg, out);
-}
-
-static int ffn_bwd_grid(int64_t M) {
-    const int64_t ntiles = (M + DD_TOK - 1) / DD_TOK;
-    return (int)(ntiles < 256 ? ntiles : 256);          // one persistent workgroup per CU; every workgroup has at least one tile
-}
-
-extern "C" int64_t b4c_ffn_bwd_workspace_bytes(int64_t M) {
-    if (M <= 0) return 0;
-    return (int64_t)ffn_bwd_grid(M) * FB_ROWS * 128 * 4;
-}
-
-extern "C" int b4c_ffn_bwd(const void *dout, const void *z, const float *stats, const float *gamma, float dropout_rate, uint64_t seed,
-                           const void *H, int ldh, const void *X, int ldx, const void *W2c, int ldw2, const void *W1c, int ldw1,
-                           int F, int Fp, void *dX, int ldo, float *dW1, int ld_dw1, float *db1, float *dW2, int ld_dw2, float *db2,
-                           float *dgamma, float *dbeta, int64_t M, void *workspace, int64_t workspace_bytes, void *stream) {
-    B4C_REQUIRE(dout && z && stats && gamma && H && X && W2c && W1c && dX && dW1 && dW2 && dgamma && dbeta && workspace,
-                "ffn_bwd: null pointer");
-    B4C_REQUIRE(M > 0 && F > 0 && F <= Fp && Fp <= 128 && Fp % 8 == 0, "ffn_bwd: hidden width %d (padded %d): 1..128, padded to a multiple of 8", F, Fp);
-    B4C_REQUIRE(ldh >= Fp && ldx >= 128 && ldw2 >= 128 && ldw1 >= Fp && ldo >= 128 && ld_dw1 >= F && ld_dw2 >= 128, "ffn_bwd: shape");
-    B4C_REQUIRE(ldh % 8 == 0 && ldx % 8 == 0 && ldw2 % 8 == 0 && ldw1 % 8 == 0 && ldo % 8 == 0 &&
-                ((((uintptr_t)dout | (uintptr_t)z | (uintptr_t)H | (uintptr_t)X | (uintptr_t)W2c | (uintptr_t)W1c | (uintptr_t)dX |
-                   (uintptr_t)gamma | (uintptr_t)workspace) & 15) == 0) && (((uintptr_t)stats & 7) == 0),
-                "ffn_bwd: operands must be 16-byte aligned with pitches % 8 == 0");
-    B4C_REQUIRE(dropout_rate >= 0.f && dropout_rate < 1.f, "ffn_bwd: dropout rate");
-    B4C_REQUIRE(M >= 2 && M < ((int64_t)1 << 24), "ffn_bwd: %lld rows (the row chunks are addressed with 32-bit byte offsets: < 16,777,216)", (long long)M);
-    B4C_REQUIRE(workspace_bytes >= b4c_ffn_bwd_workspace_bytes(M), "ffn_bwd: workspace too small");
-    FfnBwdArgs a = {};
+extern "C" int b4c_ffn_act_bwd(const void *dout, const void *z, const float *stats, const float *gamma, float dropout_rate, uint64_t seed,
+                               int act, const void *H, int ldh, const void *U, int ldu, const void *X, int ldx, const void *W2c, int ldw2,
+                               const void *W1c, int ldw1, int F, int Fp, void *dX, int ldo, float *dW1, int ld_dw1, float *db1,
+                               float *dW2, int ld_dw2, float *db2, float *dgamma, float *dbeta, int64_t M, void *workspace,
+                               int64_t workspace_bytes, void *stream) {
+    B4C_REQUIRE(dout && z && stats && gamma && H && U && X && W2c && W1c && dX && dW1 && dW2 && dgamma && dbeta && workspace,
+                "ffn_act_bwd: null pointer");
+    B4C_REQUIRE(act == B4C_ACT_GELU || act == B4C_ACT_GELU_TANH, "ffn_act_bwd: act %d (B4C_ACT_GELU or B4C_ACT_GELU_TANH; b4c_ffn_bwd is the ReLU kernel)", act);
+    B4C_REQUIRE(M > 0 && F > 0 && F <= Fp && Fp <= 128 && Fp % 8 == 0, "ffn_act_bwd: hidden width %d (padded %d): 1..128, padded to a multiple of 8", F, Fp);
+    B4C_REQUIRE(ldh >= Fp && ldu >= Fp && ldx >= 128 && ldw2 >= 128 && ldw1 >= Fp && ldo >= 128 && ld_dw1 >= F && ld_dw2 >= 128, "ffn_act_bwd: shape");
+    B4C_REQUIRE(ldh % 8 == 0 && ldu % 8 == 0 && ldx % 8 == 0 && ldw2 % 8 == 0 && ldw1 % 8 == 0 && ldo % 8 == 0 &&
+                ((((uintptr_t)dout | (uintptr_t)z | (uintptr_t)H | (uintptr_t)U | (uintptr_t)X | (uintptr_t)W2c | (uintptr_t)W1c |
+                   (uintptr_t)dX | (uintptr_t)gamma | (uintptr_t)workspace) & 15) == 0) && (((uintptr_t)stats & 7) == 0),
+                "ffn_act_bwd: operands must be 16-byte aligned with pitches % 8 == 0");
+    B4C_REQUIRE(dropout_rate >= 0.f && dropout_rate < 1.f, "ffn_act_bwd: dropout rate");
+    B4C_REQUIRE(M >= 2 && M < ((int64_t)1 << 24), "ffn_act_bwd: %lld rows (the row chunks are addressed with 32-bit byte offsets: < 16,777,216)", (long long)M);
+    B4C_REQUIRE(workspace_bytes >= b4c_ffn_bwd_workspace_bytes(M), "ffn_act_bwd: workspace too small");
+    FfnActBwdArgs a = {};
     a.dOut = (const bf16_t *)dout; a.Z = (const bf16_t *)z; a.stats = stats; a.gamma = gamma;
     a.H = (const bf16_t *)H; a.X = (const bf16_t *)X; a.W2c = (const bf16_t *)W2c; a.W1c = (const bf16_t *)W1c; a.dX = (bf16_t *)dX;
     a.part = (float *)workspace;
     a.ldh = ldh; a.ldx = ldx; a.ldw2 = ldw2; a.ldw1 = ldw1; a.ldo = ldo; a.Fp = Fp;
     a.rate = dropout_rate; a.seed = seed; a.M = M;
-#ifdef DD_EXPERIMENT
-    { static const char *e = getenv("B4C_FFN_DEBUG"); a.debug = e ? atoi(e) : 3; }
-#endif
-    FfnBwdOut out = {dW2, dW1, db2, db1, dgamma, dbeta, ld_dw2, ld_dw1, F};
-    const int grid = ffn_bwd_grid(M);
-    const size_t lds = DD_RING * (size_t)2 * DD_SUB + 2 * DD_SUB + DD_TOK * FB_OSTR + 3 * 8192;
-    b4c_allow_lds(ffn_bwd_kernel, lds);
+    a.U = (const bf16_t *)U; a.ldu = ldu;
+    // one persistent workgroup per CU, every workgroup has at least one tile: b4c_ffn_bwd's grid, which sized the workspace
+    const int64_t ntiles = (M + DD_TOK - 1) / DD_TOK;
+    const int grid = (int)(ntiles < 256 ? ntiles : 256);
     hipStream_t st = (hipStream_t)stream;
-    ffn_bwd_kernel<<<grid, 512, lds, st>>>(a);
-    ffn_bwd_reduce_kernel<<<FB_ROWS * 128 / 32, 256, 0, st>>>(a.part, grid, out);
-    return b4c_check_launch("ffn_bwd");
+    if (act == B4C_ACT_GELU) ffn_act_bwd_launch<B4C_ACT_GELU>(a, grid, st);
+    else ffn_act_bwd_launch<B4C_ACT_GELU_TANH>(a, grid, st);
+    ffn_bwd_reduce(a.part, grid, dW2, ld_dw2, dW1, ld_dw1, db2, db1, dgamma, dbeta, F, st);
+    return b4c_check_launch("ffn_act_bwd");
 }

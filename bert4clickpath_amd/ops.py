@@ -690,6 +690,45 @@ def ffn_fwd(x, wt1, b1, wt2, b2, gamma, beta, F, Fp, rate, seed, save=True):
     return h, z, out, stats
 
 
+# ---- the fused feed-forward kernels for a GELU block (csrc/ffn_act_fwd.hip, ffn_act_bwd.hip).  Off by default: B4C_FUSED_FFN_GELU=1
+# sends a GELU block of the fused shape through them (where fused_ffn_fwd / fused_ffn_bwd allow the ReLU kernels); off, a GELU
+# block keeps gemm_nt_act + gemm_nt_add_ln forward and the five kernels backward.
+fused_ffn_gelu = os.environ.get('B4C_FUSED_FFN_GELU', '0') == '1'
+
+
+def ffn_act_fwd(x, wt1, b1, wt2, b2, gamma, beta, F, Fp, act, rate, seed, save=True):
+    """-> h [M, Fp], u (None unless save), z (None unless save), out, stats (None unless save) of
+    LayerNorm(x + dropout(act(x W1 + b1) W2 + b2)), act a GELU (b4c_ffn_act_fwd); u = x W1 + b1, h = act(u).  Operands as ffn_fwd."""
+    M = x.shape[0]
+    h = torch.empty(M, Fp, dtype=x.dtype, device=x.device)
+    u = torch.empty(M, Fp, dtype=x.dtype, device=x.device) if save else None
+    z = torch.empty(M, 128, dtype=x.dtype, device=x.device) if save else None
+    out = torch.empty(M, 128, dtype=x.dtype, device=x.device)
+    stats = torch.empty(M, 2, dtype=torch.float32, device=x.device) if save else None
+    with _record('ffn_act_fwd' if 2 * M >= rec_hints.get('token_rows', 0) else 'ffn_act_fwd_rows',
+                 M * ((128 * (3 if save else 2) + Fp * (2 if save else 1)) * 2 + (8 if save else 0)), 4 * M * 128 * Fp):
+        L.check(L.lib().b4c_ffn_act_fwd(_p(x), x.stride(0), _p(wt1), wt1.stride(0), _p(b1), _p(wt2), wt2.stride(0), _p(b2), _p(gamma),
+                                        _p(beta), F, Fp, act, _p(h), h.stride(0), _p(u), u.stride(0) if save else 0, _p(z), _p(out),
+                                        _p(stats), M, LN_EPS, rate, seed, _st()), 'ffn_act_fwd')
+    return h, u, z, out, stats
+
+
+def ffn_act_bwd(dout, z, stats, gamma, rate, seed, act, h, u, x, wc2, wc1, F, dW1, db1, dW2, db2, dgamma, dbeta):
+    """dX of a GELU feed-forward block; dW1 / db1 / dW2 / db2 / dgamma / dbeta += (b4c_ffn_act_bwd).  u: the saved pre-activation;
+    the other operands as ffn_bwd."""
+    M, Fp = x.shape[0], h.shape[1]
+    dx = torch.empty(M, 128, dtype=x.dtype, device=x.device)
+    ws = _workspace('ffn_bwd', x.device, L.lib().b4c_ffn_bwd_workspace_bytes(M))
+    es = 2
+    with _record('ffn_act_bwd' if 2 * M >= rec_hints.get('token_rows', 0) else 'ffn_act_bwd_rows', M * ((4 * 128 + 2 * Fp) * es + 8),
+                 8 * M * 128 * Fp):
+        L.check(L.lib().b4c_ffn_act_bwd(_p(dout), _p(z), _p(stats), _p(gamma), rate, seed, act, _p(h), h.stride(0), _p(u), u.stride(0),
+                                        _p(x), x.stride(0), _p(wc2), wc2.stride(0), _p(wc1), wc1.stride(0), F, Fp, _p(dx), dx.stride(0),
+                                        _p(dW1), dW1.stride(0), _p(db1), _p(dW2), dW2.stride(0), _p(db2), _p(dgamma), _p(dbeta),
+                                        M, ws.data_ptr(), ws.numel(), _st()), 'ffn_act_bwd')
+    return dx
+
+
 # ---- the attention block's tail in one pass (csrc/attn_out_bwd.hip): LayerNorm + dropout backward and the output projection's dX /
 # dW / db.  B4C_FUSED_ATTN_OUT_BWD=0 keeps add_ln_bwd + the projection's own kernels.
 fused_attn_out_bwd = os.environ.get('B4C_FUSED_ATTN_OUT_BWD', '1') != '0'
@@ -2261,7 +2300,8 @@ class MQAttnBlockFn(torch.autograd.Function):
 class FFNBlockFn(torch.autograd.Function):
     """R9 + second half of R10: LN2(x + drop(act(x W1 + b1) W2 + b2)), act = relu (the reference) or a GELU (`act`: B4C_ACT_*,
     no reference counterpart).  A GELU block saves the pre-activation u beside h = gelu(u) -- one GEMM launch writes both --
-    and its backward gates with gelu'(u); the fused kernels (b4c_ffn_fwd / b4c_ffn_bwd) are ReLU kernels and are not taken."""
+    and its backward gates with gelu'(u); the fused kernels b4c_ffn_fwd / b4c_ffn_bwd are ReLU kernels and are not taken.  With
+    `fused_ffn_gelu` (off by default) a GELU block of the fused shape takes b4c_ffn_act_fwd / b4c_ffn_act_bwd instead."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, gamma, beta, pk1, pk2, rate, seed, training, act=L.ACT_RELU):
@@ -2271,11 +2311,15 @@ class FFNBlockFn(torch.autograd.Function):
         wt2, _, bb2 = pk2.get(x.dtype, Fp, training)
         relu = act == L.ACT_RELU
         # a GELU block in training: the pre-activation leaves the first GEMM beside h (inference saves nothing extra)
-        u = torch.empty(T_tok, Fp, dtype=x.dtype, device=x.device) if (training and not relu) else None
+        fused_act = not relu and fused_ffn_gelu
         if relu and fused_ffn_fwd and ffn_fwd_supported(x, Fp):
             h, z, out, stats = ffn_fwd(x, wt1, bb1, wt2, bb2, gamma.detach(), beta.detach(), pk1.N, Fp, rate if training else 0.0, seed,
                                        save=training)
+        elif fused_act and fused_ffn_fwd and ffn_fwd_supported(x, Fp):
+            h, u, z, out, stats = ffn_act_fwd(x, wt1, bb1, wt2, bb2, gamma.detach(), beta.detach(), pk1.N, Fp, act,
+                                              rate if training else 0.0, seed, save=training)
         else:
+            u = torch.empty(T_tok, Fp, dtype=x.dtype, device=x.device) if (training and not relu) else None
             h = gemm_nt(x, wt1, Fp, bb1, act=act, pre=u)
             z, out, stats = _residual_ln_fwd(h, wt2, bb2, x, gamma, beta, rate, seed, training)
         if training:
@@ -2287,7 +2331,7 @@ class FFNBlockFn(torch.autograd.Function):
             # A model of the fused kernels' shape runs the head's dW sweep in the foreground (_background_dw_for) -- decided by the
             # SHAPE, whatever the batch's row count, so that it agrees with background_dw_expected(), by which callers order their
             # gradient arenas (a background sweep's gradient completes last and belongs to the reducer's last bucket)
-            if relu and fused_ffn_bwd and ffn_bwd_shape_ok(x, h, z):
+            if (relu or fused_act) and fused_ffn_bwd and ffn_bwd_shape_ok(x, h, z):
                 actx = arena_context(w1, b1, w2, b2, gamma, beta)
                 if actx is not None:
                     actx.fused_blocks = True
@@ -2307,6 +2351,11 @@ class FFNBlockFn(torch.autograd.Function):
         _, wc2, _ = pk2.get(x.dtype, Fp, True)
         if relu and _arena_routes(actx) and fused_ffn_bwd and ffn_bwd_supported(x, h, z):
             dx = ffn_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, h, x, wc2, wc1, pk1.N, gw1, gb1, gw2, gb2, ggam, gbet)
+            _ready(w1, b1, w2, b2, gam, bet)
+            return sink_returns(ctx, (dx,), actx, sinks)
+        if not relu and fused_ffn_gelu and _arena_routes(actx) and fused_ffn_bwd and ffn_bwd_supported(x, h, z):
+            dx = ffn_act_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, ctx.act, h, ctx.saved_tensors[5], x, wc2, wc1,
+                             pk1.N, gw1, gb1, gw2, gb2, ggam, gbet)
             _ready(w1, b1, w2, b2, gam, bet)
             return sink_returns(ctx, (dx,), actx, sinks)
         dz, dy, _, _ = add_dropout_layernorm_bwd(dout.contiguous(), z, stats, gamma.detach(), rate, seed, into=(ggam, gbet))
@@ -2390,10 +2439,12 @@ overlap_vocab_dw = {'1': True, '0': False}.get(os.environ.get('B4C_OVERLAP_DW', 
 
 def background_dw_expected(d_model, dff, dtype, ffn_activation='relu'):
     """Will a model of this shape run the vocabulary head's dW sweep as a background job (see overlap_vocab_dw)?
-    (The fused feed-forward backward is a ReLU kernel: a GELU model never takes it and keeps the background sweep.)"""
+    (b4c_ffn_bwd is a ReLU kernel: a GELU model takes a fused backward, b4c_ffn_act_bwd, only with `fused_ffn_gelu`, which is off
+    by default, and otherwise keeps the background sweep.)"""
     if overlap_vocab_dw is not None:
         return overlap_vocab_dw
-    return not (fused_ffn_bwd and d_model == 128 and dff <= 128 and dtype == torch.bfloat16 and ffn_activation == 'relu')
+    return not (fused_ffn_bwd and d_model == 128 and dff <= 128 and dtype == torch.bfloat16 and
+                (ffn_activation == 'relu' or fused_ffn_gelu))
 
 
 def _background_dw_for(actx):

@@ -242,6 +242,27 @@ int b4c_ffn_fwd(const void *X, int ldx, const void *W1t, int ldw1, const float *
                 const float *gamma, const float *beta, int F, int Fp, void *H, int ldh, void *Z, void *Out, float *stats,
                 int64_t M, float eps, float dropout_rate, uint64_t seed, void *stream);
 
+/* (ABI 12, additive) b4c_ffn_fwd / b4c_ffn_bwd for a feed-forward block with a GELU activation: act = B4C_ACT_GELU or
+ * B4C_ACT_GELU_TANH, anything else is refused (B4C_ACT_RELU is b4c_ffn_fwd / b4c_ffn_bwd).  Every other argument, the shapes they
+ * take (bf16, d_model = 128, F <= 128; backward 2 <= M < 2^24) and the accumulate-into-gradients contract are those of the ReLU pair.
+ * Both round where b4c_gemm_nt_act's bf16 epilogue rounds (the fp32 sum to bf16, the rest in fp32, the result to bf16), so that a
+ * model computes the same step on either route, up to the order of the fp32 sums.
+ * Forward:   u = bf16(X W1) + b1;   H = bf16(act(u)) [M][ldh],   U = bf16(u) [M][ldu] (Fp stored columns each): C and `pre` of
+ *   b4c_gemm_nt_act;   Z, Out, stats those of b4c_gemm_nt_add_ln (y = bf16(bf16(H W2) + b2)).  U is required when Z is given (a training call: GELU is not monotone, the
+ *   backward pass gates with act'(u)) and may be NULL at inference (Z NULL), which then writes neither.
+ * Backward:  dh = bf16(bf16(dy W2c^T) * act'(U)): C of b4c_gemm_nt_act(gate = U, gate_act = act);   dW2 += H^T dy as before: it
+ *   reads both H and U, 1,240 + 2 Fp B per token.  Memory past a row's Fp columns of H or U (a pitch above Fp) is never used,
+ *   whatever it holds.  workspace: b4c_ffn_bwd_workspace_bytes(M). */
+int b4c_ffn_act_fwd(const void *X, int ldx, const void *W1t, int ldw1, const float *b1, const void *W2t, int ldw2,
+                    const float *b2, const float *gamma, const float *beta, int F, int Fp, int act, void *H, int ldh,
+                    void *U, int ldu, void *Z, void *Out, float *stats, int64_t M, float eps, float dropout_rate,
+                    uint64_t seed, void *stream);
+int b4c_ffn_act_bwd(const void *dout, const void *z, const float *stats, const float *gamma, float dropout_rate, uint64_t seed,
+                    int act, const void *H, int ldh, const void *U, int ldu, const void *X, int ldx, const void *W2c, int ldw2,
+                    const void *W1c, int ldw1, int F, int Fp, void *dX, int ldo, float *dW1, int ld_dw1, float *db1,
+                    float *dW2, int ld_dw2, float *db2, float *dgamma, float *dbeta, int64_t M, void *workspace,
+                    int64_t workspace_bytes, void *stream);
+
 /* several dW problems over the SAME M tokens in one launch (bf16; the four weight gradients of an encoder layer):
  * the ~256 workgroups of the split are shared by all problems, so every output tile has ~256 / (total tiles)
  * partial sums, and the group needs one main + one reduce kernel.  Problem i: dW_i[K][n_seg * seg_width] split into
