@@ -7,6 +7,8 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('B4C_LIB_PATH') or os.path.join(_HERE, 'libb4c_hip.so')     # override: A/B of two builds (scratch)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')
+# extension headers: further entry points of the same ABI in files of their own, which b4c.h includes (a C caller includes b4c.h alone)
+EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_ex.h'),)
 
 
 class B4CError(RuntimeError):
@@ -79,8 +81,8 @@ def parse_header(src):
 
 
 def header_constants(src):
-    """{name: value} of the header's integer #defines (B4C_F32, B4C_MAX_TOPK, B4C_EINVAL, ...)"""
-    return {k: int(v) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(B4C_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$', src, flags=re.M)}
+    """{name: value} of the header's integer #defines (B4C_F32, B4C_MAX_TOPK, B4C_EINVAL, B4C_ATTN_CAUSAL 1u, ...)"""
+    return {k: int(v) for k, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(B4C_\w+)[ \t]+\(?(-?\d+)[uU]?\)?[ \t]*$', src, flags=re.M)}
 
 
 def signatures(header_path=HEADER_PATH):
@@ -92,7 +94,18 @@ def declared_symbols(header_path=HEADER_PATH):
     return sorted(signatures(header_path))
 
 
-_C = header_constants(_header_text(HEADER_PATH))
+def all_signatures():
+    """signatures() of include/b4c.h and of every extension header it includes: what lib() binds.  A name declared twice raises."""
+    table = signatures()
+    for path in EXT_HEADER_PATHS:
+        for name, sig in signatures(path).items():
+            if name in table:
+                raise B4CError('%s declares %s, which another header of the ABI declares too' % (path, name))
+            table[name] = sig
+    return table
+
+
+_C = header_constants(''.join(_header_text(p) for p in (HEADER_PATH,) + EXT_HEADER_PATHS))
 ABI_VERSION = _C['B4C_ABI_VERSION']       # b4c_abi_version() of the library must agree
 F32, BF16 = _C['B4C_F32'], _C['B4C_BF16']
 ACT_NONE, ACT_RELU = _C['B4C_ACT_NONE'], _C['B4C_ACT_RELU']
@@ -101,6 +114,7 @@ CE_TF, CE_PLAIN = _C['B4C_CE_TF'], _C['B4C_CE_PLAIN']
 MAX_FEATURES, MAX_TOPK = _C['B4C_MAX_FEATURES'], _C['B4C_MAX_TOPK']
 MAX_EXCL, MAX_CAND = _C['B4C_MAX_EXCL'], _C['B4C_MAX_CAND']
 GRAD_CHUNK, GRAD_GROUP = _C['B4C_GRAD_CHUNK'], _C['B4C_GRAD_GROUP']
+ATTN_CAUSAL = _C['B4C_ATTN_CAUSAL']       # flag bit of the b4c_attn_*_ex entry points
 
 _lib = None
 
@@ -122,7 +136,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        sig = signatures()
+        sig = all_signatures()
         # The argument lists of the header belong to ONE ABI version: a library that exports the same names with older lists would
         # take a device pointer for a stream and fault on the GPU.  Compare before anything is bound.
         try:

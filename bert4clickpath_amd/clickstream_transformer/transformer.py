@@ -55,6 +55,15 @@ def _attention_rate(rate):
     return rate
 
 
+ATTENTION_KINDS = ('bidirectional', 'causal')
+
+
+def _attention_kind(attention):
+    if attention not in ATTENTION_KINDS:
+        raise ValueError("attention must be 'bidirectional' or 'causal', got %r" % (attention,))
+    return attention
+
+
 def create_segment_markers(seq, sep=SEP):
     """Cumulative count of SEP tokens along axis 1 (reference transformer.py:6-34; unused on the hot path)."""
     return torch.cumsum((seq == sep).to(torch.int32), dim=1)
@@ -64,6 +73,13 @@ def create_padding_mask(seq):
     """float32 (B,1,1,S) mask, 1 where the id is the pad id (reference transformer.py:38-41).
     The hot path carries the same information as one byte per token from the embedding kernel."""
     return (seq == INPUT_PAD).to(torch.float32)[:, None, None, :]
+
+
+def create_look_ahead_mask(size):
+    """float32 (size, size) mask, 1 above the diagonal: position q may not look at the positions after q (the reference family's
+    helper; the reference's scaled_dot_product_attention documents the mask kind, its encoder never builds one).  The kernels
+    never read such a matrix: `causal=True` / attention='causal' is this mask."""
+    return torch.triu(torch.ones(size, size, dtype=torch.float32), diagonal=1)
 
 
 _pe_cache = {}
@@ -97,8 +113,9 @@ def _key_mask_bytes(mask, B, Sk, device):
     if mask is None:
         return ops.zeros(B, Sk, dtype=torch.uint8, device=device)
     if mask.numel() != B * Sk:
-        raise B4CError('MI355X build: attention masks are key-side padding masks of %d x %d elements, got shape %s'
-                       % (B, Sk, tuple(mask.shape)))
+        raise B4CError('MI355X build: attention masks are key-side padding masks of %d x %d elements, got shape %s; '
+                       'a look-ahead mask is the argument causal=True (with the padding mask as `mask`), other (Sq, Sk) masks '
+                       'are not supported' % (B, Sk, tuple(mask.shape)))
     return (mask.reshape(B, Sk) != 0).to(torch.uint8).contiguous()
 
 
@@ -109,10 +126,22 @@ def _pad_rows(x, S):
     return torch.nn.functional.pad(x, (0, 0, 0, S - x.shape[1]))
 
 
-def scaled_dot_product_attention(q, k, v, mask=None, return_weights=False):
+def _causal_kw(causal, Sq, Sk):
+    """keywords of a causal launch ({} for a bidirectional one: the calls it has always made)"""
+    if not causal:
+        return {}
+    if Sq != Sk:
+        raise ValueError('causal attention needs queries and keys of one length (Sq = %d, Sk = %d)' % (Sq, Sk))
+    return {'causal': True}
+
+
+def scaled_dot_product_attention(q, k, v, mask=None, return_weights=False, causal=False):
     """q: (B, H, Sq, depth), k / v: (B, H, Sk, depth) on the HIP device -> (output (B,H,Sq,depth), weights).
     The attention-weight matrix (B,H,Sq,Sk) is materialised only with return_weights=True (the reference returns it
-    and its only caller discards it, transformer.py:203); otherwise the second result is None."""
+    and its only caller discards it, transformer.py:203); otherwise the second result is None.
+    mask: the key-side padding mask.  causal=True is the reference's look-ahead mask (create_look_ahead_mask(Sq)) on top of it:
+    query q sees keys 0 .. q only (Sq == Sk, otherwise ValueError); the returned weights are zero above the diagonal."""
+    ckw = _causal_kw(causal, q.shape[2], k.shape[2])
     ops._cuda(q, k, v)
     B, H, Sq, dh = q.shape
     Sk = k.shape[2]
@@ -122,8 +151,8 @@ def scaled_dot_product_attention(q, k, v, mask=None, return_weights=False):
         key_pad = torch.nn.functional.pad(key_pad, (0, S - Sk), value=1)
     pack = torch.cat([_pad_rows(t.permute(0, 2, 1, 3).reshape(B, -1, H * dh), S).reshape(B * S, H * dh) for t in (q, k, v)],
                      dim=1).contiguous()
-    o, lse = ops.attn_fwd(pack, key_pad, B, S, H, dh)
-    w = ops.attn_weights(pack, key_pad, lse, B, S, H, dh)[:, :, :Sq, :Sk] if return_weights else None
+    o, lse = ops.attn_fwd(pack, key_pad, B, S, H, dh, **ckw)
+    w = ops.attn_weights(pack, key_pad, lse, B, S, H, dh, **ckw)[:, :, :Sq, :Sk] if return_weights else None
     return o.view(B, S, H, dh)[:, :Sq].permute(0, 2, 1, 3), w
 
 
@@ -161,11 +190,14 @@ class MultiHeadAttention(nn.Module):
     def get_config(self):
         return {'d_model': self.d_model, 'num_heads': self.num_heads}
 
-    def forward(self, v, k, q, mask, return_weights=False):
+    def forward(self, v, k, q, mask, return_weights=False, causal=False):
         """call(v, k, q, mask) of the reference (:137-160): q (B, Sq, d), k / v (B, Sk, d), key-side padding mask
         ((B,1,1,Sk) float, 1 = pad, or (B,Sk) bytes) -> (output (B, Sq, d), attention weights (B, H, Sq, Sk) or None).
         Differentiable; the weights are materialised only on request (the encoder discards them, :203).
-        Sequences of different length are padded to the longer one (pad keys masked, pad queries dropped)."""
+        Sequences of different length are padded to the longer one (pad keys masked, pad queries dropped).
+        causal=True: the look-ahead mask on top of the padding mask (Sq == Sk, otherwise ValueError); the weights are zero above
+        the diagonal."""
+        ckw = _causal_kw(causal, q.shape[1], k.shape[1])
         ops._cuda(v, k, q)
         B, Sq, d = q.shape
         Sk = k.shape[1]
@@ -181,7 +213,7 @@ class MultiHeadAttention(nn.Module):
         xv = xq if same else (xk if v is k else _pad_rows(v, S).reshape(B * S, d))
         out, w = ops.MHAFn.apply(xq, xk, xv, key_pad, self.wq.kernel, self.wq.bias, self.wk.kernel, self.wk.bias,
                                  self.wv.kernel, self.wv.bias, self.dense.kernel, self.dense.bias, self._pk_qkv, self._pk_o,
-                                 B, S, self.num_heads, same, bool(return_weights))
+                                 B, S, self.num_heads, same, bool(return_weights), *([True] if ckw else []))
         out = out.view(B, S, d)[:, :Sq]
         return out, (w[:, :, :Sq, :Sk] if return_weights else None)
 
@@ -218,12 +250,16 @@ class EncoderLayer(nn.Module):
     Runs as two fused autograd blocks of HIP kernels.
     attention_dropout_rate (BERT's attention_probs_dropout_prob; no reference counterpart): dropout on the attention
     probabilities inside the attention kernels, in training only.  Its seed is a THIRD draw from dropout_seeds, taken after the
-    two of the residual branches and only when the rate is > 0: at rate 0 the seed stream is what it always was."""
+    two of the residual branches and only when the rate is > 0: at rate 0 the seed stream is what it always was.
+    attention ('bidirectional' | 'causal'; no reference counterpart): 'causal' is left-to-right self-attention inside the kernels,
+    position q attends to positions 0 .. q only (the position in the dense layout, the row inside the sequence in the packed one)."""
 
-    def __init__(self, d_model, num_heads, dff, rate=0.1, ffn_activation='relu', attention_dropout_rate=0.0, **kwargs):
+    def __init__(self, d_model, num_heads, dff, rate=0.1, ffn_activation='relu', attention_dropout_rate=0.0,
+                 attention='bidirectional', **kwargs):
         super().__init__()
         self.d_model, self.num_heads, self.dff, self.rate = d_model, num_heads, dff, rate
         self.ffn_activation = ffn_activation
+        self.attention = _attention_kind(attention)
         self.attention_dropout_rate = _attention_rate(attention_dropout_rate)
         self.mha = MultiHeadAttention(d_model, num_heads)
         self.ffn = point_wise_feed_forward_network(d_model, dff, ffn_activation)
@@ -233,7 +269,8 @@ class EncoderLayer(nn.Module):
     def get_config(self):
         return {'d_model': self.d_model, 'num_heads': self.num_heads, 'dff': self.dff, 'rate': self.rate,
                 **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
-                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {})}
+                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {}),
+                **({'attention': self.attention} if self.attention != 'bidirectional' else {})}
 
     def forward(self, x, training=None, mask=None, packed=None, rows=None):
         """x (B, S, d); or, with `packed` (ops.Packed), the (1, T, d) rows of the real tokens only and mask = the (T,) key
@@ -262,6 +299,9 @@ class EncoderLayer(nn.Module):
         s3 = dropout_seeds.next() if a_rate > 0 else 0
         need_tape = training or torch.is_grad_enabled()
         if rows is not None:
+            if self.attention == 'causal':
+                raise B4CError('the masked-query last layer (rows=) has no causal form: evaluate the full layer of a causal '
+                               'encoder and gather its rows (Encoder.rows_supported(dtype, training))')
             if a_rate > 0 and not ops.mq_attn_dropout:
                 raise B4CError('the masked-query last layer (rows=) has no attention dropout: evaluate the full layer while '
                                'training with attention_dropout_rate > 0 (Encoder.rows_supported(dtype, training))')
@@ -279,7 +319,7 @@ class EncoderLayer(nn.Module):
             out1 = ops.AttnBlockFn.apply(x2, key_pad, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel, m.wv.bias,
                                          m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
                                          m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape, cu,
-                                         a_rate, s3)
+                                         a_rate, s3, *([True] if self.attention == 'causal' else []))
         out2 = ops.FFNBlockFn.apply(out1, f[0].kernel, f[0].bias, f[1].kernel, f[1].bias, self.layernorm2.gamma,
                                     self.layernorm2.beta, f._pk1, f._pk2, self.rate if training else 0.0, s2, need_tape, f.act)
         return out2 if rows is not None else out2.view(out_shape)      # rows: (R, d) as the blocks leave it
@@ -291,21 +331,23 @@ class Encoder(nn.Module):
     an Encoder called on its own applies it with the stand-alone dropout kernel (same keep-mask generator)."""
 
     def __init__(self, num_layers, d_model, num_heads, dff, dropout_rate, ffn_activation='relu', attention_dropout_rate=0.0,
-                 **kwargs):
+                 attention='bidirectional', **kwargs):
         super().__init__()
         self.num_layers, self.d_model, self.num_heads, self.dff, self.dropout_rate = \
             num_layers, d_model, num_heads, dff, dropout_rate
         ops.ffn_act_code(ffn_activation)        # (ValueError also for an encoder of no layers)
         self.ffn_activation = ffn_activation
         self.attention_dropout_rate = _attention_rate(attention_dropout_rate)
+        self.attention = _attention_kind(attention)
         self.enc_layers = nn.ModuleList([EncoderLayer(d_model, num_heads, dff, dropout_rate, ffn_activation,
-                                                      self.attention_dropout_rate) for _ in range(num_layers)])
+                                                      self.attention_dropout_rate, self.attention) for _ in range(num_layers)])
 
     def get_config(self):
         return {'num_layers': self.num_layers, 'd_model': self.d_model, 'num_heads': self.num_heads, 'dff': self.dff,
                 'dropout_rate': self.dropout_rate,
                 **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
-                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {})}
+                **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {}),
+                **({'attention': self.attention} if self.attention != 'bidirectional' else {})}
 
     def forward(self, inputs, training=None, mask=None, _input_dropout_done=False, packed=None, rows=None):
         """rows (see EncoderLayer.forward): the LAST layer is evaluated for those query rows only; returns (R, d)."""
@@ -320,8 +362,9 @@ class Encoder(nn.Module):
 
     def rows_supported(self, x_dtype, training=False):
         """The masked-query form of the last layer: head depth 32 / 64 (b4c_attn_mq_*), at least one layer.  Those kernels have no
-        attention dropout: a training pass with attention_dropout_rate > 0 takes the full last layer and gathers its rows."""
-        if not self.enc_layers or (training and self.attention_dropout_rate > 0):
+        attention dropout: a training pass with attention_dropout_rate > 0 takes the full last layer and gathers its rows.  They
+        have no causal form either: a causal encoder always takes the full last layer."""
+        if not self.enc_layers or self.attention == 'causal' or (training and self.attention_dropout_rate > 0):
             return False
         return (self.d_model // self.num_heads) in (32, 64) and self.d_model % 8 == 0
 
@@ -375,13 +418,15 @@ class Transformer(nn.Module):
     attention_dropout_rate: dropout on the attention probabilities (BERT's attention_probs_dropout_prob), in training only;
     embedding_layernorm=True: the input stage is drop(LayerNorm(scale * rows + PE)) with the parameters
     ``embedding_norm.gamma`` / ``.beta`` (eps 1e-6, as every LayerNormalization here); embedding_scale: a positive number in
-    place of sqrt(d_model) (None; the paper does not scale: 1.0)."""
+    place of sqrt(d_model) (None; the paper does not scale: 1.0); attention='causal': left-to-right self-attention in every layer
+    (SASRec, the paper's unidirectional arm) instead of 'bidirectional'."""
 
     def __init__(self, num_layers, num_attention_heads, embedding_sizes, embedding_dims, encoder_ff_dim, dropout_rate,
                  item_embedding_weights=None, compute_dtype=torch.float32, feature_combine='concat', ffn_activation='relu',
                  position_encoding='sinusoidal', max_positions=None, attention_dropout_rate=0.0, embedding_layernorm=False,
-                 embedding_scale=None, **kwargs):
+                 embedding_scale=None, attention='bidirectional', **kwargs):
         super().__init__()
+        self.attention = _attention_kind(attention)
         if embedding_scale is not None and not (isinstance(embedding_scale, numbers.Real) and not isinstance(embedding_scale, bool)
                                                 and 0 < float(embedding_scale) < float('inf')):
             raise ValueError('embedding_scale must be None (sqrt(d_model)) or a positive number, got %r' % (embedding_scale,))
@@ -419,7 +464,7 @@ class Transformer(nn.Module):
                 raise B4CError('MI355X build: embedding dim of feature %r is %d; must be a multiple of 8' % (f, dim))
         self.compute_dtype = compute_dtype
         self.encoder = Encoder(num_layers, self.d_model, num_attention_heads, encoder_ff_dim, dropout_rate, ffn_activation,
-                               self.attention_dropout_rate)
+                               self.attention_dropout_rate, self.attention)
         self.embedding_layers = _FeatureModules({f: _Embedding(int(embedding_sizes[f]), int(embedding_dims[f]))
                                                  for f in embedding_dims.keys()})
         if position_encoding == 'learned':
@@ -448,7 +493,8 @@ class Transformer(nn.Module):
                    if self.position_encoding == 'learned' else {}),
                 **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {}),
                 **({'embedding_layernorm': True} if self.embedding_layernorm else {}),
-                **({'embedding_scale': self.embedding_scale} if self.embedding_scale is not None else {})}
+                **({'embedding_scale': self.embedding_scale} if self.embedding_scale is not None else {}),
+                **({'attention': self.attention} if self.attention != 'bidirectional' else {})}
 
     @property
     def position_table(self):

@@ -33,7 +33,10 @@ __device__ __forceinline__ void stage_tile(const T *__restrict__ base, int ld, i
 
 // DROP (all three kernels): attention-probability dropout by the keep rule of common.h (b4c_attn_keep); q and k are the positions,
 // the pitch is S.  The DROP = false instantiations are the kernels without it.
-template <typename T, int DH, bool DROP>
+// CAUSAL (all three kernels; the CAUSAL = false instantiations are the kernels without it): key k is visible to query q iff k <= q.
+// The key loop (forward, dQ) or the query loop (dK / dV) is clamped at the diagonal: per workgroup for the staging (every thread
+// takes part in it), per thread for the arithmetic.  The dropout keep rule is untouched.
+template <typename T, int DH, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(256) attn_fwd_row_kernel(const T *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                            T *__restrict__ o, int ld_o, float *__restrict__ lse, int S, int H,
                                                            float sqrt_dk, float rate, uint64_t seed) {
@@ -53,14 +56,15 @@ __global__ void __launch_bounds__(256) attn_fwd_row_kernel(const T *__restrict__
     const uint32_t thr = DROP ? b4c_keep_threshold(rate) : 0u;
     const uint64_t drow = (uint64_t)blockIdx.y * S + (uint32_t)qi;
     uint32_t kb = 0;
-    for (int k0 = 0; k0 < S; k0 += ATT_TILE) {
+    const int k_end = CAUSAL ? min(S, (int)blockIdx.x * 256 + 256) : S;      // past the workgroup's last query nothing is visible
+    for (int k0 = 0; k0 < k_end; k0 += ATT_TILE) {
         __syncthreads();
         stage_tile<T, DH>(qkv, ld, tok0, k0, S, dm + h * DH, sK, tid);
         stage_tile<T, DH>(qkv, ld, tok0, k0, S, 2 * dm + h * DH, sV, tid);
         if (tid < ATT_TILE) sPad[tid] = (k0 + tid < S) ? key_pad[tok0 + k0 + tid] : 1;
         __syncthreads();
         if (!active) continue;
-        const int nk = min(ATT_TILE, S - k0);
+        const int nk = CAUSAL ? min(ATT_TILE, qi + 1 - k0) : min(ATT_TILE, S - k0);
         for (int j = 0; j < nk; ++j) {
             float s = dot_lds<DH>(q, &sK[j][0]) / sqrt_dk;
             if (sPad[j]) s += -1e9f;
@@ -97,7 +101,7 @@ __global__ void __launch_bounds__(256) attn_fwd_row_kernel(const T *__restrict__
 }
 
 // dQ: thread per query; also writes delta[q] = sum_d dO[q][d] * O[q][d]
-template <typename T, int DH, bool DROP>
+template <typename T, int DH, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                           const T *__restrict__ o, int ld_o, const T *__restrict__ d_o, int ld_do,
                                                           const float *__restrict__ lse, float *__restrict__ delta,
@@ -129,14 +133,15 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T *__restrict__ 
     const float inv_keep = DROP ? 1.0f / (1.0f - rate) : 1.0f;
     const uint64_t drow = (uint64_t)blockIdx.y * S + (uint32_t)qi;
     uint32_t kb = 0;
-    for (int k0 = 0; k0 < S; k0 += ATT_TILE) {
+    const int k_end = CAUSAL ? min(S, (int)blockIdx.x * 256 + 256) : S;
+    for (int k0 = 0; k0 < k_end; k0 += ATT_TILE) {
         __syncthreads();
         stage_tile<T, DH>(qkv, ld, tok0, k0, S, dm + h * DH, sK, tid);
         stage_tile<T, DH>(qkv, ld, tok0, k0, S, 2 * dm + h * DH, sV, tid);
         if (tid < ATT_TILE) sPad[tid] = (k0 + tid < S) ? key_pad[tok0 + k0 + tid] : 1;
         __syncthreads();
         if (!active) continue;
-        const int nk = min(ATT_TILE, S - k0);
+        const int nk = CAUSAL ? min(ATT_TILE, qi + 1 - k0) : min(ATT_TILE, S - k0);
         for (int j = 0; j < nk; ++j) {
             if (DROP && (j & 3) == 0) kb = b4c_attn_keep4(seed, b4c_attn_ctr(drow, k0 + j, S), thr);
             if (sPad[j]) continue;  // p == 0 exactly (exp(-1e9 - lse))
@@ -163,7 +168,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T *__restrict__ 
 }
 
 // dK, dV: thread per key; queries (q, dO, lse, delta) stream through LDS
-template <typename T, int DH, bool DROP>
+template <typename T, int DH, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                            const T *__restrict__ d_o, int ld_do, const float *__restrict__ lse,
                                                            const float *__restrict__ delta, T *__restrict__ dqkv, int ld_dq, int S,
@@ -184,7 +189,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T *__restrict__
         load_row<T, DH>(qkv + (tok0 + kj) * ld + dm + h * DH, k);
         load_row<T, DH>(qkv + (tok0 + kj) * ld + 2 * dm + h * DH, v);
     }
-    for (int q0 = 0; q0 < S; q0 += ATT_TILE) {
+    for (int q0 = CAUSAL ? (int)blockIdx.x * 256 : 0; q0 < S; q0 += ATT_TILE) {      // CAUSAL: no query before the workgroup's first key sees it
         __syncthreads();
         stage_tile<T, DH>(qkv, ld, tok0, q0, S, h * DH, sQ, tid);
         stage_tile<T, DH>(d_o, ld_do, tok0, q0, S, h * DH, sG, tid);
@@ -196,7 +201,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T *__restrict__
         __syncthreads();
         if (!active) continue;
         const int nq = min(ATT_TILE, S - q0);
-        for (int i = 0; i < nq; ++i) {
+        for (int i = CAUSAL ? max(0, kj - q0) : 0; i < nq; ++i) {
             const float s = dot_lds<DH>(k, &sQ[i][0]) / sqrt_dk;
             const float p = expf(s - sL[i]);
             float dp = dot_lds<DH>(v, &sG[i][0]);
@@ -235,10 +240,11 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T *__restrict__
 
 // bf16 MFMA forward/backward (attn_mfma.hip); return B4C_EUNSUPPORTED when the shape is not covered.
 int b4c_attn_fwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B, int S,
-                      int H, int dh, const int32_t *cu, float rate, uint64_t seed, hipStream_t st);
+                      int H, int dh, const int32_t *cu, float rate, uint64_t seed, bool causal, hipStream_t st);
 int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o, const void *d_o,
                       int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B, int S, int H, int dh,
-                      void *workspace, int64_t workspace_bytes, const int32_t *cu, float rate, uint64_t seed, hipStream_t st);
+                      void *workspace, int64_t workspace_bytes, const int32_t *cu, float rate, uint64_t seed, bool causal,
+                      hipStream_t st);
 int64_t b4c_attn_bwd_mfma_workspace_bytes(int B, int S, int H, int dh);
 
 // bf16 shapes the MFMA kernels do not cover (S > 512 or head depth 16 / 128) run on the fp32-math row kernels, which are
@@ -265,25 +271,29 @@ static int check_attn_rate(const char *who, float rate) {
 }
 
 // rate == 0 selects the DROP = false instantiations: the kernels of the entry points without dropout
-#define ATT_DISPATCH_DH(dh, KERNEL, T, DR, ...)                      \
+// and !causal the CAUSAL = false ones
+#define ATT_DISPATCH_DH(dh, KERNEL, T, DR, CA, ...)                  \
     switch (dh) {                                                    \
-        case 16: KERNEL<T, 16, DR> __VA_ARGS__; break;               \
-        case 32: KERNEL<T, 32, DR> __VA_ARGS__; break;               \
-        case 64: KERNEL<T, 64, DR> __VA_ARGS__; break;               \
-        default: KERNEL<T, 128, DR> __VA_ARGS__; break;              \
+        case 16: KERNEL<T, 16, DR, CA> __VA_ARGS__; break;           \
+        case 32: KERNEL<T, 32, DR, CA> __VA_ARGS__; break;           \
+        case 64: KERNEL<T, 64, DR, CA> __VA_ARGS__; break;           \
+        default: KERNEL<T, 128, DR, CA> __VA_ARGS__; break;          \
     }
+#define ATT_DISPATCH_DR(dh, KERNEL, T, CA, ...)                                              \
+    if (rate == 0.f) { ATT_DISPATCH_DH(dh, KERNEL, T, false, CA, __VA_ARGS__) }              \
+    else { ATT_DISPATCH_DH(dh, KERNEL, T, true, CA, __VA_ARGS__) }
 #define ATT_DISPATCH(dh, KERNEL, T, ...)                                                     \
-    if (rate == 0.f) { ATT_DISPATCH_DH(dh, KERNEL, T, false, __VA_ARGS__) }                  \
-    else { ATT_DISPATCH_DH(dh, KERNEL, T, true, __VA_ARGS__) }
+    if (!causal) { ATT_DISPATCH_DR(dh, KERNEL, T, false, __VA_ARGS__) }                      \
+    else { ATT_DISPATCH_DR(dh, KERNEL, T, true, __VA_ARGS__) }
 
 static int attn_fwd_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
-                        int S, int H, int dh, float rate, uint64_t seed, int dtype, void *stream) {
+                        int S, int H, int dh, float rate, uint64_t seed, bool causal, int dtype, void *stream) {
     B4C_REQUIRE(qkv && key_pad && o, "%s: null pointer", who);
     int rc = check_attn(who, ld_qkv, ld_o, B, S, H, dh);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == B4C_BF16) {
-        rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, nullptr, rate, seed, st);
+        rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, nullptr, rate, seed, causal, st);
         if (rc != B4C_EUNSUPPORTED) return rc;
         note_row_fallback(who, S, dh);
     }
@@ -300,14 +310,14 @@ static int attn_fwd_any(const char *who, const void *qkv, int ld_qkv, const uint
 
 extern "C" int b4c_attn_fwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
                             int S, int H, int dh, int dtype, void *stream) {
-    return attn_fwd_any("attn_fwd", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, 0.f, 0, dtype, stream);
+    return attn_fwd_any("attn_fwd", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, 0.f, 0, false, dtype, stream);
 }
 
 extern "C" int b4c_attn_fwd_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
                                  int S, int H, int dh, int dtype, void *stream, float dropout_rate, uint64_t seed) {
     int rc = check_attn_rate("attn_fwd_drop", dropout_rate);
     if (rc) return rc;
-    return attn_fwd_any("attn_fwd_drop", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, dropout_rate, seed, dtype, stream);
+    return attn_fwd_any("attn_fwd_drop", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, dropout_rate, seed, false, dtype, stream);
 }
 
 extern "C" int64_t b4c_attn_bwd_workspace_bytes(int B, int S, int H, int dh, int dtype) {
@@ -316,8 +326,8 @@ extern "C" int64_t b4c_attn_bwd_workspace_bytes(int B, int S, int H, int dh, int
 
 static int attn_bwd_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
                         const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B,
-                        int S, int H, int dh, void *workspace, int64_t workspace_bytes, float rate, uint64_t seed, int dtype,
-                        void *stream) {
+                        int S, int H, int dh, void *workspace, int64_t workspace_bytes, float rate, uint64_t seed, bool causal,
+                        int dtype, void *stream) {
     B4C_REQUIRE(qkv && key_pad && o && d_o && lse && delta && dqkv, "%s: null pointer", who);
     int rc = check_attn(who, ld_qkv, ld_o, B, S, H, dh);
     if (rc) return rc;
@@ -325,7 +335,7 @@ static int attn_bwd_any(const char *who, const void *qkv, int ld_qkv, const uint
     hipStream_t st = (hipStream_t)stream;
     if (dtype == B4C_BF16) {
         rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
-                               workspace_bytes, nullptr, rate, seed, st);
+                               workspace_bytes, nullptr, rate, seed, causal, st);
         if (rc != B4C_EUNSUPPORTED) return rc;
         note_row_fallback(who, S, dh);
     }
@@ -352,7 +362,7 @@ extern "C" int b4c_attn_bwd_ws(const void *qkv, int ld_qkv, const uint8_t *key_p
                                const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B,
                                int S, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype, void *stream) {
     return attn_bwd_any("attn_bwd", qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
-                        workspace_bytes, 0.f, 0, dtype, stream);
+                        workspace_bytes, 0.f, 0, false, dtype, stream);
 }
 
 extern "C" int b4c_attn_bwd_drop_ws(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
@@ -362,7 +372,7 @@ extern "C" int b4c_attn_bwd_drop_ws(const void *qkv, int ld_qkv, const uint8_t *
     int rc = check_attn_rate("attn_bwd_drop", dropout_rate);
     if (rc) return rc;
     return attn_bwd_any("attn_bwd_drop", qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
-                        workspace_bytes, dropout_rate, seed, dtype, stream);
+                        workspace_bytes, dropout_rate, seed, false, dtype, stream);
 }
 
 
@@ -371,20 +381,20 @@ extern "C" int b4c_attn_bwd_drop_ws(const void *qkv, int ld_qkv, const uint8_t *
 // packed layout exists for the throughput path, the fp32 parity path stays dense.  key_pad [total tokens]: all zeros unless
 // the caller keeps masked keys inside the packed rows.
 static int attn_fwd_varlen_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o,
-                               int ld_o, float *lse, int B, int max_len, int H, int dh, float rate, uint64_t seed, int dtype,
-                               void *stream) {
+                               int ld_o, float *lse, int B, int max_len, int H, int dh, float rate, uint64_t seed, bool causal,
+                               int dtype, void *stream) {
     B4C_REQUIRE(qkv && key_pad && cu_seqlens && o, "%s: null pointer", who);
     int rc = check_attn(who, ld_qkv, ld_o, B, max_len, H, dh);
     if (rc) return rc;
     B4C_REQUIRE(dtype == B4C_BF16, "%s: bf16 only", who);
-    rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, max_len, H, dh, cu_seqlens, rate, seed, (hipStream_t)stream);
+    rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, max_len, H, dh, cu_seqlens, rate, seed, causal, (hipStream_t)stream);
     B4C_REQUIRE(rc != B4C_EUNSUPPORTED, "%s: max_len %d / head depth %d outside the MFMA kernels (<= 512, 32 or 64)", who, max_len, dh);
     return rc;
 }
 
 extern "C" int b4c_attn_fwd_varlen(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
                                    float *lse, int B, int max_len, int H, int dh, int dtype, void *stream) {
-    return attn_fwd_varlen_any("attn_fwd_varlen", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, max_len, H, dh, 0.f, 0, dtype, stream);
+    return attn_fwd_varlen_any("attn_fwd_varlen", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, max_len, H, dh, 0.f, 0, false, dtype, stream);
 }
 
 extern "C" int b4c_attn_fwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o,
@@ -393,20 +403,20 @@ extern "C" int b4c_attn_fwd_varlen_drop(const void *qkv, int ld_qkv, const uint8
     int rc = check_attn_rate("attn_fwd_varlen_drop", dropout_rate);
     if (rc) return rc;
     return attn_fwd_varlen_any("attn_fwd_varlen_drop", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, max_len, H, dh, dropout_rate,
-                               seed, dtype, stream);
+                               seed, false, dtype, stream);
 }
 
 static int attn_bwd_varlen_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens,
                                const void *o, int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv,
                                int ld_dqkv, int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes, float rate,
-                               uint64_t seed, int dtype, void *stream) {
+                               uint64_t seed, bool causal, int dtype, void *stream) {
     B4C_REQUIRE(qkv && key_pad && cu_seqlens && o && d_o && lse && delta && dqkv, "%s: null pointer", who);
     int rc = check_attn(who, ld_qkv, ld_o, B, max_len, H, dh);
     if (rc) return rc;
     B4C_REQUIRE(dtype == B4C_BF16, "%s: bf16 only", who);
     B4C_REQUIRE(ld_do >= H * dh && ld_do % 8 == 0 && ld_dqkv >= 3 * H * dh && ld_dqkv % 8 == 0, "%s: bad pitch", who);
     rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, max_len, H, dh, workspace,
-                           workspace_bytes, cu_seqlens, rate, seed, (hipStream_t)stream);
+                           workspace_bytes, cu_seqlens, rate, seed, causal, (hipStream_t)stream);
     B4C_REQUIRE(rc != B4C_EUNSUPPORTED, "%s: shape outside the MFMA kernels, or workspace missing for max_len > 256", who);
     return rc;
 }
@@ -416,7 +426,7 @@ extern "C" int b4c_attn_bwd_varlen(const void *qkv, int ld_qkv, const uint8_t *k
                                    int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype,
                                    void *stream) {
     return attn_bwd_varlen_any("attn_bwd_varlen", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B,
-                               max_len, H, dh, workspace, workspace_bytes, 0.f, 0, dtype, stream);
+                               max_len, H, dh, workspace, workspace_bytes, 0.f, 0, false, dtype, stream);
 }
 
 extern "C" int b4c_attn_bwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, const void *o,
@@ -426,7 +436,42 @@ extern "C" int b4c_attn_bwd_varlen_drop(const void *qkv, int ld_qkv, const uint8
     int rc = check_attn_rate("attn_bwd_varlen_drop", dropout_rate);
     if (rc) return rc;
     return attn_bwd_varlen_any("attn_bwd_varlen_drop", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv,
-                               B, max_len, H, dh, workspace, workspace_bytes, dropout_rate, seed, dtype, stream);
+                               B, max_len, H, dh, workspace, workspace_bytes, dropout_rate, seed, false, dtype, stream);
+}
+
+// ---- one entry point per direction that takes everything (include/b4c_attn_ex.h): layout by cu_seqlens (NULL: dense), dropout by the
+// rate, causal masking by flags.  flags == 0 reaches exactly the launches of the entry points above.
+static int check_attn_flags(const char *who, uint32_t flags) {
+    B4C_REQUIRE((flags & ~B4C_ATTN_CAUSAL) == 0, "%s: unknown flag bits 0x%x", who, flags & ~B4C_ATTN_CAUSAL);
+    return B4C_OK;
+}
+
+extern "C" int b4c_attn_fwd_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
+                               float *lse, int B, int S, int H, int dh, int dtype, void *stream, float dropout_rate, uint64_t seed,
+                               uint32_t flags) {
+    int rc = check_attn_flags("attn_fwd_ex", flags);
+    if (!rc) rc = check_attn_rate("attn_fwd_ex", dropout_rate);
+    if (rc) return rc;
+    const bool causal = (flags & B4C_ATTN_CAUSAL) != 0;
+    if (cu_seqlens)
+        return attn_fwd_varlen_any("attn_fwd_ex", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, S, H, dh, dropout_rate, seed, causal,
+                                   dtype, stream);
+    return attn_fwd_any("attn_fwd_ex", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, dropout_rate, seed, causal, dtype, stream);
+}
+
+extern "C" int b4c_attn_bwd_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, const void *o,
+                               int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv,
+                               int B, int S, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype, void *stream,
+                               float dropout_rate, uint64_t seed, uint32_t flags) {
+    int rc = check_attn_flags("attn_bwd_ex", flags);
+    if (!rc) rc = check_attn_rate("attn_bwd_ex", dropout_rate);
+    if (rc) return rc;
+    const bool causal = (flags & B4C_ATTN_CAUSAL) != 0;
+    if (cu_seqlens)
+        return attn_bwd_varlen_any("attn_bwd_ex", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B,
+                                   S, H, dh, workspace, workspace_bytes, dropout_rate, seed, causal, dtype, stream);
+    return attn_bwd_any("attn_bwd_ex", qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
+                        workspace_bytes, dropout_rate, seed, causal, dtype, stream);
 }
 
 // the keep rule of the *_drop entry points on the host (common.h: b4c_attn_keep_elem)

@@ -12,6 +12,9 @@
 // The v_mfma_f32_32x32x16_bf16 operand maps and the fragment helpers (rowmap, pack8, frag_tr, frag_from_2x8B) are mfma.h's.
 // DROP (template parameter; the DROP = false bodies are the kernels without it): attention-probability dropout by the keep rule
 // of common.h; the backward kernels build a tile's keep bits with keep_tile_bwd (mfma.h).
+// CAUSAL (template parameter; the CAUSAL = false bodies are the kernels without it): key k is visible to query q iff k <= q, both
+// counted inside the sequence.  Score tiles above the diagonal are never computed; the element mask (-inf in the forward, p = 0
+// in the backward) is applied in the diagonal tile only, behind a wave-uniform branch.  The dropout keep rule is untouched.
 #include <math.h>
 
 #include "mfma.h"
@@ -57,9 +60,16 @@ __device__ __forceinline__ void stage_transposed8(const bf16_t *__restrict__ src
 
 // ------------------------------------------------------------------------------------------
 // forward: 512 threads, wave w owns query tiles w, w + 8, ... (QPW of them: S <= 256 QPW; QPW = 2 covers S <= 512, where
-// the K / V images of one (sequence, head) take 147 KB of LDS and one workgroup runs per CU)
+// the K / V images of one (sequence, head) take 147 KB of LDS and one workgroup runs per CU).
+// CAUSAL with QPW = 2: wave w owns tiles w and 15 - w, 17 visible score tiles for every wave (w and w + 8 would be 2 w + 10).
 // ------------------------------------------------------------------------------------------
-template <int DH, int QPW, bool DROP>
+template <int QPW, bool CAUSAL> __device__ __forceinline__ int att_fwd_qtile(int wave, int qi) {
+    if (!CAUSAL) return wave + 8 * qi;
+    // (a scalar: the tile bounds the key loop and selects the diagonal branch, both uniform over the wave; as a vector value it cost
+    // the depth-32 QPW = 2 forms a wave of occupancy)
+    return __builtin_amdgcn_readfirstlane((QPW == 2 && qi == 1) ? 15 - wave : wave + 8 * qi);
+}
+template <int DH, int QPW, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(const bf16_t *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                             bf16_t *__restrict__ o, int ld_o, float *__restrict__ lse, int S_arg, int H,
                                                             float scale, const int32_t *__restrict__ cu, float rate, uint64_t seed) {
@@ -90,8 +100,8 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
     bf16x8 qf[QPW][NKS];
 #pragma unroll
     for (int qi = 0; qi < QPW; ++qi) {
-        const int qrow = (wave + 8 * qi) * 32 + r;
-        const bool qvalid = wave + 8 * qi < nkt && qrow < S;
+        const int qrow = att_fwd_qtile<QPW, CAUSAL>(wave, qi) * 32 + r;
+        const bool qvalid = att_fwd_qtile<QPW, CAUSAL>(wave, qi) < nkt && qrow < S;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             u32x4 v = {0u, 0u, 0u, 0u};
@@ -137,7 +147,14 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
     int any_live = 0;
 #pragma unroll
     for (int kt = 0; kt < ATT_MAX_KT * QPW; ++kt) any_live |= (kt < nkt) ? sLive[kt] : 0;
-    const int force = !any_live;
+    const int force_all = !any_live;
+    // CAUSAL: the same per QUERY TILE over its visible key tiles 0 .. qt (leading pads: the live keys may all lie behind it,
+    // and skipping every visible tile would end in l = 0).
+    unsigned live_bits = 0;
+    if (CAUSAL) {
+#pragma unroll
+        for (int kt = 0; kt < ATT_MAX_KT * QPW; ++kt) live_bits |= (kt < nkt && sLive[kt]) ? 1u << kt : 0u;
+    }
 
     // Online softmax over the key tiles (one 32 x 32 score tile live at a time instead of all of them: ~100 registers,
     // two workgroups per CU).  Scores are in log2 units; p = 2^(s - m) against a per-query reference m that is raised
@@ -157,8 +174,10 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
     }
 #pragma unroll
     for (int qi = 0; qi < QPW; ++qi) {
-        const bool active = wave + 8 * qi < nkt;     // wave-uniform
-        for (int kt = 0; kt < (active ? nkt : 0); ++kt) {
+        const int qt = att_fwd_qtile<QPW, CAUSAL>(wave, qi);
+        const bool active = qt < nkt;                // wave-uniform
+        const int force = CAUSAL ? !(live_bits & ((2u << qt) - 1u)) : force_all;
+        for (int kt = 0; kt < (active ? (CAUSAL ? qt + 1 : nkt) : 0); ++kt) {
             if (!(sLive[kt] | force)) continue;       // wave-uniform
             f32x16 acc;
 #pragma unroll
@@ -172,7 +191,15 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 acc[t] = __builtin_fmaf(acc[t], scale2, sMask[kt * 32 + rowmap(t, hf)]);
-                tm = fmaxf(tm, acc[t]);
+                if (!CAUSAL) tm = fmaxf(tm, acc[t]);
+            }
+            if (CAUSAL) {
+                if (kt == qt) {                       // the diagonal tile (wave-uniform): keys behind the lane's query are out
+#pragma unroll
+                    for (int t = 0; t < 16; ++t) acc[t] = rowmap(t, hf) > r ? -INFINITY : acc[t];
+                }
+#pragma unroll
+                for (int t = 0; t < 16; ++t) tm = fmaxf(tm, acc[t]);
             }
             tm = fmaxf(tm, __shfl_xor(tm, 32));
             const bool raise = tm > m[qi] + 12.0f;
@@ -196,7 +223,7 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
             if (DROP) {
                 // l keeps the undropped sum; the dropped probabilities only lose their place in P V (1 / (1 - rate) joins the
                 // final 1 / l).  Registers 4 tq .. 4 tq + 3 are the keys kt*32 + 8 tq + 4 hf + {0..3} of this lane's query: one hash.
-                const uint32_t s4q = b4c_attn_s4(S_arg) >> 2, dq = (uint32_t)((wave + 8 * qi) * 32 + r) * s4q;
+                const uint32_t s4q = b4c_attn_s4(S_arg) >> 2, dq = (uint32_t)(att_fwd_qtile<QPW, CAUSAL>(wave, qi) * 32 + r) * s4q;
 #pragma unroll
                 for (int tq = 0; tq < 4; ++tq) {
                     const uint32_t kb = b4c_attn_keep4(seed, attn_ctr_base(blockIdx.x, S_arg) + (dq + (uint32_t)(kt * 8 + 2 * tq + hf)), thr);
@@ -227,7 +254,7 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
     B4C_LDS_BARRIER();
 #pragma unroll
     for (int qi = 0; qi < QPW; ++qi) {
-        const int qt = wave + 8 * qi;
+        const int qt = att_fwd_qtile<QPW, CAUSAL>(wave, qi);
         if (qt < nkt) {
             const float inv = DROP ? (1.0f / (1.0f - rate)) / l[qi] : 1.0f / l[qi];
             char *st = smem + qt * (32 * KSTR);
@@ -257,7 +284,7 @@ __global__ void __launch_bounds__(512, (QPW == 1 ? 4 : 2)) attn_fwd_mfma_kernel(
 // stream through a double-buffered LDS image with register prefetch; delta = rowsum(dO * O) is
 // computed while staging; dQ tile = 8 (16 x 16) MFMA tiles, one per wave.
 // ------------------------------------------------------------------------------------------
-template <int DH, bool DROP>
+template <int DH, bool DROP, bool CAUSAL>
 __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                    const bf16_t *__restrict__ o, int ld_o, const bf16_t *__restrict__ d_o,
                                                    int ld_do, const float *__restrict__ lse, bf16_t *__restrict__ dqkv,
@@ -267,6 +294,9 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
     // dQ that sums over them.  acc_mode 0: dQ is complete, written as bf16; 1: first block of several, the partial dQ goes
     // to dq_acc (fp32 [B*S][H*DH]); 2: middle block, dq_acc += partial; 3: last block, dQ = bf16(dq_acc + partial).  Every
     // block streams all the query tiles.  (A dQ element is written and read back by the SAME thread in every block.)
+    // CAUSAL: the block starts at its own first query tile qt0 = key0 / 32 (no earlier query sees one of its keys; the last
+    // block turns the partial dQ of those rows into bf16 first, as the nkt == 0 branch does), wave kt joins at the diagonal
+    // tile qt == key0 / 32 + kt, and the dQ MFMA loop stops there: the dS columns behind the diagonal are never read.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KSTR = DH * 2 + 16;
     constexpr int NKS = DH / 16, NDT = DH / 32, CH = DH / 8;
@@ -287,6 +317,13 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
             }
         }
         return;
+    }
+    const int qt0 = CAUSAL ? key0 >> 5 : 0;                          // first query tile of this block (nkt > 0: qt0 < nqt)
+    if (CAUSAL && acc_mode == 3) {
+        for (int c = threadIdx.x; c < qt0 * 32 * DH; c += 512) {
+            const int q = c / DH, e = c % DH;
+            dqkv[(tok0 + q) * ld_dq + hh * DH + e] = (bf16_t)dq_acc[(tok0 + q) * (int64_t)dm + hh * DH + e];
+        }
     }
     const int TSTR = S_pad * 2 + 16;
     char *sK = smem;
@@ -334,7 +371,7 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
         if (tid < 32) reinterpret_cast<float *>(buf + 2 * 32 * KSTR)[tid] = pre_lse;
     };
 
-    prefetch(0);
+    prefetch(qt0 * 32);
     for (int c = tid; c < S_pad * CH; c += 512) {
         const int row = c / CH, part = c % CH;
         u32x4 kv = {0u, 0u, 0u, 0u}, vv = {0u, 0u, 0u, 0u};
@@ -345,7 +382,7 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
         *reinterpret_cast<u32x4 *>(sK + row * KSTR + part * 16) = kv;
         *reinterpret_cast<u32x4 *>(sV + row * KSTR + part * 16) = vv;
     }
-    commit(sQB);
+    commit(sQB + (qt0 & 1) * QBUF);
 
     // this wave's key tile; the lane's key inside it is r
     const int kt = wave;
@@ -362,14 +399,15 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
         for (int t = 0; t < 16; ++t) { dk[dt][t] = 0.f; dv[dt][t] = 0.f; }
     __syncthreads();
 
-    for (int qt = 0; qt < nqt; ++qt) {
+    for (int qt = qt0; qt < nqt; ++qt) {
         const int q0 = qt * 32;
         char *cur = sQB + (qt & 1) * QBUF;
         const char *sQ = cur, *sdO = cur + 32 * KSTR;
         const float *sLse = reinterpret_cast<const float *>(cur + 2 * 32 * KSTR), *sDelta = sLse + 32;
         const bool more = qt + 1 < nqt;
         if (more) prefetch(q0 + 32);
-        if (kt < nkt) {
+        if (kt < nkt && (!CAUSAL || qt >= qt0 + kt)) {
+            const bool diag = CAUSAL && qt == qt0 + kt;      // wave-uniform
             if (tile_live) {
                 f32x16 sa, pa;
 #pragma unroll
@@ -389,7 +427,8 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
 #pragma unroll
                 for (int t = 0; t < 16; ++t) {
                     const int q = rowmap(t, hf);
-                    const float p = __expf(sa[t] * scale + madd - sLse[q]);
+                    float p = __expf(sa[t] * scale + madd - sLse[q]);
+                    if (CAUSAL) p = (diag && r > q) ? 0.f : p;
                     if (DROP) {
                         const bool kp = (km >> t) & 1u;
                         pv[t] = kp ? p * inv_keep : 0.f;
@@ -424,7 +463,8 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
         if (wave < 2 * (DH / 16)) {                       // dQ[32 q][DH] as (16 q) x (16 dh) tiles, one per wave
             const int qi = wave / (DH / 16), di = wave % (DH / 16);
             f32x4 qa = {0.f, 0.f, 0.f, 0.f};
-            for (int ks = 0; ks < nkt; ++ks) {
+            const int nks = CAUSAL ? (qt - qt0 + 1 < nkt ? qt - qt0 + 1 : nkt) : nkt;
+            for (int ks = 0; ks < nks; ++ks) {
                 const bf16x8 fs = *reinterpret_cast<const bf16x8 *>(sDS + (qi * 16 + li) * TSTR + (ks * 32 + 8 * g) * 2);
                 // K^T: B[k = key ks*32 + 8 g + j][col = dh di*16 + li] via two transposed 4-key reads
                 const char *kb = sK + (ks * 32 + 8 * g + (li >> 2)) * KSTR + (di * 16 + 4 * (li & 3)) * 2;
@@ -470,7 +510,7 @@ __device__ __forceinline__ void attn_bwd_key_block(const bf16_t *__restrict__ qk
 // Sequences of up to 256 keys: one block (acc_mode 0).  Longer ones (S <= 512): the workgroup walks the blocks of 256 keys
 // one after the other in ONE launch (round 2 launched the kernel once per block): Q, dO, O and the fp32 partial dQ of the
 // second pass come out of L2 right behind the first instead of from HBM behind a whole launch.
-template <int DH, bool DROP>
+template <int DH, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(512) attn_bwd_mfma_kernel(const bf16_t *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                             const bf16_t *__restrict__ o, int ld_o, const bf16_t *__restrict__ d_o,
                                                             int ld_do, const float *__restrict__ lse, bf16_t *__restrict__ dqkv,
@@ -478,7 +518,7 @@ __global__ void __launch_bounds__(512) attn_bwd_mfma_kernel(const bf16_t *__rest
                                                             const int32_t *__restrict__ cu, float rate, uint64_t seed) {
     for (int kb = 0; kb < nblk; ++kb) {
         const int mode = nblk == 1 ? 0 : (kb == 0 ? 1 : (kb == nblk - 1 ? 3 : 2));
-        attn_bwd_key_block<DH, DROP>(qkv, ld, key_pad, o, ld_o, d_o, ld_do, lse, dqkv, ld_dq, S_arg, H, scale, kb * 256, dq_acc, mode, cu, rate, seed);
+        attn_bwd_key_block<DH, DROP, CAUSAL>(qkv, ld, key_pad, o, ld_o, d_o, ld_do, lse, dqkv, ld_dq, S_arg, H, scale, kb * 256, dq_acc, mode, cu, rate, seed);
     }
 }
 
@@ -488,7 +528,8 @@ __global__ void __launch_bounds__(512) attn_bwd_mfma_kernel(const bf16_t *__rest
 // streaming kernel above spends ~60 % of its wave-cycles parked on those, SQ_WAIT_ANY) -- then the 32-query
 // tiles run back to back out of LDS.
 // ------------------------------------------------------------------------------------------
-template <int DH, bool DROP>
+// CAUSAL: wave kt joins at the diagonal query tile qt == kt and the dQ MFMA loop stops there.
+template <int DH, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(512) attn_bwd_resident_kernel(const bf16_t *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                                 const bf16_t *__restrict__ o, int ld_o, const bf16_t *__restrict__ d_o,
                                                                 int ld_do, const float *__restrict__ lse, bf16_t *__restrict__ dqkv,
@@ -637,7 +678,8 @@ __global__ void __launch_bounds__(512) attn_bwd_resident_kernel(const bf16_t *__
         const int q0 = qt * 32;
         const char *sQ = sQa + q0 * KSTR, *sdO = sGa + q0 * KSTR;
         const float *sLse = sLseA + q0, *sDelta = sDeltaA + q0;
-        if (kt < nkt && tile_live) {
+        if (kt < nkt && tile_live && (!CAUSAL || qt >= kt)) {
+            const bool diag = CAUSAL && qt == kt;            // wave-uniform
             f32x16 sa, pa;
 #pragma unroll
             for (int t = 0; t < 16; ++t) { sa[t] = 0.f; pa[t] = 0.f; }
@@ -654,7 +696,8 @@ __global__ void __launch_bounds__(512) attn_bwd_resident_kernel(const bf16_t *__
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 const int q = rowmap(t, hf);
-                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[t], scale2, madd - sLse[q]));
+                float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[t], scale2, madd - sLse[q]));
+                if (CAUSAL) p = (diag && r > q) ? 0.f : p;
                 if (DROP) {
                     const bool kp = (km >> t) & 1u;
                     pv[t] = kp ? p * inv_keep : 0.f;
@@ -683,7 +726,7 @@ __global__ void __launch_bounds__(512) attn_bwd_resident_kernel(const bf16_t *__
         if (wave < 2 * (DH / 16)) {
             const int qi = wave / (DH / 16), di = wave % (DH / 16);
             f32x4 qa = {0.f, 0.f, 0.f, 0.f};
-            for (int ks = 0; ks < nkt; ++ks) {
+            for (int ks = 0; ks < (CAUSAL ? qt + 1 : nkt); ++ks) {
                 const bf16x8 fs = *reinterpret_cast<const bf16x8 *>(sDS + (qi * 16 + li) * TSTR + (ks * 32 + 8 * g) * 2);
                 const char *kb = sK + (ks * 32 + 8 * g + (li >> 2)) * KSTR + (di * 16 + 4 * (li & 3)) * 2;
                 const bf16x8 fk = frag_tr(kb, 4 * KSTR);
@@ -758,24 +801,27 @@ static bool mfma_shape_ok(int S, int dh) { return (dh == 32 || dh == 64) && S <=
 
 // rate == 0 launches the DROP = false instantiations: the kernels of the entry points without dropout.
 int b4c_attn_fwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B, int S,
-                      int H, int dh, const int32_t *cu, float rate, uint64_t seed, hipStream_t st) {
+                      int H, int dh, const int32_t *cu, float rate, uint64_t seed, bool causal, hipStream_t st) {
     if (!mfma_shape_ok(S, dh)) return B4C_EUNSUPPORTED;
     const int S_pad = (S + 31) / 32 * 32;
     const int qpw = S_pad > 32 * ATT_MAX_KT ? 2 : 1;
     const size_t shm = 2 * (size_t)S_pad * (dh * 2 + 16) + (size_t)S_pad * 4 + ATT_MAX_KT * qpw * 4;
     const float scale = 1.0f / sqrtf((float)dh);
-#define ATT_FWD_LAUNCH(DHH, QQ, DR)                                                                                      \
+#define ATT_FWD_LAUNCH(DHH, QQ, DR, CA)                                                                                  \
     do {                                                                                                                 \
-        b4c_allow_lds(attn_fwd_mfma_kernel<DHH, QQ, DR>, shm);                                                         \
-        attn_fwd_mfma_kernel<DHH, QQ, DR><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, scale, cu, rate, seed); \
+        b4c_allow_lds(attn_fwd_mfma_kernel<DHH, QQ, DR, CA>, shm);                                                     \
+        attn_fwd_mfma_kernel<DHH, QQ, DR, CA><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, scale, cu, rate, seed); \
     } while (0)
+#define ATT_FWD_LAUNCH_Q(DHH, DR, CA)                                                                                    \
+    do { if (qpw == 1) ATT_FWD_LAUNCH(DHH, 1, DR, CA); else ATT_FWD_LAUNCH(DHH, 2, DR, CA); } while (0)
 #define ATT_FWD_LAUNCH_DH(DHH)                                                                                           \
     do {                                                                                                                 \
-        if (rate == 0.f) { if (qpw == 1) ATT_FWD_LAUNCH(DHH, 1, false); else ATT_FWD_LAUNCH(DHH, 2, false); }            \
-        else { if (qpw == 1) ATT_FWD_LAUNCH(DHH, 1, true); else ATT_FWD_LAUNCH(DHH, 2, true); }                          \
+        if (!causal) { if (rate == 0.f) ATT_FWD_LAUNCH_Q(DHH, false, false); else ATT_FWD_LAUNCH_Q(DHH, true, false); }  \
+        else { if (rate == 0.f) ATT_FWD_LAUNCH_Q(DHH, false, true); else ATT_FWD_LAUNCH_Q(DHH, true, true); }            \
     } while (0)
     if (dh == 64) ATT_FWD_LAUNCH_DH(64); else ATT_FWD_LAUNCH_DH(32);
 #undef ATT_FWD_LAUNCH_DH
+#undef ATT_FWD_LAUNCH_Q
 #undef ATT_FWD_LAUNCH
     return b4c_check_launch("attn_fwd_mfma");
 }
@@ -787,23 +833,26 @@ int64_t b4c_attn_bwd_mfma_workspace_bytes(int B, int S, int H, int dh) {
 
 int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o, const void *d_o,
                       int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B, int S, int H, int dh,
-                      void *workspace, int64_t workspace_bytes, const int32_t *cu, float rate, uint64_t seed, hipStream_t st) {
+                      void *workspace, int64_t workspace_bytes, const int32_t *cu, float rate, uint64_t seed, bool causal,
+                      hipStream_t st) {
     if (!mfma_shape_ok(S, dh)) return B4C_EUNSUPPORTED;
     const float scale = 1.0f / sqrtf((float)dh);
-#define ATT_BWD_BLOCKS(DHH, DR, SHM, NBLK, ACC)                                                                          \
+#define ATT_BWD_BLOCKS(DHH, DR, CA, SHM, NBLK, ACC)                                                                      \
     do {                                                                                                                 \
-        b4c_allow_lds(attn_bwd_mfma_kernel<DHH, DR>, SHM);                                                             \
-        attn_bwd_mfma_kernel<DHH, DR><<<B * H, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, NBLK, ACC, cu, rate, seed); \
+        b4c_allow_lds(attn_bwd_mfma_kernel<DHH, DR, CA>, SHM);                                                         \
+        attn_bwd_mfma_kernel<DHH, DR, CA><<<B * H, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, NBLK, ACC, cu, rate, seed); \
     } while (0)
-#define ATT_BWD_RESIDENT(DHH, DR, SHM, GRID)                                                                             \
+#define ATT_BWD_RESIDENT(DHH, DR, CA, SHM, GRID)                                                                         \
     do {                                                                                                                 \
-        b4c_allow_lds(attn_bwd_resident_kernel<DHH, DR>, SHM);                                                         \
-        attn_bwd_resident_kernel<DHH, DR><<<GRID, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, B * H, (int *)delta, cu, rate, seed); \
+        b4c_allow_lds(attn_bwd_resident_kernel<DHH, DR, CA>, SHM);                                                     \
+        attn_bwd_resident_kernel<DHH, DR, CA><<<GRID, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, B * H, (int *)delta, cu, rate, seed); \
     } while (0)
+#define ATT_BWD_SELECT_DR(LAUNCH, DHH, CA, ...)                                                                          \
+    do { if (rate == 0.f) LAUNCH(DHH, false, CA, __VA_ARGS__); else LAUNCH(DHH, true, CA, __VA_ARGS__); } while (0)
 #define ATT_BWD_SELECT(LAUNCH, ...)                                                                                      \
     do {                                                                                                                 \
-        if (dh == 64) { if (rate == 0.f) LAUNCH(64, false, __VA_ARGS__); else LAUNCH(64, true, __VA_ARGS__); }           \
-        else { if (rate == 0.f) LAUNCH(32, false, __VA_ARGS__); else LAUNCH(32, true, __VA_ARGS__); }                    \
+        if (dh == 64) { if (!causal) ATT_BWD_SELECT_DR(LAUNCH, 64, false, __VA_ARGS__); else ATT_BWD_SELECT_DR(LAUNCH, 64, true, __VA_ARGS__); } \
+        else { if (!causal) ATT_BWD_SELECT_DR(LAUNCH, 32, false, __VA_ARGS__); else ATT_BWD_SELECT_DR(LAUNCH, 32, true, __VA_ARGS__); }          \
     } while (0)
     if (S > 32 * ATT_MAX_KT) {
         // the blocks of 256 keys one after the other inside one launch; their partial dQ sums meet in an fp32 accumulator
@@ -828,6 +877,7 @@ int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const
     }
     ATT_BWD_SELECT(ATT_BWD_BLOCKS, shm, 1, (float *)nullptr);
 #undef ATT_BWD_SELECT
+#undef ATT_BWD_SELECT_DR
 #undef ATT_BWD_RESIDENT
 #undef ATT_BWD_BLOCKS
     return b4c_check_launch("attn_bwd_mfma");

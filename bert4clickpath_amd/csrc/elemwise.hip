@@ -356,8 +356,10 @@ extern "C" int b4c_compact_labels(const float *labels, int B, int M, const int32
 // attention weights on request (MultiHeadAttention.call's second result, transformer.py:64-97):
 //   w[b][h][i][j] = exp(q_i . k_j / sqrt(dh) + pad_j * -1e9 - lse[b][h][i])          fp32 [B][H][S][S]
 // 64 x 64 tile per workgroup, q and k rows staged in LDS as fp32.
+// CAUSAL (b4c_attn_weights_ex; the CAUSAL = false instantiations are the kernels without it): w[b][h][i][j] = 0 for j > i, with lse
+// the log-sum-exp over the visible keys; a tile above the diagonal is zero-filled without staging anything.
 // ------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool CAUSAL>
 __global__ void __launch_bounds__(256) attn_weights_kernel(const T *__restrict__ qkv, int ld, const uint8_t *__restrict__ key_pad,
                                                            const float *__restrict__ lse, float *__restrict__ w, int S, int H,
                                                            int dh, float sqrt_dk) {
@@ -367,6 +369,12 @@ __global__ void __launch_bounds__(256) attn_weights_kernel(const T *__restrict__
     const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
     const int64_t tok0 = (int64_t)b * S;
     float *sq = sm, *sk = sm + 64 * (dh + 1);
+    if (CAUSAL && j0 > i0) {                               // (tiles are 64-aligned: j0 > i0 puts every key behind every query)
+        const int j = tid & 63;
+        for (int i = tid >> 6; i < 64; i += 4)
+            if (i0 + i < S && j0 + j < S) w[(((int64_t)b * H + h) * S + i0 + i) * S + j0 + j] = 0.f;
+        return;
+    }
     for (int e = tid; e < 64 * dh; e += 256) {
         const int r = e / dh, c = e % dh;
         sq[r * (dh + 1) + c] = (i0 + r < S) ? (float)qkv[(tok0 + i0 + r) * ld + h * dh + c] : 0.f;
@@ -376,6 +384,10 @@ __global__ void __launch_bounds__(256) attn_weights_kernel(const T *__restrict__
     const int j = tid & 63;
     for (int i = tid >> 6; i < 64; i += 4) {
         if (i0 + i >= S || j0 + j >= S) continue;
+        if (CAUSAL && j0 + j > i0 + i) {
+            w[(((int64_t)b * H + h) * S + i0 + i) * S + j0 + j] = 0.f;
+            continue;
+        }
         float s = 0.f;
         for (int c = 0; c < dh; ++c) s += sq[i * (dh + 1) + c] * sk[j * (dh + 1) + c];
         s /= sqrt_dk;
@@ -385,8 +397,8 @@ __global__ void __launch_bounds__(256) attn_weights_kernel(const T *__restrict__
     }
 }
 
-extern "C" int b4c_attn_weights(const void *qkv, int ld_qkv, const uint8_t *key_pad, const float *lse, float *weights, int B,
-                                int S, int H, int dh, int dtype, void *stream) {
+static int attn_weights_any(const void *qkv, int ld_qkv, const uint8_t *key_pad, const float *lse, float *weights, int B,
+                            int S, int H, int dh, int dtype, void *stream, bool causal) {
     B4C_REQUIRE(qkv && key_pad && lse && weights && B > 0 && S > 0 && H > 0 && dh > 0, "attn_weights: bad argument");
     B4C_REQUIRE(ld_qkv >= 3 * H * dh, "attn_weights: bad pitch");
     B4C_REQUIRE((int64_t)B * H <= 65535, "attn_weights: B*H exceeds 65535");
@@ -394,10 +406,23 @@ extern "C" int b4c_attn_weights(const void *qkv, int ld_qkv, const uint8_t *key_
     dim3 grid((S + 63) / 64, (S + 63) / 64, B * H);
     const size_t shm = (size_t)2 * 64 * (dh + 1) * sizeof(float);
     const float sq = sqrtf((float)dh);
-    if (dtype == B4C_F32) attn_weights_kernel<float><<<grid, 256, shm, st>>>((const float *)qkv, ld_qkv, key_pad, lse, weights, S, H, dh, sq);
-    else if (dtype == B4C_BF16) attn_weights_kernel<bf16_t><<<grid, 256, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, lse, weights, S, H, dh, sq);
+#define ATT_W_LAUNCH(T, CA) attn_weights_kernel<T, CA><<<grid, 256, shm, st>>>((const T *)qkv, ld_qkv, key_pad, lse, weights, S, H, dh, sq)
+    if (dtype == B4C_F32) { if (causal) ATT_W_LAUNCH(float, true); else ATT_W_LAUNCH(float, false); }
+    else if (dtype == B4C_BF16) { if (causal) ATT_W_LAUNCH(bf16_t, true); else ATT_W_LAUNCH(bf16_t, false); }
     else B4C_REQUIRE(false, "attn_weights: dtype %d", dtype);
+#undef ATT_W_LAUNCH
     return b4c_check_launch("attn_weights");
+}
+
+extern "C" int b4c_attn_weights(const void *qkv, int ld_qkv, const uint8_t *key_pad, const float *lse, float *weights, int B,
+                                int S, int H, int dh, int dtype, void *stream) {
+    return attn_weights_any(qkv, ld_qkv, key_pad, lse, weights, B, S, H, dh, dtype, stream, false);
+}
+
+extern "C" int b4c_attn_weights_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const float *lse, float *weights, int B,
+                                   int S, int H, int dh, int dtype, void *stream, uint32_t flags) {
+    B4C_REQUIRE((flags & ~B4C_ATTN_CAUSAL) == 0, "attn_weights_ex: unknown flag bits 0x%x", flags & ~B4C_ATTN_CAUSAL);
+    return attn_weights_any(qkv, ld_qkv, key_pad, lse, weights, B, S, H, dh, dtype, stream, (flags & B4C_ATTN_CAUSAL) != 0);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -955,42 +955,60 @@ def _attn_rate(rate):
     return rate
 
 
-def attn_fwd(qkv, key_pad, B, S, H, dh, cu=None, rate=0.0, seed=0):
+ATTN_CAUSAL = L.ATTN_CAUSAL        # B4C_ATTN_CAUSAL of include/b4c_attn_ex.h (flags of the b4c_attn_*_ex entry points)
+
+
+def _attn_pairs(T_tok, S, cu, causal):
+    """(query, key) pairs a launch works on, for the roofline table.  Bidirectional: sum of len^2 (packed layout: the host hint
+    'sum_len_sq'; T x S is an upper bound and what the padded layout computes).  Causal: the triangle, sum of len (len + 1) / 2 --
+    skipped tiles are not credited; sum len is the token count, so the same hint serves."""
+    pairs = rec_hints.get('sum_len_sq', T_tok * S) if cu is not None else T_tok * S
+    return (pairs + T_tok) // 2 if causal else pairs
+
+
+def attn_fwd(qkv, key_pad, B, S, H, dh, cu=None, rate=0.0, seed=0, causal=False):
     """cu (int32 [B+1]): packed layout -- sequence b owns rows cu[b] .. cu[b+1] of qkv, S = upper bound of the longest one.
     rate > 0: dropout on the attention probabilities, mask b4c_attn_keep(seed, b, h, q, k, H, S, rate) (include/b4c.h); lse is that
-    of the undropped softmax.  rate == 0 is the call without dropout."""
+    of the undropped softmax.  rate == 0 is the call without dropout.
+    causal: key k is visible to query q iff k <= q (b4c_attn_fwd_ex with B4C_ATTN_CAUSAL); lse is over the visible keys.  Without
+    it the call is the one it has always been."""
     rate = _attn_rate(rate)
     d = H * dh
     T_tok = qkv.shape[0]
     o = torch.empty(T_tok, d, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(B, H, S, dtype=torch.float32, device=qkv.device)
-    # algorithmic work of the packed layout: sum over sequences of len^2 (host hint; T x S is an upper bound and what the
-    # padded layout computes)
-    pairs = rec_hints.get('sum_len_sq', T_tok * S) if cu is not None else T_tok * S
-    with _record('attn_fwd', T_tok * 4 * d * qkv.element_size(), 4 * pairs * d):
+    with _record('attn_fwd', T_tok * 4 * d * qkv.element_size(), 4 * _attn_pairs(T_tok, S, cu, causal) * d):
+        if causal:
+            L.check(L.lib().b4c_attn_fwd_ex(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), d, _p(lse), B, S, H, dh,
+                                            dt_code(qkv.dtype), _st(), rate, seed, ATTN_CAUSAL), 'attn_fwd_ex')
+            return o, lse
         args = [_p(qkv), qkv.stride(0), _p(key_pad)] + ([] if cu is None else [_p(cu)]) + \
             [_p(o), d, _p(lse), B, S, H, dh, dt_code(qkv.dtype), _st()]
         _attn_call('attn_fwd', args + ([rate, seed] if rate > 0 else []), varlen=cu is not None, drop=rate > 0)
     return o, lse
 
 
-def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None, rate=0.0, seed=0):
+def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None, rate=0.0, seed=0, causal=False):
     """actx: the ArenaContext of the training step in flight (its background work gets a launch opportunity behind this kernel)
-    rate, seed: those of the forward (attn_fwd); o is the forward's output, dropped probabilities included."""
+    rate, seed, causal: those of the forward (attn_fwd); o is the forward's output, dropped probabilities included."""
     rate = _attn_rate(rate)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
     need = L.lib().b4c_attn_bwd_workspace_bytes(B, S, H, dh, dt_code(qkv.dtype))     # > 0 only for bf16 256 < S <= 512
     ws = _workspace('attn_bwd', qkv.device, need) if need else None
     T_tok = qkv.shape[0]
-    pairs = rec_hints.get('sum_len_sq', T_tok * S) if cu is not None else T_tok * S
-    with _record('attn_bwd', T_tok * 8 * H * dh * qkv.element_size(), 10 * pairs * H * dh):
-        args = [_p(qkv), qkv.stride(0), _p(key_pad)] + ([] if cu is None else [_p(cu)]) + \
-            [_p(o), o.stride(0), _p(d_o), d_o.stride(0), _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
-             dt_code(qkv.dtype), _st()]
-        # (the dense entry points that take the workspace are b4c_attn_bwd_ws / b4c_attn_bwd_drop_ws)
-        _attn_call('attn_bwd', args + ([rate, seed] if rate > 0 else []), varlen=cu is not None, drop=rate > 0,
-                   dense_suffix='_ws')
+    with _record('attn_bwd', T_tok * 8 * H * dh * qkv.element_size(), 10 * _attn_pairs(T_tok, S, cu, causal) * H * dh):
+        if causal:
+            L.check(L.lib().b4c_attn_bwd_ex(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
+                                            _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
+                                            dt_code(qkv.dtype), _st(), rate, seed, ATTN_CAUSAL), 'attn_bwd_ex')
+        else:
+            args = [_p(qkv), qkv.stride(0), _p(key_pad)] + ([] if cu is None else [_p(cu)]) + \
+                [_p(o), o.stride(0), _p(d_o), d_o.stride(0), _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
+                 dt_code(qkv.dtype), _st()]
+            # (the dense entry points that take the workspace are b4c_attn_bwd_ws / b4c_attn_bwd_drop_ws)
+            _attn_call('attn_bwd', args + ([rate, seed] if rate > 0 else []), varlen=cu is not None, drop=rate > 0,
+                       dense_suffix='_ws')
     _background_kick(actx)      # the next piece of the vocabulary head's dW sweep starts when this kernel has left the CUs
     return dqkv
 
@@ -2162,11 +2180,12 @@ def _attn_tail_bwd(dout, z, stats, gamma, rate, seed, o, wc_o, params, actx, sin
 
 class AttnBlockFn(torch.autograd.Function):
     """R8 + first half of R10: LN1(x + drop(MHA(x))).  x: [T, d] in the compute dtype.
-    attn_rate, attn_seed: dropout on the attention probabilities (attn_fwd; no reference counterpart), applied as given."""
+    attn_rate, attn_seed: dropout on the attention probabilities (attn_fwd; no reference counterpart), applied as given.
+    causal: left-to-right attention (attn_fwd(causal=True))."""
 
     @staticmethod
     def forward(ctx, x, key_pad, wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta, pk_qkv, pk_o, B, S, H, rate, seed, training, cu=None,
-                attn_rate=0.0, attn_seed=0):
+                attn_rate=0.0, attn_seed=0, causal=False):
         T_tok, d = x.shape
         dh = d // H
         wt_qkv, _, b_qkv = pk_qkv.get(x.dtype, d, training)
@@ -2175,6 +2194,8 @@ class AttnBlockFn(torch.autograd.Function):
             qkv = gemm_nt(x, wt_qkv, 3 * d, b_qkv)
         # (without attention dropout: attn_fwd / attn_bwd are called as they have always been, without the keywords)
         attn_drop = {'rate': attn_rate, 'seed': attn_seed} if attn_rate > 0 else {}
+        if causal:              # (likewise: a bidirectional block makes the calls it makes without this keyword)
+            attn_drop['causal'] = True
         with _timed('attn_fwd'):
             o, lse = attn_fwd(qkv, key_pad, B, S, H, dh, cu, **attn_drop)
         z, out, stats = _residual_ln_fwd(o, wt_o, b_o, x, gamma, beta, rate, seed, training)
@@ -2831,8 +2852,13 @@ def compact_labels(labels_padded, counts, offsets, cap, flat_idx=None):
     return out
 
 
-def attn_weights(qkv, key_pad, lse, B, S, H, dh):
+def attn_weights(qkv, key_pad, lse, B, S, H, dh, causal=False):
+    """causal: lse is that of attn_fwd(causal=True); the weights of the keys behind the query are exactly 0."""
     w = torch.empty(B, H, S, S, dtype=torch.float32, device=qkv.device)
+    if causal:
+        L.check(L.lib().b4c_attn_weights_ex(_p(qkv), qkv.stride(0), _p(key_pad), _p(lse), _p(w), B, S, H, dh, dt_code(qkv.dtype),
+                                            _st(), ATTN_CAUSAL), 'attn_weights_ex')
+        return w
     L.check(L.lib().b4c_attn_weights(_p(qkv), qkv.stride(0), _p(key_pad), _p(lse), _p(w), B, S, H, dh, dt_code(qkv.dtype),
                                      _st()), 'attn_weights')
     return w
@@ -2859,10 +2885,11 @@ def rows_scatter_add_f32_(dst, idx, src):
 class MHAFn(torch.autograd.Function):
     """MultiHeadAttention.call(v, k, q, mask) in general (transformer.py:137-160): distinct value / key / query inputs
     of one padded length S, key-side padding mask, attention weights on request.  Differentiable in the three inputs
-    and all eight parameters.  apply(xq, xk, xv, key_pad, wq, bq, wk, bk, wv, bv, wo, bo, pk_qkv, pk_o, B, S, H, same, want_w)"""
+    and all eight parameters.  apply(xq, xk, xv, key_pad, wq, bq, wk, bk, wv, bv, wo, bo, pk_qkv, pk_o, B, S, H, same, want_w
+    [, causal])"""
 
     @staticmethod
-    def forward(ctx, xq, xk, xv, key_pad, wq, bq, wk, bk, wv, bv, wo, bo, pk_qkv, pk_o, B, S, H, same, want_w):
+    def forward(ctx, xq, xk, xv, key_pad, wq, bq, wk, bk, wv, bv, wo, bo, pk_qkv, pk_o, B, S, H, same, want_w, causal=False):
         T_tok, d = xq.shape
         dh = d // H
         wt_qkv, _, b_qkv = pk_qkv.get(xq.dtype, d, True)
@@ -2873,11 +2900,12 @@ class MHAFn(torch.autograd.Function):
             qkv = torch.empty(T_tok, 3 * d, dtype=xq.dtype, device=xq.device)
             for i, x in enumerate((xq, xk, xv)):
                 gemm_nt(x, wt_qkv[i * d:(i + 1) * d], d, b_qkv[i * d:(i + 1) * d], out=qkv[:, i * d:(i + 1) * d])
-        o, lse = attn_fwd(qkv, key_pad, B, S, H, dh)
+        ckw = {'causal': True} if causal else {}        # (a bidirectional call is the call it has always been)
+        o, lse = attn_fwd(qkv, key_pad, B, S, H, dh, **ckw)
         out = gemm_nt(o, wt_o, d, b_o)
-        w = attn_weights(qkv, key_pad, lse, B, S, H, dh) if want_w else None
+        w = attn_weights(qkv, key_pad, lse, B, S, H, dh, **ckw) if want_w else None
         ctx.save_for_backward(xq, xk, xv, key_pad, qkv, o, lse)
-        ctx.pk, ctx.dims, ctx.same = (pk_qkv, pk_o), (B, S, H, dh), same
+        ctx.pk, ctx.dims, ctx.same, ctx.ckw = (pk_qkv, pk_o), (B, S, H, dh), same, ckw
         ctx.params = (wq, bq, wk, bk, wv, bv, wo, bo)
         if w is None:
             w = torch.empty(0, device=xq.device)
@@ -2897,7 +2925,7 @@ class MHAFn(torch.autograd.Function):
         dy = dout.contiguous()
         gemm_tn(o, dy, d, d, into=(gw[3:], gb[3:]))
         d_o = gemm_nt(dy, wc_o, d)
-        dqkv = attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh)
+        dqkv = attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, **ctx.ckw)
         if ctx.same:
             gemm_tn(xq, dqkv, d, 3 * d, into=(gw[:3], gb[:3]))
             gx = (gemm_nt(dqkv, wc_qkv, d), None, None)

@@ -75,6 +75,9 @@ def main():
                          'the last for test, reported once at the end; default 1: the callbacks monitor the last item')
     ap.add_argument('--last_item_rate', type=float, default=0.0,
                     help='with --device_batches: the share of training rows whose only masked position is the last one')
+    ap.add_argument('--attention', default='bidirectional', choices=['bidirectional', 'causal'],
+                    help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
+                         'left-to-right next-item model')
     a = ap.parse_args()
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
@@ -87,7 +90,7 @@ def main():
     else:
         data = input_pipeline.BeautyCloze(a.data)
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
-    model = build_model(data.V, a.dropout, dtype, seed=1234 + a.seed).cuda()
+    model = build_model(data.V, a.dropout, dtype, seed=1234 + a.seed, attention=a.attention).cuda()
     opt = optim.Adam(model.parameters())
     T.set_dropout_seed(a.seed)
     tmp = tempfile.mkdtemp(prefix='b4c_beauty_')

@@ -27,21 +27,23 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def build_model(V, dropout, dtype, seed=1234, paper_positions=None):
-    """paper_positions (the longest encoder input): the BERT4Rec paper's model, one constructor call"""
+def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='bidirectional'):
+    """paper_positions (the longest encoder input): the BERT4Rec paper's model, one constructor call.
+    attention='causal': left-to-right self-attention (SASRec, the paper's unidirectional arm)."""
     from bert4clickpath_amd.clickstream_transformer import ClickstreamTransformer, ClozeMaskedItemPrediction, SoftMaxHead
     torch.manual_seed(seed)            # CPU generator: identical initial weights on any machine
     vocab = ['item%d' % i for i in range(V)]
+    kw = {'attention': attention} if attention != 'bidirectional' else {}
     if paper_positions is not None:
         return ClickstreamTransformer({'items': ['asin']}, {'items': vocab}, {'items': 64},
                                       ClozeMaskedItemPrediction([], V, transform='gelu_tanh'), value_to_head='[MASK]',
                                       num_encoder_layers=2, num_attention_heads=2, encoder_ff_dim=256, dropout_rate=dropout,
                                       attention_dropout_rate=dropout, compute_dtype=dtype, ffn_activation='gelu_tanh',
                                       position_encoding='learned', max_positions=paper_positions, embedding_layernorm=True,
-                                      embedding_scale=1.0)
+                                      embedding_scale=1.0, **kw)
     head = SoftMaxHead([1024, 512, 256, 128], V)
     return ClickstreamTransformer({'items': ['asin']}, {'items': vocab}, {'items': 64}, head, value_to_head='[MASK]',
-                                  num_encoder_layers=2, num_attention_heads=2, dropout_rate=dropout, compute_dtype=dtype)
+                                  num_encoder_layers=2, num_attention_heads=2, dropout_rate=dropout, compute_dtype=dtype, **kw)
 
 
 def main():
@@ -84,6 +86,9 @@ def main():
                          'paper\'s leave-one-out split; both are reported); default 1: the last item is the test target')
     ap.add_argument('--last_item_rate', type=float, default=0.0,
                     help='with --device_batches: the share of training rows whose only masked position is the last one')
+    ap.add_argument('--attention', default='bidirectional', choices=['bidirectional', 'causal'],
+                    help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
+                         'left-to-right next-item model (every training row predicts the item after its prefix)')
     a = ap.parse_args()
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
@@ -94,7 +99,7 @@ def main():
     data = input_pipeline.BeautyCloze(a.data)
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
     longest = (int(np.diff(data.offsets).max()) if a.max_len is None else a.max_len) + 3       # [CLS] [SEP] items [SEP]
-    model = build_model(data.V, a.dropout, dtype, paper_positions=longest if a.paper_model else None).cuda()
+    model = build_model(data.V, a.dropout, dtype, paper_positions=longest if a.paper_model else None, attention=a.attention).cuda()
     lr = WarmupLinearDecay(1e-3, a.warmup, max(a.steps, a.warmup + 1)) if a.warmup > 0 else 1e-3
     opt = optim.Adam(model.parameters(), learning_rate=lr, global_clipnorm=a.clipnorm, weight_decay=a.weight_decay,
                      exclude_from_weight_decay=optim.no_decay_params(model) if a.weight_decay is not None else ())

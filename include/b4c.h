@@ -878,4 +878,9 @@ int b4c_attn_mq_bwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, con
 #ifdef __cplusplus
 }
 #endif
+
+/* ---- extension headers: part of this ABI, declared in files of their own and included here, so that b4c.h is all a caller includes.
+ * (The ctypes binding reads them beside this file: bert4clickpath_amd/_lib.py, EXT_HEADER_PATHS.) */
+#include "b4c_attn_ex.h"   /* b4c_attn_fwd_ex / b4c_attn_bwd_ex / b4c_attn_weights_ex, B4C_ATTN_CAUSAL: causal self-attention */
+
 #endif /* B4C_H */
