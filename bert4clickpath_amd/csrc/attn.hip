@@ -269,87 +269,108 @@ static int check_attn_rate(const char *who, float rate) {
     B4C_REQUIRE(rate >= 0.f && rate < 1.f, "%s: dropout rate %g outside [0, 1)", who, (double)rate);
     return B4C_OK;
 }
+static int check_attn_flags(const char *who, uint32_t flags) {
+    B4C_REQUIRE((flags & ~B4C_ATTN_CAUSAL) == 0, "%s: unknown flag bits 0x%x", who, flags & ~B4C_ATTN_CAUSAL);
+    return B4C_OK;
+}
 
-// rate == 0 selects the DROP = false instantiations: the kernels of the entry points without dropout
-// and !causal the CAUSAL = false ones
-#define ATT_DISPATCH_DH(dh, KERNEL, T, DR, CA, ...)                  \
-    switch (dh) {                                                    \
-        case 16: KERNEL<T, 16, DR, CA> __VA_ARGS__; break;           \
-        case 32: KERNEL<T, 32, DR, CA> __VA_ARGS__; break;           \
-        case 64: KERNEL<T, 64, DR, CA> __VA_ARGS__; break;           \
-        default: KERNEL<T, 128, DR, CA> __VA_ARGS__; break;          \
-    }
-#define ATT_DISPATCH_DR(dh, KERNEL, T, CA, ...)                                              \
-    if (rate == 0.f) { ATT_DISPATCH_DH(dh, KERNEL, T, false, CA, __VA_ARGS__) }              \
-    else { ATT_DISPATCH_DH(dh, KERNEL, T, true, CA, __VA_ARGS__) }
-#define ATT_DISPATCH(dh, KERNEL, T, ...)                                                     \
-    if (!causal) { ATT_DISPATCH_DR(dh, KERNEL, T, false, __VA_ARGS__) }                      \
-    else { ATT_DISPATCH_DR(dh, KERNEL, T, true, __VA_ARGS__) }
-
-static int attn_fwd_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
-                        int S, int H, int dh, float rate, uint64_t seed, bool causal, int dtype, void *stream) {
+// One host path per direction, behind every entry point below.  cu_seqlens: NULL is the dense layout, S rows per sequence.
+// Otherwise the packed (padding-free) layout: sequence b owns rows cu_seqlens[b] .. cu_seqlens[b+1] of qkv / o / d_o / dqkv and S
+// is max_len, the longest sequence (LDS sizing, lse / delta pitch: [B][H][max_len]); key_pad [total tokens] is all zeros unless the
+// caller keeps masked keys inside the packed rows.  The packed layout exists for the throughput path -- bf16, head depth 32 / 64,
+// max_len <= 512, an error outside it --, the fp32 parity path stays dense, and dense bf16 outside the MFMA kernels falls back to
+// the row kernels.  rate == 0 selects the DROP = false instantiations, the kernels of the entry points without dropout, and
+// !causal the CAUSAL = false ones.
+static int attn_fwd_launch(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o,
+                           int ld_o, float *lse, int B, int S, int H, int dh, float rate, uint64_t seed, bool causal, int dtype,
+                           void *stream) {
     B4C_REQUIRE(qkv && key_pad && o, "%s: null pointer", who);
     int rc = check_attn(who, ld_qkv, ld_o, B, S, H, dh);
     if (rc) return rc;
+    B4C_REQUIRE(!cu_seqlens || dtype == B4C_BF16, "%s: bf16 only", who);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == B4C_BF16) {
-        rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, nullptr, rate, seed, causal, st);
+        rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, cu_seqlens, rate, seed, causal, st);
+        B4C_REQUIRE(!cu_seqlens || rc != B4C_EUNSUPPORTED, "%s: max_len %d / head depth %d outside the MFMA kernels (<= 512, 32 or 64)", who, S, dh);
         if (rc != B4C_EUNSUPPORTED) return rc;
         note_row_fallback(who, S, dh);
     }
     const float sq = sqrtf((float)dh);
     dim3 grid((S + 255) / 256, B * H);
-    if (dtype == B4C_F32) {
-        ATT_DISPATCH(dh, attn_fwd_row_kernel, float, <<<grid, 256, 0, st>>>((const float *)qkv, ld_qkv, key_pad, (float *)o, ld_o, lse, S, H, sq, rate, seed))
-    } else if (dtype == B4C_BF16) {
-        ATT_DISPATCH(dh, attn_fwd_row_kernel, bf16_t, <<<grid, 256, 0, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, sq, rate, seed))
-    } else
-        B4C_REQUIRE(false, "%s: dtype %d", who, dtype);
+    auto rows = [&](auto *t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        b4c_by_int<16, 32, 64, 128>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) { b4c_by_bool(causal, [&](auto CA) {
+            attn_fwd_row_kernel<T, DH(), DR(), CA()><<<grid, 256, 0, st>>>((const T *)qkv, ld_qkv, key_pad, (T *)o, ld_o, lse, S, H, sq, rate, seed);
+        }); }); });
+    };
+    if (dtype == B4C_F32) rows((float *)nullptr);
+    else if (dtype == B4C_BF16) rows((bf16_t *)nullptr);
+    else B4C_REQUIRE(false, "%s: dtype %d", who, dtype);
     return b4c_check_launch(who);
 }
 
-extern "C" int b4c_attn_fwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
-                            int S, int H, int dh, int dtype, void *stream) {
-    return attn_fwd_any("attn_fwd", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, 0.f, 0, false, dtype, stream);
-}
-
-extern "C" int b4c_attn_fwd_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
-                                 int S, int H, int dh, int dtype, void *stream, float dropout_rate, uint64_t seed) {
-    int rc = check_attn_rate("attn_fwd_drop", dropout_rate);
+static int attn_bwd_launch(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                           const void *o, int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv,
+                           int ld_dqkv, int B, int S, int H, int dh, void *workspace, int64_t workspace_bytes, float rate,
+                           uint64_t seed, bool causal, int dtype, void *stream) {
+    B4C_REQUIRE(qkv && key_pad && o && d_o && lse && delta && dqkv, "%s: null pointer", who);
+    int rc = check_attn(who, ld_qkv, ld_o, B, S, H, dh);
     if (rc) return rc;
-    return attn_fwd_any("attn_fwd_drop", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, dropout_rate, seed, false, dtype, stream);
+    B4C_REQUIRE(!cu_seqlens || dtype == B4C_BF16, "%s: bf16 only", who);
+    B4C_REQUIRE(ld_do >= H * dh && ld_do % 8 == 0 && ld_dqkv >= 3 * H * dh && ld_dqkv % 8 == 0, "%s: bad pitch", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == B4C_BF16) {
+        rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
+                               workspace_bytes, cu_seqlens, rate, seed, causal, st);
+        B4C_REQUIRE(!cu_seqlens || rc != B4C_EUNSUPPORTED, "%s: shape outside the MFMA kernels, or workspace missing for max_len > 256", who);
+        if (rc != B4C_EUNSUPPORTED) return rc;
+        note_row_fallback(who, S, dh);
+    }
+    const float sq = sqrtf((float)dh);
+    dim3 grid((S + 255) / 256, B * H);
+    auto rows = [&](auto *t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        b4c_by_int<16, 32, 64, 128>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) { b4c_by_bool(causal, [&](auto CA) {
+            attn_bwd_dq_kernel<T, DH(), DR(), CA()><<<grid, 256, 0, st>>>((const T *)qkv, ld_qkv, key_pad, (const T *)o, ld_o, (const T *)d_o, ld_do, lse, delta, (T *)dqkv, ld_dqkv, S, H, sq, rate, seed);
+            attn_bwd_dkv_kernel<T, DH(), DR(), CA()><<<grid, 256, 0, st>>>((const T *)qkv, ld_qkv, key_pad, (const T *)d_o, ld_do, lse, delta, (T *)dqkv, ld_dqkv, S, H, sq, rate, seed);
+        }); }); });
+    };
+    if (dtype == B4C_F32) rows((float *)nullptr);
+    else if (dtype == B4C_BF16) rows((bf16_t *)nullptr);
+    else B4C_REQUIRE(false, "%s: dtype %d", who, dtype);
+    return b4c_check_launch(who);
 }
 
 extern "C" int64_t b4c_attn_bwd_workspace_bytes(int B, int S, int H, int dh, int dtype) {
     return dtype == B4C_BF16 ? b4c_attn_bwd_mfma_workspace_bytes(B, S, H, dh) : 0;
 }
 
-static int attn_bwd_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
-                        const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B,
-                        int S, int H, int dh, void *workspace, int64_t workspace_bytes, float rate, uint64_t seed, bool causal,
-                        int dtype, void *stream) {
-    B4C_REQUIRE(qkv && key_pad && o && d_o && lse && delta && dqkv, "%s: null pointer", who);
-    int rc = check_attn(who, ld_qkv, ld_o, B, S, H, dh);
-    if (rc) return rc;
-    B4C_REQUIRE(ld_do >= H * dh && ld_do % 8 == 0 && ld_dqkv >= 3 * H * dh && ld_dqkv % 8 == 0, "%s: bad pitch", who);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == B4C_BF16) {
-        rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
-                               workspace_bytes, nullptr, rate, seed, causal, st);
-        if (rc != B4C_EUNSUPPORTED) return rc;
-        note_row_fallback(who, S, dh);
-    }
-    const float sq = sqrtf((float)dh);
-    dim3 grid((S + 255) / 256, B * H);
-    if (dtype == B4C_F32) {
-        ATT_DISPATCH(dh, attn_bwd_dq_kernel, float, <<<grid, 256, 0, st>>>((const float *)qkv, ld_qkv, key_pad, (const float *)o, ld_o, (const float *)d_o, ld_do, lse, delta, (float *)dqkv, ld_dqkv, S, H, sq, rate, seed))
-        ATT_DISPATCH(dh, attn_bwd_dkv_kernel, float, <<<grid, 256, 0, st>>>((const float *)qkv, ld_qkv, key_pad, (const float *)d_o, ld_do, lse, delta, (float *)dqkv, ld_dqkv, S, H, sq, rate, seed))
-    } else if (dtype == B4C_BF16) {
-        ATT_DISPATCH(dh, attn_bwd_dq_kernel, bf16_t, <<<grid, 256, 0, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, delta, (bf16_t *)dqkv, ld_dqkv, S, H, sq, rate, seed))
-        ATT_DISPATCH(dh, attn_bwd_dkv_kernel, bf16_t, <<<grid, 256, 0, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)d_o, ld_do, lse, delta, (bf16_t *)dqkv, ld_dqkv, S, H, sq, rate, seed))
-    } else
-        B4C_REQUIRE(false, "%s: dtype %d", who, dtype);
-    return b4c_check_launch(who);
+// ---- the entry points of include/b4c.h: each fixes what its name leaves out (dense: no cu_seqlens; no _drop: rate 0; never causal)
+// and is otherwise the call above.  A _varlen entry point without cu_seqlens is a null pointer, not a dense launch.
+extern "C" int b4c_attn_fwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
+                            int S, int H, int dh, int dtype, void *stream) {
+    return attn_fwd_launch("attn_fwd", qkv, ld_qkv, key_pad, nullptr, o, ld_o, lse, B, S, H, dh, 0.f, 0, false, dtype, stream);
+}
+
+extern "C" int b4c_attn_fwd_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, void *o, int ld_o, float *lse, int B,
+                                 int S, int H, int dh, int dtype, void *stream, float dropout_rate, uint64_t seed) {
+    if (int rc = check_attn_rate("attn_fwd_drop", dropout_rate)) return rc;
+    return attn_fwd_launch("attn_fwd_drop", qkv, ld_qkv, key_pad, nullptr, o, ld_o, lse, B, S, H, dh, dropout_rate, seed, false, dtype, stream);
+}
+
+extern "C" int b4c_attn_fwd_varlen(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
+                                   float *lse, int B, int max_len, int H, int dh, int dtype, void *stream) {
+    B4C_REQUIRE(cu_seqlens, "attn_fwd_varlen: null pointer");
+    return attn_fwd_launch("attn_fwd_varlen", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, max_len, H, dh, 0.f, 0, false, dtype, stream);
+}
+
+extern "C" int b4c_attn_fwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o,
+                                        int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype, void *stream,
+                                        float dropout_rate, uint64_t seed) {
+    if (int rc = check_attn_rate("attn_fwd_varlen_drop", dropout_rate)) return rc;
+    B4C_REQUIRE(cu_seqlens, "attn_fwd_varlen_drop: null pointer");
+    return attn_fwd_launch("attn_fwd_varlen_drop", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, max_len, H, dh, dropout_rate, seed,
+                           false, dtype, stream);
 }
 
 extern "C" int b4c_attn_bwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
@@ -361,117 +382,57 @@ extern "C" int b4c_attn_bwd(const void *qkv, int ld_qkv, const uint8_t *key_pad,
 extern "C" int b4c_attn_bwd_ws(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
                                const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B,
                                int S, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype, void *stream) {
-    return attn_bwd_any("attn_bwd", qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
-                        workspace_bytes, 0.f, 0, false, dtype, stream);
+    return attn_bwd_launch("attn_bwd", qkv, ld_qkv, key_pad, nullptr, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
+                           workspace_bytes, 0.f, 0, false, dtype, stream);
 }
 
 extern "C" int b4c_attn_bwd_drop_ws(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o,
                                     const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B,
                                     int S, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype, void *stream,
                                     float dropout_rate, uint64_t seed) {
-    int rc = check_attn_rate("attn_bwd_drop", dropout_rate);
-    if (rc) return rc;
-    return attn_bwd_any("attn_bwd_drop", qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
-                        workspace_bytes, dropout_rate, seed, false, dtype, stream);
-}
-
-
-// ---- packed (padding-free) layout: sequence b owns rows cu_seqlens[b] .. cu_seqlens[b+1] of qkv / o / d_o / dqkv; max_len is
-// the longest sequence (LDS sizing, lse / delta pitch: [B][H][max_len]).  bf16, head depth 32 / 64, max_len <= 512 only: the
-// packed layout exists for the throughput path, the fp32 parity path stays dense.  key_pad [total tokens]: all zeros unless
-// the caller keeps masked keys inside the packed rows.
-static int attn_fwd_varlen_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o,
-                               int ld_o, float *lse, int B, int max_len, int H, int dh, float rate, uint64_t seed, bool causal,
-                               int dtype, void *stream) {
-    B4C_REQUIRE(qkv && key_pad && cu_seqlens && o, "%s: null pointer", who);
-    int rc = check_attn(who, ld_qkv, ld_o, B, max_len, H, dh);
-    if (rc) return rc;
-    B4C_REQUIRE(dtype == B4C_BF16, "%s: bf16 only", who);
-    rc = b4c_attn_fwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, lse, B, max_len, H, dh, cu_seqlens, rate, seed, causal, (hipStream_t)stream);
-    B4C_REQUIRE(rc != B4C_EUNSUPPORTED, "%s: max_len %d / head depth %d outside the MFMA kernels (<= 512, 32 or 64)", who, max_len, dh);
-    return rc;
-}
-
-extern "C" int b4c_attn_fwd_varlen(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
-                                   float *lse, int B, int max_len, int H, int dh, int dtype, void *stream) {
-    return attn_fwd_varlen_any("attn_fwd_varlen", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, max_len, H, dh, 0.f, 0, false, dtype, stream);
-}
-
-extern "C" int b4c_attn_fwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o,
-                                        int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype, void *stream,
-                                        float dropout_rate, uint64_t seed) {
-    int rc = check_attn_rate("attn_fwd_varlen_drop", dropout_rate);
-    if (rc) return rc;
-    return attn_fwd_varlen_any("attn_fwd_varlen_drop", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, max_len, H, dh, dropout_rate,
-                               seed, false, dtype, stream);
-}
-
-static int attn_bwd_varlen_any(const char *who, const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens,
-                               const void *o, int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv,
-                               int ld_dqkv, int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes, float rate,
-                               uint64_t seed, bool causal, int dtype, void *stream) {
-    B4C_REQUIRE(qkv && key_pad && cu_seqlens && o && d_o && lse && delta && dqkv, "%s: null pointer", who);
-    int rc = check_attn(who, ld_qkv, ld_o, B, max_len, H, dh);
-    if (rc) return rc;
-    B4C_REQUIRE(dtype == B4C_BF16, "%s: bf16 only", who);
-    B4C_REQUIRE(ld_do >= H * dh && ld_do % 8 == 0 && ld_dqkv >= 3 * H * dh && ld_dqkv % 8 == 0, "%s: bad pitch", who);
-    rc = b4c_attn_bwd_mfma(qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, max_len, H, dh, workspace,
-                           workspace_bytes, cu_seqlens, rate, seed, causal, (hipStream_t)stream);
-    B4C_REQUIRE(rc != B4C_EUNSUPPORTED, "%s: shape outside the MFMA kernels, or workspace missing for max_len > 256", who);
-    return rc;
+    if (int rc = check_attn_rate("attn_bwd_drop", dropout_rate)) return rc;
+    return attn_bwd_launch("attn_bwd_drop", qkv, ld_qkv, key_pad, nullptr, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh,
+                           workspace, workspace_bytes, dropout_rate, seed, false, dtype, stream);
 }
 
 extern "C" int b4c_attn_bwd_varlen(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, const void *o,
                                    int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv,
                                    int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype,
                                    void *stream) {
-    return attn_bwd_varlen_any("attn_bwd_varlen", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B,
-                               max_len, H, dh, workspace, workspace_bytes, 0.f, 0, false, dtype, stream);
+    B4C_REQUIRE(cu_seqlens, "attn_bwd_varlen: null pointer");
+    return attn_bwd_launch("attn_bwd_varlen", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, max_len,
+                           H, dh, workspace, workspace_bytes, 0.f, 0, false, dtype, stream);
 }
 
 extern "C" int b4c_attn_bwd_varlen_drop(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, const void *o,
                                         int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv,
                                         int ld_dqkv, int B, int max_len, int H, int dh, void *workspace, int64_t workspace_bytes,
                                         int dtype, void *stream, float dropout_rate, uint64_t seed) {
-    int rc = check_attn_rate("attn_bwd_varlen_drop", dropout_rate);
-    if (rc) return rc;
-    return attn_bwd_varlen_any("attn_bwd_varlen_drop", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv,
-                               B, max_len, H, dh, workspace, workspace_bytes, dropout_rate, seed, false, dtype, stream);
+    if (int rc = check_attn_rate("attn_bwd_varlen_drop", dropout_rate)) return rc;
+    B4C_REQUIRE(cu_seqlens, "attn_bwd_varlen_drop: null pointer");
+    return attn_bwd_launch("attn_bwd_varlen_drop", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B,
+                           max_len, H, dh, workspace, workspace_bytes, dropout_rate, seed, false, dtype, stream);
 }
 
 // ---- one entry point per direction that takes everything (include/b4c_attn_ex.h): layout by cu_seqlens (NULL: dense), dropout by the
 // rate, causal masking by flags.  flags == 0 reaches exactly the launches of the entry points above.
-static int check_attn_flags(const char *who, uint32_t flags) {
-    B4C_REQUIRE((flags & ~B4C_ATTN_CAUSAL) == 0, "%s: unknown flag bits 0x%x", who, flags & ~B4C_ATTN_CAUSAL);
-    return B4C_OK;
-}
-
 extern "C" int b4c_attn_fwd_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
                                float *lse, int B, int S, int H, int dh, int dtype, void *stream, float dropout_rate, uint64_t seed,
                                uint32_t flags) {
-    int rc = check_attn_flags("attn_fwd_ex", flags);
-    if (!rc) rc = check_attn_rate("attn_fwd_ex", dropout_rate);
-    if (rc) return rc;
-    const bool causal = (flags & B4C_ATTN_CAUSAL) != 0;
-    if (cu_seqlens)
-        return attn_fwd_varlen_any("attn_fwd_ex", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, S, H, dh, dropout_rate, seed, causal,
-                                   dtype, stream);
-    return attn_fwd_any("attn_fwd_ex", qkv, ld_qkv, key_pad, o, ld_o, lse, B, S, H, dh, dropout_rate, seed, causal, dtype, stream);
+    if (int rc = check_attn_flags("attn_fwd_ex", flags)) return rc;
+    if (int rc = check_attn_rate("attn_fwd_ex", dropout_rate)) return rc;
+    return attn_fwd_launch("attn_fwd_ex", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, lse, B, S, H, dh, dropout_rate, seed,
+                           (flags & B4C_ATTN_CAUSAL) != 0, dtype, stream);
 }
 
 extern "C" int b4c_attn_bwd_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, const void *o,
                                int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv,
                                int B, int S, int H, int dh, void *workspace, int64_t workspace_bytes, int dtype, void *stream,
                                float dropout_rate, uint64_t seed, uint32_t flags) {
-    int rc = check_attn_flags("attn_bwd_ex", flags);
-    if (!rc) rc = check_attn_rate("attn_bwd_ex", dropout_rate);
-    if (rc) return rc;
-    const bool causal = (flags & B4C_ATTN_CAUSAL) != 0;
-    if (cu_seqlens)
-        return attn_bwd_varlen_any("attn_bwd_ex", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B,
-                                   S, H, dh, workspace, workspace_bytes, dropout_rate, seed, causal, dtype, stream);
-    return attn_bwd_any("attn_bwd_ex", qkv, ld_qkv, key_pad, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh, workspace,
-                        workspace_bytes, dropout_rate, seed, causal, dtype, stream);
+    if (int rc = check_attn_flags("attn_bwd_ex", flags)) return rc;
+    if (int rc = check_attn_rate("attn_bwd_ex", dropout_rate)) return rc;
+    return attn_bwd_launch("attn_bwd_ex", qkv, ld_qkv, key_pad, cu_seqlens, o, ld_o, d_o, ld_do, lse, delta, dqkv, ld_dqkv, B, S, H, dh,
+                           workspace, workspace_bytes, dropout_rate, seed, (flags & B4C_ATTN_CAUSAL) != 0, dtype, stream);
 }
 
 // the keep rule of the *_drop entry points on the host (common.h: b4c_attn_keep_elem)

@@ -807,22 +807,10 @@ int b4c_attn_fwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, void 
     const int qpw = S_pad > 32 * ATT_MAX_KT ? 2 : 1;
     const size_t shm = 2 * (size_t)S_pad * (dh * 2 + 16) + (size_t)S_pad * 4 + ATT_MAX_KT * qpw * 4;
     const float scale = 1.0f / sqrtf((float)dh);
-#define ATT_FWD_LAUNCH(DHH, QQ, DR, CA)                                                                                  \
-    do {                                                                                                                 \
-        b4c_allow_lds(attn_fwd_mfma_kernel<DHH, QQ, DR, CA>, shm);                                                     \
-        attn_fwd_mfma_kernel<DHH, QQ, DR, CA><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, scale, cu, rate, seed); \
-    } while (0)
-#define ATT_FWD_LAUNCH_Q(DHH, DR, CA)                                                                                    \
-    do { if (qpw == 1) ATT_FWD_LAUNCH(DHH, 1, DR, CA); else ATT_FWD_LAUNCH(DHH, 2, DR, CA); } while (0)
-#define ATT_FWD_LAUNCH_DH(DHH)                                                                                           \
-    do {                                                                                                                 \
-        if (!causal) { if (rate == 0.f) ATT_FWD_LAUNCH_Q(DHH, false, false); else ATT_FWD_LAUNCH_Q(DHH, true, false); }  \
-        else { if (rate == 0.f) ATT_FWD_LAUNCH_Q(DHH, false, true); else ATT_FWD_LAUNCH_Q(DHH, true, true); }            \
-    } while (0)
-    if (dh == 64) ATT_FWD_LAUNCH_DH(64); else ATT_FWD_LAUNCH_DH(32);
-#undef ATT_FWD_LAUNCH_DH
-#undef ATT_FWD_LAUNCH_Q
-#undef ATT_FWD_LAUNCH
+    b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_int<1, 2>(qpw, [&](auto Q) { b4c_by_bool(rate != 0.f, [&](auto DR) { b4c_by_bool(causal, [&](auto CA) {
+        b4c_allow_lds(attn_fwd_mfma_kernel<DH(), Q(), DR(), CA()>, shm);
+        attn_fwd_mfma_kernel<DH(), Q(), DR(), CA()><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (bf16_t *)o, ld_o, lse, S, H, scale, cu, rate, seed);
+    }); }); }); });
     return b4c_check_launch("attn_fwd_mfma");
 }
 
@@ -837,23 +825,16 @@ int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const
                       hipStream_t st) {
     if (!mfma_shape_ok(S, dh)) return B4C_EUNSUPPORTED;
     const float scale = 1.0f / sqrtf((float)dh);
-#define ATT_BWD_BLOCKS(DHH, DR, CA, SHM, NBLK, ACC)                                                                      \
-    do {                                                                                                                 \
-        b4c_allow_lds(attn_bwd_mfma_kernel<DHH, DR, CA>, SHM);                                                         \
-        attn_bwd_mfma_kernel<DHH, DR, CA><<<B * H, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, NBLK, ACC, cu, rate, seed); \
-    } while (0)
-#define ATT_BWD_RESIDENT(DHH, DR, CA, SHM, GRID)                                                                         \
-    do {                                                                                                                 \
-        b4c_allow_lds(attn_bwd_resident_kernel<DHH, DR, CA>, SHM);                                                     \
-        attn_bwd_resident_kernel<DHH, DR, CA><<<GRID, 512, SHM, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, B * H, (int *)delta, cu, rate, seed); \
-    } while (0)
-#define ATT_BWD_SELECT_DR(LAUNCH, DHH, CA, ...)                                                                          \
-    do { if (rate == 0.f) LAUNCH(DHH, false, CA, __VA_ARGS__); else LAUNCH(DHH, true, CA, __VA_ARGS__); } while (0)
-#define ATT_BWD_SELECT(LAUNCH, ...)                                                                                      \
-    do {                                                                                                                 \
-        if (dh == 64) { if (!causal) ATT_BWD_SELECT_DR(LAUNCH, 64, false, __VA_ARGS__); else ATT_BWD_SELECT_DR(LAUNCH, 64, true, __VA_ARGS__); } \
-        else { if (!causal) ATT_BWD_SELECT_DR(LAUNCH, 32, false, __VA_ARGS__); else ATT_BWD_SELECT_DR(LAUNCH, 32, true, __VA_ARGS__); }          \
-    } while (0)
+    // launch(DH, DR, CA) with the head depth, rate != 0 and causal as constants
+    auto select = [&](auto launch) {
+        b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) { b4c_by_bool(causal, [&](auto CA) { launch(DH, DR, CA); }); }); });
+    };
+    auto blocks = [&](size_t shm, int nblk, float *acc) {
+        select([&](auto DH, auto DR, auto CA) {
+            b4c_allow_lds(attn_bwd_mfma_kernel<DH(), DR(), CA()>, shm);
+            attn_bwd_mfma_kernel<DH(), DR(), CA()><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, nblk, acc, cu, rate, seed);
+        });
+    };
     if (S > 32 * ATT_MAX_KT) {
         // the blocks of 256 keys one after the other inside one launch; their partial dQ sums meet in an fp32 accumulator
         // (caller's workspace)
@@ -861,7 +842,7 @@ int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const
         const size_t kstr2 = dh * 2 + 16, tstr2 = 256 * 2 + 16;
         const size_t shm2 = 2 * 256 * kstr2 + 2 * (2 * 32 * kstr2 + 256) + 32 * tstr2;
         const int nblk = (S + 255) / 256;
-        ATT_BWD_SELECT(ATT_BWD_BLOCKS, shm2, nblk, (float *)workspace);
+        blocks(shm2, nblk, (float *)workspace);
         return b4c_check_launch("attn_bwd_mfma (key blocks)");
     }
     const int S_pad = (S + 31) / 32 * 32;
@@ -872,13 +853,12 @@ int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const
         const int grid_res = B * H < att_num_cus() ? B * H : att_num_cus();   // > 80 KB of LDS: one workgroup per CU
         // delta itself is computed while staging dO / O; its first word is the work counter of the persistent grid
         if (hipMemsetAsync(delta, 0, sizeof(int), st) != hipSuccess) return B4C_ELAUNCH;
-        ATT_BWD_SELECT(ATT_BWD_RESIDENT, shm_res, grid_res);
+        select([&](auto DH, auto DR, auto CA) {
+            b4c_allow_lds(attn_bwd_resident_kernel<DH(), DR(), CA()>, shm_res);
+            attn_bwd_resident_kernel<DH(), DR(), CA()><<<grid_res, 512, shm_res, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, B * H, (int *)delta, cu, rate, seed);
+        });
         return b4c_check_launch("attn_bwd_resident");
     }
-    ATT_BWD_SELECT(ATT_BWD_BLOCKS, shm, 1, (float *)nullptr);
-#undef ATT_BWD_SELECT
-#undef ATT_BWD_SELECT_DR
-#undef ATT_BWD_RESIDENT
-#undef ATT_BWD_BLOCKS
+    blocks(shm, 1, nullptr);
     return b4c_check_launch("attn_bwd_mfma");
 }

@@ -750,12 +750,6 @@ static int mq_check_drop(const char *who, const int32_t *q_rows, float rate) {
 }
 
 // rate == 0 launches the DROP = false instantiations: the kernels of the entry points without dropout
-#define MQ_BY_RATE(LAUNCH, ...)                            \
-    do {                                                   \
-        if (rate == 0.f) LAUNCH(__VA_ARGS__, false);       \
-        else LAUNCH(__VA_ARGS__, true);                    \
-    } while (0)
-
 static int mq_fwd_any(const char *who, const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
                       const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype, void *stream,
                       const int32_t *q_rows, float rate, uint64_t seed) {
@@ -769,24 +763,19 @@ static int mq_fwd_any(const char *who, const void *q, int ld_q, const void *kv, 
         const int n_items = B * H;
         const size_t shm_m = (size_t)MQ_WAVES * 2 * 32 * (dh * 2 + 16);
         const int grid = (n_items + MQ_WAVES - 1) / MQ_WAVES;
-#define MQ_MFMA(DHH, PP, DR)                                                                                                         \
-    attn_mq_fwd_mfma_kernel<DHH, PP, DR><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens, \
-                                                                       q_offsets, (bf16_t *)o, ld_o, lse, H, n_items, 1.0f / sq, q_rows, max_len, rate, seed)
-        if (dh == 64) { if (key_pad) MQ_BY_RATE(MQ_MFMA, 64, true); else MQ_BY_RATE(MQ_MFMA, 64, false); }
-        else { if (key_pad) MQ_BY_RATE(MQ_MFMA, 32, true); else MQ_BY_RATE(MQ_MFMA, 32, false); }
-#undef MQ_MFMA
+        b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(key_pad != nullptr, [&](auto PP) { b4c_by_bool(rate != 0.f, [&](auto DR) {
+            attn_mq_fwd_mfma_kernel<DH(), PP(), DR()><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens,
+                                                                                  q_offsets, (bf16_t *)o, ld_o, lse, H, n_items, 1.0f / sq, q_rows, max_len, rate, seed);
+        }); }); });
         return b4c_check_launch(who);
     }
     const size_t shm = mq_fwd_lds(SP, dh, sizeof(float));
     B4C_REQUIRE(shm <= 160 * 1024, "%s: max_len %d needs %zu bytes of LDS", who, max_len, shm);
-#define MQ_FWD(TT, DHH, DR)                                                                                                          \
-    do {                                                                                                                             \
-        b4c_allow_lds(attn_mq_fwd_kernel<TT, DHH, DR>, shm);                                                                         \
-        attn_mq_fwd_kernel<TT, DHH, DR><<<B * H, MQ_THREADS, shm, st>>>((const TT *)q, ld_q, (const TT *)kv, ld_kv, key_pad, cu_seqlens, q_offsets, \
-                                                                 (TT *)o, ld_o, lse, H, SP, sq, q_rows, max_len, rate, seed);        \
-    } while (0)
-    if (dh == 64) MQ_BY_RATE(MQ_FWD, float, 64); else MQ_BY_RATE(MQ_FWD, float, 32);
-#undef MQ_FWD
+    b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) {
+        b4c_allow_lds(attn_mq_fwd_kernel<float, DH(), DR()>, shm);
+        attn_mq_fwd_kernel<float, DH(), DR()><<<B * H, MQ_THREADS, shm, st>>>((const float *)q, ld_q, (const float *)kv, ld_kv, key_pad, cu_seqlens, q_offsets,
+                                                                       (float *)o, ld_o, lse, H, SP, sq, q_rows, max_len, rate, seed);
+    }); });
     return b4c_check_launch(who);
 }
 
@@ -820,29 +809,22 @@ static int mq_bwd_any(const char *who, const void *q, int ld_q, const void *kv, 
     if (dtype == B4C_BF16) {      // matrix-core form, one wave per (sequence, head)
         const int n_items = B * H, kstr = dh * 2 + 16;
         const int grid = (n_items + MQ_WAVES - 1) / MQ_WAVES;
-#define MQ_MFMA_B(DHH, PP, DR)                                                                                                       \
-    do {                                                                                                                             \
-        const size_t shm_m = (size_t)MQ_WAVES * (3 * 32 * kstr + 32 * (32 * 2 + 16) + (DR ? 3 : 2) * 32 * 4);                        \
-        b4c_allow_lds(attn_mq_bwd_mfma_kernel<DHH, PP, DR>, shm_m);                                                                  \
-        attn_mq_bwd_mfma_kernel<DHH, PP, DR><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens, \
-            q_offsets, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dq, ld_dq, (bf16_t *)dkv, ld_dkv, H, n_items, 1.0f / sq, \
-            q_rows, max_len, rate, seed);                                                                                            \
-    } while (0)
-        if (dh == 64) { if (key_pad) MQ_BY_RATE(MQ_MFMA_B, 64, true); else MQ_BY_RATE(MQ_MFMA_B, 64, false); }
-        else { if (key_pad) MQ_BY_RATE(MQ_MFMA_B, 32, true); else MQ_BY_RATE(MQ_MFMA_B, 32, false); }
-#undef MQ_MFMA_B
+        b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(key_pad != nullptr, [&](auto PP) { b4c_by_bool(rate != 0.f, [&](auto DR) {
+            const size_t shm_m = (size_t)MQ_WAVES * (3 * 32 * kstr + 32 * (32 * 2 + 16) + (DR() ? 3 : 2) * 32 * 4);
+            b4c_allow_lds(attn_mq_bwd_mfma_kernel<DH(), PP(), DR()>, shm_m);
+            attn_mq_bwd_mfma_kernel<DH(), PP(), DR()><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens,
+                q_offsets, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dq, ld_dq, (bf16_t *)dkv, ld_dkv, H, n_items, 1.0f / sq,
+                q_rows, max_len, rate, seed);
+        }); }); });
         return b4c_check_launch(who);
     }
-#define MQ_BWD(TT, DHH, DR)                                                                                                          \
-    do {                                                                                                                             \
-        const size_t shm = mq_bwd_lds(dh, sizeof(float), DR);                                                                        \
-        b4c_allow_lds(attn_mq_bwd_kernel<TT, DHH, DR>, shm);                                                                         \
-        attn_mq_bwd_kernel<TT, DHH, DR><<<B * H, MQ_THREADS, shm, st>>>((const TT *)q, ld_q, (const TT *)kv, ld_kv, key_pad, cu_seqlens, q_offsets, \
-                                                                 (const TT *)o, ld_o, (const TT *)d_o, ld_do, lse, (TT *)dq, ld_dq,  \
-                                                                 (TT *)dkv, ld_dkv, H, sq, q_rows, max_len, rate, seed);             \
-    } while (0)
-    if (dh == 64) MQ_BY_RATE(MQ_BWD, float, 64); else MQ_BY_RATE(MQ_BWD, float, 32);
-#undef MQ_BWD
+    b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) {
+        const size_t shm = mq_bwd_lds(dh, sizeof(float), DR());
+        b4c_allow_lds(attn_mq_bwd_kernel<float, DH(), DR()>, shm);
+        attn_mq_bwd_kernel<float, DH(), DR()><<<B * H, MQ_THREADS, shm, st>>>((const float *)q, ld_q, (const float *)kv, ld_kv, key_pad, cu_seqlens, q_offsets,
+                                                                       (const float *)o, ld_o, (const float *)d_o, ld_do, lse, (float *)dq, ld_dq,
+                                                                       (float *)dkv, ld_dkv, H, sq, q_rows, max_len, rate, seed);
+    }); });
     return b4c_check_launch(who);
 }
 

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/b4c.h"
 
 typedef __bf16 bf16_t;
@@ -50,6 +52,17 @@ template <typename K> static void b4c_allow_lds(K kernel, size_t bytes) {
     if (i < ndone && done_bytes[i] >= bytes) return;
     (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (i < CAP) { done[i] = (const void *)kernel; done_bytes[i] = bytes; if (i == ndone) ++ndone; }
+}
+
+// A run-time value as a template argument: f is called with std::true_type / std::false_type, or with the
+// std::integral_constant<int, V> of the listed V that v equals (returns false, f not called, when v is none of them).  Nested, they
+// take the place of one macro ladder per launcher; the launch statement is written once, inside the innermost lambda:
+//   b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(causal, [&](auto CA) { kernel<DH(), CA()><<<grid, block, 0, st>>>(...); }); });
+template <typename F> static inline void b4c_by_bool(bool v, F &&f) {
+    if (v) f(std::true_type{}); else f(std::false_type{});
+}
+template <int... Vs, typename F> static inline bool b4c_by_int(int v, F &&f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
 }
 
 // ---- element IO: 8 consecutive elements <-> 8 floats (16 B for bf16, 32 B for fp32) ----

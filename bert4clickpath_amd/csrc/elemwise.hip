@@ -406,11 +406,11 @@ static int attn_weights_any(const void *qkv, int ld_qkv, const uint8_t *key_pad,
     dim3 grid((S + 63) / 64, (S + 63) / 64, B * H);
     const size_t shm = (size_t)2 * 64 * (dh + 1) * sizeof(float);
     const float sq = sqrtf((float)dh);
-#define ATT_W_LAUNCH(T, CA) attn_weights_kernel<T, CA><<<grid, 256, shm, st>>>((const T *)qkv, ld_qkv, key_pad, lse, weights, S, H, dh, sq)
-    if (dtype == B4C_F32) { if (causal) ATT_W_LAUNCH(float, true); else ATT_W_LAUNCH(float, false); }
-    else if (dtype == B4C_BF16) { if (causal) ATT_W_LAUNCH(bf16_t, true); else ATT_W_LAUNCH(bf16_t, false); }
-    else B4C_REQUIRE(false, "attn_weights: dtype %d", dtype);
-#undef ATT_W_LAUNCH
+    B4C_REQUIRE(dtype == B4C_F32 || dtype == B4C_BF16, "attn_weights: dtype %d", dtype);
+    b4c_by_bool(causal, [&](auto CA) {
+        if (dtype == B4C_F32) attn_weights_kernel<float, CA()><<<grid, 256, shm, st>>>((const float *)qkv, ld_qkv, key_pad, lse, weights, S, H, dh, sq);
+        else attn_weights_kernel<bf16_t, CA()><<<grid, 256, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, lse, weights, S, H, dh, sq);
+    });
     return b4c_check_launch("attn_weights");
 }
 

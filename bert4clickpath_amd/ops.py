@@ -894,13 +894,6 @@ def _tied_table_steps_whole(table):
         lz.all_rows = True
 
 
-def _attn_call(stem, args, varlen=False, drop=False, dense_suffix=''):
-    """One launch of the attention family `stem`: b4c_<stem>[_varlen][_drop], chosen by the layout (cu given: _varlen) and by
-    whether dropout is on (rate 0 is the entry point without dropout); `args` is that entry point's list."""
-    name = stem + ('_varlen' if varlen else '') + ('_drop' if drop else '')
-    L.check(getattr(L.lib(), 'b4c_' + name + ('' if varlen else dense_suffix))(*args), name)
-
-
 def _attn_mq_drop(q_rows, rate):
     rate = _attn_rate(rate)
     if rate > 0 and q_rows is None:
@@ -909,9 +902,10 @@ def _attn_mq_drop(q_rows, rate):
 
 
 def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None, q_rows=None, rate=0.0, seed=0):
-    """Attention of a few query rows per sequence against all of its keys (b4c_attn_mq_fwd).
+    """Attention of a few query rows per sequence against all of its keys (b4c_attn_mq_fwd_drop; rate 0 launches the kernels of
+    b4c_attn_mq_fwd).
     q [R, H*dh]; kv [T, 2*H*dh] (k | v); cu [B+1] token offsets; moff [B+1] query-row offsets -> (o [R, H*dh], lse [R, H]).
-    rate > 0 (b4c_attn_mq_fwd_drop): dropout on the attention probabilities with the masks attn_fwd(..., rate, seed) draws for the
+    rate > 0: dropout on the attention probabilities with the masks attn_fwd(..., rate, seed) draws for the
     token rows q_rows [R] (int32; an unused row holds -1): b4c_attn_keep(seed, b, h, q_rows[r] - cu[b], k, H, max_len, rate)."""
     rate = _attn_mq_drop(q_rows, rate)
     R = q.shape[0]
@@ -923,9 +917,8 @@ def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None, q_rows=None, r
     es = q.element_size()
     # algorithmic work: every query row against the keys of its own sequence (host hint; R x max_len is an upper bound)
     with _record('attn_mq_fwd', kv.shape[0] * 2 * H * dh * es + 2 * R * H * dh * es, 4 * rec_hints.get('sum_q_len', R * max_len) * H * dh):
-        args = [_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0), _p(lse), B, max_len, H, dh,
-                dt_code(q.dtype), _st()]
-        _attn_call('attn_mq_fwd', args + ([_p(q_rows), rate, seed] if rate > 0 else []), drop=rate > 0)
+        L.check(L.lib().b4c_attn_mq_fwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
+                                             _p(lse), B, max_len, H, dh, dt_code(q.dtype), _st(), _p(q_rows), rate, seed), 'attn_mq_fwd_drop')
     return o, lse
 
 
@@ -942,9 +935,9 @@ def attn_mq_bwd(q, kv, cu, moff, o, d_o, lse, B, max_len, H, dh, key_pad=None, q
         return dq, dkv
     es = q.element_size()
     with _record('attn_mq_bwd', kv.shape[0] * 4 * H * dh * es + 4 * R * H * dh * es, 10 * rec_hints.get('sum_q_len', R * max_len) * H * dh):
-        args = [_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
-                _p(lse), _p(dq), dq.stride(0), _p(dkv), dkv.stride(0), B, max_len, H, dh, dt_code(q.dtype), _st()]
-        _attn_call('attn_mq_bwd', args + ([_p(q_rows), rate, seed] if rate > 0 else []), drop=rate > 0)
+        L.check(L.lib().b4c_attn_mq_bwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
+                                             _p(d_o), d_o.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dkv), dkv.stride(0), B, max_len, H, dh,
+                                             dt_code(q.dtype), _st(), _p(q_rows), rate, seed), 'attn_mq_bwd_drop')
     return dq, dkv
 
 
@@ -969,22 +962,18 @@ def _attn_pairs(T_tok, S, cu, causal):
 def attn_fwd(qkv, key_pad, B, S, H, dh, cu=None, rate=0.0, seed=0, causal=False):
     """cu (int32 [B+1]): packed layout -- sequence b owns rows cu[b] .. cu[b+1] of qkv, S = upper bound of the longest one.
     rate > 0: dropout on the attention probabilities, mask b4c_attn_keep(seed, b, h, q, k, H, S, rate) (include/b4c.h); lse is that
-    of the undropped softmax.  rate == 0 is the call without dropout.
-    causal: key k is visible to query q iff k <= q (b4c_attn_fwd_ex with B4C_ATTN_CAUSAL); lse is over the visible keys.  Without
-    it the call is the one it has always been."""
+    of the undropped softmax.  rate == 0 launches the kernels without dropout.
+    causal: key k is visible to query q iff k <= q (B4C_ATTN_CAUSAL); lse is over the visible keys.
+    Always b4c_attn_fwd_ex: the layout, the rate and the flags select the launch, and cu = None, rate = 0, flags = 0 is the
+    launch of b4c_attn_fwd."""
     rate = _attn_rate(rate)
     d = H * dh
     T_tok = qkv.shape[0]
     o = torch.empty(T_tok, d, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(B, H, S, dtype=torch.float32, device=qkv.device)
     with _record('attn_fwd', T_tok * 4 * d * qkv.element_size(), 4 * _attn_pairs(T_tok, S, cu, causal) * d):
-        if causal:
-            L.check(L.lib().b4c_attn_fwd_ex(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), d, _p(lse), B, S, H, dh,
-                                            dt_code(qkv.dtype), _st(), rate, seed, ATTN_CAUSAL), 'attn_fwd_ex')
-            return o, lse
-        args = [_p(qkv), qkv.stride(0), _p(key_pad)] + ([] if cu is None else [_p(cu)]) + \
-            [_p(o), d, _p(lse), B, S, H, dh, dt_code(qkv.dtype), _st()]
-        _attn_call('attn_fwd', args + ([rate, seed] if rate > 0 else []), varlen=cu is not None, drop=rate > 0)
+        L.check(L.lib().b4c_attn_fwd_ex(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), d, _p(lse), B, S, H, dh,
+                                        dt_code(qkv.dtype), _st(), rate, seed, ATTN_CAUSAL if causal else 0), 'attn_fwd_ex')
     return o, lse
 
 
@@ -998,17 +987,9 @@ def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None, rate=0.
     ws = _workspace('attn_bwd', qkv.device, need) if need else None
     T_tok = qkv.shape[0]
     with _record('attn_bwd', T_tok * 8 * H * dh * qkv.element_size(), 10 * _attn_pairs(T_tok, S, cu, causal) * H * dh):
-        if causal:
-            L.check(L.lib().b4c_attn_bwd_ex(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
-                                            _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
-                                            dt_code(qkv.dtype), _st(), rate, seed, ATTN_CAUSAL), 'attn_bwd_ex')
-        else:
-            args = [_p(qkv), qkv.stride(0), _p(key_pad)] + ([] if cu is None else [_p(cu)]) + \
-                [_p(o), o.stride(0), _p(d_o), d_o.stride(0), _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
-                 dt_code(qkv.dtype), _st()]
-            # (the dense entry points that take the workspace are b4c_attn_bwd_ws / b4c_attn_bwd_drop_ws)
-            _attn_call('attn_bwd', args + ([rate, seed] if rate > 0 else []), varlen=cu is not None, drop=rate > 0,
-                       dense_suffix='_ws')
+        L.check(L.lib().b4c_attn_bwd_ex(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
+                                        _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
+                                        dt_code(qkv.dtype), _st(), rate, seed, ATTN_CAUSAL if causal else 0), 'attn_bwd_ex')
     _background_kick(actx)      # the next piece of the vocabulary head's dW sweep starts when this kernel has left the CUs
     return dqkv
 
@@ -2855,12 +2836,8 @@ def compact_labels(labels_padded, counts, offsets, cap, flat_idx=None):
 def attn_weights(qkv, key_pad, lse, B, S, H, dh, causal=False):
     """causal: lse is that of attn_fwd(causal=True); the weights of the keys behind the query are exactly 0."""
     w = torch.empty(B, H, S, S, dtype=torch.float32, device=qkv.device)
-    if causal:
-        L.check(L.lib().b4c_attn_weights_ex(_p(qkv), qkv.stride(0), _p(key_pad), _p(lse), _p(w), B, S, H, dh, dt_code(qkv.dtype),
-                                            _st(), ATTN_CAUSAL), 'attn_weights_ex')
-        return w
-    L.check(L.lib().b4c_attn_weights(_p(qkv), qkv.stride(0), _p(key_pad), _p(lse), _p(w), B, S, H, dh, dt_code(qkv.dtype),
-                                     _st()), 'attn_weights')
+    L.check(L.lib().b4c_attn_weights_ex(_p(qkv), qkv.stride(0), _p(key_pad), _p(lse), _p(w), B, S, H, dh, dt_code(qkv.dtype),
+                                        _st(), ATTN_CAUSAL if causal else 0), 'attn_weights_ex')
     return w
 
 

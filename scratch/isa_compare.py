@@ -10,6 +10,14 @@ tests/test_vmcnt_accounting.py reads them).  The assembly is cut per kernel, fro
 of its descriptor (so code, register counts and LDS size all count), the per-translation-unit `__hip_cuid_<hash>` name is
 normalised, and the texts are compared.  Prints one line per file: kernels identical / total, and the names of the rest.
 Exit status 0 iff every kernel of every file is identical and both sides hold the same kernels.
+
+What is compared is the code, not the order in which the compiler emitted it.  A kernel template that is instantiated from
+inside a lambda (the launch dispatchers of csrc/common.h) leaves the compiler at another place in the file than one instantiated
+from a macro ladder, and local labels carry the number of the function they lie in: `.LBB14_2` for `.LBB0_2`, `.Lfunc_end14`, and
+the same names again inside the `; %bb`, loop and register-count comments, whose padding moves with their width.  So per kernel
+the comments are dropped, runs of blanks become one, and the local labels (`.L...`) are renumbered in the order in which the
+kernel first names them -- two kernels still have to branch to the same places.  Every instruction, directive and descriptor
+field (`.amdhsa_next_free_vgpr`, `.amdhsa_group_segment_fixed_size`, ...) is compared as before.
 """
 import argparse
 import concurrent.futures
@@ -63,8 +71,24 @@ _CUID = re.compile(r'__hip_cuid_[0-9a-f]+')
 _LABEL = re.compile(r'^([A-Za-z_$][\w$]*):')       # `name:   ; @name`; local labels begin with a dot
 
 
+_LOCAL = re.compile(r'\.L[\w$.]+')
+
+
+def normalise(lines):
+    """one kernel's lines without comments, blank runs and emission-order label numbers (module docstring)"""
+    seen = {}
+    out = []
+    for l in lines:
+        if '"' not in l:                            # (a `;` inside a string is no comment; such lines are kept whole)
+            l = l.split(';', 1)[0]
+        l = ' '.join(l.split())
+        if l:
+            out.append(_LOCAL.sub(lambda m: seen.setdefault(m.group(0), '.L%d' % len(seen)), l))
+    return '\n'.join(out)
+
+
 def kernels(path):
-    """-> {kernel name: its text, label .. .end_amdhsa_kernel}"""
+    """-> {kernel name: its normalised text, label .. .end_amdhsa_kernel}"""
     lines = [_CUID.sub('__hip_cuid_X', l.rstrip()) for l in open(path, errors='replace')]
     label = {}
     for i, l in enumerate(lines):
@@ -76,7 +100,7 @@ def kernels(path):
         m = re.match(r'\s*\.amdhsa_kernel\s+(\S+)', l)
         if m:
             end = next(j for j in range(i, len(lines)) if lines[j].strip() == '.end_amdhsa_kernel')
-            res[m.group(1)] = '\n'.join(lines[label[m.group(1)]:end + 1])
+            res[m.group(1)] = normalise(lines[label[m.group(1)]:end + 1])
     return res
 
 

@@ -152,14 +152,24 @@ def test_rate_zero_entry_points_equal_the_old_ones(ops, dtype, lens, packed, H, 
     B, S, cu, off, qkv, do, pad = _parity_case(ops, dtype, lens, packed, H, dh, n_pad, 0.0, 0)
     qd, dod, padd = qkv.cuda(), do.cuda(), pad.cuda()
     d = H * dh
-    o0, lse0 = ops.attn_fwd(qd, padd, B, S, H, dh, cu)
-    dq0 = ops.attn_bwd(qd, padd, o0, dod, lse0, B, S, H, dh, cu)
     p, st, dt = ops._p, ops._st(), ops.dt_code(qd.dtype)
+    # the old side: raw calls of the entry points without dropout (ops itself goes through b4c_attn_*_ex)
+    o0 = torch.empty(qd.shape[0], d, dtype=qd.dtype, device='cuda')
+    lse0 = torch.full((B, H, S), float('nan'), dtype=torch.float32, device='cuda')
+    dq0 = torch.empty_like(qd)
     o1, lse1, dq1 = torch.empty_like(o0), torch.full_like(lse0, float('nan')), torch.empty_like(dq0)
     delta = torch.empty_like(lse0)
     need = L.lib().b4c_attn_bwd_workspace_bytes(B, S, H, dh, dt)
     assert (need > 0) == (S > 256)
     ws = torch.empty(max(need, 8), dtype=torch.uint8, device='cuda')
+    if cu is None:
+        L.check(L.lib().b4c_attn_fwd(p(qd), qd.stride(0), p(padd), p(o0), d, p(lse0), B, S, H, dh, dt, st))
+        L.check(L.lib().b4c_attn_bwd_ws(p(qd), qd.stride(0), p(padd), p(o0), d, p(dod), d, p(lse0), p(delta), p(dq0), dq0.stride(0),
+                                        B, S, H, dh, p(ws), need, dt, st))
+    else:
+        L.check(L.lib().b4c_attn_fwd_varlen(p(qd), qd.stride(0), p(padd), p(cu), p(o0), d, p(lse0), B, S, H, dh, dt, st))
+        L.check(L.lib().b4c_attn_bwd_varlen(p(qd), qd.stride(0), p(padd), p(cu), p(o0), d, p(dod), d, p(lse0), p(delta), p(dq0),
+                                            dq0.stride(0), B, S, H, dh, p(ws), need, dt, st))
     seed = 12345                                          # ignored at rate 0
     if cu is None:
         L.check(L.lib().b4c_attn_fwd_drop(p(qd), qd.stride(0), p(padd), p(o1), d, p(lse1), B, S, H, dh, dt, st, 0.0, seed))

@@ -9,7 +9,8 @@ bidirectional attention over prefixes).
    from p on; the weights above the diagonal are 0.
 3. leading pads (queries whose visible keys are all padded): everything finite, the real rows within the bounds.
 4. dropout x causal: the recovered masks are the host's keep bits AND visible AND NOT pad.
-5. flags = 0 of the *_ex entry points: the bits of the existing entry points.
+5. flags = 0 of the *_ex entry points: the bits of raw calls of the existing entry points; ops (which always calls *_ex) without
+   options likewise; a _varlen entry point handed cu_seqlens = NULL stays an error.
 
 Routes (the launch code of attn_mfma.hip): bf16 with head depth 32 / 64 and S <= 512 runs the matrix-core kernels -- forward QPW = 2
 for S > 256; backward resident while its LDS image fits (S <= 224 at depth 64), else blocks of 256 keys with a workspace iff
@@ -350,13 +351,28 @@ def test_flags_zero_is_the_existing_entry_point(ops, lens, packed, rate):
     padd = torch.zeros(T, dtype=torch.uint8, device='cuda')
     if not packed:
         padd = _pads(B, S).reshape(-1).cuda()
-    o0, lse0 = ops.attn_fwd(qd, padd, B, S, H, dh, cu, rate, seed)
-    dq0 = ops.attn_bwd(qd, padd, o0, dod, lse0, B, S, H, dh, cu, None, rate, seed)
     p, st, dt = ops._p, ops._st(), ops.dt_code(qd.dtype)
+    o0 = torch.empty(T, d, dtype=BF16, device='cuda')
+    lse0 = torch.full((B, H, S), float('nan'), dtype=torch.float32, device='cuda')
+    dq0 = torch.empty_like(qd)
     o1, lse1, dq1 = torch.empty_like(o0), torch.full_like(lse0, float('nan')), torch.empty_like(dq0)
     delta = torch.empty_like(lse0)
     need = L.lib().b4c_attn_bwd_workspace_bytes(B, S, H, dh, dt)
     ws = torch.empty(max(need, 8), dtype=torch.uint8, device='cuda')
+    # the left side: raw calls of the existing entry point that the (layout, rate) case names -- b4c_attn_fwd[_varlen][_drop],
+    # b4c_attn_bwd_ws / _drop_ws / _varlen[_drop] (ops itself goes through b4c_attn_*_ex)
+    layout = (p(cu),) if packed else ()
+    drop = (rate, seed) if rate > 0 else ()
+    fwd_name = 'b4c_attn_fwd' + ('_varlen' if packed else '') + ('_drop' if drop else '')
+    bwd_name = 'b4c_attn_bwd' + ('_varlen' if packed else '') + ('_drop' if drop else '') + ('' if packed else '_ws')
+    L.check(getattr(L.lib(), fwd_name)(p(qd), qd.stride(0), p(padd), *layout, p(o0), d, p(lse0), B, S, H, dh, dt, st, *drop), fwd_name)
+    L.check(getattr(L.lib(), bwd_name)(p(qd), qd.stride(0), p(padd), *layout, p(o0), d, p(dod), d, p(lse0), p(delta), p(dq0),
+                                       dq0.stride(0), B, S, H, dh, p(ws), need, dt, st, *drop), bwd_name)
+    if S <= 256 and not packed and not drop:      # the form without a workspace
+        dq2 = torch.empty_like(dq0)
+        L.check(L.lib().b4c_attn_bwd(p(qd), qd.stride(0), p(padd), p(o0), d, p(dod), d, p(lse0), p(delta), p(dq2), dq2.stride(0),
+                                     B, S, H, dh, dt, st), 'b4c_attn_bwd')
+        assert torch.equal(dq2, dq0)
     L.check(L.lib().b4c_attn_fwd_ex(p(qd), qd.stride(0), p(padd), p(cu), p(o1), d, p(lse1), B, S, H, dh, dt, st, rate, seed, 0))
     L.check(L.lib().b4c_attn_bwd_ex(p(qd), qd.stride(0), p(padd), p(cu), p(o1), d, p(dod), d, p(lse1), p(delta), p(dq1), dq1.stride(0),
                                     B, S, H, dh, p(ws), need, dt, st, rate, seed, 0))
@@ -365,8 +381,9 @@ def test_flags_zero_is_the_existing_entry_point(ops, lens, packed, rate):
     for b, Lb in enumerate(lens):
         assert torch.equal(lse1[b, :, :Lb], lse0[b, :, :Lb])
     if not packed and rate == 0.0:
-        w0 = ops.attn_weights(qd, padd, lse0, B, S, H, dh)
+        w0 = torch.empty(B, H, S, S, dtype=torch.float32, device='cuda')
         w1 = torch.empty_like(w0)
+        L.check(L.lib().b4c_attn_weights(p(qd), qd.stride(0), p(padd), p(lse0), p(w0), B, S, H, dh, dt, st))
         L.check(L.lib().b4c_attn_weights_ex(p(qd), qd.stride(0), p(padd), p(lse0), p(w1), B, S, H, dh, dt, st, 0))
         assert torch.equal(w1, w0)
         # the packed layout keeps its limits under the new name: fp32 is refused
@@ -374,3 +391,71 @@ def test_flags_zero_is_the_existing_entry_point(ops, lens, packed, rate):
         cu2 = torch.tensor([0, 96, 192], dtype=torch.int32, device='cuda')
         rc = L.lib().b4c_attn_fwd_ex(p(q32), q32.stride(0), p(padd), p(cu2), p(o1), d, p(lse1), B, S, H, dh, L.F32, st, 0.0, 0, 1)
         assert rc != 0 and b'bf16 only' in L.lib().b4c_last_error()
+
+
+@pytest.mark.parametrize('packed', [False, True], ids=['dense', 'packed'])
+def test_ops_without_options_is_the_existing_entry_point(ops, packed):
+    """ops.attn_fwd / attn_bwd / attn_weights make one call per direction, b4c_attn_*_ex; without dropout and causal masking their
+    results are, bit for bit, those of raw calls of b4c_attn_fwd / b4c_attn_bwd_ws / b4c_attn_weights (dense) and
+    b4c_attn_fwd_varlen / b4c_attn_bwd_varlen (packed)"""
+    from bert4clickpath_amd import _lib as L
+    lens = [5, 32, 33] if packed else [33, 33, 33]
+    g = torch.Generator().manual_seed(sum(lens) + 1)
+    H, dh = 2, 64
+    B, S = len(lens), max(lens)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    d, T = H * dh, int(off[-1])
+    cu = torch.tensor(off, dtype=torch.int32, device='cuda') if packed else None
+    qd = (torch.randn(T, 3 * d, generator=g) * 0.8).to(BF16).cuda()
+    dod = torch.randn(T, d, generator=g).to(BF16).cuda()
+    padd = torch.zeros(T, dtype=torch.uint8, device='cuda') if packed else _pads(B, S).reshape(-1).cuda()
+    p, st, dt = ops._p, ops._st(), ops.dt_code(qd.dtype)
+    o0 = torch.empty(T, d, dtype=BF16, device='cuda')
+    lse0 = torch.full((B, H, S), float('nan'), dtype=torch.float32, device='cuda')
+    dq0, delta = torch.empty_like(qd), torch.empty_like(lse0)
+    lib = L.lib()
+    assert lib.b4c_attn_bwd_workspace_bytes(B, S, H, dh, dt) == 0
+    if packed:
+        L.check(lib.b4c_attn_fwd_varlen(p(qd), qd.stride(0), p(padd), p(cu), p(o0), d, p(lse0), B, S, H, dh, dt, st))
+        L.check(lib.b4c_attn_bwd_varlen(p(qd), qd.stride(0), p(padd), p(cu), p(o0), d, p(dod), d, p(lse0), p(delta), p(dq0),
+                                        dq0.stride(0), B, S, H, dh, None, 0, dt, st))
+    else:
+        L.check(lib.b4c_attn_fwd(p(qd), qd.stride(0), p(padd), p(o0), d, p(lse0), B, S, H, dh, dt, st))
+        L.check(lib.b4c_attn_bwd_ws(p(qd), qd.stride(0), p(padd), p(o0), d, p(dod), d, p(lse0), p(delta), p(dq0), dq0.stride(0),
+                                    B, S, H, dh, None, 0, dt, st))
+    o1, lse1 = ops.attn_fwd(qd, padd, B, S, H, dh, cu)
+    dq1 = ops.attn_bwd(qd, padd, o1, dod, lse1, B, S, H, dh, cu)
+    torch.cuda.synchronize()
+    assert torch.equal(o1, o0) and torch.equal(dq1, dq0)
+    for b, Lb in enumerate(lens):
+        assert torch.equal(lse1[b, :, :Lb], lse0[b, :, :Lb])
+    if not packed:
+        w0 = torch.empty(B, H, S, S, dtype=torch.float32, device='cuda')
+        L.check(lib.b4c_attn_weights(p(qd), qd.stride(0), p(padd), p(lse0), p(w0), B, S, H, dh, dt, st))
+        assert torch.equal(ops.attn_weights(qd, padd, lse0, B, S, H, dh), w0)
+
+
+def test_varlen_entry_points_refuse_a_null_cu_seqlens(ops):
+    """b4c_attn_fwd_varlen / b4c_attn_bwd_varlen share their host path with the dense entry points, where cu_seqlens = NULL means the
+    dense layout: called with NULL they still are B4C_EINVAL 'null pointer' and launch nothing.  B = 1, S = 32: the buffers hold
+    the 32 token rows a dense launch would work on, so a wrongly accepted call stays inside them and shows as changed outputs."""
+    from bert4clickpath_amd import _lib as L
+    B, S, H, dh = 1, 32, 2, 32
+    d = H * dh
+    g = torch.Generator().manual_seed(32)
+    qd = (torch.randn(B * S, 3 * d, generator=g) * 0.8).to(BF16).cuda()
+    dod = torch.randn(B * S, d, generator=g).to(BF16).cuda()
+    padd = torch.zeros(B * S, dtype=torch.uint8, device='cuda')
+    o = torch.full((B * S, d), 7.0, dtype=BF16, device='cuda')
+    lse = torch.full((B, H, S), 7.0, dtype=torch.float32, device='cuda')
+    delta, dqkv = torch.full_like(lse, 7.0), torch.full_like(qd, 7.0)
+    ws = torch.full((64,), 7, dtype=torch.uint8, device='cuda')
+    p, st, dt, lib = ops._p, ops._st(), ops.dt_code(BF16), L.lib()
+    rc = lib.b4c_attn_fwd_varlen(p(qd), qd.stride(0), p(padd), None, p(o), d, p(lse), B, S, H, dh, dt, st)
+    assert rc == L._C['B4C_EINVAL'] and b'null pointer' in lib.b4c_last_error()
+    rc = lib.b4c_attn_bwd_varlen(p(qd), qd.stride(0), p(padd), None, p(o), d, p(dod), d, p(lse), p(delta), p(dqkv), dqkv.stride(0),
+                                 B, S, H, dh, p(ws), ws.numel(), dt, st)
+    assert rc == L._C['B4C_EINVAL'] and b'null pointer' in lib.b4c_last_error()
+    torch.cuda.synchronize()
+    for t in (o, lse, delta, dqkv, ws):
+        assert bool((t == 7).all())

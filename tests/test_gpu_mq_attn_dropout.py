@@ -293,6 +293,26 @@ def test_rate_zero_is_the_old_entry_point(ops, layouts, dtype, dh, kind):
 
 
 @pytest.mark.parametrize('dtype,dh', KERNELS)
+def test_ops_at_rate_zero_is_the_old_entry_point(ops, layouts, dtype, dh):
+    """ops.attn_mq_fwd / attn_mq_bwd always call the _drop entry points; at rate 0 (with and without q_rows) their results are, bit
+    for bit, those of raw calls of b4c_attn_mq_fwd / b4c_attn_mq_bwd"""
+    lay = layouts['packed']
+    _, q, kv, do = _operands(lay, dtype, dh, 29 + dh + lay.T)
+    q, kv, do = q.cuda(), kv.cuda(), do.cuda()
+    o = torch.zeros(lay.R, H * dh, dtype=dtype, device='cuda')
+    lse = torch.zeros(lay.R, H, dtype=torch.float32, device='cuda')
+    dq, dkv = torch.zeros_like(o), torch.full_like(kv, float('nan'))
+    assert _raw(ops, lay, dtype, dh, 'b4c_attn_mq_fwd', q, kv, o, lse) == 0
+    assert _raw(ops, lay, dtype, dh, 'b4c_attn_mq_bwd', q, kv, o, lse, do, dq, dkv) == 0
+    for q_rows in (None, lay.q_rows_d):
+        o1, lse1 = ops.attn_mq_fwd(q, kv, lay.cu_d, lay.moff_d, lay.B, lay.S_arg, H, dh, lay.kp_d, q_rows)
+        dq1, dkv1 = ops.attn_mq_bwd(q, kv, lay.cu_d, lay.moff_d, o1, do, lse1, lay.B, lay.S_arg, H, dh, lay.kp_d, q_rows)
+        torch.cuda.synchronize()
+        for a, b in ((o, o1), (lse, lse1), (dq, dq1), (dkv, dkv1)):
+            assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize('dtype,dh', KERNELS)
 def test_bad_arguments_write_nothing(ops, layouts, dtype, dh):
     from bert4clickpath_amd import _lib as L
     lay = layouts['packed']
