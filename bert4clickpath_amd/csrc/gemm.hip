@@ -1027,14 +1027,14 @@ template <typename T> struct TNStage;
 template <> struct TNStage<bf16_t> {
     static constexpr int TOK = 64;  // tokens per step; wave w owns tokens [16w, 16w+16)
     unsigned v[2][8];               // [group of 8 tokens][token] -> features (2*lane, 2*lane+1) packed
-    __device__ __forceinline__ void load(const bf16_t *__restrict__ P, int ld, int f0, int64_t tok0, int64_t tok_end, int lane, int wave) {
+    __device__ __forceinline__ void load(const bf16_t *__restrict__ P, int ld, int w, int f0, int64_t tok0, int64_t tok_end, int lane, int wave) {
         const int f = f0 + 2 * lane;
 #pragma unroll
         for (int g = 0; g < 2; ++g)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int64_t t = tok0 + wave * 16 + g * 8 + j;
-                v[g][j] = (t < tok_end && f < ld) ? *reinterpret_cast<const unsigned *>(P + t * ld + f) : 0u;
+                v[g][j] = (t < tok_end && f < w) ? *reinterpret_cast<const unsigned *>(P + t * ld + f) : 0u;
             }
     }
     __device__ __forceinline__ void store(char *s, int lane, int wave) const {
@@ -1069,7 +1069,7 @@ template <> struct TNStage<bf16_t> {
 template <> struct TNStage<float> {
     static constexpr int TOK = 32;  // wave w owns tokens [8w, 8w+8)
     float v[2][4][2];               // [group of 4 tokens][token][feature lane / lane+64]
-    __device__ __forceinline__ void load(const float *__restrict__ P, int ld, int f0, int64_t tok0, int64_t tok_end, int lane, int wave) {
+    __device__ __forceinline__ void load(const float *__restrict__ P, int ld, int w, int f0, int64_t tok0, int64_t tok_end, int lane, int wave) {
 #pragma unroll
         for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -1078,7 +1078,7 @@ template <> struct TNStage<float> {
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int f = f0 + lane + 64 * q;
-                    v[g][j][q] = (t < tok_end && f < ld) ? P[t * ld + f] : 0.f;
+                    v[g][j][q] = (t < tok_end && f < w) ? P[t * ld + f] : 0.f;
                 }
             }
     }
@@ -1125,8 +1125,8 @@ __global__ void __launch_bounds__(256) gemm_tn_kernel(const T *__restrict__ A, i
     const int nsteps = (int)((m_end - m_begin + TOK - 1) / TOK);
     TNStage<T> sa, sg;
     if (nsteps > 0) {
-        sa.load(A, lda, k0, m_begin, m_end, lane, wave);
-        sg.load(G, ldg, n0, m_begin, m_end, lane, wave);
+        sa.load(A, lda, K, k0, m_begin, m_end, lane, wave);
+        sg.load(G, ldg, N, n0, m_begin, m_end, lane, wave);
         sa.store(smem, lane, wave);
         sg.store(smem + TILE_BYTES, lane, wave);
         if (want_db) sg.colsum(bs0, bs1);
@@ -1135,8 +1135,8 @@ __global__ void __launch_bounds__(256) gemm_tn_kernel(const T *__restrict__ A, i
     for (int st = 0; st < nsteps; ++st) {
         const bool more = st + 1 < nsteps;
         if (more) {
-            sa.load(A, lda, k0, m_begin + (int64_t)(st + 1) * TOK, m_end, lane, wave);
-            sg.load(G, ldg, n0, m_begin + (int64_t)(st + 1) * TOK, m_end, lane, wave);
+            sa.load(A, lda, K, k0, m_begin + (int64_t)(st + 1) * TOK, m_end, lane, wave);
+            sg.load(G, ldg, N, n0, m_begin + (int64_t)(st + 1) * TOK, m_end, lane, wave);
         }
         mma_stage<T>(smem, smem + TILE_BYTES, wm, wn, r, h, acc);
         __syncthreads();
@@ -1170,13 +1170,13 @@ __global__ void __launch_bounds__(256) gemm_tn_kernel(const T *__restrict__ A, i
 #define TN_TILE_BYTES (64 * TN_STR)     // one operand, one stage
 
 __device__ __forceinline__ bf16x8 tn_frag(const char *p) { return frag_tr(p, 4 * TN_STR); }   // tokens +0..3 and +4..7 of the lane's feature
-__device__ __forceinline__ void tn_load16(const bf16_t *__restrict__ P, int ld, int f0, int64_t tok0, int64_t tok_end, int tid, u32x4 (&reg)[4]) {
+__device__ __forceinline__ void tn_load16(const bf16_t *__restrict__ P, int ld, int w, int f0, int64_t tok0, int64_t tok_end, int tid, u32x4 (&reg)[4]) {
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc(P + tok0 * ld, tok_end - tok0, 64, (int64_t)ld * 2);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int c = tid + i * 256;
         const int f = f0 + (c & 15) * 8;
-        reg[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (((c >> 4) * ld + f) * 2) | oob_if(f >= ld), 0, 0);
+        reg[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (((c >> 4) * ld + f) * 2) | oob_if(f >= w), 0, 0);
     }
 }
 __device__ __forceinline__ void tn_store16(char *s, int tid, const u32x4 (&reg)[4]) {
@@ -1226,8 +1226,8 @@ __device__ __forceinline__ void tn_bf16_body(const bf16_t *__restrict__ A, int l
     auto load = [&](int t, u32x4 (&qa)[4], u32x4 (&qg)[4]) {
         const int64_t tok0 = m_begin + (int64_t)t * 64;
         const int64_t e = tok0 < m_end ? m_end : tok0;
-        tn_load16(A, lda, k0, tok0, e, tid, qa);
-        tn_load16(G, ldg, n0, tok0, e, tid, qg);
+        tn_load16(A, lda, K, k0, tok0, e, tid, qa);
+        tn_load16(G, ldg, N, n0, tok0, e, tid, qg);
     };
 #pragma unroll
     for (int p = 0; p < D; ++p) load(p, ra[p], rg[p]);
@@ -1363,6 +1363,19 @@ extern "C" int64_t b4c_gemm_tn_workspace_bytes(int M, int K, int N, int dtype) {
     return nsplit * ((int64_t)tk * tn * 16384 + (int64_t)tn * 128) * 4;
 }
 
+// Operand contract of the TN family (b4c_gemm_tn, _seg, _group).  A is M rows of K valid features at pitch lda >= K, G is M rows
+// of N valid features at pitch ldg >= N; either may be a column block of a wider buffer, its last block included.  The loaders
+// guard the feature index by the valid width (K resp. N), never by the pitch, and the token index by M, so every access starts
+// at a column f < width of a row t < M and is as wide as the route's load:
+//   fp32                one float:  column f;
+//   bf16, generic       one dword:  columns f, f + 1 with f even.  The pointer is 4-byte aligned and the pitch even, so the view
+//                       starts at an even column of its (4-byte aligned) parent rows and the parent's row length is even: a view that
+//                       ends inside its parent row leaves room for column `width` when width is odd;
+//   bf16, 16-byte path  eight columns f .. f + 7 with f % 8 == 0.  Pointer % 16 == 0 and pitch % 8 == 0: the view starts at a column
+//                       divisible by 8 of rows whose length is divisible by 8, so start + round_up(width, 8) <= row length.
+// So a launch reads the operand's own columns, rounded up to the access width, of rows [0, M) and nothing else: not the columns
+// beside a slice (they may hold anything; what is read of them beyond `width` is masked at the emit), not the row after the last.
+// Columns past the valid width enter the tiles and the column sums as zeros.
 static int gemm_tn_launch(const void *A, int lda, const void *G, int ldg, TNOut out, int M, int K, int N, int dtype,
                           void *workspace, int64_t workspace_bytes, void *stream) {
     B4C_REQUIRE(A && G && out.dW[0] && M > 0 && K > 0 && N > 0, "gemm_tn: null pointer / empty");
@@ -1481,7 +1494,7 @@ extern "C" int b4c_gemm_tn_group(const b4c_tn_desc *h_desc, int n_prob, int M, i
         g.tiles += p.tk * p.tn;
         p.out = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}, d.seg_width, d.ldw, nsplit == 1 ? TN_DIRECT : TN_WS, nullptr, nullptr};
         for (int sgi = 0; sgi < d.n_seg; ++sgi) {
-            B4C_REQUIRE(d.dW[sgi], "gemm_tn_group: problem %d segment %d has no dW", i, sgi);
+            B4C_REQUIRE(d.dW[sgi] && (d.db[sgi] || !d.db[0]), "gemm_tn_group: problem %d segment %d has no dW, or no db beside a db[0]", i, sgi);
             p.out.dW[sgi] = d.dW[sgi];
             p.out.db[sgi] = d.db[sgi];
         }

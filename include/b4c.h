@@ -271,7 +271,7 @@ typedef struct {
     const void *A;          /* [M][lda], K columns used */
     const void *G;          /* [M][ldg], n_seg * seg_width columns used */
     float *dW[4];           /* device pointers, [K][ldw] each */
-    float *db[4];           /* or NULL */
+    float *db[4];           /* all n_seg of them, or db[0] NULL: no column sums for this problem */
     int32_t lda, ldg, K, n_seg, seg_width, ldw;
 } b4c_tn_desc;
 int64_t b4c_gemm_tn_group_workspace_bytes(const b4c_tn_desc *h_desc, int n_prob, int M);
