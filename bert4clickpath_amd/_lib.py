@@ -9,6 +9,9 @@ LIB_PATH = os.environ.get('B4C_LIB_PATH') or os.path.join(_HERE, 'libb4c_hip.so'
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')
 # extension headers: further entry points of the same ABI in files of their own, which b4c.h includes (a C caller includes b4c.h alone)
 EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_ex.h'),)
+# add-on headers: the entry points of later features, one header each, which b4c.h includes as well.  A feature adds its header
+# here: lib() binds whatever these declare (addon_signatures()); signatures() and all_signatures() keep to the lists above.
+ADDON_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss.h'),)
 
 
 class B4CError(RuntimeError):
@@ -105,7 +108,20 @@ def all_signatures():
     return table
 
 
-_C = header_constants(''.join(_header_text(p) for p in (HEADER_PATH,) + EXT_HEADER_PATHS))
+def addon_signatures():
+    """signatures() of every add-on header (ADDON_HEADER_PATHS): what lib() binds beside all_signatures().  A name that another
+    header of the ABI declares raises."""
+    taken = all_signatures()
+    table = {}
+    for path in ADDON_HEADER_PATHS:
+        for name, sig in signatures(path).items():
+            if name in taken or name in table:
+                raise B4CError('%s declares %s, which another header of the ABI declares too' % (path, name))
+            table[name] = sig
+    return table
+
+
+_C = header_constants(''.join(_header_text(p) for p in (HEADER_PATH,) + EXT_HEADER_PATHS + ADDON_HEADER_PATHS))
 ABI_VERSION = _C['B4C_ABI_VERSION']       # b4c_abi_version() of the library must agree
 F32, BF16 = _C['B4C_F32'], _C['B4C_BF16']
 ACT_NONE, ACT_RELU = _C['B4C_ACT_NONE'], _C['B4C_ACT_RELU']
@@ -115,6 +131,7 @@ MAX_FEATURES, MAX_TOPK = _C['B4C_MAX_FEATURES'], _C['B4C_MAX_TOPK']
 MAX_EXCL, MAX_CAND = _C['B4C_MAX_EXCL'], _C['B4C_MAX_CAND']
 GRAD_CHUNK, GRAD_GROUP = _C['B4C_GRAD_CHUNK'], _C['B4C_GRAD_GROUP']
 ATTN_CAUSAL = _C['B4C_ATTN_CAUSAL']       # flag bit of the b4c_attn_*_ex entry points
+CAND_BCE, CAND_SOFTMAX = _C['B4C_CAND_BCE'], _C['B4C_CAND_SOFTMAX']      # loss kinds of b4c_candidate_loss_fwd
 
 _lib = None
 
@@ -148,7 +165,7 @@ def lib():
         if have != ABI_VERSION:
             raise B4CError('%s is ABI %d, this binding expects ABI %d; rebuild it (`make -C bert4clickpath_amd/csrc`)'
                            % (LIB_PATH, have, ABI_VERSION))
-        for name, (res, args) in sig.items():
+        for name, (res, args) in list(sig.items()) + list(addon_signatures().items()):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -398,17 +398,9 @@ class ClickstreamTransformer(nn.Module):
         rows = ops.GatherRowsFn.apply(enc.reshape(-1, d), flat_idx, flat_idx.shape[0])
         return rows, lab
 
-    def cloze_loss(self, inputs, labels, training=True, flat_idx=None, variant='tf', unit_grad=False, max_masked_per_row=None,
-                   packed=None, n_real_tokens=None):
-        """Masked-item training loss == ClozeMaskedLoss(sparse_categorical_crossentropy)(labels, self(inputs)).
-        labels: (B, M) float32 padded with -1 (reference format) or compact (R,) int ids in row-major mask order.
-        flat_idx (R,) int32 skips the device-side index generation.  max_masked_per_row=M (the pipeline's
-        MAX_MASKED_ITEMS, cloze_constants.py:1) selects the sync-free form: [MASK] positions and the labels of the padded
-        (B, Mlab) tensor are compacted on the device, the head runs on B*M rows (the unused ones are ignored rows), and no
-        value is read back to the host.
-        n_real_tokens (host int: non-pad positions of the chained batch, which the input pipeline knows when it pads) /
-        packed: run the encoder on the padding-free layout (bf16 throughput path; same loss and gradients, the pad
-        positions' work is not done)."""
+    def _loss_rows(self, inputs, labels, training, flat_idx, max_masked_per_row, packed, n_real_tokens):
+        """what the training losses share -> (rows [R, d] at the [MASK] positions, compact int32 labels [R], poison): the forms of
+        cloze_loss's docstring.  poison: None, or the int32 device flag whose negative value must turn the loss into NaN."""
         pack = self._use_packed(inputs, packed, n_real_tokens)
         lab = torch.as_tensor(labels, device=self.transformer.position_table.device)
         if max_masked_per_row is not None and flat_idx is None:
@@ -423,10 +415,24 @@ class ClickstreamTransformer(nn.Module):
             lab = lab.to(torch.int32).contiguous()
             if lab.shape[0] != rows.shape[0]:
                 raise ValueError('%d labels for %d masked positions' % (lab.shape[0], rows.shape[0]))
-        code = CE_TF if variant == 'tf' else CE_PLAIN
         # a wrong n_real_tokens would silently drop or invent tokens, more [MASK] positions than B x max_masked_per_row
         # would drop rows: the device-side counts disagree -> NaN loss (no read-back)
         poison = self._packed.ids_packed if (self._packed is not None and n_real_tokens is not None) else self._mask_flag
+        return rows, lab, poison
+
+    def cloze_loss(self, inputs, labels, training=True, flat_idx=None, variant='tf', unit_grad=False, max_masked_per_row=None,
+                   packed=None, n_real_tokens=None):
+        """Masked-item training loss == ClozeMaskedLoss(sparse_categorical_crossentropy)(labels, self(inputs)).
+        labels: (B, M) float32 padded with -1 (reference format) or compact (R,) int ids in row-major mask order.
+        flat_idx (R,) int32 skips the device-side index generation.  max_masked_per_row=M (the pipeline's
+        MAX_MASKED_ITEMS, cloze_constants.py:1) selects the sync-free form: [MASK] positions and the labels of the padded
+        (B, Mlab) tensor are compacted on the device, the head runs on B*M rows (the unused ones are ignored rows), and no
+        value is read back to the host.
+        n_real_tokens (host int: non-pad positions of the chained batch, which the input pipeline knows when it pads) /
+        packed: run the encoder on the padding-free layout (bf16 throughput path; same loss and gradients, the pad
+        positions' work is not done)."""
+        rows, lab, poison = self._loss_rows(inputs, labels, training, flat_idx, max_masked_per_row, packed, n_real_tokens)
+        code = CE_TF if variant == 'tf' else CE_PLAIN
         if hasattr(self.head, 'cloze_ce'):
             if poison is not None and getattr(self.head, 'accepts_poison', False):
                 loss = self.head.cloze_ce(rows, lab, code, unit_grad, poison=poison)      # folded into the loss kernel
@@ -439,6 +445,48 @@ class ClickstreamTransformer(nn.Module):
         if poison is not None:
             loss = loss + torch.where(poison[0] < 0, float('nan'), 0.0).to(loss.dtype)
         return loss
+
+    def candidate_loss(self, inputs, labels, candidates=None, num_negatives=None, loss='bce', exclude=None, item_cdf=None, seed=None,
+                       row_base=0, training=True, flat_idx=None, unit_grad=False, max_masked_per_row=None, packed=None,
+                       n_real_tokens=None):
+        """Sampled-negative training loss: each masked row against its own list of items, the label first -- loss='bce' (SASRec:
+        softplus(-s_label) + the sum of softplus(s_negative)) or 'softmax' (the list-wise softmax over the label and the negatives,
+        the loss of the sampled-negative HitRate / NDCG protocol) -- mean over the rows with a valid label.  The head's projection
+        is read and receives gradient at the listed rows only (head.candidate_loss; ClozeMaskedItemPrediction, SampledSoftmaxHead).
+        inputs, labels, training, flat_idx, max_masked_per_row, packed, n_real_tokens: as in cloze_loss, the sync-free form and the
+        NaN loss on a contradicted token count included.  Exactly one of
+          candidates:    integer lists (label space; < 0 or >= V: absent), (R, C) one per masked row or (B, C) one per sequence,
+                         C <= 1024, whose column 0 is the row's label: a row where it is not turns the loss into NaN (checked on
+                         the device, no read-back);
+          num_negatives: the lists are drawn here (ops.sample_candidates: never the label, never an item of `exclude`, uniform or
+                         by item_cdf), a pure function of (seed, row_base + row); seed None: the next of the model's dropout seeds.
+        exclude: (R, E) or (B, E) as in predict_topk -- e.g. the user's own items."""
+        if (candidates is None) == (num_negatives is None):
+            raise B4CError('candidate_loss: give exactly one of candidates and num_negatives')
+        if loss not in ops.CAND_LOSS_KINDS:
+            raise B4CError("candidate_loss: loss %r ('bce' or 'softmax')" % (loss,))
+        if not hasattr(self.head, 'candidate_loss'):
+            raise B4CError('candidate_loss: the head %s has no vocabulary projection to score items with' % type(self.head).__name__)
+        rows, lab, poison = self._loss_rows(inputs, labels, training, flat_idx, max_masked_per_row, packed, n_real_tokens)
+        V = self.head.output_vocab_size
+        bad = None
+        if candidates is not None:
+            if exclude is not None or item_cdf is not None:
+                raise B4CError('candidate_loss: exclude / item_cdf shape the lists drawn here; leave such items out of `candidates`')
+            cand = self._row_candidates(candidates, rows.shape[0], rows.device, 'candidate_loss')
+            lab_ok = (lab >= 0) & (lab < V)
+            bad = (lab_ok & (cand[:, 0] != lab)).any()
+            cand = torch.cat([torch.where(lab_ok, lab, torch.full_like(lab, -1))[:, None], cand[:, 1:]], 1)
+        else:
+            ex = self._row_exclusions(exclude, rows.shape[0], rows.device, lab) if exclude is not None else None
+            from .transformer import dropout_seeds
+            cand, _ = ops.sample_candidates(lab, V, num_negatives, dropout_seeds.next() if seed is None else seed, row_base, ex, item_cdf)
+        out = self.head.candidate_loss(rows, cand, loss, unit_grad)
+        if poison is not None:
+            out = out + torch.where(poison[0] < 0, float('nan'), 0.0).to(out.dtype)
+        if bad is not None:
+            out = out + torch.where(bad, float('nan'), 0.0).to(out.dtype)
+        return out
 
     @torch.no_grad()
     def predict_topk(self, inputs, k, labels=None, flat_idx=None, packed=None, n_real_tokens=None, exclude=None, candidates=None):
@@ -519,9 +567,15 @@ class ClickstreamTransformer(nn.Module):
             if offsets is None or c.shape[0] != offsets.shape[0] - 1:
                 raise B4CError('%s: candidates have %d lists for %d masked rows%s' % (
                     who, c.shape[0], R, '' if offsets is None else ' of %d sequences' % (offsets.shape[0] - 1)))
-            seq = torch.searchsorted(offsets[1:].long(), torch.arange(R, device=device), right=True)
-            c = c[seq]
+            c = c[self._sequence_of_rows(R, device)]
         return c.contiguous()
+
+    def _sequence_of_rows(self, R, device):
+        """the sequence of each of the R masked rows (self._row_offsets).  The sync-free form runs on more rows than there are
+        [MASK] positions: the rows past the last one are ignored rows and are given the last sequence's list"""
+        offsets = self._row_offsets
+        seq = torch.searchsorted(offsets[1:].long(), torch.arange(R, device=device), right=True)
+        return seq.clamp_(max=offsets.shape[0] - 2)
 
     def _row_exclusions(self, exclude, R, device, lab):
         """predict_topk's `exclude` -> the canonical (R, E) lists of ops.exclusions, one per masked row"""
@@ -535,8 +589,7 @@ class ClickstreamTransformer(nn.Module):
             if offsets is None or exclude.shape[0] != offsets.shape[0] - 1:
                 raise B4CError('predict_topk: exclude has %d lists for %d masked rows%s' % (
                     exclude.shape[0], R, '' if offsets is None else ' of %d sequences' % (offsets.shape[0] - 1)))
-            seq = torch.searchsorted(offsets[1:].long(), torch.arange(R, device=device), right=True)
-            exclude = exclude[seq]
+            exclude = exclude[self._sequence_of_rows(R, device)]
         return ops.exclusions(exclude, self.head.output_vocab_size, lab)
 
     def get_serving_signature(self):

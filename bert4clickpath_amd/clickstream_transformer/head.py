@@ -151,6 +151,24 @@ class SoftMaxHead(nn.Module):
             wt, _, b = self._packs[-1].get(h.dtype, K, False)
             return ops.candidate_scores(h, wt, b, cand, self.output_vocab_size, labels, k, want_scores)
 
+    vocab_major = False        # the projection is stored [V][K], so its gradient over a candidate list is row-sparse
+    last_candidates = None     # int32 [R, C] lists of the latest candidate_loss step
+
+    def candidate_loss(self, x2d, cand, kind, unit_grad=False):
+        """Mean over the rows with a valid target of the sampled-negative loss of each row's own list cand (int32 [R, C], label-space
+        ids, target in column 0; < 0 or >= V: absent): kind 'bce' or 'softmax' (ops.CandidateLossFn, b4c_candidate_loss_fwd / _bwd).
+        Only the listed rows of the projection are read and receive gradient.  The vocabulary-major heads only."""
+        if not self.vocab_major:
+            raise ops.B4CError('candidate_loss: %s stores its projection as a Keras kernel [K][V], whose gradient is not row-sparse; '
+                               'use ClozeMaskedItemPrediction or SampledSoftmaxHead' % type(self).__name__)
+        h = self.trunk(x2d)
+        K, table, bias = self._proj()
+        if K % 8 or h.shape[1] != K:
+            raise ops.B4CError('candidate_loss: the projection input is %d wide; the candidate kernels need a multiple of 8' % K)
+        self.last_candidates = cand
+        off = self._packs[-1].tied_offset
+        return ops.CandidateLossFn.apply(h, table, bias, cand, off, kind, unit_grad, table is getattr(self, '_table', None))
+
     def forward(self, inputs, **kwargs):
         """inputs (B, M, d) -> probabilities (B, M, V), materialised as the reference does."""
         shp = inputs.shape
@@ -315,6 +333,8 @@ class ClozeMaskedItemPrediction(SoftMaxHead):
         if input_dim is not None:
             self.build(input_dim)
 
+    vocab_major = True
+
     def tie(self, embedding_weight):
         """embedding_weight: the (V + 11, d_item) Parameter of Transformer.embedding_layers[<items>]
         (kept by reference, not registered a second time: the model owns it)."""
@@ -432,9 +452,19 @@ class SampledSoftmaxHead(SoftMaxHead):
         return self._project(self.trunk(x2d), out_fp32)
 
     def touched_rows(self):
-        """Rows of ``output_embedding`` the latest sampled training step touched (for GradReducer.set_touched_rows)."""
+        """Rows of ``output_embedding`` the latest training step touched (for GradReducer.set_touched_rows): the samples and the
+        labels of a sampled step, the unique present listed ids of a candidate_loss step."""
+        if self.last_samples is None:
+            c = self.last_candidates.reshape(-1)
+            return torch.unique(c[(c >= 0) & (c < self.output_vocab_size)]).to(torch.int64)
         s, y = self.last_samples
         return torch.cat([s, y.to(torch.int64).clamp(min=0)])
+
+    vocab_major = True
+
+    def candidate_loss(self, x2d, cand, kind, unit_grad=False):
+        self.last_samples = None          # the latest step is a candidate step: touched_rows() reads last_candidates
+        return super().candidate_loss(x2d, cand, kind, unit_grad)
 
     accepts_poison = False
 

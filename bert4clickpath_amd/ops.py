@@ -1590,6 +1590,77 @@ def candidate_rank_rows(scores, V, cand, labels=None, k=0):
     return rank, idx
 
 
+CAND_LOSS_KINDS = {'bce': L.CAND_BCE, 'softmax': L.CAND_SOFTMAX}
+
+
+def _cand_loss_args(who, h, table, row_off, V, cand):
+    """the operand checks candidate_loss_fwd and candidate_loss_bwd share -> (cand, ld_c, C, R, K, dtype code)"""
+    if not isinstance(h, torch.Tensor) or h.dim() != 2:
+        raise B4CError('%s: h must be an [R, K] tensor' % who)
+    R, K = h.shape
+    dt = dt_code(h.dtype)
+    if K % 8 or not 8 <= K <= 1024 or h.stride(1) != 1 or h.stride(0) % 8:
+        raise B4CError('%s: K = %d (a multiple of 8, 8 .. 1024, contiguous rows with a pitch that is a multiple of 8)' % (who, K))
+    if (not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32 or table.shape[1] < K
+            or table.stride(1) != 1 or table.stride(0) % 4):
+        raise B4CError('%s: table must be the fp32 master table [rows, >= K] with a pitch that is a multiple of 4' % who)
+    if not 0 <= int(row_off) <= table.shape[0] - V:
+        raise B4CError('%s: rows %d .. %d of a table of %d rows' % (who, row_off, row_off + V, table.shape[0]))
+    cand, ld_c, C = _cand_args(cand, R, who)
+    return cand, ld_c, C, R, K, dt
+
+
+def candidate_loss_fwd(h, table, bias, cand, V, kind, row_off=0, want_scores=False):
+    """-> (item_loss fp32 [R], g fp32 [R, C], scores fp32 [R, C] or None) of each row's own candidate list, target in column 0
+    (b4c_candidate_loss_fwd, include/b4c_cand_loss.h): kind 'bce' = softplus(-s_0) + sum of softplus(s_c) over the other present
+    entries, 'softmax' = logsumexp over the present entries - s_0; g the loss's derivative by each score.  An entry < 0 or >= V is
+    absent (g = 0); a row whose column 0 is absent is ignored (loss 0, g = 0).  s = h . table[row_off + id] + bias[id] in fp32;
+    for bf16 h the table's elements are rounded to bf16 first.  h [R, K] bf16 or fp32, table the fp32 master [rows, >= K]."""
+    if kind not in CAND_LOSS_KINDS:
+        raise B4CError("candidate_loss_fwd: kind %r ('bce' or 'softmax')" % (kind,))
+    cand, ld_c, C, R, K, dt = _cand_loss_args('candidate_loss_fwd', h, table, row_off, V, cand)
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.numel() < V:
+        raise B4CError('candidate_loss_fwd: bias must be fp32 [>= V]')
+    _cuda(h, table, bias, cand)
+    dev = h.device
+    item = torch.empty(R, dtype=torch.float32, device=dev)
+    g = torch.empty(R, C, dtype=torch.float32, device=dev)
+    scores = torch.empty(R, C, dtype=torch.float32, device=dev) if want_scores else None
+    if R == 0:
+        return item, g, scores
+    with _record('candidate_loss_fwd', R * K * h.element_size() + R * C * (K * 4 + 12), 2 * R * C * K):
+        L.check(L.lib().b4c_candidate_loss_fwd(_p(h), h.stride(0), _p(table), table.stride(0), table.shape[0], int(row_off),
+                                               _p(bias.contiguous()), _p(cand), ld_c, R, C, V, K, dt, CAND_LOSS_KINDS[kind], _p(item),
+                                               _p(g), C, _p(scores), C, _st()), 'candidate_loss_fwd')
+    return item, g, scores
+
+
+def candidate_loss_bwd(h, table, cand, g, gscale, V, dtable, dbias, row_off=0):
+    """-> dh [R, K] in h's dtype = gscale * sum_c g[r][c] * table[row_off + cand[r][c]], and ADDS gscale * g[r][c] * h[r] into row
+    row_off + cand[r][c] of dtable (fp32, the table's shape) and gscale * g[r][c] into dbias[cand[r][c]] (fp32 [>= V]) with float
+    atomics (b4c_candidate_loss_bwd).  g [R, C] from candidate_loss_fwd, gscale a device fp32 [1]."""
+    who = 'candidate_loss_bwd'
+    cand, ld_c, C, R, K, dt = _cand_loss_args(who, h, table, row_off, V, cand)
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.shape != (R, C) or (R and g.stride(1) != 1):
+        raise B4CError('%s: g must be the fp32 [R, C] = [%d, %d] coefficients of candidate_loss_fwd' % (who, R, C))
+    if not isinstance(gscale, torch.Tensor) or gscale.dtype != torch.float32 or gscale.numel() != 1:
+        raise B4CError('%s: gscale must be a device fp32 tensor of one element' % who)
+    if (not isinstance(dtable, torch.Tensor) or dtable.dtype != torch.float32 or dtable.shape != table.shape
+            or not dtable.is_contiguous()):
+        raise B4CError('%s: dtable must be a contiguous fp32 tensor of the table\'s shape' % who)
+    if not isinstance(dbias, torch.Tensor) or dbias.dtype != torch.float32 or dbias.numel() < V or not dbias.is_contiguous():
+        raise B4CError('%s: dbias must be contiguous fp32 [>= V]' % who)
+    _cuda(h, table, cand, g, gscale, dtable, dbias)
+    dh = torch.empty(R, K, dtype=h.dtype, device=h.device)
+    if R == 0:
+        return dh
+    with _record('candidate_loss_bwd', R * K * h.element_size() * 2 + R * C * (K * 8 + 12), 4 * R * C * K):
+        L.check(L.lib().b4c_candidate_loss_bwd(_p(h), h.stride(0), _p(table), table.stride(0), table.shape[0], int(row_off), _p(cand),
+                                               ld_c, _p(g), max(g.stride(0), C), _p(gscale), R, C, V, K, dt, _p(dh), K, _p(dtable),
+                                               dtable.stride(0), _p(dbias), _st()), 'candidate_loss_bwd')
+    return dh
+
+
 # ---- Cloze batches (include/b4c.h "Cloze batches"): model inputs and padded labels from a CSR data set on the device ----
 CLOZE_TRAIN, CLOZE_EVAL = 0, 1
 CLOZE_MAX_WIDTH, CLOZE_MAX_LABELS = 1021, 64
@@ -3062,4 +3133,37 @@ class SampledCEFn(torch.autograd.Function):
         scatter_add_1d_(bg, samples, dbs.contiguous())
         scatter_add_1d_(bg, idx_y, dtrue.contiguous())
         _ready(table, bias)
+        return sink_returns(ctx, (dh,), actx, (tg, bg))
+
+
+class CandidateLossFn(torch.autograd.Function):
+    """Sampled-negative masked-item loss over each row's own candidate list, target in column 0 (include/b4c_cand_loss.h): 'bce'
+    (SASRec) or 'softmax' (list-wise), mean over the rows with a valid target.  The table -- vocabulary-major projection
+    (row_off 0) or tied item embedding (row_off = its id offset) -- is read and receives gradient at the listed rows only.
+    apply(h [R, K], table (rows, K) fp32, bias (V,) fp32, cand int32 [R, C], row_off, kind, unit_grad[, shared_table])
+    shared_table: the table is the embedding layer's too, whose backward runs last and announces its gradient."""
+
+    @staticmethod
+    def forward(ctx, h, table, bias, cand, row_off, kind, unit_grad, shared_table=False):
+        h = h.contiguous()
+        V = bias.shape[0]
+        present = (cand >= 0) & (cand < V)
+        valid = present[:, 0].sum().to(torch.float32)
+        scale = torch.where(valid > 0, 1.0 / valid.clamp(min=1.0), torch.zeros_like(valid)).reshape(1)
+        lz = getattr(table, '_b4c_lazy', None)
+        if lz is not None:          # row-lazy optimizer: the listed rows are brought up to date before they are read
+            lz.catch_up(torch.where(present, cand + int(row_off), torch.full_like(cand, -1)), note=ctx.needs_input_grad[1])
+        item, g, _ = candidate_loss_fwd(h, table.detach(), bias.detach(), cand, V, kind, row_off)
+        ctx.save_for_backward(h, g, cand, scale)
+        ctx.params, ctx.row_off, ctx.unit_grad, ctx.shared_table = (table, bias), int(row_off), unit_grad, bool(shared_table)
+        return item.sum() * scale[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        h, g, cand, scale = ctx.saved_tensors
+        table, bias = ctx.params
+        gscale = scale if ctx.unit_grad else scale * gout.to(torch.float32)
+        actx, (tg, bg) = grad_sinks(table, bias)
+        dh = candidate_loss_bwd(h, table.detach(), cand, g, gscale.contiguous(), bias.shape[0], tg, bg, ctx.row_off)
+        _ready(*((bias,) if ctx.shared_table else (table, bias)))
         return sink_returns(ctx, (dh,), actx, (tg, bg))

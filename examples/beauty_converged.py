@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from examples.beauty_hitrate import build_model  # noqa: E402
+from examples.beauty_hitrate import add_train_loss_arguments, build_model, training_loss  # noqa: E402
 
 
 def evaluate(model, data, batch=1024, split='test', filtered=False):
@@ -78,6 +78,7 @@ def main():
     ap.add_argument('--attention', default='bidirectional', choices=['bidirectional', 'causal'],
                     help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
                          'left-to-right next-item model')
+    add_train_loss_arguments(ap)
     a = ap.parse_args()
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
@@ -90,7 +91,7 @@ def main():
     else:
         data = input_pipeline.BeautyCloze(a.data)
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
-    model = build_model(data.V, a.dropout, dtype, seed=1234 + a.seed, attention=a.attention).cuda()
+    model = build_model(data.V, a.dropout, dtype, seed=1234 + a.seed, attention=a.attention, tied_head=a.train_loss != 'full').cuda()
     opt = optim.Adam(model.parameters())
     T.set_dropout_seed(a.seed)
     tmp = tempfile.mkdtemp(prefix='b4c_beauty_')
@@ -107,11 +108,11 @@ def main():
             b = next(batches)
             opt.zero_grad()
             if a.device_batches:
-                loss = model.cloze_loss({'asin': b['items']}, b['labels_padded'], training=True,
-                                        max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
+                loss = training_loss(model, a, {'asin': b['items']}, b['labels_padded'],
+                                     max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
             else:
                 items = torch.from_numpy(b['ids'])[:, 2:-1].contiguous().cuda()
-                loss = model.cloze_loss({'asin': items}, torch.from_numpy(b['labels_padded']).cuda(), training=True, max_masked_per_row=10)
+                loss = training_loss(model, a, {'asin': items}, torch.from_numpy(b['labels_padded']).cuda(), max_masked_per_row=10)
             loss.backward()
             opt.step()
             tl = loss

@@ -27,9 +27,11 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='bidirectional'):
+def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='bidirectional', tied_head=False):
     """paper_positions (the longest encoder input): the BERT4Rec paper's model, one constructor call.
-    attention='causal': left-to-right self-attention (SASRec, the paper's unidirectional arm)."""
+    attention='causal': left-to-right self-attention (SASRec, the paper's unidirectional arm).
+    tied_head: score an item by the dot product of the encoder output with its embedding (SASRec's head), in place of the reference's
+    dense stack -- the sampled-negative losses (--train_loss bce / softmax) need a projection stored per item."""
     from bert4clickpath_amd.clickstream_transformer import ClickstreamTransformer, ClozeMaskedItemPrediction, SoftMaxHead
     torch.manual_seed(seed)            # CPU generator: identical initial weights on any machine
     vocab = ['item%d' % i for i in range(V)]
@@ -41,9 +43,29 @@ def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='b
                                       attention_dropout_rate=dropout, compute_dtype=dtype, ffn_activation='gelu_tanh',
                                       position_encoding='learned', max_positions=paper_positions, embedding_layernorm=True,
                                       embedding_scale=1.0, **kw)
-    head = SoftMaxHead([1024, 512, 256, 128], V)
+    head = ClozeMaskedItemPrediction([], V) if tied_head else SoftMaxHead([1024, 512, 256, 128], V)
     return ClickstreamTransformer({'items': ['asin']}, {'items': vocab}, {'items': 64}, head, value_to_head='[MASK]',
                                   num_encoder_layers=2, num_attention_heads=2, dropout_rate=dropout, compute_dtype=dtype, **kw)
+
+
+def add_train_loss_arguments(ap):
+    ap.add_argument('--train_loss', default='full', choices=['full', 'bce', 'softmax'],
+                    help='full: the softmax over all V items (cloze_loss); bce / softmax: each target against --train_negatives sampled '
+                         'items that its sequence does not hold (model.candidate_loss) -- binary cross-entropy per item (SASRec) or '
+                         'the list-wise softmax; the head is then the tied dot product with the item embedding.  SASRec\'s recipe: '
+                         '--device_batches --attention causal --last_item_rate 1.0 --train_loss bce --train_negatives 1')
+    ap.add_argument('--train_negatives', type=int, default=1, help='with --train_loss bce / softmax: negatives drawn per target')
+
+
+def training_loss(model, a, feats, labels, **kw):
+    """the loss --train_loss selects; kw: cloze_loss's flat_idx / max_masked_per_row / n_real_tokens"""
+    if a.train_loss == 'full':
+        return model.cloze_loss(feats, labels, training=True, **kw)
+    from bert4clickpath_amd import cloze
+    seen = cloze.seen_items(feats['asin'])                   # (B, S): a sequence's own items are never its negatives
+    if kw.get('flat_idx') is not None:                       # rows are named by position: one exclusion list per row
+        seen = seen[(kw['flat_idx'].long() // (feats['asin'].shape[1] + 3))]       # [CLS] [SEP] items [SEP]
+    return model.candidate_loss(feats, labels, num_negatives=a.train_negatives, loss=a.train_loss, exclude=seen, training=True, **kw)
 
 
 def main():
@@ -89,6 +111,7 @@ def main():
     ap.add_argument('--attention', default='bidirectional', choices=['bidirectional', 'causal'],
                     help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
                          'left-to-right next-item model (every training row predicts the item after its prefix)')
+    add_train_loss_arguments(ap)
     a = ap.parse_args()
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
@@ -99,7 +122,8 @@ def main():
     data = input_pipeline.BeautyCloze(a.data)
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
     longest = (int(np.diff(data.offsets).max()) if a.max_len is None else a.max_len) + 3       # [CLS] [SEP] items [SEP]
-    model = build_model(data.V, a.dropout, dtype, paper_positions=longest if a.paper_model else None, attention=a.attention).cuda()
+    model = build_model(data.V, a.dropout, dtype, paper_positions=longest if a.paper_model else None, attention=a.attention,
+                        tied_head=a.train_loss != 'full').cuda()
     lr = WarmupLinearDecay(1e-3, a.warmup, max(a.steps, a.warmup + 1)) if a.warmup > 0 else 1e-3
     opt = optim.Adam(model.parameters(), learning_rate=lr, global_clipnorm=a.clipnorm, weight_decay=a.weight_decay,
                      exclude_from_weight_decay=optim.no_decay_params(model) if a.weight_decay is not None else ())
@@ -112,13 +136,13 @@ def main():
     for step, b in enumerate((dev_data or data).train_batches(a.batch, a.seed, a.steps)):
         opt.zero_grad()
         if dev_data is not None:      # items and padded labels are on the device already; nothing is read back
-            loss = model.cloze_loss({'asin': b['items']}, b['labels_padded'], training=True,
-                                    max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
+            loss = training_loss(model, a, {'asin': b['items']}, b['labels_padded'],
+                                 max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
         else:
             ids = torch.from_numpy(b['ids'])
             items = ids[:, 2:-1].contiguous().cuda()
-            loss = model.cloze_loss({'asin': items}, torch.from_numpy(b['labels']).cuda(), training=True,
-                                    flat_idx=torch.from_numpy(b['flat_idx']).cuda())
+            loss = training_loss(model, a, {'asin': items}, torch.from_numpy(b['labels']).cuda(),
+                                 flat_idx=torch.from_numpy(b['flat_idx']).cuda())
         loss.backward()
         opt.step()
         if step % 100 == 0 or step == a.steps - 1:

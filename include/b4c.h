@@ -882,5 +882,8 @@ int b4c_attn_mq_bwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, con
 /* ---- extension headers: part of this ABI, declared in files of their own and included here, so that b4c.h is all a caller includes.
  * (The ctypes binding reads them beside this file: bert4clickpath_amd/_lib.py, EXT_HEADER_PATHS.) */
 #include "b4c_attn_ex.h"   /* b4c_attn_fwd_ex / b4c_attn_bwd_ex / b4c_attn_weights_ex, B4C_ATTN_CAUSAL: causal self-attention */
+/* ---- add-on headers: the same, for the entry points of later features -- one header per feature, listed here and in _lib.py's
+ * ADDON_HEADER_PATHS, which binds whatever they declare. */
+#include "b4c_cand_loss.h" /* b4c_candidate_loss_fwd / _bwd, B4C_CAND_BCE / B4C_CAND_SOFTMAX: sampled-negative training losses */
 
 #endif /* B4C_H */
