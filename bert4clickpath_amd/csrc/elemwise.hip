@@ -882,44 +882,71 @@ extern "C" int b4c_poison_rows(void *x, int ld, int64_t rows, int width, const i
 
 // ------------------------------------------------------------------------------------------------------------------
 // Stable LSD radix sort of token positions by table row (the order the sorted embedding backward walks): 8-bit digits,
-// one wave per 1024-key chunk, per pass a histogram, two scan and a scatter launch.  order[i] = position of the i-th
-// smallest id (ties in position order) -- what torch.sort(stable) returned through 14 launches.
+// one 1024-thread workgroup per 4096-key chunk, two launches per pass (histogram, scatter).  order[i] = position of the
+// i-th smallest id (ties in position order) -- what torch.sort(stable) returned through 14 launches.
 //   ids int64 [n] (clamped to [0, n_rows - 1] as the embedding kernels clamp them); workspace: see b4c_sort_ids_workspace_bytes
+// A thread holds SORT_KPT keys, all loaded before the first is used; key r of thread t is element chunk + r * 1024 + t, so the
+// chunk's order is (r, wave, lane).  The clamped keys travel beside the positions from pass to pass (pass 2 reads two
+// coalesced arrays, not ids[pos[i]]).  The scatter takes its bases from the histogram itself:
+// base(d, b) = keys of the digits before d + keys of digit d in the chunks before b.  Up to SORT_DIRECT_BLOCKS chunks (1 M keys)
+// the counts are stored block-major, hist[nblocks][256], and every workgroup adds them up on its own (<= 256 KB, in L2: a
+// thread per digit, coalesced); past that they are stored digit-major, hist[256][nblocks], a scan launch (sort_rowscan_kernel)
+// leaves the row prefixes and the row totals, and a pass takes three launches.
 // ------------------------------------------------------------------------------------------------------------------
-#define SORT_CHUNK 1024
+#define SORT_THREADS 1024
+#define SORT_WAVES (SORT_THREADS / 64)
+#define SORT_KPT 4
+#define SORT_CHUNK (SORT_THREADS * SORT_KPT)
+#define SORT_DIRECT_BLOCKS 256
 
-__device__ __forceinline__ unsigned sort_key(const int64_t *ids, const int32_t *pos_in, int64_t i, int n_rows) {
-    const int64_t p = pos_in ? pos_in[i] : i;
-    int64_t v = ids[p];
-    v = v < 0 ? 0 : (v >= n_rows ? n_rows - 1 : v);
-    return (unsigned)v;
-}
-
-__global__ void __launch_bounds__(64) sort_hist_kernel(const int64_t *__restrict__ ids, const int32_t *__restrict__ pos_in, int64_t n,
-                                                       int n_rows, int shift, int nblocks, int32_t *__restrict__ hist) {
-    __shared__ int cnt[256];
-    const int lane = threadIdx.x;
-    for (int d = lane; d < 256; d += 64) cnt[d] = 0;
-    __builtin_amdgcn_wave_barrier();
-    const int64_t i0 = (int64_t)blockIdx.x * SORT_CHUNK;
-    for (int g = 0; g < SORT_CHUNK; g += 64) {
-        const int64_t i = i0 + g + lane;
-        if (i < n) atomicAdd(&cnt[(sort_key(ids, pos_in, i, n_rows) >> shift) & 255], 1);
+// the chunk's keys (and positions, when POS) into registers; dead slots (past n) repeat the last element and are masked later.
+// FIRST: pass 0, the keys are the clamped ids and the positions 0 .. n - 1; else both come from the pass before.
+template <bool FIRST, bool POS>
+__device__ __forceinline__ void sort_load(const int64_t *__restrict__ ids, const uint32_t *__restrict__ keys_in,
+                                          const int32_t *__restrict__ pos_in, int64_t n, int n_rows, int64_t i0,
+                                          uint32_t (&key)[SORT_KPT], int32_t (&pos)[SORT_KPT]) {
+    int64_t v[SORT_KPT];
+#pragma unroll
+    for (int r = 0; r < SORT_KPT; ++r) {
+        const int64_t i = i0 + r * SORT_THREADS + threadIdx.x;
+        const int64_t ic = i < n ? i : n - 1;
+        if (FIRST) v[r] = ids[ic];
+        else key[r] = keys_in[ic];
+        if (POS) pos[r] = FIRST ? (int32_t)ic : pos_in[ic];
     }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    for (int d = lane; d < 256; d += 64) hist[(int64_t)d * nblocks + blockIdx.x] = cnt[d];      // digit-major: one scan orders it
+    if (FIRST) {
+#pragma unroll
+        for (int r = 0; r < SORT_KPT; ++r) key[r] = (uint32_t)(v[r] < 0 ? 0 : (v[r] >= n_rows ? n_rows - 1 : v[r]));
+    }
 }
 
-// exclusive prefix sum over hist[256][nblocks] (digit-major) in place, in two launches of 256 workgroups: each digit's row
-// is scanned on its own and leaves its total; then every row adds the totals of the digits before it.  (One workgroup
-// walking all 256 * nblocks entries took 180 us.)
+template <bool FIRST>
+__global__ void __launch_bounds__(SORT_THREADS) sort_hist_kernel(const int64_t *__restrict__ ids, const uint32_t *__restrict__ keys_in,
+                                                                 int64_t n, int n_rows, int shift, int64_t digit_pitch, int block_pitch,
+                                                                 int32_t *__restrict__ hist) {
+    __shared__ int cnt[256];
+    const int tid = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * SORT_CHUNK;
+    uint32_t key[SORT_KPT];
+    int32_t pos[SORT_KPT];
+    sort_load<FIRST, false>(ids, keys_in, nullptr, n, n_rows, i0, key, pos);
+    if (tid < 256) cnt[tid] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < SORT_KPT; ++r)
+        if (i0 + r * SORT_THREADS + tid < n) atomicAdd(&cnt[(key[r] >> shift) & 255u], 1);
+    __syncthreads();
+    if (tid < 256) hist[tid * digit_pitch + (int64_t)blockIdx.x * block_pitch] = cnt[tid];
+}
+
+// exclusive prefix sum of every digit's row of hist[256][nblocks] in place, one workgroup per row; totals[d] = the row's sum
+// (only past SORT_DIRECT_BLOCKS chunks)
 __global__ void __launch_bounds__(256) sort_rowscan_kernel(int32_t *__restrict__ hist, int nblocks, int32_t *__restrict__ totals) {
     __shared__ int part[256];
     const int tid = threadIdx.x;
     int32_t *row = hist + (int64_t)blockIdx.x * nblocks;
     const int per = (nblocks + 255) / 256;
-    const int lo = tid * per, hi = min(nblocks, lo + per);
+    const int lo = min(nblocks, tid * per), hi = min(nblocks, lo + per);
     int s = 0;
     for (int i = lo; i < hi; ++i) s += row[i];
     part[tid] = s;
@@ -938,53 +965,119 @@ __global__ void __launch_bounds__(256) sort_rowscan_kernel(int32_t *__restrict__
     }
     if (tid == 255) totals[blockIdx.x] = part[255];
 }
-__global__ void __launch_bounds__(256) sort_addbase_kernel(int32_t *__restrict__ hist, int nblocks, const int32_t *__restrict__ totals) {
-    __shared__ int sbase;
-    if (threadIdx.x < 64) {
-        int s = 0;
-        for (int d = threadIdx.x; d < (int)blockIdx.x; d += 64) s += totals[d];
+
+// SCANNED: hist[256][nblocks] holds the row prefixes and totals the row sums (sort_rowscan_kernel ran); else hist[nblocks][256]
+// holds the raw counts
+template <bool SCANNED, bool FIRST>
+__global__ void __launch_bounds__(SORT_THREADS) sort_scatter_kernel(const int64_t *__restrict__ ids, const uint32_t *__restrict__ keys_in,
+                                                                    const int32_t *__restrict__ pos_in, int64_t n, int n_rows, int shift,
+                                                                    int nblocks, const int32_t *__restrict__ hist,
+                                                                    const int32_t *__restrict__ totals, uint32_t *__restrict__ keys_out,
+                                                                    int32_t *__restrict__ pos_out) {
+    __shared__ unsigned short cnt[SORT_KPT][SORT_WAVES][256];      // keys of digit d in (round r, wave w); then: before (r, w) within r
+    __shared__ int rtot[SORT_KPT][256];                            // keys of digit d in round r
+    __shared__ int base[256];                                      // first output slot of digit d of this chunk
+    __shared__ int sbef[4][256], stot[4][256];                     // partial sums: keys of digit d in the chunks before this one / in all
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int blk = blockIdx.x;
+    const int64_t i0 = (int64_t)blk * SORT_CHUNK;
+    uint32_t key[SORT_KPT];
+    int32_t pos[SORT_KPT];
+    sort_load<FIRST, true>(ids, keys_in, pos_in, n, n_rows, i0, key, pos);
+
+    {   // zero the counts: 32 KB, 32 B per thread
+        uint32_t *z = reinterpret_cast<uint32_t *>(&cnt[0][0][0]);
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if (threadIdx.x == 0) sbase = s;
+        for (int k = 0; k < SORT_KPT * SORT_WAVES * 256 / 2 / SORT_THREADS; ++k) z[k * SORT_THREADS + tid] = 0u;
+    }
+    // the histogram's share of the bases, as four partial sums per digit (thread = digit d, part q)
+    {
+        const int d = tid & 255, q = tid >> 8;
+        int bef = 0, tot = 0;
+        if (SCANNED) {
+            if (q == 0) {
+                bef = hist[(int64_t)d * nblocks + blk];
+                tot = totals[d];
+            }
+        } else {
+            // block-major counts hist[nblocks][256] (nblocks <= SORT_DIRECT_BLOCKS): part q adds the chunks q, q + 4, ..., sixteen
+            // loads in flight at a time (clamped, not conditional)
+            constexpr int NB = 16;
+            for (int b0 = q; b0 < nblocks; b0 += 4 * NB) {
+                int c[NB];
+#pragma unroll
+                for (int u = 0; u < NB; ++u) c[u] = hist[min(b0 + 4 * u, nblocks - 1) * 256 + d];
+#pragma unroll
+                for (int u = 0; u < NB; ++u) {
+                    const int b = b0 + 4 * u;
+                    tot += b < nblocks ? c[u] : 0;
+                    bef += b < blk ? c[u] : 0;
+                }
+            }
+        }
+        sbef[q][d] = bef;
+        stot[q][d] = tot;
     }
     __syncthreads();
-    const int base = sbase;
-    int32_t *row = hist + (int64_t)blockIdx.x * nblocks;
-    for (int i = threadIdx.x; i < nblocks; i += 256) row[i] += base;
-}
 
-__global__ void __launch_bounds__(64) sort_scatter_kernel(const int64_t *__restrict__ ids, const int32_t *__restrict__ pos_in, int64_t n,
-                                                          int n_rows, int shift, int nblocks, const int32_t *__restrict__ offs,
-                                                          int32_t *__restrict__ pos_out) {
-    __shared__ int base[256];
-    const int lane = threadIdx.x;
-    for (int d = lane; d < 256; d += 64) base[d] = offs[(int64_t)d * nblocks + blockIdx.x];
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const int64_t i0 = (int64_t)blockIdx.x * SORT_CHUNK;
-    for (int g = 0; g < SORT_CHUNK; g += 64) {
-        const int64_t i = i0 + g + lane;
-        const bool live = i < n;
-        const unsigned digit = live ? ((sort_key(ids, pos_in, i, n_rows) >> shift) & 255u) : 256u;      // 256: matches nobody live
-        // lanes with the same digit: eight ballots (one per bit), then the dead-lane bit
+    // rank inside the wave: lanes with the same digit (eight ballots, one per bit); the first of them leaves their count
+    int rank[SORT_KPT];
+#pragma unroll
+    for (int r = 0; r < SORT_KPT; ++r) {
+        const bool live = i0 + r * SORT_THREADS + tid < n;
+        const unsigned digit = (key[r] >> shift) & 255u;
         unsigned long long same = __ballot(live);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
             const unsigned long long m = __ballot((digit >> b) & 1u);
             same &= ((digit >> b) & 1u) ? m : ~m;
         }
-        const unsigned long long lt = (1ull << lane) - 1ull;
-        const int rank = __popcll(same & lt), count = __popcll(same);
-        int b0 = 0;
-        if (live) b0 = base[digit];
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (live) {
-            pos_out[b0 + rank] = pos_in ? pos_in[i] : (int32_t)i;
-            if (rank == count - 1) base[digit] = b0 + count;        // the group's last lane moves its digit's cursor
+        rank[r] = __popcll(same & ((1ull << lane) - 1ull));
+        if (live && rank[r] == 0) cnt[r][wave][digit] = (unsigned short)__popcll(same);
+    }
+    // digits before d in the whole array: wave 0 scans the digit totals, four digits per lane
+    if (wave == 0) {
+        int v[4], bef[4], sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int d = lane * 4 + k;
+            v[k] = stot[0][d] + stot[1][d] + stot[2][d] + stot[3][d];
+            bef[k] = sbef[0][d] + sbef[1][d] + sbef[2][d] + sbef[3][d];
+            sum += v[k];
         }
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        int inc = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(inc, o);
+            if (lane >= o) inc += t;
+        }
+        int run = inc - sum;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { base[lane * 4 + k] = bef[k] + run; run += v[k]; }
+    }
+    __syncthreads();
+    {   // thread (r, d): the waves of round r in order
+        const int r = tid >> 8, d = tid & 255;
+        int run = 0;
+#pragma unroll
+        for (int w = 0; w < SORT_WAVES; ++w) {
+            const int c = cnt[r][w][d];
+            cnt[r][w][d] = (unsigned short)run;
+            run += c;
+        }
+        rtot[r][d] = run;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < SORT_KPT; ++r) {
+        if (i0 + r * SORT_THREADS + tid >= n) continue;
+        const unsigned digit = (key[r] >> shift) & 255u;
+        int at = base[digit] + cnt[r][wave][digit] + rank[r];
+#pragma unroll
+        for (int q = 0; q < SORT_KPT - 1; ++q)
+            if (q < r) at += rtot[q][digit];
+        pos_out[at] = pos[r];
+        if (keys_out) keys_out[at] = key[r];
     }
 }
 
@@ -996,7 +1089,7 @@ static int sort_passes(int n_rows) {
 extern "C" int64_t b4c_sort_ids_workspace_bytes(int64_t n, int n_rows) {
     if (n <= 0) return 0;
     const int64_t nblocks = (n + SORT_CHUNK - 1) / SORT_CHUNK;
-    return (256 * nblocks + 256 + n) * 4;           // histogram + digit totals + one ping-pong position array
+    return (256 * nblocks + 256 + 3 * n) * 4;       // histogram + digit totals + one ping-pong position array + two key arrays
 }
 
 extern "C" int b4c_sort_ids(const int64_t *ids, int64_t n, int n_rows, int32_t *order, void *workspace, int64_t workspace_bytes,
@@ -1010,17 +1103,31 @@ extern "C" int b4c_sort_ids(const int64_t *ids, int64_t n, int n_rows, int32_t *
     int32_t *hist = (int32_t *)workspace;
     int32_t *totals = hist + 256 * (int64_t)nblocks;
     int32_t *tmp = totals + 256;
+    uint32_t *kbuf[2] = {(uint32_t *)(tmp + n), (uint32_t *)(tmp + 2 * n)};
     const int passes = sort_passes(n_rows);
+    const bool direct = nblocks <= SORT_DIRECT_BLOCKS;
     // the last pass must land in `order`: with an even number of passes the first goes to tmp
     int32_t *dst = (passes % 2) ? order : tmp;
-    const int32_t *src = nullptr;                    // pass 0 reads positions 0..n-1 implicitly
+    const int32_t *src = nullptr;                    // pass 0 reads positions 0..n-1 implicitly, and the keys from ids
+    const uint32_t *ksrc = nullptr;
     for (int p = 0; p < passes; ++p) {
-        sort_hist_kernel<<<nblocks, 64, 0, st>>>(ids, src, n, n_rows, 8 * p, nblocks, hist);
-        sort_rowscan_kernel<<<256, 256, 0, st>>>(hist, nblocks, totals);
-        sort_addbase_kernel<<<256, 256, 0, st>>>(hist, nblocks, totals);
-        sort_scatter_kernel<<<nblocks, 64, 0, st>>>(ids, src, n, n_rows, 8 * p, nblocks, hist, dst);
+        uint32_t *kdst = p + 1 < passes ? kbuf[p & 1] : nullptr;      // the last pass's keys are nobody's input
+        const int shift = 8 * p;
+        const int64_t dpitch = direct ? 1 : nblocks;
+        const int bpitch = direct ? 256 : 1;
+#define SORT_SCATTER(SC, FI) sort_scatter_kernel<SC, FI><<<nblocks, SORT_THREADS, 0, st>>>(ids, ksrc, src, n, n_rows, shift, nblocks, hist, totals, kdst, dst)
+        if (p == 0) sort_hist_kernel<true><<<nblocks, SORT_THREADS, 0, st>>>(ids, ksrc, n, n_rows, shift, dpitch, bpitch, hist);
+        else sort_hist_kernel<false><<<nblocks, SORT_THREADS, 0, st>>>(ids, ksrc, n, n_rows, shift, dpitch, bpitch, hist);
+        if (direct) {
+            if (p == 0) SORT_SCATTER(false, true); else SORT_SCATTER(false, false);
+        } else {
+            sort_rowscan_kernel<<<256, 256, 0, st>>>(hist, nblocks, totals);
+            if (p == 0) SORT_SCATTER(true, true); else SORT_SCATTER(true, false);
+        }
+#undef SORT_SCATTER
         src = dst;
         dst = (dst == order) ? tmp : order;
+        ksrc = kdst;
     }
     return b4c_check_launch("sort_ids");
 }

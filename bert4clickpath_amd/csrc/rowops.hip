@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(256) embed_bwd_kernel(EmbedArgs a, float scale
 }
 
 static int fill_embed_args(EmbedArgs &a, int n_feat, const int64_t *const *h_ids, float *const *h_tables,
-                           const int *h_dims, const int64_t *h_rows, int d_model) {
+                           const int *h_dims, const int64_t *h_rows, int d_model, int dim_multiple = 8) {
     B4C_REQUIRE(n_feat >= 1 && n_feat <= B4C_MAX_FEATURES, "embed: n_feat %d out of range", n_feat);
     memset(&a, 0, sizeof(a));
     a.n = n_feat;
@@ -153,7 +153,7 @@ static int fill_embed_args(EmbedArgs &a, int n_feat, const int64_t *const *h_ids
     for (int f = 0; f < n_feat; ++f) a.sum = a.sum && h_dims[f] == d_model;
     int off = 0;
     for (int f = 0; f < n_feat; ++f) {
-        B4C_REQUIRE(h_dims[f] > 0 && h_dims[f] % 8 == 0, "embed: feature dim %d must be a positive multiple of 8", h_dims[f]);
+        B4C_REQUIRE(h_dims[f] > 0 && h_dims[f] % dim_multiple == 0, "embed: feature dim %d must be a positive multiple of %d", h_dims[f], dim_multiple);
         B4C_REQUIRE(h_ids[f] && h_tables[f] && h_rows[f] > 0, "embed: null pointer / empty table for feature %d", f);
         a.ids[f] = h_ids[f];
         a.table[f] = h_tables[f];
@@ -358,8 +358,22 @@ struct EmbedOrder {
 // DET: a run that continues in a neighbouring wave's range is NOT added with float atomics (whose order, and so the sum's last
 // bit, changes from run to run): the wave stores its share -- slot 0: the run comes in from the wave before, slot 1: the run
 // goes on into the wave after -- and embed_bwd_runs_kernel adds the shares of one run in wave order.
+// Nothing the wave waits for sits inside its serial walk.  The row a run is added to is loaded with the batch of entries the
+// run starts in (every entry's row: a repeated id is a cache hit), so the run's end is one add and a store nobody waits for --
+// no other wave writes that row, a run inside the range has one owner.  The range's tokens and the two entries just outside it
+// are fetched together, then their ids together: two round trips before the first row.  What a batch holds per entry (token,
+// id) is read into scalar registers, so run boundaries are scalar branches.
+// Dropout: elements e .. e + 3 (e % 4 == 0) share one hash and belong to lanes 2k, 2k + 1; of two consecutive entries the even
+// lane hashes the first and the odd lane the second, and each hands its neighbour the 32 bits that one needs (needs d_model and
+// the feature's first column to be multiples of 4; else every lane hashes for itself).
+__device__ __forceinline__ int wave_get(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ int64_t wave_get(int64_t v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
 template <typename T, bool DET>
-__global__ void __launch_bounds__(256) embed_bwd_sorted_kernel(EmbedArgs a, EmbedOrder ord, float scale, const T *__restrict__ dout,
+__global__ void __launch_bounds__(256, 7) embed_bwd_sorted_kernel(EmbedArgs a, EmbedOrder ord, float scale, const T *__restrict__ dout,
                                                                int ld, int64_t T_tok, int d, float rate, uint64_t seed) {
     const int f = blockIdx.y;
     const int lane = threadIdx.x & 63;
@@ -370,26 +384,25 @@ __global__ void __launch_bounds__(256) embed_bwd_sorted_kernel(EmbedArgs a, Embe
     const int32_t *order = ord.order[f];
     const int64_t *ids = a.ids[f];
     const int64_t nrows = a.rows[f];
-    auto id_at = [&](int64_t p) -> int64_t {
-        int64_t id = ids[order[p]];
-        return id < 0 ? 0 : (id >= nrows ? nrows - 1 : id);
-    };
-    const int my_tok = lane < np ? order[p0 + lane] : 0;
-    int64_t my_id = -1;
-    if (lane < np) {
-        my_id = ids[my_tok];
-        my_id = my_id < 0 ? 0 : (my_id >= nrows ? nrows - 1 : my_id);
-    }
+    // lane 0: the entry before the range, the other lanes: the entry after it (clamped into the array; unused where there is none)
+    const int64_t pe = lane == 0 ? (p0 > 0 ? p0 - 1 : 0) : (p0 + np < T_tok ? p0 + np : T_tok - 1);
+    const int my_tok = lane < np ? order[p0 + lane] : 0;       // lanes past np hold token 0: a valid row
+    const int edge_tok = order[pe];
+    int64_t my_id = ids[my_tok], edge_id = ids[edge_tok];
+    my_id = my_id < 0 ? 0 : (my_id >= nrows ? nrows - 1 : my_id);
+    edge_id = edge_id < 0 ? 0 : (edge_id >= nrows ? nrows - 1 : edge_id);
     // the ids just outside the range (wave-uniform)
-    const int64_t prev_id = p0 > 0 ? id_at(p0 - 1) : -2, next_id = p0 + np < T_tok ? id_at(p0 + np) : -3;
+    const int64_t prev_id = p0 > 0 ? wave_get(edge_id, 0) : -2, next_id = p0 + np < T_tok ? wave_get(edge_id, 1) : -3;
     const float mul = scale * (rate > 0.f ? 1.0f / (1.0f - rate) : 1.0f);
     const uint32_t thr = b4c_keep_threshold(rate);
+    const bool pair_hash = ((d | c0) & 3) == 0;
+    const bool odd = lane & 1;
     float *table = a.table[f];
     for (int cb = 0; cb < fd; cb += 128) {          // 128 columns per pass: the lane owns columns cb + 2 lane, + 1
         const int col = cb + 2 * lane;
         const bool on = col < fd;
-        float acc0 = 0.f, acc1 = 0.f;
-        int64_t cur = __shfl(my_id, 0);
+        float acc0 = 0.f, acc1 = 0.f, row0 = 0.f, row1 = 0.f;      // row: the gradient row of the current run as the kernel found it
+        int64_t cur = -1;                            // no run yet
         auto flush = [&](int64_t id) {
             if (DET && (id == prev_id || id == next_id)) {
                 if (on) {
@@ -405,25 +418,63 @@ __global__ void __launch_bounds__(256) embed_bwd_sorted_kernel(EmbedArgs a, Embe
                     atomicAdd(row, acc0);
                     atomicAdd(row + 1, acc1);
                 } else {
-                    row[0] += acc0;
-                    row[1] += acc1;
+                    row[0] = row0 + acc0;
+                    row[1] = row1 + acc1;
                 }
             }
         };
         constexpr int NR = 8;                        // rows in flight (16 measured slower)
         const int colc = on ? col : 0;               // loads are unconditional on clamped indices (a conditional load is
         for (int j0 = 0; j0 < np; j0 += NR) {        // waited for at its join: one row in flight instead of NR)
-            float g0[NR], g1[NR];
+            float g0[NR], g1[NR], t0[NR], t1[NR];
+            uint32_t gp[NR];                         // bf16: the two columns as loaded, one dword
             int tk[NR];
             int64_t idj[NR];
+            uint32_t drop = 0u;                      // bit 2 u: column col of entry u is dropped, bit 2 u + 1: column col + 1
 #pragma unroll
             for (int u = 0; u < NR; ++u) {
-                const int j = j0 + u;
-                tk[u] = __shfl(my_tok, j & 63);      // lanes past np hold token 0: a valid row
-                idj[u] = __shfl(my_id, j & 63);
+                const int j = (j0 + u) & 63;
+                tk[u] = wave_get(my_tok, j);
+                idj[u] = wave_get(my_id, j);
                 const T *src = dout + (int64_t)tk[u] * ld + c0 + colc;
-                g0[u] = (float)src[0];
-                g1[u] = (float)src[1];
+                if constexpr (sizeof(T) == 2) {      // ld, c0 and col are even: the pair is one aligned dword
+                    gp[u] = *reinterpret_cast<const uint32_t *>(src);
+                } else {
+                    g0[u] = (float)src[0];
+                    g1[u] = (float)src[1];
+                }
+                const float *trow = table + idj[u] * fd + colc;
+                t0[u] = trow[0];
+                t1[u] = trow[1];
+            }
+            if constexpr (sizeof(T) == 2) {
+#pragma unroll
+                for (int u = 0; u < NR; ++u) {
+                    g0[u] = __uint_as_float(gp[u] << 16);
+                    g1[u] = __uint_as_float(gp[u] & 0xFFFF0000u);
+                }
+            }
+            if (rate > 0.f) {
+                if (pair_hash) {
+#pragma unroll
+                    for (int u = 0; u < NR; u += 2) {
+                        const uint64_t e = (uint64_t)(odd ? tk[u + 1] : tk[u]) * d + c0 + col;
+                        const uint64_t hsh = b4c_rand64(seed, e >> 2);
+                        const uint32_t x0 = (uint32_t)hsh, x1 = (uint32_t)(hsh >> 32);
+                        const uint32_t mine = odd ? x1 : x0;
+                        const uint32_t got = (uint32_t)__builtin_amdgcn_mov_dpp((int)(odd ? x0 : x1), 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
+                        const uint32_t ka = odd ? got : mine, kb = odd ? mine : got;
+                        drop |= ((ka & 0xFFFFu) < thr ? 1u : 0u) << (2 * u) | ((ka >> 16) < thr ? 2u : 0u) << (2 * u);
+                        drop |= ((kb & 0xFFFFu) < thr ? 4u : 0u) << (2 * u) | ((kb >> 16) < thr ? 8u : 0u) << (2 * u);
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < NR; ++u) {
+                        const uint64_t e = (uint64_t)tk[u] * d + c0 + col;      // e and e + 1 share a 4-element block
+                        const uint32_t kb = (uint32_t)(b4c_rand64(seed, e >> 2) >> (16 * (int)(e & 3)));
+                        drop |= ((kb & 0xFFFFu) < thr ? 1u : 0u) << (2 * u) | ((kb >> 16) < thr ? 2u : 0u) << (2 * u);
+                    }
+                }
             }
 #pragma unroll
             for (int u = 0; u < NR; ++u) {
@@ -433,20 +484,17 @@ __global__ void __launch_bounds__(256) embed_bwd_sorted_kernel(EmbedArgs a, Embe
             for (int u = 0; u < NR; ++u) {
                 if (j0 + u >= np) break;             // wave-uniform
                 if (idj[u] != cur) {                 // wave-uniform
-                    flush(cur);
+                    if (cur >= 0) flush(cur);
                     acc0 = acc1 = 0.f;
                     cur = idj[u];
+                    row0 = t0[u];
+                    row1 = t1[u];
                 }
                 if (g0[u] != 0.f || g1[u] != 0.f) {
-                    if (rate > 0.f) {
-                        const uint64_t e = (uint64_t)tk[u] * d + c0 + col;      // e and e + 1 share a 4-element block
-                        const uint64_t hsh = b4c_rand64(seed, e >> 2);
-                        const int sh = 16 * (int)(e & 3);
-                        if (((uint32_t)(hsh >> sh) & 0xFFFFu) < thr) g0[u] = 0.f;
-                        if (((uint32_t)(hsh >> (sh + 16)) & 0xFFFFu) < thr) g1[u] = 0.f;
-                    }
-                    acc0 += g0[u] * mul;
-                    acc1 += g1[u] * mul;
+                    if ((drop >> (2 * u)) & 1u) g0[u] = 0.f;
+                    if ((drop >> (2 * u)) & 2u) g1[u] = 0.f;
+                    acc0 = __builtin_fmaf(g0[u], mul, acc0);        // one rounding per entry, in sorted order
+                    acc1 = __builtin_fmaf(g1[u], mul, acc1);
                 }
             }
         }
@@ -472,16 +520,24 @@ __global__ void __launch_bounds__(256) embed_bwd_runs_kernel(EmbedArgs a, EmbedO
         return id < 0 ? 0 : (id >= nrows ? nrows - 1 : id);
     };
     const int64_t pb = b << 6;                              // first entry of range b
-    const int64_t id = id_at(pb + 63);
-    if (id_at(pb + 64) != id) return;                       // nothing crosses this boundary
+    const int64_t id = id_at(pb + 63), id_after = id_at(pb + 64);      // (both chains in flight together)
+    if (id_after != id) return;                             // nothing crosses this boundary
     if (id_at(pb) == id && b > 0 && id_at(pb - 1) == id) return;      // the run came in from before range b: not its first range
     // the last range the run reaches into: the entries are sorted by id, so "first entry of range w is this id" is monotone in w
-    // -- a binary search instead of a walk (the hottest id of a Zipf batch fills hundreds of ranges, and every step of a walk
-    // is two dependent loads)
+    // -- a 64-way search instead of a walk (the hottest id of a Zipf batch fills hundreds of ranges, and every step of a walk
+    // is two dependent loads): the lanes probe 64 ranges at once, so 7,000 ranges take three steps where halving took thirteen
     int64_t lo = b + 1, hi = nw - 1;                        // range b + 1 starts with this id; find the largest w that does
     while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (id_at(mid << 6) == id) lo = mid; else hi = mid - 1;
+        const int64_t step = (hi - lo + 63) >> 6;           // lane l probes range lo + (l + 1) step, clamped to hi
+        const int64_t w = min(lo + (lane + 1) * step, hi);
+        const int k = __popcll(__ballot(id_at(w << 6) == id));      // monotone: exactly the first k probes start with this id
+        if (k == 64) {                                      // probe 63 is range hi
+            lo = hi;
+            break;
+        }
+        const int64_t fail = min(lo + (k + 1) * step, hi);  // probe k: the first that does not
+        if (k > 0) lo = min(lo + k * step, hi);
+        hi = fail - 1;
     }
     const int64_t e = lo;
     const float *part = ord.part[f];
@@ -491,18 +547,18 @@ __global__ void __launch_bounds__(256) embed_bwd_runs_kernel(EmbedArgs a, EmbedO
         if (col >= fd) continue;
         const float *t = part + (b * 2 + 1) * (int64_t)fd + col;
         float s0 = t[0], s1 = t[1];
-        // (independent loads: the order of the adds is what is fixed) -- 16 shares in flight, then added in range order
+        // (independent loads: the order of the adds is what is fixed) -- 32 shares in flight, then added in range order
         int64_t w = b + 1;
-        for (; w + 16 <= e + 1; w += 16) {
-            float x0[16], x1[16];
+        for (; w + 32 <= e + 1; w += 32) {
+            float x0[32], x1[32];
 #pragma unroll
-            for (int u = 0; u < 16; ++u) {
+            for (int u = 0; u < 32; ++u) {
                 const float *h = part + ((w + u) * 2) * (int64_t)fd + col;
                 x0[u] = h[0];
                 x1[u] = h[1];
             }
 #pragma unroll
-            for (int u = 0; u < 16; ++u) { s0 += x0[u]; s1 += x1[u]; }
+            for (int u = 0; u < 32; ++u) { s0 += x0[u]; s1 += x1[u]; }
         }
         for (; w <= e; ++w) {
             const float *h = part + (w * 2) * (int64_t)fd + col;
@@ -535,9 +591,10 @@ extern "C" int b4c_embed_concat_pe_bwd_sorted_ws(int n_feat, const int64_t *cons
                                                  const void *dout, int ld_dout, int B, int S, int d_model, float dropout_rate,
                                                  uint64_t seed, void *workspace, int64_t workspace_bytes, int dtype, void *stream) {
     EmbedArgs a;
-    int rc = fill_embed_args(a, n_feat, h_ids, h_dtables, h_dims, h_rows, d_model);
+    int rc = fill_embed_args(a, n_feat, h_ids, h_dtables, h_dims, h_rows, d_model, 2);       // a lane owns two columns: even widths
     if (rc) return rc;
-    B4C_REQUIRE(dout && h_order && B > 0 && S > 0 && ld_dout >= d_model && ld_dout % 2 == 0, "embed_bwd_sorted: bad shape");
+    B4C_REQUIRE(dout && h_order && B > 0 && S > 0 && ld_dout >= d_model && ld_dout % 2 == 0 && ((uintptr_t)dout & 3) == 0,
+                "embed_bwd_sorted: bad shape (dout 4-byte aligned, even pitch)");
     B4C_REQUIRE((int64_t)B * S < (1ll << 31), "embed_bwd_sorted: more than 2^31 tokens");
     EmbedOrder ord = {};
     const int64_t T_tok = (int64_t)B * S;
@@ -1429,8 +1486,10 @@ __global__ void __launch_bounds__(256) pack_batched_kernel(const b4c_pack_desc *
             }
         }
     }
-    if (blockIdx.x == 0 && d.bias_src && d.bias_dst)
-        for (int n = threadIdx.x; n < d.N; n += 256) d.bias_dst[d.col_off + n] = d.bias_src[n];
+    // the bias: every tile of the first tile row copies its own 64 columns.  (One workgroup copying all N of them was the
+    // launch's critical path: at N = 50,000 that is 196 load - store trips one after the other in one workgroup while the
+    // other 1,563 have long finished -- the [128][50,000] projection alone took 57 us with it and takes 13 us without.)
+    if (k0 == 0 && tid < 64 && n0 + tid < d.N && d.bias_src && d.bias_dst) d.bias_dst[d.col_off + n0 + tid] = d.bias_src[n0 + tid];
 }
 
 extern "C" int b4c_pack_weights_batched(const b4c_pack_desc *d_desc, int n_desc, int max_tiles, int dtype, void *stream) {

@@ -247,7 +247,7 @@ def embed_concat_pe_fwd(ids_list, tables, pe, scale, rate, seed, dtype, packed=N
     return out, key_pad
 
 
-library_sort = True      # b4c_sort_ids (6 - 9 launches) instead of torch.sort (14 launches through rocPRIM)
+library_sort = True      # b4c_sort_ids (2 launches per 8-bit pass) instead of torch.sort (14 launches through rocPRIM)
 
 
 # ---- scratch memory the library's entry points take from the caller -----------------------------------------------------

@@ -761,7 +761,7 @@ int b4c_attn_bwd_varlen(const void *qkv, int ld_qkv, const uint8_t *key_pad, con
  * dh in {32, 64}; max_len = longest sequence (LDS sizing). */
 /* order[i] = position (0..n-1) of the i-th smallest id, ties in position order (a stable sort of the token positions by
  * table row: the order b4c_embed_concat_pe_bwd_sorted walks); ids are clamped to [0, n_rows - 1] as the embedding kernels
- * clamp them.  LSD radix, 8-bit digits, 4 launches per pass; workspace >= b4c_sort_ids_workspace_bytes(n, n_rows), 4-B aligned. */
+ * clamp them.  LSD radix, 8-bit digits, 2 launches per pass (3 past 1 M keys); workspace >= b4c_sort_ids_workspace_bytes(n, n_rows), 4-B aligned. */
 int64_t b4c_sort_ids_workspace_bytes(int64_t n, int n_rows);
 int b4c_sort_ids(const int64_t *ids, int64_t n, int n_rows, int32_t *order, void *workspace, int64_t workspace_bytes, void *stream);
 int b4c_gather_i64(const int64_t *src, const int32_t *idx, int64_t *out, int64_t n, void *stream);   /* out[i] = src[idx[i]] */
