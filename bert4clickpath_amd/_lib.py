@@ -11,7 +11,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')
 EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_ex.h'),)
 # add-on headers: the entry points of later features, one header each, which b4c.h includes as well.  A feature adds its header
 # here: lib() binds whatever these declare (addon_signatures()); signatures() and all_signatures() keep to the lists above.
-ADDON_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss.h'),)
+ADDON_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss.h'),
+                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_next_item.h'))
 
 
 class B4CError(RuntimeError):
@@ -132,6 +133,8 @@ MAX_EXCL, MAX_CAND = _C['B4C_MAX_EXCL'], _C['B4C_MAX_CAND']
 GRAD_CHUNK, GRAD_GROUP = _C['B4C_GRAD_CHUNK'], _C['B4C_GRAD_GROUP']
 ATTN_CAUSAL = _C['B4C_ATTN_CAUSAL']       # flag bit of the b4c_attn_*_ex entry points
 CAND_BCE, CAND_SOFTMAX = _C['B4C_CAND_BCE'], _C['B4C_CAND_SOFTMAX']      # loss kinds of b4c_candidate_loss_fwd
+NEXT_TRAIN, NEXT_EVAL = _C['B4C_NEXT_TRAIN'], _C['B4C_NEXT_EVAL']        # modes of b4c_next_item_batch
+NEXT_EXCL_NONE, NEXT_EXCL_HISTORY = _C['B4C_NEXT_EXCL_NONE'], _C['B4C_NEXT_EXCL_HISTORY']
 
 _lib = None
 

@@ -488,6 +488,30 @@ class ClickstreamTransformer(nn.Module):
             out = out + torch.where(bad, float('nan'), 0.0).to(out.dtype)
         return out
 
+    def next_item_loss(self, batch, loss='full', variant='tf', unit_grad=False, training=True):
+        """Next-item training loss of a device-built batch (cloze_batches.DeviceCloze.next_item_batches): every real position of
+        the unmasked rows predicts the item after it.  loss 'full': cloze_loss over the whole vocabulary (variant as there);
+        'bce' / 'softmax': candidate_loss over the batch's own lists (built with num_negatives > 0).  A thin entry: the batch's
+        flat_idx, labels, candidates and n_real_tokens go to those two methods, whose NaN conventions carry over; compact rows
+        past the batch's targets (rows=) are ignored rows."""
+        if loss != 'full' and loss not in ops.CAND_LOSS_KINDS:
+            raise B4CError("next_item_loss: loss %r ('full', 'bce' or 'softmax')" % (loss,))
+        inputs = {self._next_item_feature(): batch['items']}
+        if loss == 'full':
+            return self.cloze_loss(inputs, batch['labels'], training=training, flat_idx=batch['flat_idx'], variant=variant,
+                                   unit_grad=unit_grad, n_real_tokens=batch['n_real_tokens'])
+        if batch.get('candidates') is None:
+            raise B4CError('next_item_loss: loss %r needs the batch\'s candidate lists; build it with num_negatives > 0' % (loss,))
+        return self.candidate_loss(inputs, batch['labels'], candidates=batch['candidates'], loss=loss, training=training,
+                                   flat_idx=batch['flat_idx'], unit_grad=unit_grad, n_real_tokens=batch['n_real_tokens'])
+
+    def _next_item_feature(self):
+        """the one feature of a one-feature model: the layout [CLS] [SEP] items .. [SEP] the batch's flat_idx is built for"""
+        names = [n for chain in self.sequential_input_config.values() for n in chain]
+        if len(names) != 1:
+            raise B4CError('next_item_loss: a one-feature model is needed (multi-feature next-item batches are not built), got %s' % names)
+        return names[0]
+
     @torch.no_grad()
     def predict_topk(self, inputs, k, labels=None, flat_idx=None, packed=None, n_real_tokens=None, exclude=None, candidates=None):
         """Top-k item ids (label space) at every masked position, ranked over all V items: the fp32 path ranks the fp32

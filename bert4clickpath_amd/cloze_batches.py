@@ -12,7 +12,11 @@ A row is a WINDOW of a sequence.  By default every sequence is one window (all b
 evaluation).  The BERT4Rec paper's data protocol is four constructor arguments: max_len / stride cut the training view of a long
 sequence into sliding windows and keep the most recent max_len positions for evaluation, holdout=2 holds out the penultimate
 item for validation and the last for test, last_item_rate adds training rows whose only masked position is the last one.  The
-window table is built once with numpy and uploaded once; a batch names its windows by index."""
+window table is built once with numpy and uploaded once; a batch names its windows by index.
+
+The next_item_* methods build the left-to-right objective over the same windows (ops.next_item_batch, include/b4c_next_item.h): rows
+without a [MASK], every real position's target the item after it, each target's own sampled negatives; model.next_item_loss takes
+such a batch."""
 import collections
 
 import numpy as np
@@ -90,6 +94,7 @@ class DeviceCloze:
         self._win_count = np.bincount(self.windows.seq, minlength=self.n_seq)
         self._win_first = np.cumsum(self._win_count) - self._win_count
         self._eval = {}                                              # split -> (Windows, device tensors)
+        self._next_tr, self._next_ev = None, {}                      # the next-item rows' target counts: TRAIN table, split -> EVAL tables
         self.items_dev = self.offsets_dev = self.windows_dev = None
         if device is not None:
             self.items_dev = torch.from_numpy(items).to(device)
@@ -237,6 +242,119 @@ class DeviceCloze:
         seq_dev = torch.arange(n, dtype=torch.int32, device=self.items_dev.device)
         for s in range(0, n, batch_size):
             yield self._batch(table, seq[s:s + batch_size], seq_dev[s:s + batch_size], seq_dev[s:s + batch_size], EVAL, 0, width)
+
+    # ---- next-item batches: every real position predicts the item after it (include/b4c_next_item.h) -------------------------
+    def next_item_counts(self, win_idx):
+        """host int64: inputs (= targets) of the TRAIN next-item row of every named window; a negative index: 0.  A window at
+        a > 0 takes one extra input in front, the first window of a sequence gives up its last item as a target only."""
+        win = np.asarray(win_idx, dtype=np.int64).reshape(-1)
+        return np.where(win >= 0, self._next_train()[0][np.maximum(win, 0)], 0)
+
+    def next_item_sizes(self, win_idx):
+        """host (n_targets, n_real_tokens) of the TRAIN next-item batch of the named windows"""
+        n_in = self.next_item_counts(win_idx)
+        return int(n_in.sum()), int(n_in.sum()) + 3 * len(n_in)
+
+    def _next_train(self):
+        """(host int64 [n_windows], device int32 [n_windows]): the target count of every window's row, uploaded once"""
+        if self._next_tr is None:
+            w = self.windows
+            n_in = np.where(w.start > 0, w.len, np.maximum(w.len - 1, 0)).astype(np.int64)
+            self._next_tr = (n_in, self._upload(n_in))
+        return self._next_tr
+
+    def _next_eval(self, split):
+        """split -> (n_in host [n_seq], has-target host [n_seq], has-target device int32, first compact row of every sequence
+        host [n_seq + 1], the sequences that have a target device int32): sequence g's row is the most recent
+        min(t, max_len) items in front of its target t = n_g - drop; t < 1: no target"""
+        if split not in self._next_ev:
+            t = self.lengths - self._drop(split)
+            n_in = np.maximum(t, 0) if self.max_len is None else np.minimum(np.maximum(t, 0), self.max_len)
+            has = (t >= 1).astype(np.int64)
+            first = np.concatenate([[0], np.cumsum(has)])
+            self._next_ev[split] = (n_in.astype(np.int64), has, self._upload(has), first, self._upload(np.flatnonzero(has)))
+        return self._next_ev[split]
+
+    def _next_batch(self, mode, row_host, row_dev, seq_dev, n_in, n_tgt, cnt_dev, seed, width, num_negatives, exclude, item_cdf, rows,
+                    holdout):
+        """rows row_host (TRAIN: window indices, EVAL: sequences; negative: an empty row) with their host-known input and target
+        counts, and the device table cnt_dev of target counts that row_dev indexes -> the batch dict"""
+        W = self._width(n_in, width)
+        if W > ops.CLOZE_MAX_WIDTH:
+            raise ValueError('DeviceCloze: a row of %d items; at most %d' % (W, ops.CLOZE_MAX_WIDTH))
+        R = int(n_tgt.sum())
+        if rows is not None and int(rows) < R:
+            raise ValueError('DeviceCloze: rows = %d for a batch of %d targets' % (rows, R))
+        self._need_device()
+        B = len(row_host)
+        cnt = cnt_dev[row_dev.clamp(min=0).long()] * (row_dev >= 0)
+        row_off = torch.zeros(B + 1, dtype=torch.int32, device=row_dev.device)
+        row_off[1:] = torch.cumsum(cnt, 0)
+        win = self.windows_dev if mode == ops.NEXT_TRAIN else (None, None, None)
+        items, flat, lab, cand, short = ops.next_item_batch(
+            self.items_dev, self.offsets_dev, win[0], win[1], win[2], row_dev, row_off, W, mode, R, self.V, holdout=holdout,
+            max_len=self.max_len, num_negatives=num_negatives, seed=seed, exclude=exclude, item_cdf=item_cdf, rows=rows)
+        return {'items': items, 'flat_idx': flat, 'labels': lab, 'candidates': cand, 'row_offsets': row_off, 'short': short,
+                'seq_idx': seq_dev, 'win_idx': row_dev, 'n_targets': R, 'n_real_tokens': int(n_in.sum()) + 3 * B}
+
+    def next_item_window_batch(self, win_idx, seed=0, width=None, num_negatives=0, exclude='history', item_cdf=None, rows=None):
+        """One TRAIN next-item batch of the windows win_idx (host indices into self.windows, any order, repeats allowed; negative:
+        an empty row) -> dict(items (B, W) int64 -- no [MASK] --, flat_idx [R] int32, labels [R] int32, candidates [R, 1 + N]
+        int32 or None, row_offsets [B + 1] int32, short int32 [1], seq_idx, win_idx: device tensors; n_targets = R,
+        n_real_tokens: host ints): what model.next_item_loss takes.  rows: a fixed compact row count >= R (the rest all -1).
+        num_negatives, exclude ('history': never an item of the sequence's training view; None), item_cdf (device int64 [V]):
+        each target's own negatives, a pure function of (seed, the target token)."""
+        win = np.asarray(win_idx, dtype=np.int64).reshape(-1)
+        if len(win) and win.max() >= self.n_windows:
+            raise ValueError('DeviceCloze: window indices outside [0, %d)' % self.n_windows)
+        n_in = self.next_item_counts(win)
+        seq = np.where(win >= 0, self.windows.seq[np.maximum(win, 0)] if self.n_windows else 0, -1)
+        return self._next_batch(ops.NEXT_TRAIN, win, self._upload(win), self._upload(seq), n_in, n_in, self._next_train()[1], seed, width,
+                                num_negatives, exclude, item_cdf, rows, self.holdout)
+
+    def next_item_batches(self, batch_size, seed, steps, rank=0, world=1, width=None, num_negatives=0, exclude='history', item_cdf=None,
+                          rows=None):
+        """`steps` TRAIN next-item batches of batch_size windows for rank `rank` of `world`: train_batches' epoch permutation
+        (uploaded once per epoch), rank slices and per-epoch seed rand64_host(seed, e); no per-batch upload."""
+        self._need_device()
+        order, slices = self.rank_slices(batch_size, seed, 0, rank, world)
+        if steps > 0 and not slices:
+            raise ValueError('DeviceCloze: %d %s do not fill one batch of %d x %d'
+                             % (self.n_windows, 'sequences' if self.max_len is None else 'windows', batch_size, world))
+        n_in_all, cnt_dev = self._next_train()
+        done = epoch = 0
+        while done < steps:
+            if epoch:
+                order, slices = self.rank_slices(batch_size, seed, epoch, rank, world)
+            order_dev = self._upload(order)
+            seq_dev = self.windows_dev[0][order_dev.long()]
+            draw_seed = int(ops.rand64_host(seed, epoch))
+            for lo, hi in slices:
+                n_in = n_in_all[order[lo:hi]]
+                yield self._next_batch(ops.NEXT_TRAIN, order[lo:hi], order_dev[lo:hi], seq_dev[lo:hi], n_in, n_in, cnt_dev, draw_seed,
+                                       width, num_negatives, exclude, item_cdf, rows, self.holdout)
+                done += 1
+                if done >= steps:
+                    return
+            epoch += 1
+
+    def next_item_eval_batches(self, batch_size, limit=None, width=None, split='test'):
+        """EVAL next-item batches of the sequences 0 .. limit in order, the last one partial: every row is the most recent
+        max_len items in front of the split's target, unmasked, and has ONE compact row -- at its last input -- whose label is
+        the target; a sequence with nothing in front of its target has none.  Beside next_item_window_batch's keys:
+        'target_seq_idx' int32 [R], the sequence of every compact row (history(b['target_seq_idx'], split) is their exclude=)."""
+        n_in_all, has, has_dev, first, tgt_seq_dev = self._next_eval(split)
+        drop = self._drop(split)
+        self._need_device()
+        n = self.n_seq if limit is None else min(int(limit), self.n_seq)
+        seq = np.arange(n, dtype=np.int64)
+        seq_dev = torch.arange(n, dtype=torch.int32, device=self.items_dev.device)
+        for s in range(0, n, batch_size):
+            e = min(s + batch_size, n)
+            b = self._next_batch(ops.NEXT_EVAL, seq[s:e], seq_dev[s:e], seq_dev[s:e], n_in_all[s:e], has[s:e], has_dev, 0, width, 0, None,
+                                 None, None, drop)
+            b['target_seq_idx'] = tgt_seq_dev[int(first[s]):int(first[e])]
+            yield b
 
     # ---- filtered evaluation ---------------------------------------------------------------------------------------------------
     def history(self, seq_idx_dev, split='test', width=None):

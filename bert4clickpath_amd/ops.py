@@ -1813,6 +1813,121 @@ def cloze_history(items, offsets, seq_idx, E, drop=1):
     return out
 
 
+NEXT_TRAIN, NEXT_EVAL = L.NEXT_TRAIN, L.NEXT_EVAL            # modes of next_item_batch (include/b4c_next_item.h)
+NEXT_EXCLUDE = {None: L.NEXT_EXCL_NONE, 'history': L.NEXT_EXCL_HISTORY}
+
+
+def _next_item_args(who, W, mode, holdout, max_len, V, num_negatives, seed, exclude):
+    """the checks next_item_batch and next_item_row_host share -> (W, mode, holdout, max_len, V, N, excl code)"""
+    W, mode, holdout, V, N = int(W), int(mode), int(holdout), int(V), int(num_negatives)
+    if mode not in (NEXT_TRAIN, NEXT_EVAL):
+        raise B4CError('%s: mode %d (NEXT_TRAIN = 0, NEXT_EVAL = 1)' % (who, mode))
+    if not 1 <= W <= CLOZE_MAX_WIDTH:
+        raise B4CError('%s: W = %d (1 .. %d)' % (who, W, CLOZE_MAX_WIDTH))
+    max_len = CLOZE_MAX_WIDTH if max_len is None else int(max_len)
+    if holdout < 0 or (mode == NEXT_EVAL and (holdout < 1 or max_len < 1)):
+        raise B4CError('%s: holdout / drop = %d (TRAIN: >= 0, EVAL: >= 1), max_len = %d (>= 1)' % (who, holdout, max_len))
+    if V <= 0 or not 0 <= N < L.MAX_CAND:
+        raise B4CError('%s: V = %d, num_negatives = %d (0 .. %d)' % (who, V, N, L.MAX_CAND - 1))
+    if exclude not in NEXT_EXCLUDE:
+        raise B4CError("%s: exclude %r ('history' or None)" % (who, exclude))
+    if not 0 <= int(seed) < (1 << 64):
+        raise B4CError('%s: seed %d (0 .. 2^64)' % (who, seed))
+    return W, mode, holdout, max_len, V, N, NEXT_EXCLUDE[exclude]
+
+
+def next_item_batch(items, offsets, win_seq, win_start, win_len, row_win, row_off, W, mode, n_targets, V, holdout=1, max_len=None,
+                    num_negatives=0, seed=0, exclude='history', item_cdf=None, rows=None):
+    """-> (items_out int64 [B, W], flat_idx int32 [rows], labels int32 [rows], cand int32 [rows, 1 + N] or None, short int32 [1])
+    (b4c_next_item_batch, include/b4c_next_item.h): the next-item batch of the rows row_win -- NEXT_TRAIN: windows of the device
+    table (win_seq, win_start, win_len), every input position's target the item after it; NEXT_EVAL: sequences, one target each
+    (item n_g - holdout) behind the most recent max_len inputs; a negative entry: an empty row.  No [MASK] anywhere.
+    row_off int32 [B + 1]: the exclusive prefix sum of the rows' target counts, on the device; n_targets = row_off[B] as the HOST
+    knows it (nothing is read back); rows (default n_targets) compact rows come back, those past n_targets all -1.
+    num_negatives N > 0: cand[r] = [label, N negatives], each list what ops.sample_candidates draws for that one target with
+    row_base = the target token's CSR index, excluding ('history') the sequence's items in front of the held-out ones.
+    Stream-ordered: row_win and the table are NOT checked against the data set."""
+    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
+        raise B4CError('next_item_batch: items must be an int32 [N] tensor of item indices')
+    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
+        raise B4CError('next_item_batch: offsets must be an int64 [n_seq + 1] tensor')
+    W, mode, holdout, max_len, V, N, excl = _next_item_args('next_item_batch', W, mode, holdout, max_len, V, num_negatives, seed, exclude)
+    if mode == NEXT_TRAIN:
+        for name, t in (('win_seq', win_seq), ('win_start', win_start), ('win_len', win_len)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.shape[0] != win_seq.shape[0]:
+                raise B4CError('next_item_batch: %s must be an int32 [n_win] tensor (win_seq, win_start, win_len: one length)' % name)
+    else:
+        win_seq = win_start = win_len = None
+    if not isinstance(row_win, torch.Tensor) or row_win.dim() != 1 or row_win.dtype != torch.int32:
+        raise B4CError('next_item_batch: row_win must be an int32 [B] tensor of window (TRAIN) or sequence (EVAL) indices')
+    B = row_win.shape[0]
+    if not isinstance(row_off, torch.Tensor) or row_off.dtype != torch.int32 or row_off.dim() != 1 or row_off.shape[0] != B + 1:
+        raise B4CError('next_item_batch: row_off must be an int32 [B + 1] = [%d] tensor' % (B + 1))
+    R = int(n_targets)
+    rows = R if rows is None else int(rows)
+    if R < 0 or rows < R:
+        raise ValueError('next_item_batch: rows = %d for %d targets' % (rows, R))
+    if B * (W + 3) >= 1 << 31:
+        raise B4CError('next_item_batch: B (W + 3) = %d does not fit the int32 flat_idx' % (B * (W + 3)))
+    if item_cdf is not None:
+        if not isinstance(item_cdf, torch.Tensor) or item_cdf.dtype != torch.int64 or item_cdf.dim() != 1 or item_cdf.shape[0] != V:
+            raise B4CError('next_item_batch: item_cdf must be an int64 [V] = [%d] prefix sum of item counts' % V)
+        item_cdf = item_cdf.contiguous()
+    _cuda(items, offsets, win_seq, win_start, win_len, row_win, row_off, item_cdf)
+    items, offsets, row_win, row_off = items.contiguous(), offsets.contiguous(), row_win.contiguous(), row_off.contiguous()
+    if mode == NEXT_TRAIN:
+        win_seq, win_start, win_len = win_seq.contiguous(), win_start.contiguous(), win_len.contiguous()
+    dev = items.device
+    out = torch.empty(B, W, dtype=torch.int64, device=dev)
+    alloc = max(rows, 1)            # (a batch without a target still hands the entry point real pointers)
+    flat_buf = torch.empty(alloc, dtype=torch.int32, device=dev)
+    lab_buf = torch.empty(alloc, dtype=torch.int32, device=dev)
+    cand_buf = torch.empty(alloc, N + 1, dtype=torch.int32, device=dev) if N > 0 else None
+    flat, lab, cand = flat_buf[:rows], lab_buf[:rows], None if cand_buf is None else cand_buf[:rows]
+    short = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        flat.fill_(-1)
+        lab.fill_(-1)
+        if cand is not None:
+            cand.fill_(-1)
+        return out, flat, lab, cand, short
+    with _record('next_item_batch', B * (W * 12 + 40) + rows * (8 + (N + 1) * 4 if N else 8)):
+        L.check(L.lib().b4c_next_item_batch(_p(items), _p(offsets), _p(win_seq), _p(win_start), _p(win_len), _p(row_win), _p(row_off), B, W,
+                                            mode, holdout, max_len, V, N, int(seed), excl, _p(item_cdf), _p(out), W, _p(flat_buf),
+                                            _p(lab_buf), _p(cand_buf), N + 1, rows, _p(short) if N > 0 else None, _st()), 'next_item_batch')
+    return out, flat, lab, cand, short
+
+
+def next_item_row_host(seq, seq_off, W, mode, V, a=0, L=0, holdout=1, max_len=None, num_negatives=0, seed=0, exclude='history',
+                       item_cdf=None):
+    """-> dict(inputs int64 [W], labels int32 [n], pos int32 [n], candidates int32 [n, 1 + N] or None, n_in, short) in numpy
+    (b4c_next_item_row: next_item_batch's rule for ONE row evaluated on the host, no device work).  seq: the items of sequence g,
+    seq_off = offsets[g]; (a, L): the window (TRAIN).  item_cdf: a host int64 [V] array."""
+    import ctypes
+    import numpy as np
+    from . import _lib              # (the argument L, the header's name, hides this module's alias)
+    W, mode, holdout, max_len, V, N, excl = _next_item_args('next_item_row', W, mode, holdout, max_len, V, num_negatives, seed, exclude)
+    seq = np.ascontiguousarray(seq, dtype=np.int32).reshape(-1)
+    if int(a) < 0 or int(L) < 0 or int(seq_off) < 0:
+        raise B4CError('next_item_row: window (a = %d, L = %d), seq_off = %d' % (a, L, seq_off))
+    cdf = None
+    if item_cdf is not None:
+        cdf = np.ascontiguousarray(item_cdf, dtype=np.int64).reshape(-1)
+        if cdf.shape[0] != V:
+            raise B4CError('next_item_row: item_cdf must be an int64 [V] = [%d] prefix sum of item counts' % V)
+    inputs = np.empty(W, dtype=np.int64)
+    lab, pos = np.empty(W, dtype=np.int32), np.empty(W, dtype=np.int32)
+    cand = np.empty((W, N + 1), dtype=np.int32) if N > 0 else None
+    counts = (ctypes.c_int32 * 3)()
+    _lib.check(_lib.lib().b4c_next_item_row(seq.ctypes.data if len(seq) else None, len(seq), int(seq_off), int(a), int(L), W, mode, holdout,
+                                            max_len, V, N, int(seed), excl, None if cdf is None else cdf.ctypes.data, inputs.ctypes.data,
+                                            lab.ctypes.data, pos.ctypes.data, None if cand is None else cand.ctypes.data, N + 1,
+                                            ctypes.addressof(counts)), 'next_item_row')
+    n = int(counts[1])
+    return {'inputs': inputs, 'labels': lab[:n].copy(), 'pos': pos[:n].copy(), 'candidates': None if cand is None else cand[:n].copy(),
+            'n_in': int(counts[0]), 'short': int(counts[2])}
+
+
 def adam_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul=1.0, coef=None, decay=None, blocks=None):
     """Dense Adam over a flat fp32 range (b4c_adam_step).  coef (device fp32 scalar of grad_clip_coef_): the gradient is scaled by
     grad_mul * coef[0] (b4c_adam_step_clipped).  decay: decoupled weight decay -- the elements of the 64-element blocks flagged in

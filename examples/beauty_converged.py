@@ -25,18 +25,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from examples.beauty_hitrate import add_train_loss_arguments, build_model, training_loss  # noqa: E402
+from examples.beauty_hitrate import (add_objective_argument, add_train_loss_arguments, build_model, next_item_train_batches,  # noqa: E402
+                                     training_loss)
 
 
-def evaluate(model, data, batch=1024, split='test', filtered=False):
+def evaluate(model, data, batch=1024, split='test', filtered=False, next_item=False):
     """-> (val_loss, HitRate@10 %, NDCG@10 %) on every user: mask the split's target, rank over all V items; filtered: the
     ranking leaves out the user's history (DeviceCloze.history: a row's window does not hold the older items).
-    data: input_pipeline.BeautyCloze (host batches) or cloze_batches.DeviceCloze (batches built on the device)."""
+    data: input_pipeline.BeautyCloze (host batches) or cloze_batches.DeviceCloze (batches built on the device).
+    next_item: the rows end at the item in front of the target and hold no [MASK] (DeviceCloze.next_item_eval_batches)."""
     tot = hits = ndcg = n = 0.0
     with torch.no_grad():
-        for b in (data.eval_batches(batch, split=split) if hasattr(data, 'history') else data.eval_batches(batch)):
+        for b in (data.next_item_eval_batches(batch, split=split) if next_item else
+                  data.eval_batches(batch, split=split) if hasattr(data, 'history') else data.eval_batches(batch)):
             seen = None
-            if 'items' in b:           # DeviceCloze: at most one [MASK] per row; a sequence too short for the target has none
+            if next_item:              # one compact row per sequence that has a target, at its last input
+                items, lab, flat = b['items'], b['labels'], b['flat_idx']
+                if filtered:
+                    seen = data.history(b['target_seq_idx'], split=split)
+            elif 'items' in b:           # DeviceCloze: at most one [MASK] per row; a sequence too short for the target has none
                 real = b['n_masked'] == 1
                 items, lab, flat = b['items'][real], b['labels_padded'][real].reshape(-1).to(torch.int32), None
                 if filtered:
@@ -79,7 +86,11 @@ def main():
                     help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
                          'left-to-right next-item model')
     add_train_loss_arguments(ap)
+    add_objective_argument(ap)
     a = ap.parse_args()
+    next_item = a.objective == 'next_item'
+    if next_item and not a.device_batches:
+        ap.error('--objective next_item needs --device_batches')
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
         ap.error('--max_len, --stride, --holdout and --last_item_rate need --device_batches')
@@ -98,7 +109,8 @@ def main():
     saver = ck.ModelCheckpoint(tmp, model, opt, save_best_only=True)
     plateau = ck.ReduceLROnPlateau(opt, factor=0.317, patience=10)
     stopper = ck.EarlyStopping(patience=30)
-    batches = data.train_batches(a.batch, a.seed, a.steps_per_epoch * a.max_epochs)
+    steps = a.steps_per_epoch * a.max_epochs
+    batches = next_item_train_batches(data, a, steps) if next_item else data.train_batches(a.batch, a.seed, steps)
     monitored = 'valid' if a.holdout == 2 else 'test'      # the split the callbacks see
     t0 = time.perf_counter()
     curve, stopped_by, best = [], 'max_epochs', None
@@ -107,7 +119,9 @@ def main():
         for _ in range(a.steps_per_epoch):
             b = next(batches)
             opt.zero_grad()
-            if a.device_batches:
+            if next_item:
+                loss = model.next_item_loss(b, loss=a.train_loss)
+            elif a.device_batches:
                 loss = training_loss(model, a, {'asin': b['items']}, b['labels_padded'],
                                      max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
             else:
@@ -116,7 +130,7 @@ def main():
             loss.backward()
             opt.step()
             tl = loss
-        val_loss, hr, nd = evaluate(model, data, split=monitored)
+        val_loss, hr, nd = evaluate(model, data, split=monitored, next_item=next_item)
         row = {'epoch': epoch + 1, 'train_loss_last': float(tl), 'val_loss': val_loss, 'hitrate@10': hr, 'ndcg@10': nd,
                'lr': opt.lr, 'seconds': time.perf_counter() - t0}
         curve.append(row)
@@ -139,9 +153,9 @@ def main():
     if a.device_batches:
         report['data_protocol'] = dict(protocol, monitored_split=monitored)
     if a.holdout == 2:                 # the held-out last item, read once: the weights are the last epoch's
-        loss, hr, nd = evaluate(model, data, split='test')
+        loss, hr, nd = evaluate(model, data, split='test', next_item=next_item)
         report['test'] = {'loss': loss, 'hitrate@10': hr, 'ndcg@10': nd}
-        _, fhr, fnd = evaluate(model, data, split='test', filtered=True)
+        _, fhr, fnd = evaluate(model, data, split='test', filtered=True, next_item=next_item)
         report['test'].update({'filtered_hitrate@10': fhr, 'filtered_ndcg@10': fnd})
     print(json.dumps({'what': 'Amazon Beauty, HIP path, reference loop controls (ReduceLROnPlateau 0.317/10, EarlyStopping 30, '
                               'best-val_loss checkpoint)', 'dtype': a.dtype, 'seed': a.seed, 'batch': a.batch,

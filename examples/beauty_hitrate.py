@@ -53,8 +53,21 @@ def add_train_loss_arguments(ap):
                     help='full: the softmax over all V items (cloze_loss); bce / softmax: each target against --train_negatives sampled '
                          'items that its sequence does not hold (model.candidate_loss) -- binary cross-entropy per item (SASRec) or '
                          'the list-wise softmax; the head is then the tied dot product with the item embedding.  SASRec\'s recipe: '
-                         '--device_batches --attention causal --last_item_rate 1.0 --train_loss bce --train_negatives 1')
+                         '--device_batches --attention causal --objective next_item --train_loss bce --train_negatives 1')
     ap.add_argument('--train_negatives', type=int, default=1, help='with --train_loss bce / softmax: negatives drawn per target')
+
+
+def add_objective_argument(ap):
+    ap.add_argument('--objective', default='cloze', choices=['cloze', 'next_item'],
+                    help='cloze: masked positions predict their own item; next_item (needs --device_batches, meant for --attention '
+                         'causal): every real position of an unmasked row predicts the item after it, with --train_loss bce / softmax '
+                         'against --train_negatives items the user never touched (DeviceCloze.next_item_batches, model.next_item_loss); '
+                         'evaluation rows end at the item in front of the target: no [MASK] in training or in evaluation')
+
+
+def next_item_train_batches(dev_data, a, steps):
+    """the --objective next_item training batches: negatives only where --train_loss reads them"""
+    return dev_data.next_item_batches(a.batch, a.seed, steps, num_negatives=0 if a.train_loss == 'full' else a.train_negatives)
 
 
 def training_loss(model, a, feats, labels, **kw):
@@ -112,7 +125,10 @@ def main():
                     help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
                          'left-to-right next-item model (every training row predicts the item after its prefix)')
     add_train_loss_arguments(ap)
+    add_objective_argument(ap)
     a = ap.parse_args()
+    if a.objective == 'next_item' and not a.device_batches:
+        ap.error('--objective next_item needs --device_batches')
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
         ap.error('--max_len, --stride, --holdout and --last_item_rate need --device_batches')
@@ -133,9 +149,13 @@ def main():
     if a.device_batches:
         from bert4clickpath_amd.cloze_batches import DeviceCloze
         dev_data = DeviceCloze.from_npz(a.data, **protocol)
-    for step, b in enumerate((dev_data or data).train_batches(a.batch, a.seed, a.steps)):
+    next_item = a.objective == 'next_item'
+    for step, b in enumerate(next_item_train_batches(dev_data, a, a.steps) if next_item
+                             else (dev_data or data).train_batches(a.batch, a.seed, a.steps)):
         opt.zero_grad()
-        if dev_data is not None:      # items and padded labels are on the device already; nothing is read back
+        if next_item:                 # unmasked rows, every position's target and its negatives: all built on the device
+            loss = model.next_item_loss(b, loss=a.train_loss)
+        elif dev_data is not None:      # items and padded labels are on the device already; nothing is read back
             loss = training_loss(model, a, {'asin': b['items']}, b['labels_padded'],
                                  max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
         else:
@@ -162,9 +182,14 @@ def main():
     def evaluate(split):
         """the metrics of one split ('test': the last item; 'valid', with --holdout 2: the penultimate one)"""
         hits = ndcg = n = fhits = fndcg = shits = sndcg = 0.0
-        for b in (dev_data.eval_batches(1024, a.eval_limit, split=split) if dev_data is not None else data.eval_batches(1024, a.eval_limit)):
+        for b in (dev_data.next_item_eval_batches(1024, a.eval_limit, split=split) if next_item else
+                  dev_data.eval_batches(1024, a.eval_limit, split=split) if dev_data is not None else data.eval_batches(1024, a.eval_limit)):
             seen = None
-            if dev_data is not None:      # at most one [MASK] per row; a sequence too short for the target has none
+            if next_item:                 # one compact row per sequence that has a target, at its last input; the row holds no [MASK]
+                items, labels, flat = b['items'], b['labels'], b['flat_idx']
+                if a.exclude_seen or a.negatives:
+                    seen = dev_data.history(b['target_seq_idx'], split=split)
+            elif dev_data is not None:      # at most one [MASK] per row; a sequence too short for the target has none
                 real = b['n_masked'] == 1
                 items, labels, flat = b['items'][real], b['labels_padded'][real].reshape(-1).to(torch.int32), None
                 if a.max_len is not None and (a.exclude_seen or a.negatives):      # a window does not hold the older items
@@ -175,15 +200,16 @@ def main():
                 labels, flat = torch.from_numpy(b['labels']).cuda(), torch.from_numpy(b['flat_idx']).cuda()
             if seen is None and (a.exclude_seen or a.negatives):
                 seen = cloze.seen_items(items)
-            _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat)
+            kw = {'n_real_tokens': b['n_real_tokens']} if next_item else {}
+            _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, **kw)
             hits += float(h.sum()); ndcg += float(nd.sum()); n += h.numel()
             if a.exclude_seen:          # one [MASK] (the target) per sequence: the rows are the sequences, in order
-                _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, exclude=seen)
+                _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, exclude=seen, **kw)
                 fhits += float(h.sum()); fndcg += float(nd.sum())
             if a.negatives:             # row_base: the draws of a row do not depend on the batch size
                 cand = cloze.sample_candidates(labels, a.negatives, exclude=seen, item_counts=counts, seed=a.seed,
                                                row_base=int(n) - labels.numel(), num_items=data.V)
-                _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, candidates=cand)
+                _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, candidates=cand, **kw)
                 shits += float(h.sum()); sndcg += float(nd.sum())
         res = {'hitrate@10': 100.0 * hits / n, 'ndcg@10': 100.0 * ndcg / n, 'n_eval': int(n)}
         if a.exclude_seen:
@@ -201,6 +227,7 @@ def main():
                                    % (a.negatives, a.sampler))
     if a.device_batches:
         out['data_protocol'] = protocol
+        out['objective'] = a.objective
     if a.holdout == 2:                # the split a model is selected on; the test numbers above are read once, at the end
         out['valid'] = evaluate('valid')
     print(json.dumps(out))
