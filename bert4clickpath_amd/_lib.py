@@ -12,7 +12,8 @@ EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_ex
 # add-on headers: the entry points of later features, one header each, which b4c.h includes as well.  A feature adds its header
 # here: lib() binds whatever these declare (addon_signatures()); signatures() and all_signatures() keep to the lists above.
 ADDON_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss.h'),
-                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_next_item.h'))
+                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_next_item.h'),
+                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_batch_features.h'))
 
 
 class B4CError(RuntimeError):
@@ -135,6 +136,9 @@ ATTN_CAUSAL = _C['B4C_ATTN_CAUSAL']       # flag bit of the b4c_attn_*_ex entry 
 CAND_BCE, CAND_SOFTMAX = _C['B4C_CAND_BCE'], _C['B4C_CAND_SOFTMAX']      # loss kinds of b4c_candidate_loss_fwd
 NEXT_TRAIN, NEXT_EVAL = _C['B4C_NEXT_TRAIN'], _C['B4C_NEXT_EVAL']        # modes of b4c_next_item_batch
 NEXT_EXCL_NONE, NEXT_EXCL_HISTORY = _C['B4C_NEXT_EXCL_NONE'], _C['B4C_NEXT_EXCL_HISTORY']
+FEAT_EVENT, FEAT_ITEM = _C['B4C_FEAT_EVENT'], _C['B4C_FEAT_ITEM']        # source kinds of b4c_batch_features
+FEAT_MASKED, FEAT_KEPT = _C['B4C_FEAT_MASKED'], _C['B4C_FEAT_KEPT']      # what a [MASK] position of the item row does to a feature
+FEAT_CLOZE, FEAT_NEXT_TRAIN, FEAT_NEXT_EVAL = _C['B4C_FEAT_CLOZE'], _C['B4C_FEAT_NEXT_TRAIN'], _C['B4C_FEAT_NEXT_EVAL']      # row layouts
 
 _lib = None
 

@@ -493,10 +493,12 @@ class ClickstreamTransformer(nn.Module):
         the unmasked rows predicts the item after it.  loss 'full': cloze_loss over the whole vocabulary (variant as there);
         'bce' / 'softmax': candidate_loss over the batch's own lists (built with num_negatives > 0).  A thin entry: the batch's
         flat_idx, labels, candidates and n_real_tokens go to those two methods, whose NaN conventions carry over; compact rows
-        past the batch's targets (rows=) are ignored rows."""
+        past the batch's targets (rows=) are ignored rows.  A model with side features -- every chain naming ONE input, so that each
+        is laid out [CLS] [SEP] values .. [SEP] as the batch's flat_idx expects -- takes them from batch['features'] by name
+        (DeviceCloze(features=...)); the first chain's input is the items.  Names the model does not use are ignored."""
         if loss != 'full' and loss not in ops.CAND_LOSS_KINDS:
             raise B4CError("next_item_loss: loss %r ('full', 'bce' or 'softmax')" % (loss,))
-        inputs = {self._next_item_feature(): batch['items']}
+        inputs = self._next_item_inputs(batch)
         if loss == 'full':
             return self.cloze_loss(inputs, batch['labels'], training=training, flat_idx=batch['flat_idx'], variant=variant,
                                    unit_grad=unit_grad, n_real_tokens=batch['n_real_tokens'])
@@ -505,12 +507,22 @@ class ClickstreamTransformer(nn.Module):
         return self.candidate_loss(inputs, batch['labels'], candidates=batch['candidates'], loss=loss, training=training,
                                    flat_idx=batch['flat_idx'], unit_grad=unit_grad, n_real_tokens=batch['n_real_tokens'])
 
-    def _next_item_feature(self):
-        """the one feature of a one-feature model: the layout [CLS] [SEP] items .. [SEP] the batch's flat_idx is built for"""
-        names = [n for chain in self.sequential_input_config.values() for n in chain]
-        if len(names) != 1:
-            raise B4CError('next_item_loss: a one-feature model is needed (multi-feature next-item batches are not built), got %s' % names)
-        return names[0]
+    def _next_item_inputs(self, batch):
+        """the model's inputs of a next-item batch (no device work).  Every chain names one input: the layout [CLS] [SEP] values ..
+        [SEP] the batch's flat_idx is built for; the first chain's is the items, the others come from batch['features'] by name."""
+        chains = list(self.sequential_input_config.values())
+        if not chains or any(len(chain) != 1 for chain in chains):
+            raise B4CError('next_item_loss: every chain of the model must name exactly one input (the batch\'s positions are those of '
+                           '[CLS] [SEP] items .. [SEP]), got %s' % (chains,))
+        names = [chain[0] for chain in chains]
+        inputs = {names[0]: batch['items']}
+        have = batch.get('features') or {}
+        for name in names[1:]:
+            if name not in have:
+                raise B4CError('next_item_loss: the model takes the feature %r, which the batch does not carry (it has %s); build the '
+                               'batches with DeviceCloze(features={%r: Feature(...)})' % (name, sorted(have) or 'none', name))
+            inputs[name] = have[name]
+        return inputs
 
     @torch.no_grad()
     def predict_topk(self, inputs, k, labels=None, flat_idx=None, packed=None, n_real_tokens=None, exclude=None, candidates=None):

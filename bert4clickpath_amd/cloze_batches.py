@@ -16,7 +16,12 @@ window table is built once with numpy and uploaded once; a batch names its windo
 
 The next_item_* methods build the left-to-right objective over the same windows (ops.next_item_batch, include/b4c_next_item.h): rows
 without a [MASK], every real position's target the item after it, each target's own sampled negatives; model.next_item_loss takes
-such a batch."""
+such a batch.
+
+features={name: Feature(...)} hands over side columns of the click paths -- one value per event (an action, a dwell bucket) or one
+per item (a category, a brand).  They are validated and uploaded once; every batch dict then carries 'features': {name: (B, W)
+int64 ids} built from the item row in one launch (ops.batch_features, include/b4c_batch_features.h), [MASK] where the item row has
+it unless the feature says on_mask='keep'.  inputs(batch, item_feature) is the dict the model's entry points take."""
 import collections
 
 import numpy as np
@@ -48,16 +53,33 @@ def window_table(lengths, max_len=None, stride=None, holdout=1):
     return Windows(seq.astype(np.int32), start.astype(np.int32), np.minimum(T[seq], max_len).astype(np.int32))
 
 
+class Feature:
+    """One side feature of the click paths, categorical: values are integers in [0, size).
+    per='event': one value per token, aligned with the data set's `items` array (an action type, a dwell bucket);
+    per='item': a table of V values, one per item (a category, a brand, a popularity bucket).
+    on_mask='mask' (default): a [MASK] position of the item row is [MASK] in this feature too -- what a function of the item needs,
+    or it gives the target away; 'keep': the value stays visible there (a feature of the event usually should).
+    The model's vocabulary of the feature has `size` tokens: id = value + 10, as for items."""
+
+    def __init__(self, values, size, per='event', on_mask='mask'):
+        if per not in ops.FEAT_KINDS:
+            raise ValueError("Feature: per = %r ('event' or 'item')" % (per,))
+        if on_mask not in ops.FEAT_ON_MASK:
+            raise ValueError("Feature: on_mask = %r ('mask' or 'keep')" % (on_mask,))
+        self.values, self.size, self.per, self.on_mask = np.asarray(values), int(size), per, on_mask
+
+
 class DeviceCloze:
     """items: item indices of every sequence back to back (label space: input id = 10 + index), offsets [n_seq + 1]: their
     CSR bounds -- numpy arrays or CPU tensors, as data/beauty_sequences.npz holds them.  V: vocabulary size (labels are float32,
     the reference's format, and must be exact: V <= 2^24).  device=None keeps the host side only (no batches can be built).
     max_len (None: whole sequences), stride (None: max_len; 1 .. max_len): the training windows (window_table) and the
     evaluation rows' length; holdout 1 (the last item is the test target) or 2 (the penultimate is the validation target too);
-    last_item_rate in [0, 1]: the share of training rows that mask only their last position."""
+    last_item_rate in [0, 1]: the share of training rows that mask only their last position.
+    features: {name: Feature}, at most B4C_MAX_FEATURES - 1 side features beside the items; every batch dict then has 'features'."""
 
     def __init__(self, items, offsets, V=None, max_masked=MAX_MASKED_ITEMS, masked_percentage=MASKED_PERCENTAGE, device='cuda',
-                 max_len=None, stride=None, holdout=1, last_item_rate=0.0):
+                 max_len=None, stride=None, holdout=1, last_item_rate=0.0, features=None):
         items = np.ascontiguousarray(np.asarray(items), dtype=np.int32)
         offsets = np.ascontiguousarray(np.asarray(offsets), dtype=np.int64)
         if items.ndim != 1 or offsets.ndim != 1 or len(offsets) < 1:
@@ -95,16 +117,56 @@ class DeviceCloze:
         self._win_first = np.cumsum(self._win_count) - self._win_count
         self._eval = {}                                              # split -> (Windows, device tensors)
         self._next_tr, self._next_ev = None, {}                      # the next-item rows' target counts: TRAIN table, split -> EVAL tables
+        self.features = self._check_features(features)              # name -> (int32 host values, Feature)
         self.items_dev = self.offsets_dev = self.windows_dev = None
+        self._feature_sources = []                                   # (device values, per, on_mask) in the order of self.features
         if device is not None:
             self.items_dev = torch.from_numpy(items).to(device)
             self.offsets_dev = torch.from_numpy(offsets).to(device)
             self.windows_dev = tuple(torch.from_numpy(a).to(device) for a in self.windows)
+            self._feature_sources = [(torch.from_numpy(v).to(device), f.per, f.on_mask) for v, f in self.features.values()]
 
     @classmethod
     def from_npz(cls, path, **kw):
         z = np.load(path, allow_pickle=False)
         return cls(z['items'], z['offsets'], V=int(z['vocab'].shape[0]), **kw)
+
+    # ---- side features ------------------------------------------------------------------------------------------------------------
+    def _check_features(self, features):
+        """{name: Feature} -> {name: (int32 host values, Feature)}: every check the device does not make, once, on the host"""
+        out = collections.OrderedDict()
+        if not features:
+            return out
+        if len(features) > ops.L.MAX_FEATURES - 1:
+            raise ValueError('DeviceCloze: %d features %s; at most %d beside the items (B4C_MAX_FEATURES = %d)'
+                             % (len(features), sorted(features), ops.L.MAX_FEATURES - 1, ops.L.MAX_FEATURES))
+        for name, f in features.items():
+            if not isinstance(name, str) or not isinstance(f, Feature):
+                raise ValueError('DeviceCloze: features maps names to cloze_batches.Feature objects, got %r: %s' % (name, type(f).__name__))
+            v = f.values
+            want = len(self.items) if f.per == 'event' else self.V
+            if v.ndim != 1 or len(v) != want:
+                raise ValueError("DeviceCloze: feature %r is per %r: %s values, %d %s" % (
+                    name, f.per, 'x'.join(str(d) for d in v.shape), want, 'tokens in items' if f.per == 'event' else 'items (V)'))
+            if v.dtype.kind not in 'iu':
+                raise ValueError('DeviceCloze: feature %r: values of dtype %s; integers are needed' % (name, v.dtype))
+            if f.size < 1 or (len(v) and (int(v.min()) < 0 or int(v.max()) >= f.size)):
+                raise ValueError('DeviceCloze: feature %r: values outside [0, size = %d)' % (name, f.size))
+            out[name] = (np.ascontiguousarray(v, dtype=np.int32), f)
+        return out
+
+    def _features(self, layout, table_dev, row_dev, W, items_in, holdout=1):
+        """{name: (B, W) int64 ids} of the rows whose item rows items_in were just built (one launch: ops.batch_features)"""
+        win = table_dev if table_dev is not None else (None, None, None)
+        outs = ops.batch_features(self.items_dev, self.offsets_dev, win[0], win[1], win[2], row_dev, W, layout, items_in,
+                                  self._feature_sources, holdout=holdout, max_len=self.max_len)
+        return dict(zip(self.features, outs))
+
+    @staticmethod
+    def inputs(batch, item_feature):
+        """the model's input dict of a batch: its items under the model's name for them, beside its side features -- what forward,
+        cloze_loss, candidate_loss and predict_topk take"""
+        return {item_feature: batch['items'], **batch.get('features', {})}
 
     # ---- the evaluation rows: one per sequence and split ------------------------------------------------------------------
     def _drop(self, split):
@@ -157,8 +219,11 @@ class DeviceCloze:
         self._need_device()
         items, lab, nm = ops.cloze_batch_windows(self.items_dev, self.offsets_dev, dev[0], dev[1], dev[2], row_dev, W, _MODES[mode], seed,
                                                  self.masked_percentage, self.max_masked, last_thr=self.last_thr)
-        return {'items': items, 'labels_padded': lab, 'n_masked': nm, 'seq_idx': seq_dev, 'win_idx': row_dev,
-                'n_real_tokens': int(L.sum()) + 3 * len(L)}
+        out = {'items': items, 'labels_padded': lab, 'n_masked': nm, 'seq_idx': seq_dev, 'win_idx': row_dev,
+               'n_real_tokens': int(L.sum()) + 3 * len(L)}
+        if self.features:
+            out['features'] = self._features(ops.FEAT_CLOZE, dev, row_dev, W, items)
+        return out
 
     def _need_device(self):
         if self.items_dev is None:
@@ -294,8 +359,13 @@ class DeviceCloze:
         items, flat, lab, cand, short = ops.next_item_batch(
             self.items_dev, self.offsets_dev, win[0], win[1], win[2], row_dev, row_off, W, mode, R, self.V, holdout=holdout,
             max_len=self.max_len, num_negatives=num_negatives, seed=seed, exclude=exclude, item_cdf=item_cdf, rows=rows)
-        return {'items': items, 'flat_idx': flat, 'labels': lab, 'candidates': cand, 'row_offsets': row_off, 'short': short,
-                'seq_idx': seq_dev, 'win_idx': row_dev, 'n_targets': R, 'n_real_tokens': int(n_in.sum()) + 3 * B}
+        out = {'items': items, 'flat_idx': flat, 'labels': lab, 'candidates': cand, 'row_offsets': row_off, 'short': short,
+               'seq_idx': seq_dev, 'win_idx': row_dev, 'n_targets': R, 'n_real_tokens': int(n_in.sum()) + 3 * B}
+        if self.features:
+            train = mode == ops.NEXT_TRAIN
+            out['features'] = self._features(ops.FEAT_NEXT_TRAIN if train else ops.FEAT_NEXT_EVAL, self.windows_dev if train else None,
+                                             row_dev, W, items, holdout)
+        return out
 
     def next_item_window_batch(self, win_idx, seed=0, width=None, num_negatives=0, exclude='history', item_cdf=None, rows=None):
         """One TRAIN next-item batch of the windows win_idx (host indices into self.windows, any order, repeats allowed; negative:

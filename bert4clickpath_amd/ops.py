@@ -1928,6 +1928,125 @@ def next_item_row_host(seq, seq_off, W, mode, V, a=0, L=0, holdout=1, max_len=No
             'n_in': int(counts[0]), 'short': int(counts[2])}
 
 
+# ---- side features beside the items of a device-built batch (include/b4c_batch_features.h) ----
+FEAT_EVENT, FEAT_ITEM = L.FEAT_EVENT, L.FEAT_ITEM                  # where a feature's value comes from: the token / the item
+FEAT_MASKED, FEAT_KEPT = L.FEAT_MASKED, L.FEAT_KEPT                # what a [MASK] of the item row does to the feature
+FEAT_CLOZE, FEAT_NEXT_TRAIN, FEAT_NEXT_EVAL = L.FEAT_CLOZE, L.FEAT_NEXT_TRAIN, L.FEAT_NEXT_EVAL      # the row geometry
+FEAT_KINDS = {'event': FEAT_EVENT, 'item': FEAT_ITEM}
+FEAT_ON_MASK = {'mask': FEAT_MASKED, 'keep': FEAT_KEPT}
+FEAT_LAYOUTS = (FEAT_CLOZE, FEAT_NEXT_TRAIN, FEAT_NEXT_EVAL)
+
+
+def _batch_features_args(who, W, layout, holdout, max_len, per, on_mask):
+    """the checks batch_features and batch_features_row_host share -> (W, layout, holdout, max_len, kind code, on_mask code)"""
+    W, layout, holdout = int(W), int(layout), int(holdout)
+    if layout not in FEAT_LAYOUTS:
+        raise B4CError('%s: layout %d (FEAT_CLOZE = 0, FEAT_NEXT_TRAIN = 1, FEAT_NEXT_EVAL = 2)' % (who, layout))
+    if not 1 <= W <= CLOZE_MAX_WIDTH:
+        raise B4CError('%s: W = %d (1 .. %d)' % (who, W, CLOZE_MAX_WIDTH))
+    max_len = CLOZE_MAX_WIDTH if max_len is None else int(max_len)
+    if layout != FEAT_CLOZE and (holdout < 1 or max_len < 1):
+        raise B4CError('%s: holdout / drop = %d, max_len = %d (next-item layouts: >= 1)' % (who, holdout, max_len))
+    if per not in FEAT_KINDS:
+        raise B4CError("%s: per %r ('event' or 'item')" % (who, per))
+    if on_mask not in FEAT_ON_MASK:
+        raise B4CError("%s: on_mask %r ('mask' or 'keep')" % (who, on_mask))
+    return W, layout, holdout, max_len, FEAT_KINDS[per], FEAT_ON_MASK[on_mask]
+
+
+def batch_features(items, offsets, win_seq, win_start, win_len, row_win, W, layout, items_in, sources, holdout=1, max_len=None):
+    """-> [out_f int64 [B, W] for every source] (b4c_batch_features, include/b4c_batch_features.h): the side features of the batch
+    rows whose item row items_in int64 [B, >= W] has just been built -- layout FEAT_CLOZE: by cloze_batch_windows from the windows
+    row_win of the device table (win_seq, win_start, win_len); FEAT_NEXT_TRAIN / FEAT_NEXT_EVAL: by next_item_batch in that mode
+    with the same holdout / max_len (EVAL: row_win names sequences, the table is not read).  row_win None: row b is window b.
+    sources: up to B4C_MAX_FEATURES triples (src int32 device tensor, per, on_mask) -- per 'event': src [n_items] is aligned with
+    `items`; 'item': src [V] is a table over the items; on_mask 'mask': [MASK] where the item row has it, 'keep': the value.
+    Ids are value + 10, 0 past the row.  One launch for all sources, stream-ordered, nothing is read back: neither the rows nor
+    the values are range-checked (cloze_batches.DeviceCloze checks its features on the host, once)."""
+    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
+        raise B4CError('batch_features: items must be an int32 [N] tensor of item indices')
+    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
+        raise B4CError('batch_features: offsets must be an int64 [n_seq + 1] tensor')
+    sources = list(sources)
+    if not 1 <= len(sources) <= L.MAX_FEATURES:
+        raise B4CError('batch_features: %d sources (1 .. %d = B4C_MAX_FEATURES)' % (len(sources), L.MAX_FEATURES))
+    codes, V = [], 0
+    for f, source in enumerate(sources):
+        if len(source) != 3:
+            raise B4CError('batch_features: source %d must be (src, per, on_mask)' % f)
+        src, per, on_mask = source
+        W, layout, holdout_c, max_len_c, kind, keep = _batch_features_args('batch_features', W, layout, holdout, max_len, per, on_mask)
+        if not isinstance(src, torch.Tensor) or src.dim() != 1 or src.dtype != torch.int32:
+            raise B4CError('batch_features: src of source %d must be an int32 one-dimensional tensor' % f)
+        if kind == FEAT_EVENT and src.shape[0] != items.shape[0]:
+            raise B4CError("batch_features: source %d is per 'event': %d values for %d tokens" % (f, src.shape[0], items.shape[0]))
+        if kind == FEAT_ITEM:
+            if src.shape[0] < 1 or (V and src.shape[0] != V):
+                raise B4CError("batch_features: source %d is per 'item': a table of %d entries (another has %d)" % (f, src.shape[0], V))
+            V = int(src.shape[0])
+        codes.append((kind, keep))
+    if layout != FEAT_NEXT_EVAL:
+        for name, t in (('win_seq', win_seq), ('win_start', win_start), ('win_len', win_len)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.shape[0] != win_seq.shape[0]:
+                raise B4CError('batch_features: %s must be an int32 [n_win] tensor (win_seq, win_start, win_len: one length)' % name)
+    else:
+        win_seq = win_start = win_len = None
+    if not isinstance(items_in, torch.Tensor) or items_in.dim() != 2 or items_in.dtype != torch.int64 or items_in.shape[1] < W:
+        raise B4CError('batch_features: items_in must be the int64 [B, >= W = %d] item rows' % W)
+    B = items_in.shape[0]
+    if row_win is not None and (not isinstance(row_win, torch.Tensor) or row_win.dim() != 1 or row_win.dtype != torch.int32
+                                or row_win.shape[0] != B):
+        raise B4CError('batch_features: row_win must be an int32 [B] = [%d] tensor of window (EVAL: sequence) indices, or None' % B)
+    srcs = [s[0] for s in sources]
+    _cuda(items, offsets, win_seq, win_start, win_len, row_win, items_in, *srcs)
+    items, offsets = items.contiguous(), offsets.contiguous()
+    row_win = None if row_win is None else row_win.contiguous()
+    if layout != FEAT_NEXT_EVAL:
+        win_seq, win_start, win_len = win_seq.contiguous(), win_start.contiguous(), win_len.contiguous()
+    if B and items_in.stride(1) != 1:
+        items_in = items_in.contiguous()
+    srcs = [s.contiguous() for s in srcs]
+    outs = [torch.empty(B, W, dtype=torch.int64, device=items.device) for _ in srcs]
+    if B == 0:
+        return outs
+    n = len(srcs)
+    src_arr = (ctypes.c_void_p * n)(*[s.data_ptr() for s in srcs])
+    out_arr = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    kind_arr = (ctypes.c_int * n)(*[c[0] for c in codes])
+    keep_arr = (ctypes.c_int * n)(*[c[1] for c in codes])
+    with _record('batch_features', B * (W * 8 * (n + 1) + W * 4 * (n + 1) + 40)):
+        L.check(L.lib().b4c_batch_features(_p(items), _p(offsets), _p(win_seq), _p(win_start), _p(win_len), _p(row_win), B, W, layout,
+                                           holdout_c, max_len_c, V, _p(items_in), int(items_in.stride(0)), n, src_arr, kind_arr, keep_arr,
+                                           out_arr, W, _st()), 'batch_features')
+    return outs
+
+
+def batch_features_row_host(seq, seq_off, W, layout, src, per, on_mask, items_in, a=0, L=0, holdout=1, max_len=None):
+    """-> (out int64 numpy [W], first, n) (b4c_batch_features_row: batch_features' rule for ONE row and ONE source evaluated on the
+    host, no device work).  seq: the items of sequence g, seq_off = offsets[g]; (a, L): the window (ignored for FEAT_NEXT_EVAL);
+    src: the WHOLE source array (per 'event': one value per token of the data set; 'item': the table); items_in: the item row."""
+    import numpy as np
+    from . import _lib              # (the argument L, the header's name, hides this module's alias)
+    W, layout, holdout, max_len, kind, keep = _batch_features_args('batch_features_row', W, layout, holdout, max_len, per, on_mask)
+    seq = np.ascontiguousarray(seq, dtype=np.int32).reshape(-1)
+    src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+    items_in = np.ascontiguousarray(items_in, dtype=np.int64).reshape(-1)
+    if int(a) < 0 or int(L) < 0 or int(seq_off) < 0:
+        raise B4CError('batch_features_row: window (a = %d, L = %d), seq_off = %d' % (a, L, seq_off))
+    if items_in.shape[0] < W:
+        raise B4CError('batch_features_row: items_in holds %d columns, W = %d' % (items_in.shape[0], W))
+    if kind == FEAT_EVENT and src.shape[0] < int(seq_off) + len(seq):
+        raise B4CError("batch_features_row: per 'event': %d values, the sequence ends at token %d" % (src.shape[0], int(seq_off) + len(seq)))
+    if len(src) < 1:
+        raise B4CError('batch_features_row: an empty source')
+    out = np.empty(W, dtype=np.int64)
+    geom = (ctypes.c_int32 * 2)()
+    _lib.check(_lib.lib().b4c_batch_features_row(seq.ctypes.data if len(seq) else None, len(seq), int(seq_off), int(a), int(L), W, layout,
+                                                 holdout, max_len, len(src) if kind == FEAT_ITEM else 0, src.ctypes.data, kind, keep,
+                                                 items_in.ctypes.data, out.ctypes.data, ctypes.addressof(geom)), 'batch_features_row')
+    return out, int(geom[0]), int(geom[1])
+
+
 def adam_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul=1.0, coef=None, decay=None, blocks=None):
     """Dense Adam over a flat fp32 range (b4c_adam_step).  coef (device fp32 scalar of grad_clip_coef_): the gradient is scaled by
     grad_mul * coef[0] (b4c_adam_step_clipped).  decay: decoupled weight decay -- the elements of the 64-element blocks flagged in

@@ -11,6 +11,8 @@ recipe (--clipnorm 5 --warmup 100 --weight_decay 0.01) and --negatives 100 its s
 --device_batches with --max_len / --stride / --holdout / --last_item_rate is the paper's DATA protocol: sliding training windows, the
 penultimate item held out for validation and the last for test (both reported), last-item training rows; the filtered and the
 sampled-negative figures then exclude a user's whole history (DeviceCloze.history), not only the row's window.
+--device_batches --popularity_buckets K trains a TWO-feature model: beside the item, the bucket (of K, equally filled by rank) of its
+count in the training split -- a feature of the item, so it is [MASK] wherever the item is (DeviceCloze(features=), Feature(per='item')).
 
     python examples/beauty_hitrate.py --steps 3000 --dtype f32
 Prints one JSON line.  The CPU counterpart on the oracle is oracle/train_beauty_cpu.py (same seeds, batches,
@@ -27,8 +29,21 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='bidirectional', tied_head=False):
+POPULARITY = 'popularity'         # the side feature of --popularity_buckets: its name in the batches and in the model's inputs
+
+
+def popularity_buckets(counts, K):
+    """int32 [V]: the bucket 0 .. K - 1 of every item, the items ranked by their count (most frequent first, ties by index) and
+    cut into K runs of equal length"""
+    order = np.argsort(-np.asarray(counts, dtype=np.int64), kind='stable')
+    bucket = np.empty(len(order), dtype=np.int32)
+    bucket[order] = (np.arange(len(order), dtype=np.int64) * K // max(len(order), 1)).astype(np.int32)
+    return bucket
+
+
+def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='bidirectional', tied_head=False, buckets=0):
     """paper_positions (the longest encoder input): the BERT4Rec paper's model, one constructor call.
+    buckets K > 0: a second embedded feature of K values, summed with the item's embedding (the width stays 64).
     attention='causal': left-to-right self-attention (SASRec, the paper's unidirectional arm).
     tied_head: score an item by the dot product of the encoder output with its embedding (SASRec's head), in place of the reference's
     dense stack -- the sampled-negative losses (--train_loss bce / softmax) need a projection stored per item."""
@@ -44,7 +59,11 @@ def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='b
                                       position_encoding='learned', max_positions=paper_positions, embedding_layernorm=True,
                                       embedding_scale=1.0, **kw)
     head = ClozeMaskedItemPrediction([], V) if tied_head else SoftMaxHead([1024, 512, 256, 128], V)
-    return ClickstreamTransformer({'items': ['asin']}, {'items': vocab}, {'items': 64}, head, value_to_head='[MASK]',
+    chains, vocabs, dims = {'items': ['asin']}, {'items': vocab}, {'items': 64}
+    if buckets:
+        chains['buckets'], vocabs['buckets'], dims['buckets'] = [POPULARITY], ['bucket%d' % i for i in range(buckets)], 64
+        kw['feature_combine'] = 'sum'
+    return ClickstreamTransformer(chains, vocabs, dims, head, value_to_head='[MASK]',
                                   num_encoder_layers=2, num_attention_heads=2, dropout_rate=dropout, compute_dtype=dtype, **kw)
 
 
@@ -124,9 +143,14 @@ def main():
     ap.add_argument('--attention', default='bidirectional', choices=['bidirectional', 'causal'],
                     help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
                          'left-to-right next-item model (every training row predicts the item after its prefix)')
+    ap.add_argument('--popularity_buckets', type=int, default=0,
+                    help='with --device_batches: K > 0 adds a second feature to the model and to every batch -- the bucket, of K, of '
+                         'the item\'s count in the training split (masked with the item); default 0: the one-feature model')
     add_train_loss_arguments(ap)
     add_objective_argument(ap)
     a = ap.parse_args()
+    if a.popularity_buckets and (not a.device_batches or a.paper_model or a.popularity_buckets < 0):
+        ap.error('--popularity_buckets K > 0 needs --device_batches and the reference\'s model (no --paper_model)')
     if a.objective == 'next_item' and not a.device_batches:
         ap.error('--objective next_item needs --device_batches')
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
@@ -139,7 +163,7 @@ def main():
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
     longest = (int(np.diff(data.offsets).max()) if a.max_len is None else a.max_len) + 3       # [CLS] [SEP] items [SEP]
     model = build_model(data.V, a.dropout, dtype, paper_positions=longest if a.paper_model else None, attention=a.attention,
-                        tied_head=a.train_loss != 'full').cuda()
+                        tied_head=a.train_loss != 'full', buckets=a.popularity_buckets).cuda()
     lr = WarmupLinearDecay(1e-3, a.warmup, max(a.steps, a.warmup + 1)) if a.warmup > 0 else 1e-3
     opt = optim.Adam(model.parameters(), learning_rate=lr, global_clipnorm=a.clipnorm, weight_decay=a.weight_decay,
                      exclude_from_weight_decay=optim.no_decay_params(model) if a.weight_decay is not None else ())
@@ -147,8 +171,14 @@ def main():
     t0, losses = time.perf_counter(), []
     dev_data = None
     if a.device_batches:
-        from bert4clickpath_amd.cloze_batches import DeviceCloze
-        dev_data = DeviceCloze.from_npz(a.data, **protocol)
+        from bert4clickpath_amd.cloze_batches import DeviceCloze, Feature
+        if a.popularity_buckets:        # counted on the training views of the same protocol, on the host
+            counts = DeviceCloze.from_npz(a.data, device=None, **protocol).item_counts('train')
+            protocol_kw = dict(protocol, features={POPULARITY: Feature(popularity_buckets(counts, a.popularity_buckets),
+                                                                       a.popularity_buckets, per='item', on_mask='mask')})
+        else:
+            protocol_kw = protocol
+        dev_data = DeviceCloze.from_npz(a.data, **protocol_kw)
     next_item = a.objective == 'next_item'
     for step, b in enumerate(next_item_train_batches(dev_data, a, a.steps) if next_item
                              else (dev_data or data).train_batches(a.batch, a.seed, a.steps)):
@@ -156,7 +186,7 @@ def main():
         if next_item:                 # unmasked rows, every position's target and its negatives: all built on the device
             loss = model.next_item_loss(b, loss=a.train_loss)
         elif dev_data is not None:      # items and padded labels are on the device already; nothing is read back
-            loss = training_loss(model, a, {'asin': b['items']}, b['labels_padded'],
+            loss = training_loss(model, a, dev_data.inputs(b, 'asin'), b['labels_padded'],
                                  max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
         else:
             ids = torch.from_numpy(b['ids'])
@@ -184,14 +214,15 @@ def main():
         hits = ndcg = n = fhits = fndcg = shits = sndcg = 0.0
         for b in (dev_data.next_item_eval_batches(1024, a.eval_limit, split=split) if next_item else
                   dev_data.eval_batches(1024, a.eval_limit, split=split) if dev_data is not None else data.eval_batches(1024, a.eval_limit)):
-            seen = None
+            seen, side = None, {}
             if next_item:                 # one compact row per sequence that has a target, at its last input; the row holds no [MASK]
-                items, labels, flat = b['items'], b['labels'], b['flat_idx']
+                items, labels, flat, side = b['items'], b['labels'], b['flat_idx'], b.get('features', {})
                 if a.exclude_seen or a.negatives:
                     seen = dev_data.history(b['target_seq_idx'], split=split)
             elif dev_data is not None:      # at most one [MASK] per row; a sequence too short for the target has none
                 real = b['n_masked'] == 1
                 items, labels, flat = b['items'][real], b['labels_padded'][real].reshape(-1).to(torch.int32), None
+                side = {k: v[real] for k, v in b.get('features', {}).items()}
                 if a.max_len is not None and (a.exclude_seen or a.negatives):      # a window does not hold the older items
                     seen = dev_data.history(b['seq_idx'], split=split)[real]
             else:
@@ -201,15 +232,16 @@ def main():
             if seen is None and (a.exclude_seen or a.negatives):
                 seen = cloze.seen_items(items)
             kw = {'n_real_tokens': b['n_real_tokens']} if next_item else {}
-            _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, **kw)
+            feats = {'asin': items, **side}
+            _, h, nd = model.predict_topk(feats, 10, labels, flat_idx=flat, **kw)
             hits += float(h.sum()); ndcg += float(nd.sum()); n += h.numel()
             if a.exclude_seen:          # one [MASK] (the target) per sequence: the rows are the sequences, in order
-                _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, exclude=seen, **kw)
+                _, h, nd = model.predict_topk(feats, 10, labels, flat_idx=flat, exclude=seen, **kw)
                 fhits += float(h.sum()); fndcg += float(nd.sum())
             if a.negatives:             # row_base: the draws of a row do not depend on the batch size
                 cand = cloze.sample_candidates(labels, a.negatives, exclude=seen, item_counts=counts, seed=a.seed,
                                                row_base=int(n) - labels.numel(), num_items=data.V)
-                _, h, nd = model.predict_topk({'asin': items}, 10, labels, flat_idx=flat, candidates=cand, **kw)
+                _, h, nd = model.predict_topk(feats, 10, labels, flat_idx=flat, candidates=cand, **kw)
                 shits += float(h.sum()); sndcg += float(nd.sum())
         res = {'hitrate@10': 100.0 * hits / n, 'ndcg@10': 100.0 * ndcg / n, 'n_eval': int(n)}
         if a.exclude_seen:
@@ -228,6 +260,7 @@ def main():
     if a.device_batches:
         out['data_protocol'] = protocol
         out['objective'] = a.objective
+        out['popularity_buckets'] = a.popularity_buckets
     if a.holdout == 2:                # the split a model is selected on; the test numbers above are read once, at the end
         out['valid'] = evaluate('valid')
     print(json.dumps(out))
