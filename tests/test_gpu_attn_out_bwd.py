@@ -5,6 +5,8 @@ roundings, other summation order, no float atomics (two runs: the same bits)."""
 import pytest
 import torch
 
+import fused_rows_ref as fr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -45,14 +47,7 @@ def _fused(a, rate, seed):
 
 
 def _float64(a, rate):
-    d = lambda t: t.double().cpu()
-    dout, z, gamma, o, wc = d(a['dout']), d(a['z']), d(a['gamma']), d(a['o']), d(a['wc'])
-    mean, rstd = d(a['stats'])[:, :1], d(a['stats'])[:, 1:]
-    xh = (z - mean) * rstd
-    gv = dout * gamma
-    dz = rstd * (gv - gv.mean(1, keepdim=True) - xh * (gv * xh).mean(1, keepdim=True))
-    dy = torch.where(a['keep'], dz / (1.0 - rate), torch.zeros((), dtype=torch.float64))
-    return dz, dy @ wc.T, o.T @ dy, dy.sum(0), (dout * xh).sum(0), dout.sum(0)
+    return fr.attn_out_bwd_float64(a, rate)
 
 
 NAMES = ('dz', 'd_o', 'dW', 'db', 'dgamma', 'dbeta')

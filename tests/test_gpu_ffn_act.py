@@ -7,6 +7,7 @@ ops.fused_ffn_gelu: the route it takes with the switch on and off, on against of
 import pytest
 import torch
 
+import fused_rows_ref as fr
 import paper_encoder_ref as pr
 
 pytestmark = pytest.mark.gpu
@@ -39,17 +40,7 @@ def _fwd_two_kernels(a, act, rate, seed):
 
 
 def _fwd_float64(a, act, rate, seed):
-    from bert4clickpath_amd import ops
-    d = lambda t: t.double().cpu()
-    x, wt1, wt2 = d(a['x']), d(a['wt1']), d(a['wt2'])
-    u = x @ wt1.T + d(a['b1'])
-    h = pr.act(act, u)
-    hb = h.bfloat16().double()                                  # (the second Dense reads the bf16 h, on either route)
-    y = hb @ wt2.T + d(a['b2'])
-    z = x + torch.where(_keep(x.shape[0], seed, rate), y / (1.0 - rate), torch.zeros((), dtype=torch.float64))
-    mean, var = z.mean(1, keepdim=True), z.var(1, unbiased=False, keepdim=True)
-    rstd = 1.0 / torch.sqrt(var + ops.LN_EPS)
-    return h, u, z, (z - mean) * rstd * d(a['gamma']) + d(a['beta']), torch.cat([mean, rstd], 1)
+    return fr.ffn_fwd_float64(a, rate, seed, act=act)
 
 
 @pytest.mark.parametrize('M,F,rate,act', CASES)
@@ -138,18 +129,7 @@ def _bwd_five_kernels(a, act, rate, seed):
 
 
 def _bwd_float64(a, act, rate):
-    """the block's backward in float64 from the same bf16 inputs (no intermediate rounding)"""
-    F = a['F']
-    d = lambda t: t.double().cpu()
-    dout, z, gamma, h, u, x = d(a['dout']), d(a['z']), d(a['gamma']), d(a['h'])[:, :F], d(a['u'])[:, :F], d(a['x'])
-    w1, w2 = d(a['wc1'])[:, :F], d(a['wc2'])[:F]
-    mean, rstd = d(a['stats'])[:, :1], d(a['stats'])[:, 1:]
-    xh = (z - mean) * rstd
-    gv = dout * gamma
-    dz = rstd * (gv - gv.mean(1, keepdim=True) - xh * (gv * xh).mean(1, keepdim=True))
-    dy = torch.where(a['keep'], dz / (1.0 - rate), torch.zeros((), dtype=torch.float64))
-    dh = (dy @ w2.T) * pr.act_grad(act, u)
-    return dh @ w1.T + dz, x.T @ dh, dh.sum(0), h.T @ dy, dy.sum(0), (dout * xh).sum(0), dout.sum(0)
+    return fr.ffn_bwd_float64(a, rate, act=act)
 
 
 NAMES = ('dx', 'dW1', 'db1', 'dW2', 'db2', 'dgamma', 'dbeta')

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import fused_rows_ref as fr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -66,18 +68,7 @@ def _fused(a, rate, seed):
 
 
 def _float64(a, rate):
-    """the block's backward in float64 from the same bf16 inputs (no intermediate rounding)"""
-    F = a['F']
-    d = lambda t: t.double().cpu()
-    dout, z, gamma, h, x = d(a['dout']), d(a['z']), d(a['gamma']), d(a['h'])[:, :F], d(a['x'])
-    w1, w2 = d(a['wc1'])[:, :F], d(a['wc2'])[:F]
-    mean, rstd = d(a['stats'])[:, :1], d(a['stats'])[:, 1:]
-    xh = (z - mean) * rstd
-    gv = dout * gamma
-    dz = rstd * (gv - gv.mean(1, keepdim=True) - xh * (gv * xh).mean(1, keepdim=True))
-    dy = torch.where(a['keep'], dz / (1.0 - rate), torch.zeros((), dtype=torch.float64))
-    dh = (dy @ w2.T) * (h > 0)
-    return dh @ w1.T + dz, x.T @ dh, dh.sum(0), h.T @ dy, dy.sum(0), (dout * xh).sum(0), dout.sum(0)
+    return fr.ffn_bwd_float64(a, rate)
 
 
 NAMES = ('dx', 'dW1', 'db1', 'dW2', 'db2', 'dgamma', 'dbeta')

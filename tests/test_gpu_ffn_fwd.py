@@ -3,6 +3,8 @@ b4c_gemm_nt_add_ln) on the same inputs and against a float64 restatement of tran
 import pytest
 import torch
 
+import fused_rows_ref as fr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -30,18 +32,7 @@ def _two_kernels(a, rate, seed, save=True):
 
 
 def _float64(a, rate, seed):
-    from bert4clickpath_amd import ops
-    d = lambda t: t.double().cpu()
-    x, wt1, wt2 = d(a['x']), d(a['wt1']), d(a['wt2'])
-    M = x.shape[0]
-    h = torch.relu(x @ wt1.T + d(a['b1']))
-    hb = h.bfloat16().double()                                  # (the second Dense reads the bf16 h, on either route)
-    y = hb @ wt2.T + d(a['b2'])
-    keep = torch.from_numpy(ops.keep_mask(seed, M * 128, rate)).reshape(M, 128) if rate > 0 else torch.ones(M, 128, dtype=torch.bool)
-    z = x + torch.where(keep, y / (1.0 - rate), torch.zeros((), dtype=torch.float64))
-    mean, var = z.mean(1, keepdim=True), z.var(1, unbiased=False, keepdim=True)
-    rstd = 1.0 / torch.sqrt(var + ops.LN_EPS)
-    return h, z, (z - mean) * rstd * d(a['gamma']) + d(a['beta']), torch.cat([mean, rstd], 1)
+    return fr.ffn_fwd_float64(a, rate, seed)
 
 
 @pytest.mark.parametrize('M,F,rate', [(4096, 100, 0.1), (4097, 100, 0.0), (19201, 100, 0.1), (100001, 100, 0.1), (8192, 64, 0.2),
