@@ -131,6 +131,7 @@ ACT_GELU, ACT_GELU_TANH = _C['B4C_ACT_GELU'], _C['B4C_ACT_GELU_TANH']
 CE_TF, CE_PLAIN = _C['B4C_CE_TF'], _C['B4C_CE_PLAIN']
 MAX_FEATURES, MAX_TOPK = _C['B4C_MAX_FEATURES'], _C['B4C_MAX_TOPK']
 MAX_EXCL, MAX_CAND = _C['B4C_MAX_EXCL'], _C['B4C_MAX_CAND']
+MAX_BATCH_WIDTH, MAX_CLOZE_LABELS = _C['B4C_MAX_BATCH_WIDTH'], _C['B4C_MAX_CLOZE_LABELS']      # limits of the device-built batches
 GRAD_CHUNK, GRAD_GROUP = _C['B4C_GRAD_CHUNK'], _C['B4C_GRAD_GROUP']
 ATTN_CAUSAL = _C['B4C_ATTN_CAUSAL']       # flag bit of the b4c_attn_*_ex entry points
 CAND_BCE, CAND_SOFTMAX = _C['B4C_CAND_BCE'], _C['B4C_CAND_SOFTMAX']      # loss kinds of b4c_candidate_loss_fwd

@@ -202,11 +202,12 @@ class DeviceCloze:
 
     def _width(self, L, width):
         longest = int(L.max()) if len(L) else 0
-        if width is None:
-            return max(longest, 1)
-        if int(width) < longest:
+        if width is not None and int(width) < longest:
             raise ValueError('DeviceCloze: width = %d is shorter than a row of %d items' % (width, longest))
-        return int(width)
+        W = max(longest, 1) if width is None else int(width)
+        if W > ops.CLOZE_MAX_WIDTH:
+            raise ValueError('DeviceCloze: a row of %d items; at most %d' % (W, ops.CLOZE_MAX_WIDTH))
+        return W
 
     def _batch(self, table, row_host, row_dev, seq_dev, mode, seed, width):
         """rows row_host (window indices of `table` = (Windows, device tensors); negative: an empty row) -> the batch dict"""
@@ -214,8 +215,6 @@ class DeviceCloze:
         row_host = np.asarray(row_host, dtype=np.int64)
         L = np.where(row_host >= 0, host.len[np.maximum(row_host, 0)], 0).astype(np.int64)
         W = self._width(L, width)
-        if W > ops.CLOZE_MAX_WIDTH:
-            raise ValueError('DeviceCloze: a row of %d items; at most %d' % (W, ops.CLOZE_MAX_WIDTH))
         self._need_device()
         items, lab, nm = ops.cloze_batch_windows(self.items_dev, self.offsets_dev, dev[0], dev[1], dev[2], row_dev, W, _MODES[mode], seed,
                                                  self.masked_percentage, self.max_masked, last_thr=self.last_thr)
@@ -273,28 +272,34 @@ class DeviceCloze:
         G = batch_size * world
         return order, [(s + rank * batch_size, s + (rank + 1) * batch_size) for s in range(0, self.n_windows - G + 1, G)]
 
-    def train_batches(self, batch_size, seed, steps, rank=0, world=1, width=None):
-        """`steps` TRAIN batches of batch_size windows for rank `rank` of `world`: one seeded permutation per epoch (uploaded
-        once), the mask seed of epoch e is rand64_host(seed, e)."""
+    def _epoch_steps(self, batch_size, seed, steps, rank, world, seq_of):
+        """`steps` times (order, order_dev, seq_dev, epoch seed): rank `rank`'s slice of the next global batch of the epoch's
+        seeded permutation of the windows -- uploaded once per epoch, seq_dev = seq_of(the uploaded order) sliced with it -- and
+        the epoch's seed rand64_host(seed, e)"""
         self._need_device()
         order, slices = self.rank_slices(batch_size, seed, 0, rank, world)
         if steps > 0 and not slices:
             raise ValueError('DeviceCloze: %d %s do not fill one batch of %d x %d'
                              % (self.n_windows, 'sequences' if self.max_len is None else 'windows', batch_size, world))
-        table = (self.windows, self.windows_dev)
         done = epoch = 0
         while done < steps:
             if epoch:
                 order, slices = self.rank_slices(batch_size, seed, epoch, rank, world)
             order_dev = self._upload(order)
-            seq_dev = order_dev if self.max_len is None else self.windows_dev[0][order_dev.long()]      # (a window's sequence)
-            mask_seed = int(ops.rand64_host(seed, epoch))
-            for lo, hi in slices:
-                yield self._batch(table, order[lo:hi], order_dev[lo:hi], seq_dev[lo:hi], TRAIN, mask_seed, width)
-                done += 1
-                if done >= steps:
-                    return
+            seq_dev = seq_of(order_dev)
+            epoch_seed = int(ops.rand64_host(seed, epoch))
+            for lo, hi in slices[:steps - done]:
+                yield order[lo:hi], order_dev[lo:hi], seq_dev[lo:hi], epoch_seed
+            done += len(slices)
             epoch += 1
+
+    def train_batches(self, batch_size, seed, steps, rank=0, world=1, width=None):
+        """`steps` TRAIN batches of batch_size windows for rank `rank` of `world`: one seeded permutation per epoch (uploaded
+        once), the mask seed of epoch e is rand64_host(seed, e)."""
+        table = (self.windows, self.windows_dev)
+        seq_of = lambda o: o if self.max_len is None else self.windows_dev[0][o.long()]      # (a window's sequence)
+        for order, order_dev, seq_dev, mask_seed in self._epoch_steps(batch_size, seed, steps, rank, world, seq_of):
+            yield self._batch(table, order, order_dev, seq_dev, TRAIN, mask_seed, width)
 
     def eval_batches(self, batch_size, limit=None, width=None, split='test'):
         """EVAL batches of the sequences 0 .. limit in order, the last one partial; split 'test' (the last item) or, with
@@ -345,8 +350,6 @@ class DeviceCloze:
         """rows row_host (TRAIN: window indices, EVAL: sequences; negative: an empty row) with their host-known input and target
         counts, and the device table cnt_dev of target counts that row_dev indexes -> the batch dict"""
         W = self._width(n_in, width)
-        if W > ops.CLOZE_MAX_WIDTH:
-            raise ValueError('DeviceCloze: a row of %d items; at most %d' % (W, ops.CLOZE_MAX_WIDTH))
         R = int(n_tgt.sum())
         if rows is not None and int(rows) < R:
             raise ValueError('DeviceCloze: rows = %d for a batch of %d targets' % (rows, R))
@@ -386,27 +389,12 @@ class DeviceCloze:
                           rows=None):
         """`steps` TRAIN next-item batches of batch_size windows for rank `rank` of `world`: train_batches' epoch permutation
         (uploaded once per epoch), rank slices and per-epoch seed rand64_host(seed, e); no per-batch upload."""
-        self._need_device()
-        order, slices = self.rank_slices(batch_size, seed, 0, rank, world)
-        if steps > 0 and not slices:
-            raise ValueError('DeviceCloze: %d %s do not fill one batch of %d x %d'
-                             % (self.n_windows, 'sequences' if self.max_len is None else 'windows', batch_size, world))
-        n_in_all, cnt_dev = self._next_train()
-        done = epoch = 0
-        while done < steps:
-            if epoch:
-                order, slices = self.rank_slices(batch_size, seed, epoch, rank, world)
-            order_dev = self._upload(order)
-            seq_dev = self.windows_dev[0][order_dev.long()]
-            draw_seed = int(ops.rand64_host(seed, epoch))
-            for lo, hi in slices:
-                n_in = n_in_all[order[lo:hi]]
-                yield self._next_batch(ops.NEXT_TRAIN, order[lo:hi], order_dev[lo:hi], seq_dev[lo:hi], n_in, n_in, cnt_dev, draw_seed,
-                                       width, num_negatives, exclude, item_cdf, rows, self.holdout)
-                done += 1
-                if done >= steps:
-                    return
-            epoch += 1
+        seq_of = lambda o: self.windows_dev[0][o.long()]
+        for order, order_dev, seq_dev, draw_seed in self._epoch_steps(batch_size, seed, steps, rank, world, seq_of):
+            n_in_all, cnt_dev = self._next_train()
+            n_in = n_in_all[order]
+            yield self._next_batch(ops.NEXT_TRAIN, order, order_dev, seq_dev, n_in, n_in, cnt_dev, draw_seed, width, num_negatives, exclude,
+                                   item_cdf, rows, self.holdout)
 
     def next_item_eval_batches(self, batch_size, limit=None, width=None, split='test'):
         """EVAL next-item batches of the sequences 0 .. limit in order, the last one partial: every row is the most recent

@@ -7,46 +7,11 @@
 // 16-byte boundary (an odd pitch puts every other row off it), 8 bytes per lane otherwise and for the last column of an odd W.
 // The sources' pointers and codes travel by value in the kernel arguments; the feature loop is unrolled over B4C_MAX_FEATURES so
 // that they are never indexed by a register.
-#include "common.h"
+#include "batch_rows.h"
 
-#define FEAT_MAX_W 1021      // as the batch builders: S = W + 3 <= 1024
-#define FEAT_THREADS 256
-#define FEAT_RESERVED 10     // NUM_RESERVED_TOKENS: id = value + 10
-#define FEAT_MASK_ID 1
-#define FEAT_INPUT_PAD 0
-
-// ---- the rule: shared by the kernel and the host entry ---------------------------------------------------------------------
-struct FeatRow {
-    int64_t first;   // token p of the row is s_g[first + p]
-    int n;           // tokens
-};
-__host__ __device__ __forceinline__ FeatRow feat_rule(int layout, int64_t a, int L, int64_t n_g, int holdout, int max_len, int W) {
-    FeatRow r = {0, 0};
-    if (layout == B4C_FEAT_CLOZE) {
-        r.first = a;
-        r.n = L < 0 || a < 0 ? 0 : (L > W ? W : L);
-    } else if (layout == B4C_FEAT_NEXT_TRAIN) {
-        const int64_t T = n_g - holdout > 0 ? n_g - holdout : 0;
-        const int64_t first = a > 0 ? a - 1 : 0;
-        int64_t n = a > 0 ? L : (L > 1 ? L - 1 : 0);
-        if (n > W) n = W;
-        if (n > T - first - 1) n = T - first - 1;              // a target never leaves the view
-        if (n < 0 || a < 0) n = 0;
-        r.first = first;
-        r.n = (int)n;
-    } else {
-        const int64_t t = n_g - holdout;
-        int64_t n = t < 1 ? 0 : t;
-        if (n > max_len) n = max_len;
-        if (n > W) n = W;
-        r.first = t < 1 ? 0 : t - n;
-        r.n = (int)n;
-    }
-    return r;
-}
 // one column of one feature; value: the feature's value at the token (read only where p < n)
 __host__ __device__ __forceinline__ int64_t feat_id(bool real, bool masked_here, int value) {
-    return !real ? FEAT_INPUT_PAD : (masked_here ? FEAT_MASK_ID : (int64_t)value + FEAT_RESERVED);
+    return !real ? ROW_INPUT_PAD : (masked_here ? ROW_MASK_ID : (int64_t)value + ROW_RESERVED);
 }
 
 // ---- kernel ----------------------------------------------------------------------------------------------------------------
@@ -60,32 +25,16 @@ struct alignas(16) FeatPair {
     int64_t x, y;
 };
 
-__global__ void __launch_bounds__(FEAT_THREADS) batch_features_kernel(
+__global__ void __launch_bounds__(ROW_THREADS) batch_features_kernel(
     const int32_t *__restrict__ items, const int64_t *__restrict__ offsets, const int32_t *__restrict__ win_seq,
     const int32_t *__restrict__ win_start, const int32_t *__restrict__ win_len, const int32_t *__restrict__ row_win, int W, int layout,
     int holdout, int max_len, const int64_t *__restrict__ items_in, int ld_items, int n_feat, FeatArgs fa, int ld_out) {
     const int64_t b = blockIdx.x;
     // the row's geometry
-    const int64_t w = row_win ? (int64_t)row_win[b] : b;
-    int64_t g = -1, a = 0;
-    int len = 0;
-    if (w >= 0) {
-        if (layout == B4C_FEAT_NEXT_EVAL) {
-            g = w;
-        } else {
-            g = win_seq[w];
-            a = win_start[w];
-            len = win_len[w];
-        }
-    }
-    int64_t o0 = 0, n_g = 0;
-    if (g >= 0) {
-        o0 = offsets[g];
-        n_g = offsets[g + 1] - o0;
-    }
-    const FeatRow r = feat_rule(layout, a, len, n_g, holdout, max_len, W);
-    const int n = g >= 0 ? r.n : 0;
-    const int64_t base = o0 + r.first;                         // CSR index of the row's first token
+    const RowWindow win = row_window(row_win, win_seq, win_start, win_len, offsets, b, layout != B4C_FEAT_NEXT_EVAL);
+    const BatchRow r = batch_row_rule(layout, win.a, win.len, win.n_g, holdout, max_len, W);
+    const int n = r.n;
+    const int64_t base = win.o0 + r.first;                     // CSR index of the row's first token
     bool any_masked = false, any_item = false;
 #pragma unroll
     for (int f = 0; f < B4C_MAX_FEATURES; ++f)
@@ -96,18 +45,18 @@ __global__ void __launch_bounds__(FEAT_THREADS) batch_features_kernel(
     const int64_t *in_row = items_in + b * (int64_t)ld_items;
     const bool in_vec = ((uintptr_t)in_row & 15) == 0;
     // two columns per lane
-    for (int p0 = 2 * (int)threadIdx.x; p0 < W; p0 += 2 * FEAT_THREADS) {
+    for (int p0 = 2 * (int)threadIdx.x; p0 < W; p0 += 2 * ROW_THREADS) {
         const bool two = p0 + 1 < W;
         const bool real0 = p0 < n, real1 = p0 + 1 < n;         // (n <= W: real1 implies two)
         bool m0 = false, m1 = false;
         if (any_masked) {
             if (in_vec && two) {
                 const FeatPair v = *reinterpret_cast<const FeatPair *>(in_row + p0);
-                m0 = v.x == FEAT_MASK_ID;
-                m1 = v.y == FEAT_MASK_ID;
+                m0 = v.x == ROW_MASK_ID;
+                m1 = v.y == ROW_MASK_ID;
             } else {
-                m0 = in_row[p0] == FEAT_MASK_ID;
-                m1 = two && in_row[p0 + 1] == FEAT_MASK_ID;
+                m0 = in_row[p0] == ROW_MASK_ID;
+                m1 = two && in_row[p0 + 1] == ROW_MASK_ID;
             }
         }
         int item0 = 0, item1 = 0;
@@ -143,16 +92,12 @@ extern "C" int b4c_batch_features(const int32_t *items, const int64_t *offsets, 
                                   const int32_t *win_len, const int32_t *row_win, int B, int W, int layout, int holdout, int max_len, int V,
                                   const int64_t *items_in, int ld_items, int n_feat, const int32_t *const *src, const int *kind,
                                   const int *on_mask, int64_t *const *out, int ld_out, void *stream) {
-    B4C_REQUIRE(B >= 0 && W >= 1 && W <= FEAT_MAX_W, "batch_features: B = %d, W = %d (1 .. %d)", B, W, FEAT_MAX_W);
-    B4C_REQUIRE(layout == B4C_FEAT_CLOZE || layout == B4C_FEAT_NEXT_TRAIN || layout == B4C_FEAT_NEXT_EVAL,
-                "batch_features: layout %d (0 = CLOZE, 1 = NEXT_TRAIN, 2 = NEXT_EVAL)", layout);
+    if (const int rc = rows_check_args("batch_features", B, W, ld_items, layout, holdout, 1, max_len)) return rc;
     B4C_REQUIRE(n_feat >= 1 && n_feat <= B4C_MAX_FEATURES, "batch_features: n_feat = %d (1 .. %d)", n_feat, B4C_MAX_FEATURES);
-    B4C_REQUIRE(layout == B4C_FEAT_CLOZE || holdout >= 1, "batch_features: holdout / drop = %d (next-item layouts: >= 1)", holdout);
-    B4C_REQUIRE(layout != B4C_FEAT_NEXT_EVAL || max_len >= 1, "batch_features: max_len = %d (NEXT_EVAL: >= 1)", max_len);
-    B4C_REQUIRE(ld_items >= W && ld_out >= W, "batch_features: ld_items = %d or ld_out = %d < W = %d", ld_items, ld_out, W);
+    B4C_REQUIRE(ld_out >= W, "batch_features: ld_out = %d < W = %d", ld_out, W);
     if (B == 0) return B4C_OK;
     B4C_REQUIRE(items && offsets && items_in && src && kind && on_mask && out, "batch_features: null pointer");
-    B4C_REQUIRE(layout == B4C_FEAT_NEXT_EVAL || (win_seq && win_start && win_len), "batch_features: null pointer (window table)");
+    if (const int rc = rows_check_table("batch_features", B, layout, win_seq, win_start, win_len)) return rc;
     FeatArgs fa = {};
     for (int f = 0; f < n_feat; ++f) {
         B4C_REQUIRE(src[f] && out[f], "batch_features: null pointer (src / out of feature %d)", f);
@@ -166,7 +111,7 @@ extern "C" int b4c_batch_features(const int32_t *items, const int64_t *offsets, 
         fa.kind[f] = kind[f];
         fa.on_mask[f] = on_mask[f];
     }
-    batch_features_kernel<<<(unsigned)B, FEAT_THREADS, 0, (hipStream_t)stream>>>(items, offsets, win_seq, win_start, win_len, row_win, W, layout,
+    batch_features_kernel<<<(unsigned)B, ROW_THREADS, 0, (hipStream_t)stream>>>(items, offsets, win_seq, win_start, win_len, row_win, W, layout,
                                                                                 holdout, max_len, items_in, ld_items, n_feat, fa, ld_out);
     return b4c_check_launch("batch_features");
 }
@@ -175,18 +120,14 @@ extern "C" int b4c_batch_features(const int32_t *items, const int64_t *offsets, 
 extern "C" int b4c_batch_features_row(const int32_t *seq, int n_g, int64_t seq_off, int a, int L, int W, int layout, int holdout, int max_len,
                                       int V, const int32_t *src, int kind, int on_mask, const int64_t *items_in, int64_t *out,
                                       int32_t *geom_out) {
-    B4C_REQUIRE(W >= 1 && W <= FEAT_MAX_W && n_g >= 0 && seq_off >= 0, "batch_features_row: W = %d (1 .. %d), n_g = %d, seq_off = %lld", W,
-                FEAT_MAX_W, n_g, (long long)seq_off);
-    B4C_REQUIRE(layout == B4C_FEAT_CLOZE || layout == B4C_FEAT_NEXT_TRAIN || layout == B4C_FEAT_NEXT_EVAL,
-                "batch_features_row: layout %d (0 = CLOZE, 1 = NEXT_TRAIN, 2 = NEXT_EVAL)", layout);
+    if (const int rc = rows_check_args("batch_features_row", 1, W, W, layout, holdout, 1, max_len)) return rc;
+    B4C_REQUIRE(n_g >= 0 && seq_off >= 0, "batch_features_row: n_g = %d, seq_off = %lld", n_g, (long long)seq_off);
     B4C_REQUIRE(kind == B4C_FEAT_EVENT || kind == B4C_FEAT_ITEM, "batch_features_row: kind %d (0 = EVENT, 1 = ITEM)", kind);
     B4C_REQUIRE(on_mask == B4C_FEAT_MASKED || on_mask == B4C_FEAT_KEPT, "batch_features_row: on_mask %d (0 = MASKED, 1 = KEPT)", on_mask);
-    B4C_REQUIRE(layout == B4C_FEAT_CLOZE || holdout >= 1, "batch_features_row: holdout / drop = %d (next-item layouts: >= 1)", holdout);
-    B4C_REQUIRE(layout != B4C_FEAT_NEXT_EVAL || max_len >= 1, "batch_features_row: max_len = %d (NEXT_EVAL: >= 1)", max_len);
     B4C_REQUIRE(layout == B4C_FEAT_NEXT_EVAL || (a >= 0 && L >= 0), "batch_features_row: window (a = %d, L = %d)", a, L);
     B4C_REQUIRE(kind == B4C_FEAT_EVENT || V > 0, "batch_features_row: V = %d with an ITEM table", V);
     B4C_REQUIRE((seq || n_g == 0) && src && items_in && out && geom_out, "batch_features_row: null pointer");
-    const FeatRow r = feat_rule(layout, a, L, n_g, holdout, max_len, W);
+    const BatchRow r = batch_row_rule(layout, a, L, n_g, holdout, max_len, W);
     B4C_REQUIRE(r.first + r.n <= n_g, "batch_features_row: the row [%lld, %lld) leaves its sequence of %d items", (long long)r.first,
                 (long long)r.first + r.n, n_g);
     for (int p = 0; p < r.n; ++p)
@@ -196,7 +137,7 @@ extern "C" int b4c_batch_features_row(const int32_t *seq, int n_g, int64_t seq_o
         const bool real = p < r.n;
         int value = 0;
         if (real) value = kind == B4C_FEAT_ITEM ? src[seq[r.first + p]] : src[seq_off + r.first + p];
-        out[p] = feat_id(real, on_mask == B4C_FEAT_MASKED && items_in[p] == FEAT_MASK_ID, value);
+        out[p] = feat_id(real, on_mask == B4C_FEAT_MASKED && items_in[p] == ROW_MASK_ID, value);
     }
     geom_out[0] = (int32_t)r.first;
     geom_out[1] = r.n;

@@ -12,7 +12,7 @@
             for (int p = lane; p < C; p += 64) {
                 const int c = si[p];
                 if (c < 0) continue;
-                int s = cand_hash_slot(c, hb);
+                int s = sampler_hash_slot(c, hb);
                 for (;;) {
                     const int old = atomicCAS(&hk[s], -1, c);
                     if (old == -1 || old == c) break;
@@ -26,7 +26,7 @@
                 if (c < 0 || c == y) continue;
                 const float s = sv[p];
                 if (s > sy || (s == sy && c < y)) {
-                    int t = cand_hash_slot(c, hb);
+                    int t = sampler_hash_slot(c, hb);
                     while (hk[t] != c) t = (t + 1) & hm;
                     cnt += hp[t] == p ? 1 : 0;
                 }

@@ -5,16 +5,9 @@
 // between waves, and a one-wave barrier costs nothing.  Scoring is batched GEMV work (a row's own h against its own C rows of
 // wt): FP32 FMAs on the VALU, bound by the gather of the wt rows (from L2 / the Infinity Cache for a table of a few MB).
 #include "common.h"
+#include "sampler.h"
 
 __device__ __forceinline__ bool cand_better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
-// LDS hash tables of item ids (linear probing, 2^hb slots): the rank's first-occurrence table and the sampler's accepted set
-__device__ __forceinline__ int cand_hash_slot(int item, int hb) { return (int)(((uint32_t)item * 2654435761u) >> (32 - hb)); }
-// hb of a table for n ids: at least 64 slots, at most half full
-static inline int cand_hash_bits(int n) {
-    int hb = 6;
-    while ((1 << hb) < 2 * n) ++hb;
-    return hb;
-}
 
 // ---- scoring --------------------------------------------------------------------------------------------------------------
 // A wt row of K elements is nch = K / 8 chunks of 8 (16 B bf16, 32 B fp32).  G lanes (a power of two >= nch, at most 64) share
@@ -119,46 +112,15 @@ __global__ void __launch_bounds__(64) cand_rank_rows_kernel(const T *__restrict_
 }
 
 // ---- sampler --------------------------------------------------------------------------------------------------------------
-// Step t of a row: lane l makes attempt j = 64 t + l.  The accepted set is an open-addressing hash table in LDS (hs slots: a
-// power of two >= 2 N, at least 64: at most half full), the exclusion list is binary-searched in LDS, an earlier lane of the
-// same step with the same item wins (its attempt comes first), and the accepted lanes append in lane order through a ballot
-// prefix count.
-__device__ __forceinline__ bool cand_hash_has(const int *tab, int hb, int item) {
-    for (int s = cand_hash_slot(item, hb);; s = (s + 1) & ((1 << hb) - 1)) {
-        const int v = tab[s];
-        if (v == item) return true;
-        if (v < 0) return false;
-    }
-}
-__device__ __forceinline__ void cand_hash_put(int *tab, int hb, int item) {
-    for (int s = cand_hash_slot(item, hb);; s = (s + 1) & ((1 << hb) - 1))
-        if (atomicCAS(&tab[s], -1, item) == -1) return;
-}
-__device__ __forceinline__ bool cand_sorted_has(const int *sx, int n, int item) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sx[mid] < item) lo = mid + 1; else hi = mid;
-    }
-    return lo < n && sx[lo] == item;
-}
-
+// The row's list is one wave's work (sampler.h); its exclusion list is copied to LDS for the binary search.
 __global__ void __launch_bounds__(64) cand_sample_kernel(const int32_t *__restrict__ labels, int V, int N, uint64_t seed,
                                                          int64_t row_base, const int32_t *__restrict__ excl, int ld_e, int E,
                                                          const int64_t *__restrict__ cdf, int32_t *__restrict__ cand, int ld_c,
                                                          int32_t *__restrict__ short_count, int hb) {
     extern __shared__ int cand_lds[];
-    const int hs = 1 << hb;
-    int *tab = cand_lds, *stage = cand_lds + hs, *sx = cand_lds + hs + 64;
+    int *tab = cand_lds, *sx = cand_lds + (1 << hb);
     const int lane = threadIdx.x;
     const int64_t row = blockIdx.x;
-    int32_t *out = cand + row * (int64_t)ld_c;
-    const int y = labels[row];
-    if (y < 0 || y >= V) {
-        for (int p = lane; p <= N; p += 64) out[p] = -1;
-        return;
-    }
-    for (int i = lane; i < hs; i += 64) tab[i] = -1;
     int nx = 0;                                  // canonical list: ascending ids, then -1
     for (int i = lane; i < E; i += 64) {
         const int v = excl[row * (int64_t)ld_e + i];
@@ -168,43 +130,8 @@ __global__ void __launch_bounds__(64) cand_sample_kernel(const int32_t *__restri
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) nx += __shfl_xor(nx, o);
     const uint64_t total = cdf ? (uint64_t)cdf[V - 1] : 0;
-    const uint64_t base = (uint64_t)(row_base + row) << 20;
-    __syncthreads();
-    int count = 0;
-    for (int t = 0; t < N && count < N; ++t) {
-        const uint64_t x = b4c_rand64(seed, base | (uint64_t)(t * 64 + lane));
-        int item = -1;
-        if (!cdf) item = (int)__umul64hi(x, (uint64_t)V);
-        else if ((int64_t)total > 0) {
-            const uint64_t u = __umul64hi(x, total);
-            int lo = 0, hi = V - 1;                  // min{i : cdf[i] > u}; cdf[V-1] = total > u
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if ((uint64_t)cdf[mid] > u) hi = mid; else lo = mid + 1;
-            }
-            item = lo;
-        }
-        bool ok = item >= 0 && item != y && !cand_sorted_has(sx, nx, item) && !cand_hash_has(tab, hb, item);
-        stage[lane] = ok ? item : -1;
-        __syncthreads();
-        if (ok)
-            for (int l = 0; l < lane; ++l)
-                if (stage[l] == item) { ok = false; break; }
-        const uint64_t m = __ballot(ok);
-        const int pre = __popcll(m & ((1ull << lane) - 1ull));
-        if (ok && count + pre < N) {
-            out[1 + count + pre] = item;
-            cand_hash_put(tab, hb, item);
-        }
-        count += __popcll(m);
-        __syncthreads();
-    }
-    if (count > N) count = N;
-    for (int p = 1 + count + lane; p <= N; p += 64) out[p] = -1;
-    if (lane == 0) {
-        out[0] = y;
-        if (count < N) atomicAdd(short_count, 1);
-    }
+    sampler_wave(sx, nx, tab, hb, labels[row], V, N, seed, (uint64_t)(row_base + row), cdf, total, cand + row * (int64_t)ld_c, short_count,
+                 lane);
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------------------
@@ -220,8 +147,8 @@ extern "C" int b4c_sample_candidates(const int32_t *labels, int64_t R, int V, in
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(short_count, 0, 4, st);
     if (R == 0) return B4C_OK;
-    const int hb = cand_hash_bits(N);
-    const size_t lds = (size_t)((1 << hb) + 64 + E) * 4;
+    const int hb = sampler_hash_bits(N);
+    const size_t lds = (size_t)((1 << hb) + E) * 4;
     cand_sample_kernel<<<(unsigned)R, 64, lds, st>>>(labels, V, N, seed, row_base, excl, ld_e, E, cdf, cand, ld_c, short_count, hb);
     return b4c_check_launch("sample_candidates");
 }
@@ -231,7 +158,7 @@ static void cand_score_launch(const void *h, int ld_h, const void *wt, int ld_w,
                               int64_t R, int C, int V, int K, const int32_t *labels, float *scores, int ld_s, int32_t *rank, int k,
                               int32_t *idx, hipStream_t st) {
     constexpr int U = G >= 16 ? 4 : (G >= 4 ? 2 : 1);
-    const int hb = cand_hash_bits(C);
+    const int hb = sampler_hash_bits(C);
     const size_t lds = (size_t)(C + 1) * 8 + (rank ? (size_t)8 << hb : 0);
     cand_score_kernel<T, G, NC, U><<<(unsigned)R, 64, lds, st>>>((const T *)h, ld_h, (const T *)wt, ld_w, bias, cand, ld_c, C, V, K,
                                                                  labels, scores, ld_s, rank, k, idx, hb);
@@ -286,7 +213,7 @@ extern "C" int b4c_candidate_rank_rows(const void *scores, int ld, int dtype, co
                 B4C_MAX_TOPK);
     if (R == 0) return B4C_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int hb = cand_hash_bits(C);
+    const int hb = sampler_hash_bits(C);
     const size_t lds = (size_t)C * 8 + (rank ? (size_t)8 << hb : 0);
     if (dtype == B4C_F32)
         cand_rank_rows_kernel<float><<<(unsigned)R, 64, lds, st>>>((const float *)scores, ld, cand, ld_c, C, V, labels, rank, k, idx, hb);

@@ -1663,16 +1663,60 @@ def candidate_loss_bwd(h, table, cand, g, gscale, V, dtable, dbias, row_off=0):
 
 # ---- Cloze batches (include/b4c.h "Cloze batches"): model inputs and padded labels from a CSR data set on the device ----
 CLOZE_TRAIN, CLOZE_EVAL = 0, 1
-CLOZE_MAX_WIDTH, CLOZE_MAX_LABELS = 1021, 64
+CLOZE_MAX_WIDTH, CLOZE_MAX_LABELS = L.MAX_BATCH_WIDTH, L.MAX_CLOZE_LABELS
+
+
+# what the batch builders (Cloze, next-item, side features) check alike; `who` names the caller in the message
+def _csr_pair(who, items, offsets):
+    """the data set -> (items, offsets), contiguous"""
+    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
+        raise B4CError('%s: items must be an int32 [N] tensor of item indices' % who)
+    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
+        raise B4CError('%s: offsets must be an int64 [n_seq + 1] tensor' % who)
+    return items.contiguous(), offsets.contiguous()
+
+
+def _window_table(who, win_seq, win_start, win_len, read=True):
+    """the device window table -> its three tensors, contiguous; (None, None, None) for a layout that does not read it"""
+    if not read:
+        return None, None, None
+    for name, t in (('win_seq', win_seq), ('win_start', win_start), ('win_len', win_len)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.shape[0] != win_seq.shape[0]:
+            raise B4CError('%s: %s must be an int32 [n_win] tensor (win_seq, win_start, win_len: one length)' % (who, name))
+    return win_seq.contiguous(), win_start.contiguous(), win_len.contiguous()
+
+
+def _row_index(who, name, t, what, B=None, optional=False):
+    """seq_idx / row_win: what every batch row names -> contiguous; None where optional (row b names b)"""
+    if t is None and optional:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or (B is not None and t.shape[0] != B):
+        raise B4CError('%s: %s must be an int32 [B]%s tensor of %s%s' % (who, name, '' if B is None else ' = [%d]' % B, what,
+                                                                     ', or None' if optional else ''))
+    return t.contiguous()
+
+
+def _batch_width(who, W):
+    if not 1 <= int(W) <= CLOZE_MAX_WIDTH:
+        raise B4CError('%s: W = %d (1 .. %d)' % (who, W, CLOZE_MAX_WIDTH))
+    return int(W)
+
+
+def _holdout_args(who, holdout, max_len, least, max_len_read):
+    """-> (holdout, max_len): holdout / drop >= least (None: the layout does not read it), max_len (None: the width limit) >= 1
+    where the layout reads it"""
+    holdout, max_len = int(holdout), CLOZE_MAX_WIDTH if max_len is None else int(max_len)
+    if (least is not None and holdout < least) or (max_len_read and max_len < 1):
+        raise B4CError('%s: holdout / drop = %d (>= %s), max_len = %d (>= 1)' % (who, holdout, least, max_len))
+    return holdout, max_len
 
 
 def _cloze_rule_args(who, offsets, W, mode, seed, masked_percentage, max_masked, M):
     """the checks cloze_batch and cloze_batch_windows share -> (W, mode, max_masked, M)"""
-    W, mode, max_masked = int(W), int(mode), int(max_masked)
+    mode, max_masked = int(mode), int(max_masked)
     if mode not in (CLOZE_TRAIN, CLOZE_EVAL):
         raise B4CError('%s: mode %d (CLOZE_TRAIN = 0, CLOZE_EVAL = 1)' % (who, mode))
-    if not 1 <= W <= CLOZE_MAX_WIDTH:
-        raise B4CError('%s: W = %d (1 .. %d)' % (who, W, CLOZE_MAX_WIDTH))
+    W = _batch_width(who, W)
     M = (max_masked if mode == CLOZE_TRAIN else 1) if M is None else int(M)
     if not mode <= M <= CLOZE_MAX_LABELS or (mode == CLOZE_TRAIN and not 0 <= max_masked <= M):
         raise B4CError('%s: max_masked = %d, M = %d (0 <= max_masked <= M <= %d; EVAL: M >= 1)' % (who, max_masked, M, CLOZE_MAX_LABELS))
@@ -1691,16 +1735,11 @@ def cloze_batch(items, offsets, seq_idx, W, mode, seed, masked_percentage=0.4, m
     keys b4c_rand64(seed, (g << 10) | p) (cloze_choose_host regenerates them); CLOZE_EVAL: the last position masked.
     M: label columns, default max_masked (TRAIN) / 1 (EVAL).  Stream-ordered, nothing is read back: seq_idx is NOT checked
     against n_seq here, and a sequence longer than W is cut at W -- cloze_batches.DeviceCloze checks both on its host copies."""
-    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
-        raise B4CError('cloze_batch: items must be an int32 [N] tensor of item indices')
-    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
-        raise B4CError('cloze_batch: offsets must be an int64 [n_seq + 1] tensor')
-    if not isinstance(seq_idx, torch.Tensor) or seq_idx.dim() != 1 or seq_idx.dtype != torch.int32:
-        raise B4CError('cloze_batch: seq_idx must be an int32 [B] tensor of sequence indices')
+    items, offsets = _csr_pair('cloze_batch', items, offsets)
+    seq_idx = _row_index('cloze_batch', 'seq_idx', seq_idx, 'sequence indices')
     B = seq_idx.shape[0]
     W, mode, max_masked, M = _cloze_rule_args('cloze_batch', offsets, W, mode, seed, masked_percentage, max_masked, M)
     _cuda(items, offsets, seq_idx)
-    items, offsets, seq_idx = items.contiguous(), offsets.contiguous(), seq_idx.contiguous()
     dev = items.device
     out = torch.empty(B, W, dtype=torch.int64, device=dev)
     lab = torch.empty(B, M, dtype=torch.float32, device=dev)
@@ -1742,15 +1781,9 @@ def cloze_batch_windows(items, offsets, win_seq, win_start, win_len, row_win, W,
     (last_thr = cloze_last_thr(rate), 0 .. 2^24; cloze_choose_window_host regenerates both); CLOZE_EVAL: the last position.
     A whole-sequence window (g, 0, n_g - 1) with last_thr = 0 is cloze_batch's TRAIN row.  Stream-ordered, nothing is read back:
     row_win is NOT checked against n_win nor a window against its sequence, and win_len is cut at W."""
-    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
-        raise B4CError('cloze_batch_windows: items must be an int32 [N] tensor of item indices')
-    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
-        raise B4CError('cloze_batch_windows: offsets must be an int64 [n_seq + 1] tensor')
-    for name, t in (('win_seq', win_seq), ('win_start', win_start), ('win_len', win_len)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.shape[0] != win_seq.shape[0]:
-            raise B4CError('cloze_batch_windows: %s must be an int32 [n_win] tensor (win_seq, win_start, win_len: one length)' % name)
-    if row_win is not None and (not isinstance(row_win, torch.Tensor) or row_win.dim() != 1 or row_win.dtype != torch.int32):
-        raise B4CError('cloze_batch_windows: row_win must be an int32 [B] tensor of window indices, or None')
+    items, offsets = _csr_pair('cloze_batch_windows', items, offsets)
+    win_seq, win_start, win_len = _window_table('cloze_batch_windows', win_seq, win_start, win_len)
+    row_win = _row_index('cloze_batch_windows', 'row_win', row_win, 'window indices', optional=True)
     B = win_seq.shape[0] if row_win is None else row_win.shape[0]
     W, mode, max_masked, M = _cloze_rule_args('cloze_batch_windows', offsets, W, mode, seed, masked_percentage, max_masked, M)
     last_thr = int(last_thr)
@@ -1759,8 +1792,6 @@ def cloze_batch_windows(items, offsets, win_seq, win_start, win_len, row_win, W,
     if mode == CLOZE_EVAL:
         last_thr = 0
     _cuda(items, offsets, win_seq, win_start, win_len, row_win)
-    items, offsets, win_seq, win_start, win_len = (t.contiguous() for t in (items, offsets, win_seq, win_start, win_len))
-    row_win = None if row_win is None else row_win.contiguous()
     dev = items.device
     out = torch.empty(B, W, dtype=torch.int64, device=dev)
     lab = torch.empty(B, M, dtype=torch.float32, device=dev)
@@ -1794,17 +1825,12 @@ def cloze_history(items, offsets, seq_idx, E, drop=1):
     item n_g - drop --, the most recent E when there are more, then -1.  A negative seq_idx: all -1.  The `exclude=` of
     predict_topk, of the ranking metrics and of cloze.sample_candidates takes it (through ops.exclusions).  Stream-ordered,
     nothing is read back: seq_idx is NOT checked against n_seq."""
-    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
-        raise B4CError('cloze_history: items must be an int32 [N] tensor of item indices')
-    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
-        raise B4CError('cloze_history: offsets must be an int64 [n_seq + 1] tensor')
-    if not isinstance(seq_idx, torch.Tensor) or seq_idx.dim() != 1 or seq_idx.dtype != torch.int32:
-        raise B4CError('cloze_history: seq_idx must be an int32 [B] tensor of sequence indices')
+    items, offsets = _csr_pair('cloze_history', items, offsets)
+    seq_idx = _row_index('cloze_history', 'seq_idx', seq_idx, 'sequence indices')
     E, drop = int(E), int(drop)
     if not 1 <= E <= L.MAX_EXCL or drop < 1:
         raise B4CError('cloze_history: E = %d (1 .. %d = B4C_MAX_EXCL), drop = %d (>= 1)' % (E, L.MAX_EXCL, drop))
     _cuda(items, offsets, seq_idx)
-    items, offsets, seq_idx = items.contiguous(), offsets.contiguous(), seq_idx.contiguous()
     B = seq_idx.shape[0]
     out = torch.empty(B, E, dtype=torch.int32, device=items.device)
     if B:
@@ -1819,14 +1845,11 @@ NEXT_EXCLUDE = {None: L.NEXT_EXCL_NONE, 'history': L.NEXT_EXCL_HISTORY}
 
 def _next_item_args(who, W, mode, holdout, max_len, V, num_negatives, seed, exclude):
     """the checks next_item_batch and next_item_row_host share -> (W, mode, holdout, max_len, V, N, excl code)"""
-    W, mode, holdout, V, N = int(W), int(mode), int(holdout), int(V), int(num_negatives)
+    mode, V, N = int(mode), int(V), int(num_negatives)
     if mode not in (NEXT_TRAIN, NEXT_EVAL):
         raise B4CError('%s: mode %d (NEXT_TRAIN = 0, NEXT_EVAL = 1)' % (who, mode))
-    if not 1 <= W <= CLOZE_MAX_WIDTH:
-        raise B4CError('%s: W = %d (1 .. %d)' % (who, W, CLOZE_MAX_WIDTH))
-    max_len = CLOZE_MAX_WIDTH if max_len is None else int(max_len)
-    if holdout < 0 or (mode == NEXT_EVAL and (holdout < 1 or max_len < 1)):
-        raise B4CError('%s: holdout / drop = %d (TRAIN: >= 0, EVAL: >= 1), max_len = %d (>= 1)' % (who, holdout, max_len))
+    W = _batch_width(who, W)
+    holdout, max_len = _holdout_args(who, holdout, max_len, 1 if mode == NEXT_EVAL else 0, mode == NEXT_EVAL)
     if V <= 0 or not 0 <= N < L.MAX_CAND:
         raise B4CError('%s: V = %d, num_negatives = %d (0 .. %d)' % (who, V, N, L.MAX_CAND - 1))
     if exclude not in NEXT_EXCLUDE:
@@ -1847,19 +1870,10 @@ def next_item_batch(items, offsets, win_seq, win_start, win_len, row_win, row_of
     num_negatives N > 0: cand[r] = [label, N negatives], each list what ops.sample_candidates draws for that one target with
     row_base = the target token's CSR index, excluding ('history') the sequence's items in front of the held-out ones.
     Stream-ordered: row_win and the table are NOT checked against the data set."""
-    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
-        raise B4CError('next_item_batch: items must be an int32 [N] tensor of item indices')
-    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
-        raise B4CError('next_item_batch: offsets must be an int64 [n_seq + 1] tensor')
+    items, offsets = _csr_pair('next_item_batch', items, offsets)
     W, mode, holdout, max_len, V, N, excl = _next_item_args('next_item_batch', W, mode, holdout, max_len, V, num_negatives, seed, exclude)
-    if mode == NEXT_TRAIN:
-        for name, t in (('win_seq', win_seq), ('win_start', win_start), ('win_len', win_len)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.shape[0] != win_seq.shape[0]:
-                raise B4CError('next_item_batch: %s must be an int32 [n_win] tensor (win_seq, win_start, win_len: one length)' % name)
-    else:
-        win_seq = win_start = win_len = None
-    if not isinstance(row_win, torch.Tensor) or row_win.dim() != 1 or row_win.dtype != torch.int32:
-        raise B4CError('next_item_batch: row_win must be an int32 [B] tensor of window (TRAIN) or sequence (EVAL) indices')
+    win_seq, win_start, win_len = _window_table('next_item_batch', win_seq, win_start, win_len, read=mode == NEXT_TRAIN)
+    row_win = _row_index('next_item_batch', 'row_win', row_win, 'window (TRAIN) or sequence (EVAL) indices')
     B = row_win.shape[0]
     if not isinstance(row_off, torch.Tensor) or row_off.dtype != torch.int32 or row_off.dim() != 1 or row_off.shape[0] != B + 1:
         raise B4CError('next_item_batch: row_off must be an int32 [B + 1] = [%d] tensor' % (B + 1))
@@ -1874,9 +1888,7 @@ def next_item_batch(items, offsets, win_seq, win_start, win_len, row_win, row_of
             raise B4CError('next_item_batch: item_cdf must be an int64 [V] = [%d] prefix sum of item counts' % V)
         item_cdf = item_cdf.contiguous()
     _cuda(items, offsets, win_seq, win_start, win_len, row_win, row_off, item_cdf)
-    items, offsets, row_win, row_off = items.contiguous(), offsets.contiguous(), row_win.contiguous(), row_off.contiguous()
-    if mode == NEXT_TRAIN:
-        win_seq, win_start, win_len = win_seq.contiguous(), win_start.contiguous(), win_len.contiguous()
+    row_off = row_off.contiguous()
     dev = items.device
     out = torch.empty(B, W, dtype=torch.int64, device=dev)
     alloc = max(rows, 1)            # (a batch without a target still hands the entry point real pointers)
@@ -1939,14 +1951,11 @@ FEAT_LAYOUTS = (FEAT_CLOZE, FEAT_NEXT_TRAIN, FEAT_NEXT_EVAL)
 
 def _batch_features_args(who, W, layout, holdout, max_len, per, on_mask):
     """the checks batch_features and batch_features_row_host share -> (W, layout, holdout, max_len, kind code, on_mask code)"""
-    W, layout, holdout = int(W), int(layout), int(holdout)
+    layout = int(layout)
     if layout not in FEAT_LAYOUTS:
         raise B4CError('%s: layout %d (FEAT_CLOZE = 0, FEAT_NEXT_TRAIN = 1, FEAT_NEXT_EVAL = 2)' % (who, layout))
-    if not 1 <= W <= CLOZE_MAX_WIDTH:
-        raise B4CError('%s: W = %d (1 .. %d)' % (who, W, CLOZE_MAX_WIDTH))
-    max_len = CLOZE_MAX_WIDTH if max_len is None else int(max_len)
-    if layout != FEAT_CLOZE and (holdout < 1 or max_len < 1):
-        raise B4CError('%s: holdout / drop = %d, max_len = %d (next-item layouts: >= 1)' % (who, holdout, max_len))
+    W = _batch_width(who, W)
+    holdout, max_len = _holdout_args(who, holdout, max_len, None if layout == FEAT_CLOZE else 1, layout != FEAT_CLOZE)
     if per not in FEAT_KINDS:
         raise B4CError("%s: per %r ('event' or 'item')" % (who, per))
     if on_mask not in FEAT_ON_MASK:
@@ -1963,10 +1972,7 @@ def batch_features(items, offsets, win_seq, win_start, win_len, row_win, W, layo
     `items`; 'item': src [V] is a table over the items; on_mask 'mask': [MASK] where the item row has it, 'keep': the value.
     Ids are value + 10, 0 past the row.  One launch for all sources, stream-ordered, nothing is read back: neither the rows nor
     the values are range-checked (cloze_batches.DeviceCloze checks its features on the host, once)."""
-    if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int32:
-        raise B4CError('batch_features: items must be an int32 [N] tensor of item indices')
-    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape[0] < 1:
-        raise B4CError('batch_features: offsets must be an int64 [n_seq + 1] tensor')
+    items, offsets = _csr_pair('batch_features', items, offsets)
     sources = list(sources)
     if not 1 <= len(sources) <= L.MAX_FEATURES:
         raise B4CError('batch_features: %d sources (1 .. %d = B4C_MAX_FEATURES)' % (len(sources), L.MAX_FEATURES))
@@ -1985,24 +1991,13 @@ def batch_features(items, offsets, win_seq, win_start, win_len, row_win, W, layo
                 raise B4CError("batch_features: source %d is per 'item': a table of %d entries (another has %d)" % (f, src.shape[0], V))
             V = int(src.shape[0])
         codes.append((kind, keep))
-    if layout != FEAT_NEXT_EVAL:
-        for name, t in (('win_seq', win_seq), ('win_start', win_start), ('win_len', win_len)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.shape[0] != win_seq.shape[0]:
-                raise B4CError('batch_features: %s must be an int32 [n_win] tensor (win_seq, win_start, win_len: one length)' % name)
-    else:
-        win_seq = win_start = win_len = None
+    win_seq, win_start, win_len = _window_table('batch_features', win_seq, win_start, win_len, read=layout != FEAT_NEXT_EVAL)
     if not isinstance(items_in, torch.Tensor) or items_in.dim() != 2 or items_in.dtype != torch.int64 or items_in.shape[1] < W:
         raise B4CError('batch_features: items_in must be the int64 [B, >= W = %d] item rows' % W)
     B = items_in.shape[0]
-    if row_win is not None and (not isinstance(row_win, torch.Tensor) or row_win.dim() != 1 or row_win.dtype != torch.int32
-                                or row_win.shape[0] != B):
-        raise B4CError('batch_features: row_win must be an int32 [B] = [%d] tensor of window (EVAL: sequence) indices, or None' % B)
+    row_win = _row_index('batch_features', 'row_win', row_win, 'window (EVAL: sequence) indices', B=B, optional=True)
     srcs = [s[0] for s in sources]
     _cuda(items, offsets, win_seq, win_start, win_len, row_win, items_in, *srcs)
-    items, offsets = items.contiguous(), offsets.contiguous()
-    row_win = None if row_win is None else row_win.contiguous()
-    if layout != FEAT_NEXT_EVAL:
-        win_seq, win_start, win_len = win_seq.contiguous(), win_start.contiguous(), win_len.contiguous()
     if B and items_in.stride(1) != 1:
         items_in = items_in.contiguous()
     srcs = [s.contiguous() for s in srcs]

@@ -550,6 +550,8 @@ int b4c_candidate_rank_rows(const void *scores, int ld, int dtype, const int32_t
  *   outside the row.  B = 0 is a no-op.
  * b4c_cloze_choose is the TRAIN rule on the HOST (no device work): pos[0 .. n) = the n masked positions of [0, L) for
  *   sequence g, ascending; 0 <= n <= L <= 1021. */
+#define B4C_MAX_BATCH_WIDTH 1021   /* widest row W of every device-built batch: S = W + 3 <= 1024, p < 1024 in the counter */
+#define B4C_MAX_CLOZE_LABELS 64    /* most label columns M of a Cloze batch */
 int b4c_cloze_batch(const int32_t *items, const int64_t *offsets, const int32_t *seq_idx, int B, int W, int mode,
                     float masked_percentage, int max_masked, uint64_t seed, int64_t *items_out, int ld_items,
                     float *labels_out, int ld_lab, int M, int32_t *n_masked_out, void *stream);

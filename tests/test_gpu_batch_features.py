@@ -171,6 +171,25 @@ def test_row_win_null_names_the_windows_in_order(ops, data, case):
     assert all(np.array_equal(g, w) for g, w in zip(got, want)) and (want[1] != 0).sum() > 20
 
 
+def test_a_feature_that_copies_the_items_is_the_item_row_of_every_builder(ops, data):
+    """The builders and the feature kernel share one row geometry (csrc/batch_rows.h): with the single source (items, 'event',
+    'mask') ops.batch_features returns exactly the item row the layout's builder has just written -- 0 in the pads, 1 at a [MASK],
+    item + 10 elsewhere -- for Cloze TRAIN windows, next-item TRAIN windows and next-item EVAL sequences.  The case rows of
+    tests/test_gpu_next_item.py (_case_rows is the same list here), W = 8: wider than any window, B <= 16."""
+    W, it, off = 8, data['items_d'], data['offsets_d']
+    table = _table(data['offsets'], 1)
+    tab = [_dev(t, np.int32) for t in table]
+    for case in ('cloze_train', 'next_train', 'next_eval'):
+        rows = _case_rows(table) if case != 'next_eval' else np.array(list(range(len(data['offsets']) - 1)) + [-1], np.int64)
+        assert len(rows) <= 16
+        layout, ftable, items_in, n_masked = _item_rows(ops, data, case, rows, table, W, 1)
+        win = tab if ftable is not None else [None] * 3
+        out, = ops.batch_features(it, off, win[0], win[1], win[2], _dev(rows, np.int32), W, layout, items_in, [(it, 'event', 'mask')],
+                                  holdout=1, max_len=MAX_LEN)
+        assert torch.equal(out, items_in), case
+        assert int((items_in >= 10).sum()) > 10 and (n_masked > 0) == (case == 'cloze_train') and int((items_in == 1).sum()) == n_masked
+
+
 # ---- DeviceCloze -----------------------------------------------------------------------------------------------------------------
 FEATURES = [('action', 'event', 'keep'), ('category', 'item', 'mask'), ('dwell', 'event', 'mask')]
 
