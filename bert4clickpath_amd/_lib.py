@@ -13,7 +13,8 @@ EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_ex
 # here: lib() binds whatever these declare (addon_signatures()); signatures() and all_signatures() keep to the lists above.
 ADDON_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss.h'),
                       os.path.join(os.path.dirname(_HERE), 'include', 'b4c_next_item.h'),
-                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_batch_features.h'))
+                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_batch_features.h'),
+                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss_ex.h'))
 
 
 class B4CError(RuntimeError):
@@ -135,6 +136,8 @@ MAX_BATCH_WIDTH, MAX_CLOZE_LABELS = _C['B4C_MAX_BATCH_WIDTH'], _C['B4C_MAX_CLOZE
 GRAD_CHUNK, GRAD_GROUP = _C['B4C_GRAD_CHUNK'], _C['B4C_GRAD_GROUP']
 ATTN_CAUSAL = _C['B4C_ATTN_CAUSAL']       # flag bit of the b4c_attn_*_ex entry points
 CAND_BCE, CAND_SOFTMAX = _C['B4C_CAND_BCE'], _C['B4C_CAND_SOFTMAX']      # loss kinds of b4c_candidate_loss_fwd
+CANDX_BCE, CANDX_SOFTMAX, CANDX_BPR = _C['B4C_CANDX_BCE'], _C['B4C_CANDX_SOFTMAX'], _C['B4C_CANDX_BPR']      # of b4c_candidate_loss_fwd_ex
+CANDX_KINDS, CANDX_CORR_TARGET = _C['B4C_CANDX_KINDS'], _C['B4C_CANDX_CORR_TARGET']      # (CORR_TARGET: its flags bit)
 NEXT_TRAIN, NEXT_EVAL = _C['B4C_NEXT_TRAIN'], _C['B4C_NEXT_EVAL']        # modes of b4c_next_item_batch
 NEXT_EXCL_NONE, NEXT_EXCL_HISTORY = _C['B4C_NEXT_EXCL_NONE'], _C['B4C_NEXT_EXCL_HISTORY']
 FEAT_EVENT, FEAT_ITEM = _C['B4C_FEAT_EVENT'], _C['B4C_FEAT_ITEM']        # source kinds of b4c_batch_features

@@ -446,12 +446,42 @@ class ClickstreamTransformer(nn.Module):
             loss = loss + torch.where(poison[0] < 0, float('nan'), 0.0).to(loss.dtype)
         return loss
 
+    CANDIDATE_LOSSES = ('bce', 'softmax', 'bpr', 'gbce')
+
+    @staticmethod
+    def gbce_beta(num_negatives, num_items, t):
+        """gSASRec's exponent of the positive probability (Petrov & Macdonald 2023), here the weight of the target's BCE term:
+        beta = alpha * (t * (1 - 1 / alpha) + 1 / alpha) with the sampling rate alpha = N / (V - 1); t = 0: 1 (BCE), t = 1: alpha."""
+        alpha = float(num_negatives) / float(num_items - 1)
+        return alpha * (float(t) * (1.0 - 1.0 / alpha) + 1.0 / alpha)
+
+    def _candidate_loss_options(self, who, loss, gbce_t, logq, correct_target, extra=()):
+        """the host checks of the loss keywords candidate_loss and next_item_loss share (before any device work)"""
+        names = tuple(extra) + self.CANDIDATE_LOSSES
+        if loss not in names:
+            raise B4CError('%s: loss %r (%s or %r)' % (who, loss, ', '.join(repr(n) for n in names[:-1]), names[-1]))
+        try:
+            ok = 0.0 <= float(gbce_t) <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise B4CError('%s: gbce_t = %r (the calibration parameter t of gBCE, in [0, 1])' % (who, gbce_t))
+        if logq is None and correct_target:
+            raise B4CError('%s: correct_target=True needs logq (there is no correction to apply to the target)' % who)
+        if logq is not None and (not isinstance(logq, torch.Tensor) or logq.dtype != torch.float32 or logq.dim() != 1):
+            raise B4CError('%s: logq must be a device fp32 [V] tensor (cloze.log_expected_count)' % who)
+
     def candidate_loss(self, inputs, labels, candidates=None, num_negatives=None, loss='bce', exclude=None, item_cdf=None, seed=None,
                        row_base=0, training=True, flat_idx=None, unit_grad=False, max_masked_per_row=None, packed=None,
-                       n_real_tokens=None):
+                       n_real_tokens=None, gbce_t=0.75, logq=None, correct_target=False):
         """Sampled-negative training loss: each masked row against its own list of items, the label first -- loss='bce' (SASRec:
-        softplus(-s_label) + the sum of softplus(s_negative)) or 'softmax' (the list-wise softmax over the label and the negatives,
-        the loss of the sampled-negative HitRate / NDCG protocol) -- mean over the rows with a valid label.  The head's projection
+        softplus(-s_label) + the sum of softplus(s_negative)), 'softmax' (the list-wise softmax over the label and the negatives,
+        the loss of the sampled-negative HitRate / NDCG protocol), 'bpr' (the sum over the negatives of softplus(s_negative -
+        s_label)) or 'gbce' (gSASRec: 'bce' with the label's term times beta = gbce_beta(N, V, gbce_t), N the negatives per list,
+        which undoes the over-confidence of BCE with few negatives; gbce_t in [0, 1], 0 is 'bce') -- mean over the rows with a valid
+        label.  logq (device fp32 [V], cloze.log_expected_count of the counts the lists are drawn by): the sampled-softmax logQ
+        correction -- every negative is scored s - logq[item]; the label too only with correct_target=True (it stands in its list
+        with probability 1).  The head's projection
         is read and receives gradient at the listed rows only (head.candidate_loss; ClozeMaskedItemPrediction, SampledSoftmaxHead).
         inputs, labels, training, flat_idx, max_masked_per_row, packed, n_real_tokens: as in cloze_loss, the sync-free form and the
         NaN loss on a contradicted token count included.  Exactly one of
@@ -463,8 +493,7 @@ class ClickstreamTransformer(nn.Module):
         exclude: (R, E) or (B, E) as in predict_topk -- e.g. the user's own items."""
         if (candidates is None) == (num_negatives is None):
             raise B4CError('candidate_loss: give exactly one of candidates and num_negatives')
-        if loss not in ops.CAND_LOSS_KINDS:
-            raise B4CError("candidate_loss: loss %r ('bce' or 'softmax')" % (loss,))
+        self._candidate_loss_options('candidate_loss', loss, gbce_t, logq, correct_target)
         if not hasattr(self.head, 'candidate_loss'):
             raise B4CError('candidate_loss: the head %s has no vocabulary projection to score items with' % type(self.head).__name__)
         rows, lab, poison = self._loss_rows(inputs, labels, training, flat_idx, max_masked_per_row, packed, n_real_tokens)
@@ -481,23 +510,36 @@ class ClickstreamTransformer(nn.Module):
             ex = self._row_exclusions(exclude, rows.shape[0], rows.device, lab) if exclude is not None else None
             from .transformer import dropout_seeds
             cand, _ = ops.sample_candidates(lab, V, num_negatives, dropout_seeds.next() if seed is None else seed, row_base, ex, item_cdf)
-        out = self.head.candidate_loss(rows, cand, loss, unit_grad)
+        kind, kw = loss, {}
+        if loss == 'gbce':
+            N = int(cand.shape[1]) - 1
+            if N < 1 or V < 2:
+                raise B4CError("candidate_loss: 'gbce' needs at least one negative per list and two items (N = %d, V = %d)" % (N, V))
+            kind, beta = 'bce', self.gbce_beta(N, V, gbce_t)
+            if beta != 1.0:
+                kw['beta'] = beta
+        if logq is not None:
+            if logq.numel() != V:
+                raise B4CError('candidate_loss: logq has %d entries for V = %d items' % (logq.numel(), V))
+            kw.update(corr=logq, correct_target=bool(correct_target))
+        out = self.head.candidate_loss(rows, cand, kind, unit_grad, **kw)
         if poison is not None:
             out = out + torch.where(poison[0] < 0, float('nan'), 0.0).to(out.dtype)
         if bad is not None:
             out = out + torch.where(bad, float('nan'), 0.0).to(out.dtype)
         return out
 
-    def next_item_loss(self, batch, loss='full', variant='tf', unit_grad=False, training=True):
+    def next_item_loss(self, batch, loss='full', variant='tf', unit_grad=False, training=True, gbce_t=0.75, logq=None,
+                       correct_target=False):
         """Next-item training loss of a device-built batch (cloze_batches.DeviceCloze.next_item_batches): every real position of
         the unmasked rows predicts the item after it.  loss 'full': cloze_loss over the whole vocabulary (variant as there);
-        'bce' / 'softmax': candidate_loss over the batch's own lists (built with num_negatives > 0).  A thin entry: the batch's
+        'bce' / 'softmax' / 'bpr' / 'gbce': candidate_loss over the batch's own lists (built with num_negatives > 0), with its
+        gbce_t, logq and correct_target.  A thin entry: the batch's
         flat_idx, labels, candidates and n_real_tokens go to those two methods, whose NaN conventions carry over; compact rows
         past the batch's targets (rows=) are ignored rows.  A model with side features -- every chain naming ONE input, so that each
         is laid out [CLS] [SEP] values .. [SEP] as the batch's flat_idx expects -- takes them from batch['features'] by name
         (DeviceCloze(features=...)); the first chain's input is the items.  Names the model does not use are ignored."""
-        if loss != 'full' and loss not in ops.CAND_LOSS_KINDS:
-            raise B4CError("next_item_loss: loss %r ('full', 'bce' or 'softmax')" % (loss,))
+        self._candidate_loss_options('next_item_loss', loss, gbce_t, logq, correct_target, extra=('full',))
         inputs = self._next_item_inputs(batch)
         if loss == 'full':
             return self.cloze_loss(inputs, batch['labels'], training=training, flat_idx=batch['flat_idx'], variant=variant,
@@ -505,7 +547,8 @@ class ClickstreamTransformer(nn.Module):
         if batch.get('candidates') is None:
             raise B4CError('next_item_loss: loss %r needs the batch\'s candidate lists; build it with num_negatives > 0' % (loss,))
         return self.candidate_loss(inputs, batch['labels'], candidates=batch['candidates'], loss=loss, training=training,
-                                   flat_idx=batch['flat_idx'], unit_grad=unit_grad, n_real_tokens=batch['n_real_tokens'])
+                                   flat_idx=batch['flat_idx'], unit_grad=unit_grad, n_real_tokens=batch['n_real_tokens'], gbce_t=gbce_t,
+                                   logq=logq, correct_target=correct_target)
 
     def _next_item_inputs(self, batch):
         """the model's inputs of a next-item batch (no device work).  Every chain names one input: the layout [CLS] [SEP] values ..

@@ -154,9 +154,11 @@ class SoftMaxHead(nn.Module):
     vocab_major = False        # the projection is stored [V][K], so its gradient over a candidate list is row-sparse
     last_candidates = None     # int32 [R, C] lists of the latest candidate_loss step
 
-    def candidate_loss(self, x2d, cand, kind, unit_grad=False):
+    def candidate_loss(self, x2d, cand, kind, unit_grad=False, *, beta=1.0, corr=None, correct_target=False):
         """Mean over the rows with a valid target of the sampled-negative loss of each row's own list cand (int32 [R, C], label-space
-        ids, target in column 0; < 0 or >= V: absent): kind 'bce' or 'softmax' (ops.CandidateLossFn, b4c_candidate_loss_fwd / _bwd).
+        ids, target in column 0; < 0 or >= V: absent): kind 'bce', 'softmax' or 'bpr' (ops.CandidateLossFn, b4c_candidate_loss_fwd /
+        _fwd_ex / _bwd).  beta weights the target's 'bce' term (gBCE); corr (fp32 [V], data: no gradient) is subtracted from the score
+        of every present negative, and of the target too with correct_target (include/b4c_cand_loss_ex.h).
         Only the listed rows of the projection are read and receive gradient.  The vocabulary-major heads only."""
         if not self.vocab_major:
             raise ops.B4CError('candidate_loss: %s stores its projection as a Keras kernel [K][V], whose gradient is not row-sparse; '
@@ -167,7 +169,8 @@ class SoftMaxHead(nn.Module):
             raise ops.B4CError('candidate_loss: the projection input is %d wide; the candidate kernels need a multiple of 8' % K)
         self.last_candidates = cand
         off = self._packs[-1].tied_offset
-        return ops.CandidateLossFn.apply(h, table, bias, cand, off, kind, unit_grad, table is getattr(self, '_table', None))
+        return ops.CandidateLossFn.apply(h, table, bias, cand, off, kind, unit_grad, table is getattr(self, '_table', None), beta, corr,
+                                         correct_target)
 
     def forward(self, inputs, **kwargs):
         """inputs (B, M, d) -> probabilities (B, M, V), materialised as the reference does."""
@@ -462,9 +465,9 @@ class SampledSoftmaxHead(SoftMaxHead):
 
     vocab_major = True
 
-    def candidate_loss(self, x2d, cand, kind, unit_grad=False):
+    def candidate_loss(self, x2d, cand, kind, unit_grad=False, **kw):
         self.last_samples = None          # the latest step is a candidate step: touched_rows() reads last_candidates
-        return super().candidate_loss(x2d, cand, kind, unit_grad)
+        return super().candidate_loss(x2d, cand, kind, unit_grad, **kw)
 
     accepts_poison = False
 

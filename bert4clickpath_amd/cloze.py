@@ -3,6 +3,7 @@
 
 y_true: (B, M) labels padded with -1;  y_pred: (B, M, V) probabilities (or any monotone score for
 the metrics).  All accumulators live on the device; ``result()`` returns a 0-d tensor."""
+import math
 import weakref
 
 import torch
@@ -77,6 +78,40 @@ def item_counts(ids, V, label_offset=NUM_RESERVED_TOKENS):
     t = t.reshape(-1).to(torch.int64) - int(label_offset)
     t = t[(t >= 0) & (t < V)]
     return torch.bincount(t.cpu(), minlength=V).to(torch.int64)
+
+
+def log_expected_count(item_counts=None, num_items=None, num_negatives=1, device=None):
+    """fp32 [V]: log of the expected number of times each item stands among the num_negatives drawn negatives of one list -- the
+    logQ correction of the sampled softmax, for candidate_loss(logq=...) / next_item_loss(logq=...).  item_counts (int [V], the
+    counts sample_candidates draws by: item_counts() of the training split, DeviceCloze.item_counts): log(N * count_v / total),
+    and 0.0 for an item of count 0, which is never drawn and so never read.  None: uniform over num_items = V items, the constant
+    log(N / V).  `device`: where the tensor is put (default: the CPU; the loss takes a device tensor).
+    AN APPROXIMATION, the one TensorFlow's sampled_softmax_loss makes: the sampler rejects the row's label and its excluded
+    items and draws DISTINCT items, so an item's true inclusion probability depends on the row; the correction uses the
+    unconditional N * q_v.  The target stands in its list with probability 1, not N * q_y: the losses leave its score
+    uncorrected unless correct_target=True."""
+    N = int(num_negatives)
+    if N < 1:
+        raise ValueError('log_expected_count: num_negatives = %d' % N)
+    if item_counts is not None:
+        cnt = torch.as_tensor(item_counts)
+        if cnt.dim() != 1 or cnt.dtype.is_floating_point or cnt.dtype == torch.bool:
+            raise ValueError('log_expected_count: item_counts must be an integer [V] tensor')
+        cnt = cnt.to(torch.int64).cpu()
+        if num_items is not None and int(num_items) != cnt.shape[0]:
+            raise ValueError('log_expected_count: %d item counts for num_items = %d' % (cnt.shape[0], num_items))
+        if bool((cnt < 0).any()) or int(cnt.sum()) <= 0:
+            raise ValueError('log_expected_count: item counts must be >= 0 with a positive total')
+        q = cnt.to(torch.float64) * (float(N) / float(int(cnt.sum())))
+        out = torch.where(cnt > 0, torch.log(q.clamp(min=1e-300)), torch.zeros_like(q)).to(torch.float32)
+    elif num_items is None:
+        raise ValueError('log_expected_count: give item_counts (popularity) or num_items (uniform)')
+    else:
+        V = int(num_items)
+        if V <= 0:
+            raise ValueError('log_expected_count: num_items = %d' % V)
+        out = torch.full((V,), math.log(float(N) / V), dtype=torch.float32)
+    return out if device is None else out.to(device)
 
 
 def _labels_i32(y_true, device):

@@ -1,5 +1,6 @@
-// Sampled-negative training (include/b4c_cand_loss.h): the loss of each row over its own candidate list -- target in column 0,
-// SASRec's binary cross-entropy or the list-wise softmax -- and its backward into dh and the row-sparse fp32 gradient sinks.
+// Sampled-negative training (include/b4c_cand_loss.h, include/b4c_cand_loss_ex.h): the loss of each row over its own candidate
+// list -- target in column 0; SASRec's binary cross-entropy (its target term weighted by beta: gBCE), the list-wise softmax or BPR,
+// over scores that a per-item correction (logQ) may shift -- and its backward into dh and the row-sparse fp32 gradient sinks.
 //
 // One wave per row as its own 64-thread workgroup, as in candidates.hip: rows share nothing.  Both kernels read the fp32 MASTER
 // table at the listed rows (for bf16 h each element is rounded to bf16 first: the value the packed copy would hold), so nothing
@@ -7,6 +8,7 @@
 // floats per row of h) with FP32 FMAs on the VALU; the backward gathers the same rows once more for dh and adds C rows of K
 // floats into the table's gradient with float atomics: its floor is the chip-wide atomic rate.
 #include "common.h"
+#include <cfloat>
 
 template <typename T> __device__ __forceinline__ float cl_operand(float w) { return w; }
 template <> __device__ __forceinline__ float cl_operand<bf16_t>(float w) { return (float)(bf16_t)w; }
@@ -35,10 +37,11 @@ template <typename T, int G, int NC, int U>
 __global__ void __launch_bounds__(64) cand_loss_fwd_kernel(const T *__restrict__ h, int ld_h, const float *__restrict__ table, int ld_t,
                                                            int64_t row_off, const float *__restrict__ bias,
                                                            const int32_t *__restrict__ cand, int ld_c, int C, int V, int K, int kind,
+                                                           float beta, const float *__restrict__ corr, int flags,
                                                            float *__restrict__ item_loss, float *__restrict__ g, int ld_g,
                                                            float *__restrict__ scores, int ld_s) {
     extern __shared__ int cl_lds[];
-    float *sv = reinterpret_cast<float *>(cl_lds);      // [C] scores of the list
+    float *sv = reinterpret_cast<float *>(cl_lds);      // [C] corrected scores z of the list (z = s without corr)
     int *si = cl_lds + C;                               // [C] ids, -1 where absent
     constexpr int PER = 64 / G;
     const int lane = threadIdx.x, sub = lane % G, slot = lane / G;
@@ -96,22 +99,51 @@ __global__ void __launch_bounds__(64) cand_loss_fwd_kernel(const T *__restrict__
         }
     }
     __syncthreads();
+    if (corr) {
+        // z = s - corr[id]: one fp32 subtraction on the stored score, after the gather (inside it, next to the bias load, the
+        // K = 128 bf16 form needs 66 VGPRs and drops to 7 waves / SIMD; here every form keeps the registers it had -- DESIGN.md)
+        const int first = (flags & B4C_CANDX_CORR_TARGET) ? 0 : 1;
+        for (int p = lane; p < C; p += 64)
+            if (p >= first && si[p] >= 0) sv[p] -= corr[si[p]];
+        __syncthreads();
+    }
     float loss;
-    if (kind == B4C_CAND_BCE) {
-        // the target's term is softplus(-s_0) with coefficient -sigma(-s_0) = sigma(s_0) - 1: one form, x = -s at the target
+    if (kind == B4C_CANDX_BCE) {
+        // the target's term is beta * softplus(-z_0) with coefficient -(beta * sigma(-z_0)): one form, x = -z at the target.
+        // (beta == 1: the products are exact, the bits of b4c_candidate_loss_fwd)
         float l = 0.f;
         for (int p = lane; p < C; p += 64) {
             float gc = 0.f;
             if (si[p] >= 0) {
                 const float x = p == 0 ? -sv[p] : sv[p];
                 const float e = expf(-fabsf(x));
-                l += fmaxf(x, 0.f) + log1pf(e);
+                const float t = fmaxf(x, 0.f) + log1pf(e);
                 const float sig = (x >= 0.f ? 1.f : e) / (1.f + e);
-                gc = p == 0 ? -sig : sig;
+                l += p == 0 ? beta * t : t;
+                gc = p == 0 ? -(beta * sig) : sig;
             }
             gr[p] = gc;
         }
         loss = wave_sum(l);
+    } else if (kind == B4C_CANDX_BPR) {
+        // every present negative against the target: softplus(z_c - z_0); the target's coefficient is minus the sum of the others'
+        const float z0 = sv[0];
+        float l = 0.f, gsum = 0.f;
+        for (int p = lane; p < C; p += 64) {
+            if (p == 0) continue;
+            float gc = 0.f;
+            if (si[p] >= 0) {
+                const float x = sv[p] - z0;
+                const float e = expf(-fabsf(x));
+                l += fmaxf(x, 0.f) + log1pf(e);
+                gc = (x >= 0.f ? 1.f : e) / (1.f + e);
+                gsum += gc;
+            }
+            gr[p] = gc;
+        }
+        loss = wave_sum(l);
+        gsum = wave_sum(gsum);
+        if (lane == 0) gr[0] = 0.f - gsum;                  // no present negative: 0 - 0, and the loss is the empty sum
     } else {
         float m = -__builtin_inff();
         for (int p = lane; p < C; p += 64)
@@ -247,6 +279,25 @@ static int cl_check(const char *who, const void *h, int ld_h, const float *table
     return B4C_OK;
 }
 
+// the one forward launch of both entry points; lds = 8 C bytes
+static_assert(B4C_CAND_BCE == B4C_CANDX_BCE && B4C_CAND_SOFTMAX == B4C_CANDX_SOFTMAX, "the extended kinds continue the first two");
+static void cl_launch_fwd(const void *h, int ld_h, const float *table, int ld_t, int64_t row_off, const float *bias, const int32_t *cand,
+                          int ld_c, int64_t R, int C, int V, int K, int dtype, int kind, float beta, const float *corr, int flags,
+                          float *item_loss, float *g, int ld_g, float *scores, int ld_s, hipStream_t st) {
+    const size_t lds = (size_t)C * 8;
+    cl_by_chunks(K / 8, [&](auto G, auto NC) {
+        constexpr int U = cl_unroll<G()>();
+        if (dtype == B4C_F32)
+            cand_loss_fwd_kernel<float, G(), NC(), U><<<(unsigned)R, 64, lds, st>>>((const float *)h, ld_h, table, ld_t, row_off, bias, cand,
+                                                                                  ld_c, C, V, K, kind, beta, corr, flags, item_loss, g,
+                                                                                  ld_g, scores, ld_s);
+        else
+            cand_loss_fwd_kernel<bf16_t, G(), NC(), U><<<(unsigned)R, 64, lds, st>>>((const bf16_t *)h, ld_h, table, ld_t, row_off, bias, cand,
+                                                                                   ld_c, C, V, K, kind, beta, corr, flags, item_loss, g,
+                                                                                   ld_g, scores, ld_s);
+    });
+}
+
 extern "C" int b4c_candidate_loss_fwd(const void *h, int ld_h, const float *table, int ld_t, int64_t rows, int64_t row_off,
                                       const float *bias, const int32_t *cand, int ld_c, int64_t R, int C, int V, int K, int dtype,
                                       int kind, float *item_loss, float *g, int ld_g, float *scores, int ld_s, void *stream) {
@@ -256,18 +307,29 @@ extern "C" int b4c_candidate_loss_fwd(const void *h, int ld_h, const float *tabl
     B4C_REQUIRE(bias && item_loss && g, "candidate_loss_fwd: null pointer (bias, item_loss or g)");
     B4C_REQUIRE(ld_g >= C && (!scores || ld_s >= C), "candidate_loss_fwd: ld_g = %d or ld_s = %d below C = %d", ld_g, ld_s, C);
     if (R == 0) return B4C_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)C * 8;
-    cl_by_chunks(K / 8, [&](auto G, auto NC) {
-        constexpr int U = cl_unroll<G()>();
-        if (dtype == B4C_F32)
-            cand_loss_fwd_kernel<float, G(), NC(), U><<<(unsigned)R, 64, lds, st>>>((const float *)h, ld_h, table, ld_t, row_off, bias, cand,
-                                                                                  ld_c, C, V, K, kind, item_loss, g, ld_g, scores, ld_s);
-        else
-            cand_loss_fwd_kernel<bf16_t, G(), NC(), U><<<(unsigned)R, 64, lds, st>>>((const bf16_t *)h, ld_h, table, ld_t, row_off, bias, cand,
-                                                                                   ld_c, C, V, K, kind, item_loss, g, ld_g, scores, ld_s);
-    });
+    // (B4C_CAND_BCE / _SOFTMAX are B4C_CANDX_BCE / _SOFTMAX; beta = 1, no correction: the kernel's products by beta are exact)
+    cl_launch_fwd(h, ld_h, table, ld_t, row_off, bias, cand, ld_c, R, C, V, K, dtype, kind, 1.f, nullptr, 0, item_loss, g, ld_g, scores,
+                  ld_s, (hipStream_t)stream);
     return b4c_check_launch("candidate_loss_fwd");
+}
+
+extern "C" int b4c_candidate_loss_fwd_ex(const void *h, int ld_h, const float *table, int ld_t, int64_t rows, int64_t row_off,
+                                         const float *bias, const int32_t *cand, int ld_c, int64_t R, int C, int V, int K, int dtype,
+                                         int kind, float beta, const float *corr, int flags, float *item_loss, float *g, int ld_g,
+                                         float *scores, int ld_s, void *stream) {
+    const int rc = cl_check("candidate_loss_fwd_ex", h, ld_h, table, ld_t, rows, row_off, cand, ld_c, R, C, V, K, dtype);
+    if (rc != B4C_OK) return rc;
+    B4C_REQUIRE(kind >= 0 && kind < B4C_CANDX_KINDS, "candidate_loss_fwd_ex: kind %d (B4C_CANDX_BCE, B4C_CANDX_SOFTMAX, B4C_CANDX_BPR)",
+                kind);
+    B4C_REQUIRE((flags & ~B4C_CANDX_CORR_TARGET) == 0, "candidate_loss_fwd_ex: flags 0x%x (B4C_CANDX_CORR_TARGET is the one bit)", flags);
+    B4C_REQUIRE(corr || !(flags & B4C_CANDX_CORR_TARGET), "candidate_loss_fwd_ex: B4C_CANDX_CORR_TARGET without corr");
+    B4C_REQUIRE(beta >= 0.f && beta <= FLT_MAX, "candidate_loss_fwd_ex: beta = %g (finite, >= 0)", (double)beta);
+    B4C_REQUIRE(bias && item_loss && g, "candidate_loss_fwd_ex: null pointer (bias, item_loss or g)");
+    B4C_REQUIRE(ld_g >= C && (!scores || ld_s >= C), "candidate_loss_fwd_ex: ld_g = %d or ld_s = %d below C = %d", ld_g, ld_s, C);
+    if (R == 0) return B4C_OK;
+    cl_launch_fwd(h, ld_h, table, ld_t, row_off, bias, cand, ld_c, R, C, V, K, dtype, kind, beta, corr, flags, item_loss, g, ld_g, scores,
+                  ld_s, (hipStream_t)stream);
+    return b4c_check_launch("candidate_loss_fwd_ex");
 }
 
 extern "C" int b4c_candidate_loss_bwd(const void *h, int ld_h, const float *table, int ld_t, int64_t rows, int64_t row_off,

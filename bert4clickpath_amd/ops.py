@@ -1635,6 +1635,48 @@ def candidate_loss_fwd(h, table, bias, cand, V, kind, row_off=0, want_scores=Fal
     return item, g, scores
 
 
+CANDX_LOSS_KINDS = {'bce': L.CANDX_BCE, 'softmax': L.CANDX_SOFTMAX, 'bpr': L.CANDX_BPR}
+
+
+def candidate_loss_fwd_ex(h, table, bias, cand, V, kind, row_off=0, want_scores=False, beta=1.0, corr=None, correct_target=False):
+    """candidate_loss_fwd with the additions of include/b4c_cand_loss_ex.h (b4c_candidate_loss_fwd_ex) -> (item_loss, g, scores or
+    None).  kind 'bce' = beta * softplus(-z_0) + sum of softplus(z_c) (beta finite, >= 0; 1.0: SASRec's, another value: gSASRec's
+    gBCE), 'softmax' as there, 'bpr' = sum over the present negatives of softplus(z_c - z_0).  z = s - corr[id] at every present
+    negative, and at the target too with correct_target (corr fp32 [>= V], e.g. cloze.log_expected_count: the logQ correction);
+    corr None: z = s.  scores are the uncorrected s; g is the derivative by z and by s alike, candidate_loss_bwd takes it as it is.
+    With 'bce' / 'softmax', beta 1.0 and no corr the result is bit for bit candidate_loss_fwd's."""
+    who = 'candidate_loss_fwd_ex'
+    if kind not in CANDX_LOSS_KINDS:
+        raise B4CError("%s: kind %r ('bce', 'softmax' or 'bpr')" % (who, kind))
+    try:
+        beta = float(beta)
+    except (TypeError, ValueError):
+        raise B4CError('%s: beta = %r (a finite number >= 0)' % (who, beta)) from None
+    if not (0.0 <= beta < float('inf')):
+        raise B4CError('%s: beta = %r (a finite number >= 0)' % (who, beta))
+    if corr is None and correct_target:
+        raise B4CError('%s: correct_target needs corr (there is no correction to apply to the target)' % who)
+    cand, ld_c, C, R, K, dt = _cand_loss_args(who, h, table, row_off, V, cand)
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.numel() < V:
+        raise B4CError('%s: bias must be fp32 [>= V]' % who)
+    if corr is not None and (not isinstance(corr, torch.Tensor) or corr.dtype != torch.float32 or corr.dim() != 1 or corr.numel() < V
+                             or not corr.is_contiguous()):
+        raise B4CError('%s: corr must be a contiguous fp32 [>= V] tensor' % who)
+    _cuda(h, table, bias, cand, *(() if corr is None else (corr,)))
+    dev = h.device
+    item = torch.empty(R, dtype=torch.float32, device=dev)
+    g = torch.empty(R, C, dtype=torch.float32, device=dev)
+    scores = torch.empty(R, C, dtype=torch.float32, device=dev) if want_scores else None
+    if R == 0:
+        return item, g, scores
+    flags = L.CANDX_CORR_TARGET if correct_target else 0
+    with _record(who, R * K * h.element_size() + R * C * (K * 4 + (12 if corr is None else 16)), 2 * R * C * K):
+        L.check(L.lib().b4c_candidate_loss_fwd_ex(_p(h), h.stride(0), _p(table), table.stride(0), table.shape[0], int(row_off),
+                                                  _p(bias.contiguous()), _p(cand), ld_c, R, C, V, K, dt, CANDX_LOSS_KINDS[kind], beta,
+                                                  _p(corr), flags, _p(item), _p(g), C, _p(scores), C, _st()), who)
+    return item, g, scores
+
+
 def candidate_loss_bwd(h, table, cand, g, gscale, V, dtable, dbias, row_off=0):
     """-> dh [R, K] in h's dtype = gscale * sum_c g[r][c] * table[row_off + cand[r][c]], and ADDS gscale * g[r][c] * h[r] into row
     row_off + cand[r][c] of dtable (fp32, the table's shape) and gscale * g[r][c] into dbias[cand[r][c]] (fp32 [>= V]) with float
@@ -3366,14 +3408,18 @@ class SampledCEFn(torch.autograd.Function):
 
 
 class CandidateLossFn(torch.autograd.Function):
-    """Sampled-negative masked-item loss over each row's own candidate list, target in column 0 (include/b4c_cand_loss.h): 'bce'
-    (SASRec) or 'softmax' (list-wise), mean over the rows with a valid target.  The table -- vocabulary-major projection
-    (row_off 0) or tied item embedding (row_off = its id offset) -- is read and receives gradient at the listed rows only.
-    apply(h [R, K], table (rows, K) fp32, bias (V,) fp32, cand int32 [R, C], row_off, kind, unit_grad[, shared_table])
-    shared_table: the table is the embedding layer's too, whose backward runs last and announces its gradient."""
+    """Sampled-negative masked-item loss over each row's own candidate list, target in column 0 (include/b4c_cand_loss.h,
+    include/b4c_cand_loss_ex.h): 'bce' (SASRec; its target term times beta: gBCE), 'softmax' (list-wise) or 'bpr', mean over the
+    rows with a valid target.  The table -- vocabulary-major projection (row_off 0) or tied item embedding (row_off = its id
+    offset) -- is read and receives gradient at the listed rows only.
+    apply(h [R, K], table (rows, K) fp32, bias (V,) fp32, cand int32 [R, C], row_off, kind, unit_grad[, shared_table[, beta[, corr[,
+          correct_target]]]])
+    shared_table: the table is the embedding layer's too, whose backward runs last and announces its gradient.  beta, corr,
+    correct_target: candidate_loss_fwd_ex's; corr is data (fp32 [V], no gradient).  With all three at their defaults and kind 'bce'
+    or 'softmax' the forward is candidate_loss_fwd -- the same kernel, the same bits."""
 
     @staticmethod
-    def forward(ctx, h, table, bias, cand, row_off, kind, unit_grad, shared_table=False):
+    def forward(ctx, h, table, bias, cand, row_off, kind, unit_grad, shared_table=False, beta=1.0, corr=None, correct_target=False):
         h = h.contiguous()
         V = bias.shape[0]
         present = (cand >= 0) & (cand < V)
@@ -3382,7 +3428,11 @@ class CandidateLossFn(torch.autograd.Function):
         lz = getattr(table, '_b4c_lazy', None)
         if lz is not None:          # row-lazy optimizer: the listed rows are brought up to date before they are read
             lz.catch_up(torch.where(present, cand + int(row_off), torch.full_like(cand, -1)), note=ctx.needs_input_grad[1])
-        item, g, _ = candidate_loss_fwd(h, table.detach(), bias.detach(), cand, V, kind, row_off)
+        if kind in CAND_LOSS_KINDS and beta == 1.0 and corr is None and not correct_target:
+            item, g, _ = candidate_loss_fwd(h, table.detach(), bias.detach(), cand, V, kind, row_off)
+        else:
+            item, g, _ = candidate_loss_fwd_ex(h, table.detach(), bias.detach(), cand, V, kind, row_off, False, beta,
+                                               None if corr is None else corr.detach(), correct_target)
         ctx.save_for_backward(h, g, cand, scale)
         ctx.params, ctx.row_off, ctx.unit_grad, ctx.shared_table = (table, bias), int(row_off), unit_grad, bool(shared_table)
         return item.sum() * scale[0]

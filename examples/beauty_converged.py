@@ -25,8 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from examples.beauty_hitrate import (add_objective_argument, add_train_loss_arguments, build_model, next_item_train_batches,  # noqa: E402
-                                     training_loss)
+from examples.beauty_hitrate import (add_objective_argument, add_train_loss_arguments, build_model, check_train_loss_arguments,  # noqa: E402
+                                     next_item_train_batches, next_item_training_loss, train_sampling, training_loss)
 
 
 def evaluate(model, data, batch=1024, split='test', filtered=False, next_item=False):
@@ -91,6 +91,7 @@ def main():
     next_item = a.objective == 'next_item'
     if next_item and not a.device_batches:
         ap.error('--objective next_item needs --device_batches')
+    check_train_loss_arguments(ap, a)
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
         ap.error('--max_len, --stride, --holdout and --last_item_rate need --device_batches')
@@ -110,7 +111,8 @@ def main():
     plateau = ck.ReduceLROnPlateau(opt, factor=0.317, patience=10)
     stopper = ck.EarlyStopping(patience=30)
     steps = a.steps_per_epoch * a.max_epochs
-    batches = next_item_train_batches(data, a, steps) if next_item else data.train_batches(a.batch, a.seed, steps)
+    sampling = train_sampling(data, a)
+    batches = next_item_train_batches(data, a, steps, sampling['item_cdf']) if next_item else data.train_batches(a.batch, a.seed, steps)
     monitored = 'valid' if a.holdout == 2 else 'test'      # the split the callbacks see
     t0 = time.perf_counter()
     curve, stopped_by, best = [], 'max_epochs', None
@@ -120,9 +122,9 @@ def main():
             b = next(batches)
             opt.zero_grad()
             if next_item:
-                loss = model.next_item_loss(b, loss=a.train_loss)
+                loss = next_item_training_loss(model, a, b, sampling['logq'])
             elif a.device_batches:
-                loss = training_loss(model, a, {'asin': b['items']}, b['labels_padded'],
+                loss = training_loss(model, a, {'asin': b['items']}, b['labels_padded'], **sampling,
                                      max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
             else:
                 items = torch.from_numpy(b['ids'])[:, 2:-1].contiguous().cuda()

@@ -46,7 +46,7 @@ def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='b
     buckets K > 0: a second embedded feature of K values, summed with the item's embedding (the width stays 64).
     attention='causal': left-to-right self-attention (SASRec, the paper's unidirectional arm).
     tied_head: score an item by the dot product of the encoder output with its embedding (SASRec's head), in place of the reference's
-    dense stack -- the sampled-negative losses (--train_loss bce / softmax) need a projection stored per item."""
+    dense stack -- the sampled-negative losses (--train_loss bce / softmax / bpr / gbce) need a projection stored per item."""
     from bert4clickpath_amd.clickstream_transformer import ClickstreamTransformer, ClozeMaskedItemPrediction, SoftMaxHead
     torch.manual_seed(seed)            # CPU generator: identical initial weights on any machine
     vocab = ['item%d' % i for i in range(V)]
@@ -68,12 +68,19 @@ def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='b
 
 
 def add_train_loss_arguments(ap):
-    ap.add_argument('--train_loss', default='full', choices=['full', 'bce', 'softmax'],
-                    help='full: the softmax over all V items (cloze_loss); bce / softmax: each target against --train_negatives sampled '
-                         'items that its sequence does not hold (model.candidate_loss) -- binary cross-entropy per item (SASRec) or '
-                         'the list-wise softmax; the head is then the tied dot product with the item embedding.  SASRec\'s recipe: '
+    ap.add_argument('--train_loss', default='full', choices=['full', 'bce', 'softmax', 'bpr', 'gbce'],
+                    help='full: the softmax over all V items (cloze_loss); bce / softmax / bpr / gbce: each target against '
+                         '--train_negatives sampled items that its sequence does not hold (model.candidate_loss) -- binary '
+                         'cross-entropy per item (SASRec), the list-wise softmax, the pairwise BPR loss, or gSASRec\'s generalised BCE '
+                         '(--gbce_t); the head is then the tied dot product with the item embedding.  SASRec\'s recipe: '
                          '--device_batches --attention causal --objective next_item --train_loss bce --train_negatives 1')
-    ap.add_argument('--train_negatives', type=int, default=1, help='with --train_loss bce / softmax: negatives drawn per target')
+    ap.add_argument('--train_negatives', type=int, default=1, help='with a sampled --train_loss: negatives drawn per target')
+    ap.add_argument('--gbce_t', type=float, default=0.75,
+                    help='with --train_loss gbce: the calibration parameter t in [0, 1] (0: plain bce; gSASRec uses 0.75 with 256 negatives)')
+    ap.add_argument('--logq', action='store_true',
+                    help='with a sampled --train_loss and --device_batches: draw the training negatives by popularity (the item counts of '
+                         'the training views) and subtract the matching log expected count from every negative\'s score -- the '
+                         'sampled-softmax logQ correction (cloze.log_expected_count)')
 
 
 def add_objective_argument(ap):
@@ -84,20 +91,50 @@ def add_objective_argument(ap):
                          'evaluation rows end at the item in front of the target: no [MASK] in training or in evaluation')
 
 
-def next_item_train_batches(dev_data, a, steps):
-    """the --objective next_item training batches: negatives only where --train_loss reads them"""
-    return dev_data.next_item_batches(a.batch, a.seed, steps, num_negatives=0 if a.train_loss == 'full' else a.train_negatives)
+def check_train_loss_arguments(ap, a):
+    if a.logq and (a.train_loss == 'full' or not a.device_batches):
+        ap.error('--logq corrects sampled negatives drawn from the device data set\'s counts: it needs --device_batches and a '
+                 '--train_loss other than full')
+    if not 0.0 <= a.gbce_t <= 1.0:
+        ap.error('--gbce_t must be in [0, 1]')
 
 
-def training_loss(model, a, feats, labels, **kw):
-    """the loss --train_loss selects; kw: cloze_loss's flat_idx / max_masked_per_row / n_real_tokens"""
+def train_sampling(dev_data, a):
+    """how the training negatives are drawn and corrected -> dict(item_cdf=, logq=): both None (uniform, no correction) without
+    --logq; with it the prefix sum of the training views' item counts, which the sampler draws by, and the log expected count of every
+    item among the --train_negatives negatives of a list, on the device"""
+    if not a.logq:
+        return dict(item_cdf=None, logq=None)
+    from bert4clickpath_amd import cloze
+    counts = dev_data.item_counts('train')
+    return dict(item_cdf=torch.from_numpy(np.cumsum(counts)).cuda(),
+                logq=cloze.log_expected_count(counts, num_negatives=a.train_negatives, device='cuda'))
+
+
+def next_item_train_batches(dev_data, a, steps, item_cdf=None):
+    """the --objective next_item training batches: negatives only where --train_loss reads them (item_cdf: drawn by popularity)"""
+    return dev_data.next_item_batches(a.batch, a.seed, steps, num_negatives=0 if a.train_loss == 'full' else a.train_negatives,
+                                      item_cdf=item_cdf)
+
+
+def next_item_training_loss(model, a, batch, logq=None):
+    """model.next_item_loss with what --train_loss, --gbce_t and --logq select"""
+    if a.train_loss == 'full':
+        return model.next_item_loss(batch, loss='full')
+    return model.next_item_loss(batch, loss=a.train_loss, gbce_t=a.gbce_t, logq=logq)
+
+
+def training_loss(model, a, feats, labels, item_cdf=None, logq=None, **kw):
+    """the loss --train_loss selects; item_cdf, logq: train_sampling's; kw: cloze_loss's flat_idx / max_masked_per_row /
+    n_real_tokens"""
     if a.train_loss == 'full':
         return model.cloze_loss(feats, labels, training=True, **kw)
     from bert4clickpath_amd import cloze
     seen = cloze.seen_items(feats['asin'])                   # (B, S): a sequence's own items are never its negatives
     if kw.get('flat_idx') is not None:                       # rows are named by position: one exclusion list per row
         seen = seen[(kw['flat_idx'].long() // (feats['asin'].shape[1] + 3))]       # [CLS] [SEP] items [SEP]
-    return model.candidate_loss(feats, labels, num_negatives=a.train_negatives, loss=a.train_loss, exclude=seen, training=True, **kw)
+    return model.candidate_loss(feats, labels, num_negatives=a.train_negatives, loss=a.train_loss, exclude=seen, training=True,
+                                item_cdf=item_cdf, gbce_t=a.gbce_t, logq=logq, **kw)
 
 
 def main():
@@ -153,6 +190,7 @@ def main():
         ap.error('--popularity_buckets K > 0 needs --device_batches and the reference\'s model (no --paper_model)')
     if a.objective == 'next_item' and not a.device_batches:
         ap.error('--objective next_item needs --device_batches')
+    check_train_loss_arguments(ap, a)
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
         ap.error('--max_len, --stride, --holdout and --last_item_rate need --device_batches')
@@ -180,13 +218,14 @@ def main():
             protocol_kw = protocol
         dev_data = DeviceCloze.from_npz(a.data, **protocol_kw)
     next_item = a.objective == 'next_item'
-    for step, b in enumerate(next_item_train_batches(dev_data, a, a.steps) if next_item
+    sampling = train_sampling(dev_data, a)
+    for step, b in enumerate(next_item_train_batches(dev_data, a, a.steps, sampling['item_cdf']) if next_item
                              else (dev_data or data).train_batches(a.batch, a.seed, a.steps)):
         opt.zero_grad()
         if next_item:                 # unmasked rows, every position's target and its negatives: all built on the device
-            loss = model.next_item_loss(b, loss=a.train_loss)
+            loss = next_item_training_loss(model, a, b, sampling['logq'])
         elif dev_data is not None:      # items and padded labels are on the device already; nothing is read back
-            loss = training_loss(model, a, dev_data.inputs(b, 'asin'), b['labels_padded'],
+            loss = training_loss(model, a, dev_data.inputs(b, 'asin'), b['labels_padded'], **sampling,
                                  max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
         else:
             ids = torch.from_numpy(b['ids'])
