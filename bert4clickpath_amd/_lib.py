@@ -14,7 +14,8 @@ EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_ex
 ADDON_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss.h'),
                       os.path.join(os.path.dirname(_HERE), 'include', 'b4c_next_item.h'),
                       os.path.join(os.path.dirname(_HERE), 'include', 'b4c_batch_features.h'),
-                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss_ex.h'))
+                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss_ex.h'),
+                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_mq_ex.h'))
 
 
 class B4CError(RuntimeError):

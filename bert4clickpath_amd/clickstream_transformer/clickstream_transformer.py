@@ -356,9 +356,12 @@ class ClickstreamTransformer(nn.Module):
         return logits
 
     # ---- fused MI355X entry points ----------------------------------------------------------------
-    def _masked_rows(self, inputs, training, flat_idx=None, cap=None, labels_padded=None, pack=False, n_real_tokens=None):
+    def _masked_rows(self, inputs, training, flat_idx=None, cap=None, labels_padded=None, pack=False, n_real_tokens=None,
+                     row_offsets=None):
         """Encoder output rows at the [MASK] positions, row-major.
-        flat_idx given: used as is.  cap given: the sync-free form -- index generation and label compaction stay on
+        flat_idx given: used as is; with row_offsets ([B + 1] int32: rows row_offsets[b] .. row_offsets[b + 1] of flat_idx are
+        sequence b's, in ascending order; the rows behind row_offsets[B] hold -1) the last layer can still be evaluated at those
+        rows only.  cap given: the sync-free form -- index generation and label compaction stay on
         the device, exactly `cap` rows come back (those beyond the real count R are zero rows whose label is -1) together
         with the compact int32 labels.  Neither: R is read back from the device (one host sync).
         pack: the encoder runs on the padding-free layout; the dense [MASK] indices are mapped to its rows."""
@@ -384,7 +387,17 @@ class ClickstreamTransformer(nn.Module):
         # The positions depend on the ids alone.  With them in hand BEFORE the encoder runs, its last layer is evaluated
         # for those rows only (ops.MQAttnBlockFn): nothing else of that layer's output is ever read on this path.
         # (in training with attention dropout only with ops.mq_attn_dropout: without it the full layer runs and its rows are gathered)
-        mq = flat_idx is None and ops.mq_last_layer and self.transformer.encoder.rows_route(None, bool(training))
+        given = flat_idx is not None and row_offsets is not None
+        mq = (flat_idx is None or given) and ops.mq_last_layer and self.transformer.encoder.rows_route(None, bool(training))
+        if mq and given:
+            # the caller's rows and their per-sequence offsets (a next-item evaluation batch carries both): the same route; the rows
+            # behind row_offsets[B] belong to no sequence and stay zeros
+            dev = self.transformer.position_table.device
+            fi = torch.as_tensor(flat_idx).to(device=dev, dtype=torch.int32)
+            off = torch.as_tensor(row_offsets).to(device=dev, dtype=torch.int32)
+            self._row_offsets = off
+            rows, _, _, _, _ = self._encode(inputs, training, pack, n_real_tokens, rows_of=lambda ids_first, raw_first: (fi, off, None))
+            return rows, None
         if mq:
             rows, _, _, _, _ = self._encode(inputs, training, pack, n_real_tokens, rows_of=positions)
             return rows, self._rows_extra
@@ -568,7 +581,8 @@ class ClickstreamTransformer(nn.Module):
         return inputs
 
     @torch.no_grad()
-    def predict_topk(self, inputs, k, labels=None, flat_idx=None, packed=None, n_real_tokens=None, exclude=None, candidates=None):
+    def predict_topk(self, inputs, k, labels=None, flat_idx=None, packed=None, n_real_tokens=None, exclude=None, candidates=None,
+                     row_offsets=None):
         """Top-k item ids (label space) at every masked position, ranked over all V items: the fp32 path ranks the fp32
         probabilities as the reference's metrics do (utils.py:176, 245), the bf16 path the fp32 logits (head.SoftMaxHead.topk);
         returns (topk_idx (R,k) int32, hit (R,), ndcg (R,)) -- the latter two when labels are given.
@@ -579,11 +593,16 @@ class ClickstreamTransformer(nn.Module):
         candidates: the ranking is limited to a list of items per row (label space; < 0 or >= V: absent) -- an integer tensor
         (R, C) one list per masked row, or (B, C) one per sequence, C <= 1024 (cloze.sample_candidates for the sampled-negative
         protocol); the fp32 logits of the listed items are ranked, the label counts only where it is listed, and hit / ndcg
-        come from the label's rank among the listed items.  Not together with exclude."""
+        come from the label's rank among the listed items.  Not together with exclude.
+        row_offsets (with flat_idx; a next-item batch's b['row_offsets']): the [B + 1] int32 offsets of the compact rows per
+        sequence.  With them the last encoder layer is evaluated at the given rows only where that route is open
+        (ops.mq_last_layer, Encoder.rows_route: a bidirectional model, or a causal one with ops.mq_causal), and (B, ...) exclude /
+        candidates lists are spread over the rows by them; without them, or with the route closed, the full last layer runs and
+        its rows are gathered."""
         if candidates is not None and exclude is not None:
             raise B4CError('predict_topk: candidates and exclude together; leave excluded items out of the lists')
         rows, _ = self._masked_rows(inputs, False, flat_idx, pack=self._use_packed(inputs, packed, n_real_tokens),
-                                    n_real_tokens=n_real_tokens)
+                                    n_real_tokens=n_real_tokens, row_offsets=row_offsets)
         lab = None
         if labels is not None:
             lab = torch.as_tensor(labels, device=rows.device)
@@ -617,13 +636,14 @@ class ClickstreamTransformer(nn.Module):
         return idx, hit, ndcg
 
     @torch.no_grad()
-    def score_candidates(self, inputs, candidates, labels=None, flat_idx=None, packed=None, n_real_tokens=None):
+    def score_candidates(self, inputs, candidates, labels=None, flat_idx=None, packed=None, n_real_tokens=None, row_offsets=None):
         """fp32 logits (R, C) of each [MASK] row's own candidate list (label-space ids; an id < 0 or >= V is absent and scores
         NaN): the head's projection at the listed items only (head.SoftMaxHead.score_candidates, b4c_candidate_score).
         candidates: an integer tensor (R, C) one list per masked row in row-major order, or (B, C) one per sequence, C <= 1024.
-        labels are not needed for the scores; they are accepted as predict_topk accepts them (and ignored)."""
+        labels are not needed for the scores; they are accepted as predict_topk accepts them (and ignored).
+        row_offsets: as in predict_topk."""
         rows, _ = self._masked_rows(inputs, False, flat_idx, pack=self._use_packed(inputs, packed, n_real_tokens),
-                                    n_real_tokens=n_real_tokens)
+                                    n_real_tokens=n_real_tokens, row_offsets=row_offsets)
         cand = self._row_candidates(candidates, rows.shape[0], rows.device, 'score_candidates')
         if hasattr(self.head, 'score_candidates'):
             scores, _, _ = self.head.score_candidates(rows, cand)

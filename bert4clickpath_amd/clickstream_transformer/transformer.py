@@ -278,7 +278,9 @@ class EncoderLayer(nn.Module):
         rows = (midx [R] int32 token rows, moff [B+1] int32 per-sequence offsets into them): the layer is evaluated for
         those query rows only (keys / values from every token) and returns (R, d) -- the last layer of the Cloze path.
         In training with attention_dropout_rate > 0 that takes ops.mq_attn_dropout (off by default: B4CError); the masked-query
-        kernels then draw, with the layer's third seed, the masks the full layer draws for those rows."""
+        kernels then draw, with the layer's third seed, the masks the full layer draws for those rows.
+        On a causal layer it takes ops.mq_causal (off by default: B4CError): each query row then attends to the keys up to its own
+        position, as the full causal layer does at that row."""
         B, S, d = x.shape
         training = bool(training)
         cu = None
@@ -299,9 +301,10 @@ class EncoderLayer(nn.Module):
         s3 = dropout_seeds.next() if a_rate > 0 else 0
         need_tape = training or torch.is_grad_enabled()
         if rows is not None:
-            if self.attention == 'causal':
-                raise B4CError('the masked-query last layer (rows=) has no causal form: evaluate the full layer of a causal '
-                               'encoder and gather its rows (Encoder.rows_supported(dtype, training))')
+            if self.attention == 'causal' and not ops.mq_causal:
+                raise B4CError('the masked-query last layer (rows=) of a causal encoder needs ops.mq_causal (B4C_MQ_CAUSAL=1; off by '
+                               'default): evaluate the full layer of a causal encoder and gather its rows '
+                               '(Encoder.rows_supported(dtype, training), Encoder.rows_route)')
             if a_rate > 0 and not ops.mq_attn_dropout:
                 raise B4CError('the masked-query last layer (rows=) has no attention dropout: evaluate the full layer while '
                                'training with attention_dropout_rate > 0 (Encoder.rows_supported(dtype, training))')
@@ -314,7 +317,7 @@ class EncoderLayer(nn.Module):
             out1 = ops.MQAttnBlockFn.apply(x2, midx, moff, cu, kp, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel,
                                            m.wv.bias, m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
                                            m._pk_qkv, m._pk_o, B, S, self.num_heads, self.rate if training else 0.0, s1, need_tape,
-                                           a_rate, s3)
+                                           a_rate, s3, *([True] if self.attention == 'causal' else []))
         else:
             out1 = ops.AttnBlockFn.apply(x2, key_pad, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel, m.wv.bias,
                                          m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta,
@@ -362,15 +365,22 @@ class Encoder(nn.Module):
 
     def rows_supported(self, x_dtype, training=False):
         """The masked-query form of the last layer: head depth 32 / 64 (b4c_attn_mq_*), at least one layer.  Those kernels have no
-        attention dropout: a training pass with attention_dropout_rate > 0 takes the full last layer and gathers its rows.  They
-        have no causal form either: a causal encoder always takes the full last layer."""
+        attention dropout: a training pass with attention_dropout_rate > 0 takes the full last layer and gathers its rows.  A causal
+        encoder takes the full last layer too: the kernels' causal form (b4c_attn_mq_*_ex) is behind a switch that is off by
+        default and that rows_route applies (ops.mq_causal), so this answer stays False for it."""
         if not self.enc_layers or self.attention == 'causal' or (training and self.attention_dropout_rate > 0):
             return False
         return (self.d_model // self.num_heads) in (32, 64) and self.d_model % 8 == 0
 
     def rows_route(self, x_dtype, training=False):
         """Does the last layer take its masked-query form in this pass?  rows_supported(...); with ops.mq_attn_dropout on, the same
-        shape conditions without the dropout exclusion (b4c_attn_mq_*_drop draws the full layer's masks for the query rows)."""
+        shape conditions without the dropout exclusion (b4c_attn_mq_*_drop draws the full layer's masks for the query rows).
+        A causal encoder: False, as rows_supported says, unless ops.mq_causal is on; then the shape conditions (b4c_attn_mq_*_ex with
+        B4C_ATTN_CAUSAL), and in a training pass with attention_dropout_rate > 0 ops.mq_attn_dropout on top, as above."""
+        if self.attention == 'causal':
+            if not ops.mq_causal or not self.enc_layers or (training and self.attention_dropout_rate > 0 and not ops.mq_attn_dropout):
+                return False
+            return (self.d_model // self.num_heads) in (32, 64) and self.d_model % 8 == 0
         if ops.mq_attn_dropout:
             return self.rows_supported(x_dtype, False)
         return self.rows_supported(x_dtype, training)

@@ -22,16 +22,35 @@
 // q = q_rows[r] - cu[b], the pitch S_arg is the launch's max_len -- the masks are those of the full layer's kernels for the same
 // rows.  q_rows is read for the rows below the sequence's query count only (an unused slot holds -1) and no address depends on
 // it.  The DROP = false instantiations are the kernels without it.
+//
+// CAUSAL (all four kernels): the last layer of a left-to-right encoder.  Query row r of sequence b sits at p = q_rows[r] - cu[b]
+// and sees the keys 0 .. p of its sequence: a key behind it is excluded outright (never a term of the softmax, weight and gradient
+// exactly zero), and the key loop of a query chunk / tile stops behind the largest position in it, so those keys are not even
+// read.  p is read as DROP reads it (rows below the sequence's query count, no address depends on it).  A slot with p < 0 (the -1
+// of an unused slot inside a range) sees no key: o = 0, lse = 0, dq = 0, nothing added to dk | dv.  The backward still writes every
+// token row of dkv: zeros behind the sequence's last query.  The CAUSAL = false instantiations are the kernels without it.
 #include <math.h>
 
 #include "mfma.h"
+
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+__device__ __forceinline__ int wave_imax(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ int wave_imin(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+    return v;
+}
 
 #define MQ 16            // query rows per chunk
 #define MQ_THREADS 256
 #define MQ_KB 128        // keys per block: TWO threads per key (lanes l and l + 32 of a wave own the two halves of its row)
 
 // LDS (dynamic): sQ [MQ][DH] f32 | sP [MQ][SP] f32 | sV [MQ_KB][DH] T          (SP = padded longest sequence)
-template <typename T, int DH, bool DROP>
+template <typename T, int DH, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__restrict__ q, int ld_q, const T *__restrict__ kv, int ld_kv,
                                                                  const uint8_t *__restrict__ key_pad, const int32_t *__restrict__ cu,
                                                                  const int32_t *__restrict__ moff, T *__restrict__ o, int ld_o,
@@ -54,19 +73,26 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
     const float inv_keep = DROP ? 1.0f / (1.0f - rate) : 1.0f;
     for (int mc = 0; mc < M; mc += MQ) {
         const int mq = min(MQ, M - mc);
+        // (CAUSAL) the keys this chunk reads: up to its largest query position
+        int kend = S;
+        if (CAUSAL) {
+            int pm = -1;
+            for (int m = 0; m < mq; ++m) pm = max(pm, q_rows[r0 + mc + m] - (int)tok0);
+            kend = min(S, pm + 1);
+        }
         // every global load of the first key block goes out before the first wait: the K half row of this thread's key, the
         // V block (raw, on its way to LDS), the chunk's query rows -- one memory round trip per item instead of three
         float kr0[HD];
 #pragma unroll
         for (int d = 0; d < HD; ++d) kr0[d] = 0.f;
-        if (kl < S) load_row<T, HD>(kv + (tok0 + kl) * ld_kv + h * DH + half * HD, kr0);
+        if (kl < kend) load_row<T, HD>(kv + (tok0 + kl) * ld_kv + h * DH + half * HD, kr0);
         float vraw[VCH][8];
 #pragma unroll
         for (int i = 0; i < VCH; ++i) {
             const int c = tid + i * MQ_THREADS, row = c / (DH / 8), part = c % (DH / 8);
 #pragma unroll
             for (int k = 0; k < 8; ++k) vraw[i][k] = 0.f;
-            if (row < S) Vec8<T>::load(kv + (tok0 + row) * ld_kv + dm + h * DH + part * 8, vraw[i]);
+            if (row < kend) Vec8<T>::load(kv + (tok0 + row) * ld_kv + dm + h * DH + part * 8, vraw[i]);
         }
         __syncthreads();                                      // the previous chunk's readers are done with sQ / sP / sV
         for (int c = tid; c < MQ * (DH / 8); c += MQ_THREADS) {       // rows past the chunk are zeros: the loops below run on
@@ -83,7 +109,7 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
         }
         __syncthreads();
         // phase 1: scores of every key against the chunk's queries (two threads per key, their half dots meet by a shuffle)
-        for (int k0 = 0; k0 < S; k0 += MQ_KB) {
+        for (int k0 = 0; k0 < kend; k0 += MQ_KB) {
             const int j = k0 + kl;
             float kr[HD];
 #pragma unroll
@@ -91,9 +117,9 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
             if (k0 > 0) {
 #pragma unroll
                 for (int d = 0; d < HD; ++d) kr[d] = 0.f;
-                if (j < S) load_row<T, HD>(kv + (tok0 + j) * ld_kv + h * DH + half * HD, kr);
+                if (j < kend) load_row<T, HD>(kv + (tok0 + j) * ld_kv + h * DH + half * HD, kr);
             }
-            const bool pad = j < S && key_pad && key_pad[tok0 + j];
+            const bool pad = j < kend && key_pad && key_pad[tok0 + j];
             for (int m0 = 0; m0 < mq; m0 += 4) {              // four independent dot -> shuffle chains in flight
                 float s4[4];
 #pragma unroll
@@ -104,7 +130,7 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
                 for (int u = 0; u < 4; ++u) {
                     float sc = s4[u] / sqrt_dk;
                     if (pad) sc += -1e9f;
-                    if (half == 0 && j < S) sP[(size_t)(m0 + u) * SP + j] = sc;
+                    if (half == 0 && j < kend) sP[(size_t)(m0 + u) * SP + j] = sc;
                 }
             }
         }
@@ -112,21 +138,24 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
         // softmax over the keys: query m of the chunk belongs to wave m % 4
         for (int m = wave; m < mq; m += 4) {
             float *row = sP + (size_t)m * SP;
+            // (CAUSAL) the row's softmax runs over its n visible keys; the scores behind them are never read and become exact zeros
+            const int n = CAUSAL ? min(max(q_rows[r0 + mc + m] - (int)tok0 + 1, 0), kend) : S;
             float mx = -INFINITY;
-            for (int j = lane; j < S; j += 64) mx = fmaxf(mx, row[j]);
+            for (int j = lane; j < n; j += 64) mx = fmaxf(mx, row[j]);
             mx = wave_max(mx);
             float sum = 0.f;
-            for (int j = lane; j < S; j += 64) sum += expf(row[j] - mx);
+            for (int j = lane; j < n; j += 64) sum += expf(row[j] - mx);
             sum = wave_sum(sum);
-            const float L = mx + logf(sum);
-            for (int j = lane; j < S; j += 64) row[j] = expf(row[j] - L);
-            for (int j = S + lane; j < SP; j += 64) row[j] = 0.f;     // (the loop below runs over whole groups of four keys)
+            float L = mx + logf(sum);
+            if (CAUSAL) { if (n == 0) L = 0.f; }              // a slot without a visible key: lse 0, every weight 0, o = 0
+            for (int j = lane; j < n; j += 64) row[j] = expf(row[j] - L);
+            for (int j = n + lane; j < SP; j += 64) row[j] = 0.f;     // (the loop below runs over whole groups of four keys)
             if (lane == 0) lse[(int64_t)(r0 + mc + m) * H + h] = L;
             if (DROP) {
                 // the row holds the undropped p (lse is theirs); the dropped ones lose their place in P V and 1 / (1 - rate) joins
                 // the output.  A lane takes four consecutive keys: one hash.  (The wave's own LDS writes are in order.)
                 const uint64_t drow = (uint64_t)blockIdx.x * S_arg + (uint32_t)(q_rows[r0 + mc + m] - (int)tok0);
-                for (int j = 4 * lane; j < S; j += 256) {
+                for (int j = 4 * lane; j < n; j += 256) {
                     const uint32_t kb = b4c_attn_keep4(seed, b4c_attn_ctr(drow, j, S_arg), thr);
                     f32x4 p4 = *reinterpret_cast<const f32x4 *>(row + j);
 #pragma unroll
@@ -140,18 +169,18 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
         float acc[QW];
 #pragma unroll
         for (int i = 0; i < QW; ++i) acc[i] = 0.f;
-        for (int k0 = 0; k0 < S; k0 += MQ_KB) {
+        for (int k0 = 0; k0 < kend; k0 += MQ_KB) {
             if (k0 > 0) {
                 __syncthreads();                              // the previous V block is consumed
                 for (int c = tid; c < MQ_KB * (DH / 8); c += MQ_THREADS) {
                     const int row = c / (DH / 8), part = c % (DH / 8);
                     float t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    if (k0 + row < S) Vec8<T>::load(kv + (tok0 + k0 + row) * ld_kv + dm + h * DH + part * 8, t);
+                    if (k0 + row < kend) Vec8<T>::load(kv + (tok0 + k0 + row) * ld_kv + dm + h * DH + part * 8, t);
                     Vec8<T>::store(sV + row * DH + part * 8, t);          // rows past the sequence: zeros
                 }
                 __syncthreads();
             }
-            const int nk = min(MQ_KB, S - k0);
+            const int nk = min(MQ_KB, kend - k0);
             if (lane < DH) {
                 // all reads of a step are requested before the first is used (the compiler waits once per group)
                 const int nk4 = (nk + 3) & ~3;                // rows of sV and columns of sP past the sequence are zeros
@@ -179,8 +208,8 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_fwd_kernel(const T *__rest
     }
 }
 
-// LDS (dynamic): sQ [MQ][DH] | sG [MQ][DH] | sLse [MQ] | sDelta [MQ] | sDS [MQ][MQ_KB] (f32) | sK [MQ_KB][DH] T | DROP: sPos [MQ] i32
-template <typename T, int DH, bool DROP>
+// LDS (dynamic): sQ [MQ][DH] | sG [MQ][DH] | sLse [MQ] | sDelta [MQ] | sDS [MQ][MQ_KB] (f32) | sK [MQ_KB][DH] T | DROP or CAUSAL: sPos [MQ] i32
+template <typename T, int DH, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__restrict__ q, int ld_q, const T *__restrict__ kv, int ld_kv,
                                                                  const uint8_t *__restrict__ key_pad, const int32_t *__restrict__ cu,
                                                                  const int32_t *__restrict__ moff, const T *__restrict__ o, int ld_o,
@@ -196,7 +225,7 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
     float *sDelta = sLse + MQ;
     float *sDS = sDelta + MQ;
     T *sK = reinterpret_cast<T *>(sDS + MQ * MQ_KB);
-    int32_t *sPos = reinterpret_cast<int32_t *>(sK + MQ_KB * DH);      // (DROP only) the chunk's query positions
+    int32_t *sPos = reinterpret_cast<int32_t *>(sK + MQ_KB * DH);      // (DROP / CAUSAL only) the chunk's query positions
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, kl = wave * 32 + (lane & 31);
     const int b = blockIdx.x / H, h = blockIdx.x % H, dm = H * DH;
@@ -215,13 +244,21 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
         return;
     }
     const int nchunk = (M + MQ - 1) / MQ;
+    // (CAUSAL) the sequence's largest query position: the keys behind it are not read, their dk | dv rows leave as the zeros they
+    // start as
+    int pall = 0;
+    if (CAUSAL) {
+        int pm = -1;
+        for (int i = lane; i < M; i += 64) pm = max(pm, q_rows[r0 + i] - (int)tok0);
+        pall = wave_imax(pm);
+    }
     for (int k0 = 0; k0 < S; k0 += MQ_KB) {
         const int j = k0 + kl;
         const bool live = j < S;
         float kr[HD], vr[HD], dk[HD], dv[HD];
 #pragma unroll
         for (int d = 0; d < HD; ++d) { kr[d] = 0.f; vr[d] = 0.f; dk[d] = 0.f; dv[d] = 0.f; }
-        if (live) {
+        if (CAUSAL ? (live && j <= pall) : live) {
             load_row<T, HD>(kv + (tok0 + j) * ld_kv + h * DH + half * HD, kr);
             load_row<T, HD>(kv + (tok0 + j) * ld_kv + dm + h * DH + half * HD, vr);
         }
@@ -230,6 +267,12 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
         store_row<T, HD>(sK + kl * DH + half * HD, kr);          // (zeros for the slots past the sequence)
         for (int ci = 0; ci < nchunk; ++ci) {
             const int mc = ci * MQ, mq = min(MQ, M - mc);
+            if (CAUSAL) {
+                // a key block behind every query of the chunk adds nothing to it (workgroup-uniform; the first block always runs: it
+                // writes the chunk's dq rows)
+                const int cm = wave_imax(lane < mq ? q_rows[r0 + mc + lane] - (int)tok0 : -1);
+                if (k0 > 0 && k0 > cm) continue;
+            }
             __syncthreads();                                  // the previous chunk's dq phase is done with sQ / sG / sDS
             for (int c = tid; c < MQ * (DH / 8); c += MQ_THREADS) {   // rows past the chunk: zeros (q, dO) -> dS = dV = dK terms 0
                 const int m = c / (DH / 8), part = c % (DH / 8);
@@ -253,7 +296,8 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
                 if (part == 0) {
                     sDelta[m] = pd;
                     sLse[m] = m < mq ? lse[(int64_t)(r0 + mc + m) * H + h] : INFINITY;     // p = exp(s - inf) = 0 for the zero rows
-                    if (DROP) sPos[m] = m < mq ? q_rows[r0 + mc + m] - (int)tok0 : 0;
+                    if (DROP && !CAUSAL) sPos[m] = m < mq ? q_rows[r0 + mc + m] - (int)tok0 : 0;
+                    if (CAUSAL) sPos[m] = m < mq ? q_rows[r0 + mc + m] - (int)tok0 : -1;
                 }
             }
             __syncthreads();
@@ -264,7 +308,7 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
                 sc += __shfl_xor(sc, 32);
                 dp += __shfl_xor(dp, 32);
                 float p = 0.f, ds = 0.f;
-                if (live && !pad) {                           // a padded key has p == 0 exactly (exp(-1e9 - lse))
+                if (live && !pad && (!CAUSAL || j <= sPos[m])) {     // a padded key has p == 0 exactly (exp(-1e9 - lse)), one behind the query too
                     p = expf(sc / sqrt_dk - sLse[m]);
                     if (DROP) {
                         // dS = P o (keep / (1 - rate) * dP~ - delta) with the undropped P; dV takes the dropped, rescaled P~
@@ -340,7 +384,7 @@ __global__ void __launch_bounds__(MQ_THREADS) attn_mq_bwd_kernel(const T *__rest
 //   double buffer, for the transposed fragment reads).  The next tile's K and V loads are in flight during a tile.
 // ------------------------------------------------------------------------------------------------------------------
 #define MQ_WAVES 4
-template <int DH, bool HAS_PAD, bool DROP>
+template <int DH, bool HAS_PAD, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(const bf16_t *__restrict__ q, int ld_q, const bf16_t *__restrict__ kv,
                                                                          int ld_kv, const uint8_t *__restrict__ key_pad,
                                                                          const int32_t *__restrict__ cu, const int32_t *__restrict__ moff,
@@ -370,6 +414,16 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
         // (DROP) the lane part of the hash counter: this lane's query position times S4 / 4
         uint32_t dq = 0;
         if (DROP) { if (qvalid) dq = (uint32_t)(q_rows[r0 + qrow] - (int)tok0) * (b4c_attn_s4(S_arg) >> 2); }
+        // (CAUSAL) this lane's query position (-1: no visible key), the tile's largest (its key loop ends there) and the smallest
+        // valid one (the tiles in front of it need no per-key test)
+        int pos = -1, pmax = 0, pmin = 0;
+        if (CAUSAL) {
+            if (qvalid) pos = q_rows[r0 + qrow] - (int)tok0;
+            pmax = wave_imax(pos);
+            pmin = wave_imin(pos < 0 ? 0x7fffffff : pos);
+        }
+        const int nkt_q = CAUSAL ? min(nkt, (pmax >> 5) + 1) : nkt;       // (pmax = -1: no tile)
+        const int krows = CAUSAL ? min(S, max(pmax, 0) + 1) : S;           // rows behind them read as zeros
         bf16x8 qf[NKS];
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
@@ -379,7 +433,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
         }
         // K / V rows through buffer loads: one descriptor for the sequence's rows (reads past its end return zeros), 32-bit
         // per-lane offsets -- no 64-bit address pair per load in the register file
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t *>(kbase), 0, (unsigned)((int64_t)S * ld_kv * 2 - (int64_t)hh * DH * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t *>(kbase), 0, (unsigned)((int64_t)krows * ld_kv * 2 - (int64_t)hh * DH * 2), 0x00020000);
         const int koff = (r * ld_kv + hf * 8) * 2;                        // this lane's K row, its half of a k-step
         const int voff0 = ((lane / CH) * ld_kv + dm + (lane % CH) * 8) * 2;     // V chunk i: rows (lane + 64 i) / CH
         const int tile_bytes = 32 * ld_kv * 2;
@@ -400,7 +454,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
         for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int t = 0; t < 16; ++t) oacc[dt][t] = 0.f;
-        for (int kt = 0; kt < nkt; ++kt) {
+        for (int kt = 0; kt < nkt_q; ++kt) {
             char *vt = sV + (kt & 1) * (32 * KSTR);
 #pragma unroll
             for (int i = 0; i < VC; ++i) {
@@ -413,18 +467,19 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[ks]), qf[ks], acc, 0, 0, 0);
-            if (kt + 1 < nkt) {                                // in flight during this tile's softmax and P V
+            if (kt + 1 < nkt_q) {                              // in flight during this tile's softmax and P V
                 fetch_k(kt + 1, kf);
                 fetch_v(kt + 1, rv);
             }
             float tm = -INFINITY;
             const bool edge = (kt + 1) * 32 > S;              // keys past the sequence in this tile (wave-uniform)
-            if (HAS_PAD || edge) {
+            const bool diag = CAUSAL && kt * 32 + 31 > pmin;  // keys behind one of the tile's queries (wave-uniform)
+            if (HAS_PAD || edge || diag) {
 #pragma unroll
                 for (int t = 0; t < 16; ++t) {
                     const int key = kt * 32 + rowmap(t, hf);
                     float madd = 0.f;
-                    if (key >= S) madd = -INFINITY;
+                    if (key >= S || (CAUSAL && key > pos)) madd = -INFINITY;
                     else if (HAS_PAD && key_pad[tok0 + key]) madd = -1e9f * 1.4426950408889634f;
                     acc[t] = __builtin_fmaf(acc[t], scale2, madd);
                     tm = fmaxf(tm, acc[t]);
@@ -485,6 +540,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
         l += __shfl_xor(l, 32);
         if (qvalid) {
             const float inv = DROP ? (1.0f / (1.0f - rate)) / l : 1.0f / l;
+            const bool none = CAUSAL && pos < 0;              // a slot without a visible key: o = 0, lse = 0 (whatever l is)
             bf16_t *orow = o + (int64_t)(r0 + qrow) * ld_o + hh * DH;
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt)
@@ -492,10 +548,10 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
                 for (int tq = 0; tq < 4; ++tq) {
                     bf16x4 w;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(oacc[dt][4 * tq + j] * inv);
+                    for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(none ? 0.f : oacc[dt][4 * tq + j] * inv);
                     *reinterpret_cast<bf16x4 *>(orow + dt * 32 + 8 * tq + 4 * hf) = w;
                 }
-            if (hf == 0) lse[(int64_t)(r0 + qrow) * H + hh] = (m + __log2f(l)) * 0.6931471805599453f;
+            if (hf == 0) lse[(int64_t)(r0 + qrow) * H + hh] = none ? 0.f : (m + __log2f(l)) * 0.6931471805599453f;
         }
     }
 }
@@ -508,9 +564,12 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 3) attn_mq_fwd_mfma_kernel(cons
 //   tiles).  dK / dV of a tile leave as 8-byte pieces of their rows.  More than 32 query rows: further passes that add to
 //   the dK / dV rows already written.
 // LDS per wave: sQ | sG [32][KSTR] (the query tile and its dO), sK [32][KSTR] (current key tile), sDS [32][TSTR], lse2 / delta;
-// DROP: the tile's 32 query positions behind them (sPos): keep_tile_bwd (mfma.h) takes the query of tile row i at sPos[i].
+// DROP / CAUSAL: the tile's 32 query positions behind them (sPos): keep_tile_bwd (mfma.h) takes the query of tile row i at sPos[i].
+// CAUSAL: a query pass runs over the key tiles up to its largest position.  The dK / dV rows of the tiles the FIRST pass leaves out
+// are zeroed in front of it, by the lane and in the pieces that write and re-read them later: a later pass only ever adds to rows
+// that the first pass or this zeroing has written.
 // ------------------------------------------------------------------------------------------------------------------
-template <int DH, bool HAS_PAD, bool DROP>
+template <int DH, bool HAS_PAD, bool DROP, bool CAUSAL>
 __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(const bf16_t *__restrict__ q, int ld_q, const bf16_t *__restrict__ kv,
                                                                          int ld_kv, const uint8_t *__restrict__ key_pad,
                                                                          const int32_t *__restrict__ cu, const int32_t *__restrict__ moff,
@@ -522,7 +581,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KSTR = DH * 2 + 16, TSTR = 32 * 2 + 16;
     constexpr int NKS = DH / 16, NDT = DH / 32, CH = DH / 8, VC = 32 * CH / 64;
-    constexpr int WBYTES = 3 * 32 * KSTR + 32 * TSTR + (DROP ? 3 : 2) * 32 * 4;
+    constexpr int WBYTES = 3 * 32 * KSTR + 32 * TSTR + ((DROP || CAUSAL) ? 3 : 2) * 32 * 4;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31, hf = lane >> 5, li = lane & 15, g = lane >> 4;
     char *sQ = smem + wave * WBYTES;
     char *sG = sQ + 32 * KSTR;
@@ -530,7 +589,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
     char *sDS = sK + 32 * KSTR;
     float *sLse = reinterpret_cast<float *>(sDS + 32 * TSTR);
     float *sDelta = sLse + 32;
-    int32_t *sPos = reinterpret_cast<int32_t *>(sDelta + 32);   // (DROP only)
+    int32_t *sPos = reinterpret_cast<int32_t *>(sDelta + 32);   // (DROP / CAUSAL only)
     const int item = blockIdx.x * MQ_WAVES + wave;
     if (item >= n_items) return;                              // (no workgroup barrier anywhere below)
     const int b = item / H, hh = item % H, dm = H * DH;
@@ -557,9 +616,28 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
     const int koff0 = ((lane / CH) * ld_kv + (lane % CH) * 8) * 2;            // K chunk i: rows (lane + 64 i) / CH
     const int voff = (r * ld_kv + dm + hf * 8) * 2;                            // this lane's V row (as the B operand of dP)
     const int tile_bytes = 32 * ld_kv * 2;
+    if (CAUSAL) {
+        const int p0 = wave_imax((lane < 32 && lane < M) ? q_rows[r0 + lane] - (int)tok0 : -1);
+        for (int kt = min(nkt, (p0 >> 5) + 1); kt < nkt; ++kt) {
+            const int key = kt * 32 + r;
+            if (key < S) {
+                bf16_t *krow = dkbase + (int64_t)key * ld_dkv;
+                const bf16x4 z = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+#pragma unroll
+                for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+                    for (int tq = 0; tq < 4; ++tq) {
+                        bf16_t *pk = krow + dt * 32 + 8 * tq + 4 * hf;
+                        *reinterpret_cast<bf16x4 *>(pk) = z;
+                        *reinterpret_cast<bf16x4 *>(pk + dm) = z;
+                    }
+            }
+        }
+    }
     for (int q0 = 0; q0 < M; q0 += 32) {
         const int qrow = q0 + r;
         const bool qvalid = qrow < M;
+        int pmax = 0, pmin = 0;                               // (CAUSAL) the largest and smallest position of the tile's query rows
         // ---- the query tile: Q and dO rows -> LDS (row-major, zero rows past M), delta = rowsum(dO * O), lse in log2 units
         {
             float pd = 0.f;
@@ -582,8 +660,15 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
                 if (part == 0) sDelta[row] = pd;
             }
             if (lane < 32) sLse[lane] = (q0 + lane < M) ? lse[(int64_t)(r0 + q0 + lane) * H + hh] * 1.4426950408889634f : INFINITY;
-            if (DROP) { if (lane < 32) sPos[lane] = (q0 + lane < M) ? q_rows[r0 + q0 + lane] - (int)tok0 : 0; }
+            if (DROP && !CAUSAL) { if (lane < 32) sPos[lane] = (q0 + lane < M) ? q_rows[r0 + q0 + lane] - (int)tok0 : 0; }
+            if (CAUSAL) {
+                const int pp = (lane < 32 && q0 + lane < M) ? q_rows[r0 + q0 + lane] - (int)tok0 : -1;
+                if (lane < 32) sPos[lane] = pp;
+                pmax = wave_imax(pp);
+                pmin = wave_imin((lane < 32 && q0 + lane < M) ? pp : 0x7fffffff);     // (a slot without a visible key counts: -1)
+            }
         }
+        const int nkt_q = CAUSAL ? min(nkt, (pmax >> 5) + 1) : nkt;       // (pmax = -1: no tile)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         bf16x8 qa[NKS], ga[NKS];                              // A operands: this lane's query row (half a k-step each)
@@ -600,6 +685,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
 #pragma unroll
             for (int j = 0; j < 4; ++j) { lq[4 * tq + j] = a4[j]; dl[4 * tq + j] = b4[j]; }
         }
+
         f32x16 dqa[NDT];
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt)
@@ -613,7 +699,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
             for (int ks = 0; ks < NKS; ++ks) vb[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + kt * tile_bytes + ks * 32, 0, 0);
         };
         fetch(0);
-        for (int kt = 0; kt < nkt; ++kt) {
+        for (int kt = 0; kt < nkt_q; ++kt) {
             const int key = kt * 32 + r;
 #pragma unroll
             for (int i = 0; i < VC; ++i) {
@@ -627,7 +713,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
             if (HAS_PAD) { if (key < S && key_pad[tok0 + key]) madd = -1e9f * 1.4426950408889634f; }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
-            if (kt + 1 < nkt) fetch(kt + 1);                  // in flight during this tile
+            if (kt + 1 < nkt_q) fetch(kt + 1);                // in flight during this tile
             f32x16 sa, pa;
 #pragma unroll
             for (int t = 0; t < 16; ++t) { sa[t] = 0.f; pa[t] = 0.f; }
@@ -639,10 +725,25 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
             }
             float pv[16], dsv[16];
             // dropout: dV takes the dropped, rescaled P~; dS = P o (keep / (1 - rate) * dP~ - delta) with the undropped P
+            // (CAUSAL) bit t: this lane's key is visible to the query of register t.  Only a tile that reaches behind one of its query
+            // rows reads their positions (wave-uniform); the tile rows past M have zero q / dO rows and lse = inf: p = 0 as ever
+            uint32_t vis = 0xffffu;
+            if (CAUSAL) {
+                if (kt * 32 + 31 > pmin) {
+                    vis = 0u;
+#pragma unroll
+                    for (int tq = 0; tq < 4; ++tq) {
+                        const i32x4 c4 = *reinterpret_cast<const i32x4 *>(sPos + 8 * tq + 4 * hf);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) vis |= (key <= c4[j] ? 1u : 0u) << (4 * tq + j);
+                    }
+                }
+            }
             const uint32_t km = DROP ? keep_tile_bwd(seed, attn_ctr_base(item, S_arg), S_arg, [sPos](int i) { return sPos[i]; }, kt * 32, thr, r, hf) : 0u;
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
-                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[t], scale2, madd - lq[t]));
+                float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sa[t], scale2, madd - lq[t]));
+                if (CAUSAL) p = ((vis >> t) & 1u) ? p : 0.f;        // a key behind the query: exactly 0, and so is dS
                 if (DROP) {
                     const bool kp = (km >> t) & 1u;
                     pv[t] = kp ? p * inv_keep : 0.f;
@@ -727,7 +828,7 @@ __global__ void __launch_bounds__(64 * MQ_WAVES, 2) attn_mq_bwd_mfma_kernel(cons
 }
 
 static size_t mq_fwd_lds(int SP, int dh, int esz) { return (size_t)MQ * dh * 4 + (size_t)MQ * SP * 4 + (size_t)MQ_KB * dh * esz; }
-static size_t mq_bwd_lds(int dh, int esz, bool drop) {
+static size_t mq_bwd_lds(int dh, int esz, bool drop /* or causal: sPos */) {
     return (size_t)2 * MQ * dh * 4 + 2 * MQ * 4 + (size_t)MQ * MQ_KB * 4 + (size_t)MQ_KB * dh * esz + (drop ? MQ * 4 : 0);
 }
 
@@ -749,10 +850,18 @@ static int mq_check_drop(const char *who, const int32_t *q_rows, float rate) {
     return B4C_OK;
 }
 
-// rate == 0 launches the DROP = false instantiations: the kernels of the entry points without dropout
+// the *_ex entry points: B4C_ATTN_CAUSAL is the one flag bit, and it needs the query rows' token rows at any rate
+static int mq_check_flags(const char *who, const int32_t *q_rows, uint32_t flags) {
+    B4C_REQUIRE((flags & ~B4C_ATTN_CAUSAL) == 0, "%s: unknown flag bits 0x%x", who, flags & ~B4C_ATTN_CAUSAL);
+    B4C_REQUIRE(!(flags & B4C_ATTN_CAUSAL) || q_rows, "%s: B4C_ATTN_CAUSAL needs q_rows", who);
+    return B4C_OK;
+}
+
+// rate == 0 launches the DROP = false instantiations: the kernels of the entry points without dropout; causal == false the
+// CAUSAL = false ones: the kernels of the entry points without flags
 static int mq_fwd_any(const char *who, const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
                       const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype, void *stream,
-                      const int32_t *q_rows, float rate, uint64_t seed) {
+                      const int32_t *q_rows, float rate, uint64_t seed, bool causal) {
     const int rc = mq_check(who, q, kv, cu_seqlens, q_offsets, ld_q, ld_kv, B, max_len, H, dh, dtype);
     if (rc != B4C_OK) return rc;
     B4C_REQUIRE(o && lse && ld_o >= H * dh && ld_o % 8 == 0, "%s: output", who);
@@ -763,19 +872,19 @@ static int mq_fwd_any(const char *who, const void *q, int ld_q, const void *kv, 
         const int n_items = B * H;
         const size_t shm_m = (size_t)MQ_WAVES * 2 * 32 * (dh * 2 + 16);
         const int grid = (n_items + MQ_WAVES - 1) / MQ_WAVES;
-        b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(key_pad != nullptr, [&](auto PP) { b4c_by_bool(rate != 0.f, [&](auto DR) {
-            attn_mq_fwd_mfma_kernel<DH(), PP(), DR()><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens,
+        b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(key_pad != nullptr, [&](auto PP) { b4c_by_bool(rate != 0.f, [&](auto DR) { b4c_by_bool(causal, [&](auto CA) {
+            attn_mq_fwd_mfma_kernel<DH(), PP(), DR(), CA()><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens,
                                                                                   q_offsets, (bf16_t *)o, ld_o, lse, H, n_items, 1.0f / sq, q_rows, max_len, rate, seed);
-        }); }); });
+        }); }); }); });
         return b4c_check_launch(who);
     }
     const size_t shm = mq_fwd_lds(SP, dh, sizeof(float));
     B4C_REQUIRE(shm <= 160 * 1024, "%s: max_len %d needs %zu bytes of LDS", who, max_len, shm);
-    b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) {
-        b4c_allow_lds(attn_mq_fwd_kernel<float, DH(), DR()>, shm);
-        attn_mq_fwd_kernel<float, DH(), DR()><<<B * H, MQ_THREADS, shm, st>>>((const float *)q, ld_q, (const float *)kv, ld_kv, key_pad, cu_seqlens, q_offsets,
+    b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) { b4c_by_bool(causal, [&](auto CA) {
+        b4c_allow_lds(attn_mq_fwd_kernel<float, DH(), DR(), CA()>, shm);
+        attn_mq_fwd_kernel<float, DH(), DR(), CA()><<<B * H, MQ_THREADS, shm, st>>>((const float *)q, ld_q, (const float *)kv, ld_kv, key_pad, cu_seqlens, q_offsets,
                                                                        (float *)o, ld_o, lse, H, SP, sq, q_rows, max_len, rate, seed);
-    }); });
+    }); }); });
     return b4c_check_launch(who);
 }
 
@@ -783,7 +892,7 @@ extern "C" int b4c_attn_mq_fwd(const void *q, int ld_q, const void *kv, int ld_k
                                const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype,
                                void *stream) {
     return mq_fwd_any("attn_mq_fwd", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, lse, B, max_len, H, dh, dtype, stream,
-                      nullptr, 0.f, 0);
+                      nullptr, 0.f, 0, false);
 }
 
 extern "C" int b4c_attn_mq_fwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
@@ -792,13 +901,23 @@ extern "C" int b4c_attn_mq_fwd_drop(const void *q, int ld_q, const void *kv, int
     const int rc = mq_check_drop("attn_mq_fwd_drop", q_rows, dropout_rate);
     if (rc != B4C_OK) return rc;
     return mq_fwd_any("attn_mq_fwd_drop", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, lse, B, max_len, H, dh, dtype, stream,
-                      q_rows, dropout_rate, seed);
+                      q_rows, dropout_rate, seed, false);
+}
+
+// b4c_attn_mq_ex.h: the *_drop entry point with flags (0: its very launches)
+extern "C" int b4c_attn_mq_fwd_ex(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                                  const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype,
+                                  void *stream, const int32_t *q_rows, float dropout_rate, uint64_t seed, uint32_t flags) {
+    if (int rc = mq_check_drop("attn_mq_fwd_ex", q_rows, dropout_rate)) return rc;
+    if (int rc = mq_check_flags("attn_mq_fwd_ex", q_rows, flags)) return rc;
+    return mq_fwd_any("attn_mq_fwd_ex", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, lse, B, max_len, H, dh, dtype, stream,
+                      q_rows, dropout_rate, seed, (flags & B4C_ATTN_CAUSAL) != 0);
 }
 
 static int mq_bwd_any(const char *who, const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
                       const int32_t *q_offsets, const void *o, int ld_o, const void *d_o, int ld_do, const float *lse, void *dq, int ld_dq,
                       void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream, const int32_t *q_rows, float rate,
-                      uint64_t seed) {
+                      uint64_t seed, bool causal) {
     const int rc = mq_check(who, q, kv, cu_seqlens, q_offsets, ld_q, ld_kv, B, max_len, H, dh, dtype);
     if (rc != B4C_OK) return rc;
     B4C_REQUIRE(o && d_o && lse && dq && dkv, "%s: null pointer", who);
@@ -809,22 +928,22 @@ static int mq_bwd_any(const char *who, const void *q, int ld_q, const void *kv, 
     if (dtype == B4C_BF16) {      // matrix-core form, one wave per (sequence, head)
         const int n_items = B * H, kstr = dh * 2 + 16;
         const int grid = (n_items + MQ_WAVES - 1) / MQ_WAVES;
-        b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(key_pad != nullptr, [&](auto PP) { b4c_by_bool(rate != 0.f, [&](auto DR) {
-            const size_t shm_m = (size_t)MQ_WAVES * (3 * 32 * kstr + 32 * (32 * 2 + 16) + (DR() ? 3 : 2) * 32 * 4);
-            b4c_allow_lds(attn_mq_bwd_mfma_kernel<DH(), PP(), DR()>, shm_m);
-            attn_mq_bwd_mfma_kernel<DH(), PP(), DR()><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens,
+        b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(key_pad != nullptr, [&](auto PP) { b4c_by_bool(rate != 0.f, [&](auto DR) { b4c_by_bool(causal, [&](auto CA) {
+            const size_t shm_m = (size_t)MQ_WAVES * (3 * 32 * kstr + 32 * (32 * 2 + 16) + ((DR() || CA()) ? 3 : 2) * 32 * 4);
+            b4c_allow_lds(attn_mq_bwd_mfma_kernel<DH(), PP(), DR(), CA()>, shm_m);
+            attn_mq_bwd_mfma_kernel<DH(), PP(), DR(), CA()><<<grid, 64 * MQ_WAVES, shm_m, st>>>((const bf16_t *)q, ld_q, (const bf16_t *)kv, ld_kv, key_pad, cu_seqlens,
                 q_offsets, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dq, ld_dq, (bf16_t *)dkv, ld_dkv, H, n_items, 1.0f / sq,
                 q_rows, max_len, rate, seed);
-        }); }); });
+        }); }); }); });
         return b4c_check_launch(who);
     }
-    b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) {
-        const size_t shm = mq_bwd_lds(dh, sizeof(float), DR());
-        b4c_allow_lds(attn_mq_bwd_kernel<float, DH(), DR()>, shm);
-        attn_mq_bwd_kernel<float, DH(), DR()><<<B * H, MQ_THREADS, shm, st>>>((const float *)q, ld_q, (const float *)kv, ld_kv, key_pad, cu_seqlens, q_offsets,
+    b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) { b4c_by_bool(causal, [&](auto CA) {
+        const size_t shm = mq_bwd_lds(dh, sizeof(float), DR() || CA());
+        b4c_allow_lds(attn_mq_bwd_kernel<float, DH(), DR(), CA()>, shm);
+        attn_mq_bwd_kernel<float, DH(), DR(), CA()><<<B * H, MQ_THREADS, shm, st>>>((const float *)q, ld_q, (const float *)kv, ld_kv, key_pad, cu_seqlens, q_offsets,
                                                                        (const float *)o, ld_o, (const float *)d_o, ld_do, lse, (float *)dq, ld_dq,
                                                                        (float *)dkv, ld_dkv, H, sq, q_rows, max_len, rate, seed);
-    }); });
+    }); }); });
     return b4c_check_launch(who);
 }
 
@@ -832,7 +951,7 @@ extern "C" int b4c_attn_mq_bwd(const void *q, int ld_q, const void *kv, int ld_k
                                const int32_t *q_offsets, const void *o, int ld_o, const void *d_o, int ld_do, const float *lse,
                                void *dq, int ld_dq, void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream) {
     return mq_bwd_any("attn_mq_bwd", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, d_o, ld_do, lse, dq, ld_dq, dkv, ld_dkv, B,
-                      max_len, H, dh, dtype, stream, nullptr, 0.f, 0);
+                      max_len, H, dh, dtype, stream, nullptr, 0.f, 0, false);
 }
 
 extern "C" int b4c_attn_mq_bwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
@@ -842,5 +961,15 @@ extern "C" int b4c_attn_mq_bwd_drop(const void *q, int ld_q, const void *kv, int
     const int rc = mq_check_drop("attn_mq_bwd_drop", q_rows, dropout_rate);
     if (rc != B4C_OK) return rc;
     return mq_bwd_any("attn_mq_bwd_drop", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, d_o, ld_do, lse, dq, ld_dq, dkv, ld_dkv,
-                      B, max_len, H, dh, dtype, stream, q_rows, dropout_rate, seed);
+                      B, max_len, H, dh, dtype, stream, q_rows, dropout_rate, seed, false);
+}
+
+extern "C" int b4c_attn_mq_bwd_ex(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                                  const int32_t *q_offsets, const void *o, int ld_o, const void *d_o, int ld_do, const float *lse,
+                                  void *dq, int ld_dq, void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream,
+                                  const int32_t *q_rows, float dropout_rate, uint64_t seed, uint32_t flags) {
+    if (int rc = mq_check_drop("attn_mq_bwd_ex", q_rows, dropout_rate)) return rc;
+    if (int rc = mq_check_flags("attn_mq_bwd_ex", q_rows, flags)) return rc;
+    return mq_bwd_any("attn_mq_bwd_ex", q, ld_q, kv, ld_kv, key_pad, cu_seqlens, q_offsets, o, ld_o, d_o, ld_do, lse, dq, ld_dq, dkv, ld_dkv,
+                      B, max_len, H, dh, dtype, stream, q_rows, dropout_rate, seed, (flags & B4C_ATTN_CAUSAL) != 0);
 }

@@ -894,20 +894,34 @@ def _tied_table_steps_whole(table):
         lz.all_rows = True
 
 
-def _attn_mq_drop(q_rows, rate):
+def _attn_mq_drop(q_rows, rate, causal=False):
     rate = _attn_rate(rate)
     if rate > 0 and q_rows is None:
         raise ValueError('attention dropout in the masked-query kernels needs q_rows (the token row of each query row)')
+    if causal and q_rows is None:
+        raise ValueError('causal attention in the masked-query kernels needs q_rows (the token row of each query row)')
     return rate
 
 
-def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None, q_rows=None, rate=0.0, seed=0):
+def _attn_mq_pairs(R, max_len, causal):
+    """(query, key) pairs of a masked-query launch for the work hint: rec_hints['sum_q_len'] (every query row against its sequence),
+    for a causal launch rec_hints['sum_q_visible'] (the sum of p + 1 over the query rows) when the caller gives it; R x max_len
+    is the upper bound of both"""
+    if causal and 'sum_q_visible' in rec_hints:
+        return rec_hints['sum_q_visible']
+    return rec_hints.get('sum_q_len', R * max_len)
+
+
+def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None, q_rows=None, rate=0.0, seed=0, causal=False):
     """Attention of a few query rows per sequence against all of its keys (b4c_attn_mq_fwd_drop; rate 0 launches the kernels of
     b4c_attn_mq_fwd).
     q [R, H*dh]; kv [T, 2*H*dh] (k | v); cu [B+1] token offsets; moff [B+1] query-row offsets -> (o [R, H*dh], lse [R, H]).
     rate > 0: dropout on the attention probabilities with the masks attn_fwd(..., rate, seed) draws for the
-    token rows q_rows [R] (int32; an unused row holds -1): b4c_attn_keep(seed, b, h, q_rows[r] - cu[b], k, H, max_len, rate)."""
-    rate = _attn_mq_drop(q_rows, rate)
+    token rows q_rows [R] (int32; an unused row holds -1): b4c_attn_keep(seed, b, h, q_rows[r] - cu[b], k, H, max_len, rate).
+    causal (b4c_attn_mq_fwd_ex with B4C_ATTN_CAUSAL; needs q_rows): query row r sees the keys 0 .. q_rows[r] - cu[b] of its
+    sequence, the rows attn_fwd(..., causal=True) computes at those positions; a row inside a range whose q_rows is below cu[b]
+    (-1) sees none: o = 0, lse = 0.  Without it the calls are the ones made before there was such a form."""
+    rate = _attn_mq_drop(q_rows, rate, causal)
     R = q.shape[0]
     # rows outside every [moff[b], moff[b+1]) range (the unused tail of the sync-free form) are not written: zeros, not garbage
     o = zeros(R, H * dh, dtype=q.dtype, device=q.device)
@@ -916,16 +930,22 @@ def attn_mq_fwd(q, kv, cu, moff, B, max_len, H, dh, key_pad=None, q_rows=None, r
         return o, lse
     es = q.element_size()
     # algorithmic work: every query row against the keys of its own sequence (host hint; R x max_len is an upper bound)
-    with _record('attn_mq_fwd', kv.shape[0] * 2 * H * dh * es + 2 * R * H * dh * es, 4 * rec_hints.get('sum_q_len', R * max_len) * H * dh):
-        L.check(L.lib().b4c_attn_mq_fwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
-                                             _p(lse), B, max_len, H, dh, dt_code(q.dtype), _st(), _p(q_rows), rate, seed), 'attn_mq_fwd_drop')
+    with _record('attn_mq_fwd', kv.shape[0] * 2 * H * dh * es + 2 * R * H * dh * es, 4 * _attn_mq_pairs(R, max_len, causal) * H * dh):
+        if causal:
+            L.check(L.lib().b4c_attn_mq_fwd_ex(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
+                                               _p(lse), B, max_len, H, dh, dt_code(q.dtype), _st(), _p(q_rows), rate, seed, L.ATTN_CAUSAL),
+                    'attn_mq_fwd_ex')
+        else:
+            L.check(L.lib().b4c_attn_mq_fwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
+                                                 _p(lse), B, max_len, H, dh, dt_code(q.dtype), _st(), _p(q_rows), rate, seed), 'attn_mq_fwd_drop')
     return o, lse
 
 
-def attn_mq_bwd(q, kv, cu, moff, o, d_o, lse, B, max_len, H, dh, key_pad=None, q_rows=None, rate=0.0, seed=0):
-    """-> (dq [R, H*dh], dkv [T, 2*H*dh]); every token row of dkv is written (zeros where no query reads the sequence).
-    q_rows, rate, seed: those of the forward (attn_mq_fwd); o is the forward's output, dropped probabilities included."""
-    rate = _attn_mq_drop(q_rows, rate)
+def attn_mq_bwd(q, kv, cu, moff, o, d_o, lse, B, max_len, H, dh, key_pad=None, q_rows=None, rate=0.0, seed=0, causal=False):
+    """-> (dq [R, H*dh], dkv [T, 2*H*dh]); every token row of dkv is written (zeros where no query reads the sequence; causal:
+    also behind a sequence's last query position).
+    q_rows, rate, seed, causal: those of the forward (attn_mq_fwd); o is the forward's output, dropped probabilities included."""
+    rate = _attn_mq_drop(q_rows, rate, causal)
     R = q.shape[0]
     dq = zeros(q.shape[0], q.shape[1], dtype=q.dtype, device=q.device)
     if R == 0:                 # no query row anywhere: no key or value receives a gradient from this layer
@@ -934,10 +954,15 @@ def attn_mq_bwd(q, kv, cu, moff, o, d_o, lse, B, max_len, H, dh, key_pad=None, q
     if kv.shape[0] == 0:
         return dq, dkv
     es = q.element_size()
-    with _record('attn_mq_bwd', kv.shape[0] * 4 * H * dh * es + 4 * R * H * dh * es, 10 * rec_hints.get('sum_q_len', R * max_len) * H * dh):
-        L.check(L.lib().b4c_attn_mq_bwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
-                                             _p(d_o), d_o.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dkv), dkv.stride(0), B, max_len, H, dh,
-                                             dt_code(q.dtype), _st(), _p(q_rows), rate, seed), 'attn_mq_bwd_drop')
+    with _record('attn_mq_bwd', kv.shape[0] * 4 * H * dh * es + 4 * R * H * dh * es, 10 * _attn_mq_pairs(R, max_len, causal) * H * dh):
+        if causal:
+            L.check(L.lib().b4c_attn_mq_bwd_ex(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
+                                               _p(d_o), d_o.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dkv), dkv.stride(0), B, max_len, H, dh,
+                                               dt_code(q.dtype), _st(), _p(q_rows), rate, seed, L.ATTN_CAUSAL), 'attn_mq_bwd_ex')
+        else:
+            L.check(L.lib().b4c_attn_mq_bwd_drop(_p(q), q.stride(0), _p(kv), kv.stride(0), _p(key_pad), _p(cu), _p(moff), _p(o), o.stride(0),
+                                                 _p(d_o), d_o.stride(0), _p(lse), _p(dq), dq.stride(0), _p(dkv), dkv.stride(0), B, max_len, H, dh,
+                                                 dt_code(q.dtype), _st(), _p(q_rows), rate, seed), 'attn_mq_bwd_drop')
     return dq, dkv
 
 
@@ -2582,6 +2607,10 @@ mq_last_layer = os.environ.get('B4C_MQ_LAST_LAYER', '1') != '0'
 # (b4c_attn_mq_*_drop).  Off (B4C_MQ_ATTN_DROPOUT=1 switches it on): such a pass takes the full last layer and gathers its rows,
 # Encoder.rows_supported's answer; Encoder.rows_route is the route with this switch applied.
 mq_attn_dropout = os.environ.get('B4C_MQ_ATTN_DROPOUT', '0') == '1'
+# ... and for a causal encoder (attention='causal'): the masked-query kernels' causal form (b4c_attn_mq_*_ex, B4C_ATTN_CAUSAL), every
+# query row over the keys up to its own position.  Off (B4C_MQ_CAUSAL=1 switches it on): a causal encoder takes the full last layer
+# and gathers its rows, Encoder.rows_supported's answer; Encoder.rows_route is the route with this switch applied too.
+mq_causal = os.environ.get('B4C_MQ_CAUSAL', '0') == '1'
 
 
 class MQAttnBlockFn(torch.autograd.Function):
@@ -2590,11 +2619,13 @@ class MQAttnBlockFn(torch.autograd.Function):
     [MASK] rows); keys and values still come from every token.
       x [T, d] (all tokens), midx [R] int32 (token row of each query row, -1 = unused row), moff [B+1] (query rows of
       sequence b), cu [B+1] (its token rows), key_pad [T] or None  ->  out1_m [R, d].
-    attn_rate > 0: dropout on the attention probabilities, the masks AttnBlockFn draws with attn_seed for the rows midx."""
+    attn_rate > 0: dropout on the attention probabilities, the masks AttnBlockFn draws with attn_seed for the rows midx.
+    causal (a trailing argument a bidirectional caller does not pass): the last layer of a causal encoder, each query row over the
+    keys up to its own position (midx is the kernels' q_rows either way)."""
 
     @staticmethod
     def forward(ctx, x, midx, moff, cu, key_pad, wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta, pk_qkv, pk_o, B, max_len, H, rate, seed,
-                training, attn_rate=0.0, attn_seed=0):
+                training, attn_rate=0.0, attn_seed=0, causal=False):
         T_tok, d = x.shape
         dh = d // H
         R = midx.shape[0]
@@ -2603,12 +2634,13 @@ class MQAttnBlockFn(torch.autograd.Function):
         kv = gemm_nt(x, wt_qkv[d:3 * d], 2 * d, b_qkv[d:3 * d])            # K | V of every token
         x_m = gather_rows(x, midx, R)
         q_m = gemm_nt(x_m, wt_qkv[:d], d, b_qkv[:d])
-        o_m, lse = attn_mq_fwd(q_m, kv, cu, moff, B, max_len, H, dh, key_pad, midx, attn_rate, attn_seed)
+        o_m, lse = attn_mq_fwd(q_m, kv, cu, moff, B, max_len, H, dh, key_pad, midx, attn_rate, attn_seed, **({'causal': True} if causal else {}))
         z, out, stats = _residual_ln_fwd(o_m, wt_o, b_o, x_m, gamma, beta, rate, seed, training)
         if training:
             ctx.save_for_backward(x, x_m, midx, moff, cu, key_pad, q_m, kv, o_m, lse, z, stats, gamma)
             ctx.pk = (pk_qkv, pk_o)
             ctx.dims = (B, max_len, H, dh, rate, seed, attn_rate, attn_seed)
+            ctx.causal = bool(causal)
             ctx.params = (wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta)
         return out
 
@@ -2624,7 +2656,8 @@ class MQAttnBlockFn(torch.autograd.Function):
         _, wc_o, _ = pk_o.get(x.dtype, d, True)
         _, wc_qkv, _ = pk_qkv.get(x.dtype, d, True)
         dz, d_o = _attn_tail_bwd(dout, z, stats, gamma, rate, seed, o_m, wc_o, ctx.params, actx, sinks, dxdw=False)
-        dq, dkv = attn_mq_bwd(q_m, kv, cu, moff, o_m, d_o, lse, B, max_len, H, dh, key_pad, midx, attn_rate, attn_seed)
+        dq, dkv = attn_mq_bwd(q_m, kv, cu, moff, o_m, d_o, lse, B, max_len, H, dh, key_pad, midx, attn_rate, attn_seed,
+                              **({'causal': True} if ctx.causal else {}))
         queue_dw(actx, x_m, dq, d, d, [gwq], [gbq], (wq, bq))
         flush_pending_dw(actx)                  # (the query-row problems have R rows, the key / value problem T)
         dx_m = gemm_nt(dq, wc_qkv[:, :d], d, residual=dz, out_dtype=torch.float32)      # query rows: through Wq + the residual branch (kept in fp32 until it joins dx)

@@ -38,9 +38,10 @@ def evaluate(model, data, batch=1024, split='test', filtered=False, next_item=Fa
     with torch.no_grad():
         for b in (data.next_item_eval_batches(batch, split=split) if next_item else
                   data.eval_batches(batch, split=split) if hasattr(data, 'history') else data.eval_batches(batch)):
-            seen = None
+            seen, kw = None, {}
             if next_item:              # one compact row per sequence that has a target, at its last input
                 items, lab, flat = b['items'], b['labels'], b['flat_idx']
+                kw = {'row_offsets': b['row_offsets']}     # the last layer at the named rows only, where that route is open
                 if filtered:
                     seen = data.history(b['target_seq_idx'], split=split)
             elif 'items' in b:           # DeviceCloze: at most one [MASK] per row; a sequence too short for the target has none
@@ -53,7 +54,7 @@ def evaluate(model, data, batch=1024, split='test', filtered=False, next_item=Fa
                 lab = torch.from_numpy(b['labels']).cuda()
                 flat = torch.from_numpy(b['flat_idx']).cuda()
             loss = model.cloze_loss({'asin': items}, lab, training=False, flat_idx=flat)
-            _, h, nd = model.predict_topk({'asin': items}, 10, lab, flat_idx=flat, exclude=seen)
+            _, h, nd = model.predict_topk({'asin': items}, 10, lab, flat_idx=flat, exclude=seen, **kw)
             tot += float(loss) * h.numel()
             hits += float(h.sum()); ndcg += float(nd.sum()); n += h.numel()
     return tot / n, 100.0 * hits / n, 100.0 * ndcg / n
@@ -85,6 +86,9 @@ def main():
     ap.add_argument('--attention', default='bidirectional', choices=['bidirectional', 'causal'],
                     help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
                          'left-to-right next-item model')
+    ap.add_argument('--mq_causal', action='store_true',
+                    help='with --attention causal: evaluate the last encoder layer at the rows the head reads only (ops.mq_causal, off '
+                         'by default)')
     add_train_loss_arguments(ap)
     add_objective_argument(ap)
     a = ap.parse_args()
@@ -95,7 +99,9 @@ def main():
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
         ap.error('--max_len, --stride, --holdout and --last_item_rate need --device_batches')
-    from bert4clickpath_amd import checkpoint as ck, input_pipeline, optim
+    from bert4clickpath_amd import checkpoint as ck, input_pipeline, ops, optim
+    if a.mq_causal:
+        ops.mq_causal = True
     from bert4clickpath_amd.clickstream_transformer import transformer as T
     if a.device_batches:
         from bert4clickpath_amd.cloze_batches import DeviceCloze

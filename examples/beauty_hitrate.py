@@ -180,6 +180,10 @@ def main():
     ap.add_argument('--attention', default='bidirectional', choices=['bidirectional', 'causal'],
                     help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
                          'left-to-right next-item model (every training row predicts the item after its prefix)')
+    ap.add_argument('--mq_causal', action='store_true',
+                    help='with --attention causal: evaluate the last encoder layer at the rows the head reads only (ops.mq_causal, off '
+                         'by default; with attention dropout in training also B4C_MQ_ATTN_DROPOUT=1); the next-item evaluation names '
+                         'its rows and passes row_offsets= either way')
     ap.add_argument('--popularity_buckets', type=int, default=0,
                     help='with --device_batches: K > 0 adds a second feature to the model and to every batch -- the bucket, of K, of '
                          'the item\'s count in the training split (masked with the item); default 0: the one-feature model')
@@ -194,10 +198,12 @@ def main():
     protocol = dict(max_len=a.max_len, stride=a.stride, holdout=a.holdout, last_item_rate=a.last_item_rate)
     if not a.device_batches and protocol != dict(max_len=None, stride=None, holdout=1, last_item_rate=0.0):
         ap.error('--max_len, --stride, --holdout and --last_item_rate need --device_batches')
-    from bert4clickpath_amd import input_pipeline, optim
+    from bert4clickpath_amd import input_pipeline, ops, optim
     from bert4clickpath_amd.clickstream_transformer.training_utils import WarmupLinearDecay
     from bert4clickpath_amd.clickstream_transformer import transformer as T
     data = input_pipeline.BeautyCloze(a.data)
+    if a.mq_causal:
+        ops.mq_causal = True
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
     longest = (int(np.diff(data.offsets).max()) if a.max_len is None else a.max_len) + 3       # [CLS] [SEP] items [SEP]
     model = build_model(data.V, a.dropout, dtype, paper_positions=longest if a.paper_model else None, attention=a.attention,
@@ -270,7 +276,9 @@ def main():
                 labels, flat = torch.from_numpy(b['labels']).cuda(), torch.from_numpy(b['flat_idx']).cuda()
             if seen is None and (a.exclude_seen or a.negatives):
                 seen = cloze.seen_items(items)
-            kw = {'n_real_tokens': b['n_real_tokens']} if next_item else {}
+            # (row_offsets: the last layer runs at the named rows only where that route is open -- a bidirectional model, a causal one
+            # with --mq_causal)
+            kw = {'n_real_tokens': b['n_real_tokens'], 'row_offsets': b['row_offsets']} if next_item else {}
             feats = {'asin': items, **side}
             _, h, nd = model.predict_topk(feats, 10, labels, flat_idx=flat, **kw)
             hits += float(h.sum()); ndcg += float(nd.sum()); n += h.numel()

@@ -25,7 +25,8 @@ extern "C" {
  * only) comes out finite; its value is not otherwise pinned, as for a sequence without a live key in b4c_attn_fwd.
  * Dropout: a causal launch draws, for every visible (q, k), the bit b4c_attn_keep(seed, b, h, q, k, H, S, rate) that the
  * bidirectional launch draws.  b4c_attn_weights_ex returns the undropped P, 0 for k > q, from the lse of a causal forward.
- * Not covered: causal masked-query kernels (b4c_attn_mq_*) and general [Sq][Sk] masks. */
+ * The masked-query kernels (b4c_attn_mq_*) take the same flag through b4c_attn_mq_fwd_ex / b4c_attn_mq_bwd_ex (b4c_attn_mq_ex.h).
+ * Not covered: general [Sq][Sk] masks. */
 #define B4C_ATTN_CAUSAL 1u
 int b4c_attn_fwd_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens /* NULL: dense */, void *o,
                     int ld_o, float *lse, int B, int S /* or max_len */, int H, int dh, int dtype, void *stream,
