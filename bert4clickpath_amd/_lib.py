@@ -16,6 +16,9 @@ ADDON_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_
                       os.path.join(os.path.dirname(_HERE), 'include', 'b4c_batch_features.h'),
                       os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss_ex.h'),
                       os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_mq_ex.h'))
+# pre-LN headers: the entry points of the pre-LN encoder blocks, which b4c.h includes too.  A list of its own: lib() binds what it
+# declares (pre_ln_signatures()); signatures(), all_signatures() and addon_signatures() keep to the lists above.
+PRE_LN_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_pre_ln.h'),)
 
 
 class B4CError(RuntimeError):
@@ -125,7 +128,21 @@ def addon_signatures():
     return table
 
 
-_C = header_constants(''.join(_header_text(p) for p in (HEADER_PATH,) + EXT_HEADER_PATHS + ADDON_HEADER_PATHS))
+def pre_ln_signatures():
+    """signatures() of every pre-LN header (PRE_LN_HEADER_PATHS): what lib() binds beside all_signatures() and addon_signatures().
+    A name that another header of the ABI declares raises."""
+    taken = dict(all_signatures())
+    taken.update(addon_signatures())
+    table = {}
+    for path in PRE_LN_HEADER_PATHS:
+        for name, sig in signatures(path).items():
+            if name in taken or name in table:
+                raise B4CError('%s declares %s, which another header of the ABI declares too' % (path, name))
+            table[name] = sig
+    return table
+
+
+_C = header_constants(''.join(_header_text(p) for p in (HEADER_PATH,) + EXT_HEADER_PATHS + ADDON_HEADER_PATHS + PRE_LN_HEADER_PATHS))
 ABI_VERSION = _C['B4C_ABI_VERSION']       # b4c_abi_version() of the library must agree
 F32, BF16 = _C['B4C_F32'], _C['B4C_BF16']
 ACT_NONE, ACT_RELU = _C['B4C_ACT_NONE'], _C['B4C_ACT_RELU']
@@ -177,7 +194,7 @@ def lib():
         if have != ABI_VERSION:
             raise B4CError('%s is ABI %d, this binding expects ABI %d; rebuild it (`make -C bert4clickpath_amd/csrc`)'
                            % (LIB_PATH, have, ABI_VERSION))
-        for name, (res, args) in list(sig.items()) + list(addon_signatures().items()):
+        for name, (res, args) in list(sig.items()) + list(addon_signatures().items()) + list(pre_ln_signatures().items()):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -99,7 +99,7 @@ class ClickstreamTransformer(nn.Module):
                  value_to_head=None, num_encoder_layers=1, num_attention_heads=1, dropout_rate=0.1,
                  compute_dtype=torch.float32, feature_combine='concat', encoder_ff_dim=100, ffn_activation='relu',
                  position_encoding='sinusoidal', max_positions=None, attention_dropout_rate=0.0, embedding_layernorm=False,
-                 embedding_scale=None, attention='bidirectional', **kwargs):
+                 embedding_scale=None, attention='bidirectional', norm='post', **kwargs):
         super().__init__()
         # ffn_activation / position_encoding / max_positions: the BERT4Rec paper's GELU feed-forward and learned positions
         # (extensions, validated by transformer.Transformer); the defaults are the reference's ReLU and fixed sinusoid
@@ -132,7 +132,10 @@ class ClickstreamTransformer(nn.Module):
             dropout_rate=dropout_rate, compute_dtype=compute_dtype, feature_combine=feature_combine,
             ffn_activation=ffn_activation, position_encoding=position_encoding, max_positions=max_positions,
             attention_dropout_rate=attention_dropout_rate, embedding_layernorm=embedding_layernorm,
-            embedding_scale=embedding_scale, attention=attention)
+            embedding_scale=embedding_scale, attention=attention, **({'norm': norm} if norm != 'post' else {}))
+        # norm: 'post' (the reference) | 'pre' (pre-LN layers and a final LayerNorm, transformer.Encoder; validated by
+        # transformer.Transformer).  A pre-LN encoder evaluates its full last layer (no masked-query form).
+        self.norm = self.transformer.norm
         self.max_positions = self.transformer.max_positions
         # attention: 'bidirectional' (the reference, BERT4Rec) | 'causal' (left-to-right: SASRec, the paper's unidirectional arm;
         # validated by transformer.Transformer).  A causal encoder evaluates its full last layer (no masked-query form).
@@ -167,7 +170,8 @@ class ClickstreamTransformer(nn.Module):
                 **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {}),
                 **({'embedding_layernorm': True} if self.embedding_layernorm else {}),
                 **({'embedding_scale': self.embedding_scale} if self.embedding_scale is not None else {}),
-                **({'attention': self.attention} if self.attention != 'bidirectional' else {})}
+                **({'attention': self.attention} if self.attention != 'bidirectional' else {}),
+                **({'norm': self.norm} if self.norm != 'post' else {})}
 
     @staticmethod
     def _create_lookup_tables(vocabularies, tokens_to_prepend=None):

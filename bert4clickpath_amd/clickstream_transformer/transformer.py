@@ -64,6 +64,15 @@ def _attention_kind(attention):
     return attention
 
 
+NORM_KINDS = ('post', 'pre')
+
+
+def _norm_kind(norm):
+    if norm not in NORM_KINDS:
+        raise ValueError("norm must be 'post' or 'pre', got %r" % (norm,))
+    return norm
+
+
 def create_segment_markers(seq, sep=SEP):
     """Cumulative count of SEP tokens along axis 1 (reference transformer.py:6-34; unused on the hot path)."""
     return torch.cumsum((seq == sep).to(torch.int32), dim=1)
@@ -252,14 +261,19 @@ class EncoderLayer(nn.Module):
     probabilities inside the attention kernels, in training only.  Its seed is a THIRD draw from dropout_seeds, taken after the
     two of the residual branches and only when the rate is > 0: at rate 0 the seed stream is what it always was.
     attention ('bidirectional' | 'causal'; no reference counterpart): 'causal' is left-to-right self-attention inside the kernels,
-    position q attends to positions 0 .. q only (the position in the dense layout, the row inside the sequence in the packed one)."""
+    position q attends to positions 0 .. q only (the position in the dense layout, the row inside the sequence in the packed one).
+    norm ('post' | 'pre'; no reference counterpart): 'pre' is the pre-LN block, torch's norm_first layer -- x' = x + drop(mha(LN1(x))),
+    x'' = x' + drop(ffn(LN2(x'))): q, k and v are all taken from the normalised rows, the layer returns the UN-normalised stream and
+    the norm that ends a stack belongs to Encoder (final_norm).  Same parameters, names and dropout seeds as the post-LN layer; no
+    masked-query form (rows=)."""
 
     def __init__(self, d_model, num_heads, dff, rate=0.1, ffn_activation='relu', attention_dropout_rate=0.0,
-                 attention='bidirectional', **kwargs):
+                 attention='bidirectional', norm='post', **kwargs):
         super().__init__()
         self.d_model, self.num_heads, self.dff, self.rate = d_model, num_heads, dff, rate
         self.ffn_activation = ffn_activation
         self.attention = _attention_kind(attention)
+        self.norm = _norm_kind(norm)
         self.attention_dropout_rate = _attention_rate(attention_dropout_rate)
         self.mha = MultiHeadAttention(d_model, num_heads)
         self.ffn = point_wise_feed_forward_network(d_model, dff, ffn_activation)
@@ -270,7 +284,27 @@ class EncoderLayer(nn.Module):
         return {'d_model': self.d_model, 'num_heads': self.num_heads, 'dff': self.dff, 'rate': self.rate,
                 **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
                 **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {}),
-                **({'attention': self.attention} if self.attention != 'bidirectional' else {})}
+                **({'attention': self.attention} if self.attention != 'bidirectional' else {}),
+                **({'norm': self.norm} if self.norm != 'post' else {})}
+
+    def pre_ln_halves(self, x2, n, stats, key_pad, B, S, cu, training, next_norm):
+        """The two pre-LN halves on the stream x2 [T, d] with n = LN1(x2) and its stats given -> (x'', LN(x''; next_norm), its
+        stats): each tail writes the stream and the NEXT norm's rows in one launch (ops.PreLNAttnBlockFn / PreLNFFNBlockFn)."""
+        m, f = self.mha, self.ffn
+        s1 = dropout_seeds.next() if training else 0
+        s2 = dropout_seeds.next() if training else 0
+        a_rate = self.attention_dropout_rate if training else 0.0
+        s3 = dropout_seeds.next() if a_rate > 0 else 0
+        need_tape = training or torch.is_grad_enabled()
+        rate = self.rate if training else 0.0
+        x1, n1, st1 = ops.PreLNAttnBlockFn.apply(x2, m.wq.kernel, m.wq.bias, m.wk.kernel, m.wk.bias, m.wv.kernel, m.wv.bias,
+                                                 m.dense.kernel, m.dense.bias, self.layernorm1.gamma, self.layernorm1.beta, n, stats,
+                                                 key_pad, self.layernorm2.gamma, self.layernorm2.beta, m._pk_qkv, m._pk_o, B, S,
+                                                 self.num_heads, rate, s1, need_tape, cu, a_rate, s3,
+                                                 *([True] if self.attention == 'causal' else []))
+        return ops.PreLNFFNBlockFn.apply(x1, f[0].kernel, f[0].bias, f[1].kernel, f[1].bias, self.layernorm2.gamma,
+                                         self.layernorm2.beta, n1, st1, next_norm.gamma, next_norm.beta, f._pk1, f._pk2, rate, s2,
+                                         need_tape, f.act)
 
     def forward(self, x, training=None, mask=None, packed=None, rows=None):
         """x (B, S, d); or, with `packed` (ops.Packed), the (1, T, d) rows of the real tokens only and mask = the (T,) key
@@ -294,6 +328,13 @@ class EncoderLayer(nn.Module):
                 _mask_to_bytes(mask, B, S, x.device)
             x2 = x.reshape(B * S, d)
             out_shape = (B, S, d)
+        if self.norm == 'pre':
+            if rows is not None:
+                raise B4CError('a pre-LN layer has no masked-query form (rows=): evaluate the full layer and gather its rows '
+                               '(Encoder.rows_supported / rows_route answer False)')
+            # a layer on its own: LN1 is launched here, and the last tail's norm output (no next norm to feed) is dropped
+            n, stats = ops.layernorm_fwd(x2, self.layernorm1.gamma.detach(), self.layernorm1.beta.detach())
+            return self.pre_ln_halves(x2, n, stats, key_pad, B, S, cu, training, self.layernorm1)[0].view(out_shape)
         m, f = self.mha, self.ffn
         s1 = dropout_seeds.next() if training else 0
         s2 = dropout_seeds.next() if training else 0
@@ -331,10 +372,13 @@ class EncoderLayer(nn.Module):
 class Encoder(nn.Module):
     """num_layers EncoderLayers; no final LayerNorm (reference :255-268).  The input dropout of the
     reference's Encoder.call (:263) is fused into the embedding kernel when ``Transformer`` calls the Encoder;
-    an Encoder called on its own applies it with the stand-alone dropout kernel (same keep-mask generator)."""
+    an Encoder called on its own applies it with the stand-alone dropout kernel (same keep-mask generator).
+    norm='pre' (no reference counterpart): pre-LN layers (EncoderLayer) and one LayerNorm after the last of them, ``final_norm``
+    (gamma ones, beta zeros, eps 1e-6) -- nn.TransformerEncoder(norm_first layers, norm=LayerNorm).  The full last layer always
+    runs: rows= is refused, rows_supported / rows_route answer False."""
 
     def __init__(self, num_layers, d_model, num_heads, dff, dropout_rate, ffn_activation='relu', attention_dropout_rate=0.0,
-                 attention='bidirectional', **kwargs):
+                 attention='bidirectional', norm='post', **kwargs):
         super().__init__()
         self.num_layers, self.d_model, self.num_heads, self.dff, self.dropout_rate = \
             num_layers, d_model, num_heads, dff, dropout_rate
@@ -342,21 +386,52 @@ class Encoder(nn.Module):
         self.ffn_activation = ffn_activation
         self.attention_dropout_rate = _attention_rate(attention_dropout_rate)
         self.attention = _attention_kind(attention)
+        self.norm = _norm_kind(norm)
         self.enc_layers = nn.ModuleList([EncoderLayer(d_model, num_heads, dff, dropout_rate, ffn_activation,
-                                                      self.attention_dropout_rate, self.attention) for _ in range(num_layers)])
+                                                      self.attention_dropout_rate, self.attention,
+                                                      **({'norm': 'pre'} if self.norm == 'pre' else {})) for _ in range(num_layers)])
+        if self.norm == 'pre':
+            self.final_norm = LayerNormalization(d_model, 1e-6)
 
     def get_config(self):
         return {'num_layers': self.num_layers, 'd_model': self.d_model, 'num_heads': self.num_heads, 'dff': self.dff,
                 'dropout_rate': self.dropout_rate,
                 **({'ffn_activation': self.ffn_activation} if self.ffn_activation != 'relu' else {}),
                 **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {}),
-                **({'attention': self.attention} if self.attention != 'bidirectional' else {})}
+                **({'attention': self.attention} if self.attention != 'bidirectional' else {}),
+                **({'norm': self.norm} if self.norm != 'post' else {})}
+
+    def _forward_pre(self, x, training, mask, packed):
+        """The pre-LN stack: one layernorm_fwd (LN1 of the first layer), then every half's tail writes the stream and the next
+        norm's rows; the last tail is given final_norm, whose rows are the encoder's output."""
+        B, S, d = x.shape
+        if packed is not None:
+            key_pad, cu = mask, packed.cu
+            x2 = x.reshape(-1, d)
+            B, S = packed.B, packed.max_len
+        else:
+            key_pad = mask if (mask is not None and mask.dtype == torch.uint8 and mask.dim() == 2) else \
+                _mask_to_bytes(mask, B, S, x.device)
+            cu = None
+            x2 = x.reshape(B * S, d)
+        norms = [layer.layernorm1 for layer in self.enc_layers] + [self.final_norm]
+        n, stats = ops.layernorm_fwd(x2, norms[0].gamma.detach(), norms[0].beta.detach())
+        for i, layer in enumerate(self.enc_layers):
+            x2, n, stats = layer.pre_ln_halves(x2, n, stats, key_pad, B, S, cu, bool(training), norms[i + 1])
+        out = ops.PreLNFinalNormFn.apply(x2, self.final_norm.gamma, self.final_norm.beta, n, stats,
+                                         bool(training) or torch.is_grad_enabled())
+        return out.view(x.shape)
 
     def forward(self, inputs, training=None, mask=None, _input_dropout_done=False, packed=None, rows=None):
         """rows (see EncoderLayer.forward): the LAST layer is evaluated for those query rows only; returns (R, d)."""
         x = inputs
         if training and self.dropout_rate > 0 and not _input_dropout_done:
             x = ops.DropoutFn.apply(x, float(self.dropout_rate), dropout_seeds.next())
+        if self.norm == 'pre':
+            if rows is not None:
+                raise B4CError('a pre-LN encoder has no masked-query last layer (rows=): rows_supported / rows_route answer False, '
+                               'evaluate the full encoder and gather its rows')
+            return self._forward_pre(x, training, mask, packed)
         B, S, d = x.shape
         last = len(self.enc_layers) - 1
         for i, layer in enumerate(self.enc_layers):
@@ -367,7 +442,10 @@ class Encoder(nn.Module):
         """The masked-query form of the last layer: head depth 32 / 64 (b4c_attn_mq_*), at least one layer.  Those kernels have no
         attention dropout: a training pass with attention_dropout_rate > 0 takes the full last layer and gathers its rows.  A causal
         encoder takes the full last layer too: the kernels' causal form (b4c_attn_mq_*_ex) is behind a switch that is off by
-        default and that rows_route applies (ops.mq_causal), so this answer stays False for it."""
+        default and that rows_route applies (ops.mq_causal), so this answer stays False for it.  A pre-LN encoder: False (the
+        masked-query kernels' tail is the post-LN one)."""
+        if self.norm == 'pre':
+            return False
         if not self.enc_layers or self.attention == 'causal' or (training and self.attention_dropout_rate > 0):
             return False
         return (self.d_model // self.num_heads) in (32, 64) and self.d_model % 8 == 0
@@ -376,7 +454,10 @@ class Encoder(nn.Module):
         """Does the last layer take its masked-query form in this pass?  rows_supported(...); with ops.mq_attn_dropout on, the same
         shape conditions without the dropout exclusion (b4c_attn_mq_*_drop draws the full layer's masks for the query rows).
         A causal encoder: False, as rows_supported says, unless ops.mq_causal is on; then the shape conditions (b4c_attn_mq_*_ex with
-        B4C_ATTN_CAUSAL), and in a training pass with attention_dropout_rate > 0 ops.mq_attn_dropout on top, as above."""
+        B4C_ATTN_CAUSAL), and in a training pass with attention_dropout_rate > 0 ops.mq_attn_dropout on top, as above.
+        A pre-LN encoder: False whatever the switches say."""
+        if self.norm == 'pre':
+            return False
         if self.attention == 'causal':
             if not ops.mq_causal or not self.enc_layers or (training and self.attention_dropout_rate > 0 and not ops.mq_attn_dropout):
                 return False
@@ -429,14 +510,16 @@ class Transformer(nn.Module):
     embedding_layernorm=True: the input stage is drop(LayerNorm(scale * rows + PE)) with the parameters
     ``embedding_norm.gamma`` / ``.beta`` (eps 1e-6, as every LayerNormalization here); embedding_scale: a positive number in
     place of sqrt(d_model) (None; the paper does not scale: 1.0); attention='causal': left-to-right self-attention in every layer
-    (SASRec, the paper's unidirectional arm) instead of 'bidirectional'."""
+    (SASRec, the paper's unidirectional arm) instead of 'bidirectional'; norm='pre': pre-LN encoder layers and the encoder's
+    ``encoder.final_norm`` behind the last of them (Encoder) instead of the reference's post-LN layers."""
 
     def __init__(self, num_layers, num_attention_heads, embedding_sizes, embedding_dims, encoder_ff_dim, dropout_rate,
                  item_embedding_weights=None, compute_dtype=torch.float32, feature_combine='concat', ffn_activation='relu',
                  position_encoding='sinusoidal', max_positions=None, attention_dropout_rate=0.0, embedding_layernorm=False,
-                 embedding_scale=None, attention='bidirectional', **kwargs):
+                 embedding_scale=None, attention='bidirectional', norm='post', **kwargs):
         super().__init__()
         self.attention = _attention_kind(attention)
+        self.norm = _norm_kind(norm)
         if embedding_scale is not None and not (isinstance(embedding_scale, numbers.Real) and not isinstance(embedding_scale, bool)
                                                 and 0 < float(embedding_scale) < float('inf')):
             raise ValueError('embedding_scale must be None (sqrt(d_model)) or a positive number, got %r' % (embedding_scale,))
@@ -474,7 +557,7 @@ class Transformer(nn.Module):
                 raise B4CError('MI355X build: embedding dim of feature %r is %d; must be a multiple of 8' % (f, dim))
         self.compute_dtype = compute_dtype
         self.encoder = Encoder(num_layers, self.d_model, num_attention_heads, encoder_ff_dim, dropout_rate, ffn_activation,
-                               self.attention_dropout_rate, self.attention)
+                               self.attention_dropout_rate, self.attention, **({'norm': 'pre'} if self.norm == 'pre' else {}))
         self.embedding_layers = _FeatureModules({f: _Embedding(int(embedding_sizes[f]), int(embedding_dims[f]))
                                                  for f in embedding_dims.keys()})
         if position_encoding == 'learned':
@@ -504,7 +587,8 @@ class Transformer(nn.Module):
                 **({'attention_dropout_rate': self.attention_dropout_rate} if self.attention_dropout_rate else {}),
                 **({'embedding_layernorm': True} if self.embedding_layernorm else {}),
                 **({'embedding_scale': self.embedding_scale} if self.embedding_scale is not None else {}),
-                **({'attention': self.attention} if self.attention != 'bidirectional' else {})}
+                **({'attention': self.attention} if self.attention != 'bidirectional' else {}),
+                **({'norm': self.norm} if self.norm != 'post' else {})}
 
     @property
     def position_table(self):

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "ln_bwd_rows.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -165,12 +166,6 @@ static int fill_embed_args(EmbedArgs &a, int n_feat, const int64_t *const *h_ids
     for (int f = n_feat; f <= B4C_MAX_FEATURES; ++f) a.col0[f] = a.sum ? d_model : off;
     B4C_REQUIRE(a.sum || off == d_model, "embed: sum of feature dims %d != d_model %d (and not every feature is d_model wide)", off, d_model);
     return B4C_OK;
-}
-
-static inline int grid_for(int64_t work_items, int block) {
-    int64_t g = ceil_div64(work_items, block);
-    const int64_t cap = 256 * 8;  // 256 CUs x 8 blocks, grid-stride the rest
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 extern "C" int b4c_embed_concat_pe_fwd(int n_feat, const int64_t *const *h_ids, const float *const *h_tables,
@@ -631,7 +626,6 @@ extern "C" int b4c_embed_concat_pe_bwd_sorted_ws(int n_feat, const int64_t *cons
 // residual + dropout + LayerNorm.  A row of d elements is owned by G lanes (8 elements per lane
 // per pass); G is a power of two so rows never straddle a wave.  d <= 1024.
 // ------------------------------------------------------------------------------------------
-#define LN_MAX_PASS 2  // d <= 64 lanes * 8 elems * 2 passes = 1024 (keeps the per-lane row slice in registers)
 
 // Where a LayerNorm row comes from: load(row, c, v) = its columns c .. c+7 in fp32 (c < d).
 template <typename T> struct AddDropSrc {       // x + drop(y), saved to z when z != NULL
@@ -695,19 +689,6 @@ struct DropEpi {        // inverted dropout, element row * d + c + k of the keep
         }
     }
 };
-template <typename T> struct GateEpi {          // o *= act'(gate[row][c + k]): ReLU = the gate's sign, a GELU = its derivative (NULL: none)
-    static constexpr bool kNone = false;
-    const T *gate;
-    int ld, act;
-    __device__ __forceinline__ void apply(int64_t row, int c, float (&o)[8]) const {
-        if (!gate) return;
-        float u[8];
-        Vec8<T>::load(gate + row * ld + c, u);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = act == B4C_ACT_RELU ? (u[k] > 0.f ? o[k] : 0.f) : o[k] * act_gelu_grad(u[k], act);
-    }
-};
-
 // The LayerNorm row body: rows from `src`, out[row] = epi(gamma * (v - mean) * rstd + beta), stats[row] = {mean, rstd}.
 template <typename T, int G, typename Src, typename Epi>
 __device__ __forceinline__ void ln_fwd_rows(const Src &src, const Epi &epi, const float *__restrict__ gamma,
@@ -800,15 +781,6 @@ __global__ void __launch_bounds__(256) embed_ln_fwd_kernel(EmbedSrc src, DropEpi
     ln_fwd_rows<T, G>(src, drop, gamma, beta, out, ld_out, stats, rows, src.d, eps);
 }
 
-// Where the backward's rows come from: load(row, c, go, zz) = the upstream gradient and the LayerNorm input, columns c .. c+7.
-template <typename T> struct RowGradSrc {
-    const T *dout, *z;
-    int d;
-    __device__ __forceinline__ void load(int64_t row, int c, float (&go)[8], float (&zz)[8]) const {
-        Vec8<T>::load(dout + row * d + c, go);
-        Vec8<T>::load(z + row * d + c, zz);
-    }
-};
 template <typename T> struct EmbedGradSrc {     // go = the forward's dropout on dout; the pre-norm row is gathered again
     EmbedSrc pre;
     DropEpi drop;
@@ -821,118 +793,6 @@ template <typename T> struct EmbedGradSrc {     // go = the forward's dropout on
     }
 };
 
-// The backward row body: dz = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dout * gamma.
-// dgamma/dbeta: per-thread partials over the block's rows -> LDS -> one atomic per column per block.
-// DET (deterministic form, `partial` != NULL): the threads' partials meet in a fixed order -- through LDS [row group][2][d], summed
-// group by group, the block's sums stored to partial[block][2][d]; ln_bwd_reduce_kernel then adds the blocks in block order.
-// dz pitch ld_dz; `epi` is applied to dz; dy = the forward's dropout on dz, written by the forms without an epilogue only.
-template <typename T, int G, int NP, bool DET, typename Src, typename Epi>
-__device__ __forceinline__ void ln_bwd_rows(const Src &src, const Epi &epi, const float *__restrict__ stats,
-                                            const float *__restrict__ gamma, T *__restrict__ dz, int ld_dz, T *__restrict__ dy,
-                                            float *__restrict__ dgamma, float *__restrict__ dbeta, int64_t rows, int d, float rate,
-                                            uint64_t seed, float *__restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) float red[];  // [2][d]  (DET: [256 / G][2][d])
-    const int lane_in_row = threadIdx.x & (G - 1);
-    const int rows_per_block = 256 / G;
-    const float inv_keep = rate > 0.f ? 1.0f / (1.0f - rate) : 1.0f;
-    const float inv_d = 1.0f / (float)d;
-    if (!DET) {
-        for (int i = threadIdx.x; i < 2 * d; i += 256) red[i] = 0.f;
-        __syncthreads();
-    }
-    // NP = passes of G * 8 columns a row needs (1 for d <= 128 at G = 16): a runtime pass count kept the second pass's
-    // 64 registers allocated
-    float pg[NP][8], pb[NP][8];
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) pg[p][k] = pb[p][k] = 0.f;
-
-    for (int64_t row = blockIdx.x * (int64_t)rows_per_block + threadIdx.x / G; row < rows;
-         row += (int64_t)gridDim.x * rows_per_block) {
-        const float mean = stats[row * 2], rstd = stats[row * 2 + 1];
-        float gv[NP][8], xh[NP][8];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            {
-                const int c = (p * G + lane_in_row) * 8;
-                if (c < d) {
-                    float go[8], zz[8], gm[8];
-                    src.load(row, c, go, zz);
-                    Vec8<float>::load(gamma + c, gm);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        xh[p][k] = (zz[k] - mean) * rstd;
-                        gv[p][k] = go[k] * gm[k];
-                        s1 += gv[p][k];
-                        s2 += gv[p][k] * xh[p][k];
-                        pg[p][k] += go[k] * xh[p][k];
-                        pb[p][k] += go[k];
-                    }
-                }
-            }
-        }
-        s1 = group_sum<G>(s1) * inv_d;
-        s2 = group_sum<G>(s2) * inv_d;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            {
-                const int c = (p * G + lane_in_row) * 8;
-                if (c < d) {
-                    float o[8];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) o[k] = rstd * (gv[p][k] - s1 - xh[p][k] * s2);
-                    if (!Epi::kNone) epi.apply(row, c, o);          // (a form with an epilogue has no dy: its callers pass rate 0)
-                    Vec8<T>::template store_sel<B4C_NT(B4C_NT_LNBWD_DZ)>(dz + row * ld_dz + c, o);
-                    if (Epi::kNone && rate > 0.f && dy) {
-                        const uint32_t km = b4c_keep8(seed, (uint64_t)(row * d + c), b4c_keep_threshold(rate));
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) o[k] = ((km >> k) & 1u) ? o[k] * inv_keep : 0.f;
-                        Vec8<T>::template store_sel<B4C_NT(B4C_NT_LNBWD_DY)>(dy + row * d + c, o);
-                    }
-                }
-            }
-        }
-    }
-    if (DET) {
-        float *mine = red + (threadIdx.x / G) * 2 * d;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const int c = (p * G + lane_in_row) * 8;
-            if (c < d) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { mine[c + k] = pg[p][k]; mine[d + c + k] = pb[p][k]; }
-            }
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < 2 * d; i += 256) {
-            float sum = 0.f;
-            for (int grp = 0; grp < rows_per_block; ++grp) sum += red[grp * 2 * d + i];
-            partial[(int64_t)blockIdx.x * 2 * d + i] = sum;
-        }
-        return;
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        {
-            const int c = (p * G + lane_in_row) * 8;
-            if (c < d) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    atomicAdd(&red[c + k], pg[p][k]);
-                    atomicAdd(&red[d + c + k], pb[p][k]);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < d; i += 256) {
-        atomicAdd(dgamma + i, red[i]);
-        atomicAdd(dbeta + i, red[d + i]);
-    }
-}
-
 template <typename T, int G, int NP, bool DET>
 __global__ void __launch_bounds__(256, 4) add_ln_bwd_kernel(const T *__restrict__ dout, const T *__restrict__ z,
                                                          const float *__restrict__ stats, const float *__restrict__ gamma,
@@ -943,16 +803,6 @@ __global__ void __launch_bounds__(256, 4) add_ln_bwd_kernel(const T *__restrict_
     ln_bwd_rows<T, G, NP, DET>(src, NoEpi(), stats, gamma, dz, d, dy, dgamma, dbeta, rows, d, rate, seed, partial);
 }
 
-// plain LayerNorm backward, deterministic form only; dx *= act'(gate) when a gate is given (the activation in front of the norm)
-template <typename T, int G, int NP>
-__global__ void __launch_bounds__(256, 4) ln_bwd_kernel(const T *__restrict__ dout, const T *__restrict__ x,
-                                                        const float *__restrict__ stats, const float *__restrict__ gamma,
-                                                        T *__restrict__ dx, GateEpi<T> gate, int64_t rows, int d,
-                                                        float *__restrict__ partial) {
-    const RowGradSrc<T> src = {dout, x, d};
-    ln_bwd_rows<T, G, NP, true>(src, gate, stats, gamma, dx, d, (T *)nullptr, (float *)nullptr, (float *)nullptr, rows, d, 0.f, 0, partial);
-}
-
 // backward of embed_ln_fwd_kernel up to the pre-norm row: dpre, and the partial dgamma / dbeta sums (deterministic form only)
 template <typename T, int G, int NP>
 __global__ void __launch_bounds__(256, 4) embed_ln_bwd_kernel(EmbedGradSrc<T> src, const float *__restrict__ stats,
@@ -960,24 +810,6 @@ __global__ void __launch_bounds__(256, 4) embed_ln_bwd_kernel(EmbedGradSrc<T> sr
                                                               int64_t rows, float *__restrict__ partial) {
     ln_bwd_rows<T, G, NP, true>(src, NoEpi(), stats, gamma, dpre, ld_dpre, (T *)nullptr, (float *)nullptr, (float *)nullptr, rows,
                                 src.pre.d, 0.f, 0, partial);
-}
-
-// dgamma[i] += sum over blocks of partial[block][0][i]; dbeta likewise.  One wave per column, in a FIXED order: lane l adds the
-// blocks l, l + 64, l + 128, ... one after the other, then the 64 lane sums meet in wave_sum's fixed butterfly.
-__global__ void __launch_bounds__(256) ln_bwd_reduce_kernel(const float *__restrict__ partial, int nblocks, int d, float *__restrict__ dgamma,
-                                                            float *__restrict__ dbeta) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= 2 * d) return;
-    float sum = 0.f;
-    for (int b = lane; b < nblocks; b += 64) sum += partial[(int64_t)b * 2 * d + i];
-    sum = wave_sum(sum);
-    if (lane == 0) { if (i < d) dgamma[i] += sum; else dbeta[i - d] += sum; }
-}
-
-static int ln_group(int d) {
-    int g = 1;
-    while (g * 8 < d && g < 64) g <<= 1;
-    return g;
 }
 
 #define LN_DISPATCH_G(KERNEL, T, g, ...)                                         \
@@ -1075,33 +907,6 @@ extern "C" int b4c_layernorm_fwd(const void *x, const float *gamma, const float 
     return b4c_check_launch("layernorm_fwd");
 }
 
-// grid, LDS bytes and passes of the deterministic backward kernels (ln_bwd_kernel, embed_ln_bwd_kernel): those of add_ln_bwd_kernel<.., true>
-struct LnBwdShape {
-    int g, grid, npass;
-    size_t shm;
-};
-static LnBwdShape ln_bwd_shape(int64_t rows, int d) {
-    LnBwdShape s;
-    s.g = ln_group(d);
-    s.grid = grid_for(rows * s.g, 256);
-    if (s.grid > 1024) s.grid = 1024;      // b4c_add_dropout_layernorm_bwd_workspace_bytes holds 1024 blocks' partial sums
-    s.npass = (d + s.g * 8 - 1) / (s.g * 8);
-    s.shm = (size_t)(256 / s.g) * 2 * (size_t)d * sizeof(float);
-    return s;
-}
-// KERNEL<TT, G, NP><<<grid, 256, shm, st>>>(args) for the row group and pass count of `sh`
-#define LN_DET_BWD_DISPATCH(KERNEL, TT, sh, ...)                                                                     \
-    switch ((sh).g) {                                                                                                \
-        case 1: KERNEL<TT, 1, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                               \
-        case 2: KERNEL<TT, 2, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                               \
-        case 4: KERNEL<TT, 4, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                               \
-        case 8: KERNEL<TT, 8, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                               \
-        case 16: KERNEL<TT, 16, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                             \
-        case 32: KERNEL<TT, 32, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                             \
-        default: if ((sh).npass == 1) KERNEL<TT, 64, 1><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__;               \
-                 else KERNEL<TT, 64, 2><<<(sh).grid, 256, (sh).shm, st>>> __VA_ARGS__; break;                        \
-    }
-
 extern "C" int64_t b4c_layernorm_bwd_workspace_bytes(int64_t rows, int d) { return b4c_add_dropout_layernorm_bwd_workspace_bytes(rows, d); }
 
 extern "C" int b4c_layernorm_bwd(const void *dout, const void *x, const float *stats, const float *gamma, void *dx, float *dgamma,
@@ -1112,19 +917,10 @@ extern "C" int b4c_layernorm_bwd(const void *dout, const void *x, const float *s
     B4C_REQUIRE(workspace && workspace_bytes >= b4c_layernorm_bwd_workspace_bytes(rows, d), "layernorm_bwd: workspace too small");
     B4C_REQUIRE(!gate || (ld_gate >= d && ld_gate % 8 == 0 && (gate_act == B4C_ACT_RELU || gate_act == B4C_ACT_GELU || gate_act == B4C_ACT_GELU_TANH)),
                 "layernorm_bwd: gate pitch %d / gate_act %d", ld_gate, gate_act);
-    const LnBwdShape sh = ln_bwd_shape(rows, d);
-    float *partial = (float *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == B4C_F32) {
-        const GateEpi<float> ge = {(const float *)gate, ld_gate, gate_act};
-        LN_DET_BWD_DISPATCH(ln_bwd_kernel, float, sh, ((const float *)dout, (const float *)x, stats, gamma, (float *)dx, ge, rows, d, partial))
-    } else if (dtype == B4C_BF16) {
-        const GateEpi<bf16_t> ge = {(const bf16_t *)gate, ld_gate, gate_act};
-        LN_DET_BWD_DISPATCH(ln_bwd_kernel, bf16_t, sh, ((const bf16_t *)dout, (const bf16_t *)x, stats, gamma, (bf16_t *)dx, ge, rows, d, partial))
-    } else
-        B4C_REQUIRE(false, "layernorm_bwd: dtype %d", dtype);
-    ln_bwd_reduce_kernel<<<(2 * d + 3) / 4, 256, 0, st>>>(partial, sh.grid, d, dgamma, dbeta);
-    return b4c_check_launch("layernorm_bwd");
+    B4C_REQUIRE(dtype == B4C_F32 || dtype == B4C_BF16, "layernorm_bwd: dtype %d", dtype);
+    // (the kernel is b4c_layernorm_bwd_add's, without a residual term: pre_ln.hip)
+    return b4c_ln_bwd_gate_res(dout, x, stats, gamma, dx, dgamma, dbeta, rows, d, gate, ld_gate, gate_act, nullptr, 0, workspace, dtype,
+                               stream, "layernorm_bwd");
 }
 
 // the embedding stage with LayerNorm (embed_ln_fwd_kernel) and its backward up to the pre-norm row

@@ -1129,6 +1129,79 @@ def layernorm_bwd(dout, x, stats, gamma, into=None, gate=None, gate_act=L.ACT_RE
     return dx, dgamma, dbeta
 
 
+def layernorm_bwd_add(dout, x, stats, gamma, res, into=None, dx=None, workspace=None):
+    """res + backward of layernorm_fwd (b4c_layernorm_bwd_add) -> (dx, dgamma, dbeta): the input gradient of a pre-LN encoder half,
+    res = the residual stream's gradient ([rows, d] view, unit column stride, 16-B aligned rows), added in fp32 before dx is
+    rounded.  into = (dgamma, dbeta): fp32 [d] sinks, added to.  Fixed summation order: the same bits every launch, and with
+    res == 0 the bits of layernorm_bwd."""
+    rows, d = x.shape
+    _cuda(dout, x, stats, gamma, res)
+    if into is not None:
+        dgamma, dbeta = into
+    else:
+        dgamma, dbeta = zeros(d, device=x.device), zeros(d, device=x.device)
+    _ln_vectors(d, gamma, dgamma, dbeta)
+    dx = torch.empty_like(x) if dx is None else dx
+    if dout.dtype != x.dtype or dout.shape != x.shape or not dout.is_contiguous() or not x.is_contiguous() or \
+            dx.dtype != x.dtype or dx.shape != x.shape or not dx.is_contiguous():
+        raise B4CError('layernorm_bwd_add: dout, x and dx must be contiguous tensors of one shape and dtype')
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (rows, 2) or not stats.is_contiguous():
+        raise B4CError('layernorm_bwd_add: stats must be the contiguous float32 [%d, 2] tensor of the forward call' % rows)
+    if res.dtype != x.dtype or tuple(res.shape) != (rows, d) or res.stride(1) != 1 or \
+            (res.stride(0) * res.element_size()) % 16 or res.data_ptr() % 16:
+        raise B4CError('layernorm_bwd_add: res must be a [%d, %d] %s view with unit column stride' % (rows, d, x.dtype))
+    if rows == 0:
+        return dx, dgamma, dbeta
+    ws = workspace if workspace is not None else \
+        _workspace('ln_bwd', x.device, L.lib().b4c_layernorm_bwd_add_workspace_bytes(rows, d))
+    with _record('layernorm_bwd_add', rows * d * x.element_size() * 4 + 8 * rows):
+        L.check(L.lib().b4c_layernorm_bwd_add(_p(dout), _p(x), _p(stats), _p(gamma), _p(res), res.stride(0), _p(dx), _p(dgamma),
+                                              _p(dbeta), rows, d, ws.data_ptr(), ws.numel() * ws.element_size(),
+                                              dt_code(x.dtype), _st()), 'layernorm_bwd_add')
+    return dx, dgamma, dbeta
+
+
+def gemm_ln_bwd_supported(a, bt, n):
+    """b4c_gemm_nt_ln_bwd_add takes it: bf16, at most 256 columns, 16-byte rows"""
+    return a.dtype == torch.bfloat16 and bt.dtype == torch.bfloat16 and n <= 256 and n % 8 == 0 and a.shape[1] % 8 == 0 and \
+        a.stride(1) == 1 and bt.stride(1) == 1 and a.stride(0) % 8 == 0 and bt.stride(0) % 8 == 0 and \
+        a.data_ptr() % 16 == 0 and bt.data_ptr() % 16 == 0
+
+
+def gemm_nt_ln_bwd_add(a, bt, x, stats, gamma, res, into=None, dx=None):
+    """res + backward of layernorm_fwd at dout = bf16(a @ bt^T), which never reaches memory (b4c_gemm_nt_ln_bwd_add) -> (dx, dgamma,
+    dbeta): gemm_nt(a, bt, n) followed by layernorm_bwd_add, up to the order of the fp32 sums.  a [M, Kp], bt [>= n, Kp] (the dX
+    operand of gemm_nt), x / dx [M, n] contiguous, res an [M, n] view; bf16, n <= 256."""
+    M, K = a.shape
+    n = x.shape[1]
+    _cuda(a, bt, x, stats, gamma, res)
+    if into is not None:
+        dgamma, dbeta = into
+    else:
+        dgamma, dbeta = zeros(n, device=x.device), zeros(n, device=x.device)
+    _ln_vectors(n, gamma, dgamma, dbeta)
+    dx = torch.empty_like(x) if dx is None else dx
+    if not gemm_ln_bwd_supported(a, bt, n) or bt.shape[0] < n or bt.shape[1] < K:
+        raise B4CError('gemm_nt_ln_bwd_add: a [M, K] and bt [>= %d, >= K] must be bf16 with 16-byte rows, K a multiple of 8, at most 256 '
+                       'columns' % n)
+    if x.dtype != a.dtype or x.shape[0] != M or not x.is_contiguous() or dx.dtype != x.dtype or dx.shape != x.shape or \
+            not dx.is_contiguous():
+        raise B4CError('gemm_nt_ln_bwd_add: x and dx must be contiguous bf16 [%d, %d] tensors' % (M, n))
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (M, 2) or not stats.is_contiguous():
+        raise B4CError('gemm_nt_ln_bwd_add: stats must be the contiguous float32 [%d, 2] tensor of the forward call' % M)
+    if res.dtype != x.dtype or tuple(res.shape) != (M, n) or res.stride(1) != 1 or (res.stride(0) * res.element_size()) % 16 or \
+            res.data_ptr() % 16:
+        raise B4CError('gemm_nt_ln_bwd_add: res must be a [%d, %d] %s view with unit column stride' % (M, n, x.dtype))
+    if M == 0:
+        return dx, dgamma, dbeta
+    ws = _workspace('ln_bwd', x.device, L.lib().b4c_gemm_nt_ln_bwd_add_workspace_bytes(M, n))
+    with _record('gemm_nt_ln_bwd_add', (M * K + n * K + 3 * M * n) * 2 + 8 * M, 2 * M * n * K):
+        L.check(L.lib().b4c_gemm_nt_ln_bwd_add(_p(a), a.stride(0), _p(bt), bt.stride(0), _p(x), _p(stats), _p(gamma), _p(res),
+                                               res.stride(0), _p(dx), _p(dgamma), _p(dbeta), M, n, K, ws.data_ptr(),
+                                               ws.numel() * ws.element_size(), dt_code(x.dtype), _st()), 'gemm_nt_ln_bwd_add')
+    return dx, dgamma, dbeta
+
+
 def mask_positions(ids, value, cap=None, poison=None):
     """-> counts[B], offsets[B+1], flat_idx[cap], maxcount[1] (all int32, device).  More matches than `cap`: offsets stay
     within cap, maxcount comes back as -(longest row) - 1 and the int32 flag `poison` (optional) is set to -1 (include/b4c.h)."""
@@ -2745,6 +2818,183 @@ class FFNBlockFn(torch.autograd.Function):
         return sink_returns(ctx, (dx,), actx, sinks)
 
 
+# ---- pre-LN encoder halves (norm='pre'):  x' = x + drop(sublayer(LN(x; gamma, beta))),  no reference counterpart ---------------
+# The residual stream x is what a half takes and returns; the normalised rows n = LN(x) and their stats ride beside it.  The
+# forward needs no launch of its own: the tail kernel of the post-LN half (_residual_ln_fwd) writes z = x + drop(a W^T + b) AND
+# LN(z), so with the NEXT norm's gamma / beta its two outputs are the stream and the next half's normalised input -- the LayerNorm
+# parameters shift by one place, one layernorm_fwd in front of the first layer starts the chain and the last half is given the
+# encoder's final norm.  n and stats are therefore NON-differentiable companions: the half that consumes them owns their LayerNorm
+# backward and adds it to the stream's gradient (layernorm_bwd_add), with its own gamma / beta sinks.  The four persistent
+# kernels (b4c_ffn_bwd, b4c_ffn_act_bwd, b4c_attn_out_bwd, b4c_ffn_fwd / b4c_ffn_act_fwd) are post-LN kernels and are not taken;
+# actx.fused_blocks is not set (background_dw_expected(norm='pre')).
+#
+# The input-gradient step of a half -- dn = dqkv Wqkv^T (dn = dh W1^T) with the weight gradient n^T dqkv (n^T dh), then
+# dx = g + LNbwd(dn) -- has three forms.  'pair': b4c_gemm_nt, then b4c_layernorm_bwd_add, the weight gradient queued for the
+# layer's grouped launch; it exists everywhere.  'fused': b4c_gemm_nt_ln_bwd_add does both in one pass and dn never reaches memory
+# (bf16, d_model <= 256: gemm_ln_bwd_supported), the weight gradient queued as in 'pair'.  'dxdw': the attention half's step takes
+# b4c_gemm_dxdw (dn and dW in one pass over dqkv; bf16, d_model 128, an arena, 4,096 rows or more) and b4c_layernorm_bwd_add; its
+# feed-forward half, and every shape b4c_gemm_dxdw does not take, runs 'pair'.  B4C_PRE_LN_INPUT_BWD names the form.
+pre_ln_input_bwd = os.environ.get('B4C_PRE_LN_INPUT_BWD', 'dxdw')
+PRE_LN_INPUT_BWD_FORMS = ('dxdw', 'pair', 'fused')
+
+
+def _pre_ln_input_form():
+    if pre_ln_input_bwd not in PRE_LN_INPUT_BWD_FORMS:
+        raise ValueError('pre_ln_input_bwd must be one of %r, got %r' % (PRE_LN_INPUT_BWD_FORMS, pre_ln_input_bwd))
+    return pre_ln_input_bwd
+
+
+def _pre_ln_input_bwd(g_in, wc, x, stats, gamma, g, sinks):
+    """dx = g + LNbwd(g_in wc^T; x, stats, gamma) in the 'fused' form where the kernel takes the shape, else as the pair"""
+    d = x.shape[1]
+    if _pre_ln_input_form() == 'fused' and gemm_ln_bwd_supported(g_in, wc, d):
+        return gemm_nt_ln_bwd_add(g_in, wc, x, stats, gamma.detach(), g, into=sinks)[0]
+    return layernorm_bwd_add(gemm_nt(g_in, wc, d), x, stats, gamma.detach(), g, into=sinks)[0]
+
+
+def _pre_ln_tail_fwd(a, wt, bias, x, next_gamma, next_beta, rate, seed):
+    """-> (x' = x + drop(a @ wt^T + bias), n' = LN(x'; the next norm), its stats): _residual_ln_fwd in its training form, so that
+    the stream is produced in inference too"""
+    return _residual_ln_fwd(a, wt, bias, x, next_gamma, next_beta, rate, seed, True)
+
+
+def _pre_ln_stream_grad(g, dtype, rate, seed):
+    """(g as the kernels take it, the sublayer output's gradient drop(g)): the keep rule on e = t * d_model + col, as the forward's"""
+    g = _rows_ok(g, dtype).contiguous()
+    return g, (dropout(g, rate, seed) if rate > 0 else g)
+
+
+class PreLNAttnBlockFn(torch.autograd.Function):
+    """The attention half of a pre-LN layer.  apply(x, <the ten parameters of AttnBlockFn: gamma, beta = THIS half's norm>, n, stats,
+    key_pad, next_gamma, next_beta, pk_qkv, pk_o, B, S, H, rate, seed, training, cu, attn_rate, attn_seed, causal)
+    -> (x', n', stats'):  n = LN(x; gamma, beta) and stats as the previous tail (or layernorm_fwd) left them;
+    x' = x + drop(MHA(n, n, n) Wo + bo), n' = LN(x'; next_gamma, next_beta).  Only x' is differentiable, and only in x."""
+
+    @staticmethod
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta, n, stats, key_pad, next_gamma, next_beta, pk_qkv, pk_o, B, S, H,
+                rate, seed, training, cu=None, attn_rate=0.0, attn_seed=0, causal=False):
+        T_tok, d = x.shape
+        dh = d // H
+        wt_qkv, _, b_qkv = pk_qkv.get(x.dtype, d, training)
+        wt_o, _, b_o = pk_o.get(x.dtype, d, training)
+        with _timed('qkv_fwd'):
+            qkv = gemm_nt(n, wt_qkv, 3 * d, b_qkv)
+        attn_drop = {'rate': attn_rate, 'seed': attn_seed} if attn_rate > 0 else {}
+        if causal:
+            attn_drop['causal'] = True
+        with _timed('attn_fwd'):
+            o, lse = attn_fwd(qkv, key_pad, B, S, H, dh, cu, **attn_drop)
+        z, out, stats2 = _pre_ln_tail_fwd(o, wt_o, b_o, x, next_gamma, next_beta, rate, seed)
+        if training:
+            ctx.save_for_backward(x, n, stats, key_pad, qkv, o, lse, gamma)
+            ctx.pk = (pk_qkv, pk_o)
+            ctx.dims = (B, S, H, dh, rate, seed)
+            ctx.cu = cu
+            ctx.attn_drop = attn_drop
+            ctx.params = (wq, bq, wk, bk, wv, bv, wo, bo, gamma, beta)
+        ctx.mark_non_differentiable(out, stats2)
+        return z, out, stats2
+
+    @staticmethod
+    def backward(ctx, g, _dn, _dstats):
+        x, n, stats, key_pad, qkv, o, lse, gamma = ctx.saved_tensors
+        pk_qkv, pk_o = ctx.pk
+        B, S, H, dh, rate, seed = ctx.dims
+        wq, bq, wk, bk, wv, bv, wo, bo, gam, bet = ctx.params
+        d = H * dh
+        actx, sinks = grad_sinks(*ctx.params)
+        gwq, gbq, gwk, gbk, gwv, gbv, gwo, gbo, ggam, gbet = sinks
+        routes = _arena_routes(actx)
+        _, wc_o, _ = pk_o.get(x.dtype, d, True)
+        _, wc_qkv, _ = pk_qkv.get(x.dtype, d, True)
+        g, dy = _pre_ln_stream_grad(g, x.dtype, rate, seed)
+        if routes and fused_dxdw >= 3 and dxdw_supported(o, dy, 1):
+            d_o = gemm_dxdw(o, dy, wc_o, [gwo], [gbo])
+            _ready(wo, bo)
+        else:
+            queue_dw(actx, o, dy, d, d, [gwo], [gbo], (wo, bo))
+            d_o = gemm_nt(dy, wc_o, d)
+        with _timed('attn_bwd'):
+            dqkv = attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, ctx.cu, actx, **ctx.attn_drop)
+        # the weight-gradient operand is the normalised rows; the input gradient is the stream's plus the norm's backward
+        if _pre_ln_input_form() == 'dxdw' and routes and fused_dxdw and dxdw_supported(n, dqkv, 3):
+            dn = gemm_dxdw(n, dqkv, wc_qkv, [gwq, gwk, gwv], [gbq, gbk, gbv])
+            _ready(wq, bq, wk, bk, wv, bv)
+            dx, _, _ = layernorm_bwd_add(dn, x, stats, gamma.detach(), g, into=(ggam, gbet))
+        else:
+            queue_dw(actx, n, dqkv, d, 3 * d, [gwq, gwk, gwv], [gbq, gbk, gbv], (wq, bq, wk, bk, wv, bv))
+            dx = _pre_ln_input_bwd(dqkv, wc_qkv, x, stats, gamma, g, (ggam, gbet))
+        _ready(gam, bet)
+        flush_pending_dw(actx)      # this layer's weight gradients (two queued by PreLNFFNBlockFn.backward) in one launch
+        return sink_returns(ctx, (dx,), actx, sinks)
+
+
+class PreLNFFNBlockFn(torch.autograd.Function):
+    """The feed-forward half of a pre-LN layer.  apply(x, w1, b1, w2, b2, gamma, beta, n, stats, next_gamma, next_beta, pk1, pk2,
+    rate, seed, training, act) -> (x', n', stats'):  x' = x + drop(act(n W1 + b1) W2 + b2) with n = LN(x; gamma, beta) given,
+    n' = LN(x'; next_gamma, next_beta).  A GELU saves the pre-activation beside the activation, as FFNBlockFn does."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, n, stats, next_gamma, next_beta, pk1, pk2, rate, seed, training,
+                act=L.ACT_RELU):
+        T_tok, d = x.shape
+        wt1, _, bb1 = pk1.get(x.dtype, d, training)
+        Fp = pk1.Np
+        wt2, _, bb2 = pk2.get(x.dtype, Fp, training)
+        relu = act == L.ACT_RELU
+        u = torch.empty(T_tok, Fp, dtype=x.dtype, device=x.device) if (training and not relu) else None
+        h = gemm_nt(n, wt1, Fp, bb1, act=act, pre=u)
+        z, out, stats2 = _pre_ln_tail_fwd(h, wt2, bb2, x, next_gamma, next_beta, rate, seed)
+        if training:
+            ctx.save_for_backward(x, n, stats, h, gamma, *(() if relu else (u,)))
+            ctx.pk = (pk1, pk2)
+            ctx.dims = (rate, seed)
+            ctx.act = act
+            ctx.params = (w1, b1, w2, b2, gamma, beta)
+        ctx.mark_non_differentiable(out, stats2)
+        return z, out, stats2
+
+    @staticmethod
+    def backward(ctx, g, _dn, _dstats):
+        x, n, stats, h, gamma = ctx.saved_tensors[:5]
+        pk1, pk2 = ctx.pk
+        rate, seed = ctx.dims
+        relu = ctx.act == L.ACT_RELU
+        w1, b1, w2, b2, gam, bet = ctx.params
+        d, Fp = x.shape[1], h.shape[1]
+        actx, sinks = grad_sinks(*ctx.params)
+        gw1, gb1, gw2, gb2, ggam, gbet = sinks
+        _, wc1, _ = pk1.get(x.dtype, d, True)
+        _, wc2, _ = pk2.get(x.dtype, Fp, True)
+        g, dy = _pre_ln_stream_grad(g, x.dtype, rate, seed)
+        queue_dw(actx, h, dy, pk2.K, d, [gw2], [gb2], (w2, b2))
+        dh = gemm_nt(dy, wc2, Fp, gate=h) if relu else gemm_nt(dy, wc2, Fp, gate=ctx.saved_tensors[5], gate_act=ctx.act)
+        queue_dw(actx, n, dh, d, pk1.N, [gw1], [gb1], (w1, b1))
+        dx = _pre_ln_input_bwd(dh, wc1, x, stats, gamma, g, (ggam, gbet))
+        _ready(gam, bet)
+        return sink_returns(ctx, (dx,), actx, sinks)
+
+
+class PreLNFinalNormFn(torch.autograd.Function):
+    """The encoder's final norm.  apply(x, gamma, beta, n, stats) -> n = LN(x; gamma, beta), which the last half's tail has already
+    computed: nothing is launched in the forward; the backward is layernorm_bwd (the stream ends here: no residual term)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, n, stats, training):
+        if training:
+            ctx.save_for_backward(x, stats, gamma)
+            ctx.params = (gamma, beta)
+        return n.view_as(n)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, stats, gamma = ctx.saved_tensors
+        actx, sinks = grad_sinks(*ctx.params)
+        dx, _, _ = layernorm_bwd(_rows_ok(dout, x.dtype).contiguous(), x, stats, gamma.detach(), into=tuple(sinks))
+        _ready(*ctx.params)
+        return sink_returns(ctx, (dx,), actx, sinks)
+
+
 class MLPFn(torch.autograd.Function):
     """Chain of dense layers (relu on all but the last): the SoftMaxHead's trunk + vocabulary
     projection (R12, logits).  apply(x, packs, training, out_fp32, relu_last, *[k0, b0, k1, b1, ...]); out_fp32: the last layer's
@@ -2814,12 +3064,17 @@ class MLPFn(torch.autograd.Function):
 overlap_vocab_dw = {'1': True, '0': False}.get(os.environ.get('B4C_OVERLAP_DW', ''), None)
 
 
-def background_dw_expected(d_model, dff, dtype, ffn_activation='relu'):
+def background_dw_expected(d_model, dff, dtype, ffn_activation='relu', norm='post'):
     """Will a model of this shape run the vocabulary head's dW sweep as a background job (see overlap_vocab_dw)?
     (b4c_ffn_bwd is a ReLU kernel: a GELU model takes a fused backward, b4c_ffn_act_bwd, only with `fused_ffn_gelu`, which is off
-    by default, and otherwise keeps the background sweep.)"""
+    by default, and otherwise keeps the background sweep.  norm='pre': the fused backward kernels are post-LN kernels, a pre-LN
+    model takes none of them and answers as an unfused model does.)"""
+    if norm not in ('post', 'pre'):
+        raise ValueError("norm must be 'post' or 'pre', got %r" % (norm,))
     if overlap_vocab_dw is not None:
         return overlap_vocab_dw
+    if norm == 'pre':
+        return True
     return not (fused_ffn_bwd and d_model == 128 and dff <= 128 and dtype == torch.bfloat16 and
                 (ffn_activation == 'relu' or fused_ffn_gelu))
 

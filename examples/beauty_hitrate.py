@@ -41,16 +41,19 @@ def popularity_buckets(counts, K):
     return bucket
 
 
-def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='bidirectional', tied_head=False, buckets=0):
+def build_model(V, dropout, dtype, seed=1234, paper_positions=None, attention='bidirectional', tied_head=False, buckets=0, norm='post'):
     """paper_positions (the longest encoder input): the BERT4Rec paper's model, one constructor call.
     buckets K > 0: a second embedded feature of K values, summed with the item's embedding (the width stays 64).
     attention='causal': left-to-right self-attention (SASRec, the paper's unidirectional arm).
+    norm='pre': pre-LN encoder blocks and a final LayerNorm (the common SASRec re-implementations; the reference's blocks are post-LN).
     tied_head: score an item by the dot product of the encoder output with its embedding (SASRec's head), in place of the reference's
     dense stack -- the sampled-negative losses (--train_loss bce / softmax / bpr / gbce) need a projection stored per item."""
     from bert4clickpath_amd.clickstream_transformer import ClickstreamTransformer, ClozeMaskedItemPrediction, SoftMaxHead
     torch.manual_seed(seed)            # CPU generator: identical initial weights on any machine
     vocab = ['item%d' % i for i in range(V)]
     kw = {'attention': attention} if attention != 'bidirectional' else {}
+    if norm != 'post':
+        kw['norm'] = norm
     if paper_positions is not None:
         return ClickstreamTransformer({'items': ['asin']}, {'items': vocab}, {'items': 64},
                                       ClozeMaskedItemPrediction([], V, transform='gelu_tanh'), value_to_head='[MASK]',
@@ -180,6 +183,9 @@ def main():
     ap.add_argument('--attention', default='bidirectional', choices=['bidirectional', 'causal'],
                     help='causal: left-to-right self-attention inside the kernels; with --device_batches --last_item_rate 1.0 a '
                          'left-to-right next-item model (every training row predicts the item after its prefix)')
+    ap.add_argument('--norm', default='post', choices=['post', 'pre'],
+                    help='pre: pre-LN encoder blocks, x + drop(sublayer(LayerNorm(x))), and one LayerNorm behind the last layer (q, k and v '
+                         'all from the normalised rows; the full last layer always runs); post: the reference\'s blocks')
     ap.add_argument('--mq_causal', action='store_true',
                     help='with --attention causal: evaluate the last encoder layer at the rows the head reads only (ops.mq_causal, off '
                          'by default; with attention dropout in training also B4C_MQ_ATTN_DROPOUT=1); the next-item evaluation names '
@@ -207,7 +213,7 @@ def main():
     dtype = torch.float32 if a.dtype == 'f32' else torch.bfloat16
     longest = (int(np.diff(data.offsets).max()) if a.max_len is None else a.max_len) + 3       # [CLS] [SEP] items [SEP]
     model = build_model(data.V, a.dropout, dtype, paper_positions=longest if a.paper_model else None, attention=a.attention,
-                        tied_head=a.train_loss != 'full', buckets=a.popularity_buckets).cuda()
+                        tied_head=a.train_loss != 'full', buckets=a.popularity_buckets, norm=a.norm).cuda()
     lr = WarmupLinearDecay(1e-3, a.warmup, max(a.steps, a.warmup + 1)) if a.warmup > 0 else 1e-3
     opt = optim.Adam(model.parameters(), learning_rate=lr, global_clipnorm=a.clipnorm, weight_decay=a.weight_decay,
                      exclude_from_weight_decay=optim.no_decay_params(model) if a.weight_decay is not None else ())

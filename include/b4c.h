@@ -891,5 +891,7 @@ int b4c_attn_mq_bwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, con
 #include "b4c_batch_features.h" /* b4c_batch_features / _row, B4C_FEAT_*: side features beside the items of a device-built batch */
 #include "b4c_cand_loss_ex.h" /* b4c_candidate_loss_fwd_ex, B4C_CANDX_*: BPR, a weighted BCE target term and a logQ correction for the lists */
 #include "b4c_attn_mq_ex.h" /* b4c_attn_mq_fwd_ex / _bwd_ex: the masked-query kernels with flags (B4C_ATTN_CAUSAL: the causal last layer) */
+/* ---- the pre-LN header: _lib.py binds it from a list of its own (PRE_LN_HEADER_PATHS, pre_ln_signatures()). */
+#include "b4c_pre_ln.h" /* b4c_layernorm_bwd_add: the residual gradient + LayerNorm backward of a pre-LN encoder half */
 
 #endif /* B4C_H */
