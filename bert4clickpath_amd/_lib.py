@@ -6,19 +6,7 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('B4C_LIB_PATH') or os.path.join(_HERE, 'libb4c_hip.so')     # override: A/B of two builds (scratch)
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')
-# extension headers: further entry points of the same ABI in files of their own, which b4c.h includes (a C caller includes b4c.h alone)
-EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_ex.h'),)
-# add-on headers: the entry points of later features, one header each, which b4c.h includes as well.  A feature adds its header
-# here: lib() binds whatever these declare (addon_signatures()); signatures() and all_signatures() keep to the lists above.
-ADDON_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss.h'),
-                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_next_item.h'),
-                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_batch_features.h'),
-                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_cand_loss_ex.h'),
-                      os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_mq_ex.h'))
-# pre-LN headers: the entry points of the pre-LN encoder blocks, which b4c.h includes too.  A list of its own: lib() binds what it
-# declares (pre_ln_signatures()); signatures(), all_signatures() and addon_signatures() keep to the lists above.
-PRE_LN_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_pre_ln.h'),)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')      # the whole ABI: a feature adds its entry points there
 
 
 class B4CError(RuntimeError):
@@ -82,8 +70,10 @@ def parse_header(src):
         if not decl:
             continue
         m = re.fullmatch(r'(.*?)\b(\w+) ?\(([^()]*)\)', decl)
-        if not m or not m.group(1).strip() or m.group(2) in table:
+        if not m or not m.group(1).strip():
             raise B4CError('include/b4c.h: cannot parse the declaration %r' % decl)
+        if m.group(2) in table:                      # (the one duplicate check of the ABI: one header, one table)
+            raise B4CError('include/b4c.h declares %s twice: %r' % (m.group(2), decl))
         ret, name, args = m.groups()
         args = [] if args.strip() == 'void' else [_ctype(a, decl) for a in args.split(',')]
         table[name] = (_ctype(ret, decl, True), args)
@@ -96,53 +86,16 @@ def header_constants(src):
 
 
 def signatures(header_path=HEADER_PATH):
+    """{name: (restype, [argtypes])} of every entry point include/b4c.h declares: the whole ABI, and what lib() binds."""
     return parse_header(_header_text(header_path))
 
 
 def declared_symbols(header_path=HEADER_PATH):
-    """Names of every function include/b4c.h declares (used by the symbol-export test)."""
+    """Names of every function include/b4c.h declares (build() and the symbol-export test compare them with the library's exports)."""
     return sorted(signatures(header_path))
 
 
-def all_signatures():
-    """signatures() of include/b4c.h and of every extension header it includes: what lib() binds.  A name declared twice raises."""
-    table = signatures()
-    for path in EXT_HEADER_PATHS:
-        for name, sig in signatures(path).items():
-            if name in table:
-                raise B4CError('%s declares %s, which another header of the ABI declares too' % (path, name))
-            table[name] = sig
-    return table
-
-
-def addon_signatures():
-    """signatures() of every add-on header (ADDON_HEADER_PATHS): what lib() binds beside all_signatures().  A name that another
-    header of the ABI declares raises."""
-    taken = all_signatures()
-    table = {}
-    for path in ADDON_HEADER_PATHS:
-        for name, sig in signatures(path).items():
-            if name in taken or name in table:
-                raise B4CError('%s declares %s, which another header of the ABI declares too' % (path, name))
-            table[name] = sig
-    return table
-
-
-def pre_ln_signatures():
-    """signatures() of every pre-LN header (PRE_LN_HEADER_PATHS): what lib() binds beside all_signatures() and addon_signatures().
-    A name that another header of the ABI declares raises."""
-    taken = dict(all_signatures())
-    taken.update(addon_signatures())
-    table = {}
-    for path in PRE_LN_HEADER_PATHS:
-        for name, sig in signatures(path).items():
-            if name in taken or name in table:
-                raise B4CError('%s declares %s, which another header of the ABI declares too' % (path, name))
-            table[name] = sig
-    return table
-
-
-_C = header_constants(''.join(_header_text(p) for p in (HEADER_PATH,) + EXT_HEADER_PATHS + ADDON_HEADER_PATHS + PRE_LN_HEADER_PATHS))
+_C = header_constants(_header_text(HEADER_PATH))
 ABI_VERSION = _C['B4C_ABI_VERSION']       # b4c_abi_version() of the library must agree
 F32, BF16 = _C['B4C_F32'], _C['B4C_BF16']
 ACT_NONE, ACT_RELU = _C['B4C_ACT_NONE'], _C['B4C_ACT_RELU']
@@ -182,7 +135,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        sig = all_signatures()
+        sig = signatures()
         # The argument lists of the header belong to ONE ABI version: a library that exports the same names with older lists would
         # take a device pointer for a stream and fault on the GPU.  Compare before anything is bound.
         try:
@@ -194,7 +147,7 @@ def lib():
         if have != ABI_VERSION:
             raise B4CError('%s is ABI %d, this binding expects ABI %d; rebuild it (`make -C bert4clickpath_amd/csrc`)'
                            % (LIB_PATH, have, ABI_VERSION))
-        for name, (res, args) in list(sig.items()) + list(addon_signatures().items()) + list(pre_ln_signatures().items()):
+        for name, (res, args) in sig.items():
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -158,7 +158,7 @@ class SoftMaxHead(nn.Module):
         """Mean over the rows with a valid target of the sampled-negative loss of each row's own list cand (int32 [R, C], label-space
         ids, target in column 0; < 0 or >= V: absent): kind 'bce', 'softmax' or 'bpr' (ops.CandidateLossFn, b4c_candidate_loss_fwd /
         _fwd_ex / _bwd).  beta weights the target's 'bce' term (gBCE); corr (fp32 [V], data: no gradient) is subtracted from the score
-        of every present negative, and of the target too with correct_target (include/b4c_cand_loss_ex.h).
+        of every present negative, and of the target too with correct_target (include/b4c.h).
         Only the listed rows of the projection are read and receive gradient.  The vocabulary-major heads only."""
         if not self.vocab_major:
             raise ops.B4CError('candidate_loss: %s stores its projection as a Keras kernel [K][V], whose gradient is not row-sparse; '

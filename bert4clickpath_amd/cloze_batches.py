@@ -14,13 +14,13 @@ sequence into sliding windows and keep the most recent max_len positions for eva
 item for validation and the last for test, last_item_rate adds training rows whose only masked position is the last one.  The
 window table is built once with numpy and uploaded once; a batch names its windows by index.
 
-The next_item_* methods build the left-to-right objective over the same windows (ops.next_item_batch, include/b4c_next_item.h): rows
+The next_item_* methods build the left-to-right objective over the same windows (ops.next_item_batch, include/b4c.h): rows
 without a [MASK], every real position's target the item after it, each target's own sampled negatives; model.next_item_loss takes
 such a batch.
 
 features={name: Feature(...)} hands over side columns of the click paths -- one value per event (an action, a dwell bucket) or one
 per item (a category, a brand).  They are validated and uploaded once; every batch dict then carries 'features': {name: (B, W)
-int64 ids} built from the item row in one launch (ops.batch_features, include/b4c_batch_features.h), [MASK] where the item row has
+int64 ids} built from the item row in one launch (ops.batch_features, include/b4c.h), [MASK] where the item row has
 it unless the feature says on_mask='keep'.  inputs(batch, item_feature) is the dict the model's entry points take."""
 import collections
 
@@ -313,7 +313,7 @@ class DeviceCloze:
         for s in range(0, n, batch_size):
             yield self._batch(table, seq[s:s + batch_size], seq_dev[s:s + batch_size], seq_dev[s:s + batch_size], EVAL, 0, width)
 
-    # ---- next-item batches: every real position predicts the item after it (include/b4c_next_item.h) -------------------------
+    # ---- next-item batches: every real position predicts the item after it (include/b4c.h) -------------------------
     def next_item_counts(self, win_idx):
         """host int64: inputs (= targets) of the TRAIN next-item row of every named window; a negative index: 0.  A window at
         a > 0 takes one extra input in front, the first window of a sequence gives up its last item as a target only."""

@@ -414,7 +414,7 @@ extern "C" int b4c_attn_bwd_varlen_drop(const void *qkv, int ld_qkv, const uint8
                            max_len, H, dh, workspace, workspace_bytes, dropout_rate, seed, false, dtype, stream);
 }
 
-// ---- one entry point per direction that takes everything (include/b4c_attn_ex.h): layout by cu_seqlens (NULL: dense), dropout by the
+// ---- one entry point per direction that takes everything (include/b4c.h): layout by cu_seqlens (NULL: dense), dropout by the
 // rate, causal masking by flags.  flags == 0 reaches exactly the launches of the entry points above.
 extern "C" int b4c_attn_fwd_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
                                float *lse, int B, int S, int H, int dh, int dtype, void *stream, float dropout_rate, uint64_t seed,

@@ -904,7 +904,7 @@ extern "C" int b4c_attn_mq_fwd_drop(const void *q, int ld_q, const void *kv, int
                       q_rows, dropout_rate, seed, false);
 }
 
-// b4c_attn_mq_ex.h: the *_drop entry point with flags (0: its very launches)
+// b4c_attn_mq_*_ex: the *_drop entry point with flags (0: its very launches)
 extern "C" int b4c_attn_mq_fwd_ex(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
                                   const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype,
                                   void *stream, const int32_t *q_rows, float dropout_rate, uint64_t seed, uint32_t flags) {

@@ -1,4 +1,4 @@
-// Side features beside the items of a device-built batch (include/b4c_batch_features.h): per batch row the ids of up to four
+// Side features beside the items of a device-built batch (include/b4c.h): per batch row the ids of up to four
 // further features -- gathered by token (EVENT) or through the item (ITEM) -- with [MASK] copied from the item row where the
 // feature asks for it.  A pure gather: B W 8 bytes read, n_feat B W 8 written, 4 n (1 + n_feat) gathered; no LDS, no atomics.
 //

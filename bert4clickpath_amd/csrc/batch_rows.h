@@ -8,7 +8,7 @@
 #define ROW_MASK_ID 1
 #define ROW_INPUT_PAD 0
 
-// The layouts are b4c_batch_features.h's codes.  That of a next-item mode, one of two: a kernel that says so carries no Cloze branch.
+// The layouts are b4c_batch_features' codes (B4C_FEAT_*).  That of a next-item mode, one of two: a kernel that says so carries no Cloze branch.
 __host__ __device__ __forceinline__ int next_item_layout(int mode) { return mode == B4C_NEXT_TRAIN ? B4C_FEAT_NEXT_TRAIN : B4C_FEAT_NEXT_EVAL; }
 
 // ---- the window fetch --------------------------------------------------------------------------------------------------------

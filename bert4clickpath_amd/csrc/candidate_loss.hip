@@ -1,4 +1,4 @@
-// Sampled-negative training (include/b4c_cand_loss.h, include/b4c_cand_loss_ex.h): the loss of each row over its own candidate
+// Sampled-negative training (include/b4c.h): the loss of each row over its own candidate
 // list -- target in column 0; SASRec's binary cross-entropy (its target term weighted by beta: gBCE), the list-wise softmax or BPR,
 // over scores that a per-item correction (logQ) may shift -- and its backward into dh and the row-sparse fp32 gradient sinks.
 //

@@ -1,4 +1,4 @@
-// Next-item batches built on the device (include/b4c_next_item.h): per window the unmasked input row, the compact positions and
+// Next-item batches built on the device (include/b4c.h): per window the unmasked input row, the compact positions and
 // shifted targets of every real position, and each target's own negatives -- none of them an item of the sequence.
 //
 // One 256-thread workgroup per batch row, four phases:

@@ -1,4 +1,4 @@
-// Pre-LN encoder halves (include/b4c_pre_ln.h): x' = x + drop(sublayer(LN(x))).  The forward runs on the post-LN launches with the
+// Pre-LN encoder halves (include/b4c.h): x' = x + drop(sublayer(LN(x))).  The forward runs on the post-LN launches with the
 // LayerNorm parameters shifted by one place; the backward needs  dx = g + LNbwd(dn; x, stats, gamma)  -- the residual stream's
 // gradient g added to the LayerNorm backward of the sublayer-input gradient dn.  The row kernel here is b4c_layernorm_bwd's (its
 // row body: ln_bwd_rows.h) with that sum as its epilogue, rounded once more at the store; b4c_layernorm_bwd launches the same kernel.

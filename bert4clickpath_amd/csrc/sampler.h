@@ -1,5 +1,5 @@
 // The negative sampler of candidates.hip (b4c_sample_candidates) and of next_item_batch.hip, which promises each of its lists to be
-// what b4c_sample_candidates draws for that one target (include/b4c_next_item.h): one wave per list, both call sampler_wave.
+// what b4c_sample_candidates draws for that one target (include/b4c.h): one wave per list, both call sampler_wave.
 #pragma once
 #include "common.h"
 

@@ -973,7 +973,7 @@ def _attn_rate(rate):
     return rate
 
 
-ATTN_CAUSAL = L.ATTN_CAUSAL        # B4C_ATTN_CAUSAL of include/b4c_attn_ex.h (flags of the b4c_attn_*_ex entry points)
+ATTN_CAUSAL = L.ATTN_CAUSAL        # B4C_ATTN_CAUSAL of include/b4c.h (flags of the b4c_attn_*_ex entry points)
 
 
 def _attn_pairs(T_tok, S, cu, causal):
@@ -1710,7 +1710,7 @@ def _cand_loss_args(who, h, table, row_off, V, cand):
 
 def candidate_loss_fwd(h, table, bias, cand, V, kind, row_off=0, want_scores=False):
     """-> (item_loss fp32 [R], g fp32 [R, C], scores fp32 [R, C] or None) of each row's own candidate list, target in column 0
-    (b4c_candidate_loss_fwd, include/b4c_cand_loss.h): kind 'bce' = softplus(-s_0) + sum of softplus(s_c) over the other present
+    (b4c_candidate_loss_fwd, include/b4c.h): kind 'bce' = softplus(-s_0) + sum of softplus(s_c) over the other present
     entries, 'softmax' = logsumexp over the present entries - s_0; g the loss's derivative by each score.  An entry < 0 or >= V is
     absent (g = 0); a row whose column 0 is absent is ignored (loss 0, g = 0).  s = h . table[row_off + id] + bias[id] in fp32;
     for bf16 h the table's elements are rounded to bf16 first.  h [R, K] bf16 or fp32, table the fp32 master [rows, >= K]."""
@@ -1737,7 +1737,7 @@ CANDX_LOSS_KINDS = {'bce': L.CANDX_BCE, 'softmax': L.CANDX_SOFTMAX, 'bpr': L.CAN
 
 
 def candidate_loss_fwd_ex(h, table, bias, cand, V, kind, row_off=0, want_scores=False, beta=1.0, corr=None, correct_target=False):
-    """candidate_loss_fwd with the additions of include/b4c_cand_loss_ex.h (b4c_candidate_loss_fwd_ex) -> (item_loss, g, scores or
+    """candidate_loss_fwd with the additions of include/b4c.h (b4c_candidate_loss_fwd_ex) -> (item_loss, g, scores or
     None).  kind 'bce' = beta * softplus(-z_0) + sum of softplus(z_c) (beta finite, >= 0; 1.0: SASRec's, another value: gSASRec's
     gBCE), 'softmax' as there, 'bpr' = sum over the present negatives of softplus(z_c - z_0).  z = s - corr[id] at every present
     negative, and at the target too with correct_target (corr fp32 [>= V], e.g. cloze.log_expected_count: the logQ correction);
@@ -1979,7 +1979,7 @@ def cloze_history(items, offsets, seq_idx, E, drop=1):
     return out
 
 
-NEXT_TRAIN, NEXT_EVAL = L.NEXT_TRAIN, L.NEXT_EVAL            # modes of next_item_batch (include/b4c_next_item.h)
+NEXT_TRAIN, NEXT_EVAL = L.NEXT_TRAIN, L.NEXT_EVAL            # modes of next_item_batch (include/b4c.h)
 NEXT_EXCLUDE = {None: L.NEXT_EXCL_NONE, 'history': L.NEXT_EXCL_HISTORY}
 
 
@@ -2002,7 +2002,7 @@ def _next_item_args(who, W, mode, holdout, max_len, V, num_negatives, seed, excl
 def next_item_batch(items, offsets, win_seq, win_start, win_len, row_win, row_off, W, mode, n_targets, V, holdout=1, max_len=None,
                     num_negatives=0, seed=0, exclude='history', item_cdf=None, rows=None):
     """-> (items_out int64 [B, W], flat_idx int32 [rows], labels int32 [rows], cand int32 [rows, 1 + N] or None, short int32 [1])
-    (b4c_next_item_batch, include/b4c_next_item.h): the next-item batch of the rows row_win -- NEXT_TRAIN: windows of the device
+    (b4c_next_item_batch, include/b4c.h): the next-item batch of the rows row_win -- NEXT_TRAIN: windows of the device
     table (win_seq, win_start, win_len), every input position's target the item after it; NEXT_EVAL: sequences, one target each
     (item n_g - holdout) behind the most recent max_len inputs; a negative entry: an empty row.  No [MASK] anywhere.
     row_off int32 [B + 1]: the exclusive prefix sum of the rows' target counts, on the device; n_targets = row_off[B] as the HOST
@@ -2080,7 +2080,7 @@ def next_item_row_host(seq, seq_off, W, mode, V, a=0, L=0, holdout=1, max_len=No
             'n_in': int(counts[0]), 'short': int(counts[2])}
 
 
-# ---- side features beside the items of a device-built batch (include/b4c_batch_features.h) ----
+# ---- side features beside the items of a device-built batch (include/b4c.h) ----
 FEAT_EVENT, FEAT_ITEM = L.FEAT_EVENT, L.FEAT_ITEM                  # where a feature's value comes from: the token / the item
 FEAT_MASKED, FEAT_KEPT = L.FEAT_MASKED, L.FEAT_KEPT                # what a [MASK] of the item row does to the feature
 FEAT_CLOZE, FEAT_NEXT_TRAIN, FEAT_NEXT_EVAL = L.FEAT_CLOZE, L.FEAT_NEXT_TRAIN, L.FEAT_NEXT_EVAL      # the row geometry
@@ -2104,7 +2104,7 @@ def _batch_features_args(who, W, layout, holdout, max_len, per, on_mask):
 
 
 def batch_features(items, offsets, win_seq, win_start, win_len, row_win, W, layout, items_in, sources, holdout=1, max_len=None):
-    """-> [out_f int64 [B, W] for every source] (b4c_batch_features, include/b4c_batch_features.h): the side features of the batch
+    """-> [out_f int64 [B, W] for every source] (b4c_batch_features, include/b4c.h): the side features of the batch
     rows whose item row items_in int64 [B, >= W] has just been built -- layout FEAT_CLOZE: by cloze_batch_windows from the windows
     row_win of the device table (win_seq, win_start, win_len); FEAT_NEXT_TRAIN / FEAT_NEXT_EVAL: by next_item_batch in that mode
     with the same holdout / max_len (EVAL: row_win names sequences, the table is not read).  row_win None: row b is window b.
@@ -3696,8 +3696,8 @@ class SampledCEFn(torch.autograd.Function):
 
 
 class CandidateLossFn(torch.autograd.Function):
-    """Sampled-negative masked-item loss over each row's own candidate list, target in column 0 (include/b4c_cand_loss.h,
-    include/b4c_cand_loss_ex.h): 'bce' (SASRec; its target term times beta: gBCE), 'softmax' (list-wise) or 'bpr', mean over the
+    """Sampled-negative masked-item loss over each row's own candidate list, target in column 0 (include/b4c.h):
+    'bce' (SASRec; its target term times beta: gBCE), 'softmax' (list-wise) or 'bpr', mean over the
     rows with a valid target.  The table -- vocabulary-major projection (row_off 0) or tied item embedding (row_off = its id
     offset) -- is read and receives gradient at the listed rows only.
     apply(h [R, K], table (rows, K) fp32, bias (V,) fp32, cand int32 [R, C], row_off, kind, unit_grad[, shared_table[, beta[, corr[,

@@ -877,21 +877,301 @@ int b4c_attn_mq_bwd_drop(const void *q, int ld_q, const void *kv, int ld_kv, con
                          void *dq, int ld_dq, void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream,
                          const int32_t *q_rows, float dropout_rate, uint64_t seed);
 
+/* ==== the attention entry points that take everything (additive to ABI 12) ====================================================== */
+
+/* ---- causal (left-to-right) self-attention (the "look ahead" mask of the reference's scaled_dot_product_attention,
+ * transformer.py:64-97, which its encoder never builds; SASRec and the BERT4Rec paper's unidirectional arm) -- additive to ABI 12 ----
+ * One entry point per direction that takes everything: the layout (cu_seqlens == NULL: dense, S rows per sequence; otherwise the
+ * packed layout with S = max_len and its limits: bf16, head depth 32 / 64, max_len <= 512), attention dropout (dropout_rate, seed
+ * as in the *_drop entry points; 0 = none) and flags.  flags == 0 reaches exactly the launches of b4c_attn_fwd[_varlen][_drop] /
+ * b4c_attn_bwd_ws / _drop_ws / _varlen[_drop] / b4c_attn_weights; an unknown flag bit is B4C_EINVAL.  The backward workspace is
+ * b4c_attn_bwd_workspace_bytes'.
+ * B4C_ATTN_CAUSAL: key k is visible to query q iff k <= q, both counted inside the sequence as the keep rule counts them (dense:
+ * the position; packed: row - cu_seqlens[b]).  Over the visible keys
+ *   P[q][k] = softmax_{k <= q}(q . k / sqrt(dh) + pad[k] * -1e9),   lse[q] = the log-sum-exp over the visible keys,
+ * and the keys behind q are excluded outright (-inf, not -1e9): exactly zero weight and exactly zero gradient whatever the padding
+ * looks like.  Key q is always visible to query q, so no row is empty.  A query whose visible keys are all padded (leading pads
+ * only) comes out finite; its value is not otherwise pinned, as for a sequence without a live key in b4c_attn_fwd.
+ * Dropout: a causal launch draws, for every visible (q, k), the bit b4c_attn_keep(seed, b, h, q, k, H, S, rate) that the
+ * bidirectional launch draws.  b4c_attn_weights_ex returns the undropped P, 0 for k > q, from the lse of a causal forward.
+ * The masked-query kernels (b4c_attn_mq_*) take the same flag through b4c_attn_mq_fwd_ex / b4c_attn_mq_bwd_ex (below).
+ * Not covered: general [Sq][Sk] masks. */
+#define B4C_ATTN_CAUSAL 1u
+int b4c_attn_fwd_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens /* NULL: dense */, void *o,
+                    int ld_o, float *lse, int B, int S /* or max_len */, int H, int dh, int dtype, void *stream,
+                    float dropout_rate, uint64_t seed, uint32_t flags);
+int b4c_attn_bwd_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens /* NULL: dense */,
+                    const void *o, int ld_o, const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv,
+                    int ld_dqkv, int B, int S /* or max_len */, int H, int dh, void *workspace, int64_t workspace_bytes,
+                    int dtype, void *stream, float dropout_rate, uint64_t seed, uint32_t flags);
+int b4c_attn_weights_ex(const void *qkv, int ld_qkv, const uint8_t *key_pad, const float *lse, float *weights, int B, int S,
+                        int H, int dh, int dtype, void *stream, uint32_t flags);
+
+/* ==== sampled-negative training: the loss over a per-row candidate list and its backward (additive to ABI 12) =================== */
+
+/* ---- the definition ----------------------------------------------------------------------------------------------------------
+ * h     [R][K] (pitch ld_h) bf16 or fp32 (dtype), K % 8 == 0, 8 <= K <= 1024, rows 16-byte aligned.
+ * table the fp32 MASTER table [rows][ld_t] (ld_t % 4 == 0, 16-byte aligned); item id is row row_off + id: the vocabulary-major
+ *       projection with row_off = 0, the tied item-embedding table with row_off = its id offset.  row_off + V <= rows.
+ * bias  fp32 [V].
+ * cand  int32 [R][C] (pitch ld_c), 1 <= C <= B4C_MAX_CAND, label-space ids.  Column 0 is the row's TARGET (the layout
+ *       b4c_sample_candidates writes).  An entry < 0 or >= V is ABSENT: no term, coefficient exactly 0.  A row whose column 0 is
+ *       absent is an IGNORED row: loss exactly 0, exactly zero gradient everywhere.  Every present position is its own term: a
+ *       repeated id is not merged.
+ * Score: s_c = sum_k h[k] * w_c[k] + bias[c], fp32 accumulation; for bf16 h every table element is rounded to bf16 (nearest
+ *       even) before the product -- the value the packed copy of the table would hold.  The master table is what is read, so
+ *       the kernels work under the row-lazy optimizer and on a table that is never packed.
+ * kind  B4C_CAND_BCE:     l = softplus(-s_0) + sum_{c >= 1 present} softplus(s_c);   g_0 = sigma(s_0) - 1,  g_c = sigma(s_c)
+ *       B4C_CAND_SOFTMAX: l = logsumexp_{present c} s_c - s_0 (max-subtracted);       g_c = p_c - [c == 0]
+ *                         (C == 1: loss and coefficient exactly 0)
+ *       softplus / sigma in their stable forms (|s| = 100: a finite loss, a coefficient in [0, 1]); expf, log1pf and logf, not the
+ *       fast intrinsics.  Any other kind is B4C_EINVAL.
+ * The model loss is sum_r l_r / max(#rows with a present target, 1), formed by the caller.
+ *
+ * b4c_candidate_loss_fwd: item_loss [R] and the coefficients g [R][ld_g] (0 at absent entries and in ignored rows), fp32;
+ *   scores [R][ld_s] only when given (NaN at absent entries and throughout an ignored row, whose list is not read).  One wave
+ *   per row; the V logits never exist.
+ * b4c_candidate_loss_bwd: with gs = gscale[0] (a DEVICE scalar: 1 / valid rows, times the upstream gradient)
+ *     dh[r][:]                  = gs * sum_c g[r][c] * w_c[:]      fp32 accumulation, stored once in h's dtype (ld_dh, aligned as h)
+ *     dtable[row_off + id][:]  += gs * g[r][c] * h[r][:]           fp32 gradient sinks: ACCUMULATED, no-return float atomics,
+ *     dbias[id]                += gs * g[r][c]                     one table row segment per wave-instruction
+ *   An entry whose gs * g is exactly 0 adds nothing.  Two list entries of a launch that name the same item make dtable / dbias
+ *   depend on the arrival order in the last bits; with pairwise disjoint lists every element receives one add and the result is
+ *   reproducible.  dtable [rows][ld_dt] is addressed like table.
+ * R == 0 is a no-op.  Null pointers, K, C, a pitch below its width, a misaligned operand, kind and dtype are B4C_EINVAL before
+ * any launch. */
+#define B4C_CAND_BCE 0
+#define B4C_CAND_SOFTMAX 1
+#define B4C_CAND_KINDS 2   /* kinds are 0 .. B4C_CAND_KINDS - 1 */
+int b4c_candidate_loss_fwd(const void *h, int ld_h, const float *table, int ld_t, int64_t rows, int64_t row_off, const float *bias,
+                           const int32_t *cand, int ld_c, int64_t R, int C, int V, int K, int dtype, int kind, float *item_loss,
+                           float *g, int ld_g, float *scores /* may be NULL */, int ld_s, void *stream);
+int b4c_candidate_loss_bwd(const void *h, int ld_h, const float *table, int ld_t, int64_t rows, int64_t row_off,
+                           const int32_t *cand, int ld_c, const float *g, int ld_g, const float *gscale, int64_t R, int C, int V,
+                           int K, int dtype, void *dh, int ld_dh, float *dtable, int ld_dt, float *dbias, void *stream);
+
+/* ==== next-item batches built on the device (additive to ABI 12): every real position of a left-to-right row predicts the item
+ * that follows it, each target against its own negatives, none of them an item of the user's ================================== */
+
+/* ---- the rule ----------------------------------------------------------------------------------------------------------------
+ * Data: the CSR data set of the Cloze batches (above, "Cloze batches"): items int32 [n_items] label-space indices, offsets int64
+ * [n_seq + 1]; s_g is sequence g, n_g its length, offsets[g] its start.  Input id = item + 10, pad 0; no [MASK] anywhere.
+ *
+ * TRAIN row of the window (g, a, L) of the table (win_seq, win_start, win_len), with the training view [0, T_g),
+ *   T_g = max(n_g - holdout, 0):  first = a > 0 ? a - 1 : 0,  n_in = a > 0 ? L : max(L - 1, 0)  (a later window takes one extra
+ *   input in front, so abutting windows make every item of the view but the first a target exactly once).
+ *   Input p is s_g[first + p], target p is s_g[first + p + 1], 0 <= p < n_in.  n_in is cut at W and at T_g - first - 1 (a target
+ *   never leaves the view; a table built by the window rule is never cut).
+ * EVAL row of sequence g (row_win names SEQUENCES here; the window table is not read), drop = `holdout` argument (1: the last
+ *   item is the target, 2: the penultimate):  t = n_g - drop,  n_in = min(t, max_len, W),  first = t - n_in.  One target, at the
+ *   last input position p = n_in - 1, label s_g[t].  t < 1: no input and no target.
+ * A negative row_win[b] (or sequence) is an empty row.
+ *
+ * Compact rows: target number q of batch row b (TRAIN: q = p; EVAL: q = 0) is compact row r = row_off[b] + q; row_off int32
+ *   [B + 1] is the exclusive prefix sum of the rows' target counts (the caller forms it from its host-known table; nothing is
+ *   read back), row_off[B] = R.  flat_idx[r] = b * (W + 3) + 2 + p: the position of input p in the chained layout
+ *   [CLS] [SEP] items .. [SEP] of a one-feature model; B * (W + 3) < 2^31.  labels[r] = the target's item index.
+ *   The outputs hold `rows` >= R compact rows: rows R .. rows get flat_idx = -1, label = -1, candidates -1 (the "zero row" of
+ *   b4c_remap_index and of the row gather; a label the losses ignore).  A compact row >= `rows` is never written.
+ *
+ * Negatives (0 <= N < B4C_MAX_CAND; N == 0: no sampler, cand is not written and may be NULL): cand[r] = [y, N negatives] is
+ *   what b4c_sample_candidates returns for ONE row with label y = labels[r], row_base + row = i, where
+ *   i = offsets[g] + first + p + 1 is the CSR index of the target token, the same seed and cdf (NULL: uniform), and the
+ *   exclusion list X_g minus {y}: attempt j draws b4c_rand64(seed, (i << 20) | j), the first N distinct accepted items are kept
+ *   in attempt order, at most 64 N attempts; a short row keeps -1 in its tail and adds one to short_count[0] (zeroed here).
+ *   X_g, excl = B4C_NEXT_EXCL_HISTORY: the items of s_g[max(0, T - B4C_MAX_EXCL) .. T), T = T_g (TRAIN: the training view, never
+ *   a held-out item, the whole sequence's view and not the window's) or t (EVAL: everything in front of the target).
+ *   excl = B4C_NEXT_EXCL_NONE: empty.
+ * The result is a pure function of (seed, data set, g, position, N, cdf, excl): independent of the batch, of the row's place in
+ * it, of the batch size and of the rank.
+ *
+ * b4c_next_item_batch: one workgroup per batch row; X_g is sorted into LDS once and shared by the row's targets, one wave per
+ *   target at a time.  items_out int64 [B][ld_items >= W]: columns 0 .. W of every row are written.  Every refusal -- null
+ *   pointers, W outside 1 .. 1021, N, V, max_len (EVAL), holdout, the pitches, rows, B (W + 3) >= 2^31, mode, excl -- is
+ *   B4C_EINVAL before any launch; B == 0 launches nothing (short_count is still zeroed when given, tails are NOT written).
+ * b4c_next_item_row: the same rule for ONE row on the host, into host arrays -- seq = s_g (n_g items), seq_off = offsets[g];
+ *   (a, L) the window (TRAIN; ignored for EVAL).  inputs_out int64 [W] (ids, 0 past n_in), labels_out int32 [W],
+ *   pos_out int32 [W] (the input position p of each target), cand_out int32 [n_targets][ld_c] (N > 0), counts_out int32 [3] =
+ *   (n_in, n_targets, short rows).  cdf is a HOST array here. */
+#define B4C_NEXT_TRAIN 0
+#define B4C_NEXT_EVAL 1
+#define B4C_NEXT_EXCL_NONE 0
+#define B4C_NEXT_EXCL_HISTORY 1
+int b4c_next_item_batch(const int32_t *items, const int64_t *offsets, const int32_t *win_seq, const int32_t *win_start,
+                        const int32_t *win_len, const int32_t *row_win, const int32_t *row_off, int B, int W, int mode, int holdout,
+                        int max_len, int V, int N, uint64_t seed, int excl, const int64_t *cdf /* may be NULL */, int64_t *items_out,
+                        int ld_items, int32_t *flat_idx, int32_t *labels, int32_t *cand /* NULL iff N == 0 */, int ld_c, int64_t rows,
+                        int32_t *short_count /* NULL iff N == 0 */, void *stream);
+int b4c_next_item_row(const int32_t *seq, int n_g, int64_t seq_off, int a, int L, int W, int mode, int holdout, int max_len, int V, int N,
+                      uint64_t seed, int excl, const int64_t *cdf /* may be NULL */, int64_t *inputs_out, int32_t *labels_out,
+                      int32_t *pos_out, int32_t *cand_out /* NULL iff N == 0 */, int ld_c, int32_t *counts_out);
+
+/* ==== side features beside the items of a device-built batch (additive to ABI 12): for every row that b4c_cloze_batch_windows or
+ * b4c_next_item_batch has just written, the ids of up to B4C_MAX_FEATURES further embedded features (an action per event, a
+ * category per item, ...), masked where the item row is and the feature would give the target away ============================= */
+
+/* ---- the rule ----------------------------------------------------------------------------------------------------------------
+ * Data: the CSR data set of the Cloze batches (above, "Cloze batches"): items int32 [n_items] label-space indices, offsets int64
+ * [n_seq + 1]; s_g is sequence g, n_g its length.
+ *
+ * Sources: feature f of n_feat (1 <= n_feat <= B4C_MAX_FEATURES) is an int32 device array src_f and two codes.
+ *   kind B4C_FEAT_EVENT: src_f [n_items] is aligned with `items`, the value of token i is src_f[i]            (an action, a dwell bucket)
+ *   kind B4C_FEAT_ITEM:  src_f [V] is a table over the items, the value of token i is src_f[items[i]]         (a category, a brand)
+ *   on_mask B4C_FEAT_MASKED: a [MASK] position of the item row is a [MASK] position of this feature (a function of the item
+ *   would give the target away);  B4C_FEAT_KEPT: the value stays visible there.
+ *
+ * Row geometry: batch row b covers the n tokens of sequence g from position `first` on; a negative row_win[b] is an empty row
+ * (n = 0); row_win NULL: w = b.  The three layouts restate the rows of the builders the item row came from:
+ *   B4C_FEAT_CLOZE       b4c_cloze_batch_windows' row (above): w = row_win[b] names a window of the table (win_seq, win_start,
+ *                        win_len): g = win_seq[w], first = win_start[w], n = clamp(win_len[w], 0, W).  TRAIN and EVAL rows alike
+ *                        (an evaluation row is a window that ends at its target).
+ *   B4C_FEAT_NEXT_TRAIN  the TRAIN row of b4c_next_item_batch: the window (g, a, L) as above, T_g = max(n_g - holdout, 0):
+ *                        first = a > 0 ? a - 1 : 0,  n = a > 0 ? L : max(L - 1, 0), cut at W and at T_g - first - 1.
+ *   B4C_FEAT_NEXT_EVAL   the EVAL row of b4c_next_item_batch: w = row_win[b] names SEQUENCE g = w (the table is not read),
+ *                        t = n_g - holdout:  n = min(t, max_len, W), first = t - n;  t < 1: n = 0.
+ *
+ * Output: out_f int64 [B][ld_out >= W]; columns 0 .. W of every row are written and nothing past them.  Column p, with
+ * i = offsets[g] + first + p:
+ *   p >= n                                                        0        (INPUT_PAD)
+ *   p <  n, on_mask_f is MASKED and items_in[b][p] == 1           1        (MASK_ID)
+ *   otherwise                                                     value + 10  (NUM_RESERVED_TOKENS)
+ * items_in int64 [B][ld_items >= W] is the row the item builder has just written; it is read only to learn which positions are
+ * [MASK] -- no draw is repeated here, so the two cannot disagree.  A row is a pure function of its item row and the data set:
+ * independent of the batch, of the row's place in it and of the rank.
+ * Nothing is range-checked on the device -- row_win against the table, a window against its sequence, an item against V, a
+ * value against the feature's vocabulary: the caller's (cloze_batches.DeviceCloze checks all of them on the host, once).
+ *
+ * b4c_batch_features: ONE launch for all features, one workgroup per batch row.  src, kind, on_mask and out are HOST arrays of
+ *   n_feat device pointers / codes (the form of b4c_chain_ids); they travel by value in the kernel's arguments.  V: the entries
+ *   of an ITEM table (> 0 when a feature is one; otherwise unused).  Every refusal -- null pointers, n_feat, W outside 1 .. 1021,
+ *   a pitch below W, an unknown layout / kind / on_mask code, a missing table pointer in the layouts CLOZE and NEXT_TRAIN,
+ *   holdout < 1 in the next-item layouts, max_len < 1 in NEXT_EVAL, B < 0 -- is B4C_EINVAL before any launch; B == 0 launches
+ *   nothing.
+ * b4c_batch_features_row: the same rule for ONE row and ONE feature on the host, into host arrays -- seq = s_g (n_g items),
+ *   seq_off = offsets[g]; (a, L) the window (ignored for NEXT_EVAL); src the WHOLE source array (EVENT: [n_items], read at
+ *   seq_off + first + p; ITEM: [V], an item outside [0, V) is refused); items_in int64 [W] the item row; out int64 [W];
+ *   geom_out int32 [2] = (first, n). */
+#define B4C_FEAT_EVENT 0
+#define B4C_FEAT_ITEM 1
+#define B4C_FEAT_MASKED 0
+#define B4C_FEAT_KEPT 1
+#define B4C_FEAT_CLOZE 0
+#define B4C_FEAT_NEXT_TRAIN 1
+#define B4C_FEAT_NEXT_EVAL 2
+int b4c_batch_features(const int32_t *items, const int64_t *offsets, const int32_t *win_seq, const int32_t *win_start,
+                       const int32_t *win_len, const int32_t *row_win /* may be NULL */, int B, int W, int layout, int holdout, int max_len,
+                       int V, const int64_t *items_in, int ld_items, int n_feat, const int32_t *const *src, const int *kind,
+                       const int *on_mask, int64_t *const *out, int ld_out, void *stream);
+int b4c_batch_features_row(const int32_t *seq, int n_g, int64_t seq_off, int a, int L, int W, int layout, int holdout, int max_len, int V,
+                           const int32_t *src, int kind, int on_mask, const int64_t *items_in, int64_t *out, int32_t *geom_out);
+
+/* ==== sampled-negative training, the extended forward (additive to ABI 12): BPR, a weighted target term for the binary
+ * cross-entropy (gSASRec's gBCE) and a per-item score correction (the sampled-softmax logQ correction) for the loss over a per-row
+ * candidate list.  The operands, the list conventions and the backward are those of b4c_candidate_loss_fwd / _bwd ============== */
+
+/* ---- the definition ----------------------------------------------------------------------------------------------------------
+ * h, table, rows, row_off, bias, cand, R, C, V, K, dtype, item_loss, g, scores, stream: exactly those of b4c_candidate_loss_fwd
+ *       (above), with its conventions: an entry < 0 or >= V is ABSENT (no term, coefficient exactly 0); a row whose
+ *       column 0 is absent is IGNORED (nothing of it is read past column 0, loss 0, g = 0, scores = NaN); every present position is
+ *       its own term, a repeated id is not merged; R == 0 is a no-op.
+ * Score: s_c = sum_k h[k] * w_c[k] + bias[c], exactly the score of b4c_candidate_loss_fwd.
+ * corr  fp32 [V] or NULL, read only at present entries.  The CORRECTED score is
+ *           z_c = s_c - corr[id_c]      at every present entry c >= 1
+ *           z_0 = s_0 - corr[id_0]      when flags has B4C_CANDX_CORR_TARGET, else z_0 = s_0
+ *       one more fp32 subtraction on s; corr == NULL: z = s everywhere.  With corr[v] = log(expected count of v in a drawn list)
+ *       this is the logQ correction of the sampled softmax; the target is in its list with probability 1, hence the flag.
+ *       scores, when given, still receives the UNCORRECTED s.  dz / ds = 1: g is the derivative by z AND by s, and
+ *       b4c_candidate_loss_bwd consumes it unchanged.
+ * kind  B4C_CANDX_BCE:     l = beta * softplus(-z_0) + sum_{c >= 1 present} softplus(z_c)
+ *                          g_0 = beta * (sigma(z_0) - 1) = -(beta * sigma(-z_0)),  g_c = sigma(z_c)
+ *                          beta finite and >= 0 (gSASRec's generalised BCE; beta = 1: SASRec's)
+ *       B4C_CANDX_SOFTMAX: l = logsumexp_{present c} z_c - z_0 (max-subtracted);  g_c = p_c - [c == 0];  beta is ignored
+ *       B4C_CANDX_BPR:     l = sum_{c >= 1 present} softplus(z_c - z_0);  g_c = sigma(z_c - z_0),  g_0 = -sum_c g_c;  beta is ignored.
+ *                          A row with no present negative (C == 1 included): loss and every coefficient exactly 0.
+ *       softplus(x) = max(x, 0) + log1p(exp(-|x|)) and sigma in their stable forms; expf, log1pf and logf, not the fast intrinsics.
+ * With kind BCE or SOFTMAX, beta == 1, corr == NULL and flags == 0 the result is bit for bit that of b4c_candidate_loss_fwd --
+ * item_loss, g, scores and the untouched padding: the two entries launch one kernel.
+ * The model loss is sum_r l_r / max(#rows with a present target, 1), formed by the caller.
+ *
+ * B4C_EINVAL before any launch: everything b4c_candidate_loss_fwd refuses (null pointers, K, C, a pitch below its width -- ld_g
+ * and ld_s below C included --, a misaligned operand, dtype), a kind outside 0 .. B4C_CANDX_KINDS - 1, flags with an unknown
+ * bit, B4C_CANDX_CORR_TARGET without corr, a beta that is negative or not finite. */
+#define B4C_CANDX_BCE 0
+#define B4C_CANDX_SOFTMAX 1
+#define B4C_CANDX_BPR 2
+#define B4C_CANDX_KINDS 3   /* kinds are 0 .. B4C_CANDX_KINDS - 1 */
+#define B4C_CANDX_CORR_TARGET 1   /* flags bit: the target's score is corrected too */
+int b4c_candidate_loss_fwd_ex(const void *h, int ld_h, const float *table, int ld_t, int64_t rows, int64_t row_off,
+                              const float *bias, const int32_t *cand, int ld_c, int64_t R, int C, int V, int K, int dtype, int kind,
+                              float beta, const float *corr /* may be NULL */, int flags, float *item_loss, float *g, int ld_g,
+                              float *scores /* may be NULL */, int ld_s, void *stream);
+
+/* ==== the masked-query attention entry points that take flags (additive to ABI 12): the causal (left-to-right) form of the last
+ * encoder layer evaluated at a few query rows per sequence.  The operands and layouts are those of b4c_attn_mq_fwd_drop /
+ * b4c_attn_mq_bwd_drop; the flag bit is B4C_ATTN_CAUSAL ========================================================================= */
+
+/* b4c_attn_mq_fwd_drop / b4c_attn_mq_bwd_drop with a trailing `flags`.  flags == 0 reaches exactly the launches of those entry
+ * points; an unknown flag bit is B4C_EINVAL; B4C_ATTN_CAUSAL with q_rows == NULL is B4C_EINVAL at any rate.
+ * B4C_ATTN_CAUSAL: query row r of sequence b sits at position p = q_rows[r] - cu_seqlens[b] and sees the keys 0 .. p of its
+ * sequence.  Over the visible keys
+ *   P[r][k] = softmax_{k <= p}(q_r . k / sqrt(dh) + pad[k] * -1e9),   lse[r] = the log-sum-exp over the visible keys,
+ * and the keys behind p are excluded outright (-inf, not -1e9): exactly zero weight and exactly zero gradient whatever the padding
+ * or the (finite) k | v rows behind p look like; the kernels do not read the key rows behind the largest position of a query chunk
+ * (fp32: 16 rows) or tile (bf16: 32 rows).  p >= the sequence's length sees every key.
+ * Dropout: for every visible pair, the bit b4c_attn_keep(seed, b, h, p, k, H, max_len, rate) that the full causal layer
+ * (b4c_attn_fwd_ex) draws for that (b, h, p, k).
+ * A query row inside a sequence's range with q_rows[r] < cu_seqlens[b] (the -1 of an unused slot) has no visible key: its o row is
+ * exactly 0, its lse 0, its dq row exactly 0, and it adds exactly nothing to dk | dv; nothing is NaN in either direction.  (The
+ * launches without the flag keep treating such a slot as a query over every key.)
+ * A query whose visible keys are all padded (leading pads only) comes out finite; its value is not otherwise pinned, as in
+ * b4c_attn_fwd_ex.
+ * b4c_attn_mq_bwd_ex writes every token row of dkv, as b4c_attn_mq_bwd does: the rows behind a sequence's last query position and
+ * the rows of a sequence without a query are exact zeros.
+ * Not covered: general [Sq][Sk] masks. */
+int b4c_attn_mq_fwd_ex(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                       const int32_t *q_offsets, void *o, int ld_o, float *lse, int B, int max_len, int H, int dh, int dtype,
+                       void *stream, const int32_t *q_rows, float dropout_rate, uint64_t seed, uint32_t flags);
+int b4c_attn_mq_bwd_ex(const void *q, int ld_q, const void *kv, int ld_kv, const uint8_t *key_pad, const int32_t *cu_seqlens,
+                       const int32_t *q_offsets, const void *o, int ld_o, const void *d_o, int ld_do, const float *lse,
+                       void *dq, int ld_dq, void *dkv, int ld_dkv, int B, int max_len, int H, int dh, int dtype, void *stream,
+                       const int32_t *q_rows, float dropout_rate, uint64_t seed, uint32_t flags);
+
+/* ==== pre-LN encoder blocks (additive to ABI 12): the backward of a pre-LN encoder half's input norm -- the LayerNorm backward of
+ * the sublayer-input gradient with the residual stream's gradient added as it is stored.
+ *
+ * A pre-LN half is  x' = x + drop(sublayer(LN(x; gamma, beta))).  With g the gradient of x' and dn the gradient of the normalised
+ * rows that the sublayer's backward leaves,  dx = g + LNbwd(dn; x, stats, gamma):  the forward needs no kernel of its own
+ * (b4c_layernorm_fwd, b4c_gemm_nt_add_ln / b4c_add_dropout_layernorm_fwd with the NEXT norm's gamma / beta), this sum does. ===== */
+
+/* dx[row][j] = res[row][j] + rstd * (a - mean_j(a) - xhat * mean_j(a * xhat)),  a = dout * gamma, xhat = (x - mean) * rstd from the
+ * saved stats [rows][2] = {mean, rstd}: b4c_layernorm_bwd (gate == NULL) with `res` added in fp32 before the one rounding of the
+ * store.  dout, x, dx: [rows][d] contiguous; res: [rows][d] with pitch ld_res elements (>= d, a multiple of 8; 16-byte aligned),
+ * required.  dgamma += sum_rows dout * xhat, dbeta += sum_rows dout (fp32 [d], ADDED to) through per-workgroup sums in the
+ * workspace (b4c_layernorm_bwd_add_workspace_bytes, required), added in a fixed order: no float atomics, the same bits on every
+ * launch, and the bits of b4c_layernorm_bwd on the same operands.  res == 0 everywhere gives b4c_layernorm_bwd's dx bit for bit.
+ * fp32 and bf16; d a multiple of 8, <= 1024; rows is a 64-bit count.  dx must not overlap an input.  Bad arguments: B4C_EINVAL,
+ * nothing is launched. */
+int64_t b4c_layernorm_bwd_add_workspace_bytes(int64_t rows, int d);
+int b4c_layernorm_bwd_add(const void *dout, const void *x, const float *stats, const float *gamma, const void *res, int ld_res,
+                          void *dx, float *dgamma, float *dbeta, int64_t rows, int d, void *workspace, int64_t workspace_bytes,
+                          int dtype, void *stream);
+
+/* The same with dout = A . Bt^T formed in the kernel (matrix cores), so that the sublayer-input gradient never reaches memory:
+ *   dn = bf16(A . Bt^T)  -- the accumulator rounded to the bf16 value b4c_gemm_nt (act NONE, no bias) would have stored --
+ *   dx = res + LNbwd(dn; x, stats, gamma),  dgamma += sum_rows dn * xhat,  dbeta += sum_rows dn.
+ * A [M][K] (pitch lda), Bt [N][K] (pitch ldb: the dX operand of b4c_gemm_nt), x / dx [M][N] contiguous, res [M][N] with pitch
+ * ld_res; bf16 only; N = d_model <= 256, N and K multiples of 8 (K covers 3 d and the padded dff); lda, ldb >= K, multiples of 8,
+ * and a 128-row tile of either spans less than 2^30 bytes (b4c_gemm_nt's rule); every operand 16-byte aligned.  A workgroup
+ * owns complete rows, so the two row sums of the LayerNorm backward are taken in its epilogue; taking this kernel or b4c_gemm_nt +
+ * b4c_layernorm_bwd_add differs by the order of fp32 sums only.  Deterministic: per-workgroup dgamma / dbeta sums through the
+ * workspace (b4c_gemm_nt_ln_bwd_add_workspace_bytes, required) in a fixed order.  Bad arguments: B4C_EINVAL, nothing is launched. */
+int64_t b4c_gemm_nt_ln_bwd_add_workspace_bytes(int M, int N);
+int b4c_gemm_nt_ln_bwd_add(const void *A, int lda, const void *Bt, int ldb, const void *x, const float *stats, const float *gamma,
+                           const void *res, int ld_res, void *dx, float *dgamma, float *dbeta, int M, int N, int K, void *workspace,
+                           int64_t workspace_bytes, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
-
-/* ---- extension headers: part of this ABI, declared in files of their own and included here, so that b4c.h is all a caller includes.
- * (The ctypes binding reads them beside this file: bert4clickpath_amd/_lib.py, EXT_HEADER_PATHS.) */
-#include "b4c_attn_ex.h"   /* b4c_attn_fwd_ex / b4c_attn_bwd_ex / b4c_attn_weights_ex, B4C_ATTN_CAUSAL: causal self-attention */
-/* ---- add-on headers: the same, for the entry points of later features -- one header per feature, listed here and in _lib.py's
- * ADDON_HEADER_PATHS, which binds whatever they declare. */
-#include "b4c_cand_loss.h" /* b4c_candidate_loss_fwd / _bwd, B4C_CAND_BCE / B4C_CAND_SOFTMAX: sampled-negative training losses */
-#include "b4c_next_item.h" /* b4c_next_item_batch / _row, B4C_NEXT_TRAIN / B4C_NEXT_EVAL: next-item batches built on the device */
-#include "b4c_batch_features.h" /* b4c_batch_features / _row, B4C_FEAT_*: side features beside the items of a device-built batch */
-#include "b4c_cand_loss_ex.h" /* b4c_candidate_loss_fwd_ex, B4C_CANDX_*: BPR, a weighted BCE target term and a logQ correction for the lists */
-#include "b4c_attn_mq_ex.h" /* b4c_attn_mq_fwd_ex / _bwd_ex: the masked-query kernels with flags (B4C_ATTN_CAUSAL: the causal last layer) */
-/* ---- the pre-LN header: _lib.py binds it from a list of its own (PRE_LN_HEADER_PATHS, pre_ln_signatures()). */
-#include "b4c_pre_ln.h" /* b4c_layernorm_bwd_add: the residual gradient + LayerNorm backward of a pre-LN encoder half */
 
 #endif /* B4C_H */

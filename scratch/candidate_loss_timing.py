@@ -4,7 +4,7 @@ b4c_sample_candidates (uniform).  Device events around `iters` back-to-back laun
 windows; one JSON line.  Beside each backward time: the table gradient's added bytes R C K 4 over the time, to be read against
 the chip-wide float-atomic rate (about 1.3 TB/s).
 
-The forward of b4c_candidate_loss_fwd_ex (include/b4c_cand_loss_ex.h) is timed beside them: BPR, and the kinds with a per-item
+The forward of b4c_candidate_loss_fwd_ex (include/b4c.h) is timed beside them: BPR, and the kinds with a per-item
 correction (a random fp32 [V] vector: the cost is one more gathered float per entry).
 
 --parent_lib PATH: a libb4c_hip.so built from the commit before the extended forward.  Its b4c_candidate_loss_fwd is timed against
@@ -49,7 +49,7 @@ def raw_forward(lib):
     """b4c_candidate_loss_fwd of a build of the library through the bare binding, into outputs the caller keeps: the same host
     path for this tree's build and for another one (the entry point's argument list did not change)"""
     fn = lib.b4c_candidate_loss_fwd
-    fn.restype, fn.argtypes = _lib.addon_signatures()['b4c_candidate_loss_fwd']
+    fn.restype, fn.argtypes = _lib.signatures()['b4c_candidate_loss_fwd']
 
     def fwd(h, table, bias, cand, V, kind, off, item, g):
         R, K = h.shape

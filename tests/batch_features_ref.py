@@ -1,4 +1,4 @@
-"""Host restatement of the side-feature rule (include/b4c_batch_features.h, "the rule"), in numpy and Python integers, written from
+"""Host restatement of the side-feature rule (include/b4c.h, "the rule"), in numpy and Python integers, written from
 the header's text.  Used by test_batch_features_cpu.py and test_gpu_batch_features.py.  Every real position asserts that the item
 row holds [MASK] or the item the geometry points at: a geometry that disagrees with the item builder's fails here instead of
 gathering from the wrong place."""

@@ -1,4 +1,4 @@
-"""The extended candidate-list losses of include/b4c_cand_loss_ex.h restated in numpy -- BPR, the weighted binary cross-entropy
+"""The extended candidate-list losses of include/b4c.h restated in numpy -- BPR, the weighted binary cross-entropy
 (gBCE) and the per-item score correction (logQ) --, their derived fp32 error bounds, and the settings of the GPU tests.  The
 inputs, the committed shapes and the helpers are those of tests/candidate_loss_ref.py (same seeds, same cases); this module adds
 the correction vector of a case, generated from a seed.

@@ -1,4 +1,4 @@
-"""The candidate-list losses of include/b4c_cand_loss.h restated in numpy, their derived fp32 error bounds, and the committed
+"""The candidate-list losses of include/b4c.h restated in numpy, their derived fp32 error bounds, and the committed
 cases of the GPU tests (shared with the CPU tests: same seeds, same inputs).
 
 restate(...) evaluates the definition -- scores, per-row loss, coefficients g, dh, dW, db -- in float64, or (dtype=np.float32) with

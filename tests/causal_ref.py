@@ -1,7 +1,7 @@
 """float64 restatement of causal (left-to-right) self-attention (an extension: the reference's encoder never builds a look-ahead
 mask, so there is NO REFERENCE ORACLE under oracle/; this file is the checker, as tests/attn_dropout_ref.py is for attention dropout).
 
-Semantics (include/b4c_attn_ex.h, B4C_ATTN_CAUSAL): key k is visible to query q iff k <= q, both counted inside the sequence;
+Semantics (include/b4c.h, B4C_ATTN_CAUSAL): key k is visible to query q iff k <= q, both counted inside the sequence;
   P[q][k] = softmax_{k <= q}(q . k / sqrt(dh) + pad[k] * -1e9),   lse[q] = the log-sum-exp over the visible keys.
 The keys behind q are excluded outright: the additive mask is pad * -1e9 + triu(-inf, 1), handed to attn_dropout_ref.attention,
 which takes any additive mask (and the regenerated dropout keep bits).  The backward is autograd's through these lines."""

@@ -1,4 +1,4 @@
-"""Host restatement of the next-item batch rule (include/b4c_next_item.h), in numpy and Python integers: rows, flat_idx, labels,
+"""Host restatement of the next-item batch rule (include/b4c.h), in numpy and Python integers: rows, flat_idx, labels,
 row_off, X_g; the negatives through tests/candidates_ref.sample_rows, called per target with row_base = the target token's CSR
 index.  Used by test_next_item_cpu.py and test_gpu_next_item.py."""
 import numpy as np

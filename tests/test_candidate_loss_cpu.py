@@ -1,9 +1,6 @@
 """Sampled-negative training losses over per-row candidate lists, the parts that need no GPU (NO REFERENCE ORACLE: an extension --
-the float64 restatement is tests/candidate_loss_ref.py): the add-on header and its binding, the argument checks that refuse a call
-before any launch, the restatement against itself, and the head that cannot take the loss.
-
-The add-on list is NOT pinned here: these tests ask for this feature's names, not for the absence of others."""
-import os
+the float64 restatement is tests/candidate_loss_ref.py): the entry points' declarations and their binding, the argument checks that refuse
+a call before any launch, the restatement against itself, and the head that cannot take the loss."""
 import re
 import shutil
 import subprocess
@@ -19,14 +16,11 @@ NAMES = ('b4c_candidate_loss_fwd', 'b4c_candidate_loss_bwd')
 
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------------
-def test_addon_header_declares_the_entry_points_and_they_are_bound():
+def test_header_declares_the_entry_points_and_they_are_bound():
     from bert4clickpath_amd import _lib, ops
     c = _lib.ctypes
     lib = _lib.lib()
-    path = [p for p in _lib.ADDON_HEADER_PATHS if os.path.basename(p) == 'b4c_cand_loss.h']
-    assert len(path) == 1 and os.path.dirname(path[0]) == os.path.dirname(_lib.HEADER_PATH)
-    declared = _lib.signatures(path[0])
-    addon = _lib.addon_signatures()
+    declared = _lib.signatures()
     ptr, i32, i64 = c.c_void_p, c.c_int, c.c_int64
     lists = {
         # (h, ld_h, table, ld_t, rows, row_off, bias, cand, ld_c, R, C, V, K, dtype, kind, item_loss, g, ld_g, scores, ld_s, stream)
@@ -36,18 +30,15 @@ def test_addon_header_declares_the_entry_points_and_they_are_bound():
                                    ptr],
     }
     for name in NAMES:
-        assert name in declared and name in addon, name
-        assert addon[name] == declared[name] == (c.c_int, lists[name]), name
+        assert name in declared, name
+        assert declared[name] == (c.c_int, lists[name]), name
         assert hasattr(lib, name) and list(getattr(lib, name).argtypes) == lists[name] and getattr(lib, name).restype is c.c_int
-        assert name not in _lib.all_signatures()                 # an add-on: not in b4c.h's or the extension header's list
-    consts = _lib.header_constants(_lib._header_text(path[0]))
+    consts = _lib.header_constants(_lib._header_text(_lib.HEADER_PATH))
     assert (consts['B4C_CAND_BCE'], consts['B4C_CAND_SOFTMAX'], consts['B4C_CAND_KINDS']) == (0, 1, 2)
     assert (_lib.CAND_BCE, _lib.CAND_SOFTMAX) == (0, 1) and ops.CAND_LOSS_KINDS == {'bce': 0, 'softmax': 1}
-    with open(path[0]) as f:
-        text = f.read()
-    assert '#ifndef B4C_CAND_LOSS_H' in text and 'extern "C"' in text
     with open(_lib.HEADER_PATH) as f:
-        assert re.search(r'^#include "b4c_cand_loss.h"', f.read(), flags=re.M)
+        text = f.read()
+    assert '#ifndef B4C_H' in text and 'extern "C"' in text
     cc = shutil.which('cc') or shutil.which('gcc') or shutil.which('clang')
     if cc:              # what a C compiler sees of b4c.h alone
         pre = subprocess.run([cc, '-E', '-dD', _lib.HEADER_PATH], capture_output=True, text=True, check=True).stdout
@@ -60,18 +51,8 @@ def test_addon_header_declares_the_entry_points_and_they_are_bound():
 def test_the_pinned_lists_still_hold():
     from bert4clickpath_amd import _lib
     lib = _lib.lib()
-    assert len(_lib.declared_symbols()) == 127 and len(_lib.EXT_HEADER_PATHS) == 1
-    assert len(_lib.all_signatures()) == 130 and len(_lib.declared_symbols(_lib.EXT_HEADER_PATHS[0])) == 3
+    assert len(_lib.signatures()) == 143 == len(_lib.declared_symbols())
     assert _lib.ABI_VERSION == 12 and lib.b4c_abi_version() == 12
-
-
-def test_a_name_declared_twice_raises(tmp_path, monkeypatch):
-    from bert4clickpath_amd import _lib
-    dup = tmp_path / 'dup.h'
-    dup.write_text('int b4c_abi_version(void);\n')
-    monkeypatch.setattr(_lib, 'ADDON_HEADER_PATHS', _lib.ADDON_HEADER_PATHS + (str(dup),))
-    with pytest.raises(_lib.B4CError, match='b4c_abi_version'):
-        _lib.addon_signatures()
 
 
 def _fwd(L, h=A, ld_h=128, table=A, ld_t=128, rows=1000, row_off=10, bias=A, cand=A, ld_c=8, R=4, C=8, V=500, K=128, dtype=1, kind=0,

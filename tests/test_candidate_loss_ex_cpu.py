@@ -1,9 +1,8 @@
-"""The extended sampled-negative losses (include/b4c_cand_loss_ex.h: BPR, the weighted BCE of gBCE, the logQ correction), the parts
-that need no GPU (NO REFERENCE ORACLE: an extension -- the float64 restatement is tests/candidate_loss_ex_ref.py): the add-on
-header and its binding, the argument checks that refuse a call before any launch, the host checks of ops.candidate_loss_fwd_ex
+"""The extended sampled-negative losses (include/b4c.h: BPR, the weighted BCE of gBCE, the logQ correction), the parts
+that need no GPU (NO REFERENCE ORACLE: an extension -- the float64 restatement is tests/candidate_loss_ex_ref.py): the entry
+point's declaration and its binding, the argument checks that refuse a call before any launch, the host checks of ops.candidate_loss_fwd_ex
 and of the model's keywords, the restatement against candidate_loss_ref's and against itself, cloze.log_expected_count."""
 import math
-import os
 import re
 import shutil
 import subprocess
@@ -20,34 +19,24 @@ NAME = 'b4c_candidate_loss_fwd_ex'
 
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------------
-def test_addon_header_declares_the_entry_point_and_it_is_bound():
+def test_header_declares_the_entry_point_and_it_is_bound():
     from bert4clickpath_amd import _lib, ops
     c = _lib.ctypes
     lib = _lib.lib()
-    path = [p for p in _lib.ADDON_HEADER_PATHS if os.path.basename(p) == 'b4c_cand_loss_ex.h']
-    assert len(path) == 1 and os.path.dirname(path[0]) == os.path.dirname(_lib.HEADER_PATH)
-    declared = _lib.signatures(path[0])
-    addon = _lib.addon_signatures()
+    declared = _lib.signatures()
     ptr, i32, i64, f32 = c.c_void_p, c.c_int, c.c_int64, c.c_float
     # (h, ld_h, table, ld_t, rows, row_off, bias, cand, ld_c, R, C, V, K, dtype, kind, beta, corr, flags, item_loss, g, ld_g, scores,
     #  ld_s, stream): b4c_candidate_loss_fwd's operands in its order, with beta, corr and flags after kind
     want = [ptr, i32, ptr, i32, i64, i64, ptr, ptr, i32, i64, i32, i32, i32, i32, i32, f32, ptr, i32, ptr, ptr, i32, ptr, i32, ptr]
-    assert list(declared) == [NAME]
-    assert addon[NAME] == declared[NAME] == (c.c_int, want)
+    assert declared[NAME] == (c.c_int, want)
     assert list(getattr(lib, NAME).argtypes) == want and getattr(lib, NAME).restype is c.c_int
-    assert NAME not in _lib.all_signatures()                     # an add-on: not in b4c.h's or the extension header's list
-    legacy = addon['b4c_candidate_loss_fwd'][1]
+    legacy = declared['b4c_candidate_loss_fwd'][1]
     assert want[:15] == legacy[:15] and want[18:] == legacy[15:]
-    consts = _lib.header_constants(_lib._header_text(path[0]))
+    consts = {k: v for k, v in _lib.header_constants(_lib._header_text(_lib.HEADER_PATH)).items() if k.startswith('B4C_CANDX_')}
     assert consts == {'B4C_CANDX_BCE': 0, 'B4C_CANDX_SOFTMAX': 1, 'B4C_CANDX_BPR': 2, 'B4C_CANDX_KINDS': 3, 'B4C_CANDX_CORR_TARGET': 1}
     assert (_lib.CANDX_BCE, _lib.CANDX_SOFTMAX, _lib.CANDX_BPR, _lib.CANDX_KINDS, _lib.CANDX_CORR_TARGET) == (0, 1, 2, 3, 1)
     assert ops.CANDX_LOSS_KINDS == {'bce': 0, 'softmax': 1, 'bpr': 2}
     assert ops.CAND_LOSS_KINDS == {'bce': 0, 'softmax': 1}       # the first feature's surface is as it was
-    with open(path[0]) as f:
-        text = f.read()
-    assert '#ifndef B4C_CAND_LOSS_EX_H' in text and 'extern "C"' in text
-    with open(_lib.HEADER_PATH) as f:
-        assert re.search(r'^#include "b4c_cand_loss_ex.h"', f.read(), flags=re.M)
     assert _lib.ABI_VERSION == 12 and lib.b4c_abi_version() == 12
     cc = shutil.which('cc') or shutil.which('gcc') or shutil.which('clang')
     if cc:              # what a C compiler sees of b4c.h alone

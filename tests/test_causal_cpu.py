@@ -68,8 +68,8 @@ def test_look_ahead_mask_helper():
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------------
 def test_header_declares_the_entry_points_and_the_abi_stays_12():
-    """the three entry points and the flag live in the extension header include/b4c_attn_ex.h, which b4c.h includes (a C caller
-    includes b4c.h alone: the preprocessed b4c.h declares them); the binding reads both files; b4c.h's own list is untouched"""
+    """the three entry points and the flag are declared in include/b4c.h (the preprocessed header shows them to a C caller) and
+    bound with the lists it gives"""
     import re
     import shutil
     import subprocess
@@ -77,24 +77,20 @@ def test_header_declares_the_entry_points_and_the_abi_stays_12():
     lib = _lib.lib()
     assert lib.b4c_abi_version() == 12 and _lib.ABI_VERSION == 12
     new = ('b4c_attn_fwd_ex', 'b4c_attn_bwd_ex', 'b4c_attn_weights_ex')
-    ext, = _lib.EXT_HEADER_PATHS
-    assert os.path.basename(ext) == 'b4c_attn_ex.h' and os.path.dirname(ext) == os.path.dirname(_lib.HEADER_PATH)
-    assert _lib.declared_symbols(ext) == sorted(new)
-    sig = _lib.all_signatures()
-    assert set(sig) == set(_lib.declared_symbols()) | set(new) and not set(new) & set(_lib.declared_symbols())
+    sig = _lib.signatures()
+    assert set(sig) == set(_lib.declared_symbols()) and len(sig) == 143
+    assert {n for n in sig if re.fullmatch(r'b4c_attn_(?!mq_)\w+_ex', n)} == set(new)
     for name in new:
         assert hasattr(lib, name) and list(getattr(lib, name).argtypes) == sig[name][1], name
-    with open(_lib.HEADER_PATH) as f:
-        assert re.search(r'^#include "b4c_attn_ex.h"', f.read(), flags=re.M)
     cc = shutil.which('cc') or shutil.which('gcc') or shutil.which('clang')
     if cc:              # what a C compiler sees of b4c.h
         pre = subprocess.run([cc, '-E', '-dD', _lib.HEADER_PATH], capture_output=True, text=True, check=True).stdout
         for name in new:
             assert re.search(r'\bint %s\(' % name, pre), name
         assert re.search(r'#define B4C_ATTN_CAUSAL 1u', pre)
-    assert _lib.header_constants(_lib._header_text(ext))['B4C_ATTN_CAUSAL'] == 1
+    assert _lib.header_constants(_lib._header_text(_lib.HEADER_PATH))['B4C_ATTN_CAUSAL'] == 1
     assert _lib.ATTN_CAUSAL == ops.ATTN_CAUSAL == 1
-    with open(ext) as f:
+    with open(_lib.HEADER_PATH) as f:
         assert '#define B4C_ATTN_CAUSAL 1u' in f.read()
     c = _lib.ctypes
     tail = [c.c_float, c.c_uint64, c.c_uint32]                      # (dropout_rate, seed, flags)

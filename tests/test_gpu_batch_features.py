@@ -1,4 +1,4 @@
-"""Side features of device-built batches (include/b4c_batch_features.h; NO REFERENCE ORACLE: an extension -- the restatement is
+"""Side features of device-built batches (include/b4c.h; NO REFERENCE ORACLE: an extension -- the restatement is
 tests/batch_features_ref.py): the kernel bit for bit on item rows that the real builders wrote, purity, every builder of
 DeviceCloze(features=...), and two-feature models fed from such batches against the same losses on host-built inputs.
 Everything about the batches is integer-exact: no tolerance.  Gradients of two routes through the same kernels differ only by the

@@ -1,4 +1,4 @@
-"""The extended sampled-negative losses on the device (include/b4c_cand_loss_ex.h: BPR, the weighted BCE of gBCE, the logQ
+"""The extended sampled-negative losses on the device (include/b4c.h: BPR, the weighted BCE of gBCE, the logQ
 correction; NO REFERENCE ORACLE: an extension -- the float64 restatement and the derived bounds are tests/candidate_loss_ex_ref.py):
 b4c_candidate_loss_fwd_ex and the unchanged b4c_candidate_loss_bwd on the grid of candidate_loss_ref.CASES, element by element; the
 bit-identity of the first entry point with the shared kernel; the model's candidate_loss('bpr' | 'gbce', logq=, item_cdf=) against

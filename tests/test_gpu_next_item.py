@@ -1,4 +1,4 @@
-"""Next-item batches built on the device (include/b4c_next_item.h; NO REFERENCE ORACLE: an extension -- the restatement is
+"""Next-item batches built on the device (include/b4c.h; NO REFERENCE ORACLE: an extension -- the restatement is
 tests/next_item_ref.py): every output of the kernel bit for bit on the case list, every list against the existing sampler (an
 independent kernel), purity, and the model entry next_item_loss against cloze_loss / candidate_loss on host-built inputs.
 Everything about the batches is integer-exact: no tolerance.  Gradients of two routes through the same kernels differ only by the

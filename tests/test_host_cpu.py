@@ -21,6 +21,33 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().b4c_abi_version() == _lib.ABI_VERSION == 12
 
 
+def test_every_declared_entry_point_is_an_export_of_the_built_library():
+    """the dynamic symbol table of the file on disk, read without loading it: all of the one header's 143 names are defined there"""
+    import shutil
+    import subprocess
+    from bert4clickpath_amd import _lib
+    declared = set(_lib.signatures())
+    assert len(declared) == 143 == len(_lib.declared_symbols()) and _lib.ABI_VERSION == 12
+    assert all(n.startswith('b4c_') for n in declared)
+    nm = shutil.which('nm')
+    if nm:
+        out = subprocess.run([nm, '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+        exported = {line.split()[-1] for line in out.splitlines() if line.split()}
+    else:
+        L = ctypes.CDLL(_lib.LIB_PATH)
+        exported = {n for n in declared if hasattr(L, n)}
+    assert declared <= exported, sorted(declared - exported)
+
+
+def test_a_name_declared_twice_is_refused():
+    """one header, one table: parse_header is where a second declaration of a name is caught"""
+    from bert4clickpath_amd import _lib
+    with pytest.raises(_lib.B4CError, match='b4c_dropout'):
+        _lib.parse_header('int b4c_dropout(int x);\nint b4c_abi_version(void);\nint b4c_dropout(int x);\n')
+    with pytest.raises(_lib.B4CError, match='b4c_dropout'):      # ... also beside the header's own declaration of it
+        _lib.parse_header(_lib._header_text(_lib.HEADER_PATH) + '\nint b4c_dropout(int x);\n')
+
+
 def test_binding_is_derived_from_the_header(tmp_path):
     """_lib binds every entry point with the argument list include/b4c.h declares, and takes its constants from the header's
     #defines; what the parser does not understand is an error that names the declaration, never a guess."""

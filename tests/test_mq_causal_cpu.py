@@ -1,4 +1,4 @@
-"""The causal form of the masked-query last layer, the parts that need no GPU: the add-on header and its two entry points, the
+"""The causal form of the masked-query last layer, the parts that need no GPU: the two entry points include/b4c.h declares, the
 switch ops.mq_causal and the route it opens (Encoder.rows_route beside the unchanged Encoder.rows_supported), the trailing
 argument EncoderLayer.forward(rows=) hands to the masked-query block, and the rows a caller names with flat_idx + row_offsets."""
 import os
@@ -14,32 +14,26 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ---- the header ----------------------------------------------------------------------------------------------------------------------
 def test_header_declares_the_drop_signatures_plus_flags():
     from bert4clickpath_amd import _lib
-    path = os.path.join(ROOT, 'include', 'b4c_attn_mq_ex.h')
-    assert path in _lib.ADDON_HEADER_PATHS and path not in _lib.EXT_HEADER_PATHS
-    sig, base, c = _lib.signatures(path), _lib.signatures(), _lib.ctypes
-    assert sorted(sig) == ['b4c_attn_mq_bwd_ex', 'b4c_attn_mq_fwd_ex']
+    sig, c = _lib.signatures(), _lib.ctypes
+    assert {'b4c_attn_mq_bwd_ex', 'b4c_attn_mq_fwd_ex'} <= set(sig)
     for new, old in (('b4c_attn_mq_fwd_ex', 'b4c_attn_mq_fwd_drop'), ('b4c_attn_mq_bwd_ex', 'b4c_attn_mq_bwd_drop')):
-        assert sig[new][0] == base[old][0]
-        assert sig[new][1] == base[old][1] + [c.c_uint32]           # a trailing uint32_t flags
-        assert _lib.addon_signatures()[new] == sig[new]
-    # the flag bit is b4c_attn_ex.h's: the new header defines no constant of its own
-    assert _lib.header_constants(_lib._header_text(path)) == {}
-    assert _lib.ATTN_CAUSAL == 1
+        assert sig[new][0] == sig[old][0]
+        assert sig[new][1] == sig[old][1] + [c.c_uint32]           # a trailing uint32_t flags
+    assert _lib.ATTN_CAUSAL == 1                                    # the flag bit is that of the b4c_attn_*_ex entry points
 
 
 def test_pinned_counts_and_abi_version_stay():
     from bert4clickpath_amd import _lib
     assert _lib.ABI_VERSION == 12
-    assert len(_lib.signatures()) == 127 and len(_lib.EXT_HEADER_PATHS) == 1 and len(_lib.all_signatures()) == 130
-    assert len(_lib.signatures(_lib.EXT_HEADER_PATHS[0])) == 3
-    assert len(_lib.all_signatures()) + len(_lib.addon_signatures()) == 139          # the README's entry-point count
+    assert len(_lib.signatures()) == 143 == len(_lib.declared_symbols())          # the README's entry-point count
 
 
 def test_library_exports_the_entry_points():
     from bert4clickpath_amd import _lib
-    lib = _lib.lib()
+    lib, sig = _lib.lib(), _lib.signatures()
     assert lib.b4c_abi_version() == 12
-    assert hasattr(lib, 'b4c_attn_mq_fwd_ex') and hasattr(lib, 'b4c_attn_mq_bwd_ex')
+    for name in ('b4c_attn_mq_fwd_ex', 'b4c_attn_mq_bwd_ex'):
+        assert hasattr(lib, name) and list(getattr(lib, name).argtypes) == sig[name][1]
 
 
 # ---- the switch ----------------------------------------------------------------------------------------------------------------------

@@ -1,9 +1,6 @@
 """Next-item batches, the parts that need no GPU (NO REFERENCE ORACLE: an extension -- the restatement is tests/next_item_ref.py):
-the add-on header and its binding, the argument checks that refuse a launch, the rule on the host (b4c_next_item_row) against the
+the entry points' declarations and their binding, the argument checks that refuse a launch, the rule on the host (b4c_next_item_row) against the
 restatement, and DeviceCloze's host side."""
-import os
-import re
-
 import numpy as np
 import pytest
 
@@ -13,14 +10,11 @@ A = 1 << 20                                                       # a well-align
 NAMES = ('b4c_next_item_batch', 'b4c_next_item_row')
 
 
-def test_addon_header_declares_the_entry_points_and_they_are_bound():
+def test_header_declares_the_entry_points_and_they_are_bound():
     from bert4clickpath_amd import _lib, ops
     c = _lib.ctypes
     lib = _lib.lib()
-    path = [p for p in _lib.ADDON_HEADER_PATHS if os.path.basename(p) == 'b4c_next_item.h']
-    assert len(path) == 1 and os.path.dirname(path[0]) == os.path.dirname(_lib.HEADER_PATH)
-    declared = _lib.signatures(path[0])
-    addon = _lib.addon_signatures()
+    declared = _lib.signatures()
     ptr, i32, i64, u64 = c.c_void_p, c.c_int, c.c_int64, c.c_uint64
     lists = {
         # (items, offsets, win_seq, win_start, win_len, row_win, row_off, B, W, mode, holdout, max_len, V, N, seed, excl, cdf, items_out,
@@ -31,16 +25,10 @@ def test_addon_header_declares_the_entry_points_and_they_are_bound():
         'b4c_next_item_row': [ptr, i32, i64] + [i32] * 8 + [u64, i32, ptr, ptr, ptr, ptr, ptr, i32, ptr],
     }
     for name in NAMES:
-        assert name in declared and name in addon, name
-        assert addon[name] == declared[name] == (c.c_int, lists[name]), name
+        assert name in declared, name
+        assert declared[name] == (c.c_int, lists[name]), name
         assert hasattr(lib, name) and list(getattr(lib, name).argtypes) == lists[name] and getattr(lib, name).restype is c.c_int
-        assert name not in _lib.all_signatures()
     assert (ops.NEXT_TRAIN, ops.NEXT_EVAL) == (0, 1) and ops.NEXT_EXCLUDE == {None: 0, 'history': 1}
-    with open(path[0]) as f:
-        text = f.read()
-    assert '#ifndef B4C_NEXT_ITEM_H' in text and 'extern "C"' in text
-    with open(_lib.HEADER_PATH) as f:
-        assert re.search(r'^#include "b4c_next_item.h"', f.read(), flags=re.M)
     assert _lib.ABI_VERSION == 12 and lib.b4c_abi_version() == 12
 
 

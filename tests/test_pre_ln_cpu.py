@@ -1,6 +1,6 @@
 """Pre-LN encoder blocks (norm='pre'), the parts that need no GPU: the float64 restatement tests/pre_ln_ref.py against an
-independent implementation (torch.nn.TransformerEncoderLayer(norm_first=True)), the header and its list in _lib.py beside the pinned
-counts, the argument refusals of b4c_layernorm_bwd_add, the keyword on the four classes, get_config, state-dict names, the
+independent implementation (torch.nn.TransformerEncoderLayer(norm_first=True)), the entry points' declarations in include/b4c.h and their
+binding, the argument refusals of b4c_layernorm_bwd_add, the keyword on the four classes, get_config, state-dict names, the
 masked-query route's answer and background_dw_expected(norm=)."""
 import ctypes
 import os
@@ -107,46 +107,31 @@ def test_closed_form_of_the_row_kernel_is_the_autograd_of_layer_norm():
 
 
 # ---- the header and the binding ----------------------------------------------------------------------------------------------------
-def test_header_third_list_and_pinned_counts_hold_at_once():
+def test_header_declares_the_entry_points_and_the_counts_hold():
     from bert4clickpath_amd import _lib
-    path = os.path.join(ROOT, 'include', 'b4c_pre_ln.h')
-    assert _lib.PRE_LN_HEADER_PATHS == (path,)
-    assert path not in _lib.ADDON_HEADER_PATHS and path not in _lib.EXT_HEADER_PATHS
-    sig = _lib.pre_ln_signatures()
-    assert sorted(sig) == ['b4c_gemm_nt_ln_bwd_add', 'b4c_gemm_nt_ln_bwd_add_workspace_bytes', 'b4c_layernorm_bwd_add',
-                           'b4c_layernorm_bwd_add_workspace_bytes'] and sig == _lib.signatures(path)
+    sig = _lib.signatures()
+    names = ['b4c_gemm_nt_ln_bwd_add', 'b4c_gemm_nt_ln_bwd_add_workspace_bytes', 'b4c_layernorm_bwd_add',
+             'b4c_layernorm_bwd_add_workspace_bytes']
+    assert set(names) <= set(sig)
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
     assert sig['b4c_layernorm_bwd_add'] == (i32, [vp, vp, vp, vp, vp, i32, vp, vp, vp, i64, i32, vp, i64, i32, vp])
-    assert sig['b4c_layernorm_bwd_add_workspace_bytes'] == _lib.signatures()['b4c_layernorm_bwd_workspace_bytes']
+    assert sig['b4c_layernorm_bwd_add_workspace_bytes'] == sig['b4c_layernorm_bwd_workspace_bytes']
     assert sig['b4c_gemm_nt_ln_bwd_add'] == (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i64, i32, vp])
     assert sig['b4c_gemm_nt_ln_bwd_add_workspace_bytes'] == (i64, [i32, i32])
-    assert _lib.header_constants(_lib._header_text(path)) == {}
-    # the pinned counts of the other lists, and the ABI version
-    assert _lib.ABI_VERSION == 12
-    assert len(_lib.signatures()) == 127 and len(_lib.all_signatures()) == 130
-    assert len(_lib.all_signatures()) + len(_lib.addon_signatures()) == 139
-    assert not set(sig) & (set(_lib.all_signatures()) | set(_lib.addon_signatures()))
-    with open(os.path.join(ROOT, 'include', 'b4c.h')) as f:
-        assert '#include "b4c_pre_ln.h"' in f.read()
+    # the whole ABI, and its version
+    assert len(sig) == 143 == len(_lib.declared_symbols()) and _lib.ABI_VERSION == 12
     with open(os.path.join(ROOT, 'bert4clickpath_amd', 'csrc', 'Makefile')) as f:
-        mk = f.read()
-    assert 'pre_ln.hip' in mk and 'b4c_pre_ln.h' in mk
-
-
-def test_a_name_declared_twice_is_refused(tmp_path, monkeypatch):
-    from bert4clickpath_amd import _lib
-    dup = tmp_path / 'dup.h'
-    dup.write_text('int b4c_dropout(int x);\n')
-    monkeypatch.setattr(_lib, 'PRE_LN_HEADER_PATHS', _lib.PRE_LN_HEADER_PATHS + (str(dup),))
-    with pytest.raises(_lib.B4CError, match='b4c_dropout'):
-        _lib.pre_ln_signatures()
+        assert 'pre_ln.hip' in f.read()
+    lib = _lib.lib()
+    for name in names:
+        assert list(getattr(lib, name).argtypes) == sig[name][1] and getattr(lib, name).restype is sig[name][0], name
 
 
 def test_library_exports_and_binds_the_entry_points():
     from bert4clickpath_amd import _lib
     lib = _lib.lib()
     assert lib.b4c_abi_version() == 12
-    assert lib.b4c_layernorm_bwd_add.argtypes == _lib.pre_ln_signatures()['b4c_layernorm_bwd_add'][1]
+    assert lib.b4c_layernorm_bwd_add.argtypes == _lib.signatures()['b4c_layernorm_bwd_add'][1]
     assert lib.b4c_layernorm_bwd_add_workspace_bytes(100, 128) == lib.b4c_layernorm_bwd_workspace_bytes(100, 128) > 0
     assert lib.b4c_layernorm_bwd_add_workspace_bytes(0, 128) == 0
 
