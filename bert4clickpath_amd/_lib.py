@@ -1,4 +1,4 @@
-"""ctypes binding of libb4c_hip.so (include/b4c.h).  There is no CPU fallback: if the
+"""ctypes binding of libb4c_hip.so (include/b4c.h and the extension headers of EXT_HEADER_PATHS).  There is no CPU fallback: if the
 library is missing, or a call fails, this raises -- the product path is the HIP path."""
 import ctypes
 import os
@@ -6,7 +6,11 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('B4C_LIB_PATH') or os.path.join(_HERE, 'libb4c_hip.so')     # override: A/B of two builds (scratch)
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')      # the whole ABI: a feature adds its entry points there
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')      # the main ABI (B4C_ABI_VERSION): signatures() describes it alone
+# Extension headers, same grammar, bound after the main table: a family added while b4c.h and its ABI version stay as they are.
+# Each carries its own version: (path, version constant, the function that returns it).
+EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_nce.h'),)
+_EXT_VERSIONS = {'b4c_nce.h': ('B4C_NCE_VERSION', 'b4c_nce_version')}
 
 
 class B4CError(RuntimeError):
@@ -95,6 +99,20 @@ def declared_symbols(header_path=HEADER_PATH):
     return sorted(signatures(header_path))
 
 
+def extension_signatures(header_paths=None, main=None):
+    """{name: (restype, [argtypes])} of every entry point the extension headers declare (include/b4c_nce.h), in one table.  A name
+    that two headers declare -- the main one (`main`: its table, default signatures()) included -- is refused as a duplicate inside
+    one header is."""
+    seen = dict(signatures() if main is None else main)
+    table = {}
+    for path in (EXT_HEADER_PATHS if header_paths is None else header_paths):
+        for name, sig in parse_header(_header_text(path)).items():
+            if name in seen:
+                raise B4CError('include/b4c.h declares %s twice: %r' % (name, '%s (again in %s)' % (name, os.path.basename(path))))
+            seen[name] = table[name] = sig
+    return table
+
+
 _C = header_constants(_header_text(HEADER_PATH))
 ABI_VERSION = _C['B4C_ABI_VERSION']       # b4c_abi_version() of the library must agree
 F32, BF16 = _C['B4C_F32'], _C['B4C_BF16']
@@ -114,6 +132,11 @@ NEXT_EXCL_NONE, NEXT_EXCL_HISTORY = _C['B4C_NEXT_EXCL_NONE'], _C['B4C_NEXT_EXCL_
 FEAT_EVENT, FEAT_ITEM = _C['B4C_FEAT_EVENT'], _C['B4C_FEAT_ITEM']        # source kinds of b4c_batch_features
 FEAT_MASKED, FEAT_KEPT = _C['B4C_FEAT_MASKED'], _C['B4C_FEAT_KEPT']      # what a [MASK] position of the item row does to a feature
 FEAT_CLOZE, FEAT_NEXT_TRAIN, FEAT_NEXT_EVAL = _C['B4C_FEAT_CLOZE'], _C['B4C_FEAT_NEXT_TRAIN'], _C['B4C_FEAT_NEXT_EVAL']      # row layouts
+
+_CX = {}
+for _path in EXT_HEADER_PATHS:
+    _CX.update(header_constants(_header_text(_path)))
+NCE_VERSION, NCE_COSINE, NCE_MAX_N = _CX['B4C_NCE_VERSION'], _CX['B4C_NCE_COSINE'], _CX['B4C_NCE_MAX_N']      # include/b4c_nce.h
 
 _lib = None
 
@@ -148,6 +171,28 @@ def lib():
             raise B4CError('%s is ABI %d, this binding expects ABI %d; rebuild it (`make -C bert4clickpath_amd/csrc`)'
                            % (LIB_PATH, have, ABI_VERSION))
         for name, (res, args) in sig.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                raise B4CError('%s (ABI %d) does not export %s; rebuild it (`make -C bert4clickpath_amd/csrc`)'
+                               % (LIB_PATH, have, name)) from None
+            fn.restype = res
+            fn.argtypes = args
+        # the extension table, after the main one: the same refusals (a name declared twice, a name the library lacks, a version
+        # that is not the header's)
+        ext = extension_signatures(main=sig)
+        for path in EXT_HEADER_PATHS:
+            const, getter = _EXT_VERSIONS[os.path.basename(path)]
+            try:
+                fn = getattr(L, getter)
+            except AttributeError:
+                raise B4CError('%s (ABI %d) does not export %s; rebuild it (`make -C bert4clickpath_amd/csrc`)'
+                               % (LIB_PATH, have, getter)) from None
+            fn.restype, fn.argtypes = ctypes.c_int, []
+            if int(fn()) != _CX[const]:
+                raise B4CError('%s (ABI %d) does not export %s = %d (it reports %d); rebuild it (`make -C bert4clickpath_amd/csrc`)'
+                               % (LIB_PATH, have, const, _CX[const], int(fn())))
+        for name, (res, args) in ext.items():
             try:
                 fn = getattr(L, name)
             except AttributeError:

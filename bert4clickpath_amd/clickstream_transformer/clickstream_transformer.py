@@ -363,7 +363,8 @@ class ClickstreamTransformer(nn.Module):
     def _masked_rows(self, inputs, training, flat_idx=None, cap=None, labels_padded=None, pack=False, n_real_tokens=None,
                      row_offsets=None):
         """Encoder output rows at the [MASK] positions, row-major.
-        flat_idx given: used as is; with row_offsets ([B + 1] int32: rows row_offsets[b] .. row_offsets[b + 1] of flat_idx are
+        flat_idx given: used as is (a callable: called with the first chain's (B, S) ids once they are on the device, returns the
+        indices); with row_offsets ([B + 1] int32: rows row_offsets[b] .. row_offsets[b + 1] of flat_idx are
         sequence b's, in ascending order; the rows behind row_offsets[B] hold -1) the last layer can still be evaluated at those
         rows only.  cap given: the sync-free form -- index generation and label compaction stay on
         the device, exactly `cap` rows come back (those beyond the real count R are zero rows whose label is -1) together
@@ -397,10 +398,13 @@ class ClickstreamTransformer(nn.Module):
             # the caller's rows and their per-sequence offsets (a next-item evaluation batch carries both): the same route; the rows
             # behind row_offsets[B] belong to no sequence and stay zeros
             dev = self.transformer.position_table.device
-            fi = torch.as_tensor(flat_idx).to(device=dev, dtype=torch.int32)
             off = torch.as_tensor(row_offsets).to(device=dev, dtype=torch.int32)
             self._row_offsets = off
-            rows, _, _, _, _ = self._encode(inputs, training, pack, n_real_tokens, rows_of=lambda ids_first, raw_first: (fi, off, None))
+
+            def named(ids_first, raw_first):
+                fi = flat_idx(ids_first) if callable(flat_idx) else flat_idx
+                return torch.as_tensor(fi).to(device=dev, dtype=torch.int32), off, None
+            rows, _, _, _, _ = self._encode(inputs, training, pack, n_real_tokens, rows_of=named)
             return rows, None
         if mq:
             rows, _, _, _, _ = self._encode(inputs, training, pack, n_real_tokens, rows_of=positions)
@@ -410,6 +414,8 @@ class ClickstreamTransformer(nn.Module):
         lab = None
         if flat_idx is None:
             flat_idx, _, lab = positions(ids_first, raw_first)
+        elif callable(flat_idx):
+            flat_idx = torch.as_tensor(flat_idx(ids_first)).to(device=enc.device, dtype=torch.int32)
         if self._packed is not None:
             flat_idx = ops.remap_index(flat_idx.contiguous(), self._packed.packed_of)
         rows = ops.GatherRowsFn.apply(enc.reshape(-1, d), flat_idx, flat_idx.shape[0])
@@ -566,6 +572,79 @@ class ClickstreamTransformer(nn.Module):
         return self.candidate_loss(inputs, batch['labels'], candidates=batch['candidates'], loss=loss, training=training,
                                    flat_idx=batch['flat_idx'], unit_grad=unit_grad, n_real_tokens=batch['n_real_tokens'], gbce_t=gbce_t,
                                    logq=logq, correct_target=correct_target)
+
+    CONTRASTIVE_SIMILARITIES = ('dot', 'cos')
+
+    def _sequence_rows(self, inputs, flat_idx, training, packed, n_real_tokens):
+        """one encoder row per sequence -> (B, d): at flat_idx ((B,) int32, b * S + s), or by default at each sequence's last item --
+        the last non-pad position in front of the chain's closing [SEP], index (non-pad count) - 2 of a right-padded row [CLS] [SEP]
+        items .. [SEP], from the counts the device already has (the packed layout's, else one b4c_nonpad_positions launch)."""
+        pack = self._use_packed(inputs, packed, n_real_tokens)
+
+        def last_items(ids_first):
+            B, S = ids_first.shape
+            if self._packed is not None:
+                counts = self._packed.cu[1:] - self._packed.cu[:-1]
+            else:
+                counts = ops.nonpad_positions(ids_first.contiguous(), B * S)[0]
+            return (torch.arange(B, dtype=torch.int32, device=ids_first.device) * S + (counts.to(torch.int32) - 2).clamp(min=0))
+
+        if flat_idx is None:
+            fi = last_items
+        else:
+            fi = torch.as_tensor(flat_idx, device=self.transformer.position_table.device).to(torch.int32).reshape(-1)
+        first_in = self.sequential_input_config[list(self.sequential_input_config.keys())[0]][0]
+        x = inputs[first_in]
+        B = int(x.shape[0]) if isinstance(x, torch.Tensor) else int(np.asarray(x, dtype=object).shape[0])
+        if flat_idx is not None and fi.shape[0] != B:
+            raise B4CError('contrastive_loss: flat_idx names %d rows for %d sequences (one position per sequence)' % (fi.shape[0], B))
+        off = torch.arange(B + 1, dtype=torch.int32, device=self.transformer.position_table.device)
+        rows, _ = self._masked_rows(inputs, training, fi, pack=pack, n_real_tokens=n_real_tokens, row_offsets=off)
+        return rows
+
+    def contrastive_loss(self, inputs, inputs_b=None, flat_idx=None, temperature=1.0, similarity='dot', same_target=None, training=True,
+                         packed=None, n_real_tokens=None):
+        """In-batch contrastive loss between two views of the batch's B sequences (InfoNCE / NT-Xent: the auxiliary loss of CL4SRec
+        and DuoRec), a scalar to add to any of the training losses:
+            loss = model.next_item_loss(batch) + lam * model.contrastive_loss(inputs, ...)
+        A sequence's representation is its encoder row at one position: flat_idx ((B,) int32, b * S + s, the same for both views), by
+        default the position of its last item (found on the device, no host loop).  A model on the masked-query route evaluates its
+        last layer at those B rows only.
+        Views.  inputs_b given: the second view, B sequences the caller augmented (CL4SRec: crop / mask / reorder).  inputs_b None: the
+        same inputs are encoded twice under two successive draws of the dropout seeds (DuoRec's unsupervised view, SimCSE); that needs
+        training=True and dropout_rate > 0 -- otherwise the two views are identical and the loss a constant: B4CError.
+        Loss.  z = cat(rows_a, rows_b) (2B rows), the positive of row i is the other view of its sequence, the negatives are every
+        other row of the 2B; same_target ((B,) integer, negative: none; DuoRec): two sequences with the same target item are not
+        each other's negatives.  s = z_i . z_j / temperature ('dot') or the rows' cosine / temperature ('cos'); mean over the 2B rows
+        of logsumexp over the keys - s at the positive.  One fused kernel pair (ops.InfoNCEFn, include/b4c_nce.h): the [2B, 2B]
+        scores never reach memory; d_model must be a multiple of 8, at most 128.
+        Cost: two more encoder passes on top of the main loss's (one per view).  Under data parallelism the negatives are the rank's
+        own batch: there is no all-gather.  No reference oracle (the reference trains with the Cloze loss alone); the float64
+        restatement is tests/nce_ref.py."""
+        if similarity not in self.CONTRASTIVE_SIMILARITIES:
+            raise B4CError("contrastive_loss: similarity %r ('dot' or 'cos')" % (similarity,))
+        if inputs_b is None and not (training and float(self.dropout_rate) > 0.0):
+            raise B4CError('contrastive_loss: inputs_b=None takes its two views from two dropout realisations of the same inputs; that '
+                           'needs training=True and dropout_rate > 0 (here training=%r, dropout_rate=%g): the views would be identical '
+                           'and the loss constant.  Pass an augmented second view as inputs_b.' % (bool(training), float(self.dropout_rate)))
+        rows_a = self._sequence_rows(inputs, flat_idx, training, packed, n_real_tokens)
+        rows_b = self._sequence_rows(inputs if inputs_b is None else inputs_b, flat_idx, training, packed,
+                                     n_real_tokens if inputs_b is None else None)
+        B = rows_a.shape[0]
+        if rows_b.shape[0] != B:
+            raise B4CError('contrastive_loss: the two views hold %d and %d sequences' % (B, rows_b.shape[0]))
+        dev = rows_a.device
+        z = torch.cat([rows_a, rows_b], 0)
+        idx = torch.arange(B, dtype=torch.int32, device=dev)
+        pos = torch.cat([idx + B, idx])
+        group = None
+        if same_target is not None:
+            g = torch.as_tensor(same_target, device=dev).reshape(-1)
+            if g.shape[0] != B or g.is_floating_point():
+                raise B4CError('contrastive_loss: same_target must be a (B,) = (%d,) integer tensor (negative: none)' % B)
+            g = g.to(torch.int32)
+            group = torch.cat([g, g])
+        return ops.InfoNCEFn.apply(z, pos, group, float(temperature), similarity)
 
     def _next_item_inputs(self, batch):
         """the model's inputs of a next-item batch (no device work).  Every chain names one input: the layout [CLS] [SEP] values ..

@@ -1801,6 +1801,79 @@ def candidate_loss_bwd(h, table, cand, g, gscale, V, dtable, dbias, row_off=0):
     return dh
 
 
+# ---- in-batch contrastive loss (include/b4c_nce.h): NT-Xent / InfoNCE over the rows of a batch ----
+NCE_SIMILARITIES = ('dot', 'cos')
+
+
+def _nce_args(who, z, pos, group, temperature, similarity):
+    """the operand checks nce_fwd and nce_bwd share -> (pos, group or None, N, K, dtype code, inv_temp, flags)"""
+    if not isinstance(z, torch.Tensor) or z.dim() != 2:
+        raise B4CError('%s: z must be an [N, K] tensor' % who)
+    N, K = z.shape
+    dt = dt_code(z.dtype)
+    per16 = 16 // z.element_size()
+    if K % 8 or not 8 <= K <= 128 or z.stride(1) != 1 or z.stride(0) % per16 or z.stride(0) < K or z.data_ptr() % 16:
+        raise B4CError('%s: K = %d (a multiple of 8, 8 .. 128, contiguous 16-byte aligned rows)' % (who, K))
+    if N >= L.NCE_MAX_N:
+        raise B4CError('%s: N = %d rows (below 2^24)' % (who, N))
+    if similarity not in NCE_SIMILARITIES:
+        raise B4CError("%s: similarity %r ('dot' or 'cos')" % (who, similarity))
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        raise B4CError('%s: temperature = %r (a finite number > 0)' % (who, temperature)) from None
+    if not (0.0 < t < float('inf')) or not (0.0 < 1.0 / t < 3.0e38):
+        raise B4CError('%s: temperature = %r (a finite number > 0 whose inverse is a finite float)' % (who, temperature))
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or pos.shape != (N,):
+        raise B4CError('%s: pos must be an int32 [N] = [%d] tensor (the row of each row\'s positive; out of range or itself: ignored)'
+                       % (who, N))
+    if group is not None and (not isinstance(group, torch.Tensor) or group.dtype != torch.int32 or group.shape != (N,)):
+        raise B4CError('%s: group must be None or an int32 [N] = [%d] tensor (negative: none)' % (who, N))
+    _cuda(z, pos, group)
+    return pos.contiguous(), (None if group is None else group.contiguous()), N, K, dt, 1.0 / t, (L.NCE_COSINE if similarity == 'cos' else 0)
+
+
+def nce_fwd(z, pos, group=None, temperature=1.0, similarity='dot'):
+    """-> (item_loss fp32 [N], lse fp32 [N], rnorm fp32 [N] or None) of the in-batch contrastive loss (b4c_nce_fwd, include/b4c_nce.h):
+    row i is a query when pos[i] names another row of the batch; its keys are that positive and every other query row, except (group
+    given) rows of its own non-negative group; item_loss[i] = logsumexp over the keys of s_ij - s_{i, pos[i]}, s = z_i . z_j /
+    temperature ('dot') or the cosine of the two rows / temperature ('cos': rnorm comes back, 1 / max(||z_i||, 1e-12)).  Other rows:
+    0.  z [N, K] bf16 or fp32, K % 8 == 0, 8 .. 128.  The [N, N] scores never reach memory."""
+    who = 'nce_fwd'
+    pos, group, N, K, dt, inv_t, flags = _nce_args(who, z, pos, group, temperature, similarity)
+    dev = z.device
+    item = torch.empty(N, dtype=torch.float32, device=dev)
+    lse = torch.empty(N, dtype=torch.float32, device=dev)
+    rnorm = torch.empty(N, dtype=torch.float32, device=dev) if flags else None
+    if N == 0:
+        return item, lse, rnorm
+    with _record(who, N * K * z.element_size() * (1 + (N + 127) // 128) + N * 24, 2 * N * N * K):
+        L.check(L.lib().b4c_nce_fwd(_p(z), z.stride(0), N, K, dt, _p(pos), _p(group), inv_t, flags, _p(rnorm), _p(lse), _p(item), _st()), who)
+    return item, lse, rnorm
+
+
+def nce_bwd(z, pos, group, temperature, similarity, rnorm, lse, gscale):
+    """-> dz [N, K] in z's dtype: gscale[0] times the derivative of the sum of nce_fwd's item_loss by z (b4c_nce_bwd), written, not
+    accumulated.  lse, rnorm: nce_fwd's (rnorm None for 'dot'); gscale a device fp32 [1].  One sweep over the score tiles serves
+    a row's own loss and its part in every other row's."""
+    who = 'nce_bwd'
+    pos, group, N, K, dt, inv_t, flags = _nce_args(who, z, pos, group, temperature, similarity)
+    if not isinstance(lse, torch.Tensor) or lse.dtype != torch.float32 or lse.shape != (N,) or not lse.is_contiguous():
+        raise B4CError('%s: lse must be the contiguous fp32 [N] = [%d] of nce_fwd' % (who, N))
+    if flags and (not isinstance(rnorm, torch.Tensor) or rnorm.dtype != torch.float32 or rnorm.shape != (N,) or not rnorm.is_contiguous()):
+        raise B4CError("%s: similarity 'cos' needs the contiguous fp32 [N] = [%d] rnorm of nce_fwd" % (who, N))
+    if not isinstance(gscale, torch.Tensor) or gscale.dtype != torch.float32 or gscale.numel() != 1:
+        raise B4CError('%s: gscale must be a device fp32 tensor of one element' % who)
+    _cuda(lse, gscale, rnorm if flags else None)
+    dz = torch.empty(N, K, dtype=z.dtype, device=z.device)
+    if N == 0:
+        return dz
+    with _record(who, N * K * z.element_size() * (2 + (N + 127) // 128) + N * 28, 4 * N * N * K):
+        L.check(L.lib().b4c_nce_bwd(_p(z), z.stride(0), N, K, dt, _p(pos), _p(group), inv_t, flags, _p(rnorm) if flags else None, _p(lse),
+                                    _p(gscale), _p(dz), K, _st()), who)
+    return dz
+
+
 # ---- Cloze batches (include/b4c.h "Cloze batches"): model inputs and padded labels from a CSR data set on the device ----
 CLOZE_TRAIN, CLOZE_EVAL = 0, 1
 CLOZE_MAX_WIDTH, CLOZE_MAX_LABELS = L.MAX_BATCH_WIDTH, L.MAX_CLOZE_LABELS
@@ -3734,3 +3807,29 @@ class CandidateLossFn(torch.autograd.Function):
         dh = candidate_loss_bwd(h, table.detach(), cand, g, gscale.contiguous(), bias.shape[0], tg, bg, ctx.row_off)
         _ready(*((bias,) if ctx.shared_table else (table, bias)))
         return sink_returns(ctx, (dh,), actx, (tg, bg))
+
+
+class InfoNCEFn(torch.autograd.Function):
+    """In-batch contrastive loss (NT-Xent / InfoNCE; include/b4c_nce.h): the mean of nce_fwd's item_loss over the live rows -- rows
+    whose pos names another row of the batch.  apply(z [N, K], pos int32 [N], group int32 [N] or None, temperature, similarity) ->
+    scalar.  The count of live rows and gscale = 1 / max(count, 1) are formed on the device: no read-back."""
+
+    @staticmethod
+    def forward(ctx, z, pos, group, temperature=1.0, similarity='dot'):
+        z = z.contiguous()
+        N = z.shape[0]
+        item, lse, rnorm = nce_fwd(z, pos, group, temperature, similarity)
+        idx = torch.arange(N, dtype=torch.int32, device=z.device)
+        live = ((pos >= 0) & (pos < N) & (pos != idx)).sum().to(torch.float32)
+        scale = (1.0 / live.clamp(min=1.0)).reshape(1)
+        ctx.save_for_backward(z, pos, lse, scale, *(() if rnorm is None else (rnorm,)))
+        ctx.group, ctx.temperature, ctx.similarity = group, temperature, similarity
+        return item.sum() * scale[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        z, pos, lse, scale = ctx.saved_tensors[:4]
+        rnorm = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        gscale = (scale * gout.to(torch.float32)).contiguous()
+        dz = nce_bwd(z, pos, ctx.group, ctx.temperature, ctx.similarity, rnorm, lse, gscale)
+        return dz, None, None, None, None

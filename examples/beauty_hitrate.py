@@ -94,6 +94,45 @@ def add_objective_argument(ap):
                          'evaluation rows end at the item in front of the target: no [MASK] in training or in evaluation')
 
 
+def add_contrastive_arguments(ap):
+    ap.add_argument('--contrastive_weight', type=float, default=0.0, metavar='LAM',
+                    help='LAM > 0 adds LAM * model.contrastive_loss to the training loss: in-batch InfoNCE between two dropout views of '
+                         'every sequence of the batch, read at its last item (the auxiliary loss of DuoRec / CL4SRec; needs --dropout > '
+                         '0; two more encoder passes per step).  With every objective and --train_loss')
+    ap.add_argument('--contrastive_temperature', type=float, default=1.0, help='with --contrastive_weight: the temperature')
+    ap.add_argument('--contrastive_sim', default='dot', choices=['dot', 'cos'], help='with --contrastive_weight: dot product or cosine')
+    ap.add_argument('--contrastive_same_target', action='store_true',
+                    help='with --contrastive_weight: two sequences with the same (last) target item are not each other\'s negatives (DuoRec)')
+
+
+def check_contrastive_arguments(ap, a):
+    if a.contrastive_weight < 0 or a.contrastive_temperature <= 0:
+        ap.error('--contrastive_weight must be >= 0 and --contrastive_temperature > 0')
+    if a.contrastive_weight > 0 and a.dropout <= 0:
+        ap.error('--contrastive_weight takes its two views from dropout: it needs --dropout > 0')
+
+
+def last_targets(labels_padded=None, labels=None, row_offsets=None):
+    """the last target of every sequence of a batch, on the device (-1: none): of the padded (B, M) Cloze labels, or of the compact
+    labels of a next-item batch and their per-sequence offsets"""
+    if labels_padded is not None:
+        lab = labels_padded.to(torch.int64)
+        n = (lab >= 0).sum(1)
+        return torch.where(n > 0, lab.gather(1, (n - 1).clamp(min=0)[:, None])[:, 0], torch.full_like(n, -1))
+    off = row_offsets.long()
+    if labels.numel() == 0:
+        return torch.full((off.shape[0] - 1,), -1, dtype=torch.int64, device=off.device)
+    return torch.where(off[1:] > off[:-1], labels.long()[(off[1:] - 1).clamp(min=0, max=labels.shape[0] - 1)], torch.full_like(off[1:], -1))
+
+
+def contrastive_term(model, a, inputs, same_target=None, **kw):
+    """--contrastive_weight times the in-batch contrastive loss of two dropout views of `inputs` (0.0 without the option)"""
+    if a.contrastive_weight <= 0:
+        return 0.0
+    return a.contrastive_weight * model.contrastive_loss(inputs, temperature=a.contrastive_temperature, similarity=a.contrastive_sim,
+                                                         same_target=same_target if a.contrastive_same_target else None, **kw)
+
+
 def check_train_loss_arguments(ap, a):
     if a.logq and (a.train_loss == 'full' or not a.device_batches):
         ap.error('--logq corrects sampled negatives drawn from the device data set\'s counts: it needs --device_batches and a '
@@ -195,7 +234,9 @@ def main():
                          'the item\'s count in the training split (masked with the item); default 0: the one-feature model')
     add_train_loss_arguments(ap)
     add_objective_argument(ap)
+    add_contrastive_arguments(ap)
     a = ap.parse_args()
+    check_contrastive_arguments(ap, a)
     if a.popularity_buckets and (not a.device_batches or a.paper_model or a.popularity_buckets < 0):
         ap.error('--popularity_buckets K > 0 needs --device_batches and the reference\'s model (no --paper_model)')
     if a.objective == 'next_item' and not a.device_batches:
@@ -236,14 +277,22 @@ def main():
         opt.zero_grad()
         if next_item:                 # unmasked rows, every position's target and its negatives: all built on the device
             loss = next_item_training_loss(model, a, b, sampling['logq'])
+            if a.contrastive_weight > 0:
+                loss = loss + contrastive_term(model, a, model._next_item_inputs(b), last_targets(labels=b['labels'], row_offsets=b['row_offsets']),
+                                               n_real_tokens=b['n_real_tokens'])
         elif dev_data is not None:      # items and padded labels are on the device already; nothing is read back
             loss = training_loss(model, a, dev_data.inputs(b, 'asin'), b['labels_padded'], **sampling,
                                  max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
+            if a.contrastive_weight > 0:
+                loss = loss + contrastive_term(model, a, dev_data.inputs(b, 'asin'), last_targets(labels_padded=b['labels_padded']),
+                                               n_real_tokens=b['n_real_tokens'])
         else:
             ids = torch.from_numpy(b['ids'])
             items = ids[:, 2:-1].contiguous().cuda()
             loss = training_loss(model, a, {'asin': items}, torch.from_numpy(b['labels']).cuda(),
                                  flat_idx=torch.from_numpy(b['flat_idx']).cuda())
+            if a.contrastive_weight > 0:
+                loss = loss + contrastive_term(model, a, {'asin': items}, last_targets(labels_padded=torch.from_numpy(b['labels_padded']).cuda()))
         loss.backward()
         opt.step()
         if step % 100 == 0 or step == a.steps - 1:
@@ -314,7 +363,10 @@ def main():
         out['data_protocol'] = protocol
         out['objective'] = a.objective
         out['popularity_buckets'] = a.popularity_buckets
-    if a.holdout == 2:                # the split a model is selected on; the test numbers above are read once, at the end
+    if a.contrastive_weight > 0:
+        out['contrastive'] = dict(weight=a.contrastive_weight, temperature=a.contrastive_temperature, similarity=a.contrastive_sim,
+                                  same_target=a.contrastive_same_target)
+    if a.holdout == 2:               # the split a model is selected on; the test numbers above are read once, at the end
         out['valid'] = evaluate('valid')
     print(json.dumps(out))
 
