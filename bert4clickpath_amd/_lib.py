@@ -1,4 +1,4 @@
-"""ctypes binding of libb4c_hip.so (include/b4c.h and the extension headers of EXT_HEADER_PATHS).  There is no CPU fallback: if the
+"""ctypes binding of libb4c_hip.so (include/b4c.h and the extension headers of EXT_HEADER_PATHS and AUG_HEADER_PATHS).  There is no CPU fallback: if the
 library is missing, or a call fails, this raises -- the product path is the HIP path."""
 import ctypes
 import os
@@ -11,6 +11,10 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')      # th
 # Each carries its own version: (path, version constant, the function that returns it).
 EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_nce.h'),)
 _EXT_VERSIONS = {'b4c_nce.h': ('B4C_NCE_VERSION', 'b4c_nce_version')}
+# A second list of extension headers with its own version table, bound after the first (extension_signatures() with its defaults
+# describes the first list alone): the contrastive views.
+AUG_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_aug.h'),)
+_AUG_VERSIONS = {'b4c_aug.h': ('B4C_AUG_VERSION', 'b4c_aug_version')}
 
 
 class B4CError(RuntimeError):
@@ -138,7 +142,39 @@ for _path in EXT_HEADER_PATHS:
     _CX.update(header_constants(_header_text(_path)))
 NCE_VERSION, NCE_COSINE, NCE_MAX_N = _CX['B4C_NCE_VERSION'], _CX['B4C_NCE_COSINE'], _CX['B4C_NCE_MAX_N']      # include/b4c_nce.h
 
+_CA = {}
+for _path in AUG_HEADER_PATHS:
+    _CA.update(header_constants(_header_text(_path)))
+AUG_VERSION, AUG_MAX_VIEWS = _CA['B4C_AUG_VERSION'], _CA['B4C_AUG_MAX_VIEWS']      # include/b4c_aug.h
+AUG_CROP, AUG_MASK, AUG_REORDER, AUG_SAME_TARGET = _CA['B4C_AUG_CROP'], _CA['B4C_AUG_MASK'], _CA['B4C_AUG_REORDER'], _CA['B4C_AUG_SAME_TARGET']
+
 _lib = None
+
+
+def _bind_extension(L, have, paths, versions, consts, seen):
+    """bind the entry points of one list of extension headers after the tables `seen` ({name: signature}): the same refusals as for
+    the main table (a name declared twice, a name the library lacks) and a version that is not the header's -> the list's table"""
+    ext = extension_signatures(header_paths=paths, main=seen)
+    for path in paths:
+        const, getter = versions[os.path.basename(path)]
+        try:
+            fn = getattr(L, getter)
+        except AttributeError:
+            raise B4CError('%s (ABI %d) does not export %s; rebuild it (`make -C bert4clickpath_amd/csrc`)'
+                           % (LIB_PATH, have, getter)) from None
+        fn.restype, fn.argtypes = ctypes.c_int, []
+        if int(fn()) != consts[const]:
+            raise B4CError('%s (ABI %d) does not export %s = %d (it reports %d); rebuild it (`make -C bert4clickpath_amd/csrc`)'
+                           % (LIB_PATH, have, const, consts[const], int(fn())))
+    for name, (res, args) in ext.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise B4CError('%s (ABI %d) does not export %s; rebuild it (`make -C bert4clickpath_amd/csrc`)'
+                           % (LIB_PATH, have, name)) from None
+        fn.restype = res
+        fn.argtypes = args
+    return ext
 
 
 def lib():
@@ -178,28 +214,10 @@ def lib():
                                % (LIB_PATH, have, name)) from None
             fn.restype = res
             fn.argtypes = args
-        # the extension table, after the main one: the same refusals (a name declared twice, a name the library lacks, a version
-        # that is not the header's)
-        ext = extension_signatures(main=sig)
-        for path in EXT_HEADER_PATHS:
-            const, getter = _EXT_VERSIONS[os.path.basename(path)]
-            try:
-                fn = getattr(L, getter)
-            except AttributeError:
-                raise B4CError('%s (ABI %d) does not export %s; rebuild it (`make -C bert4clickpath_amd/csrc`)'
-                               % (LIB_PATH, have, getter)) from None
-            fn.restype, fn.argtypes = ctypes.c_int, []
-            if int(fn()) != _CX[const]:
-                raise B4CError('%s (ABI %d) does not export %s = %d (it reports %d); rebuild it (`make -C bert4clickpath_amd/csrc`)'
-                               % (LIB_PATH, have, const, _CX[const], int(fn())))
-        for name, (res, args) in ext.items():
-            try:
-                fn = getattr(L, name)
-            except AttributeError:
-                raise B4CError('%s (ABI %d) does not export %s; rebuild it (`make -C bert4clickpath_amd/csrc`)'
-                               % (LIB_PATH, have, name)) from None
-            fn.restype = res
-            fn.argtypes = args
+        # the extension tables, after the main one and in this order: the same refusals (a name declared twice, a name the library
+        # lacks, a version that is not the header's)
+        ext = _bind_extension(L, have, EXT_HEADER_PATHS, _EXT_VERSIONS, _CX, sig)
+        _bind_extension(L, have, AUG_HEADER_PATHS, _AUG_VERSIONS, _CA, {**sig, **ext})
         _lib = L
     return _lib
 

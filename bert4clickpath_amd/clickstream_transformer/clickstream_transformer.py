@@ -603,14 +603,17 @@ class ClickstreamTransformer(nn.Module):
         return rows
 
     def contrastive_loss(self, inputs, inputs_b=None, flat_idx=None, temperature=1.0, similarity='dot', same_target=None, training=True,
-                         packed=None, n_real_tokens=None):
+                         packed=None, n_real_tokens=None, n_real_tokens_b=None):
         """In-batch contrastive loss between two views of the batch's B sequences (InfoNCE / NT-Xent: the auxiliary loss of CL4SRec
         and DuoRec), a scalar to add to any of the training losses:
             loss = model.next_item_loss(batch) + lam * model.contrastive_loss(inputs, ...)
         A sequence's representation is its encoder row at one position: flat_idx ((B,) int32, b * S + s, the same for both views), by
         default the position of its last item (found on the device, no host loop).  A model on the masked-query route evaluates its
         last layer at those B rows only.
-        Views.  inputs_b given: the second view, B sequences the caller augmented (CL4SRec: crop / mask / reorder).  inputs_b None: the
+        Views.  inputs_b given: the second view, B sequences the caller augmented (CL4SRec: crop / mask / reorder; DuoRec: the row
+        of another sequence in front of the same target) -- cloze_batches.DeviceCloze.views builds them on the device; its
+        view['n_real_tokens'] as n_real_tokens_b lets the second view take the padding-free layout too (None: the dense one, unless
+        packed=True).  inputs_b None: the
         same inputs are encoded twice under two successive draws of the dropout seeds (DuoRec's unsupervised view, SimCSE); that needs
         training=True and dropout_rate > 0 -- otherwise the two views are identical and the loss a constant: B4CError.
         Loss.  z = cat(rows_a, rows_b) (2B rows), the positive of row i is the other view of its sequence, the negatives are every
@@ -629,7 +632,7 @@ class ClickstreamTransformer(nn.Module):
                            'and the loss constant.  Pass an augmented second view as inputs_b.' % (bool(training), float(self.dropout_rate)))
         rows_a = self._sequence_rows(inputs, flat_idx, training, packed, n_real_tokens)
         rows_b = self._sequence_rows(inputs if inputs_b is None else inputs_b, flat_idx, training, packed,
-                                     n_real_tokens if inputs_b is None else None)
+                                     n_real_tokens if inputs_b is None else n_real_tokens_b)
         B = rows_a.shape[0]
         if rows_b.shape[0] != B:
             raise B4CError('contrastive_loss: the two views hold %d and %d sequences' % (B, rows_b.shape[0]))

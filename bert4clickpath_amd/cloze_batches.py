@@ -21,13 +21,18 @@ such a batch.
 features={name: Feature(...)} hands over side columns of the click paths -- one value per event (an action, a dwell bucket) or one
 per item (a category, a brand).  They are validated and uploaded once; every batch dict then carries 'features': {name: (B, W)
 int64 ids} built from the item row in one launch (ops.batch_features, include/b4c.h), [MASK] where the item row has
-it unless the feature says on_mask='keep'.  inputs(batch, item_feature) is the dict the model's entry points take."""
+it unless the feature says on_mask='keep'.  inputs(batch, item_feature) is the dict the model's entry points take.
+
+views(batch, seed, ...) builds contrastive views of a training batch's rows on the device (ops.augment_views, include/b4c_aug.h):
+CL4SRec's item crop / mask / reorder and DuoRec's same-target row, each with the host-known n_real_tokens that lets
+model.contrastive_loss(..., inputs_b=, n_real_tokens_b=) encode the view padding-free."""
 import collections
 
 import numpy as np
 import torch
 
 from . import ops
+from . import ops as _ops            # (DeviceCloze.views has an argument called ops)
 from .input_pipeline import EVAL, MASKED_PERCENTAGE, MAX_MASKED_ITEMS, TRAIN
 
 _MODES = {TRAIN: ops.CLOZE_TRAIN, EVAL: ops.CLOZE_EVAL, ops.CLOZE_TRAIN: ops.CLOZE_TRAIN, ops.CLOZE_EVAL: ops.CLOZE_EVAL}
@@ -117,6 +122,7 @@ class DeviceCloze:
         self._win_first = np.cumsum(self._win_count) - self._win_count
         self._eval = {}                                              # split -> (Windows, device tensors)
         self._next_tr, self._next_ev = None, {}                      # the next-item rows' target counts: TRAIN table, split -> EVAL tables
+        self._tgt_index = None                                       # the same-target index of views(): host arrays, device tensors
         self.features = self._check_features(features)              # name -> (int32 host values, Feature)
         self.items_dev = self.offsets_dev = self.windows_dev = None
         self._feature_sources = []                                   # (device values, per, on_mask) in the order of self.features
@@ -218,6 +224,7 @@ class DeviceCloze:
         self._need_device()
         items, lab, nm = ops.cloze_batch_windows(self.items_dev, self.offsets_dev, dev[0], dev[1], dev[2], row_dev, W, _MODES[mode], seed,
                                                  self.masked_percentage, self.max_masked, last_thr=self.last_thr)
+        row_dev._host_rows = (_MODES[mode] == ops.CLOZE_TRAIN, row_host)       # (what views() computes its host counts from)
         out = {'items': items, 'labels_padded': lab, 'n_masked': nm, 'seq_idx': seq_dev, 'win_idx': row_dev,
                'n_real_tokens': int(L.sum()) + 3 * len(L)}
         if self.features:
@@ -362,6 +369,7 @@ class DeviceCloze:
         items, flat, lab, cand, short = ops.next_item_batch(
             self.items_dev, self.offsets_dev, win[0], win[1], win[2], row_dev, row_off, W, mode, R, self.V, holdout=holdout,
             max_len=self.max_len, num_negatives=num_negatives, seed=seed, exclude=exclude, item_cdf=item_cdf, rows=rows)
+        row_dev._host_rows = (mode == ops.NEXT_TRAIN, np.asarray(row_host, dtype=np.int64))
         out = {'items': items, 'flat_idx': flat, 'labels': lab, 'candidates': cand, 'row_offsets': row_off, 'short': short,
                'seq_idx': seq_dev, 'win_idx': row_dev, 'n_targets': R, 'n_real_tokens': int(n_in.sum()) + 3 * B}
         if self.features:
@@ -413,6 +421,153 @@ class DeviceCloze:
                                  None, None, drop)
             b['target_seq_idx'] = tgt_seq_dev[int(first[s]):int(first[e])]
             yield b
+
+    # ---- contrastive views of a training batch (include/b4c_aug.h) ---------------------------------------------------------------
+    VIEW_OBJECTIVES = {'cloze': ops.FEAT_CLOZE, 'next_item': ops.FEAT_NEXT_TRAIN}
+
+    def target_index(self):
+        """host (tgt_first int64 [V + 1], tgt_tok int64 [n], tgt_seq int32 [n], key int64 [n]): the same-target index -- every
+        token at position q of its sequence with 1 <= q < T_g (a target of the training view with an input in front of it), in the
+        order (item, token index); item y's list is tgt_tok[tgt_first[y] .. tgt_first[y + 1]).  key = item * (n_tok + 1) + token,
+        ascending: the host's search array.  Built once, with numpy, and uploaded once."""
+        if self._tgt_index is None:
+            n_tok = len(self.items)
+            pos = np.arange(n_tok, dtype=np.int64) - np.repeat(self.offsets[:-1], self.lengths)
+            tok = np.flatnonzero((pos >= 1) & (pos < np.repeat(np.maximum(self.lengths - self.holdout, 0), self.lengths))).astype(np.int64)
+            tok = tok[np.argsort(self.items[tok], kind='stable')]
+            seq = np.repeat(np.arange(self.n_seq, dtype=np.int32), self.lengths)[tok]
+            y = self.items[tok].astype(np.int64)
+            first = np.concatenate([[0], np.cumsum(np.bincount(y, minlength=self.V))]).astype(np.int64)
+            host = (first, tok, seq, y * (n_tok + 1) + tok)
+            dev = None
+            if self.items_dev is not None:
+                dev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.items_dev.device) for a in host[:3])
+            self._tgt_index = (host, dev)
+        return self._tgt_index[0]
+
+    def _view_rows(self, win, layout, W):
+        """host int64 [B]: (i, n) of the named windows' source rows -- the CSR index of the first token and the token count of
+        the row rule of include/b4c.h (an empty row: n = 0)"""
+        ok = win >= 0
+        w = np.where(ok, win, 0)
+        if not self.n_windows:
+            return np.zeros(len(win), np.int64), np.zeros(len(win), np.int64)
+        g, a, L = (t[w].astype(np.int64) for t in self.windows)
+        if layout == ops.FEAT_CLOZE:
+            first, n = a, np.minimum(L, W)
+        else:
+            T = np.maximum(self.lengths[g] - self.holdout, 0)
+            first = np.where(a > 0, a - 1, 0)
+            n = np.maximum(np.minimum(np.minimum(np.where(a > 0, L, L - 1), W), T - first - 1), 0)
+        return self.offsets[g] + first, np.where(ok, n, 0)
+
+    def view_lengths(self, win_idx, seed, ops=('crop', 'mask', 'reorder'), n_views=2, objective='next_item', width=None, crop_ratio=0.6,
+                     mask_ratio=0.3, reorder_ratio=0.6):
+        """host int64 [n_views, B]: the item count of every view views() builds of the windows win_idx at width W (None: the longest
+        source row) -- the rule of include/b4c_aug.h as far as the lengths need it (the op, then the length), evaluated with
+        ops.rand64_host and numpy from the window table, the offsets and the same-target index: no loop over rows, no device work."""
+        who = 'DeviceCloze.view_lengths'
+        if objective not in self.VIEW_OBJECTIVES:
+            raise ValueError("DeviceCloze: objective %r ('cloze' or 'next_item')" % (objective,))
+        layout = self.VIEW_OBJECTIVES[objective]
+        win = np.asarray(win_idx, dtype=np.int64).reshape(-1)
+        if len(win) and win.max() >= self.n_windows:
+            raise ValueError('DeviceCloze: window indices outside [0, %d)' % self.n_windows)
+        W = int(width) if width is not None else max(int(self._view_rows(win, layout, _ops.CLOZE_MAX_WIDTH)[1].max()) if len(win) else 0, 1)
+        W, layout, _, max_len, n_views, mask, crop_ratio, mask_ratio, reorder_ratio = _ops._augment_args(
+            who, W, layout, self.holdout, self.max_len, n_views, ops, seed, crop_ratio, mask_ratio, reorder_ratio)
+        i, n = self._view_rows(win, layout, W)
+        ctr = i.astype(np.uint64)
+        enabled = np.array([bit for bit in _ops.AUG_OPS.values() if mask & bit], dtype=np.int64)
+        share = lambda ratio: (n.astype(np.float32) * np.float32(ratio)).astype(np.int64)
+        same = bool(mask & _ops.L.AUG_SAME_TARGET)
+        if same:
+            first, tok, seq, key = self.target_index()
+            t = np.where(n > 0, i + n, 0)
+            y = self.items[t].astype(np.int64) if len(self.items) else np.zeros(len(t), np.int64)
+            want = y * (len(self.items) + 1) + t
+            at = np.searchsorted(key, want, side='left')
+            found = (at < len(key)) & (key[np.minimum(at, max(len(key) - 1, 0))] == want) if len(key) else np.zeros(len(t), bool)
+            own = at - first[y]
+            others = first[y + 1] - first[y] - found
+        out = np.zeros((n_views, len(win)), np.int64)
+        for v in range(n_views):
+            seed_v = int(_ops.rand64_host(int(seed) ^ 0xA0761D6478BD642F, np.array([v], np.uint64))[0])
+            op = enabled[_ops.mulhi64_host(_ops.rand64_host(seed_v ^ 0xE7037ED1A0B428DB, ctr), len(enabled)).astype(np.int64)]
+            length = np.where(op == _ops.L.AUG_CROP, np.maximum(share(crop_ratio), 1), n)
+            if same and len(key):
+                h_at = _ops.rand64_host(seed_v ^ 0x8EBC6AF09C88C6E3, ctr)
+                u = _ops.mulhi64_host(h_at, np.maximum(others, 1)).astype(np.int64)
+                k = np.minimum(first[y] + u + (found & (u >= own)), len(key) - 1)
+                q = tok[k] - self.offsets[seq[k]]
+                length = np.where((op == _ops.L.AUG_SAME_TARGET) & (others > 0), np.minimum(np.minimum(q, W), max_len), length)
+            out[v] = np.where(n > 0, length, 0)
+        return out
+
+    def views(self, batch, seed, ops=('crop', 'mask', 'reorder'), n_views=2, objective=None, crop_ratio=0.6, mask_ratio=0.3, reorder_ratio=0.6,
+              win_idx=None):
+        """n_views contrastive views of a TRAIN batch's rows, built on the device in one launch (ops.augment_views, include/b4c_aug.h)
+        -> a list of n_views dicts(items (B, W) int64 -- W the batch's own width --, n_items, op, target (B,) int32, src_tok (B, W)
+        int64: device tensors; n_real_tokens: host int; features {name: (B, W) int64} when the data set has side features; self_count
+        int32 [1], shared: the 'same_target' rows that had no partner).
+        ops: the operators one of which is drawn per (row, view) -- CL4SRec: ('crop', 'mask', 'reorder'); DuoRec's supervised
+        positive: ('same_target',), next-item batches only: the inputs in front of another occurrence of the row's target.
+        objective 'cloze' (the views are cut from the batch's UNMASKED windows) or 'next_item'; None: 'next_item' for a batch with
+        'row_offsets'.  A view is a pure function of (seed, view, window); the training generators' per-epoch seed is
+        rand64_host(seed, epoch).  contrastive_loss(inputs, inputs_b={name: view['items'], ...}, n_real_tokens_b=view['n_real_tokens'])
+        takes a view; 'target' is its same_target=.
+        The batch's windows are read from batch['win_idx'] on the device; the host count needs them on the host: the batches this
+        class builds remember them, for any other batch pass win_idx (host integers)."""
+        self._need_device()
+        if objective is None:
+            objective = 'next_item' if 'row_offsets' in batch else 'cloze'
+        if objective not in self.VIEW_OBJECTIVES:
+            raise ValueError("DeviceCloze: objective %r ('cloze' or 'next_item')" % (objective,))
+        row_dev = batch['win_idx']
+        if win_idx is None:
+            train, win_idx = getattr(row_dev, '_host_rows', (True, None))
+            if win_idx is None:
+                raise ValueError("DeviceCloze.views: batch['win_idx'] was not built by this class; pass win_idx (host integers)")
+            if not train:
+                raise ValueError('DeviceCloze.views: an evaluation batch; views are built of training rows')
+        win = np.asarray(win_idx, dtype=np.int64).reshape(-1)
+        B, W = batch['items'].shape
+        if len(win) != B or row_dev.shape[0] != B:
+            raise ValueError('DeviceCloze.views: %d window indices for a batch of %d rows' % (len(win), B))
+        n_items = self.view_lengths(win, seed, ops, n_views, objective, W, crop_ratio, mask_ratio, reorder_ratio)
+        view_ops = (ops,) if isinstance(ops, str) else tuple(ops)
+        index = None
+        if 'same_target' in view_ops:
+            self.target_index()
+            index = self._tgt_index[1]
+        tab = self.windows_dev
+        items, tok, n_out, op, target, self_count = _ops.augment_views(
+            self.items_dev, self.offsets_dev, tab[0], tab[1], tab[2], row_dev, W, self.VIEW_OBJECTIVES[objective], view_ops, seed,
+            n_views=n_views, holdout=self.holdout, max_len=self.max_len, crop_ratio=crop_ratio, mask_ratio=mask_ratio,
+            reorder_ratio=reorder_ratio, target_index=index, V=self.V)
+        out = []
+        for v in range(int(n_views)):
+            view = {'items': items[v], 'n_items': n_out[v], 'op': op[v], 'target': target[v], 'src_tok': tok[v],
+                    'n_real_tokens': int(n_items[v].sum()) + 3 * B, 'self_count': self_count}
+            if self.features:
+                view['features'] = self._view_features(items[v], tok[v])
+            out.append(view)
+        return out
+
+    def _view_features(self, items, src_tok):
+        """{name: (B, W) int64 ids} of one view, gathered in torch through src_tok (the CSR index of every position's token, -1 at
+        pad): per 'event' values[src_tok], per 'item' table[items[src_tok]]; id = value + 10, pad 0, [MASK] where the item row has
+        it unless the feature keeps its value there"""
+        real = src_tok >= 0
+        at = src_tok.clamp(min=0)
+        out = {}
+        for name, (values, per, on_mask) in zip(self.features, self._feature_sources):
+            src = values[at] if per == 'event' else values[self.items_dev[at].long()]
+            ids = torch.where(real, src.to(torch.int64) + 10, torch.zeros_like(src_tok))
+            if on_mask == 'mask':
+                ids = torch.where(items == 1, torch.ones_like(ids), ids)
+            out[name] = ids
+        return out
 
     # ---- filtered evaluation ---------------------------------------------------------------------------------------------------
     def history(self, seq_idx_dev, split='test', width=None):

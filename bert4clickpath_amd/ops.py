@@ -2255,6 +2255,112 @@ def batch_features_row_host(seq, seq_off, W, layout, src, per, on_mask, items_in
     return out, int(geom[0]), int(geom[1])
 
 
+# ---- contrastive views of a device-built batch (include/b4c_aug.h): crop, mask, reorder, the same-target row ----
+AUG_OPS = {'crop': L.AUG_CROP, 'mask': L.AUG_MASK, 'reorder': L.AUG_REORDER, 'same_target': L.AUG_SAME_TARGET}      # name -> op bit
+AUG_LAYOUTS = (FEAT_CLOZE, FEAT_NEXT_TRAIN)
+
+
+def _augment_args(who, W, layout, holdout, max_len, n_views, view_ops, seed, crop_ratio, mask_ratio, reorder_ratio):
+    """the checks augment_views and augment_row_host share -> (W, layout, holdout, max_len, n_views, ops_mask, the three ratios)"""
+    layout, n_views = int(layout), int(n_views)
+    if layout not in AUG_LAYOUTS:
+        raise B4CError('%s: layout %d (FEAT_CLOZE = 0 or FEAT_NEXT_TRAIN = 1; views of evaluation rows are not built)' % (who, layout))
+    W = _batch_width(who, W)
+    holdout, max_len = _holdout_args(who, holdout, max_len, None if layout == FEAT_CLOZE else 0, False)
+    if not 1 <= n_views <= L.AUG_MAX_VIEWS:
+        raise B4CError('%s: n_views = %d (1 .. %d)' % (who, n_views, L.AUG_MAX_VIEWS))
+    view_ops = (view_ops,) if isinstance(view_ops, str) else tuple(view_ops)
+    if not view_ops or any(o not in AUG_OPS for o in view_ops):
+        raise B4CError('%s: ops %r (one or more of %s)' % (who, view_ops, ', '.join(repr(o) for o in AUG_OPS)))
+    mask = 0
+    for o in view_ops:
+        mask |= AUG_OPS[o]
+    if mask & L.AUG_SAME_TARGET and layout != FEAT_NEXT_TRAIN:
+        raise B4CError("%s: 'same_target' needs the next-item layout (a Cloze row has no target)" % who)
+    crop_ratio, mask_ratio, reorder_ratio = float(crop_ratio), float(mask_ratio), float(reorder_ratio)
+    if not 0.0 < crop_ratio <= 1.0 or not 0.0 <= mask_ratio <= 1.0 or not 0.0 <= reorder_ratio <= 1.0:
+        raise B4CError('%s: crop_ratio = %g (0 < . <= 1), mask_ratio = %g, reorder_ratio = %g (0 <= . <= 1)'
+                       % (who, crop_ratio, mask_ratio, reorder_ratio))
+    if not 0 <= int(seed) < (1 << 64):
+        raise B4CError('%s: seed %d (0 .. 2^64)' % (who, seed))
+    return W, layout, holdout, max_len, n_views, mask, crop_ratio, mask_ratio, reorder_ratio
+
+
+def augment_views(items, offsets, win_seq, win_start, win_len, row_win, W, layout, view_ops, seed, n_views=2, holdout=1, max_len=None,
+                  crop_ratio=0.6, mask_ratio=0.3, reorder_ratio=0.6, target_index=None, V=0):
+    """-> (items_out int64 [n_views, B, W], src_tok int64 [n_views, B, W], n_items, op, target int32 [n_views, B], self_count int32
+    [1]) (b4c_augment_views, include/b4c_aug.h): n_views contrastive views of the batch rows row_win (windows of the device table)
+    whose item rows cloze_batch_windows (layout FEAT_CLOZE) or next_item_batch in TRAIN mode (FEAT_NEXT_TRAIN, the same holdout)
+    built.  Per (row, view) one of view_ops is drawn -- 'crop': a contiguous slice of crop_ratio of the row; 'mask': mask_ratio of
+    its positions become [MASK]; 'reorder': a span of reorder_ratio of the row is shuffled; 'same_target' (next-item only): the
+    items in front of another occurrence of the row's target item, of any sequence, the most recent min(W, max_len) of them -- the
+    row itself where there is none (self_count counts those).  target_index = (tgt_first int64 [V + 1], tgt_tok int64 [n],
+    tgt_seq int32 [n]) on the device, with V: 'same_target' needs it.  src_tok: the CSR index of every output position's token, -1
+    at pad; op: the drawn op's bit (ops.AUG_OPS); target: the row's target item (next-item), -1 for Cloze rows.  A row is a pure
+    function of (seed, view, window).  Stream-ordered, nothing is read back; rows and index are not checked against the data set."""
+    who = 'augment_views'
+    items, offsets = _csr_pair(who, items, offsets)
+    W, layout, holdout, max_len, n_views, mask, crop_ratio, mask_ratio, reorder_ratio = _augment_args(
+        who, W, layout, holdout, max_len, n_views, view_ops, seed, crop_ratio, mask_ratio, reorder_ratio)
+    win_seq, win_start, win_len = _window_table(who, win_seq, win_start, win_len)
+    row_win = _row_index(who, 'row_win', row_win, 'window indices')
+    B = row_win.shape[0]
+    idx = (None, None, None)
+    if mask & L.AUG_SAME_TARGET:
+        V = int(V)
+        ok = target_index is not None and len(target_index) == 3 and all(isinstance(t, torch.Tensor) and t.dim() == 1 for t in target_index)
+        if not ok or V < 1 or target_index[0].dtype != torch.int64 or target_index[0].shape[0] != V + 1 or target_index[1].dtype != torch.int64 \
+                or target_index[2].dtype != torch.int32 or target_index[1].shape != target_index[2].shape:
+            raise B4CError("%s: 'same_target' needs target_index = (tgt_first int64 [V + 1], tgt_tok int64 [n], tgt_seq int32 [n]) and V > 0"
+                           % who)
+        idx = tuple(t.contiguous() for t in target_index)
+    _cuda(items, offsets, win_seq, win_start, win_len, row_win, *idx)
+    dev = items.device
+    out = torch.empty(n_views, B, W, dtype=torch.int64, device=dev)
+    tok = torch.empty(n_views, B, W, dtype=torch.int64, device=dev)
+    n_out = torch.empty(n_views, B, dtype=torch.int32, device=dev)
+    op = torch.empty(n_views, B, dtype=torch.int32, device=dev)
+    target = torch.empty(n_views, B, dtype=torch.int32, device=dev)
+    self_count = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return out, tok, n_out, op, target, self_count
+    with _record(who, n_views * B * (W * 20 + 40)):
+        L.check(L.lib().b4c_augment_views(_p(items), _p(offsets), _p(win_seq), _p(win_start), _p(win_len), _p(row_win), B, W, layout, holdout,
+                                          max_len, n_views, mask, crop_ratio, mask_ratio, reorder_ratio, int(seed), _p(idx[0]), _p(idx[1]),
+                                          _p(idx[2]), V if mask & L.AUG_SAME_TARGET else 0, _p(out), W, _p(tok), W, _p(n_out), _p(op),
+                                          _p(target), _p(self_count), _st()), who)
+    return out, tok, n_out, op, target, self_count
+
+
+def augment_row_host(items, offsets, g, W, layout, view_ops, seed, view=0, a=0, L=0, holdout=1, max_len=None, crop_ratio=0.6,
+                     mask_ratio=0.3, reorder_ratio=0.6, target_index=None, V=0):
+    """-> dict(items int64 [W], src_tok int64 [W], n_items, op, target, self) in numpy and ints (b4c_augment_row: augment_views' rule
+    for ONE row and ONE view evaluated on the host, no device work).  items / offsets: the whole CSR pair as host arrays; (g, a, L):
+    the window, g < 0: an empty row; target_index: host arrays."""
+    import numpy as np
+    from . import _lib              # (the argument L, the header's name, hides this module's alias)
+    who = 'augment_row'
+    W, layout, holdout, max_len, _, mask, crop_ratio, mask_ratio, reorder_ratio = _augment_args(
+        who, W, layout, holdout, max_len, 1, view_ops, seed, crop_ratio, mask_ratio, reorder_ratio)
+    items = np.ascontiguousarray(items, dtype=np.int32).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    idx = [None, None, None]
+    if mask & _lib.AUG_SAME_TARGET:
+        if target_index is None or len(target_index) != 3 or int(V) < 1:
+            raise B4CError("%s: 'same_target' needs target_index = (tgt_first, tgt_tok, tgt_seq) and V > 0" % who)
+        idx = [np.ascontiguousarray(t, dtype=dt).reshape(-1) for t, dt in zip(target_index, (np.int64, np.int64, np.int32))]
+        if len(idx[0]) != int(V) + 1 or len(idx[1]) != len(idx[2]):
+            raise B4CError('%s: tgt_first holds %d entries for V = %d; tgt_tok %d, tgt_seq %d' % (who, len(idx[0]), V, len(idx[1]), len(idx[2])))
+    out, tok = np.empty(W, dtype=np.int64), np.empty(W, dtype=np.int64)
+    head = (ctypes.c_int32 * 4)()
+    ptr = lambda x: None if x is None or not len(x) else x.ctypes.data
+    _lib.check(_lib.lib().b4c_augment_row(items.ctypes.data, offsets.ctypes.data, len(offsets) - 1, int(g), int(a), int(L), W, layout, holdout,
+                                          max_len, int(view), mask, crop_ratio, mask_ratio, reorder_ratio, int(seed), ptr(idx[0]), ptr(idx[1]),
+                                          ptr(idx[2]), int(V) if mask & _lib.AUG_SAME_TARGET else 0, out.ctypes.data, tok.ctypes.data,
+                                          ctypes.addressof(head)), who)
+    return {'items': out, 'src_tok': tok, 'n_items': int(head[0]), 'op': int(head[1]), 'target': int(head[2]), 'self': int(head[3])}
+
+
 def adam_step_(p, g, m, v, lr_t, beta1, beta2, eps, grad_mul=1.0, coef=None, decay=None, blocks=None):
     """Dense Adam over a flat fp32 range (b4c_adam_step).  coef (device fp32 scalar of grad_clip_coef_): the gradient is scaled by
     grad_mul * coef[0] (b4c_adam_step_clipped).  decay: decoupled weight decay -- the elements of the 64-element blocks flagged in
@@ -2349,13 +2455,17 @@ def rand64_host(seed, ctr):
 
 def mulhi64_host(x, v):
     """Host restatement of the sampler's mulhi64 (csrc/candidates.hip): the high 64 bits of the 128-bit product of uint64 x
-    (array) and 0 <= v < 2^64, exact (32-bit halves)."""
+    (array) and 0 <= v < 2^64 (an integer, or an array that broadcasts against x), exact (32-bit halves)."""
     import numpy as np
     M = np.uint64(0xFFFFFFFF)
     s32 = np.uint64(32)
     x = np.asarray(x, dtype=np.uint64)
-    v = int(v)
-    vl, vh = np.uint64(v & 0xFFFFFFFF), np.uint64(v >> 32)
+    if isinstance(v, np.ndarray):
+        v = v.astype(np.uint64)
+        vl, vh = v & M, v >> s32
+    else:
+        v = int(v)
+        vl, vh = np.uint64(v & 0xFFFFFFFF), np.uint64(v >> 32)
     xl, xh = x & M, x >> s32
     t = xl * vl
     m1 = xh * vl + (t >> s32)

@@ -99,6 +99,13 @@ def add_contrastive_arguments(ap):
                     help='LAM > 0 adds LAM * model.contrastive_loss to the training loss: in-batch InfoNCE between two dropout views of '
                          'every sequence of the batch, read at its last item (the auxiliary loss of DuoRec / CL4SRec; needs --dropout > '
                          '0; two more encoder passes per step).  With every objective and --train_loss')
+    ap.add_argument('--contrastive_views', default='dropout', metavar='dropout|crop,mask,reorder|same_target',
+                    help="with --contrastive_weight: where the two views come from.  'dropout' (default): two dropout passes over the "
+                         "batch's inputs (needs --dropout > 0).  A comma list of crop, mask, reorder (CL4SRec): two augmented views of "
+                         "every row, one operator drawn per row and view.  'same_target' (DuoRec, --objective next_item): the batch's "
+                         "inputs against the inputs in front of another occurrence of each row's target item, rows with the same target "
+                         "not each other's negatives.  The last two are built on the device (DeviceCloze.views: --device_batches), "
+                         "encoded padding-free, and work at --dropout 0")
     ap.add_argument('--contrastive_temperature', type=float, default=1.0, help='with --contrastive_weight: the temperature')
     ap.add_argument('--contrastive_sim', default='dot', choices=['dot', 'cos'], help='with --contrastive_weight: dot product or cosine')
     ap.add_argument('--contrastive_same_target', action='store_true',
@@ -108,8 +115,17 @@ def add_contrastive_arguments(ap):
 def check_contrastive_arguments(ap, a):
     if a.contrastive_weight < 0 or a.contrastive_temperature <= 0:
         ap.error('--contrastive_weight must be >= 0 and --contrastive_temperature > 0')
-    if a.contrastive_weight > 0 and a.dropout <= 0:
-        ap.error('--contrastive_weight takes its two views from dropout: it needs --dropout > 0')
+    a.contrastive_ops = None if a.contrastive_views == 'dropout' else tuple(a.contrastive_views.split(','))
+    if a.contrastive_ops is None:
+        if a.contrastive_weight > 0 and a.dropout <= 0:
+            ap.error('--contrastive_weight takes its two views from dropout: it needs --dropout > 0 (or --contrastive_views crop,mask,reorder)')
+        return
+    if a.contrastive_ops != ('same_target',) and not set(a.contrastive_ops) <= {'crop', 'mask', 'reorder'}:
+        ap.error("--contrastive_views: 'dropout', 'same_target', or a comma list of crop, mask, reorder")
+    if not getattr(a, 'device_batches', False) and getattr(a, 'objective', 'cloze') != 'next_item':
+        ap.error('--contrastive_views %s builds its views on the device: it needs --device_batches' % a.contrastive_views)
+    if a.contrastive_ops == ('same_target',) and getattr(a, 'objective', 'cloze') != 'next_item':
+        ap.error('--contrastive_views same_target needs --objective next_item (a Cloze row has no target)')
 
 
 def last_targets(labels_padded=None, labels=None, row_offsets=None):
@@ -125,10 +141,22 @@ def last_targets(labels_padded=None, labels=None, row_offsets=None):
     return torch.where(off[1:] > off[:-1], labels.long()[(off[1:] - 1).clamp(min=0, max=labels.shape[0] - 1)], torch.full_like(off[1:], -1))
 
 
-def contrastive_term(model, a, inputs, same_target=None, **kw):
-    """--contrastive_weight times the in-batch contrastive loss of two dropout views of `inputs` (0.0 without the option)"""
+def contrastive_term(model, a, inputs, same_target=None, dev_data=None, batch=None, view_seed=0, **kw):
+    """--contrastive_weight times the in-batch contrastive loss of two views of the batch (0.0 without the option): two dropout
+    passes over `inputs`, or (--contrastive_views) views of `batch` that dev_data builds on the device"""
     if a.contrastive_weight <= 0:
         return 0.0
+    if a.contrastive_ops == ('same_target',):        # DuoRec's supervised positive beside the batch's own inputs
+        (view,) = dev_data.views(batch, view_seed, ops='same_target', n_views=1)
+        return a.contrastive_weight * model.contrastive_loss(inputs, dev_data.inputs(view, 'asin'), temperature=a.contrastive_temperature,
+                                                             similarity=a.contrastive_sim, same_target=view['target'],
+                                                             n_real_tokens_b=view['n_real_tokens'], **kw)
+    if a.contrastive_ops is not None:                # CL4SRec: two augmented views
+        one, two = dev_data.views(batch, view_seed, ops=a.contrastive_ops, n_views=2)
+        return a.contrastive_weight * model.contrastive_loss(dev_data.inputs(one, 'asin'), dev_data.inputs(two, 'asin'),
+                                                             temperature=a.contrastive_temperature, similarity=a.contrastive_sim,
+                                                             same_target=same_target if a.contrastive_same_target else None,
+                                                             n_real_tokens=one['n_real_tokens'], n_real_tokens_b=two['n_real_tokens'])
     return a.contrastive_weight * model.contrastive_loss(inputs, temperature=a.contrastive_temperature, similarity=a.contrastive_sim,
                                                          same_target=same_target if a.contrastive_same_target else None, **kw)
 
@@ -272,20 +300,24 @@ def main():
         dev_data = DeviceCloze.from_npz(a.data, **protocol_kw)
     next_item = a.objective == 'next_item'
     sampling = train_sampling(dev_data, a)
+    per_epoch = max(dev_data.n_windows // a.batch, 1) if dev_data is not None else 1
     for step, b in enumerate(next_item_train_batches(dev_data, a, a.steps, sampling['item_cdf']) if next_item
                              else (dev_data or data).train_batches(a.batch, a.seed, a.steps)):
         opt.zero_grad()
+        views = {}
+        if a.contrastive_weight > 0 and a.contrastive_ops is not None:      # the views' seed of the epoch, as the builders' own
+            views = dict(dev_data=dev_data, batch=b, view_seed=int(ops.rand64_host(a.seed, step // per_epoch)))
         if next_item:                 # unmasked rows, every position's target and its negatives: all built on the device
             loss = next_item_training_loss(model, a, b, sampling['logq'])
             if a.contrastive_weight > 0:
                 loss = loss + contrastive_term(model, a, model._next_item_inputs(b), last_targets(labels=b['labels'], row_offsets=b['row_offsets']),
-                                               n_real_tokens=b['n_real_tokens'])
+                                               n_real_tokens=b['n_real_tokens'], **views)
         elif dev_data is not None:      # items and padded labels are on the device already; nothing is read back
             loss = training_loss(model, a, dev_data.inputs(b, 'asin'), b['labels_padded'], **sampling,
                                  max_masked_per_row=b['labels_padded'].shape[1], n_real_tokens=b['n_real_tokens'])
             if a.contrastive_weight > 0:
                 loss = loss + contrastive_term(model, a, dev_data.inputs(b, 'asin'), last_targets(labels_padded=b['labels_padded']),
-                                               n_real_tokens=b['n_real_tokens'])
+                                               n_real_tokens=b['n_real_tokens'], **views)
         else:
             ids = torch.from_numpy(b['ids'])
             items = ids[:, 2:-1].contiguous().cuda()
@@ -364,7 +396,7 @@ def main():
         out['objective'] = a.objective
         out['popularity_buckets'] = a.popularity_buckets
     if a.contrastive_weight > 0:
-        out['contrastive'] = dict(weight=a.contrastive_weight, temperature=a.contrastive_temperature, similarity=a.contrastive_sim,
+        out['contrastive'] = dict(weight=a.contrastive_weight, views=a.contrastive_views, temperature=a.contrastive_temperature, similarity=a.contrastive_sim,
                                   same_target=a.contrastive_same_target)
     if a.holdout == 2:               # the split a model is selected on; the test numbers above are read once, at the end
         out['valid'] = evaluate('valid')
