@@ -1,4 +1,4 @@
-"""ctypes binding of libb4c_hip.so (include/b4c.h and the extension headers of EXT_HEADER_PATHS and AUG_HEADER_PATHS).  There is no CPU fallback: if the
+"""ctypes binding of libb4c_hip.so (include/b4c.h and the extension headers of EXT_HEADER_PATHS, AUG_HEADER_PATHS and LONG_HEADER_PATHS).  There is no CPU fallback: if the
 library is missing, or a call fails, this raises -- the product path is the HIP path."""
 import ctypes
 import os
@@ -15,6 +15,9 @@ _EXT_VERSIONS = {'b4c_nce.h': ('B4C_NCE_VERSION', 'b4c_nce_version')}
 # describes the first list alone): the contrastive views.
 AUG_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_aug.h'),)
 _AUG_VERSIONS = {'b4c_aug.h': ('B4C_AUG_VERSION', 'b4c_aug_version')}
+# A third list, bound after the second: the streamed attention kernels for sequences past the resident ones.
+LONG_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_long.h'),)
+_LONG_VERSIONS = {'b4c_attn_long.h': ('B4C_ATTN_LONG_VERSION', 'b4c_attn_long_version')}
 
 
 class B4CError(RuntimeError):
@@ -148,6 +151,11 @@ for _path in AUG_HEADER_PATHS:
 AUG_VERSION, AUG_MAX_VIEWS = _CA['B4C_AUG_VERSION'], _CA['B4C_AUG_MAX_VIEWS']      # include/b4c_aug.h
 AUG_CROP, AUG_MASK, AUG_REORDER, AUG_SAME_TARGET = _CA['B4C_AUG_CROP'], _CA['B4C_AUG_MASK'], _CA['B4C_AUG_REORDER'], _CA['B4C_AUG_SAME_TARGET']
 
+_CL = {}
+for _path in LONG_HEADER_PATHS:
+    _CL.update(header_constants(_header_text(_path)))
+ATTN_LONG_VERSION, ATTN_LONG_MAX_S = _CL['B4C_ATTN_LONG_VERSION'], _CL['B4C_ATTN_LONG_MAX_S']      # include/b4c_attn_long.h
+
 _lib = None
 
 
@@ -217,7 +225,8 @@ def lib():
         # the extension tables, after the main one and in this order: the same refusals (a name declared twice, a name the library
         # lacks, a version that is not the header's)
         ext = _bind_extension(L, have, EXT_HEADER_PATHS, _EXT_VERSIONS, _CX, sig)
-        _bind_extension(L, have, AUG_HEADER_PATHS, _AUG_VERSIONS, _CA, {**sig, **ext})
+        aug = _bind_extension(L, have, AUG_HEADER_PATHS, _AUG_VERSIONS, _CA, {**sig, **ext})
+        _bind_extension(L, have, LONG_HEADER_PATHS, _LONG_VERSIONS, _CL, {**sig, **ext, **aug})
         _lib = L
     return _lib
 

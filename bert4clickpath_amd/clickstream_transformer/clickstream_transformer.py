@@ -254,7 +254,8 @@ class ClickstreamTransformer(nn.Module):
                 for n in first_in) + len(first_in) + 2
         ok = self.transformer.packed_supported(S)
         if packed is True and not ok:
-            raise B4CError('packed=True needs bf16 compute, head depth 32 / 64 and an encoder length <= 512')
+            raise B4CError('packed=True needs bf16 compute, head depth 32 / 64 and an encoder length <= %s'
+                           % ('%d' % ops.ATTN_LONG_MAX_S if ops.long_attn else '512'))
         return ok
 
     def _match_positions(self, ids_first, raw_first, cap=None, poison=None):

@@ -596,9 +596,10 @@ class Transformer(nn.Module):
         return self.position_embedding.weight if self.position_encoding == 'learned' else self.pos_encoding
 
     def packed_supported(self, S):
-        """The padding-free layout runs on the bf16 MFMA attention kernels only (head depth 32 / 64, S <= 512)."""
+        """The padding-free layout runs on the bf16 MFMA attention kernels only (head depth 32 / 64, S <= 512; with ops.long_attn
+        on, S <= 2048: the streamed kernels)."""
         dh = self.d_model // self.num_attention_heads
-        return self.compute_dtype == torch.bfloat16 and dh in (32, 64) and S <= 512
+        return self.compute_dtype == torch.bfloat16 and dh in (32, 64) and S <= (ops.ATTN_LONG_MAX_S if ops.long_attn else 512)
 
     def forward(self, inputs, training=None, mask=None, return_key_pad=False, packed=None, rows=None):
         """inputs: dict feature -> (B,S) int64 ids (first feature defines the padding mask).
@@ -616,7 +617,7 @@ class Transformer(nn.Module):
         rate = self.dropout_rate if training else 0.0
         seed = dropout_seeds.next() if training else 0
         if packed is not None and not self.packed_supported(S):
-            raise B4CError('packed layout needs bf16, head depth 32 / 64 and S <= 512')
+            raise B4CError('packed layout needs bf16, head depth 32 / 64 and S <= %s' % ('%d' % ops.ATTN_LONG_MAX_S if ops.long_attn else '512'))
         # the positional table is a differentiable input when it is the learned parameter (its gradient: b4c_pos_table_bwd); the
         # sinusoidal EmbedFn call is the reference's, EmbedLNFn the paper's input stage
         args = (self.scale, rate, seed, self.compute_dtype, packed, self.feature_combine, len(ids), *ids, *tables)

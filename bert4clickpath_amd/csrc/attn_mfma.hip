@@ -862,3 +862,22 @@ int b4c_attn_bwd_mfma(const void *qkv, int ld_qkv, const uint8_t *key_pad, const
     blocks(shm, 1, nullptr);
     return b4c_check_launch("attn_bwd_mfma");
 }
+
+// The key-block walk alone, for any S <= 2048 (attn_long.hip: b4c_attn_long_bwd, which has checked the arguments): one launch,
+// ceil(S / 256) <= 8 blocks, the first in mode 1, the last in mode 3 and the ones between in mode 2 (S <= 256: one block, mode 0,
+// dq_acc untouched).  dq_acc: fp32 [rows][H * dh].  The same kernel instantiations as the S <= 512 walk above.
+int b4c_attn_bwd_blocks(const void *qkv, int ld_qkv, const uint8_t *key_pad, const void *o, int ld_o, const void *d_o, int ld_do,
+                        const float *lse, void *dqkv, int ld_dqkv, int B, int S, int H, int dh, float *dq_acc, const int32_t *cu,
+                        float rate, uint64_t seed, bool causal, hipStream_t st) {
+    const int nblk = (S + 255) / 256;
+    const int kpad = nblk > 1 ? 256 : (S + 31) / 32 * 32;         // keys of the largest block
+    const size_t kstr = dh * 2 + 16, tstr = kpad * 2 + 16;
+    const size_t shm = 2 * kpad * kstr + 2 * (2 * 32 * kstr + 256) + 32 * tstr;
+    const float scale = 1.0f / sqrtf((float)dh);
+    const bool ok = b4c_by_int<32, 64>(dh, [&](auto DH) { b4c_by_bool(rate != 0.f, [&](auto DR) { b4c_by_bool(causal, [&](auto CA) {
+        b4c_allow_lds(attn_bwd_mfma_kernel<DH(), DR(), CA()>, shm);
+        attn_bwd_mfma_kernel<DH(), DR(), CA()><<<B * H, 512, shm, st>>>((const bf16_t *)qkv, ld_qkv, key_pad, (const bf16_t *)o, ld_o, (const bf16_t *)d_o, ld_do, lse, (bf16_t *)dqkv, ld_dqkv, S, H, scale, nblk, dq_acc, cu, rate, seed);
+    }); }); });
+    if (!ok) return B4C_EUNSUPPORTED;
+    return b4c_check_launch("attn_bwd_mfma (key blocks)");
+}

@@ -43,7 +43,7 @@ __device__ __forceinline__ bf16x8 frag_tr(const char *p, int second_off) { retur
 // exactly such four keys: each lane hashes the queries of the registers (r & 3) + 4 tq, tq = 0..3, and the quad exchanges the
 // bits (DPP quad broadcast) -- four hashes per lane per tile, as in the forward, where the four keys are four registers of one
 // lane.  The hash counter b4c_attn_ctr(row, k0, S_arg) is split into the workgroup-uniform base = attn_ctr_base(b*H + h, S_arg)
-// and a 32-bit lane part q * (S4 / 4) + k0 / 4 (q < 512, S4 / 4 <= 128).  qpos(i) = position of the query of tile row i inside its
+// and a 32-bit lane part q * (S4 / 4) + k0 / 4 (q < 2048, S4 / 4 <= 512 with the key-block walk of attn_long.hip: below 2^21).  qpos(i) = position of the query of tile row i inside its
 // sequence, k_tile = first key of the tile.  EXEC must be full.
 template <typename QPos>
 __device__ __forceinline__ uint32_t keep_tile_bwd(uint64_t seed, uint64_t base, int S_arg, QPos qpos, int k_tile, uint32_t thr, int r, int hf) {

@@ -992,6 +992,8 @@ def attn_fwd(qkv, key_pad, B, S, H, dh, cu=None, rate=0.0, seed=0, causal=False)
     Always b4c_attn_fwd_ex: the layout, the rate and the flags select the launch, and cu = None, rate = 0, flags = 0 is the
     launch of b4c_attn_fwd."""
     rate = _attn_rate(rate)
+    if long_attn and S > 512 and attn_long_supported(qkv.dtype, S, dh):
+        return attn_long_fwd(qkv, key_pad, B, S, H, dh, cu=cu, rate=rate, seed=seed, causal=causal)
     d = H * dh
     T_tok = qkv.shape[0]
     o = torch.empty(T_tok, d, dtype=qkv.dtype, device=qkv.device)
@@ -1006,6 +1008,8 @@ def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None, rate=0.
     """actx: the ArenaContext of the training step in flight (its background work gets a launch opportunity behind this kernel)
     rate, seed, causal: those of the forward (attn_fwd); o is the forward's output, dropped probabilities included."""
     rate = _attn_rate(rate)
+    if long_attn and S > 512 and attn_long_supported(qkv.dtype, S, dh):
+        return attn_long_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=cu, actx=actx, rate=rate, seed=seed, causal=causal)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
     need = L.lib().b4c_attn_bwd_workspace_bytes(B, S, H, dh, dt_code(qkv.dtype))     # > 0 only for bf16 256 < S <= 512
@@ -1016,6 +1020,50 @@ def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None, rate=0.
                                         _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), need,
                                         dt_code(qkv.dtype), _st(), rate, seed, ATTN_CAUSAL if causal else 0), 'attn_bwd_ex')
     _background_kick(actx)      # the next piece of the vocabulary head's dW sweep starts when this kernel has left the CUs
+    return dqkv
+
+
+# Sequences past the resident bf16 MFMA kernels (512 < S <= 2048): the streamed kernels of include/b4c_attn_long.h instead of the
+# fp32-math row kernels (dense layout) or a refusal (packed layout).  Off (B4C_ATTN_LONG=1 switches it on): with it off every launch,
+# message and result is what it was without these kernels.
+long_attn = os.environ.get('B4C_ATTN_LONG', '0') == '1'
+ATTN_LONG_MAX_S = L.ATTN_LONG_MAX_S
+
+
+def attn_long_supported(dtype, S, dh):
+    """what b4c_attn_long_fwd / _bwd take: bf16, head depth 32 / 64, 1 <= S <= 2048 (the routing of attn_fwd / attn_bwd adds
+    S > 512 and the switch long_attn)"""
+    return dtype == torch.bfloat16 and dh in (32, 64) and 1 <= S <= ATTN_LONG_MAX_S
+
+
+def attn_long_fwd(qkv, key_pad, B, S, H, dh, cu=None, rate=0.0, seed=0, causal=False):
+    """attn_fwd on the streamed kernels (b4c_attn_long_fwd): same arguments, layouts, dropout masks and results (o, lse)"""
+    rate = _attn_rate(rate)
+    d = H * dh
+    T_tok = qkv.shape[0]
+    o = torch.empty(T_tok, d, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(B, H, S, dtype=torch.float32, device=qkv.device)
+    with _record('attn_fwd', T_tok * 4 * d * qkv.element_size(), 4 * _attn_pairs(T_tok, S, cu, causal) * d):
+        L.check(L.lib().b4c_attn_long_fwd(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), d, _p(lse), B, S, H, dh, _st(), rate, seed,
+                                          ATTN_CAUSAL if causal else 0), 'attn_long_fwd')
+    return o, lse
+
+
+def attn_long_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None, rate=0.0, seed=0, causal=False):
+    """attn_bwd on the key-block walk (b4c_attn_long_bwd); the fp32 dQ accumulator [rows, H dh] comes from _workspace"""
+    rate = _attn_rate(rate)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty_like(lse)
+    T_tok = qkv.shape[0]
+    need = L.lib().b4c_attn_long_bwd_workspace_bytes(T_tok, H, dh)
+    if need < 0:
+        raise B4CError('attn_long_bwd: head depth %d not in {32, 64}' % dh)
+    ws = _workspace('attn_long_bwd', qkv.device, need)
+    with _record('attn_bwd', T_tok * 8 * H * dh * qkv.element_size(), 10 * _attn_pairs(T_tok, S, cu, causal) * H * dh):
+        L.check(L.lib().b4c_attn_long_bwd(_p(qkv), qkv.stride(0), _p(key_pad), _p(cu), _p(o), o.stride(0), _p(d_o), d_o.stride(0),
+                                          _p(lse), _p(delta), _p(dqkv), dqkv.stride(0), B, S, H, dh, _p(ws), ws.numel(), _st(), rate, seed,
+                                          ATTN_CAUSAL if causal else 0), 'attn_long_bwd')
+    _background_kick(actx)
     return dqkv
 
 
