@@ -1,4 +1,4 @@
-"""ctypes binding of libb4c_hip.so (include/b4c.h and the extension headers of EXT_HEADER_PATHS, AUG_HEADER_PATHS and LONG_HEADER_PATHS).  There is no CPU fallback: if the
+"""ctypes binding of libb4c_hip.so (include/b4c.h).  There is no CPU fallback: if the
 library is missing, or a call fails, this raises -- the product path is the HIP path."""
 import ctypes
 import os
@@ -6,18 +6,7 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('B4C_LIB_PATH') or os.path.join(_HERE, 'libb4c_hip.so')     # override: A/B of two builds (scratch)
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')      # the main ABI (B4C_ABI_VERSION): signatures() describes it alone
-# Extension headers, same grammar, bound after the main table: a family added while b4c.h and its ABI version stay as they are.
-# Each carries its own version: (path, version constant, the function that returns it).
-EXT_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_nce.h'),)
-_EXT_VERSIONS = {'b4c_nce.h': ('B4C_NCE_VERSION', 'b4c_nce_version')}
-# A second list of extension headers with its own version table, bound after the first (extension_signatures() with its defaults
-# describes the first list alone): the contrastive views.
-AUG_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_aug.h'),)
-_AUG_VERSIONS = {'b4c_aug.h': ('B4C_AUG_VERSION', 'b4c_aug_version')}
-# A third list, bound after the second: the streamed attention kernels for sequences past the resident ones.
-LONG_HEADER_PATHS = (os.path.join(os.path.dirname(_HERE), 'include', 'b4c_attn_long.h'),)
-_LONG_VERSIONS = {'b4c_attn_long.h': ('B4C_ATTN_LONG_VERSION', 'b4c_attn_long_version')}
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'b4c.h')      # the whole ABI (B4C_ABI_VERSION): the one header, read when lib() binds
 
 
 class B4CError(RuntimeError):
@@ -106,20 +95,6 @@ def declared_symbols(header_path=HEADER_PATH):
     return sorted(signatures(header_path))
 
 
-def extension_signatures(header_paths=None, main=None):
-    """{name: (restype, [argtypes])} of every entry point the extension headers declare (include/b4c_nce.h), in one table.  A name
-    that two headers declare -- the main one (`main`: its table, default signatures()) included -- is refused as a duplicate inside
-    one header is."""
-    seen = dict(signatures() if main is None else main)
-    table = {}
-    for path in (EXT_HEADER_PATHS if header_paths is None else header_paths):
-        for name, sig in parse_header(_header_text(path)).items():
-            if name in seen:
-                raise B4CError('include/b4c.h declares %s twice: %r' % (name, '%s (again in %s)' % (name, os.path.basename(path))))
-            seen[name] = table[name] = sig
-    return table
-
-
 _C = header_constants(_header_text(HEADER_PATH))
 ABI_VERSION = _C['B4C_ABI_VERSION']       # b4c_abi_version() of the library must agree
 F32, BF16 = _C['B4C_F32'], _C['B4C_BF16']
@@ -139,50 +114,12 @@ NEXT_EXCL_NONE, NEXT_EXCL_HISTORY = _C['B4C_NEXT_EXCL_NONE'], _C['B4C_NEXT_EXCL_
 FEAT_EVENT, FEAT_ITEM = _C['B4C_FEAT_EVENT'], _C['B4C_FEAT_ITEM']        # source kinds of b4c_batch_features
 FEAT_MASKED, FEAT_KEPT = _C['B4C_FEAT_MASKED'], _C['B4C_FEAT_KEPT']      # what a [MASK] position of the item row does to a feature
 FEAT_CLOZE, FEAT_NEXT_TRAIN, FEAT_NEXT_EVAL = _C['B4C_FEAT_CLOZE'], _C['B4C_FEAT_NEXT_TRAIN'], _C['B4C_FEAT_NEXT_EVAL']      # row layouts
-
-_CX = {}
-for _path in EXT_HEADER_PATHS:
-    _CX.update(header_constants(_header_text(_path)))
-NCE_VERSION, NCE_COSINE, NCE_MAX_N = _CX['B4C_NCE_VERSION'], _CX['B4C_NCE_COSINE'], _CX['B4C_NCE_MAX_N']      # include/b4c_nce.h
-
-_CA = {}
-for _path in AUG_HEADER_PATHS:
-    _CA.update(header_constants(_header_text(_path)))
-AUG_VERSION, AUG_MAX_VIEWS = _CA['B4C_AUG_VERSION'], _CA['B4C_AUG_MAX_VIEWS']      # include/b4c_aug.h
-AUG_CROP, AUG_MASK, AUG_REORDER, AUG_SAME_TARGET = _CA['B4C_AUG_CROP'], _CA['B4C_AUG_MASK'], _CA['B4C_AUG_REORDER'], _CA['B4C_AUG_SAME_TARGET']
-
-_CL = {}
-for _path in LONG_HEADER_PATHS:
-    _CL.update(header_constants(_header_text(_path)))
-ATTN_LONG_VERSION, ATTN_LONG_MAX_S = _CL['B4C_ATTN_LONG_VERSION'], _CL['B4C_ATTN_LONG_MAX_S']      # include/b4c_attn_long.h
+NCE_COSINE, NCE_MAX_N = _C['B4C_NCE_COSINE'], _C['B4C_NCE_MAX_N']        # the in-batch contrastive loss (b4c_nce_fwd / _bwd)
+AUG_CROP, AUG_MASK, AUG_REORDER, AUG_SAME_TARGET = _C['B4C_AUG_CROP'], _C['B4C_AUG_MASK'], _C['B4C_AUG_REORDER'], _C['B4C_AUG_SAME_TARGET']
+AUG_MAX_VIEWS = _C['B4C_AUG_MAX_VIEWS']      # (the ops_mask bits and the view limit of b4c_augment_views)
+ATTN_LONG_MAX_S = _C['B4C_ATTN_LONG_MAX_S']      # longest sequence of b4c_attn_long_fwd / _bwd
 
 _lib = None
-
-
-def _bind_extension(L, have, paths, versions, consts, seen):
-    """bind the entry points of one list of extension headers after the tables `seen` ({name: signature}): the same refusals as for
-    the main table (a name declared twice, a name the library lacks) and a version that is not the header's -> the list's table"""
-    ext = extension_signatures(header_paths=paths, main=seen)
-    for path in paths:
-        const, getter = versions[os.path.basename(path)]
-        try:
-            fn = getattr(L, getter)
-        except AttributeError:
-            raise B4CError('%s (ABI %d) does not export %s; rebuild it (`make -C bert4clickpath_amd/csrc`)'
-                           % (LIB_PATH, have, getter)) from None
-        fn.restype, fn.argtypes = ctypes.c_int, []
-        if int(fn()) != consts[const]:
-            raise B4CError('%s (ABI %d) does not export %s = %d (it reports %d); rebuild it (`make -C bert4clickpath_amd/csrc`)'
-                           % (LIB_PATH, have, const, consts[const], int(fn())))
-    for name, (res, args) in ext.items():
-        try:
-            fn = getattr(L, name)
-        except AttributeError:
-            raise B4CError('%s (ABI %d) does not export %s; rebuild it (`make -C bert4clickpath_amd/csrc`)'
-                           % (LIB_PATH, have, name)) from None
-        fn.restype = res
-        fn.argtypes = args
-    return ext
 
 
 def lib():
@@ -202,7 +139,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        sig = signatures()
+        sig = signatures(HEADER_PATH)        # (the module's HEADER_PATH now, not the default bound when signatures was defined)
         # The argument lists of the header belong to ONE ABI version: a library that exports the same names with older lists would
         # take a device pointer for a stream and fault on the GPU.  Compare before anything is bound.
         try:
@@ -222,11 +159,6 @@ def lib():
                                % (LIB_PATH, have, name)) from None
             fn.restype = res
             fn.argtypes = args
-        # the extension tables, after the main one and in this order: the same refusals (a name declared twice, a name the library
-        # lacks, a version that is not the header's)
-        ext = _bind_extension(L, have, EXT_HEADER_PATHS, _EXT_VERSIONS, _CX, sig)
-        aug = _bind_extension(L, have, AUG_HEADER_PATHS, _AUG_VERSIONS, _CA, {**sig, **ext})
-        _bind_extension(L, have, LONG_HEADER_PATHS, _LONG_VERSIONS, _CL, {**sig, **ext, **aug})
         _lib = L
     return _lib
 

@@ -620,7 +620,7 @@ class ClickstreamTransformer(nn.Module):
         Loss.  z = cat(rows_a, rows_b) (2B rows), the positive of row i is the other view of its sequence, the negatives are every
         other row of the 2B; same_target ((B,) integer, negative: none; DuoRec): two sequences with the same target item are not
         each other's negatives.  s = z_i . z_j / temperature ('dot') or the rows' cosine / temperature ('cos'); mean over the 2B rows
-        of logsumexp over the keys - s at the positive.  One fused kernel pair (ops.InfoNCEFn, include/b4c_nce.h): the [2B, 2B]
+        of logsumexp over the keys - s at the positive.  One fused kernel pair (ops.InfoNCEFn, include/b4c.h): the [2B, 2B]
         scores never reach memory; d_model must be a multiple of 8, at most 128.
         Cost: two more encoder passes on top of the main loss's (one per view).  Under data parallelism the negatives are the rank's
         own batch: there is no all-gather.  No reference oracle (the reference trains with the Cloze loss alone); the float64

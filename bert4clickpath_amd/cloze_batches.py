@@ -23,7 +23,7 @@ per item (a category, a brand).  They are validated and uploaded once; every bat
 int64 ids} built from the item row in one launch (ops.batch_features, include/b4c.h), [MASK] where the item row has
 it unless the feature says on_mask='keep'.  inputs(batch, item_feature) is the dict the model's entry points take.
 
-views(batch, seed, ...) builds contrastive views of a training batch's rows on the device (ops.augment_views, include/b4c_aug.h):
+views(batch, seed, ...) builds contrastive views of a training batch's rows on the device (ops.augment_views, include/b4c.h):
 CL4SRec's item crop / mask / reorder and DuoRec's same-target row, each with the host-known n_real_tokens that lets
 model.contrastive_loss(..., inputs_b=, n_real_tokens_b=) encode the view padding-free."""
 import collections
@@ -422,7 +422,7 @@ class DeviceCloze:
             b['target_seq_idx'] = tgt_seq_dev[int(first[s]):int(first[e])]
             yield b
 
-    # ---- contrastive views of a training batch (include/b4c_aug.h) ---------------------------------------------------------------
+    # ---- contrastive views of a training batch (include/b4c.h) ---------------------------------------------------------------
     VIEW_OBJECTIVES = {'cloze': ops.FEAT_CLOZE, 'next_item': ops.FEAT_NEXT_TRAIN}
 
     def target_index(self):
@@ -464,7 +464,7 @@ class DeviceCloze:
     def view_lengths(self, win_idx, seed, ops=('crop', 'mask', 'reorder'), n_views=2, objective='next_item', width=None, crop_ratio=0.6,
                      mask_ratio=0.3, reorder_ratio=0.6):
         """host int64 [n_views, B]: the item count of every view views() builds of the windows win_idx at width W (None: the longest
-        source row) -- the rule of include/b4c_aug.h as far as the lengths need it (the op, then the length), evaluated with
+        source row) -- the rule of include/b4c.h as far as the lengths need it (the op, then the length), evaluated with
         ops.rand64_host and numpy from the window table, the offsets and the same-target index: no loop over rows, no device work."""
         who = 'DeviceCloze.view_lengths'
         if objective not in self.VIEW_OBJECTIVES:
@@ -506,7 +506,7 @@ class DeviceCloze:
 
     def views(self, batch, seed, ops=('crop', 'mask', 'reorder'), n_views=2, objective=None, crop_ratio=0.6, mask_ratio=0.3, reorder_ratio=0.6,
               win_idx=None):
-        """n_views contrastive views of a TRAIN batch's rows, built on the device in one launch (ops.augment_views, include/b4c_aug.h)
+        """n_views contrastive views of a TRAIN batch's rows, built on the device in one launch (ops.augment_views, include/b4c.h)
         -> a list of n_views dicts(items (B, W) int64 -- W the batch's own width --, n_items, op, target (B,) int32, src_tok (B, W)
         int64: device tensors; n_real_tokens: host int; features {name: (B, W) int64} when the data set has side features; self_count
         int32 [1], shared: the 'same_target' rows that had no partner).

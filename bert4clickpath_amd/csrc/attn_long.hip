@@ -1,4 +1,4 @@
-// bf16 MFMA attention for sequences past the resident kernels of attn_mfma.hip (include/b4c_attn_long.h): S <= 2048.
+// bf16 MFMA attention for sequences past the resident kernels of attn_mfma.hip (include/b4c.h): S <= 2048.
 //
 // forward : a 512-thread workgroup owns 256 queries of one (sequence, head) -- wave w the 32-query tile w of the block -- and
 //           streams the keys in blocks of 128 through a double-buffered K | V | mask image (2 x (2 x 128 x (2 dh + 16) + 512) B and
@@ -13,7 +13,6 @@
 #include <math.h>
 
 #include "mfma.h"
-#include "../../include/b4c_attn_long.h"
 
 #define ATL_KB 128     // keys per stage
 #define ATL_QB 256     // queries per workgroup
@@ -253,8 +252,6 @@ static int atl_check(const char *who, int ld_qkv, int ld_o, int B, int S, int H,
                 "%s: bad pitch (ld_qkv = %d, ld_o = %d)", who, ld_qkv, ld_o);
     return B4C_OK;
 }
-
-extern "C" int b4c_attn_long_version(void) { return B4C_ATTN_LONG_VERSION; }
 
 extern "C" int b4c_attn_long_fwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
                                  float *lse, int B, int S, int H, int dh, void *stream, float dropout_rate, uint64_t seed,

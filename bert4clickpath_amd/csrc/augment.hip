@@ -1,4 +1,4 @@
-// Contrastive views of a device-built batch (include/b4c_aug.h, whose comment is the definition): per (row, view) one of item
+// Contrastive views of a device-built batch (include/b4c.h, whose comment is the definition): per (row, view) one of item
 // crop, item mask, item reorder (CL4SRec) or the row of another sequence in front of the same target item (DuoRec).
 //
 // One 256-thread workgroup per (row, view), grid (B, n_views).  The row's geometry (batch_rows.h) and the view's plan -- the op, its
@@ -8,7 +8,6 @@
 // O(n^2) compares per row at most: integer work beside a training step of milliseconds; nothing here is tuned further.
 #include "batch_rows.h"
 #include "sampler.h"
-#include "../../include/b4c_aug.h"
 
 #define AUG_OPS (B4C_AUG_CROP | B4C_AUG_MASK | B4C_AUG_REORDER | B4C_AUG_SAME_TARGET)
 
@@ -164,8 +163,6 @@ __global__ void __launch_bounds__(ROW_THREADS) augment_views_kernel(
 }
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------
-extern "C" int b4c_aug_version(void) { return B4C_AUG_VERSION; }
-
 // what b4c_augment_views and b4c_augment_row check alike, before any pointer is looked at
 static int aug_check_args(const char *who, int B, int W, int layout, int holdout, int ld_items, int n_views, uint32_t ops_mask, float crop_ratio,
                           float mask_ratio, float reorder_ratio) {

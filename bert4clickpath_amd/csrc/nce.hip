@@ -1,4 +1,4 @@
-// In-batch contrastive loss (NT-Xent / InfoNCE over the rows of a batch): b4c_nce_fwd / b4c_nce_bwd of include/b4c_nce.h, whose
+// In-batch contrastive loss (NT-Xent / InfoNCE over the rows of a batch): b4c_nce_fwd / b4c_nce_bwd of include/b4c.h, whose
 // comment is the definition.  The [N, N] scores never reach memory.
 //
 // bf16: one matrix-core kernel per direction (nce_mfma_kernel).  A workgroup of 4 waves owns 32 query rows (query i = the lane's
@@ -16,7 +16,6 @@
 #include <math.h>
 
 #include "mfma.h"
-#include "../../include/b4c_nce.h"
 
 #define NCE_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #define NCE_NEG (-3.0e38f)          // "no key yet": finite, so that exp(m - m') never sees inf - inf
@@ -420,8 +419,6 @@ template <bool BWD> static void nce_launch(const NceArgs &a, int dtype, hipStrea
         nce_mfma_kernel<128, BWD><<<grid, 256, lds, st>>>(a);
     }
 }
-
-extern "C" int b4c_nce_version(void) { return B4C_NCE_VERSION; }
 
 extern "C" int b4c_nce_fwd(const void *z, int ld_z, int64_t N, int K, int dtype, const int32_t *pos, const int32_t *group, float inv_temp,
                            uint32_t flags, float *rnorm, float *lse, float *item_loss, void *stream) {

@@ -1023,7 +1023,7 @@ def attn_bwd(qkv, key_pad, o, d_o, lse, B, S, H, dh, cu=None, actx=None, rate=0.
     return dqkv
 
 
-# Sequences past the resident bf16 MFMA kernels (512 < S <= 2048): the streamed kernels of include/b4c_attn_long.h instead of the
+# Sequences past the resident bf16 MFMA kernels (512 < S <= 2048): the streamed kernels of include/b4c.h instead of the
 # fp32-math row kernels (dense layout) or a refusal (packed layout).  Off (B4C_ATTN_LONG=1 switches it on): with it off every launch,
 # message and result is what it was without these kernels.
 long_attn = os.environ.get('B4C_ATTN_LONG', '0') == '1'
@@ -1849,7 +1849,7 @@ def candidate_loss_bwd(h, table, cand, g, gscale, V, dtable, dbias, row_off=0):
     return dh
 
 
-# ---- in-batch contrastive loss (include/b4c_nce.h): NT-Xent / InfoNCE over the rows of a batch ----
+# ---- in-batch contrastive loss (include/b4c.h): NT-Xent / InfoNCE over the rows of a batch ----
 NCE_SIMILARITIES = ('dot', 'cos')
 
 
@@ -1882,7 +1882,7 @@ def _nce_args(who, z, pos, group, temperature, similarity):
 
 
 def nce_fwd(z, pos, group=None, temperature=1.0, similarity='dot'):
-    """-> (item_loss fp32 [N], lse fp32 [N], rnorm fp32 [N] or None) of the in-batch contrastive loss (b4c_nce_fwd, include/b4c_nce.h):
+    """-> (item_loss fp32 [N], lse fp32 [N], rnorm fp32 [N] or None) of the in-batch contrastive loss (b4c_nce_fwd, include/b4c.h):
     row i is a query when pos[i] names another row of the batch; its keys are that positive and every other query row, except (group
     given) rows of its own non-negative group; item_loss[i] = logsumexp over the keys of s_ij - s_{i, pos[i]}, s = z_i . z_j /
     temperature ('dot') or the cosine of the two rows / temperature ('cos': rnorm comes back, 1 / max(||z_i||, 1e-12)).  Other rows:
@@ -2303,7 +2303,7 @@ def batch_features_row_host(seq, seq_off, W, layout, src, per, on_mask, items_in
     return out, int(geom[0]), int(geom[1])
 
 
-# ---- contrastive views of a device-built batch (include/b4c_aug.h): crop, mask, reorder, the same-target row ----
+# ---- contrastive views of a device-built batch (include/b4c.h): crop, mask, reorder, the same-target row ----
 AUG_OPS = {'crop': L.AUG_CROP, 'mask': L.AUG_MASK, 'reorder': L.AUG_REORDER, 'same_target': L.AUG_SAME_TARGET}      # name -> op bit
 AUG_LAYOUTS = (FEAT_CLOZE, FEAT_NEXT_TRAIN)
 
@@ -2337,7 +2337,7 @@ def _augment_args(who, W, layout, holdout, max_len, n_views, view_ops, seed, cro
 def augment_views(items, offsets, win_seq, win_start, win_len, row_win, W, layout, view_ops, seed, n_views=2, holdout=1, max_len=None,
                   crop_ratio=0.6, mask_ratio=0.3, reorder_ratio=0.6, target_index=None, V=0):
     """-> (items_out int64 [n_views, B, W], src_tok int64 [n_views, B, W], n_items, op, target int32 [n_views, B], self_count int32
-    [1]) (b4c_augment_views, include/b4c_aug.h): n_views contrastive views of the batch rows row_win (windows of the device table)
+    [1]) (b4c_augment_views, include/b4c.h): n_views contrastive views of the batch rows row_win (windows of the device table)
     whose item rows cloze_batch_windows (layout FEAT_CLOZE) or next_item_batch in TRAIN mode (FEAT_NEXT_TRAIN, the same holdout)
     built.  Per (row, view) one of view_ops is drawn -- 'crop': a contiguous slice of crop_ratio of the row; 'mask': mask_ratio of
     its positions become [MASK]; 'reorder': a span of reorder_ratio of the row is shuffled; 'same_target' (next-item only): the
@@ -3968,7 +3968,7 @@ class CandidateLossFn(torch.autograd.Function):
 
 
 class InfoNCEFn(torch.autograd.Function):
-    """In-batch contrastive loss (NT-Xent / InfoNCE; include/b4c_nce.h): the mean of nce_fwd's item_loss over the live rows -- rows
+    """In-batch contrastive loss (NT-Xent / InfoNCE; include/b4c.h): the mean of nce_fwd's item_loss over the live rows -- rows
     whose pos names another row of the batch.  apply(z [N, K], pos int32 [N], group int32 [N] or None, temperature, similarity) ->
     scalar.  The count of live rows and gscale = 1 / max(count, 1) are formed on the device: no read-back."""
 

@@ -23,6 +23,8 @@ static float rng_unit(void) { return (float)((rng_next() >> 40) / 16777216.0); }
 
 int main(void) {
     printf("libb4c_hip ABI version %d\n", b4c_abi_version());
+    /* (host only) the long-attention family is a section of the same header: rows * H * dh * 4 bytes */
+    if (b4c_attn_long_bwd_workspace_bytes(1024, 2, 64) != 1024 * 2 * 64 * 4) return 1;
     hipStream_t st;
     CHECK_HIP(hipStreamCreate(&st));
 

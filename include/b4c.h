@@ -55,7 +55,11 @@ extern "C" {
 #define B4C_CE_TF 0    /* clip[1e-7,1-1e-7] -> log -> log-softmax (tf.keras.backend, TF 2.3.1) */
 #define B4C_CE_PLAIN 1 /* -log p_y                                                            */
 
-#define B4C_ABI_VERSION 12   /* what b4c_abi_version() returns; additive entry points (new names, no signature changed) keep it */
+/* What b4c_abi_version() returns.  Additive entry points (new names, no signature changed) keep it.  13: the contrastive loss,
+ * the contrastive views and the long attention were three extension headers with a version and a version getter each
+ * (b4c_*_version); they are sections of this header now and the three getters left the library, so a C caller built against an
+ * extension header no longer links -- a removal, which is what this number reports.  No signature changed from 12. */
+#define B4C_ABI_VERSION 13
 
 int b4c_abi_version(void);
 const char *b4c_last_error(void);
@@ -1169,6 +1173,160 @@ int64_t b4c_gemm_nt_ln_bwd_add_workspace_bytes(int M, int N);
 int b4c_gemm_nt_ln_bwd_add(const void *A, int lda, const void *Bt, int ldb, const void *x, const float *stats, const float *gamma,
                            const void *res, int ld_res, void *dx, float *dgamma, float *dbeta, int M, int N, int K, void *workspace,
                            int64_t workspace_bytes, int dtype, void *stream);
+
+/* ==== the in-batch contrastive loss (additive to ABI 12): NT-Xent / InfoNCE over the rows of a batch; the auxiliary loss of
+ * CL4SRec and DuoRec ============================================================================================================== */
+
+/* No reference counterpart (the reference trains with the Cloze loss alone); the float64 restatement is tests/nce_ref.py, written
+ * from the definition below.
+ *
+ * Definition.  z is [N][ld_z] of T (bf16 or fp32), K columns used; pos int32 [N]; group int32 [N] or NULL.
+ *   Score     s_ij = inv_temp * (zh_i . zh_j), accumulated in fp32.  zh = z by default; with flags & B4C_NCE_COSINE
+ *             zh_i = z_i * rnorm[i], rnorm[i] = 1 / max(||z_i||_2, 1e-12) (fp32, the norm of the stored values).  The scaling
+ *             is applied to the fp32 score, not to the operands: s_ij = inv_temp * (rnorm[i] * rnorm[j]) * (z_i . z_j); for bf16
+ *             the matrix-core operands are the stored values.  b4c_nce_fwd writes rnorm, b4c_nce_bwd reads it; it may be NULL
+ *             without the flag.
+ *   Live rows live(i) iff 0 <= pos[i] < N and pos[i] != i.  Only live rows are queries; every other row has item_loss = 0,
+ *             lse = 0 and a dz contribution from being someone's positive only.
+ *   Keys      key(i, j) iff j != i and at least one of
+ *               j == pos[i];
+ *               live(j) and (group == NULL or group[i] < 0 or group[j] < 0 or group[i] != group[j]).
+ *             (DuoRec: two sequences with the same target item are not each other's negatives.)
+ *   Forward   lse[i] = log sum_{j : key(i, j)} exp(s_ij), a max-shifted log-sum-exp in fp32;
+ *             item_loss[i] = lse[i] - s_{i, pos[i]}.
+ *   Backward  G_ij = [key(i, j)] exp(s_ij - lse[i]) - [j == pos[i]] for live i, else 0;
+ *             dzh_i = gscale[0] * inv_temp * sum_j (G_ij + G_ji) zh_j;
+ *             dz_i = dzh_i without the flag, rnorm[i] * (dzh_i - zh_i (zh_i . dzh_i)) with it.
+ *             dz ([N][ld_dz] of T) is written, not accumulated.  pos need not be an involution: G_ji is evaluated from lse[j],
+ *             pos[j] and group[j].  S is symmetric, so one score tile serves G and its transpose: one sweep of 4 N^2 K flops.
+ *             bf16: the coefficient (G_ij + G_ji) * rnorm[j] (rnorm = 1 without the flag) is rounded to bf16, the operand of the
+ *             second matrix-core product (a 32 x 32 block of scores that holds a -[j == pos[i]] term also adds the product with
+ *             the rounding residual: its coefficients carry 16 bits); the sum over j is fp32 and dz is rounded once when stored.
+ *   Deterministic: no atomics; a workgroup owns a tile of rows and walks the column tiles in ascending order, a row's sums are
+ *             taken in an order that depends on N alone.  Two launches on the same inputs give the same bits.
+ *
+ * Limits: K % 8 == 0, 8 <= K <= 128; 0 <= N < 2^24; z, dz 16-byte aligned, rows included (ld % 8 == 0 for bf16, % 4 for fp32),
+ * ld >= K, and all N * ld elements addressable (the tile loader reads whole 16-byte chunks of a row's pitch).
+ * Checks, in this order and before any pointer is looked at: K, dtype, inv_temp (finite, > 0), flags (B4C_NCE_COSINE is the one
+ * bit), N -- B4C_EINVAL with a message that names the argument; then N == 0 returns B4C_OK; then rnorm missing with the flag, the
+ * other pointers, pitches and alignment.  Nothing is launched or written after a refusal. */
+#define B4C_NCE_COSINE 1u   /* flags bit: cosine similarity (scores scaled by rnorm[i] * rnorm[j]) */
+#define B4C_NCE_MAX_N 16777216   /* N < 2^24 */
+int b4c_nce_fwd(const void *z, int ld_z, int64_t N, int K, int dtype, const int32_t *pos, const int32_t *group,
+                float inv_temp, uint32_t flags, float *rnorm, float *lse, float *item_loss, void *stream);
+int b4c_nce_bwd(const void *z, int ld_z, int64_t N, int K, int dtype, const int32_t *pos, const int32_t *group,
+                float inv_temp, uint32_t flags, const float *rnorm, const float *lse, const float *gscale,
+                void *dz, int ld_dz, void *stream);
+
+/* ==== the contrastive views of a device-built batch (additive to ABI 12): CL4SRec's item crop, item mask and item reorder;
+ * DuoRec's supervised positive, the row of another sequence in front of the same target item =================================== */
+
+/* No reference counterpart (the reference trains with the Cloze loss alone); the integer restatement is tests/augment_ref.py,
+ * written from the definition below.
+ *
+ * Definition.  The data set is b4c_batch_features' CSR pair (items int32 [n_tok], offsets int64 [n_seq + 1]) with the window table
+ * (win_seq, win_start, win_len) and row_win int32 [B] (NULL: row b is window b; a negative entry, or a negative sequence or start
+ * in the table: an empty row).  Row b's window is (g, a, L); o0 = offsets[g], n_g = offsets[g + 1] - o0.
+ *   Source    src = s_g[first .. first + n), s_g = items + o0, by the row rule of b4c_batch_features for `layout`:
+ *               B4C_FEAT_CLOZE       first = a, n = min(L, W): the UNMASKED window (holdout and max_len are not read for it);
+ *               B4C_FEAT_NEXT_TRAIN  the input row of b4c_next_item_batch's TRAIN mode: T = max(n_g - holdout, 0),
+ *                                    first = a > 0 ? a - 1 : 0, n = max(min(a > 0 ? L : L - 1, W, T - first - 1), 0).
+ *             i = o0 + first is the CSR index of the row's first token.
+ *   Random    rand64 = b4c_rand64 (Threefry-2x32, 12 rounds: key, counter).  For view v = 0 .. n_views - 1:
+ *               seed_v = rand64(seed ^ 0xA0761D6478BD642F, v);
+ *               h_op   = rand64(seed_v ^ 0xE7037ED1A0B428DB, i);   h_at = rand64(seed_v ^ 0x8EBC6AF09C88C6E3, i);
+ *               k_p    = rand64(seed_v, (i << 10) | p), the key of position p of the row.
+ *             mulhi(x, m) = the high 64 bits of the 128-bit product x * m (uniform in [0, m)).  (k_p, p) < (k_q, q) is
+ *             lexicographic: ties of the key go to the lower position.  "(int)((float)n * r)" is a float32 product of the float32
+ *             n and r, then truncation.  Ids: out = item + 10, [MASK] = 1, pad = 0.
+ *   A row and a view write items_out[v][b][0 .. W), src_tok[v][b][0 .. W) (the CSR index of the token each output position came
+ *   from), n_out[v][b], op_out[v][b], target_out[v][b]:
+ *   1. Empty  n = 0 (an empty row, an empty window): all pad, n_out = 0, op_out = 0, target_out = -1.
+ *   2. Op     the bits set in ops_mask in ascending order are e_0 .. e_{m-1}; op = e_{mulhi(h_op, m)}; op_out = the op's bit.
+ *   3. CROP   Lc = max(1, (int)((float)n * crop_ratio)), c = mulhi(h_at, n - Lc + 1); out[p] = src[c + p] + 10 for p < Lc;
+ *             n_out = Lc.
+ *   4. MASK   m = min(n, (int)((float)n * mask_ratio)); the positions of the m smallest (k_p, p), p in [0, n), are [MASK], the
+ *             others src[p] + 10; n_out = n.
+ *   5. REORDER  Lr = min(n, (int)((float)n * reorder_ratio)), r0 = mulhi(h_at, n - Lr + 1); for p in the span [r0, r0 + Lr):
+ *             rho(p) = #{q in the span : (k_q, q) < (k_p, p)} and out[r0 + rho(p)] = src[p] + 10; outside the span
+ *             out[p] = src[p] + 10; n_out = n.
+ *   6. SAME_TARGET (B4C_FEAT_NEXT_TRAIN only)  t = i + n is the CSR index of the row's target (inside the training view by the
+ *             row rule), y = items[t].  The index: tgt_first int64 [V + 1], tgt_tok int64 [n_tgt], tgt_seq int32 [n_tgt]; y's
+ *             list is tgt_tok[tgt_first[y] .. tgt_first[y + 1]), CSR indices of tokens that hold y, ascending, cnt entries (y
+ *             outside [0, V): an empty list); tgt_seq[k] is the sequence of token tgt_tok[k].  own = the number of entries of
+ *             the list below t (its lower-bound position), found = (t is in the list), others = cnt - found.
+ *             others = 0: the view is the row's own inputs, out[p] = src[p] + 10, n_out = n, and self_count[0] is incremented
+ *             (DuoRec's fallback).  Otherwise u = mulhi(h_at, others), k = tgt_first[y] + u + (found && u >= own ? 1 : 0),
+ *             j = tgt_tok[k], g' = tgt_seq[k], q = j - offsets[g'] (the items of g' in front of its y);
+ *             n_out = min(q, W, max_len) (max_len <= 0: no cap) and out[p] = s_g'[q - n_out + p] + 10 for p < n_out: the most
+ *             recent n_out items in front of the partner's target.
+ *   7. Every op  out[p] = 0 and src_tok = -1 for n_out <= p < W.  target_out = items[i + n] for B4C_FEAT_NEXT_TRAIN, -1 for
+ *             B4C_FEAT_CLOZE.  src_tok follows the same moves (CROP: i + c + p; REORDER: i + the source position; SAME_TARGET:
+ *             offsets[g'] + q - n_out + p or i + p); a [MASK] position keeps its source token.
+ *   A row is a pure function of (seed, v, the window): not of its place in the batch, nor of B or n_views.
+ *
+ * b4c_augment_views: one 256-thread workgroup per (row, view), grid (B, n_views).  items_out int64 [n_views][B][ld_items];
+ * src_tok int64 [n_views][B][ld_src] or NULL; n_out, op_out int32 [n_views][B]; target_out int32 [n_views][B] or NULL;
+ * self_count int32 [1], set to 0 by the entry before the launch and incremented once per self row (required with
+ * B4C_AUG_SAME_TARGET, else it may be NULL).  Stream-ordered; nothing is read back; neither the rows nor the index are checked
+ * against the data set.
+ * Checks, in this order and before any pointer is looked at -- B4C_EINVAL with a message that names the argument: B and W
+ * (1 .. B4C_MAX_BATCH_WIDTH), layout (one of the three B4C_FEAT_* row layouts), holdout (NEXT_TRAIN: >= 0), ld_items >= W, layout
+ * once more (B4C_FEAT_NEXT_EVAL: views of evaluation rows are not built), n_views (1 .. B4C_AUG_MAX_VIEWS), ops_mask (a non-empty
+ * subset of the four bits), crop_ratio in (0, 1], mask_ratio and reorder_ratio in [0, 1] (a NaN or an infinity is outside),
+ * B4C_AUG_SAME_TARGET with another layout than NEXT_TRAIN, ld_src >= W (src_tok given); then B == 0 returns B4C_OK;
+ * then the index missing with B4C_AUG_SAME_TARGET (tgt_first, tgt_tok, tgt_seq, V > 0, self_count), then the other pointers.  Nothing is launched or written after a refusal.
+ *
+ * b4c_augment_row: the same rule for ONE (row, view) on the host, from the same functions; every pointer is a HOST pointer.
+ * items / offsets: the whole CSR pair (n_seq sequences); (g, a, L): the window, g < 0: an empty row; out int64 [W];
+ * src_tok_out int64 [W]; head_out int32 [4] = {n_out, op, target, self (1: a same-target row that fell back to itself)}. */
+#define B4C_AUG_CROP 1u         /* ops_mask / op_out bits */
+#define B4C_AUG_MASK 2u
+#define B4C_AUG_REORDER 4u
+#define B4C_AUG_SAME_TARGET 8u
+#define B4C_AUG_MAX_VIEWS 4
+int b4c_augment_views(const int32_t *items, const int64_t *offsets, const int32_t *win_seq, const int32_t *win_start,
+                      const int32_t *win_len, const int32_t *row_win, int B, int W, int layout, int holdout, int max_len,
+                      int n_views, uint32_t ops_mask, float crop_ratio, float mask_ratio, float reorder_ratio, uint64_t seed,
+                      const int64_t *tgt_first, const int64_t *tgt_tok, const int32_t *tgt_seq, int V, int64_t *items_out,
+                      int ld_items, int64_t *src_tok, int ld_src, int32_t *n_out, int32_t *op_out, int32_t *target_out,
+                      int32_t *self_count, void *stream);
+int b4c_augment_row(const int32_t *items, const int64_t *offsets, int64_t n_seq, int64_t g, int a, int L, int W, int layout,
+                    int holdout, int max_len, int view, uint32_t ops_mask, float crop_ratio, float mask_ratio,
+                    float reorder_ratio, uint64_t seed, const int64_t *tgt_first, const int64_t *tgt_tok, const int32_t *tgt_seq,
+                    int V, int64_t *out, int64_t *src_tok_out, int32_t *head_out);
+
+/* ==== long-sequence attention (additive to ABI 12): bf16 matrix-core self-attention for sequences longer than the resident
+ * kernels of b4c_attn_fwd_ex / b4c_attn_bwd_ex hold (S <= 512, all K and V of a (sequence, head) in LDS): the keys are streamed == */
+
+/* Arguments, layouts and semantics are exactly those of b4c_attn_fwd_ex / b4c_attn_bwd_ex with dtype = B4C_BF16:
+ *   qkv [rows][ld_qkv] = Q | K | V of H heads of depth dh; key_pad uint8 [rows] (1 = padded key); cu_seqlens NULL: dense, B
+ *   sequences of S rows each; else int32 [B + 1], sequence b owns rows cu_seqlens[b] .. cu_seqlens[b + 1] and S is max_len, an
+ *   upper bound of the longest one.  o [rows][ld_o]; lse, delta fp32 [B][H][S] (delta is scratch of the backward);
+ *   dqkv [rows][ld_dqkv] is written, not accumulated.
+ *   A padded key adds -1e9 to its score (a sequence without a live key: uniform weights over all its keys); flags &
+ *   B4C_ATTN_CAUSAL: key k is visible to query q iff k <= q, the others get exactly zero weight and zero gradient.
+ *   dropout_rate in [0, 1): keep rule b4c_attn_keep(seed, b, h, q, k, H, S, rate), lse is that of the undropped softmax.
+ *   The dK / dV rows of padded keys are exact zeros.
+ * Rounding: P is rounded to bf16 once, in front of P V; o once, when stored; lse is fp32.  Backward: P and dS once each in front
+ *   of their products, dQ once after the fp32 sum over all key blocks (workspace), dK / dV once.
+ * Deterministic: no atomics, no workgroup waits for another; two launches on the same inputs give the same bits.
+ *
+ * Limits: head depth 32 or 64; 1 <= S <= B4C_ATTN_LONG_MAX_S; pitches multiples of 8 elements, rows 16-byte aligned.
+ * b4c_attn_long_bwd needs a workspace of b4c_attn_long_bwd_workspace_bytes(rows, H, dh) = rows * H * dh * 4 bytes, rows = B * S
+ * (dense) or cu_seqlens[B] (packed): the fp32 dQ accumulator.  (-1 for arguments outside the limits.)
+ * Checks, in this order and before any pointer is looked at: flags, dropout_rate, head depth, S, the other shape arguments and
+ * the pitches, workspace_bytes (backward, dense layout: against B * S rows; the packed layout's row count lives on the device and
+ * is the caller's to size for) -- B4C_EINVAL with a message that names the argument; then the pointers.  Nothing is launched or
+ * written after a refusal. */
+#define B4C_ATTN_LONG_MAX_S 2048
+int b4c_attn_long_fwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, void *o, int ld_o,
+                      float *lse, int B, int S, int H, int dh, void *stream, float dropout_rate, uint64_t seed, uint32_t flags);
+int64_t b4c_attn_long_bwd_workspace_bytes(int64_t rows, int H, int dh);
+int b4c_attn_long_bwd(const void *qkv, int ld_qkv, const uint8_t *key_pad, const int32_t *cu_seqlens, const void *o, int ld_o,
+                      const void *d_o, int ld_do, const float *lse, float *delta, void *dqkv, int ld_dqkv, int B, int S, int H,
+                      int dh, void *workspace, int64_t workspace_bytes, void *stream, float dropout_rate, uint64_t seed,
+                      uint32_t flags);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""The streamed attention kernels (ops.attn_long_fwd / attn_long_bwd, include/b4c_attn_long.h) against what the same shapes ran on
+"""The streamed attention kernels (ops.attn_long_fwd / attn_long_bwd, include/b4c.h) against what the same shapes ran on
 before them: the fp32-math row kernels, reached through ops.attn_fwd / attn_bwd with ops.long_attn off (dense only: the packed layout
 was refused past S = 512, so its numbers stand alone).  bf16, H = 2, dh = 64, B * H = 512, S = 1024 and 2048, dense and packed (lengths
 uniform in [S / 2, S], one at S), causal and not, forward and forward + backward.  The two sides alternate inside one process, WINDOWS

@@ -1,4 +1,4 @@
-"""Host restatement of the contrastive views (include/b4c_aug.h), written from the header's definition in numpy and Python
+"""Host restatement of the contrastive views (include/b4c.h), written from the header's definition in numpy and Python
 integers: ops.rand64_host for the random stream, a stable argsort on (k, p) for the ranks, float32 products for the shares.  It does
 not call b4c_augment_row.  Used by test_augment_cpu.py and test_gpu_augment.py."""
 import functools

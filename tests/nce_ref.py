@@ -1,4 +1,4 @@
-"""The in-batch contrastive loss of include/b4c_nce.h restated in numpy from that header's comment, its derived fp32 error bounds, and
+"""The in-batch contrastive loss of include/b4c.h restated in numpy from that header's comment, its derived fp32 error bounds, and
 the committed cases of the GPU tests (shared with the CPU tests: same seeds, same inputs).
 
 restate(...) evaluates the definition -- rnorm, scores, keys, lse, item_loss, the coefficients G, dz -- in float64, or

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import abi_pin
+
 
 def _param(*shape):
     return torch.nn.Parameter(torch.randn(*shape) if shape else torch.randn(10, 8))
@@ -206,7 +208,7 @@ def test_adamw_entry_points_are_exported_and_check_their_arguments():
     for name in ('b4c_adamw_step', 'b4c_adamw_rows'):
         assert name in E and hasattr(L, name)
     assert [s for s in E if not hasattr(L, s)] == []
-    assert L.b4c_abi_version() == 12 == _lib.ABI_VERSION          # additive: no existing signature changed
+    assert L.b4c_abi_version() == abi_pin.ABI_VERSION == _lib.ABI_VERSION          # additive: no existing signature changed
     A = 1 << 20                                                   # a well-aligned, never dereferenced "pointer"
     # dense form: (p, g, m, v, n, lr_t, b1, b2, eps, grad_mul, coef | NULL, decay, blocks, stream)
     assert L.b4c_adamw_step(None, A, A, A, 64, 1e-3, 0.9, 0.999, 1e-9, 1.0, None, 1e-5, A, None) == -1

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_pin
 import attn_dropout_ref as ref
 from attn_dropout_ref import elem_index
 
@@ -71,7 +72,7 @@ def test_recovery_construction_on_the_restatement(S, dh):
 
 def test_abi_version_stays_12(lib):
     from bert4clickpath_amd import _lib
-    assert lib.b4c_abi_version() == 12 and _lib.ABI_VERSION == 12
+    assert lib.b4c_abi_version() == abi_pin.ABI_VERSION and _lib.ABI_VERSION == abi_pin.ABI_VERSION
     for name in ('b4c_attn_keep', 'b4c_attn_fwd_drop', 'b4c_attn_bwd_drop_ws', 'b4c_attn_fwd_varlen_drop', 'b4c_attn_bwd_varlen_drop'):
         assert name in _lib.declared_symbols() and hasattr(lib, name)
     # (dropout_rate, seed) are appended to the lists of the entry points they mirror

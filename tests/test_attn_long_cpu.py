@@ -1,4 +1,4 @@
-"""The extension header include/b4c_attn_long.h, its binding, the argument refusals of its entry points (NULL device pointers: nothing
+"""The long-attention section of include/b4c.h, its binding, the argument refusals of its entry points (NULL device pointers: nothing
 is launched), the workspace arithmetic and the host routing of the streamed attention kernels, without a GPU; and the emulated
 rounding of route 'mfma' (tests/local_bounds.py) on the shapes tests/test_gpu_attn_long.py runs: what the element bounds must accept."""
 import ctypes
@@ -7,6 +7,7 @@ import os
 import pytest
 import torch
 
+import abi_pin
 import local_bounds as lb
 
 V_, I, I64, F, U32, U64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint64
@@ -32,42 +33,33 @@ def ops():
 
 # ---- header and binding -----------------------------------------------------------------------------------------------------------
 def test_header_parses_to_the_declared_table(L):
-    path = os.path.join(os.path.dirname(L.HEADER_PATH), 'b4c_attn_long.h')
-    assert L.LONG_HEADER_PATHS == (path,) and path not in L.EXT_HEADER_PATHS and path not in L.AUG_HEADER_PATHS
-    text = L._header_text(path)
-    table = L.parse_header(text)
-    assert table == {'b4c_attn_long_version': (I, []), 'b4c_attn_long_fwd': (I, FWD), 'b4c_attn_long_bwd_workspace_bytes': (I64, [I64, I, I]),
-                     'b4c_attn_long_bwd': (I, BWD)}
-    assert L.header_constants(text) == {'B4C_ATTN_LONG_VERSION': 1, 'B4C_ATTN_LONG_MAX_S': 2048}
-    assert (L.ATTN_LONG_VERSION, L.ATTN_LONG_MAX_S) == (1, 2048)
-
-
-def test_no_name_is_declared_twice_and_the_other_tables_are_what_they_were(L):
     sig = L.signatures()
-    assert len(sig) == 143 and L.ABI_VERSION == 12
-    ext = L.extension_signatures()
-    aug = L.extension_signatures(header_paths=L.AUG_HEADER_PATHS, main={**sig, **ext})
-    long_ = L.extension_signatures(header_paths=L.LONG_HEADER_PATHS, main={**sig, **ext, **aug})       # what lib() hands the third list's parse
-    assert sorted(ext) == ['b4c_nce_bwd', 'b4c_nce_fwd', 'b4c_nce_version'] and len(aug) == 3 and len(long_) == 4
-    assert len({**sig, **ext, **aug, **long_}) == 143 + 3 + 3 + 4
+    assert sig['b4c_attn_long_fwd'] == (I, FWD) and sig['b4c_attn_long_bwd'] == (I, BWD)
+    assert sig['b4c_attn_long_bwd_workspace_bytes'] == (I64, [I64, I, I])
+    const = L.header_constants(L._header_text(L.HEADER_PATH))
+    assert {k: v for k, v in const.items() if k.startswith('B4C_ATTN_LONG_')} == {'B4C_ATTN_LONG_MAX_S': 2048}
+    assert L.ATTN_LONG_MAX_S == 2048
+
+
+def test_no_name_is_declared_twice_and_one_header_declares_the_family(L):
+    sig = L.signatures()
+    assert len(sig) == abi_pin.ENTRY_POINTS and L.ABI_VERSION == abi_pin.ABI_VERSION
+    assert os.listdir(os.path.dirname(L.HEADER_PATH)) == ['b4c.h']
+    assert {'b4c_attn_long_fwd', 'b4c_attn_long_bwd_workspace_bytes', 'b4c_attn_long_bwd'} <= set(sig)
     with pytest.raises(L.B4CError, match='declares b4c_attn_long_fwd twice'):
-        L.extension_signatures(header_paths=L.LONG_HEADER_PATHS, main={'b4c_attn_long_fwd': long_['b4c_attn_long_fwd']})
+        L.parse_header(L._header_text(L.HEADER_PATH) + '\nint b4c_attn_long_fwd(const void *z, int ld_z);\n')
 
 
-def test_the_binding_checks_the_version_and_the_names(L, monkeypatch, tmp_path):
+def test_the_binding_checks_the_names(L, monkeypatch, tmp_path):
     lib = L.lib()
-    assert lib.b4c_attn_long_version() == L.ATTN_LONG_VERSION == 1
     assert lib.b4c_attn_long_fwd.argtypes == FWD and lib.b4c_attn_long_bwd.argtypes == BWD
     assert lib.b4c_attn_long_bwd_workspace_bytes.restype is I64
     more = tmp_path / 'b4c_more.h'
-    more.write_text('#define B4C_ATTN_LONG_VERSION 1\nint b4c_attn_long_version(void);\nint b4c_attn_long_not_there(int n);\n')
-    monkeypatch.setattr(L, 'LONG_HEADER_PATHS', (str(more),))
-    monkeypatch.setattr(L, '_LONG_VERSIONS', {'b4c_more.h': ('B4C_ATTN_LONG_VERSION', 'b4c_attn_long_version')})
+    with open(L.HEADER_PATH) as f:
+        more.write_text(f.read() + '\nint b4c_attn_long_not_there(int n);\n')
+    monkeypatch.setattr(L, 'HEADER_PATH', str(more))
     monkeypatch.setattr(L, '_lib', None)
     with pytest.raises(L.B4CError, match=r'does not export b4c_attn_long_not_there; rebuild it'):
-        L.lib()
-    monkeypatch.setattr(L, '_CL', dict(L._CL, B4C_ATTN_LONG_VERSION=2))
-    with pytest.raises(L.B4CError, match=r'does not export B4C_ATTN_LONG_VERSION = 2 .*rebuild it'):
         L.lib()
 
 

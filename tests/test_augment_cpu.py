@@ -1,5 +1,5 @@
-"""The extension header include/b4c_aug.h, its binding and the host rule of the contrastive views, without a GPU: the header parses
-to the declared table, the main and the nce tables are what they were, a duplicate name is refused, the library exports the names;
+"""The contrastive-views section of include/b4c.h, its binding and the host rule of the views, without a GPU: the header parses
+to the declared table, include/ holds the one header, a duplicate name is refused, the library exports the names;
 every argument b4c_augment_views refuses is refused with NULL pointers; b4c_augment_row equals the restatement tests/augment_ref.py
 (written from the header's text) on every window of the case data; the structural properties of the ops hold on the restatement;
 DeviceCloze's host token count equals the restatement's.  Everything is integer-exact: no tolerance."""
@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_pin
 import augment_ref as ar
 import next_item_ref as nref
 
@@ -39,62 +40,49 @@ def data():
 
 
 # ---- header and binding -----------------------------------------------------------------------------------------------------------
+NAMES = {'b4c_augment_views', 'b4c_augment_row'}
+
+
 def test_header_parses_to_the_declared_table(L):
-    path = os.path.join(os.path.dirname(L.HEADER_PATH), 'b4c_aug.h')
-    assert L.AUG_HEADER_PATHS == (path,) and path not in L.EXT_HEADER_PATHS
-    text = L._header_text(path)
-    table = L.parse_header(text)
-    assert table == {'b4c_aug_version': (I, []), 'b4c_augment_views': (I, VIEWS), 'b4c_augment_row': (I, ROW)}
-    assert L.extension_signatures(header_paths=L.AUG_HEADER_PATHS) == table
-    const = L.header_constants(text)
-    assert const == {'B4C_AUG_VERSION': 1, 'B4C_AUG_CROP': 1, 'B4C_AUG_MASK': 2, 'B4C_AUG_REORDER': 4, 'B4C_AUG_SAME_TARGET': 8,
-                     'B4C_AUG_MAX_VIEWS': 4}
-    assert (L.AUG_VERSION, L.AUG_CROP, L.AUG_MASK, L.AUG_REORDER, L.AUG_SAME_TARGET) == (1, 1, 2, 4, 8)
-
-
-def test_main_and_nce_tables_are_what_they_were(L):
     sig = L.signatures()
-    assert len(sig) == 143 and L.ABI_VERSION == 12
-    assert sorted(L.extension_signatures()) == ['b4c_nce_bwd', 'b4c_nce_fwd', 'b4c_nce_version']
-    assert len(L.EXT_HEADER_PATHS) == 1 and L.EXT_HEADER_PATHS[0].endswith('b4c_nce.h')
-    aug = set(L.extension_signatures(header_paths=L.AUG_HEADER_PATHS))
-    assert not aug & set(sig) and not aug & set(L.extension_signatures())
+    assert sig['b4c_augment_views'] == (I, VIEWS) and sig['b4c_augment_row'] == (I, ROW)
+    const = L.header_constants(L._header_text(L.HEADER_PATH))
+    assert {k: v for k, v in const.items() if k.startswith('B4C_AUG_')} == {
+        'B4C_AUG_CROP': 1, 'B4C_AUG_MASK': 2, 'B4C_AUG_REORDER': 4, 'B4C_AUG_SAME_TARGET': 8, 'B4C_AUG_MAX_VIEWS': 4}
+    assert (L.AUG_CROP, L.AUG_MASK, L.AUG_REORDER, L.AUG_SAME_TARGET, L.AUG_MAX_VIEWS) == (1, 2, 4, 8, 4)
 
 
-def test_a_duplicate_name_is_refused(L, tmp_path):
-    """against the main table and against the nce table: what lib() hands the second list's parse"""
-    seen = {**L.signatures(), **L.extension_signatures()}
-    for name in ('b4c_abi_version', 'b4c_nce_fwd'):
-        dup = tmp_path / ('dup_%s.h' % name)
-        dup.write_text('#define B4C_AUG_VERSION 1\nint b4c_aug_version(void);\nint %s(void);\n' % name)
-        with pytest.raises(L.B4CError, match=r'declares %s twice' % name):
-            L.extension_signatures(header_paths=[str(dup)], main=seen)
+def test_one_header_declares_the_family(L):
+    sig = L.signatures()
+    assert len(sig) == abi_pin.ENTRY_POINTS and L.ABI_VERSION == abi_pin.ABI_VERSION
+    assert os.listdir(os.path.dirname(L.HEADER_PATH)) == ['b4c.h']
+    assert NAMES <= set(sig)
 
 
-def test_the_library_exports_the_names_and_reports_the_version(L):
-    names = set(L.extension_signatures(header_paths=L.AUG_HEADER_PATHS))
+def test_a_duplicate_name_is_refused(L):
+    with pytest.raises(L.B4CError, match=r'declares b4c_augment_views twice'):
+        L.parse_header(L._header_text(L.HEADER_PATH) + '\nint b4c_augment_views(const void *z, int ld_z);\n')
+
+
+def test_the_library_exports_the_names(L):
     nm = shutil.which('nm')
     if nm:
         out = subprocess.run([nm, '-D', '--defined-only', L.LIB_PATH], capture_output=True, text=True, check=True).stdout
         exported = {line.split()[-1] for line in out.splitlines() if line.split()}
     else:
         lib = ctypes.CDLL(L.LIB_PATH)
-        exported = {n for n in names if hasattr(lib, n)}
-    assert names <= exported, sorted(names - exported)
-    assert L.lib().b4c_aug_version() == L.AUG_VERSION == 1
+        exported = {n for n in NAMES if hasattr(lib, n)}
+    assert NAMES <= exported, sorted(NAMES - exported)
 
 
-def test_a_library_without_the_extension_is_refused(L, monkeypatch, tmp_path):
-    """lib() binds the second list after the nce table with the same refusals: a name the library lacks, a version mismatch"""
+def test_a_library_without_a_declared_name_is_refused(L, monkeypatch, tmp_path):
+    """lib() raises its usual error for a name the .so lacks: here a header that declares one more name than the library has"""
     more = tmp_path / 'b4c_more.h'
-    more.write_text('#define B4C_AUG_VERSION 1\nint b4c_aug_version(void);\nint b4c_augment_not_there(int n);\n')
-    monkeypatch.setattr(L, 'AUG_HEADER_PATHS', (str(more),))
-    monkeypatch.setattr(L, '_AUG_VERSIONS', {'b4c_more.h': ('B4C_AUG_VERSION', 'b4c_aug_version')})
+    with open(L.HEADER_PATH) as f:
+        more.write_text(f.read() + '\nint b4c_augment_not_there(int n);\n')
+    monkeypatch.setattr(L, 'HEADER_PATH', str(more))
     monkeypatch.setattr(L, '_lib', None)
     with pytest.raises(L.B4CError, match=r'does not export b4c_augment_not_there; rebuild it'):
-        L.lib()
-    monkeypatch.setattr(L, '_CA', dict(L._CA, B4C_AUG_VERSION=2))
-    with pytest.raises(L.B4CError, match=r'does not export B4C_AUG_VERSION = 2 .*rebuild it'):
         L.lib()
 
 

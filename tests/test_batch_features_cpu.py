@@ -4,6 +4,7 @@ tests/batch_features_ref.py): the entry points' declarations and their binding, 
 import numpy as np
 import pytest
 
+import abi_pin
 import batch_features_ref as ref
 
 A = 1 << 20                                                       # a well-aligned, never dereferenced "pointer"
@@ -30,7 +31,7 @@ def test_header_declares_the_entry_points_and_they_are_bound():
     assert (ops.FEAT_EVENT, ops.FEAT_ITEM, ops.FEAT_MASKED, ops.FEAT_KEPT) == (0, 1, 0, 1)
     assert (ops.FEAT_CLOZE, ops.FEAT_NEXT_TRAIN, ops.FEAT_NEXT_EVAL) == (0, 1, 2)
     assert ops.FEAT_KINDS == ref.KINDS and ops.FEAT_ON_MASK == ref.ON_MASK
-    assert _lib.ABI_VERSION == 12 and lib.b4c_abi_version() == 12 and _lib.MAX_FEATURES == 4
+    assert _lib.ABI_VERSION == abi_pin.ABI_VERSION and lib.b4c_abi_version() == abi_pin.ABI_VERSION and _lib.MAX_FEATURES == 4
 
 
 def _launch(L, items=A, offsets=A, win_seq=A, win_start=A, win_len=A, row_win=A, B=4, W=8, layout=0, holdout=1, max_len=8, V=500, items_in=A,

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_pin
 import candidate_loss_ref as cl
 
 A = 1 << 20                                                       # a well-aligned, never dereferenced "pointer"
@@ -51,8 +52,8 @@ def test_header_declares_the_entry_points_and_they_are_bound():
 def test_the_pinned_lists_still_hold():
     from bert4clickpath_amd import _lib
     lib = _lib.lib()
-    assert len(_lib.signatures()) == 143 == len(_lib.declared_symbols())
-    assert _lib.ABI_VERSION == 12 and lib.b4c_abi_version() == 12
+    assert len(_lib.signatures()) == abi_pin.ENTRY_POINTS == len(_lib.declared_symbols())
+    assert _lib.ABI_VERSION == abi_pin.ABI_VERSION and lib.b4c_abi_version() == abi_pin.ABI_VERSION
 
 
 def _fwd(L, h=A, ld_h=128, table=A, ld_t=128, rows=1000, row_off=10, bias=A, cand=A, ld_c=8, R=4, C=8, V=500, K=128, dtype=1, kind=0,

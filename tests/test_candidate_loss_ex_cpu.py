@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_pin
 import candidate_loss_ex_ref as cx
 import candidate_loss_ref as cl
 
@@ -37,7 +38,7 @@ def test_header_declares_the_entry_point_and_it_is_bound():
     assert (_lib.CANDX_BCE, _lib.CANDX_SOFTMAX, _lib.CANDX_BPR, _lib.CANDX_KINDS, _lib.CANDX_CORR_TARGET) == (0, 1, 2, 3, 1)
     assert ops.CANDX_LOSS_KINDS == {'bce': 0, 'softmax': 1, 'bpr': 2}
     assert ops.CAND_LOSS_KINDS == {'bce': 0, 'softmax': 1}       # the first feature's surface is as it was
-    assert _lib.ABI_VERSION == 12 and lib.b4c_abi_version() == 12
+    assert _lib.ABI_VERSION == abi_pin.ABI_VERSION and lib.b4c_abi_version() == abi_pin.ABI_VERSION
     cc = shutil.which('cc') or shutil.which('gcc') or shutil.which('clang')
     if cc:              # what a C compiler sees of b4c.h alone
         pre = subprocess.run([cc, '-E', '-dD', _lib.HEADER_PATH], capture_output=True, text=True, check=True).stdout

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_pin
 import attn_dropout_ref as ad
 import causal_ref as cr
 
@@ -75,10 +76,10 @@ def test_header_declares_the_entry_points_and_the_abi_stays_12():
     import subprocess
     from bert4clickpath_amd import _lib, ops
     lib = _lib.lib()
-    assert lib.b4c_abi_version() == 12 and _lib.ABI_VERSION == 12
+    assert lib.b4c_abi_version() == abi_pin.ABI_VERSION and _lib.ABI_VERSION == abi_pin.ABI_VERSION
     new = ('b4c_attn_fwd_ex', 'b4c_attn_bwd_ex', 'b4c_attn_weights_ex')
     sig = _lib.signatures()
-    assert set(sig) == set(_lib.declared_symbols()) and len(sig) == 143
+    assert set(sig) == set(_lib.declared_symbols()) and len(sig) == abi_pin.ENTRY_POINTS
     assert {n for n in sig if re.fullmatch(r'b4c_attn_(?!mq_)\w+_ex', n)} == set(new)
     for name in new:
         assert hasattr(lib, name) and list(getattr(lib, name).argtypes) == sig[name][1], name

@@ -1,11 +1,12 @@
 """Host side of the device-built Cloze batches (no GPU): the header declares the two entry points and the library exports
-them at ABI 12, the masking rule on the host (b4c_cloze_choose -- the kernel's own __host__ __device__ rule) equals its numpy
+them at the pinned ABI version, the masking rule on the host (b4c_cloze_choose -- the kernel's own __host__ __device__ rule) equals its numpy
 restatement (tests/cloze_batch_ref.py), the draw is uniform within 4 sigma, argument errors are refused before any launch, and
 DeviceCloze's host arithmetic: token counts, the epoch permutation and its rank slices, ValueErrors."""
 import numpy as np
 import pytest
 import torch
 
+import abi_pin
 import cloze_batch_ref as ref
 
 SEEDS = (0, 1234, 2 ** 63 + 12345)
@@ -20,7 +21,7 @@ def test_header_declares_and_library_exports_both_entry_points_at_abi_12():
     for name in ('b4c_cloze_batch', 'b4c_cloze_choose'):
         assert name in sig and hasattr(L, name)
     assert len(sig['b4c_cloze_batch'][1]) == 16 and len(sig['b4c_cloze_choose'][1]) == 5
-    assert _lib.ABI_VERSION == 12 and L.b4c_abi_version() == 12
+    assert _lib.ABI_VERSION == abi_pin.ABI_VERSION and L.b4c_abi_version() == abi_pin.ABI_VERSION
 
 
 def test_the_restatements_n_masked_equals_the_pipelines():

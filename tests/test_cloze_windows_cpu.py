@@ -1,11 +1,12 @@
 """Host side of the paper's data protocol in DeviceCloze (no GPU): the vectorised window table against the loop of
 tests/cloze_window_ref.py (count formula, coverage, no window reaches a held-out item), the windowed masking rule on the host
 (b4c_cloze_choose_window) against b4c_cloze_choose and the restatement, the last-only draw and its rate, the data-parallel
-slices over windows, the defaults, the argument errors, and the new symbols at ABI 12."""
+slices over windows, the defaults, the argument errors, and the new symbols at the pinned ABI version."""
 import numpy as np
 import pytest
 import torch
 
+import abi_pin
 import cloze_window_ref as ref
 
 WS = (1, 4, 7, 50)
@@ -31,7 +32,7 @@ def test_the_new_symbols_are_declared_and_exported_at_abi_12():
         assert name in sig and name in _lib.declared_symbols() and hasattr(L, name)
         assert len(sig[name][1]) == n_args
     assert len(sig['b4c_cloze_batch'][1]) == 16 and len(sig['b4c_cloze_choose'][1]) == 5      # the old lists are as they were
-    assert _lib.ABI_VERSION == 12 and L.b4c_abi_version() == 12
+    assert _lib.ABI_VERSION == abi_pin.ABI_VERSION and L.b4c_abi_version() == abi_pin.ABI_VERSION
 
 
 @pytest.mark.parametrize('holdout', HOLDOUTS)

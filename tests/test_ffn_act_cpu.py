@@ -1,10 +1,12 @@
-"""Host side of the fused GELU feed-forward kernels (no GPU): the two entry points in the header and the library at ABI 12, the
+"""Host side of the fused GELU feed-forward kernels (no GPU): the two entry points in the header and the library at the pinned ABI version, the
 switch and what it does to the vocabulary head's sweep, and the argument checks that refuse a call before any launch."""
 import subprocess
 import sys
 import os
 
 import torch
+
+import abi_pin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A = 1 << 20                                                       # a well-aligned, never dereferenced "pointer"
@@ -20,8 +22,8 @@ def test_the_entry_points_are_declared_and_exported_at_abi_12():
     # the ReLU pair's lists plus act and U, ldu; the old lists are as they were
     assert len(sig['b4c_ffn_fwd'][1]) == 22 and len(sig['b4c_ffn_bwd'][1]) == 30
     assert [s for s in _lib.declared_symbols() if not hasattr(L, s)] == []
-    assert len(_lib.signatures()) == 143 == len(_lib.declared_symbols())
-    assert _lib.ABI_VERSION == 12 and L.b4c_abi_version() == 12      # additive: no existing signature changed
+    assert len(_lib.signatures()) == abi_pin.ENTRY_POINTS == len(_lib.declared_symbols())
+    assert _lib.ABI_VERSION == abi_pin.ABI_VERSION and L.b4c_abi_version() == abi_pin.ABI_VERSION      # additive: no existing signature changed
 
 
 def test_the_switch_is_off_by_default():

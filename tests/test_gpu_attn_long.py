@@ -1,4 +1,4 @@
-"""The streamed bf16 attention kernels of include/b4c_attn_long.h (csrc/attn_long.hip: the forward with 256 queries per workgroup and
+"""The streamed bf16 attention kernels of include/b4c.h (csrc/attn_long.hip: the forward with 256 queries per workgroup and
 the keys in double-buffered blocks of 128; the backward as attn_bwd_mfma_kernel's walk over up to 8 key blocks of 256, whose middle
 mode -- dq_acc += partial -- runs here for the first time), called through ops.attn_long_fwd / ops.attn_long_bwd.
 

@@ -1,4 +1,4 @@
-"""Contrastive views built on the device (include/b4c_aug.h; NO REFERENCE ORACLE: an extension -- the restatement is
+"""Contrastive views built on the device (include/b4c.h; NO REFERENCE ORACLE: an extension -- the restatement is
 tests/augment_ref.py, written from the header's text): every output of the kernel bit for bit on the case list of
 test_augment_cpu.py, the smallest shapes where it can still go wrong, purity, DeviceCloze.views' host count and features, and
 model.contrastive_loss with a device view on the padding-free layout.  Everything about the views is integer-exact: no tolerance

@@ -1,5 +1,5 @@
 """The in-batch contrastive loss on the device (NO REFERENCE ORACLE: an extension -- the float64 restatement and the derived bounds
-are tests/nce_ref.py, written from the comment of include/b4c_nce.h): both kernels (the bf16 matrix-core sweep, the fp32 row kernel)
+are tests/nce_ref.py, written from the comment of include/b4c.h): both kernels (the bf16 matrix-core sweep, the fp32 row kernel)
 on the committed cases, element by element; two launches bit for bit; a permutation of the rows; refused arguments that write
 nothing; the autograd block against torch autograd over a dense float64 evaluation.
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_pin
 from oracle import numpy_ref as nr
 
 
@@ -18,16 +19,17 @@ def test_library_exports_every_declared_symbol():
     L = ctypes.CDLL(_lib.LIB_PATH)          # loads without a GPU: no device call at load time
     for n in names:
         assert hasattr(L, n), 'libb4c_hip.so does not export %s' % n
-    assert _lib.lib().b4c_abi_version() == _lib.ABI_VERSION == 12
+    assert _lib.lib().b4c_abi_version() == _lib.ABI_VERSION == abi_pin.ABI_VERSION
 
 
 def test_every_declared_entry_point_is_an_export_of_the_built_library():
-    """the dynamic symbol table of the file on disk, read without loading it: all of the one header's 143 names are defined there"""
+    """the dynamic symbol table of the file on disk, read without loading it: all of the one header's names are defined there"""
+    import re
     import shutil
     import subprocess
     from bert4clickpath_amd import _lib
     declared = set(_lib.signatures())
-    assert len(declared) == 143 == len(_lib.declared_symbols()) and _lib.ABI_VERSION == 12
+    assert len(declared) == abi_pin.ENTRY_POINTS == len(_lib.declared_symbols()) and _lib.ABI_VERSION == abi_pin.ABI_VERSION
     assert all(n.startswith('b4c_') for n in declared)
     nm = shutil.which('nm')
     if nm:
@@ -37,6 +39,7 @@ def test_every_declared_entry_point_is_an_export_of_the_built_library():
         L = ctypes.CDLL(_lib.LIB_PATH)
         exported = {n for n in declared if hasattr(L, n)}
     assert declared <= exported, sorted(declared - exported)
+    assert [n for n in exported if re.fullmatch(r'b4c_\w*_version', n)] == ['b4c_abi_version']      # one header, one version
 
 
 def test_a_name_declared_twice_is_refused():
@@ -95,7 +98,7 @@ def test_binding_is_derived_from_the_header(tmp_path):
         assert getattr(_lib, name) == int(defines['B4C_' + name]), name
     assert (_lib.F32, _lib.BF16, _lib.ACT_NONE, _lib.ACT_RELU, _lib.CE_TF, _lib.CE_PLAIN) == (0, 1, 0, 1, 0, 1)
     assert (_lib.MAX_FEATURES, _lib.MAX_TOPK, _lib.MAX_EXCL, _lib.MAX_CAND, _lib.GRAD_CHUNK, _lib.GRAD_GROUP) == (4, 16, 1024, 1024, 1024, 4096)
-    assert L.b4c_abi_version() == _lib.ABI_VERSION == int(defines['B4C_ABI_VERSION']) == 12
+    assert L.b4c_abi_version() == _lib.ABI_VERSION == int(defines['B4C_ABI_VERSION']) == abi_pin.ABI_VERSION
 
 
 def test_keep_mask_hash_host_vs_library():

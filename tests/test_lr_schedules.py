@@ -6,6 +6,8 @@ import math
 import pytest
 import torch
 
+import abi_pin
+
 REL = 1e-12          # float64 host arithmetic against hand-computed float64 values
 
 
@@ -118,7 +120,7 @@ def test_new_entry_points_check_their_arguments_without_a_gpu():
     E = _lib.declared_symbols()
     for name in ('b4c_grad_sumsq', 'b4c_grad_sumsq_rows', 'b4c_grad_clip_coef', 'b4c_adam_step_clipped', 'b4c_adam_rows_clipped'):
         assert name in E
-    assert L.b4c_abi_version() == 12                      # additive: no existing signature changed
+    assert L.b4c_abi_version() == abi_pin.ABI_VERSION                      # additive: no existing signature changed
     A = 1 << 20                                           # a well-aligned, never dereferenced "pointer"
     # null pointers
     assert L.b4c_grad_sumsq(None, 4096, 0, 4096, A, None) == -1 and b'grad_sumsq' in L.b4c_last_error()

@@ -4,6 +4,8 @@ the masked-query block, and the two entry points in the header."""
 import pytest
 import torch
 
+import abi_pin
+
 
 def _encoder(attn_rate):
     from bert4clickpath_amd.clickstream_transformer import transformer as T
@@ -105,7 +107,7 @@ def test_rows_at_rate_zero_is_unchanged(monkeypatch, switch, attn_rate, training
 
 def test_header_declares_the_entry_points_and_the_abi_stays_12():
     from bert4clickpath_amd import _lib
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == abi_pin.ABI_VERSION
     sig = _lib.signatures()
     c = _lib.ctypes
     for new, old in (('b4c_attn_mq_fwd_drop', 'b4c_attn_mq_fwd'), ('b4c_attn_mq_bwd_drop', 'b4c_attn_mq_bwd')):
@@ -119,7 +121,7 @@ def test_header_declares_the_entry_points_and_the_abi_stays_12():
 def test_library_exports_the_entry_points():
     from bert4clickpath_amd import _lib
     lib = _lib.lib()
-    assert lib.b4c_abi_version() == 12
+    assert lib.b4c_abi_version() == abi_pin.ABI_VERSION
     assert hasattr(lib, 'b4c_attn_mq_fwd_drop') and hasattr(lib, 'b4c_attn_mq_bwd_drop')
 
 

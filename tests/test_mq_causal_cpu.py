@@ -8,6 +8,8 @@ import sys
 import pytest
 import torch
 
+import abi_pin
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -24,14 +26,14 @@ def test_header_declares_the_drop_signatures_plus_flags():
 
 def test_pinned_counts_and_abi_version_stay():
     from bert4clickpath_amd import _lib
-    assert _lib.ABI_VERSION == 12
-    assert len(_lib.signatures()) == 143 == len(_lib.declared_symbols())          # the README's entry-point count
+    assert _lib.ABI_VERSION == abi_pin.ABI_VERSION
+    assert len(_lib.signatures()) == abi_pin.ENTRY_POINTS == len(_lib.declared_symbols())          # the README's entry-point count
 
 
 def test_library_exports_the_entry_points():
     from bert4clickpath_amd import _lib
     lib, sig = _lib.lib(), _lib.signatures()
-    assert lib.b4c_abi_version() == 12
+    assert lib.b4c_abi_version() == abi_pin.ABI_VERSION
     for name in ('b4c_attn_mq_fwd_ex', 'b4c_attn_mq_bwd_ex'):
         assert hasattr(lib, name) and list(getattr(lib, name).argtypes) == sig[name][1]
 

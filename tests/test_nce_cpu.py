@@ -1,8 +1,8 @@
-"""The extension header include/b4c_nce.h and its binding, without a GPU: the header parses with the main header's grammar and says
-what the issue's lists say; a name in both headers is refused; the built library exports the three names; the main table is still
-b4c.h alone; every argument the entry points refuse is refused with NULL pointers (the checks come before any pointer is looked
-at); N == 0 is B4C_OK.  And the restatement tests/nce_ref.py: its float32 mode against float64 in units of the derived bound (the
-number the GPU gate is built from), and the exact zeros of its bound."""
+"""The contrastive-loss section of include/b4c.h and its binding, without a GPU: the header says what the issue's lists say; a
+name declared twice is refused; the built library exports the two names; include/ holds the one header; every argument the entry
+points refuse is refused with NULL pointers (the checks come before any pointer is looked at); N == 0 is B4C_OK.  And the
+restatement tests/nce_ref.py: its float32 mode against float64 in units of the derived bound (the number the GPU gate is built
+from), and the exact zeros of its bound."""
 import ctypes
 import os
 import shutil
@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_pin
 import nce_ref as nr
 
 V, I, I64, F, U32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint32
@@ -24,62 +25,48 @@ def L():
     return _lib
 
 
-def test_extension_header_parses_and_matches_the_declared_lists(L):
-    path = os.path.join(os.path.dirname(L.HEADER_PATH), 'b4c_nce.h')
-    assert path in L.EXT_HEADER_PATHS
-    text = L._header_text(path)
-    table = L.parse_header(text)
-    assert table == {'b4c_nce_version': (I, []), 'b4c_nce_fwd': (I, FWD), 'b4c_nce_bwd': (I, BWD)}
-    assert L.extension_signatures() == table
-    const = L.header_constants(text)
-    assert const['B4C_NCE_VERSION'] == 1 == L.NCE_VERSION and const['B4C_NCE_COSINE'] == 1 == L.NCE_COSINE
+NAMES = {'b4c_nce_fwd', 'b4c_nce_bwd'}
 
 
-def test_main_table_is_still_the_main_header_alone(L):
+def test_header_parses_and_matches_the_declared_lists(L):
     sig = L.signatures()
-    assert len(sig) == 143 and L.ABI_VERSION == 12
-    assert not any(n.startswith('b4c_nce') for n in sig)
+    assert sig['b4c_nce_fwd'] == (I, FWD) and sig['b4c_nce_bwd'] == (I, BWD)
+    const = L.header_constants(L._header_text(L.HEADER_PATH))
+    assert const['B4C_NCE_COSINE'] == 1 == L.NCE_COSINE and const['B4C_NCE_MAX_N'] == 1 << 24 == L.NCE_MAX_N
+
+
+def test_one_header_declares_the_family(L):
+    sig = L.signatures()
+    assert len(sig) == abi_pin.ENTRY_POINTS and L.ABI_VERSION == abi_pin.ABI_VERSION
+    assert os.listdir(os.path.dirname(L.HEADER_PATH)) == ['b4c.h']
+    assert NAMES <= set(sig)
     assert L.declared_symbols() == sorted(sig)
-    assert not set(sig) & set(L.extension_signatures())
 
 
-def test_a_name_declared_in_both_headers_is_refused(L, tmp_path):
-    dup = tmp_path / 'b4c_dup.h'
-    dup.write_text('/* an extension that re-declares a main entry point */\n#define B4C_DUP_VERSION 1\n'
-                   'int b4c_dup_version(void);\nint b4c_abi_version(void);\n')
-    with pytest.raises(L.B4CError, match=r'declares b4c_abi_version twice'):
-        L.extension_signatures([str(dup)])
-    both = tmp_path / 'b4c_nce_again.h'
-    both.write_text('int b4c_nce_fwd(const void *z, int ld_z);\n')
+def test_a_name_declared_twice_is_refused(L):
     with pytest.raises(L.B4CError, match=r'declares b4c_nce_fwd twice'):
-        L.extension_signatures(list(L.EXT_HEADER_PATHS) + [str(both)])
+        L.parse_header(L._header_text(L.HEADER_PATH) + '\nint b4c_nce_fwd(const void *z, int ld_z);\n')
 
 
-def test_the_built_library_exports_the_extension(L):
-    names = set(L.extension_signatures())
+def test_the_built_library_exports_the_family(L):
     nm = shutil.which('nm')
     if nm:
         out = subprocess.run([nm, '-D', '--defined-only', L.LIB_PATH], capture_output=True, text=True, check=True).stdout
         exported = {line.split()[-1] for line in out.splitlines() if line.split()}
     else:
         lib = ctypes.CDLL(L.LIB_PATH)
-        exported = {n for n in names if hasattr(lib, n)}
-    assert names <= exported, sorted(names - exported)
-    assert L.lib().b4c_nce_version() == L.NCE_VERSION
+        exported = {n for n in NAMES if hasattr(lib, n)}
+    assert NAMES <= exported, sorted(NAMES - exported)
 
 
-def test_a_library_without_the_extension_is_refused(L, tmp_path, monkeypatch):
-    """lib() binds the extension table after the main one and raises its usual error for a name the .so lacks: here a header that
-    declares one more name than the library has"""
+def test_a_library_without_a_declared_name_is_refused(L, tmp_path, monkeypatch):
+    """lib() raises its usual error for a name the .so lacks: here a header that declares one more name than the library has"""
     more = tmp_path / 'b4c_more.h'
-    more.write_text('#define B4C_NCE_VERSION 1\nint b4c_nce_version(void);\nint b4c_nce_not_there(int n);\n')
-    monkeypatch.setattr(L, 'EXT_HEADER_PATHS', (str(more),))
-    monkeypatch.setattr(L, '_EXT_VERSIONS', {'b4c_more.h': ('B4C_NCE_VERSION', 'b4c_nce_version')})
+    with open(L.HEADER_PATH) as f:
+        more.write_text(f.read() + '\nint b4c_nce_not_there(int n);\n')
+    monkeypatch.setattr(L, 'HEADER_PATH', str(more))
     monkeypatch.setattr(L, '_lib', None)
     with pytest.raises(L.B4CError, match=r'does not export b4c_nce_not_there; rebuild it'):
-        L.lib()
-    monkeypatch.setattr(L, '_CX', dict(L._CX, B4C_NCE_VERSION=2))
-    with pytest.raises(L.B4CError, match=r'does not export B4C_NCE_VERSION = 2 .*rebuild it'):
         L.lib()
 
 

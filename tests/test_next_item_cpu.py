@@ -4,6 +4,7 @@ restatement, and DeviceCloze's host side."""
 import numpy as np
 import pytest
 
+import abi_pin
 import next_item_ref as ref
 
 A = 1 << 20                                                       # a well-aligned, never dereferenced "pointer"
@@ -29,7 +30,7 @@ def test_header_declares_the_entry_points_and_they_are_bound():
         assert declared[name] == (c.c_int, lists[name]), name
         assert hasattr(lib, name) and list(getattr(lib, name).argtypes) == lists[name] and getattr(lib, name).restype is c.c_int
     assert (ops.NEXT_TRAIN, ops.NEXT_EVAL) == (0, 1) and ops.NEXT_EXCLUDE == {None: 0, 'history': 1}
-    assert _lib.ABI_VERSION == 12 and lib.b4c_abi_version() == 12
+    assert _lib.ABI_VERSION == abi_pin.ABI_VERSION and lib.b4c_abi_version() == abi_pin.ABI_VERSION
 
 
 def _launch(L, items=A, offsets=A, win_seq=A, win_start=A, win_len=A, row_win=A, row_off=A, B=4, W=8, mode=0, holdout=1, max_len=8, V=500,

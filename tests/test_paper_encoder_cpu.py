@@ -4,6 +4,8 @@ header and its binding, constructor validation and get_config() rules of `ffn_ac
 import pytest
 import torch
 
+import abi_pin
+
 DEFAULT_KEYS = [
     'head.intermediate_layers.0.kernel', 'head.intermediate_layers.0.bias', 'head.output_layer.kernel', 'head.output_layer.bias',
     'transformer.encoder.enc_layers.0.mha.wq.kernel', 'transformer.encoder.enc_layers.0.mha.wq.bias',
@@ -29,7 +31,7 @@ def test_header_constants_abi_and_entry_points():
     consts = L.header_constants(L._header_text(L.HEADER_PATH))
     assert consts['B4C_ACT_GELU'] == 2 and consts['B4C_ACT_GELU_TANH'] == 3
     assert (L.ACT_NONE, L.ACT_RELU, L.ACT_GELU, L.ACT_GELU_TANH) == (0, 1, 2, 3)
-    assert L.ABI_VERSION == 12
+    assert L.ABI_VERSION == abi_pin.ABI_VERSION
     names = L.declared_symbols()
     for n in ('b4c_gemm_nt_act', 'b4c_pos_table_bwd', 'b4c_pos_table_bwd_workspace_bytes'):
         assert n in names

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_pin
 import paper_model_ref as pm
 from test_paper_encoder_cpu import DEFAULT_KEYS
 
@@ -148,7 +149,7 @@ def test_state_dict_names_and_parameters():
 def test_header_declares_the_entry_points_and_the_binding_parses_them():
     import ctypes
     from bert4clickpath_amd import _lib as L
-    assert L.ABI_VERSION == 12
+    assert L.ABI_VERSION == abi_pin.ABI_VERSION
     sig = L.signatures()
     new = ('b4c_embed_ln_fwd', 'b4c_embed_ln_bwd', 'b4c_embed_ln_bwd_workspace_bytes', 'b4c_layernorm_fwd', 'b4c_layernorm_bwd',
            'b4c_layernorm_bwd_workspace_bytes')

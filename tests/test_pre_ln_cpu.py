@@ -8,6 +8,7 @@ import os
 import pytest
 import torch
 
+import abi_pin
 import pre_ln_ref as plr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -119,7 +120,7 @@ def test_header_declares_the_entry_points_and_the_counts_hold():
     assert sig['b4c_gemm_nt_ln_bwd_add'] == (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i64, i32, vp])
     assert sig['b4c_gemm_nt_ln_bwd_add_workspace_bytes'] == (i64, [i32, i32])
     # the whole ABI, and its version
-    assert len(sig) == 143 == len(_lib.declared_symbols()) and _lib.ABI_VERSION == 12
+    assert len(sig) == abi_pin.ENTRY_POINTS == len(_lib.declared_symbols()) and _lib.ABI_VERSION == abi_pin.ABI_VERSION
     with open(os.path.join(ROOT, 'bert4clickpath_amd', 'csrc', 'Makefile')) as f:
         assert 'pre_ln.hip' in f.read()
     lib = _lib.lib()
@@ -130,7 +131,7 @@ def test_header_declares_the_entry_points_and_the_counts_hold():
 def test_library_exports_and_binds_the_entry_points():
     from bert4clickpath_amd import _lib
     lib = _lib.lib()
-    assert lib.b4c_abi_version() == 12
+    assert lib.b4c_abi_version() == abi_pin.ABI_VERSION
     assert lib.b4c_layernorm_bwd_add.argtypes == _lib.signatures()['b4c_layernorm_bwd_add'][1]
     assert lib.b4c_layernorm_bwd_add_workspace_bytes(100, 128) == lib.b4c_layernorm_bwd_workspace_bytes(100, 128) > 0
     assert lib.b4c_layernorm_bwd_add_workspace_bytes(0, 128) == 0
